@@ -3,6 +3,13 @@
 threshold+segment stage and the CPU oracle timed beside it.
 
     python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py ... --full                             (also the measurements beside the headline, see below)
+    python bench.py ... --dump-outputs DIR                 (what the last timed step returned, as DIR/<name>.npy)
+
+A plain run sets up, warms up, times the K steps and prints one JSON line: frames/s, ms_per_step, the stage split of the
+last step and the roofline figure of threshold+segment taken from the timed steps' own events.  --full adds what takes runs
+of its own: the device-to-device copy ceiling, the clusters-stage bandwidth line, the `also` runs (quad_decimate = 2, low-noise
+frames, BASELINE configs 3 and 5), the collective alone (N > 1) and the CPU oracle baseline.
 
 A step = one pass of the whole path (threshold -> segment -> clusters -> quad fit -> decode -> glue -> SQPnP -> 64-byte pose
 records) over one batch of synthetic frames that is already resident in HBM.  Workload at every N: BASELINE.json
@@ -143,6 +150,16 @@ def cpu_baseline(frames, gyro, task, cfg, budget_s=10.0):
                       f"Rust path cannot be built here), detect+pose, POSIX threads over frames (oracle/bench_threads.c); " + "; ".join(sample)}
 
 
+def dump_outputs(path, recs, valid):
+    """The last timed step's results as DIR/<name>.npy, float64: one file per field of the 64-byte records (records_<field>,
+    one row per gathered record; `reserved` is [rows, 6]) and `valid` (this rank's per-frame flags)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {f"records_{k}": recs[k] for k in recs.dtype.names}
+    arrays["valid"] = valid
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def visible_gpus():
     """GPUs of this host counted WITHOUT touching HIP (the parent of the ranks must not initialise the GPU before it starts
     them): KFD topology nodes that have SIMDs (CPU nodes have simd_count 0), narrowed by ROCR/HIP_VISIBLE_DEVICES when set;
@@ -197,8 +214,12 @@ def main():
     ap.add_argument("--noise", type=int, default=3)
     ap.add_argument("--decimate", type=int, default=1)
     ap.add_argument("--unique", type=int, default=0, help="distinct frames rendered per stream (0 = every frame of the batch is distinct)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the two extra measurements reported under \"also\"")
+    ap.add_argument("--full", action="store_true", help="also the measurements beside the headline (copy ceiling, gradient, \"also\", "
+                                                         "collective timing, CPU baseline); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the records and valid flags of the last timed step as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the gradient line and the measurements under \"also\"")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -288,9 +309,18 @@ def main():
         tdist.all_reduce(tmax, op=tdist.ReduceOp.MAX)
     dt = float(tmax.item())
 
+    # what the last timed step handed its caller (the gathered records, this rank's valid flags), taken before anything below
+    # reuses d_rec / d_valid
+    recs = valid = None
+    if rank == 0:
+        recs = dist.records_to_numpy(gathered)
+        valid = d_valid.cpu().numpy()
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, recs, valid)
+
     # the collective alone, after the timed region: enqueue + completion of one gather of this batch's records, wall clock
     gather_us = None
-    if comm is not None:
+    if comm is not None and args.full:
         comm.sync()
         ts = []
         for _ in range(20):
@@ -302,22 +332,23 @@ def main():
                      "what": "ck_gather_poses(sync=0) + ck_comm_sync, host wall clock, 20 repeats after the timed region"}
     if rank == 0:
         stage = task.detector.stage_ms()
-        recs = dist.records_to_numpy(gathered)
         valid_frac = float(np.count_nonzero(recs["tag_count"] > 0)) / len(recs)
         ms_thr = float(np.mean(thr_ms))
         achieved = ALG_BYTES_PER_PX * w * h * n / (ms_thr * 1e-3) / 1e9
-        # attainable ceiling next to the spec peak: a 1 GiB device-to-device copy, read + write bytes
-        src = torch.empty(1 << 30, dtype=torch.uint8, device=dev)
-        dst = torch.empty_like(src)
-        dst.copy_(src)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(5):
+        copy_gbps = None
+        if args.full:
+            # attainable ceiling next to the spec peak: a 1 GiB device-to-device copy, read + write bytes
+            src = torch.empty(1 << 30, dtype=torch.uint8, device=dev)
+            dst = torch.empty_like(src)
             dst.copy_(src)
-        e1.record()
-        torch.cuda.synchronize()
-        copy_gbps = 5 * 2 * (1 << 30) / (e0.elapsed_time(e1) * 1e-3) / 1e9
-        del src, dst
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(5):
+                dst.copy_(src)
+            e1.record()
+            torch.cuda.synchronize()
+            copy_gbps = 5 * 2 * (1 << 30) / (e0.elapsed_time(e1) * 1e-3) / 1e9
+            del src, dst
         # HBM bytes per launch come from rocprofv3 PMC passes (FETCH_SIZE / WRITE_SIZE in separate runs of this same command:
         # tools/collect_profiles.sh), which cannot run inside this process; the file names the round and commit it was taken at
         traffic, traffic_src = None, None
@@ -352,12 +383,12 @@ def main():
                          "achieved_is": "algorithmic bytes (7 B/px, SURVEY 8d) / measured time; the kernels move `traffic` bytes",
                          "real_hbm_GBps": (round(traffic / (ms_thr * 1e-3) / 1e9, 1) if traffic else None),
                          "real_hbm_frac_of_peak": (round(traffic / (ms_thr * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4) if traffic else None),
-                         "traffic": traffic, "traffic_source": traffic_src, "measured_copy_GBps": round(copy_gbps, 1),
+                         "traffic": traffic, "traffic_source": traffic_src, "measured_copy_GBps": (round(copy_gbps, 1) if copy_gbps is not None else None),
                          "algorithmic_bytes_per_launch": ALG_BYTES_PER_PX * w * h * n, "avg_launch_ms": round(ms_thr, 4),
                          "launch_ms_p10_median_p90": [round(float(np.percentile(thr_ms, q)), 4) for q in (10, 50, 90)]},
             "stage_ms_last_step": {k: round(v, 3) for k, v in stage.items()},
         }
-        if world == 1 and not args.no_extras:   # (--no-extras: the profiled runs, whose kernel averages must be over whole-batch launches only)
+        if args.full and world == 1 and not args.no_extras:   # (--no-extras: the profiled runs, whose kernel averages must be over whole-batch launches only)
             # "Gradient extraction (next stage) = 5 B/px read (label + thresh) + compacted output, reported separately":
             # the clusters stage (k_emit -> k_scan -> k_scatter: boundary points between adjacent black / white components, keyed by the
             # component pair, compacted per cluster).  Algorithmic bytes = 5 per pixel read + 4 bytes per point written, read and
@@ -375,7 +406,7 @@ def main():
                                    "points_counted_on": f"{ns} frames of the batch", "ms": round(gms, 4),
                                    "achieved": round(gbytes / (gms * 1e-3) / 1e9, 1), "unit": "GB/s", "frac": round(gbytes / (gms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
                                    "bytes_is": "algorithmic: 5 B/px read (1 thresholded + 4 label, SURVEY 8d) + 12 B per boundary point"}
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             # Not part of the contract fields: the same live run at (a) the detector's library-default quad_decimate = 2, which is
             # what the reference actually runs (it never changes detector defaults, crates/apriltags/src/lib.rs:258-262), and
             # (b) threshold+segment on a low-noise background (noise +-1 plus the ramp stays under min_white_black_diff = 5, so the background
@@ -446,7 +477,7 @@ def main():
                     except Exception as e:  # noqa: BLE001
                         also[name] = {"error": str(e)[:300]}
             out["also"] = also
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cfg = default_config(w, h, quad_decimate=args.decimate)
             out["cpu_baseline"] = cpu_baseline(frames[:args.unique], gyro[:args.unique], task, cfg)
         else:

@@ -304,13 +304,45 @@ def test_bench_loop_runs_the_c_abi_gather_on_one_rank(built):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, CK_BENCH_FORCE_COMM="1", HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1", "--master-port", "29561",
-           os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "16", "--no-cpu-baseline", "--no-extras"]
+           os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "16", "--full", "--no-cpu-baseline", "--no-extras"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stdout[-1000:] + r.stderr[-3000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
     out = json.loads(line)
     assert out["config"]["gather"].startswith("ck_gather_poses") and out["config"]["gather_us"]["bytes_per_rank"] == 16 * 64
     assert out["config"]["frames_with_pose"] == 1.0 and out["n_gpus"] == 1
+
+
+def test_bench_dumps_what_its_last_step_computed(built, tmp_path):
+    """A plain bench.py run (no --full) times exactly --steps steps, carries ms_per_step, measures nothing beside the headline, and
+    --dump-outputs writes the last step's records and valid flags as float64 .npy files equal to what AprilTags.process_batch
+    returns for the same seeded frames."""
+    import json
+    from chalkydri_amd import scenes as S
+    from chalkydri_amd.apriltags import AprilTags
+    from chalkydri_amd.dist import records_to_numpy
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n, w, h = 16, 1280, 800
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", str(n),
+           "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-1000:] + r.stderr[-3000:]
+    out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["unit"] == "frames/s" and out["higher_is_better"] is True
+    assert "also" not in out and "gradient" not in out and out["cpu_baseline"] is None
+    files = sorted(os.listdir(tmp_path))
+    assert sum(os.path.getsize(tmp_path / f) for f in files) <= 64 << 20
+    got = {f[:-4]: np.load(tmp_path / f) for f in files}
+    assert all(a.dtype == np.float64 for a in got.values())
+    frames, gyro, layout, calib, r2c = S.bench_stream(2, n, w, h, 6, stream=0, unique=n, noise_amp=3)
+    task = AprilTags(w, h, layout, calib, r2c, cam_id=0, max_batch=n, quad_decimate=1)
+    recs, valid = task.process_batch(frames, list(gyro))
+    want = records_to_numpy(np.frombuffer(bytes(recs), np.uint8).reshape(n, 64))
+    assert set(got) == {"valid"} | {f"records_{k}" for k in want.dtype.names}
+    for k in want.dtype.names:
+        assert np.array_equal(got[f"records_{k}"], want[k].astype(np.float64)), k
+    assert np.array_equal(got["valid"], valid.astype(np.float64))
+    task.detector.close()
 
 
 def test_full_size_batch_properties(oracle):

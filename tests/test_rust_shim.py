@@ -1,6 +1,7 @@
 """CPU: the Rust FFI layer cannot drift from the C ABI.  rust/chalkydri_hip_sys/src/lib.rs is generated from
 include/chalkydri_hip.h (tools/gen_rust_sys.py); the two safe crates keep the public surface of the reference crates.  No Rust
 toolchain exists in this image, so nothing here compiles Rust: the checks are textual."""
+import json
 import os
 import re
 import subprocess
@@ -55,14 +56,12 @@ def _consts(text):
 
 
 def test_shim_constants_equal_the_references():
-    """every constant the shim re-declares has the reference's value (crates/chalkydri_sqpnp/src/lib.rs:29-39); the reference
-    is read as text, and only here in the container — the GPU box has no /root/reference, the test is CPU-only"""
-    ref_path = "/root/reference/crates/chalkydri_sqpnp/src/lib.rs"
+    """every constant the shim re-declares has the reference's value (crates/chalkydri_sqpnp/src/lib.rs:29-39), as recorded in
+    tests/golden/sqpnp_reference_constants.json"""
     want = {"XY_STD_DEV_SCALAR": 5.0, "THETA_STD_DEV_SCALAR": 2.0, "MAX_TRUSTABLE_RMS": 0.1, "MAX_GYRO_DELTA": 30.0, "TAG_SIZE": 0.1651,
             "CORNER_DISTANCE": 0.08255}
-    if os.path.exists(ref_path):
-        ref = _consts(open(ref_path).read())
-        assert {k: ref[k] for k in want} == want, "the reference's constants have changed: update this test and the shim"
+    ref = json.load(open(os.path.join(ROOT, "tests", "golden", "sqpnp_reference_constants.json")))["constants"]
+    assert {k: ref[k] for k in want} == want, "the reference's constants have changed: update this test and the shim"
     mine = _consts(open(os.path.join(ROOT, "rust", "chalkydri_sqpnp", "src", "lib.rs")).read())
     assert {k: mine.get(k) for k in want} == want
 

@@ -3,7 +3,7 @@
 # single-frame latency, PCIe-inclusive streaming.  Everything lands under gpurun_out/final/.
 out=$GRAFT_REPO_ROOT/gpurun_out/final
 mkdir -p $out
-python bench.py --steps 10 > $out/bench_default.json 2> $out/bench_default.err && echo "bench done" &&
+python bench.py --steps 10 --full > $out/bench_default.json 2> $out/bench_default.err && echo "bench done" &&
 python tools/bench_latency.py 3 2 > $out/latency_n3_d2.json && python tools/bench_latency.py 3 1 > $out/latency_n3_d1.json &&
 python tools/bench_latency.py 1 2 > $out/latency_n1_d2.json && echo "latency done" &&
 python tools/bench_stream.py 8 3 1 > $out/stream_n3_d1.json && python tools/bench_stream.py 8 3 2 > $out/stream_n3_d2.json &&
