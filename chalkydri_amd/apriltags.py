@@ -32,7 +32,7 @@ def load_field_layout(path_or_dict):
 
 class AprilTags:
     def __init__(self, width, height, field, calib, robot_to_cam, cam_id=0, family="tag36h11", bits_corrected=3,
-                 max_batch=1, device=0, **cfg):
+                 max_batch=1, device=0, quad_sigma=0.0, **cfg):
         calib = json.loads(calib) if isinstance(calib, str) else calib
         r2c = json.loads(robot_to_cam) if isinstance(robot_to_cam, str) else robot_to_cam
         m = calib["OpenCVModel5"]
@@ -40,7 +40,7 @@ class AprilTags:
         # argument order of the reference call (lib.rs:247-254): x, y, z, roll, pitch, yaw
         self.robot_to_cam = SqPnP.create_solver_camera_transform(r2c["x"], r2c["y"], r2c["z"], r2c["roll"], r2c["pitch"], r2c["yaw"])
         self.detector = AprilTagDetector(width, height, max_batch=max_batch, families=(family,), bits_corrected=bits_corrected,
-                                         device=device, **cfg)
+                                         device=device, quad_sigma=quad_sigma, **cfg)
         self.solver = SqPnP(self.detector)
         self.tags = field if isinstance(field, dict) and all(isinstance(v, A.Iso3) for v in field.values()) else load_field_layout(field)
         self.cam_id = cam_id

@@ -205,10 +205,10 @@ int ck_stage_device_frames(ck_handle *h, const uint8_t *d_frames, int n, int str
     return CK_OK;
 }
 
-// Runs decimate (if configured) + threshold + segment on n staged frames.
+// Runs decimate and / or the quad_sigma filter (if configured) + threshold + segment on n staged frames.
 int ck_run_threshold_segment(ck_handle *h, const uint8_t *frames, int stride, size_t pitch, int n) {
-    if (h->cfg.quad_decimate > 1) {
-        int rc = ck_launch_decimate(h, frames, stride, pitch, n);
+    if (ck_quad_separate(h)) {
+        int rc = h->qf_ksz > 1 ? ck_launch_prefilter(h, frames, stride, pitch, n) : ck_launch_decimate(h, frames, stride, pitch, n);
         if (rc != CK_OK) return rc;
         return ck_launch_threshold_segment(h, h->d_qframes, round_up(h->qw, 16), (size_t)round_up(h->qw, 16) * h->qh, n);
     }
@@ -254,6 +254,50 @@ extern "C" int ck_segment_batch(ck_handle_t *h, const ck_image_u8_t *imgs, int32
     }
     (void)ck_free_dev(d_canon); (void)ck_free_dev(d_sizes);
     return rc;
+}
+
+extern "C" int ck_set_quad_sigma(ck_handle_t *h, float sigma) {
+    if (!h) return CK_EINVAL;
+    uint8_t k[33];
+    int32_t ksz = 1;
+    int rc = ck_quad_sigma_kernel(sigma, k, 33, &ksz);
+    if (rc != CK_OK) return rc;
+    if (ksz > 1 && !h->d_qframes) { // quad_decimate 1: the quad image becomes a buffer of its own the first time the filter is on
+        CK_HIP(hipSetDevice(h->device));
+        const size_t bytes = (size_t)round_up(h->qw, 16) * h->qh * (size_t)h->cfg.max_batch;
+        hipError_t e = ck_malloc_dev(&h->d_qframes, bytes);
+        if (e != hipSuccess) {
+            snprintf(ck_err_text, sizeof ck_err_text, "quad image allocation (%zu bytes) failed: %s", bytes, hipGetErrorString(e));
+            (void)hipGetLastError();
+            h->d_qframes = nullptr;
+            return e == hipErrorOutOfMemory ? CK_ENOMEM : CK_EDEVICE;
+        }
+    }
+    h->quad_sigma = sigma;
+    h->qf_ksz = ksz;
+    memcpy(h->qf_k, k, sizeof h->qf_k);
+    return CK_OK;
+}
+
+extern "C" int ck_quad_image_batch(ck_handle_t *h, const ck_image_u8_t *imgs, int32_t n, uint8_t *out) {
+    if (!h || !out) return CK_EINVAL;
+    int rc = stage_input(h, imgs, n);
+    if (rc != CK_OK) return rc;
+    if (n == 0) return CK_OK;
+    CK_HIP(hipSetDevice(h->device));
+    const uint8_t *q = h->d_frames;
+    size_t qstride = (size_t)h->frame_stride, qpitch = h->frame_pitch;
+    if (ck_quad_separate(h)) {
+        rc = h->qf_ksz > 1 ? ck_launch_prefilter(h, h->d_frames, h->frame_stride, h->frame_pitch, n)
+                           : ck_launch_decimate(h, h->d_frames, h->frame_stride, h->frame_pitch, n);
+        if (rc != CK_OK) return rc;
+        q = h->d_qframes; qstride = (size_t)round_up(h->qw, 16); qpitch = qstride * h->qh;
+    }
+    for (int i = 0; i < n; i++)
+        CK_HIP(hipMemcpy2DAsync(out + (size_t)i * h->npix, (size_t)h->qw, q + (size_t)i * qpitch, qstride, (size_t)h->qw, (size_t)h->qh,
+                                hipMemcpyDeviceToHost, h->stream));
+    CK_HIP(hipStreamSynchronize(h->stream));
+    return CK_OK;
 }
 
 extern "C" int ck_time_threshold_segment(ck_handle_t *h, int32_t n, int32_t iters, float *ms_out) {

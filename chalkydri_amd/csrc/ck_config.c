@@ -1,5 +1,6 @@
 // Host-side defaults and error strings of the C ABI (no device code).
 #include "chalkydri_hip.h"
+#include <math.h>
 #include <string.h>
 
 int ck_abi_version(void) { return CK_ABI_VERSION; }
@@ -44,4 +45,25 @@ void ck_config_default(ck_config_t *cfg, int32_t width, int32_t height, int32_t 
 void ck_sqpnp_params_default(ck_sqpnp_params_t *p) {
     p->max_iter = 15;   /* chalkydri_sqpnp/src/lib.rs:203 */
     p->tol_sq = 1e-16;  /* chalkydri_sqpnp/src/lib.rs:204 */
+}
+
+/* quad_sigma: the u8 Gaussian AprilTag-3 convolves the quad image with (image_u8_gaussian_blur), restated step by step in
+ * DESIGN.md §quad_sigma and tests/quad_filter_ref.py.  Plain host arithmetic in double precision, libm exp. */
+int ck_quad_sigma_kernel(float sigma, uint8_t *k_out, int32_t cap, int32_t *ksz_out) {
+    if (!ksz_out || isnan(sigma) || isinf(sigma)) return CK_EINVAL;
+    const float s = fabsf(sigma);
+    if (s > 8.0f) return CK_EUNSUPPORTED; /* ksz <= 33: the widest class of the device kernel */
+    int ksz = (int)(4.0f * s);
+    if ((ksz & 1) == 0) ksz++;
+    if (ksz <= 1) { *ksz_out = 1; return CK_OK; }
+    *ksz_out = ksz;
+    if (!k_out || cap < ksz) return CK_EINVAL;
+    double dk[33], acc = 0;
+    for (int i = 0; i < ksz; i++) {
+        const double x = (double)(i - ksz / 2) / (double)s;
+        dk[i] = exp(-0.5 * (x * x));
+    }
+    for (int i = 0; i < ksz; i++) acc += dk[i];
+    for (int i = 0; i < ksz; i++) k_out[i] = (uint8_t)(dk[i] / acc * 255);
+    return CK_OK;
 }

@@ -172,7 +172,12 @@ struct ck_handle {
     uint8_t *d_frames;   // staged input frames, pitch = frame_stride
     int frame_stride;
     size_t frame_pitch;
-    uint8_t *d_qframes;  // decimated copy (== d_frames when quad_decimate == 1)
+    uint8_t *d_qframes;  // the quad image Q when it is a buffer of its own (ck_quad_separate): decimated and/or filtered copy, rows
+                         // padded to 16 bytes; at quad_decimate 1 allocated by the first ck_set_quad_sigma that turns the filter on
+    // quad_sigma (k_prefilter.hip): qf_ksz <= 1 = no filter (the default: nothing about the path changes)
+    float quad_sigma;
+    int qf_ksz;          // taps of the Gaussian, odd, <= 33
+    uint8_t qf_k[33];    // its u8 weights (ck_quad_sigma_kernel)
     uint8_t *d_thresh;   // [n][qh][qw]
     ck_label_t *d_labels; // [n][qh][qw] label words
     uint32_t *d_groot;   // [n][broot_cap] slot table: frame-level root (pixel index) of every ring-touching tile-local component
@@ -226,6 +231,12 @@ static inline int ck_knob_(const char *name, int dflt, int base) { const char *e
 #endif
 int ck_streams_wanted(); // ck_stages.hip: CK_STREAMS (1 or 2), read once
 
+// The quad stages run on a buffer of their own (d_qframes) when the frame is decimated or filtered; otherwise on the frame itself.
+static inline bool ck_quad_separate(const ck_handle *h) { return h->cfg.quad_decimate > 1 || h->qf_ksz > 1; }
+// Edge refinement and decode read the quad image instead of the frame: at quad_decimate 1 with the filter on (upstream blurs the
+// caller's image in place there, so its later stages see the filtered pixels).  The one routing predicate.
+static inline bool ck_refine_reads_quad(const ck_handle *h) { return h->cfg.quad_decimate == 1 && h->qf_ksz > 1; }
+
 // Device allocation of the handle's buffers.  CK_POISON=1 (tests) fills every buffer with 0xA5 bytes, so that a kernel which
 // reads an entry nobody wrote in this call — what an undersized capacity once made of the cluster and run tables — meets the
 // same garbage on every run instead of whatever the allocator happens to hand back.  CK_POISON=2 also lists the buffers.
@@ -260,6 +271,8 @@ int ck_launch_threshold_segment(ck_handle *h, const uint8_t *frames, int stride,
 // canonical labels (min pixel index, flags stripped) and exact sizes — parity/test path, not the hot path
 int ck_launch_canonical_labels(ck_handle *h, int n, uint32_t *d_labels_out, uint32_t *d_sizes_out);
 int ck_launch_decimate(ck_handle *h, const uint8_t *frames, int stride, size_t frame_pitch, int n);
+// quad_sigma filter (+ decimation at quad_decimate 2) of frames [0,n) into d_qframes (k_prefilter.hip)
+int ck_launch_prefilter(ck_handle *h, const uint8_t *frames, int stride, size_t frame_pitch, int n);
 // workspace of the irregular stages (clusters / quads / decode)
 int ck_stage_alloc(ck_handle *h);
 void ck_stage_free(ck_handle *h);

@@ -138,7 +138,7 @@ static ck_handle make_view(const ck_handle *h, int f0, bool second_stream = true
     const size_t f = (size_t)f0, npix = h->npix;
     if (second_stream) v.stream = h->stream2;
     v.d_frames += f * h->frame_pitch;
-    if (h->cfg.quad_decimate > 1) v.d_qframes += f * (size_t)((h->qw + 15) / 16 * 16) * h->qh;
+    if (ck_quad_separate(h)) v.d_qframes += f * (size_t)((h->qw + 15) / 16 * 16) * h->qh;
     else v.d_qframes = v.d_frames;
     v.d_thresh += f * npix; v.d_labels += f * npix;
     v.d_groot += f * h->broot_cap; v.d_gsize += f * h->broot_cap; v.d_gscratch += f * 2 * h->broot_cap; v.d_xband += f * 2 * h->broot_cap;
@@ -164,9 +164,10 @@ static int run_tail(ck_handle *h, const uint8_t *frames, int stride, size_t pitc
     int rc = ck_launch_clusters(h, n);
     if (rc != CK_OK) return rc;
     if (events) CK_HIP(hipEventRecord(ev[3], h->stream));
+    const uint8_t *q = frames; int qs = stride; size_t qp = pitch;
+    if (ck_quad_separate(h)) { q = h->d_qframes; qs = (h->qw + 15) / 16 * 16; qp = (size_t)qs * h->qh; }
+    if (ck_refine_reads_quad(h)) { frames = q; stride = qs; pitch = qp; } // edge refinement and decode read Q as well
     if (upto >= 2) {
-        const uint8_t *q = frames; int qs = stride; size_t qp = pitch;
-        if (h->cfg.quad_decimate > 1) { q = h->d_qframes; qs = (h->qw + 15) / 16 * 16; qp = (size_t)qs * h->qh; }
         rc = ck_launch_fit_quads(h, q, qs, qp, frames, stride, pitch, n);
         if (rc != CK_OK) return rc;
     }

@@ -61,6 +61,9 @@ def _bind(L):
     L.ck_ingest_submit.argtypes = [vp, i32, i32]
     L.ck_detect_ingested.argtypes = [vp, i32, i32, _P(A.Detection), i32, _P(i32), u32p]
     L.ck_process_ingested.argtypes = [vp, i32, i32, _P(A.ProcessParams), vp, vp, _P(A.VisionMeasurement), _P(i32)]
+    L.ck_quad_sigma_kernel.argtypes = [C.c_float, vp, i32, _P(i32)]
+    L.ck_set_quad_sigma.argtypes = [vp, C.c_float]
+    L.ck_quad_image_batch.argtypes = [vp, _P(A.ImageU8), i32, vp]
     L._ck_bound = True
     return L
 
@@ -116,7 +119,7 @@ class Detection:
 class AprilTagDetector:
     """One handle = one GPU + its stream; not thread-safe (mirrors `&mut self`)."""
 
-    def __init__(self, width, height, max_batch=1, families=("tag36h11",), bits_corrected=3, device=0, **cfg):
+    def __init__(self, width, height, max_batch=1, families=("tag36h11",), bits_corrected=3, device=0, quad_sigma=0.0, **cfg):
         self._L = _bind(lib())
         self.cfg = default_config(width, height, max_batch, families, max_hamming=bits_corrected, device=device,
                                   **cfg)
@@ -125,6 +128,15 @@ class AprilTagDetector:
         h = C.c_void_p()
         check(self._L.ck_create(C.byref(self.cfg), C.byref(h)), "ck_create")
         self._h = h
+        self.quad_sigma = 0.0
+        if quad_sigma:
+            self.set_quad_sigma(quad_sigma)
+
+    def set_quad_sigma(self, sigma):
+        """AprilTag-3's quad_sigma: > 0 blurs, < 0 sharpens the image the quad stages run on; |sigma| < 0.5 is off.  May be
+        changed between calls."""
+        check(self._L.ck_set_quad_sigma(self._h, float(sigma)), "ck_set_quad_sigma")
+        self.quad_sigma = float(sigma)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -157,6 +169,13 @@ class AprilTagDetector:
         check(self._L.ck_segment_batch(self._h, arr, n, labels.ctypes.data, sz.ctypes.data if sizes else None),
               "ck_segment_batch")
         return labels, sz
+
+    def quad_image(self, frames=None, n=None):
+        """[n][qh][qw]: the image the quad stages run on (decimated and / or filtered frame)."""
+        arr, keep, n = self._in(frames, n)
+        out = np.empty((n, self.qh, self.qw), np.uint8)
+        check(self._L.ck_quad_image_batch(self._h, arr, n, out.ctypes.data), "ck_quad_image_batch")
+        return out
 
     def time_threshold_segment(self, n, iters=10):
         ms = C.c_float(0)

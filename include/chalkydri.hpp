@@ -72,6 +72,8 @@ class Handle {
     Handle &operator=(const Handle &) = delete;
     ck_handle_t *get() const { return h_; }
     const ck_config_t &config() const { return cfg_; }
+    // AprilTag-3's quad_sigma (chalkydri_hip.h: ck_set_quad_sigma): > 0 blurs, < 0 sharpens the quad image; may change between calls
+    void set_quad_sigma(float sigma) { check(ck_set_quad_sigma(h_, sigma), "ck_set_quad_sigma"); }
 
   private:
     ck_config_t cfg_{};
@@ -529,6 +531,7 @@ class AprilTags {
         std::map<size_t, sqpnp::Iso3> layout;   // AprilTagFieldLayout::load (field_layout.rs:18-44)
         uint8_t cam_id = 0;                     // lib.rs:256
         int device = 0, max_batch = 1, quad_decimate = 1;
+        float quad_sigma = 0.0f;                // AprilTag-3 detector field; 0 = no filter
     };
     explicit AprilTags(const Config &c)
         : cfg_(c), h_(std::make_shared<Handle>((int)c.width, (int)c.height, c.max_batch, std::vector<std::string>{c.family}, (int)c.bits_corrected,
@@ -539,6 +542,7 @@ class AprilTags {
             t.pose = kv.second.raw();
             field_.push_back(t);
         }
+        if (c.quad_sigma != 0.0f) h_->set_quad_sigma(c.quad_sigma);
         pp_.cam = c.calib;
         pp_.robot_to_cam = sqpnp::SqPnP::create_solver_camera_transform(c.robot_to_cam.x, c.robot_to_cam.y, c.robot_to_cam.z, c.robot_to_cam.roll,
                                                                         c.robot_to_cam.pitch, c.robot_to_cam.yaw).raw(); // lib.rs:247-254

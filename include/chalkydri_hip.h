@@ -180,6 +180,25 @@ int ck_segment_batch(ck_handle_t *h, const ck_image_u8_t *imgs, int32_t n, uint3
  * handle's stream between HIP events and returns the mean milliseconds per pass in *ms_out. */
 int ck_time_threshold_segment(ck_handle_t *h, int32_t n, int32_t iters, float *ms_out);
 
+/* ---- quad_sigma: Gaussian blur / sharpen of the quad image (AprilTag-3's detector field quad_sigma) -------------------------
+ * sigma > 0 blurs the image the quad stages run on (the decimated frame D, or the frame itself at quad_decimate 1) with a
+ * Gaussian of ksz taps, sigma < 0 sharpens it (clamp(2 D - blur, 0, 255)); |sigma| < 0.5 (ksz <= 1) is no filter at all, the
+ * default.  Threshold, segmentation, clusters and the quad fit's gradient weights read the filtered image Q; edge refinement and
+ * decode read the unfiltered frame at quad_decimate 2 and Q at quad_decimate 1 (upstream filters the caller's image in place
+ * there; the library reproduces that result without writing to the caller's frame).  DESIGN.md §quad_sigma has the exact rule.
+ * While the filter is on, ck_last_stage_ms().threshold and ck_time_threshold_segment include it, as they include decimation. */
+/* The u8 weights of a sigma: pure host arithmetic, no device needed.  *ksz_out = taps (1: no filter, k_out untouched);
+ * k_out[0..ksz) = the weights.  CK_EINVAL for NaN / inf, a null ksz_out, or (filter on) a null k_out or cap < ksz (*ksz_out is
+ * set then); CK_EUNSUPPORTED for |sigma| > 8 (ksz > 33). */
+int ck_quad_sigma_kernel(float sigma, uint8_t *k_out, int32_t cap, int32_t *ksz_out);
+/* Sets the handle's quad_sigma; may be called at any time between calls (a batch already enqueued keeps the value it was
+ * enqueued with).  At quad_decimate 1 the first value that turns the filter on allocates the quad-image buffer (one byte per
+ * pixel per max_batch frame): CK_ENOMEM when that fails.  Errors as ck_quad_sigma_kernel; the handle keeps its value then. */
+int ck_set_quad_sigma(ck_handle_t *h, float sigma);
+/* out: [n][height / quad_decimate][width / quad_decimate] — the image the quad stages run on (Q; D when the filter is off).
+ * Runs on frames staged by ck_upload_frames when imgs == NULL. */
+int ck_quad_image_batch(ck_handle_t *h, const ck_image_u8_t *imgs, int32_t n, uint8_t *out);
+
 /* Boundary points grouped in clusters.  A point packs x,y in half-pixel units and the gradient sign. */
 typedef struct ck_cluster_point {
     uint16_t x, y;  /* half-pixel coordinates 2*px+dx, 2*py+dy */
