@@ -76,6 +76,31 @@ extern "C" int ck_device_count(void) {
 
 static int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
+// The rules beside ck_family_t in chalkydri_hip.h.  k_decode relies on them: 8 * width_at_border border samples and the
+// total_width^2 grid live in fixed LDS arrays, every bit cell is written into that grid, a code word is one lane's register
+// of at most 64 bits, and the codebook search packs the id into 20 bits of its key.
+static bool family_ok(const ck_family_t *f) {
+    if (!f) return false;
+    if (!f->codes || !f->bit_x || !f->bit_y) return false;
+    if (f->nbits < 1) return false;
+    if (f->nbits > 64) return false;
+    if (f->ncodes < 1) return false;
+    if (f->ncodes >= (1u << 20)) return false;
+    if (f->n_upstream > f->ncodes) return false;
+    if (f->width_at_border < 1) return false;
+    if (f->total_width > 16) return false;
+    if (f->width_at_border > f->total_width) return false;
+    const int min_coord = (f->width_at_border - f->total_width) / 2; // (k_decode's and AprilTag-3's)
+    for (uint32_t i = 0; i < f->nbits; i++) {
+        const int x = (int)f->bit_x[i], y = (int)f->bit_y[i];
+        if (x < min_coord || x >= min_coord + f->total_width || y < min_coord || y >= min_coord + f->total_width) return false;
+    }
+    if (f->nbits < 64)
+        for (uint32_t k = 0; k < f->ncodes; k++)
+            if (f->codes[k] >> f->nbits) return false;
+    return true;
+}
+
 extern "C" int ck_create(const ck_config_t *cfg, ck_handle_t **out) {
     if (!cfg || !out) return CK_EINVAL;
     *out = nullptr;
@@ -83,8 +108,7 @@ extern "C" int ck_create(const ck_config_t *cfg, ck_handle_t **out) {
     if (cfg->max_batch < 1 || cfg->n_families < 1 || cfg->n_families > CK_MAX_FAMILIES) return CK_EINVAL;
     if (cfg->quad_decimate != 1 && cfg->quad_decimate != 2) return CK_EUNSUPPORTED;
     for (int i = 0; i < cfg->n_families; i++)
-        if (!cfg->families[i] || cfg->families[i]->nbits > 64 || cfg->families[i]->total_width > 16 ||
-            cfg->families[i]->n_upstream > cfg->families[i]->ncodes) return CK_EINVAL;
+        if (!family_ok(cfg->families[i])) return CK_EINVAL;
     int qw = cfg->width / cfg->quad_decimate, qh = cfg->height / cfg->quad_decimate;
     if (qw < 8 || qh < 8) return CK_EINVAL;
     if (cfg->min_component_px < 1 || cfg->min_component_px > 0x3FFFFFFF) return CK_EINVAL;

@@ -74,7 +74,7 @@ __device__ __forceinline__ unsigned long long code_rotate90(unsigned long long w
     int p = nbits; unsigned long long l = 0;
     if (nbits % 4 == 1) { p = nbits - 1; l = 1; }
     w = ((w >> l) << (p / 4 + l)) | (w >> (3 * p / 4 + l) << l) | (w & l);
-    w &= ((1ull << nbits) - 1);
+    w &= nbits >= 64 ? ~0ull : ((1ull << nbits) - 1); // (a shift by 64 is undefined; the 64-bit shift takes the count mod 64, which would make the mask 0)
     return w;
 }
 

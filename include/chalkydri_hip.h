@@ -86,6 +86,12 @@ typedef struct ck_family {
                                * built against ABI version 1, which had no such field) means ncodes: the caller vouches
                                * for its table; a value above ncodes is refused by ck_create (CK_EINVAL). */
 } ck_family_t;
+/* What ck_create accepts as a family (CK_EINVAL otherwise): codes, bit_x and bit_y not NULL; 1 <= nbits <= 64;
+ * 1 <= ncodes < 2^20; every code < 2^nbits; 1 <= width_at_border <= total_width <= 16; every bit cell inside the grid,
+ * min_coord <= bit_x[i], bit_y[i] < min_coord + total_width with min_coord = (width_at_border - total_width) / 2 (C division,
+ * AprilTag-3's; bit_x and bit_y are read as int32 there, so cells outside the border are negative); n_upstream <= ncodes.
+ * The bit layout must follow AprilTag-3's convention for rotations to decode: bits nbits/4 apart are one quarter turn of the
+ * tag apart (the centre cell last when nbits % 4 == 1), as in the built-in tables. */
 
 /* Built-in tables.  "tag16h5": all 30 upstream codes (n_upstream = 30).  "tag36h11": upstream layout, 587 codes of which
  * IDs 0..38 are upstream codes (n_upstream = 39: every tag of the reference's field.json, IDs 1..32) and IDs 39..586 are a
@@ -146,7 +152,8 @@ int ck_device_count(void);       /* 0 when no HIP device is visible */
 
 /* Frame geometry accepted by ck_create: any width and height of 16..4095 pixels (at least 8 after quad_decimate) — what an
  * image_u8_t can describe within the 13-bit half-pixel coordinates of the boundary points; quad_decimate 1 or 2
- * (CK_EUNSUPPORTED otherwise); min_component_px >= 1; 1..CK_MAX_FAMILIES families, each with n_upstream <= ncodes.
+ * (CK_EUNSUPPORTED otherwise); min_component_px >= 1; 1..CK_MAX_FAMILIES families, each valid as ck_family_t's
+ * rules say.
  * CK_EINVAL for everything else.  Arguments are validated before a device is looked for (CK_ENODEVICE). */
 int ck_create(const ck_config_t *cfg, ck_handle_t **out);
 void ck_destroy(ck_handle_t *h);

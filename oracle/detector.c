@@ -642,7 +642,7 @@ static uint64_t code_rotate90(uint64_t w, int nbits) {
     int p = nbits; uint64_t l = 0;
     if (nbits % 4 == 1) { p = nbits - 1; l = 1; }
     w = ((w >> l) << (p / 4 + l)) | (w >> (3 * p / 4 + l) << l) | (w & l);
-    w &= (((uint64_t)1 << nbits) - 1);
+    w &= nbits >= 64 ? ~(uint64_t)0 : (((uint64_t)1 << nbits) - 1); /* (a 64-bit shift is undefined: x86 masks the count to 0) */
     return w;
 }
 

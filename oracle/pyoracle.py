@@ -102,6 +102,32 @@ def detect(img, cfg, cap=256):
     return dets_to_list(dets, n.value), st.value
 
 
+def quads(img, cfg):
+    """The quads ora_detect decodes: decimation, threshold, segmentation, clusters and fit with cfg's settings."""
+    img, p = _u8(img)
+    h, w = img.shape
+    q = img
+    if cfg.quad_decimate > 1:
+        f = cfg.quad_decimate
+        q = np.empty((h // f, w // f), np.uint8)
+        lib().ora_decimate(C.c_void_p(p), w, h, w, f, C.c_void_p(q.ctypes.data))
+    th = threshold(q, cfg.min_white_black_diff)
+    lab, sz = segment(th)
+    cl, pts, _ = clusters(th, lab, sz, cfg.min_component_px)
+    return fit_quads(img, cfg, cl, pts, quad_img=q)[0]
+
+
+def decode_quads(img, cfg, quad_list, cap=256):
+    """ora_decode_quads on the given quads (de-duplication included: pass one quad to see everything it decodes to)."""
+    img, p = _u8(img)
+    h, w = img.shape
+    arr = (A.Quad * max(len(quad_list), 1))(*quad_list)
+    dets = (A.Detection * cap)()
+    n = C.c_int(0)
+    lib().ora_decode_quads(C.c_void_p(p), w, h, w, C.byref(cfg), arr, len(quad_list), dets, cap, C.byref(n))
+    return dets_to_list(dets, n.value)
+
+
 def dets_to_list(dets, n):
     out = []
     for i in range(n):

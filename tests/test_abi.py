@@ -105,6 +105,71 @@ def test_create_validates_before_touching_a_device(built):
         L.ck_destroy(h)
 
 
+def test_create_refuses_bad_families(built):
+    """ck_create checks what k_decode relies on for memory safety (ck_family_t's rules in chalkydri_hip.h): each bad table is
+    CK_EINVAL before any device is looked for; the good table it was made from is accepted."""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import family_gen as fg
+    from chalkydri_amd.detector import _bind
+    L = _bind(_lib.lib())
+    h = C.c_void_p()
+    nbits, wab, tw, rev, cells, mh, _ = fg.MATRIX["std41r"]
+    bx, by = fg.layout(cells, wab)
+    codes = [int(c) for c in fg.tables(fg.make("std41r"))[6]]
+
+    def rc(**kw):
+        a = dict(nbits=nbits, wab=wab, tw=tw, rev=rev, bx=bx, by=by, codes=codes, min_hamming=mh)
+        a.update(kw)
+        fam = fg.family_from("bad", **a)
+        cfg = default_config(640, 480, families=(_lib.family("tag36h11"), fam))
+        r = L.ck_create(C.byref(cfg), C.byref(h))
+        if h.value:
+            L.ck_destroy(h)
+            h.value = None
+        return r
+
+    assert rc() in (A.CK_OK, A.CK_ENODEVICE)
+    # every bad table below breaks exactly one rule (the others hold for it), so each rule is pinned by its own case
+    shift = lambda d: dict(bx=[x + d for x in bx], by=[y + d for y in by])
+    assert rc(nbits=0, codes=[0]) == A.CK_EINVAL                                        # nbits >= 1
+    assert rc(nbits=65, bx=bx + bx[:24], by=by + by[:24]) == A.CK_EINVAL               # nbits <= 64 (65 valid cells)
+    assert rc(codes=[]) == A.CK_EINVAL                                                  # ncodes >= 1
+    assert rc(codes=[codes[0]] * (1 << 20)) == A.CK_EINVAL                              # ids are 20 bits of the codebook search's key
+    assert rc(codes=[codes[0]] * ((1 << 20) - 1)) in (A.CK_OK, A.CK_ENODEVICE)
+    assert rc(n_upstream=len(codes) + 1) == A.CK_EINVAL                                 # n_upstream <= ncodes
+    assert rc(wab=0, **shift(-2)) == A.CK_EINVAL                                        # width_at_border >= 1 (grid [-4, 5))
+    assert rc(tw=17) == A.CK_EINVAL                                                     # total_width <= 16 (grid [-6, 11))
+    # width_at_border <= total_width: 8 * 17 = 136 border samples would overrun k_decode's 128 (grid [0, 16))
+    assert rc(wab=17, tw=16, **shift(2)) == A.CK_EINVAL
+    assert rc(wab=16, tw=16, **shift(2)) in (A.CK_OK, A.CK_ENODEVICE)
+    lo, hi = (wab - tw) // 2, (wab - tw) // 2 + tw                                      # every cell in the grid [lo, hi) = [-2, 7)
+    assert rc(bx=[lo] + bx[1:], by=[lo] + by[1:]) in (A.CK_OK, A.CK_ENODEVICE) and rc(bx=bx[:-1] + [hi - 1]) in (A.CK_OK, A.CK_ENODEVICE)
+    for i, x, y in [(0, lo - 1, None), (7, None, hi), (40, hi, None), (20, None, lo - 1), (3, 1 << 20, None)]:
+        assert rc(bx=[x if (j == i and x is not None) else v for j, v in enumerate(bx)],
+                  by=[y if (j == i and y is not None) else v for j, v in enumerate(by)]) == A.CK_EINVAL, i
+    assert rc(codes=codes + [codes[0] | (1 << nbits)]) == A.CK_EINVAL                  # every code < 2^nbits
+    # NULL tables, in a child: without the check ck_create would read through the NULL pointer, which ends the process
+    import subprocess
+    child = ("import sys, ctypes as C; sys.path[:0] = [{root!r}, {here!r}]\n"
+             "import family_gen as fg\n"
+             "from chalkydri_amd import _abi as A, _lib, default_config\n"
+             "from chalkydri_amd.detector import _bind\n"
+             "L, h = _bind(_lib.lib()), C.c_void_p()\n"
+             "fam = fg.make('std41r')\n"
+             "setattr(fam.contents, sys.argv[1], None)\n"
+             "print('rc', L.ck_create(C.byref(default_config(640, 480, families=(fam,))), C.byref(h)))\n"
+             ).format(root=ROOT, here=os.path.dirname(os.path.abspath(__file__)))
+    for field in ("codes", "bit_x", "bit_y"):
+        r = subprocess.run([sys.executable, "-c", child, field], capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0 and f"rc {A.CK_EINVAL}" in r.stdout, (field, r.returncode, r.stdout[-500:], r.stderr[-500:])
+    # the 64-bit word: every code is in range, none is refused for its top bit
+    assert L.ck_create(C.byref(default_config(640, 480, families=(fg.make("full64"), fg.make("full64w")))), C.byref(h)) in (A.CK_OK, A.CK_ENODEVICE)
+    if h.value:
+        L.ck_destroy(h)
+        h.value = None
+
+
 def test_product_library_reads_no_diagnostic_knob(built):
     """The drop-in must not change what it returns with the environment: the measurement / path-forcing knobs (CK_*_STOP_AFTER,
     CK_FIT_SKIP, CK_FMERGE_CAP, CK_SEG_CHUNKS, ...) exist only in the -DCK_DIAG build (lib/diag/).  The product library names exactly
