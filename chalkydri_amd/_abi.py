@@ -75,6 +75,16 @@ class OpenCV5(C.Structure):
     _fields_ = [(k, C.c_double) for k in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3")]
 
 
+class TagPoseParams(C.Structure):
+    _fields_ = [("cam", OpenCV5), ("tagsize", C.c_double * CK_MAX_FAMILIES), ("n_iters", C.c_int32), ("pad", C.c_int32)]
+
+
+class TagPose(C.Structure):
+    _fields_ = [("id", C.c_int32), ("family", C.c_int32), ("valid", C.c_int32), ("has_alt", C.c_int32),
+                ("R", C.c_double * 9), ("t", C.c_double * 3), ("err", C.c_double), ("R_alt", C.c_double * 9),
+                ("t_alt", C.c_double * 3), ("err_alt", C.c_double), ("H", C.c_double * 9)]
+
+
 class VisionMeasurement(C.Structure):
     _fields_ = [("pose_x", C.c_double), ("pose_y", C.c_double), ("pose_rot", C.c_double),
                 ("std_x", C.c_double), ("std_y", C.c_double), ("std_rot", C.c_double), ("ts", C.c_uint64),
@@ -103,6 +113,7 @@ class SynthParams(C.Structure):
 
 
 assert C.sizeof(VisionMeasurement) == 64  # crates/whacknet/src/lib.rs:92-95
+assert C.sizeof(TagPoseParams) == 112 and C.sizeof(TagPose) == 296
 
 # per-frame status bits (include/chalkydri_hip.h)
 CK_FRAME_OK, CK_FRAME_POINTS_OVERFLOW, CK_FRAME_CLUSTERS_OVERFLOW, CK_FRAME_QUADS_OVERFLOW, CK_FRAME_DETS_OVERFLOW = 0, 1, 2, 4, 8

@@ -68,6 +68,8 @@ def lib():
     L.ck_config_default.argtypes = [P(A.Config), C.c_int32, C.c_int32, C.c_int32]
     L.ck_sqpnp_params_default.restype = None
     L.ck_sqpnp_params_default.argtypes = [P(A.SqpnpParams)]
+    L.ck_tag_pose_params_default.restype = None
+    L.ck_tag_pose_params_default.argtypes = [P(A.TagPoseParams)]
     L.ck_synth_params_default.restype = None
     L.ck_synth_params_default.argtypes = [P(A.SynthParams), C.c_int32, C.c_int32, C.c_int32]
     L.ck_synth_render.restype = C.c_int

@@ -119,6 +119,7 @@ extern "C" int ck_create(const ck_config_t *cfg, ck_handle_t **out) {
     h->cfg = *cfg;
     h->device = cfg->device;
     h->n_last_pose = -1;
+    h->n_last_dets = -1;
     h->w = cfg->width; h->h = cfg->height; h->qw = qw; h->qh = qh;
     h->npix = (size_t)qw * qh;
     h->tiles_x = (qw + CK_TW - 1) / CK_TW; h->tiles_y = (qh + CK_TH - 1) / CK_TH;
@@ -177,6 +178,7 @@ extern "C" void ck_destroy(ck_handle_t *h) {
     if (h->seg_stream) (void)hipStreamSynchronize(h->seg_stream);
     ck_stage_free(h);
     (void)ck_free_dev(h->d_frames); (void)ck_free_dev(h->d_qframes); (void)ck_free_dev(h->d_thresh); (void)ck_free_dev(h->d_labels);
+    (void)ck_free_dev(h->d_tp_dets); (void)ck_free_dev(h->d_tp_out); (void)ck_free_dev(h->d_tp_counts);
     (void)ck_free_dev(h->d_groot); (void)ck_free_dev(h->d_gsize); (void)ck_free_dev(h->d_gscratch); (void)ck_free_dev(h->d_xband); (void)ck_free_dev(h->d_broots); (void)ck_free_dev(h->d_tile_count); (void)ck_free_dev(h->d_ring);
     for (auto &e : h->ev) if (e) (void)hipEventDestroy(e);
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);

@@ -198,6 +198,12 @@ struct ck_handle {
     ck_dev_family *d_fams;
     int n_staged;        // frames currently staged in d_frames
     int n_last_pose;     // records the last ck_process_* call left in ws.d_meas (what ck_gather_poses may send); -1: none yet
+    int n_last_dets;     // frames whose detections the last ck_detect_* / ck_process_* call left in ws (what ck_last_tag_poses reads);
+                         // -1: none yet, or a later call (ck_clusters_batch, ck_quads_batch, a failed pipeline) rewrote the workspace
+    // per-tag pose (k_tagpose.hip): allocated by the first ck_estimate_tag_poses / ck_last_tag_poses, max_batch * det_cap entries
+    ck_detection_t *d_tp_dets; // caller detections staged for ck_estimate_tag_poses
+    ck_tag_pose_t *d_tp_out;   // pose records
+    int32_t *d_tp_counts;      // [max_batch] per-frame counts of ck_last_tag_poses
     bool fmerge_lds_allowed; // k_fmerge's dynamic LDS limit has been raised on this handle's device
 };
 

@@ -194,6 +194,7 @@ static int parts_wanted() {
 static int run_pipeline(ck_handle *h, const uint8_t *frames, int stride, size_t pitch, int n, int upto /*1 clusters, 2 quads, 3 all*/,
                         ck_split *split = nullptr) {
     hipEvent_t *ev = h->ev;
+    h->n_last_dets = -1; // the workspace is rewritten from here on; it holds this call's detections only once they are all enqueued
     CK_HIP(hipEventRecord(ev[1], h->stream));
     int rc = ck_run_threshold_segment(h, frames, stride, pitch, n);
     if (rc != CK_OK) return rc;
@@ -202,7 +203,9 @@ static int run_pipeline(ck_handle *h, const uint8_t *frames, int stride, size_t 
     if (parts > n) parts = n;
     if (!split || parts < 2 || ck_streams_wanted() < 2) {
         if (split) { split->parts = 1; split->first[0] = 0; split->first[1] = n; }
-        return run_tail(h, frames, stride, pitch, n, upto, true);
+        rc = run_tail(h, frames, stride, pitch, n, upto, true);
+        if (rc == CK_OK && upto >= 3) h->n_last_dets = n;
+        return rc;
     }
     split->parts = parts;
     for (int p = 0; p <= parts; p++) split->first[p] = (int)((long long)n * p / parts);
@@ -215,6 +218,7 @@ static int run_pipeline(ck_handle *h, const uint8_t *frames, int stride, size_t 
         rc = run_tail(hp, frames + (size_t)f0 * pitch, stride, pitch, cnt, upto, p == 0);
         if (rc != CK_OK) return rc;
     }
+    if (upto >= 3) h->n_last_dets = n;
     return CK_OK;
 }
 // the handle's stream continues only after stream2 has finished its half

@@ -64,6 +64,8 @@ def _bind(L):
     L.ck_quad_sigma_kernel.argtypes = [C.c_float, vp, i32, _P(i32)]
     L.ck_set_quad_sigma.argtypes = [vp, C.c_float]
     L.ck_quad_image_batch.argtypes = [vp, _P(A.ImageU8), i32, vp]
+    L.ck_estimate_tag_poses.argtypes = [vp, _P(A.TagPoseParams), vp, i32, vp]
+    L.ck_last_tag_poses.argtypes = [vp, _P(A.TagPoseParams), vp, i32, vp]
     L._ck_bound = True
     return L
 
@@ -114,6 +116,76 @@ class Detection:
 
     def __repr__(self):
         return f"Detection(id={self._id}, hamming={self._hamming}, margin={self._margin:.1f})"
+
+
+def tag_pose_params(fx, fy, cx, cy, tagsize=0.1651, distortion=None, n_iters=50):
+    """ck_tag_pose_params_t for estimate_tag_poses / last_tag_poses.  tagsize: edge of the black square in metres, one value
+    for every family or a sequence by family index; distortion: OpenCV-5 (k1, k2, p1, p2, k3), None = pinhole."""
+    pp = A.TagPoseParams()
+    lib().ck_tag_pose_params_default(C.byref(pp))
+    k1, k2, p1, p2, k3 = (0.0,) * 5 if distortion is None else (float(v) for v in distortion)
+    pp.cam = A.OpenCV5(float(fx), float(fy), float(cx), float(cy), k1, k2, p1, p2, k3)
+    sizes = [tagsize] * A.CK_MAX_FAMILIES if np.ndim(tagsize) == 0 else list(tagsize)
+    for i, v in enumerate(sizes[:A.CK_MAX_FAMILIES]):
+        pp.tagsize[i] = float(v)
+    pp.n_iters = int(n_iters)
+    return pp
+
+
+class TagPose:
+    """One ck_tag_pose_t: the pose of a tag relative to the camera (tag -> camera; camera x right, y down, z forward), as
+    AprilTag-3's estimate_tag_pose returns it, with the other local minimum kept beside it."""
+    __slots__ = ("id", "family", "valid", "has_alt", "_R", "_t", "_err", "_R_alt", "_t_alt", "_err_alt", "_H")
+
+    def __init__(self, r):
+        self.id, self.family, self.valid, self.has_alt = r.id, r.family, bool(r.valid), bool(r.has_alt)
+        self._R = np.array(r.R[:]).reshape(3, 3)
+        self._t = np.array(r.t[:])
+        self._err = r.err
+        self._R_alt = np.array(r.R_alt[:]).reshape(3, 3)
+        self._t_alt = np.array(r.t_alt[:])
+        self._err_alt = r.err_alt
+        self._H = np.array(r.H[:]).reshape(3, 3)
+
+    def rotation(self):
+        return self._R
+
+    def translation(self):
+        return self._t
+
+    def error(self):
+        return self._err
+
+    def homography(self):
+        return self._H
+
+    def alternative(self):
+        """(R, t, err) of the other local minimum, or None."""
+        return (self._R_alt, self._t_alt, self._err_alt) if self.has_alt else None
+
+    def ambiguity(self):
+        """err / err_alt: near 1 when the two minima explain the corners equally well; 0 without an alternative."""
+        return self._err / self._err_alt if self.has_alt and self._err_alt > 0 else 0.0
+
+    def __repr__(self):
+        return f"TagPose(id={self.id}, valid={self.valid}, t={np.round(self._t, 4).tolist()}, err={self._err:.3g})"
+
+
+def _raw_detections(dets):
+    """Detection objects, ck_detection_t arrays or an [n] ctypes array -> ctypes array (+ count)."""
+    if isinstance(dets, C.Array):
+        return dets, len(dets)
+    arr = (A.Detection * max(len(dets), 1))()
+    for i, d in enumerate(dets):
+        if isinstance(d, A.Detection):
+            arr[i] = d
+            continue
+        r = arr[i]
+        r.id, r.hamming, r.family, r.decision_margin = d.id(), d.hamming(), d.family(), d.decision_margin()
+        r.c[0], r.c[1] = d.center()
+        for k in range(4):
+            r.p[k][0], r.p[k][1] = d.corners()[k]
+    return arr, len(dets)
 
 
 class AprilTagDetector:
@@ -224,6 +296,26 @@ class AprilTagDetector:
         check(self._L.ck_detect_batch_device(self._h, C.c_void_p(ptr), n, stride, frame_pitch, dets, cap, counts,
                                              status), "ck_detect_batch_device")
         return [[Detection(dets[i * cap + k]) for k in range(counts[i])] for i in range(n)], list(status)
+
+    # -- per-tag pose (AprilTag-3's estimate_tag_pose), on the GPU ---------------------------------------------------
+    def estimate_tag_poses(self, dets, params, raw=False):
+        """Poses of caller detections (Detection objects or ck_detection_t records): one TagPose per detection."""
+        arr, n = _raw_detections(dets)
+        out = (A.TagPose * max(n, 1))()
+        check(self._L.ck_estimate_tag_poses(self._h, C.byref(params), arr, n, out), "ck_estimate_tag_poses")
+        return out[:n] if raw else [TagPose(out[i]) for i in range(n)]
+
+    def last_tag_poses(self, params, cap=64, raw=False):
+        """Poses of the detections the last detect / process call of this handle produced (still on the device):
+        a list per frame of that call, truncated to `cap` like the detections."""
+        nb = self.max_batch
+        out = (A.TagPose * (nb * cap))()
+        counts = (C.c_int32 * nb)(*([-1] * nb))   # the call writes one count per frame of the last call: the rest stay -1
+        check(self._L.ck_last_tag_poses(self._h, C.byref(params), out, cap, counts), "ck_last_tag_poses")
+        n = sum(1 for c in counts if c >= 0)
+        if raw:
+            return [[out[i * cap + k] for k in range(counts[i])] for i in range(n)]
+        return [[TagPose(out[i * cap + k]) for k in range(counts[i])] for i in range(n)]
 
     def stage_ms(self):
         ms = A.StageMs()

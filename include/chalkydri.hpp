@@ -21,6 +21,7 @@
 #include <sys/socket.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <array>
 #include <atomic>
 #include <cmath>
@@ -96,6 +97,61 @@ class Detection {
   private:
     ck_detection_t d_;
 };
+
+// ---- per-tag pose (chalkydri_hip.h: ck_estimate_tag_poses / ck_last_tag_poses), AprilTag-3's estimate_tag_pose ----------
+// What `apriltag::TagParams {tagsize, fx, fy, cx, cy}` carries; the OpenCV-5 distortion stays zero (pinhole) unless set.
+inline ck_tag_pose_params_t tag_pose_params(double fx, double fy, double cx, double cy, double tagsize = 0.1651, int n_iters = 50) {
+    ck_tag_pose_params_t pp;
+    ck_tag_pose_params_default(&pp);
+    pp.cam.fx = fx; pp.cam.fy = fy; pp.cam.cx = cx; pp.cam.cy = cy;
+    for (double &s : pp.tagsize) s = tagsize;
+    pp.n_iters = n_iters;
+    return pp;
+}
+
+// One pose record: tag -> camera (camera x right, y down, z forward), the lower-error minimum first.
+class TagPose {
+  public:
+    explicit TagPose(const ck_tag_pose_t &r) : r_(r) {}
+    bool valid() const { return r_.valid != 0; }
+    std::array<double, 9> rotation() const { std::array<double, 9> a; std::copy(r_.R, r_.R + 9, a.begin()); return a; }
+    std::array<double, 3> translation() const { return {r_.t[0], r_.t[1], r_.t[2]}; }
+    double error() const { return r_.err; }
+    bool has_alternative() const { return r_.has_alt != 0; }
+    std::array<double, 9> alternative_rotation() const { std::array<double, 9> a; std::copy(r_.R_alt, r_.R_alt + 9, a.begin()); return a; }
+    std::array<double, 3> alternative_translation() const { return {r_.t_alt[0], r_.t_alt[1], r_.t_alt[2]}; }
+    double alternative_error() const { return r_.err_alt; }
+    // err / err_alt: near 1 when both minima explain the corners equally well (an ambiguous view); 0 without an alternative
+    double ambiguity() const { return r_.has_alt && r_.err_alt > 0 ? r_.err / r_.err_alt : 0.0; }
+    const ck_tag_pose_t &raw() const { return r_; }
+
+  private:
+    ck_tag_pose_t r_;
+};
+
+inline std::vector<TagPose> estimate_tag_poses(Handle &h, const ck_tag_pose_params_t &pp, const std::vector<Detection> &dets) {
+    std::vector<ck_detection_t> in;
+    for (const Detection &d : dets) in.push_back(d.raw());
+    std::vector<ck_tag_pose_t> out(in.size() ? in.size() : 1);
+    check(ck_estimate_tag_poses(h.get(), &pp, in.data(), (int32_t)in.size(), out.data()), "ck_estimate_tag_poses");
+    std::vector<TagPose> r;
+    for (size_t i = 0; i < in.size(); i++) r.emplace_back(out[i]);
+    return r;
+}
+
+// Poses of the detections the handle's last detect / process call produced, per frame of that call.
+inline std::vector<std::vector<TagPose>> last_tag_poses(Handle &h, const ck_tag_pose_params_t &pp, int cap_per_frame = 64) {
+    const int nb = h.config().max_batch;
+    std::vector<ck_tag_pose_t> out((size_t)nb * cap_per_frame);
+    std::vector<int32_t> counts((size_t)nb, -1); // one count per frame of the last call is written: the rest stay -1
+    check(ck_last_tag_poses(h.get(), &pp, out.data(), cap_per_frame, counts.data()), "ck_last_tag_poses");
+    std::vector<std::vector<TagPose>> r;
+    for (int f = 0; f < nb && counts[f] >= 0; f++) {
+        r.emplace_back();
+        for (int k = 0; k < counts[f]; k++) r.back().emplace_back(out[(size_t)f * cap_per_frame + k]);
+    }
+    return r;
+}
 
 namespace apriltags {
 

@@ -365,6 +365,51 @@ int ck_detect_ingested(ck_ingest_t *ing, int32_t slot, int32_t n, ck_detection_t
 int ck_process_ingested(ck_ingest_t *ing, int32_t slot, int32_t n, const ck_process_params_t *pp, const double *gyro,
                         const uint8_t *has_gyro, ck_vision_measurement_t *out, int32_t *valid);
 
+/* ---- per-tag pose: AprilTag-3's estimate_tag_pose ----------------------------------------------------------------------
+ * The pose of each single tag relative to the camera: homography -> orthogonal iteration (Lu, Hager & Mjolsness) -> second
+ * local minimum (Schweighofer & Pinz) -> the lower object-space error first.  One fp64 lane per detection on the handle's
+ * stream; nothing is computed on the host.  DESIGN.md §Per-tag pose has the exact contract.  Tag frame: object corners
+ * s*(-1,1,0), s*(1,1,0), s*(1,-1,0), s*(-1,-1,0) in ck_detection_t's corner order, s = tagsize / 2. */
+typedef struct ck_tag_pose_params {
+    ck_opencv5_t cam;                  /* fx, fy, cx, cy, k1, k2, p1, p2, k3; all-zero distortion = AprilTag-3's pinhole */
+    double tagsize[CK_MAX_FAMILIES];   /* edge of the black square in metres, by ck_detection_t.family */
+    int32_t n_iters;                   /* orthogonal-iteration steps per minimum: 50, as estimate_tag_pose */
+    int32_t pad;
+} ck_tag_pose_params_t;
+
+typedef struct ck_tag_pose {
+    int32_t id, family;                /* copied from the detection */
+    int32_t valid;                     /* 0: no pose (degenerate input); every other field but id / family is then 0 */
+    int32_t has_alt;                   /* a second local minimum was found */
+    double R[9];                       /* tag -> camera, row-major; camera x right, y down, z forward */
+    double t[3];                       /* tag centre in camera coordinates, metres */
+    double err;                        /* object-space error of (R, t) */
+    double R_alt[9], t_alt[3];         /* the other minimum (zero when has_alt == 0) */
+    double err_alt;                    /* +inf when has_alt == 0 */
+    double H[9];                       /* pixel homography, tag square (the object corners / s) -> image, H[8] = 1 */
+} ck_tag_pose_t;
+
+/* n_iters 50, every tagsize 0.1651 (the reference's TAG_SIZE, chalkydri_sqpnp/src/lib.rs:38), cam all zero */
+void ck_tag_pose_params_default(ck_tag_pose_params_t *pp);
+/* Poses of caller detections: out[i] for dets[i].  dets and out may be host or device pointers (hipMemcpyDefault, as
+ * ck_process_* accepts).  CK_EINVAL: a null pointer, n < 0, fx / fy not finite or <= 0, cx / cy / a distortion coefficient
+ * not finite, a tagsize of one of the handle's families not finite or <= 0, n_iters outside 1..1000.
+ * CK_ECAPACITY: n > max_batch * 256 (the per-frame detection capacity).  The first call that needs them allocates the
+ * device buffers of the pose records (CK_ENOMEM when that fails); ck_create allocates nothing for them. */
+int ck_estimate_tag_poses(ck_handle_t *h, const ck_tag_pose_params_t *pp, const ck_detection_t *dets, int32_t n,
+                          ck_tag_pose_t *out);
+/* Poses of the detections the handle's last ck_detect_batch / ck_detect_batch_device / ck_detect_uploaded /
+ * ck_detect_ingested / ck_process_* call produced.  Those detections are still on the device, so only the pose records cross
+ * the bus.  out is [n][cap_per_frame] and counts[n] gets min(detections, cap_per_frame), the truncation ck_detect_* applies,
+ * with n = the frames of that call; the entries of a frame past its count are zero records.  out and counts may be host or
+ * device pointers.  Errors as ck_estimate_tag_poses, and CK_EINVAL for cap_per_frame < 1 or when the detection workspace
+ * holds no such call's result: no detect / process call since ck_create, a failed one, or a later call that rewrote the
+ * workspace: ck_clusters_batch and ck_quads_batch.  ck_upload_frames, ck_threshold_batch, ck_segment_batch,
+ * ck_quad_image_batch, ck_time_threshold_segment, ck_set_quad_sigma, ck_sqpnp_solve_batch, ck_gather_poses, the ck_cat_*
+ * and ck_ingest_write / ck_ingest_submit calls leave it as it is. */
+int ck_last_tag_poses(ck_handle_t *h, const ck_tag_pose_params_t *pp, ck_tag_pose_t *out, int32_t cap_per_frame,
+                      int32_t *counts);
+
 /* ---- multi-GPU: the final pose gather ----------------------------------------------------------------------------------
  * Frames shard over GPUs without any data-path collective (one handle, one process or host thread per GPU).  The only
  * exchange is the gather of the 64-byte records (the wire struct of crates/whacknet/src/lib.rs:43-66): ONE ncclAllGather
