@@ -85,6 +85,15 @@ class TagPose(C.Structure):
                 ("t_alt", C.c_double * 3), ("err_alt", C.c_double), ("H", C.c_double * 9)]
 
 
+class JpegFrame(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("size", C.c_int64)]
+
+
+class JpegInfo(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("width", "height", "n_components", "h_samp", "v_samp", "restart_interval", "has_dht",
+                                         "pad")]
+
+
 class VisionMeasurement(C.Structure):
     _fields_ = [("pose_x", C.c_double), ("pose_y", C.c_double), ("pose_rot", C.c_double),
                 ("std_x", C.c_double), ("std_y", C.c_double), ("std_rot", C.c_double), ("ts", C.c_uint64),
@@ -114,7 +123,11 @@ class SynthParams(C.Structure):
 
 assert C.sizeof(VisionMeasurement) == 64  # crates/whacknet/src/lib.rs:92-95
 assert C.sizeof(TagPoseParams) == 112 and C.sizeof(TagPose) == 296
+assert C.sizeof(JpegFrame) == 16 and C.sizeof(JpegInfo) == 32
 
 # per-frame status bits (include/chalkydri_hip.h)
 CK_FRAME_OK, CK_FRAME_POINTS_OVERFLOW, CK_FRAME_CLUSTERS_OVERFLOW, CK_FRAME_QUADS_OVERFLOW, CK_FRAME_DETS_OVERFLOW = 0, 1, 2, 4, 8
 CK_FRAME_UNVERIFIED_ID = 16
+
+# per-frame jpeg_status bits (ck_upload_jpeg / ck_jpeg_luma_batch)
+CK_JPEG_OK, CK_JPEG_UNSUPPORTED, CK_JPEG_GEOMETRY, CK_JPEG_CORRUPT = 0, 1, 2, 4

@@ -177,6 +177,7 @@ extern "C" void ck_destroy(ck_handle_t *h) {
     for (auto &st : h->fit_stream) if (st) (void)hipStreamSynchronize(st);
     if (h->seg_stream) (void)hipStreamSynchronize(h->seg_stream);
     ck_stage_free(h);
+    ck_jpeg_free(h);
     (void)ck_free_dev(h->d_frames); (void)ck_free_dev(h->d_qframes); (void)ck_free_dev(h->d_thresh); (void)ck_free_dev(h->d_labels);
     (void)ck_free_dev(h->d_tp_dets); (void)ck_free_dev(h->d_tp_out); (void)ck_free_dev(h->d_tp_counts);
     (void)ck_free_dev(h->d_groot); (void)ck_free_dev(h->d_gsize); (void)ck_free_dev(h->d_gscratch); (void)ck_free_dev(h->d_xband); (void)ck_free_dev(h->d_broots); (void)ck_free_dev(h->d_tile_count); (void)ck_free_dev(h->d_ring);

@@ -204,6 +204,8 @@ struct ck_handle {
     ck_detection_t *d_tp_dets; // caller detections staged for ck_estimate_tag_poses
     ck_tag_pose_t *d_tp_out;   // pose records
     int32_t *d_tp_counts;      // [max_batch] per-frame counts of ck_last_tag_poses
+    // baseline JPEG decode (ck_jpeg.hip, k_jpeg.hip): allocated by the first ck_upload_jpeg / ck_jpeg_luma_batch, grown on demand
+    struct ck_jpeg_ws *jpeg;
     bool fmerge_lds_allowed; // k_fmerge's dynamic LDS limit has been raised on this handle's device
 };
 
@@ -282,6 +284,7 @@ int ck_launch_prefilter(ck_handle *h, const uint8_t *frames, int stride, size_t 
 // workspace of the irregular stages (clusters / quads / decode)
 int ck_stage_alloc(ck_handle *h);
 void ck_stage_free(ck_handle *h);
+void ck_jpeg_free(ck_handle *h); // ck_jpeg.hip: the JPEG workspace
 int ck_stage_device_frames(ck_handle *h, const uint8_t *d_frames, int n, int stride, int64_t frame_pitch, const uint8_t **use,
                            int *use_stride, size_t *use_pitch);
 int ck_run_threshold_segment(ck_handle *h, const uint8_t *frames, int stride, size_t pitch, int n);

@@ -1,0 +1,71 @@
+// Baseline JPEG luma decode: what the host parse (ck_jpeg.hip) hands the device kernels (k_jpeg.hip).  DESIGN.md §4c.
+#ifndef CK_JPEG_H
+#define CK_JPEG_H
+
+#include <stdint.h>
+
+constexpr int CK_JPEG_SUB_BITS = 512;       // bits of scan one lane decodes speculatively (a subsequence)
+constexpr int CK_JPEG_FRAME_THREADS = 1024; // workgroup of k_jpeg_frame (one per frame)
+
+// One subsequence: a piece of at most CK_JPEG_SUB_BITS bits of one restart interval.  A decoder state packs
+// (bit position << 16) | (block slot in the MCU << 8) | (zig-zag index: 0 = the DC comes next).
+struct ck_jpeg_sub {
+    uint32_t start, end;  // bit range in the frame's unstuffed scan: the lane decodes every code that starts in it
+    uint32_t interval;    // restart interval it belongs to
+    uint32_t first;       // 1: the interval's first piece (its entry state is exact: slot 0, DC)
+    uint64_t entry;       // the state the last decode of the piece started from
+    uint64_t exit[2];     // the state it ended in (double-buffered across the synchronisation rounds)
+    uint32_t nb;          // blocks completed inside the piece (ending inside the interval)
+    uint32_t blk0;        // index in the interval of the block in progress at entry
+};
+static_assert(sizeof(ck_jpeg_sub) == 48, "subsequence record");
+
+// Canonical decode table of one DHT, libjpeg's layout: a 9-bit lookahead for the short codes, maxcode / valoff for the rest.
+struct ck_jpeg_huff {
+    uint16_t look[512];   // (length << 8) | symbol of the code the 9 bits start with; 0 = a longer code or none
+    int32_t maxcode[18];  // largest code of each length 1..16 (-1: none)
+    int32_t valoff[18];   // index into vals of the code c of length l = c + valoff[l]
+    uint8_t vals[256];
+};
+static_assert(sizeof(ck_jpeg_huff) % 16 == 0, "tables are copied as 16-byte units");
+
+// One frame of a call.  Offsets are into the call's device buffers.
+struct ck_jpeg_desc {
+    uint64_t raw_off;      // scan payload (the bytes after the SOS header up to the end of the frame) in the payload area; its
+                           // unstuffed copy lands at the same offset in d_compact.  16-byte aligned
+    uint64_t int_off;      // first entry of the frame's interval starts in d_int ([nint + 1] byte offsets in the compact stream)
+    uint64_t sub_off;      // first record of the frame's subsequences in d_sub
+    uint32_t raw_len;      // payload bytes (its region is raw_len + 4 rounded up to 16)
+    uint32_t status;       // CK_JPEG_* bits found by the host (non-zero: the frame is staged as zeros)
+    uint32_t sub_cap;      // subsequence records the frame may use
+    uint32_t nint;         // restart intervals (1 without DRI)
+    uint32_t restart;      // MCUs per interval (= nmcu without DRI)
+    uint32_t nmcu;         // MCUs of the scan
+    uint32_t mcux;         // MCUs per row
+    uint32_t bpm;          // blocks per MCU
+    uint32_t nyb;          // Y blocks per MCU (1 for grey)
+    uint32_t hs;           // Y blocks per MCU along x
+    uint32_t yblk_stride;  // Y blocks per row of the frame (mcux * hs)
+    uint32_t yblk_rows;    // Y block rows of the frame
+    uint32_t qt;           // index of Y's quantisation table in the quant area
+    uint16_t dc[3], ac[3]; // indices of the scan components' tables in the table area (unused entries 0)
+};
+
+// Device workspace of the JPEG path (ck_handle::jpeg), grown on demand (ck_jpeg.hip).
+struct ck_jpeg_ws {
+    uint8_t *h_stage; size_t stage_cap;     // pinned host staging: descriptors | Huffman tables | quant tables | payloads
+    uint8_t *d_in; size_t in_cap;           // its device copy
+    uint8_t *d_compact; size_t compact_cap; // unstuffed scans, at the payloads' offsets
+    uint32_t *d_int; size_t int_cap;        // interval starts
+    ck_jpeg_sub *d_sub; size_t sub_cap;     // subsequence records
+    int16_t *d_coef; size_t coef_cap;       // Y coefficients [frame][block][64], natural order
+    uint32_t *d_status;                     // [max_batch] final per-frame status
+    uint32_t *h_status;                     // pinned [max_batch]
+};
+
+struct ck_handle;
+// k_jpeg.hip: the per-frame decode and the IDCT of n described frames into the handle's staged frames (statuses in jpeg->d_status)
+int ck_launch_jpeg(ck_handle *h, int n, const ck_jpeg_desc *d_desc, const ck_jpeg_huff *d_huff, const int32_t *d_qt, const uint8_t *d_raw,
+                   size_t coef_frame_blocks);
+
+#endif

@@ -1,0 +1,419 @@
+// Baseline JPEG (MJPEG) luma decode: the host half.  Parses each frame's markers up to SOS (never an entropy-coded byte),
+// deduplicates the Huffman and quantisation tables of the batch, builds libjpeg's canonical decode tables, packs the frame
+// descriptors and the payloads into one pinned buffer and copies it with one asynchronous copy; k_jpeg.hip does the rest.
+#include <map>
+#include <new>
+#include <string.h>
+#include <vector>
+
+#include "ck_internal.h"
+#include "ck_jpeg.h"
+
+namespace {
+
+const uint8_t kNatural[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                              41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                              30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+// ITU-T T.81 Annex K.3: the tables a stream without DHT relies on (libjpeg's std_huff_tables), by [class][slot 0 / 1]
+const uint8_t kStdBits[2][2][17] = {
+    {{0, 0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, {0, 0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}},
+    {{0, 0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d}, {0, 0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77}}};
+const uint8_t kStdDcVals[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
+const uint8_t kStdAcLum[162] = {
+    0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81,
+    0x91, 0xa1, 0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18,
+    0x19, 0x1a, 0x25, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48,
+    0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75,
+    0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99,
+    0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3,
+    0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5,
+    0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa};
+const uint8_t kStdAcChr[162] = {
+    0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08,
+    0x14, 0x42, 0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25,
+    0xf1, 0x17, 0x18, 0x19, 0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47,
+    0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74,
+    0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97,
+    0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba,
+    0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe2, 0xe3, 0xe4,
+    0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa};
+
+struct HuffSpec {
+    bool present = false;
+    uint8_t bits[17] = {};  // codes of each length 1..16
+    uint8_t vals[256] = {};
+    int nvals = 0;
+};
+
+struct Parsed {
+    ck_jpeg_info_t info{};
+    int ncomp = 0;
+    int comp_id[3] = {}, comp_tq[3] = {};
+    int scan_td[3] = {}, scan_ta[3] = {};
+    bool qt_present[4] = {};
+    uint16_t qt[4][64] = {};  // natural order
+    HuffSpec dc[4], ac[4];
+    int64_t scan_off = 0;     // first byte after the SOS header
+};
+
+// libjpeg's jpeg_make_d_derived_tbl checks: at most 256 symbols, the codes fit their lengths with the all-ones code of every
+// length left unused, DC categories <= 15
+bool huff_ok(const HuffSpec &t, bool dc) {
+    int code = 0, p = 0;
+    for (int l = 1; l <= 16; l++) {
+        code += t.bits[l];
+        p += t.bits[l];
+        if (code >= (1 << l)) return false;
+        code <<= 1;
+    }
+    if (p != t.nvals || p > 256) return false;
+    if (dc)
+        for (int i = 0; i < p; i++)
+            if (t.vals[i] > 15) return false;
+    return true;
+}
+
+HuffSpec std_table(int cls, int slot) {
+    HuffSpec t;
+    t.present = true;
+    memcpy(t.bits, kStdBits[cls][slot], 17);
+    if (cls == 0) { memcpy(t.vals, kStdDcVals, 12); t.nvals = 12; }
+    else { memcpy(t.vals, slot ? kStdAcChr : kStdAcLum, 162); t.nvals = 162; }
+    return t;
+}
+
+int parse(const uint8_t *p, int64_t n, Parsed &P) {
+    if (!p || n < 4 || p[0] != 0xFF || p[1] != 0xD8) return CK_EINVAL;
+    int64_t i = 2;
+    bool sof = false;
+    int comp_h[3] = {}, comp_v[3] = {};
+    int restart = 0;
+    for (;;) {
+        while (i < n && p[i] != 0xFF) i++; // bytes between segments are skipped, as libjpeg skips them
+        while (i < n && p[i] == 0xFF) i++; // fill bytes
+        if (i >= n) return CK_EINVAL;      // header truncated before SOS
+        const int m = p[i++];
+        if (m == 0x00 || m == 0x01 || (m >= 0xD0 && m <= 0xD7)) continue; // no segment
+        if (m == 0xD8 || m == 0xD9) return CK_EINVAL;                      // SOI again / EOI before any scan
+        if (i + 2 > n) return CK_EINVAL;
+        const int seglen = (p[i] << 8) | p[i + 1];
+        if (seglen < 2 || i + seglen > n) return CK_EINVAL;
+        const uint8_t *s = p + i + 2;
+        const int sl = seglen - 2;
+        i += seglen;
+        if (m == 0xC0 || m == 0xC1) { // baseline / extended sequential, Huffman
+            if (sof || sl < 6) return CK_EINVAL;
+            sof = true;
+            const int prec = s[0], height = (s[1] << 8) | s[2], width = (s[3] << 8) | s[4], nf = s[5];
+            if (prec == 12) return CK_EUNSUPPORTED;
+            if (prec != 8) return CK_EINVAL;
+            if (width == 0 || nf == 0) return CK_EINVAL;
+            if (sl < 6 + 3 * nf) return CK_EINVAL;
+            if (height == 0) return CK_EUNSUPPORTED; // the height follows in a DNL marker
+            if (nf != 1 && nf != 3) return CK_EUNSUPPORTED;
+            P.ncomp = nf;
+            for (int c = 0; c < nf; c++) {
+                P.comp_id[c] = s[6 + 3 * c];
+                comp_h[c] = s[7 + 3 * c] >> 4;
+                comp_v[c] = s[7 + 3 * c] & 15;
+                P.comp_tq[c] = s[8 + 3 * c];
+                if (comp_h[c] < 1 || comp_h[c] > 4 || comp_v[c] < 1 || comp_v[c] > 4 || P.comp_tq[c] > 3) return CK_EINVAL;
+                for (int e = 0; e < c; e++)
+                    if (P.comp_id[e] == P.comp_id[c]) return CK_EINVAL;
+            }
+            if (comp_h[0] > 2 || comp_v[0] > 2) return CK_EUNSUPPORTED;
+            for (int c = 1; c < nf; c++)
+                if (comp_h[c] != 1 || comp_v[c] != 1) return CK_EUNSUPPORTED;
+            P.info.width = width; P.info.height = height; P.info.n_components = nf;
+            P.info.h_samp = comp_h[0]; P.info.v_samp = comp_v[0];
+        } else if ((m >= 0xC2 && m <= 0xCF) && m != 0xC4) { // progressive, lossless, hierarchical, arithmetic (and DAC)
+            return CK_EUNSUPPORTED;
+        } else if (m == 0xC4) { // DHT
+            int o = 0;
+            while (o < sl) {
+                const int tc = s[o] >> 4, th = s[o] & 15;
+                if (tc > 1 || th > 3 || o + 17 > sl) return CK_EINVAL;
+                HuffSpec t;
+                t.present = true;
+                int cnt = 0;
+                for (int l = 1; l <= 16; l++) { t.bits[l] = s[o + l]; cnt += t.bits[l]; }
+                if (cnt > 256 || o + 17 + cnt > sl) return CK_EINVAL;
+                memcpy(t.vals, s + o + 17, (size_t)cnt);
+                t.nvals = cnt;
+                if (!huff_ok(t, tc == 0)) return CK_EINVAL;
+                (tc ? P.ac : P.dc)[th] = t;
+                o += 17 + cnt;
+            }
+            P.info.has_dht = 1;
+        } else if (m == 0xDB) { // DQT
+            int o = 0;
+            while (o < sl) {
+                const int pq = s[o] >> 4, tq = s[o] & 15;
+                if (pq > 1 || tq > 3 || o + 1 + 64 * (pq + 1) > sl) return CK_EINVAL;
+                for (int k = 0; k < 64; k++)
+                    P.qt[tq][kNatural[k]] = pq ? (uint16_t)((s[o + 1 + 2 * k] << 8) | s[o + 2 + 2 * k]) : s[o + 1 + k];
+                P.qt_present[tq] = true;
+                o += 1 + 64 * (pq + 1);
+            }
+        } else if (m == 0xDD) { // DRI
+            if (sl != 2) return CK_EINVAL;
+            restart = (s[0] << 8) | s[1];
+        } else if (m == 0xDA) { // SOS
+            if (!sof || sl < 1) return CK_EINVAL;
+            const int ns = s[0];
+            if (ns < 1 || ns > 4 || sl < 1 + 2 * ns + 3) return CK_EINVAL;
+            int idx[4];
+            for (int c = 0; c < ns; c++) {
+                const int cs = s[1 + 2 * c], td = s[2 + 2 * c] >> 4, ta = s[2 + 2 * c] & 15;
+                if (td > 3 || ta > 3) return CK_EINVAL;
+                idx[c] = -1;
+                for (int e = 0; e < P.ncomp; e++)
+                    if (P.comp_id[e] == cs) idx[c] = e;
+                if (idx[c] < 0) return CK_EINVAL;
+                for (int e = 0; e < c; e++)
+                    if (idx[e] == idx[c]) return CK_EINVAL;
+                if (c < 3) { P.scan_td[c] = td; P.scan_ta[c] = ta; }
+            }
+            const int ss = s[1 + 2 * ns], se = s[2 + 2 * ns], ahal = s[3 + 2 * ns];
+            if (ss != 0 || se != 63 || ahal != 0) return CK_EINVAL; // a sequential scan's spectral selection / approximation
+            if (ns != P.ncomp) return CK_EUNSUPPORTED;               // non-interleaved scans (one scan per component, or Y missing)
+            for (int c = 0; c < ns; c++)
+                if (idx[c] != c) return CK_EINVAL;                   // scan components follow the frame's order
+            for (int c = 0; c < P.ncomp; c++) {
+                if (!P.qt_present[P.comp_tq[c]]) return CK_EINVAL;
+                // a missing table 0 / 1 is the standard one (libjpeg-turbo: jpeg_std_huff_table); 2 / 3 must have been sent
+                if (!P.dc[P.scan_td[c]].present && P.scan_td[c] > 1) return CK_EINVAL;
+                if (!P.ac[P.scan_ta[c]].present && P.scan_ta[c] > 1) return CK_EINVAL;
+            }
+            P.info.restart_interval = restart;
+            P.scan_off = i;
+            return CK_OK;
+        }
+        // APPn, COM and every other segment: skipped
+    }
+}
+
+// libjpeg's derived table (jdhuff.c: jpeg_make_d_derived_tbl) in the device layout
+void derive(const HuffSpec &t, ck_jpeg_huff &o) {
+    memset(&o, 0, sizeof o);
+    int code = 0, p = 0;
+    for (int l = 1; l <= 16; l++) {
+        if (t.bits[l]) {
+            o.valoff[l] = p - code;
+            for (int k = 0; k < t.bits[l]; k++, p++, code++)
+                if (l <= 9)
+                    for (int x = 0; x < (1 << (9 - l)); x++) o.look[(code << (9 - l)) | x] = (uint16_t)((l << 8) | t.vals[p]);
+            o.maxcode[l] = code - 1;
+        } else {
+            o.maxcode[l] = -1;
+        }
+        code <<= 1;
+    }
+    o.maxcode[17] = -1;
+    memcpy(o.vals, t.vals, 256);
+}
+
+size_t al16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+template <typename T>
+int grow_dev(T **p, size_t *cap, size_t need) {
+    if (need <= *cap) return CK_OK;
+    (void)ck_free_dev(*p);
+    *p = nullptr; *cap = 0;
+    const size_t want = need + need / 4;
+    hipError_t e = ck_malloc_dev(p, want);
+    if (e != hipSuccess) {
+        snprintf(ck_err_text, sizeof ck_err_text, "JPEG workspace (%zu bytes) failed: %s", want, hipGetErrorString(e));
+        (void)hipGetLastError();
+        *p = nullptr;
+        return e == hipErrorOutOfMemory ? CK_ENOMEM : CK_EDEVICE;
+    }
+    *cap = want;
+    return CK_OK;
+}
+
+int grow_host(uint8_t **p, size_t *cap, size_t need) {
+    if (need <= *cap) return CK_OK;
+    if (*p) (void)hipHostFree(*p);
+    *p = nullptr; *cap = 0;
+    const size_t want = need + need / 4;
+    hipError_t e = hipHostMalloc(reinterpret_cast<void **>(p), want, hipHostMallocDefault);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        *p = nullptr;
+        return CK_ENOMEM;
+    }
+    *cap = want;
+    return CK_OK;
+}
+
+int jpeg_run(ck_handle *h, const ck_jpeg_frame_t *frames, int n, uint32_t *jpeg_status) {
+    CK_HIP(hipSetDevice(h->device));
+    if (!h->jpeg) {
+        h->jpeg = new (std::nothrow) ck_jpeg_ws();
+        if (!h->jpeg) return CK_ENOMEM;
+        memset(h->jpeg, 0, sizeof *h->jpeg);
+        ck_jpeg_ws &J = *h->jpeg;
+        if (hipHostMalloc(reinterpret_cast<void **>(&J.h_status), sizeof(uint32_t) * (size_t)h->cfg.max_batch, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            J.h_status = nullptr;
+            ck_jpeg_free(h);
+            return CK_ENOMEM;
+        }
+        size_t cap = 0;
+        int rc = grow_dev(&J.d_status, &cap, sizeof(uint32_t) * (size_t)h->cfg.max_batch);
+        if (rc != CK_OK) { ck_jpeg_free(h); return rc; }
+    }
+    ck_jpeg_ws &J = *h->jpeg;
+    if (n == 0) {
+        h->n_staged = 0;
+        return CK_OK;
+    }
+    // ---- parse + deduplicate --------------------------------------------------------------------------------------------------
+    std::vector<Parsed> P((size_t)n);
+    std::vector<ck_jpeg_desc> D((size_t)n);
+    std::vector<ck_jpeg_huff> tabs;
+    std::vector<int32_t> qts;
+    std::map<std::vector<uint8_t>, int> tab_ix, qt_ix;
+    auto table_index = [&](const HuffSpec &t) {
+        std::vector<uint8_t> key(t.bits, t.bits + 17);
+        key.insert(key.end(), t.vals, t.vals + t.nvals);
+        auto it = tab_ix.find(key);
+        if (it != tab_ix.end()) return it->second;
+        tabs.emplace_back();
+        derive(t, tabs.back());
+        const int ix = (int)tabs.size() - 1;
+        tab_ix.emplace(std::move(key), ix);
+        return ix;
+    };
+    // the Y coefficient store of a frame: the largest MCU grid the handle's geometry can have (2 x 2 sampling)
+    const size_t coef_frame_blocks = (size_t)((h->w + 15) / 16) * 2 * (size_t)((h->h + 15) / 16) * 2;
+    uint64_t raw_total = 0, int_total = 0, sub_total = 0;
+    for (int f = 0; f < n; f++) {
+        Parsed &p = P[f];
+        ck_jpeg_desc &d = D[f];
+        memset(&d, 0, sizeof d);
+        const int rc = parse(frames[f].data, frames[f].size, p);
+        if (rc != CK_OK) { d.status = rc == CK_EUNSUPPORTED ? CK_JPEG_UNSUPPORTED : CK_JPEG_CORRUPT; continue; }
+        if (p.info.width != h->w || p.info.height != h->h) { d.status = CK_JPEG_GEOMETRY; continue; }
+        const int64_t raw_len = frames[f].size - p.scan_off;
+        if (raw_len > ((int64_t)1 << 28)) { d.status = CK_JPEG_UNSUPPORTED; continue; } // bit positions are 32-bit
+        const int H = p.ncomp == 1 ? 1 : p.info.h_samp, V = p.ncomp == 1 ? 1 : p.info.v_samp;
+        d.mcux = (uint32_t)((h->w + 8 * H - 1) / (8 * H));
+        const uint32_t mcuy = (uint32_t)((h->h + 8 * V - 1) / (8 * V));
+        d.nmcu = d.mcux * mcuy;
+        d.nyb = (uint32_t)(H * V);
+        d.bpm = p.ncomp == 1 ? 1u : d.nyb + 2;
+        d.hs = (uint32_t)H;
+        d.yblk_stride = d.mcux * H;
+        d.yblk_rows = mcuy * V;
+        d.restart = p.info.restart_interval ? (uint32_t)p.info.restart_interval : d.nmcu;
+        d.nint = (d.nmcu + d.restart - 1) / d.restart;
+        d.raw_len = (uint32_t)raw_len;
+        d.sub_cap = d.nint + (uint32_t)(((uint64_t)raw_len * 8 + CK_JPEG_SUB_BITS - 1) / CK_JPEG_SUB_BITS) + 1;
+        for (int c = 0; c < p.ncomp; c++) {
+            const HuffSpec &dc = p.dc[p.scan_td[c]].present ? p.dc[p.scan_td[c]] : std_table(0, p.scan_td[c]);
+            const HuffSpec &ac = p.ac[p.scan_ta[c]].present ? p.ac[p.scan_ta[c]] : std_table(1, p.scan_ta[c]);
+            d.dc[c] = (uint16_t)table_index(dc);
+            d.ac[c] = (uint16_t)table_index(ac);
+        }
+        {
+            const uint16_t *q = p.qt[p.comp_tq[0]];
+            std::vector<uint8_t> key(reinterpret_cast<const uint8_t *>(q), reinterpret_cast<const uint8_t *>(q) + 128);
+            auto it = qt_ix.find(key);
+            if (it == qt_ix.end()) {
+                it = qt_ix.emplace(std::move(key), (int)(qts.size() / 64)).first;
+                for (int k = 0; k < 64; k++) qts.push_back(q[k]);
+            }
+            d.qt = (uint32_t)it->second;
+        }
+        d.raw_off = raw_total;
+        raw_total += al16((size_t)raw_len + 4);
+        d.int_off = int_total;
+        int_total += d.nint + 1;
+        d.sub_off = sub_total;
+        sub_total += d.sub_cap;
+    }
+    if (tabs.empty()) tabs.emplace_back(); // (every frame bad: the kernels still get valid pointers)
+    if (qts.empty()) qts.assign(64, 0);
+    // ---- stage: descriptors | tables | quant tables | payloads -----------------------------------------------------------------
+    const size_t off_tab = al16(sizeof(ck_jpeg_desc) * (size_t)n);
+    const size_t off_qt = off_tab + sizeof(ck_jpeg_huff) * tabs.size();
+    const size_t off_raw = al16(off_qt + sizeof(int32_t) * qts.size());
+    const size_t total = off_raw + raw_total;
+    int rc = grow_host(&J.h_stage, &J.stage_cap, total);
+    if (rc == CK_OK) rc = grow_dev(&J.d_in, &J.in_cap, total);
+    if (rc == CK_OK) rc = grow_dev(&J.d_compact, &J.compact_cap, raw_total ? raw_total : 16);
+    if (rc == CK_OK) rc = grow_dev(&J.d_int, &J.int_cap, sizeof(uint32_t) * (int_total ? int_total : 1));
+    if (rc == CK_OK) rc = grow_dev(&J.d_sub, &J.sub_cap, sizeof(ck_jpeg_sub) * (sub_total ? sub_total : 1));
+    if (rc == CK_OK) rc = grow_dev(&J.d_coef, &J.coef_cap, sizeof(int16_t) * 64 * coef_frame_blocks * (size_t)n);
+    if (rc != CK_OK) return rc;
+    CK_HIP(hipStreamSynchronize(h->stream)); // (the staging buffer may still feed an earlier call's copy)
+    uint8_t *S = J.h_stage;
+    memcpy(S, D.data(), sizeof(ck_jpeg_desc) * (size_t)n);
+    memcpy(S + off_tab, tabs.data(), sizeof(ck_jpeg_huff) * tabs.size());
+    memcpy(S + off_qt, qts.data(), sizeof(int32_t) * qts.size());
+    for (int f = 0; f < n; f++) {
+        if (D[f].status) continue;
+        uint8_t *dst = S + off_raw + D[f].raw_off;
+        memcpy(dst, frames[f].data + P[f].scan_off, D[f].raw_len);
+        memset(dst + D[f].raw_len, 0, al16((size_t)D[f].raw_len + 4) - D[f].raw_len);
+    }
+    CK_HIP(hipMemcpyAsync(J.d_in, S, total, hipMemcpyHostToDevice, h->stream));
+    rc = ck_launch_jpeg(h, n, reinterpret_cast<const ck_jpeg_desc *>(J.d_in), reinterpret_cast<const ck_jpeg_huff *>(J.d_in + off_tab),
+                        reinterpret_cast<const int32_t *>(J.d_in + off_qt), J.d_in + off_raw, coef_frame_blocks);
+    if (rc != CK_OK) return rc;
+    CK_HIP(hipMemcpyAsync(J.h_status, J.d_status, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    CK_HIP(hipStreamSynchronize(h->stream));
+    if (jpeg_status) memcpy(jpeg_status, J.h_status, sizeof(uint32_t) * (size_t)n);
+    h->n_staged = n;
+    return CK_OK;
+}
+
+int check_frames(const ck_handle *h, const ck_jpeg_frame_t *frames, int32_t n) {
+    if (!h || !frames || n < 0) return CK_EINVAL;
+    if (n > h->cfg.max_batch) return CK_ECAPACITY;
+    for (int i = 0; i < n; i++)
+        if (!frames[i].data || frames[i].size < 4) return CK_EINVAL;
+    return CK_OK;
+}
+
+} // namespace
+
+void ck_jpeg_free(ck_handle *h) {
+    if (!h || !h->jpeg) return;
+    ck_jpeg_ws &J = *h->jpeg;
+    if (J.h_stage) (void)hipHostFree(J.h_stage);
+    if (J.h_status) (void)hipHostFree(J.h_status);
+    (void)ck_free_dev(J.d_in); (void)ck_free_dev(J.d_compact); (void)ck_free_dev(J.d_int); (void)ck_free_dev(J.d_sub);
+    (void)ck_free_dev(J.d_coef); (void)ck_free_dev(J.d_status);
+    delete h->jpeg;
+    h->jpeg = nullptr;
+}
+
+extern "C" int ck_jpeg_info(const uint8_t *data, int64_t size, ck_jpeg_info_t *out) {
+    if (!data || !out) return CK_EINVAL;
+    Parsed p;
+    const int rc = parse(data, size, p);
+    if (rc == CK_OK) *out = p.info;
+    return rc;
+}
+
+extern "C" int ck_upload_jpeg(ck_handle_t *h, const ck_jpeg_frame_t *frames, int32_t n, uint32_t *jpeg_status) {
+    const int rc = check_frames(h, frames, n);
+    if (rc != CK_OK) return rc;
+    return jpeg_run(h, frames, n, jpeg_status);
+}
+
+extern "C" int ck_jpeg_luma_batch(ck_handle_t *h, const ck_jpeg_frame_t *frames, int32_t n, uint8_t *luma_out, uint32_t *jpeg_status) {
+    if (!luma_out) return CK_EINVAL;
+    int rc = check_frames(h, frames, n);
+    if (rc != CK_OK) return rc;
+    rc = jpeg_run(h, frames, n, jpeg_status);
+    if (rc != CK_OK || n == 0) return rc;
+    CK_HIP(hipMemcpy2DAsync(luma_out, (size_t)h->w, h->d_frames, (size_t)h->frame_stride, (size_t)h->w, (size_t)h->h * n,
+                            hipMemcpyDeviceToHost, h->stream));
+    CK_HIP(hipStreamSynchronize(h->stream));
+    return CK_OK;
+}

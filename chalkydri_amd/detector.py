@@ -66,6 +66,9 @@ def _bind(L):
     L.ck_quad_image_batch.argtypes = [vp, _P(A.ImageU8), i32, vp]
     L.ck_estimate_tag_poses.argtypes = [vp, _P(A.TagPoseParams), vp, i32, vp]
     L.ck_last_tag_poses.argtypes = [vp, _P(A.TagPoseParams), vp, i32, vp]
+    L.ck_jpeg_info.argtypes = [vp, C.c_int64, _P(A.JpegInfo)]
+    L.ck_upload_jpeg.argtypes = [vp, _P(A.JpegFrame), i32, u32p]
+    L.ck_jpeg_luma_batch.argtypes = [vp, _P(A.JpegFrame), i32, vp, u32p]
     L._ck_bound = True
     return L
 
@@ -171,6 +174,24 @@ class TagPose:
         return f"TagPose(id={self.id}, valid={self.valid}, t={np.round(self._t, 4).tolist()}, err={self._err:.3g})"
 
 
+def _jpeg_frames(frames):
+    """bytes-like JPEG frames -> (ck_jpeg_frame_t array, keepalive)."""
+    keep = [np.frombuffer(bytes(f), np.uint8) for f in frames]
+    arr = (A.JpegFrame * max(len(keep), 1))()
+    for i, b in enumerate(keep):
+        arr[i].data, arr[i].size = b.ctypes.data, b.size
+    return arr, keep
+
+
+def jpeg_info(data):
+    """ck_jpeg_info: the header of one JPEG as a dict (width, height, n_components, h_samp, v_samp, restart_interval, has_dht).
+    Raises ChalkydriError with CK_EUNSUPPORTED for a valid JPEG outside the supported subset, CK_EINVAL for anything else."""
+    b = np.frombuffer(bytes(data), np.uint8)
+    info = A.JpegInfo()
+    check(_bind(lib()).ck_jpeg_info(b.ctypes.data if b.size else None, b.size, C.byref(info)), "ck_jpeg_info")
+    return {k: getattr(info, k) for k, _ in A.JpegInfo._fields_ if k != "pad"}
+
+
 def _raw_detections(dets):
     """Detection objects, ck_detection_t arrays or an [n] ctypes array -> ctypes array (+ count)."""
     if isinstance(dets, C.Array):
@@ -226,6 +247,23 @@ class AprilTagDetector:
         arr, keep = _images(frames)
         check(self._L.ck_upload_frames(self._h, arr, len(arr)), "ck_upload_frames")
         return len(arr)
+
+    def upload_jpeg(self, frames, return_status=False):
+        """Decodes the luma of baseline JPEG frames (bytes each) on the device into the staged frames, as `upload` stages raw
+        luma: detect_batch(None, n) / the process and pose calls follow.  A frame that is unsupported, of another size or
+        corrupt is staged as zeros; its CK_JPEG_* bits are in the status list (return_status=True)."""
+        arr, keep = _jpeg_frames(frames)
+        status = (C.c_uint32 * max(len(keep), 1))()
+        check(self._L.ck_upload_jpeg(self._h, arr, len(keep), status), "ck_upload_jpeg")
+        return (len(keep), list(status)[:len(keep)]) if return_status else len(keep)
+
+    def decode_jpeg(self, frames, return_status=False):
+        """[n][height][width] uint8: the luma the device decodes from the JPEG frames (bit-identical to libjpeg's islow IDCT)."""
+        arr, keep = _jpeg_frames(frames)
+        out = np.empty((len(keep), self.height, self.width), np.uint8)
+        status = (C.c_uint32 * max(len(keep), 1))()
+        check(self._L.ck_jpeg_luma_batch(self._h, arr, len(keep), out.ctypes.data, status), "ck_jpeg_luma_batch")
+        return (out, list(status)[:len(keep)]) if return_status else out
 
     # -- stages -------------------------------------------------------------------------------------------
     def threshold(self, frames=None, n=None):

@@ -153,6 +153,36 @@ inline std::vector<std::vector<TagPose>> last_tag_poses(Handle &h, const ck_tag_
     return r;
 }
 
+// ---- baseline JPEG (MJPEG) luma decode on the device (chalkydri_hip.h: ck_jpeg_info / ck_upload_jpeg / ck_jpeg_luma_batch) ----
+// The frames an `image/jpeg` appsink hands over (crates/chalkydri/src/cameras/pipeline.rs:43-44,123-124), decoded to the luma
+// the detector stages, bit-identical to libjpeg's islow IDCT.  Statuses are the CK_JPEG_* bits per frame.
+inline std::optional<ck_jpeg_info_t> jpeg_info(const std::vector<uint8_t> &jpeg) {
+    ck_jpeg_info_t info{};
+    if (ck_jpeg_info(jpeg.data(), (int64_t)jpeg.size(), &info) != CK_OK) return std::nullopt;
+    return info;
+}
+inline std::vector<ck_jpeg_frame_t> jpeg_frames(const std::vector<std::vector<uint8_t>> &jpegs) {
+    std::vector<ck_jpeg_frame_t> f;
+    for (const auto &j : jpegs) f.push_back({j.data(), (int64_t)j.size()});
+    return f;
+}
+// Stages the decoded luma (ck_detect_uploaded / ck_process_uploaded follow); returns the per-frame statuses.
+inline std::vector<uint32_t> upload_jpeg(Handle &h, const std::vector<std::vector<uint8_t>> &jpegs) {
+    std::vector<ck_jpeg_frame_t> f = jpeg_frames(jpegs);
+    std::vector<uint32_t> st(f.size());
+    check(ck_upload_jpeg(h.get(), f.data(), (int32_t)f.size(), st.data()), "ck_upload_jpeg");
+    return st;
+}
+// The same, and the luma itself: [n][height][width].
+inline std::vector<uint8_t> decode_jpeg(Handle &h, const std::vector<std::vector<uint8_t>> &jpegs, std::vector<uint32_t> *status = nullptr) {
+    std::vector<ck_jpeg_frame_t> f = jpeg_frames(jpegs);
+    std::vector<uint8_t> out((size_t)f.size() * h.config().width * h.config().height);
+    std::vector<uint32_t> st(f.size());
+    check(ck_jpeg_luma_batch(h.get(), f.data(), (int32_t)f.size(), out.data(), st.data()), "ck_jpeg_luma_batch");
+    if (status) *status = st;
+    return out;
+}
+
 namespace apriltags {
 
 enum class Color : uint8_t { Black = 0, White = 1, Other = 2 }; // src/utils.rs:2-6

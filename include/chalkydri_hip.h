@@ -410,6 +410,48 @@ int ck_estimate_tag_poses(ck_handle_t *h, const ck_tag_pose_params_t *pp, const 
 int ck_last_tag_poses(ck_handle_t *h, const ck_tag_pose_params_t *pp, ck_tag_pose_t *out, int32_t cap_per_frame,
                       int32_t *counts);
 
+/* ---- baseline JPEG (MJPEG) luma decode on the device ---------------------------------------------------------------------
+ * What the reference's camera layer would hand a `jpegdec` element (crates/chalkydri/src/cameras/pipeline.rs:43-44,123-124):
+ * one complete JPEG per frame.  The library decodes its luma on the device into the handle's staged frames, bit-identical to
+ * libjpeg's integer ("islow") IDCT — what a grayscale decode by libjpeg returns.  Supported: SOF0, and SOF1 at 8-bit precision,
+ * Huffman coded, one interleaved scan; 1 component, or 3 with Y first; Y sampling 1x1, 2x1, 1x2 or 2x2 with chroma at 1x1; DRI
+ * present or absent; 8- or 16-bit DQT; no DHT = the standard tables of ITU-T T.81 Annex K.3 (the UVC / AVI1 MJPEG convention).
+ * DESIGN.md §4c has the stages.  Workspace (allocated by the first JPEG call, grown on demand; ck_create allocates none of it):
+ * per frame of a call, the compressed bytes three times (pinned host staging, its device copy, the device's unstuffed copy),
+ * a 48-byte record per 512 bits of scan plus one per restart interval, 4 bytes per restart interval, and the Y coefficients at
+ * 2 bytes per pixel of the frame rounded up to whole 16 x 16 MCUs (2.0 MB for 1280 x 800). */
+typedef struct ck_jpeg_frame {
+    const uint8_t *data;     /* one complete JPEG (SOI..EOI) in host memory */
+    int64_t size;
+} ck_jpeg_frame_t;
+typedef struct ck_jpeg_info {
+    int32_t width, height, n_components;   /* 1 (grey) or 3 (Y first) */
+    int32_t h_samp, v_samp;                /* Y's sampling factors = Hmax, Vmax in {1,2} */
+    int32_t restart_interval;              /* MCUs, 0 = none */
+    int32_t has_dht;                       /* 0: stream relies on the standard tables (UVC/AVI1 MJPEG convention) */
+    int32_t pad;
+} ck_jpeg_info_t;
+/* per-frame jpeg_status bits */
+enum {
+    CK_JPEG_OK = 0,
+    CK_JPEG_UNSUPPORTED = 1, /* a valid JPEG outside the supported subset (what ck_jpeg_info answers with CK_EUNSUPPORTED) */
+    CK_JPEG_GEOMETRY = 2,    /* not the handle's width x height */
+    CK_JPEG_CORRUPT = 4      /* invalid Huffman code, AC run past coefficient 63, an interval that ends before its MCUs do,
+                              * a restart marker missing / out of sequence / in excess, or a header ck_jpeg_info refuses */
+};
+/* Parses markers up to SOS on the host (no device needed).  CK_OK, CK_EUNSUPPORTED (valid JPEG outside the supported subset:
+ * progressive, lossless, arithmetic coding, 12-bit, more than one scan, other sampling factors, a scan without Y),
+ * CK_EINVAL (null pointer, size < 4, not a JPEG, a truncated or inconsistent header). */
+int ck_jpeg_info(const uint8_t *data, int64_t size, ck_jpeg_info_t *out);
+/* Decodes the luma of n frames on the device into the handle's staged frames: after it, ck_detect_uploaded, ck_process_uploaded,
+ * ck_time_threshold_segment and ck_last_tag_poses work exactly as after ck_upload_frames.  A frame that is unsupported, has the
+ * wrong geometry or is corrupt is staged as all zeros and flagged in jpeg_status[n] (may be NULL); the call still returns CK_OK.
+ * CK_EINVAL: null handle or frames, n < 0, a frame with a null data pointer or size < 4.  CK_ECAPACITY: n > max_batch.
+ * CK_ENOMEM: the workspace could not grow.  Trailing bytes after the last MCU and after EOI are ignored. */
+int ck_upload_jpeg(ck_handle_t *h, const ck_jpeg_frame_t *frames, int32_t n, uint32_t *jpeg_status);
+/* The same, then copies the decoded luma out: luma_out is [n][height][width]. */
+int ck_jpeg_luma_batch(ck_handle_t *h, const ck_jpeg_frame_t *frames, int32_t n, uint8_t *luma_out, uint32_t *jpeg_status);
+
 /* ---- multi-GPU: the final pose gather ----------------------------------------------------------------------------------
  * Frames shard over GPUs without any data-path collective (one handle, one process or host thread per GPU).  The only
  * exchange is the gather of the 64-byte records (the wire struct of crates/whacknet/src/lib.rs:43-66): ONE ncclAllGather
