@@ -68,6 +68,12 @@ bool ck_guarded_free(void *p) {
 
 extern "C" const char *ck_last_error(void) { return ck_err_text; }
 
+int ck_hip_failed(hipError_t e, const char *call, const char *file, int line, bool alloc) {
+    snprintf(ck_err_text, sizeof ck_err_text, "%s failed: %s (%s:%d)", call, hipGetErrorString(e), file, line);
+    (void)hipGetLastError();
+    return alloc && e == hipErrorOutOfMemory ? CK_ENOMEM : CK_EDEVICE;
+}
+
 extern "C" int ck_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -101,6 +107,23 @@ static bool family_ok(const ck_family_t *f) {
     return true;
 }
 
+// streams, events and buffers of a new handle; what fails here for lack of memory is CK_ENOMEM, whichever call it is
+static int create_device_side(ck_handle *h) {
+    CK_HIP_ALLOC(hipSetDevice(h->device));
+    CK_HIP_ALLOC(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    CK_HIP_ALLOC(hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking));
+    for (auto &e : h->ev) CK_HIP_ALLOC(hipEventCreate(&e));
+    CK_HIP_ALLOC(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
+    CK_HIP_ALLOC(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
+    CK_HIP_ALLOC(hipEventCreateWithFlags(&h->ev_fit_fork, hipEventDisableTiming));
+    for (auto &st : h->fit_stream) CK_HIP_ALLOC(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    CK_HIP_ALLOC(hipStreamCreateWithFlags(&h->seg_stream, hipStreamNonBlocking));
+    for (auto &e : h->ev_seg) CK_HIP_ALLOC(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    CK_HIP_ALLOC(hipEventCreateWithFlags(&h->ev_seg_join, hipEventDisableTiming));
+    for (auto &e : h->ev_fit_join) CK_HIP_ALLOC(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    return ck_bufs_create(h);
+}
+
 extern "C" int ck_create(const ck_config_t *cfg, ck_handle_t **out) {
     if (!cfg || !out) return CK_EINVAL;
     *out = nullptr;
@@ -127,44 +150,8 @@ extern "C" int ck_create(const ck_config_t *cfg, ck_handle_t **out) {
     h->ring_len = (2 * ((size_t)h->tiles_y * qw + (size_t)h->tiles_x * qh) + 3) & ~(size_t)3; // frames stay 8-byte aligned
     h->frame_stride = round_up(cfg->width, 16);
     h->frame_pitch = (size_t)h->frame_stride * cfg->height;
-    const size_t nb = (size_t)cfg->max_batch;
-    int rc = CK_OK;
-    auto fail = [&](int code) { ck_destroy(h); return code; };
-#define CK_TRY(call)                                                                                  \
-    do {                                                                                              \
-        hipError_t e_ = (call);                                                                       \
-        if (e_ != hipSuccess) {                                                                       \
-            snprintf(ck_err_text, sizeof ck_err_text, "%s failed: %s", #call, hipGetErrorString(e_)); \
-            (void)hipGetLastError(); /* (not left behind for a later call's launch check) */         \
-            return fail(e_ == hipErrorOutOfMemory ? CK_ENOMEM : CK_EDEVICE);                          \
-        }                                                                                             \
-    } while (0)
-    CK_TRY(hipSetDevice(h->device));
-    CK_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    CK_TRY(hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking));
-    for (auto &e : h->ev) CK_TRY(hipEventCreate(&e));
-    CK_TRY(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-    CK_TRY(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
-    CK_TRY(hipEventCreateWithFlags(&h->ev_fit_fork, hipEventDisableTiming));
-    for (auto &st : h->fit_stream) CK_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    CK_TRY(hipStreamCreateWithFlags(&h->seg_stream, hipStreamNonBlocking));
-    for (auto &e : h->ev_seg) CK_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    CK_TRY(hipEventCreateWithFlags(&h->ev_seg_join, hipEventDisableTiming));
-    for (auto &e : h->ev_fit_join) CK_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    CK_TRY(ck_malloc_dev(&h->d_frames, h->frame_pitch * nb));
-    if (cfg->quad_decimate > 1) CK_TRY(ck_malloc_dev(&h->d_qframes, (size_t)round_up(qw, 16) * qh * nb));
-    CK_TRY(ck_malloc_dev(&h->d_thresh, h->npix * nb));
-    CK_TRY(ck_malloc_dev(&h->d_labels, h->npix * nb * sizeof(ck_label_t)));
-    CK_TRY(ck_malloc_dev(&h->d_groot, (size_t)h->broot_cap * nb * sizeof(uint32_t)));
-    CK_TRY(ck_malloc_dev(&h->d_gsize, (size_t)h->broot_cap * nb * sizeof(uint32_t)));
-    CK_TRY(ck_malloc_dev(&h->d_gscratch, 2 * (size_t)h->broot_cap * nb * sizeof(uint32_t)));
-    CK_TRY(ck_malloc_dev(&h->d_xband, 2 * (size_t)h->broot_cap * nb * sizeof(uint32_t)));
-    CK_TRY(ck_malloc_dev(&h->d_broots, 2 * (size_t)h->broot_cap * nb * sizeof(ck_border_root)));
-    CK_TRY(ck_malloc_dev(&h->d_tile_count, (size_t)h->tiles_x * h->tiles_y * nb * sizeof(uint32_t)));
-    CK_TRY(ck_malloc_dev(&h->d_ring, h->ring_len * nb * sizeof(uint16_t)));
-    rc = ck_stage_alloc(h);
-    if (rc != CK_OK) return fail(rc);
-#undef CK_TRY
+    const int rc = create_device_side(h);
+    if (rc != CK_OK) { ck_destroy(h); return rc; }
     *out = h;
     return CK_OK;
 }
@@ -176,11 +163,8 @@ extern "C" void ck_destroy(ck_handle_t *h) {
     if (h->stream2) (void)hipStreamSynchronize(h->stream2);
     for (auto &st : h->fit_stream) if (st) (void)hipStreamSynchronize(st);
     if (h->seg_stream) (void)hipStreamSynchronize(h->seg_stream);
-    ck_stage_free(h);
+    ck_bufs_free(h);
     ck_jpeg_free(h);
-    (void)ck_free_dev(h->d_frames); (void)ck_free_dev(h->d_qframes); (void)ck_free_dev(h->d_thresh); (void)ck_free_dev(h->d_labels);
-    (void)ck_free_dev(h->d_tp_dets); (void)ck_free_dev(h->d_tp_out); (void)ck_free_dev(h->d_tp_counts);
-    (void)ck_free_dev(h->d_groot); (void)ck_free_dev(h->d_gsize); (void)ck_free_dev(h->d_gscratch); (void)ck_free_dev(h->d_xband); (void)ck_free_dev(h->d_broots); (void)ck_free_dev(h->d_tile_count); (void)ck_free_dev(h->d_ring);
     for (auto &e : h->ev) if (e) (void)hipEventDestroy(e);
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
     if (h->ev_join) (void)hipEventDestroy(h->ev_join);
@@ -218,28 +202,30 @@ extern "C" int ck_upload_frames(ck_handle_t *h, const ck_image_u8_t *imgs, int32
 }
 
 // Makes d_frames hold a 16-byte aligned copy of caller-resident device frames when their layout is not directly usable.
-int ck_stage_device_frames(ck_handle *h, const uint8_t *d_frames, int n, int stride, int64_t frame_pitch, const uint8_t **use,
-                           int *use_stride, size_t *use_pitch) {
+int ck_stage_device_frames(ck_handle *h, const uint8_t *d_frames, int n, int stride, int64_t frame_pitch, ck_dev_image *use) {
     if (!d_frames || n < 0 || stride < h->w || frame_pitch < (int64_t)stride * h->h) return CK_EINVAL;
     if (n > h->cfg.max_batch) return CK_ECAPACITY;
     bool aligned = ((uintptr_t)d_frames % 16 == 0) && (stride % 16 == 0) && (frame_pitch % 16 == 0);
-    if (aligned) { *use = d_frames; *use_stride = stride; *use_pitch = (size_t)frame_pitch; return CK_OK; }
+    if (aligned) { *use = {d_frames, stride, (size_t)frame_pitch}; return CK_OK; }
     for (int i = 0; i < n; i++)
         CK_HIP(hipMemcpy2DAsync(h->d_frames + (size_t)i * h->frame_pitch, (size_t)h->frame_stride, d_frames + (size_t)i * frame_pitch,
                                 (size_t)stride, (size_t)h->w, (size_t)h->h, hipMemcpyDeviceToDevice, h->stream));
     h->n_staged = n;
-    *use = h->d_frames; *use_stride = h->frame_stride; *use_pitch = h->frame_pitch;
+    *use = ck_staged_image(h);
     return CK_OK;
 }
 
-// Runs decimate and / or the quad_sigma filter (if configured) + threshold + segment on n staged frames.
-int ck_run_threshold_segment(ck_handle *h, const uint8_t *frames, int stride, size_t pitch, int n) {
-    if (ck_quad_separate(h)) {
-        int rc = h->qf_ksz > 1 ? ck_launch_prefilter(h, frames, stride, pitch, n) : ck_launch_decimate(h, frames, stride, pitch, n);
-        if (rc != CK_OK) return rc;
-        return ck_launch_threshold_segment(h, h->d_qframes, round_up(h->qw, 16), (size_t)round_up(h->qw, 16) * h->qh, n);
-    }
-    return ck_launch_threshold_segment(h, frames, stride, pitch, n);
+// Q of n frames into d_qframes when the quad image is a buffer of its own: decimation and / or the quad_sigma filter
+static int make_quad_image(ck_handle *h, const ck_dev_image &img, int n) {
+    if (!ck_quad_separate(h)) return CK_OK;
+    return h->qf_ksz > 1 ? ck_launch_prefilter(h, img, n) : ck_launch_decimate(h, img, n);
+}
+
+// Runs that (if configured) + threshold + segment on n staged frames.
+int ck_run_threshold_segment(ck_handle *h, const ck_dev_image &img, int n) {
+    int rc = make_quad_image(h, img, n);
+    if (rc != CK_OK) return rc;
+    return ck_launch_threshold_segment(h, ck_quad_image(h, img), n);
 }
 
 static int stage_input(ck_handle *h, const ck_image_u8_t *imgs, int n) {
@@ -253,7 +239,7 @@ extern "C" int ck_threshold_batch(ck_handle_t *h, const ck_image_u8_t *imgs, int
     int rc = stage_input(h, imgs, n);
     if (rc != CK_OK) return rc;
     CK_HIP(hipSetDevice(h->device));
-    rc = ck_run_threshold_segment(h, h->d_frames, h->frame_stride, h->frame_pitch, n);
+    rc = ck_run_threshold_segment(h, ck_staged_image(h), n);
     if (rc != CK_OK) return rc;
     CK_HIP(hipMemcpyAsync(thresh_out, h->d_thresh, h->npix * (size_t)n, hipMemcpyDeviceToHost, h->stream));
     CK_HIP(hipStreamSynchronize(h->stream));
@@ -265,21 +251,23 @@ extern "C" int ck_segment_batch(ck_handle_t *h, const ck_image_u8_t *imgs, int32
     int rc = stage_input(h, imgs, n);
     if (rc != CK_OK) return rc;
     CK_HIP(hipSetDevice(h->device));
-    rc = ck_run_threshold_segment(h, h->d_frames, h->frame_stride, h->frame_pitch, n);
+    rc = ck_run_threshold_segment(h, ck_staged_image(h), n);
     if (rc != CK_OK) return rc;
     size_t total = h->npix * (size_t)n;
     uint32_t *d_canon = nullptr, *d_sizes = nullptr;
-    // (a failed allocation leaves the runtime's per-thread error behind: cleared, so that the next call's launch check does not meet it)
-    if (ck_malloc_dev(&d_canon, total * sizeof(uint32_t)) != hipSuccess) { (void)hipGetLastError(); return CK_ENOMEM; }
-    if (sizes_out && ck_malloc_dev(&d_sizes, total * sizeof(uint32_t)) != hipSuccess) { (void)ck_free_dev(d_canon); (void)hipGetLastError(); return CK_ENOMEM; }
-    rc = ck_launch_canonical_labels(h, n, d_canon, d_sizes);
-    if (rc == CK_OK) {
-        hipError_t e = hipMemcpyAsync(labels_out, d_canon, total * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess && sizes_out) e = hipMemcpyAsync(sizes_out, d_sizes, total * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) { snprintf(ck_err_text, sizeof ck_err_text, "segment D2H failed: %s", hipGetErrorString(e)); rc = CK_EDEVICE; }
-    }
-    (void)ck_free_dev(d_canon); (void)ck_free_dev(d_sizes);
+    auto fetch = [&]() -> int {
+        int r = ck_launch_canonical_labels(h, n, d_canon, d_sizes);
+        if (r != CK_OK) return r;
+        CK_HIP(hipMemcpyAsync(labels_out, d_canon, total * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+        if (sizes_out) CK_HIP(hipMemcpyAsync(sizes_out, d_sizes, total * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+        CK_HIP(hipStreamSynchronize(h->stream));
+        return CK_OK;
+    };
+    hipError_t e = ck_malloc_dev(&d_canon, total * sizeof(uint32_t));
+    if (e == hipSuccess && sizes_out) e = ck_malloc_dev(&d_sizes, total * sizeof(uint32_t));
+    if (e == hipSuccess) rc = fetch();
+    else { (void)ck_hip_failed(e, "ck_malloc_dev(label arrays)", __FILE__, __LINE__, true); rc = CK_ENOMEM; } // (here any failed allocation is CK_ENOMEM)
+    (void)ck_free_dev(d_canon); (void)ck_free_dev(d_sizes); // one exit: nothing leaks on an error path
     return rc;
 }
 
@@ -291,14 +279,8 @@ extern "C" int ck_set_quad_sigma(ck_handle_t *h, float sigma) {
     if (rc != CK_OK) return rc;
     if (ksz > 1 && !h->d_qframes) { // quad_decimate 1: the quad image becomes a buffer of its own the first time the filter is on
         CK_HIP(hipSetDevice(h->device));
-        const size_t bytes = (size_t)round_up(h->qw, 16) * h->qh * (size_t)h->cfg.max_batch;
-        hipError_t e = ck_malloc_dev(&h->d_qframes, bytes);
-        if (e != hipSuccess) {
-            snprintf(ck_err_text, sizeof ck_err_text, "quad image allocation (%zu bytes) failed: %s", bytes, hipGetErrorString(e));
-            (void)hipGetLastError();
-            h->d_qframes = nullptr;
-            return e == hipErrorOutOfMemory ? CK_ENOMEM : CK_EDEVICE;
-        }
+        rc = ck_buf_alloc(h, &h->d_qframes);
+        if (rc != CK_OK) return rc;
     }
     h->quad_sigma = sigma;
     h->qf_ksz = ksz;
@@ -312,16 +294,11 @@ extern "C" int ck_quad_image_batch(ck_handle_t *h, const ck_image_u8_t *imgs, in
     if (rc != CK_OK) return rc;
     if (n == 0) return CK_OK;
     CK_HIP(hipSetDevice(h->device));
-    const uint8_t *q = h->d_frames;
-    size_t qstride = (size_t)h->frame_stride, qpitch = h->frame_pitch;
-    if (ck_quad_separate(h)) {
-        rc = h->qf_ksz > 1 ? ck_launch_prefilter(h, h->d_frames, h->frame_stride, h->frame_pitch, n)
-                           : ck_launch_decimate(h, h->d_frames, h->frame_stride, h->frame_pitch, n);
-        if (rc != CK_OK) return rc;
-        q = h->d_qframes; qstride = (size_t)round_up(h->qw, 16); qpitch = qstride * h->qh;
-    }
+    rc = make_quad_image(h, ck_staged_image(h), n);
+    if (rc != CK_OK) return rc;
+    const ck_dev_image q = ck_quad_image(h, ck_staged_image(h));
     for (int i = 0; i < n; i++)
-        CK_HIP(hipMemcpy2DAsync(out + (size_t)i * h->npix, (size_t)h->qw, q + (size_t)i * qpitch, qstride, (size_t)h->qw, (size_t)h->qh,
+        CK_HIP(hipMemcpy2DAsync(out + (size_t)i * h->npix, (size_t)h->qw, q.p + (size_t)i * q.pitch, (size_t)q.stride, (size_t)h->qw, (size_t)h->qh,
                                 hipMemcpyDeviceToHost, h->stream));
     CK_HIP(hipStreamSynchronize(h->stream));
     return CK_OK;
@@ -330,11 +307,11 @@ extern "C" int ck_quad_image_batch(ck_handle_t *h, const ck_image_u8_t *imgs, in
 extern "C" int ck_time_threshold_segment(ck_handle_t *h, int32_t n, int32_t iters, float *ms_out) {
     if (!h || !ms_out || iters < 1 || n < 1 || n > h->n_staged) return CK_EINVAL;
     CK_HIP(hipSetDevice(h->device));
-    int rc = ck_run_threshold_segment(h, h->d_frames, h->frame_stride, h->frame_pitch, n); // warm-up
+    int rc = ck_run_threshold_segment(h, ck_staged_image(h), n); // warm-up
     if (rc != CK_OK) return rc;
     CK_HIP(hipEventRecord(h->ev[0], h->stream));
     for (int i = 0; i < iters; i++) {
-        rc = ck_run_threshold_segment(h, h->d_frames, h->frame_stride, h->frame_pitch, n);
+        rc = ck_run_threshold_segment(h, ck_staged_image(h), n);
         if (rc != CK_OK) return rc;
     }
     CK_HIP(hipEventRecord(h->ev[1], h->stream));
@@ -371,17 +348,18 @@ extern "C" int ck_selftest_fp64(ck_handle_t *h, int32_t op, const double *a, con
     if (n == 0) return CK_OK;
     double *da = nullptr, *db = nullptr, *dout = nullptr;
     const size_t bytes = sizeof(double) * (size_t)n;
-    hipError_t e = ck_malloc_dev(&da, bytes);
-    if (e == hipSuccess) e = ck_malloc_dev(&dout, bytes);
-    if (e == hipSuccess && b) e = ck_malloc_dev(&db, bytes);
-    if (e == hipSuccess) e = hipMemcpy(da, a, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess && b) e = hipMemcpy(db, b, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
+    auto run = [&]() -> int { // (every failure of the probe, its allocations included, is CK_EDEVICE)
+        CK_HIP(ck_malloc_dev(&da, bytes));
+        CK_HIP(ck_malloc_dev(&dout, bytes));
+        if (b) CK_HIP(ck_malloc_dev(&db, bytes));
+        CK_HIP(hipMemcpy(da, a, bytes, hipMemcpyHostToDevice));
+        if (b) CK_HIP(hipMemcpy(db, b, bytes, hipMemcpyHostToDevice));
         hipLaunchKernelGGL(k_fp64_probe, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, op, da, db, n, dout);
-        e = hipStreamSynchronize(h->stream);
-    }
-    if (e == hipSuccess) e = hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost);
+        CK_HIP(hipStreamSynchronize(h->stream));
+        CK_HIP(hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost));
+        return CK_OK;
+    };
+    const int rc = run();
     (void)ck_free_dev(da); (void)ck_free_dev(db); (void)ck_free_dev(dout); // one exit: nothing leaks on an error path
-    if (e != hipSuccess) { snprintf(ck_err_text, sizeof ck_err_text, "fp64 probe failed: %s", hipGetErrorString(e)); return CK_EDEVICE; }
-    return CK_OK;
+    return rc;
 }

@@ -99,7 +99,7 @@ extern "C" int ck_detect_ingested(ck_ingest_t *g, int32_t slot, int32_t n, ck_de
     ck_handle *h = g->h;
     CK_HIP(hipSetDevice(h->device));
     CK_HIP(hipStreamWaitEvent(h->stream, g->ready[slot], 0));
-    return ck_detect_frames(h, g->dev[slot], h->frame_stride, h->frame_pitch, n, dets, cap, counts, status);
+    return ck_detect_frames(h, {g->dev[slot], h->frame_stride, h->frame_pitch}, n, dets, cap, counts, status);
 }
 
 extern "C" int ck_process_ingested(ck_ingest_t *g, int32_t slot, int32_t n, const ck_process_params_t *pp, const double *gyro,
@@ -109,5 +109,5 @@ extern "C" int ck_process_ingested(ck_ingest_t *g, int32_t slot, int32_t n, cons
     ck_handle *h = g->h;
     CK_HIP(hipSetDevice(h->device));
     CK_HIP(hipStreamWaitEvent(h->stream, g->ready[slot], 0));
-    return ck_process_frames(h, g->dev[slot], h->frame_stride, h->frame_pitch, n, pp, gyro, has_gyro, out, valid);
+    return ck_process_frames(h, {g->dev[slot], h->frame_stride, h->frame_pitch}, n, pp, gyro, has_gyro, out, valid);
 }

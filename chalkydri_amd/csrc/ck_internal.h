@@ -196,6 +196,7 @@ struct ck_handle {
     ck_stage_ws ws;      // workspace of clusters / quads / decode
     ck_stage_ms_t last_ms;
     ck_dev_family *d_fams;
+    uint64_t *d_fam_codes; // every family's code table, one after the other (ck_dev_family::codes point into it)
     int n_staged;        // frames currently staged in d_frames
     int n_last_pose;     // records the last ck_process_* call left in ws.d_meas (what ck_gather_poses may send); -1: none yet
     int n_last_dets;     // frames whose detections the last ck_detect_* / ck_process_* call left in ws (what ck_last_tag_poses reads);
@@ -210,16 +211,16 @@ struct ck_handle {
 };
 
 extern thread_local char ck_err_text[512];
-#define CK_HIP(call)                                                                                       \
-    do {                                                                                                    \
-        hipError_t e_ = (call);                                                                             \
-        if (e_ != hipSuccess) {                                                                             \
-            snprintf(ck_err_text, sizeof ck_err_text, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), \
-                     __FILE__, __LINE__);                                                                   \
-            (void)hipGetLastError(); /* the runtime keeps the error per thread: the next launch check must not meet it */ \
-            return CK_EDEVICE;                                                                              \
-        }                                                                                                   \
+// The one path of a failed runtime call (ck_api.hip): writes ck_err_text, clears the runtime's per-thread error (the next launch
+// check must not meet it) and gives the code: CK_ENOMEM for an allocation that failed for lack of memory, CK_EDEVICE otherwise.
+int ck_hip_failed(hipError_t e, const char *call, const char *file, int line, bool alloc);
+#define CK_HIP_(call, alloc)                                                              \
+    do {                                                                                  \
+        hipError_t e_ = (call);                                                           \
+        if (e_ != hipSuccess) return ck_hip_failed(e_, #call, __FILE__, __LINE__, alloc); \
     } while (0)
+#define CK_HIP(call) CK_HIP_(call, false)
+#define CK_HIP_ALLOC(call) CK_HIP_(call, true)
 
 // Diagnostic knobs (CK_TILE_STOP_AFTER, CK_FIT_SKIP, CK_FMERGE_CAP, ...: kernels cut short, classes skipped, paths forced, launch
 // geometry varied) exist only in the -DCK_DIAG build (`make diag` -> chalkydri_amd/lib/diag/libchalkydri_hip.so), which the
@@ -244,6 +245,17 @@ static inline bool ck_quad_separate(const ck_handle *h) { return h->cfg.quad_dec
 // Edge refinement and decode read the quad image instead of the frame: at quad_decimate 1 with the filter on (upstream blurs the
 // caller's image in place there, so its later stages see the filtered pixels).  The one routing predicate.
 static inline bool ck_refine_reads_quad(const ck_handle *h) { return h->cfg.quad_decimate == 1 && h->qf_ksz > 1; }
+// n frames of 8-bit pixels on the device: row i of frame f starts at p + f * pitch + i * stride
+struct ck_dev_image { const uint8_t *p; int stride; size_t pitch; };
+static inline ck_dev_image ck_staged_image(const ck_handle *h) { return {h->d_frames, h->frame_stride, h->frame_pitch}; }
+// d_qframes as an image (rows padded to 16 bytes), whether or not the quad stages use it at the moment: the one place its pitch is
+static inline ck_dev_image ck_qframes_image(const ck_handle *h) {
+    const int stride = (h->qw + 15) / 16 * 16;
+    return {h->d_qframes, stride, (size_t)stride * h->qh};
+}
+// the image the quad stages (threshold .. quad fit) read, and the one edge refinement and decode read, for the input image `in`
+static inline ck_dev_image ck_quad_image(const ck_handle *h, const ck_dev_image &in) { return ck_quad_separate(h) ? ck_qframes_image(h) : in; }
+static inline ck_dev_image ck_refine_image(const ck_handle *h, const ck_dev_image &in) { return ck_refine_reads_quad(h) ? ck_qframes_image(h) : in; }
 
 // Device allocation of the handle's buffers.  CK_POISON=1 (tests) fills every buffer with 0xA5 bytes, so that a kernel which
 // reads an entry nobody wrote in this call — what an undersized capacity once made of the cluster and run tables — meets the
@@ -272,32 +284,39 @@ static inline hipError_t ck_free_dev(const void *p) {
     if (p && ck_guarded_free(const_cast<void *>(p))) return hipSuccess;
     return hipFree(const_cast<void *>(p));
 }
+// a temporary of one call (plain hipMalloc: not handle workspace)
+template <typename T>
+struct DevBuf {
+    T *p = nullptr;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    int alloc(size_t n) { return hipMalloc(&p, sizeof(T) * (n ? n : 1)) == hipSuccess ? CK_OK : CK_ENOMEM; }
+};
 
 // ---- stage launchers (k_*.hip) ------------------------------------------------------------------------
 // threshold + tile-local CCL + cross-tile merge + border-root flatten, on frames [0,n) of `frames`
-int ck_launch_threshold_segment(ck_handle *h, const uint8_t *frames, int stride, size_t frame_pitch, int n, bool precomputed = false);
+int ck_launch_threshold_segment(ck_handle *h, const ck_dev_image &img, int n, bool precomputed = false);
 // canonical labels (min pixel index, flags stripped) and exact sizes — parity/test path, not the hot path
 int ck_launch_canonical_labels(ck_handle *h, int n, uint32_t *d_labels_out, uint32_t *d_sizes_out);
-int ck_launch_decimate(ck_handle *h, const uint8_t *frames, int stride, size_t frame_pitch, int n);
+int ck_launch_decimate(ck_handle *h, const ck_dev_image &img, int n);
 // quad_sigma filter (+ decimation at quad_decimate 2) of frames [0,n) into d_qframes (k_prefilter.hip)
-int ck_launch_prefilter(ck_handle *h, const uint8_t *frames, int stride, size_t frame_pitch, int n);
-// workspace of the irregular stages (clusters / quads / decode)
-int ck_stage_alloc(ck_handle *h);
-void ck_stage_free(ck_handle *h);
+int ck_launch_prefilter(ck_handle *h, const ck_dev_image &img, int n);
+// The handle's device buffers, all of them described once by the table in ck_stages.hip: capacities + every buffer ck_create
+// allocates; one buffer that is allocated on first use (`member` = the address of its pointer in the handle; a no-op once it
+// exists); all of them released
+int ck_bufs_create(ck_handle *h);
+int ck_buf_alloc(ck_handle *h, const void *member);
+void ck_bufs_free(ck_handle *h);
 void ck_jpeg_free(ck_handle *h); // ck_jpeg.hip: the JPEG workspace
-int ck_stage_device_frames(ck_handle *h, const uint8_t *d_frames, int n, int stride, int64_t frame_pitch, const uint8_t **use,
-                           int *use_stride, size_t *use_pitch);
-int ck_run_threshold_segment(ck_handle *h, const uint8_t *frames, int stride, size_t pitch, int n);
+int ck_stage_device_frames(ck_handle *h, const uint8_t *d_frames, int n, int stride, int64_t frame_pitch, ck_dev_image *use);
+int ck_run_threshold_segment(ck_handle *h, const ck_dev_image &img, int n);
 // gradient clusters from thresh/labels/csize of frames [0,n)
 int ck_launch_clusters(ck_handle *h, int n);
 // quad fit (+ edge refinement) of every cluster; qframes = image the clusters came from, frames = full resolution
-int ck_launch_fit_quads(ck_handle *h, const uint8_t *qframes, int qstride, size_t qpitch, const uint8_t *frames, int stride,
-                        size_t pitch, int n);
-int ck_launch_decode(ck_handle *h, const uint8_t *frames, int stride, size_t pitch, int n);
+int ck_launch_fit_quads(ck_handle *h, const ck_dev_image &qimg, const ck_dev_image &img, int n);
+int ck_launch_decode(ck_handle *h, const ck_dev_image &img, int n);
 // whole pipeline on device-resident frames (16-byte aligned rows): detections to the host / pose records
-int ck_detect_frames(ck_handle *h, const uint8_t *frames, int stride, size_t pitch, int n, ck_detection_t *dets, int cap, int32_t *counts,
-                     uint32_t *status);
-int ck_process_frames(ck_handle *h, const uint8_t *frames, int stride, size_t pitch, int n, const ck_process_params_t *pp, const double *gyro,
+int ck_detect_frames(ck_handle *h, const ck_dev_image &img, int n, ck_detection_t *dets, int cap, int32_t *counts, uint32_t *status);
+int ck_process_frames(ck_handle *h, const ck_dev_image &img, int n, const ck_process_params_t *pp, const double *gyro,
                       const uint8_t *has_gyro, ck_vision_measurement_t *out, int32_t *valid);
 // glue + SQPnP + measurement on the detections left on the device by the last pipeline run
 int ck_run_pose(ck_handle *h, int n, const ck_process_params_t *pp, const double *gyro, const uint8_t *has_gyro,

@@ -222,13 +222,7 @@ int grow_dev(T **p, size_t *cap, size_t need) {
     (void)ck_free_dev(*p);
     *p = nullptr; *cap = 0;
     const size_t want = need + need / 4;
-    hipError_t e = ck_malloc_dev(p, want);
-    if (e != hipSuccess) {
-        snprintf(ck_err_text, sizeof ck_err_text, "JPEG workspace (%zu bytes) failed: %s", want, hipGetErrorString(e));
-        (void)hipGetLastError();
-        *p = nullptr;
-        return e == hipErrorOutOfMemory ? CK_ENOMEM : CK_EDEVICE;
-    }
+    CK_HIP_ALLOC(ck_malloc_dev(p, want));
     *cap = want;
     return CK_OK;
 }

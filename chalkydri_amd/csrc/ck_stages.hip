@@ -1,4 +1,5 @@
-// ck_stages.hip — workspace of the irregular stages and the detect / clusters / quads entry points.
+// ck_stages.hip — the handle's device buffers (one table: allocation, release, the views of a split batch, the names CK_POISON=2
+// prints) and the detect / clusters / quads / process entry points.
 #include <string.h>
 
 #include <vector>
@@ -7,18 +8,114 @@
 
 static int next_pow2(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 
-// an allocation that fails for lack of memory is CK_ENOMEM, as in ck_create (not the CK_EDEVICE of a runtime failure)
-#define CK_ALLOC(call)                                                                                     \
-    do {                                                                                                    \
-        hipError_t e_ = (call);                                                                             \
-        if (e_ != hipSuccess) {                                                                             \
-            snprintf(ck_err_text, sizeof ck_err_text, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), \
-                     __FILE__, __LINE__);                                                                   \
-            (void)hipGetLastError();                                                                        \
-            return e_ == hipErrorOutOfMemory ? CK_ENOMEM : CK_EDEVICE;                                      \
-        }                                                                                                   \
-    } while (0)
-int ck_stage_alloc(ck_handle *h) {
+// ---- the handle's device buffers ---------------------------------------------------------------------------------------------
+// Every device buffer of ck_handle / ck_stage_ws is one row of ck_bufs[]: allocation (ck_bufs_create in this order; ck_buf_alloc
+// for the ones allocated on first use), release (ck_bufs_free), the per-frame advance of a split batch's views (make_view) and
+// the name CK_POISON=2 prints all walk this table.  A new buffer is a member + a row; ck_jpeg_ws (grown per call) keeps its own.
+enum : unsigned {
+    CK_BUF_FRAME = 1, // [max_batch][bytes]: a view of the frames from f0 on starts f0 * bytes further
+    CK_BUF_TWIN = 2,  // [2][bytes], per handle: the second copy is the one the pieces on stream2 use
+    CK_BUF_LAZY = 4,  // not allocated by ck_create (d_qframes: at quad_decimate 2 it is)
+    CK_BUF_ALIAS = 8, // the row before it seen as another type: same storage, same pitch in bytes; not allocated, not freed
+};
+struct ck_buf_desc {
+    const char *name;
+    size_t member;                     // offsetof(ck_handle, the pointer)
+    unsigned flags;                    // (none: one array of `bytes` per handle)
+    size_t (*bytes)(const ck_handle *); // per frame / per copy / in all; 0: this handle has no such buffer
+};
+#define CK_BUF(member, flags, expr) \
+    {#member, offsetof(ck_handle, member), flags, [](const ck_handle *h) -> size_t { const ck_stage_ws &w = h->ws; (void)w; return (size_t)(expr); }}
+static size_t fam_codes_bytes(const ck_handle *h) {
+    size_t n = 0;
+    for (int f = 0; f < h->cfg.n_families; f++) n += h->cfg.families[f]->ncodes;
+    return n * sizeof(uint64_t);
+}
+static constexpr ck_buf_desc ck_bufs[] = {
+    CK_BUF(d_frames, CK_BUF_FRAME, h->frame_pitch),
+    CK_BUF(d_qframes, CK_BUF_FRAME | CK_BUF_LAZY, ck_qframes_image(h).pitch),
+    CK_BUF(d_thresh, CK_BUF_FRAME, h->npix),
+    CK_BUF(d_labels, CK_BUF_FRAME, h->npix * sizeof(ck_label_t)),
+    CK_BUF(d_groot, CK_BUF_FRAME, h->broot_cap * sizeof(uint32_t)),
+    CK_BUF(d_gsize, CK_BUF_FRAME, h->broot_cap * sizeof(uint32_t)),
+    CK_BUF(d_gscratch, CK_BUF_FRAME, 2 * h->broot_cap * sizeof(uint32_t)),
+    CK_BUF(d_xband, CK_BUF_FRAME, 2 * h->broot_cap * sizeof(uint32_t)),
+    CK_BUF(d_broots, CK_BUF_FRAME, 2 * h->broot_cap * sizeof(ck_border_root)),
+    CK_BUF(d_tile_count, CK_BUF_FRAME, (size_t)h->tiles_x * h->tiles_y * sizeof(uint32_t)),
+    CK_BUF(d_ring, CK_BUF_FRAME, h->ring_len * sizeof(uint16_t)),
+    CK_BUF(ws.d_ht_keys, CK_BUF_FRAME, w.ht_size * sizeof(unsigned long long)),
+    CK_BUF(ws.d_ht_count, CK_BUF_FRAME, w.ht_size * sizeof(uint32_t)),
+    CK_BUF(ws.d_ht_off, CK_BUF_FRAME, w.ht_size * sizeof(uint32_t)),
+    CK_BUF(ws.d_tmp, CK_BUF_FRAME, w.ext_cap * sizeof(ck_packed_point)),
+    CK_BUF(ws.d_ext_xy, CK_BUF_FRAME | CK_BUF_ALIAS, w.ext_cap * sizeof(uint32_t)),
+    CK_BUF(ws.d_points, CK_BUF_FRAME, w.ext_cap * sizeof(ck_packed_point)),
+    CK_BUF(ws.d_maxval, CK_BUF_FRAME | CK_BUF_ALIAS, (w.ext_cap / 2) * sizeof(double)),
+    CK_BUF(ws.d_ext_w, CK_BUF_FRAME, w.ext_cap * sizeof(uint16_t)),
+    CK_BUF(ws.d_maxpos, CK_BUF_FRAME, (w.ext_cap / 2) * sizeof(uint16_t)),
+    CK_BUF(ws.d_maxmask, CK_BUF_FRAME, (w.ext_cap / 64) * sizeof(unsigned long long)),
+    CK_BUF(ws.d_maxpre, CK_BUF_FRAME, (w.ext_cap / 64) * sizeof(uint16_t)),
+    CK_BUF(ws.d_blk, CK_BUF_FRAME, 6 * (size_t)(w.ext_cap / 32) * sizeof(long long)),
+    CK_BUF(ws.d_cstate, CK_BUF_FRAME, 2 * w.cluster_cap * sizeof(uint32_t)),
+    CK_BUF(ws.d_runs, CK_BUF_FRAME, w.run_cap * sizeof(ck_run)),
+    CK_BUF(ws.d_lscratch, CK_BUF_TWIN, sizeof(unsigned long long) * CK_LSCRATCH_PER_WG * CK_LSCRATCH_WGS),
+    // (1920 x 1080: 18 432 points, 144 MiB instead of the 512 MiB of the class's template capacity)
+    CK_BUF(ws.d_hscratch, CK_BUF_TWIN, w.max_cluster_points > 16384 || CK_KNOB_SET("CK_FIT_GK") ? sizeof(unsigned long long) * 2 * w.hcap * CK_HUGE_WGS : 0),
+    CK_BUF(ws.d_clusters, CK_BUF_FRAME, w.cluster_cap * sizeof(ck_cluster_t)),
+    CK_BUF(ws.d_counters, CK_BUF_FRAME, CK_CNT_STRIDE * sizeof(uint32_t)),
+    CK_BUF(ws.d_quads, CK_BUF_FRAME, w.quad_cap * sizeof(ck_quad_t)),
+    CK_BUF(ws.d_dets, CK_BUF_FRAME, w.det_cap * sizeof(ck_detection_t)),
+    CK_BUF(ws.d_fit_scratch, CK_BUF_TWIN, w.fit_scratch_bytes),
+    CK_BUF(ws.d_wimg, CK_BUF_FRAME, h->npix * sizeof(uint16_t)),
+    CK_BUF(ws.d_field, 0, w.field_cap * sizeof(ck_field_tag_t)),
+    CK_BUF(ws.d_gyro, CK_BUF_FRAME, sizeof(double)),
+    CK_BUF(ws.d_has_gyro, CK_BUF_FRAME, 1),
+    CK_BUF(ws.d_problems, CK_BUF_FRAME, sizeof(ck_sqpnp_problem_t)),
+    CK_BUF(ws.d_pose_tags, CK_BUF_FRAME, w.det_cap * sizeof(ck_iso3_t)),
+    CK_BUF(ws.d_bearings, CK_BUF_FRAME, w.det_cap * 12 * sizeof(double)),
+    CK_BUF(ws.d_world, CK_BUF_FRAME, w.det_cap * 12 * sizeof(double)),
+    CK_BUF(ws.d_results, CK_BUF_FRAME, sizeof(ck_sqpnp_result_t)),
+    CK_BUF(ws.d_meas, CK_BUF_FRAME, sizeof(ck_vision_measurement_t)),
+    CK_BUF(ws.d_valid, CK_BUF_FRAME, sizeof(int32_t)),
+    CK_BUF(d_fam_codes, 0, fam_codes_bytes(h)),
+    CK_BUF(d_fams, 0, h->cfg.n_families * sizeof(ck_dev_family)),
+    // per-tag pose (k_tagpose.hip), by the first call that needs them; one call's records, never part of a split
+    CK_BUF(d_tp_dets, CK_BUF_LAZY, (size_t)h->cfg.max_batch * w.det_cap * sizeof(ck_detection_t)),
+    CK_BUF(d_tp_counts, CK_BUF_LAZY, h->cfg.max_batch * sizeof(int32_t)),
+    CK_BUF(d_tp_out, CK_BUF_LAZY, (size_t)h->cfg.max_batch * w.det_cap * sizeof(ck_tag_pose_t)),
+};
+#undef CK_BUF
+// A pointer added to ck_stage_ws without a row above stops the build here (so does any other member: then correct the 64 bytes
+// that its capacities and their padding take)
+constexpr int ws_rows() {
+    int n = 0;
+    for (const ck_buf_desc &d : ck_bufs) n += d.member >= offsetof(ck_handle, ws) && d.member < offsetof(ck_handle, ws) + sizeof(ck_stage_ws);
+    return n;
+}
+static_assert(sizeof(ck_stage_ws) == ws_rows() * sizeof(void *) + 64, "every pointer of ck_stage_ws has one row in ck_bufs[]");
+
+static char *&buf_ptr(ck_handle *h, const ck_buf_desc &d) { return *reinterpret_cast<char **>(reinterpret_cast<char *>(h) + d.member); }
+
+static int alloc_one(ck_handle *h, const ck_buf_desc &d) {
+    if (d.flags & CK_BUF_ALIAS) { buf_ptr(h, d) = buf_ptr(h, (&d)[-1]); return CK_OK; }
+    const size_t bytes = d.bytes(h) * (d.flags & CK_BUF_FRAME ? (size_t)h->cfg.max_batch : d.flags & CK_BUF_TWIN ? 2 : 1);
+    if (!bytes || buf_ptr(h, d)) return CK_OK;
+    CK_HIP_ALLOC(ck_malloc_dev_at(&buf_ptr(h, d), bytes, d.name, __LINE__)); // (a buffer whose fill failed is still the handle's: ck_bufs_free)
+    return CK_OK;
+}
+
+int ck_buf_alloc(ck_handle *h, const void *member) {
+    for (const ck_buf_desc &d : ck_bufs)
+        if (reinterpret_cast<const char *>(h) + d.member == member) return alloc_one(h, d);
+    return CK_EINVAL;
+}
+
+void ck_bufs_free(ck_handle *h) {
+    for (const ck_buf_desc &d : ck_bufs)
+        if (!(d.flags & CK_BUF_ALIAS)) (void)ck_free_dev(buf_ptr(h, d));
+}
+
+// capacities of the workspace of the irregular stages, from the configuration
+static int stage_caps(ck_handle *h) {
     ck_stage_ws &ws = h->ws;
     const ck_config_t &cfg = h->cfg;
     const size_t nb = (size_t)cfg.max_batch;
@@ -35,55 +132,34 @@ int ck_stage_alloc(ck_handle *h) {
     if (ws.ht_size < 1024) ws.ht_size = 1024;
     ws.max_cluster_points = 3 * (2 * h->qw + 2 * h->qh); // AprilTag-3's bound; <= 3 * 4 * 4095 < CK_HUGE_CAP (ck_create bounds the sides)
     if (cfg.max_nmaxima < 4 || cfg.max_nmaxima > 12) return CK_EINVAL;
-    CK_ALLOC(ck_malloc_dev(&ws.d_ht_keys, sizeof(unsigned long long) * (size_t)ws.ht_size * nb));
-    CK_ALLOC(ck_malloc_dev(&ws.d_ht_count, sizeof(uint32_t) * (size_t)ws.ht_size * nb));
-    CK_ALLOC(ck_malloc_dev(&ws.d_ht_off, sizeof(uint32_t) * (size_t)ws.ht_size * nb));
     {   // frame pitch of the point arrays = positions of the split fit's extended sequences (ck_internal.h)
         const size_t e = (size_t)ws.point_cap + (size_t)CK_EXT_HALO * ws.cluster_cap;
         const size_t r = (e + CK_SPAN - 1) / CK_SPAN * CK_SPAN;
         if (r > 0x7FFFFFFFu - 4096) return CK_EINVAL;
         ws.ext_cap = (int)r;
     }
-    CK_ALLOC(ck_malloc_dev(&ws.d_tmp, sizeof(ck_packed_point) * (size_t)ws.ext_cap * nb));
-    CK_ALLOC(ck_malloc_dev(&ws.d_points, sizeof(ck_packed_point) * (size_t)ws.ext_cap * nb));
-    ws.d_ext_xy = ws.d_tmp; ws.d_maxval = reinterpret_cast<double *>(ws.d_points);
-    CK_ALLOC(ck_malloc_dev(&ws.d_ext_w, sizeof(uint16_t) * (size_t)ws.ext_cap * nb));
-    CK_ALLOC(ck_malloc_dev(&ws.d_maxpos, sizeof(uint16_t) * (size_t)(ws.ext_cap / 2) * nb));
-    CK_ALLOC(ck_malloc_dev(&ws.d_maxmask, sizeof(unsigned long long) * (size_t)(ws.ext_cap / 64) * nb));
-    CK_ALLOC(ck_malloc_dev(&ws.d_maxpre, sizeof(uint16_t) * (size_t)(ws.ext_cap / 64) * nb));
-    CK_ALLOC(ck_malloc_dev(&ws.d_blk, sizeof(long long) * 6 * (size_t)(ws.ext_cap / 32) * nb));
-    CK_ALLOC(ck_malloc_dev(&ws.d_cstate, sizeof(uint32_t) * 2 * (size_t)ws.cluster_cap * nb));
     ws.run_cap = 4 * ws.cluster_cap;
-    CK_ALLOC(ck_malloc_dev(&ws.d_runs, sizeof(ck_run) * (size_t)ws.run_cap * nb));
-    CK_ALLOC(ck_malloc_dev(&ws.d_lscratch, 2 * sizeof(unsigned long long) * (size_t)CK_LSCRATCH_PER_WG * CK_LSCRATCH_WGS));
-    ws.d_hscratch = nullptr;
-    ws.hcap = (ws.max_cluster_points + 1023) & ~1023; // (1920 x 1080: 18 432 points, 144 MiB instead of the 512 MiB of the class's template capacity)
+    ws.hcap = (ws.max_cluster_points + 1023) & ~1023;
     if (ws.hcap < 16384 && CK_KNOB_SET("CK_FIT_GK")) ws.hcap = 16384;
-    if (ws.max_cluster_points > 16384 || CK_KNOB_SET("CK_FIT_GK")) // (one copy per stream of a split batch)
-        CK_ALLOC(ck_malloc_dev(&ws.d_hscratch, 2 * sizeof(unsigned long long) * 2 * (size_t)ws.hcap * CK_HUGE_WGS));
-    CK_ALLOC(ck_malloc_dev(&ws.d_clusters, sizeof(ck_cluster_t) * (size_t)ws.cluster_cap * nb));
-    CK_ALLOC(ck_malloc_dev(&ws.d_counters, sizeof(uint32_t) * CK_CNT_STRIDE * nb));
-    CK_ALLOC(ck_malloc_dev(&ws.d_quads, sizeof(ck_quad_t) * (size_t)ws.quad_cap * nb));
-    CK_ALLOC(ck_malloc_dev(&ws.d_dets, sizeof(ck_detection_t) * (size_t)ws.det_cap * nb));
     // fit scratch: one work list per size class + counters, then the decode candidates
     size_t list_bytes = ((size_t)CK_FIT_LISTS * ws.cluster_cap * nb + 32) * sizeof(uint32_t);
     size_t cand_bytes = 256 + ((nb * 4 + 255) / 256) * 256 + sizeof(ck_detection_t) * (size_t)ws.quad_cap * cfg.n_families * nb;
     ws.fit_scratch_bytes = ((list_bytes + 255) / 256) * 256 + cand_bytes;
-    CK_ALLOC(ck_malloc_dev(&ws.d_fit_scratch, 2 * ws.fit_scratch_bytes)); // second copy: the half-batch that runs on stream2
-    CK_ALLOC(ck_malloc_dev(&ws.d_wimg, sizeof(uint16_t) * h->npix * nb));
     ws.field_cap = 1024;
-    CK_ALLOC(ck_malloc_dev(&ws.d_field, sizeof(ck_field_tag_t) * (size_t)ws.field_cap));
-    CK_ALLOC(ck_malloc_dev(&ws.d_gyro, sizeof(double) * nb));
-    CK_ALLOC(ck_malloc_dev(&ws.d_has_gyro, nb));
-    CK_ALLOC(ck_malloc_dev(&ws.d_problems, sizeof(ck_sqpnp_problem_t) * nb));
-    CK_ALLOC(ck_malloc_dev(&ws.d_pose_tags, sizeof(ck_iso3_t) * nb * ws.det_cap));
-    CK_ALLOC(ck_malloc_dev(&ws.d_bearings, sizeof(double) * 12 * nb * ws.det_cap));
-    CK_ALLOC(ck_malloc_dev(&ws.d_world, sizeof(double) * 12 * nb * ws.det_cap));
-    CK_ALLOC(ck_malloc_dev(&ws.d_results, sizeof(ck_sqpnp_result_t) * nb));
-    CK_ALLOC(ck_malloc_dev(&ws.d_meas, sizeof(ck_vision_measurement_t) * nb));
-    CK_ALLOC(ck_malloc_dev(&ws.d_valid, sizeof(int32_t) * nb));
-    // family tables
+    return CK_OK;
+}
+
+int ck_bufs_create(ck_handle *h) {
+    int rc = stage_caps(h);
+    for (const ck_buf_desc &d : ck_bufs) {
+        const bool now = !(d.flags & CK_BUF_LAZY) || (d.member == offsetof(ck_handle, d_qframes) && h->cfg.quad_decimate > 1);
+        if (rc == CK_OK && now) rc = alloc_one(h, d);
+    }
+    if (rc != CK_OK) return rc;
+    // family tables: the codes go into d_fam_codes one family after the other
+    const ck_config_t &cfg = h->cfg;
     std::vector<ck_dev_family> fams((size_t)cfg.n_families);
+    uint64_t *dc = h->d_fam_codes;
     for (int f = 0; f < cfg.n_families; f++) {
         const ck_family_t *src = cfg.families[f];
         ck_dev_family &d = fams[(size_t)f];
@@ -91,33 +167,12 @@ int ck_stage_alloc(ck_handle *h) {
         d.nbits = src->nbits; d.ncodes = src->ncodes; d.n_upstream = src->n_upstream ? src->n_upstream : src->ncodes; /* 0 (a table built against ABI v1, or zero-initialised): the caller vouches for all of it */ d.width_at_border = src->width_at_border;
         d.total_width = src->total_width; d.reversed_border = src->reversed_border;
         for (uint32_t i = 0; i < src->nbits; i++) { d.bit_x[i] = src->bit_x[i]; d.bit_y[i] = src->bit_y[i]; }
-        uint64_t *dc = nullptr;
-        CK_ALLOC(ck_malloc_dev(&dc, sizeof(uint64_t) * src->ncodes));
         CK_HIP(hipMemcpy(dc, src->codes, sizeof(uint64_t) * src->ncodes, hipMemcpyHostToDevice));
         d.codes = dc;
+        dc += src->ncodes;
     }
-    CK_ALLOC(ck_malloc_dev(&h->d_fams, sizeof(ck_dev_family) * fams.size()));
     CK_HIP(hipMemcpy(h->d_fams, fams.data(), sizeof(ck_dev_family) * fams.size(), hipMemcpyHostToDevice));
     return CK_OK;
-}
-#undef CK_ALLOC
-
-void ck_stage_free(ck_handle *h) {
-    ck_stage_ws &ws = h->ws;
-    if (h->d_fams) {
-        std::vector<ck_dev_family> fams((size_t)h->cfg.n_families);
-        if (hipMemcpy(fams.data(), h->d_fams, sizeof(ck_dev_family) * fams.size(), hipMemcpyDeviceToHost) == hipSuccess)
-            for (auto &f : fams) (void)ck_free_dev(const_cast<uint64_t *>(f.codes));
-        (void)ck_free_dev(h->d_fams);
-    }
-    (void)ck_free_dev(ws.d_ht_keys); (void)ck_free_dev(ws.d_ht_count); (void)ck_free_dev(ws.d_ht_off); (void)ck_free_dev(ws.d_tmp);
-    (void)ck_free_dev(ws.d_ext_w); (void)ck_free_dev(ws.d_maxpos); (void)ck_free_dev(ws.d_maxmask); (void)ck_free_dev(ws.d_maxpre); (void)ck_free_dev(ws.d_blk);
-    (void)ck_free_dev(ws.d_cstate);
-    (void)ck_free_dev(ws.d_points); (void)ck_free_dev(ws.d_runs); (void)ck_free_dev(ws.d_lscratch); (void)ck_free_dev(ws.d_hscratch); (void)ck_free_dev(ws.d_clusters); (void)ck_free_dev(ws.d_counters); (void)ck_free_dev(ws.d_quads);
-    (void)ck_free_dev(ws.d_dets); (void)ck_free_dev(ws.d_fit_scratch); (void)ck_free_dev(ws.d_wimg);
-    (void)ck_free_dev(ws.d_field); (void)ck_free_dev(ws.d_gyro); (void)ck_free_dev(ws.d_has_gyro); (void)ck_free_dev(ws.d_problems);
-    (void)ck_free_dev(ws.d_pose_tags); (void)ck_free_dev(ws.d_bearings); (void)ck_free_dev(ws.d_world); (void)ck_free_dev(ws.d_results);
-    (void)ck_free_dev(ws.d_meas); (void)ck_free_dev(ws.d_valid);
 }
 
 // the whole detector on n frames resident on the device
@@ -133,47 +188,31 @@ int ck_streams_wanted() {
     return v;
 }
 static ck_handle make_view(const ck_handle *h, int f0, bool second_stream = true) {
-    ck_handle v = *h;
-    ck_stage_ws &w = v.ws;
-    const size_t f = (size_t)f0, npix = h->npix;
+    ck_handle v = *h; // (capacities and the rest stay; only the pointers move)
     if (second_stream) v.stream = h->stream2;
-    v.d_frames += f * h->frame_pitch;
-    if (ck_quad_separate(h)) v.d_qframes += f * (size_t)((h->qw + 15) / 16 * 16) * h->qh;
-    else v.d_qframes = v.d_frames;
-    v.d_thresh += f * npix; v.d_labels += f * npix;
-    v.d_groot += f * h->broot_cap; v.d_gsize += f * h->broot_cap; v.d_gscratch += f * 2 * h->broot_cap; v.d_xband += f * 2 * h->broot_cap;
-    v.d_broots += f * 2 * h->broot_cap; v.d_tile_count += f * (size_t)(h->tiles_x * h->tiles_y); v.d_ring += f * h->ring_len;
-    w.d_ht_keys += f * w.ht_size; w.d_ht_count += f * w.ht_size; w.d_ht_off += f * w.ht_size;
-    w.d_tmp += f * w.ext_cap; w.d_points += f * w.ext_cap; w.d_runs += f * w.run_cap;
-    w.d_ext_xy += f * w.ext_cap; w.d_ext_w += f * w.ext_cap; w.d_maxval += f * (size_t)(w.ext_cap / 2); w.d_maxpos += f * (size_t)(w.ext_cap / 2);
-    w.d_maxmask += f * (size_t)(w.ext_cap / 64); w.d_maxpre += f * (size_t)(w.ext_cap / 64); w.d_blk += f * 6 * (size_t)(w.ext_cap / 32);
-    w.d_cstate += f * 2 * w.cluster_cap;
-    if (second_stream) w.d_lscratch += (size_t)CK_LSCRATCH_PER_WG * CK_LSCRATCH_WGS;
-    if (second_stream && w.d_hscratch) w.d_hscratch += 2 * (size_t)w.hcap * CK_HUGE_WGS;
-    w.d_clusters += f * w.cluster_cap; w.d_counters += f * CK_CNT_STRIDE; w.d_quads += f * w.quad_cap; w.d_dets += f * w.det_cap;
-    w.d_wimg += f * npix;
-    if (second_stream) w.d_fit_scratch = static_cast<uint8_t *>(w.d_fit_scratch) + w.fit_scratch_bytes;
-    w.d_gyro += f; w.d_has_gyro += f; w.d_problems += f; w.d_pose_tags += f * w.det_cap; w.d_bearings += f * w.det_cap * 12;
-    w.d_world += f * w.det_cap * 12; w.d_results += f; w.d_meas += f; w.d_valid += f;
+    for (const ck_buf_desc &d : ck_bufs) {
+        char *&p = buf_ptr(&v, d);
+        if (!p) continue;
+        if (d.flags & CK_BUF_FRAME) p += (size_t)f0 * d.bytes(h);
+        else if ((d.flags & CK_BUF_TWIN) && second_stream) p += d.bytes(h);
+    }
     return v;
 }
 
 // clusters -> quad fit -> decode of n frames on h->stream
-static int run_tail(ck_handle *h, const uint8_t *frames, int stride, size_t pitch, int n, int upto, bool events) {
+static int run_tail(ck_handle *h, const ck_dev_image &img, int n, int upto, bool events) {
     hipEvent_t *ev = h->ev;
     int rc = ck_launch_clusters(h, n);
     if (rc != CK_OK) return rc;
     if (events) CK_HIP(hipEventRecord(ev[3], h->stream));
-    const uint8_t *q = frames; int qs = stride; size_t qp = pitch;
-    if (ck_quad_separate(h)) { q = h->d_qframes; qs = (h->qw + 15) / 16 * 16; qp = (size_t)qs * h->qh; }
-    if (ck_refine_reads_quad(h)) { frames = q; stride = qs; pitch = qp; } // edge refinement and decode read Q as well
+    const ck_dev_image fine = ck_refine_image(h, img);
     if (upto >= 2) {
-        rc = ck_launch_fit_quads(h, q, qs, qp, frames, stride, pitch, n);
+        rc = ck_launch_fit_quads(h, ck_quad_image(h, img), fine, n);
         if (rc != CK_OK) return rc;
     }
     if (events) CK_HIP(hipEventRecord(ev[4], h->stream));
     if (upto >= 3) {
-        rc = ck_launch_decode(h, frames, stride, pitch, n);
+        rc = ck_launch_decode(h, fine, n);
         if (rc != CK_OK) return rc;
     }
     if (events) CK_HIP(hipEventRecord(ev[5], h->stream));
@@ -191,19 +230,18 @@ static int parts_wanted() {
     return v < 1 ? 1 : (v > 8 ? 8 : v);
 }
 
-static int run_pipeline(ck_handle *h, const uint8_t *frames, int stride, size_t pitch, int n, int upto /*1 clusters, 2 quads, 3 all*/,
-                        ck_split *split = nullptr) {
+static int run_pipeline(ck_handle *h, const ck_dev_image &img, int n, int upto /*1 clusters, 2 quads, 3 all*/, ck_split *split = nullptr) {
     hipEvent_t *ev = h->ev;
     h->n_last_dets = -1; // the workspace is rewritten from here on; it holds this call's detections only once they are all enqueued
     CK_HIP(hipEventRecord(ev[1], h->stream));
-    int rc = ck_run_threshold_segment(h, frames, stride, pitch, n);
+    int rc = ck_run_threshold_segment(h, img, n);
     if (rc != CK_OK) return rc;
     CK_HIP(hipEventRecord(ev[2], h->stream));
     int parts = parts_wanted();
     if (parts > n) parts = n;
     if (!split || parts < 2 || ck_streams_wanted() < 2) {
         if (split) { split->parts = 1; split->first[0] = 0; split->first[1] = n; }
-        rc = run_tail(h, frames, stride, pitch, n, upto, true);
+        rc = run_tail(h, img, n, upto, true);
         if (rc == CK_OK && upto >= 3) h->n_last_dets = n;
         return rc;
     }
@@ -215,19 +253,26 @@ static int run_pipeline(ck_handle *h, const uint8_t *frames, int stride, size_t 
         const int f0 = split->first[p], cnt = split->first[p + 1] - f0;
         ck_handle *hp = h;
         if (p > 0) { split->view[p] = make_view(h, f0, (p & 1) != 0); hp = &split->view[p]; }
-        rc = run_tail(hp, frames + (size_t)f0 * pitch, stride, pitch, cnt, upto, p == 0);
+        rc = run_tail(hp, {img.p + (size_t)f0 * img.pitch, img.stride, img.pitch}, cnt, upto, p == 0);
         if (rc != CK_OK) return rc;
     }
     if (upto >= 3) h->n_last_dets = n;
     return CK_OK;
 }
 // the handle's stream continues only after stream2 has finished its half
-static int join_split(ck_handle *h, const ck_split &sp, int n) {
-    (void)n;
+static int join_split(ck_handle *h, const ck_split &sp) {
     if (!sp.split()) return CK_OK;
     CK_HIP(hipEventRecord(h->ev_join, h->stream2));
     CK_HIP(hipStreamWaitEvent(h->stream, h->ev_join, 0));
     return CK_OK;
+}
+
+static void fill_stage_ms(ck_handle *h) {
+    ck_stage_ms_t &ms = h->last_ms;
+    float t;
+    auto el = [&](int a, int b) { t = 0; (void)hipEventElapsedTime(&t, h->ev[a], h->ev[b]); return t; };
+    ms.h2d = el(0, 1); ms.threshold = el(1, 2); ms.segment = 0; ms.clusters = el(2, 3); ms.quads = el(3, 4);
+    ms.decode = el(4, 5); ms.d2h = el(5, 6); ms.total = el(0, 6); // (ck_process_*: d2h slot = glue + SQPnP + 64-byte records back)
 }
 
 static int fetch_detections(ck_handle *h, int n, ck_detection_t *dets, int cap, int32_t *counts, uint32_t *status) {
@@ -246,12 +291,17 @@ static int fetch_detections(ck_handle *h, int n, ck_detection_t *dets, int cap, 
         counts[i] = (int32_t)nd;
         if (status) status[i] = st;
     }
-    ck_stage_ms_t &ms = h->last_ms;
-    float t;
-    auto el = [&](int a, int b) { t = 0; (void)hipEventElapsedTime(&t, h->ev[a], h->ev[b]); return t; };
-    ms.h2d = el(0, 1); ms.threshold = el(1, 2); ms.segment = 0; ms.clusters = el(2, 3); ms.quads = el(3, 4);
-    ms.decode = el(4, 5); ms.d2h = el(5, 6); ms.total = el(0, 6);
+    fill_stage_ms(h);
     return CK_OK;
+}
+
+// what every detect entry point does once its input is staged (ev[0] recorded before the staging)
+static int detect_common(ck_handle *h, const ck_dev_image &img, int n, ck_detection_t *dets, int cap, int32_t *counts, uint32_t *status) {
+    ck_split sp;
+    int rc = run_pipeline(h, img, n, 3, &sp);
+    if (rc == CK_OK) rc = join_split(h, sp);
+    if (rc != CK_OK) return rc;
+    return fetch_detections(h, n, dets, cap, counts, status);
 }
 
 extern "C" int ck_detect_uploaded(ck_handle_t *h, int32_t n, ck_detection_t *dets, int32_t cap, int32_t *counts, uint32_t *status) {
@@ -259,11 +309,7 @@ extern "C" int ck_detect_uploaded(ck_handle_t *h, int32_t n, ck_detection_t *det
     if (n == 0) return CK_OK;
     CK_HIP(hipSetDevice(h->device));
     CK_HIP(hipEventRecord(h->ev[0], h->stream));
-    ck_split sp;
-    int rc = run_pipeline(h, h->d_frames, h->frame_stride, h->frame_pitch, n, 3, &sp);
-    if (rc == CK_OK) rc = join_split(h, sp, n);
-    if (rc != CK_OK) return rc;
-    return fetch_detections(h, n, dets, cap, counts, status);
+    return detect_common(h, ck_staged_image(h), n, dets, cap, counts, status);
 }
 
 extern "C" int ck_detect_batch(ck_handle_t *h, const ck_image_u8_t *imgs, int32_t n, ck_detection_t *dets, int32_t cap,
@@ -274,11 +320,7 @@ extern "C" int ck_detect_batch(ck_handle_t *h, const ck_image_u8_t *imgs, int32_
     CK_HIP(hipEventRecord(h->ev[0], h->stream));
     int rc = ck_upload_frames(h, imgs, n);
     if (rc != CK_OK) return rc;
-    ck_split sp;
-    rc = run_pipeline(h, h->d_frames, h->frame_stride, h->frame_pitch, n, 3, &sp);
-    if (rc == CK_OK) rc = join_split(h, sp, n);
-    if (rc != CK_OK) return rc;
-    return fetch_detections(h, n, dets, cap, counts, status);
+    return detect_common(h, ck_staged_image(h), n, dets, cap, counts, status);
 }
 
 extern "C" int ck_detect_batch_device(ck_handle_t *h, const uint8_t *d_frames, int32_t n, int32_t stride, int64_t frame_pitch,
@@ -287,41 +329,40 @@ extern "C" int ck_detect_batch_device(ck_handle_t *h, const uint8_t *d_frames, i
     if (n == 0) return CK_OK;
     CK_HIP(hipSetDevice(h->device));
     CK_HIP(hipEventRecord(h->ev[0], h->stream));
-    const uint8_t *use; int us; size_t up;
-    int rc = ck_stage_device_frames(h, d_frames, n, stride, frame_pitch, &use, &us, &up);
+    ck_dev_image use;
+    int rc = ck_stage_device_frames(h, d_frames, n, stride, frame_pitch, &use);
     if (rc != CK_OK) return rc;
-    ck_split sp;
-    rc = run_pipeline(h, use, us, up, n, 3, &sp);
-    if (rc == CK_OK) rc = join_split(h, sp, n);
-    if (rc != CK_OK) return rc;
-    return fetch_detections(h, n, dets, cap, counts, status);
+    return detect_common(h, use, n, dets, cap, counts, status);
 }
 
-int ck_detect_frames(ck_handle *h, const uint8_t *frames, int stride, size_t pitch, int n, ck_detection_t *dets, int cap, int32_t *counts,
-                     uint32_t *status) {
+int ck_detect_frames(ck_handle *h, const ck_dev_image &img, int n, ck_detection_t *dets, int cap, int32_t *counts, uint32_t *status) {
     if (!h || !dets || !counts || cap < 1 || n < 0 || n > h->cfg.max_batch) return CK_EINVAL;
     if (n == 0) return CK_OK;
     CK_HIP(hipEventRecord(h->ev[0], h->stream));
-    ck_split sp;
-    int rc = run_pipeline(h, frames, stride, pitch, n, 3, &sp);
-    if (rc == CK_OK) rc = join_split(h, sp, n);
+    return detect_common(h, img, n, dets, cap, counts, status);
+}
+
+// ck_clusters_batch / ck_quads_batch: stage the input, run up to stage `upto`, wait, read the frames' counters
+static int run_upto(ck_handle *h, const ck_image_u8_t *imgs, int n, int upto, std::vector<uint32_t> &counters) {
+    CK_HIP(hipSetDevice(h->device));
+    int rc = imgs ? ck_upload_frames(h, imgs, n) : (n <= h->n_staged ? CK_OK : CK_EINVAL);
     if (rc != CK_OK) return rc;
-    return fetch_detections(h, n, dets, cap, counts, status);
+    rc = run_pipeline(h, ck_staged_image(h), n, upto);
+    if (rc != CK_OK) return rc;
+    CK_HIP(hipStreamSynchronize(h->stream));
+    counters.resize((size_t)n * CK_CNT_STRIDE);
+    CK_HIP(hipMemcpy(counters.data(), h->ws.d_counters, counters.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return CK_OK;
 }
 
 extern "C" int ck_clusters_batch(ck_handle_t *h, const ck_image_u8_t *imgs, int32_t n, ck_cluster_t *clusters, int32_t cluster_cap,
                                  int32_t *n_clusters, ck_cluster_point_t *points, int32_t point_cap, int32_t *n_points) {
     if (!h || !clusters || !n_clusters || !points || !n_points || n < 0 || cluster_cap < 0 || point_cap < 0) return CK_EINVAL;
     if (n == 0) return CK_OK;
-    CK_HIP(hipSetDevice(h->device));
-    int rc = imgs ? ck_upload_frames(h, imgs, n) : (n <= h->n_staged ? CK_OK : CK_EINVAL);
-    if (rc != CK_OK) return rc;
-    rc = run_pipeline(h, h->d_frames, h->frame_stride, h->frame_pitch, n, 1);
+    std::vector<uint32_t> counters;
+    int rc = run_upto(h, imgs, n, 1, counters);
     if (rc != CK_OK) return rc;
     ck_stage_ws &ws = h->ws;
-    CK_HIP(hipStreamSynchronize(h->stream));
-    std::vector<uint32_t> counters((size_t)n * CK_CNT_STRIDE);
-    CK_HIP(hipMemcpy(counters.data(), ws.d_counters, counters.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     for (int i = 0; i < n; i++) {
         uint32_t nc = counters[(size_t)i * CK_CNT_STRIDE + CK_CNT_CLUSTERS], np = counters[(size_t)i * CK_CNT_STRIDE + CK_CNT_POINTS];
         if ((int)nc > cluster_cap || (int)np > point_cap) return CK_ECAPACITY;
@@ -337,15 +378,10 @@ extern "C" int ck_clusters_batch(ck_handle_t *h, const ck_image_u8_t *imgs, int3
 extern "C" int ck_quads_batch(ck_handle_t *h, const ck_image_u8_t *imgs, int32_t n, ck_quad_t *quads, int32_t quad_cap, int32_t *n_quads) {
     if (!h || !quads || !n_quads || n < 0 || quad_cap < 0) return CK_EINVAL;
     if (n == 0) return CK_OK;
-    CK_HIP(hipSetDevice(h->device));
-    int rc = imgs ? ck_upload_frames(h, imgs, n) : (n <= h->n_staged ? CK_OK : CK_EINVAL);
-    if (rc != CK_OK) return rc;
-    rc = run_pipeline(h, h->d_frames, h->frame_stride, h->frame_pitch, n, 2);
+    std::vector<uint32_t> counters;
+    int rc = run_upto(h, imgs, n, 2, counters);
     if (rc != CK_OK) return rc;
     ck_stage_ws &ws = h->ws;
-    CK_HIP(hipStreamSynchronize(h->stream));
-    std::vector<uint32_t> counters((size_t)n * CK_CNT_STRIDE);
-    CK_HIP(hipMemcpy(counters.data(), ws.d_counters, counters.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     for (int i = 0; i < n; i++) {
         uint32_t nq = counters[(size_t)i * CK_CNT_STRIDE + CK_CNT_QUADS];
         if (nq > (uint32_t)ws.quad_cap) nq = (uint32_t)ws.quad_cap; // the counter keeps counting past the capacity (status bit set)
@@ -356,37 +392,33 @@ extern "C" int ck_quads_batch(ck_handle_t *h, const ck_image_u8_t *imgs, int32_t
     return CK_OK;
 }
 
-static int process_common(ck_handle *h, const uint8_t *frames, int stride, size_t pitch, int n, const ck_process_params_t *pp,
-                          const double *gyro, const uint8_t *has_gyro, ck_vision_measurement_t *out, int32_t *valid) {
+static int process_common(ck_handle *h, const ck_dev_image &img, int n, const ck_process_params_t *pp, const double *gyro,
+                          const uint8_t *has_gyro, ck_vision_measurement_t *out, int32_t *valid) {
     if (!pp || !gyro || !has_gyro || !out || !valid || (pp->n_field > 0 && !pp->field) || pp->n_field < 0) return CK_EINVAL;
     CK_HIP(hipEventRecord(h->ev[0], h->stream));
     if (pp->n_field > h->ws.field_cap) return CK_ECAPACITY;
     // the field layout is shared by both halves: upload it once, ahead of the fork
     if (pp->n_field) CK_HIP(hipMemcpyAsync(h->ws.d_field, pp->field, sizeof(ck_field_tag_t) * (size_t)pp->n_field, hipMemcpyDefault, h->stream));
     ck_split sp;
-    int rc = run_pipeline(h, frames, stride, pitch, n, 3, &sp);
+    int rc = run_pipeline(h, img, n, 3, &sp);
     if (rc != CK_OK) return rc;
     for (int p = 0; p < sp.parts && rc == CK_OK; p++) {
         const int f0 = sp.first[p], cnt = sp.first[p + 1] - f0;
         rc = ck_run_pose(p ? &sp.view[p] : h, cnt, pp, gyro + f0, has_gyro + f0, out + f0, valid + f0, false, false);
     }
-    if (rc == CK_OK) rc = join_split(h, sp, n);
+    if (rc == CK_OK) rc = join_split(h, sp);
     h->n_last_pose = rc == CK_OK ? n : -1;
     CK_HIP(hipEventRecord(h->ev[6], h->stream));
     CK_HIP(hipStreamSynchronize(h->stream));
-    ck_stage_ms_t &ms = h->last_ms;
-    float t;
-    auto el = [&](int a, int b) { t = 0; (void)hipEventElapsedTime(&t, h->ev[a], h->ev[b]); return t; };
-    ms.h2d = el(0, 1); ms.threshold = el(1, 2); ms.segment = 0; ms.clusters = el(2, 3); ms.quads = el(3, 4);
-    ms.decode = el(4, 5); ms.d2h = el(5, 6); ms.total = el(0, 6); // d2h slot = glue + SQPnP + 64-byte records back
+    fill_stage_ms(h);
     return rc;
 }
 
-int ck_process_frames(ck_handle *h, const uint8_t *frames, int stride, size_t pitch, int n, const ck_process_params_t *pp, const double *gyro,
+int ck_process_frames(ck_handle *h, const ck_dev_image &img, int n, const ck_process_params_t *pp, const double *gyro,
                       const uint8_t *has_gyro, ck_vision_measurement_t *out, int32_t *valid) {
     if (!h || n < 0 || n > h->cfg.max_batch) return CK_EINVAL;
     if (n == 0) return CK_OK;
-    return process_common(h, frames, stride, pitch, n, pp, gyro, has_gyro, out, valid);
+    return process_common(h, img, n, pp, gyro, has_gyro, out, valid);
 }
 
 extern "C" int ck_process_uploaded(ck_handle_t *h, int32_t n, const ck_process_params_t *pp, const double *gyro, const uint8_t *has_gyro,
@@ -394,7 +426,7 @@ extern "C" int ck_process_uploaded(ck_handle_t *h, int32_t n, const ck_process_p
     if (!h || n < 0 || n > h->n_staged) return CK_EINVAL;
     if (n == 0) return CK_OK;
     CK_HIP(hipSetDevice(h->device));
-    return process_common(h, h->d_frames, h->frame_stride, h->frame_pitch, n, pp, gyro, has_gyro, out, valid);
+    return process_common(h, ck_staged_image(h), n, pp, gyro, has_gyro, out, valid);
 }
 
 extern "C" int ck_process_batch_device(ck_handle_t *h, const uint8_t *d_frames, int32_t n, int32_t stride, int64_t frame_pitch,
@@ -403,8 +435,8 @@ extern "C" int ck_process_batch_device(ck_handle_t *h, const uint8_t *d_frames, 
     if (!h) return CK_EINVAL;
     if (n == 0) return CK_OK;
     CK_HIP(hipSetDevice(h->device));
-    const uint8_t *use; int us; size_t up;
-    int rc = ck_stage_device_frames(h, d_frames, n, stride, frame_pitch, &use, &us, &up);
+    ck_dev_image use;
+    int rc = ck_stage_device_frames(h, d_frames, n, stride, frame_pitch, &use);
     if (rc != CK_OK) return rc;
-    return process_common(h, use, us, up, n, pp, gyro, has_gyro, out, valid);
+    return process_common(h, use, n, pp, gyro, has_gyro, out, valid);
 }

@@ -218,13 +218,6 @@ __global__ __launch_bounds__(NT) void k_cat_roots(uint32_t *__restrict__ roots, 
     if (roots[i] == CK_LBL_INVALID) { roots[i] = (uint32_t)i; sizes[i] = 1; }
 }
 
-template <typename T>
-struct DevBuf {
-    T *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int alloc(size_t n) { return hipMalloc(&p, sizeof(T) * (n ? n : 1)) == hipSuccess ? CK_OK : CK_ENOMEM; }
-};
-
 int exclusive_scan(hipStream_t st, const uint32_t *d_in, uint32_t *d_excl, uint32_t *d_sums, uint32_t *d_total, int n) {
     int nb = (n + SB - 1) / SB;
     hipLaunchKernelGGL(k_scan_blocks, dim3((unsigned)nb), dim3(NT), 0, st, d_in, d_excl, d_sums, n);
@@ -333,12 +326,13 @@ extern "C" int ck_cat_connected_components(ck_handle_t *h, const uint8_t *classe
     if (w != h->qw || ht != h->qh) return CK_EINVAL; // the detector is created for one geometry (Detector::new, lib.rs:158)
     CK_HIP(hipSetDevice(h->device));
     size_t n = (size_t)w * ht;
-    const int stride = (w + 15) / 16 * 16;
+    ck_dev_image tri = ck_qframes_image(h); // (the layout of a quad image: w x ht is the handle's geometry)
     DevBuf<uint8_t> dcls, dtri; DevBuf<uint32_t> droots, dsizes;
-    if (dcls.alloc(n) || dtri.alloc((size_t)stride * ht) || droots.alloc(n) || dsizes.alloc(n)) return CK_ENOMEM;
+    if (dcls.alloc(n) || dtri.alloc(tri.pitch) || droots.alloc(n) || dsizes.alloc(n)) return CK_ENOMEM;
+    tri.p = dtri.p;
     CK_HIP(hipMemcpyAsync(dcls.p, classes, n, hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(k_class_to_tri, dim3((unsigned)((n + NT - 1) / NT)), dim3(NT), 0, h->stream, dcls.p, w, ht, stride, dtri.p);
-    int rc = ck_launch_threshold_segment(h, dtri.p, stride, (size_t)stride * ht, 1, true);
+    hipLaunchKernelGGL(k_class_to_tri, dim3((unsigned)((n + NT - 1) / NT)), dim3(NT), 0, h->stream, dcls.p, w, ht, tri.stride, dtri.p);
+    int rc = ck_launch_threshold_segment(h, tri, 1, true);
     if (rc != CK_OK) return rc;
     rc = ck_launch_canonical_labels(h, 1, droots.p, dsizes.p);
     if (rc != CK_OK) return rc;

@@ -59,7 +59,7 @@ static_assert(TW == 128, "a node index splits with >> 7 / & 127");
 //                       looks up at most two);
 //                       while the threshold is computed the same bytes hold the staged image and the 4x4 min/max (the
 //                       per-4x4 threshold words sit in the list's bytes, which is not alive yet)
-//   list    u32[LIST_CAP]  the tile's nodes: lookup pixel | colour << 12 | pixel count << 16; the white ones from the front, the black ones
+//   list    u32[LIST_CAP]  the tile's nodes: lookup pixel | label-table index << 12 | pixel count << 25; the white ones from the front, the black ones
 //                       from the back (the two waves that build it need not know each other's counts); a tile with more nodes
 //                       (one-pixel patterns) does without the list
 //   pool    u32[POOL_CAP]  links that need an atomic union (two u16 entries each)
@@ -573,8 +573,10 @@ __global__ __launch_bounds__(KNT) __attribute__((amdgpu_num_sgpr(80))) void k_ti
             const uint32_t t_up = upbase + su + (((nUt >> su) & 1u) << 7);
             parent[base + lk] = (uint16_t)(base + mn);           // (in this order: the two are one entry when the node's first column has a top pixel)
             parent[base + mn] = (uint16_t)(e ? t_up : CK_ROOT);  // no link to an earlier node: a root (count 0 for now)
-            // the list entry: lookup pixel | colour << 12 | pixel count << 16.  (A tile with more nodes than the list holds — one-pixel
-            // patterns — does without it: the index then runs past either end and nothing is stored.)
+            // the list entry: lookup pixel | label-table index << 12 | pixel count << 25 (a node is a run of a 2 x 32 pair of rows: 64
+            // pixels at most).  (A tile with more nodes than the list holds — one-pixel patterns — does without it: the index
+            // then runs past either end and nothing is stored.)
+            static_assert(2 * 32 < (1 << 7), "a node's pixel count fits the 7 bits above bit 25");
             if (li < (uint32_t)LIST_CAP) list[li] = lk | lcol | (((uint32_t)__popc(Mt & span) + (uint32_t)__popc(Mb & span)) << 25);
         }
         // (c) what is left: the vertical links one loop, the two diagonal kinds one loop each, then the three links that cross a
@@ -1687,6 +1689,7 @@ __device__ __forceinline__ uint32_t x_find(uint32_t *xpar, uint32_t a, bool halv
 // that took part hands its smallest pixel and its pixel count to its final root.  A join the pixel on the left (or, for up-right,
 // the pixel on the right) makes as its own vertical join is left to it: along a run of one component over one component only the
 // run's ends join.
+static_assert(CK_TW == 128 && TW == CK_TW, "k_fseam / k_fapply take a pixel's tile column with x >> 7");
 template <bool FOLD>
 __global__ __launch_bounds__(NT) void k_fseam(const uint16_t *__restrict__ ring, size_t ring_len, uint32_t *__restrict__ groot_all,
                                               uint32_t *__restrict__ gsize_all, uint32_t *__restrict__ xband, int w, int tiles_x, int tiles_y,
@@ -1803,7 +1806,7 @@ __global__ __launch_bounds__(NT) void k_decimate(const uint8_t *__restrict__ src
 
 } // namespace
 
-int ck_launch_threshold_segment(ck_handle *h, const uint8_t *frames, int stride, size_t frame_pitch, int n, bool precomputed) {
+int ck_launch_threshold_segment(ck_handle *h, const ck_dev_image &img, int n, bool precomputed) {
     const int tiles = h->tiles_x * h->tiles_y;
     static const int stop_after = CK_KNOB("CK_TILE_STOP_AFTER", 99);
     static const int sweeps = CK_KNOB("CK_TILE_SWEEPS", 0); // (pointer-jumping sweeps before the pooled unions: 0, 1 and 2 time the same since the nodes are pair components)
@@ -1855,11 +1858,11 @@ int ck_launch_threshold_segment(ck_handle *h, const uint8_t *frames, int stride,
         const int xcd_map = xcd_env >= 0 ? xcd_env : (cn >= 16 ? 1 : 0);
         const unsigned grid = xcd_map ? (unsigned)(((cn + 7) / 8) * 8 * tiles) : (unsigned)(tiles * cn);
         if (precomputed)
-            hipLaunchKernelGGL(k_tile<true>, dim3(grid), dim3(KNT), 0, h->stream, frames, frame_pitch, stride, h->qw, h->qh,
+            hipLaunchKernelGGL(k_tile<true>, dim3(grid), dim3(KNT), 0, h->stream, img.p, img.pitch, img.stride, h->qw, h->qh,
                                h->tiles_x, h->tiles_y, f0, f1, xcd_map, h->cfg.min_white_black_diff, h->cfg.min_component_px, h->d_thresh, h->d_labels,
                                h->d_broots, h->d_tile_count, h->d_ring, h->ring_len, stop_after, sweeps);
         else
-            hipLaunchKernelGGL(k_tile<false>, dim3(grid), dim3(KNT), 0, h->stream, frames, frame_pitch, stride, h->qw, h->qh,
+            hipLaunchKernelGGL(k_tile<false>, dim3(grid), dim3(KNT), 0, h->stream, img.p, img.pitch, img.stride, h->qw, h->qh,
                                h->tiles_x, h->tiles_y, f0, f1, xcd_map, h->cfg.min_white_black_diff, h->cfg.min_component_px, h->d_thresh, h->d_labels,
                                h->d_broots, h->d_tile_count, h->d_ring, h->ring_len, stop_after, sweeps);
         if (stop_after < 98) continue; // (a k_tile cut short by the diagnostics knob leaves tile counts or ring entries unwritten: nothing for the merge to read)
@@ -1905,21 +1908,17 @@ int ck_launch_canonical_labels(ck_handle *h, int n, uint32_t *d_out, uint32_t *d
             e = hipStreamSynchronize(h->stream);
         }
         (void)ck_free_dev(cnt);
-        if (e != hipSuccess) {
-            snprintf(ck_err_text, sizeof ck_err_text, "canonical labels: %s", hipGetErrorString(e));
-            (void)hipGetLastError();
-            return e == hipErrorOutOfMemory ? CK_ENOMEM : CK_EDEVICE;
-        }
+        if (e != hipSuccess) return ck_hip_failed(e, "exact sizes of the canonical labels", __FILE__, __LINE__, true);
     }
     CK_HIP(hipGetLastError());
     return CK_OK;
 }
 
-int ck_launch_decimate(ck_handle *h, const uint8_t *frames, int stride, size_t frame_pitch, int n) {
+int ck_launch_decimate(ck_handle *h, const ck_dev_image &img, int n) {
     size_t total = h->npix * (size_t)n;
     unsigned blocks = (unsigned)((total + NT - 1) / NT);
-    hipLaunchKernelGGL(k_decimate, dim3(blocks), dim3(NT), 0, h->stream, frames, frame_pitch, stride, h->cfg.quad_decimate, h->qw,
-                       h->qh, (h->qw + 15) / 16 * 16, h->d_qframes, total);
+    hipLaunchKernelGGL(k_decimate, dim3(blocks), dim3(NT), 0, h->stream, img.p, img.pitch, img.stride, h->cfg.quad_decimate, h->qw,
+                       h->qh, ck_qframes_image(h).stride, h->d_qframes, total);
     CK_HIP(hipGetLastError());
     return CK_OK;
 }

@@ -331,10 +331,10 @@ __global__ __launch_bounds__(FNT) void k_finalize(DecodeArgs a) {
 
 } // namespace
 
-int ck_launch_decode(ck_handle *h, const uint8_t *frames, int stride, size_t pitch, int n) {
+int ck_launch_decode(ck_handle *h, const ck_dev_image &img, int n) {
     ck_stage_ws &ws = h->ws;
     DecodeArgs a;
-    a.im = frames; a.w = h->w; a.h = h->h; a.stride = stride; a.pitch = pitch;
+    a.im = img.p; a.w = h->w; a.h = h->h; a.stride = img.stride; a.pitch = img.pitch;
     a.sharpening = h->cfg.decode_sharpening; a.max_hamming = h->cfg.max_hamming; a.n_families = h->cfg.n_families;
     a.fams = h->d_fams; a.ws = ws;
     // candidate buffer lives behind the work lists in the fit scratch; the per-frame counts were zeroed with the cluster tables

@@ -162,22 +162,22 @@ __global__ __launch_bounds__(NT) void k_prefilter(const uint8_t *__restrict__ sr
 }
 
 template <int CLS, int F>
-void launch_cls(ck_handle *h, const uint8_t *frames, int stride, size_t pitch, int n, const qf_weights &k, bool sharp) {
+void launch_cls(ck_handle *h, const ck_dev_image &img, int n, const qf_weights &k, bool sharp) {
     const int tiles_x = (h->qw + TW - 1) / TW, tiles_y = (h->qh + qf_class<CLS>::TH - 1) / qf_class<CLS>::TH;
-    const int qstride = (h->qw + 15) / 16 * 16;
+    const ck_dev_image q = ck_qframes_image(h);
     const dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)n);
     if (sharp)
-        hipLaunchKernelGGL((k_prefilter<CLS, F, true>), grid, dim3(NT), 0, h->stream, frames, pitch, stride, h->qw, h->qh, tiles_x,
-                           h->qf_ksz / 2, k, h->d_qframes, qstride, (size_t)qstride * h->qh);
+        hipLaunchKernelGGL((k_prefilter<CLS, F, true>), grid, dim3(NT), 0, h->stream, img.p, img.pitch, img.stride, h->qw, h->qh, tiles_x,
+                           h->qf_ksz / 2, k, h->d_qframes, q.stride, q.pitch);
     else
-        hipLaunchKernelGGL((k_prefilter<CLS, F, false>), grid, dim3(NT), 0, h->stream, frames, pitch, stride, h->qw, h->qh, tiles_x,
-                           h->qf_ksz / 2, k, h->d_qframes, qstride, (size_t)qstride * h->qh);
+        hipLaunchKernelGGL((k_prefilter<CLS, F, false>), grid, dim3(NT), 0, h->stream, img.p, img.pitch, img.stride, h->qw, h->qh, tiles_x,
+                           h->qf_ksz / 2, k, h->d_qframes, q.stride, q.pitch);
 }
 
 } // namespace
 
 // Q of frames [0, n) into h->d_qframes with the handle's current weights (by value: a batch keeps the sigma it was enqueued with)
-int ck_launch_prefilter(ck_handle *h, const uint8_t *frames, int stride, size_t frame_pitch, int n) {
+int ck_launch_prefilter(ck_handle *h, const ck_dev_image &img, int n) {
     const int ksz = h->qf_ksz, half = ksz / 2;
     if (ksz <= 1 || ksz > 33 || !h->d_qframes) return CK_EINVAL;
     if (n == 0) return CK_OK;
@@ -192,10 +192,10 @@ int ck_launch_prefilter(ck_handle *h, const uint8_t *frames, int stride, size_t 
     const bool sharp = h->quad_sigma < 0;
     const bool dec = h->cfg.quad_decimate > 1;
     switch (cls) {
-    case 0: dec ? launch_cls<0, 2>(h, frames, stride, frame_pitch, n, k, sharp) : launch_cls<0, 1>(h, frames, stride, frame_pitch, n, k, sharp); break;
-    case 1: dec ? launch_cls<1, 2>(h, frames, stride, frame_pitch, n, k, sharp) : launch_cls<1, 1>(h, frames, stride, frame_pitch, n, k, sharp); break;
-    case 2: dec ? launch_cls<2, 2>(h, frames, stride, frame_pitch, n, k, sharp) : launch_cls<2, 1>(h, frames, stride, frame_pitch, n, k, sharp); break;
-    default: dec ? launch_cls<3, 2>(h, frames, stride, frame_pitch, n, k, sharp) : launch_cls<3, 1>(h, frames, stride, frame_pitch, n, k, sharp); break;
+    case 0: dec ? launch_cls<0, 2>(h, img, n, k, sharp) : launch_cls<0, 1>(h, img, n, k, sharp); break;
+    case 1: dec ? launch_cls<1, 2>(h, img, n, k, sharp) : launch_cls<1, 1>(h, img, n, k, sharp); break;
+    case 2: dec ? launch_cls<2, 2>(h, img, n, k, sharp) : launch_cls<2, 1>(h, img, n, k, sharp); break;
+    default: dec ? launch_cls<3, 2>(h, img, n, k, sharp) : launch_cls<3, 1>(h, img, n, k, sharp); break;
     }
     CK_HIP(hipGetLastError());
     return CK_OK;

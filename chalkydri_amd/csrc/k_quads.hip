@@ -2402,8 +2402,7 @@ extern "C" int ck_fit_profile_read(unsigned long long *out, int reset) {
 }
 #endif
 
-int ck_launch_fit_quads(ck_handle *h, const uint8_t *qframes, int qstride, size_t qpitch, const uint8_t *frames, int stride,
-                        size_t pitch, int n) {
+int ck_launch_fit_quads(ck_handle *h, const ck_dev_image &qimg, const ck_dev_image &img, int n) {
     ck_stage_ws &ws = h->ws;
     if (n > 4095 || ws.cluster_cap > (1 << 20)) return CK_EINVAL;
     // work lists, their counts and the dequeue heads live in the fit scratch; counts and heads were zeroed with the cluster
@@ -2422,12 +2421,12 @@ int ck_launch_fit_quads(ck_handle *h, const uint8_t *qframes, int qstride, size_
     const int split = side_by_side ? 0 : fit_split;
     hipLaunchKernelGGL(k_classify, dim3((unsigned)n), dim3(1024), 0, h->stream, ws, n, lists, list_counts, list_cap, split);
     FitArgs a;
-    a.qim = qframes; a.qw = h->qw; a.qh = h->qh; a.qstride = qstride; a.qpitch = qpitch;
+    a.qim = qimg.p; a.qw = h->qw; a.qh = h->qh; a.qstride = qimg.stride; a.qpitch = qimg.pitch;
     a.wimg = ws.d_wimg;
     auto launch_wimg = [&](hipStream_t st) {
         const int w4 = (h->qw + 3) / 4;
-        hipLaunchKernelGGL(k_weight_image, dim3((unsigned)((w4 + 63) / 64), (unsigned)((h->qh + 3) / 4), (unsigned)n), dim3(256), 0, st, qframes,
-                           qpitch, qstride, h->qw, h->qh, ws.d_wimg);
+        hipLaunchKernelGGL(k_weight_image, dim3((unsigned)((w4 + 63) / 64), (unsigned)((h->qh + 3) / 4), (unsigned)n), dim3(256), 0, st, qimg.p,
+                           qimg.pitch, qimg.stride, h->qw, h->qh, ws.d_wimg);
     };
     // The split fit needs the weights in its second kernel only: the weight image (a streaming kernel, bound by HBM) then runs on the
     // second side stream beside the first kernels (bound by their sort) instead of before them (CK_FIT_WIMG_ASIDE=0: as before)
@@ -2437,7 +2436,7 @@ int ck_launch_fit_quads(ck_handle *h, const uint8_t *qframes, int qstride, size_
     const bool flat0 = flat_env0 >= 2 || (flat_env0 == 1 && !side_by_side && (size_t)n * (size_t)h->qw * (size_t)h->qh >= ((size_t)100 << 20));
     const bool wimg_aside = flat0 && !side_by_side && tails_aside_ok0 && wimg_aside_env;
     if (!wimg_aside) launch_wimg(h->stream);
-    a.im = frames; a.w = h->w; a.h = h->h; a.stride = stride; a.pitch = pitch;
+    a.im = img.p; a.w = h->w; a.h = h->h; a.stride = img.stride; a.pitch = img.pitch;
     a.decimate = h->cfg.quad_decimate; a.refine = h->cfg.refine_edges; a.max_nmaxima = h->cfg.max_nmaxima;
     a.cos_critical = h->cfg.cos_critical_rad; a.max_mse = h->cfg.max_line_fit_mse;
     a.normal_ok = 0; a.reversed_ok = 0; a.min_tag_width = 1 << 30;

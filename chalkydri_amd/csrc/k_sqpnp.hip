@@ -489,13 +489,6 @@ __global__ void k_measure(ck_stage_ws ws, const ck_sqpnp_result_t *res, uint8_t 
     valid[f] = ok;
 }
 
-template <typename T>
-struct DevBuf {
-    T *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int alloc(size_t n) { return hipMalloc(&p, sizeof(T) * (n ? n : 1)) == hipSuccess ? CK_OK : CK_ENOMEM; }
-};
-
 } // namespace
 
 extern "C" int ck_sqpnp_solve_batch(ck_handle_t *h, const ck_sqpnp_params_t *params, const ck_sqpnp_problem_t *problems, int32_t n,

@@ -410,19 +410,10 @@ int check_params(const ck_handle *h, const ck_tag_pose_params_t *pp) {
 
 // the pose buffers, allocated by the first call that needs them (ck_create allocates exactly what it did before)
 int alloc_buffers(ck_handle *h) {
-    if (h->d_tp_out) return CK_OK;
-    const size_t cap = (size_t)h->cfg.max_batch * h->ws.det_cap;
-    hipError_t e = ck_malloc_dev(&h->d_tp_dets, sizeof(ck_detection_t) * cap);
-    if (e == hipSuccess) e = ck_malloc_dev(&h->d_tp_counts, sizeof(int32_t) * (size_t)h->cfg.max_batch);
-    if (e == hipSuccess) e = ck_malloc_dev(&h->d_tp_out, sizeof(ck_tag_pose_t) * cap);
-    if (e != hipSuccess) {
-        snprintf(ck_err_text, sizeof ck_err_text, "tag pose buffers (%zu records) failed: %s", cap, hipGetErrorString(e));
-        (void)hipGetLastError();
-        (void)ck_free_dev(h->d_tp_dets); (void)ck_free_dev(h->d_tp_counts); (void)ck_free_dev(h->d_tp_out);
-        h->d_tp_dets = nullptr; h->d_tp_counts = nullptr; h->d_tp_out = nullptr;
-        return e == hipErrorOutOfMemory ? CK_ENOMEM : CK_EDEVICE;
-    }
-    return CK_OK;
+    int rc = ck_buf_alloc(h, &h->d_tp_dets);
+    if (rc == CK_OK) rc = ck_buf_alloc(h, &h->d_tp_counts);
+    if (rc == CK_OK) rc = ck_buf_alloc(h, &h->d_tp_out);
+    return rc; // (what a failure leaves allocated is kept for the next call, and released with the handle)
 }
 
 TagPoseArgs make_args(const ck_handle *h, const ck_tag_pose_params_t *pp) {
