@@ -94,6 +94,10 @@ class JpegInfo(C.Structure):
                                          "pad")]
 
 
+class RawFormat(C.Structure):
+    _fields_ = [("fourcc", C.c_uint32), ("orientation", C.c_int32)]
+
+
 class VisionMeasurement(C.Structure):
     _fields_ = [("pose_x", C.c_double), ("pose_y", C.c_double), ("pose_rot", C.c_double),
                 ("std_x", C.c_double), ("std_y", C.c_double), ("std_rot", C.c_double), ("ts", C.c_uint64),
@@ -124,6 +128,7 @@ class SynthParams(C.Structure):
 assert C.sizeof(VisionMeasurement) == 64  # crates/whacknet/src/lib.rs:92-95
 assert C.sizeof(TagPoseParams) == 112 and C.sizeof(TagPose) == 296
 assert C.sizeof(JpegFrame) == 16 and C.sizeof(JpegInfo) == 32
+assert C.sizeof(RawFormat) == 8
 
 # per-frame status bits (include/chalkydri_hip.h)
 CK_FRAME_OK, CK_FRAME_POINTS_OVERFLOW, CK_FRAME_CLUSTERS_OVERFLOW, CK_FRAME_QUADS_OVERFLOW, CK_FRAME_DETS_OVERFLOW = 0, 1, 2, 4, 8
@@ -131,3 +136,11 @@ CK_FRAME_UNVERIFIED_ID = 16
 
 # per-frame jpeg_status bits (ck_upload_jpeg / ck_jpeg_luma_batch)
 CK_JPEG_OK, CK_JPEG_UNSUPPORTED, CK_JPEG_GEOMETRY, CK_JPEG_CORRUPT = 0, 1, 2, 4
+
+# ck_raw_format_t.orientation: the reference's VideoOrientation, by its serde names (chalkydri_core/src/config.rs:201-207)
+CK_ORIENT_NONE, CK_ORIENT_CLOCKWISE, CK_ORIENT_ROTATE_180, CK_ORIENT_COUNTERCLOCKWISE = 0, 1, 2, 3
+ORIENTATIONS = {"none": CK_ORIENT_NONE, "clockwise": CK_ORIENT_CLOCKWISE, "rotate-180": CK_ORIENT_ROTATE_180,
+                "counterclockwise": CK_ORIENT_COUNTERCLOCKWISE}
+# the fourccs of the raw entry points (ck_raw_layout answers CK_EUNSUPPORTED to every other one)
+RAW_FOURCCS = ("GREY", "GRAY", "Y800", "NV12", "NV21", "I420", "YV12", "YUYV", "YUY2", "UYVY", "RGB3", "RGB ", "BGR3", "BGR ",
+               "RGBA", "BGRA")

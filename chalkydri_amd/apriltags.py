@@ -32,7 +32,10 @@ def load_field_layout(path_or_dict):
 
 class AprilTags:
     def __init__(self, width, height, field, calib, robot_to_cam, cam_id=0, family="tag36h11", bits_corrected=3,
-                 max_batch=1, device=0, quad_sigma=0.0, **cfg):
+                 max_batch=1, device=0, quad_sigma=0.0, fourcc=None, orientation="none", **cfg):
+        """width x height is the image the detector sees, and calib its intrinsics: with an `orientation` ("none", "clockwise",
+        "rotate-180", "counterclockwise": the reference's VideoOrientation names) those of the ORIENTED image.  `fourcc` names the
+        raw format of the camera's frames for process_raw_batch ("YUYV", "RGB3", ...; None: 8-bit luma)."""
         calib = json.loads(calib) if isinstance(calib, str) else calib
         r2c = json.loads(robot_to_cam) if isinstance(robot_to_cam, str) else robot_to_cam
         m = calib["OpenCVModel5"]
@@ -44,6 +47,7 @@ class AprilTags:
         self.solver = SqPnP(self.detector)
         self.tags = field if isinstance(field, dict) and all(isinstance(v, A.Iso3) for v in field.values()) else load_field_layout(field)
         self.cam_id = cam_id
+        self.fourcc, self.orientation = fourcc, orientation
         self._field = (A.FieldTag * max(len(self.tags), 1))()
         for i, (tid, pose) in enumerate(sorted(self.tags.items())):
             self._field[i].id, self._field[i].pose = tid, pose
@@ -69,6 +73,12 @@ class AprilTags:
         valid = (C.c_int32 * n)()
         check(det._L.ck_process_uploaded(det._h, n, C.byref(self._pp), g.ctypes.data, has.ctypes.data, out, valid), "ck_process_uploaded")
         return out, np.array(valid[:], bool)
+
+    def process_raw_batch(self, raw_frames, gyro=None):
+        """The camera's frames as it hands them over ([rows][bytes] each, in the task's fourcc): converted to luma and turned by
+        the task's orientation on the device, then processed like process_batch."""
+        n = self.detector.upload_raw(raw_frames, self.fourcc or "GREY", self.orientation)
+        return self.process_batch(None, gyro, n=n)
 
     def process_uploaded_into(self, n, gyro_ptr, has_gyro_ptr, out_ptr, valid_ptr):
         """Runs the whole path on the uploaded frames; every pointer may be host or device memory (no host round trip when

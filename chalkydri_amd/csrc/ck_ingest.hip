@@ -10,6 +10,7 @@
 #include <new>
 
 #include "ck_internal.h"
+#include "ck_rawfmt.h"
 
 struct ck_ingest {
     ck_handle *h;
@@ -20,6 +21,14 @@ struct ck_ingest {
     hipEvent_t ready[8];
     int staged[8];
     hipStream_t copy;
+    // a ring of ck_ingest_create_raw: the pinned slots and rawdev[] hold raw frames (rows of rstride, frames of rpitch); submit
+    // converts them into dev[], which is luma in the handle's staged layout on either kind of ring
+    bool raw;
+    ck_raw_format_t fmt;
+    ck_raw_class cls;
+    int sw, sh, min_stride, rstride;
+    size_t rpitch;
+    uint8_t *rawdev[8];
 };
 
 static bool luma_first(uint32_t fourcc) {
@@ -28,28 +37,53 @@ static bool luma_first(uint32_t fourcc) {
            fourcc == cc("I420") || fourcc == cc("YV12");
 }
 
-extern "C" int ck_ingest_create(ck_handle_t *h, int32_t n_slots, ck_ingest_t **out) {
+static int ingest_create(ck_handle_t *h, int32_t n_slots, const ck_raw_format_t *fmt, ck_ingest_t **out) {
     if (!h || !out || n_slots < 1 || n_slots > 8) return CK_EINVAL;
     *out = nullptr;
+    int32_t sw = 0, sh = 0, min_stride = 0;
+    int64_t min_bytes = 0;
+    ck_raw_class cls = {};
+    if (fmt) {
+        const int rc = ck_raw_layout(fmt, h->w, h->h, &sw, &sh, &min_stride, &min_bytes);
+        if (rc != CK_OK) return rc;
+        (void)ck_raw_classify(fmt->fourcc, &cls);
+    }
     CK_HIP(hipSetDevice(h->device));
     ck_ingest *g = new (std::nothrow) ck_ingest();
     if (!g) return CK_ENOMEM;
     memset(g, 0, sizeof *g);
     g->h = h; g->nslots = n_slots;
-    g->slot_bytes = h->frame_pitch * (size_t)h->cfg.max_batch;
+    const size_t dev_bytes = h->frame_pitch * (size_t)h->cfg.max_batch;
+    g->slot_bytes = dev_bytes;
+    if (fmt) {
+        g->raw = true; g->fmt = *fmt; g->cls = cls;
+        g->sw = sw; g->sh = sh; g->min_stride = min_stride;
+        g->rstride = (min_stride + 15) / 16 * 16;
+        g->rpitch = (size_t)g->rstride * sh;
+        g->slot_bytes = g->rpitch * (size_t)h->cfg.max_batch;
+    }
     hipError_t e = hipStreamCreateWithFlags(&g->copy, hipStreamNonBlocking);
     for (int s = 0; s < n_slots && e == hipSuccess; s++) {
         e = hipHostMalloc(reinterpret_cast<void **>(&g->host[s]), g->slot_bytes, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&g->dev[s]), g->slot_bytes);
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&g->dev[s]), dev_bytes);
+        if (e == hipSuccess && g->raw) e = hipMalloc(reinterpret_cast<void **>(&g->rawdev[s]), g->slot_bytes);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&g->ready[s], hipEventDisableTiming);
     }
     if (e != hipSuccess) {
         snprintf(ck_err_text, sizeof ck_err_text, "ingest ring allocation failed: %s", hipGetErrorString(e));
+        (void)hipGetLastError();
         ck_ingest_destroy(g);
         return CK_ENOMEM;
     }
     *out = g;
     return CK_OK;
+}
+
+extern "C" int ck_ingest_create(ck_handle_t *h, int32_t n_slots, ck_ingest_t **out) { return ingest_create(h, n_slots, nullptr, out); }
+
+extern "C" int ck_ingest_create_raw(ck_handle_t *h, int32_t n_slots, const ck_raw_format_t *fmt, ck_ingest_t **out) {
+    if (!fmt) return CK_EINVAL;
+    return ingest_create(h, n_slots, fmt, out);
 }
 
 extern "C" void ck_ingest_destroy(ck_ingest_t *g) {
@@ -59,22 +93,30 @@ extern "C" void ck_ingest_destroy(ck_ingest_t *g) {
     for (int s = 0; s < g->nslots; s++) {
         if (g->host[s]) (void)hipHostFree(g->host[s]);
         if (g->dev[s]) (void)hipFree(g->dev[s]);
+        if (g->rawdev[s]) (void)hipFree(g->rawdev[s]);
         if (g->ready[s]) (void)hipEventDestroy(g->ready[s]);
     }
     if (g->copy) (void)hipStreamDestroy(g->copy);
     delete g;
 }
 
-extern "C" int32_t ck_ingest_stride(const ck_ingest_t *g) { return g ? g->h->frame_stride : 0; }
+extern "C" int32_t ck_ingest_stride(const ck_ingest_t *g) { return !g ? 0 : g->raw ? g->rstride : g->h->frame_stride; }
 
 extern "C" uint8_t *ck_ingest_frame(ck_ingest_t *g, int32_t slot, int32_t index) {
     if (!g || slot < 0 || slot >= g->nslots || index < 0 || index >= g->h->cfg.max_batch) return nullptr;
-    return g->host[slot] + (size_t)index * g->h->frame_pitch;
+    return g->host[slot] + (size_t)index * (g->raw ? g->rpitch : g->h->frame_pitch);
 }
 
 extern "C" int ck_ingest_write(ck_ingest_t *g, int32_t slot, int32_t index, const ck_image_u8_t *img, uint32_t fourcc) {
     uint8_t *dst = ck_ingest_frame(g, slot, index);
     if (!dst || !img || !img->buf) return CK_EINVAL;
+    if (g->raw) { // exactly the ring's family, the ring's source geometry, min_stride bytes per row
+        ck_raw_class cls;
+        if (ck_raw_classify(fourcc, &cls) != CK_OK || !ck_raw_same_family(cls, g->cls)) return CK_EUNSUPPORTED;
+        if (img->width != g->sw || img->height != g->sh || img->stride < g->min_stride) return CK_EINVAL;
+        for (int y = 0; y < g->sh; y++) memcpy(dst + (size_t)y * g->rstride, img->buf + (size_t)y * img->stride, (size_t)g->min_stride);
+        return CK_OK;
+    }
     if (!luma_first(fourcc)) return CK_EUNSUPPORTED;
     const ck_handle *h = g->h;
     if (img->width != h->w || img->height != h->h || img->stride < img->width) return CK_EINVAL;
@@ -85,7 +127,11 @@ extern "C" int ck_ingest_write(ck_ingest_t *g, int32_t slot, int32_t index, cons
 extern "C" int ck_ingest_submit(ck_ingest_t *g, int32_t slot, int32_t n) {
     if (!g || slot < 0 || slot >= g->nslots || n < 0 || n > g->h->cfg.max_batch) return CK_EINVAL;
     CK_HIP(hipSetDevice(g->h->device));
-    if (n) CK_HIP(hipMemcpyAsync(g->dev[slot], g->host[slot], g->h->frame_pitch * (size_t)n, hipMemcpyHostToDevice, g->copy));
+    if (n && g->raw) { // the copy and the conversion both run on the copy stream, ahead of the slot's event
+        CK_HIP(hipMemcpyAsync(g->rawdev[slot], g->host[slot], g->rpitch * (size_t)n, hipMemcpyHostToDevice, g->copy));
+        const int rc = ck_launch_rawfmt(g->h, g->copy, {g->rawdev[slot], g->rstride, g->rpitch, g->sw, g->sh}, g->cls, g->fmt.orientation, g->dev[slot], n);
+        if (rc != CK_OK) return rc;
+    } else if (n) CK_HIP(hipMemcpyAsync(g->dev[slot], g->host[slot], g->h->frame_pitch * (size_t)n, hipMemcpyHostToDevice, g->copy));
     CK_HIP(hipEventRecord(g->ready[slot], g->copy));
     g->staged[slot] = n;
     return CK_OK;

@@ -207,6 +207,8 @@ struct ck_handle {
     int32_t *d_tp_counts;      // [max_batch] per-frame counts of ck_last_tag_poses
     // baseline JPEG decode (ck_jpeg.hip, k_jpeg.hip): allocated by the first ck_upload_jpeg / ck_jpeg_luma_batch, grown on demand
     struct ck_jpeg_ws *jpeg;
+    // raw camera formats (ck_rawfmt.hip, k_rawfmt.hip): staging of the host-frame entry points, allocated by the first raw call
+    struct ck_raw_ws *raw;
     bool fmerge_lds_allowed; // k_fmerge's dynamic LDS limit has been raised on this handle's device
 };
 
@@ -307,6 +309,7 @@ int ck_bufs_create(ck_handle *h);
 int ck_buf_alloc(ck_handle *h, const void *member);
 void ck_bufs_free(ck_handle *h);
 void ck_jpeg_free(ck_handle *h); // ck_jpeg.hip: the JPEG workspace
+void ck_raw_free(ck_handle *h);  // ck_rawfmt.hip: the raw-format staging
 int ck_stage_device_frames(ck_handle *h, const uint8_t *d_frames, int n, int stride, int64_t frame_pitch, ck_dev_image *use);
 int ck_run_threshold_segment(ck_handle *h, const ck_dev_image &img, int n);
 // gradient clusters from thresh/labels/csize of frames [0,n)

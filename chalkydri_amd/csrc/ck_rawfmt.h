@@ -1,0 +1,42 @@
+// Raw camera formats -> oriented luma: what the host half (ck_rawfmt.hip, ck_ingest.hip) hands k_rawfmt.hip.
+#ifndef CK_RAWFMT_H
+#define CK_RAWFMT_H
+
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include "chalkydri_hip.h"
+
+// 16-bit fixed-point weights of L(R,G,B) (libjpeg's jccolor.c grey conversion); they sum to 65536
+#define CK_LUMA_R 19595u
+#define CK_LUMA_G 38470u
+#define CK_LUMA_B 7471u
+
+// A fourcc as the kernel sees it: bytes per pixel + where the luma comes from.  Two fourccs with equal classes are one family.
+struct ck_raw_class {
+    int bpp;         // 1: a leading luma plane, 2: packed 4:2:2, 3 / 4: packed colour
+    uint32_t k[3];   // bpp 3 / 4: weight of byte 0, 1, 2 of a pixel.  bpp 2: v_perm_b32 selector that picks the four luma bytes of
+                     // two dwords in order, the one that picks them reversed, the luma's byte offset in a pixel.  bpp 1: unused
+};
+static inline bool ck_raw_same_family(const ck_raw_class &a, const ck_raw_class &b) {
+    return a.bpp == b.bpp && a.k[0] == b.k[0] && a.k[1] == b.k[1] && a.k[2] == b.k[2];
+}
+// CK_OK / CK_EUNSUPPORTED (a fourcc outside the table of §4d)
+int ck_raw_classify(uint32_t fourcc, ck_raw_class *out);
+
+// The source side of one conversion: n frames of sw x sh pixels in device memory, row y of frame f at p + f * pitch + y * stride
+struct ck_raw_src { const uint8_t *p; int stride; size_t pitch; int sw, sh; };
+
+struct ck_handle;
+// k_rawfmt.hip: converts + orients n frames into dst (the handle's staged layout: rows of h->frame_stride, frames of h->frame_pitch)
+int ck_launch_rawfmt(ck_handle *h, hipStream_t st, const ck_raw_src &src, const ck_raw_class &cls, int orientation, uint8_t *dst, int n);
+
+// Staging of the host-frame entry points (ck_handle::raw): allocated by the first raw call, grown on demand (ck_rawfmt.hip)
+struct ck_raw_ws {
+    uint8_t *h_stage; size_t h_cap; // pinned host: [n][sh][stride16] raw rows, stride16 = the minimum stride rounded up to 16
+    uint8_t *d_stage; size_t d_cap; // its device copy; it ends with the last row's last byte the kernel may read
+};
+void ck_raw_free(ck_handle *h);
+
+#endif

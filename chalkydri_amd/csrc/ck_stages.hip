@@ -11,7 +11,7 @@ static int next_pow2(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 // ---- the handle's device buffers ---------------------------------------------------------------------------------------------
 // Every device buffer of ck_handle / ck_stage_ws is one row of ck_bufs[]: allocation (ck_bufs_create in this order; ck_buf_alloc
 // for the ones allocated on first use), release (ck_bufs_free), the per-frame advance of a split batch's views (make_view) and
-// the name CK_POISON=2 prints all walk this table.  A new buffer is a member + a row; ck_jpeg_ws (grown per call) keeps its own.
+// the name CK_POISON=2 prints all walk this table.  A new buffer is a member + a row; ck_jpeg_ws and ck_raw_ws (grown per call) keep their own.
 enum : unsigned {
     CK_BUF_FRAME = 1, // [max_batch][bytes]: a view of the frames from f0 on starts f0 * bytes further
     CK_BUF_TWIN = 2,  // [2][bytes], per handle: the second copy is the one the pieces on stream2 use

@@ -69,6 +69,12 @@ def _bind(L):
     L.ck_jpeg_info.argtypes = [vp, C.c_int64, _P(A.JpegInfo)]
     L.ck_upload_jpeg.argtypes = [vp, _P(A.JpegFrame), i32, u32p]
     L.ck_jpeg_luma_batch.argtypes = [vp, _P(A.JpegFrame), i32, vp, u32p]
+    rf = _P(A.RawFormat)
+    L.ck_raw_layout.argtypes = [rf, i32, i32, _P(i32), _P(i32), _P(i32), _P(C.c_int64)]
+    L.ck_upload_raw.argtypes = [vp, _P(A.ImageU8), i32, rf]
+    L.ck_upload_raw_device.argtypes = [vp, vp, i32, i32, C.c_int64, rf]
+    L.ck_raw_luma_batch.argtypes = [vp, _P(A.ImageU8), i32, rf, vp]
+    L.ck_ingest_create_raw.argtypes = [vp, i32, rf, _P(vp)]
     L._ck_bound = True
     return L
 
@@ -192,6 +198,47 @@ def jpeg_info(data):
     return {k: getattr(info, k) for k, _ in A.JpegInfo._fields_ if k != "pad"}
 
 
+def orientation_code(orientation):
+    """'none' / 'clockwise' / 'rotate-180' / 'counterclockwise' (the reference's serde names) or 0..3 -> CK_ORIENT_*."""
+    if isinstance(orientation, str):
+        if orientation not in A.ORIENTATIONS:
+            raise ValueError(f"orientation must be one of {sorted(A.ORIENTATIONS)}")
+        return A.ORIENTATIONS[orientation]
+    return int(orientation)
+
+
+def raw_format(code, orientation="none"):
+    """ck_raw_format_t from a fourcc string (or its u32) and an orientation."""
+    return A.RawFormat(fourcc(code) if isinstance(code, str) else int(code), orientation_code(orientation))
+
+
+def raw_layout(code, width, height, orientation="none"):
+    """ck_raw_layout: (sw, sh, min_stride, min_bytes) of the source of an oriented width x height frame.  No device needed."""
+    sw, sh, ms, mb = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+    fmt = raw_format(code, orientation)
+    check(_bind(lib()).ck_raw_layout(C.byref(fmt), width, height, C.byref(sw), C.byref(sh), C.byref(ms), C.byref(mb)), "ck_raw_layout")
+    return sw.value, sh.value, ms.value, mb.value
+
+
+def _raw_images(frames, sw, sh):
+    """Raw frames — one uint8 array [n][sh][stride] or a sequence of [sh][stride] arrays (stride in bytes, rows contiguous) ->
+    (ImageU8 array declaring sw x sh, keepalive)."""
+    if isinstance(frames, np.ndarray) and frames.ndim == 2:
+        frames = [frames]
+    keep = []
+    for f in frames:
+        f = np.asarray(f)
+        if f.dtype != np.uint8 or f.ndim != 2 or f.strides[1] != 1:
+            f = np.ascontiguousarray(f, dtype=np.uint8)
+            if f.ndim != 2:
+                raise ValueError("a raw frame is a 2-D uint8 array [rows][bytes]")
+        keep.append(f)
+    arr = (A.ImageU8 * max(len(keep), 1))()
+    for i, f in enumerate(keep):
+        arr[i].buf, arr[i].width, arr[i].height, arr[i].stride = f.ctypes.data, sw, sh, f.strides[0]
+    return arr, keep
+
+
 def _raw_detections(dets):
     """Detection objects, ck_detection_t arrays or an [n] ctypes array -> ctypes array (+ count)."""
     if isinstance(dets, C.Array):
@@ -264,6 +311,38 @@ class AprilTagDetector:
         status = (C.c_uint32 * max(len(keep), 1))()
         check(self._L.ck_jpeg_luma_batch(self._h, arr, len(keep), out.ctypes.data, status), "ck_jpeg_luma_batch")
         return (out, list(status)[:len(keep)]) if return_status else out
+
+    def upload_raw(self, frames, code, orientation="none"):
+        """Raw camera frames ([rows][bytes] each: 'YUYV', 'RGB3', 'BGRA', ... as ck_raw_layout lists them) are converted to luma
+        and turned by `orientation` on the device into the staged frames; the detector's width x height is the ORIENTED frame.
+        detect_batch(None, n=...) / the process and pose calls follow, as after `upload`."""
+        fmt = raw_format(code, orientation)
+        sw, sh, _, _ = raw_layout(fmt.fourcc, self.width, self.height, fmt.orientation)
+        arr, keep = _raw_images(frames, sw, sh)
+        for f in keep:
+            if f.shape[0] < sh:
+                raise ValueError(f"a raw frame needs {sh} rows")
+        check(self._L.ck_upload_raw(self._h, arr, len(keep), C.byref(fmt)), "ck_upload_raw")
+        return len(keep)
+
+    def upload_raw_device(self, ptr, n, stride, frame_pitch, code, orientation="none"):
+        """The same from device-resident frames (a torch tensor's data_ptr(), another decoder's output): no host copy.  The
+        work that produced them must have completed (torch.cuda.synchronize / the producing stream)."""
+        fmt = raw_format(code, orientation)
+        check(self._L.ck_upload_raw_device(self._h, C.c_void_p(ptr), n, stride, frame_pitch, C.byref(fmt)), "ck_upload_raw_device")
+        return n
+
+    def raw_luma(self, frames, code, orientation="none"):
+        """[n][height][width] uint8: the oriented luma the device makes of the raw frames (and leaves staged)."""
+        fmt = raw_format(code, orientation)
+        sw, sh, _, _ = raw_layout(fmt.fourcc, self.width, self.height, fmt.orientation)
+        arr, keep = _raw_images(frames, sw, sh)
+        for f in keep:
+            if f.shape[0] < sh:
+                raise ValueError(f"a raw frame needs {sh} rows")
+        out = np.empty((len(keep), self.height, self.width), np.uint8)
+        check(self._L.ck_raw_luma_batch(self._h, arr, len(keep), C.byref(fmt), out.ctypes.data), "ck_raw_luma_batch")
+        return out
 
     # -- stages -------------------------------------------------------------------------------------------
     def threshold(self, frames=None, n=None):
@@ -387,12 +466,20 @@ def fourcc(code):
 
 class IngestRing:
     """Pinned host slots + asynchronous upload in front of a detector (the pooled host buffers of the reference's camera
-    layer, gst_to_cu.rs:49-72,131-188).  slot_view(s) is a writable numpy view [max_batch][h][stride] of pinned memory."""
+    layer, gst_to_cu.rs:49-72,131-188).  slot_view(s) is a writable numpy view [max_batch][h][stride] of pinned memory.
+    With a fourcc the slots hold RAW frames of that format ([max_batch][sh][raw stride]); submit converts and orients them on
+    the device, and detect / process work as on a plain ring."""
 
-    def __init__(self, detector, n_slots=2):
+    def __init__(self, detector, n_slots=2, fourcc=None, orientation="none"):
         self.det, self._L = detector, detector._L
         g = C.c_void_p()
-        check(self._L.ck_ingest_create(detector._h, n_slots, C.byref(g)), "ck_ingest_create")
+        self.code, self.rows = fourcc, detector.cfg.height
+        if fourcc is None:
+            check(self._L.ck_ingest_create(detector._h, n_slots, C.byref(g)), "ck_ingest_create")
+        else:
+            fmt = raw_format(fourcc, orientation)
+            check(self._L.ck_ingest_create_raw(detector._h, n_slots, C.byref(fmt), C.byref(g)), "ck_ingest_create_raw")
+            self.sw, self.rows, self.min_stride, _ = raw_layout(fmt.fourcc, detector.width, detector.height, fmt.orientation)
         self._g, self.n_slots = g, n_slots
         self.stride = self._L.ck_ingest_stride(g)
 
@@ -404,13 +491,19 @@ class IngestRing:
     def slot_view(self, slot):
         cfg = self.det.cfg
         ptr = self._L.ck_ingest_frame(self._g, slot, 0)
-        pitch = self._L.ck_ingest_frame(self._g, slot, 1) - ptr if cfg.max_batch > 1 else self.stride * cfg.height
+        pitch = self._L.ck_ingest_frame(self._g, slot, 1) - ptr if cfg.max_batch > 1 else self.stride * self.rows
         buf = (C.c_uint8 * (pitch * cfg.max_batch)).from_address(ptr)
-        a = np.frombuffer(buf, np.uint8).reshape(cfg.max_batch, pitch)[:, :self.stride * cfg.height]
-        return a.reshape(cfg.max_batch, cfg.height, self.stride)
+        a = np.frombuffer(buf, np.uint8).reshape(cfg.max_batch, pitch)[:, :self.stride * self.rows]
+        return a.reshape(cfg.max_batch, self.rows, self.stride)
 
-    def write(self, slot, index, frame, code="GREY"):
-        arr, keep = _images(frame)
+    def write(self, slot, index, frame, code=None):
+        """Stride-aware copy of one caller frame into the slot: a luma frame [h][>=w] on a plain ring, a raw frame
+        [sh][>=min_stride bytes] of the ring's format family on a raw ring."""
+        if self.code is None:
+            arr, keep = _images(frame)
+        else:
+            arr, keep = _raw_images(frame, self.sw, self.rows)
+        code = code or self.code or "GREY"
         check(self._L.ck_ingest_write(self._g, slot, index, arr, fourcc(code)), "ck_ingest_write")
 
     def submit(self, slot, n):

@@ -75,11 +75,46 @@ class Handle {
     const ck_config_t &config() const { return cfg_; }
     // AprilTag-3's quad_sigma (chalkydri_hip.h: ck_set_quad_sigma): > 0 blurs, < 0 sharpens the quad image; may change between calls
     void set_quad_sigma(float sigma) { check(ck_set_quad_sigma(h_, sigma), "ck_set_quad_sigma"); }
+    // Raw camera frames (chalkydri_hip.h: ck_upload_raw) converted to luma and turned by fmt.orientation on the device, into the
+    // staged frames; the handle's width x height is the ORIENTED frame, imgs carry the source's sw x sh (ck_raw_layout)
+    void upload_raw(const std::vector<ck_image_u8_t> &imgs, const ck_raw_format_t &fmt) {
+        check(ck_upload_raw(h_, imgs.data(), (int32_t)imgs.size(), &fmt), "ck_upload_raw");
+    }
+    void upload_raw_device(const uint8_t *d_raw, int n, int stride, int64_t frame_pitch, const ck_raw_format_t &fmt) {
+        check(ck_upload_raw_device(h_, d_raw, n, stride, frame_pitch, &fmt), "ck_upload_raw_device");
+    }
+    // the same, and the oriented luma [n][height][width] back on the host
+    std::vector<uint8_t> raw_luma(const std::vector<ck_image_u8_t> &imgs, const ck_raw_format_t &fmt) {
+        std::vector<uint8_t> out(imgs.size() * (size_t)cfg_.width * (size_t)cfg_.height);
+        check(ck_raw_luma_batch(h_, imgs.data(), (int32_t)imgs.size(), &fmt, out.data()), "ck_raw_luma_batch");
+        return out;
+    }
 
   private:
     ck_config_t cfg_{};
     ck_handle_t *h_ = nullptr;
 };
+
+// ck_raw_format_t from a fourcc ("YUYV", "RGB3", "BGR ", ...) and the reference's VideoOrientation serde name
+// (crates/chalkydri_core/src/config.rs:201-207): "none", "clockwise", "rotate-180", "counterclockwise"
+inline ck_raw_format_t raw_format(const std::string &fourcc, const std::string &orientation = "none") {
+    if (fourcc.size() != 4) throw Panic("a fourcc has exactly 4 characters: " + fourcc, CK_EINVAL);
+    ck_raw_format_t f{};
+    for (int i = 0; i < 4; i++) f.fourcc |= (uint32_t)(uint8_t)fourcc[i] << (8 * i);
+    if (orientation == "none") f.orientation = CK_ORIENT_NONE;
+    else if (orientation == "clockwise") f.orientation = CK_ORIENT_CLOCKWISE;
+    else if (orientation == "rotate-180") f.orientation = CK_ORIENT_ROTATE_180;
+    else if (orientation == "counterclockwise") f.orientation = CK_ORIENT_COUNTERCLOCKWISE;
+    else throw Panic("unknown orientation " + orientation, CK_EINVAL);
+    return f;
+}
+struct RawLayout { int32_t sw = 0, sh = 0, min_stride = 0; int64_t min_bytes = 0; };
+// source geometry of an oriented width x height frame (no device needed); throws for a fourcc outside the table
+inline RawLayout raw_layout(const ck_raw_format_t &fmt, int width, int height) {
+    RawLayout l;
+    check(ck_raw_layout(&fmt, width, height, &l.sw, &l.sh, &l.min_stride, &l.min_bytes), "ck_raw_layout");
+    return l;
+}
 
 // What the reference reads from an `apriltag::Detection` (crates/apriltags/src/lib.rs:306-314).
 class Detection {
@@ -586,6 +621,10 @@ class Comm {
 class IngestRing {
   public:
     IngestRing(const std::shared_ptr<Handle> &h, int n_slots = 2) : h_(h) { check(ck_ingest_create(h_->get(), n_slots, &g_), "ck_ingest_create"); }
+    // slots of RAW frames: submit converts and orients them on the device (ck_ingest_create_raw)
+    IngestRing(const std::shared_ptr<Handle> &h, int n_slots, const ck_raw_format_t &fmt) : h_(h) {
+        check(ck_ingest_create_raw(h_->get(), n_slots, &fmt, &g_), "ck_ingest_create_raw");
+    }
     ~IngestRing() { ck_ingest_destroy(g_); }
     IngestRing(const IngestRing &) = delete;
     IngestRing &operator=(const IngestRing &) = delete;
@@ -618,6 +657,10 @@ class AprilTags {
         uint8_t cam_id = 0;                     // lib.rs:256
         int device = 0, max_batch = 1, quad_decimate = 1;
         float quad_sigma = 0.0f;                // AprilTag-3 detector field; 0 = no filter
+        // the camera's raw format ("" = 8-bit luma, else a fourcc of ck_raw_layout's table) and mounting: `process` then takes the
+        // frames as the camera hands them over; width / height / calib are those of the ORIENTED image
+        std::string fourcc;
+        std::string orientation = "none";
     };
     explicit AprilTags(const Config &c)
         : cfg_(c), h_(std::make_shared<Handle>((int)c.width, (int)c.height, c.max_batch, std::vector<std::string>{c.family}, (int)c.bits_corrected,
@@ -644,7 +687,8 @@ class AprilTags {
     std::vector<std::pair<whacknet::VisionMeasurement, bool>> process(const std::vector<ck_image_u8_t> &imgs, const std::vector<std::optional<double>> &gyro) {
         const int n = (int)imgs.size();
         if (n > cfg_.max_batch || gyro.size() != imgs.size()) throw Panic("process: batch larger than max_batch or gyro size mismatch", CK_EINVAL);
-        check(ck_upload_frames(h_->get(), imgs.data(), n), "ck_upload_frames");
+        if (cfg_.fourcc.empty() && cfg_.orientation == "none") check(ck_upload_frames(h_->get(), imgs.data(), n), "ck_upload_frames");
+        else h_->upload_raw(imgs, raw_format(cfg_.fourcc.empty() ? "GREY" : cfg_.fourcc, cfg_.orientation));
         std::vector<double> g(n);
         std::vector<uint8_t> has(n);
         for (int i = 0; i < n; i++) { has[i] = gyro[i].has_value(); g[i] = gyro[i].value_or(0.0); }

@@ -404,7 +404,7 @@ int ck_estimate_tag_poses(ck_handle_t *h, const ck_tag_pose_params_t *pp, const 
  * with n = the frames of that call; the entries of a frame past its count are zero records.  out and counts may be host or
  * device pointers.  Errors as ck_estimate_tag_poses, and CK_EINVAL for cap_per_frame < 1 or when the detection workspace
  * holds no such call's result: no detect / process call since ck_create, a failed one, or a later call that rewrote the
- * workspace: ck_clusters_batch and ck_quads_batch.  ck_upload_frames, ck_threshold_batch, ck_segment_batch,
+ * workspace: ck_clusters_batch and ck_quads_batch.  ck_upload_frames, ck_upload_raw, ck_upload_raw_device, ck_raw_luma_batch, ck_threshold_batch, ck_segment_batch,
  * ck_quad_image_batch, ck_time_threshold_segment, ck_set_quad_sigma, ck_sqpnp_solve_batch, ck_gather_poses, the ck_cat_*
  * and ck_ingest_write / ck_ingest_submit calls leave it as it is. */
 int ck_last_tag_poses(ck_handle_t *h, const ck_tag_pose_params_t *pp, ck_tag_pose_t *out, int32_t cap_per_frame,
@@ -451,6 +451,59 @@ int ck_jpeg_info(const uint8_t *data, int64_t size, ck_jpeg_info_t *out);
 int ck_upload_jpeg(ck_handle_t *h, const ck_jpeg_frame_t *frames, int32_t n, uint32_t *jpeg_status);
 /* The same, then copies the decoded luma out: luma_out is [n][height][width]. */
 int ck_jpeg_luma_batch(ck_handle_t *h, const ck_jpeg_frame_t *frames, int32_t n, uint8_t *luma_out, uint32_t *jpeg_status);
+
+/* ---- raw camera formats and orientation on the device -------------------------------------------------------------------
+ * What the reference does between the camera and AprilTags::process with `videoconvert` + a GRAY8 caps filter and `videoflip`
+ * (crates/chalkydri/src/cameras/pipeline.rs:96-137): raw frames in one of the formats of its buffer layer
+ * (crates/chalkydri/src/cameras/gst_to_cu.rs:152-188) become 8-bit luma, turned by the camera's mounting, on the device, straight
+ * into the staged frames.  DESIGN.md §4d is the contract.  fourcc (four ASCII bytes, little-endian), minimum row stride, luma of
+ * pixel x of a row r[]:
+ *   GREY GRAY Y800 NV12 NV21 I420 YV12   sw             r[x]  (only the leading plane is read)
+ *   YUYV YUY2                            4*ceil(sw/2)   r[2x]
+ *   UYVY                                 4*ceil(sw/2)   r[2x+1]
+ *   RGB3 "RGB "  /  BGR3 "BGR "          3*sw           L(r[3x], r[3x+1], r[3x+2])  /  L(r[3x+2], r[3x+1], r[3x])
+ *   RGBA  /  BGRA                        4*sw           L(r[4x], r[4x+1], r[4x+2])  /  L(r[4x+2], r[4x+1], r[4x]), alpha ignored
+ * L(R,G,B) = (19595 R + 38470 G + 7471 B + 32768) >> 16: the JFIF luma in libjpeg's fixed point, the Y that ck_upload_jpeg
+ * reproduces.  The Y byte of the YUV formats is copied as it is.  Any stride at or above the minimum, any base alignment; bytes
+ * of a row beyond the minimum and the planes behind a luma plane are never read.
+ * The handle's width x height is the ORIENTED frame W x H; the source is sw x sh = W x H (none, rotate-180) or H x W (the
+ * quarter turns).  With S the source's luma: none out[y][x] = S[y][x]; clockwise out[y][x] = S[sh-1-x][y]; rotate-180
+ * out[y][x] = S[sh-1-y][sw-1-x]; counterclockwise out[y][x] = S[x][sw-1-y]. */
+enum {
+    CK_ORIENT_NONE = 0,            /* the reference's VideoOrientation discriminants (chalkydri_core/src/config.rs:201-207) */
+    CK_ORIENT_CLOCKWISE = 1,
+    CK_ORIENT_ROTATE_180 = 2,
+    CK_ORIENT_COUNTERCLOCKWISE = 3
+};
+typedef struct ck_raw_format {
+    uint32_t fourcc;
+    int32_t orientation;
+} ck_raw_format_t;
+/* Host only (no device needed): the source geometry of an oriented width x height frame.  min_bytes = sh * min_stride.
+ * CK_EINVAL: a null pointer, width or height < 1, an orientation outside 0..3; CK_EUNSUPPORTED: a fourcc outside the table.
+ * Every raw entry point validates its format through this. */
+int ck_raw_layout(const ck_raw_format_t *fmt, int32_t width, int32_t height, int32_t *sw, int32_t *sh, int32_t *min_stride,
+                  int64_t *min_bytes);
+/* Host frames (width / height = sw / sh, stride in bytes) -> one pinned staging buffer -> one asynchronous copy -> the convert
+ * kernel on the handle's stream -> the staged frames: after it ck_detect_uploaded, ck_process_uploaded,
+ * ck_time_threshold_segment and ck_last_tag_poses work exactly as after ck_upload_frames.  Returns when the frames are staged.
+ * Errors of ck_raw_layout, and CK_EINVAL: null handle / imgs / buffer, n < 0, a geometry that is not the one ck_raw_layout gives
+ * for the handle, a stride below the minimum.  CK_ECAPACITY: n > max_batch.  CK_ENOMEM: the staging memory (pinned host + device,
+ * n * sh rows of the minimum stride rounded up to 16; allocated by the first raw call, grown on demand; ck_create allocates none
+ * of it) could not grow. */
+int ck_upload_raw(ck_handle_t *h, const ck_image_u8_t *imgs, int32_t n, const ck_raw_format_t *fmt);
+/* The same from device-resident frames (row y of frame f at d_raw + f * frame_pitch + y * stride), no host copy and no staging.
+ * The caller's work on d_raw must have completed; the source may be reused when the call returns.  CK_EINVAL also for
+ * frame_pitch < stride * sh. */
+int ck_upload_raw_device(ck_handle_t *h, const uint8_t *d_raw, int32_t n, int32_t stride, int64_t frame_pitch,
+                         const ck_raw_format_t *fmt);
+/* As ck_upload_raw, then copies the oriented luma out: luma_out is [n][height][width]. */
+int ck_raw_luma_batch(ck_handle_t *h, const ck_image_u8_t *imgs, int32_t n, const ck_raw_format_t *fmt, uint8_t *luma_out);
+/* An ingest ring whose pinned slots hold RAW frames: ck_ingest_stride is the slot's raw row stride, ck_ingest_frame the raw
+ * frame; ck_ingest_write takes exactly the fourccs of the ring's family (CK_EUNSUPPORTED otherwise) and sw x sh frames and copies
+ * min_stride bytes per row; ck_ingest_submit enqueues the copy and the conversion on the ring's copy stream, so the slot's device
+ * frames are oriented luma and ck_detect_ingested / ck_process_ingested work as on a ring of ck_ingest_create. */
+int ck_ingest_create_raw(ck_handle_t *h, int32_t n_slots, const ck_raw_format_t *fmt, ck_ingest_t **out);
 
 /* ---- multi-GPU: the final pose gather ----------------------------------------------------------------------------------
  * Frames shard over GPUs without any data-path collective (one handle, one process or host thread per GPU).  The only
