@@ -98,6 +98,10 @@ class RawFormat(C.Structure):
     _fields_ = [("fourcc", C.c_uint32), ("orientation", C.c_int32)]
 
 
+class PreviewParams(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("width", "height", "quality", "restart_rows", "overlay", "pad")]
+
+
 class VisionMeasurement(C.Structure):
     _fields_ = [("pose_x", C.c_double), ("pose_y", C.c_double), ("pose_rot", C.c_double),
                 ("std_x", C.c_double), ("std_y", C.c_double), ("std_rot", C.c_double), ("ts", C.c_uint64),
@@ -129,6 +133,7 @@ assert C.sizeof(VisionMeasurement) == 64  # crates/whacknet/src/lib.rs:92-95
 assert C.sizeof(TagPoseParams) == 112 and C.sizeof(TagPose) == 296
 assert C.sizeof(JpegFrame) == 16 and C.sizeof(JpegInfo) == 32
 assert C.sizeof(RawFormat) == 8
+assert C.sizeof(PreviewParams) == 24
 
 # per-frame status bits (include/chalkydri_hip.h)
 CK_FRAME_OK, CK_FRAME_POINTS_OVERFLOW, CK_FRAME_CLUSTERS_OVERFLOW, CK_FRAME_QUADS_OVERFLOW, CK_FRAME_DETS_OVERFLOW = 0, 1, 2, 4, 8
@@ -136,6 +141,9 @@ CK_FRAME_UNVERIFIED_ID = 16
 
 # per-frame jpeg_status bits (ck_upload_jpeg / ck_jpeg_luma_batch)
 CK_JPEG_OK, CK_JPEG_UNSUPPORTED, CK_JPEG_GEOMETRY, CK_JPEG_CORRUPT = 0, 1, 2, 4
+
+# per-frame status bits of ck_preview_jpeg
+CK_PREVIEW_OK, CK_PREVIEW_TRUNCATED = 0, 1
 
 # ck_raw_format_t.orientation: the reference's VideoOrientation, by its serde names (chalkydri_core/src/config.rs:201-207)
 CK_ORIENT_NONE, CK_ORIENT_CLOCKWISE, CK_ORIENT_ROTATE_180, CK_ORIENT_COUNTERCLOCKWISE = 0, 1, 2, 3

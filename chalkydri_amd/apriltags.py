@@ -74,6 +74,12 @@ class AprilTags:
         check(det._L.ck_process_uploaded(det._h, n, C.byref(self._pp), g.ctypes.data, has.ctypes.data, out, valid), "ck_process_uploaded")
         return out, np.array(valid[:], bool)
 
+    def preview(self, frames=None, n=None, overlay=True, **kw):
+        """After process_batch: the driver-station JPEGs (bytes each) of the frames just processed — indices into the staged
+        frames, or n for 0..n-1 — scaled and encoded on the device, the tags the call found outlined (overlay=True).  Keyword
+        arguments as AprilTagDetector.preview_jpeg (width=640, height=480, quality=50, restart_rows=0)."""
+        return self.detector.preview_jpeg(frames, n, overlay=overlay, **kw)
+
     def process_raw_batch(self, raw_frames, gyro=None):
         """The camera's frames as it hands them over ([rows][bytes] each, in the task's fourcc): converted to luma and turned by
         the task's orientation on the device, then processed like process_batch."""

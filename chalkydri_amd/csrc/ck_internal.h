@@ -209,6 +209,8 @@ struct ck_handle {
     struct ck_jpeg_ws *jpeg;
     // raw camera formats (ck_rawfmt.hip, k_rawfmt.hip): staging of the host-frame entry points, allocated by the first raw call
     struct ck_raw_ws *raw;
+    // JPEG preview of the staged frames (ck_preview.hip, k_jpegenc.hip): allocated by the first preview call, grown on demand
+    struct ck_preview_ws *preview;
     bool fmerge_lds_allowed; // k_fmerge's dynamic LDS limit has been raised on this handle's device
 };
 
@@ -310,6 +312,7 @@ int ck_buf_alloc(ck_handle *h, const void *member);
 void ck_bufs_free(ck_handle *h);
 void ck_jpeg_free(ck_handle *h); // ck_jpeg.hip: the JPEG workspace
 void ck_raw_free(ck_handle *h);  // ck_rawfmt.hip: the raw-format staging
+void ck_preview_free(ck_handle *h); // ck_preview.hip: the preview encoder's workspace
 int ck_stage_device_frames(ck_handle *h, const uint8_t *d_frames, int n, int stride, int64_t frame_pitch, ck_dev_image *use);
 int ck_run_threshold_segment(ck_handle *h, const ck_dev_image &img, int n);
 // gradient clusters from thresh/labels/csize of frames [0,n)

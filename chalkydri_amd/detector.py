@@ -75,6 +75,12 @@ def _bind(L):
     L.ck_upload_raw_device.argtypes = [vp, vp, i32, i32, C.c_int64, rf]
     L.ck_raw_luma_batch.argtypes = [vp, _P(A.ImageU8), i32, rf, vp]
     L.ck_ingest_create_raw.argtypes = [vp, i32, rf, _P(vp)]
+    pv = _P(A.PreviewParams)
+    L.ck_preview_params_default.argtypes = [pv]
+    L.ck_preview_params_default.restype = None
+    L.ck_preview_layout.argtypes = [pv, i32, i32, _P(i32), _P(i32), _P(C.c_int64)]
+    L.ck_preview_jpeg.argtypes = [vp, pv, vp, i32, vp, C.c_int64, vp, vp]
+    L.ck_preview_luma.argtypes = [vp, pv, vp, i32, vp]
     L._ck_bound = True
     return L
 
@@ -256,6 +262,42 @@ def _raw_detections(dets):
     return arr, len(dets)
 
 
+def preview_params(width=640, height=480, quality=50, restart_rows=0, overlay=False):
+    """ck_preview_params_t; the defaults are the reference's driver-station stream (640 x 480, quality 50)."""
+    pp = A.PreviewParams()
+    _bind(lib()).ck_preview_params_default(C.byref(pp))
+    pp.width, pp.height, pp.quality, pp.restart_rows, pp.overlay = int(width), int(height), int(quality), int(restart_rows), int(bool(overlay))
+    return pp
+
+
+def preview_layout(params, width, height):
+    """ck_preview_layout: (pw, ph, max_bytes) of a preview of a width x height handle.  No device needed."""
+    pw, ph, mb = C.c_int32(), C.c_int32(), C.c_int64()
+    check(_bind(lib()).ck_preview_layout(C.byref(params), width, height, C.byref(pw), C.byref(ph), C.byref(mb)), "ck_preview_layout")
+    return pw.value, ph.value, mb.value
+
+
+def mjpeg_part(jpeg):
+    """One part of the reference's multipart stream (crates/chalkydri/src/cameras/mjpeg.rs:122-128): the boundary, the length and
+    the content type in front of a complete JPEG."""
+    jpeg = bytes(jpeg)
+    return b"--frame\r\nContent-Length: " + str(len(jpeg)).encode("ascii") + b"\r\nContent-Type: image/jpeg\r\n\r\n" + jpeg
+
+
+class MjpegStream:
+    """The reference's rate limit in front of the framing (videorate max-rate 20, drop-only: mjpeg.rs:30-34): part(jpeg, now)
+    gives the framed bytes, or None for a frame that comes sooner than 1 / max_rate seconds after the last one sent."""
+
+    def __init__(self, max_rate=20.0):
+        self.period, self._last = 1.0 / float(max_rate), None
+
+    def part(self, jpeg, now):
+        if self._last is not None and now - self._last < self.period:
+            return None
+        self._last = now
+        return mjpeg_part(jpeg)
+
+
 class AprilTagDetector:
     """One handle = one GPU + its stream; not thread-safe (mirrors `&mut self`)."""
 
@@ -433,6 +475,50 @@ class AprilTagDetector:
         if raw:
             return [[out[i * cap + k] for k in range(counts[i])] for i in range(n)]
         return [[TagPose(out[i * cap + k]) for k in range(counts[i])] for i in range(n)]
+
+    # -- JPEG preview of the staged frames, encoded on the GPU (the driver-station stream) ------------------------------
+    def _preview_in(self, frames, n, width, height, quality, restart_rows, overlay):
+        pp = preview_params(width, height, quality, restart_rows, overlay)
+        pw, ph, max_bytes = preview_layout(pp, self.width, self.height)
+        if frames is None:
+            if n is None:
+                raise ValueError("frames (indices into the staged frames) or n is required")
+            return pp, pw, ph, max_bytes, None, int(n)
+        idx = np.ascontiguousarray(frames, np.int32).reshape(-1)
+        return pp, pw, ph, max_bytes, idx, idx.size
+
+    def preview_jpeg(self, frames=None, n=None, width=640, height=480, quality=50, restart_rows=0, overlay=False, cap=None,
+                     return_status=False):
+        """Baseline JPEG files (bytes each) of staged frames, scaled to width x height (nearest neighbour; never enlarged) and
+        encoded on the device exactly as libjpeg writes them.  frames: indices into the staged frames, or n for 0..n-1.
+        overlay=True outlines the detections of the last detect / process call.  cap: bytes per file (default: the bound of
+        ck_preview_layout); a file that does not fit comes back cut to cap with CK_PREVIEW_TRUNCATED in its status."""
+        pp, pw, ph, max_bytes, idx, n = self._preview_in(frames, n, width, height, quality, restart_rows, overlay)
+        # without a cap the slots are sized for the pixels themselves (a file beyond that is noise at the highest qualities) and
+        # the call is repeated with the bound of ck_preview_layout if a file did not fit; the buffer is kept between calls
+        tries = [min(max_bytes, pw * ph + 1024), max_bytes] if cap is None else [int(cap)]
+        for c in tries:
+            need = max(n, 1) * max(c, 1)
+            if getattr(self, "_pv_buf", None) is None or self._pv_buf.size < need:
+                self._pv_buf = np.empty(need, np.uint8)
+            out = self._pv_buf[:need].reshape(max(n, 1), max(c, 1))
+            sizes = (C.c_int64 * max(n, 1))()
+            status = (C.c_uint32 * max(n, 1))()
+            check(self._L.ck_preview_jpeg(self._h, C.byref(pp), idx.ctypes.data if idx is not None else None, n, out.ctypes.data, c,
+                                          sizes, status), "ck_preview_jpeg")
+            if cap is not None or not any(status[:n]):
+                break
+        files = [out[i, :min(sizes[i], c)].tobytes() for i in range(n)]
+        return (files, list(sizes)[:n], list(status)[:n]) if return_status else files
+
+    def preview_luma(self, frames=None, n=None, width=640, height=480, quality=50, restart_rows=0, overlay=False):
+        """[n][ph][pw] uint8: the scaled (+ overlaid) pixels the encoder is given."""
+        pp, pw, ph, _, idx, n = self._preview_in(frames, n, width, height, quality, restart_rows, overlay)
+        out = np.empty((n, ph, pw), np.uint8)
+        buf = out if n else np.empty(1, np.uint8)
+        check(self._L.ck_preview_luma(self._h, C.byref(pp), idx.ctypes.data if idx is not None else None, n, buf.ctypes.data),
+              "ck_preview_luma")
+        return out
 
     def stage_ms(self):
         ms = A.StageMs()

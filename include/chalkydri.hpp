@@ -218,6 +218,55 @@ inline std::vector<uint8_t> decode_jpeg(Handle &h, const std::vector<std::vector
     return out;
 }
 
+// ---- JPEG preview of the staged frames, encoded on the device (chalkydri_hip.h: ck_preview_jpeg / ck_preview_luma) -------------
+// The reference's driver-station stream (crates/chalkydri/src/cameras/mjpeg.rs): scale to 640 x 480, JPEG at quality 50, multipart
+// framing.  frames: indices into the staged frames; the files equal libjpeg's byte for byte.
+inline ck_preview_params_t preview_params(int width = 640, int height = 480, int quality = 50, int restart_rows = 0, bool overlay = false) {
+    ck_preview_params_t pp;
+    ck_preview_params_default(&pp);
+    pp.width = width; pp.height = height; pp.quality = quality; pp.restart_rows = restart_rows; pp.overlay = overlay ? 1 : 0;
+    return pp;
+}
+inline std::vector<std::vector<uint8_t>> preview_jpeg(Handle &h, const std::vector<int32_t> &frames, const ck_preview_params_t &pp) {
+    int64_t bound = 0;
+    int32_t pw = 0, ph = 0;
+    check(ck_preview_layout(&pp, h.config().width, h.config().height, &pw, &ph, &bound), "ck_preview_layout");
+    const size_t n = frames.size();
+    // slots sized for the pixels themselves first (a file beyond that is noise at the highest qualities); the bound if one did not fit
+    int64_t cap = std::min<int64_t>(bound, (int64_t)pw * ph + 1024);
+    std::vector<uint8_t> out;
+    std::vector<int64_t> sizes(n);
+    for (;;) {
+        out.resize(n * (size_t)cap);
+        check(ck_preview_jpeg(h.get(), &pp, frames.data(), (int32_t)n, out.data(), cap, sizes.data(), nullptr), "ck_preview_jpeg");
+        bool fits = true;
+        for (size_t i = 0; i < n; i++) fits = fits && sizes[i] <= cap;
+        if (fits || cap == bound) break;
+        cap = bound;
+    }
+    std::vector<std::vector<uint8_t>> files(n);
+    for (size_t i = 0; i < n; i++) files[i].assign(out.begin() + i * (size_t)cap, out.begin() + i * (size_t)cap + (size_t)sizes[i]);
+    return files;
+}
+// The scaled (+ overlaid) pixels the encoder is given: [n][ph][pw]; pw / ph come back through the pointers.
+inline std::vector<uint8_t> preview_luma(Handle &h, const std::vector<int32_t> &frames, const ck_preview_params_t &pp, int32_t *pw = nullptr,
+                                         int32_t *ph = nullptr) {
+    int32_t w = 0, hh = 0;
+    check(ck_preview_layout(&pp, h.config().width, h.config().height, &w, &hh, nullptr), "ck_preview_layout");
+    std::vector<uint8_t> out(frames.size() * (size_t)w * (size_t)hh);
+    check(ck_preview_luma(h.get(), &pp, frames.data(), (int32_t)frames.size(), out.data()), "ck_preview_luma");
+    if (pw) *pw = w;
+    if (ph) *ph = hh;
+    return out;
+}
+// One part of the multipart stream (mjpeg.rs:122-128): boundary, length and content type in front of a complete JPEG.
+inline std::vector<uint8_t> mjpeg_part(const std::vector<uint8_t> &jpeg) {
+    const std::string head = "--frame\r\nContent-Length: " + std::to_string(jpeg.size()) + "\r\nContent-Type: image/jpeg\r\n\r\n";
+    std::vector<uint8_t> out(head.begin(), head.end());
+    out.insert(out.end(), jpeg.begin(), jpeg.end());
+    return out;
+}
+
 namespace apriltags {
 
 enum class Color : uint8_t { Black = 0, White = 1, Other = 2 }; // src/utils.rs:2-6

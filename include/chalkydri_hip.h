@@ -405,7 +405,8 @@ int ck_estimate_tag_poses(ck_handle_t *h, const ck_tag_pose_params_t *pp, const 
  * device pointers.  Errors as ck_estimate_tag_poses, and CK_EINVAL for cap_per_frame < 1 or when the detection workspace
  * holds no such call's result: no detect / process call since ck_create, a failed one, or a later call that rewrote the
  * workspace: ck_clusters_batch and ck_quads_batch.  ck_upload_frames, ck_upload_raw, ck_upload_raw_device, ck_raw_luma_batch, ck_threshold_batch, ck_segment_batch,
- * ck_quad_image_batch, ck_time_threshold_segment, ck_set_quad_sigma, ck_sqpnp_solve_batch, ck_gather_poses, the ck_cat_*
+ * ck_quad_image_batch, ck_time_threshold_segment, ck_set_quad_sigma, ck_sqpnp_solve_batch, ck_gather_poses, ck_preview_jpeg,
+ * ck_preview_luma, the ck_cat_*
  * and ck_ingest_write / ck_ingest_submit calls leave it as it is. */
 int ck_last_tag_poses(ck_handle_t *h, const ck_tag_pose_params_t *pp, ck_tag_pose_t *out, int32_t cap_per_frame,
                       int32_t *counts);
@@ -504,6 +505,55 @@ int ck_raw_luma_batch(ck_handle_t *h, const ck_image_u8_t *imgs, int32_t n, cons
  * min_stride bytes per row; ck_ingest_submit enqueues the copy and the conversion on the ring's copy stream, so the slot's device
  * frames are oriented luma and ck_detect_ingested / ck_process_ingested work as on a ring of ck_ingest_create. */
 int ck_ingest_create_raw(ck_handle_t *h, int32_t n_slots, const ck_raw_format_t *fmt, ck_ingest_t **out);
+
+/* ---- JPEG preview of the staged frames, encoded on the device -------------------------------------------------------------
+ * The way back of the camera layer: what the reference's driver-station stream does with videoconvertscale (nearest neighbour,
+ * 640 x 480) and turbojpeg::compress(quality 50) (crates/chalkydri/src/cameras/mjpeg.rs:30-51,108-128), on the staged frames
+ * (whatever staged them: ck_upload_frames, ck_upload_jpeg, ck_upload_raw*), so that only compressed bytes cross the bus.
+ * DESIGN.md §4e is the contract.  Per frame F (W x H, the handle's geometry):
+ *   scale    P[y][x] = F[(2y+1) H / (2 ph)][(2x+1) W / (2 pw)] in integers (pw = W, ph = H is the identity);
+ *   overlay  (overlay = 1) the outlines of the detections the handle's last ck_detect_* / ck_process_* call left on the device
+ *            for frame index frames[i] of that call: corner (px, py) -> pixel ((int)floor(px * pw / W), (int)floor(py * ph / H))
+ *            in double, clamped to the preview; edges corner k -> (k+1) mod 4 by the integer Bresenham line of §4e; every line
+ *            pixel of the frame forms a mask first, then P = P < 128 ? 255 : 0 where the mask is set;
+ *   encode   a 1-component baseline JPEG exactly as libjpeg writes it (jpeg_fdct_islow, jpeg_set_quality(quality, baseline),
+ *            Annex-K luminance Huffman tables, JFIF 1.01 header, DRI = restart_rows * ceil(pw / 8) when restart_rows > 0):
+ *            the file equals libjpeg(-turbo)'s byte for byte.
+ * width / height: 0 = W / H; larger than W / H is clipped to it (the library never enlarges); below 8 or negative is CK_EINVAL. */
+typedef struct ck_preview_params {
+    int32_t width, height;   /* preview size */
+    int32_t quality;         /* 1..100 */
+    int32_t restart_rows;    /* block rows per restart interval, 0 = no restart markers */
+    int32_t overlay;         /* 0 / 1 */
+    int32_t pad;
+} ck_preview_params_t;
+/* per-frame preview status bits */
+enum {
+    CK_PREVIEW_OK = 0,
+    CK_PREVIEW_TRUNCATED = 1 /* the file did not fit cap_per_frame: sizes[i] is the size it needs */
+};
+/* 640 x 480, quality 50, no restart markers, no overlay: the reference's stream (mjpeg.rs:41-49,116) */
+void ck_preview_params_default(ck_preview_params_t *pp);
+/* Host only (no device needed): validates pp against a W x H handle geometry and resolves the preview size; max_bytes = an
+ * upper bound of a file's size (a baseline block is at most 264 bytes before byte stuffing).  pw, ph, max_bytes may be NULL.
+ * CK_EINVAL: a null pp, W or H < 1, width or height negative or (after resolving) below 8, quality outside 1..100,
+ * restart_rows < 0 or restart_rows * ceil(pw / 8) > 65535.  Every preview entry point validates through this. */
+int ck_preview_layout(const ck_preview_params_t *pp, int32_t W, int32_t H, int32_t *pw, int32_t *ph, int64_t *max_bytes);
+/* Encodes n staged frames.  frames: n indices into the staged frames of the last upload (NULL = 0..n-1; an index may repeat).
+ * out: [n][cap_per_frame], a host or a device pointer; sizes[n]: the size of every file; status[n] (may be NULL): CK_PREVIEW_*.
+ * A file that does not fit cap_per_frame writes nothing past its slot, reports the size it needs and CK_PREVIEW_TRUNCATED; the
+ * call still returns CK_OK.  Only the sizes and the bytes used are copied to a host `out`.  Runs on the handle's stream after
+ * whatever was enqueued, returns when the files are complete, and leaves the staged frames and the detection workspace as they
+ * are.  CK_EINVAL: a null handle / pp / out / sizes, n < 0, cap_per_frame < 1, an index outside the staged frames, what
+ * ck_preview_layout refuses, and with overlay = 1: no valid detection result on the handle (ck_last_tag_poses' rule) or an
+ * index that call did not cover.  CK_ECAPACITY: n > max_batch.  CK_ENOMEM: the workspace (allocated by the first preview call,
+ * grown on demand; ck_create allocates none of it: per frame of a call 128 bytes of coefficients + 272 bytes of bit buffer per
+ * 8 x 8 block of the preview, pw * ph / 8 bytes of mask, and the output staging) could not grow. */
+int ck_preview_jpeg(ck_handle_t *h, const ck_preview_params_t *pp, const int32_t *frames, int32_t n, uint8_t *out,
+                    int64_t cap_per_frame, int64_t *sizes, uint32_t *status);
+/* The scaled (+ overlaid) pixels the encoder is given, out [n][ph][pw] (host or device pointer): for tests and for callers with
+ * an encoder of their own.  quality and restart_rows are validated and otherwise unused.  Errors as ck_preview_jpeg. */
+int ck_preview_luma(ck_handle_t *h, const ck_preview_params_t *pp, const int32_t *frames, int32_t n, uint8_t *out);
 
 /* ---- multi-GPU: the final pose gather ----------------------------------------------------------------------------------
  * Frames shard over GPUs without any data-path collective (one handle, one process or host thread per GPU).  The only
