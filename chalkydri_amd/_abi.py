@@ -152,3 +152,5 @@ ORIENTATIONS = {"none": CK_ORIENT_NONE, "clockwise": CK_ORIENT_CLOCKWISE, "rotat
 # the fourccs of the raw entry points (ck_raw_layout answers CK_EUNSUPPORTED to every other one)
 RAW_FOURCCS = ("GREY", "GRAY", "Y800", "NV12", "NV21", "I420", "YV12", "YUYV", "YUY2", "UYVY", "RGB3", "RGB ", "BGR3", "BGR ",
                "RGBA", "BGRA")
+# the names the host layers accept for compressed frames (IngestRing, AprilTags): not raw formats, so not ck_raw_layout's business
+JPEG_FOURCCS = ("MJPG", "JPEG")

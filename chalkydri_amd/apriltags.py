@@ -35,7 +35,11 @@ class AprilTags:
                  max_batch=1, device=0, quad_sigma=0.0, fourcc=None, orientation="none", **cfg):
         """width x height is the image the detector sees, and calib its intrinsics: with an `orientation` ("none", "clockwise",
         "rotate-180", "counterclockwise": the reference's VideoOrientation names) those of the ORIENTED image.  `fourcc` names the
-        raw format of the camera's frames for process_raw_batch ("YUYV", "RGB3", ...; None: 8-bit luma)."""
+        raw format of the camera's frames for process_raw_batch ("YUYV", "RGB3", ...; None: 8-bit luma), or "MJPG" / "JPEG": the
+        camera delivers one JPEG per frame (what the reference's USB cameras do at full rate), decoded and turned on the device."""
+        if fourcc in A.JPEG_FOURCCS:
+            from .detector import orientation_code
+            orientation_code(orientation)                           # (ValueError for an unknown name, before any device work)
         calib = json.loads(calib) if isinstance(calib, str) else calib
         r2c = json.loads(robot_to_cam) if isinstance(robot_to_cam, str) else robot_to_cam
         m = calib["OpenCVModel5"]
@@ -83,8 +87,13 @@ class AprilTags:
     def process_raw_batch(self, raw_frames, gyro=None):
         """The camera's frames as it hands them over ([rows][bytes] each, in the task's fourcc): converted to luma and turned by
         the task's orientation on the device, then processed like process_batch."""
-        n = self.detector.upload_raw(raw_frames, self.fourcc or "GREY", self.orientation)
+        if self.fourcc in A.JPEG_FOURCCS:   # one bytes object per frame
+            n = self.detector.upload_jpeg(raw_frames, self.orientation)
+        else:
+            n = self.detector.upload_raw(raw_frames, self.fourcc or "GREY", self.orientation)
         return self.process_batch(None, gyro, n=n)
+
+    process_raw = process_raw_batch
 
     def process_uploaded_into(self, n, gyro_ptr, has_gyro_ptr, out_ptr, valid_ptr):
         """Runs the whole path on the uploaded frames; every pointer may be host or device memory (no host round trip when

@@ -10,6 +10,7 @@
 #include <new>
 
 #include "ck_internal.h"
+#include "ck_jpeg.h"
 #include "ck_rawfmt.h"
 
 struct ck_ingest {
@@ -29,6 +30,10 @@ struct ck_ingest {
     int sw, sh, min_stride, rstride;
     size_t rpitch;
     uint8_t *rawdev[8];
+    // a ring of ck_ingest_create_jpeg: no pinned luma slots (host[] stays null); the compressed frames, their staging and the decode
+    // workspace of every slot live in `jpeg` (ck_jpeg.hip), and submit decodes them into dev[]
+    ck_jpeg_slots *jpeg;
+    bool pending[8]; // the slot's last submit may still be reading its staging (cleared once ready[slot] has been waited for)
 };
 
 static bool luma_first(uint32_t fourcc) {
@@ -37,7 +42,8 @@ static bool luma_first(uint32_t fourcc) {
            fourcc == cc("I420") || fourcc == cc("YV12");
 }
 
-static int ingest_create(ck_handle_t *h, int32_t n_slots, const ck_raw_format_t *fmt, ck_ingest_t **out) {
+static int ingest_create(ck_handle_t *h, int32_t n_slots, const ck_raw_format_t *fmt, ck_ingest_t **out, bool jpeg = false,
+                         int32_t orientation = 0, int64_t max_frame_bytes = 0) {
     if (!h || !out || n_slots < 1 || n_slots > 8) return CK_EINVAL;
     *out = nullptr;
     int32_t sw = 0, sh = 0, min_stride = 0;
@@ -64,7 +70,7 @@ static int ingest_create(ck_handle_t *h, int32_t n_slots, const ck_raw_format_t 
     }
     hipError_t e = hipStreamCreateWithFlags(&g->copy, hipStreamNonBlocking);
     for (int s = 0; s < n_slots && e == hipSuccess; s++) {
-        e = hipHostMalloc(reinterpret_cast<void **>(&g->host[s]), g->slot_bytes, hipHostMallocDefault);
+        if (!jpeg) e = hipHostMalloc(reinterpret_cast<void **>(&g->host[s]), g->slot_bytes, hipHostMallocDefault);
         if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&g->dev[s]), dev_bytes);
         if (e == hipSuccess && g->raw) e = hipMalloc(reinterpret_cast<void **>(&g->rawdev[s]), g->slot_bytes);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&g->ready[s], hipEventDisableTiming);
@@ -75,8 +81,17 @@ static int ingest_create(ck_handle_t *h, int32_t n_slots, const ck_raw_format_t 
         ck_ingest_destroy(g);
         return CK_ENOMEM;
     }
+    if (jpeg) {
+        const int rc = ck_jpeg_slots_create(h, n_slots, orientation, max_frame_bytes, &g->jpeg);
+        if (rc != CK_OK) { ck_ingest_destroy(g); return rc; }
+    }
     *out = g;
     return CK_OK;
+}
+
+extern "C" int ck_ingest_create_jpeg(ck_handle_t *h, int32_t n_slots, int32_t orientation, int64_t max_frame_bytes, ck_ingest_t **out) {
+    if (orientation < CK_ORIENT_NONE || orientation > CK_ORIENT_COUNTERCLOCKWISE || max_frame_bytes < 0) return CK_EINVAL;
+    return ingest_create(h, n_slots, nullptr, out, true, orientation, max_frame_bytes);
 }
 
 extern "C" int ck_ingest_create(ck_handle_t *h, int32_t n_slots, ck_ingest_t **out) { return ingest_create(h, n_slots, nullptr, out); }
@@ -97,17 +112,19 @@ extern "C" void ck_ingest_destroy(ck_ingest_t *g) {
         if (g->ready[s]) (void)hipEventDestroy(g->ready[s]);
     }
     if (g->copy) (void)hipStreamDestroy(g->copy);
+    ck_jpeg_slots_free(g->jpeg);
     delete g;
 }
 
-extern "C" int32_t ck_ingest_stride(const ck_ingest_t *g) { return !g ? 0 : g->raw ? g->rstride : g->h->frame_stride; }
+extern "C" int32_t ck_ingest_stride(const ck_ingest_t *g) { return !g || g->jpeg ? 0 : g->raw ? g->rstride : g->h->frame_stride; }
 
 extern "C" uint8_t *ck_ingest_frame(ck_ingest_t *g, int32_t slot, int32_t index) {
-    if (!g || slot < 0 || slot >= g->nslots || index < 0 || index >= g->h->cfg.max_batch) return nullptr;
+    if (!g || g->jpeg || slot < 0 || slot >= g->nslots || index < 0 || index >= g->h->cfg.max_batch) return nullptr;
     return g->host[slot] + (size_t)index * (g->raw ? g->rpitch : g->h->frame_pitch);
 }
 
 extern "C" int ck_ingest_write(ck_ingest_t *g, int32_t slot, int32_t index, const ck_image_u8_t *img, uint32_t fourcc) {
+    if (g && g->jpeg) return CK_EUNSUPPORTED; // (compressed frames go through ck_ingest_write_jpeg)
     uint8_t *dst = ck_ingest_frame(g, slot, index);
     if (!dst || !img || !img->buf) return CK_EINVAL;
     if (g->raw) { // exactly the ring's family, the ring's source geometry, min_stride bytes per row
@@ -124,10 +141,38 @@ extern "C" int ck_ingest_write(ck_ingest_t *g, int32_t slot, int32_t index, cons
     return CK_OK;
 }
 
+extern "C" int ck_ingest_write_jpeg(ck_ingest_t *g, int32_t slot, int32_t index, const uint8_t *data, int64_t size) {
+    if (!g || !g->jpeg || !data || size < 4 || slot < 0 || slot >= g->nslots || index < 0 || index >= g->h->cfg.max_batch) return CK_EINVAL;
+    if (g->pending[slot]) { // (a caller that keeps the header's rule never waits here: the call that processed the slot already has)
+        CK_HIP(hipSetDevice(g->h->device));
+        CK_HIP(hipEventSynchronize(g->ready[slot]));
+        g->pending[slot] = false;
+    }
+    return ck_jpeg_slots_write(g->jpeg, slot, index, data, size);
+}
+
+extern "C" int ck_ingest_jpeg_status(ck_ingest_t *g, int32_t slot, int32_t n, uint32_t *jpeg_status) {
+    if (!g || !g->jpeg || !jpeg_status || slot < 0 || slot >= g->nslots || n != g->staged[slot]) return CK_EINVAL;
+    if (n == 0) return CK_OK;
+    CK_HIP(hipSetDevice(g->h->device));
+    CK_HIP(hipEventSynchronize(g->ready[slot]));
+    g->pending[slot] = false;
+    memcpy(jpeg_status, ck_jpeg_slots_status(g->jpeg, slot), sizeof(uint32_t) * (size_t)n);
+    return CK_OK;
+}
+
 extern "C" int ck_ingest_submit(ck_ingest_t *g, int32_t slot, int32_t n) {
     if (!g || slot < 0 || slot >= g->nslots || n < 0 || n > g->h->cfg.max_batch) return CK_EINVAL;
     CK_HIP(hipSetDevice(g->h->device));
-    if (n && g->raw) { // the copy and the conversion both run on the copy stream, ahead of the slot's event
+    if (g->jpeg) { // head copy, payload copy, decode, oriented IDCT and the status copy, all on the copy stream ahead of the slot's event
+        if (g->pending[slot]) { // the slot's staging and workspace may still serve its last submit
+            CK_HIP(hipEventSynchronize(g->ready[slot]));
+            g->pending[slot] = false;
+        }
+        const int rc = ck_jpeg_slots_submit(g->jpeg, slot, n, g->copy, {g->dev[slot], g->h->frame_stride, g->h->frame_pitch});
+        if (rc != CK_OK) return rc;
+        g->pending[slot] = n > 0;
+    } else if (n && g->raw) { // the copy and the conversion both run on the copy stream, ahead of the slot's event
         CK_HIP(hipMemcpyAsync(g->rawdev[slot], g->host[slot], g->rpitch * (size_t)n, hipMemcpyHostToDevice, g->copy));
         const int rc = ck_launch_rawfmt(g->h, g->copy, {g->rawdev[slot], g->rstride, g->rpitch, g->sw, g->sh}, g->cls, g->fmt.orientation, g->dev[slot], n);
         if (rc != CK_OK) return rc;
@@ -145,7 +190,9 @@ extern "C" int ck_detect_ingested(ck_ingest_t *g, int32_t slot, int32_t n, ck_de
     ck_handle *h = g->h;
     CK_HIP(hipSetDevice(h->device));
     CK_HIP(hipStreamWaitEvent(h->stream, g->ready[slot], 0));
-    return ck_detect_frames(h, {g->dev[slot], h->frame_stride, h->frame_pitch}, n, dets, cap, counts, status);
+    const int rc = ck_detect_frames(h, {g->dev[slot], h->frame_stride, h->frame_pitch}, n, dets, cap, counts, status);
+    if (rc == CK_OK) g->pending[slot] = false; // (the results are on the host: the stream, and the event it waited for, are done)
+    return rc;
 }
 
 extern "C" int ck_process_ingested(ck_ingest_t *g, int32_t slot, int32_t n, const ck_process_params_t *pp, const double *gyro,
@@ -155,5 +202,7 @@ extern "C" int ck_process_ingested(ck_ingest_t *g, int32_t slot, int32_t n, cons
     ck_handle *h = g->h;
     CK_HIP(hipSetDevice(h->device));
     CK_HIP(hipStreamWaitEvent(h->stream, g->ready[slot], 0));
-    return ck_process_frames(h, {g->dev[slot], h->frame_stride, h->frame_pitch}, n, pp, gyro, has_gyro, out, valid);
+    const int rc = ck_process_frames(h, {g->dev[slot], h->frame_stride, h->frame_pitch}, n, pp, gyro, has_gyro, out, valid);
+    if (rc == CK_OK) g->pending[slot] = false;
+    return rc;
 }

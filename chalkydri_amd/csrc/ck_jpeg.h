@@ -2,6 +2,7 @@
 #ifndef CK_JPEG_H
 #define CK_JPEG_H
 
+#include <hip/hip_runtime.h>
 #include <stdint.h>
 
 constexpr int CK_JPEG_SUB_BITS = 512;       // bits of scan one lane decodes speculatively (a subsequence)
@@ -51,7 +52,8 @@ struct ck_jpeg_desc {
     uint16_t dc[3], ac[3]; // indices of the scan components' tables in the table area (unused entries 0)
 };
 
-// Device workspace of the JPEG path (ck_handle::jpeg), grown on demand (ck_jpeg.hip).
+// Device workspace of a JPEG decode in flight: the handle's (ck_handle::jpeg, grown on demand) and one per slot of a JPEG ingest
+// ring (sized once by ck_ingest_create_jpeg), ck_jpeg.hip.
 struct ck_jpeg_ws {
     uint8_t *h_stage; size_t stage_cap;     // pinned host staging: descriptors | Huffman tables | quant tables | payloads
     uint8_t *d_in; size_t in_cap;           // its device copy
@@ -64,8 +66,21 @@ struct ck_jpeg_ws {
 };
 
 struct ck_handle;
-// k_jpeg.hip: the per-frame decode and the IDCT of n described frames into the handle's staged frames (statuses in jpeg->d_status)
-int ck_launch_jpeg(ck_handle *h, int n, const ck_jpeg_desc *d_desc, const ck_jpeg_huff *d_huff, const int32_t *d_qt, const uint8_t *d_raw,
-                   size_t coef_frame_blocks);
+struct ck_dev_image;
+// k_jpeg.hip: the per-frame decode and the IDCT of n described frames on stream s, with workspace J, into the frames `dst`
+// (statuses in J.d_status).  The streams are sw x sh; dst holds them turned by `orientation` (CK_ORIENT_*).
+int ck_launch_jpeg(const ck_jpeg_ws &J, hipStream_t s, int n, const ck_jpeg_desc *d_desc, const ck_jpeg_huff *d_huff, const int32_t *d_qt,
+                   const uint8_t *d_raw, size_t coef_frame_blocks, const ck_dev_image &dst, int sw, int sh, int orientation);
+
+// The JPEG half of an ingest ring (ck_ingest_create_jpeg; ck_jpeg.hip): per slot one workspace sized once for max_batch frames of
+// at most max_frame_bytes, the parsed headers of the frames written since the slot's last submit, and which indices they are.
+struct ck_jpeg_slots;
+int ck_jpeg_slots_create(ck_handle *h, int n_slots, int orientation, int64_t max_frame_bytes, ck_jpeg_slots **out);
+void ck_jpeg_slots_free(ck_jpeg_slots *q);
+// parse + copy of the scan into the slot's pinned staging (the caller has made sure no earlier submit still reads it)
+int ck_jpeg_slots_write(ck_jpeg_slots *q, int slot, int index, const uint8_t *data, int64_t size);
+// descriptors + merged tables of frames [0, n), then copy, decode, IDCT and the status copy enqueued on s; no synchronisation
+int ck_jpeg_slots_submit(ck_jpeg_slots *q, int slot, int n, hipStream_t s, const ck_dev_image &dst);
+const uint32_t *ck_jpeg_slots_status(const ck_jpeg_slots *q, int slot); // pinned [max_batch]: valid once the submit's work is done
 
 #endif

@@ -1,6 +1,7 @@
 // Baseline JPEG (MJPEG) luma decode: the host half.  Parses each frame's markers up to SOS (never an entropy-coded byte),
 // deduplicates the Huffman and quantisation tables of the batch, builds libjpeg's canonical decode tables, packs the frame
 // descriptors and the payloads into one pinned buffer and copies it with one asynchronous copy; k_jpeg.hip does the rest.
+#include <algorithm>
 #include <map>
 #include <new>
 #include <string.h>
@@ -217,21 +218,21 @@ void derive(const HuffSpec &t, ck_jpeg_huff &o) {
 size_t al16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 template <typename T>
-int grow_dev(T **p, size_t *cap, size_t need) {
+int grow_dev(T **p, size_t *cap, size_t need, bool exact = false) {
     if (need <= *cap) return CK_OK;
     (void)ck_free_dev(*p);
     *p = nullptr; *cap = 0;
-    const size_t want = need + need / 4;
+    const size_t want = exact ? need : need + need / 4;
     CK_HIP_ALLOC(ck_malloc_dev(p, want));
     *cap = want;
     return CK_OK;
 }
 
-int grow_host(uint8_t **p, size_t *cap, size_t need) {
+int grow_host(uint8_t **p, size_t *cap, size_t need, bool exact = false) {
     if (need <= *cap) return CK_OK;
     if (*p) (void)hipHostFree(*p);
     *p = nullptr; *cap = 0;
-    const size_t want = need + need / 4;
+    const size_t want = exact ? need : need + need / 4;
     hipError_t e = hipHostMalloc(reinterpret_cast<void **>(p), want, hipHostMallocDefault);
     if (e != hipSuccess) {
         (void)hipGetLastError();
@@ -242,35 +243,12 @@ int grow_host(uint8_t **p, size_t *cap, size_t need) {
     return CK_OK;
 }
 
-int jpeg_run(ck_handle *h, const ck_jpeg_frame_t *frames, int n, uint32_t *jpeg_status) {
-    CK_HIP(hipSetDevice(h->device));
-    if (!h->jpeg) {
-        h->jpeg = new (std::nothrow) ck_jpeg_ws();
-        if (!h->jpeg) return CK_ENOMEM;
-        memset(h->jpeg, 0, sizeof *h->jpeg);
-        ck_jpeg_ws &J = *h->jpeg;
-        if (hipHostMalloc(reinterpret_cast<void **>(&J.h_status), sizeof(uint32_t) * (size_t)h->cfg.max_batch, hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError();
-            J.h_status = nullptr;
-            ck_jpeg_free(h);
-            return CK_ENOMEM;
-        }
-        size_t cap = 0;
-        int rc = grow_dev(&J.d_status, &cap, sizeof(uint32_t) * (size_t)h->cfg.max_batch);
-        if (rc != CK_OK) { ck_jpeg_free(h); return rc; }
-    }
-    ck_jpeg_ws &J = *h->jpeg;
-    if (n == 0) {
-        h->n_staged = 0;
-        return CK_OK;
-    }
-    // ---- parse + deduplicate --------------------------------------------------------------------------------------------------
-    std::vector<Parsed> P((size_t)n);
-    std::vector<ck_jpeg_desc> D((size_t)n);
+// The Huffman and quantisation tables of a batch, each distinct one once, in the device layout
+struct Tables {
     std::vector<ck_jpeg_huff> tabs;
     std::vector<int32_t> qts;
     std::map<std::vector<uint8_t>, int> tab_ix, qt_ix;
-    auto table_index = [&](const HuffSpec &t) {
+    int huff(const HuffSpec &t) {
         std::vector<uint8_t> key(t.bits, t.bits + 17);
         key.insert(key.end(), t.vals, t.vals + t.nvals);
         auto it = tab_ix.find(key);
@@ -280,93 +258,178 @@ int jpeg_run(ck_handle *h, const ck_jpeg_frame_t *frames, int n, uint32_t *jpeg_
         const int ix = (int)tabs.size() - 1;
         tab_ix.emplace(std::move(key), ix);
         return ix;
-    };
-    // the Y coefficient store of a frame: the largest MCU grid the handle's geometry can have (2 x 2 sampling)
-    const size_t coef_frame_blocks = (size_t)((h->w + 15) / 16) * 2 * (size_t)((h->h + 15) / 16) * 2;
+    }
+    int quant(const uint16_t *q) {
+        std::vector<uint8_t> key(reinterpret_cast<const uint8_t *>(q), reinterpret_cast<const uint8_t *>(q) + 128);
+        auto it = qt_ix.find(key);
+        if (it == qt_ix.end()) {
+            it = qt_ix.emplace(std::move(key), (int)(qts.size() / 64)).first;
+            for (int k = 0; k < 64; k++) qts.push_back(q[k]);
+        }
+        return it->second;
+    }
+    void finish() {
+        if (tabs.empty()) tabs.emplace_back(); // (every frame bad: the kernels still get valid pointers)
+        if (qts.empty()) qts.assign(64, 0);
+    }
+};
+
+// the Y coefficient store of a frame: the largest MCU grid a sw x sh stream can have (2 x 2 sampling)
+size_t coef_blocks(int sw, int sh) { return (size_t)((sw + 15) / 16) * 2 * (size_t)((sh + 15) / 16) * 2; }
+
+// The descriptor of one frame of `size` bytes that parse() answered with rc, for sw x sh streams: everything but its three
+// offsets.  d.status != 0: the frame is staged as zeros and has no payload.
+void describe(const Parsed &p, int rc, int64_t size, int sw, int sh, Tables &T, ck_jpeg_desc &d) {
+    memset(&d, 0, sizeof d);
+    if (rc != CK_OK) { d.status = rc == CK_EUNSUPPORTED ? CK_JPEG_UNSUPPORTED : CK_JPEG_CORRUPT; return; }
+    if (p.info.width != sw || p.info.height != sh) { d.status = CK_JPEG_GEOMETRY; return; }
+    const int64_t raw_len = size - p.scan_off;
+    if (raw_len > ((int64_t)1 << 28)) { d.status = CK_JPEG_UNSUPPORTED; return; } // bit positions are 32-bit
+    const int H = p.ncomp == 1 ? 1 : p.info.h_samp, V = p.ncomp == 1 ? 1 : p.info.v_samp;
+    d.mcux = (uint32_t)((sw + 8 * H - 1) / (8 * H));
+    const uint32_t mcuy = (uint32_t)((sh + 8 * V - 1) / (8 * V));
+    d.nmcu = d.mcux * mcuy;
+    d.nyb = (uint32_t)(H * V);
+    d.bpm = p.ncomp == 1 ? 1u : d.nyb + 2;
+    d.hs = (uint32_t)H;
+    d.yblk_stride = d.mcux * H;
+    d.yblk_rows = mcuy * V;
+    d.restart = p.info.restart_interval ? (uint32_t)p.info.restart_interval : d.nmcu;
+    d.nint = (d.nmcu + d.restart - 1) / d.restart;
+    d.raw_len = (uint32_t)raw_len;
+    d.sub_cap = d.nint + (uint32_t)(((uint64_t)raw_len * 8 + CK_JPEG_SUB_BITS - 1) / CK_JPEG_SUB_BITS) + 1;
+    for (int c = 0; c < p.ncomp; c++) {
+        const HuffSpec &dc = p.dc[p.scan_td[c]].present ? p.dc[p.scan_td[c]] : std_table(0, p.scan_td[c]);
+        const HuffSpec &ac = p.ac[p.scan_ta[c]].present ? p.ac[p.scan_ta[c]] : std_table(1, p.scan_ta[c]);
+        d.dc[c] = (uint16_t)T.huff(dc);
+        d.ac[c] = (uint16_t)T.huff(ac);
+    }
+    d.qt = (uint32_t)T.quant(p.qt[p.comp_tq[0]]);
+}
+
+// The staging buffer of a call: descriptors | tables | quant tables | payloads
+struct Layout {
+    size_t off_tab, off_qt, off_raw, head_bytes; // head_bytes: what precedes the payloads, unpadded
+};
+Layout layout(int n, const Tables &T) {
+    Layout L;
+    L.off_tab = al16(sizeof(ck_jpeg_desc) * (size_t)n);
+    L.off_qt = L.off_tab + sizeof(ck_jpeg_huff) * T.tabs.size();
+    L.head_bytes = L.off_qt + sizeof(int32_t) * T.qts.size();
+    L.off_raw = al16(L.head_bytes);
+    return L;
+}
+void stage_head(uint8_t *S, const Layout &L, const ck_jpeg_desc *D, int n, const Tables &T) {
+    memcpy(S, D, sizeof(ck_jpeg_desc) * (size_t)n);
+    memcpy(S + L.off_tab, T.tabs.data(), sizeof(ck_jpeg_huff) * T.tabs.size());
+    memcpy(S + L.off_qt, T.qts.data(), sizeof(int32_t) * T.qts.size());
+}
+// one frame's scan and the zeros that pad its region to raw_len + 4 rounded up to 16
+void stage_scan(uint8_t *dst, const uint8_t *scan, uint32_t raw_len) {
+    memcpy(dst, scan, raw_len);
+    memset(dst + raw_len, 0, al16((size_t)raw_len + 4) - raw_len);
+}
+
+// the status array of a workspace (fixed size) and the buffers whose size follows the streams
+int ws_status(ck_jpeg_ws &J, int max_batch) {
+    if (hipHostMalloc(reinterpret_cast<void **>(&J.h_status), sizeof(uint32_t) * (size_t)max_batch, hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        J.h_status = nullptr;
+        return CK_ENOMEM;
+    }
+    size_t cap = 0;
+    return grow_dev(&J.d_status, &cap, sizeof(uint32_t) * (size_t)max_batch);
+}
+// (exact: a ring's workspace never grows, so it gets no headroom)
+int ws_reserve(ck_jpeg_ws &J, size_t stage_bytes, size_t raw_bytes, size_t n_int, size_t n_sub, size_t coef_blocks_total, bool exact = false) {
+    int rc = grow_host(&J.h_stage, &J.stage_cap, stage_bytes, exact);
+    if (rc == CK_OK) rc = grow_dev(&J.d_in, &J.in_cap, stage_bytes, exact);
+    if (rc == CK_OK) rc = grow_dev(&J.d_compact, &J.compact_cap, raw_bytes ? raw_bytes : 16, exact);
+    if (rc == CK_OK) rc = grow_dev(&J.d_int, &J.int_cap, sizeof(uint32_t) * (n_int ? n_int : 1), exact);
+    if (rc == CK_OK) rc = grow_dev(&J.d_sub, &J.sub_cap, sizeof(ck_jpeg_sub) * (n_sub ? n_sub : 1), exact);
+    if (rc == CK_OK) rc = grow_dev(&J.d_coef, &J.coef_cap, sizeof(int16_t) * 64 * coef_blocks_total, exact);
+    return rc;
+}
+void ws_release(ck_jpeg_ws &J) {
+    if (J.h_stage) (void)hipHostFree(J.h_stage);
+    if (J.h_status) (void)hipHostFree(J.h_status);
+    (void)ck_free_dev(J.d_in); (void)ck_free_dev(J.d_compact); (void)ck_free_dev(J.d_int); (void)ck_free_dev(J.d_sub);
+    (void)ck_free_dev(J.d_coef); (void)ck_free_dev(J.d_status);
+    memset(&J, 0, sizeof J);
+}
+
+// decode + IDCT of the n frames whose staging (layout L, payloads at off_raw) is on its way to J.d_in on stream s, into dst turned by
+// `orientation`, and the statuses on their way back to J.h_status: everything enqueued, nothing awaited
+int enqueue_decode(const ck_jpeg_ws &J, hipStream_t s, int n, const Layout &L, size_t off_raw, const ck_dev_image &dst, int sw, int sh,
+                   int orientation) {
+    const int rc = ck_launch_jpeg(J, s, n, reinterpret_cast<const ck_jpeg_desc *>(J.d_in), reinterpret_cast<const ck_jpeg_huff *>(J.d_in + L.off_tab),
+                                  reinterpret_cast<const int32_t *>(J.d_in + L.off_qt), J.d_in + off_raw, coef_blocks(sw, sh), dst, sw, sh, orientation);
+    if (rc != CK_OK) return rc;
+    CK_HIP(hipMemcpyAsync(J.h_status, J.d_status, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
+    return CK_OK;
+}
+
+void source_size(const ck_handle *h, int orientation, int *sw, int *sh) {
+    const bool quarter = orientation == CK_ORIENT_CLOCKWISE || orientation == CK_ORIENT_COUNTERCLOCKWISE;
+    *sw = quarter ? h->h : h->w;
+    *sh = quarter ? h->w : h->h;
+}
+
+// ck_upload_jpeg[_oriented]: the handle's workspace, the handle's stream, the staged frames, and the two synchronisations
+int jpeg_run(ck_handle *h, const ck_jpeg_frame_t *frames, int n, int orientation, uint32_t *jpeg_status) {
+    CK_HIP(hipSetDevice(h->device));
+    if (!h->jpeg) {
+        h->jpeg = new (std::nothrow) ck_jpeg_ws();
+        if (!h->jpeg) return CK_ENOMEM;
+        memset(h->jpeg, 0, sizeof *h->jpeg);
+        const int rc = ws_status(*h->jpeg, h->cfg.max_batch);
+        if (rc != CK_OK) { ck_jpeg_free(h); return rc; }
+    }
+    ck_jpeg_ws &J = *h->jpeg;
+    if (n == 0) {
+        h->n_staged = 0;
+        return CK_OK;
+    }
+    int sw, sh;
+    source_size(h, orientation, &sw, &sh);
+    // ---- parse + deduplicate --------------------------------------------------------------------------------------------------
+    std::vector<Parsed> P((size_t)n);
+    std::vector<ck_jpeg_desc> D((size_t)n);
+    Tables T;
     uint64_t raw_total = 0, int_total = 0, sub_total = 0;
     for (int f = 0; f < n; f++) {
-        Parsed &p = P[f];
         ck_jpeg_desc &d = D[f];
-        memset(&d, 0, sizeof d);
-        const int rc = parse(frames[f].data, frames[f].size, p);
-        if (rc != CK_OK) { d.status = rc == CK_EUNSUPPORTED ? CK_JPEG_UNSUPPORTED : CK_JPEG_CORRUPT; continue; }
-        if (p.info.width != h->w || p.info.height != h->h) { d.status = CK_JPEG_GEOMETRY; continue; }
-        const int64_t raw_len = frames[f].size - p.scan_off;
-        if (raw_len > ((int64_t)1 << 28)) { d.status = CK_JPEG_UNSUPPORTED; continue; } // bit positions are 32-bit
-        const int H = p.ncomp == 1 ? 1 : p.info.h_samp, V = p.ncomp == 1 ? 1 : p.info.v_samp;
-        d.mcux = (uint32_t)((h->w + 8 * H - 1) / (8 * H));
-        const uint32_t mcuy = (uint32_t)((h->h + 8 * V - 1) / (8 * V));
-        d.nmcu = d.mcux * mcuy;
-        d.nyb = (uint32_t)(H * V);
-        d.bpm = p.ncomp == 1 ? 1u : d.nyb + 2;
-        d.hs = (uint32_t)H;
-        d.yblk_stride = d.mcux * H;
-        d.yblk_rows = mcuy * V;
-        d.restart = p.info.restart_interval ? (uint32_t)p.info.restart_interval : d.nmcu;
-        d.nint = (d.nmcu + d.restart - 1) / d.restart;
-        d.raw_len = (uint32_t)raw_len;
-        d.sub_cap = d.nint + (uint32_t)(((uint64_t)raw_len * 8 + CK_JPEG_SUB_BITS - 1) / CK_JPEG_SUB_BITS) + 1;
-        for (int c = 0; c < p.ncomp; c++) {
-            const HuffSpec &dc = p.dc[p.scan_td[c]].present ? p.dc[p.scan_td[c]] : std_table(0, p.scan_td[c]);
-            const HuffSpec &ac = p.ac[p.scan_ta[c]].present ? p.ac[p.scan_ta[c]] : std_table(1, p.scan_ta[c]);
-            d.dc[c] = (uint16_t)table_index(dc);
-            d.ac[c] = (uint16_t)table_index(ac);
-        }
-        {
-            const uint16_t *q = p.qt[p.comp_tq[0]];
-            std::vector<uint8_t> key(reinterpret_cast<const uint8_t *>(q), reinterpret_cast<const uint8_t *>(q) + 128);
-            auto it = qt_ix.find(key);
-            if (it == qt_ix.end()) {
-                it = qt_ix.emplace(std::move(key), (int)(qts.size() / 64)).first;
-                for (int k = 0; k < 64; k++) qts.push_back(q[k]);
-            }
-            d.qt = (uint32_t)it->second;
-        }
+        describe(P[f], parse(frames[f].data, frames[f].size, P[f]), frames[f].size, sw, sh, T, d);
+        if (d.status) continue;
         d.raw_off = raw_total;
-        raw_total += al16((size_t)raw_len + 4);
+        raw_total += al16((size_t)d.raw_len + 4);
         d.int_off = int_total;
         int_total += d.nint + 1;
         d.sub_off = sub_total;
         sub_total += d.sub_cap;
     }
-    if (tabs.empty()) tabs.emplace_back(); // (every frame bad: the kernels still get valid pointers)
-    if (qts.empty()) qts.assign(64, 0);
+    T.finish();
     // ---- stage: descriptors | tables | quant tables | payloads -----------------------------------------------------------------
-    const size_t off_tab = al16(sizeof(ck_jpeg_desc) * (size_t)n);
-    const size_t off_qt = off_tab + sizeof(ck_jpeg_huff) * tabs.size();
-    const size_t off_raw = al16(off_qt + sizeof(int32_t) * qts.size());
-    const size_t total = off_raw + raw_total;
-    int rc = grow_host(&J.h_stage, &J.stage_cap, total);
-    if (rc == CK_OK) rc = grow_dev(&J.d_in, &J.in_cap, total);
-    if (rc == CK_OK) rc = grow_dev(&J.d_compact, &J.compact_cap, raw_total ? raw_total : 16);
-    if (rc == CK_OK) rc = grow_dev(&J.d_int, &J.int_cap, sizeof(uint32_t) * (int_total ? int_total : 1));
-    if (rc == CK_OK) rc = grow_dev(&J.d_sub, &J.sub_cap, sizeof(ck_jpeg_sub) * (sub_total ? sub_total : 1));
-    if (rc == CK_OK) rc = grow_dev(&J.d_coef, &J.coef_cap, sizeof(int16_t) * 64 * coef_frame_blocks * (size_t)n);
+    const Layout L = layout(n, T);
+    const size_t total = L.off_raw + raw_total;
+    int rc = ws_reserve(J, total, raw_total, int_total, sub_total, coef_blocks(sw, sh) * (size_t)n);
     if (rc != CK_OK) return rc;
     CK_HIP(hipStreamSynchronize(h->stream)); // (the staging buffer may still feed an earlier call's copy)
     uint8_t *S = J.h_stage;
-    memcpy(S, D.data(), sizeof(ck_jpeg_desc) * (size_t)n);
-    memcpy(S + off_tab, tabs.data(), sizeof(ck_jpeg_huff) * tabs.size());
-    memcpy(S + off_qt, qts.data(), sizeof(int32_t) * qts.size());
-    for (int f = 0; f < n; f++) {
-        if (D[f].status) continue;
-        uint8_t *dst = S + off_raw + D[f].raw_off;
-        memcpy(dst, frames[f].data + P[f].scan_off, D[f].raw_len);
-        memset(dst + D[f].raw_len, 0, al16((size_t)D[f].raw_len + 4) - D[f].raw_len);
-    }
+    stage_head(S, L, D.data(), n, T);
+    for (int f = 0; f < n; f++)
+        if (!D[f].status) stage_scan(S + L.off_raw + D[f].raw_off, frames[f].data + P[f].scan_off, D[f].raw_len);
     CK_HIP(hipMemcpyAsync(J.d_in, S, total, hipMemcpyHostToDevice, h->stream));
-    rc = ck_launch_jpeg(h, n, reinterpret_cast<const ck_jpeg_desc *>(J.d_in), reinterpret_cast<const ck_jpeg_huff *>(J.d_in + off_tab),
-                        reinterpret_cast<const int32_t *>(J.d_in + off_qt), J.d_in + off_raw, coef_frame_blocks);
+    rc = enqueue_decode(J, h->stream, n, L, L.off_raw, ck_staged_image(h), sw, sh, orientation);
     if (rc != CK_OK) return rc;
-    CK_HIP(hipMemcpyAsync(J.h_status, J.d_status, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
     CK_HIP(hipStreamSynchronize(h->stream));
     if (jpeg_status) memcpy(jpeg_status, J.h_status, sizeof(uint32_t) * (size_t)n);
     h->n_staged = n;
     return CK_OK;
 }
 
-int check_frames(const ck_handle *h, const ck_jpeg_frame_t *frames, int32_t n) {
-    if (!h || !frames || n < 0) return CK_EINVAL;
+int check_frames(const ck_handle *h, const ck_jpeg_frame_t *frames, int32_t n, int32_t orientation) {
+    if (!h || !frames || n < 0 || orientation < CK_ORIENT_NONE || orientation > CK_ORIENT_COUNTERCLOCKWISE) return CK_EINVAL;
     if (n > h->cfg.max_batch) return CK_ECAPACITY;
     for (int i = 0; i < n; i++)
         if (!frames[i].data || frames[i].size < 4) return CK_EINVAL;
@@ -377,11 +440,7 @@ int check_frames(const ck_handle *h, const ck_jpeg_frame_t *frames, int32_t n) {
 
 void ck_jpeg_free(ck_handle *h) {
     if (!h || !h->jpeg) return;
-    ck_jpeg_ws &J = *h->jpeg;
-    if (J.h_stage) (void)hipHostFree(J.h_stage);
-    if (J.h_status) (void)hipHostFree(J.h_status);
-    (void)ck_free_dev(J.d_in); (void)ck_free_dev(J.d_compact); (void)ck_free_dev(J.d_int); (void)ck_free_dev(J.d_sub);
-    (void)ck_free_dev(J.d_coef); (void)ck_free_dev(J.d_status);
+    ws_release(*h->jpeg);
     delete h->jpeg;
     h->jpeg = nullptr;
 }
@@ -394,20 +453,136 @@ extern "C" int ck_jpeg_info(const uint8_t *data, int64_t size, ck_jpeg_info_t *o
     return rc;
 }
 
-extern "C" int ck_upload_jpeg(ck_handle_t *h, const ck_jpeg_frame_t *frames, int32_t n, uint32_t *jpeg_status) {
-    const int rc = check_frames(h, frames, n);
+extern "C" int ck_upload_jpeg_oriented(ck_handle_t *h, const ck_jpeg_frame_t *frames, int32_t n, int32_t orientation, uint32_t *jpeg_status) {
+    const int rc = check_frames(h, frames, n, orientation);
     if (rc != CK_OK) return rc;
-    return jpeg_run(h, frames, n, jpeg_status);
+    return jpeg_run(h, frames, n, orientation, jpeg_status);
 }
 
-extern "C" int ck_jpeg_luma_batch(ck_handle_t *h, const ck_jpeg_frame_t *frames, int32_t n, uint8_t *luma_out, uint32_t *jpeg_status) {
+extern "C" int ck_upload_jpeg(ck_handle_t *h, const ck_jpeg_frame_t *frames, int32_t n, uint32_t *jpeg_status) {
+    return ck_upload_jpeg_oriented(h, frames, n, CK_ORIENT_NONE, jpeg_status);
+}
+
+extern "C" int ck_jpeg_luma_batch_oriented(ck_handle_t *h, const ck_jpeg_frame_t *frames, int32_t n, int32_t orientation, uint8_t *luma_out,
+                                           uint32_t *jpeg_status) {
     if (!luma_out) return CK_EINVAL;
-    int rc = check_frames(h, frames, n);
+    int rc = check_frames(h, frames, n, orientation);
     if (rc != CK_OK) return rc;
-    rc = jpeg_run(h, frames, n, jpeg_status);
+    rc = jpeg_run(h, frames, n, orientation, jpeg_status);
     if (rc != CK_OK || n == 0) return rc;
     CK_HIP(hipMemcpy2DAsync(luma_out, (size_t)h->w, h->d_frames, (size_t)h->frame_stride, (size_t)h->w, (size_t)h->h * n,
                             hipMemcpyDeviceToHost, h->stream));
     CK_HIP(hipStreamSynchronize(h->stream));
     return CK_OK;
 }
+
+extern "C" int ck_jpeg_luma_batch(ck_handle_t *h, const ck_jpeg_frame_t *frames, int32_t n, uint8_t *luma_out, uint32_t *jpeg_status) {
+    return ck_jpeg_luma_batch_oriented(h, frames, n, CK_ORIENT_NONE, luma_out, jpeg_status);
+}
+
+// ---- the JPEG half of an ingest ring ------------------------------------------------------------------------------------------
+// A slot's staging has a fixed layout, so that ck_ingest_write_jpeg can place a frame's scan before the slot's tables are known:
+// head_cap bytes for descriptors | tables | quant tables (their worst case: six Huffman tables and one quantisation table per frame),
+// then one region of frame_cap bytes per frame index.  Submit copies the head with one copy and the regions of frames [0, n), as far
+// as the longest scan reaches, with one pitched copy.
+struct ck_jpeg_slots {
+    ck_handle *h;
+    int nslots, orientation, sw, sh;
+    int64_t max_frame_bytes;
+    size_t frame_cap, head_cap, int_cap, sub_cap;
+    struct Slot {
+        ck_jpeg_ws J;
+        std::vector<Parsed> P;
+        std::vector<int> rc;
+        std::vector<int64_t> size;
+        std::vector<uint8_t> written;
+        std::vector<ck_jpeg_desc> D;
+    } slot[8];
+};
+
+void ck_jpeg_slots_free(ck_jpeg_slots *q) {
+    if (!q) return;
+    for (int s = 0; s < q->nslots; s++) ws_release(q->slot[s].J);
+    delete q;
+}
+
+int ck_jpeg_slots_create(ck_handle *h, int n_slots, int orientation, int64_t max_frame_bytes, ck_jpeg_slots **out) {
+    ck_jpeg_slots *q = new (std::nothrow) ck_jpeg_slots();
+    if (!q) return CK_ENOMEM;
+    q->h = h; q->nslots = n_slots; q->orientation = orientation;
+    source_size(h, orientation, &q->sw, &q->sh);
+    q->max_frame_bytes = max_frame_bytes ? max_frame_bytes : (int64_t)q->sw * q->sh;
+    const size_t nb = (size_t)h->cfg.max_batch;
+    q->frame_cap = al16((size_t)q->max_frame_bytes + 4);
+    q->head_cap = al16(al16(sizeof(ck_jpeg_desc) * nb) + sizeof(ck_jpeg_huff) * 6 * nb + sizeof(int32_t) * 64 * nb);
+    // a frame has at most one restart interval per MCU and at most one MCU per 8 x 8 pixels; its subsequences: ck_jpeg_desc::sub_cap
+    const size_t nmcu_max = (size_t)((q->sw + 7) / 8) * (size_t)((q->sh + 7) / 8);
+    q->int_cap = (nmcu_max + 1) * nb;
+    q->sub_cap = (nmcu_max + ((size_t)q->max_frame_bytes * 8 + CK_JPEG_SUB_BITS - 1) / CK_JPEG_SUB_BITS + 1) * nb;
+    int rc = CK_OK;
+    try {
+        for (int s = 0; s < n_slots; s++) {
+            ck_jpeg_slots::Slot &S = q->slot[s];
+            memset(&S.J, 0, sizeof S.J);
+            S.P.resize(nb); S.rc.assign(nb, CK_EINVAL); S.size.assign(nb, 0); S.written.assign(nb, 0); S.D.resize(nb);
+        }
+    } catch (const std::bad_alloc &) { rc = CK_ENOMEM; }
+    for (int s = 0; s < n_slots && rc == CK_OK; s++) {
+        ck_jpeg_ws &J = q->slot[s].J;
+        rc = ws_status(J, h->cfg.max_batch);
+        if (rc == CK_OK) rc = ws_reserve(J, q->head_cap + q->frame_cap * nb, q->frame_cap * nb, q->int_cap, q->sub_cap, coef_blocks(q->sw, q->sh) * nb, true);
+    }
+    if (rc != CK_OK) { ck_jpeg_slots_free(q); return rc; }
+    *out = q;
+    return CK_OK;
+}
+
+int ck_jpeg_slots_write(ck_jpeg_slots *q, int slot, int index, const uint8_t *data, int64_t size) {
+    if (size > q->max_frame_bytes) return CK_ECAPACITY;
+    ck_jpeg_slots::Slot &S = q->slot[slot];
+    Parsed &p = S.P[index];
+    p = Parsed();
+    const int rc = parse(data, size, p);
+    S.rc[index] = rc;
+    S.size[index] = size;
+    // (a frame that describe() will refuse at submit has no payload; the same tests as there)
+    if (rc == CK_OK && p.info.width == q->sw && p.info.height == q->sh && size - p.scan_off <= ((int64_t)1 << 28))
+        stage_scan(S.J.h_stage + q->head_cap + q->frame_cap * (size_t)index, data + p.scan_off, (uint32_t)(size - p.scan_off));
+    S.written[index] = 1;
+    return CK_OK;
+}
+
+int ck_jpeg_slots_submit(ck_jpeg_slots *q, int slot, int n, hipStream_t s, const ck_dev_image &dst) {
+    ck_jpeg_slots::Slot &S = q->slot[slot];
+    for (int f = 0; f < n; f++)
+        if (!S.written[f]) return CK_EINVAL;
+    if (n == 0) return CK_OK;
+    Tables T;
+    uint64_t int_total = 0, sub_total = 0;
+    size_t longest = 0;
+    for (int f = 0; f < n; f++) {
+        ck_jpeg_desc &d = S.D[f];
+        describe(S.P[f], S.rc[f], S.size[f], q->sw, q->sh, T, d);
+        if (d.status) continue;
+        d.raw_off = q->frame_cap * (uint64_t)f; // its unstuffed copy lands at the same offset of d_compact
+        d.int_off = int_total;
+        int_total += d.nint + 1;
+        d.sub_off = sub_total;
+        sub_total += d.sub_cap;
+        if (al16((size_t)d.raw_len + 4) > longest) longest = al16((size_t)d.raw_len + 4);
+    }
+    T.finish();
+    const Layout L = layout(n, T);
+    if (L.head_bytes > q->head_cap || int_total > q->int_cap || sub_total > q->sub_cap || longest > q->frame_cap) return CK_ECAPACITY; // (cannot happen: the caps are the worst case)
+    const ck_jpeg_ws &J = S.J;
+    stage_head(J.h_stage, L, S.D.data(), n, T);
+    CK_HIP(hipMemcpyAsync(J.d_in, J.h_stage, L.head_bytes, hipMemcpyHostToDevice, s));
+    if (longest)
+        CK_HIP(hipMemcpy2DAsync(J.d_in + q->head_cap, q->frame_cap, J.h_stage + q->head_cap, q->frame_cap, longest, (size_t)n, hipMemcpyHostToDevice, s));
+    const int rc = enqueue_decode(J, s, n, L, q->head_cap, dst, q->sw, q->sh, q->orientation);
+    if (rc != CK_OK) return rc;
+    std::fill(S.written.begin(), S.written.end(), (uint8_t)0);
+    return CK_OK;
+}
+
+const uint32_t *ck_jpeg_slots_status(const ck_jpeg_slots *q, int slot) { return q->slot[slot].J.h_status; }

@@ -504,16 +504,28 @@ __device__ __forceinline__ uint8_t range_limit(int64_t x) {
     return (uint8_t)(j < 128 ? j + 128 : j < 512 ? 255 : j < 896 ? 0 : j - 896);
 }
 
+// The staged frame is orient(S, O) of the decoded luma S (sw x sh): the contract of chalkydri_hip.h's raw formats, DESIGN.md §4c.
+// The two passes run in libjpeg's order whatever O is; the turn happens on the eight finished bytes of a lane.  O = none is the
+// kernel as it was before frames could be turned: row c of block (bx, by) goes to row by*8+c, column bx*8 with one 8-byte store.
+// rotate-180: a lane reverses its bytes, and the block lands mirrored.  The quarter turns transpose the block's 8 x 8 bytes
+// between its eight lanes through a padded LDS tile, so that every lane again owns one row of the TURNED block and stores it
+// with one row-contiguous store (8 bytes when its first column is a multiple of 8 and the block does not hang over the frame,
+// bytes otherwise).  Every store is to a pixel (x, y) with 0 <= x < the oriented width and 0 <= y < the oriented height.
+template <int O>
 __global__ void __launch_bounds__(IDCT_NT) k_jpeg_idct(const ck_jpeg_desc *__restrict__ descs, const int32_t *__restrict__ qts,
                                                        const int16_t *__restrict__ coef_base, size_t coef_frame_blocks,
                                                        const uint32_t *__restrict__ status, uint8_t *__restrict__ frames, int stride,
-                                                       size_t pitch, int w, int h) {
+                                                       size_t pitch, int w, int h) { // w x h: the source S
     __shared__ int32_t ws[IDCT_BLOCKS][8][9];
     const int f = blockIdx.y, g = threadIdx.x >> 3, c = threadIdx.x & 7;
     const int bxn = (w + 7) / 8, byn = (h + 7) / 8;
     const int b = blockIdx.x * IDCT_BLOCKS + g;
     const bool live = b < bxn * byn;
-    const int by = live ? b / bxn : 0, bx = live ? b % bxn : 0;
+    // consecutive blocks follow a row of the ORIENTED frame, so that the eight blocks of a wave store 64 contiguous bytes per row:
+    // a source row for none and rotate-180, a source column for the quarter turns (a block's coefficients are one 128-byte line
+    // wherever its neighbours lie, so the reads do not care)
+    constexpr bool kQuarter = O == CK_ORIENT_CLOCKWISE || O == CK_ORIENT_COUNTERCLOCKWISE;
+    const int by = !live ? 0 : kQuarter ? b % byn : b / bxn, bx = !live ? 0 : kQuarter ? b / byn : b % bxn;
     const bool ok = status[f] == 0;
     const ck_jpeg_desc &d = descs[f];
     if (live && ok) { // pass 1: column c
@@ -525,39 +537,100 @@ __global__ void __launch_bounds__(IDCT_NT) k_jpeg_idct(const ck_jpeg_desc *__res
         for (int r = 0; r < 8; r++) ws[g][r][c] = (int32_t)((out[r] + 1024) >> 11);      // DESCALE(., CONST_BITS - PASS1_BITS)
     }
     __syncthreads();
-    if (!live) return;
-    const int y = by * 8 + c;
-    if (y >= h) return;
-    uint8_t px[8];
-    if (ok) { // pass 2: row c
-        int64_t in[8], out[8];
-        for (int k = 0; k < 8; k++) in[k] = ws[g][c][k];
-        islow_1d(in, out);
-        for (int k = 0; k < 8; k++) px[k] = range_limit((out[k] + (1 << 17)) >> 18); // DESCALE(., CONST_BITS + PASS1_BITS + 3)
+    if constexpr (O == CK_ORIENT_NONE) {
+        if (!live) return;
+        const int y = by * 8 + c;
+        if (y >= h) return;
+        uint8_t px[8];
+        if (ok) { // pass 2: row c
+            int64_t in[8], out[8];
+            for (int k = 0; k < 8; k++) in[k] = ws[g][c][k];
+            islow_1d(in, out);
+            for (int k = 0; k < 8; k++) px[k] = range_limit((out[k] + (1 << 17)) >> 18); // DESCALE(., CONST_BITS + PASS1_BITS + 3)
+        } else {
+            for (int k = 0; k < 8; k++) px[k] = 0;
+        }
+        uint8_t *row = frames + (size_t)f * pitch + (size_t)y * stride + bx * 8;
+        if (bx * 8 + 8 <= w) {
+            uint64_t v = 0;
+            for (int k = 0; k < 8; k++) v |= (uint64_t)px[k] << (8 * k);
+            *reinterpret_cast<uint64_t *>(row) = v;
+        } else {
+            for (int k = 0; k < 8 && bx * 8 + k < w; k++) row[k] = px[k];
+        }
     } else {
-        for (int k = 0; k < 8; k++) px[k] = 0;
-    }
-    uint8_t *row = frames + (size_t)f * pitch + (size_t)y * stride + bx * 8;
-    if (bx * 8 + 8 <= w) {
+        // row c of the source block as two words, byte k of v = S[by*8+c][bx*8+k] (rows and columns past sw / sh are JPEG's padding
+        // to whole MCUs: computed like the rest and cropped on the turned side)
         uint64_t v = 0;
-        for (int k = 0; k < 8; k++) v |= (uint64_t)px[k] << (8 * k);
-        *reinterpret_cast<uint64_t *>(row) = v;
-    } else {
-        for (int k = 0; k < 8 && bx * 8 + k < w; k++) row[k] = px[k];
+        if (live && ok) { // pass 2: row c
+            int64_t in[8], out[8];
+            for (int k = 0; k < 8; k++) in[k] = ws[g][c][k];
+            islow_1d(in, out);
+            for (int k = 0; k < 8; k++) v |= (uint64_t)range_limit((out[k] + (1 << 17)) >> 18) << (8 * k);
+        }
+        int y, x0; // the lane's row of the turned block: out[y][x0 + j] = byte j of v, for the j with 0 <= x0 + j < W
+        bool row_ok;
+        if constexpr (O == CK_ORIENT_ROTATE_180) {
+            v = __builtin_bswap64(v);
+            y = h - 1 - (by * 8 + c);
+            x0 = w - 8 - bx * 8;
+            row_ok = live && y >= 0;
+        } else {
+            // 18 words per block: the eight rows of two words and a pad that spreads the blocks of a half-wave over the 32 banks
+            // of ds_read_b32 (block g starts at bank 18 g mod 32: 0, 18, 4, 22 / 8, 26, 12, 30, each followed by its r*2 + {0, 1})
+            __shared__ uint32_t tr[IDCT_BLOCKS][18];
+            tr[g][c * 2] = (uint32_t)v;
+            tr[g][c * 2 + 1] = (uint32_t)(v >> 32);
+            __syncthreads();
+            // lane c now takes source COLUMN c: byte r of t = S[by*8+r][bx*8+c]
+            uint64_t t = 0;
+            for (int r = 0; r < 8; r++) t |= (uint64_t)((tr[g][r * 2 + (c >> 2)] >> (8 * (c & 3))) & 0xFFu) << (8 * r);
+            if constexpr (O == CK_ORIENT_CLOCKWISE) { // out[y][x] = S[sh-1-x][y]: row bx*8+c, columns sh-8-by*8 .., source rows descending
+                v = __builtin_bswap64(t);
+                y = bx * 8 + c;
+                x0 = h - 8 - by * 8;
+                row_ok = live && y < w;
+            } else {                                  // out[y][x] = S[x][sw-1-y]: row sw-1-(bx*8+c), columns by*8 .., source rows ascending
+                v = t;
+                y = w - 1 - (bx * 8 + c);
+                x0 = by * 8;
+                row_ok = live && y >= 0;
+            }
+        }
+        if (!row_ok) return;
+        const int W = (O == CK_ORIENT_ROTATE_180) ? w : h; // the oriented width (its height bounds y above)
+        uint8_t *row = frames + (size_t)f * pitch + (size_t)y * stride;
+        if (x0 >= 0 && x0 + 8 <= W && (x0 & 7) == 0) {
+            *reinterpret_cast<uint64_t *>(row + x0) = v;
+        } else {
+            for (int j = 0; j < 8; j++)
+                if (x0 + j >= 0 && x0 + j < W) row[x0 + j] = (uint8_t)(v >> (8 * j));
+        }
     }
+}
+
+template <int O>
+void launch_idct(hipStream_t s, int n, const ck_jpeg_desc *d_desc, const int32_t *d_qt, const ck_jpeg_ws &J, size_t coef_frame_blocks,
+                 const ck_dev_image &dst, int sw, int sh) {
+    const int nblk = ((sw + 7) / 8) * ((sh + 7) / 8);
+    hipLaunchKernelGGL(k_jpeg_idct<O>, dim3((unsigned)((nblk + IDCT_BLOCKS - 1) / IDCT_BLOCKS), (unsigned)n), dim3(IDCT_NT), 0, s, d_desc, d_qt,
+                       J.d_coef, coef_frame_blocks, J.d_status, const_cast<uint8_t *>(dst.p), dst.stride, dst.pitch, sw, sh);
 }
 
 } // namespace
 
-int ck_launch_jpeg(ck_handle *h, int n, const ck_jpeg_desc *d_desc, const ck_jpeg_huff *d_huff, const int32_t *d_qt, const uint8_t *d_raw,
-                   size_t coef_frame_blocks) {
-    ck_jpeg_ws &J = *h->jpeg;
-    hipLaunchKernelGGL(k_jpeg_frame, dim3((unsigned)n), dim3(NT), 0, h->stream, d_desc, d_huff, d_raw, J.d_compact, J.d_int, J.d_sub,
-                       J.d_coef, coef_frame_blocks, J.d_status);
+int ck_launch_jpeg(const ck_jpeg_ws &J, hipStream_t s, int n, const ck_jpeg_desc *d_desc, const ck_jpeg_huff *d_huff, const int32_t *d_qt,
+                   const uint8_t *d_raw, size_t coef_frame_blocks, const ck_dev_image &dst, int sw, int sh, int orientation) {
+    hipLaunchKernelGGL(k_jpeg_frame, dim3((unsigned)n), dim3(NT), 0, s, d_desc, d_huff, d_raw, J.d_compact, J.d_int, J.d_sub, J.d_coef,
+                       coef_frame_blocks, J.d_status);
     CK_HIP(hipGetLastError());
-    const int nblk = ((h->w + 7) / 8) * ((h->h + 7) / 8);
-    hipLaunchKernelGGL(k_jpeg_idct, dim3((unsigned)((nblk + IDCT_BLOCKS - 1) / IDCT_BLOCKS), (unsigned)n), dim3(IDCT_NT), 0, h->stream,
-                       d_desc, d_qt, J.d_coef, coef_frame_blocks, J.d_status, h->d_frames, h->frame_stride, h->frame_pitch, h->w, h->h);
+    switch (orientation) {
+    case CK_ORIENT_NONE: launch_idct<CK_ORIENT_NONE>(s, n, d_desc, d_qt, J, coef_frame_blocks, dst, sw, sh); break;
+    case CK_ORIENT_CLOCKWISE: launch_idct<CK_ORIENT_CLOCKWISE>(s, n, d_desc, d_qt, J, coef_frame_blocks, dst, sw, sh); break;
+    case CK_ORIENT_ROTATE_180: launch_idct<CK_ORIENT_ROTATE_180>(s, n, d_desc, d_qt, J, coef_frame_blocks, dst, sw, sh); break;
+    case CK_ORIENT_COUNTERCLOCKWISE: launch_idct<CK_ORIENT_COUNTERCLOCKWISE>(s, n, d_desc, d_qt, J, coef_frame_blocks, dst, sw, sh); break;
+    default: return CK_EINVAL;
+    }
     CK_HIP(hipGetLastError());
     return CK_OK;
 }

@@ -69,6 +69,11 @@ def _bind(L):
     L.ck_jpeg_info.argtypes = [vp, C.c_int64, _P(A.JpegInfo)]
     L.ck_upload_jpeg.argtypes = [vp, _P(A.JpegFrame), i32, u32p]
     L.ck_jpeg_luma_batch.argtypes = [vp, _P(A.JpegFrame), i32, vp, u32p]
+    L.ck_upload_jpeg_oriented.argtypes = [vp, _P(A.JpegFrame), i32, i32, u32p]
+    L.ck_jpeg_luma_batch_oriented.argtypes = [vp, _P(A.JpegFrame), i32, i32, vp, u32p]
+    L.ck_ingest_create_jpeg.argtypes = [vp, i32, i32, C.c_int64, _P(vp)]
+    L.ck_ingest_write_jpeg.argtypes = [vp, i32, i32, vp, C.c_int64]
+    L.ck_ingest_jpeg_status.argtypes = [vp, i32, i32, u32p]
     rf = _P(A.RawFormat)
     L.ck_raw_layout.argtypes = [rf, i32, i32, _P(i32), _P(i32), _P(i32), _P(C.c_int64)]
     L.ck_upload_raw.argtypes = [vp, _P(A.ImageU8), i32, rf]
@@ -337,21 +342,26 @@ class AprilTagDetector:
         check(self._L.ck_upload_frames(self._h, arr, len(arr)), "ck_upload_frames")
         return len(arr)
 
-    def upload_jpeg(self, frames, return_status=False):
+    def upload_jpeg(self, frames, orientation="none", return_status=False):
         """Decodes the luma of baseline JPEG frames (bytes each) on the device into the staged frames, as `upload` stages raw
         luma: detect_batch(None, n) / the process and pose calls follow.  A frame that is unsupported, of another size or
-        corrupt is staged as zeros; its CK_JPEG_* bits are in the status list (return_status=True)."""
+        corrupt is staged as zeros; its CK_JPEG_* bits are in the status list (return_status=True).  With an `orientation` the
+        frames are staged turned, the detector's width x height being the ORIENTED frame (the streams are height x width for
+        the quarter turns), as upload_raw does it."""
         arr, keep = _jpeg_frames(frames)
         status = (C.c_uint32 * max(len(keep), 1))()
-        check(self._L.ck_upload_jpeg(self._h, arr, len(keep), status), "ck_upload_jpeg")
+        o = orientation_code(orientation)
+        check(self._L.ck_upload_jpeg_oriented(self._h, arr, len(keep), o, status), "ck_upload_jpeg_oriented")
         return (len(keep), list(status)[:len(keep)]) if return_status else len(keep)
 
-    def decode_jpeg(self, frames, return_status=False):
-        """[n][height][width] uint8: the luma the device decodes from the JPEG frames (bit-identical to libjpeg's islow IDCT)."""
+    def decode_jpeg(self, frames, return_status=False, orientation="none"):
+        """[n][height][width] uint8: the luma the device decodes from the JPEG frames (bit-identical to libjpeg's islow IDCT),
+        turned by `orientation`."""
         arr, keep = _jpeg_frames(frames)
         out = np.empty((len(keep), self.height, self.width), np.uint8)
         status = (C.c_uint32 * max(len(keep), 1))()
-        check(self._L.ck_jpeg_luma_batch(self._h, arr, len(keep), out.ctypes.data, status), "ck_jpeg_luma_batch")
+        o = orientation_code(orientation)
+        check(self._L.ck_jpeg_luma_batch_oriented(self._h, arr, len(keep), o, out.ctypes.data, status), "ck_jpeg_luma_batch_oriented")
         return (out, list(status)[:len(keep)]) if return_status else out
 
     def upload_raw(self, frames, code, orientation="none"):
@@ -554,18 +564,26 @@ class IngestRing:
     """Pinned host slots + asynchronous upload in front of a detector (the pooled host buffers of the reference's camera
     layer, gst_to_cu.rs:49-72,131-188).  slot_view(s) is a writable numpy view [max_batch][h][stride] of pinned memory.
     With a fourcc the slots hold RAW frames of that format ([max_batch][sh][raw stride]); submit converts and orients them on
-    the device, and detect / process work as on a plain ring."""
+    the device, and detect / process work as on a plain ring.  With fourcc "MJPG" (or "JPEG") the slots take one compressed
+    frame per index (write(slot, index, data) with bytes, at most max_frame_bytes each; 0 = sw * sh); submit decodes and
+    orients them on the ring's copy stream, and jpeg_status(slot, n) gives their CK_JPEG_* words."""
 
-    def __init__(self, detector, n_slots=2, fourcc=None, orientation="none"):
+    def __init__(self, detector, n_slots=2, fourcc=None, orientation="none", max_frame_bytes=0):
         self.det, self._L = detector, detector._L
         g = C.c_void_p()
-        self.code, self.rows = fourcc, detector.cfg.height
+        self._g = None
+        self.code, self.rows = fourcc, detector.height
+        self.jpeg = isinstance(fourcc, str) and fourcc in A.JPEG_FOURCCS
         if fourcc is None:
             check(self._L.ck_ingest_create(detector._h, n_slots, C.byref(g)), "ck_ingest_create")
+        elif self.jpeg:
+            o = orientation_code(orientation)
+            check(self._L.ck_ingest_create_jpeg(detector._h, n_slots, o, int(max_frame_bytes), C.byref(g)), "ck_ingest_create_jpeg")
         else:
             fmt = raw_format(fourcc, orientation)
-            check(self._L.ck_ingest_create_raw(detector._h, n_slots, C.byref(fmt), C.byref(g)), "ck_ingest_create_raw")
+            # (the layout first: an unknown fourcc or orientation is refused on the host, before the ring touches the device)
             self.sw, self.rows, self.min_stride, _ = raw_layout(fmt.fourcc, detector.width, detector.height, fmt.orientation)
+            check(self._L.ck_ingest_create_raw(detector._h, n_slots, C.byref(fmt), C.byref(g)), "ck_ingest_create_raw")
         self._g, self.n_slots = g, n_slots
         self.stride = self._L.ck_ingest_stride(g)
 
@@ -584,7 +602,11 @@ class IngestRing:
 
     def write(self, slot, index, frame, code=None):
         """Stride-aware copy of one caller frame into the slot: a luma frame [h][>=w] on a plain ring, a raw frame
-        [sh][>=min_stride bytes] of the ring's format family on a raw ring."""
+        [sh][>=min_stride bytes] of the ring's format family on a raw ring, the bytes of one JPEG on a JPEG ring."""
+        if self.jpeg:
+            b = np.frombuffer(bytes(frame), np.uint8)
+            check(self._L.ck_ingest_write_jpeg(self._g, slot, index, b.ctypes.data if b.size else None, b.size), "ck_ingest_write_jpeg")
+            return
         if self.code is None:
             arr, keep = _images(frame)
         else:
@@ -594,6 +616,12 @@ class IngestRing:
 
     def submit(self, slot, n):
         check(self._L.ck_ingest_submit(self._g, slot, n), "ck_ingest_submit")
+
+    def jpeg_status(self, slot, n):
+        """The CK_JPEG_* words of the n frames the slot was submitted with (waits for the slot's decode)."""
+        status = (C.c_uint32 * max(n, 1))()
+        check(self._L.ck_ingest_jpeg_status(self._g, slot, n, status), "ck_ingest_jpeg_status")
+        return list(status)[:n]
 
     def detect(self, slot, n, cap=64):
         dets = (A.Detection * (cap * n))()

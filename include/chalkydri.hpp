@@ -89,6 +89,15 @@ class Handle {
         check(ck_raw_luma_batch(h_, imgs.data(), (int32_t)imgs.size(), &fmt, out.data()), "ck_raw_luma_batch");
         return out;
     }
+    // JPEG frames (chalkydri_hip.h: ck_upload_jpeg_oriented) decoded and turned by `orientation` (CK_ORIENT_*) on the device into
+    // the staged frames; returns the per-frame CK_JPEG_* statuses.  The streams are sw x sh of the ORIENTED width x height.
+    std::vector<uint32_t> upload_jpeg(const std::vector<std::vector<uint8_t>> &jpegs, int32_t orientation = CK_ORIENT_NONE) {
+        std::vector<ck_jpeg_frame_t> f;
+        for (const auto &j : jpegs) f.push_back({j.data(), (int64_t)j.size()});
+        std::vector<uint32_t> st(f.size());
+        check(ck_upload_jpeg_oriented(h_, f.data(), (int32_t)f.size(), orientation, st.data()), "ck_upload_jpeg_oriented");
+        return st;
+    }
 
   private:
     ck_config_t cfg_{};
@@ -97,17 +106,22 @@ class Handle {
 
 // ck_raw_format_t from a fourcc ("YUYV", "RGB3", "BGR ", ...) and the reference's VideoOrientation serde name
 // (crates/chalkydri_core/src/config.rs:201-207): "none", "clockwise", "rotate-180", "counterclockwise"
+inline int32_t orientation_code(const std::string &orientation) {
+    if (orientation == "none") return CK_ORIENT_NONE;
+    if (orientation == "clockwise") return CK_ORIENT_CLOCKWISE;
+    if (orientation == "rotate-180") return CK_ORIENT_ROTATE_180;
+    if (orientation == "counterclockwise") return CK_ORIENT_COUNTERCLOCKWISE;
+    throw Panic("unknown orientation " + orientation, CK_EINVAL);
+}
 inline ck_raw_format_t raw_format(const std::string &fourcc, const std::string &orientation = "none") {
     if (fourcc.size() != 4) throw Panic("a fourcc has exactly 4 characters: " + fourcc, CK_EINVAL);
     ck_raw_format_t f{};
     for (int i = 0; i < 4; i++) f.fourcc |= (uint32_t)(uint8_t)fourcc[i] << (8 * i);
-    if (orientation == "none") f.orientation = CK_ORIENT_NONE;
-    else if (orientation == "clockwise") f.orientation = CK_ORIENT_CLOCKWISE;
-    else if (orientation == "rotate-180") f.orientation = CK_ORIENT_ROTATE_180;
-    else if (orientation == "counterclockwise") f.orientation = CK_ORIENT_COUNTERCLOCKWISE;
-    else throw Panic("unknown orientation " + orientation, CK_EINVAL);
+    f.orientation = orientation_code(orientation);
     return f;
 }
+// the names the host layers take for a camera that delivers one JPEG per frame (not raw formats: ck_raw_layout refuses them)
+inline bool is_jpeg_fourcc(const std::string &fourcc) { return fourcc == "MJPG" || fourcc == "JPEG"; }
 struct RawLayout { int32_t sw = 0, sh = 0, min_stride = 0; int64_t min_bytes = 0; };
 // source geometry of an oriented width x height frame (no device needed); throws for a fourcc outside the table
 inline RawLayout raw_layout(const ck_raw_format_t &fmt, int width, int height) {
@@ -214,6 +228,15 @@ inline std::vector<uint8_t> decode_jpeg(Handle &h, const std::vector<std::vector
     std::vector<uint8_t> out((size_t)f.size() * h.config().width * h.config().height);
     std::vector<uint32_t> st(f.size());
     check(ck_jpeg_luma_batch(h.get(), f.data(), (int32_t)f.size(), out.data(), st.data()), "ck_jpeg_luma_batch");
+    if (status) *status = st;
+    return out;
+}
+// ... turned by `orientation` (CK_ORIENT_*; the handle's geometry is the oriented frame): [n][height][width]
+inline std::vector<uint8_t> decode_jpeg(Handle &h, const std::vector<std::vector<uint8_t>> &jpegs, int32_t orientation, std::vector<uint32_t> *status = nullptr) {
+    std::vector<ck_jpeg_frame_t> f = jpeg_frames(jpegs);
+    std::vector<uint8_t> out((size_t)f.size() * h.config().width * h.config().height);
+    std::vector<uint32_t> st(f.size());
+    check(ck_jpeg_luma_batch_oriented(h.get(), f.data(), (int32_t)f.size(), orientation, out.data(), st.data()), "ck_jpeg_luma_batch_oriented");
     if (status) *status = st;
     return out;
 }
@@ -674,6 +697,21 @@ class IngestRing {
     IngestRing(const std::shared_ptr<Handle> &h, int n_slots, const ck_raw_format_t &fmt) : h_(h) {
         check(ck_ingest_create_raw(h_->get(), n_slots, &fmt, &g_), "ck_ingest_create_raw");
     }
+    // slots of JPEG frames, one compressed frame per index: submit decodes and orients them on the ring's copy stream
+    // (ck_ingest_create_jpeg; max_frame_bytes 0 = sw * sh)
+    struct Jpeg { int32_t orientation = CK_ORIENT_NONE; int64_t max_frame_bytes = 0; };
+    IngestRing(const std::shared_ptr<Handle> &h, int n_slots, const Jpeg &j) : h_(h) {
+        check(ck_ingest_create_jpeg(h_->get(), n_slots, j.orientation, j.max_frame_bytes, &g_), "ck_ingest_create_jpeg");
+    }
+    void write_jpeg(int slot, int index, const uint8_t *data, size_t size) { check(ck_ingest_write_jpeg(g_, slot, index, data, (int64_t)size), "ck_ingest_write_jpeg"); }
+    void write_jpeg(int slot, int index, const std::vector<uint8_t> &jpeg) { write_jpeg(slot, index, jpeg.data(), jpeg.size()); }
+    // the CK_JPEG_* words of the n frames the slot was submitted with (waits for the slot's decode)
+    std::vector<uint32_t> jpeg_status(int slot, int n) {
+        std::vector<uint32_t> st((size_t)std::max(n, 1));
+        check(ck_ingest_jpeg_status(g_, slot, n, st.data()), "ck_ingest_jpeg_status");
+        st.resize((size_t)n);
+        return st;
+    }
     ~IngestRing() { ck_ingest_destroy(g_); }
     IngestRing(const IngestRing &) = delete;
     IngestRing &operator=(const IngestRing &) = delete;
@@ -707,7 +745,8 @@ class AprilTags {
         int device = 0, max_batch = 1, quad_decimate = 1;
         float quad_sigma = 0.0f;                // AprilTag-3 detector field; 0 = no filter
         // the camera's raw format ("" = 8-bit luma, else a fourcc of ck_raw_layout's table) and mounting: `process` then takes the
-        // frames as the camera hands them over; width / height / calib are those of the ORIENTED image
+        // frames as the camera hands them over; width / height / calib are those of the ORIENTED image.  "MJPG" / "JPEG": the camera
+        // delivers one JPEG per frame, which `process_jpeg` takes
         std::string fourcc;
         std::string orientation = "none";
     };
@@ -738,6 +777,23 @@ class AprilTags {
         if (n > cfg_.max_batch || gyro.size() != imgs.size()) throw Panic("process: batch larger than max_batch or gyro size mismatch", CK_EINVAL);
         if (cfg_.fourcc.empty() && cfg_.orientation == "none") check(ck_upload_frames(h_->get(), imgs.data(), n), "ck_upload_frames");
         else h_->upload_raw(imgs, raw_format(cfg_.fourcc.empty() ? "GREY" : cfg_.fourcc, cfg_.orientation));
+        std::vector<double> g(n);
+        std::vector<uint8_t> has(n);
+        for (int i = 0; i < n; i++) { has[i] = gyro[i].has_value(); g[i] = gyro[i].value_or(0.0); }
+        std::vector<whacknet::VisionMeasurement> out(n);
+        std::vector<int32_t> valid(n);
+        check(ck_process_uploaded(h_->get(), n, &pp_, g.data(), has.data(), out.data(), valid.data()), "ck_process_uploaded");
+        std::vector<std::pair<whacknet::VisionMeasurement, bool>> r;
+        for (int i = 0; i < n; i++) r.emplace_back(out[i], valid[i] != 0);
+        return r;
+    }
+    // a camera that delivers MJPG (Config::fourcc "MJPG" / "JPEG"): one JPEG per frame, decoded and turned by Config::orientation on
+    // the device; a frame the decoder refuses (CK_JPEG_* status) is a black frame: no detections, no pose
+    std::vector<std::pair<whacknet::VisionMeasurement, bool>> process_jpeg(const std::vector<std::vector<uint8_t>> &jpegs, const std::vector<std::optional<double>> &gyro) {
+        const int n = (int)jpegs.size();
+        if (!is_jpeg_fourcc(cfg_.fourcc)) throw Panic("process_jpeg: the task's fourcc is not MJPG", CK_EINVAL);
+        if (n > cfg_.max_batch || gyro.size() != jpegs.size()) throw Panic("process_jpeg: batch larger than max_batch or gyro size mismatch", CK_EINVAL);
+        (void)h_->upload_jpeg(jpegs, orientation_code(cfg_.orientation));
         std::vector<double> g(n);
         std::vector<uint8_t> has(n);
         for (int i = 0; i < n; i++) { has[i] = gyro[i].has_value(); g[i] = gyro[i].value_or(0.0); }

@@ -452,6 +452,39 @@ int ck_jpeg_info(const uint8_t *data, int64_t size, ck_jpeg_info_t *out);
 int ck_upload_jpeg(ck_handle_t *h, const ck_jpeg_frame_t *frames, int32_t n, uint32_t *jpeg_status);
 /* The same, then copies the decoded luma out: luma_out is [n][height][width]. */
 int ck_jpeg_luma_batch(ck_handle_t *h, const ck_jpeg_frame_t *frames, int32_t n, uint8_t *luma_out, uint32_t *jpeg_status);
+/* JPEG frames turned by the camera's mounting (the reference's jpegdec -> videoflip, crates/chalkydri/src/cameras/pipeline.rs:123-162).
+ * orientation is a CK_ORIENT_* value (below) and the handle's width x height the ORIENTED frame W x H, as for the raw formats: the
+ * streams must be sw x sh as ck_raw_layout({GREY, orientation}, W, H) gives it (W x H for none and rotate-180, H x W for the
+ * quarter turns), and with S the luma ck_upload_jpeg would stage for a stream, the staged frame is orient(S, orientation) by the four
+ * formulas of the raw formats' contract below.  The IDCT kernel writes the turned blocks itself: no second pass over the frame.
+ * CK_ORIENT_NONE is ck_upload_jpeg / ck_jpeg_luma_batch byte for byte.  A stream that is not sw x sh is CK_JPEG_GEOMETRY and staged
+ * as zeros; the other status bits and the errors are ck_upload_jpeg's, and CK_EINVAL also for an orientation outside 0..3.
+ * DESIGN.md §4c, "JPEG frames: orientation and the ring". */
+int ck_upload_jpeg_oriented(ck_handle_t *h, const ck_jpeg_frame_t *frames, int32_t n, int32_t orientation, uint32_t *jpeg_status);
+int ck_jpeg_luma_batch_oriented(ck_handle_t *h, const ck_jpeg_frame_t *frames, int32_t n, int32_t orientation, uint8_t *luma_out,
+                                uint32_t *jpeg_status);
+/* An ingest ring whose slots take JPEG frames: the asynchronous form of ck_upload_jpeg_oriented.  ck_ingest_create_jpeg allocates,
+ * once, for every slot: the pinned staging and its device copy (max_batch regions of max_frame_bytes + the tables), the unstuffed
+ * copy, the decode workspace at its worst case for sw x sh streams of max_frame_bytes (one 48-byte record per 512 bits of scan and
+ * per 8 x 8 pixels, the Y coefficients) and the slot's device frames; ck_ingest_destroy releases them.  max_frame_bytes bounds one
+ * frame's size; 0 = sw * sh, which no camera's JPEG of that size exceeds in practice — a caller that knows its camera's largest
+ * frame saves memory by saying so.  CK_EINVAL: a null handle / out, n_slots outside 1..8, an orientation outside 0..3, a negative
+ * max_frame_bytes.  CK_ENOMEM as ck_ingest_create.
+ * ck_ingest_write_jpeg parses the header on the host and copies the scan into the slot's pinned staging; the caller's buffer is free
+ * when it returns.  A stream that is unsupported, corrupt in its header or of the wrong geometry is not an error of the call: CK_OK,
+ * and the frame comes out as zeros with its CK_JPEG_* bit, exactly as through ck_upload_jpeg.  CK_ECAPACITY: size > max_frame_bytes.
+ * CK_EINVAL: a null pointer, size < 4, a slot or index out of range, a ring that is not a JPEG ring.
+ * ck_ingest_submit(ing, slot, n) on a JPEG ring: CK_EINVAL unless every index in [0, n) has been written since the slot's last
+ * submit; it merges the frames' tables, enqueues the copies, the decode and the oriented IDCT on the ring's copy stream into the
+ * slot's device frames and records the slot's event, without allocating and without waiting for the device.  ck_detect_ingested /
+ * ck_process_ingested then work as on every ring.  ck_ingest_jpeg_status waits for the slot's decode and gives the n status words
+ * (n = the count the slot was submitted with, CK_EINVAL otherwise).
+ * On a JPEG ring ck_ingest_write returns CK_EUNSUPPORTED, ck_ingest_frame NULL and ck_ingest_stride 0.
+ * On EVERY kind of ring a slot must not be written again before the call that processes it (ck_detect_ingested,
+ * ck_process_ingested) has returned: until then its staging may still be feeding the copy. */
+int ck_ingest_create_jpeg(ck_handle_t *h, int32_t n_slots, int32_t orientation, int64_t max_frame_bytes, ck_ingest_t **out);
+int ck_ingest_write_jpeg(ck_ingest_t *ing, int32_t slot, int32_t index, const uint8_t *data, int64_t size);
+int ck_ingest_jpeg_status(ck_ingest_t *ing, int32_t slot, int32_t n, uint32_t *jpeg_status);
 
 /* ---- raw camera formats and orientation on the device -------------------------------------------------------------------
  * What the reference does between the camera and AprilTags::process with `videoconvert` + a GRAY8 caps filter and `videoflip`
