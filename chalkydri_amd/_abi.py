@@ -102,6 +102,23 @@ class PreviewParams(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("width", "height", "quality", "restart_rows", "overlay", "pad")]
 
 
+CK_EXPOSURE_GAMMAS, CK_EXPOSURE_BINS = 7, 192
+
+
+class Rect(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("x0", "y0", "x1", "y1")]
+
+
+class ExposureStats(C.Structure):
+    _fields_ = [("luma", C.c_uint32 * 256), ("grad", (C.c_uint32 * CK_EXPOSURE_BINS) * CK_EXPOSURE_GAMMAS),
+                ("n_luma", C.c_uint32), ("n_grad", C.c_uint32), ("pad", C.c_uint32 * 2)]
+
+
+class ExposureParams(C.Structure):
+    _fields_ = [("gamma", C.c_double * CK_EXPOSURE_GAMMAS), ("lambda_", C.c_double), ("delta", C.c_double), ("kp", C.c_double),
+                ("e_min", C.c_double), ("e_max", C.c_double)]
+
+
 class VisionMeasurement(C.Structure):
     _fields_ = [("pose_x", C.c_double), ("pose_y", C.c_double), ("pose_rot", C.c_double),
                 ("std_x", C.c_double), ("std_y", C.c_double), ("std_rot", C.c_double), ("ts", C.c_uint64),
@@ -134,6 +151,7 @@ assert C.sizeof(TagPoseParams) == 112 and C.sizeof(TagPose) == 296
 assert C.sizeof(JpegFrame) == 16 and C.sizeof(JpegInfo) == 32
 assert C.sizeof(RawFormat) == 8
 assert C.sizeof(PreviewParams) == 24
+assert C.sizeof(Rect) == 16 and C.sizeof(ExposureStats) == 6416 and C.sizeof(ExposureParams) == 96
 
 # per-frame status bits (include/chalkydri_hip.h)
 CK_FRAME_OK, CK_FRAME_POINTS_OVERFLOW, CK_FRAME_CLUSTERS_OVERFLOW, CK_FRAME_QUADS_OVERFLOW, CK_FRAME_DETS_OVERFLOW = 0, 1, 2, 4, 8

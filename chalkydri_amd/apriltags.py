@@ -32,11 +32,14 @@ def load_field_layout(path_or_dict):
 
 class AprilTags:
     def __init__(self, width, height, field, calib, robot_to_cam, cam_id=0, family="tag36h11", bits_corrected=3,
-                 max_batch=1, device=0, quad_sigma=0.0, fourcc=None, orientation="none", **cfg):
+                 max_batch=1, device=0, quad_sigma=0.0, fourcc=None, orientation="none", auto_exposure=False, exposure0=1.0,
+                 exposure_params=None, **cfg):
         """width x height is the image the detector sees, and calib its intrinsics: with an `orientation` ("none", "clockwise",
         "rotate-180", "counterclockwise": the reference's VideoOrientation names) those of the ORIENTED image.  `fourcc` names the
         raw format of the camera's frames for process_raw_batch ("YUYV", "RGB3", ...; None: 8-bit luma), or "MJPG" / "JPEG": the
-        camera delivers one JPEG per frame (what the reference's USB cameras do at full rate), decoded and turned on the device."""
+        camera delivers one JPEG per frame (what the reference's USB cameras do at full rate), decoded and turned on the device.
+        auto_exposure=True (the reference's Camera.auto_exposure) meters the last frame of every batch the task stages, on the
+        device, and keeps the exposure to set next in `exposure` (unit and start: exposure0); off, nothing is launched."""
         if fourcc in A.JPEG_FOURCCS:
             from .detector import orientation_code
             orientation_code(orientation)                           # (ValueError for an unknown name, before any device work)
@@ -60,6 +63,10 @@ class AprilTags:
         self._pp.field, self._pp.n_field = self._field, len(self.tags)
         self._pp.camera_id, self._pp.sign_change_error = cam_id, SIGN_FLIP_CONST
         self._pp.sqpnp = self.solver._prm
+        self._exposure = None
+        if auto_exposure:
+            from .exposure import ExposureController
+            self._exposure = ExposureController(exposure_params, exposure0)
 
     def process_batch(self, frames=None, gyro=None, n=None):
         """frames [n][h][w] (or None to reuse uploaded frames); gyro: per-frame heading or None entries ("no gyro").
@@ -76,7 +83,14 @@ class AprilTags:
         out = (A.VisionMeasurement * n)()
         valid = (C.c_int32 * n)()
         check(det._L.ck_process_uploaded(det._h, n, C.byref(self._pp), g.ctypes.data, has.ctypes.data, out, valid), "ck_process_uploaded")
+        if self._exposure is not None and n > 0:   # the newest frame of the batch says what to set for the next one
+            self._exposure.update(det.exposure_stats(frames=[n - 1], params=self._exposure.params))
         return out, np.array(valid[:], bool)
+
+    @property
+    def exposure(self):
+        """The exposure to set next, in exposure0's unit (None unless auto_exposure=True)."""
+        return None if self._exposure is None else self._exposure.exposure
 
     def preview(self, frames=None, n=None, overlay=True, **kw):
         """After process_batch: the driver-station JPEGs (bytes each) of the frames just processed — indices into the staged

@@ -167,6 +167,7 @@ extern "C" void ck_destroy(ck_handle_t *h) {
     ck_jpeg_free(h);
     ck_raw_free(h);
     ck_preview_free(h);
+    ck_exposure_free(h);
     for (auto &e : h->ev) if (e) (void)hipEventDestroy(e);
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
     if (h->ev_join) (void)hipEventDestroy(h->ev_join);

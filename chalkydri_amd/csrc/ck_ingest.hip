@@ -9,6 +9,7 @@
 
 #include <new>
 
+#include "ck_exposure.h"
 #include "ck_internal.h"
 #include "ck_jpeg.h"
 #include "ck_rawfmt.h"
@@ -205,4 +206,14 @@ extern "C" int ck_process_ingested(ck_ingest_t *g, int32_t slot, int32_t n, cons
     const int rc = ck_process_frames(h, {g->dev[slot], h->frame_stride, h->frame_pitch}, n, pp, gyro, has_gyro, out, valid);
     if (rc == CK_OK) g->pending[slot] = false;
     return rc;
+}
+
+// Exposure metering (ck_exposure.hip) of a submitted slot's frames; the slot stays as it is, so ck_detect_ingested may follow.
+extern "C" int ck_exposure_stats_ingested(ck_ingest_t *g, int32_t slot, const int32_t *frames, int32_t n, const ck_exposure_params_t *p,
+                                          const ck_rect_t *roi, ck_exposure_stats_t *out) {
+    if (!g || slot < 0 || slot >= g->nslots) return CK_EINVAL;
+    ck_handle *h = g->h;
+    CK_HIP(hipSetDevice(h->device));
+    if (g->staged[slot] > 0) CK_HIP(hipStreamWaitEvent(h->stream, g->ready[slot], 0));
+    return ck_exposure_run(h, {g->dev[slot], h->frame_stride, h->frame_pitch}, g->staged[slot], frames, n, p, roi, out);
 }

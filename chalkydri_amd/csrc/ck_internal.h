@@ -211,6 +211,8 @@ struct ck_handle {
     struct ck_raw_ws *raw;
     // JPEG preview of the staged frames (ck_preview.hip, k_jpegenc.hip): allocated by the first preview call, grown on demand
     struct ck_preview_ws *preview;
+    // exposure metering of the staged frames (ck_exposure.hip, k_exposure.hip): allocated by the first exposure call, grown on demand
+    struct ck_exposure_ws *exposure;
     bool fmerge_lds_allowed; // k_fmerge's dynamic LDS limit has been raised on this handle's device
 };
 
@@ -313,6 +315,7 @@ void ck_bufs_free(ck_handle *h);
 void ck_jpeg_free(ck_handle *h); // ck_jpeg.hip: the JPEG workspace
 void ck_raw_free(ck_handle *h);  // ck_rawfmt.hip: the raw-format staging
 void ck_preview_free(ck_handle *h); // ck_preview.hip: the preview encoder's workspace
+void ck_exposure_free(ck_handle *h); // ck_exposure.hip: the exposure meter's workspace
 int ck_stage_device_frames(ck_handle *h, const uint8_t *d_frames, int n, int stride, int64_t frame_pitch, ck_dev_image *use);
 int ck_run_threshold_segment(ck_handle *h, const ck_dev_image &img, int n);
 // gradient clusters from thresh/labels/csize of frames [0,n)

@@ -86,6 +86,14 @@ def _bind(L):
     L.ck_preview_layout.argtypes = [pv, i32, i32, _P(i32), _P(i32), _P(C.c_int64)]
     L.ck_preview_jpeg.argtypes = [vp, pv, vp, i32, vp, C.c_int64, vp, vp]
     L.ck_preview_luma.argtypes = [vp, pv, vp, i32, vp]
+    ep, es = _P(A.ExposureParams), _P(A.ExposureStats)
+    L.ck_exposure_params_default.argtypes = [ep]
+    L.ck_exposure_params_default.restype = None
+    L.ck_exposure_luts.argtypes = [ep, vp]
+    L.ck_exposure_metric.argtypes = [ep, es, _P(C.c_double)]
+    L.ck_exposure_recommend.argtypes = [ep, es, C.c_double, _P(C.c_double), _P(C.c_double)]
+    L.ck_exposure_stats.argtypes = [vp, vp, i32, ep, vp, vp]
+    L.ck_exposure_stats_ingested.argtypes = [vp, i32, vp, i32, ep, vp, vp]
     L._ck_bound = True
     return L
 
@@ -530,6 +538,15 @@ class AprilTagDetector:
               "ck_preview_luma")
         return out
 
+    # -- exposure metering of the staged frames, on the GPU (chalkydri_amd/exposure.py has the parameters and the controller) ----
+    def exposure_stats(self, n=None, frames=None, roi=None, params=None):
+        """One ck_exposure_stats_t per metered frame, as a structured numpy array (fields luma [256], grad [7][192], n_luma,
+        n_grad): the luma histogram and, per gamma curve of `params` (ExposureParams; None: the defaults), the histogram of the
+        Sobel gradient magnitude, over `roi`.  frames: indices into the staged frames, or n for 0..n-1.  roi: None (whole
+        frames), one (x0, y0, x1, y1) for every frame, or one per frame; half-open, clamped to the frame."""
+        from . import exposure as X
+        return X.stats_call(self, None, n, frames, roi, params)
+
     def stage_ms(self):
         ms = A.StageMs()
         check(self._L.ck_last_stage_ms(self._h, C.byref(ms)), "ck_last_stage_ms")
@@ -622,6 +639,11 @@ class IngestRing:
         status = (C.c_uint32 * max(n, 1))()
         check(self._L.ck_ingest_jpeg_status(self._g, slot, n, status), "ck_ingest_jpeg_status")
         return list(status)[:n]
+
+    def exposure_stats(self, slot, n=None, frames=None, roi=None, params=None):
+        """AprilTagDetector.exposure_stats on the frames of a submitted slot (waits for its upload; the slot stays as it is)."""
+        from . import exposure as X
+        return X.stats_call(self.det, (self._g, slot), n, frames, roi, params)
 
     def detect(self, slot, n, cap=64):
         dets = (A.Detection * (cap * n))()

@@ -290,6 +290,61 @@ inline std::vector<uint8_t> mjpeg_part(const std::vector<uint8_t> &jpeg) {
     return out;
 }
 
+// ---- exposure metering of the staged frames on the device (chalkydri_hip.h: ck_exposure_stats / ck_exposure_recommend) ----------
+// The loop the reference leaves open (Camera.auto_exposure, crates/chalkydri_core/src/config.rs:64-65; the V4L2 controls commented
+// out in crates/chalkydri/src/cameras/pipeline.rs:237-245): the device histograms the gradients of every staged frame under seven
+// gamma curves, the host turns them into the exposure to set next.  Driving the camera stays the caller's part.
+inline ck_exposure_params_t exposure_params() {
+    ck_exposure_params_t p;
+    ck_exposure_params_default(&p);
+    return p;
+}
+// One record per entry of `frames` (indices into the staged frames); roi: empty = whole frames, else one rectangle per entry.
+inline std::vector<ck_exposure_stats_t> exposure_stats(Handle &h, const std::vector<int32_t> &frames, const ck_exposure_params_t &p,
+                                                       const std::vector<ck_rect_t> &roi = {}) {
+    if (!roi.empty() && roi.size() != frames.size()) throw Panic("exposure_stats: one rectangle per frame", CK_EINVAL);
+    std::vector<ck_exposure_stats_t> out(frames.size() ? frames.size() : 1);
+    check(ck_exposure_stats(h.get(), frames.data(), (int32_t)frames.size(), &p, roi.empty() ? nullptr : roi.data(), out.data()), "ck_exposure_stats");
+    out.resize(frames.size());
+    return out;
+}
+// Keeps one camera's exposure (in the caller's unit: a V4L2 exposure_time_absolute, milliseconds, a gain) and moves it by what
+// every metered frame recommends.
+class ExposureController {
+  public:
+    explicit ExposureController(double exposure0, const ck_exposure_params_t &p = exposure_params()) : p_(p), exposure_(exposure0) {
+        uint8_t lut[CK_EXPOSURE_GAMMAS * 256];
+        check(ck_exposure_luts(&p_, lut), "ck_exposure_luts"); // (refuses bad parameters here, not at the first frame)
+        if (!(exposure0 > 0) || !std::isfinite(exposure0)) throw Panic("ExposureController: exposure must be positive", CK_EINVAL);
+    }
+    double update(const ck_exposure_stats_t &s) {
+        double next = exposure_;
+        check(ck_exposure_recommend(&p_, &s, exposure_, &next, &gamma_hat_), "ck_exposure_recommend");
+        return exposure_ = next;
+    }
+    double exposure() const { return exposure_; }
+    double gamma_hat() const { return gamma_hat_; } // of the last update: below 1 = the frame wanted brightening
+    const ck_exposure_params_t &params() const { return p_; }
+    // The rectangle to meter next: the bounding box of a frame's detections grown by `margin` pixels and clamped to the frame, or
+    // the whole frame when there are none.
+    static ck_rect_t roi_from_detections(const std::vector<Detection> &dets, int margin, int w, int h) {
+        if (dets.empty()) return {0, 0, w, h};
+        double x0 = 1e300, y0 = 1e300, x1 = -1e300, y1 = -1e300;
+        for (const Detection &d : dets)
+            for (const auto &c : d.corners()) {
+                x0 = std::min(x0, c[0]); x1 = std::max(x1, c[0]);
+                y0 = std::min(y0, c[1]); y1 = std::max(y1, c[1]);
+            }
+        const auto clampi = [](double v, int hi) { return (int32_t)std::min<double>(std::max<double>(v, 0), hi); };
+        return {clampi(std::floor(x0) - margin, w), clampi(std::floor(y0) - margin, h), clampi(std::floor(x1) + 1 + margin, w),
+                clampi(std::floor(y1) + 1 + margin, h)};
+    }
+
+  private:
+    ck_exposure_params_t p_;
+    double exposure_, gamma_hat_ = 1.0;
+};
+
 namespace apriltags {
 
 enum class Color : uint8_t { Black = 0, White = 1, Other = 2 }; // src/utils.rs:2-6

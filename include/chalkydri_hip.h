@@ -406,7 +406,7 @@ int ck_estimate_tag_poses(ck_handle_t *h, const ck_tag_pose_params_t *pp, const 
  * holds no such call's result: no detect / process call since ck_create, a failed one, or a later call that rewrote the
  * workspace: ck_clusters_batch and ck_quads_batch.  ck_upload_frames, ck_upload_raw, ck_upload_raw_device, ck_raw_luma_batch, ck_threshold_batch, ck_segment_batch,
  * ck_quad_image_batch, ck_time_threshold_segment, ck_set_quad_sigma, ck_sqpnp_solve_batch, ck_gather_poses, ck_preview_jpeg,
- * ck_preview_luma, the ck_cat_*
+ * ck_preview_luma, ck_exposure_stats, ck_exposure_stats_ingested, the ck_cat_*
  * and ck_ingest_write / ck_ingest_submit calls leave it as it is. */
 int ck_last_tag_poses(ck_handle_t *h, const ck_tag_pose_params_t *pp, ck_tag_pose_t *out, int32_t cap_per_frame,
                       int32_t *counts);
@@ -587,6 +587,63 @@ int ck_preview_jpeg(ck_handle_t *h, const ck_preview_params_t *pp, const int32_t
 /* The scaled (+ overlaid) pixels the encoder is given, out [n][ph][pw] (host or device pointer): for tests and for callers with
  * an encoder of their own.  quality and restart_rows are validated and otherwise unused.  Errors as ck_preview_jpeg. */
 int ck_preview_luma(ck_handle_t *h, const ck_preview_params_t *pp, const int32_t *frames, int32_t n, uint8_t *out);
+
+/* ---- exposure metering of the staged frames on the device ---------------------------------------------------------------
+ * The camera-side loop the reference leaves open (Camera.auto_exposure / manual_exposure, crates/chalkydri_core/src/config.rs:64-65;
+ * the commented-out V4L2 controls of crates/chalkydri/src/cameras/pipeline.rs:237-245; the stub crate crates/aaec): gradient-based
+ * metering with a gamma sweep, after Shim, Lee and Kweon (2014).  The device re-renders every staged frame under CK_EXPOSURE_GAMMAS
+ * gamma curves and histograms the Sobel gradient magnitude of each; the host turns the histograms into the gamma that carries the
+ * most gradient information and scales the caller's exposure by it.  Everything the device produces is an integer.  DESIGN.md §4f
+ * is the contract.  Per selected frame F (W x H) and rectangle R (clamped to the frame; NULL = the frame; empty = all-zero stats):
+ *   luma[v]      pixels of R with F = v; n_luma = |R|
+ *   I_k          lut[k][F], lut = ck_exposure_luts(p)
+ *   Gx, Gy       the 3 x 3 Sobel pair on I_k (weights 1 2 1, not normalised): |Gx|, |Gy| <= 1020
+ *   bin          floor(sqrt(Gx^2 + Gy^2)) >> 3, 0..180, the floor exact
+ *   grad[k][bin] pixels of R intersected with [1, W-1) x [1, H-1): neighbours outside R are read; n_grad = that area */
+#define CK_EXPOSURE_GAMMAS 7
+#define CK_EXPOSURE_BINS 192 /* bins 0..180 are reachable */
+typedef struct ck_rect {
+    int32_t x0, y0, x1, y1;  /* half-open: x0 <= x < x1, y0 <= y < y1 */
+} ck_rect_t;
+typedef struct ck_exposure_stats {
+    uint32_t luma[256];
+    uint32_t grad[CK_EXPOSURE_GAMMAS][CK_EXPOSURE_BINS];
+    uint32_t n_luma, n_grad;
+    uint32_t pad[2];
+} ck_exposure_stats_t;
+typedef struct ck_exposure_params {
+    double gamma[CK_EXPOSURE_GAMMAS]; /* strictly increasing, all > 0; default 1/1.9, 1/1.5, 1/1.2, 1, 1.2, 1.5, 1.9 */
+    double lambda, delta;             /* the metric's weight W(m); default 1000, 0.06 */
+    double kp;                        /* gain of the recommendation; default 1 */
+    double e_min, e_max;              /* clamp of the recommendation; default 1e-6, 1e6 */
+} ck_exposure_params_t;
+/* Host arithmetic, no device needed.  CK_EINVAL from all of them: a null pointer, a parameter that is not finite, a gamma, lambda,
+ * kp, e_min or e_max <= 0, gammas not strictly increasing, delta outside [0, 1), e_min > e_max.
+ *   ck_exposure_luts       lut[k][v] = floor(255 (v / 255)^gamma[k] + 0.5), lut[k][0] = 0, lut[k][255] = 255, identity at gamma 1
+ *   ck_exposure_metric     m[k] = (1 / n_grad) sum_b grad[k][b] W(b / 180) in ascending b, W(x) = log(lambda (x - delta) + 1) /
+ *                          log(lambda (1 - delta) + 1) for x >= delta, else 0; n_grad = 0 gives 0
+ *   ck_exposure_recommend  k* = first index of the largest m; gamma_hat = gamma[k*] at an end index, else the vertex of the parabola
+ *                          through (ln gamma[j], m[j]), j = k*-1..k*+1, clamped to [gamma[k*-1], gamma[k*+1]] (gamma[k*] when the
+ *                          second difference is zero); all m equal gives 1.  next = clamp(exposure gamma_hat^-kp, e_min, e_max):
+ *                          a best gamma below 1 means the frame wants brightening.  exposure must be finite and > 0; its unit is
+ *                          the caller's.  gamma_hat may be NULL. */
+void ck_exposure_params_default(ck_exposure_params_t *p);
+int ck_exposure_luts(const ck_exposure_params_t *p, uint8_t *lut);
+int ck_exposure_metric(const ck_exposure_params_t *p, const ck_exposure_stats_t *s, double *m);
+int ck_exposure_recommend(const ck_exposure_params_t *p, const ck_exposure_stats_t *s, double exposure, double *next,
+                          double *gamma_hat);
+/* Meters n staged frames (whatever staged them) in one pass on the handle's stream.  frames: n indices into the staged frames
+ * (NULL = 0..n-1; an index may repeat); roi: n rectangles or NULL; out: n records in host memory.  Returns when they are complete
+ * and leaves the staged frames and every detector buffer as they are.  CK_EINVAL: a null handle / p / out, n < 0, an index
+ * outside the staged frames, params the host functions refuse.  CK_ECAPACITY: n > max_batch.  CK_ENOMEM: the workspace (n records
+ * and the tables on the device, n records of pinned host memory; allocated by the first call, grown on demand; ck_create allocates
+ * none of it) could not grow. */
+int ck_exposure_stats(ck_handle_t *h, const int32_t *frames, int32_t n, const ck_exposure_params_t *p, const ck_rect_t *roi,
+                      ck_exposure_stats_t *out);
+/* The same on the frames of a submitted slot of an ingest ring of any kind (indices below the count the slot was submitted with);
+ * waits for the slot's upload like ck_detect_ingested, and leaves the slot as it is: ck_detect_ingested may follow. */
+int ck_exposure_stats_ingested(ck_ingest_t *ing, int32_t slot, const int32_t *frames, int32_t n, const ck_exposure_params_t *p,
+                               const ck_rect_t *roi, ck_exposure_stats_t *out);
 
 /* ---- multi-GPU: the final pose gather ----------------------------------------------------------------------------------
  * Frames shard over GPUs without any data-path collective (one handle, one process or host thread per GPU).  The only
