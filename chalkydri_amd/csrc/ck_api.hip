@@ -5,7 +5,11 @@
 #include <new>
 #include <vector>
 
+#include "ck_exposure.h"
 #include "ck_internal.h"
+#include "ck_jpeg.h"
+#include "ck_preview.h"
+#include "ck_rawfmt.h"
 
 thread_local char ck_err_text[512] = "";
 
@@ -164,10 +168,10 @@ extern "C" void ck_destroy(ck_handle_t *h) {
     for (auto &st : h->fit_stream) if (st) (void)hipStreamSynchronize(st);
     if (h->seg_stream) (void)hipStreamSynchronize(h->seg_stream);
     ck_bufs_free(h);
-    ck_jpeg_free(h);
-    ck_raw_free(h);
-    ck_preview_free(h);
-    ck_exposure_free(h);
+    delete h->jpeg; // the on-demand workspaces own their buffers (ck_grow.h)
+    delete h->raw;
+    delete h->preview;
+    delete h->exposure;
     for (auto &e : h->ev) if (e) (void)hipEventDestroy(e);
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
     if (h->ev_join) (void)hipEventDestroy(h->ev_join);
@@ -181,6 +185,12 @@ extern "C" void ck_destroy(ck_handle_t *h) {
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     (void)hipGetLastError(); // (what the clean-up calls above may have left behind — a handle that never got its device, say — is not the next call's error)
+}
+
+int ck_read_staged_luma(ck_handle *h, int n, uint8_t *luma_out) {
+    if (n) CK_HIP(hipMemcpy2DAsync(luma_out, (size_t)h->w, h->d_frames, (size_t)h->frame_stride, (size_t)h->w, (size_t)h->h * n,
+                                   hipMemcpyDeviceToHost, h->stream));
+    return CK_OK;
 }
 
 static int check_imgs(const ck_handle *h, const ck_image_u8_t *imgs, int n) {

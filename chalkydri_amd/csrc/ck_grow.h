@@ -1,0 +1,65 @@
+// The buffers of the on-demand workspaces (JPEG decode, raw staging, preview, exposure; one JPEG workspace per slot of a JPEG ingest
+// ring): each owns its memory, grows when a call needs more and releases it when its workspace is deleted.  DESIGN.md §4g.
+#ifndef CK_GROW_H
+#define CK_GROW_H
+
+#include <new>
+
+#include "ck_internal.h"
+
+// reserve(): at least `need` bytes.  A buffer that is large enough stays; otherwise it is freed and allocated again (its contents
+// are never needed across a growth), `need` bytes exactly or with a quarter of headroom, so a stream of slowly growing calls
+// does not reallocate every time.
+template <typename T>
+struct ck_dev_buf { // device memory through ck_malloc_dev: CK_POISON fill and guard pages apply
+    T *p = nullptr;
+    size_t cap = 0; // bytes
+    ck_dev_buf() = default;
+    ck_dev_buf(const ck_dev_buf &) = delete;
+    ck_dev_buf &operator=(const ck_dev_buf &) = delete;
+    ~ck_dev_buf() { (void)ck_free_dev(p); }
+    operator T *() const { return p; }
+    int reserve(size_t need, bool exact = false) { // CK_OK / CK_ENOMEM / CK_EDEVICE (ck_err_text set)
+        if (need <= cap) return CK_OK;
+        (void)ck_free_dev(p);
+        p = nullptr; cap = 0;
+        const size_t want = exact ? need : need + need / 4;
+        CK_HIP_ALLOC(ck_malloc_dev(&p, want));
+        cap = want;
+        return CK_OK;
+    }
+};
+
+template <typename T>
+struct ck_pinned_buf { // pinned host memory
+    T *p = nullptr;
+    size_t cap = 0; // bytes
+    ck_pinned_buf() = default;
+    ck_pinned_buf(const ck_pinned_buf &) = delete;
+    ck_pinned_buf &operator=(const ck_pinned_buf &) = delete;
+    ~ck_pinned_buf() { if (p) (void)hipHostFree(p); }
+    operator T *() const { return p; }
+    int reserve(size_t need, bool exact = false) { // CK_OK / CK_ENOMEM
+        if (need <= cap) return CK_OK;
+        if (p) (void)hipHostFree(p);
+        p = nullptr; cap = 0;
+        const size_t want = exact ? need : need + need / 4;
+        if (hipHostMalloc(reinterpret_cast<void **>(&p), want, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            p = nullptr;
+            return CK_ENOMEM;
+        }
+        cap = want;
+        return CK_OK;
+    }
+};
+
+// A handle's workspace of one on-demand feature (`slot` = ck_handle::jpeg, raw, preview or exposure): created by the first call that
+// needs it, deleted by ck_destroy.  nullptr: out of memory.
+template <typename W>
+static inline W *ck_workspace(W *&slot) {
+    if (!slot) slot = new (std::nothrow) W();
+    return slot;
+}
+
+#endif

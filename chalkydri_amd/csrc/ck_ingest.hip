@@ -23,13 +23,11 @@ struct ck_ingest {
     hipEvent_t ready[8];
     int staged[8];
     hipStream_t copy;
-    // a ring of ck_ingest_create_raw: the pinned slots and rawdev[] hold raw frames (rows of rstride, frames of rpitch); submit
-    // converts them into dev[], which is luma in the handle's staged layout on either kind of ring
+    // a ring of ck_ingest_create_raw: the pinned slots and rawdev[] hold raw frames (rows of geo.stride16, frames of geo.pitch16);
+    // submit converts them into dev[], which is luma in the handle's staged layout on either kind of ring
     bool raw;
     ck_raw_format_t fmt;
-    ck_raw_class cls;
-    int sw, sh, min_stride, rstride;
-    size_t rpitch;
+    ck_raw_geom geo;
     uint8_t *rawdev[8];
     // a ring of ck_ingest_create_jpeg: no pinned luma slots (host[] stays null); the compressed frames, their staging and the decode
     // workspace of every slot live in `jpeg` (ck_jpeg.hip), and submit decodes them into dev[]
@@ -37,23 +35,31 @@ struct ck_ingest {
     bool pending[8]; // the slot's last submit may still be reading its staging (cleared once ready[slot] has been waited for)
 };
 
-static bool luma_first(uint32_t fourcc) {
-    auto cc = [](const char *s) { return (uint32_t)(uint8_t)s[0] | ((uint32_t)(uint8_t)s[1] << 8) | ((uint32_t)(uint8_t)s[2] << 16) | ((uint32_t)(uint8_t)s[3] << 24); };
-    return fourcc == cc("GREY") || fourcc == cc("GRAY") || fourcc == cc("Y800") || fourcc == cc("NV12") || fourcc == cc("NV21") ||
-           fourcc == cc("I420") || fourcc == cc("YV12");
+static bool slot_ok(const ck_ingest *g, int slot) { return g && slot >= 0 && slot < g->nslots; }
+// the slot's luma frames, in the handle's staged layout
+static ck_dev_image slot_image(const ck_ingest *g, int slot) { return {g->dev[slot], g->h->frame_stride, g->h->frame_pitch}; }
+// the slot's last submit is done: its staging and its workspace are free again
+static int wait_slot(ck_ingest *g, int slot) {
+    CK_HIP(hipEventSynchronize(g->ready[slot]));
+    g->pending[slot] = false;
+    return CK_OK;
+}
+// what the *_ingested calls start with, their arguments checked: the handle's stream waits for the slot's submit
+static int await_slot(ck_ingest *g, int slot, ck_dev_image *img) {
+    CK_HIP(hipSetDevice(g->h->device));
+    if (g->staged[slot] > 0) CK_HIP(hipStreamWaitEvent(g->h->stream, g->ready[slot], 0));
+    *img = slot_image(g, slot);
+    return CK_OK;
 }
 
 static int ingest_create(ck_handle_t *h, int32_t n_slots, const ck_raw_format_t *fmt, ck_ingest_t **out, bool jpeg = false,
                          int32_t orientation = 0, int64_t max_frame_bytes = 0) {
     if (!h || !out || n_slots < 1 || n_slots > 8) return CK_EINVAL;
     *out = nullptr;
-    int32_t sw = 0, sh = 0, min_stride = 0;
-    int64_t min_bytes = 0;
-    ck_raw_class cls = {};
+    ck_raw_geom geo = {};
     if (fmt) {
-        const int rc = ck_raw_layout(fmt, h->w, h->h, &sw, &sh, &min_stride, &min_bytes);
+        const int rc = ck_raw_geometry(fmt, h->w, h->h, &geo);
         if (rc != CK_OK) return rc;
-        (void)ck_raw_classify(fmt->fourcc, &cls);
     }
     CK_HIP(hipSetDevice(h->device));
     ck_ingest *g = new (std::nothrow) ck_ingest();
@@ -63,11 +69,8 @@ static int ingest_create(ck_handle_t *h, int32_t n_slots, const ck_raw_format_t 
     const size_t dev_bytes = h->frame_pitch * (size_t)h->cfg.max_batch;
     g->slot_bytes = dev_bytes;
     if (fmt) {
-        g->raw = true; g->fmt = *fmt; g->cls = cls;
-        g->sw = sw; g->sh = sh; g->min_stride = min_stride;
-        g->rstride = (min_stride + 15) / 16 * 16;
-        g->rpitch = (size_t)g->rstride * sh;
-        g->slot_bytes = g->rpitch * (size_t)h->cfg.max_batch;
+        g->raw = true; g->fmt = *fmt; g->geo = geo;
+        g->slot_bytes = geo.pitch16 * (size_t)h->cfg.max_batch;
     }
     hipError_t e = hipStreamCreateWithFlags(&g->copy, hipStreamNonBlocking);
     for (int s = 0; s < n_slots && e == hipSuccess; s++) {
@@ -91,7 +94,7 @@ static int ingest_create(ck_handle_t *h, int32_t n_slots, const ck_raw_format_t 
 }
 
 extern "C" int ck_ingest_create_jpeg(ck_handle_t *h, int32_t n_slots, int32_t orientation, int64_t max_frame_bytes, ck_ingest_t **out) {
-    if (orientation < CK_ORIENT_NONE || orientation > CK_ORIENT_COUNTERCLOCKWISE || max_frame_bytes < 0) return CK_EINVAL;
+    if (!ck_orientation_ok(orientation) || max_frame_bytes < 0) return CK_EINVAL;
     return ingest_create(h, n_slots, nullptr, out, true, orientation, max_frame_bytes);
 }
 
@@ -117,25 +120,27 @@ extern "C" void ck_ingest_destroy(ck_ingest_t *g) {
     delete g;
 }
 
-extern "C" int32_t ck_ingest_stride(const ck_ingest_t *g) { return !g || g->jpeg ? 0 : g->raw ? g->rstride : g->h->frame_stride; }
+extern "C" int32_t ck_ingest_stride(const ck_ingest_t *g) { return !g || g->jpeg ? 0 : g->raw ? g->geo.stride16 : g->h->frame_stride; }
 
 extern "C" uint8_t *ck_ingest_frame(ck_ingest_t *g, int32_t slot, int32_t index) {
-    if (!g || g->jpeg || slot < 0 || slot >= g->nslots || index < 0 || index >= g->h->cfg.max_batch) return nullptr;
-    return g->host[slot] + (size_t)index * (g->raw ? g->rpitch : g->h->frame_pitch);
+    if (!slot_ok(g, slot) || g->jpeg || index < 0 || index >= g->h->cfg.max_batch) return nullptr;
+    return g->host[slot] + (size_t)index * (g->raw ? g->geo.pitch16 : g->h->frame_pitch);
 }
 
 extern "C" int ck_ingest_write(ck_ingest_t *g, int32_t slot, int32_t index, const ck_image_u8_t *img, uint32_t fourcc) {
     if (g && g->jpeg) return CK_EUNSUPPORTED; // (compressed frames go through ck_ingest_write_jpeg)
     uint8_t *dst = ck_ingest_frame(g, slot, index);
     if (!dst || !img || !img->buf) return CK_EINVAL;
+    ck_raw_class cls;
+    if (ck_raw_classify(fourcc, &cls) != CK_OK) return CK_EUNSUPPORTED;
     if (g->raw) { // exactly the ring's family, the ring's source geometry, min_stride bytes per row
-        ck_raw_class cls;
-        if (ck_raw_classify(fourcc, &cls) != CK_OK || !ck_raw_same_family(cls, g->cls)) return CK_EUNSUPPORTED;
-        if (img->width != g->sw || img->height != g->sh || img->stride < g->min_stride) return CK_EINVAL;
-        for (int y = 0; y < g->sh; y++) memcpy(dst + (size_t)y * g->rstride, img->buf + (size_t)y * img->stride, (size_t)g->min_stride);
+        const ck_raw_geom &G = g->geo;
+        if (!ck_raw_same_family(cls, G.cls)) return CK_EUNSUPPORTED;
+        if (img->width != G.sw || img->height != G.sh || img->stride < G.min_stride) return CK_EINVAL;
+        for (int y = 0; y < G.sh; y++) memcpy(dst + (size_t)y * G.stride16, img->buf + (size_t)y * img->stride, (size_t)G.min_stride);
         return CK_OK;
     }
-    if (!luma_first(fourcc)) return CK_EUNSUPPORTED;
+    if (cls.bpp != 1) return CK_EUNSUPPORTED; // a plain ring takes the formats that start with a luma plane
     const ck_handle *h = g->h;
     if (img->width != h->w || img->height != h->h || img->stride < img->width) return CK_EINVAL;
     for (int y = 0; y < h->h; y++) memcpy(dst + (size_t)y * h->frame_stride, img->buf + (size_t)y * img->stride, (size_t)h->w);
@@ -143,39 +148,37 @@ extern "C" int ck_ingest_write(ck_ingest_t *g, int32_t slot, int32_t index, cons
 }
 
 extern "C" int ck_ingest_write_jpeg(ck_ingest_t *g, int32_t slot, int32_t index, const uint8_t *data, int64_t size) {
-    if (!g || !g->jpeg || !data || size < 4 || slot < 0 || slot >= g->nslots || index < 0 || index >= g->h->cfg.max_batch) return CK_EINVAL;
+    if (!slot_ok(g, slot) || !g->jpeg || !data || size < 4 || index < 0 || index >= g->h->cfg.max_batch) return CK_EINVAL;
     if (g->pending[slot]) { // (a caller that keeps the header's rule never waits here: the call that processed the slot already has)
         CK_HIP(hipSetDevice(g->h->device));
-        CK_HIP(hipEventSynchronize(g->ready[slot]));
-        g->pending[slot] = false;
+        const int rc = wait_slot(g, slot);
+        if (rc != CK_OK) return rc;
     }
     return ck_jpeg_slots_write(g->jpeg, slot, index, data, size);
 }
 
 extern "C" int ck_ingest_jpeg_status(ck_ingest_t *g, int32_t slot, int32_t n, uint32_t *jpeg_status) {
-    if (!g || !g->jpeg || !jpeg_status || slot < 0 || slot >= g->nslots || n != g->staged[slot]) return CK_EINVAL;
+    if (!slot_ok(g, slot) || !g->jpeg || !jpeg_status || n != g->staged[slot]) return CK_EINVAL;
     if (n == 0) return CK_OK;
     CK_HIP(hipSetDevice(g->h->device));
-    CK_HIP(hipEventSynchronize(g->ready[slot]));
-    g->pending[slot] = false;
+    const int rc = wait_slot(g, slot);
+    if (rc != CK_OK) return rc;
     memcpy(jpeg_status, ck_jpeg_slots_status(g->jpeg, slot), sizeof(uint32_t) * (size_t)n);
     return CK_OK;
 }
 
 extern "C" int ck_ingest_submit(ck_ingest_t *g, int32_t slot, int32_t n) {
-    if (!g || slot < 0 || slot >= g->nslots || n < 0 || n > g->h->cfg.max_batch) return CK_EINVAL;
+    if (!slot_ok(g, slot) || n < 0 || n > g->h->cfg.max_batch) return CK_EINVAL;
     CK_HIP(hipSetDevice(g->h->device));
     if (g->jpeg) { // head copy, payload copy, decode, oriented IDCT and the status copy, all on the copy stream ahead of the slot's event
-        if (g->pending[slot]) { // the slot's staging and workspace may still serve its last submit
-            CK_HIP(hipEventSynchronize(g->ready[slot]));
-            g->pending[slot] = false;
-        }
-        const int rc = ck_jpeg_slots_submit(g->jpeg, slot, n, g->copy, {g->dev[slot], g->h->frame_stride, g->h->frame_pitch});
+        int rc = g->pending[slot] ? wait_slot(g, slot) : CK_OK; // the slot's staging and workspace may still serve its last submit
+        if (rc == CK_OK) rc = ck_jpeg_slots_submit(g->jpeg, slot, n, g->copy, slot_image(g, slot));
         if (rc != CK_OK) return rc;
         g->pending[slot] = n > 0;
     } else if (n && g->raw) { // the copy and the conversion both run on the copy stream, ahead of the slot's event
-        CK_HIP(hipMemcpyAsync(g->rawdev[slot], g->host[slot], g->rpitch * (size_t)n, hipMemcpyHostToDevice, g->copy));
-        const int rc = ck_launch_rawfmt(g->h, g->copy, {g->rawdev[slot], g->rstride, g->rpitch, g->sw, g->sh}, g->cls, g->fmt.orientation, g->dev[slot], n);
+        const ck_raw_geom &G = g->geo;
+        CK_HIP(hipMemcpyAsync(g->rawdev[slot], g->host[slot], G.pitch16 * (size_t)n, hipMemcpyHostToDevice, g->copy));
+        const int rc = ck_launch_rawfmt(g->h, g->copy, {g->rawdev[slot], G.stride16, G.pitch16, G.sw, G.sh}, G.cls, g->fmt.orientation, g->dev[slot], n);
         if (rc != CK_OK) return rc;
     } else if (n) CK_HIP(hipMemcpyAsync(g->dev[slot], g->host[slot], g->h->frame_pitch * (size_t)n, hipMemcpyHostToDevice, g->copy));
     CK_HIP(hipEventRecord(g->ready[slot], g->copy));
@@ -186,24 +189,22 @@ extern "C" int ck_ingest_submit(ck_ingest_t *g, int32_t slot, int32_t n) {
 // `n` is the caller's statement of how many frames its output arrays hold: it must be the count the slot was submitted with
 // (the kernels write one entry per staged frame).
 extern "C" int ck_detect_ingested(ck_ingest_t *g, int32_t slot, int32_t n, ck_detection_t *dets, int32_t cap, int32_t *counts, uint32_t *status) {
-    if (!g || slot < 0 || slot >= g->nslots || n != g->staged[slot]) return CK_EINVAL;
+    if (!slot_ok(g, slot) || n != g->staged[slot]) return CK_EINVAL;
     if (n == 0) return CK_OK;
-    ck_handle *h = g->h;
-    CK_HIP(hipSetDevice(h->device));
-    CK_HIP(hipStreamWaitEvent(h->stream, g->ready[slot], 0));
-    const int rc = ck_detect_frames(h, {g->dev[slot], h->frame_stride, h->frame_pitch}, n, dets, cap, counts, status);
+    ck_dev_image img;
+    int rc = await_slot(g, slot, &img);
+    if (rc == CK_OK) rc = ck_detect_frames(g->h, img, n, dets, cap, counts, status);
     if (rc == CK_OK) g->pending[slot] = false; // (the results are on the host: the stream, and the event it waited for, are done)
     return rc;
 }
 
 extern "C" int ck_process_ingested(ck_ingest_t *g, int32_t slot, int32_t n, const ck_process_params_t *pp, const double *gyro,
                                    const uint8_t *has_gyro, ck_vision_measurement_t *out, int32_t *valid) {
-    if (!g || slot < 0 || slot >= g->nslots || n != g->staged[slot]) return CK_EINVAL;
+    if (!slot_ok(g, slot) || n != g->staged[slot]) return CK_EINVAL;
     if (n == 0) return CK_OK;
-    ck_handle *h = g->h;
-    CK_HIP(hipSetDevice(h->device));
-    CK_HIP(hipStreamWaitEvent(h->stream, g->ready[slot], 0));
-    const int rc = ck_process_frames(h, {g->dev[slot], h->frame_stride, h->frame_pitch}, n, pp, gyro, has_gyro, out, valid);
+    ck_dev_image img;
+    int rc = await_slot(g, slot, &img);
+    if (rc == CK_OK) rc = ck_process_frames(g->h, img, n, pp, gyro, has_gyro, out, valid);
     if (rc == CK_OK) g->pending[slot] = false;
     return rc;
 }
@@ -211,9 +212,8 @@ extern "C" int ck_process_ingested(ck_ingest_t *g, int32_t slot, int32_t n, cons
 // Exposure metering (ck_exposure.hip) of a submitted slot's frames; the slot stays as it is, so ck_detect_ingested may follow.
 extern "C" int ck_exposure_stats_ingested(ck_ingest_t *g, int32_t slot, const int32_t *frames, int32_t n, const ck_exposure_params_t *p,
                                           const ck_rect_t *roi, ck_exposure_stats_t *out) {
-    if (!g || slot < 0 || slot >= g->nslots) return CK_EINVAL;
-    ck_handle *h = g->h;
-    CK_HIP(hipSetDevice(h->device));
-    if (g->staged[slot] > 0) CK_HIP(hipStreamWaitEvent(h->stream, g->ready[slot], 0));
-    return ck_exposure_run(h, {g->dev[slot], h->frame_stride, h->frame_pitch}, g->staged[slot], frames, n, p, roi, out);
+    if (!slot_ok(g, slot)) return CK_EINVAL;
+    ck_dev_image img;
+    const int rc = await_slot(g, slot, &img);
+    return rc != CK_OK ? rc : ck_exposure_run(g->h, img, g->staged[slot], frames, n, p, roi, out);
 }

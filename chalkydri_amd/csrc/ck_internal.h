@@ -263,6 +263,23 @@ static inline ck_dev_image ck_qframes_image(const ck_handle *h) {
 static inline ck_dev_image ck_quad_image(const ck_handle *h, const ck_dev_image &in) { return ck_quad_separate(h) ? ck_qframes_image(h) : in; }
 static inline ck_dev_image ck_refine_image(const ck_handle *h, const ck_dev_image &in) { return ck_refine_reads_quad(h) ? ck_qframes_image(h) : in; }
 
+// Frames arrive turned by the camera's mounting (CK_ORIENT_*): the handle's w x h is the ORIENTED frame, its source is h x w for
+// the quarter turns.  The one range check and the one source geometry of the JPEG and raw-format paths.
+static inline bool ck_orientation_ok(int o) { return o >= CK_ORIENT_NONE && o <= CK_ORIENT_COUNTERCLOCKWISE; }
+static inline void ck_source_size(int w, int h, int orientation, int *sw, int *sh) {
+    const bool quarter = orientation == CK_ORIENT_CLOCKWISE || orientation == CK_ORIENT_COUNTERCLOCKWISE;
+    *sw = quarter ? h : w;
+    *sh = quarter ? w : h;
+}
+// a caller's list of n frame indices (null: 0 .. n - 1): every entry is one of the n_avail frames at hand
+static inline bool ck_frame_list_ok(const int32_t *frames, int n, int n_avail) {
+    for (int i = 0; i < n; i++) {
+        const int f = frames ? frames[i] : i;
+        if (f < 0 || f >= n_avail) return false;
+    }
+    return true;
+}
+
 // Device allocation of the handle's buffers.  CK_POISON=1 (tests) fills every buffer with 0xA5 bytes, so that a kernel which
 // reads an entry nobody wrote in this call — what an undersized capacity once made of the cluster and run tables — meets the
 // same garbage on every run instead of whatever the allocator happens to hand back.  CK_POISON=2 also lists the buffers.
@@ -312,10 +329,8 @@ int ck_launch_prefilter(ck_handle *h, const ck_dev_image &img, int n);
 int ck_bufs_create(ck_handle *h);
 int ck_buf_alloc(ck_handle *h, const void *member);
 void ck_bufs_free(ck_handle *h);
-void ck_jpeg_free(ck_handle *h); // ck_jpeg.hip: the JPEG workspace
-void ck_raw_free(ck_handle *h);  // ck_rawfmt.hip: the raw-format staging
-void ck_preview_free(ck_handle *h); // ck_preview.hip: the preview encoder's workspace
-void ck_exposure_free(ck_handle *h); // ck_exposure.hip: the exposure meter's workspace
+// the staged luma of frames [0, n) into a packed host buffer [n][h][w], enqueued on the handle's stream (ck_api.hip)
+int ck_read_staged_luma(ck_handle *h, int n, uint8_t *luma_out);
 int ck_stage_device_frames(ck_handle *h, const uint8_t *d_frames, int n, int stride, int64_t frame_pitch, ck_dev_image *use);
 int ck_run_threshold_segment(ck_handle *h, const ck_dev_image &img, int n);
 // gradient clusters from thresh/labels/csize of frames [0,n)

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ck_grow.h"
+
 constexpr int CK_JPEG_SUB_BITS = 512;       // bits of scan one lane decodes speculatively (a subsequence)
 constexpr int CK_JPEG_FRAME_THREADS = 1024; // workgroup of k_jpeg_frame (one per frame)
 
@@ -55,18 +57,16 @@ struct ck_jpeg_desc {
 // Device workspace of a JPEG decode in flight: the handle's (ck_handle::jpeg, grown on demand) and one per slot of a JPEG ingest
 // ring (sized once by ck_ingest_create_jpeg), ck_jpeg.hip.
 struct ck_jpeg_ws {
-    uint8_t *h_stage; size_t stage_cap;     // pinned host staging: descriptors | Huffman tables | quant tables | payloads
-    uint8_t *d_in; size_t in_cap;           // its device copy
-    uint8_t *d_compact; size_t compact_cap; // unstuffed scans, at the payloads' offsets
-    uint32_t *d_int; size_t int_cap;        // interval starts
-    ck_jpeg_sub *d_sub; size_t sub_cap;     // subsequence records
-    int16_t *d_coef; size_t coef_cap;       // Y coefficients [frame][block][64], natural order
-    uint32_t *d_status;                     // [max_batch] final per-frame status
-    uint32_t *h_status;                     // pinned [max_batch]
+    ck_pinned_buf<uint8_t> h_stage;  // pinned host staging: descriptors | Huffman tables | quant tables | payloads
+    ck_dev_buf<uint8_t> d_in;        // its device copy
+    ck_dev_buf<uint8_t> d_compact;   // unstuffed scans, at the payloads' offsets
+    ck_dev_buf<uint32_t> d_int;      // interval starts
+    ck_dev_buf<ck_jpeg_sub> d_sub;   // subsequence records
+    ck_dev_buf<int16_t> d_coef;      // Y coefficients [frame][block][64], natural order
+    ck_dev_buf<uint32_t> d_status;   // [max_batch] final per-frame status
+    ck_pinned_buf<uint32_t> h_status; // pinned [max_batch]
 };
 
-struct ck_handle;
-struct ck_dev_image;
 // k_jpeg.hip: the per-frame decode and the IDCT of n described frames on stream s, with workspace J, into the frames `dst`
 // (statuses in J.d_status).  The streams are sw x sh; dst holds them turned by `orientation` (CK_ORIENT_*).
 int ck_launch_jpeg(const ck_jpeg_ws &J, hipStream_t s, int n, const ck_jpeg_desc *d_desc, const ck_jpeg_huff *d_huff, const int32_t *d_qt,

@@ -9,36 +9,9 @@
 
 #include "ck_internal.h"
 #include "ck_jpeg.h"
+#include "ck_jpeg_tables.h"
 
 namespace {
-
-const uint8_t kNatural[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                              41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                              30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
-// ITU-T T.81 Annex K.3: the tables a stream without DHT relies on (libjpeg's std_huff_tables), by [class][slot 0 / 1]
-const uint8_t kStdBits[2][2][17] = {
-    {{0, 0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, {0, 0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}},
-    {{0, 0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d}, {0, 0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77}}};
-const uint8_t kStdDcVals[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
-const uint8_t kStdAcLum[162] = {
-    0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81,
-    0x91, 0xa1, 0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18,
-    0x19, 0x1a, 0x25, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48,
-    0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75,
-    0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99,
-    0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3,
-    0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5,
-    0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa};
-const uint8_t kStdAcChr[162] = {
-    0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08,
-    0x14, 0x42, 0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25,
-    0xf1, 0x17, 0x18, 0x19, 0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47,
-    0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74,
-    0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97,
-    0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba,
-    0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe2, 0xe3, 0xe4,
-    0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa};
 
 struct HuffSpec {
     bool present = false;
@@ -75,12 +48,14 @@ bool huff_ok(const HuffSpec &t, bool dc) {
     return true;
 }
 
+// ITU-T T.81 Annex K.3: the tables a stream without DHT relies on, by class and slot 0 / 1
 HuffSpec std_table(int cls, int slot) {
+    const ck_jpeg_std_huff &k = kStdHuff[cls][slot];
     HuffSpec t;
     t.present = true;
-    memcpy(t.bits, kStdBits[cls][slot], 17);
-    if (cls == 0) { memcpy(t.vals, kStdDcVals, 12); t.nvals = 12; }
-    else { memcpy(t.vals, slot ? kStdAcChr : kStdAcLum, 162); t.nvals = 162; }
+    memcpy(t.bits + 1, k.bits, 16);
+    memcpy(t.vals, k.vals, (size_t)k.n);
+    t.nvals = k.n;
     return t;
 }
 
@@ -217,32 +192,6 @@ void derive(const HuffSpec &t, ck_jpeg_huff &o) {
 
 size_t al16(size_t v) { return (v + 15) & ~(size_t)15; }
 
-template <typename T>
-int grow_dev(T **p, size_t *cap, size_t need, bool exact = false) {
-    if (need <= *cap) return CK_OK;
-    (void)ck_free_dev(*p);
-    *p = nullptr; *cap = 0;
-    const size_t want = exact ? need : need + need / 4;
-    CK_HIP_ALLOC(ck_malloc_dev(p, want));
-    *cap = want;
-    return CK_OK;
-}
-
-int grow_host(uint8_t **p, size_t *cap, size_t need, bool exact = false) {
-    if (need <= *cap) return CK_OK;
-    if (*p) (void)hipHostFree(*p);
-    *p = nullptr; *cap = 0;
-    const size_t want = exact ? need : need + need / 4;
-    hipError_t e = hipHostMalloc(reinterpret_cast<void **>(p), want, hipHostMallocDefault);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        *p = nullptr;
-        return CK_ENOMEM;
-    }
-    *cap = want;
-    return CK_OK;
-}
-
 // The Huffman and quantisation tables of a batch, each distinct one once, in the device layout
 struct Tables {
     std::vector<ck_jpeg_huff> tabs;
@@ -332,66 +281,44 @@ void stage_scan(uint8_t *dst, const uint8_t *scan, uint32_t raw_len) {
 
 // the status array of a workspace (fixed size) and the buffers whose size follows the streams
 int ws_status(ck_jpeg_ws &J, int max_batch) {
-    if (hipHostMalloc(reinterpret_cast<void **>(&J.h_status), sizeof(uint32_t) * (size_t)max_batch, hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        J.h_status = nullptr;
-        return CK_ENOMEM;
-    }
-    size_t cap = 0;
-    return grow_dev(&J.d_status, &cap, sizeof(uint32_t) * (size_t)max_batch);
+    const int rc = J.h_status.reserve(sizeof(uint32_t) * (size_t)max_batch, true);
+    return rc != CK_OK ? rc : J.d_status.reserve(sizeof(uint32_t) * (size_t)max_batch);
 }
 // (exact: a ring's workspace never grows, so it gets no headroom)
 int ws_reserve(ck_jpeg_ws &J, size_t stage_bytes, size_t raw_bytes, size_t n_int, size_t n_sub, size_t coef_blocks_total, bool exact = false) {
-    int rc = grow_host(&J.h_stage, &J.stage_cap, stage_bytes, exact);
-    if (rc == CK_OK) rc = grow_dev(&J.d_in, &J.in_cap, stage_bytes, exact);
-    if (rc == CK_OK) rc = grow_dev(&J.d_compact, &J.compact_cap, raw_bytes ? raw_bytes : 16, exact);
-    if (rc == CK_OK) rc = grow_dev(&J.d_int, &J.int_cap, sizeof(uint32_t) * (n_int ? n_int : 1), exact);
-    if (rc == CK_OK) rc = grow_dev(&J.d_sub, &J.sub_cap, sizeof(ck_jpeg_sub) * (n_sub ? n_sub : 1), exact);
-    if (rc == CK_OK) rc = grow_dev(&J.d_coef, &J.coef_cap, sizeof(int16_t) * 64 * coef_blocks_total, exact);
+    int rc = J.h_stage.reserve(stage_bytes, exact);
+    if (rc == CK_OK) rc = J.d_in.reserve(stage_bytes, exact);
+    if (rc == CK_OK) rc = J.d_compact.reserve(raw_bytes ? raw_bytes : 16, exact);
+    if (rc == CK_OK) rc = J.d_int.reserve(sizeof(uint32_t) * (n_int ? n_int : 1), exact);
+    if (rc == CK_OK) rc = J.d_sub.reserve(sizeof(ck_jpeg_sub) * (n_sub ? n_sub : 1), exact);
+    if (rc == CK_OK) rc = J.d_coef.reserve(sizeof(int16_t) * 64 * coef_blocks_total, exact);
     return rc;
-}
-void ws_release(ck_jpeg_ws &J) {
-    if (J.h_stage) (void)hipHostFree(J.h_stage);
-    if (J.h_status) (void)hipHostFree(J.h_status);
-    (void)ck_free_dev(J.d_in); (void)ck_free_dev(J.d_compact); (void)ck_free_dev(J.d_int); (void)ck_free_dev(J.d_sub);
-    (void)ck_free_dev(J.d_coef); (void)ck_free_dev(J.d_status);
-    memset(&J, 0, sizeof J);
 }
 
 // decode + IDCT of the n frames whose staging (layout L, payloads at off_raw) is on its way to J.d_in on stream s, into dst turned by
 // `orientation`, and the statuses on their way back to J.h_status: everything enqueued, nothing awaited
 int enqueue_decode(const ck_jpeg_ws &J, hipStream_t s, int n, const Layout &L, size_t off_raw, const ck_dev_image &dst, int sw, int sh,
                    int orientation) {
-    const int rc = ck_launch_jpeg(J, s, n, reinterpret_cast<const ck_jpeg_desc *>(J.d_in), reinterpret_cast<const ck_jpeg_huff *>(J.d_in + L.off_tab),
+    const int rc = ck_launch_jpeg(J, s, n, reinterpret_cast<const ck_jpeg_desc *>(J.d_in.p), reinterpret_cast<const ck_jpeg_huff *>(J.d_in + L.off_tab),
                                   reinterpret_cast<const int32_t *>(J.d_in + L.off_qt), J.d_in + off_raw, coef_blocks(sw, sh), dst, sw, sh, orientation);
     if (rc != CK_OK) return rc;
     CK_HIP(hipMemcpyAsync(J.h_status, J.d_status, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
     return CK_OK;
 }
 
-void source_size(const ck_handle *h, int orientation, int *sw, int *sh) {
-    const bool quarter = orientation == CK_ORIENT_CLOCKWISE || orientation == CK_ORIENT_COUNTERCLOCKWISE;
-    *sw = quarter ? h->h : h->w;
-    *sh = quarter ? h->w : h->h;
-}
-
 // ck_upload_jpeg[_oriented]: the handle's workspace, the handle's stream, the staged frames, and the two synchronisations
 int jpeg_run(ck_handle *h, const ck_jpeg_frame_t *frames, int n, int orientation, uint32_t *jpeg_status) {
     CK_HIP(hipSetDevice(h->device));
-    if (!h->jpeg) {
-        h->jpeg = new (std::nothrow) ck_jpeg_ws();
-        if (!h->jpeg) return CK_ENOMEM;
-        memset(h->jpeg, 0, sizeof *h->jpeg);
-        const int rc = ws_status(*h->jpeg, h->cfg.max_batch);
-        if (rc != CK_OK) { ck_jpeg_free(h); return rc; }
-    }
+    if (!ck_workspace(h->jpeg)) return CK_ENOMEM;
     ck_jpeg_ws &J = *h->jpeg;
+    int rc = ws_status(J, h->cfg.max_batch); // (a no-op once the first call has allocated the pair)
+    if (rc != CK_OK) return rc;
     if (n == 0) {
         h->n_staged = 0;
         return CK_OK;
     }
     int sw, sh;
-    source_size(h, orientation, &sw, &sh);
+    ck_source_size(h->w, h->h, orientation, &sw, &sh);
     // ---- parse + deduplicate --------------------------------------------------------------------------------------------------
     std::vector<Parsed> P((size_t)n);
     std::vector<ck_jpeg_desc> D((size_t)n);
@@ -412,7 +339,7 @@ int jpeg_run(ck_handle *h, const ck_jpeg_frame_t *frames, int n, int orientation
     // ---- stage: descriptors | tables | quant tables | payloads -----------------------------------------------------------------
     const Layout L = layout(n, T);
     const size_t total = L.off_raw + raw_total;
-    int rc = ws_reserve(J, total, raw_total, int_total, sub_total, coef_blocks(sw, sh) * (size_t)n);
+    rc = ws_reserve(J, total, raw_total, int_total, sub_total, coef_blocks(sw, sh) * (size_t)n);
     if (rc != CK_OK) return rc;
     CK_HIP(hipStreamSynchronize(h->stream)); // (the staging buffer may still feed an earlier call's copy)
     uint8_t *S = J.h_stage;
@@ -429,7 +356,7 @@ int jpeg_run(ck_handle *h, const ck_jpeg_frame_t *frames, int n, int orientation
 }
 
 int check_frames(const ck_handle *h, const ck_jpeg_frame_t *frames, int32_t n, int32_t orientation) {
-    if (!h || !frames || n < 0 || orientation < CK_ORIENT_NONE || orientation > CK_ORIENT_COUNTERCLOCKWISE) return CK_EINVAL;
+    if (!h || !frames || n < 0 || !ck_orientation_ok(orientation)) return CK_EINVAL;
     if (n > h->cfg.max_batch) return CK_ECAPACITY;
     for (int i = 0; i < n; i++)
         if (!frames[i].data || frames[i].size < 4) return CK_EINVAL;
@@ -437,13 +364,6 @@ int check_frames(const ck_handle *h, const ck_jpeg_frame_t *frames, int32_t n, i
 }
 
 } // namespace
-
-void ck_jpeg_free(ck_handle *h) {
-    if (!h || !h->jpeg) return;
-    ws_release(*h->jpeg);
-    delete h->jpeg;
-    h->jpeg = nullptr;
-}
 
 extern "C" int ck_jpeg_info(const uint8_t *data, int64_t size, ck_jpeg_info_t *out) {
     if (!data || !out) return CK_EINVAL;
@@ -470,8 +390,8 @@ extern "C" int ck_jpeg_luma_batch_oriented(ck_handle_t *h, const ck_jpeg_frame_t
     if (rc != CK_OK) return rc;
     rc = jpeg_run(h, frames, n, orientation, jpeg_status);
     if (rc != CK_OK || n == 0) return rc;
-    CK_HIP(hipMemcpy2DAsync(luma_out, (size_t)h->w, h->d_frames, (size_t)h->frame_stride, (size_t)h->w, (size_t)h->h * n,
-                            hipMemcpyDeviceToHost, h->stream));
+    rc = ck_read_staged_luma(h, n, luma_out);
+    if (rc != CK_OK) return rc;
     CK_HIP(hipStreamSynchronize(h->stream));
     return CK_OK;
 }
@@ -500,17 +420,13 @@ struct ck_jpeg_slots {
     } slot[8];
 };
 
-void ck_jpeg_slots_free(ck_jpeg_slots *q) {
-    if (!q) return;
-    for (int s = 0; s < q->nslots; s++) ws_release(q->slot[s].J);
-    delete q;
-}
+void ck_jpeg_slots_free(ck_jpeg_slots *q) { delete q; }
 
 int ck_jpeg_slots_create(ck_handle *h, int n_slots, int orientation, int64_t max_frame_bytes, ck_jpeg_slots **out) {
     ck_jpeg_slots *q = new (std::nothrow) ck_jpeg_slots();
     if (!q) return CK_ENOMEM;
     q->h = h; q->nslots = n_slots; q->orientation = orientation;
-    source_size(h, orientation, &q->sw, &q->sh);
+    ck_source_size(h->w, h->h, orientation, &q->sw, &q->sh);
     q->max_frame_bytes = max_frame_bytes ? max_frame_bytes : (int64_t)q->sw * q->sh;
     const size_t nb = (size_t)h->cfg.max_batch;
     q->frame_cap = al16((size_t)q->max_frame_bytes + 4);
@@ -523,7 +439,6 @@ int ck_jpeg_slots_create(ck_handle *h, int n_slots, int orientation, int64_t max
     try {
         for (int s = 0; s < n_slots; s++) {
             ck_jpeg_slots::Slot &S = q->slot[s];
-            memset(&S.J, 0, sizeof S.J);
             S.P.resize(nb); S.rc.assign(nb, CK_EINVAL); S.size.assign(nb, 0); S.written.assign(nb, 0); S.D.resize(nb);
         }
     } catch (const std::bad_alloc &) { rc = CK_ENOMEM; }

@@ -2,7 +2,7 @@
 #ifndef CK_PREVIEW_H
 #define CK_PREVIEW_H
 
-#include "ck_internal.h"
+#include "ck_grow.h"
 
 #define CK_PV_BLOCK_BYTES 264 /* a baseline block before stuffing: 68 symbols of at most 31 bits */
 #define CK_PV_CHUNK 64        /* bytes of the bit buffer one lane of the stuffing passes owns */
@@ -27,18 +27,18 @@ struct ck_pv_tables {
 
 // Workspace, allocated by the first preview call and grown on demand (ck_create allocates none of it)
 struct ck_preview_ws {
-    int32_t *d_frames; size_t frames_cap;   // [n] staged-frame index of every entry
-    uint32_t *d_mask; size_t mask_cap;      // [n][mask_words] overlay bit image
-    int16_t *d_coef; size_t coef_cap;       // [n][nblk][64] quantised coefficients, zig-zag order
-    int16_t *d_dc; size_t dc_cap;           // [n][nblk] quantised DC
-    uint32_t *d_len; size_t len_cap;        // [n][nblk] AC bits of a block, then the block's first bit inside its interval
-    uint32_t *d_istart; size_t istart_cap;  // [n][nint + 1] bytes per interval, then the interval's first byte in the frame's bit buffer
-    uint32_t *d_bits; size_t bits_cap;      // [n][bit_words] the entropy-coded bits before stuffing, MSB first in every word
-    uint32_t *d_cpre; size_t cpre_cap;      // [n][chunk_cap] 0xFF bytes in front of every chunk
-    int64_t *d_sizes; size_t sizes_cap;     // [3][n] file size | offset of the file in the output | status
-    uint8_t *d_out; size_t out_cap;         // compact output staging of a call with a host `out`; ck_preview_luma's pixels
-    int64_t *h_sizes; size_t h_sizes_cap;   // pinned mirror of d_sizes
-    uint8_t *h_out; size_t h_out_cap;       // pinned staging of the files
+    ck_dev_buf<int32_t> d_frames;    // [n] staged-frame index of every entry
+    ck_dev_buf<uint32_t> d_mask;     // [n][mask_words] overlay bit image
+    ck_dev_buf<int16_t> d_coef;      // [n][nblk][64] quantised coefficients, zig-zag order
+    ck_dev_buf<int16_t> d_dc;        // [n][nblk] quantised DC
+    ck_dev_buf<uint32_t> d_len;      // [n][nblk] AC bits of a block, then the block's first bit inside its interval
+    ck_dev_buf<uint32_t> d_istart;   // [n][nint + 1] bytes per interval, then the interval's first byte in the frame's bit buffer
+    ck_dev_buf<uint32_t> d_bits;     // [n][bit_words] the entropy-coded bits before stuffing, MSB first in every word
+    ck_dev_buf<uint32_t> d_cpre;     // [n][chunk_cap] 0xFF bytes in front of every chunk
+    ck_dev_buf<int64_t> d_sizes;     // [3][n] file size | offset of the file in the output | status
+    ck_dev_buf<uint8_t> d_out;       // compact output staging of a call with a host `out`; ck_preview_luma's pixels
+    ck_pinned_buf<int64_t> h_sizes;  // pinned mirror of d_sizes
+    ck_pinned_buf<uint8_t> h_out;    // pinned staging of the files
 };
 
 // k_jpegenc.hip: the stages, enqueued on the handle's stream, in two halves.  d_out == nullptr: scale .. stuffing scan, after which
@@ -47,6 +47,5 @@ struct ck_preview_ws {
 int ck_launch_preview_encode(ck_handle *h, const ck_pv_geom &g, const ck_pv_tables &t, int n, uint8_t *d_out, int64_t cap, bool compact);
 int ck_launch_preview_mask(ck_handle *h, const ck_pv_geom &g, int n);
 int ck_launch_preview_luma(ck_handle *h, const ck_pv_geom &g, int n, uint8_t *d_out);
-void ck_preview_free(ck_handle *h);
 
 #endif

@@ -6,7 +6,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include "chalkydri_hip.h"
+#include "ck_grow.h"
 
 // 16-bit fixed-point weights of L(R,G,B) (libjpeg's jccolor.c grey conversion); they sum to 65536
 #define CK_LUMA_R 19595u
@@ -25,6 +25,12 @@ static inline bool ck_raw_same_family(const ck_raw_class &a, const ck_raw_class 
 // CK_OK / CK_EUNSUPPORTED (a fourcc outside the table of §4d)
 int ck_raw_classify(uint32_t fourcc, ck_raw_class *out);
 
+// The source of an oriented w x h frame of format `fmt`: its class, its size, the bytes a row holds at least, and the layout every
+// staging of such frames uses (the host entry points' and a raw ingest ring's): rows at the minimum stride rounded up to 16.
+// CK_EINVAL (null fmt, w or h < 1, orientation out of range) / CK_EUNSUPPORTED (fourcc), in ck_raw_layout's order.
+struct ck_raw_geom { ck_raw_class cls; int sw, sh, min_stride, stride16; size_t pitch16; };
+int ck_raw_geometry(const ck_raw_format_t *fmt, int w, int h, ck_raw_geom *out);
+
 // The source side of one conversion: n frames of sw x sh pixels in device memory, row y of frame f at p + f * pitch + y * stride
 struct ck_raw_src { const uint8_t *p; int stride; size_t pitch; int sw, sh; };
 
@@ -34,9 +40,8 @@ int ck_launch_rawfmt(ck_handle *h, hipStream_t st, const ck_raw_src &src, const 
 
 // Staging of the host-frame entry points (ck_handle::raw): allocated by the first raw call, grown on demand (ck_rawfmt.hip)
 struct ck_raw_ws {
-    uint8_t *h_stage; size_t h_cap; // pinned host: [n][sh][stride16] raw rows, stride16 = the minimum stride rounded up to 16
-    uint8_t *d_stage; size_t d_cap; // its device copy; it ends with the last row's last byte the kernel may read
+    ck_pinned_buf<uint8_t> h_stage; // pinned host: [n][sh][stride16] raw rows
+    ck_dev_buf<uint8_t> d_stage;    // its device copy; it ends with the last row's last byte the kernel may read
 };
-void ck_raw_free(ck_handle *h);
 
 #endif

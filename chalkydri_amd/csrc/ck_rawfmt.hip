@@ -3,8 +3,6 @@
 // caller's stride and base were), copies it with one asynchronous copy and runs k_rawfmt.hip into the staged frames.
 #include <string.h>
 
-#include <new>
-
 #include "ck_internal.h"
 #include "ck_rawfmt.h"
 
@@ -14,53 +12,9 @@ constexpr uint32_t cc4(const char (&s)[5]) {
     return (uint32_t)(uint8_t)s[0] | ((uint32_t)(uint8_t)s[1] << 8) | ((uint32_t)(uint8_t)s[2] << 16) | ((uint32_t)(uint8_t)s[3] << 24);
 }
 
-struct layout { ck_raw_class cls; int sw, sh, min_stride; };
-
-int raw_layout(const ck_raw_format_t *fmt, int w, int h, layout *L) {
-    if (!fmt || w < 1 || h < 1) return CK_EINVAL;
-    const int rc = ck_raw_classify(fmt->fourcc, &L->cls);
-    if (rc != CK_OK) return rc;
-    if (fmt->orientation < CK_ORIENT_NONE || fmt->orientation > CK_ORIENT_COUNTERCLOCKWISE) return CK_EINVAL;
-    const bool quarter = fmt->orientation == CK_ORIENT_CLOCKWISE || fmt->orientation == CK_ORIENT_COUNTERCLOCKWISE;
-    L->sw = quarter ? h : w;
-    L->sh = quarter ? w : h;
-    L->min_stride = L->cls.bpp == 2 ? 4 * ((L->sw + 1) / 2) : L->cls.bpp * L->sw;
-    return CK_OK;
-}
-
-int stride16(const layout &L) { return (L.min_stride + 15) / 16 * 16; }
-
-// the handle's raw staging holds at least `bytes` (exactly that after a growth: under CK_POISON=3 the device buffer then ends
-// where the kernel's last permitted read ends)
-int grow_stage(ck_handle *h, size_t bytes) {
-    if (!h->raw) {
-        h->raw = new (std::nothrow) ck_raw_ws();
-        if (!h->raw) return CK_ENOMEM;
-        memset(h->raw, 0, sizeof *h->raw);
-    }
-    ck_raw_ws &R = *h->raw;
-    if (bytes > R.h_cap) {
-        if (R.h_stage) (void)hipHostFree(R.h_stage);
-        R.h_stage = nullptr; R.h_cap = 0;
-        if (hipHostMalloc(reinterpret_cast<void **>(&R.h_stage), bytes, hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError();
-            R.h_stage = nullptr;
-            return CK_ENOMEM;
-        }
-        R.h_cap = bytes;
-    }
-    if (bytes > R.d_cap) {
-        (void)ck_free_dev(R.d_stage);
-        R.d_stage = nullptr; R.d_cap = 0;
-        CK_HIP_ALLOC(ck_malloc_dev(&R.d_stage, bytes));
-        R.d_cap = bytes;
-    }
-    return CK_OK;
-}
-
-int check_raw_imgs(const ck_handle *h, const ck_image_u8_t *imgs, int n, const ck_raw_format_t *fmt, layout *L) {
+int check_raw_imgs(const ck_handle *h, const ck_image_u8_t *imgs, int n, const ck_raw_format_t *fmt, ck_raw_geom *L) {
     if (!h) return CK_EINVAL;
-    const int rc = raw_layout(fmt, h->w, h->h, L);
+    const int rc = ck_raw_geometry(fmt, h->w, h->h, L);
     if (rc != CK_OK) return rc;
     if (n < 0 || (n > 0 && !imgs)) return CK_EINVAL;
     if (n > h->cfg.max_batch) return CK_ECAPACITY;
@@ -70,13 +24,16 @@ int check_raw_imgs(const ck_handle *h, const ck_image_u8_t *imgs, int n, const c
 }
 
 // host frames -> staging -> device -> staged frames, enqueued on the handle's stream (the caller synchronises)
-int stage_and_convert(ck_handle *h, const ck_image_u8_t *imgs, int n, const ck_raw_format_t *fmt, const layout &L) {
+int stage_and_convert(ck_handle *h, const ck_image_u8_t *imgs, int n, const ck_raw_format_t *fmt, const ck_raw_geom &L) {
     CK_HIP(hipSetDevice(h->device));
     if (n == 0) { h->n_staged = 0; return CK_OK; }
-    const size_t st = (size_t)stride16(L), pitch = st * L.sh, bytes = pitch * n - st + L.min_stride;
-    int rc = grow_stage(h, bytes);
-    if (rc != CK_OK) return rc;
+    // exactly these bytes: under CK_POISON=3 the device buffer then ends where the kernel's last permitted read ends
+    const size_t st = (size_t)L.stride16, pitch = L.pitch16, bytes = pitch * n - st + L.min_stride;
+    if (!ck_workspace(h->raw)) return CK_ENOMEM;
     ck_raw_ws &R = *h->raw;
+    int rc = R.h_stage.reserve(bytes, true);
+    if (rc == CK_OK) rc = R.d_stage.reserve(bytes, true);
+    if (rc != CK_OK) return rc;
     for (int i = 0; i < n; i++) {
         uint8_t *dst = R.h_stage + (size_t)i * pitch;
         if ((size_t)imgs[i].stride == st) memcpy(dst, imgs[i].buf, pitch - st + L.min_stride);
@@ -107,19 +64,23 @@ int ck_raw_classify(uint32_t fourcc, ck_raw_class *out) {
     return CK_EUNSUPPORTED;
 }
 
-void ck_raw_free(ck_handle *h) {
-    if (!h || !h->raw) return;
-    if (h->raw->h_stage) (void)hipHostFree(h->raw->h_stage);
-    (void)ck_free_dev(h->raw->d_stage);
-    delete h->raw;
-    h->raw = nullptr;
+int ck_raw_geometry(const ck_raw_format_t *fmt, int w, int h, ck_raw_geom *L) {
+    if (!fmt || w < 1 || h < 1) return CK_EINVAL;
+    const int rc = ck_raw_classify(fmt->fourcc, &L->cls);
+    if (rc != CK_OK) return rc;
+    if (!ck_orientation_ok(fmt->orientation)) return CK_EINVAL;
+    ck_source_size(w, h, fmt->orientation, &L->sw, &L->sh);
+    L->min_stride = L->cls.bpp == 2 ? 4 * ((L->sw + 1) / 2) : L->cls.bpp * L->sw;
+    L->stride16 = (L->min_stride + 15) / 16 * 16;
+    L->pitch16 = (size_t)L->stride16 * L->sh;
+    return CK_OK;
 }
 
 extern "C" int ck_raw_layout(const ck_raw_format_t *fmt, int32_t width, int32_t height, int32_t *sw, int32_t *sh, int32_t *min_stride,
                              int64_t *min_bytes) {
     if (!sw || !sh || !min_stride || !min_bytes) return CK_EINVAL;
-    layout L;
-    const int rc = raw_layout(fmt, width, height, &L);
+    ck_raw_geom L;
+    const int rc = ck_raw_geometry(fmt, width, height, &L);
     if (rc != CK_OK) return rc;
     *sw = L.sw; *sh = L.sh; *min_stride = L.min_stride;
     *min_bytes = (int64_t)L.sh * L.min_stride;
@@ -127,7 +88,7 @@ extern "C" int ck_raw_layout(const ck_raw_format_t *fmt, int32_t width, int32_t 
 }
 
 extern "C" int ck_upload_raw(ck_handle_t *h, const ck_image_u8_t *imgs, int32_t n, const ck_raw_format_t *fmt) {
-    layout L;
+    ck_raw_geom L;
     int rc = check_raw_imgs(h, imgs, n, fmt, &L);
     if (rc != CK_OK) return rc;
     rc = stage_and_convert(h, imgs, n, fmt, L);
@@ -138,13 +99,13 @@ extern "C" int ck_upload_raw(ck_handle_t *h, const ck_image_u8_t *imgs, int32_t 
 
 extern "C" int ck_raw_luma_batch(ck_handle_t *h, const ck_image_u8_t *imgs, int32_t n, const ck_raw_format_t *fmt, uint8_t *luma_out) {
     if (!luma_out) return CK_EINVAL;
-    layout L;
+    ck_raw_geom L;
     int rc = check_raw_imgs(h, imgs, n, fmt, &L);
     if (rc != CK_OK) return rc;
     rc = stage_and_convert(h, imgs, n, fmt, L);
     if (rc != CK_OK) return rc;
-    if (n) CK_HIP(hipMemcpy2DAsync(luma_out, (size_t)h->w, h->d_frames, (size_t)h->frame_stride, (size_t)h->w, (size_t)h->h * n,
-                                   hipMemcpyDeviceToHost, h->stream));
+    rc = ck_read_staged_luma(h, n, luma_out);
+    if (rc != CK_OK) return rc;
     CK_HIP(hipStreamSynchronize(h->stream));
     return CK_OK;
 }
@@ -152,8 +113,8 @@ extern "C" int ck_raw_luma_batch(ck_handle_t *h, const ck_image_u8_t *imgs, int3
 extern "C" int ck_upload_raw_device(ck_handle_t *h, const uint8_t *d_raw, int32_t n, int32_t stride, int64_t frame_pitch,
                                     const ck_raw_format_t *fmt) {
     if (!h) return CK_EINVAL;
-    layout L;
-    int rc = raw_layout(fmt, h->w, h->h, &L);
+    ck_raw_geom L;
+    int rc = ck_raw_geometry(fmt, h->w, h->h, &L);
     if (rc != CK_OK) return rc;
     if (!d_raw || n < 0 || stride < L.min_stride || frame_pitch < (int64_t)stride * L.sh) return CK_EINVAL;
     if (n > h->cfg.max_batch) return CK_ECAPACITY;

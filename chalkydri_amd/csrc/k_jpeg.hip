@@ -4,6 +4,7 @@
 // Every read of the scan is bounded by the frame's own region, every coefficient write by its block's 64 entries.
 #include "ck_internal.h"
 #include "ck_jpeg.h"
+#include "ck_jpeg_tables.h"
 
 namespace {
 
@@ -11,9 +12,7 @@ constexpr int NT = CK_JPEG_FRAME_THREADS;
 constexpr int NW = NT / 64;
 constexpr uint32_t SUB = CK_JPEG_SUB_BITS;
 
-__constant__ uint8_t k_natural[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                      41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                      30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+__constant__ uint8_t k_natural[64] = CK_JPEG_NATURAL_ORDER;
 
 struct FrameLds {
     ck_jpeg_huff tab[3][2]; // by scan component: DC, AC

@@ -2,6 +2,7 @@
 // integer forward DCT and quantiser, Huffman coding with the Annex-K luminance tables, bit packing, byte stuffing and restart
 // markers.  Every stage is data-parallel over the blocks (or the bytes) of all frames of a call; nothing comes back to the host
 // between the stages.  The files equal libjpeg's byte for byte (tests/np_jpeg_enc.py restates it).
+#include "ck_jpeg_tables.h"
 #include "ck_preview.h"
 
 namespace {
@@ -9,31 +10,14 @@ namespace {
 constexpr int PV_NT = 256;
 
 // zig-zag index -> natural index (ITU-T T.81 figure A.6)
-__device__ constexpr uint8_t kZZ[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                        41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                        30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
-// ITU-T T.81 Annex K.3, luminance: codes per length 1..16 and the symbols in code order
-struct HuffSpec { uint8_t bits[16]; uint8_t vals[162]; int n; };
-constexpr HuffSpec kDcSpec = {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11}, 12};
-constexpr HuffSpec kAcSpec = {
-    {0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d},
-    {0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81,
-     0x91, 0xa1, 0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18,
-     0x19, 0x1a, 0x25, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48,
-     0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75,
-     0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99,
-     0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3,
-     0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5,
-     0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa},
-    162};
+__device__ constexpr uint8_t kZZ[64] = CK_JPEG_NATURAL_ORDER;
 
 // the encoder's view of both tables: [symbol] = code | length << 16 (0 = the symbol has no code); DC at 0..15, AC at 16..271
 struct HuffEnc { uint32_t e[16 + 256]; };
 constexpr HuffEnc make_enc() {
     HuffEnc t{};
     for (int cls = 0; cls < 2; cls++) {
-        const HuffSpec &s = cls ? kAcSpec : kDcSpec;
+        const ck_jpeg_std_huff &s = kStdHuff[cls][0]; // Annex K.3, luminance
         uint32_t code = 0;
         int p = 0;
         for (int l = 1; l <= 16; l++) {

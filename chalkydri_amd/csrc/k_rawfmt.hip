@@ -154,8 +154,9 @@ int launch(hipStream_t st, const raw_args &a, int orientation, int n) {
 
 int ck_launch_rawfmt(ck_handle *h, hipStream_t st, const ck_raw_src &src, const ck_raw_class &cls, int orientation, uint8_t *dst, int n) {
     if (n <= 0) return CK_OK;
-    const bool quarter = orientation == CK_ORIENT_CLOCKWISE || orientation == CK_ORIENT_COUNTERCLOCKWISE;
-    if (src.sw != (quarter ? h->h : h->w) || src.sh != (quarter ? h->w : h->h) || n > 65535) return CK_EINVAL;
+    int sw, sh;
+    ck_source_size(h->w, h->h, orientation, &sw, &sh);
+    if (src.sw != sw || src.sh != sh || n > 65535) return CK_EINVAL;
     const raw_args a = {src.p, src.stride, src.pitch, src.sw, src.sh, dst, h->frame_stride, h->frame_pitch, h->w, h->h, cls.k[0], cls.k[1], cls.k[2]};
     switch (cls.bpp) {
     case 1: return launch<1>(st, a, orientation, n);
