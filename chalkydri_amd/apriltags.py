@@ -92,11 +92,13 @@ class AprilTags:
         """The exposure to set next, in exposure0's unit (None unless auto_exposure=True)."""
         return None if self._exposure is None else self._exposure.exposure
 
-    def preview(self, frames=None, n=None, overlay=True, **kw):
+    def preview(self, frames=None, n=None, overlay=True, color=False, **kw):
         """After process_batch: the driver-station JPEGs (bytes each) of the frames just processed — indices into the staged
         frames, or n for 0..n-1 — scaled and encoded on the device, the tags the call found outlined (overlay=True).  Keyword
-        arguments as AprilTagDetector.preview_jpeg (width=640, height=480, quality=50, restart_rows=0)."""
-        return self.detector.preview_jpeg(frames, n, overlay=overlay, **kw)
+        arguments as AprilTagDetector.preview_jpeg (width=640, height=480, quality=50, restart_rows=0).  color=True: the colour
+        files of the raw frames, after process_raw_batch of a packed colour format (AprilTagDetector.preview_jpeg_color)."""
+        call = self.detector.preview_jpeg_color if color else self.detector.preview_jpeg
+        return call(frames, n, overlay=overlay, **kw)
 
     def process_raw_batch(self, raw_frames, gyro=None):
         """The camera's frames as it hands them over ([rows][bytes] each, in the task's fourcc): converted to luma and turned by

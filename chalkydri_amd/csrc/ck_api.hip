@@ -146,6 +146,7 @@ extern "C" int ck_create(const ck_config_t *cfg, ck_handle_t **out) {
     h->cfg = *cfg;
     h->device = cfg->device;
     h->n_last_pose = -1;
+    h->n_raw_staged = -1;
     h->n_last_dets = -1;
     h->w = cfg->width; h->h = cfg->height; h->qw = qw; h->qh = qh;
     h->npix = (size_t)qw * qh;
@@ -210,7 +211,7 @@ extern "C" int ck_upload_frames(ck_handle_t *h, const ck_image_u8_t *imgs, int32
         CK_HIP(hipMemcpy2DAsync(h->d_frames + (size_t)i * h->frame_pitch, (size_t)h->frame_stride, imgs[i].buf, (size_t)imgs[i].stride,
                                 (size_t)h->w, (size_t)h->h, hipMemcpyHostToDevice, h->stream));
     CK_HIP(hipStreamSynchronize(h->stream));
-    h->n_staged = n;
+    ck_set_staged(h, n);
     return CK_OK;
 }
 
@@ -223,7 +224,7 @@ int ck_stage_device_frames(ck_handle *h, const uint8_t *d_frames, int n, int str
     for (int i = 0; i < n; i++)
         CK_HIP(hipMemcpy2DAsync(h->d_frames + (size_t)i * h->frame_pitch, (size_t)h->frame_stride, d_frames + (size_t)i * frame_pitch,
                                 (size_t)stride, (size_t)h->w, (size_t)h->h, hipMemcpyDeviceToDevice, h->stream));
-    h->n_staged = n;
+    ck_set_staged(h, n);
     *use = ck_staged_image(h);
     return CK_OK;
 }

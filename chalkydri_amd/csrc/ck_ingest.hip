@@ -12,6 +12,7 @@
 #include "ck_exposure.h"
 #include "ck_internal.h"
 #include "ck_jpeg.h"
+#include "ck_preview.h"
 #include "ck_rawfmt.h"
 
 struct ck_ingest {
@@ -216,4 +217,25 @@ extern "C" int ck_exposure_stats_ingested(ck_ingest_t *g, int32_t slot, const in
     ck_dev_image img;
     const int rc = await_slot(g, slot, &img);
     return rc != CK_OK ? rc : ck_exposure_run(g->h, img, g->staged[slot], frames, n, p, roi, out);
+}
+
+// Colour preview (ck_preview.hip) of a submitted slot of a raw ring, from the slot's raw twin: rawdev[slot] keeps the
+// frames of the last submit until the slot is submitted again.  The slot stays as it is.
+static int preview_color_ingested(ck_ingest_t *g, int32_t slot, const ck_preview_params_t *pp, const int32_t *frames, int32_t n,
+                                  uint8_t *out, bool files, int64_t cap_per_frame, int64_t *sizes, uint32_t *status) {
+    if (!slot_ok(g, slot)) return CK_EINVAL;
+    if (!g->raw) return CK_EUNSUPPORTED; // a plain ring holds luma, a JPEG ring compressed frames
+    ck_dev_image img;
+    const int rc = await_slot(g, slot, &img);
+    if (rc != CK_OK) return rc;
+    return ck_preview_color_run(g->h, pp, {g->rawdev[slot], g->geo.stride16, (int64_t)g->geo.pitch16, g->staged[slot], &g->fmt}, frames, n, out,
+                                files, cap_per_frame, sizes, status);
+}
+extern "C" int ck_preview_jpeg_color_ingested(ck_ingest_t *g, int32_t slot, const ck_preview_params_t *pp, const int32_t *frames, int32_t n,
+                                              uint8_t *out, int64_t cap_per_frame, int64_t *sizes, uint32_t *status) {
+    return preview_color_ingested(g, slot, pp, frames, n, out, true, cap_per_frame, sizes, status);
+}
+extern "C" int ck_preview_color_ingested(ck_ingest_t *g, int32_t slot, const ck_preview_params_t *pp, const int32_t *frames, int32_t n,
+                                         uint8_t *out) {
+    return preview_color_ingested(g, slot, pp, frames, n, out, false, 0, nullptr, nullptr);
 }

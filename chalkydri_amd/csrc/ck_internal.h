@@ -197,7 +197,11 @@ struct ck_handle {
     ck_stage_ms_t last_ms;
     ck_dev_family *d_fams;
     uint64_t *d_fam_codes; // every family's code table, one after the other (ck_dev_family::codes point into it)
-    int n_staged;        // frames currently staged in d_frames
+    int n_staged;        // frames currently staged in d_frames (assigned through ck_set_staged only)
+    // the raw frames the staged ones were converted from, while they still lie in raw->d_stage (ck_upload_raw, ck_raw_luma_batch):
+    // what ck_preview_jpeg_color reads.  n_raw_staged = -1: the frames were staged another way since
+    int n_raw_staged;
+    ck_raw_format_t raw_staged_fmt;
     int n_last_pose;     // records the last ck_process_* call left in ws.d_meas (what ck_gather_poses may send); -1: none yet
     int n_last_dets;     // frames whose detections the last ck_detect_* / ck_process_* call left in ws (what ck_last_tag_poses reads);
                          // -1: none yet, or a later call (ck_clusters_batch, ck_quads_batch, a failed pipeline) rewrote the workspace
@@ -270,6 +274,11 @@ static inline void ck_source_size(int w, int h, int orientation, int *sw, int *s
     const bool quarter = orientation == CK_ORIENT_CLOCKWISE || orientation == CK_ORIENT_COUNTERCLOCKWISE;
     *sw = quarter ? h : w;
     *sh = quarter ? w : h;
+}
+// The one place n_staged is assigned: frames staged any other way than from the raw staging take its colour twin with them
+static inline void ck_set_staged(ck_handle *h, int n) {
+    h->n_staged = n;
+    h->n_raw_staged = -1;
 }
 // a caller's list of n frame indices (null: 0 .. n - 1): every entry is one of the n_avail frames at hand
 static inline bool ck_frame_list_ok(const int32_t *frames, int n, int n_avail) {

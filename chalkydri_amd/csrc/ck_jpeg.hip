@@ -314,7 +314,7 @@ int jpeg_run(ck_handle *h, const ck_jpeg_frame_t *frames, int n, int orientation
     int rc = ws_status(J, h->cfg.max_batch); // (a no-op once the first call has allocated the pair)
     if (rc != CK_OK) return rc;
     if (n == 0) {
-        h->n_staged = 0;
+        ck_set_staged(h, 0);
         return CK_OK;
     }
     int sw, sh;
@@ -351,7 +351,7 @@ int jpeg_run(ck_handle *h, const ck_jpeg_frame_t *frames, int n, int orientation
     if (rc != CK_OK) return rc;
     CK_HIP(hipStreamSynchronize(h->stream));
     if (jpeg_status) memcpy(jpeg_status, J.h_status, sizeof(uint32_t) * (size_t)n);
-    h->n_staged = n;
+    ck_set_staged(h, n);
     return CK_OK;
 }
 

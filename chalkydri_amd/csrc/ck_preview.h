@@ -1,4 +1,5 @@
-// JPEG preview of the staged frames: what ck_preview.hip (host) and k_jpegenc.hip (kernels) share.
+// JPEG preview of the staged frames and its colour form from the raw frames (§4g): what ck_preview.hip (host) and
+// k_jpegenc.hip (kernels) share.
 #ifndef CK_PREVIEW_H
 #define CK_PREVIEW_H
 
@@ -6,13 +7,14 @@
 
 #define CK_PV_BLOCK_BYTES 264 /* a baseline block before stuffing: 68 symbols of at most 31 bits */
 #define CK_PV_CHUNK 64        /* bytes of the bit buffer one lane of the stuffing passes owns */
-#define CK_PV_HDR_MAX 336
+#define CK_PV_HDR_MAX 640     /* the three-component header is 623 bytes, 629 with DRI; the grey one 330 / 336 */
 
 // geometry of one call, the same for all its frames
 struct ck_pv_geom {
     int W, H, pw, ph;      // frame, preview
-    int bw, bh, nblk;      // 8 x 8 blocks of the preview
-    int R, nint;           // blocks per restart interval (nblk when there is none), intervals per frame
+    int nc;                // components: 1 (grey) or 3 (Y Cb Cr, 4:4:4: the blocks of an MCU follow each other)
+    int bw, bh, nblk;      // MCUs across and down; 8 x 8 blocks of the preview (nc * bw * bh, in scan order)
+    int R, nint;           // blocks per restart interval (nblk when there is none; a multiple of nc), intervals per frame
     int overlay;
     int mask_words;        // 32-bit words of a frame's overlay mask: ceil(pw * ph / 32)
     int bit_words;         // 32-bit words of a frame's bit buffer (a multiple of 4)
@@ -21,7 +23,7 @@ struct ck_pv_geom {
 };
 
 struct ck_pv_tables {
-    uint16_t qdiv[64];              // divisor of coefficient k (natural order): 8 * quantisation value
+    uint16_t qdiv[2][64];           // divisor of coefficient k (natural order): 8 * quantisation value; [0] Y, [1] Cb and Cr
     uint8_t hdr[CK_PV_HDR_MAX];     // the file's header, SOI .. SOS
 };
 
@@ -41,11 +43,32 @@ struct ck_preview_ws {
     ck_pinned_buf<uint8_t> h_out;    // pinned staging of the files
 };
 
+// The source of a colour preview (§4g): n_frames raw frames of a packed colour family in device memory, as ck_raw_src lays them
+// out, and what turns a pixel's bytes into component c of (Y, Cb, Cr).  Packed 4:2:2 (bpp 2): the one byte at off[c] inside the
+// pixel's 2 bytes (c = 0) or its pair's 4 bytes.  Packed colour (bpp 3 / 4): (sum_k wgt[c][k] * byte k + bias[c]) >> 16, libjpeg's
+// rgb_ycc_convert.  ovl: the overlay's triple, RGB (0, 255, 0) through the same formulas.
+struct ck_pv_csrc {
+    const uint8_t *p; int stride; size_t pitch;
+    int sw, sh, orientation, bpp;
+    int off[3];
+    int wgt[3][3], bias[3];
+    int ovl[3];
+};
+
 // k_jpegenc.hip: the stages, enqueued on the handle's stream, in two halves.  d_out == nullptr: scale .. stuffing scan, after which
 // d_sizes holds every file's size, its offset in the output (i * cap for a caller's device buffer, one file behind the other with
 // `compact`) and its status.  d_out != nullptr: the files themselves, file i at d_out + offset, never more than cap bytes each.
-int ck_launch_preview_encode(ck_handle *h, const ck_pv_geom &g, const ck_pv_tables &t, int n, uint8_t *d_out, int64_t cap, bool compact);
+// cs: the raw frames of a colour call (g.nc = 3), nullptr for the staged luma (g.nc = 1).
+int ck_launch_preview_encode(ck_handle *h, const ck_pv_geom &g, const ck_pv_tables &t, const ck_pv_csrc *cs, int n, uint8_t *d_out,
+                             int64_t cap, bool compact);
 int ck_launch_preview_mask(ck_handle *h, const ck_pv_geom &g, int n);
 int ck_launch_preview_luma(ck_handle *h, const ck_pv_geom &g, int n, uint8_t *d_out);
+int ck_launch_preview_color(ck_handle *h, const ck_pv_geom &g, const ck_pv_csrc &cs, int n, uint8_t *d_out); // [n][ph][pw][3]
+
+// ck_preview.hip: the one path of the colour entry points (the ring's are in ck_ingest.hip, where the ring is defined) on n_frames
+// raw frames of format *fmt at p.  files: the JPEG files (ck_preview_jpeg_color*), else the triples (ck_preview_color*).
+struct ck_pv_color_src { const uint8_t *p; int stride; int64_t pitch; int n_frames; const ck_raw_format_t *fmt; };
+int ck_preview_color_run(ck_handle *h, const ck_preview_params_t *pp, const ck_pv_color_src &src, const int32_t *frames, int32_t n,
+                         uint8_t *out, bool files, int64_t cap_per_frame, int64_t *sizes, uint32_t *status);
 
 #endif

@@ -1,18 +1,22 @@
-// JPEG preview of the staged frames: the host half.  Resolves the geometry (ck_preview_layout: the one place),
-// builds the quantisation divisors and the file header of a call, grows the workspace and enqueues the stages of k_jpegenc.hip on
-// the handle's stream; only the sizes and the bytes used come back to a host buffer.
+// JPEG preview of the staged frames and of the raw colour frames behind them (§4g): the host half.  Resolves the
+// geometry (ck_preview_layout: the one place), builds the quantisation divisors and the file header of a call, grows the workspace
+// and enqueues the stages of k_jpegenc.hip on the handle's stream; only the sizes and the bytes used come back to a host buffer.
 #include <string.h>
 
 #include "ck_jpeg_tables.h"
 #include "ck_preview.h"
+#include "ck_rawfmt.h"
 
 namespace {
 
-// SOI 2, APP0 18, DQT 69, SOF0 13, DHT DC 33, DHT AC 183, DRI 6 (only with a restart interval), SOS 10
-int header_len(int restart_rows) { return 2 + 18 + 69 + 13 + 33 + 183 + (restart_rows ? 6 : 0) + 10; }
+// SOI 2, APP0 18, DQT 69, SOF0 13, DHT DC 33, DHT AC 183, DRI 6 (only with a restart interval), SOS 10; with three components
+// a second DQT and DHT pair and 2 bytes per further component in SOF0 (3 each) and SOS (2 each)
+int header_len(int restart_rows, int nc) {
+    return 2 + 18 + 69 + 13 + 33 + 183 + (restart_rows ? 6 : 0) + 10 + (nc == 3 ? 69 + 33 + 183 + 2 * 3 + 2 * 2 : 0);
+}
 
-// geometry of a call; CK_EINVAL as ck_preview_layout documents it
-int resolve(const ck_preview_params_t *pp, int W, int H, ck_pv_geom *g) {
+// geometry of a call of nc components; CK_EINVAL as ck_preview_layout documents it
+int resolve(const ck_preview_params_t *pp, int W, int H, int nc, ck_pv_geom *g) {
     if (!pp || W < 1 || H < 1 || pp->width < 0 || pp->height < 0) return CK_EINVAL;
     if (pp->quality < 1 || pp->quality > 100 || pp->restart_rows < 0) return CK_EINVAL;
     if (pp->overlay != 0 && pp->overlay != 1) return CK_EINVAL;
@@ -21,16 +25,17 @@ int resolve(const ck_preview_params_t *pp, int W, int H, ck_pv_geom *g) {
     g->pw = pp->width == 0 || pp->width > W ? W : pp->width;
     g->ph = pp->height == 0 || pp->height > H ? H : pp->height;
     if (g->pw < 8 || g->ph < 8) return CK_EINVAL;
-    g->bw = (g->pw + 7) / 8; g->bh = (g->ph + 7) / 8; g->nblk = g->bw * g->bh;
+    g->nc = nc;
+    g->bw = (g->pw + 7) / 8; g->bh = (g->ph + 7) / 8; g->nblk = nc * g->bw * g->bh;
     if ((int64_t)pp->restart_rows * g->bw > 65535) return CK_EINVAL;
-    g->R = pp->restart_rows ? pp->restart_rows * g->bw : g->nblk;
+    g->R = pp->restart_rows ? nc * pp->restart_rows * g->bw : g->nblk;
     g->nint = (g->nblk + g->R - 1) / g->R;
     g->overlay = pp->overlay;
     g->mask_words = (int)(((int64_t)g->pw * g->ph + 31) / 32);
     const int64_t max_scan = (int64_t)g->nblk * CK_PV_BLOCK_BYTES + g->nint; // every interval rounds up to a whole byte
     g->chunk_cap = (int)((max_scan + CK_PV_CHUNK - 1) / CK_PV_CHUNK) + 1;
     g->bit_words = g->chunk_cap * (CK_PV_CHUNK / 4);
-    g->hdr_len = header_len(pp->restart_rows);
+    g->hdr_len = header_len(pp->restart_rows, nc);
     return CK_OK;
 }
 
@@ -38,43 +43,52 @@ int64_t max_file_bytes(const ck_pv_geom &g) { // every byte of the scan stuffed,
     return g.hdr_len + 2 * ((int64_t)g.nblk * CK_PV_BLOCK_BYTES + g.nint) + 2 * (int64_t)(g.nint - 1) + 2;
 }
 
-// libjpeg's jpeg_set_quality(quality, force_baseline) on the K.1 table; the header as libjpeg writes it for one component
+// libjpeg's jpeg_set_quality(quality, force_baseline) on the K.1 tables; the header as libjpeg writes it for g.nc components
 void make_tables(const ck_preview_params_t *pp, const ck_pv_geom &g, ck_pv_tables *t) {
     memset(t, 0, sizeof *t);
-    const int q = pp->quality, scale = q < 50 ? 5000 / q : 200 - 2 * q;
-    uint8_t qt[64];
-    for (int k = 0; k < 64; k++) {
-        int v = (kStdQ[k] * scale + 50) / 100;
-        v = v < 1 ? 1 : (v > 255 ? 255 : v);
-        qt[k] = (uint8_t)v;
-        t->qdiv[k] = (uint16_t)(8 * v);
-    }
+    const int q = pp->quality, scale = q < 50 ? 5000 / q : 200 - 2 * q, nc = g.nc, ntab = nc == 3 ? 2 : 1;
+    uint8_t qt[2][64];
+    for (int c = 0; c < 2; c++)
+        for (int k = 0; k < 64; k++) {
+            int v = ((c ? kStdQChroma[k] : kStdQ[k]) * scale + 50) / 100;
+            v = v < 1 ? 1 : (v > 255 ? 255 : v);
+            qt[c][k] = (uint8_t)v;
+            t->qdiv[c][k] = (uint16_t)(8 * v);
+        }
     uint8_t *p = t->hdr;
     auto seg = [&](int marker, int body) { *p++ = 0xFF; *p++ = (uint8_t)marker; *p++ = (uint8_t)((body + 2) >> 8); *p++ = (uint8_t)((body + 2) & 255); };
     *p++ = 0xFF; *p++ = 0xD8;
     seg(0xE0, 14);
     const uint8_t jfif[14] = {'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0}; // 1.01, no units, density 1 x 1, no thumbnail
     memcpy(p, jfif, 14); p += 14;
-    seg(0xDB, 65);
-    *p++ = 0; // 8-bit, table 0
-    for (int k = 0; k < 64; k++) *p++ = qt[kNatural[k]];
-    seg(0xC0, 9);
+    for (int c = 0; c < ntab; c++) {
+        seg(0xDB, 65);
+        *p++ = (uint8_t)c; // 8-bit, table c
+        for (int k = 0; k < 64; k++) *p++ = qt[c][kNatural[k]];
+    }
+    seg(0xC0, 6 + 3 * nc);
     *p++ = 8; *p++ = (uint8_t)(g.ph >> 8); *p++ = (uint8_t)(g.ph & 255); *p++ = (uint8_t)(g.pw >> 8); *p++ = (uint8_t)(g.pw & 255);
-    *p++ = 1; *p++ = 1; *p++ = 0x11; *p++ = 0;
-    seg(0xC4, 29);
-    *p++ = 0x00;
-    memcpy(p, kStdHuff[0][0].bits, 16); p += 16;
-    memcpy(p, kStdHuff[0][0].vals, 12); p += 12;
-    seg(0xC4, 179);
-    *p++ = 0x10;
-    memcpy(p, kStdHuff[1][0].bits, 16); p += 16;
-    memcpy(p, kStdHuff[1][0].vals, 162); p += 162;
+    *p++ = (uint8_t)nc;
+    for (int c = 0; c < nc; c++) { *p++ = (uint8_t)(c + 1); *p++ = 0x11; *p++ = c ? 1 : 0; } // id, 1 x 1, Tq
+    for (int c = 0; c < ntab; c++) {
+        seg(0xC4, 29);
+        *p++ = (uint8_t)c;
+        memcpy(p, kStdHuff[0][c].bits, 16); p += 16;
+        memcpy(p, kStdHuff[0][c].vals, 12); p += 12;
+        seg(0xC4, 179);
+        *p++ = (uint8_t)(0x10 | c);
+        memcpy(p, kStdHuff[1][c].bits, 16); p += 16;
+        memcpy(p, kStdHuff[1][c].vals, 162); p += 162;
+    }
     if (pp->restart_rows) {
         seg(0xDD, 2);
-        *p++ = (uint8_t)(g.R >> 8); *p++ = (uint8_t)(g.R & 255);
+        const int mcus = g.R / nc;
+        *p++ = (uint8_t)(mcus >> 8); *p++ = (uint8_t)(mcus & 255);
     }
-    seg(0xDA, 6);
-    *p++ = 1; *p++ = 1; *p++ = 0x00; *p++ = 0; *p++ = 63; *p++ = 0;
+    seg(0xDA, 4 + 2 * nc);
+    *p++ = (uint8_t)nc;
+    for (int c = 0; c < nc; c++) { *p++ = (uint8_t)(c + 1); *p++ = c ? 0x11 : 0x00; } // id, Td | Ta
+    *p++ = 0; *p++ = 63; *p++ = 0;
 }
 
 bool is_device_pointer(const void *p) {
@@ -87,20 +101,18 @@ bool is_device_pointer(const void *p) {
     return a.type == hipMemoryTypeDevice;
 }
 
-// what every entry point checks, in the contract's order; then the index list on the device.  *pg is the call's geometry.
-int begin(ck_handle *h, const ck_preview_params_t *pp, const int32_t *frames, int32_t n, const void *out, ck_pv_geom *pg) {
-    if (!h || !pp || !out || n < 0) return CK_EINVAL;
-    int rc = resolve(pp, h->w, h->h, pg);
-    if (rc != CK_OK) return rc;
+// what every entry point checks once its geometry *pg is resolved, in the contract's order; then the index list on the device.
+// n_avail: the frames an index may name (the staged ones, or the raw frames of a colour call)
+int begin(ck_handle *h, const int32_t *frames, int32_t n, int n_avail, const ck_pv_geom *pg) {
     if (n > h->cfg.max_batch) return CK_ECAPACITY;
     // the overlay reads the detections of the last detect / process call: ck_last_tag_poses' rule
     if (pg->overlay && h->n_last_dets < 1) return CK_EINVAL;
-    if (!ck_frame_list_ok(frames, n, h->n_staged) || (pg->overlay && !ck_frame_list_ok(frames, n, h->n_last_dets))) return CK_EINVAL;
+    if (!ck_frame_list_ok(frames, n, n_avail) || (pg->overlay && !ck_frame_list_ok(frames, n, h->n_last_dets))) return CK_EINVAL;
     if (n == 0) return CK_OK;
     CK_HIP(hipSetDevice(h->device));
     if (!ck_workspace(h->preview)) return CK_ENOMEM;
     ck_preview_ws &P = *h->preview;
-    rc = P.d_frames.reserve(sizeof(int32_t) * (size_t)n);
+    int rc = P.d_frames.reserve(sizeof(int32_t) * (size_t)n);
     if (rc == CK_OK) rc = P.h_sizes.reserve(sizeof(int64_t) * 4 * (size_t)n);
     if (rc == CK_OK && pg->overlay) rc = P.d_mask.reserve(sizeof(uint32_t) * (size_t)pg->mask_words * n);
     if (rc != CK_OK) return rc;
@@ -109,53 +121,21 @@ int begin(ck_handle *h, const ck_preview_params_t *pp, const int32_t *frames, in
     CK_HIP(hipMemcpyAsync(P.d_frames, idx, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
     return ck_launch_preview_mask(h, *pg, n);
 }
-
-} // namespace
-
-static_assert(sizeof(ck_preview_params_t) == 24, "ck_preview_params_t layout");
-
-extern "C" void ck_preview_params_default(ck_preview_params_t *pp) {
-    if (!pp) return;
-    memset(pp, 0, sizeof *pp);
-    pp->width = 640; pp->height = 480; // the caps filter of the reference's stream (mjpeg.rs:41-49)
-    pp->quality = 50;                  // turbojpeg::compress(.., 50, ..) (mjpeg.rs:116)
+// the grey entry points: the staged frames
+int begin(ck_handle *h, const ck_preview_params_t *pp, const int32_t *frames, int32_t n, const void *out, ck_pv_geom *pg) {
+    if (!h || !pp || !out || n < 0) return CK_EINVAL;
+    const int rc = resolve(pp, h->w, h->h, 1, pg);
+    return rc != CK_OK ? rc : begin(h, frames, n, h->n_staged, pg);
 }
 
-extern "C" int ck_preview_layout(const ck_preview_params_t *pp, int32_t W, int32_t H, int32_t *pw, int32_t *ph, int64_t *max_bytes) {
-    ck_pv_geom g;
-    const int rc = resolve(pp, W, H, &g);
-    if (rc != CK_OK) return rc;
-    if (pw) *pw = g.pw;
-    if (ph) *ph = g.ph;
-    if (max_bytes) *max_bytes = max_file_bytes(g);
-    return CK_OK;
-}
-
-extern "C" int ck_preview_luma(ck_handle_t *h, const ck_preview_params_t *pp, const int32_t *frames, int32_t n, uint8_t *out) {
-    ck_pv_geom g;
-    int rc = begin(h, pp, frames, n, out, &g);
-    if (rc != CK_OK || n == 0) return rc;
-    ck_preview_ws &P = *h->preview;
-    const size_t bytes = (size_t)g.pw * g.ph * n;
-    rc = P.d_out.reserve(bytes);
-    if (rc == CK_OK) rc = ck_launch_preview_luma(h, g, n, P.d_out);
-    if (rc != CK_OK) return rc;
-    CK_HIP(hipMemcpyAsync(out, P.d_out, bytes, hipMemcpyDefault, h->stream));
-    CK_HIP(hipStreamSynchronize(h->stream));
-    return CK_OK;
-}
-
-extern "C" int ck_preview_jpeg(ck_handle_t *h, const ck_preview_params_t *pp, const int32_t *frames, int32_t n, uint8_t *out,
-                               int64_t cap_per_frame, int64_t *sizes, uint32_t *status) {
-    if (!sizes || cap_per_frame < 1) return CK_EINVAL;
-    ck_pv_geom g;
-    int rc = begin(h, pp, frames, n, out, &g);
-    if (rc != CK_OK || n == 0) return rc;
+// The files of a call whose index list and mask are on the device: both halves of k_jpegenc.hip around the copy of the sizes.
+int encode_files(ck_handle *h, const ck_preview_params_t *pp, const ck_pv_geom &g, const ck_pv_csrc *cs, int n, uint8_t *out,
+                 int64_t cap_per_frame, int64_t *sizes, uint32_t *status) {
     ck_preview_ws &P = *h->preview;
     ck_pv_tables tab;
     make_tables(pp, g, &tab);
     const size_t nb = (size_t)g.nblk * n;
-    rc = P.d_coef.reserve(sizeof(int16_t) * 64 * nb);
+    int rc = P.d_coef.reserve(sizeof(int16_t) * 64 * nb);
     if (rc == CK_OK) rc = P.d_dc.reserve(sizeof(int16_t) * nb);
     if (rc == CK_OK) rc = P.d_len.reserve(sizeof(uint32_t) * nb);
     if (rc == CK_OK) rc = P.d_istart.reserve(sizeof(uint32_t) * (size_t)(g.nint + 1) * n);
@@ -164,7 +144,7 @@ extern "C" int ck_preview_jpeg(ck_handle_t *h, const ck_preview_params_t *pp, co
     if (rc == CK_OK) rc = P.d_sizes.reserve(sizeof(int64_t) * 3 * (size_t)n);
     if (rc != CK_OK) return rc;
     const bool direct = is_device_pointer(out); // a caller's device buffer is written in place: file i at out + i * cap_per_frame
-    rc = ck_launch_preview_encode(h, g, tab, n, nullptr, cap_per_frame, !direct);
+    rc = ck_launch_preview_encode(h, g, tab, cs, n, nullptr, cap_per_frame, !direct);
     if (rc != CK_OK) return rc;
     // sizes first: they say how much staging the files need and how many bytes cross the bus
     CK_HIP(hipMemcpyAsync(P.h_sizes, P.d_sizes, sizeof(int64_t) * 3 * (size_t)n, hipMemcpyDeviceToHost, h->stream));
@@ -177,7 +157,7 @@ extern "C" int ck_preview_jpeg(ck_handle_t *h, const ck_preview_params_t *pp, co
         if (rc == CK_OK) rc = P.h_out.reserve(total);
         if (rc != CK_OK) return rc;
     }
-    rc = ck_launch_preview_encode(h, g, tab, n, direct ? out : P.d_out, cap_per_frame, !direct);
+    rc = ck_launch_preview_encode(h, g, tab, cs, n, direct ? out : P.d_out, cap_per_frame, !direct);
     if (rc != CK_OK) return rc;
     if (!direct) CK_HIP(hipMemcpyAsync(P.h_out, P.d_out, total, hipMemcpyDeviceToHost, h->stream));
     uint32_t *st = reinterpret_cast<uint32_t *>(P.h_sizes + 3 * (size_t)n);
@@ -188,4 +168,134 @@ extern "C" int ck_preview_jpeg(ck_handle_t *h, const ck_preview_params_t *pp, co
     if (!direct)
         for (int i = 0; i < n; i++) memcpy(out + (size_t)i * cap_per_frame, P.h_out + off[i], (size_t)used(i));
     return CK_OK;
+}
+
+// the pixels of a call, [bytes] of them, through the workspace's staging to a host or device `out`
+template <typename Launch>
+int read_pixels(ck_handle *h, size_t bytes, uint8_t *out, Launch launch) {
+    ck_preview_ws &P = *h->preview;
+    int rc = P.d_out.reserve(bytes);
+    if (rc == CK_OK) rc = launch(P.d_out);
+    if (rc != CK_OK) return rc;
+    CK_HIP(hipMemcpyAsync(out, P.d_out, bytes, hipMemcpyDefault, h->stream));
+    CK_HIP(hipStreamSynchronize(h->stream));
+    return CK_OK;
+}
+
+// libjpeg's rgb_ycc_convert (jccolor.c) in 16-bit fixed point; row c = the weights of R, G, B in component c
+constexpr int kYcc[3][3] = {{(int)CK_LUMA_R, (int)CK_LUMA_G, (int)CK_LUMA_B}, {-11059, -21709, 32768}, {32768, -27439, -5329}};
+constexpr int kYccBias[3] = {32768, (128 << 16) + 32767, (128 << 16) + 32767};
+
+// what the kernels need of a packed colour family (ck_raw_class: bpp 2 with the luma's byte offset in k[2], bpp 3 / 4 with the luma
+// weight of a pixel's bytes 0, 1, 2: the weight of byte 0 tells RGB from BGR)
+void color_source(const ck_raw_geom &L, int orientation, const uint8_t *p, int stride, size_t pitch, ck_pv_csrc *cs) {
+    memset(cs, 0, sizeof *cs);
+    cs->p = p; cs->stride = stride; cs->pitch = pitch;
+    cs->sw = L.sw; cs->sh = L.sh; cs->orientation = orientation; cs->bpp = L.cls.bpp;
+    if (L.cls.bpp == 2) { // YUYV: Y0 U Y1 V, UYVY: U Y0 V Y1
+        const int yo = (int)L.cls.k[2];
+        cs->off[0] = yo; cs->off[1] = 1 - yo; cs->off[2] = 3 - yo;
+    }
+    const bool bgr = L.cls.k[0] == CK_LUMA_B;
+    for (int c = 0; c < 3; c++) {
+        for (int k = 0; k < 3; k++) cs->wgt[c][k] = kYcc[c][bgr ? 2 - k : k];
+        cs->bias[c] = kYccBias[c];
+        cs->ovl[c] = (kYcc[c][0] * 0 + kYcc[c][1] * 255 + kYcc[c][2] * 0 + kYccBias[c]) >> 16; // RGB (0, 255, 0)
+    }
+}
+
+} // namespace
+
+int ck_preview_color_run(ck_handle *h, const ck_preview_params_t *pp, const ck_pv_color_src &src, const int32_t *frames, int32_t n,
+                         uint8_t *out, bool files, int64_t cap_per_frame, int64_t *sizes, uint32_t *status) {
+    if (!h || !pp || !out || n < 0 || (files && (!sizes || cap_per_frame < 1))) return CK_EINVAL;
+    ck_pv_geom g;
+    int rc = resolve(pp, h->w, h->h, 3, &g);
+    if (rc != CK_OK) return rc;
+    ck_raw_geom L;
+    rc = ck_raw_geometry(src.fmt, h->w, h->h, &L);
+    if (rc != CK_OK) return rc;
+    if (L.cls.bpp == 1) return CK_EUNSUPPORTED; // a luma-first family: its chroma never reaches the device (the grey preview serves it)
+    if ((!src.p && src.n_frames > 0) || src.n_frames < 0 || src.stride < L.min_stride || src.pitch < (int64_t)src.stride * L.sh) return CK_EINVAL;
+    rc = begin(h, frames, n, src.n_frames, &g);
+    if (rc != CK_OK || n == 0) return rc;
+    ck_pv_csrc cs;
+    color_source(L, src.fmt->orientation, src.p, src.stride, (size_t)src.pitch, &cs);
+    if (files) return encode_files(h, pp, g, &cs, n, out, cap_per_frame, sizes, status);
+    return read_pixels(h, (size_t)g.pw * g.ph * 3 * n, out, [&](uint8_t *d) { return ck_launch_preview_color(h, g, cs, n, d); });
+}
+
+static_assert(sizeof(ck_preview_params_t) == 24, "ck_preview_params_t layout");
+
+extern "C" void ck_preview_params_default(ck_preview_params_t *pp) {
+    if (!pp) return;
+    memset(pp, 0, sizeof *pp);
+    pp->width = 640; pp->height = 480; // the caps filter of the reference's stream (mjpeg.rs:41-49)
+    pp->quality = 50;                  // turbojpeg::compress(.., 50, ..) (mjpeg.rs:116)
+}
+
+static int layout(const ck_preview_params_t *pp, int32_t W, int32_t H, int nc, int32_t *pw, int32_t *ph, int64_t *max_bytes) {
+    ck_pv_geom g;
+    const int rc = resolve(pp, W, H, nc, &g);
+    if (rc != CK_OK) return rc;
+    if (pw) *pw = g.pw;
+    if (ph) *ph = g.ph;
+    if (max_bytes) *max_bytes = max_file_bytes(g);
+    return CK_OK;
+}
+extern "C" int ck_preview_layout(const ck_preview_params_t *pp, int32_t W, int32_t H, int32_t *pw, int32_t *ph, int64_t *max_bytes) {
+    return layout(pp, W, H, 1, pw, ph, max_bytes);
+}
+extern "C" int ck_preview_color_layout(const ck_preview_params_t *pp, int32_t W, int32_t H, int32_t *pw, int32_t *ph, int64_t *max_bytes) {
+    return layout(pp, W, H, 3, pw, ph, max_bytes);
+}
+
+extern "C" int ck_preview_luma(ck_handle_t *h, const ck_preview_params_t *pp, const int32_t *frames, int32_t n, uint8_t *out) {
+    ck_pv_geom g;
+    const int rc = begin(h, pp, frames, n, out, &g);
+    if (rc != CK_OK || n == 0) return rc;
+    return read_pixels(h, (size_t)g.pw * g.ph * n, out, [&](uint8_t *d) { return ck_launch_preview_luma(h, g, n, d); });
+}
+
+extern "C" int ck_preview_jpeg(ck_handle_t *h, const ck_preview_params_t *pp, const int32_t *frames, int32_t n, uint8_t *out,
+                               int64_t cap_per_frame, int64_t *sizes, uint32_t *status) {
+    if (!sizes || cap_per_frame < 1) return CK_EINVAL;
+    ck_pv_geom g;
+    const int rc = begin(h, pp, frames, n, out, &g);
+    if (rc != CK_OK || n == 0) return rc;
+    return encode_files(h, pp, g, nullptr, n, out, cap_per_frame, sizes, status);
+}
+
+// ---- colour (§4g): the raw frames of the handle's staging, or of the caller's device memory ---------------------------------------
+// the raw twin of the staged frames, while the last ck_upload_raw / ck_raw_luma_batch still is what staged them
+static int staged_raw(ck_handle *h, ck_pv_color_src *src) {
+    if (!h) return CK_EINVAL;
+    if (h->n_raw_staged < 0) return CK_EINVAL;
+    ck_raw_geom L;
+    const int rc = ck_raw_geometry(&h->raw_staged_fmt, h->w, h->h, &L);
+    if (rc != CK_OK) return rc;
+    *src = {h->n_raw_staged ? (const uint8_t *)h->raw->d_stage : nullptr, L.stride16, (int64_t)L.pitch16, h->n_raw_staged, &h->raw_staged_fmt};
+    return CK_OK;
+}
+
+extern "C" int ck_preview_jpeg_color(ck_handle_t *h, const ck_preview_params_t *pp, const int32_t *frames, int32_t n, uint8_t *out,
+                                     int64_t cap_per_frame, int64_t *sizes, uint32_t *status) {
+    ck_pv_color_src src;
+    const int rc = staged_raw(h, &src);
+    return rc != CK_OK ? rc : ck_preview_color_run(h, pp, src, frames, n, out, true, cap_per_frame, sizes, status);
+}
+extern "C" int ck_preview_color(ck_handle_t *h, const ck_preview_params_t *pp, const int32_t *frames, int32_t n, uint8_t *out) {
+    ck_pv_color_src src;
+    const int rc = staged_raw(h, &src);
+    return rc != CK_OK ? rc : ck_preview_color_run(h, pp, src, frames, n, out, false, 0, nullptr, nullptr);
+}
+extern "C" int ck_preview_jpeg_color_device(ck_handle_t *h, const ck_preview_params_t *pp, const uint8_t *d_raw, int32_t stride,
+                                            int64_t frame_pitch, const ck_raw_format_t *fmt, const int32_t *frames, int32_t n_frames,
+                                            int32_t n, uint8_t *out, int64_t cap_per_frame, int64_t *sizes, uint32_t *status) {
+    return ck_preview_color_run(h, pp, {d_raw, stride, frame_pitch, n_frames, fmt}, frames, n, out, true, cap_per_frame, sizes, status);
+}
+extern "C" int ck_preview_color_device(ck_handle_t *h, const ck_preview_params_t *pp, const uint8_t *d_raw, int32_t stride,
+                                       int64_t frame_pitch, const ck_raw_format_t *fmt, const int32_t *frames, int32_t n_frames, int32_t n,
+                                       uint8_t *out) {
+    return ck_preview_color_run(h, pp, {d_raw, stride, frame_pitch, n_frames, fmt}, frames, n, out, false, 0, nullptr, nullptr);
 }

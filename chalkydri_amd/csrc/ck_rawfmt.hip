@@ -26,7 +26,8 @@ int check_raw_imgs(const ck_handle *h, const ck_image_u8_t *imgs, int n, const c
 // host frames -> staging -> device -> staged frames, enqueued on the handle's stream (the caller synchronises)
 int stage_and_convert(ck_handle *h, const ck_image_u8_t *imgs, int n, const ck_raw_format_t *fmt, const ck_raw_geom &L) {
     CK_HIP(hipSetDevice(h->device));
-    if (n == 0) { h->n_staged = 0; return CK_OK; }
+    h->n_raw_staged = -1; // the raw staging is about to be rewritten: its twin is valid again only once this call has succeeded
+    if (n == 0) { ck_set_staged(h, 0); h->n_raw_staged = 0; h->raw_staged_fmt = *fmt; return CK_OK; }
     // exactly these bytes: under CK_POISON=3 the device buffer then ends where the kernel's last permitted read ends
     const size_t st = (size_t)L.stride16, pitch = L.pitch16, bytes = pitch * n - st + L.min_stride;
     if (!ck_workspace(h->raw)) return CK_ENOMEM;
@@ -42,7 +43,9 @@ int stage_and_convert(ck_handle *h, const ck_image_u8_t *imgs, int n, const ck_r
     CK_HIP(hipMemcpyAsync(R.d_stage, R.h_stage, bytes, hipMemcpyHostToDevice, h->stream));
     rc = ck_launch_rawfmt(h, h->stream, {R.d_stage, (int)st, pitch, L.sw, L.sh}, L.cls, fmt->orientation, h->d_frames, n);
     if (rc != CK_OK) return rc;
-    h->n_staged = n;
+    ck_set_staged(h, n);
+    h->n_raw_staged = n; // (d_stage keeps the raw frames: the colour preview's source)
+    h->raw_staged_fmt = *fmt;
     return CK_OK;
 }
 
@@ -122,6 +125,6 @@ extern "C" int ck_upload_raw_device(ck_handle_t *h, const uint8_t *d_raw, int32_
     rc = ck_launch_rawfmt(h, h->stream, {d_raw, stride, (size_t)frame_pitch, L.sw, L.sh}, L.cls, fmt->orientation, h->d_frames, n);
     if (rc != CK_OK) return rc;
     CK_HIP(hipStreamSynchronize(h->stream)); // (the caller may reuse d_raw)
-    h->n_staged = n;
+    ck_set_staged(h, n);
     return CK_OK;
 }

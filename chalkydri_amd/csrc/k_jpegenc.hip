@@ -2,6 +2,10 @@
 // integer forward DCT and quantiser, Huffman coding with the Annex-K luminance tables, bit packing, byte stuffing and restart
 // markers.  Every stage is data-parallel over the blocks (or the bytes) of all frames of a call; nothing comes back to the host
 // between the stages.  The files equal libjpeg's byte for byte (tests/np_jpeg_enc.py restates it).
+// The colour form (§4g) has a front end of its own, k_pv_fdct_color: it gathers from the RAW frames (orientation, packed 2 / 3 / 4
+// byte pixels, libjpeg's colour conversion) one block per (MCU, component), and hands the same stages the interleaved block
+// sequence Y Cb Cr Y Cb Cr ...: there NC = 3, a block's component is its index mod 3, its DC predecessor lies three blocks back
+// and components 1 and 2 use the chrominance tables.  NC = 1 is the grey code as it was.
 #include "ck_jpeg_tables.h"
 #include "ck_preview.h"
 
@@ -12,28 +16,35 @@ constexpr int PV_NT = 256;
 // zig-zag index -> natural index (ITU-T T.81 figure A.6)
 __device__ constexpr uint8_t kZZ[64] = CK_JPEG_NATURAL_ORDER;
 
-// the encoder's view of both tables: [symbol] = code | length << 16 (0 = the symbol has no code); DC at 0..15, AC at 16..271
-struct HuffEnc { uint32_t e[16 + 256]; };
+// the encoder's view of both tables: [symbol] = code | length << 16 (0 = the symbol has no code); DC at 0..15, AC at 16..271;
+// the luminance pair (Annex K.3) first, the chrominance pair behind it
+constexpr int PV_ENC_WORDS = 16 + 256;
+struct HuffEnc { uint32_t e[2 * PV_ENC_WORDS]; };
 constexpr HuffEnc make_enc() {
     HuffEnc t{};
-    for (int cls = 0; cls < 2; cls++) {
-        const ck_jpeg_std_huff &s = kStdHuff[cls][0]; // Annex K.3, luminance
-        uint32_t code = 0;
-        int p = 0;
-        for (int l = 1; l <= 16; l++) {
-            for (int k = 0; k < s.bits[l - 1]; k++, p++, code++) t.e[(cls ? 16 : 0) + s.vals[p]] = code | ((uint32_t)l << 16);
-            code <<= 1;
+    for (int set = 0; set < 2; set++)
+        for (int cls = 0; cls < 2; cls++) {
+            const ck_jpeg_std_huff &s = kStdHuff[cls][set];
+            uint32_t code = 0;
+            int p = 0;
+            for (int l = 1; l <= 16; l++) {
+                for (int k = 0; k < s.bits[l - 1]; k++, p++, code++) t.e[set * PV_ENC_WORDS + (cls ? 16 : 0) + s.vals[p]] = code | ((uint32_t)l << 16);
+                code <<= 1;
+            }
         }
-    }
     return t;
 }
 __device__ constexpr HuffEnc kEnc = make_enc();
-constexpr int PV_ENC_WORDS = 16 + 256;
 
+// NC = 1: the luminance pair; NC = 3: both
+template <int NC = 1>
 __device__ __forceinline__ void load_enc(uint32_t *lds) {
-    for (int i = threadIdx.x; i < PV_ENC_WORDS; i += PV_NT) lds[i] = kEnc.e[i];
+    for (int i = threadIdx.x; i < (NC == 3 ? 2 : 1) * PV_ENC_WORDS; i += PV_NT) lds[i] = kEnc.e[i];
     __syncthreads();
 }
+// the tables of block b of the interleaved sequence
+template <int NC>
+__device__ __forceinline__ const uint32_t *enc_of(const uint32_t *lds, int b) { return NC == 3 && b % 3 ? lds + PV_ENC_WORDS : lds; }
 
 // ---- overlay: the outline pixels of a frame's detections as a bit image ----------------------------------------------------
 __device__ __forceinline__ int corner_px(double p, int pn, int fn) {
@@ -91,6 +102,61 @@ __global__ __launch_bounds__(PV_NT) void k_pv_luma(ck_pv_geom g, int n, ck_dev_i
     out[t] = (uint8_t)pv_pixel(g, s, x, y, ((2 * x + 1) * g.W) / (2 * g.pw), ((2 * y + 1) * g.H) / (2 * g.ph));
 }
 
+// ---- colour (§4g): component `comp` of pixel (ox, oy) of the ORIENTED frame, from the raw source --------------------------------
+// The address of a pixel's bytes separates into a term of ox and a term of oy under all four index maps of §4d (none: S[oy][ox],
+// clockwise: S[sh-1-ox][oy], rotate-180: S[sh-1-oy][sw-1-ox], counterclockwise: S[ox][sw-1-oy]), so a block computes eight of each.
+// Every read lies inside [row, row + min_stride) of a source row 0 .. sh-1: ox < W and oy < H bound the row and the pixel, and the
+// pair of a 4:2:2 pixel u ends at byte 4 (u >> 1) + 3 < 4 ceil(sw / 2).
+struct CLane { int comp, off, w0, w1, w2, bias, ovl; }; // a lane's component and its constants out of ck_pv_csrc
+__device__ __forceinline__ CLane clane(const ck_pv_csrc &s, int comp) {
+    const auto pick = [&](int a, int b, int c) { return comp == 0 ? a : (comp == 1 ? b : c); };
+    return {comp, pick(s.off[0], s.off[1], s.off[2]), pick(s.wgt[0][0], s.wgt[1][0], s.wgt[2][0]), pick(s.wgt[0][1], s.wgt[1][1], s.wgt[2][1]),
+            pick(s.wgt[0][2], s.wgt[1][2], s.wgt[2][2]), pick(s.bias[0], s.bias[1], s.bias[2]), pick(s.ovl[0], s.ovl[1], s.ovl[2])};
+}
+template <bool YUV>
+__device__ __forceinline__ int c_pixel_off(const ck_pv_csrc &s, const CLane &L, int u) { // pixel u of a source row
+    if (YUV) return (L.comp ? (u >> 1) << 2 : u << 1) + L.off;
+    return u * s.bpp;
+}
+template <bool YUV>
+__device__ __forceinline__ int c_term_x(const ck_pv_csrc &s, const CLane &L, int ox) {
+    switch (s.orientation) {
+    case CK_ORIENT_CLOCKWISE: return (s.sh - 1 - ox) * s.stride;
+    case CK_ORIENT_COUNTERCLOCKWISE: return ox * s.stride;
+    case CK_ORIENT_ROTATE_180: return c_pixel_off<YUV>(s, L, s.sw - 1 - ox);
+    }
+    return c_pixel_off<YUV>(s, L, ox);
+}
+template <bool YUV>
+__device__ __forceinline__ int c_term_y(const ck_pv_csrc &s, const CLane &L, int oy) {
+    switch (s.orientation) {
+    case CK_ORIENT_CLOCKWISE: return c_pixel_off<YUV>(s, L, oy);
+    case CK_ORIENT_COUNTERCLOCKWISE: return c_pixel_off<YUV>(s, L, s.sw - 1 - oy);
+    case CK_ORIENT_ROTATE_180: return (s.sh - 1 - oy) * s.stride;
+    }
+    return oy * s.stride;
+}
+// the component at byte offset `at` of the frame `p`; then the overlay (bit = the preview pixel's index in the mask)
+template <bool YUV>
+__device__ __forceinline__ int c_pixel(const uint8_t *p, int at, const CLane &L, const uint32_t *mask, int bit) {
+    int v = YUV ? (int)p[at] : (L.w0 * (int)p[at] + L.w1 * (int)p[at + 1] + L.w2 * (int)p[at + 2] + L.bias) >> 16;
+    if (mask && ((mask[bit >> 5] >> (bit & 31)) & 1u)) v = L.ovl;
+    return v;
+}
+
+// the triples the encoder is given, [n][ph][pw][3]: one lane per byte
+template <bool YUV>
+__global__ __launch_bounds__(PV_NT) void k_pv_color(ck_pv_geom g, ck_pv_csrc s, int n, const int32_t *frames, const uint32_t *mask, uint8_t *out) {
+    const long t = (long)blockIdx.x * PV_NT + threadIdx.x;
+    const long npx = (long)g.pw * g.ph;
+    if (t >= npx * n * 3) return;
+    const long q = t / 3;
+    const int i = (int)(q / npx), r = (int)(q - i * npx), y = r / g.pw, x = r - y * g.pw;
+    const CLane L = clane(s, (int)(t - q * 3));
+    const int at = c_term_x<YUV>(s, L, ((2 * x + 1) * g.W) / (2 * g.pw)) + c_term_y<YUV>(s, L, ((2 * y + 1) * g.H) / (2 * g.ph));
+    out[t] = (uint8_t)c_pixel<YUV>(s.p + (size_t)frames[i] * s.pitch, at, L, g.overlay ? mask + (size_t)i * g.mask_words : nullptr, r);
+}
+
 // ---- forward DCT: libjpeg's jpeg_fdct_islow ------------------------------------------------------------------------------------
 // CONST_BITS 13, PASS1_BITS 2.  32-bit arithmetic is exact here (libjpeg's JLONG is not needed): samples are in [-128, 127], a
 // 1-D pass amplifies by at most 8 (sum of |cos| times sqrt 2), so after the row pass (scaled by 4) |v| <= 4097; in the column pass
@@ -120,36 +186,16 @@ __device__ __forceinline__ void fdct_1d(int &d0, int &d1, int &d2, int &d3, int 
 
 __device__ __forceinline__ int category(int v) { return 32 - __clz(abs(v)); }
 
-// One 8 x 8 block per lane, the block in registers: gather (scale + overlay, right / bottom edge replicated), level shift, row
-// pass, column pass, libjpeg's quantiser (sign-magnitude, (|c| + qval / 2) / qval with qval = 8 q: the exact integer quotient),
-// coefficients out in zig-zag order; the block's AC bit count and its DC beside them for the scan that places the blocks.
-__global__ __launch_bounds__(PV_NT) void k_pv_fdct(ck_pv_geom g, ck_pv_tables tab, int n, ck_dev_image img, const int32_t *frames,
-                                                   const uint32_t *mask, int16_t *coef, int16_t *dc, uint32_t *len) {
-    __shared__ uint32_t enc[PV_ENC_WORDS];
-    load_enc(enc);
-    const long t = (long)blockIdx.x * PV_NT + threadIdx.x;
-    if (t >= (long)n * g.nblk) return;
-    const int i = (int)(t / g.nblk), b = (int)(t - (long)i * g.nblk), by = b / g.bw, bx = b - by * g.bw;
-    const PvSrc s = {img.p + (size_t)frames[i] * img.pitch, img.stride, g.overlay ? mask + (size_t)i * g.mask_words : nullptr};
-    int px[8], sx[8];
-#pragma unroll
-    for (int c = 0; c < 8; c++) {
-        px[c] = min(bx * 8 + c, g.pw - 1);
-        sx[c] = ((2 * px[c] + 1) * g.W) / (2 * g.pw);
-    }
-    int d[64];
-#pragma unroll
-    for (int r = 0; r < 8; r++) {
-        const int py = min(by * 8 + r, g.ph - 1), sy = ((2 * py + 1) * g.H) / (2 * g.ph);
-#pragma unroll
-        for (int c = 0; c < 8; c++) d[r * 8 + c] = pv_pixel(g, s, px[c], py, sx[c], sy) - 128;
-        fdct_1d<true>(d[r * 8], d[r * 8 + 1], d[r * 8 + 2], d[r * 8 + 3], d[r * 8 + 4], d[r * 8 + 5], d[r * 8 + 6], d[r * 8 + 7]);
-    }
+// What follows the row passes of block t, whose rows are in d[]: column pass, libjpeg's quantiser (sign-magnitude, (|c| + qval / 2)
+// / qval with qval = 8 q: the exact integer quotient; the chrominance divisors where `chroma`), coefficients out in zig-zag order;
+// the block's AC bit count under the tables `enc` and its DC beside them for the scan that places the blocks.
+__device__ __forceinline__ void fdct_finish(int (&d)[64], const ck_pv_tables &tab, bool chroma, const uint32_t *enc, long t, int16_t *coef,
+                                            int16_t *dc, uint32_t *len) {
 #pragma unroll
     for (int c = 0; c < 8; c++) fdct_1d<false>(d[c], d[8 + c], d[16 + c], d[24 + c], d[32 + c], d[40 + c], d[48 + c], d[56 + c]);
 #pragma unroll
     for (int k = 0; k < 64; k++) {
-        const int q = tab.qdiv[k], a = (abs(d[k]) + (q >> 1)) / q;
+        const int q = chroma ? tab.qdiv[1][k] : tab.qdiv[0][k], a = (abs(d[k]) + (q >> 1)) / q;
         d[k] = d[k] < 0 ? -a : a;
     }
     // AC bits: (run, size) codes + value bits, ZRL for every 16 zeros in front of a coefficient, EOB after the last one
@@ -175,12 +221,72 @@ __global__ __launch_bounds__(PV_NT) void k_pv_fdct(ck_pv_geom g, ck_pv_tables ta
     len[t] = bits;
 }
 
+// One 8 x 8 block per lane, the block in registers: gather (scale + overlay, right / bottom edge replicated), level shift, row
+// pass, then fdct_finish.
+__global__ __launch_bounds__(PV_NT) void k_pv_fdct(ck_pv_geom g, ck_pv_tables tab, int n, ck_dev_image img, const int32_t *frames,
+                                                   const uint32_t *mask, int16_t *coef, int16_t *dc, uint32_t *len) {
+    __shared__ uint32_t enc[PV_ENC_WORDS];
+    load_enc(enc);
+    const long t = (long)blockIdx.x * PV_NT + threadIdx.x;
+    if (t >= (long)n * g.nblk) return;
+    const int i = (int)(t / g.nblk), b = (int)(t - (long)i * g.nblk), by = b / g.bw, bx = b - by * g.bw;
+    const PvSrc s = {img.p + (size_t)frames[i] * img.pitch, img.stride, g.overlay ? mask + (size_t)i * g.mask_words : nullptr};
+    int px[8], sx[8];
+#pragma unroll
+    for (int c = 0; c < 8; c++) {
+        px[c] = min(bx * 8 + c, g.pw - 1);
+        sx[c] = ((2 * px[c] + 1) * g.W) / (2 * g.pw);
+    }
+    int d[64];
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+        const int py = min(by * 8 + r, g.ph - 1), sy = ((2 * py + 1) * g.H) / (2 * g.ph);
+#pragma unroll
+        for (int c = 0; c < 8; c++) d[r * 8 + c] = pv_pixel(g, s, px[c], py, sx[c], sy) - 128;
+        fdct_1d<true>(d[r * 8], d[r * 8 + 1], d[r * 8 + 2], d[r * 8 + 3], d[r * 8 + 4], d[r * 8 + 5], d[r * 8 + 6], d[r * 8 + 7]);
+    }
+    fdct_finish(d, tab, false, enc, t, coef, dc, len);
+}
+
+// The colour front end (§4g): one block per lane again, the lane's block being component t % 3 of MCU t / 3 of the frame — so the
+// coefficients come out in scan order.  The gather reads the raw frame through the orientation's index map and converts on the
+// way: no colour image is materialised.
+template <bool YUV>
+__global__ __launch_bounds__(PV_NT) void k_pv_fdct_color(ck_pv_geom g, ck_pv_tables tab, ck_pv_csrc s, int n, const int32_t *frames,
+                                                         const uint32_t *mask, int16_t *coef, int16_t *dc, uint32_t *len) {
+    __shared__ uint32_t enc[2 * PV_ENC_WORDS];
+    load_enc<3>(enc);
+    const long t = (long)blockIdx.x * PV_NT + threadIdx.x;
+    if (t >= (long)n * g.nblk) return;
+    const int i = (int)(t / g.nblk), b = (int)(t - (long)i * g.nblk), m = b / 3, by = m / g.bw, bx = m - by * g.bw;
+    const CLane L = clane(s, b - 3 * m);
+    const uint8_t *P = s.p + (size_t)frames[i] * s.pitch;
+    const uint32_t *M = g.overlay ? mask + (size_t)i * g.mask_words : nullptr;
+    int px[8], tx[8];
+#pragma unroll
+    for (int c = 0; c < 8; c++) {
+        px[c] = min(bx * 8 + c, g.pw - 1);
+        tx[c] = c_term_x<YUV>(s, L, ((2 * px[c] + 1) * g.W) / (2 * g.pw));
+    }
+    int d[64];
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+        const int py = min(by * 8 + r, g.ph - 1), ty = c_term_y<YUV>(s, L, ((2 * py + 1) * g.H) / (2 * g.ph));
+#pragma unroll
+        for (int c = 0; c < 8; c++) d[r * 8 + c] = c_pixel<YUV>(P, tx[c] + ty, L, M, py * g.pw + px[c]) - 128;
+        fdct_1d<true>(d[r * 8], d[r * 8 + 1], d[r * 8 + 2], d[r * 8 + 3], d[r * 8 + 4], d[r * 8 + 5], d[r * 8 + 6], d[r * 8 + 7]);
+    }
+    fdct_finish(d, tab, L.comp != 0, enc_of<3>(enc, b), t, coef, dc, len);
+}
+
 // ---- placement: where every block's bits start --------------------------------------------------------------------------------
 // One wave per (entry, restart interval): the exclusive scan of the blocks' bit counts (DC difference from the previous block's
 // DC — known, so nothing is sequential — plus the AC bits), four consecutive blocks per lane and step; then the interval's bytes.
+// NC = 3: the previous block of the same component, NC blocks back (an interval starts on an MCU), and the component's tables.
+template <int NC>
 __global__ __launch_bounds__(PV_NT) void k_pv_scan(ck_pv_geom g, int n, const int16_t *dc, uint32_t *len, uint32_t *istart) {
-    __shared__ uint32_t enc[PV_ENC_WORDS];
-    load_enc(enc);
+    __shared__ uint32_t enc[(NC == 3 ? 2 : 1) * PV_ENC_WORDS];
+    load_enc<NC>(enc);
     const int lane = threadIdx.x & 63;
     const long w = (long)blockIdx.x * (PV_NT / 64) + (threadIdx.x >> 6);
     if (w >= (long)n * g.nint) return;
@@ -196,8 +302,8 @@ __global__ __launch_bounds__(PV_NT) void k_pv_scan(ck_pv_geom g, int n, const in
             const int b = base + lane * 4 + k;
             v[k] = 0;
             if (b < b1) {
-                const int diff = (int)D[b] - (b == b0 ? 0 : (int)D[b - 1]), sz = category(diff);
-                v[k] = L[b] + (enc[sz] >> 16) + (uint32_t)sz;
+                const int diff = (int)D[b] - (b - b0 < NC ? 0 : (int)D[b - NC]), sz = category(diff);
+                v[k] = L[b] + (enc_of<NC>(enc, b)[sz] >> 16) + (uint32_t)sz;
             }
             s += v[k];
         }
@@ -264,13 +370,15 @@ struct BitWriter {
 
 // One block per lane: Huffman codes and value bits at the block's bit position; the last block of an interval pads the interval's
 // last byte with 1-bits.
+template <int NC>
 __global__ __launch_bounds__(PV_NT) void k_pv_pack(ck_pv_geom g, int n, const int16_t *coef, const int16_t *dc, const uint32_t *len,
                                                    const uint32_t *istart, uint32_t *bitbuf) {
-    __shared__ uint32_t enc[PV_ENC_WORDS];
-    load_enc(enc);
+    __shared__ uint32_t enc_all[(NC == 3 ? 2 : 1) * PV_ENC_WORDS];
+    load_enc<NC>(enc_all);
     const long t = (long)blockIdx.x * PV_NT + threadIdx.x;
     if (t >= (long)n * g.nblk) return;
     const int i = (int)(t / g.nblk), b = (int)(t - (long)i * g.nblk), j = b / g.R, b0 = j * g.R;
+    const uint32_t *enc = enc_of<NC>(enc_all, b);
     const uint32_t pos = istart[(size_t)i * (g.nint + 1) + j] * 8u + len[t];
     BitWriter W = {bitbuf + (size_t)i * g.bit_words + (pos >> 5), 0ull, (int)(pos & 31), true};
     const uint4 *c4 = reinterpret_cast<const uint4 *>(coef + (size_t)t * 64);
@@ -282,7 +390,7 @@ __global__ __launch_bounds__(PV_NT) void k_pv_pack(ck_pv_geom g, int n, const in
         for (int k = 0; k < 8; k++) {
             int v = (int)(int16_t)(cw[k >> 1] >> ((k & 1) * 16));
             const bool is_dc = q == 0 && k == 0;
-            if (is_dc) v -= b == b0 ? 0 : (int)dc[t - 1];
+            if (is_dc) v -= b - b0 < NC ? 0 : (int)dc[t - NC];
             else if (v == 0) { run++; continue; }
             for (; run > 15; run -= 16) W.put(enc[16 + 0xF0] & 0xFFFFu, (int)(enc[16 + 0xF0] >> 16));
             const int sz = category(v);
@@ -419,23 +527,47 @@ int ck_launch_preview_luma(ck_handle *h, const ck_pv_geom &g, int n, uint8_t *d_
     return CK_OK;
 }
 
-// scale .. stuffing scan: after it d_sizes holds every file's size, offset in the output and status
-int ck_launch_preview_encode(ck_handle *h, const ck_pv_geom &g, const ck_pv_tables &t, int n, uint8_t *d_out, int64_t cap, bool compact) {
+int ck_launch_preview_color(ck_handle *h, const ck_pv_geom &g, const ck_pv_csrc &cs, int n, uint8_t *d_out) {
+    ck_preview_ws &P = *h->preview;
+    const dim3 grid(blocks_for((long)n * g.pw * g.ph * 3));
+    if (cs.bpp == 2) hipLaunchKernelGGL(k_pv_color<true>, grid, dim3(PV_NT), 0, h->stream, g, cs, n, P.d_frames, P.d_mask, d_out);
+    else hipLaunchKernelGGL(k_pv_color<false>, grid, dim3(PV_NT), 0, h->stream, g, cs, n, P.d_frames, P.d_mask, d_out);
+    CK_HIP(hipGetLastError());
+    return CK_OK;
+}
+
+namespace {
+
+// front end (the staged luma, or the raw frames `cs` of a colour call) .. stuffing scan
+template <int NC>
+void launch_first_half(ck_handle *h, const ck_pv_geom &g, const ck_pv_tables &t, const ck_pv_csrc *cs, int n, int64_t cap, bool compact) {
     ck_preview_ws &P = *h->preview;
     hipStream_t st = h->stream;
+    const unsigned nb = blocks_for((long)n * g.nblk);
+    if constexpr (NC == 1) hipLaunchKernelGGL(k_pv_fdct, dim3(nb), dim3(PV_NT), 0, st, g, t, n, ck_staged_image(h), P.d_frames, P.d_mask, P.d_coef, P.d_dc, P.d_len);
+    else if (cs->bpp == 2) hipLaunchKernelGGL(k_pv_fdct_color<true>, dim3(nb), dim3(PV_NT), 0, st, g, t, *cs, n, P.d_frames, P.d_mask, P.d_coef, P.d_dc, P.d_len);
+    else hipLaunchKernelGGL(k_pv_fdct_color<false>, dim3(nb), dim3(PV_NT), 0, st, g, t, *cs, n, P.d_frames, P.d_mask, P.d_coef, P.d_dc, P.d_len);
+    hipLaunchKernelGGL(k_pv_scan<NC>, dim3((unsigned)(((long)n * g.nint + PV_NT / 64 - 1) / (PV_NT / 64))), dim3(PV_NT), 0, st, g, n, P.d_dc, P.d_len, P.d_istart);
+    hipLaunchKernelGGL(k_pv_iscan, dim3((unsigned)n), dim3(64), 0, st, g, P.d_istart);
+    const unsigned gz = (unsigned)min(64, (g.bit_words / 4 + PV_NT - 1) / PV_NT);
+    hipLaunchKernelGGL(k_pv_zero, dim3(gz, (unsigned)n), dim3(PV_NT), 0, st, g, P.d_istart, P.d_bits);
+    hipLaunchKernelGGL(k_pv_pack<NC>, dim3(nb), dim3(PV_NT), 0, st, g, n, P.d_coef, P.d_dc, P.d_len, P.d_istart, P.d_bits);
+    hipLaunchKernelGGL(k_pv_cscan, dim3((unsigned)n), dim3(PV_NT), 0, st, g, n, cap, P.d_istart, P.d_bits, P.d_cpre, P.d_sizes);
+    hipLaunchKernelGGL(k_pv_offsets, dim3(1), dim3(64), 0, st, n, cap, compact ? 1 : 0, P.d_sizes);
+}
+
+} // namespace
+
+// scale .. stuffing scan: after it d_sizes holds every file's size, offset in the output and status
+int ck_launch_preview_encode(ck_handle *h, const ck_pv_geom &g, const ck_pv_tables &t, const ck_pv_csrc *cs, int n, uint8_t *d_out,
+                             int64_t cap, bool compact) {
+    ck_preview_ws &P = *h->preview;
     if (!d_out) {
-        const unsigned nb = blocks_for((long)n * g.nblk);
-        hipLaunchKernelGGL(k_pv_fdct, dim3(nb), dim3(PV_NT), 0, st, g, t, n, ck_staged_image(h), P.d_frames, P.d_mask, P.d_coef, P.d_dc, P.d_len);
-        hipLaunchKernelGGL(k_pv_scan, dim3((unsigned)(((long)n * g.nint + PV_NT / 64 - 1) / (PV_NT / 64))), dim3(PV_NT), 0, st, g, n, P.d_dc, P.d_len, P.d_istart);
-        hipLaunchKernelGGL(k_pv_iscan, dim3((unsigned)n), dim3(64), 0, st, g, P.d_istart);
-        const unsigned gz = (unsigned)min(64, (g.bit_words / 4 + PV_NT - 1) / PV_NT);
-        hipLaunchKernelGGL(k_pv_zero, dim3(gz, (unsigned)n), dim3(PV_NT), 0, st, g, P.d_istart, P.d_bits);
-        hipLaunchKernelGGL(k_pv_pack, dim3(nb), dim3(PV_NT), 0, st, g, n, P.d_coef, P.d_dc, P.d_len, P.d_istart, P.d_bits);
-        hipLaunchKernelGGL(k_pv_cscan, dim3((unsigned)n), dim3(PV_NT), 0, st, g, n, cap, P.d_istart, P.d_bits, P.d_cpre, P.d_sizes);
-        hipLaunchKernelGGL(k_pv_offsets, dim3(1), dim3(64), 0, st, n, cap, compact ? 1 : 0, P.d_sizes);
+        if (cs) launch_first_half<3>(h, g, t, cs, n, cap, compact);
+        else launch_first_half<1>(h, g, t, nullptr, n, cap, compact);
     } else {
         const unsigned ge = (unsigned)min(64, (g.chunk_cap + PV_NT - 1) / PV_NT);
-        hipLaunchKernelGGL(k_pv_emit, dim3(ge, (unsigned)n), dim3(PV_NT), 0, st, g, t, n, cap, P.d_istart, P.d_bits, P.d_cpre, P.d_sizes, d_out);
+        hipLaunchKernelGGL(k_pv_emit, dim3(ge, (unsigned)n), dim3(PV_NT), 0, h->stream, g, t, n, cap, P.d_istart, P.d_bits, P.d_cpre, P.d_sizes, d_out);
     }
     CK_HIP(hipGetLastError());
     return CK_OK;

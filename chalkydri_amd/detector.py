@@ -86,6 +86,13 @@ def _bind(L):
     L.ck_preview_layout.argtypes = [pv, i32, i32, _P(i32), _P(i32), _P(C.c_int64)]
     L.ck_preview_jpeg.argtypes = [vp, pv, vp, i32, vp, C.c_int64, vp, vp]
     L.ck_preview_luma.argtypes = [vp, pv, vp, i32, vp]
+    L.ck_preview_color_layout.argtypes = [pv, i32, i32, _P(i32), _P(i32), _P(C.c_int64)]
+    L.ck_preview_jpeg_color.argtypes = [vp, pv, vp, i32, vp, C.c_int64, vp, vp]
+    L.ck_preview_color.argtypes = [vp, pv, vp, i32, vp]
+    L.ck_preview_jpeg_color_device.argtypes = [vp, pv, vp, i32, C.c_int64, rf, vp, i32, i32, vp, C.c_int64, vp, vp]
+    L.ck_preview_color_device.argtypes = [vp, pv, vp, i32, C.c_int64, rf, vp, i32, i32, vp]
+    L.ck_preview_jpeg_color_ingested.argtypes = [vp, i32, pv, vp, i32, vp, C.c_int64, vp, vp]
+    L.ck_preview_color_ingested.argtypes = [vp, i32, pv, vp, i32, vp]
     ep, es = _P(A.ExposureParams), _P(A.ExposureStats)
     L.ck_exposure_params_default.argtypes = [ep]
     L.ck_exposure_params_default.restype = None
@@ -287,6 +294,13 @@ def preview_layout(params, width, height):
     """ck_preview_layout: (pw, ph, max_bytes) of a preview of a width x height handle.  No device needed."""
     pw, ph, mb = C.c_int32(), C.c_int32(), C.c_int64()
     check(_bind(lib()).ck_preview_layout(C.byref(params), width, height, C.byref(pw), C.byref(ph), C.byref(mb)), "ck_preview_layout")
+    return pw.value, ph.value, mb.value
+
+
+def preview_color_layout(params, width, height):
+    """ck_preview_color_layout: (pw, ph, max_bytes) of a colour preview of a width x height handle.  No device needed."""
+    pw, ph, mb = C.c_int32(), C.c_int32(), C.c_int64()
+    check(_bind(lib()).ck_preview_color_layout(C.byref(params), width, height, C.byref(pw), C.byref(ph), C.byref(mb)), "ck_preview_color_layout")
     return pw.value, ph.value, mb.value
 
 
@@ -495,9 +509,9 @@ class AprilTagDetector:
         return [[TagPose(out[i * cap + k]) for k in range(counts[i])] for i in range(n)]
 
     # -- JPEG preview of the staged frames, encoded on the GPU (the driver-station stream) ------------------------------
-    def _preview_in(self, frames, n, width, height, quality, restart_rows, overlay):
+    def _preview_in(self, frames, n, width, height, quality, restart_rows, overlay, color=False):
         pp = preview_params(width, height, quality, restart_rows, overlay)
-        pw, ph, max_bytes = preview_layout(pp, self.width, self.height)
+        pw, ph, max_bytes = (preview_color_layout if color else preview_layout)(pp, self.width, self.height)
         if frames is None:
             if n is None:
                 raise ValueError("frames (indices into the staged frames) or n is required")
@@ -511,10 +525,15 @@ class AprilTagDetector:
         encoded on the device exactly as libjpeg writes them.  frames: indices into the staged frames, or n for 0..n-1.
         overlay=True outlines the detections of the last detect / process call.  cap: bytes per file (default: the bound of
         ck_preview_layout); a file that does not fit comes back cut to cap with CK_PREVIEW_TRUNCATED in its status."""
-        pp, pw, ph, max_bytes, idx, n = self._preview_in(frames, n, width, height, quality, restart_rows, overlay)
+        call = lambda pp, idx, n, out, c, sizes, status: self._L.ck_preview_jpeg(self._h, C.byref(pp), idx, n, out, c, sizes, status)
+        return self._preview_files(call, "ck_preview_jpeg", False, frames, n, width, height, quality, restart_rows, overlay, cap, return_status)
+
+    def _preview_files(self, call, name, color, frames, n, width, height, quality, restart_rows, overlay, cap, return_status):
+        """The files of one of the preview entry points: call(pp, idx, n, out, cap, sizes, status) -> its return code."""
+        pp, pw, ph, max_bytes, idx, n = self._preview_in(frames, n, width, height, quality, restart_rows, overlay, color)
         # without a cap the slots are sized for the pixels themselves (a file beyond that is noise at the highest qualities) and
         # the call is repeated with the bound of ck_preview_layout if a file did not fit; the buffer is kept between calls
-        tries = [min(max_bytes, pw * ph + 1024), max_bytes] if cap is None else [int(cap)]
+        tries = [min(max_bytes, (3 if color else 1) * pw * ph + 1024), max_bytes] if cap is None else [int(cap)]
         for c in tries:
             need = max(n, 1) * max(c, 1)
             if getattr(self, "_pv_buf", None) is None or self._pv_buf.size < need:
@@ -522,12 +541,49 @@ class AprilTagDetector:
             out = self._pv_buf[:need].reshape(max(n, 1), max(c, 1))
             sizes = (C.c_int64 * max(n, 1))()
             status = (C.c_uint32 * max(n, 1))()
-            check(self._L.ck_preview_jpeg(self._h, C.byref(pp), idx.ctypes.data if idx is not None else None, n, out.ctypes.data, c,
-                                          sizes, status), "ck_preview_jpeg")
+            check(call(pp, idx.ctypes.data if idx is not None else None, n, out.ctypes.data, c, sizes, status), name)
             if cap is not None or not any(status[:n]):
                 break
         files = [out[i, :min(sizes[i], c)].tobytes() for i in range(n)]
         return (files, list(sizes)[:n], list(status)[:n]) if return_status else files
+
+    def _preview_triples(self, call, name, frames, n, width, height, quality, restart_rows, overlay):
+        """[n][ph][pw][3] uint8 of one of the ck_preview_color entry points: call(pp, idx, n, out) -> its return code."""
+        pp, pw, ph, _, idx, n = self._preview_in(frames, n, width, height, quality, restart_rows, overlay, True)
+        out = np.empty((n, ph, pw, 3), np.uint8)
+        buf = out if n else np.empty(1, np.uint8)
+        check(call(pp, idx.ctypes.data if idx is not None else None, n, buf.ctypes.data), name)
+        return out
+
+    # -- the same in colour, from the raw frames (DESIGN.md §4g) ---------------------------------------------------------------
+    def preview_jpeg_color(self, frames=None, n=None, width=640, height=480, quality=50, restart_rows=0, overlay=False, cap=None,
+                           return_status=False):
+        """preview_jpeg in colour: three-component 4:4:4 files of the RAW frames the last upload_raw / raw_luma left on the
+        device (a packed colour family: 'YUYV', 'UYVY', 'RGB3', 'BGR3', 'RGBA', 'BGRA'), byte-equal to libjpeg's.  Valid until
+        frames are staged another way."""
+        call = lambda pp, idx, n, out, c, sizes, status: self._L.ck_preview_jpeg_color(self._h, C.byref(pp), idx, n, out, c, sizes, status)
+        return self._preview_files(call, "ck_preview_jpeg_color", True, frames, n, width, height, quality, restart_rows, overlay, cap, return_status)
+
+    def preview_color(self, frames=None, n=None, width=640, height=480, quality=50, restart_rows=0, overlay=False):
+        """[n][ph][pw][3] uint8: the (Y, Cb, Cr) triples the colour encoder is given."""
+        call = lambda pp, idx, n, out: self._L.ck_preview_color(self._h, C.byref(pp), idx, n, out)
+        return self._preview_triples(call, "ck_preview_color", frames, n, width, height, quality, restart_rows, overlay)
+
+    def preview_jpeg_color_device(self, ptr, n_frames, stride, frame_pitch, code, orientation="none", frames=None, n=None, width=640,
+                                  height=480, quality=50, restart_rows=0, overlay=False, cap=None, return_status=False):
+        """preview_jpeg_color of n_frames raw frames in device memory (laid out as upload_raw_device takes them)."""
+        fmt = raw_format(code, orientation)
+        call = lambda pp, idx, n, out, c, sizes, status: self._L.ck_preview_jpeg_color_device(
+            self._h, C.byref(pp), C.c_void_p(ptr), stride, frame_pitch, C.byref(fmt), idx, n_frames, n, out, c, sizes, status)
+        return self._preview_files(call, "ck_preview_jpeg_color_device", True, frames, n, width, height, quality, restart_rows, overlay, cap,
+                                   return_status)
+
+    def preview_color_device(self, ptr, n_frames, stride, frame_pitch, code, orientation="none", frames=None, n=None, width=640,
+                             height=480, quality=50, restart_rows=0, overlay=False):
+        fmt = raw_format(code, orientation)
+        call = lambda pp, idx, n, out: self._L.ck_preview_color_device(self._h, C.byref(pp), C.c_void_p(ptr), stride, frame_pitch,
+                                                                       C.byref(fmt), idx, n_frames, n, out)
+        return self._preview_triples(call, "ck_preview_color_device", frames, n, width, height, quality, restart_rows, overlay)
 
     def preview_luma(self, frames=None, n=None, width=640, height=480, quality=50, restart_rows=0, overlay=False):
         """[n][ph][pw] uint8: the scaled (+ overlaid) pixels the encoder is given."""
@@ -644,6 +700,19 @@ class IngestRing:
         """AprilTagDetector.exposure_stats on the frames of a submitted slot (waits for its upload; the slot stays as it is)."""
         from . import exposure as X
         return X.stats_call(self.det, (self._g, slot), n, frames, roi, params)
+
+    def preview_jpeg_color(self, slot, frames=None, n=None, width=640, height=480, quality=50, restart_rows=0, overlay=False, cap=None,
+                           return_status=False):
+        """AprilTagDetector.preview_jpeg_color on the raw frames of a submitted slot of a raw ring (waits for its upload; the slot
+        stays as it is).  frames: indices below the count the slot was submitted with."""
+        call = lambda pp, idx, n, out, c, sizes, status: self._L.ck_preview_jpeg_color_ingested(self._g, slot, C.byref(pp), idx, n, out, c,
+                                                                                               sizes, status)
+        return self.det._preview_files(call, "ck_preview_jpeg_color_ingested", True, frames, n, width, height, quality, restart_rows,
+                                       overlay, cap, return_status)
+
+    def preview_color(self, slot, frames=None, n=None, width=640, height=480, quality=50, restart_rows=0, overlay=False):
+        call = lambda pp, idx, n, out: self._L.ck_preview_color_ingested(self._g, slot, C.byref(pp), idx, n, out)
+        return self.det._preview_triples(call, "ck_preview_color_ingested", frames, n, width, height, quality, restart_rows, overlay)
 
     def detect(self, slot, n, cap=64):
         dets = (A.Detection * (cap * n))()

@@ -250,18 +250,16 @@ inline ck_preview_params_t preview_params(int width = 640, int height = 480, int
     pp.width = width; pp.height = height; pp.quality = quality; pp.restart_rows = restart_rows; pp.overlay = overlay ? 1 : 0;
     return pp;
 }
-inline std::vector<std::vector<uint8_t>> preview_jpeg(Handle &h, const std::vector<int32_t> &frames, const ck_preview_params_t &pp) {
-    int64_t bound = 0;
-    int32_t pw = 0, ph = 0;
-    check(ck_preview_layout(&pp, h.config().width, h.config().height, &pw, &ph, &bound), "ck_preview_layout");
-    const size_t n = frames.size();
+// The files of one of the preview entry points: `encode(out, cap, sizes)` is the call, `bound` its layout's upper bound.
+template <typename Encode>
+inline std::vector<std::vector<uint8_t>> preview_files(size_t n, int64_t first_cap, int64_t bound, Encode encode) {
     // slots sized for the pixels themselves first (a file beyond that is noise at the highest qualities); the bound if one did not fit
-    int64_t cap = std::min<int64_t>(bound, (int64_t)pw * ph + 1024);
+    int64_t cap = std::min<int64_t>(bound, first_cap);
     std::vector<uint8_t> out;
     std::vector<int64_t> sizes(n);
     for (;;) {
         out.resize(n * (size_t)cap);
-        check(ck_preview_jpeg(h.get(), &pp, frames.data(), (int32_t)n, out.data(), cap, sizes.data(), nullptr), "ck_preview_jpeg");
+        encode(out.data(), cap, sizes.data());
         bool fits = true;
         for (size_t i = 0; i < n; i++) fits = fits && sizes[i] <= cap;
         if (fits || cap == bound) break;
@@ -270,6 +268,24 @@ inline std::vector<std::vector<uint8_t>> preview_jpeg(Handle &h, const std::vect
     std::vector<std::vector<uint8_t>> files(n);
     for (size_t i = 0; i < n; i++) files[i].assign(out.begin() + i * (size_t)cap, out.begin() + i * (size_t)cap + (size_t)sizes[i]);
     return files;
+}
+inline std::vector<std::vector<uint8_t>> preview_jpeg(Handle &h, const std::vector<int32_t> &frames, const ck_preview_params_t &pp) {
+    int64_t bound = 0;
+    int32_t pw = 0, ph = 0;
+    check(ck_preview_layout(&pp, h.config().width, h.config().height, &pw, &ph, &bound), "ck_preview_layout");
+    return preview_files(frames.size(), (int64_t)pw * ph + 1024, bound, [&](uint8_t *out, int64_t cap, int64_t *sizes) {
+        check(ck_preview_jpeg(h.get(), &pp, frames.data(), (int32_t)frames.size(), out, cap, sizes, nullptr), "ck_preview_jpeg");
+    });
+}
+// The same in colour (chalkydri_hip.h: ck_preview_jpeg_color): three-component files of the raw frames the handle's last
+// ck_upload_raw left on the device (a packed colour format); frames: indices into those.
+inline std::vector<std::vector<uint8_t>> preview_jpeg_color(Handle &h, const std::vector<int32_t> &frames, const ck_preview_params_t &pp) {
+    int64_t bound = 0;
+    int32_t pw = 0, ph = 0;
+    check(ck_preview_color_layout(&pp, h.config().width, h.config().height, &pw, &ph, &bound), "ck_preview_color_layout");
+    return preview_files(frames.size(), 3 * (int64_t)pw * ph + 1024, bound, [&](uint8_t *out, int64_t cap, int64_t *sizes) {
+        check(ck_preview_jpeg_color(h.get(), &pp, frames.data(), (int32_t)frames.size(), out, cap, sizes, nullptr), "ck_preview_jpeg_color");
+    });
 }
 // The scaled (+ overlaid) pixels the encoder is given: [n][ph][pw]; pw / ph come back through the pointers.
 inline std::vector<uint8_t> preview_luma(Handle &h, const std::vector<int32_t> &frames, const ck_preview_params_t &pp, int32_t *pw = nullptr,
@@ -776,6 +792,16 @@ class IngestRing {
     void write(int slot, int index, const ck_image_u8_t &img, uint32_t code) { check(ck_ingest_write(g_, slot, index, &img, code), "ck_ingest_write"); }
     void submit(int slot, int n) { check(ck_ingest_submit(g_, slot, n), "ck_ingest_submit"); }
     ck_ingest_t *get() const { return g_; }
+    // the colour preview of a submitted slot of a raw ring, from the slot's raw frames (ck_preview_jpeg_color_ingested)
+    std::vector<std::vector<uint8_t>> preview_jpeg_color(int slot, const std::vector<int32_t> &frames, const ck_preview_params_t &pp) {
+        int64_t bound = 0;
+        int32_t pw = 0, ph = 0;
+        check(ck_preview_color_layout(&pp, h_->config().width, h_->config().height, &pw, &ph, &bound), "ck_preview_color_layout");
+        return preview_files(frames.size(), 3 * (int64_t)pw * ph + 1024, bound, [&](uint8_t *out, int64_t cap, int64_t *sizes) {
+            check(ck_preview_jpeg_color_ingested(g_, slot, &pp, frames.data(), (int32_t)frames.size(), out, cap, sizes, nullptr),
+                  "ck_preview_jpeg_color_ingested");
+        });
+    }
 
   private:
     std::shared_ptr<Handle> h_;

@@ -406,7 +406,7 @@ int ck_estimate_tag_poses(ck_handle_t *h, const ck_tag_pose_params_t *pp, const 
  * holds no such call's result: no detect / process call since ck_create, a failed one, or a later call that rewrote the
  * workspace: ck_clusters_batch and ck_quads_batch.  ck_upload_frames, ck_upload_raw, ck_upload_raw_device, ck_raw_luma_batch, ck_threshold_batch, ck_segment_batch,
  * ck_quad_image_batch, ck_time_threshold_segment, ck_set_quad_sigma, ck_sqpnp_solve_batch, ck_gather_poses, ck_preview_jpeg,
- * ck_preview_luma, ck_exposure_stats, ck_exposure_stats_ingested, the ck_cat_*
+ * ck_preview_luma, the ck_preview_*color* calls, ck_exposure_stats, ck_exposure_stats_ingested, the ck_cat_*
  * and ck_ingest_write / ck_ingest_submit calls leave it as it is. */
 int ck_last_tag_poses(ck_handle_t *h, const ck_tag_pose_params_t *pp, ck_tag_pose_t *out, int32_t cap_per_frame,
                       int32_t *counts);
@@ -587,6 +587,52 @@ int ck_preview_jpeg(ck_handle_t *h, const ck_preview_params_t *pp, const int32_t
 /* The scaled (+ overlaid) pixels the encoder is given, out [n][ph][pw] (host or device pointer): for tests and for callers with
  * an encoder of their own.  quality and restart_rows are validated and otherwise unused.  Errors as ck_preview_jpeg. */
 int ck_preview_luma(ck_handle_t *h, const ck_preview_params_t *pp, const int32_t *frames, int32_t n, uint8_t *out);
+
+/* ---- the preview in colour, from the raw camera frames ---------------------------------------------------------------------
+ * The reference's stream is a colour picture (videoconvertscale to RGB, turbojpeg::compress(.., PixelFormat::RGB, 50,
+ * Subsamp::None): mjpeg.rs:41-49,108-118); the staged frames are luma, so the colour form reads the RAW frames they were made
+ * from, while those are still on the device.  DESIGN.md §4g is the contract.  Sources: the packed colour families of
+ * ck_raw_layout (YUYV / YUY2, UYVY, RGB3 / "RGB ", BGR3 / "BGR ", RGBA, BGRA); a luma-first family (GREY .. YV12) is
+ * CK_EUNSUPPORTED: its chroma never reaches the device, and ck_preview_jpeg serves it.  Per entry, with S the sh x sw source:
+ *   orient   O[y][x] = the triple (Y, Cb, Cr) of the source pixel the index maps of ck_raw_format_t name.  RGB families: libjpeg's
+ *            rgb_ycc_convert on R, G, B (alpha ignored), in 32-bit signed arithmetic:
+ *              Y  = (19595 R + 38470 G + 7471 B + 32768) >> 16          (the staged luma)
+ *              Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16
+ *              Cr = (32768 R - 27439 G - 5329 B + (128 << 16) + 32767) >> 16
+ *            4:2:2 families: the bytes unchanged, Y = the pixel's luma byte, (Cb, Cr) = the U, V bytes of its pair x >> 1;
+ *   scale    as ck_preview_jpeg, on O;
+ *   overlay  the mask of ck_preview_jpeg; where it is set the triple of RGB (0, 255, 0): (150, 44, 21);
+ *   encode   a three-component 4:4:4 interleaved baseline JPEG exactly as libjpeg writes it from YCbCr input: table 0 and the
+ *            luminance Huffman tables for Y, the chrominance tables for Cb and Cr, DRI = restart_rows * ceil(pw / 8) MCUs.
+ *            Pillow's save(quality, subsampling=0) of the RGB picture gives the same bytes.
+ * out, cap_per_frame, sizes, status, CK_PREVIEW_TRUNCATED, the errors and the on-demand workspace (three times the blocks) are
+ * ck_preview_jpeg's; `frames` indexes the RAW frames at hand.  No call touches the staged luma, the detection workspace or a ring
+ * slot. */
+/* ck_preview_layout with the colour file's upper bound.  Host only. */
+int ck_preview_color_layout(const ck_preview_params_t *pp, int32_t W, int32_t H, int32_t *pw, int32_t *ph, int64_t *max_bytes);
+/* From the raw frames the handle's last ck_upload_raw / ck_raw_luma_batch left in its raw staging.  Valid only while they are the
+ * handle's staged frames: after any call that stages frames another way (ck_upload_frames, ck_upload_jpeg*, ck_upload_raw_device,
+ * the *_batch calls given images, the *_device calls) CK_EINVAL.  CK_EUNSUPPORTED: that upload was of a luma-first family. */
+int ck_preview_jpeg_color(ck_handle_t *h, const ck_preview_params_t *pp, const int32_t *frames, int32_t n, uint8_t *out,
+                          int64_t cap_per_frame, int64_t *sizes, uint32_t *status);
+/* From n_frames raw frames in the caller's device memory, laid out as ck_upload_raw_device takes them: any stride >= min_stride,
+ * frame_pitch >= stride * sh, any base alignment.  The work that produced them must have completed.  CK_EINVAL also for a null
+ * d_raw / fmt, n_frames < 0, a stride or pitch below the minimum, an orientation out of range; CK_EUNSUPPORTED: the fourcc. */
+int ck_preview_jpeg_color_device(ck_handle_t *h, const ck_preview_params_t *pp, const uint8_t *d_raw, int32_t stride,
+                                 int64_t frame_pitch, const ck_raw_format_t *fmt, const int32_t *frames, int32_t n_frames, int32_t n,
+                                 uint8_t *out, int64_t cap_per_frame, int64_t *sizes, uint32_t *status);
+/* From the raw twin of a submitted slot of a ck_ingest_create_raw ring (indices below the count the slot was submitted with; it is
+ * kept until the slot is submitted again).  Waits for the slot like ck_exposure_stats_ingested and leaves it as it is.
+ * CK_EUNSUPPORTED: a ring of ck_ingest_create or ck_ingest_create_jpeg. */
+int ck_preview_jpeg_color_ingested(ck_ingest_t *ing, int32_t slot, const ck_preview_params_t *pp, const int32_t *frames, int32_t n,
+                                   uint8_t *out, int64_t cap_per_frame, int64_t *sizes, uint32_t *status);
+/* The triples (Y, Cb, Cr) the encoder is given, out [n][ph][pw][3] (host or device pointer), in the same three forms: for tests
+ * and for callers with an encoder of their own.  quality and restart_rows are validated and otherwise unused. */
+int ck_preview_color(ck_handle_t *h, const ck_preview_params_t *pp, const int32_t *frames, int32_t n, uint8_t *out);
+int ck_preview_color_device(ck_handle_t *h, const ck_preview_params_t *pp, const uint8_t *d_raw, int32_t stride, int64_t frame_pitch,
+                            const ck_raw_format_t *fmt, const int32_t *frames, int32_t n_frames, int32_t n, uint8_t *out);
+int ck_preview_color_ingested(ck_ingest_t *ing, int32_t slot, const ck_preview_params_t *pp, const int32_t *frames, int32_t n,
+                              uint8_t *out);
 
 /* ---- exposure metering of the staged frames on the device ---------------------------------------------------------------
  * The camera-side loop the reference leaves open (Camera.auto_exposure / manual_exposure, crates/chalkydri_core/src/config.rs:64-65;
