@@ -119,6 +119,18 @@ class ExposureParams(C.Structure):
                 ("e_min", C.c_double), ("e_max", C.c_double)]
 
 
+CK_TRI_MAX_ROUNDS, CK_TRI_FLAT = 32, 1
+
+
+class TriOtsuParams(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("max_iters", "min_delta", "keep_tbd", "channels")]
+
+
+class TriOtsuInfo(C.Structure):
+    _fields_ = [("n_rounds", C.c_int32), ("T", C.c_int32 * CK_TRI_MAX_ROUNDS), ("T_last", C.c_int32), ("lo_final", C.c_int32),
+                ("hi_final", C.c_int32), ("n_black", C.c_uint32), ("n_white", C.c_uint32), ("n_other", C.c_uint32), ("flags", C.c_uint32)]
+
+
 class VisionMeasurement(C.Structure):
     _fields_ = [("pose_x", C.c_double), ("pose_y", C.c_double), ("pose_rot", C.c_double),
                 ("std_x", C.c_double), ("std_y", C.c_double), ("std_rot", C.c_double), ("ts", C.c_uint64),
@@ -152,6 +164,7 @@ assert C.sizeof(JpegFrame) == 16 and C.sizeof(JpegInfo) == 32
 assert C.sizeof(RawFormat) == 8
 assert C.sizeof(PreviewParams) == 24
 assert C.sizeof(Rect) == 16 and C.sizeof(ExposureStats) == 6416 and C.sizeof(ExposureParams) == 96
+assert C.sizeof(TriOtsuParams) == 16 and C.sizeof(TriOtsuInfo) == 160
 
 # per-frame status bits (include/chalkydri_hip.h)
 CK_FRAME_OK, CK_FRAME_POINTS_OVERFLOW, CK_FRAME_CLUSTERS_OVERFLOW, CK_FRAME_QUADS_OVERFLOW, CK_FRAME_DETS_OVERFLOW = 0, 1, 2, 4, 8

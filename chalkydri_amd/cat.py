@@ -3,11 +3,15 @@
 Keeps the reference's surface: new(width, height, valid_tags), calc_otsu, thresh, process_frame, detect_corners,
 check_edges, connected_components -> UnionFind{find, get_size} (src/lib.rs:42-113,158-181,191,265,291,319,480,501).
 State lives where the reference keeps it: the class buffer, the corner points and the checked lines.
+
+Beyond the reference: tri_otsu / tri_otsu_batch / tri_otsu_solve, the iterative tri-class Otsu threshold its design document asks
+for (book/src/maintenance/apriltags.md:33), producing the same three classes.
 """
 import ctypes as C
 
 import numpy as np
 
+from . import _abi as A
 from ._lib import check, default_config, lib
 from .detector import AprilTagDetector, _bind
 
@@ -21,6 +25,8 @@ def grayscale(r, g, b):
     k = np.float32(0.33)
     inner = np.float32(np.float64(np.float32(g)) * np.float64(k) + np.float64(np.float32(b) * k))   # single rounding = fmaf
     outer = np.float32(np.float64(np.float32(r)) * np.float64(k) + np.float64(inner))
+    if np.ndim(outer):   # arrays of channels: the same map, element by element, as uint8
+        return np.clip(np.trunc(outer), 0.0, 255.0).astype(np.uint8)
     return int(min(255.0, max(0.0, np.trunc(outer))))
 
 
@@ -75,6 +81,38 @@ class UnionFind:
         return int(self._sizes[i])
 
 
+# ---- iterative tri-class Otsu threshold -------------------------------------------------------------------
+TRI_INFO_DTYPE = np.dtype([("n_rounds", "<i4"), ("T", "<i4", (A.CK_TRI_MAX_ROUNDS,)), ("T_last", "<i4"), ("lo_final", "<i4"),
+                           ("hi_final", "<i4"), ("n_black", "<u4"), ("n_white", "<u4"), ("n_other", "<u4"), ("flags", "<u4")])
+assert TRI_INFO_DTYPE.itemsize == C.sizeof(A.TriOtsuInfo)
+
+
+def tri_otsu_params(max_iters=None, min_delta=None, keep_tbd=None, channels=None):
+    """ck_tri_otsu_params_t: max_iters 1..32 (8), min_delta 1..255 (1: stop when T repeats), keep_tbd 0 / 1 (1: the final interval
+    stays Other), channels 1 or 3 (3).  None keeps the library's default."""
+    p = A.TriOtsuParams()
+    _bind(lib()).ck_tri_otsu_params_default(C.byref(p))
+    for name, v in (("max_iters", max_iters), ("min_delta", min_delta), ("keep_tbd", keep_tbd), ("channels", channels)):
+        if v is not None:
+            setattr(p, name, int(v))
+    return p
+
+
+def tri_otsu_solve(hist, **params):
+    """ck_tri_otsu_solve: (record, lut[256]) of one 256-bin histogram, on the host (no device needed)."""
+    hist = np.ascontiguousarray(hist, np.uint32).reshape(-1)
+    if hist.size != 256:
+        raise ValueError("a histogram has 256 bins")
+    info, lut, p = np.zeros((), TRI_INFO_DTYPE), np.zeros(256, np.uint8), tri_otsu_params(**params)
+    check(_bind(lib()).ck_tri_otsu_solve(C.byref(p), hist.ctypes.data, C.cast(info.ctypes.data, C.POINTER(A.TriOtsuInfo)), lut.ctypes.data),
+          "ck_tri_otsu_solve")
+    return info, lut
+
+
+def _is_tensor(a):
+    return hasattr(a, "data_ptr") and hasattr(a, "is_cuda")
+
+
 class CatDetector:
     def __init__(self, width, height, valid_tags=(), device=0):
         self.width, self.height, self.valid_tags, self.device = width, height, tuple(valid_tags), device
@@ -95,6 +133,45 @@ class CatDetector:
         rgb = np.ascontiguousarray(rgb, np.uint8)
         check(self._L.ck_cat_calc_otsu(self._det._h, rgb.ctypes.data, self.width, self.height, self.buf.ctypes.data), "ck_cat_calc_otsu")
         return self.buf
+
+    def tri_otsu(self, rgb, **params):
+        """Iterative tri-class Otsu of one frame [h][w][3] (or [h][w] with channels=1) in calc_otsu's place: the classes become the
+        detector's class map, so detect_corners / check_edges / connected_components / draw follow.  The frame's record is kept
+        in self.tri_info."""
+        rgb = np.ascontiguousarray(rgb, np.uint8)
+        params.setdefault("channels", 1 if rgb.ndim == 2 else 3)
+        if rgb.size != self.width * self.height * params["channels"]:
+            raise ValueError("input is not width*height*channels bytes")
+        cls, infos, _ = self.tri_otsu_batch(rgb.reshape(1, self.height, self.width, -1), **params)
+        self.buf[...] = cls[0]
+        self.tri_info = infos[0]
+        return self.buf
+
+    def tri_otsu_batch(self, frames, **params):
+        """ck_cat_tri_otsu_batch: frames [n][h][w][c] (or [n][h][w], one channel) of any geometry -> (classes [n][h][w], one record
+        per frame, hists [n][256]).  numpy arrays in, numpy arrays out; a torch tensor on the detector's device is read in place
+        and the three results are tensors there (the records as [n][40] int32)."""
+        if frames.ndim not in (3, 4):
+            raise ValueError("frames are [n][h][w][c] or [n][h][w]")
+        n, ht, w = (int(v) for v in frames.shape[:3])
+        params.setdefault("channels", 1 if frames.ndim == 3 else int(frames.shape[3]))
+        p = tri_otsu_params(**params)
+        if frames.ndim == 4 and frames.shape[3] != p.channels:
+            raise ValueError("frames do not have `channels` bytes per pixel")
+        if _is_tensor(frames):
+            import torch
+            frames = frames.contiguous()
+            cls = torch.empty((n, ht, w), dtype=torch.uint8, device=frames.device)
+            infos = torch.empty((n, TRI_INFO_DTYPE.itemsize // 4), dtype=torch.int32, device=frames.device)
+            hists = torch.empty((n, 256), dtype=torch.int32, device=frames.device)
+            ptrs = frames.data_ptr(), cls.data_ptr(), infos.data_ptr(), hists.data_ptr()
+            torch.cuda.synchronize(frames.device)   # (the library works on its own stream)
+        else:
+            frames = np.ascontiguousarray(frames, np.uint8)
+            cls, infos, hists = np.zeros((n, ht, w), np.uint8), np.zeros(n, TRI_INFO_DTYPE), np.zeros((n, 256), np.uint32)
+            ptrs = frames.ctypes.data, cls.ctypes.data, infos.ctypes.data, hists.ctypes.data
+        check(self._L.ck_cat_tri_otsu_batch(self._det._h, C.byref(p), ptrs[0], n, w, ht, ptrs[1], ptrs[2], ptrs[3]), "ck_cat_tri_otsu_batch")
+        return cls, infos, hists
 
     def thresh(self, rgb):
         rgb = np.ascontiguousarray(rgb, np.uint8)

@@ -217,6 +217,8 @@ struct ck_handle {
     struct ck_preview_ws *preview;
     // exposure metering of the staged frames (ck_exposure.hip, k_exposure.hip): allocated by the first exposure call, grown on demand
     struct ck_exposure_ws *exposure;
+    // iterative tri-class Otsu threshold (ck_tri_otsu.hip, k_tri_otsu.hip): allocated by the first tri-class call, grown on demand
+    struct ck_tri_otsu_ws *tri_otsu;
     bool fmerge_lds_allowed; // k_fmerge's dynamic LDS limit has been raised on this handle's device
 };
 
@@ -403,6 +405,15 @@ __device__ __forceinline__ int wave_min_i32(int x) { // same DPP ladder with min
     x = min(x, __builtin_amdgcn_update_dpp(x, x, 0x142, 0xA, 0xF, false));
     x = min(x, __builtin_amdgcn_update_dpp(x, x, 0x143, 0xC, 0xF, false));
     return __builtin_amdgcn_readlane(x, 63);
+}
+
+// CAT's gray level of an RGB pixel (utils.rs:33-46): trunc(fma(r, 0.33f, fma(g, 0.33f, b * 0.33f))) in f32, saturating.  The one
+// map of k_cat.hip and k_tri_otsu.hip.
+__device__ __forceinline__ uint8_t ck_cat_grayscale(uint8_t r, uint8_t g, uint8_t b) {
+    float v = __fmaf_rn((float)r, 0.33f, __fmaf_rn((float)g, 0.33f, (float)b * 0.33f));
+    if (!(v > 0.0f)) return 0;
+    if (v >= 255.0f) return 255;
+    return (uint8_t)v;
 }
 
 #endif // __HIPCC__

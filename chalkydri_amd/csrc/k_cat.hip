@@ -21,12 +21,7 @@ namespace {
 enum { BLACK = 0, WHITE = 1, OTHER = 2 };
 constexpr int NT = 256;
 
-__device__ __forceinline__ uint8_t grayscale(uint8_t r, uint8_t g, uint8_t b) { // utils.rs:33-46
-    float v = __fmaf_rn((float)r, 0.33f, __fmaf_rn((float)g, 0.33f, (float)b * 0.33f));
-    if (!(v > 0.0f)) return 0;
-    if (v >= 255.0f) return 255;
-    return (uint8_t)v;
-}
+__device__ __forceinline__ uint8_t grayscale(uint8_t r, uint8_t g, uint8_t b) { return ck_cat_grayscale(r, g, b); } // utils.rs:33-46
 __device__ __forceinline__ uint8_t f64_as_u8(double v) {
     if (!(v > 0.0)) return 0;
     if (v >= 255.0) return 255;

@@ -101,6 +101,12 @@ def _bind(L):
     L.ck_exposure_recommend.argtypes = [ep, es, C.c_double, _P(C.c_double), _P(C.c_double)]
     L.ck_exposure_stats.argtypes = [vp, vp, i32, ep, vp, vp]
     L.ck_exposure_stats_ingested.argtypes = [vp, i32, vp, i32, ep, vp, vp]
+    tp = _P(A.TriOtsuParams)
+    L.ck_tri_otsu_params_default.argtypes = [tp]
+    L.ck_tri_otsu_params_default.restype = None
+    L.ck_tri_otsu_solve.argtypes = [tp, vp, _P(A.TriOtsuInfo), vp]
+    L.ck_cat_tri_otsu_batch.argtypes = [vp, tp, vp, i32, i32, i32, vp, vp, vp]
+    L.ck_cat_tri_otsu.argtypes = [vp, vp, i32, i32, vp]
     L._ck_bound = True
     return L
 

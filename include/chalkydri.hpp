@@ -361,6 +361,23 @@ class ExposureController {
     double exposure_, gamma_hat_ = 1.0;
 };
 
+// ---- iterative tri-class Otsu threshold (chalkydri_hip.h: ck_tri_otsu_solve / ck_cat_tri_otsu_batch) -------------
+inline ck_tri_otsu_params_t tri_otsu_params() {
+    ck_tri_otsu_params_t p;
+    ck_tri_otsu_params_default(&p);
+    return p;
+}
+struct TriOtsu {
+    ck_tri_otsu_info_t info;
+    std::array<uint8_t, 256> lut; // Color of every gray level
+};
+// The record and the table of one 256-bin histogram, on the host (no device needed)
+inline TriOtsu tri_otsu_solve(const std::array<uint32_t, 256> &hist, const ck_tri_otsu_params_t &p = tri_otsu_params()) {
+    TriOtsu r;
+    check(ck_tri_otsu_solve(&p, hist.data(), &r.info, r.lut.data()), "ck_tri_otsu_solve");
+    return r;
+}
+
 namespace apriltags {
 
 enum class Color : uint8_t { Black = 0, White = 1, Other = 2 }; // src/utils.rs:2-6
@@ -459,6 +476,14 @@ class Detector {
     void calc_otsu(std::vector<uint8_t> &input) {
         need_rgb(input.size());
         check(ck_cat_calc_otsu(h_->get(), input.data(), (int)width_, (int)height_, buf_.data()), "ck_cat_calc_otsu");
+    }
+    // The threshold the CAT design document asks for (book/src/maintenance/apriltags.md:33) in calc_otsu's place: iterative
+    // tri-class Otsu of the frame's gray levels.  `input` is [h][w][p.channels]; returns the frame's record.
+    ck_tri_otsu_info_t tri_otsu(const std::vector<uint8_t> &input, const ck_tri_otsu_params_t &p = tri_otsu_params()) {
+        if (input.size() != width_ * height_ * (size_t)p.channels) throw Panic("input is not width*height*channels bytes", CK_EINVAL);
+        ck_tri_otsu_info_t info;
+        check(ck_cat_tri_otsu_batch(h_->get(), &p, input.data(), 1, (int)width_, (int)height_, buf_.data(), &info, nullptr), "ck_cat_tri_otsu_batch");
+        return info;
     }
     // lib.rs:319-334
     void thresh(const std::vector<uint8_t> &input) {

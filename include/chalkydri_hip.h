@@ -261,6 +261,52 @@ int ck_cat_process_frame(ck_handle_t *h, const uint8_t *rgb, size_t rgb_len, int
                          int32_t height, uint8_t *classes_out, uint32_t *points_xy, int32_t point_cap,
                          int32_t *n_points, uint32_t *lines_xyxy, int32_t line_cap, int32_t *n_lines);
 
+/* ---- CAT: iterative tri-class Otsu threshold, batched -------------------------------------------------------------------
+ * The threshold the CAT design document asks for (book/src/maintenance/apriltags.md:33), after Cai, Yang, Cao, Xia and Xu,
+ * "A new iterative triclass thresholding technique in image segmentation" (IEEE TIP 2014), restated in integers; DESIGN.md §4h is
+ * the contract.  Per frame: hist[g] counts the pixels of gray level g = grayscale(r, g, b) (utils.rs:33-46; a 1-channel pixel v is
+ * grayscale(v, v, v)).  The state is an inclusive interval [lo, hi] = [0, 255] of levels still to be determined.  Round k:
+ *   1. N = sum hist[g], S = sum g hist[g] over [lo, hi] (int64); fewer than two occupied levels there: stop, no threshold
+ *   2. T_k = the smallest t in lo..hi-1 with the strictly greatest v(t) = (d d) / ((double)n (double)(N - n)), d = (double)(S n - N s),
+ *      n = sum_{g<=t} hist[g], s = sum_{g<=t} g hist[g] inside the interval, among the t with n > 0 and N - n > 0; two
+ *      multiplications and one division in double, in that order, not contracted; S n - N s in 64-bit two's complement
+ *   3. lo' = ceil(s / n), hi' = floor((S - s) / (N - n)) at t = T_k: levels below the lower class mean are Black, above the upper White
+ *   4. k >= 2 and |T_k - T_{k-1}| < min_delta: adopt [lo', hi'] and stop; k == max_iters: adopt and stop; lo' > hi': stop without
+ *      adopting; otherwise adopt and go on
+ * lut[g]: Black below lo_final, White above hi_final; inside the final interval Other (keep_tbd = 1) or Black up to T_last and White
+ * above it (keep_tbd = 0).  A frame with fewer than two occupied levels has no threshold: lut[g] = g < 128 ? Black : White for both
+ * values of keep_tbd, n_rounds 0, T_last -1, the interval [0, 255], CK_TRI_FLAT set. */
+#define CK_TRI_MAX_ROUNDS 32
+#define CK_TRI_FLAT 1 /* ck_tri_otsu_info_t.flags: fewer than two occupied gray levels */
+typedef struct ck_tri_otsu_params {
+    int32_t max_iters; /* 1..32, default 8 */
+    int32_t min_delta; /* 1..255, default 1: stop when T repeats */
+    int32_t keep_tbd;  /* 0 / 1, default 1 */
+    int32_t channels;  /* 1 or 3, default 3 */
+} ck_tri_otsu_params_t;
+typedef struct ck_tri_otsu_info {
+    int32_t n_rounds;                     /* rounds that produced a threshold */
+    int32_t T[CK_TRI_MAX_ROUNDS];         /* T_1 .. T_n_rounds, -1 past the end */
+    int32_t T_last, lo_final, hi_final;
+    uint32_t n_black, n_white, n_other;   /* sum of hist[g] over the levels of each class */
+    uint32_t flags;
+} ck_tri_otsu_info_t;
+void ck_tri_otsu_params_default(ck_tri_otsu_params_t *p);
+/* Host arithmetic, no device needed: the record and the table lut[256] of one histogram hist[256].  CK_EINVAL: a null pointer, a
+ * parameter out of range. */
+int ck_tri_otsu_solve(const ck_tri_otsu_params_t *p, const uint32_t *hist, ck_tri_otsu_info_t *info, uint8_t *lut);
+/* n dense frames px [n][height][width][channels] -> classes_out [n][height][width] on the handle's stream: a histogram pass, one
+ * wave per frame that produces exactly the bytes of ck_tri_otsu_solve, and a look-up pass.  info_out [n] and hist_out [n][256] may
+ * be NULL.  Every pointer may be a host or a device pointer; arrays on the handle's device are used in place.  n is not bound to
+ * max_batch and the geometry not to the handle's; the staged frames and the detection workspace stay as they are.  Returns when the
+ * outputs are complete.  CK_EINVAL: a null h, p, px or classes_out, n < 0, width or height < 1, width * height >= 2^31, a parameter
+ * out of range.  CK_ENOMEM: the workspace (allocated by the first call, grown on demand; ck_create allocates none of it) could not
+ * grow. */
+int ck_cat_tri_otsu_batch(ck_handle_t *h, const ck_tri_otsu_params_t *p, const uint8_t *px, int32_t n, int32_t width, int32_t height,
+                          uint8_t *classes_out, ck_tri_otsu_info_t *info_out, uint32_t *hist_out);
+/* One RGB8 frame with the default parameters: drops into the place of ck_cat_calc_otsu. */
+int ck_cat_tri_otsu(ck_handle_t *h, const uint8_t *rgb, int32_t width, int32_t height, uint8_t *classes_out);
+
 /* ---- SQPnP ------------------------------------------------------------------------------------------ */
 /* Isometry = translation + unit quaternion (w,x,y,z), matching nalgebra's Isometry3<f64> content. */
 typedef struct ck_iso3 {
@@ -407,7 +453,7 @@ int ck_estimate_tag_poses(ck_handle_t *h, const ck_tag_pose_params_t *pp, const 
  * workspace: ck_clusters_batch and ck_quads_batch.  ck_upload_frames, ck_upload_raw, ck_upload_raw_device, ck_raw_luma_batch, ck_threshold_batch, ck_segment_batch,
  * ck_quad_image_batch, ck_time_threshold_segment, ck_set_quad_sigma, ck_sqpnp_solve_batch, ck_gather_poses, ck_preview_jpeg,
  * ck_preview_luma, the ck_preview_*color* calls, ck_exposure_stats, ck_exposure_stats_ingested, the ck_cat_*
- * and ck_ingest_write / ck_ingest_submit calls leave it as it is. */
+ * calls (ck_cat_tri_otsu and ck_cat_tri_otsu_batch among them) and the ck_ingest_write / ck_ingest_submit calls leave it as it is. */
 int ck_last_tag_poses(ck_handle_t *h, const ck_tag_pose_params_t *pp, ck_tag_pose_t *out, int32_t cap_per_frame,
                       int32_t *counts);
 

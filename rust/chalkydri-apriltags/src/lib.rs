@@ -112,6 +112,22 @@ impl Detector {
     pub fn calc_otsu(&mut self, input: &mut [u8]) {
         check(unsafe { sys::ck_cat_calc_otsu(self.h, input.as_ptr(), self.width as i32, self.height as i32, self.classes.as_mut_ptr()) }, "ck_cat_calc_otsu");
     }
+    /// Not in the reference crate: the threshold its design document asks for (book/src/maintenance/apriltags.md:33),
+    /// iterative tri-class Otsu of an RGB frame's gray levels with the library's default parameters.  Takes `calc_otsu`'s
+    /// place in `process_frame` (lib.rs:271): the classes land in the same buffer, so `detect_corners` / `check_edges` follow.
+    pub fn tri_otsu(&mut self, input: &[u8]) {
+        assert_eq!(input.len(), self.width * self.height * 3);
+        check(unsafe { sys::ck_cat_tri_otsu(self.h, input.as_ptr(), self.width as i32, self.height as i32, self.classes.as_mut_ptr()) }, "ck_cat_tri_otsu");
+    }
+    /// The same with parameters (`sys::ck_tri_otsu_params_t`; `channels` 1 takes a mono8 frame); returns the frame's record.
+    pub fn tri_otsu_with(&mut self, input: &[u8], params: &sys::ck_tri_otsu_params_t) -> sys::ck_tri_otsu_info_t {
+        assert_eq!(input.len(), self.width * self.height * params.channels as usize);
+        let mut info = unsafe { std::mem::zeroed::<sys::ck_tri_otsu_info_t>() };
+        check(unsafe {
+            sys::ck_cat_tri_otsu_batch(self.h, params, input.as_ptr(), 1, self.width as i32, self.height as i32, self.classes.as_mut_ptr(), &mut info, std::ptr::null_mut())
+        }, "ck_cat_tri_otsu_batch");
+        info
+    }
     /// lib.rs:265-287 (asserts the buffer length like the reference's `assert_eq!`, lib.rs:267)
     pub fn process_frame(&mut self, input: &[u8]) {
         assert_eq!(input.len(), self.width * self.height * 3);
