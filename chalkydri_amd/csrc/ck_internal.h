@@ -61,7 +61,7 @@ struct ck_dev_family {
 // point, so the small ones run on small workgroups, many per CU)
 constexpr int CK_FIT_CLASSES = 8;
 constexpr int CK_FIT_LISTS = 9;    // work lists: one per size class + (index 8) every cluster of the batch, which the tail kernel of the split fit walks
-// The split quad fit (k_quads.hip: k_fit<..., SPLIT> -> k_chunk -> k_tail) passes a cluster's sorted, de-duplicated points on as an
+// The split quad fit (k_quads.hip: k_seq -> k_chunk -> k_tail) passes a cluster's sorted, de-duplicated points on as an
 // EXTENDED sequence: its last CK_EXT_PRE points, the points, its first CK_EXT_POST points again — so that the windowed line-fit
 // error, its smoothing and the maxima test of every point read neighbours at plain offsets and a kernel can stream over all
 // clusters of a frame without knowing where one ends.  A cluster's place in the frame's sequence is handed out when it gets there
@@ -86,6 +86,11 @@ __host__ __device__ inline ck_cluster_point_t ck_unpack_point(ck_packed_point v)
     p.x = (uint16_t)((v >> 16) & 0x1FFFu); p.y = (uint16_t)((v >> 3) & 0x1FFFu);
     p.gx = (int8_t)(dx * sgn); p.gy = (int8_t)(dy * sgn); p.pad = 0;
     return p;
+}
+// The same fields in one word, the staged form the quad fit's sort reads: x | y << 16 | (u8)gx << 32 | (u8)gy << 40
+__host__ __device__ __forceinline__ unsigned long long ck_stage_point(ck_packed_point v) {
+    const ck_cluster_point_t p = ck_unpack_point(v);
+    return (unsigned long long)p.x | ((unsigned long long)p.y << 16) | ((unsigned long long)(uint8_t)p.gx << 32) | ((unsigned long long)(uint8_t)p.gy << 40);
 }
 // One (tile, cluster) run of boundary points in the temp array
 struct ck_run {
@@ -244,11 +249,9 @@ int ck_hip_failed(hipError_t e, const char *call, const char *file, int line, bo
 static inline int ck_knob_(const char *name, int dflt, int base) { const char *e = getenv(name); return e ? (int)strtol(e, nullptr, base) : dflt; }
 #define CK_KNOB(name, dflt) ck_knob_(name, dflt, 10)
 #define CK_KNOB0(name, dflt) ck_knob_(name, dflt, 0)   /* hexadecimal masks allowed */
-#define CK_KNOB_SET(name) (getenv(name) != nullptr)
 #else
 #define CK_KNOB(name, dflt) (dflt)
 #define CK_KNOB0(name, dflt) (dflt)
-#define CK_KNOB_SET(name) (false)
 #endif
 int ck_streams_wanted(); // ck_stages.hip: CK_STREAMS (1 or 2), read once
 

@@ -59,7 +59,7 @@ static constexpr ck_buf_desc ck_bufs[] = {
     CK_BUF(ws.d_runs, CK_BUF_FRAME, w.run_cap * sizeof(ck_run)),
     CK_BUF(ws.d_lscratch, CK_BUF_TWIN, sizeof(unsigned long long) * CK_LSCRATCH_PER_WG * CK_LSCRATCH_WGS),
     // (1920 x 1080: 18 432 points, 144 MiB instead of the 512 MiB of the class's template capacity)
-    CK_BUF(ws.d_hscratch, CK_BUF_TWIN, w.max_cluster_points > 16384 || CK_KNOB_SET("CK_FIT_GK") ? sizeof(unsigned long long) * 2 * w.hcap * CK_HUGE_WGS : 0),
+    CK_BUF(ws.d_hscratch, CK_BUF_TWIN, w.max_cluster_points > 16384 ? sizeof(unsigned long long) * 2 * w.hcap * CK_HUGE_WGS : 0),
     CK_BUF(ws.d_clusters, CK_BUF_FRAME, w.cluster_cap * sizeof(ck_cluster_t)),
     CK_BUF(ws.d_counters, CK_BUF_FRAME, CK_CNT_STRIDE * sizeof(uint32_t)),
     CK_BUF(ws.d_quads, CK_BUF_FRAME, w.quad_cap * sizeof(ck_quad_t)),
@@ -140,7 +140,6 @@ static int stage_caps(ck_handle *h) {
     }
     ws.run_cap = 4 * ws.cluster_cap;
     ws.hcap = (ws.max_cluster_points + 1023) & ~1023;
-    if (ws.hcap < 16384 && CK_KNOB_SET("CK_FIT_GK")) ws.hcap = 16384;
     // fit scratch: one work list per size class + counters, then the decode candidates
     size_t list_bytes = ((size_t)CK_FIT_LISTS * ws.cluster_cap * nb + 32) * sizeof(uint32_t);
     size_t cand_bytes = 256 + ((nb * 4 + 255) / 256) * 256 + sizeof(ck_detection_t) * (size_t)ws.quad_cap * cfg.n_families * nb;

@@ -25,6 +25,8 @@
 // rest from a dequeue counter.  The phases can be cut short for measurements with CK_FIT_STOP_AFTER (tools/ablate_fit.sh).
 #include <stdlib.h>
 
+#include <utility>
+
 #include "ck_internal.h"
 
 namespace {
@@ -572,6 +574,136 @@ __device__ __forceinline__ long long keys_bucket_sort_global(unsigned long long 
     return dot;
 }
 
+// ---- the front half of the fit (phases 1-2), one text for k_fit and k_seq ---------------------------------------------------------------
+// The two kernels differ in where a cluster's points come from (rawp: loaded by k_fit, prefetched during the cluster before by k_seq)
+// and in the barrier between the phases, BAR::sync(): k_fit's carries the workgroup fence, k_seq's orders LDS traffic only where one
+// wave is the workgroup — a fence there would wait for the prefetch (see lds_barrier above).
+struct FenceBarrier { __device__ __forceinline__ static void sync() { __syncthreads(); } };
+constexpr int RAWP_MAX = 16;    // a thread holds its share of a cluster's packed points in registers up to this many
+struct Box { int xmin, xmax, ymin, ymax; };
+
+// chunked dequeue from a class work list: clusters per chunk (a quarter of a workgroup's share, 1..dqmax — a short list, one frame
+// per call, is handed out one cluster at a time so that it still spreads over the whole grid), and the guided size of the chunk
+// after the one at `base`: the chunks shrink towards the end of the list, so the launch's tail is one cluster, not one chunk
+__device__ __forceinline__ uint32_t dq_chunk(uint32_t n_work, uint32_t dqmax) {
+    const uint32_t per_wg4 = n_work / (gridDim.x * 4u);
+    return per_wg4 < 1u ? 1u : (per_wg4 > dqmax ? dqmax : per_wg4);
+}
+__device__ __forceinline__ uint32_t dq_guided(uint32_t n_work, uint32_t base, uint32_t dq) {
+    const uint32_t g = base < n_work ? (n_work - base) / (gridDim.x * 2u) : 0u;
+    return g < 1u ? 1u : (g > dq ? dq : g);
+}
+// The walk over the list, a chunk per step.  The first chunk of every workgroup is its own (no atomic: a launch with little or no work
+// — one frame per call, an empty class — must not queue thousands of adds on one address); the class counter hands out what lies
+// beyond those.  word: one LDS word that carries the counter's answer to the workgroup.
+template <uint32_t DQMAX, class BAR>
+struct ChunkQueue {
+    uint32_t n_work, dq, static_total, base, len, dq_next;
+    bool first;
+    __device__ __forceinline__ explicit ChunkQueue(const FitArgs &a) {
+        n_work = min(*a.list_count, (uint32_t)a.list_cap);
+        dq = dq_chunk(n_work, DQMAX);
+        static_total = gridDim.x * dq;
+        base = blockIdx.x * dq; len = dq; dq_next = dq;
+        first = true;
+    }
+    // the next chunk: entries base .. base + count() - 1 of the list; false when the list is used up
+    __device__ __forceinline__ bool next(const FitArgs &a, uint32_t *word) {
+        if (!first) {
+            if (static_total >= n_work) return false;
+            BAR::sync();
+            if (threadIdx.x == 0) *word = static_total + atomicAdd(a.head, dq_next);
+            BAR::sync();
+            base = *word;
+            len = dq_next;
+            if (a.guided) dq_next = dq_guided(n_work, base, dq);
+        }
+        first = false;
+        return base < n_work;
+    }
+    __device__ __forceinline__ int count() const { return (int)min(len, n_work - base); }
+};
+
+// 1. the packed points -> staged form in sKeys[0, sz0), and the bounding box (on every thread).  One coalesced pass; rawp holds the
+// thread's points tid, tid + NTH, ... when CAP / NTH <= RAWP_MAX (all of a lane's loads were issued before the first use: one
+// memory round trip), otherwise they are read from pts here.
+template <int NTH, int CAP>
+__device__ __forceinline__ Box front_box(const ck_packed_point (&rawp)[CAP / NTH <= RAWP_MAX ? CAP / NTH : 1], const ck_packed_point *pts, int sz0,
+                                         unsigned long long *sKeys, int *iscr) {
+    constexpr int EPL = CAP / NTH;
+    const int tid = threadIdx.x;
+    int xmin = 1 << 30, xmax = -(1 << 30), ymin = 1 << 30, ymax = -(1 << 30);
+    auto take = [&](int i, ck_packed_point v) {
+        const unsigned long long raw = ck_stage_point(v);
+        sKeys[i] = raw;
+        const int px = (int)(raw & 0xFFFF), py = (int)((raw >> 16) & 0xFFFF);
+        xmin = min(xmin, px); xmax = max(xmax, px);
+        ymin = min(ymin, py); ymax = max(ymax, py);
+    };
+    if constexpr (EPL <= RAWP_MAX) {
+#pragma unroll
+        for (int e = 0; e < EPL; e++) {
+            const int i = tid + e * NTH;
+            if (i < sz0) take(i, rawp[e]);
+        }
+    } else {
+        for (int i = tid; i < sz0; i += NTH) take(i, pts[i]);
+    }
+    int bb[4] = {xmin, -xmax, ymin, -ymax};
+    Block<NTH>::reduce_min4(bb, iscr);
+    return Box{bb[0], -bb[1], bb[2], -bb[3]};
+}
+
+// 2a. border direction and sort of the staged points: the bucketed rank sort, and for a cluster it leaves alone the bitonic network
+// with the keys-per-thread count that matches the cluster (padded to a power of two, at least one per thread).  Returns the
+// border-direction sum (on every thread); the keys are sorted unless its sign is one the families do not want (or !do_sort).
+template <int NTH, int CAP, bool MLDS, bool GK, class BAR>
+__device__ __forceinline__ long long front_sort(unsigned long long *sKeys, uint32_t *hist, long long *sScratch, unsigned long long *scratch8, int sz0,
+                                                const Box &b, int normal_ok, int reversed_ok, bool do_sort) {
+    constexpr int EPLS = CAP / NTH;
+    int n2 = NTH;
+    while (n2 < sz0) n2 <<= 1;
+    const int epl = n2 / NTH;
+    BAR::sync(); // raw points staged by other threads
+    bool sorted = false;
+    long long dot;
+    if constexpr (MLDS) // keys fit in registers (CAP / NTH <= 16)
+        dot = keys_bucket_sort<NTH, EPLS>(sKeys, hist, sScratch, sz0, b.xmin, b.xmax, b.ymin, b.ymax, normal_ok, reversed_ok, do_sort, &sorted);
+    else
+        dot = keys_bucket_sort_global<NTH, GK>(sKeys, hist, sScratch, scratch8, sz0, b.xmin, b.xmax, b.ymin, b.ymax, normal_ok, reversed_ok, do_sort, &sorted);
+    if (sorted || GK) {}
+    else if (EPLS >= 32 && epl == 32) dot = keys_sort<NTH, (EPLS >= 32 && !GK ? 32 : 1)>(sKeys, sScratch, sz0, b.xmin, b.xmax, b.ymin, b.ymax, normal_ok, reversed_ok, do_sort);
+    else if (EPLS >= 16 && epl == 16) dot = keys_sort<NTH, (EPLS >= 16 && !GK ? 16 : 1)>(sKeys, sScratch, sz0, b.xmin, b.xmax, b.ymin, b.ymax, normal_ok, reversed_ok, do_sort);
+    else if (EPLS >= 8 && epl == 8) dot = keys_sort<NTH, (EPLS >= 8 && !GK ? 8 : 1)>(sKeys, sScratch, sz0, b.xmin, b.xmax, b.ymin, b.ymax, normal_ok, reversed_ok, do_sort);
+    else if (EPLS >= 4 && epl == 4) dot = keys_sort<NTH, (EPLS >= 4 && !GK ? 4 : 1)>(sKeys, sScratch, sz0, b.xmin, b.xmax, b.ymin, b.ymax, normal_ok, reversed_ok, do_sort);
+    else if (EPLS >= 2 && epl == 2) dot = keys_sort<NTH, (EPLS >= 2 && !GK ? 2 : 1)>(sKeys, sScratch, sz0, b.xmin, b.xmax, b.ymin, b.ymax, normal_ok, reversed_ok, do_sort);
+    else dot = keys_sort<NTH, 1>(sKeys, sScratch, sz0, b.xmin, b.xmax, b.ymin, b.ymax, normal_ok, reversed_ok, do_sort);
+    return dot;
+}
+
+// 2b. duplicate removal, packing to (x, y): returns the number of points left, u32 x << 13 | y each, in the first half of the key
+// buffer.  The compaction writes at index <= i: a round only overwrites bytes below 4 * (base + NTH) while unread keys start at
+// byte 8 * (base + NTH).  (The caller's barrier stands between the sort and this.)
+template <int NTH, class BAR>
+__device__ __forceinline__ int front_pack(unsigned long long *sKeys, int sz0, int *iscr) {
+    const int tid = threadIdx.x;
+    uint32_t *sXY = reinterpret_cast<uint32_t *>(sKeys);
+    int sz = 0;
+    for (int base = 0; base < sz0; base += NTH) {
+        const int i = base + tid;
+        unsigned long long key = 0;
+        int keep = 0;
+        if (i < sz0) { key = sKeys[i]; keep = (i == 0) || (sKeys[i - 1] != key); }
+        int tot = 0;
+        const int incl = Block<NTH>::scan_flag(keep, iscr, &tot);
+        BAR::sync();
+        if (keep) sXY[sz + (int)incl - 1] = (uint32_t)(key & 0x3FFFFFFu);
+        sz += (int)tot;
+        BAR::sync();
+    }
+    return sz;
+}
+
 // NTH threads per cluster, up to CAP points, chunks of CH points; MLDS: the maxima list fits in LDS; GK: the per-point arrays
 // (keys, then coordinates and weights) live in a per-workgroup slice of global memory instead of LDS (the largest class)
 template <int NTH, int CAP, int CH, bool MLDS, int WPS, bool GK = false>
@@ -629,13 +761,11 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(WPS, 8))) v
     // the small class (520 k clusters per batch through one counter cost more than any phase of the fit), static striding
     // leaves the slowest workgroup ~25 % behind the average (the sum of ~100 clusters' work still varies that much); a
     // chunk keeps the counter traffic at a few thousand adds per launch and the tail at one chunk.
+    // (The arithmetic is ChunkQueue's; the walk is this kernel's own: cluster by cluster, the one barrier at the head of the loop
+    // serves the dequeue as well.)
     const uint32_t n_work = min(*a.list_count, (uint32_t)a.list_cap);
-    // A short list (one frame per call) is handed out one cluster at a time so that it still spreads over the whole grid.
     constexpr uint32_t DQMAX = CAP <= 512 ? 16u : (CAP <= 2048 ? 4u : 1u);
-    const uint32_t per_wg4 = n_work / (gridDim.x * 4u);
-    const uint32_t DQ = per_wg4 < 1u ? 1u : (per_wg4 > DQMAX ? DQMAX : per_wg4);
-    // The first chunk of every workgroup is its own (no atomic: a launch with little or no work — one frame per call, an empty
-    // class — must not queue thousands of adds on one address); the counter hands out what lies beyond those.
+    const uint32_t DQ = dq_chunk(n_work, DQMAX);
     const uint32_t static_total = gridDim.x * DQ;
     uint32_t chunk_base = blockIdx.x * DQ, chunk_left = DQ, chunk_len = DQ, dq_next = DQ;
     for (;;) {
@@ -647,10 +777,7 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(WPS, 8))) v
             chunk_base = sWork;
             if (chunk_base >= n_work) break;
             chunk_left = chunk_len = dq_next;
-            if (a.guided) { // the chunks shrink towards the end of the list: the launch's tail is one cluster, not one chunk
-                const uint32_t g = (n_work - chunk_base) / (gridDim.x * 2u);
-                dq_next = g < 1u ? 1u : (g > DQ ? DQ : g);
-            }
+            if (a.guided) dq_next = dq_guided(n_work, chunk_base, DQ);
         }
         const uint32_t work = chunk_base + (chunk_len - chunk_left);
         chunk_left--;
@@ -671,72 +798,18 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(WPS, 8))) v
 
         if (a.stop_after == 0) continue;
         // ---- 1. bounding box + border direction ----------------------------------------------------------
-        int xmin = 1 << 30, xmax = -(1 << 30), ymin = 1 << 30, ymax = -(1 << 30);
-        {   // one coalesced pass; all of a lane's loads are issued before the first use (one memory round trip, not EPL)
-            constexpr int EPL = CAP / NTH;
-            // packed point -> the staged form the sort reads: x | y << 16 | (u8)gx << 32 | (u8)gy << 40
-            auto stage = [](ck_packed_point v) -> unsigned long long {
-                const int k = (int)(v >> 1) & 3, sgn = (v & 1u) ? 1 : -1;
-                const int dx = k == 2 ? -1 : (k == 1 ? 0 : 1), dy = k == 0 ? 0 : 1;
-                return (unsigned long long)((v >> 16) & 0x1FFFu) | ((unsigned long long)((v >> 3) & 0x1FFFu) << 16) |
-                       ((unsigned long long)(uint8_t)(int8_t)(dx * sgn) << 32) | ((unsigned long long)(uint8_t)(int8_t)(dy * sgn) << 40);
-            };
-            if constexpr (EPL <= 16) {
-                ck_packed_point rawp[EPL];
+        constexpr int EPL0 = CAP / NTH;
+        ck_packed_point rawp[EPL0 <= RAWP_MAX ? EPL0 : 1];
+        if constexpr (EPL0 <= RAWP_MAX) {
 #pragma unroll
-                for (int e = 0; e < EPL; e++) { int i = tid + e * NTH; rawp[e] = (i < sz0) ? pts[i] : 0u; }
-#pragma unroll
-                for (int e = 0; e < EPL; e++) {
-                    int i = tid + e * NTH;
-                    if (i < sz0) {
-                        const unsigned long long raw = stage(rawp[e]);
-                        sKeys[i] = raw;
-                        int px = (int)(raw & 0xFFFF), py = (int)((raw >> 16) & 0xFFFF);
-                        xmin = min(xmin, px); xmax = max(xmax, px);
-                        ymin = min(ymin, py); ymax = max(ymax, py);
-                    }
-                }
-            } else {
-                for (int i = tid; i < sz0; i += NTH) {
-                    const unsigned long long raw = stage(pts[i]);
-                    sKeys[i] = raw;
-                    int px = (int)(raw & 0xFFFF), py = (int)((raw >> 16) & 0xFFFF);
-                    xmin = min(xmin, px); xmax = max(xmax, px);
-                    ymin = min(ymin, py); ymax = max(ymax, py);
-                }
-            }
+            for (int e = 0; e < EPL0; e++) { int i = tid + e * NTH; rawp[e] = (i < sz0) ? pts[i] : 0u; }
         }
         int *iscr = reinterpret_cast<int *>(sScratch);
-        {
-            int bb[4] = {xmin, -xmax, ymin, -ymax};
-            B::reduce_min4(bb, iscr);
-            xmin = bb[0]; xmax = -bb[1]; ymin = bb[2]; ymax = -bb[3];
-        }
-        if ((xmax - xmin) * (ymax - ymin) < a.min_tag_width) continue;
+        const Box box = front_box<NTH, CAP>(rawp, pts, sz0, sKeys, iscr);
+        if ((box.xmax - box.xmin) * (box.ymax - box.ymin) < a.min_tag_width) continue;
         if (a.stop_after == 10) continue;
-        long long dot;
-        {   // pick the keys-per-thread count that matches the cluster (padded to a power of two, at least one per thread)
-            constexpr int EPLS = CAP / NTH;
-            int n2 = NTH;
-            while (n2 < sz0) n2 <<= 1;
-            const int epl = n2 / NTH;
-            __syncthreads(); // raw points staged by other threads
-            bool sorted = false;
-            if constexpr (MLDS) // keys fit in registers (CAP / NTH <= 16)
-                dot = keys_bucket_sort<NTH, EPLS>(sKeys, reinterpret_cast<uint32_t *>(sPraw), sScratch, sz0, xmin, xmax, ymin, ymax,
-                                                  a.normal_ok, a.reversed_ok, a.stop_after != 11, &sorted);
-            else
-                dot = keys_bucket_sort_global<NTH, GK>(sKeys, reinterpret_cast<uint32_t *>(sPraw), sScratch,
-                                                   scratch8, sz0, xmin, xmax, ymin, ymax,
-                                                   a.normal_ok, a.reversed_ok, a.stop_after != 11, &sorted);
-            if (sorted || GK) {}
-            else if (EPLS >= 32 && epl == 32) dot = keys_sort<NTH, (EPLS >= 32 && !GK ? 32 : 1)>(sKeys, sScratch, sz0, xmin, xmax, ymin, ymax, a.normal_ok, a.reversed_ok, a.stop_after != 11);
-            else if (EPLS >= 16 && epl == 16) dot = keys_sort<NTH, (EPLS >= 16 && !GK ? 16 : 1)>(sKeys, sScratch, sz0, xmin, xmax, ymin, ymax, a.normal_ok, a.reversed_ok, a.stop_after != 11);
-            else if (EPLS >= 8 && epl == 8) dot = keys_sort<NTH, (EPLS >= 8 && !GK ? 8 : 1)>(sKeys, sScratch, sz0, xmin, xmax, ymin, ymax, a.normal_ok, a.reversed_ok, a.stop_after != 11);
-            else if (EPLS >= 4 && epl == 4) dot = keys_sort<NTH, (EPLS >= 4 && !GK ? 4 : 1)>(sKeys, sScratch, sz0, xmin, xmax, ymin, ymax, a.normal_ok, a.reversed_ok, a.stop_after != 11);
-            else if (EPLS >= 2 && epl == 2) dot = keys_sort<NTH, (EPLS >= 2 && !GK ? 2 : 1)>(sKeys, sScratch, sz0, xmin, xmax, ymin, ymax, a.normal_ok, a.reversed_ok, a.stop_after != 11);
-            else dot = keys_sort<NTH, 1>(sKeys, sScratch, sz0, xmin, xmax, ymin, ymax, a.normal_ok, a.reversed_ok, a.stop_after != 11);
-        }
+        const long long dot = front_sort<NTH, CAP, MLDS, GK, FenceBarrier>(sKeys, reinterpret_cast<uint32_t *>(sPraw), sScratch, scratch8, sz0, box,
+                                                                          a.normal_ok, a.reversed_ok, a.stop_after != 11);
         const int reversed = dot < 0;
         PROF(0);
         if (reversed && !a.reversed_ok) continue;
@@ -746,24 +819,10 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(WPS, 8))) v
         // ---- 2. duplicate removal, packing to (x,y) ----------------------------------------------------------------
         __syncthreads();
         PROF(1);
-        // compaction writes u32 (x<<13|y) at index <= i into the first half of the same buffer: a round only
-        // overwrites bytes below 4*(base+NTH) while unread keys start at byte 8*(base+NTH)
-        int sz = 0;
-        for (int base = 0; base < sz0; base += NTH) {
-            int i = base + tid;
-            unsigned long long key = 0;
-            int keep = 0;
-            if (i < sz0) { key = sKeys[i]; keep = (i == 0) || (sKeys[i - 1] != key); }
-            int tot = 0;
-            const int incl = B::scan_flag(keep, iscr, &tot);
-            __syncthreads();
-            if (keep) sXY[sz + (int)incl - 1] = (uint32_t)(key & 0x3FFFFFFu);
-            sz += (int)tot;
-            __syncthreads();
-        }
+        const int sz = front_pack<NTH, FenceBarrier>(sKeys, sz0, iscr);
         PROF(2);
         if (sz < 24) continue;
-        const int ksz = sz / 12 < 20 ? sz / 12 : 20;
+        const int ksz = sz / 12 < 20 ? sz / 12 : 20; // half-width of the line-fit window
         if (ksz < 2) continue;
 
         if (a.stop_after == 2) continue;
@@ -1308,7 +1367,7 @@ template <int NTH, int CAP, bool MLDS, int WPS, bool GK>
 __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(WPS, 8))) void k_seq(FitArgs a) {
     using B = Block<NTH>;
     constexpr int EPL = CAP / NTH;
-    constexpr bool PF = EPL <= 16; // the next cluster's points travel in registers
+    constexpr bool PF = EPL <= RAWP_MAX; // the next cluster's points travel in registers
     constexpr int HB = MLDS ? ((CAP < 2048 ? CAP : 2048) + 1) * 4 : 2 * (1024 + 1) * 4; // the sort's histogram
     __shared__ unsigned long long sKeysL[GK ? 1 : CAP];
     __shared__ __attribute__((aligned(16))) unsigned char sHist[HB];
@@ -1322,38 +1381,13 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(WPS, 8))) v
     unsigned long long *scratch8 = GK ? ws.d_hscratch + (size_t)blockIdx.x * 2 * capr + capr : ws.d_lscratch + (size_t)blockIdx.x * CK_LSCRATCH_PER_WG;
     uint32_t *sXY = reinterpret_cast<uint32_t *>(sKeys);
     int *iscr = reinterpret_cast<int *>(sScratch);
-    const uint32_t n_work = min(*a.list_count, (uint32_t)a.list_cap);
     // clusters per dequeue: an add on the one counter of a class costs ~17 ns however many workgroups wait for it (26 000 of them were
     // 0.45 of the 0.7 ms of the smallest class); the chunks shrink towards the end of the list (guided), so large ones cost no tail
     constexpr uint32_t DQMAX = CAP <= 512 ? 64u : (CAP <= 1024 ? 32u : (CAP <= 2048 ? 16u : (CAP <= 4096 ? 8u : (CAP <= 8192 ? 4u : 2u))));
-    const uint32_t per_wg4 = n_work / (gridDim.x * 4u);
-    const uint32_t DQ = per_wg4 < 1u ? 1u : (per_wg4 > DQMAX ? DQMAX : per_wg4);
-    const uint32_t static_total = gridDim.x * DQ;
-    uint32_t chunk_base = blockIdx.x * DQ, chunk_len = DQ, dq_next = DQ;
-    bool first_chunk = true;
-    // packed point -> the staged form the sort reads: x | y << 16 | (u8)gx << 32 | (u8)gy << 40
-    auto stage = [](ck_packed_point v) -> unsigned long long {
-        const int k = (int)(v >> 1) & 3, sgn = (v & 1u) ? 1 : -1;
-        const int dx = k == 2 ? -1 : (k == 1 ? 0 : 1), dy = k == 0 ? 0 : 1;
-        return (unsigned long long)((v >> 16) & 0x1FFFu) | ((unsigned long long)((v >> 3) & 0x1FFFu) << 16) |
-               ((unsigned long long)(uint8_t)(int8_t)(dx * sgn) << 32) | ((unsigned long long)(uint8_t)(int8_t)(dy * sgn) << 40);
-    };
-    for (;;) {
-        if (!first_chunk) {
-            if (static_total >= n_work) break;
-            B::sync();
-            if (tid == 0) sWork = static_total + atomicAdd(a.head, dq_next);
-            B::sync();
-            chunk_base = sWork;
-            chunk_len = dq_next;
-            if (a.guided) {
-                const uint32_t g = chunk_base < n_work ? (n_work - chunk_base) / (gridDim.x * 2u) : 0u;
-                dq_next = g < 1u ? 1u : (g > DQ ? DQ : g);
-            }
-        }
-        first_chunk = false;
-        if (chunk_base >= n_work) break;
-        const int len = (int)min(chunk_len, n_work - chunk_base);
+    ChunkQueue<DQMAX, B> queue(a);
+    while (queue.next(a, &sWork)) {
+        const uint32_t chunk_base = queue.base;
+        const int len = queue.count();
         B::sync(); // the heads of the chunk before this one have been read
         if (tid < len) {
             const uint32_t item = a.list[chunk_base + (uint32_t)tid];
@@ -1389,79 +1423,21 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(WPS, 8))) v
             if (sz0 > CAP || sz0 < 1) continue; // cannot happen: the class lists are built from the counts
             if (a.stop_after == 0) continue;
             // ---- 1. bounding box ---------------------------------------------------------------------------------------------
-            int xmin = 1 << 30, xmax = -(1 << 30), ymin = 1 << 30, ymax = -(1 << 30);
-            if constexpr (PF) {
-#pragma unroll
-                for (int e = 0; e < EPL; e++) {
-                    const int i = tid + e * NTH;
-                    if (i < sz0) {
-                        const unsigned long long raw = stage(rawp[e]);
-                        sKeys[i] = raw;
-                        const int px = (int)(raw & 0xFFFF), py = (int)((raw >> 16) & 0xFFFF);
-                        xmin = min(xmin, px); xmax = max(xmax, px);
-                        ymin = min(ymin, py); ymax = max(ymax, py);
-                    }
-                }
-            } else {
-                for (int i = tid; i < sz0; i += NTH) {
-                    const unsigned long long raw = stage(pts[i]);
-                    sKeys[i] = raw;
-                    const int px = (int)(raw & 0xFFFF), py = (int)((raw >> 16) & 0xFFFF);
-                    xmin = min(xmin, px); xmax = max(xmax, px);
-                    ymin = min(ymin, py); ymax = max(ymax, py);
-                }
-            }
-            {
-                int bb[4] = {xmin, -xmax, ymin, -ymax};
-                B::reduce_min4(bb, iscr);
-                xmin = bb[0]; xmax = -bb[1]; ymin = bb[2]; ymax = -bb[3];
-            }
-            if ((xmax - xmin) * (ymax - ymin) < a.min_tag_width) continue;
+            const Box box = front_box<NTH, CAP>(rawp, pts, sz0, sKeys, iscr);
+            if ((box.xmax - box.xmin) * (box.ymax - box.ymin) < a.min_tag_width) continue;
             if (a.stop_after == 10) continue;
             // ---- 2. border direction, sort ---------------------------------------------------------------------------------------
-            long long dot;
-            {
-                constexpr int EPLS = CAP / NTH;
-                int n2 = NTH;
-                while (n2 < sz0) n2 <<= 1;
-                const int epl = n2 / NTH;
-                B::sync(); // raw points staged by other threads
-                bool sorted = false;
-                if constexpr (MLDS)
-                    dot = keys_bucket_sort<NTH, EPLS>(sKeys, reinterpret_cast<uint32_t *>(sHist), sScratch, sz0, xmin, xmax, ymin, ymax,
-                                                      a.normal_ok, a.reversed_ok, a.stop_after != 11, &sorted);
-                else
-                    dot = keys_bucket_sort_global<NTH, GK>(sKeys, reinterpret_cast<uint32_t *>(sHist), sScratch, scratch8, sz0, xmin, xmax, ymin, ymax,
-                                                           a.normal_ok, a.reversed_ok, a.stop_after != 11, &sorted);
-                if (sorted || GK) {}
-                else if (EPLS >= 32 && epl == 32) dot = keys_sort<NTH, (EPLS >= 32 && !GK ? 32 : 1)>(sKeys, sScratch, sz0, xmin, xmax, ymin, ymax, a.normal_ok, a.reversed_ok, a.stop_after != 11);
-                else if (EPLS >= 16 && epl == 16) dot = keys_sort<NTH, (EPLS >= 16 && !GK ? 16 : 1)>(sKeys, sScratch, sz0, xmin, xmax, ymin, ymax, a.normal_ok, a.reversed_ok, a.stop_after != 11);
-                else if (EPLS >= 8 && epl == 8) dot = keys_sort<NTH, (EPLS >= 8 && !GK ? 8 : 1)>(sKeys, sScratch, sz0, xmin, xmax, ymin, ymax, a.normal_ok, a.reversed_ok, a.stop_after != 11);
-                else if (EPLS >= 4 && epl == 4) dot = keys_sort<NTH, (EPLS >= 4 && !GK ? 4 : 1)>(sKeys, sScratch, sz0, xmin, xmax, ymin, ymax, a.normal_ok, a.reversed_ok, a.stop_after != 11);
-                else if (EPLS >= 2 && epl == 2) dot = keys_sort<NTH, (EPLS >= 2 && !GK ? 2 : 1)>(sKeys, sScratch, sz0, xmin, xmax, ymin, ymax, a.normal_ok, a.reversed_ok, a.stop_after != 11);
-                else dot = keys_sort<NTH, 1>(sKeys, sScratch, sz0, xmin, xmax, ymin, ymax, a.normal_ok, a.reversed_ok, a.stop_after != 11);
-            }
+            const long long dot = front_sort<NTH, CAP, MLDS, GK, B>(sKeys, reinterpret_cast<uint32_t *>(sHist), sScratch, scratch8, sz0, box,
+                                                                    a.normal_ok, a.reversed_ok, a.stop_after != 11);
             const int reversed = dot < 0;
             if (reversed && !a.reversed_ok) continue;
             if (!reversed && !a.normal_ok) continue;
             if (a.stop_after == 1 || a.stop_after == 11) continue;
-            // ---- 3. duplicate removal, packing to (x, y) (k_fit's: the compaction writes below what is still unread) -------------
+            // ---- 3. duplicate removal, packing to (x, y) -------------------------------------------------------------------------
             B::sync();
-            int sz = 0;
-            for (int base = 0; base < sz0; base += NTH) {
-                const int i = base + tid;
-                unsigned long long key = 0;
-                int keep = 0;
-                if (i < sz0) { key = sKeys[i]; keep = (i == 0) || (sKeys[i - 1] != key); }
-                int tot = 0;
-                const int incl = B::scan_flag(keep, iscr, &tot);
-                B::sync();
-                if (keep) sXY[sz + (int)incl - 1] = (uint32_t)(key & 0x3FFFFFFu);
-                sz += (int)tot;
-                B::sync();
-            }
+            const int sz = front_pack<NTH, B>(sKeys, sz0, iscr);
             if (sz < 24) continue;
-            const int ksz = sz / 12 < 20 ? sz / 12 : 20;
+            const int ksz = sz / 12 < 20 ? sz / 12 : 20; // half-width of the line-fit window
             if (ksz < 2) continue;
             if (a.stop_after == 2) continue;
             // ---- 4. the extended sequence.  Its place in the frame is handed out in the order the clusters get here (k_chunk and k_tail
@@ -1717,13 +1693,8 @@ __device__ __forceinline__ void k_tail_body(const FitArgs &a) {
     double (*sRefine)[16][2] = reinterpret_cast<double (*)[16][2]>(sPraw);
     const int tid = threadIdx.x, lane = tid;
     const ck_stage_ws &ws = a.ws;
-    const uint32_t n_work = min(*a.list_count, (uint32_t)a.list_cap);
     constexpr uint32_t DQMAX = 64u; // (one lane per head; few adds on the one counter: see k_seq)
-    const uint32_t per_wg4 = n_work / (gridDim.x * 4u);
-    const uint32_t DQ = per_wg4 < 1u ? 1u : (per_wg4 > DQMAX ? DQMAX : per_wg4);
-    const uint32_t static_total = gridDim.x * DQ;
-    uint32_t chunk_base = blockIdx.x * DQ, chunk_len = DQ, dq_next = DQ;
-    bool first_chunk = true;
+    ChunkQueue<DQMAX, Block<NTH>> queue(a);
     auto rank_excl = [](const unsigned long long *mmask, const uint16_t *mpre, uint32_t x, uint32_t s) -> uint32_t {
         // maxima of span s before position x (clamped: bounded even on garbage)
         if (x == s * CK_SPAN) return 0u;
@@ -1732,25 +1703,12 @@ __device__ __forceinline__ void k_tail_body(const FitArgs &a) {
         const uint32_t r = (uint32_t)mpre[w] + (uint32_t)__popcll(m);
         return r > CK_SPAN / 2 ? CK_SPAN / 2 : r;
     };
-    for (;;) {
+    while (queue.next(a, &sWork)) {
         // The wave's time is a chain of memory round trips unless they are shared: the HEADS of a chunk's clusters (list entry, state
         // word, record, the ranks that bound their maxima lists) are fetched by one lane each, all at once; a cluster's maxima and its
         // first block sums are fetched while the cluster before it is fitted.
-        if (!first_chunk) {
-            if (static_total >= n_work) break;
-            wave_sync();
-            if (tid == 0) sWork = static_total + atomicAdd(a.head, dq_next);
-            wave_sync();
-            chunk_base = sWork;
-            chunk_len = dq_next;
-            if (a.guided) {
-                const uint32_t g = chunk_base < n_work ? (n_work - chunk_base) / (gridDim.x * 2u) : 0u;
-                dq_next = g < 1u ? 1u : (g > DQ ? DQ : g);
-            }
-        }
-        first_chunk = false;
-        if (chunk_base >= n_work) break;
-        const int len = (int)min(chunk_len, n_work - chunk_base);
+        const uint32_t chunk_base = queue.base;
+        const int len = queue.count();
         // ---- heads: lane l takes cluster l of the chunk ----------------------------------------------------------------------
         uint32_t h_item = 0, h_st = 0, h_e0 = 0, h_rep0 = 0, h_rep1 = 0, h_s0 = 0, h_n0 = 0, h_s1 = 0, h_n1 = 0;
         int h_nruns = 0;
@@ -2383,6 +2341,71 @@ __global__ __launch_bounds__(1024) void k_classify(ck_stage_ws ws, int n, uint32
         if (pa < (uint32_t)list_cap) lists[(size_t)CK_FIT_CLASSES * list_cap + pa] = ((uint32_t)frame << 20) | i;
     }
 }
+
+// ---- the launch plan: what each size class launches, and where ---------------------------------------------------------------------------
+// The persistent grids are sized for the 256 CUs of the device this library is written for (MI355X): a class's grid is this many
+// times its workgroups per CU.
+constexpr int FIT_CUS = 256;
+// Template parameters and grid of k_fit and of k_seq per size class (ck_internal.h: CK_FIT_CLASSES), indexed by class.  WPS: waves
+// per EU the kernel's registers are budgeted for.  Chunk sizes (CH): 512 points for the multi-wave classes (fewer scans and barriers
+// per point, 9 % less halo work); their LDS then sits at the occupancy steps — 52.9 KB (3 workgroups/CU), 80.5 KB (2/CU), ≈ 124 KB and
+// ≈ 163 KB (1/CU each).  The class with its keys in global memory (GK) has the fixed grid its scratch is laid out for, CK_HUGE_WGS.
+struct FitClass {
+    int nth, cap, ch;
+    bool mlds, gk;
+    int fit_wps, fit_wgs; // k_fit: waves per EU, workgroups per CU
+    int seq_wps, seq_wgs; // k_seq: the same
+};
+constexpr FitClass FIT_CLASS[CK_FIT_CLASSES] = {
+    // NTH  CAP          CH   MLDS   GK     k_fit     k_seq
+    {64,  512,         64,  true,  false, 3, 12,    4, 16}, // 0: 257..512 points
+    {256, 2048,        224, true,  false, 4, 4,     4, 4},  // 1: 1025..2048
+    {256, 4096,        512, true,  false, 2, 2,     3, 3},  // 2: 2049..4096 (k_seq, three workgroups per CU at 168 registers: 8.58 against 8.78 ms with two at 256)
+    {512, 8192,        896, true,  false, 2, 1,     2, 1},  // 3: 4097..8192
+    {512, 16384,       512, false, false, 2, 1,     2, 1},  // 4: 8193..16384
+    {512, CK_HUGE_CAP, 896, false, true,  2, 1,     2, 1},  // 5: the rest: only frames with more than 2730 pixels of half-perimeter have the buffer (and can have such clusters)
+    {128, 1024,        128, true,  false, 4, 7,     4, 8},  // 6: 513..1024
+    {64,  256,         64,  true,  false, 4, 16,    4, 16}, // 7: up to 256
+};
+static_assert(FIT_CUS == CK_HUGE_WGS, "the largest class: one workgroup per CU, like the two before it");
+
+// Where the classes run, and in which order they are launched.  lane[c]: 0 = the handle's stream, 1 / 2 = side stream 0 / 1.
+struct FitMode {
+    bool forks; // the side streams wait for the handle's stream before the launches, and it waits for them after
+    int8_t lane[CK_FIT_CLASSES];
+    int n_order;
+    int8_t order[CK_FIT_CLASSES];
+};
+// A small call (one frame per call is the reference's own pattern) gives every class a handful of workgroups whose time is one
+// cluster's dependency chain: the classes then run side by side on their own streams instead of one after the other — and without
+// the two youngest classes, which exist for throughput (more clusters in flight per CU) and would only add two more chains to the
+// handle's lane (0.64 -> 0.70 ms per 1280x800 frame at quad_decimate 2).  Three lanes of similar length for a typical frame:
+// {S, M1} on the handle's stream, {L1} and {M2, L2} on the side streams (more streams than that end up sharing hardware queues and
+// wait for each other anyway); the side lanes first, then the handle's own.
+constexpr FitMode FIT_SIDE_BY_SIDE = {true, {0, 0, 2, 1, 2, 0, 0, 0}, 6, {3, 2, 4, 0, 1, 5}};
+// A batch keeps one lane, except for the three classes with ONE 512-thread workgroup per CU (8193..16384 points: 2.2 clusters per
+// workgroup on average, so a quarter of the CUs do a third cluster while the rest idle; the largest; 4097..8192): one after the
+// other on a side stream, started first, their tails and barrier waits run under the small classes instead of before them.
+// (Measured: the 2049..4096 class there as well, or the three on two side streams, is slower than this.  Split fit, other
+// assignments of the classes to the three streams: 8.52 .. 8.68 ms against 8.59, all within the noise of one box.)
+constexpr FitMode FIT_TAILS_ASIDE = {true, {0, 0, 0, 1, 1, 1, 0, 0}, 8, {4, 5, 3, 7, 0, 6, 1, 2}};
+// ... and a batch in a process whose later stages already run on two streams (CK_STREAMS=2) keeps everything on the handle's stream
+constexpr FitMode FIT_SINGLE_LANE = {false, {0, 0, 0, 0, 0, 0, 0, 0}, 8, {7, 0, 6, 1, 2, 3, 4, 5}};
+
+// class C's kernel on stream st: k_seq for the split fit (flat), k_fit otherwise; wgs: workgroups per CU when not the plan's (0)
+template <int C>
+void launch_class(bool flat, int wgs, hipStream_t st, const FitArgs &a) {
+    constexpr FitClass p = FIT_CLASS[C];
+    if (p.gk && !a.ws.d_hscratch) return;
+    if (!wgs) wgs = flat ? p.seq_wgs : p.fit_wgs;
+    const unsigned grid = p.gk ? (unsigned)CK_HUGE_WGS : (unsigned)(FIT_CUS * wgs);
+    if (flat) hipLaunchKernelGGL((k_seq<p.nth, p.cap, p.mlds, p.seq_wps, p.gk>), dim3(grid), dim3(p.nth), 0, st, a);
+    else hipLaunchKernelGGL((k_fit<p.nth, p.cap, p.ch, p.mlds, p.fit_wps, p.gk>), dim3(grid), dim3(p.nth), 0, st, a);
+}
+template <int... C>
+void launch_class_of(std::integer_sequence<int, C...>, int c, bool flat, int wgs, hipStream_t st, const FitArgs &a) {
+    ((c == C ? launch_class<C>(flat, wgs, st, a) : (void)0), ...);
+}
 } // namespace
 
 #ifdef CK_FLAT_DEBUG
@@ -2405,37 +2428,41 @@ extern "C" int ck_fit_profile_read(unsigned long long *out, int reset) {
 int ck_launch_fit_quads(ck_handle *h, const ck_dev_image &qimg, const ck_dev_image &img, int n) {
     ck_stage_ws &ws = h->ws;
     if (n > 4095 || ws.cluster_cap > (1 << 20)) return CK_EINVAL;
+    // The knobs of the diagnostics build (ck_internal.h: CK_KNOB; in the product build each IS its default), read once, all here
+    // but the two that are read per call (below)
+    static const int k_split = CK_KNOB("CK_FIT_SPLIT", 3); // bit 0 = 513..1024 points have their own class, bit 1 = up to 256 points have
+    static const int k_par = CK_KNOB("CK_FIT_PAR", 0);     // the classes side by side whatever the call's size
+    static const int k_flat = CK_KNOB("CK_FIT_FLAT", 1);   // the split fit: 0 never, 2 always, 1: for the calls it pays for (below)
+    static const int k_wimg_aside = CK_KNOB("CK_FIT_WIMG_ASIDE", 1); // the split fit's weight image beside its first kernels (0: before them)
+    static const int k_tails_aside = CK_KNOB("CK_FIT_TAILS_ASIDE", 1) && ck_streams_wanted() < 2; // FIT_TAILS_ASIDE for a batch
+    static const int k_skip = CK_KNOB("CK_FIT_SKIP", 0);   // bit c set = class c is not launched
+    static const int k_wgs[2][CK_FIT_CLASSES] = {          // workgroups per CU of [k_fit, k_seq][class]; 0 = the plan's
+        {CK_KNOB("CK_FIT_S_WGS", 0), 0, 0, 0, 0, 0, 0, 0},
+        {CK_KNOB("CK_SEQ_WGS0", 0), 0, 0, 0, 0, 0, CK_KNOB("CK_SEQ_WGS6", 0), CK_KNOB("CK_SEQ_WGS7", 0)}};
+    static const int k_chunk_wgs = CK_KNOB("CK_CHUNK_WGS", 64), k_tail_wgs = CK_KNOB("CK_TAIL_WGS", 16); // k_chunk workgroups per CU over the batch, k_tail's per CU
+    // ---- policy: which form of the fit, on which lanes --------------------------------------------------------------------------
+    // (measured at 1280x800: side by side wins up to 16 frames at quad_decimate 1, up to 32 at 2, where the clusters are fewer)
+    const bool side_by_side = n <= (h->cfg.quad_decimate > 1 ? 2 * CK_FIT_PARALLEL_MAX_FRAMES : CK_FIT_PARALLEL_MAX_FRAMES) || k_par;
+    const bool tails_aside = !side_by_side && k_tails_aside;
+    const FitMode &mode = side_by_side ? FIT_SIDE_BY_SIDE : (tails_aside ? FIT_TAILS_ASIDE : FIT_SINGLE_LANE);
+    // The split fit (k_seq per class -> k_chunk over all positions -> k_tail over all clusters): for calls that run their classes one
+    // after the other AND bring enough pixels — its three stages each ramp a persistent grid up and down, which a quarter-size batch
+    // notices (1280x800 x 256 at quad_decimate 2: 2.85 against 2.52 ms unsplit; at full resolution 9.75 against 9.94, 1920x1080 21.4
+    // against 22.7, 2448x2048 x 128 27.8 against 31.5)
+    const bool flat = k_flat >= 2 || (k_flat == 1 && !side_by_side && (size_t)n * (size_t)h->qw * (size_t)h->qh >= ((size_t)100 << 20));
+    // The split fit needs the weights in its second kernel only: the weight image (a streaming kernel, bound by HBM) then runs on the
+    // second side stream beside the first kernels (bound by their sort) instead of before them
+    const bool wimg_aside = flat && tails_aside && k_wimg_aside;
+    hipStream_t lanes[1 + CK_FIT_SIDE_STREAMS] = {h->stream, h->fit_stream[0], h->fit_stream[1]};
+
     // work lists, their counts and the dequeue heads live in the fit scratch; counts and heads were zeroed with the cluster
     // tables (k_clusters.hip: k_clear)
     const ck_fit_layout fl = ck_fit_scratch_layout(ws, h->cfg.max_batch);
     const int list_cap = fl.list_cap;
-    uint32_t *lists = fl.lists, *list_counts = fl.list_counts, *heads = fl.heads;
-    static const int fit_split = CK_KNOB("CK_FIT_SPLIT", 3); // (diagnostics: bit 0 = 513..1024 points have their own class, bit 1 = up to 256 points have)
-    // A small call (one frame per call is the reference's own pattern) gives every class a handful of workgroups whose time is
-    // one cluster's dependency chain: the classes then run side by side on their own streams instead of one after the other —
-    // and without the two youngest classes, which exist for throughput (more clusters in flight per CU) and would only add two
-    // more chains to the handle's lane (0.64 -> 0.70 ms per 1280x800 frame at quad_decimate 2).
-    static const int force_par = CK_KNOB("CK_FIT_PAR", 0);
-    // (measured at 1280x800: side by side wins up to 16 frames at quad_decimate 1, up to 32 at 2, where the clusters are fewer)
-    const bool side_by_side = n <= (h->cfg.quad_decimate > 1 ? 2 * CK_FIT_PARALLEL_MAX_FRAMES : CK_FIT_PARALLEL_MAX_FRAMES) || force_par;
-    const int split = side_by_side ? 0 : fit_split;
-    hipLaunchKernelGGL(k_classify, dim3((unsigned)n), dim3(1024), 0, h->stream, ws, n, lists, list_counts, list_cap, split);
+    hipLaunchKernelGGL(k_classify, dim3((unsigned)n), dim3(1024), 0, h->stream, ws, n, fl.lists, fl.list_counts, list_cap, side_by_side ? 0 : k_split);
     FitArgs a;
     a.qim = qimg.p; a.qw = h->qw; a.qh = h->qh; a.qstride = qimg.stride; a.qpitch = qimg.pitch;
     a.wimg = ws.d_wimg;
-    auto launch_wimg = [&](hipStream_t st) {
-        const int w4 = (h->qw + 3) / 4;
-        hipLaunchKernelGGL(k_weight_image, dim3((unsigned)((w4 + 63) / 64), (unsigned)((h->qh + 3) / 4), (unsigned)n), dim3(256), 0, st, qimg.p,
-                           qimg.pitch, qimg.stride, h->qw, h->qh, ws.d_wimg);
-    };
-    // The split fit needs the weights in its second kernel only: the weight image (a streaming kernel, bound by HBM) then runs on the
-    // second side stream beside the first kernels (bound by their sort) instead of before them (CK_FIT_WIMG_ASIDE=0: as before)
-    static const int flat_env0 = CK_KNOB("CK_FIT_FLAT", 1);
-    static const int wimg_aside_env = CK_KNOB("CK_FIT_WIMG_ASIDE", 1);
-    static const int tails_aside_ok0 = CK_KNOB("CK_FIT_TAILS_ASIDE", 1) && ck_streams_wanted() < 2;
-    const bool flat0 = flat_env0 >= 2 || (flat_env0 == 1 && !side_by_side && (size_t)n * (size_t)h->qw * (size_t)h->qh >= ((size_t)100 << 20));
-    const bool wimg_aside = flat0 && !side_by_side && tails_aside_ok0 && wimg_aside_env;
-    if (!wimg_aside) launch_wimg(h->stream);
     a.im = img.p; a.w = h->w; a.h = h->h; a.stride = img.stride; a.pitch = img.pitch;
     a.decimate = h->cfg.quad_decimate; a.refine = h->cfg.refine_edges; a.max_nmaxima = h->cfg.max_nmaxima;
     a.cos_critical = h->cfg.cos_critical_rad; a.max_mse = h->cfg.max_line_fit_mse;
@@ -2449,106 +2476,42 @@ int ck_launch_fit_quads(ck_handle *h, const ck_dev_image &qimg, const ck_dev_ima
     if (a.min_tag_width < 3) a.min_tag_width = 3;
     a.ws = ws; a.list_cap = list_cap;
     a.stop_after = CK_KNOB("CK_FIT_STOP_AFTER", 99); // (read per call)
-    a.guided = CK_KNOB("CK_FIT_GUIDED", 1);
-    // chunk sizes: 512 points for the multi-wave classes (fewer scans and barriers per point, 9 % less halo work); their LDS
-    // then sits at the occupancy steps — 52.9 KB (3 workgroups/CU), 80.5 KB (2/CU), ≈ 124 KB and ≈ 163 KB (1/CU each)
-    int cus = 256;
-    // three lanes of similar length for a typical frame: {S, M1} on the handle's stream, {L1} and {M2, L2} on the side streams
-    // (more streams than that end up sharing hardware queues and wait for each other anyway)
-    hipStream_t cs[CK_FIT_CLASSES] = {h->stream, h->stream, h->stream, h->stream, h->stream, h->stream, h->stream, h->stream};
-    // A batch keeps one lane, except for the three classes with ONE 512-thread workgroup per CU (8193..16384 points: 2.2 clusters
-    // per workgroup on average, so a quarter of the CUs do a third cluster while the rest idle; the largest; 4097..8192): one after
-    // the other on a side stream, started first, their tails and barrier waits run under the small classes instead of before
-    // them.  (Measured: the 2049..4096 class there as well, or the three on two side streams, is slower than this.)
-    static const int tails_aside_ok = tails_aside_ok0;
-    const bool tails_aside = !side_by_side && tails_aside_ok;
-    if (side_by_side) { cs[3] = h->fit_stream[0]; cs[2] = h->fit_stream[1]; cs[4] = h->fit_stream[1]; }
-    if (tails_aside) { cs[4] = h->fit_stream[0]; cs[5] = h->fit_stream[0]; cs[3] = h->fit_stream[0]; }
-    // (diagnostics: CK_FIT_ASIDE: bit c set = class c on side stream 0, bit 8 + c = on side stream 1.  Split fit, measured: the three
-    // largest classes aside (0x38) 8.59 ms · with the 2049-4096 class 8.68 · with the 1025-2048 class too 8.65 · the 4097-8192 class back
-    // on the handle's stream 8.57 · or on the second side stream 8.52 · ...: all within the noise of one box)
-    static const int aside_env = CK_KNOB0("CK_FIT_ASIDE", -1);
-    if (tails_aside && aside_env >= 0)
-        for (int c = 0; c < CK_FIT_CLASSES; c++) cs[c] = ((aside_env >> c) & 1) ? h->fit_stream[0] : (((aside_env >> (8 + c)) & 1) ? h->fit_stream[1] : h->stream);
-    if (side_by_side || tails_aside) {
+    a.guided = CK_KNOB("CK_FIT_GUIDED", 1);          // (read per call)
+    auto use_list = [&](int l) { a.list = fl.lists + (size_t)l * list_cap; a.list_count = fl.list_counts + l; a.head = fl.heads + l; };
+    auto launch_wimg = [&](hipStream_t st) {
+        const int w4 = (h->qw + 3) / 4;
+        hipLaunchKernelGGL(k_weight_image, dim3((unsigned)((w4 + 63) / 64), (unsigned)((h->qh + 3) / 4), (unsigned)n), dim3(256), 0, st, qimg.p,
+                           qimg.pitch, qimg.stride, h->qw, h->qh, ws.d_wimg);
+    };
+
+    // ---- the launches ---------------------------------------------------------------------------------------------------------------
+    if (!wimg_aside) launch_wimg(h->stream);
+    if (mode.forks) {
         CK_HIP(hipEventRecord(h->ev_fit_fork, h->stream));
-        for (int k = 0; k < CK_FIT_SIDE_STREAMS; k++) CK_HIP(hipStreamWaitEvent(h->fit_stream[k], h->ev_fit_fork, 0));
+        for (int s = 0; s < CK_FIT_SIDE_STREAMS; s++) CK_HIP(hipStreamWaitEvent(h->fit_stream[s], h->ev_fit_fork, 0));
         if (wimg_aside) launch_wimg(h->fit_stream[1]); // (joined with the side streams before k_chunk)
     }
-    static const int gk_env = CK_KNOB("CK_FIT_GK", 0); // (experiment: bit c set = class c keeps its keys in global memory: small LDS, more workgroups per CU)
-    // (not for a call whose classes run side by side: the classes with their keys in global memory index ONE scratch slice by workgroup)
-    const int gk_mask = ws.d_hscratch && !side_by_side ? gk_env : 0;
-    static const int skip_mask = CK_KNOB("CK_FIT_SKIP", 0); // (diagnostics: bit c set = class c is not launched)
-    // The split fit (k_seq per class -> k_chunk over all positions -> k_tail over all clusters): CK_FIT_FLAT = 0 never, 2 always,
-    // 1 (default): for calls that run their classes one after the other AND bring enough pixels — its three stages each ramp a
-    // persistent grid up and down, which a quarter-size batch notices (1280x800 x 256 at quad_decimate 2: 2.85 against 2.52 ms
-    // unsplit; at full resolution 9.75 against 9.94, 1920x1080 21.4 against 22.7, 2448x2048 x 128 27.8 against 31.5)
-    static const int flat_env = flat_env0;
-    const bool flat = flat_env >= 2 || (flat_env == 1 && !side_by_side && (size_t)n * (size_t)h->qw * (size_t)h->qh >= ((size_t)100 << 20));
-    static const int seq_alt = CK_KNOB("CK_SEQ_ALT", 0); // (diagnostics: bit c = class c of k_seq with a tighter register budget)
-    // (diagnostics: workgroups per CU of k_seq's three smallest classes)
-    static const int seq_wgs0 = CK_KNOB("CK_SEQ_WGS0", 16), seq_wgs7 = CK_KNOB("CK_SEQ_WGS7", 16), seq_wgs6 = CK_KNOB("CK_SEQ_WGS6", 8);
-    auto launch_split = [&](int c) {
-        switch (c) {
-        // (tighter register budgets for the four classes below — six / eight / five / five waves per SIMD — measured: no difference)
-        case 0: hipLaunchKernelGGL((k_seq<64, 512, true, 4, false>), dim3((unsigned)(cus * seq_wgs0)), dim3(64), 0, cs[c], a); break;
-        case 7: hipLaunchKernelGGL((k_seq<64, 256, true, 4, false>), dim3((unsigned)(cus * seq_wgs7)), dim3(64), 0, cs[c], a); break;
-        case 6: hipLaunchKernelGGL((k_seq<128, 1024, true, 4, false>), dim3((unsigned)(cus * seq_wgs6)), dim3(128), 0, cs[c], a); break;
-        case 1: hipLaunchKernelGGL((k_seq<256, 2048, true, 4, false>), dim3((unsigned)(cus * 4)), dim3(256), 0, cs[c], a); break;
-        case 2: if (seq_alt & 16) hipLaunchKernelGGL((k_seq<256, 4096, true, 2, false>), dim3((unsigned)(cus * 2)), dim3(256), 0, cs[c], a);
-                else hipLaunchKernelGGL((k_seq<256, 4096, true, 3, false>), dim3((unsigned)(cus * 3)), dim3(256), 0, cs[c], a); // (three workgroups per CU at 168 registers: 8.58 against 8.78 ms with two at 256)
-                break;
-        case 3: hipLaunchKernelGGL((k_seq<512, 8192, true, 2, false>), dim3((unsigned)cus), dim3(512), 0, cs[c], a); break;
-        case 4: hipLaunchKernelGGL((k_seq<512, 16384, false, 2, false>), dim3((unsigned)cus), dim3(512), 0, cs[c], a); break;
-        default:
-            if (ws.d_hscratch) hipLaunchKernelGGL((k_seq<512, CK_HUGE_CAP, false, 2, true>), dim3((unsigned)CK_HUGE_WGS), dim3(512), 0, cs[c], a);
-            break;
-        }
-    };
-    auto launch = [&](int c) {
-        if ((skip_mask >> c) & 1) return;
-        a.list = lists + (size_t)c * list_cap; a.list_count = list_counts + c; a.head = heads + c;
-        if (flat) { launch_split(c); return; }
-        switch (c) {
-        case 0: { static const int s_wgs = CK_KNOB("CK_FIT_S_WGS", 12); // (diagnostics: workgroups per CU of the small class)
-            hipLaunchKernelGGL((k_fit<64, 512, 64, true, 3>), dim3((unsigned)(cus * s_wgs)), dim3(64), 0, cs[c], a); break; }
-        case 7: hipLaunchKernelGGL((k_fit<64, 256, 64, true, 4>), dim3((unsigned)(cus * 16)), dim3(64), 0, cs[c], a); break;
-        case 6: hipLaunchKernelGGL((k_fit<128, 1024, 128, true, 4>), dim3((unsigned)(cus * 7)), dim3(128), 0, cs[c], a); break;
-        case 1: hipLaunchKernelGGL((k_fit<256, 2048, 224, true, 4>), dim3((unsigned)(cus * 4)), dim3(256), 0, cs[c], a); break;
-        case 2: hipLaunchKernelGGL((k_fit<256, 4096, 512, true, 2>), dim3((unsigned)(cus * 2)), dim3(256), 0, cs[c], a); break;
-        case 3:
-            if (gk_mask & 8) hipLaunchKernelGGL((k_fit<512, 16384, 512, false, 4, true>), dim3((unsigned)CK_HUGE_WGS), dim3(512), 0, cs[c], a);
-            else hipLaunchKernelGGL((k_fit<512, 8192, 896, true, 2>), dim3((unsigned)cus), dim3(512), 0, cs[c], a);
-            break;
-        case 4:
-            if (gk_mask & 16) hipLaunchKernelGGL((k_fit<512, 16384, 512, false, 4, true>), dim3((unsigned)CK_HUGE_WGS), dim3(512), 0, cs[c], a);
-            else hipLaunchKernelGGL((k_fit<512, 16384, 512, false, 2>), dim3((unsigned)cus), dim3(512), 0, cs[c], a);
-            break;
-        default: // more than 16384 points: only frames with more than 2730 pixels of half-perimeter have the buffer (and can have such clusters)
-            if (ws.d_hscratch) hipLaunchKernelGGL((k_fit<512, CK_HUGE_CAP, 896, false, 2, true>), dim3((unsigned)CK_HUGE_WGS), dim3(512), 0, cs[c], a);
-            break;
-        }
-    };
-    if (side_by_side) { launch(3); launch(2); launch(4); launch(0); launch(1); launch(5); } // the side lanes first, then the handle's own
-    else if (tails_aside) { launch(4); launch(5); launch(3); launch(7); launch(0); launch(6); launch(1); launch(2); }
-    else { launch(7); launch(0); launch(6); for (int c = 1; c < 6; c++) launch(c); }
-    if (side_by_side || tails_aside)
-        for (int k = 0; k < CK_FIT_SIDE_STREAMS; k++) {
-            CK_HIP(hipEventRecord(h->ev_fit_join[k], h->fit_stream[k]));
-            CK_HIP(hipStreamWaitEvent(h->stream, h->ev_fit_join[k], 0));
+    for (int i = 0; i < mode.n_order; i++) {
+        const int c = mode.order[i];
+        if ((k_skip >> c) & 1) continue;
+        use_list(c);
+        launch_class_of(std::make_integer_sequence<int, CK_FIT_CLASSES>{}, c, flat, k_wgs[flat][c], lanes[mode.lane[c]], a);
+    }
+    if (mode.forks)
+        for (int s = 0; s < CK_FIT_SIDE_STREAMS; s++) {
+            CK_HIP(hipEventRecord(h->ev_fit_join[s], h->fit_stream[s]));
+            CK_HIP(hipStreamWaitEvent(h->stream, h->ev_fit_join[s], 0));
         }
     if (flat) {
         // spans per frame and workgroups that share them: a batch gives every workgroup a few spans, a short call one each
         const unsigned spans = (unsigned)(ws.ext_cap / CK_SPAN);
-        static const int chunk_wgs = CK_KNOB("CK_CHUNK_WGS", 64); // (diagnostics: k_chunk workgroups per CU over the batch)
-        static const int tail_wgs = CK_KNOB("CK_TAIL_WGS", 16);    // (diagnostics: k_tail workgroups per CU)
-        unsigned gx = (unsigned)((cus * chunk_wgs + n - 1) / n);
+        unsigned gx = (unsigned)((FIT_CUS * k_chunk_wgs + n - 1) / n);
         if (gx < 8) gx = 8;
         if (gx > spans) gx = spans;
         // (k_chunk's register count capped at 96 / 80: no difference — three workgroups per CU either way, its LDS decides)
         if (a.stop_after > 3) hipLaunchKernelGGL(k_chunk, dim3(gx, (unsigned)n), dim3(256), 0, h->stream, ws, h->qw, h->qh);
-        a.list = lists + (size_t)CK_FIT_CLASSES * list_cap; a.list_count = list_counts + CK_FIT_CLASSES; a.head = heads + CK_FIT_CLASSES;
-        hipLaunchKernelGGL(k_tail, dim3((unsigned)(cus * tail_wgs)), dim3(64), 0, h->stream, a);
+        use_list(CK_FIT_CLASSES); // every cluster of the batch
+        hipLaunchKernelGGL(k_tail, dim3((unsigned)(FIT_CUS * k_tail_wgs)), dim3(64), 0, h->stream, a);
     }
     CK_HIP(hipGetLastError());
     return CK_OK;

@@ -226,3 +226,33 @@ def test_fit_kernels_keep_their_register_budgets(built):
         assert v["vgpr_spill_count"] <= 2, (k, v)
     for k, v in pick("k_seq"):   # the sort kernels: budgets as measured; a jump means the class lost its occupancy step
         assert v["vgpr_spill_count"] <= 20, (k, v)
+
+
+def test_product_library_holds_one_fit_kernel_per_class(built):
+    """The product code object of k_quads.o holds exactly the kernels the launch plan (k_quads.hip: FIT_CLASS) can launch: one
+    k_fit and one k_seq per size class, named by their template arguments — and none that only a removed experiment reached
+    (keys of the 8193..16384 class in global memory, k_seq's 2049..4096 class at two waves per EU): each costs compile time
+    in both builds and can never run.  Reads the kernel names of the code object's metadata."""
+    import shutil
+    import subprocess
+    import tempfile
+    llvm = "/opt/rocm/lib/llvm/bin"
+    if not os.path.exists(os.path.join(llvm, "llvm-objdump")):
+        pytest.skip("no llvm-objdump in this image")
+    with tempfile.TemporaryDirectory() as td:
+        shutil.copy(os.path.join(ROOT, "chalkydri_amd", "csrc", "build", "k_quads.o"), td)
+        subprocess.check_call([os.path.join(llvm, "llvm-objdump"), "--offloading", "k_quads.o"], cwd=td, stdout=subprocess.DEVNULL)
+        co = [f for f in os.listdir(td) if f.startswith("k_quads.o") and "amdgcn" in f][0]
+        notes = subprocess.check_output([os.path.join(llvm, "llvm-readelf"), "--notes", co], cwd=td, text=True)
+    # Itanium names: k_fitILi64ELi512ELi64ELb1ELi3ELb0EE = k_fit<64, 512, 64, true, 3, false>
+    got = {"k_fit": set(), "k_seq": set()}
+    for m in re.finditer(r"\.name:\s+\S*?\d(k_fit|k_seq)I((?:L[ib]\d+E)+)E", notes):
+        got[m.group(1)].add(tuple(int(x) for x in re.findall(r"L[ib](\d+)E", m.group(2))))
+    # k_fit<NTH, CAP, CH, MLDS, WPS, GK>
+    assert got["k_fit"] == {(64, 512, 64, 1, 3, 0), (64, 256, 64, 1, 4, 0), (128, 1024, 128, 1, 4, 0), (256, 2048, 224, 1, 4, 0),
+                            (256, 4096, 512, 1, 2, 0), (512, 8192, 896, 1, 2, 0), (512, 16384, 512, 0, 2, 0),
+                            (512, 65536, 896, 0, 2, 1)}, got["k_fit"]
+    # k_seq<NTH, CAP, MLDS, WPS, GK>
+    assert got["k_seq"] == {(64, 512, 1, 4, 0), (64, 256, 1, 4, 0), (128, 1024, 1, 4, 0), (256, 2048, 1, 4, 0), (256, 4096, 1, 3, 0),
+                            (512, 8192, 1, 2, 0), (512, 16384, 0, 2, 0), (512, 65536, 0, 2, 1)}, got["k_seq"]
+    assert (512, 16384, 512, 0, 4, 1) not in got["k_fit"] and (256, 4096, 1, 2, 0) not in got["k_seq"]
