@@ -33,11 +33,12 @@ def load_field_layout(path_or_dict):
 class AprilTags:
     def __init__(self, width, height, field, calib, robot_to_cam, cam_id=0, family="tag36h11", bits_corrected=3,
                  max_batch=1, device=0, quad_sigma=0.0, fourcc=None, orientation="none", auto_exposure=False, exposure0=1.0,
-                 exposure_params=None, **cfg):
+                 exposure_params=None, jpeg_color=False, **cfg):
         """width x height is the image the detector sees, and calib its intrinsics: with an `orientation` ("none", "clockwise",
         "rotate-180", "counterclockwise": the reference's VideoOrientation names) those of the ORIENTED image.  `fourcc` names the
         raw format of the camera's frames for process_raw_batch ("YUYV", "RGB3", ...; None: 8-bit luma), or "MJPG" / "JPEG": the
-        camera delivers one JPEG per frame (what the reference's USB cameras do at full rate), decoded and turned on the device.
+        camera delivers one JPEG per frame (what the reference's USB cameras do at full rate), decoded and turned on the device;
+        with jpeg_color=True the decode keeps the frames' chroma on the device, so that preview(color=True) works for them too.
         auto_exposure=True (the reference's Camera.auto_exposure) meters the last frame of every batch the task stages, on the
         device, and keeps the exposure to set next in `exposure` (unit and start: exposure0); off, nothing is launched."""
         if fourcc in A.JPEG_FOURCCS:
@@ -54,7 +55,7 @@ class AprilTags:
         self.solver = SqPnP(self.detector)
         self.tags = field if isinstance(field, dict) and all(isinstance(v, A.Iso3) for v in field.values()) else load_field_layout(field)
         self.cam_id = cam_id
-        self.fourcc, self.orientation = fourcc, orientation
+        self.fourcc, self.orientation, self.jpeg_color = fourcc, orientation, bool(jpeg_color)
         self._field = (A.FieldTag * max(len(self.tags), 1))()
         for i, (tid, pose) in enumerate(sorted(self.tags.items())):
             self._field[i].id, self._field[i].pose = tid, pose
@@ -96,7 +97,8 @@ class AprilTags:
         """After process_batch: the driver-station JPEGs (bytes each) of the frames just processed — indices into the staged
         frames, or n for 0..n-1 — scaled and encoded on the device, the tags the call found outlined (overlay=True).  Keyword
         arguments as AprilTagDetector.preview_jpeg (width=640, height=480, quality=50, restart_rows=0).  color=True: the colour
-        files of the raw frames, after process_raw_batch of a packed colour format (AprilTagDetector.preview_jpeg_color)."""
+        files of the raw frames, after process_raw_batch of a packed colour format or of JPEG frames of a task made with
+        jpeg_color=True (AprilTagDetector.preview_jpeg_color)."""
         call = self.detector.preview_jpeg_color if color else self.detector.preview_jpeg
         return call(frames, n, overlay=overlay, **kw)
 
@@ -104,7 +106,7 @@ class AprilTags:
         """The camera's frames as it hands them over ([rows][bytes] each, in the task's fourcc): converted to luma and turned by
         the task's orientation on the device, then processed like process_batch."""
         if self.fourcc in A.JPEG_FOURCCS:   # one bytes object per frame
-            n = self.detector.upload_jpeg(raw_frames, self.orientation)
+            n = self.detector.upload_jpeg(raw_frames, self.orientation, color=self.jpeg_color)
         else:
             n = self.detector.upload_raw(raw_frames, self.fourcc or "GREY", self.orientation)
         return self.process_batch(None, gyro, n=n)

@@ -148,6 +148,7 @@ extern "C" int ck_create(const ck_config_t *cfg, ck_handle_t **out) {
     h->device = cfg->device;
     h->n_last_pose = -1;
     h->n_raw_staged = -1;
+    h->n_jpeg_color = -1;
     h->n_last_dets = -1;
     h->w = cfg->width; h->h = cfg->height; h->qw = qw; h->qh = qh;
     h->npix = (size_t)qw * qh;

@@ -53,8 +53,10 @@ static int await_slot(ck_ingest *g, int slot, ck_dev_image *img) {
     return CK_OK;
 }
 
-static int ingest_create(ck_handle_t *h, int32_t n_slots, const ck_raw_format_t *fmt, ck_ingest_t **out, bool jpeg = false,
-                         int32_t orientation = 0, int64_t max_frame_bytes = 0) {
+// what makes a ring a JPEG ring (nullptr: it is none)
+struct jpeg_ring_opts { int32_t orientation; int64_t max_frame_bytes; bool color; };
+
+static int ingest_create(ck_handle_t *h, int32_t n_slots, const ck_raw_format_t *fmt, ck_ingest_t **out, const jpeg_ring_opts *jpeg = nullptr) {
     if (!h || !out || n_slots < 1 || n_slots > 8) return CK_EINVAL;
     *out = nullptr;
     ck_raw_geom geo = {};
@@ -87,7 +89,7 @@ static int ingest_create(ck_handle_t *h, int32_t n_slots, const ck_raw_format_t 
         return CK_ENOMEM;
     }
     if (jpeg) {
-        const int rc = ck_jpeg_slots_create(h, n_slots, orientation, max_frame_bytes, &g->jpeg);
+        const int rc = ck_jpeg_slots_create(h, n_slots, jpeg->orientation, jpeg->max_frame_bytes, jpeg->color, &g->jpeg);
         if (rc != CK_OK) { ck_ingest_destroy(g); return rc; }
     }
     *out = g;
@@ -96,7 +98,14 @@ static int ingest_create(ck_handle_t *h, int32_t n_slots, const ck_raw_format_t 
 
 extern "C" int ck_ingest_create_jpeg(ck_handle_t *h, int32_t n_slots, int32_t orientation, int64_t max_frame_bytes, ck_ingest_t **out) {
     if (!ck_orientation_ok(orientation) || max_frame_bytes < 0) return CK_EINVAL;
-    return ingest_create(h, n_slots, nullptr, out, true, orientation, max_frame_bytes);
+    const jpeg_ring_opts o = {orientation, max_frame_bytes, false};
+    return ingest_create(h, n_slots, nullptr, out, &o);
+}
+
+extern "C" int ck_ingest_create_jpeg_color(ck_handle_t *h, int32_t n_slots, int32_t orientation, int64_t max_frame_bytes, ck_ingest_t **out) {
+    if (!ck_orientation_ok(orientation) || max_frame_bytes < 0) return CK_EINVAL;
+    const jpeg_ring_opts o = {orientation, max_frame_bytes, true};
+    return ingest_create(h, n_slots, nullptr, out, &o);
 }
 
 extern "C" int ck_ingest_create(ck_handle_t *h, int32_t n_slots, ck_ingest_t **out) { return ingest_create(h, n_slots, nullptr, out); }
@@ -220,15 +229,20 @@ extern "C" int ck_exposure_stats_ingested(ck_ingest_t *g, int32_t slot, const in
 }
 
 // Colour preview (ck_preview.hip) of a submitted slot of a raw ring, from the slot's raw twin: rawdev[slot] keeps the
-// frames of the last submit until the slot is submitted again.  The slot stays as it is.
+// frames of the last submit until the slot is submitted again; or (§4i) of a slot of a ring of ck_ingest_create_jpeg_color, whose
+// workspace keeps the chroma planes as long.  The slot stays as it is.
 static int preview_color_ingested(ck_ingest_t *g, int32_t slot, const ck_preview_params_t *pp, const int32_t *frames, int32_t n,
                                   uint8_t *out, bool files, int64_t cap_per_frame, int64_t *sizes, uint32_t *status) {
     if (!slot_ok(g, slot)) return CK_EINVAL;
-    if (!g->raw) return CK_EUNSUPPORTED; // a plain ring holds luma, a JPEG ring compressed frames
+    ck_jpeg_color_src js;
+    // a plain ring holds luma, a JPEG ring compressed frames: only the ring of ck_ingest_create_jpeg_color keeps their chroma planes
+    const bool decoded = g->jpeg && ck_jpeg_slots_color_source(g->jpeg, slot, slot_image(g, slot), g->staged[slot], &js);
+    if (!g->raw && !decoded) return CK_EUNSUPPORTED;
     ck_dev_image img;
     const int rc = await_slot(g, slot, &img);
     if (rc != CK_OK) return rc;
-    return ck_preview_color_run(g->h, pp, {g->rawdev[slot], g->geo.stride16, (int64_t)g->geo.pitch16, g->staged[slot], &g->fmt}, frames, n, out,
+    if (decoded) return ck_preview_color_run(g->h, pp, {nullptr, 0, 0, js.n_frames, nullptr, &js}, frames, n, out, files, cap_per_frame, sizes, status);
+    return ck_preview_color_run(g->h, pp, {g->rawdev[slot], g->geo.stride16, (int64_t)g->geo.pitch16, g->staged[slot], &g->fmt, nullptr}, frames, n, out,
                                 files, cap_per_frame, sizes, status);
 }
 extern "C" int ck_preview_jpeg_color_ingested(ck_ingest_t *g, int32_t slot, const ck_preview_params_t *pp, const int32_t *frames, int32_t n,

@@ -207,6 +207,9 @@ struct ck_handle {
     // what ck_preview_jpeg_color reads.  n_raw_staged = -1: the frames were staged another way since
     int n_raw_staged;
     ck_raw_format_t raw_staged_fmt;
+    // the frames the last ck_upload_jpeg_color staged, while their chroma planes still lie in jpeg->d_planes: the other source of
+    // ck_preview_jpeg_color.  -1: the frames were staged another way since
+    int n_jpeg_color, jpeg_color_orientation;
     int n_last_pose;     // records the last ck_process_* call left in ws.d_meas (what ck_gather_poses may send); -1: none yet
     int n_last_dets;     // frames whose detections the last ck_detect_* / ck_process_* call left in ws (what ck_last_tag_poses reads);
                          // -1: none yet, or a later call (ck_clusters_batch, ck_quads_batch, a failed pipeline) rewrote the workspace
@@ -284,6 +287,7 @@ static inline void ck_source_size(int w, int h, int orientation, int *sw, int *s
 static inline void ck_set_staged(ck_handle *h, int n) {
     h->n_staged = n;
     h->n_raw_staged = -1;
+    h->n_jpeg_color = -1;
 }
 // a caller's list of n frame indices (null: 0 .. n - 1): every entry is one of the n_avail frames at hand
 static inline bool ck_frame_list_ok(const int32_t *frames, int n, int n_avail) {

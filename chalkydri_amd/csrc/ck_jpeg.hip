@@ -1,6 +1,7 @@
-// Baseline JPEG (MJPEG) luma decode: the host half.  Parses each frame's markers up to SOS (never an entropy-coded byte),
-// deduplicates the Huffman and quantisation tables of the batch, builds libjpeg's canonical decode tables, packs the frame
-// descriptors and the payloads into one pinned buffer and copies it with one asynchronous copy; k_jpeg.hip does the rest.
+// Baseline JPEG (MJPEG) luma decode, and its colour form that keeps the chroma planes: the host half.  Parses
+// each frame's markers up to SOS (never an entropy-coded byte), deduplicates the Huffman and quantisation tables of the batch,
+// builds libjpeg's canonical decode tables, packs the frame descriptors and the payloads into one pinned buffer and copies it
+// with one asynchronous copy; k_jpeg.hip does the rest.
 #include <algorithm>
 #include <map>
 #include <new>
@@ -224,11 +225,20 @@ struct Tables {
 };
 
 // the Y coefficient store of a frame: the largest MCU grid a sw x sh stream can have (2 x 2 sampling)
-size_t coef_blocks(int sw, int sh) { return (size_t)((sw + 15) / 16) * 2 * (size_t)((sh + 15) / 16) * 2; }
+// (the colour form: and one Cb and one Cr block per MCU, most of them at 1 x 1 sampling: 256 bytes per MCU)
+size_t coef_blocks(int sw, int sh, bool color = false) {
+    return (size_t)((sw + 15) / 16) * 2 * (size_t)((sh + 15) / 16) * 2 + (color ? 2 * (size_t)((sw + 7) / 8) * (size_t)((sh + 7) / 8) : 0);
+}
+// the two chroma planes of a frame of the colour form, cw x ch each (none for a grey stream), as its region of d_planes
+size_t plane_bytes(const ck_jpeg_desc &d, int sw, int sh) {
+    if (d.status || d.bpm == 1) return 0;
+    const size_t hs = d.hs, vs = d.nyb / d.hs;
+    return al16(2 * ((sw + hs - 1) / hs) * ((sh + vs - 1) / vs));
+}
 
 // The descriptor of one frame of `size` bytes that parse() answered with rc, for sw x sh streams: everything but its three
-// offsets.  d.status != 0: the frame is staged as zeros and has no payload.
-void describe(const Parsed &p, int rc, int64_t size, int sw, int sh, Tables &T, ck_jpeg_desc &d) {
+// offsets (and plane_off).  d.status != 0: the frame is staged as zeros and has no payload.  color: the chroma's quantisation tables too.
+void describe(const Parsed &p, int rc, int64_t size, int sw, int sh, Tables &T, ck_jpeg_desc &d, bool color) {
     memset(&d, 0, sizeof d);
     if (rc != CK_OK) { d.status = rc == CK_EUNSUPPORTED ? CK_JPEG_UNSUPPORTED : CK_JPEG_CORRUPT; return; }
     if (p.info.width != sw || p.info.height != sh) { d.status = CK_JPEG_GEOMETRY; return; }
@@ -254,6 +264,8 @@ void describe(const Parsed &p, int rc, int64_t size, int sw, int sh, Tables &T, 
         d.ac[c] = (uint16_t)T.huff(ac);
     }
     d.qt = (uint32_t)T.quant(p.qt[p.comp_tq[0]]);
+    if (color)
+        for (int c = 1; c < p.ncomp; c++) d.qtc[c - 1] = (uint32_t)T.quant(p.qt[p.comp_tq[c]]);
 }
 
 // The staging buffer of a call: descriptors | tables | quant tables | payloads
@@ -285,29 +297,32 @@ int ws_status(ck_jpeg_ws &J, int max_batch) {
     return rc != CK_OK ? rc : J.d_status.reserve(sizeof(uint32_t) * (size_t)max_batch);
 }
 // (exact: a ring's workspace never grows, so it gets no headroom)
-int ws_reserve(ck_jpeg_ws &J, size_t stage_bytes, size_t raw_bytes, size_t n_int, size_t n_sub, size_t coef_blocks_total, bool exact = false) {
+int ws_reserve(ck_jpeg_ws &J, size_t stage_bytes, size_t raw_bytes, size_t n_int, size_t n_sub, size_t coef_blocks_total, size_t plane_total,
+               bool exact = false) {
     int rc = J.h_stage.reserve(stage_bytes, exact);
     if (rc == CK_OK) rc = J.d_in.reserve(stage_bytes, exact);
     if (rc == CK_OK) rc = J.d_compact.reserve(raw_bytes ? raw_bytes : 16, exact);
     if (rc == CK_OK) rc = J.d_int.reserve(sizeof(uint32_t) * (n_int ? n_int : 1), exact);
     if (rc == CK_OK) rc = J.d_sub.reserve(sizeof(ck_jpeg_sub) * (n_sub ? n_sub : 1), exact);
     if (rc == CK_OK) rc = J.d_coef.reserve(sizeof(int16_t) * 64 * coef_blocks_total, exact);
+    if (rc == CK_OK && plane_total) rc = J.d_planes.reserve(plane_total, exact);
     return rc;
 }
 
 // decode + IDCT of the n frames whose staging (layout L, payloads at off_raw) is on its way to J.d_in on stream s, into dst turned by
 // `orientation`, and the statuses on their way back to J.h_status: everything enqueued, nothing awaited
 int enqueue_decode(const ck_jpeg_ws &J, hipStream_t s, int n, const Layout &L, size_t off_raw, const ck_dev_image &dst, int sw, int sh,
-                   int orientation) {
+                   int orientation, bool color) {
     const int rc = ck_launch_jpeg(J, s, n, reinterpret_cast<const ck_jpeg_desc *>(J.d_in.p), reinterpret_cast<const ck_jpeg_huff *>(J.d_in + L.off_tab),
-                                  reinterpret_cast<const int32_t *>(J.d_in + L.off_qt), J.d_in + off_raw, coef_blocks(sw, sh), dst, sw, sh, orientation);
+                                  reinterpret_cast<const int32_t *>(J.d_in + L.off_qt), J.d_in + off_raw, coef_blocks(sw, sh, color), dst, sw, sh, orientation,
+                                  color);
     if (rc != CK_OK) return rc;
     CK_HIP(hipMemcpyAsync(J.h_status, J.d_status, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
     return CK_OK;
 }
 
-// ck_upload_jpeg[_oriented]: the handle's workspace, the handle's stream, the staged frames, and the two synchronisations
-int jpeg_run(ck_handle *h, const ck_jpeg_frame_t *frames, int n, int orientation, uint32_t *jpeg_status) {
+// ck_upload_jpeg[_oriented | _color]: the handle's workspace, the handle's stream, the staged frames, and the two synchronisations
+int jpeg_run(ck_handle *h, const ck_jpeg_frame_t *frames, int n, int orientation, uint32_t *jpeg_status, bool color = false) {
     CK_HIP(hipSetDevice(h->device));
     if (!ck_workspace(h->jpeg)) return CK_ENOMEM;
     ck_jpeg_ws &J = *h->jpeg;
@@ -315,19 +330,25 @@ int jpeg_run(ck_handle *h, const ck_jpeg_frame_t *frames, int n, int orientation
     if (rc != CK_OK) return rc;
     if (n == 0) {
         ck_set_staged(h, 0);
+        if (color) { h->n_jpeg_color = 0; h->jpeg_color_orientation = orientation; }
         return CK_OK;
     }
+    h->n_jpeg_color = -1; // (the descriptors and planes are about to be rewritten)
     int sw, sh;
     ck_source_size(h->w, h->h, orientation, &sw, &sh);
     // ---- parse + deduplicate --------------------------------------------------------------------------------------------------
     std::vector<Parsed> P((size_t)n);
     std::vector<ck_jpeg_desc> D((size_t)n);
     Tables T;
-    uint64_t raw_total = 0, int_total = 0, sub_total = 0;
+    uint64_t raw_total = 0, int_total = 0, sub_total = 0, plane_total = 0;
     for (int f = 0; f < n; f++) {
         ck_jpeg_desc &d = D[f];
-        describe(P[f], parse(frames[f].data, frames[f].size, P[f]), frames[f].size, sw, sh, T, d);
+        describe(P[f], parse(frames[f].data, frames[f].size, P[f]), frames[f].size, sw, sh, T, d, color);
         if (d.status) continue;
+        if (color) {
+            d.plane_off = plane_total;
+            plane_total += plane_bytes(d, sw, sh);
+        }
         d.raw_off = raw_total;
         raw_total += al16((size_t)d.raw_len + 4);
         d.int_off = int_total;
@@ -339,7 +360,7 @@ int jpeg_run(ck_handle *h, const ck_jpeg_frame_t *frames, int n, int orientation
     // ---- stage: descriptors | tables | quant tables | payloads -----------------------------------------------------------------
     const Layout L = layout(n, T);
     const size_t total = L.off_raw + raw_total;
-    rc = ws_reserve(J, total, raw_total, int_total, sub_total, coef_blocks(sw, sh) * (size_t)n);
+    rc = ws_reserve(J, total, raw_total, int_total, sub_total, coef_blocks(sw, sh, color) * (size_t)n, color ? plane_total + 16 : 0);
     if (rc != CK_OK) return rc;
     CK_HIP(hipStreamSynchronize(h->stream)); // (the staging buffer may still feed an earlier call's copy)
     uint8_t *S = J.h_stage;
@@ -347,11 +368,12 @@ int jpeg_run(ck_handle *h, const ck_jpeg_frame_t *frames, int n, int orientation
     for (int f = 0; f < n; f++)
         if (!D[f].status) stage_scan(S + L.off_raw + D[f].raw_off, frames[f].data + P[f].scan_off, D[f].raw_len);
     CK_HIP(hipMemcpyAsync(J.d_in, S, total, hipMemcpyHostToDevice, h->stream));
-    rc = enqueue_decode(J, h->stream, n, L, L.off_raw, ck_staged_image(h), sw, sh, orientation);
+    rc = enqueue_decode(J, h->stream, n, L, L.off_raw, ck_staged_image(h), sw, sh, orientation, color);
     if (rc != CK_OK) return rc;
     CK_HIP(hipStreamSynchronize(h->stream));
     if (jpeg_status) memcpy(jpeg_status, J.h_status, sizeof(uint32_t) * (size_t)n);
     ck_set_staged(h, n);
+    if (color) { h->n_jpeg_color = n; h->jpeg_color_orientation = orientation; }
     return CK_OK;
 }
 
@@ -377,6 +399,21 @@ extern "C" int ck_upload_jpeg_oriented(ck_handle_t *h, const ck_jpeg_frame_t *fr
     const int rc = check_frames(h, frames, n, orientation);
     if (rc != CK_OK) return rc;
     return jpeg_run(h, frames, n, orientation, jpeg_status);
+}
+
+extern "C" int ck_upload_jpeg_color(ck_handle_t *h, const ck_jpeg_frame_t *frames, int32_t n, int32_t orientation, uint32_t *jpeg_status) {
+    const int rc = check_frames(h, frames, n, orientation);
+    if (rc != CK_OK) return rc;
+    return jpeg_run(h, frames, n, orientation, jpeg_status, true);
+}
+
+int ck_jpeg_color_source(ck_handle *h, ck_jpeg_color_src *out) {
+    if (h->n_jpeg_color < 0) return CK_EINVAL;
+    const ck_jpeg_ws &J = *h->jpeg;
+    int sw, sh;
+    ck_source_size(h->w, h->h, h->jpeg_color_orientation, &sw, &sh);
+    *out = {ck_staged_image(h), reinterpret_cast<const ck_jpeg_desc *>(J.d_in.p), J.d_status, J.d_planes, h->n_jpeg_color, sw, sh, h->jpeg_color_orientation};
+    return CK_OK;
 }
 
 extern "C" int ck_upload_jpeg(ck_handle_t *h, const ck_jpeg_frame_t *frames, int32_t n, uint32_t *jpeg_status) {
@@ -408,8 +445,9 @@ extern "C" int ck_jpeg_luma_batch(ck_handle_t *h, const ck_jpeg_frame_t *frames,
 struct ck_jpeg_slots {
     ck_handle *h;
     int nslots, orientation, sw, sh;
+    bool color;
     int64_t max_frame_bytes;
-    size_t frame_cap, head_cap, int_cap, sub_cap;
+    size_t frame_cap, head_cap, int_cap, sub_cap, plane_cap; // plane_cap: a frame's region of d_planes (1 x 1 sampling), 0 without colour
     struct Slot {
         ck_jpeg_ws J;
         std::vector<Parsed> P;
@@ -422,15 +460,17 @@ struct ck_jpeg_slots {
 
 void ck_jpeg_slots_free(ck_jpeg_slots *q) { delete q; }
 
-int ck_jpeg_slots_create(ck_handle *h, int n_slots, int orientation, int64_t max_frame_bytes, ck_jpeg_slots **out) {
+int ck_jpeg_slots_create(ck_handle *h, int n_slots, int orientation, int64_t max_frame_bytes, bool color, ck_jpeg_slots **out) {
     ck_jpeg_slots *q = new (std::nothrow) ck_jpeg_slots();
     if (!q) return CK_ENOMEM;
-    q->h = h; q->nslots = n_slots; q->orientation = orientation;
+    q->h = h; q->nslots = n_slots; q->orientation = orientation; q->color = color;
     ck_source_size(h->w, h->h, orientation, &q->sw, &q->sh);
+    q->plane_cap = color ? al16(2 * (size_t)q->sw * q->sh) : 0;
     q->max_frame_bytes = max_frame_bytes ? max_frame_bytes : (int64_t)q->sw * q->sh;
     const size_t nb = (size_t)h->cfg.max_batch;
     q->frame_cap = al16((size_t)q->max_frame_bytes + 4);
-    q->head_cap = al16(al16(sizeof(ck_jpeg_desc) * nb) + sizeof(ck_jpeg_huff) * 6 * nb + sizeof(int32_t) * 64 * nb);
+    // (the colour form: three quantisation tables per frame)
+    q->head_cap = al16(al16(sizeof(ck_jpeg_desc) * nb) + sizeof(ck_jpeg_huff) * 6 * nb + sizeof(int32_t) * 64 * nb * (color ? 3 : 1));
     // a frame has at most one restart interval per MCU and at most one MCU per 8 x 8 pixels; its subsequences: ck_jpeg_desc::sub_cap
     const size_t nmcu_max = (size_t)((q->sw + 7) / 8) * (size_t)((q->sh + 7) / 8);
     q->int_cap = (nmcu_max + 1) * nb;
@@ -445,7 +485,8 @@ int ck_jpeg_slots_create(ck_handle *h, int n_slots, int orientation, int64_t max
     for (int s = 0; s < n_slots && rc == CK_OK; s++) {
         ck_jpeg_ws &J = q->slot[s].J;
         rc = ws_status(J, h->cfg.max_batch);
-        if (rc == CK_OK) rc = ws_reserve(J, q->head_cap + q->frame_cap * nb, q->frame_cap * nb, q->int_cap, q->sub_cap, coef_blocks(q->sw, q->sh) * nb, true);
+        if (rc == CK_OK) rc = ws_reserve(J, q->head_cap + q->frame_cap * nb, q->frame_cap * nb, q->int_cap, q->sub_cap, coef_blocks(q->sw, q->sh, color) * nb,
+                                            q->plane_cap * nb, true);
     }
     if (rc != CK_OK) { ck_jpeg_slots_free(q); return rc; }
     *out = q;
@@ -477,8 +518,9 @@ int ck_jpeg_slots_submit(ck_jpeg_slots *q, int slot, int n, hipStream_t s, const
     size_t longest = 0;
     for (int f = 0; f < n; f++) {
         ck_jpeg_desc &d = S.D[f];
-        describe(S.P[f], S.rc[f], S.size[f], q->sw, q->sh, T, d);
+        describe(S.P[f], S.rc[f], S.size[f], q->sw, q->sh, T, d, q->color);
         if (d.status) continue;
+        d.plane_off = q->plane_cap * (uint64_t)f;
         d.raw_off = q->frame_cap * (uint64_t)f; // its unstuffed copy lands at the same offset of d_compact
         d.int_off = int_total;
         int_total += d.nint + 1;
@@ -494,10 +536,17 @@ int ck_jpeg_slots_submit(ck_jpeg_slots *q, int slot, int n, hipStream_t s, const
     CK_HIP(hipMemcpyAsync(J.d_in, J.h_stage, L.head_bytes, hipMemcpyHostToDevice, s));
     if (longest)
         CK_HIP(hipMemcpy2DAsync(J.d_in + q->head_cap, q->frame_cap, J.h_stage + q->head_cap, q->frame_cap, longest, (size_t)n, hipMemcpyHostToDevice, s));
-    const int rc = enqueue_decode(J, s, n, L, q->head_cap, dst, q->sw, q->sh, q->orientation);
+    const int rc = enqueue_decode(J, s, n, L, q->head_cap, dst, q->sw, q->sh, q->orientation, q->color);
     if (rc != CK_OK) return rc;
     std::fill(S.written.begin(), S.written.end(), (uint8_t)0);
     return CK_OK;
+}
+
+bool ck_jpeg_slots_color_source(const ck_jpeg_slots *q, int slot, const ck_dev_image &img, int n_frames, ck_jpeg_color_src *out) {
+    if (!q->color) return false;
+    const ck_jpeg_ws &J = q->slot[slot].J;
+    *out = {img, reinterpret_cast<const ck_jpeg_desc *>(J.d_in.p), J.d_status, J.d_planes, n_frames, q->sw, q->sh, q->orientation};
+    return true;
 }
 
 const uint32_t *ck_jpeg_slots_status(const ck_jpeg_slots *q, int slot) { return q->slot[slot].J.h_status; }

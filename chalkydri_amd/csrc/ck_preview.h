@@ -4,6 +4,7 @@
 #define CK_PREVIEW_H
 
 #include "ck_grow.h"
+#include "ck_jpeg.h"
 
 #define CK_PV_BLOCK_BYTES 264 /* a baseline block before stuffing: 68 symbols of at most 31 bits */
 #define CK_PV_CHUNK 64        /* bytes of the bit buffer one lane of the stuffing passes owns */
@@ -55,19 +56,31 @@ struct ck_pv_csrc {
     int ovl[3];
 };
 
+// The third source kind (§4i): the frames of a JPEG decode in the colour form.  Y from the oriented luma, Cb and Cr from the
+// unoriented planes through the inverse index map and libjpeg's fancy upsampling.  ovl as above.
+struct ck_pv_jsrc {
+    const uint8_t *luma; int lstride; size_t lpitch;
+    const ck_jpeg_desc *descs; const uint32_t *status; const uint8_t *planes;
+    int sw, sh, orientation;
+    int ovl[3];
+};
+// the source of a colour call: one of the two
+struct ck_pv_src { const ck_pv_csrc *raw; const ck_pv_jsrc *jpeg; };
+
 // k_jpegenc.hip: the stages, enqueued on the handle's stream, in two halves.  d_out == nullptr: scale .. stuffing scan, after which
 // d_sizes holds every file's size, its offset in the output (i * cap for a caller's device buffer, one file behind the other with
 // `compact`) and its status.  d_out != nullptr: the files themselves, file i at d_out + offset, never more than cap bytes each.
-// cs: the raw frames of a colour call (g.nc = 3), nullptr for the staged luma (g.nc = 1).
-int ck_launch_preview_encode(ck_handle *h, const ck_pv_geom &g, const ck_pv_tables &t, const ck_pv_csrc *cs, int n, uint8_t *d_out,
+// cs: the source of a colour call (g.nc = 3), nullptr for the staged luma (g.nc = 1).
+int ck_launch_preview_encode(ck_handle *h, const ck_pv_geom &g, const ck_pv_tables &t, const ck_pv_src *cs, int n, uint8_t *d_out,
                              int64_t cap, bool compact);
 int ck_launch_preview_mask(ck_handle *h, const ck_pv_geom &g, int n);
 int ck_launch_preview_luma(ck_handle *h, const ck_pv_geom &g, int n, uint8_t *d_out);
-int ck_launch_preview_color(ck_handle *h, const ck_pv_geom &g, const ck_pv_csrc &cs, int n, uint8_t *d_out); // [n][ph][pw][3]
+int ck_launch_preview_color(ck_handle *h, const ck_pv_geom &g, const ck_pv_src &src, int n, uint8_t *d_out); // [n][ph][pw][3]
 
 // ck_preview.hip: the one path of the colour entry points (the ring's are in ck_ingest.hip, where the ring is defined) on n_frames
-// raw frames of format *fmt at p.  files: the JPEG files (ck_preview_jpeg_color*), else the triples (ck_preview_color*).
-struct ck_pv_color_src { const uint8_t *p; int stride; int64_t pitch; int n_frames; const ck_raw_format_t *fmt; };
+// raw frames of format *fmt at p, or (jpeg != nullptr, the rest unused) on the frames of a JPEG decode in the colour form.
+// files: the JPEG files (ck_preview_jpeg_color*), else the triples (ck_preview_color*).
+struct ck_pv_color_src { const uint8_t *p; int stride; int64_t pitch; int n_frames; const ck_raw_format_t *fmt; const ck_jpeg_color_src *jpeg; };
 int ck_preview_color_run(ck_handle *h, const ck_preview_params_t *pp, const ck_pv_color_src &src, const int32_t *frames, int32_t n,
                          uint8_t *out, bool files, int64_t cap_per_frame, int64_t *sizes, uint32_t *status);
 

@@ -129,7 +129,7 @@ int begin(ck_handle *h, const ck_preview_params_t *pp, const int32_t *frames, in
 }
 
 // The files of a call whose index list and mask are on the device: both halves of k_jpegenc.hip around the copy of the sizes.
-int encode_files(ck_handle *h, const ck_preview_params_t *pp, const ck_pv_geom &g, const ck_pv_csrc *cs, int n, uint8_t *out,
+int encode_files(ck_handle *h, const ck_preview_params_t *pp, const ck_pv_geom &g, const ck_pv_src *cs, int n, uint8_t *out,
                  int64_t cap_per_frame, int64_t *sizes, uint32_t *status) {
     ck_preview_ws &P = *h->preview;
     ck_pv_tables tab;
@@ -186,6 +186,8 @@ int read_pixels(ck_handle *h, size_t bytes, uint8_t *out, Launch launch) {
 constexpr int kYcc[3][3] = {{(int)CK_LUMA_R, (int)CK_LUMA_G, (int)CK_LUMA_B}, {-11059, -21709, 32768}, {32768, -27439, -5329}};
 constexpr int kYccBias[3] = {32768, (128 << 16) + 32767, (128 << 16) + 32767};
 
+int overlay_component(int c) { return (kYcc[c][0] * 0 + kYcc[c][1] * 255 + kYcc[c][2] * 0 + kYccBias[c]) >> 16; } // RGB (0, 255, 0)
+
 // what the kernels need of a packed colour family (ck_raw_class: bpp 2 with the luma's byte offset in k[2], bpp 3 / 4 with the luma
 // weight of a pixel's bytes 0, 1, 2: the weight of byte 0 tells RGB from BGR)
 void color_source(const ck_raw_geom &L, int orientation, const uint8_t *p, int stride, size_t pitch, ck_pv_csrc *cs) {
@@ -200,7 +202,7 @@ void color_source(const ck_raw_geom &L, int orientation, const uint8_t *p, int s
     for (int c = 0; c < 3; c++) {
         for (int k = 0; k < 3; k++) cs->wgt[c][k] = kYcc[c][bgr ? 2 - k : k];
         cs->bias[c] = kYccBias[c];
-        cs->ovl[c] = (kYcc[c][0] * 0 + kYcc[c][1] * 255 + kYcc[c][2] * 0 + kYccBias[c]) >> 16; // RGB (0, 255, 0)
+        cs->ovl[c] = overlay_component(c);
     }
 }
 
@@ -212,17 +214,28 @@ int ck_preview_color_run(ck_handle *h, const ck_preview_params_t *pp, const ck_p
     ck_pv_geom g;
     int rc = resolve(pp, h->w, h->h, 3, &g);
     if (rc != CK_OK) return rc;
-    ck_raw_geom L;
-    rc = ck_raw_geometry(src.fmt, h->w, h->h, &L);
-    if (rc != CK_OK) return rc;
-    if (L.cls.bpp == 1) return CK_EUNSUPPORTED; // a luma-first family: its chroma never reaches the device (the grey preview serves it)
-    if ((!src.p && src.n_frames > 0) || src.n_frames < 0 || src.stride < L.min_stride || src.pitch < (int64_t)src.stride * L.sh) return CK_EINVAL;
-    rc = begin(h, frames, n, src.n_frames, &g);
-    if (rc != CK_OK || n == 0) return rc;
     ck_pv_csrc cs;
-    color_source(L, src.fmt->orientation, src.p, src.stride, (size_t)src.pitch, &cs);
-    if (files) return encode_files(h, pp, g, &cs, n, out, cap_per_frame, sizes, status);
-    return read_pixels(h, (size_t)g.pw * g.ph * 3 * n, out, [&](uint8_t *d) { return ck_launch_preview_color(h, g, cs, n, d); });
+    ck_pv_jsrc js;
+    ck_pv_src any = {nullptr, nullptr};
+    if (src.jpeg) { // the frames of a JPEG decode in the colour form (§4i)
+        const ck_jpeg_color_src &J = *src.jpeg;
+        rc = begin(h, frames, n, J.n_frames, &g);
+        if (rc != CK_OK || n == 0) return rc;
+        js = {J.img.p, J.img.stride, J.img.pitch, J.descs, J.status, J.planes, J.sw, J.sh, J.orientation, {overlay_component(0), overlay_component(1), overlay_component(2)}};
+        any.jpeg = &js;
+    } else {
+        ck_raw_geom L;
+        rc = ck_raw_geometry(src.fmt, h->w, h->h, &L);
+        if (rc != CK_OK) return rc;
+        if (L.cls.bpp == 1) return CK_EUNSUPPORTED; // a luma-first family: its chroma never reaches the device (the grey preview serves it)
+        if ((!src.p && src.n_frames > 0) || src.n_frames < 0 || src.stride < L.min_stride || src.pitch < (int64_t)src.stride * L.sh) return CK_EINVAL;
+        rc = begin(h, frames, n, src.n_frames, &g);
+        if (rc != CK_OK || n == 0) return rc;
+        color_source(L, src.fmt->orientation, src.p, src.stride, (size_t)src.pitch, &cs);
+        any.raw = &cs;
+    }
+    if (files) return encode_files(h, pp, g, &any, n, out, cap_per_frame, sizes, status);
+    return read_pixels(h, (size_t)g.pw * g.ph * 3 * n, out, [&](uint8_t *d) { return ck_launch_preview_color(h, g, any, n, d); });
 }
 
 static_assert(sizeof(ck_preview_params_t) == 24, "ck_preview_params_t layout");
@@ -267,35 +280,43 @@ extern "C" int ck_preview_jpeg(ck_handle_t *h, const ck_preview_params_t *pp, co
 }
 
 // ---- colour (§4g): the raw frames of the handle's staging, or of the caller's device memory ---------------------------------------
-// the raw twin of the staged frames, while the last ck_upload_raw / ck_raw_luma_batch still is what staged them
-static int staged_raw(ck_handle *h, ck_pv_color_src *src) {
+// the colour source behind the staged frames: their raw twin, while the last ck_upload_raw / ck_raw_luma_batch still is what staged
+// them; or the chroma planes beside them, while the last ck_upload_jpeg_color is (*js is then what src->jpeg points to)
+static int staged_color_source(ck_handle *h, ck_pv_color_src *src, ck_jpeg_color_src *js) {
     if (!h) return CK_EINVAL;
+    if (h->n_jpeg_color >= 0) {
+        const int rc = ck_jpeg_color_source(h, js);
+        *src = {nullptr, 0, 0, js->n_frames, nullptr, js};
+        return rc;
+    }
     if (h->n_raw_staged < 0) return CK_EINVAL;
     ck_raw_geom L;
     const int rc = ck_raw_geometry(&h->raw_staged_fmt, h->w, h->h, &L);
     if (rc != CK_OK) return rc;
-    *src = {h->n_raw_staged ? (const uint8_t *)h->raw->d_stage : nullptr, L.stride16, (int64_t)L.pitch16, h->n_raw_staged, &h->raw_staged_fmt};
+    *src = {h->n_raw_staged ? (const uint8_t *)h->raw->d_stage : nullptr, L.stride16, (int64_t)L.pitch16, h->n_raw_staged, &h->raw_staged_fmt, nullptr};
     return CK_OK;
 }
 
 extern "C" int ck_preview_jpeg_color(ck_handle_t *h, const ck_preview_params_t *pp, const int32_t *frames, int32_t n, uint8_t *out,
                                      int64_t cap_per_frame, int64_t *sizes, uint32_t *status) {
     ck_pv_color_src src;
-    const int rc = staged_raw(h, &src);
+    ck_jpeg_color_src js;
+    const int rc = staged_color_source(h, &src, &js);
     return rc != CK_OK ? rc : ck_preview_color_run(h, pp, src, frames, n, out, true, cap_per_frame, sizes, status);
 }
 extern "C" int ck_preview_color(ck_handle_t *h, const ck_preview_params_t *pp, const int32_t *frames, int32_t n, uint8_t *out) {
     ck_pv_color_src src;
-    const int rc = staged_raw(h, &src);
+    ck_jpeg_color_src js;
+    const int rc = staged_color_source(h, &src, &js);
     return rc != CK_OK ? rc : ck_preview_color_run(h, pp, src, frames, n, out, false, 0, nullptr, nullptr);
 }
 extern "C" int ck_preview_jpeg_color_device(ck_handle_t *h, const ck_preview_params_t *pp, const uint8_t *d_raw, int32_t stride,
                                             int64_t frame_pitch, const ck_raw_format_t *fmt, const int32_t *frames, int32_t n_frames,
                                             int32_t n, uint8_t *out, int64_t cap_per_frame, int64_t *sizes, uint32_t *status) {
-    return ck_preview_color_run(h, pp, {d_raw, stride, frame_pitch, n_frames, fmt}, frames, n, out, true, cap_per_frame, sizes, status);
+    return ck_preview_color_run(h, pp, {d_raw, stride, frame_pitch, n_frames, fmt, nullptr}, frames, n, out, true, cap_per_frame, sizes, status);
 }
 extern "C" int ck_preview_color_device(ck_handle_t *h, const ck_preview_params_t *pp, const uint8_t *d_raw, int32_t stride,
                                        int64_t frame_pitch, const ck_raw_format_t *fmt, const int32_t *frames, int32_t n_frames, int32_t n,
                                        uint8_t *out) {
-    return ck_preview_color_run(h, pp, {d_raw, stride, frame_pitch, n_frames, fmt}, frames, n, out, false, 0, nullptr, nullptr);
+    return ck_preview_color_run(h, pp, {d_raw, stride, frame_pitch, n_frames, fmt, nullptr}, frames, n, out, false, 0, nullptr, nullptr);
 }

@@ -133,6 +133,13 @@ __device__ __forceinline__ uint32_t y_block(const ck_jpeg_desc &d, uint32_t k, u
     const uint32_t my = mcu / d.mcux, mx = mcu - my * d.mcux;
     return (my * (d.nyb / d.hs) + sl / d.hs) * d.yblk_stride + mx * d.hs + sl % d.hs;
 }
+// The colour form's store: the Y grid, then one Cb block per MCU in raster order over the MCUs, then the Cr blocks.  Block `b` of
+// interval `k` for every slot; below nmcu * bpm while b is below the interval's block count
+__device__ __forceinline__ uint32_t c_block(const ck_jpeg_desc &d, uint32_t mcu, uint32_t comp) { return d.nmcu * (d.nyb + comp - 1) + mcu; }
+__device__ __forceinline__ uint32_t any_block(const ck_jpeg_desc &d, uint32_t k, uint32_t b) {
+    const uint32_t sl = b % d.bpm;
+    return sl < d.nyb ? y_block(d, k, b) : c_block(d, k * d.restart + b / d.bpm, sl - d.nyb + 1);
+}
 
 struct RunOut {
     uint32_t nb;  // blocks completed at or before the interval's end
@@ -142,13 +149,13 @@ struct RunOut {
 // Decodes every code that starts before `end` from the reader's state.  Without WRITE (speculative) an invalid code or a run
 // past 63 is no failure: the decode goes on at a block start (one bit on for an invalid code), deterministically, so that a wrong
 // trajectory can still merge with the true one; only the WRITE pass from synchronised entries decides corruption.  WRITE: coefficients of the Y blocks with an index below
-// `expected` (blk0 = index of the block in progress at entry) go to coef.
-template <bool WRITE>
+// `expected` (blk0 = index of the block in progress at entry) go to coef; with COLOR those of the Cb and Cr blocks too.
+template <bool WRITE, bool COLOR = false>
 __device__ RunOut decode_run(const FrameLds &L, const ck_jpeg_desc &d, BitReader &br, uint32_t end, uint32_t lim, int &slot, int &zz,
                              int16_t *coef, uint32_t k, uint32_t blk0, uint32_t expected) {
     RunOut r{0u, -1};
     uint32_t yb = 0xFFFFFFFFu;
-    if (WRITE && blk0 < expected) yb = y_block(d, k, blk0);
+    if (WRITE && blk0 < expected) yb = COLOR ? any_block(d, k, blk0) : y_block(d, k, blk0);
     while (br.pos < end) {
         br.refill();
         const int comp = slot < (int)d.nyb ? 0 : slot - (int)d.nyb + 1;
@@ -190,7 +197,7 @@ __device__ RunOut decode_run(const FrameLds &L, const ck_jpeg_desc &d, BitReader
             if (br.pos <= lim) r.nb++;
             zz = 0;
             slot = slot + 1 == (int)d.bpm ? 0 : slot + 1;
-            if (WRITE) yb = blk0 + r.nb < expected ? y_block(d, k, blk0 + r.nb) : 0xFFFFFFFFu;
+            if (WRITE) yb = blk0 + r.nb < expected ? (COLOR ? any_block(d, k, blk0 + r.nb) : y_block(d, k, blk0 + r.nb)) : 0xFFFFFFFFu;
         }
     }
     return r;
@@ -219,6 +226,9 @@ __device__ bool frame_failed(FrameLds &L, uint32_t *status, int f) {
     return bad != 0;
 }
 
+// COLOR (ck_upload_jpeg_color, a ring of ck_ingest_create_jpeg_color): the write pass keeps the Cb and Cr coefficients as well and
+// their DC differences are summed like Y's.  Everything else, and all of the luma form, is the same code.
+template <bool COLOR>
 __global__ void __launch_bounds__(NT) k_jpeg_frame(const ck_jpeg_desc *__restrict__ descs, const ck_jpeg_huff *__restrict__ huff,
                                                    const uint8_t *__restrict__ raw_base, uint8_t *__restrict__ cmp_base,
                                                    uint32_t *__restrict__ int_base, ck_jpeg_sub *__restrict__ sub_base,
@@ -423,10 +433,10 @@ __global__ void __launch_bounds__(NT) k_jpeg_frame(const ck_jpeg_desc *__restric
             }
         }
     }
-    // zero the frame's Y coefficients (the decode writes the non-zero ones)
+    // zero the frame's Y coefficients, with COLOR all its nmcu * bpm blocks (the decode writes the non-zero ones)
     int16_t *coef = coef_base + (size_t)f * coef_frame_blocks * 64;
     {
-        const size_t n16 = (size_t)d.yblk_stride * d.yblk_rows * 64 * sizeof(int16_t) / 16;
+        const size_t n16 = (COLOR ? (size_t)d.nmcu * d.bpm : (size_t)d.yblk_stride * d.yblk_rows) * 64 * sizeof(int16_t) / 16;
         uint4 *z = reinterpret_cast<uint4 *>(coef);
         for (size_t i = tid; i < n16; i += NT) z[i] = make_uint4(0, 0, 0, 0);
     }
@@ -438,7 +448,7 @@ __global__ void __launch_bounds__(NT) k_jpeg_frame(const ck_jpeg_desc *__restric
         const uint32_t en = sub[s].end, k = sub[s].interval, blk0 = sub[s].blk0, expected = interval_blocks(d, k);
         br.seek((uint32_t)(e >> 16));
         int slot = (int)((e >> 8) & 0xFF), zz = (int)(e & 0xFF);
-        const RunOut r = decode_run<true>(L, d, br, en, interval_end_byte(d, istart, k) * 8, slot, zz, coef, k, blk0, expected);
+        const RunOut r = decode_run<true, COLOR>(L, d, br, en, interval_end_byte(d, istart, k) * 8, slot, zz, coef, k, blk0, expected);
         if (r.err >= 0 && blk0 + (uint32_t)r.err < expected) atomicOr(&L.bad, (uint32_t)CK_JPEG_CORRUPT);
     }
     if (frame_failed(L, status, f)) return;
@@ -460,6 +470,19 @@ __global__ void __launch_bounds__(NT) k_jpeg_frame(const ck_jpeg_desc *__restric
             }
             const uint32_t incl = block_seg_incl(L, v, flag, carry);
             if (valid) coef[(size_t)yb * 64] = (int16_t)incl; // libjpeg keeps the sum in an int and stores it as a JCOEF
+        }
+    }
+    if constexpr (COLOR) { // ... and one sum per chroma component over its block of every MCU
+        for (uint32_t comp = 1; comp < d.bpm - d.nyb + 1; comp++) {
+            uint32_t carry = 0;
+            for (uint32_t t0 = 0; t0 < d.nmcu; t0 += NT) {
+                const uint32_t t = t0 + tid;
+                const bool valid = t < d.nmcu;
+                const uint32_t cb = valid ? c_block(d, t, comp) : 0u;
+                const uint32_t v = valid ? (uint32_t)(int32_t)coef[(size_t)cb * 64] : 0u;
+                const uint32_t incl = block_seg_incl(L, v, valid && t % d.restart == 0, carry);
+                if (valid) coef[(size_t)cb * 64] = (int16_t)incl;
+            }
         }
     }
     if (tid == 0) status[f] = 0;
@@ -608,6 +631,40 @@ __global__ void __launch_bounds__(IDCT_NT) k_jpeg_idct(const ck_jpeg_desc *__res
     }
 }
 
+// The chroma planes of the colour form: block m of component comp = 1, 2 is MCU m's, so the plane of a component is
+// the MCU grid in blocks, cropped to cw x ch = ceil(sw / hs) x ceil(sh / vs) and never turned (the preview's sampler applies the
+// index map).  The frames of a call differ in their sampling, so the grid covers the 1 x 1 case and a frame's own MCU count
+// bounds its blocks.  Every store is to a pixel (x, y) of the frame's two planes with 0 <= x < cw and 0 <= y < ch.
+__global__ void __launch_bounds__(IDCT_NT) k_jpeg_idct_chroma(const ck_jpeg_desc *__restrict__ descs, const int32_t *__restrict__ qts,
+                                                              const int16_t *__restrict__ coef_base, size_t coef_frame_blocks,
+                                                              const uint32_t *__restrict__ status, uint8_t *__restrict__ planes, int w, int h) {
+    __shared__ int32_t ws[IDCT_BLOCKS][8][9];
+    const int f = blockIdx.y, g = threadIdx.x >> 3, c = threadIdx.x & 7;
+    const ck_jpeg_desc &d = descs[f];
+    const bool ok = status[f] == 0 && d.bpm > 1;
+    const uint32_t b = blockIdx.x * IDCT_BLOCKS + g;
+    const bool live = ok && b < 2 * d.nmcu;
+    const uint32_t comp = live && b >= d.nmcu ? 1u : 0u, m = live ? b - comp * d.nmcu : 0u;
+    if (live) { // pass 1: column c
+        const int16_t *cf = coef_base + ((size_t)f * coef_frame_blocks + c_block(d, m, comp + 1)) * 64;
+        const int32_t *q = qts + (size_t)d.qtc[comp] * 64;
+        int64_t in[8], out[8];
+        for (int r = 0; r < 8; r++) in[r] = (int64_t)((int32_t)cf[r * 8 + c] * q[r * 8 + c]);
+        islow_1d(in, out);
+        for (int r = 0; r < 8; r++) ws[g][r][c] = (int32_t)((out[r] + 1024) >> 11);
+    }
+    __syncthreads();
+    if (!live) return;
+    const int vs = (int)(d.nyb / d.hs), cw = (w + (int)d.hs - 1) / (int)d.hs, ch = (h + vs - 1) / vs;
+    const int by = (int)(m / d.mcux), bx = (int)(m - (uint32_t)by * d.mcux), y = by * 8 + c;
+    if (y >= ch) return;
+    int64_t in[8], out[8];
+    for (int k = 0; k < 8; k++) in[k] = ws[g][c][k]; // pass 2: row c
+    islow_1d(in, out);
+    uint8_t *row = planes + d.plane_off + (size_t)comp * cw * ch + (size_t)y * cw + bx * 8;
+    for (int k = 0; k < 8 && bx * 8 + k < cw; k++) row[k] = range_limit((out[k] + (1 << 17)) >> 18);
+}
+
 template <int O>
 void launch_idct(hipStream_t s, int n, const ck_jpeg_desc *d_desc, const int32_t *d_qt, const ck_jpeg_ws &J, size_t coef_frame_blocks,
                  const ck_dev_image &dst, int sw, int sh) {
@@ -619,9 +676,18 @@ void launch_idct(hipStream_t s, int n, const ck_jpeg_desc *d_desc, const int32_t
 } // namespace
 
 int ck_launch_jpeg(const ck_jpeg_ws &J, hipStream_t s, int n, const ck_jpeg_desc *d_desc, const ck_jpeg_huff *d_huff, const int32_t *d_qt,
-                   const uint8_t *d_raw, size_t coef_frame_blocks, const ck_dev_image &dst, int sw, int sh, int orientation) {
-    hipLaunchKernelGGL(k_jpeg_frame, dim3((unsigned)n), dim3(NT), 0, s, d_desc, d_huff, d_raw, J.d_compact, J.d_int, J.d_sub, J.d_coef,
-                       coef_frame_blocks, J.d_status);
+                   const uint8_t *d_raw, size_t coef_frame_blocks, const ck_dev_image &dst, int sw, int sh, int orientation, bool color) {
+    if (color) {
+        hipLaunchKernelGGL(k_jpeg_frame<true>, dim3((unsigned)n), dim3(NT), 0, s, d_desc, d_huff, d_raw, J.d_compact, J.d_int, J.d_sub, J.d_coef,
+                           coef_frame_blocks, J.d_status);
+        CK_HIP(hipGetLastError());
+        const int nblk = 2 * ((sw + 7) / 8) * ((sh + 7) / 8); // two components at 1 x 1 sampling
+        hipLaunchKernelGGL(k_jpeg_idct_chroma, dim3((unsigned)((nblk + IDCT_BLOCKS - 1) / IDCT_BLOCKS), (unsigned)n), dim3(IDCT_NT), 0, s, d_desc, d_qt,
+                           J.d_coef, coef_frame_blocks, J.d_status, J.d_planes, sw, sh);
+    } else {
+        hipLaunchKernelGGL(k_jpeg_frame<false>, dim3((unsigned)n), dim3(NT), 0, s, d_desc, d_huff, d_raw, J.d_compact, J.d_int, J.d_sub, J.d_coef,
+                           coef_frame_blocks, J.d_status);
+    }
     CK_HIP(hipGetLastError());
     switch (orientation) {
     case CK_ORIENT_NONE: launch_idct<CK_ORIENT_NONE>(s, n, d_desc, d_qt, J, coef_frame_blocks, dst, sw, sh); break;

@@ -5,7 +5,8 @@
 // The colour form (§4g) has a front end of its own, k_pv_fdct_color: it gathers from the RAW frames (orientation, packed 2 / 3 / 4
 // byte pixels, libjpeg's colour conversion) one block per (MCU, component), and hands the same stages the interleaved block
 // sequence Y Cb Cr Y Cb Cr ...: there NC = 3, a block's component is its index mod 3, its DC predecessor lies three blocks back
-// and components 1 and 2 use the chrominance tables.  NC = 1 is the grey code as it was.
+// and components 1 and 2 use the chrominance tables.  NC = 1 is the grey code as it was.  The front end is a template over the kind
+// of source: the raw families, or the frames of a JPEG decode that kept its chroma planes (§4i).
 #include "ck_jpeg_tables.h"
 #include "ck_preview.h"
 
@@ -144,17 +145,102 @@ __device__ __forceinline__ int c_pixel(const uint8_t *p, int at, const CLane &L,
     return v;
 }
 
-// the triples the encoder is given, [n][ph][pw][3]: one lane per byte
+// The source kinds of the colour front end (pv_triples, pv_fdct_color below: one body, one kernel per kind).  A kind gives a lane its constants (lane), the two terms of a pixel's place (term_x of
+// the oriented column, term_y of the oriented row; their sum is the place), a frame (frame) and the lane's component of the pixel at
+// a place of a frame, overlaid (pixel).  Raw<YUV>: the packed 4:2:2 and packed colour families above, the place a byte offset.
 template <bool YUV>
-__global__ __launch_bounds__(PV_NT) void k_pv_color(ck_pv_geom g, ck_pv_csrc s, int n, const int32_t *frames, const uint32_t *mask, uint8_t *out) {
+struct Raw {
+    ck_pv_csrc s;
+    using Lane = CLane;
+    using Frame = const uint8_t *;
+    __device__ __forceinline__ Lane lane(int comp) const { return clane(s, comp); }
+    __device__ __forceinline__ int term_x(const Lane &L, int ox) const { return c_term_x<YUV>(s, L, ox); }
+    __device__ __forceinline__ int term_y(const Lane &L, int oy) const { return c_term_y<YUV>(s, L, oy); }
+    __device__ __forceinline__ Frame frame(int f) const { return s.p + (size_t)f * s.pitch; }
+    __device__ __forceinline__ int pixel(Frame p, int at, const Lane &L, const uint32_t *mask, int bit) const { return c_pixel<YUV>(p, at, L, mask, bit); }
+};
+
+// Decoded: the frames of a JPEG decode in the colour form (§4i).  The place is a pair of coordinates x | y << 16: for Y those of the
+// ORIENTED pixel in the staged (or the slot's) luma, for Cb and Cr those of the SOURCE pixel the index maps of §4d name, whose value
+// is libjpeg's fancy upsampling of the component's cw x ch plane: at most two rows j, jn and two columns i, in of it, each inside
+// [0, ch) and [0, cw) because 0 <= x < sw <= hs cw and 0 <= y < sh <= vs ch and the neighbours are clamped.
+struct Decoded {
+    ck_pv_jsrc s;
+    struct Lane { int comp, ovl; };
+    struct Frame { const uint8_t *luma, *plane; int cw, ch, h2, v2; }; // plane == nullptr: grey or failed, Cb = Cr = 128
+    __device__ __forceinline__ Lane lane(int comp) const { return {comp, comp == 0 ? s.ovl[0] : (comp == 1 ? s.ovl[1] : s.ovl[2])}; }
+    __device__ __forceinline__ int term_x(const Lane &L, int ox) const {
+        if (L.comp == 0) return ox;
+        switch (s.orientation) {
+        case CK_ORIENT_CLOCKWISE: return (s.sh - 1 - ox) << 16;
+        case CK_ORIENT_COUNTERCLOCKWISE: return ox << 16;
+        case CK_ORIENT_ROTATE_180: return s.sw - 1 - ox;
+        }
+        return ox;
+    }
+    __device__ __forceinline__ int term_y(const Lane &L, int oy) const {
+        if (L.comp == 0) return oy << 16;
+        switch (s.orientation) {
+        case CK_ORIENT_CLOCKWISE: return oy;
+        case CK_ORIENT_COUNTERCLOCKWISE: return s.sw - 1 - oy;
+        case CK_ORIENT_ROTATE_180: return (s.sh - 1 - oy) << 16;
+        }
+        return oy << 16;
+    }
+    __device__ __forceinline__ Frame frame(int f) const {
+        const ck_jpeg_desc &d = s.descs[f];
+        Frame F = {s.luma + (size_t)f * s.lpitch, nullptr, 0, 0, 0, 0};
+        if (s.status[f] == 0 && d.bpm > 1) {
+            const int hs = (int)d.hs, vs = (int)(d.nyb / d.hs);
+            F.cw = (s.sw + hs - 1) / hs; F.ch = (s.sh + vs - 1) / vs; F.h2 = hs == 2; F.v2 = vs == 2;
+            F.plane = s.planes + d.plane_off;
+        }
+        return F;
+    }
+    __device__ __forceinline__ int pixel(const Frame &F, int at, const Lane &L, const uint32_t *mask, int bit) const {
+        const int x = at & 0xFFFF, y = at >> 16;
+        int v;
+        if (L.comp == 0) {
+            v = F.luma[(size_t)y * s.lstride + x];
+        } else if (!F.plane) {
+            v = 128;
+        } else {
+            const uint8_t *P = F.plane + (L.comp == 2 ? (size_t)F.cw * F.ch : 0);
+            const int i = F.h2 ? x >> 1 : x, j = F.v2 ? y >> 1 : y;
+            const uint8_t *r0 = P + (size_t)j * F.cw;
+            if (!F.h2 && !F.v2) {
+                v = r0[i];
+            } else {
+                const int in = (x & 1) ? min(i + 1, F.cw - 1) : max(i - 1, 0), jn = (y & 1) ? min(j + 1, F.ch - 1) : max(j - 1, 0);
+                const uint8_t *r1 = P + (size_t)jn * F.cw;
+                if (!F.v2) v = (3 * r0[i] + r0[in] + ((x & 1) ? 2 : 1)) >> 2;
+                else if (!F.h2) v = (3 * r0[i] + r1[i] + ((y & 1) ? 2 : 1)) >> 2;
+                else v = (3 * (3 * r0[i] + r1[i]) + 3 * r0[in] + r1[in] + ((x & 1) ? 7 : 8)) >> 4;
+            }
+        }
+        if (mask && ((mask[bit >> 5] >> (bit & 31)) & 1u)) v = L.ovl;
+        return v;
+    }
+};
+
+// the triples the encoder is given, [n][ph][pw][3]: one lane per byte
+template <class SRC>
+__device__ __forceinline__ void pv_triples(const ck_pv_geom &g, const SRC &s, int n, const int32_t *frames, const uint32_t *mask, uint8_t *out) {
     const long t = (long)blockIdx.x * PV_NT + threadIdx.x;
     const long npx = (long)g.pw * g.ph;
     if (t >= npx * n * 3) return;
     const long q = t / 3;
     const int i = (int)(q / npx), r = (int)(q - i * npx), y = r / g.pw, x = r - y * g.pw;
-    const CLane L = clane(s, (int)(t - q * 3));
-    const int at = c_term_x<YUV>(s, L, ((2 * x + 1) * g.W) / (2 * g.pw)) + c_term_y<YUV>(s, L, ((2 * y + 1) * g.H) / (2 * g.ph));
-    out[t] = (uint8_t)c_pixel<YUV>(s.p + (size_t)frames[i] * s.pitch, at, L, g.overlay ? mask + (size_t)i * g.mask_words : nullptr, r);
+    const typename SRC::Lane L = s.lane((int)(t - q * 3));
+    const int at = s.term_x(L, ((2 * x + 1) * g.W) / (2 * g.pw)) + s.term_y(L, ((2 * y + 1) * g.H) / (2 * g.ph));
+    out[t] = (uint8_t)s.pixel(s.frame(frames[i]), at, L, g.overlay ? mask + (size_t)i * g.mask_words : nullptr, r);
+}
+template <bool YUV>
+__global__ __launch_bounds__(PV_NT) void k_pv_color(ck_pv_geom g, ck_pv_csrc s, int n, const int32_t *frames, const uint32_t *mask, uint8_t *out) {
+    pv_triples(g, Raw<YUV>{s}, n, frames, mask, out);
+}
+__global__ __launch_bounds__(PV_NT) void k_pv_jtriples(ck_pv_geom g, ck_pv_jsrc s, int n, const int32_t *frames, const uint32_t *mask, uint8_t *out) {
+    pv_triples(g, Decoded{s}, n, frames, mask, out);
 }
 
 // ---- forward DCT: libjpeg's jpeg_fdct_islow ------------------------------------------------------------------------------------
@@ -251,32 +337,43 @@ __global__ __launch_bounds__(PV_NT) void k_pv_fdct(ck_pv_geom g, ck_pv_tables ta
 // The colour front end (§4g): one block per lane again, the lane's block being component t % 3 of MCU t / 3 of the frame — so the
 // coefficients come out in scan order.  The gather reads the raw frame through the orientation's index map and converts on the
 // way: no colour image is materialised.
-template <bool YUV>
-__global__ __launch_bounds__(PV_NT) void k_pv_fdct_color(ck_pv_geom g, ck_pv_tables tab, ck_pv_csrc s, int n, const int32_t *frames,
-                                                         const uint32_t *mask, int16_t *coef, int16_t *dc, uint32_t *len) {
-    __shared__ uint32_t enc[2 * PV_ENC_WORDS];
+template <class SRC>
+__device__ __forceinline__ void pv_fdct_color(const ck_pv_geom &g, const ck_pv_tables &tab, const SRC &s, int n, const int32_t *frames,
+                                              const uint32_t *mask, int16_t *coef, int16_t *dc, uint32_t *len, uint32_t *enc) {
     load_enc<3>(enc);
     const long t = (long)blockIdx.x * PV_NT + threadIdx.x;
     if (t >= (long)n * g.nblk) return;
     const int i = (int)(t / g.nblk), b = (int)(t - (long)i * g.nblk), m = b / 3, by = m / g.bw, bx = m - by * g.bw;
-    const CLane L = clane(s, b - 3 * m);
-    const uint8_t *P = s.p + (size_t)frames[i] * s.pitch;
+    const typename SRC::Lane L = s.lane(b - 3 * m);
+    const typename SRC::Frame P = s.frame(frames[i]);
     const uint32_t *M = g.overlay ? mask + (size_t)i * g.mask_words : nullptr;
     int px[8], tx[8];
 #pragma unroll
     for (int c = 0; c < 8; c++) {
         px[c] = min(bx * 8 + c, g.pw - 1);
-        tx[c] = c_term_x<YUV>(s, L, ((2 * px[c] + 1) * g.W) / (2 * g.pw));
+        tx[c] = s.term_x(L, ((2 * px[c] + 1) * g.W) / (2 * g.pw));
     }
     int d[64];
 #pragma unroll
     for (int r = 0; r < 8; r++) {
-        const int py = min(by * 8 + r, g.ph - 1), ty = c_term_y<YUV>(s, L, ((2 * py + 1) * g.H) / (2 * g.ph));
+        const int py = min(by * 8 + r, g.ph - 1), ty = s.term_y(L, ((2 * py + 1) * g.H) / (2 * g.ph));
 #pragma unroll
-        for (int c = 0; c < 8; c++) d[r * 8 + c] = c_pixel<YUV>(P, tx[c] + ty, L, M, py * g.pw + px[c]) - 128;
+        for (int c = 0; c < 8; c++) d[r * 8 + c] = s.pixel(P, tx[c] + ty, L, M, py * g.pw + px[c]) - 128;
         fdct_1d<true>(d[r * 8], d[r * 8 + 1], d[r * 8 + 2], d[r * 8 + 3], d[r * 8 + 4], d[r * 8 + 5], d[r * 8 + 6], d[r * 8 + 7]);
     }
     fdct_finish(d, tab, L.comp != 0, enc_of<3>(enc, b), t, coef, dc, len);
+}
+template <bool YUV>
+__global__ __launch_bounds__(PV_NT) void k_pv_fdct_color(ck_pv_geom g, ck_pv_tables tab, ck_pv_csrc s, int n, const int32_t *frames,
+                                                         const uint32_t *mask, int16_t *coef, int16_t *dc, uint32_t *len) {
+    __shared__ uint32_t enc[2 * PV_ENC_WORDS];
+    pv_fdct_color(g, tab, Raw<YUV>{s}, n, frames, mask, coef, dc, len, enc);
+}
+// ... and from the frames of a JPEG decode in the colour form (§4i)
+__global__ __launch_bounds__(PV_NT) void k_pv_jfdct(ck_pv_geom g, ck_pv_tables tab, ck_pv_jsrc s, int n, const int32_t *frames,
+                                                    const uint32_t *mask, int16_t *coef, int16_t *dc, uint32_t *len) {
+    __shared__ uint32_t enc[2 * PV_ENC_WORDS];
+    pv_fdct_color(g, tab, Decoded{s}, n, frames, mask, coef, dc, len, enc);
 }
 
 // ---- placement: where every block's bits start --------------------------------------------------------------------------------
@@ -527,11 +624,12 @@ int ck_launch_preview_luma(ck_handle *h, const ck_pv_geom &g, int n, uint8_t *d_
     return CK_OK;
 }
 
-int ck_launch_preview_color(ck_handle *h, const ck_pv_geom &g, const ck_pv_csrc &cs, int n, uint8_t *d_out) {
+int ck_launch_preview_color(ck_handle *h, const ck_pv_geom &g, const ck_pv_src &src, int n, uint8_t *d_out) {
     ck_preview_ws &P = *h->preview;
     const dim3 grid(blocks_for((long)n * g.pw * g.ph * 3));
-    if (cs.bpp == 2) hipLaunchKernelGGL(k_pv_color<true>, grid, dim3(PV_NT), 0, h->stream, g, cs, n, P.d_frames, P.d_mask, d_out);
-    else hipLaunchKernelGGL(k_pv_color<false>, grid, dim3(PV_NT), 0, h->stream, g, cs, n, P.d_frames, P.d_mask, d_out);
+    if (src.jpeg) hipLaunchKernelGGL(k_pv_jtriples, grid, dim3(PV_NT), 0, h->stream, g, *src.jpeg, n, P.d_frames, P.d_mask, d_out);
+    else if (src.raw->bpp == 2) hipLaunchKernelGGL(k_pv_color<true>, grid, dim3(PV_NT), 0, h->stream, g, *src.raw, n, P.d_frames, P.d_mask, d_out);
+    else hipLaunchKernelGGL(k_pv_color<false>, grid, dim3(PV_NT), 0, h->stream, g, *src.raw, n, P.d_frames, P.d_mask, d_out);
     CK_HIP(hipGetLastError());
     return CK_OK;
 }
@@ -540,13 +638,14 @@ namespace {
 
 // front end (the staged luma, or the raw frames `cs` of a colour call) .. stuffing scan
 template <int NC>
-void launch_first_half(ck_handle *h, const ck_pv_geom &g, const ck_pv_tables &t, const ck_pv_csrc *cs, int n, int64_t cap, bool compact) {
+void launch_first_half(ck_handle *h, const ck_pv_geom &g, const ck_pv_tables &t, const ck_pv_src *cs, int n, int64_t cap, bool compact) {
     ck_preview_ws &P = *h->preview;
     hipStream_t st = h->stream;
     const unsigned nb = blocks_for((long)n * g.nblk);
     if constexpr (NC == 1) hipLaunchKernelGGL(k_pv_fdct, dim3(nb), dim3(PV_NT), 0, st, g, t, n, ck_staged_image(h), P.d_frames, P.d_mask, P.d_coef, P.d_dc, P.d_len);
-    else if (cs->bpp == 2) hipLaunchKernelGGL(k_pv_fdct_color<true>, dim3(nb), dim3(PV_NT), 0, st, g, t, *cs, n, P.d_frames, P.d_mask, P.d_coef, P.d_dc, P.d_len);
-    else hipLaunchKernelGGL(k_pv_fdct_color<false>, dim3(nb), dim3(PV_NT), 0, st, g, t, *cs, n, P.d_frames, P.d_mask, P.d_coef, P.d_dc, P.d_len);
+    else if (cs->jpeg) hipLaunchKernelGGL(k_pv_jfdct, dim3(nb), dim3(PV_NT), 0, st, g, t, *cs->jpeg, n, P.d_frames, P.d_mask, P.d_coef, P.d_dc, P.d_len);
+    else if (cs->raw->bpp == 2) hipLaunchKernelGGL(k_pv_fdct_color<true>, dim3(nb), dim3(PV_NT), 0, st, g, t, *cs->raw, n, P.d_frames, P.d_mask, P.d_coef, P.d_dc, P.d_len);
+    else hipLaunchKernelGGL(k_pv_fdct_color<false>, dim3(nb), dim3(PV_NT), 0, st, g, t, *cs->raw, n, P.d_frames, P.d_mask, P.d_coef, P.d_dc, P.d_len);
     hipLaunchKernelGGL(k_pv_scan<NC>, dim3((unsigned)(((long)n * g.nint + PV_NT / 64 - 1) / (PV_NT / 64))), dim3(PV_NT), 0, st, g, n, P.d_dc, P.d_len, P.d_istart);
     hipLaunchKernelGGL(k_pv_iscan, dim3((unsigned)n), dim3(64), 0, st, g, P.d_istart);
     const unsigned gz = (unsigned)min(64, (g.bit_words / 4 + PV_NT - 1) / PV_NT);
@@ -559,7 +658,7 @@ void launch_first_half(ck_handle *h, const ck_pv_geom &g, const ck_pv_tables &t,
 } // namespace
 
 // scale .. stuffing scan: after it d_sizes holds every file's size, offset in the output and status
-int ck_launch_preview_encode(ck_handle *h, const ck_pv_geom &g, const ck_pv_tables &t, const ck_pv_csrc *cs, int n, uint8_t *d_out,
+int ck_launch_preview_encode(ck_handle *h, const ck_pv_geom &g, const ck_pv_tables &t, const ck_pv_src *cs, int n, uint8_t *d_out,
                              int64_t cap, bool compact) {
     ck_preview_ws &P = *h->preview;
     if (!d_out) {

@@ -74,6 +74,8 @@ def _bind(L):
     L.ck_ingest_create_jpeg.argtypes = [vp, i32, i32, C.c_int64, _P(vp)]
     L.ck_ingest_write_jpeg.argtypes = [vp, i32, i32, vp, C.c_int64]
     L.ck_ingest_jpeg_status.argtypes = [vp, i32, i32, u32p]
+    L.ck_upload_jpeg_color.argtypes = [vp, _P(A.JpegFrame), i32, i32, u32p]
+    L.ck_ingest_create_jpeg_color.argtypes = [vp, i32, i32, C.c_int64, _P(vp)]
     rf = _P(A.RawFormat)
     L.ck_raw_layout.argtypes = [rf, i32, i32, _P(i32), _P(i32), _P(i32), _P(C.c_int64)]
     L.ck_upload_raw.argtypes = [vp, _P(A.ImageU8), i32, rf]
@@ -370,16 +372,20 @@ class AprilTagDetector:
         check(self._L.ck_upload_frames(self._h, arr, len(arr)), "ck_upload_frames")
         return len(arr)
 
-    def upload_jpeg(self, frames, orientation="none", return_status=False):
+    def upload_jpeg(self, frames, orientation="none", return_status=False, color=False):
         """Decodes the luma of baseline JPEG frames (bytes each) on the device into the staged frames, as `upload` stages raw
         luma: detect_batch(None, n) / the process and pose calls follow.  A frame that is unsupported, of another size or
         corrupt is staged as zeros; its CK_JPEG_* bits are in the status list (return_status=True).  With an `orientation` the
         frames are staged turned, the detector's width x height being the ORIENTED frame (the streams are height x width for
-        the quarter turns), as upload_raw does it."""
+        the quarter turns), as upload_raw does it.  color=True (ck_upload_jpeg_color) stages the same luma and keeps the frames'
+        chroma planes on the device: preview_jpeg_color / preview_color then work on them until frames are staged another way."""
         arr, keep = _jpeg_frames(frames)
         status = (C.c_uint32 * max(len(keep), 1))()
         o = orientation_code(orientation)
-        check(self._L.ck_upload_jpeg_oriented(self._h, arr, len(keep), o, status), "ck_upload_jpeg_oriented")
+        if color:
+            check(self._L.ck_upload_jpeg_color(self._h, arr, len(keep), o, status), "ck_upload_jpeg_color")
+        else:
+            check(self._L.ck_upload_jpeg_oriented(self._h, arr, len(keep), o, status), "ck_upload_jpeg_oriented")
         return (len(keep), list(status)[:len(keep)]) if return_status else len(keep)
 
     def decode_jpeg(self, frames, return_status=False, orientation="none"):
@@ -565,8 +571,8 @@ class AprilTagDetector:
     def preview_jpeg_color(self, frames=None, n=None, width=640, height=480, quality=50, restart_rows=0, overlay=False, cap=None,
                            return_status=False):
         """preview_jpeg in colour: three-component 4:4:4 files of the RAW frames the last upload_raw / raw_luma left on the
-        device (a packed colour family: 'YUYV', 'UYVY', 'RGB3', 'BGR3', 'RGBA', 'BGRA'), byte-equal to libjpeg's.  Valid until
-        frames are staged another way."""
+        device (a packed colour family: 'YUYV', 'UYVY', 'RGB3', 'BGR3', 'RGBA', 'BGRA'), or of the JPEG frames the last
+        upload_jpeg(..., color=True) decoded, byte-equal to libjpeg's.  Valid until frames are staged another way."""
         call = lambda pp, idx, n, out, c, sizes, status: self._L.ck_preview_jpeg_color(self._h, C.byref(pp), idx, n, out, c, sizes, status)
         return self._preview_files(call, "ck_preview_jpeg_color", True, frames, n, width, height, quality, restart_rows, overlay, cap, return_status)
 
@@ -645,19 +651,25 @@ class IngestRing:
     With a fourcc the slots hold RAW frames of that format ([max_batch][sh][raw stride]); submit converts and orients them on
     the device, and detect / process work as on a plain ring.  With fourcc "MJPG" (or "JPEG") the slots take one compressed
     frame per index (write(slot, index, data) with bytes, at most max_frame_bytes each; 0 = sw * sh); submit decodes and
-    orients them on the ring's copy stream, and jpeg_status(slot, n) gives their CK_JPEG_* words."""
+    orients them on the ring's copy stream, and jpeg_status(slot, n) gives their CK_JPEG_* words; with color=True the slots also
+    keep their frames' chroma planes (ck_ingest_create_jpeg_color), the source of preview_jpeg_color / preview_color."""
 
-    def __init__(self, detector, n_slots=2, fourcc=None, orientation="none", max_frame_bytes=0):
+    def __init__(self, detector, n_slots=2, fourcc=None, orientation="none", max_frame_bytes=0, color=False):
         self.det, self._L = detector, detector._L
         g = C.c_void_p()
         self._g = None
         self.code, self.rows = fourcc, detector.height
         self.jpeg = isinstance(fourcc, str) and fourcc in A.JPEG_FOURCCS
+        if color and not self.jpeg:
+            raise ValueError("color=True is an option of a JPEG ring: a raw ring keeps its raw frames anyway")
         if fourcc is None:
             check(self._L.ck_ingest_create(detector._h, n_slots, C.byref(g)), "ck_ingest_create")
         elif self.jpeg:
             o = orientation_code(orientation)
-            check(self._L.ck_ingest_create_jpeg(detector._h, n_slots, o, int(max_frame_bytes), C.byref(g)), "ck_ingest_create_jpeg")
+            if color:
+                check(self._L.ck_ingest_create_jpeg_color(detector._h, n_slots, o, int(max_frame_bytes), C.byref(g)), "ck_ingest_create_jpeg_color")
+            else:
+                check(self._L.ck_ingest_create_jpeg(detector._h, n_slots, o, int(max_frame_bytes), C.byref(g)), "ck_ingest_create_jpeg")
         else:
             fmt = raw_format(fourcc, orientation)
             # (the layout first: an unknown fourcc or orientation is refused on the host, before the ring touches the device)
@@ -709,8 +721,8 @@ class IngestRing:
 
     def preview_jpeg_color(self, slot, frames=None, n=None, width=640, height=480, quality=50, restart_rows=0, overlay=False, cap=None,
                            return_status=False):
-        """AprilTagDetector.preview_jpeg_color on the raw frames of a submitted slot of a raw ring (waits for its upload; the slot
-        stays as it is).  frames: indices below the count the slot was submitted with."""
+        """AprilTagDetector.preview_jpeg_color on the raw frames of a submitted slot of a raw ring, or on the decoded frames of a
+        slot of a JPEG ring made with color=True (waits for its upload; the slot stays as it is).  frames: indices below the count the slot was submitted with."""
         call = lambda pp, idx, n, out, c, sizes, status: self._L.ck_preview_jpeg_color_ingested(self._g, slot, C.byref(pp), idx, n, out, c,
                                                                                                sizes, status)
         return self.det._preview_files(call, "ck_preview_jpeg_color_ingested", True, frames, n, width, height, quality, restart_rows,

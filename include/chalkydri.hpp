@@ -98,6 +98,15 @@ class Handle {
         check(ck_upload_jpeg_oriented(h_, f.data(), (int32_t)f.size(), orientation, st.data()), "ck_upload_jpeg_oriented");
         return st;
     }
+    // the same luma, and the frames' chroma planes kept on the device (ck_upload_jpeg_color): preview_jpeg_color then encodes the
+    // colour preview of these frames, until frames are staged another way
+    std::vector<uint32_t> upload_jpeg_color(const std::vector<std::vector<uint8_t>> &jpegs, int32_t orientation = CK_ORIENT_NONE) {
+        std::vector<ck_jpeg_frame_t> f;
+        for (const auto &j : jpegs) f.push_back({j.data(), (int64_t)j.size()});
+        std::vector<uint32_t> st(f.size());
+        check(ck_upload_jpeg_color(h_, f.data(), (int32_t)f.size(), orientation, st.data()), "ck_upload_jpeg_color");
+        return st;
+    }
 
   private:
     ck_config_t cfg_{};
@@ -794,10 +803,12 @@ class IngestRing {
         check(ck_ingest_create_raw(h_->get(), n_slots, &fmt, &g_), "ck_ingest_create_raw");
     }
     // slots of JPEG frames, one compressed frame per index: submit decodes and orients them on the ring's copy stream
-    // (ck_ingest_create_jpeg; max_frame_bytes 0 = sw * sh)
-    struct Jpeg { int32_t orientation = CK_ORIENT_NONE; int64_t max_frame_bytes = 0; };
+    // (ck_ingest_create_jpeg; max_frame_bytes 0 = sw * sh).  color: the slots also keep their frames' chroma planes
+    // (ck_ingest_create_jpeg_color), the source of preview_jpeg_color
+    struct Jpeg { int32_t orientation = CK_ORIENT_NONE; int64_t max_frame_bytes = 0; bool color = false; };
     IngestRing(const std::shared_ptr<Handle> &h, int n_slots, const Jpeg &j) : h_(h) {
-        check(ck_ingest_create_jpeg(h_->get(), n_slots, j.orientation, j.max_frame_bytes, &g_), "ck_ingest_create_jpeg");
+        if (j.color) check(ck_ingest_create_jpeg_color(h_->get(), n_slots, j.orientation, j.max_frame_bytes, &g_), "ck_ingest_create_jpeg_color");
+        else check(ck_ingest_create_jpeg(h_->get(), n_slots, j.orientation, j.max_frame_bytes, &g_), "ck_ingest_create_jpeg");
     }
     void write_jpeg(int slot, int index, const uint8_t *data, size_t size) { check(ck_ingest_write_jpeg(g_, slot, index, data, (int64_t)size), "ck_ingest_write_jpeg"); }
     void write_jpeg(int slot, int index, const std::vector<uint8_t> &jpeg) { write_jpeg(slot, index, jpeg.data(), jpeg.size()); }
@@ -817,7 +828,8 @@ class IngestRing {
     void write(int slot, int index, const ck_image_u8_t &img, uint32_t code) { check(ck_ingest_write(g_, slot, index, &img, code), "ck_ingest_write"); }
     void submit(int slot, int n) { check(ck_ingest_submit(g_, slot, n), "ck_ingest_submit"); }
     ck_ingest_t *get() const { return g_; }
-    // the colour preview of a submitted slot of a raw ring, from the slot's raw frames (ck_preview_jpeg_color_ingested)
+    // the colour preview of a submitted slot of a raw ring, from the slot's raw frames, or of a JPEG ring made with color
+    // (ck_preview_jpeg_color_ingested)
     std::vector<std::vector<uint8_t>> preview_jpeg_color(int slot, const std::vector<int32_t> &frames, const ck_preview_params_t &pp) {
         int64_t bound = 0;
         int32_t pw = 0, ph = 0;

@@ -531,6 +531,26 @@ int ck_jpeg_luma_batch_oriented(ck_handle_t *h, const ck_jpeg_frame_t *frames, i
 int ck_ingest_create_jpeg(ck_handle_t *h, int32_t n_slots, int32_t orientation, int64_t max_frame_bytes, ck_ingest_t **out);
 int ck_ingest_write_jpeg(ck_ingest_t *ing, int32_t slot, int32_t index, const uint8_t *data, int64_t size);
 int ck_ingest_jpeg_status(ck_ingest_t *ing, int32_t slot, int32_t n, uint32_t *jpeg_status);
+/* The colour form of the JPEG decode: the source of the colour preview for MJPEG cameras.  DESIGN.md §4i is the contract.
+ * ck_upload_jpeg_color stages the luma exactly as ck_upload_jpeg_oriented does (the same bytes, the same statuses, the same errors)
+ * and also keeps the Cb and Cr planes of the n frames on the device: per component the cw x ch plane, cw = ceil(sw / hs),
+ * ch = ceil(sh / vs) for Y sampling hs x vs, from jpeg_idct_islow with the component's own quantisation table.  The planes are the
+ * handle's colour source (ck_preview_jpeg_color, ck_preview_color) until any other call stages frames, the rule of the raw staging.
+ * The frame of triples C (sh x sw) those calls orient, scale and encode: Y = the luma; Cb, Cr = libjpeg's fancy upsampling of the
+ * plane P, in integers, with i = x >> 1, j = y >> 1:
+ *   1x1  P[y][x]
+ *   2x1  x even: x == 0 ? P[y][0] : (3 P[y][i] + P[y][i-1] + 1) >> 2;  x odd: x == 2cw-1 ? P[y][cw-1] : (3 P[y][i] + P[y][i+1] + 2) >> 2
+ *   1x2  y even: (3 P[j][x] + P[max(j-1,0)][x] + 1) >> 2;              y odd: (3 P[j][x] + P[min(j+1,ch-1)][x] + 2) >> 2
+ *   2x2  T[k] = 3 P[j][k] + P[jn][k], jn = max(j-1,0) for y even, min(j+1,ch-1) for y odd;
+ *        x even: x == 0 ? (4 T[0] + 8) >> 4 : (3 T[i] + T[i-1] + 8) >> 4;  x odd: x == 2cw-1 ? (4 T[cw-1] + 7) >> 4 : (3 T[i] + T[i+1] + 7) >> 4
+ * what libjpeg(-turbo) decodes to YCbCr.  A one-component stream has Cb = Cr = 128; a frame with a non-zero CK_JPEG_* status is
+ * (0, 128, 128) everywhere.  Workspace beyond ck_upload_jpeg's (grown on demand; ck_create allocates none of it): 256 bytes of
+ * chroma coefficients per MCU and 2 cw ch bytes of planes per frame.
+ * ck_ingest_create_jpeg_color is ck_ingest_create_jpeg whose slots also keep their frames' chroma planes (sized once, for 1x1
+ * sampling) until the slot is submitted again: the source of ck_preview_jpeg_color_ingested / ck_preview_color_ingested.  Writing,
+ * submitting, the status and the detect / process calls are those of every JPEG ring. */
+int ck_upload_jpeg_color(ck_handle_t *h, const ck_jpeg_frame_t *frames, int32_t n, int32_t orientation, uint32_t *jpeg_status);
+int ck_ingest_create_jpeg_color(ck_handle_t *h, int32_t n_slots, int32_t orientation, int64_t max_frame_bytes, ck_ingest_t **out);
 
 /* ---- raw camera formats and orientation on the device -------------------------------------------------------------------
  * What the reference does between the camera and AprilTags::process with `videoconvert` + a GRAY8 caps filter and `videoflip`
@@ -656,9 +676,11 @@ int ck_preview_luma(ck_handle_t *h, const ck_preview_params_t *pp, const int32_t
  * slot. */
 /* ck_preview_layout with the colour file's upper bound.  Host only. */
 int ck_preview_color_layout(const ck_preview_params_t *pp, int32_t W, int32_t H, int32_t *pw, int32_t *ph, int64_t *max_bytes);
-/* From the raw frames the handle's last ck_upload_raw / ck_raw_luma_batch left in its raw staging.  Valid only while they are the
- * handle's staged frames: after any call that stages frames another way (ck_upload_frames, ck_upload_jpeg*, ck_upload_raw_device,
- * the *_batch calls given images, the *_device calls) CK_EINVAL.  CK_EUNSUPPORTED: that upload was of a luma-first family. */
+/* From the raw frames the handle's last ck_upload_raw / ck_raw_luma_batch left in its raw staging, or from the frames of the last
+ * ck_upload_jpeg_color (O = orient(C, orientation) of its triples C; `frames` indexes them).  Valid only while they are the
+ * handle's staged frames: after any call that stages frames another way (ck_upload_frames, ck_upload_jpeg, ck_upload_jpeg_oriented,
+ * ck_jpeg_luma_batch*, ck_upload_raw_device, the *_batch calls given images, the *_device calls) CK_EINVAL.  CK_EUNSUPPORTED: that
+ * upload was of a luma-first family. */
 int ck_preview_jpeg_color(ck_handle_t *h, const ck_preview_params_t *pp, const int32_t *frames, int32_t n, uint8_t *out,
                           int64_t cap_per_frame, int64_t *sizes, uint32_t *status);
 /* From n_frames raw frames in the caller's device memory, laid out as ck_upload_raw_device takes them: any stride >= min_stride,
@@ -667,8 +689,9 @@ int ck_preview_jpeg_color(ck_handle_t *h, const ck_preview_params_t *pp, const i
 int ck_preview_jpeg_color_device(ck_handle_t *h, const ck_preview_params_t *pp, const uint8_t *d_raw, int32_t stride,
                                  int64_t frame_pitch, const ck_raw_format_t *fmt, const int32_t *frames, int32_t n_frames, int32_t n,
                                  uint8_t *out, int64_t cap_per_frame, int64_t *sizes, uint32_t *status);
-/* From the raw twin of a submitted slot of a ck_ingest_create_raw ring (indices below the count the slot was submitted with; it is
- * kept until the slot is submitted again).  Waits for the slot like ck_exposure_stats_ingested and leaves it as it is.
+/* From the raw twin of a submitted slot of a ck_ingest_create_raw ring, or from the frames and chroma planes of a submitted slot of a
+ * ck_ingest_create_jpeg_color ring (indices below the count the slot was submitted with; they are kept until the slot is submitted
+ * again).  Waits for the slot like ck_exposure_stats_ingested and leaves it as it is.
  * CK_EUNSUPPORTED: a ring of ck_ingest_create or ck_ingest_create_jpeg. */
 int ck_preview_jpeg_color_ingested(ck_ingest_t *ing, int32_t slot, const ck_preview_params_t *pp, const int32_t *frames, int32_t n,
                                    uint8_t *out, int64_t cap_per_frame, int64_t *sizes, uint32_t *status);
