@@ -119,7 +119,7 @@ struct ck_stage_ws {
     uint16_t *d_maxpos;        // same shape: the maximum's position inside its span
     unsigned long long *d_maxmask; // [n][ext_cap / 64] bit = position is a maximum
     uint16_t *d_maxpre;        // [n][ext_cap / 64] maxima of the span before this word
-    long long *d_blk;          // [n][ext_cap / 32][6] moment sums of every aligned block of 32 positions (Mx, My, Mxx, Mxy, Myy, W)
+    long long *d_blk;          // [n][ext_cap / 32][6] moment sums (Mx, My, Mxx, Mxy, Myy, W) from the first position of the block's span (CK_SPAN positions) through the block's last
     uint32_t *d_cstate;        // [n][cluster_cap][2] points left after duplicate removal | reversed border << 31 (0: rejected before the fit), first position of the cluster's extended sequence
     ck_run *d_runs;            // [n][run_cap]
     int run_cap;
@@ -412,6 +412,43 @@ __device__ __forceinline__ int wave_min_i32(int x) { // same DPP ladder with min
     x = min(x, __builtin_amdgcn_update_dpp(x, x, 0x142, 0xA, 0xF, false));
     x = min(x, __builtin_amdgcn_update_dpp(x, x, 0x143, 0xC, 0xF, false));
     return __builtin_amdgcn_readlane(x, 63);
+}
+
+// Moves inside every group of four lanes (DPP quad_perm: lane i of a group reads lane A, B, C or D of its own group for i = 0..3).
+// Every lane has a source; call them where all lanes are active.
+template <int A, int B, int C, int D>
+__device__ __forceinline__ uint32_t quad_perm_u32(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, A | (B << 2) | (C << 4) | (D << 6), 0xF, 0xF, true);
+}
+template <int A, int B, int C, int D>
+__device__ __forceinline__ unsigned long long quad_perm_u64(unsigned long long v) {
+    return ((unsigned long long)quad_perm_u32<A, B, C, D>((uint32_t)(v >> 32)) << 32) | quad_perm_u32<A, B, C, D>((uint32_t)v);
+}
+template <int A, int B, int C, int D>
+__device__ __forceinline__ double quad_perm_f64(double v) {
+    return __longlong_as_double((long long)quad_perm_u64<A, B, C, D>((unsigned long long)__double_as_longlong(v)));
+}
+// sums over every group of four lanes, in all four of them
+__device__ __forceinline__ uint32_t quad_sum_u32(uint32_t x) { x += quad_perm_u32<2, 3, 0, 1>(x); return x + quad_perm_u32<1, 0, 3, 2>(x); }
+__device__ __forceinline__ unsigned long long quad_sum_u64(unsigned long long x) { x += quad_perm_u64<2, 3, 0, 1>(x); return x + quad_perm_u64<1, 0, 3, 2>(x); }
+
+// The wave's smallest pair (key, tag) in lexicographic order, for every lane: wave_min_i32's ladder on three words.  Lanes without a
+// source meet their own pair.
+template <int CTRL, int ROWS>
+__device__ __forceinline__ void argmin_step(unsigned long long &key, int &tag) {
+    const uint32_t lo = (uint32_t)key, hi = (uint32_t)(key >> 32);
+    const uint32_t olo = (uint32_t)__builtin_amdgcn_update_dpp((int)lo, (int)lo, CTRL, ROWS, 0xF, false);
+    const uint32_t ohi = (uint32_t)__builtin_amdgcn_update_dpp((int)hi, (int)hi, CTRL, ROWS, 0xF, false);
+    const int otag = __builtin_amdgcn_update_dpp(tag, tag, CTRL, ROWS, 0xF, false);
+    const unsigned long long okey = ((unsigned long long)ohi << 32) | olo;
+    if (okey < key || (okey == key && otag < tag)) { key = okey; tag = otag; }
+}
+__device__ __forceinline__ void wave_argmin_u64_i32(unsigned long long &key, int &tag) {
+    argmin_step<0x111, 0xF>(key, tag); argmin_step<0x112, 0xF>(key, tag); argmin_step<0x114, 0xF>(key, tag); argmin_step<0x118, 0xF>(key, tag);
+    argmin_step<0x142, 0xA>(key, tag); argmin_step<0x143, 0xC>(key, tag);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)key, 63), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(key >> 32), 63);
+    key = ((unsigned long long)hi << 32) | lo;
+    tag = __builtin_amdgcn_readlane(tag, 63);
 }
 
 // CAT's gray level of an RGB pixel (utils.rs:33-46): trunc(fma(r, 0.33f, fma(g, 0.33f, b * 0.33f))) in f32, saturating.  The one

@@ -154,8 +154,7 @@ struct Block {
     }
     __device__ static int reduce_min(int v, int *scratch) {
         const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) v = min(v, __shfl_xor(v, d, 64));
+        v = wave_min_i32(v);
         if (NW > 1) {
             if (lane == 0) scratch[wv] = v;
             __syncthreads();
@@ -1462,7 +1461,8 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(WPS, 8))) v
 // One workgroup decides CK_SPAN = 960 consecutive positions (15 words of 64) from 1024 loaded ones; it knows nothing about clusters:
 // a cluster's extended sequence carries its own neighbours (ck_internal.h), the window half-width travels in the point word, and
 // what it finds is filed by POSITION — a bit per position, the smoothed errors of a span's maxima side by side in position
-// order, moment sums of every aligned block of 32 positions — so k_tail picks its cluster's share with a few popcounts.  Positions
+// order, the span's running moment sums at the end of every aligned block of 32 positions — so k_tail picks its cluster's share with a
+// few popcounts and a target's prefix sum with one entry per span.  Positions
 // nobody wrote (rejected clusters, the room duplicates left) compute garbage that nobody reads.  All sums are exact integers,
 // the doubles are formed by the operations of k_fit's chunk loop in the same order: the same bits.
 constexpr int KL = 1024, KOFF = 32;
@@ -1551,10 +1551,14 @@ __device__ __forceinline__ void k_chunk_body(const ck_stage_ws &ws, int qw, int 
         // at the top of the loop the request would be waited for at once); their weights once the errors are done
         const uint4 nx4 = load_xy(s + gridDim.x);
         lds_barrier();
-        // 2. moment sums of the span's 30 aligned blocks of 32 positions (Mx, My, Mxx, Mxy, Myy, W: the order of M6)
+        // 2. running moment sums at the ends of the span's 30 aligned blocks of 32 positions, from the span's first decided position
+        // (Mx, My, Mxx, Mxy, Myy, W: the order of M6).  The first-order sums are widened from 32-bit differences, which are exact
+        // whatever the span's positions hold, written in this call or not: a coordinate is 13 bits of the point word (+ 1: <= 8192)
+        // and a weight comes from the weight image (<= 362; k_tail reads nine bits of it), so a span's worth is at most
+        // 960 x 511 x 8192 < 2^32
         if (tid < 180) {
             const int b = tid / 6, q = tid - 6 * b;
-            const int jh = KOFF + 32 * b + 31, jl = jh - 32;
+            const int jh = KOFF + 32 * b + 31, jl = KOFF - 1;
             long long d;
             if (q == 0) d = (long long)(uint32_t)(sP32[0][jh] - sP32[0][jl]);
             else if (q == 1) d = (long long)(uint32_t)(sP32[1][jh] - sP32[1][jl]);
@@ -1657,9 +1661,10 @@ __device__ __forceinline__ long long readlane_i64(long long v, int l) {
 // ---- split fit, last kernel: one wave per cluster ----------------------------------------------------------------------------------
 // The cluster's maxima are runs of the position-ordered lists k_chunk left (one run per span the cluster touches); the (max_nmaxima + 1)-th
 // largest smoothed error is the threshold, the survivors in index order are the candidate corners; their moment prefix sums come
-// from the aligned block sums (a wave scan) plus at most 32 points each; from there on the phases are k_fit's (pair fits, 4-subsets,
-// corners and checks, edge refinement) on 64 lanes.  Sums that start at the block boundary before the cluster's first point carry
-// whatever the positions before it hold — the same addend in every prefix sum, so it leaves with the differences.
+// from k_chunk's running sums at the block ends (one entry, plus the totals of the spans before the target's) plus at most 32 points
+// each; from there on the phases are k_fit's (pair fits, 4-subsets, corners and checks, edge refinement) on 64 lanes.  Every prefix
+// sum starts at the first position of the cluster's first span and carries whatever lies between there and the cluster's first
+// point — the same addend in all of them, so it leaves with the differences; the cluster's total subtracts it by name (the head).
 constexpr int MAXRUN = 72; // spans a cluster of CK_HUGE_CAP points can touch
 #ifdef CK_FLAT_DEBUG
 __device__ unsigned int g_flat_dbg[32];
@@ -1736,9 +1741,9 @@ __device__ __forceinline__ void k_tail_body(const FitArgs &a) {
                 }
             }
         }
-        // what lane `lane` of cluster k needs first: its maximum (if the cluster has at most 64, in at most two runs).  (The sums of the
-        // cluster's first 64 blocks travelled this way too: twelve more registers per stage, seven spilled — and a build of this kernel
-        // that spills has returned wrong results, see the note at the kernel's definition)
+        // what lane `lane` of cluster k needs first: its maximum (if the cluster has at most 64, in at most two runs).  (Six block
+        // sums per lane travelled this way too: twelve more registers per stage, seven spilled — and a build of this kernel that spills
+        // has returned wrong results, see the note at the kernel's definition)
         struct Pre { double v; uint32_t pos; };
         auto prefetch = [&](int k) -> Pre {
             Pre p;
@@ -1777,7 +1782,7 @@ __device__ __forceinline__ void k_tail_body(const FitArgs &a) {
             }
             double ln[4];
 #pragma unroll
-            for (int q = 0; q < 4; q++) ln[q] = __shfl(line[q], (tid & ~3) | ((li + 1) & 3), 64);
+            for (int q = 0; q < 4; q++) ln[q] = quad_perm_f64<1, 2, 3, 0>(line[q]); // the next side of the same cluster (DPP: every lane reaches flush)
             double Px, Py;
             {
                 double A00 = line[3], A01 = -ln[3], A10 = -line[2], A11 = ln[2];
@@ -1789,27 +1794,24 @@ __device__ __forceinline__ void k_tail_body(const FitArgs &a) {
                 Px = line[0] + L0 * A00;
                 Py = line[1] + L0 * A10;
             }
-            const int g0 = tid & ~3;
-            auto corner_x = [&](int q) { return __shfl(Px, g0 | (q & 3), 64); };
-            auto corner_y = [&](int q) { return __shfl(Py, g0 | (q & 3), 64); };
             {
-                const int t = li & 1;
-                const int va = t ? 2 : 0, vb = t ? 3 : 1, vc = t ? 0 : 2;
-                const double ax = corner_x(va), ay = corner_y(va), bx = corner_x(vb), by = corner_y(vb), cx = corner_x(vc), cy = corner_y(vc);
+                // even lanes: the triangle of corners 0, 1, 2; odd lanes: 2, 3, 0
+                const double ax = quad_perm_f64<0, 2, 0, 2>(Px), ay = quad_perm_f64<0, 2, 0, 2>(Py), bx = quad_perm_f64<1, 3, 1, 3>(Px), by = quad_perm_f64<1, 3, 1, 3>(Py);
+                const double cx = quad_perm_f64<2, 0, 2, 0>(Px), cy = quad_perm_f64<2, 0, 2, 0>(Py);
                 double len[3];
                 { double ddx = bx - ax, ddy = by - ay; len[0] = sqrt(ddx * ddx + ddy * ddy); }
                 { double ddx = cx - bx, ddy = cy - by; len[1] = sqrt(ddx * ddx + ddy * ddy); }
                 { double ddx = ax - cx, ddy = ay - cy; len[2] = sqrt(ddx * ddx + ddy * ddy); }
                 double pp = (len[0] + len[1] + len[2]) / 2.0;
                 double term = sqrt(pp * (pp - len[0]) * (pp - len[1]) * (pp - len[2]));
-                double t0 = __shfl(term, g0, 64), t1 = __shfl(term, g0 | 1, 64);
+                double t0 = quad_perm_f64<0, 0, 0, 0>(term), t1 = quad_perm_f64<1, 1, 1, 1>(term);
                 double area = 0.0;
                 area += t0; area += t1;
                 double tw = (double)a.min_tag_width;
                 if (area < 0.95 * tw * tw) ok = 0;
             }
             {
-                const double x1 = corner_x(li + 1), y1 = corner_y(li + 1), x2 = corner_x(li + 2), y2 = corner_y(li + 2);
+                const double x1 = quad_perm_f64<1, 2, 3, 0>(Px), y1 = quad_perm_f64<1, 2, 3, 0>(Py), x2 = quad_perm_f64<2, 3, 0, 1>(Px), y2 = quad_perm_f64<2, 3, 0, 1>(Py);
                 double dx1 = x1 - Px, dy1 = y1 - Py;
                 double dx2 = x2 - x1, dy2 = y2 - y1;
                 double cs = (dx1 * dx2 + dy1 * dy2) / sqrt((dx1 * dx1 + dy1 * dy1) * (dx2 * dx2 + dy2 * dy2));
@@ -2096,11 +2098,11 @@ __device__ __forceinline__ void k_tail_body(const FitArgs &a) {
         // (the lists are in position order and so are the runs: the survivors are sorted already)
 
         if (a.stop_after == 5) continue;
-        // ---- 5b. moment prefix sums at the selected maxima: aligned block sums (wave scan) + the points beyond the last block ----------
-        const uint32_t B0 = e0 >> 5, blk_l = (e1 - 1) >> 5; // blocks of the first and of the last point
+        // ---- 5b. moment prefix sums at the selected maxima: k_chunk's running sums at the block ends + the points beyond the last block -
+        const uint32_t B0 = e0 >> 5; // block of the first point
         auto target_pos = [&](int t) -> uint32_t { return t < nsel ? e0 + (uint32_t)sSelIdx[t] : e1 - 1; };
         // four lanes per target, eight positions each: from the target's block boundary to the target (head: to the position before
-        // the first point).  Their loads are issued first and are under way while the block sums are scanned
+        // the first point).  Their loads are issued first and are under way while the block entries are fetched
         const int pt = lane >> 2, ppart = lane & 3;
         const bool plive = pt < nsel || pt == T_TAIL || pt == T_HEAD;
         uint32_t pqs = 1, pqe = 0; // inclusive range; empty when pqe + 1 == pqs
@@ -2117,34 +2119,26 @@ __device__ __forceinline__ void k_tail_body(const FitArgs &a) {
         }
         uint32_t sxy = 0, sw = 0; // the target itself (the exclusive sum is the inclusive one less its moments)
         if (pt < nsel && ppart == 0) { sxy = xy[pqe]; sw = w16[pqe]; }
-        for (int i = tid; i < (MAXSEL + 2) * 6; i += NTH) sF6[i / 6][i % 6] = 0;
-        wave_sync();
-        {
-            const int nfull = (int)(blk_l - B0); // blocks B0 .. blk_l - 1: what a target's prefix can need
-            // lane t (< 13) knows where target t's prefix ends: the sums through the block before the target's
-            const int my_kk = lane <= nsel ? (int)((target_pos(lane < nsel ? lane : T_TAIL) >> 5) - B0) - 1 : -2;
-            long long carry[6] = {0, 0, 0, 0, 0, 0};
-            for (int rb = 0; rb < nfull; rb += 64) {
-                const int b = rb + lane;
-                long long v[6] = {0, 0, 0, 0, 0, 0};
-                if (b < nfull) {
-                    const long long *src = blk + (size_t)(B0 + (uint32_t)b) * 6;
+        if (lane <= nsel + 1) { // (the run tables, whose bytes the prefix tables take, were last read before 5a's closing barrier)
+            // lane t < nsel: target t, lane nsel: the tail, lane nsel + 1: the head (the block of the first point).  k_chunk filed the
+            // running sums of every span at its block ends: the sums through the block before the target's are one entry (nothing when
+            // that block is its span's first) plus the totals (block 29) of the spans between the cluster's first and the target's
+            const uint32_t bt = lane <= nsel ? target_pos(lane < nsel ? lane : T_TAIL) >> 5 : B0;
+            const uint32_t sp = bt / (CK_SPAN / 32);
+            long long v[6] = {0, 0, 0, 0, 0, 0};
+            if (bt > sp * (CK_SPAN / 32)) {
+                const long long *src = blk + (size_t)(bt - 1) * 6;
 #pragma unroll
-                    for (int q = 0; q < 6; q++) v[q] = src[q];
-                }
-#pragma unroll
-                for (int q = 0; q < 6; q++) v[q] = (long long)wave_scan_u64((unsigned long long)v[q]) + carry[q];
-                // lane t picks its target's prefix from the lane that holds it
-                const int srcl = my_kk - rb;
-                const bool mine = srcl >= 0 && srcl < 64;
-#pragma unroll
-                for (int q = 0; q < 6; q++) {
-                    const long long got = __shfl(v[q], mine ? srcl : 0, 64);
-                    if (mine) sF6[lane < nsel ? lane : T_TAIL][q] = got;
-                }
-#pragma unroll
-                for (int q = 0; q < 6; q++) carry[q] = readlane_i64(v[q], 63);
+                for (int q = 0; q < 6; q++) v[q] = src[q];
             }
+            for (uint32_t s = s_lo; s < sp; s++) { // (two spans or fewer for all but the clusters above 960 points)
+                const long long *src = blk + ((size_t)s * (CK_SPAN / 32) + (CK_SPAN / 32 - 1)) * 6;
+#pragma unroll
+                for (int q = 0; q < 6; q++) v[q] += src[q];
+            }
+            const int slot = lane < nsel ? lane : (lane == nsel ? T_TAIL : T_HEAD);
+#pragma unroll
+            for (int q = 0; q < 6; q++) sF6[slot][q] = v[q];
         }
         wave_sync(); // the block prefixes are in place
         {
@@ -2158,11 +2152,8 @@ __device__ __forceinline__ void k_tail_body(const FitArgs &a) {
                 aMx += wx; aMy += wy; aW += Wt;
                 aMxx += (unsigned long long)wx * X; aMxy += (unsigned long long)wx * Y; aMyy += (unsigned long long)wy * Y;
             }
-#pragma unroll
-            for (int d = 2; d >= 1; d >>= 1) {
-                aMx += __shfl_xor(aMx, d, 64); aMy += __shfl_xor(aMy, d, 64); aW += __shfl_xor(aW, d, 64);
-                aMxx += __shfl_xor(aMxx, d, 64); aMxy += __shfl_xor(aMxy, d, 64); aMyy += __shfl_xor(aMyy, d, 64);
-            }
+            aMx = quad_sum_u32(aMx); aMy = quad_sum_u32(aMy); aW = quad_sum_u32(aW); // the four lanes of a target (DPP: all lanes are active here)
+            aMxx = quad_sum_u64(aMxx); aMxy = quad_sum_u64(aMxy); aMyy = quad_sum_u64(aMyy);
             if (plive && ppart == 0) {
                 const long long pv[6] = {(long long)aMx, (long long)aMy, (long long)aMxx, (long long)aMxy, (long long)aMyy, (long long)aW};
                 if (pt < nsel) {
@@ -2181,7 +2172,7 @@ __device__ __forceinline__ void k_tail_body(const FitArgs &a) {
         {
             long long tv[6];
 #pragma unroll
-            for (int q = 0; q < 6; q++) tv[q] = sF6[T_TAIL][q] + sPart[T_TAIL][q] - sPart[T_HEAD][q];
+            for (int q = 0; q < 6; q++) tv[q] = (sF6[T_TAIL][q] + sPart[T_TAIL][q]) - (sF6[T_HEAD][q] + sPart[T_HEAD][q]);
             total.Mx = tv[0]; total.My = tv[1]; total.Mxx = tv[2]; total.Mxy = tv[3]; total.Myy = tv[4]; total.W = tv[5];
         }
         auto rangeM = [&](int sa, int sb, int *N) { // points from maximum sa to maximum sb inclusive, going forward
@@ -2234,11 +2225,14 @@ __device__ __forceinline__ void k_tail_body(const FitArgs &a) {
                 if (e < best || (e == best && pk < bestc)) { best = e; bestc = pk; }
             }
         }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            double ob = __shfl_xor(best, d, 64);
-            int oc = __shfl_xor(bestc, d, 64);
-            if (ob < best || (ob == best && oc < bestc)) { best = ob; bestc = oc; }
+        {
+            // the wave's smallest (best, bestc) on the DPP ladder, `best` through its order-preserving integer image as in 5a: a lane's
+            // best is HUGE_VAL or a sum that passed `e < best`, never NaN; errors that compare equal have the same image once
+            // + 0.0 has made a -0.0 the +0.0 it equals
+            const unsigned long long bb = (unsigned long long)__double_as_longlong(best + 0.0);
+            unsigned long long bk = (bb >> 63) ? ~bb : (bb | (1ull << 63));
+            wave_argmin_u64_i32(bk, bestc);
+            best = __longlong_as_double((long long)((bk >> 63) ? (bk ^ (1ull << 63)) : ~bk));
         }
         if (best == HUGE_VAL) continue;
         FDBG(4);
@@ -2266,7 +2260,8 @@ __device__ __forceinline__ void k_tail_body(const FitArgs &a) {
     }
 }
 
-// Register budget: four waves per SIMD (128 registers, nothing spilled).  A build for five (96 registers, 59 of them spilled) once
+// Register budget: four waves per SIMD (128 registers; the code object says 118 used, no spilled register, no scratch — with the block
+// scan of 5b still in, it said 126, two spilled, 12 bytes of scratch).  A build for five (96 registers, 59 of them spilled) once
 // looked 7 % faster and was WRONG (detections missing at 1920x1080 and 2448x2048, copies of one frame differing): two v_readlane
 // reads of the chunk heads stood inside `if (lane < ...)` / `if (tid == 0)` blocks, where the lane they read may be switched off, and
 // the spill code restores active lanes only.  With every v_readlane where all lanes are active that build is correct — and 3 %
