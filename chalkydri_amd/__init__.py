@@ -5,5 +5,6 @@ Host-side mirror of the reference interface (crates/chalkydri-apriltags `Detecto
 the path runs in hand-written HIP kernels (csrc/*.hip, gfx950); there is no CPU fallback.
 """
 from ._lib import ChalkydriError, default_config, family, lib  # noqa: F401
+from .calibration import Board, Calibrator  # noqa: F401
 
-__all__ = ["ChalkydriError", "default_config", "family", "lib"]
+__all__ = ["Board", "Calibrator", "ChalkydriError", "default_config", "family", "lib"]

@@ -131,6 +131,25 @@ class TriOtsuInfo(C.Structure):
                 ("hi_final", C.c_int32), ("n_black", C.c_uint32), ("n_white", C.c_uint32), ("n_other", C.c_uint32), ("flags", C.c_uint32)]
 
 
+CK_CALIB_CONVERGED, CK_CALIB_STALLED, CK_CALIB_MAXIT, CK_CALIB_DEGENERATE = 0, 1, 2, 3
+CK_CALIB_MAX_FRAMES, CK_CALIB_MAX_POINTS = 4096, 4096
+CK_CALIB_FIX_DISTORTION, CK_CALIB_FIX_FOCAL = 0x1F0, 0x003
+
+
+class CalibParams(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("fixed_mask", C.c_uint32), ("max_iters", C.c_int32),
+                ("min_points_per_frame", C.c_int32), ("min_frames", C.c_int32)]
+
+
+class CalibProblem(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("n_frames", "start_offset", "point_offset", "pose_offset")]
+
+
+class CalibResult(C.Structure):
+    _fields_ = [("cam", OpenCV5), ("status", C.c_int32), ("iters", C.c_int32), ("n_frames", C.c_int32), ("n_points", C.c_int32),
+                ("rms", C.c_double), ("cost0", C.c_double), ("cost", C.c_double)]
+
+
 class VisionMeasurement(C.Structure):
     _fields_ = [("pose_x", C.c_double), ("pose_y", C.c_double), ("pose_rot", C.c_double),
                 ("std_x", C.c_double), ("std_y", C.c_double), ("std_rot", C.c_double), ("ts", C.c_uint64),
@@ -165,6 +184,7 @@ assert C.sizeof(RawFormat) == 8
 assert C.sizeof(PreviewParams) == 24
 assert C.sizeof(Rect) == 16 and C.sizeof(ExposureStats) == 6416 and C.sizeof(ExposureParams) == 96
 assert C.sizeof(TriOtsuParams) == 16 and C.sizeof(TriOtsuInfo) == 160
+assert C.sizeof(CalibParams) == 24 and C.sizeof(CalibProblem) == 16 and C.sizeof(CalibResult) == 112
 
 # per-frame status bits (include/chalkydri_hip.h)
 CK_FRAME_OK, CK_FRAME_POINTS_OVERFLOW, CK_FRAME_CLUSTERS_OVERFLOW, CK_FRAME_QUADS_OVERFLOW, CK_FRAME_DETS_OVERFLOW = 0, 1, 2, 4, 8

@@ -11,6 +11,7 @@
 #include "ck_preview.h"
 #include "ck_rawfmt.h"
 #include "ck_tri_otsu.h"
+#include "ck_calib.h"
 
 thread_local char ck_err_text[512] = "";
 
@@ -176,6 +177,7 @@ extern "C" void ck_destroy(ck_handle_t *h) {
     delete h->preview;
     delete h->exposure;
     delete h->tri_otsu;
+    delete h->calib;
     for (auto &e : h->ev) if (e) (void)hipEventDestroy(e);
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
     if (h->ev_join) (void)hipEventDestroy(h->ev_join);

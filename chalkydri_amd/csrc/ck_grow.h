@@ -1,4 +1,4 @@
-// The buffers of the on-demand workspaces (JPEG decode, raw staging, preview, exposure, tri-class threshold; one JPEG workspace per slot
+// The buffers of the on-demand workspaces (JPEG decode, raw staging, preview, exposure, tri-class threshold, calibration; one JPEG workspace per slot
 // of a JPEG ingest ring): each owns its memory, grows when a call needs more and releases it when its workspace is deleted.  DESIGN.md §4g.
 #ifndef CK_GROW_H
 #define CK_GROW_H
@@ -54,7 +54,7 @@ struct ck_pinned_buf { // pinned host memory
     }
 };
 
-// A handle's workspace of one on-demand feature (`slot` = ck_handle::jpeg, raw, preview, exposure or tri_otsu): created by the first call that
+// A handle's workspace of one on-demand feature (`slot` = ck_handle::jpeg, raw, preview, exposure, tri_otsu or calib): created by the first call that
 // needs it, deleted by ck_destroy.  nullptr: out of memory.
 template <typename W>
 static inline W *ck_workspace(W *&slot) {

@@ -227,6 +227,8 @@ struct ck_handle {
     struct ck_exposure_ws *exposure;
     // iterative tri-class Otsu threshold (ck_tri_otsu.hip, k_tri_otsu.hip): allocated by the first tri-class call, grown on demand
     struct ck_tri_otsu_ws *tri_otsu;
+    // camera calibration (ck_calib.hip, k_calib.hip): allocated by the first calibration call, grown on demand
+    struct ck_calib_ws *calib;
     bool fmerge_lds_allowed; // k_fmerge's dynamic LDS limit has been raised on this handle's device
 };
 

@@ -109,6 +109,15 @@ def _bind(L):
     L.ck_tri_otsu_solve.argtypes = [tp, vp, _P(A.TriOtsuInfo), vp]
     L.ck_cat_tri_otsu_batch.argtypes = [vp, tp, vp, i32, i32, i32, vp, vp, vp]
     L.ck_cat_tri_otsu.argtypes = [vp, vp, i32, i32, vp]
+    cp, cq, cr, cam = _P(A.CalibParams), _P(A.CalibProblem), _P(A.CalibResult), _P(A.OpenCV5)
+    L.ck_calib_params_default.argtypes = [cp, i32, i32]
+    L.ck_calib_params_default.restype = None
+    L.ck_calib_check.argtypes = [cp, cq, i32, vp, vp, vp, i32, i32, i32]
+    L.ck_calib_init.argtypes = [cp, cq, vp, vp, vp, i32, i32, i32, cam, vp, _P(i32)]
+    L.ck_calib_jacobian.argtypes = [cam, vp, vp, vp, i32, C.c_uint32, vp, vp]
+    L.ck_calib_refine_host.argtypes = [cp, cq, vp, vp, vp, i32, i32, i32, cam, vp, cr, vp]
+    L.ck_calib_refine_batch.argtypes = [vp, cp, cq, i32, vp, vp, vp, i32, i32, i32, cam, vp, cr, vp]
+    L.ck_calibrate_batch.argtypes = [vp, cp, cq, i32, vp, vp, vp, i32, i32, i32, cr, vp]
     L._ck_bound = True
     return L
 

@@ -953,5 +953,100 @@ class AprilTags {
     ck_process_params_t pp_{};
 };
 
+// ---- camera calibration (chalkydri_hip.h: ck_calib_*) ---------------------------------------------------------
+// The reference configurator's `Calibrator` (crates/configurator/src/calibration.rs:30-143): process() collects frames of a tag
+// board, calibrate() solves for the OpenCVModel5 of the camera.  Here the frames become point correspondences on the host and the
+// solve runs on the device.
+using OpenCv5 = ck_opencv5_t;
+
+// A grid of tags on a plane, ids row-major from the board's origin (the aprilgrid convention); x along a row, y along a column
+struct Board {
+    int rows = 6, cols = 6;
+    double tag_size = 0.088, tag_spacing = 0.3; // the defaults of the external crate's create_default_6x6_board(): measure the printed board
+    int first_id = 0;
+    double pitch() const { return tag_size * (1.0 + tag_spacing); }
+    bool has(int id) const { return id >= first_id && id < first_id + rows * cols; }
+    // board-plane coordinates of the tag's corners in ck_detection_t's corner order
+    std::array<std::array<double, 2>, 4> tag_corners(int id) const {
+        if (!has(id)) throw Panic("Board::tag_corners: no such tag", CK_EINVAL);
+        const int k = id - first_id;
+        const double s = tag_size / 2, cx = (k % cols) * pitch() + s, cy = (k / cols) * pitch() + s;
+        return {{{cx - s, cy + s}, {cx + s, cy + s}, {cx + s, cy - s}, {cx - s, cy - s}}};
+    }
+};
+
+class Calibrator {
+  public:
+    static constexpr int MIN_CORNERS = 24; // calibration.rs:30
+    struct Report {
+        ck_calib_result_t result{};
+        std::vector<std::array<double, 12>> poses; // board -> camera per kept frame: R row-major, t
+    };
+    explicit Calibrator(std::shared_ptr<Handle> h, const Board &board = Board(), int min_corners = MIN_CORNERS)
+        : h_(std::move(h)), board_(board), min_corners_(min_corners) {}
+
+    // Detects the board in the frames and keeps each one with at least min_corners corners of the board's ids decoded without a
+    // corrected bit; returns the number of frames kept so far, like the reference
+    size_t process(const std::vector<ck_image_u8_t> &imgs) {
+        const int n = (int)imgs.size(), cap = std::max(64, board_.rows * board_.cols);
+        std::vector<ck_detection_t> dets((size_t)n * cap);
+        std::vector<int32_t> counts(n);
+        check(ck_detect_batch(h_->get(), imgs.data(), n, dets.data(), cap, counts.data(), nullptr), "ck_detect_batch");
+        for (int i = 0; i < n; i++) {
+            std::vector<double> b, u;
+            std::vector<int> seen;
+            for (int k = 0; k < counts[i]; k++) {
+                const ck_detection_t &d = dets[(size_t)i * cap + k];
+                if (!board_.has(d.id) || d.hamming != 0 || d.family != 0 || std::find(seen.begin(), seen.end(), d.id) != seen.end()) continue;
+                seen.push_back(d.id);
+                const auto c = board_.tag_corners(d.id);
+                for (int j = 0; j < 4; j++) { b.push_back(c[j][0]); b.push_back(c[j][1]); u.push_back(d.p[j][0]); u.push_back(d.p[j][1]); }
+            }
+            if ((int)b.size() / 2 >= min_corners_) add_observations(b, u);
+        }
+        return starts_.size() - 1;
+    }
+    // one frame's correspondences from elsewhere: board_xy and image_uv as x0 y0 x1 y1 ...
+    void add_observations(const std::vector<double> &board_xy, const std::vector<double> &image_uv) {
+        if (board_xy.size() != image_uv.size() || board_xy.size() % 2) throw Panic("add_observations: size mismatch", CK_EINVAL);
+        bxy_.insert(bxy_.end(), board_xy.begin(), board_xy.end());
+        uv_.insert(uv_.end(), image_uv.begin(), image_uv.end());
+        starts_.push_back((int32_t)(bxy_.size() / 2));
+    }
+    size_t frames() const { return starts_.size() - 1; }
+    void clear() { bxy_.clear(); uv_.clear(); starts_.assign(1, 0); }
+
+    // calibration.rs:110-143: the model, or nullopt when the solve neither converged nor stalled at a finite rms; the frames are
+    // cleared either way, as the reference does.  fixed_mask: bits of ck_calib_params_t.fixed_mask.
+    std::optional<OpenCv5> calibrate(uint32_t fixed_mask = 0, Report *report = nullptr) {
+        ck_calib_params_t p;
+        ck_calib_params_default(&p, h_->config().width, h_->config().height);
+        p.fixed_mask = fixed_mask;
+        p.min_points_per_frame = std::max(4, min_corners_);
+        const int F = (int)frames();
+        Report r;
+        r.poses.resize(F);
+        std::optional<OpenCv5> out;
+        if (F >= p.min_frames) {
+            const ck_calib_problem_t q{F, 0, 0, 0};
+            check(ck_calibrate_batch(h_->get(), &p, &q, 1, bxy_.data(), uv_.data(), starts_.data(), starts_.back(), F + 1, F, &r.result,
+                                     F ? r.poses[0].data() : nullptr), "ck_calibrate_batch");
+            if ((r.result.status == CK_CALIB_CONVERGED || r.result.status == CK_CALIB_STALLED) && std::isfinite(r.result.rms)) out = r.result.cam;
+        } else {
+            r.result.status = CK_CALIB_DEGENERATE;
+        }
+        if (report) *report = r;
+        clear();
+        return out;
+    }
+
+  private:
+    std::shared_ptr<Handle> h_;
+    Board board_;
+    int min_corners_;
+    std::vector<double> bxy_, uv_;
+    std::vector<int32_t> starts_{0};
+};
+
 } // namespace chalkydri
 #endif // CHALKYDRI_HPP

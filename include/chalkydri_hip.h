@@ -760,6 +760,96 @@ int ck_exposure_stats(ck_handle_t *h, const int32_t *frames, int32_t n, const ck
 int ck_exposure_stats_ingested(ck_ingest_t *ing, int32_t slot, const int32_t *frames, int32_t n, const ck_exposure_params_t *p,
                                const ck_rect_t *roi, ck_exposure_stats_t *out);
 
+/* ---- camera calibration: intrinsics from board points, batched Levenberg-Marquardt ---------------------------------------
+ * What the reference's configurator computes with `Calibrator::calibrate` (crates/configurator/src/calibration.rs:110-143): the
+ * nine OpenCVModel5 parameters of a camera and one board pose per frame from point correspondences of a planar board.  The solver
+ * takes correspondences, not frames; one problem calibrates one camera, and a batch of problems (leave-frames-out subsets of one
+ * capture, say) is solved in one call, one workgroup per problem.  DESIGN.md §4j is the contract: the forward model is the one
+ * ck_unproject_opencv5 inverts, poses are kept as rotation matrices and updated through the Cayley map, and the whole solve uses
+ * only + - * / sqrt on doubles in a fixed order, so ck_calib_refine_host and ck_calib_refine_batch return the same bytes.
+ * Shared arrays of a call: board_xy [n_points_total][2] (metres, board plane, Z = 0), image_uv [n_points_total][2] (pixels),
+ * frame_start [n_starts_total] and the pose arrays [n_frames_total][12] (R row-major board -> camera, then t).  Frame f of a problem
+ * owns the points point_offset + frame_start[start_offset + f] .. point_offset + frame_start[start_offset + f + 1] and the pose
+ * pose_offset + f. */
+enum {
+    CK_CALIB_CONVERGED = 0,  /* an accepted step lowered the cost by at most 1e-14 of it, or the cost fell below 1e-20 */
+    CK_CALIB_STALLED = 1,    /* the damping passed 1e30 without an acceptable step: the numerical floor of this start */
+    CK_CALIB_MAXIT = 2,      /* max_iters outer iterations (accepted or rejected) */
+    CK_CALIB_DEGENERATE = 3  /* no start (ck_calib_init) or a start that cannot be evaluated; the other fields: see ck_calib_result_t */
+};
+#define CK_CALIB_MAX_FRAMES 4096 /* per problem */
+#define CK_CALIB_MAX_POINTS 4096 /* per frame */
+typedef struct ck_calib_params {
+    int32_t width, height;         /* of the image, >= 16: the start's principal point is ((w-1)/2, (h-1)/2) */
+    uint32_t fixed_mask;           /* bit i freezes parameter i of ck_opencv5_t's order (fx fy cx cy k1 k2 p1 p2 k3) at its start */
+    int32_t max_iters;             /* 1..10000, default 100 */
+    int32_t min_points_per_frame;  /* >= 4, default 24 (the reference's MIN_CORNERS) */
+    int32_t min_frames;            /* >= 1, default 3 */
+} ck_calib_params_t;
+typedef struct ck_calib_problem {
+    int32_t n_frames;
+    int32_t start_offset;          /* first of this problem's n_frames + 1 entries of frame_start[], non-decreasing */
+    int32_t point_offset;          /* added to those entries: index into board_xy / image_uv */
+    int32_t pose_offset;           /* first of this problem's poses in the pose arrays */
+} ck_calib_problem_t;
+#define CK_CALIB_FIX_DISTORTION 0x1F0u /* fixed_mask: k1 k2 p1 p2 k3 */
+#define CK_CALIB_FIX_FOCAL 0x003u      /* fixed_mask: fx fy */
+typedef struct ck_calib_result {
+    ck_opencv5_t cam;              /* the best accepted parameters */
+    int32_t status;                /* CK_CALIB_* */
+    int32_t iters;                 /* outer iterations, accepted or rejected */
+    int32_t n_frames, n_points;
+    double rms;                    /* sqrt(cost / n_points), pixels */
+    double cost0, cost;            /* sum of squared pixel residuals at the start and at cam; DEGENERATE: cam = the start, the
+                                    * poses the start's, rms = cost0 = cost = 0, iters = 0 */
+} ck_calib_result_t;
+void ck_calib_params_default(ck_calib_params_t *p, int32_t width, int32_t height);
+/* What every calibration entry point refuses, in this order, before it touches a device.  CK_EINVAL: a null pointer; n_problems
+ * < 0; width or height < 16; max_iters outside 1..10000; min_points_per_frame < 4; min_frames < 1; a problem with fewer than
+ * min_frames frames, offsets outside the arrays, a frame_start run that decreases or leaves the arrays, a frame with fewer than
+ * min_points_per_frame points; a coordinate that is not finite.  CK_ECAPACITY: a problem with more than CK_CALIB_MAX_FRAMES frames
+ * or a frame with more than CK_CALIB_MAX_POINTS points.  Host only. */
+int ck_calib_check(const ck_calib_params_t *p, const ck_calib_problem_t *problems, int32_t n_problems, const double *board_xy,
+                   const double *image_uv, const int32_t *frame_start, int32_t n_points_total, int32_t n_starts_total,
+                   int32_t n_frames_total);
+/* The start of one problem, on the host (no device needed): per frame a homography by the normalised DLT (h33 = 1, 8 x 8 normal
+ * equations, Gaussian elimination with partial pivoting), the principal point at the image centre, 1 / fx^2 and 1 / fy^2 by least
+ * squares over two orthogonality equations per frame, zero distortion, and per frame the pose from K^-1 H.  poses0 [n_frames_total][12], written at the problem's pose_offset.  *status_out = CK_CALIB_CONVERGED (a start exists) or
+ * CK_CALIB_DEGENERATE (singular systems, a focal length that is not positive: frames that are all parallel to the image plane, which
+ * leave the focal equations' two columns within sin^2 = 1e-4 of parallel, collinear points;
+ * cam0_out and the problem's poses are zero then).  Errors: ck_calib_check's. */
+int ck_calib_init(const ck_calib_params_t *p, const ck_calib_problem_t *problem, const double *board_xy, const double *image_uv,
+                  const int32_t *frame_start, int32_t n_points_total, int32_t n_starts_total, int32_t n_frames_total,
+                  ck_opencv5_t *cam0_out, double *poses0, int32_t *status_out);
+/* The solver's residuals and analytic Jacobian of n observations of one frame, on the host: r_out [n][2] = projection - image_uv,
+ * J_out [n][2][15] = d r / d (fx fy cx cy k1 k2 p1 p2 k3, rotation increment [3], translation increment [3]) at a zero pose
+ * increment, where the increment (w, t) moves the pose to (R C(w), t + dt) with the Cayley map C; columns of frozen intrinsics are
+ * zero.  pose: 12 doubles.  CK_EINVAL: a null pointer, n < 0. */
+int ck_calib_jacobian(const ck_opencv5_t *cam, const double *pose, const double *board_xy, const double *image_uv, int32_t n,
+                      uint32_t fixed_mask, double *r_out, double *J_out);
+/* Levenberg-Marquardt over 9 + 6 n_frames parameters from a start, on the host, one thread: the bitwise specification of the
+ * device solver.  poses0 and poses_out [n_frames_total][12] (read and written at the problem's pose_offset; they
+ * may be the same array).  A start that is not finite, has fx or fy <= 0 or whose cost is not finite: CK_OK with status DEGENERATE.
+ * Errors: ck_calib_check's, CK_ENOMEM. */
+int ck_calib_refine_host(const ck_calib_params_t *p, const ck_calib_problem_t *problem, const double *board_xy, const double *image_uv,
+                         const int32_t *frame_start, int32_t n_points_total, int32_t n_starts_total, int32_t n_frames_total,
+                         const ck_opencv5_t *cam0, const double *poses0, ck_calib_result_t *result, double *poses_out);
+/* The same for n_problems problems on the handle's stream, one workgroup of 256 threads per problem with the whole iteration
+ * inside the kernel; every byte of results and of the problems' poses equals ck_calib_refine_host's.  cams0 [n_problems].  All
+ * arrays are host arrays.  Returns when the outputs are complete.  The workspace (the inputs, 312 doubles per frame of the call
+ * and the results on the device; allocated by the first call, grown on demand; ck_create allocates none of it) is not bound to the
+ * handle's geometry or max_batch, and the staged frames and the detection workspace stay as they are.  Errors: ck_calib_check's
+ * (the handle among the null pointers), CK_ENOMEM. */
+int ck_calib_refine_batch(ck_handle_t *h, const ck_calib_params_t *p, const ck_calib_problem_t *problems, int32_t n_problems,
+                          const double *board_xy, const double *image_uv, const int32_t *frame_start, int32_t n_points_total,
+                          int32_t n_starts_total, int32_t n_frames_total, const ck_opencv5_t *cams0, const double *poses0,
+                          ck_calib_result_t *results, double *poses_out);
+/* ck_calib_init per problem, then ck_calib_refine_batch: what Calibrator::calibrate does in one call.  A problem without a start
+ * comes back DEGENERATE and does not disturb its neighbours. */
+int ck_calibrate_batch(ck_handle_t *h, const ck_calib_params_t *p, const ck_calib_problem_t *problems, int32_t n_problems,
+                       const double *board_xy, const double *image_uv, const int32_t *frame_start, int32_t n_points_total,
+                       int32_t n_starts_total, int32_t n_frames_total, ck_calib_result_t *results, double *poses_out);
+
 /* ---- multi-GPU: the final pose gather ----------------------------------------------------------------------------------
  * Frames shard over GPUs without any data-path collective (one handle, one process or host thread per GPU).  The only
  * exchange is the gather of the 64-byte records (the wire struct of crates/whacknet/src/lib.rs:43-66): ONE ncclAllGather
