@@ -71,6 +71,19 @@ class SqpnpResult(C.Structure):
                 ("std_devs", C.c_double * 3), ("yaw", C.c_double), ("energy", C.c_double)]
 
 
+CK_RIG_MAX_CAMS = 8
+
+
+class RigParams(C.Structure):
+    _fields_ = [("sqpnp", SqpnpParams), ("sign_change_error", C.c_double), ("rig_id", C.c_uint8), ("pad", C.c_uint8 * 7)]
+
+
+class RigResult(C.Structure):
+    _fields_ = [("valid", C.c_int32), ("n_tags", C.c_int32), ("rot", C.c_double * 9), ("pos", C.c_double * 3),
+                ("std_devs", C.c_double * 3), ("yaw", C.c_double), ("energy", C.c_double),
+                ("cam_tags", C.c_int32 * CK_RIG_MAX_CAMS), ("cam_rms", C.c_double * CK_RIG_MAX_CAMS)]
+
+
 class OpenCV5(C.Structure):
     _fields_ = [(k, C.c_double) for k in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3")]
 
@@ -185,6 +198,7 @@ assert C.sizeof(PreviewParams) == 24
 assert C.sizeof(Rect) == 16 and C.sizeof(ExposureStats) == 6416 and C.sizeof(ExposureParams) == 96
 assert C.sizeof(TriOtsuParams) == 16 and C.sizeof(TriOtsuInfo) == 160
 assert C.sizeof(CalibParams) == 24 and C.sizeof(CalibProblem) == 16 and C.sizeof(CalibResult) == 112
+assert C.sizeof(RigParams) == 32 and C.sizeof(RigResult) == 240
 
 # per-frame status bits (include/chalkydri_hip.h)
 CK_FRAME_OK, CK_FRAME_POINTS_OVERFLOW, CK_FRAME_CLUSTERS_OVERFLOW, CK_FRAME_QUADS_OVERFLOW, CK_FRAME_DETS_OVERFLOW = 0, 1, 2, 4, 8

@@ -12,6 +12,7 @@
 #include "ck_rawfmt.h"
 #include "ck_tri_otsu.h"
 #include "ck_calib.h"
+#include "ck_rig.h"
 
 thread_local char ck_err_text[512] = "";
 
@@ -151,6 +152,7 @@ extern "C" int ck_create(const ck_config_t *cfg, ck_handle_t **out) {
     h->n_raw_staged = -1;
     h->n_jpeg_color = -1;
     h->n_last_dets = -1;
+    h->n_pose_inputs = -1;
     h->w = cfg->width; h->h = cfg->height; h->qw = qw; h->qh = qh;
     h->npix = (size_t)qw * qh;
     h->tiles_x = (qw + CK_TW - 1) / CK_TW; h->tiles_y = (qh + CK_TH - 1) / CK_TH;
@@ -178,6 +180,7 @@ extern "C" void ck_destroy(ck_handle_t *h) {
     delete h->exposure;
     delete h->tri_otsu;
     delete h->calib;
+    delete h->rig;
     for (auto &e : h->ev) if (e) (void)hipEventDestroy(e);
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
     if (h->ev_join) (void)hipEventDestroy(h->ev_join);

@@ -211,6 +211,8 @@ struct ck_handle {
     // ck_preview_jpeg_color.  -1: the frames were staged another way since
     int n_jpeg_color, jpeg_color_orientation;
     int n_last_pose;     // records the last ck_process_* call left in ws.d_meas (what ck_gather_poses may send); -1: none yet
+    int n_pose_inputs;   // frames whose glue records (ws.d_problems, d_pose_tags, d_bearings) and detection counts the last ck_process_* call
+                         // left in ws (what ck_rig_process_last reads in place); -1: none yet, or a later pipeline call rewrote the workspace
     int n_last_dets;     // frames whose detections the last ck_detect_* / ck_process_* call left in ws (what ck_last_tag_poses reads);
                          // -1: none yet, or a later call (ck_clusters_batch, ck_quads_batch, a failed pipeline) rewrote the workspace
     // per-tag pose (k_tagpose.hip): allocated by the first ck_estimate_tag_poses / ck_last_tag_poses, max_batch * det_cap entries
@@ -229,6 +231,8 @@ struct ck_handle {
     struct ck_tri_otsu_ws *tri_otsu;
     // camera calibration (ck_calib.hip, k_calib.hip): allocated by the first calibration call, grown on demand
     struct ck_calib_ws *calib;
+    // camera rig (k_rigpnp.hip): allocated by the first rig call, grown on demand
+    struct ck_rig_ws *rig;
     bool fmerge_lds_allowed; // k_fmerge's dynamic LDS limit has been raised on this handle's device
 };
 
@@ -363,6 +367,7 @@ int ck_detect_frames(ck_handle *h, const ck_dev_image &img, int n, ck_detection_
 int ck_process_frames(ck_handle *h, const ck_dev_image &img, int n, const ck_process_params_t *pp, const double *gyro,
                       const uint8_t *has_gyro, ck_vision_measurement_t *out, int32_t *valid);
 // glue + SQPnP + measurement on the detections left on the device by the last pipeline run
+int ck_launch_sqpnp_last(ck_handle *h, int n, const ck_sqpnp_params_t *prm, hipStream_t stream); // k_sqpnp.hip
 int ck_run_pose(ck_handle *h, int n, const ck_process_params_t *pp, const double *gyro, const uint8_t *has_gyro,
                 ck_vision_measurement_t *out, int32_t *valid, bool upload_field = true, bool sync = true);
 

@@ -1,0 +1,26 @@
+// Camera rig: what k_rigpnp.hip (kernel and entry points) and the handle (ck_api.hip) share; ck_rig_c.h is the part the
+// host twin (plain C) shares too.
+#ifndef CK_RIG_H
+#define CK_RIG_H
+
+#include "ck_grow.h"
+#include "ck_rig_c.h"
+
+#define CK_RIG_POINT_DOUBLES 7 // per point of the first pass: world point [3], ray direction in the robot frame [3], camera index
+
+// Workspace, allocated by the first rig call and grown on demand (ck_create allocates none of it)
+struct ck_rig_ws {
+    ck_dev_buf<double> d_points;            // [n][max_points][CK_RIG_POINT_DOUBLES] the kernel's first pass
+    ck_dev_buf<ck_rig_result_t> d_res;      // [n]
+    ck_dev_buf<double> d_gyro;              // [n]
+    ck_dev_buf<uint8_t> d_has_gyro;         // [n] (ck_rig_process_last)
+    ck_dev_buf<ck_vision_measurement_t> d_meas; // [n]
+    ck_dev_buf<int32_t> d_valid;            // [n]
+    ck_dev_buf<ck_sqpnp_problem_t> d_prob;  // [n_cams][n] the inputs of ck_rig_solve_batch
+    ck_dev_buf<ck_iso3_t> d_tags;
+    ck_dev_buf<double> d_bearings;
+    hipEvent_t ev[CK_RIG_MAX_CAMS] = {};    // ck_rig_process_last: "camera c's records are complete", recorded on its handle's stream
+    ~ck_rig_ws() { for (auto &e : ev) if (e) (void)hipEventDestroy(e); }
+};
+
+#endif

@@ -1,0 +1,493 @@
+/* ck_rig_host.c — the rig solver on the host, one thread, plain C: the specification of k_rig (k_rigpnp.hip) and what the CPU suite
+ * tests the arithmetic with.  DESIGN.md §4k has the formulas; every sum runs over cameras in index order and points in index order,
+ * every rotation and elimination in the order of the device code, so the two agree to round-off of the transcendental functions
+ * alone.  No device, no HIP header. */
+#include <float.h>
+#include <math.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "ck_rig_c.h"
+
+#define XY_STD_DEV_SCALAR 5.0
+#define THETA_STD_DEV_SCALAR 2.0
+#define MAX_TRUSTABLE_RMS 0.1
+#define MAX_GYRO_DELTA 30.0
+#define TAG_SIZE 0.1651
+#define CORNER_DISTANCE (TAG_SIZE / 2.0)
+#define PI_D 3.14159265358979323846
+
+static void quat_to_mat(const double q[4], double R[9]) {
+    double w = q[0], x = q[1], y = q[2], z = q[3];
+    double n = sqrt(w * w + x * x + y * y + z * z);
+    w /= n; x /= n; y /= n; z /= n;
+    R[0] = 1 - 2 * (y * y + z * z); R[1] = 2 * (x * y - z * w);     R[2] = 2 * (x * z + y * w);
+    R[3] = 2 * (x * y + z * w);     R[4] = 1 - 2 * (x * x + z * z); R[5] = 2 * (y * z - x * w);
+    R[6] = 2 * (x * z - y * w);     R[7] = 2 * (y * z + x * w);     R[8] = 1 - 2 * (x * x + y * y);
+}
+static void mat3_mul(const double A[9], const double B[9], double C[9]) {
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) C[i * 3 + j] = A[i * 3] * B[j] + A[i * 3 + 1] * B[3 + j] + A[i * 3 + 2] * B[6 + j];
+}
+static void mat3_vec(const double A[9], const double v[3], double o[3]) {
+    for (int i = 0; i < 3; i++) o[i] = A[i * 3] * v[0] + A[i * 3 + 1] * v[1] + A[i * 3 + 2] * v[2];
+}
+static double mat3_det(const double m[9]) {
+    return m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
+}
+static int mat3_try_inverse(const double m[9], double o[9]) {
+    double det = mat3_det(m);
+    if (det == 0.0) return 0;
+    o[0] = (m[4] * m[8] - m[5] * m[7]) / det; o[1] = (m[2] * m[7] - m[1] * m[8]) / det; o[2] = (m[1] * m[5] - m[2] * m[4]) / det;
+    o[3] = (m[5] * m[6] - m[3] * m[8]) / det; o[4] = (m[0] * m[8] - m[2] * m[6]) / det; o[5] = (m[2] * m[3] - m[0] * m[5]) / det;
+    o[6] = (m[3] * m[7] - m[4] * m[6]) / det; o[7] = (m[1] * m[6] - m[0] * m[7]) / det; o[8] = (m[0] * m[4] - m[1] * m[3]) / det;
+    return 1;
+}
+
+/* cyclic Jacobi of a symmetric n x n matrix (n = 3, 9), row-major; the columns of V are the eigenvectors.  Stop rule, sweep order and
+ * rotation formulas are jacobi3's (ck_mat3.h) and the 9 x 9 of the pose kernels. */
+static void jacobi_eigen(double *A, int n, double *V, double *w) {
+    for (int i = 0; i < n; i++)
+        for (int j = 0; j < n; j++) V[i * n + j] = (i == j);
+    double tot = 0;
+    for (int i = 0; i < n * n; i++) tot += A[i] * A[i];
+    const double stop = 1e-32 * tot;
+    for (int sweep = 0; sweep < 64; sweep++) {
+        double off = 0;
+        for (int i = 0; i < n; i++)
+            for (int j = i + 1; j < n; j++) off += A[i * n + j] * A[i * n + j];
+        if (off <= stop) break;
+        for (int p = 0; p < n; p++)
+            for (int q = p + 1; q < n; q++) {
+                double apq = A[p * n + q];
+                if (fabs(apq) < 1e-300) continue;
+                double app = A[p * n + p], aqq = A[q * n + q];
+                double theta = (aqq - app) / (2.0 * apq);
+                double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+                double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+                for (int k = 0; k < n; k++) { double akp = A[k * n + p], akq = A[k * n + q]; A[k * n + p] = c * akp - s * akq; A[k * n + q] = s * akp + c * akq; }
+                for (int k = 0; k < n; k++) { double apk = A[p * n + k], aqk = A[q * n + k]; A[p * n + k] = c * apk - s * aqk; A[q * n + k] = s * apk + c * aqk; }
+                for (int k = 0; k < n; k++) { double vkp = V[k * n + p], vkq = V[k * n + q]; V[k * n + p] = c * vkp - s * vkq; V[k * n + q] = s * vkp + c * vkq; }
+            }
+    }
+    for (int i = 0; i < n; i++) w[i] = A[i * n + i];
+}
+
+static void svd3(const double M[9], double U[9], double s[3], double V[9]) {
+    double MtM[9], Vt[9], w[3];
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) MtM[i * 3 + j] = M[0 + i] * M[0 + j] + M[3 + i] * M[3 + j] + M[6 + i] * M[6 + j];
+    jacobi_eigen(MtM, 3, Vt, w);
+    int idx[3] = {0, 1, 2};
+    for (int i = 0; i < 3; i++)
+        for (int j = i + 1; j < 3; j++)
+            if (w[idx[j]] > w[idx[i]]) { int t = idx[i]; idx[i] = idx[j]; idx[j] = t; }
+    for (int c = 0; c < 3; c++) {
+        s[c] = sqrt(w[idx[c]] > 0 ? w[idx[c]] : 0);
+        for (int r = 0; r < 3; r++) V[r * 3 + c] = Vt[r * 3 + idx[c]];
+    }
+    for (int c = 0; c < 3; c++) {
+        double v[3] = {V[c], V[3 + c], V[6 + c]}, u[3];
+        mat3_vec(M, v, u);
+        double n = sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
+        if (n > 1e-12 * (s[0] > 0 ? s[0] : 1.0)) { for (int r = 0; r < 3; r++) U[r * 3 + c] = u[r] / n; }
+        else if (c == 2) { /* complete a right-handed frame */
+            double ua[3] = {U[0], U[3], U[6]}, ub[3] = {U[1], U[4], U[7]};
+            double cr[3] = {ua[1] * ub[2] - ua[2] * ub[1], ua[2] * ub[0] - ua[0] * ub[2], ua[0] * ub[1] - ua[1] * ub[0]};
+            double cn = sqrt(cr[0] * cr[0] + cr[1] * cr[1] + cr[2] * cr[2]);
+            for (int r = 0; r < 3; r++) U[r * 3 + 2] = cn > 0 ? cr[r] / cn : (r == 2);
+        } else if (c == 1) { /* rank 1: the coordinate axis least aligned with u0 (first on ties), made orthogonal to u0 */
+            double u0[3] = {U[0], U[3], U[6]};
+            int k = 0;
+            for (int r = 1; r < 3; r++)
+                if (fabs(u0[r]) < fabs(u0[k])) k = r;
+            double e[3] = {0, 0, 0};
+            e[k] = 1.0;
+            double d = u0[k], g[3] = {e[0] - d * u0[0], e[1] - d * u0[1], e[2] - d * u0[2]};
+            double gn = sqrt(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
+            for (int r = 0; r < 3; r++) U[r * 3 + 1] = g[r] / gn;
+        } else { /* zero matrix: U = I */
+            for (int r = 0; r < 3; r++) U[r * 3 + 0] = (r == 0);
+        }
+    }
+}
+/* nearest rotation of a row-major 3x3 (U V^T with the chirality fix) */
+static void polar_rotation(const double M[9], double out[9]) {
+    double U[9], s[3], V[9], Vt[9];
+    svd3(M, U, s, V);
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) Vt[i * 3 + j] = V[j * 3 + i];
+    mat3_mul(U, Vt, out);
+    if (mat3_det(out) < 0.0) {
+        for (int r = 0; r < 3; r++) U[r * 3 + 2] = -U[r * 3 + 2];
+        mat3_mul(U, Vt, out);
+    }
+}
+static void nearest_so3(const double r_vec[9], double out[9]) { /* column-major in and out */
+    double M[9], rot[9];
+    for (int c = 0; c < 3; c++)
+        for (int r = 0; r < 3; r++) M[r * 3 + c] = r_vec[c * 3 + r];
+    polar_rotation(M, rot);
+    for (int c = 0; c < 3; c++)
+        for (int r = 0; r < 3; r++) out[c * 3 + r] = rot[r * 3 + c];
+}
+
+/* 15x15 LU with partial pivoting (first maximum of a column); 0 when a pivot is exactly zero */
+static int lu_solve15(double *A, double *b) {
+    const int n = 15;
+    for (int col = 0; col < n; col++) {
+        int piv = col;
+        double best = fabs(A[col * n + col]);
+        for (int r = col + 1; r < n; r++)
+            if (fabs(A[r * n + col]) > best) { best = fabs(A[r * n + col]); piv = r; }
+        if (best == 0.0) return 0;
+        if (piv != col) {
+            for (int k = 0; k < n; k++) { double t = A[col * n + k]; A[col * n + k] = A[piv * n + k]; A[piv * n + k] = t; }
+            double t = b[col]; b[col] = b[piv]; b[piv] = t;
+        }
+        for (int r = col + 1; r < n; r++) {
+            double f = A[r * n + col] / A[col * n + col];
+            if (f == 0.0) continue;
+            for (int k = col; k < n; k++) A[r * n + k] -= f * A[col * n + k];
+            b[r] -= f * b[col];
+        }
+    }
+    for (int r = n - 1; r >= 0; r--) {
+        double s = b[r];
+        for (int k = r + 1; k < n; k++) s -= A[r * n + k] * b[k];
+        b[r] = s / A[r * n + r];
+    }
+    return 1;
+}
+
+/* SQP refinement of one start: the KKT step [[Omega, J^T], [J, 0]] [d; lambda] = [-(Omega r - g); -h].  Returns r^T Omega r. */
+static double optimization(int max_iter, double tol_sq, double r[9], const double omega[81], const double g[9]) {
+    for (int it = 0; it < max_iter; it++) {
+        const double *c1 = r, *c2 = r + 3, *c3 = r + 6;
+        double h[6], J[54], lhs[225], rhs[15];
+        h[0] = c1[0] * c1[0] + c1[1] * c1[1] + c1[2] * c1[2] - 1.0;
+        h[1] = c2[0] * c2[0] + c2[1] * c2[1] + c2[2] * c2[2] - 1.0;
+        h[2] = c3[0] * c3[0] + c3[1] * c3[1] + c3[2] * c3[2] - 1.0;
+        h[3] = c1[0] * c2[0] + c1[1] * c2[1] + c1[2] * c2[2];
+        h[4] = c1[0] * c3[0] + c1[1] * c3[1] + c1[2] * c3[2];
+        h[5] = c2[0] * c3[0] + c2[1] * c3[1] + c2[2] * c3[2];
+        memset(J, 0, sizeof J);
+        for (int k = 0; k < 3; k++) {
+            J[0 * 9 + k] = 2.0 * c1[k]; J[1 * 9 + 3 + k] = 2.0 * c2[k]; J[2 * 9 + 6 + k] = 2.0 * c3[k];
+            J[3 * 9 + k] = c2[k]; J[3 * 9 + 3 + k] = c1[k];
+            J[4 * 9 + k] = c3[k]; J[4 * 9 + 6 + k] = c1[k];
+            J[5 * 9 + 3 + k] = c3[k]; J[5 * 9 + 6 + k] = c2[k];
+        }
+        memset(lhs, 0, sizeof lhs);
+        for (int i = 0; i < 9; i++)
+            for (int j = 0; j < 9; j++) lhs[i * 15 + j] = omega[i * 9 + j];
+        for (int i = 0; i < 6; i++)
+            for (int j = 0; j < 9; j++) { lhs[j * 15 + 9 + i] = J[i * 9 + j]; lhs[(9 + i) * 15 + j] = J[i * 9 + j]; }
+        for (int i = 0; i < 9; i++) {
+            double s = 0;
+            for (int j = 0; j < 9; j++) s += omega[i * 9 + j] * r[j];
+            rhs[i] = -(s - g[i]);
+        }
+        for (int i = 0; i < 6; i++) rhs[9 + i] = -h[i];
+        if (!lu_solve15(lhs, rhs)) break;
+        double n2 = 0;
+        for (int k = 0; k < 9; k++) { r[k] += rhs[k]; n2 += rhs[k] * rhs[k]; }
+        if (n2 < tol_sq) break;
+    }
+    double e = 0;
+    for (int i = 0; i < 9; i++) {
+        double s = 0;
+        for (int j = 0; j < 9; j++) s += omega[i * 9 + j] * r[j];
+        e += r[i] * s;
+    }
+    return e;
+}
+/* E(r) = r^T Omega r - 2 g^T r + c, from r^T Omega r */
+static double full_energy(double rOr, const double r[9], const double g[9], double c) {
+    double gr = 0;
+    for (int k = 0; k < 9; k++) gr += g[k] * r[k];
+    return (rOr - 2.0 * gr) + c;
+}
+
+/* ck_rig_c.h */
+int ck_rig_check(const ck_rig_params_t *params, int32_t n_cams, const ck_sqpnp_problem_t *problems, int32_t n, const void *tags,
+                 int32_t n_tags_total, const void *bearings, int32_t n_bearings_total, const void *gyro, const void *out,
+                 int32_t *max_points) {
+    if (!params || !problems || !gyro || !out || n < 0 || n_cams < 1 || n_cams > CK_RIG_MAX_CAMS || n_tags_total < 0 ||
+        n_bearings_total < 0 || (n_tags_total > 0 && !tags) || (n_bearings_total > 0 && !bearings)) return CK_EINVAL;
+    int32_t most = 0;
+    for (int s = 0; s < n; s++) {
+        int64_t pts = 0;
+        for (int c = 0; c < n_cams; c++) {
+            const ck_sqpnp_problem_t *p = &problems[(size_t)c * (size_t)n + (size_t)s];
+            if (p->n_tags < 0 || p->n_bearings < 0 || p->tag_offset < 0 || p->bearing_offset < 0 ||
+                (int64_t)p->tag_offset + p->n_tags > n_tags_total || (int64_t)p->bearing_offset + p->n_bearings > n_bearings_total ||
+                (int64_t)4 * p->n_tags != p->n_bearings) return CK_EINVAL;
+            pts += p->n_bearings;
+        }
+        if (pts > 0x3FFFFFFF) return CK_EINVAL;
+        if (pts > most) most = (int32_t)pts;
+    }
+    if (max_points) *max_points = most;
+    return CK_OK;
+}
+
+static void solve_step(const ck_rig_params_t *prm, int n_cams, const ck_sqpnp_problem_t *problems, int n, int step, const ck_iso3_t *tags,
+                       const double *bearings, double gyro, double *world, double *dir, int *cam_of, ck_rig_result_t *out) {
+    static const double cp[4][3] = {{0, -CORNER_DISTANCE, -CORNER_DISTANCE}, {0, CORNER_DISTANCE, -CORNER_DISTANCE},
+                                    {0, CORNER_DISTANCE, CORNER_DISTANCE}, {0, -CORNER_DISTANCE, CORNER_DISTANCE}};
+    double A[CK_RIG_MAX_CAMS][9], b[CK_RIG_MAX_CAMS][3], o[CK_RIG_MAX_CAMS][3];
+    int base[CK_RIG_MAX_CAMS + 1], total_tags = 0;
+    memset(out, 0, sizeof *out);
+    base[0] = 0;
+    for (int c = 0; c < n_cams; c++) {
+        const ck_sqpnp_problem_t *p = &problems[(size_t)c * (size_t)n + (size_t)step];
+        quat_to_mat(p->robot_to_cam.q, A[c]);
+        for (int k = 0; k < 3; k++) b[c][k] = p->robot_to_cam.t[k];
+        for (int i = 0; i < 3; i++) o[c][i] = -(A[c][i] * b[c][0] + A[c][3 + i] * b[c][1] + A[c][6 + i] * b[c][2]);
+        base[c + 1] = base[c] + 4 * p->n_tags;
+        total_tags += p->n_tags;
+    }
+    const int N = base[n_cams];
+    if (N < 3) return;
+    double tc[3] = {0, 0, 0}; /* sum of the tag centres, cameras and tags in index order */
+    for (int c = 0; c < n_cams; c++) {
+        const ck_sqpnp_problem_t *p = &problems[(size_t)c * (size_t)n + (size_t)step];
+        const ck_iso3_t *tg = tags + p->tag_offset;
+        const double *v = bearings + (size_t)3 * (size_t)p->bearing_offset;
+        for (int j = 0; j < 4 * p->n_tags; j++) {
+            const int i = base[c] + j, t = j >> 2;
+            double R[9], pt[3];
+            quat_to_mat(tg[t].q, R);
+            mat3_vec(R, cp[j & 3], pt);
+            for (int k = 0; k < 3; k++) world[i * 3 + k] = pt[k] + tg[t].t[k];
+            for (int k = 0; k < 3; k++) dir[i * 3 + k] = A[c][k] * v[3 * j] + A[c][3 + k] * v[3 * j + 1] + A[c][6 + k] * v[3 * j + 2];
+            cam_of[i] = c;
+        }
+        for (int t = 0; t < p->n_tags; t++)
+            for (int k = 0; k < 3; k++) tc[k] += tg[t].t[k];
+    }
+    double centroid[3];
+    for (int k = 0; k < 3; k++) {
+        double s = 0;
+        for (int i = 0; i < N; i++) s += world[i * 3 + k];
+        centroid[k] = s / (double)N;
+    }
+    double Qrr[81], Qrt[27], Qtt[9], qr[9], qt[3], q0 = 0, S[9];
+    memset(Qrr, 0, sizeof Qrr); memset(Qrt, 0, sizeof Qrt); memset(Qtt, 0, sizeof Qtt); memset(qr, 0, sizeof qr); memset(qt, 0, sizeof qt);
+    memset(S, 0, sizeof S);
+    for (int k = 0; k < N; k++) {
+        const double *u = dir + 3 * k, *oc = o[cam_of[k]];
+        const double X[3] = {world[k * 3] - centroid[0], world[k * 3 + 1] - centroid[1], world[k * 3 + 2] - centroid[2]};
+        const double sq = u[0] * u[0] + u[1] * u[1] + u[2] * u[2], inv = 1.0 / sq;
+        double P[9], Mo[3];
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) P[i * 3 + j] = (i == j ? 1.0 : 0.0) - (u[i] * u[j]) * inv;
+        for (int i = 0; i < 3; i++) Mo[i] = P[i * 3] * oc[0] + P[i * 3 + 1] * oc[1] + P[i * 3 + 2] * oc[2];
+        for (int i = 0; i < 9; i++) Qtt[i] += P[i];
+        for (int a = 0; a < 3; a++) {
+            for (int i = 0; i < 3; i++) {
+                for (int j = 0; j < 3; j++) Qrt[(3 * a + i) * 3 + j] += P[i * 3 + j] * X[a];
+                qr[3 * a + i] += X[a] * Mo[i];
+            }
+            for (int bb = 0; bb < 3; bb++)
+                for (int i = 0; i < 3; i++)
+                    for (int j = 0; j < 3; j++) Qrr[(3 * a + i) * 9 + 3 * bb + j] += (P[i * 3 + j] * X[a]) * X[bb];
+        }
+        for (int i = 0; i < 3; i++) qt[i] += Mo[i];
+        q0 += oc[0] * Mo[0] + oc[1] * Mo[1] + oc[2] * Mo[2];
+        for (int i = 0; i < 3; i++)
+            for (int j = i; j < 3; j++) S[i * 3 + j] += X[i] * X[j]; /* scatter of the centred points (upper triangle) */
+    }
+    double QttInv[9], omega[81], g[9], cc;
+    if (!mat3_try_inverse(Qtt, QttInv)) memset(QttInv, 0, sizeof QttInv);
+    for (int i = 0; i < 9; i++) {
+        const double t0 = Qrt[i * 3] * QttInv[0] + Qrt[i * 3 + 1] * QttInv[3] + Qrt[i * 3 + 2] * QttInv[6];
+        const double t1 = Qrt[i * 3] * QttInv[1] + Qrt[i * 3 + 1] * QttInv[4] + Qrt[i * 3 + 2] * QttInv[7];
+        const double t2 = Qrt[i * 3] * QttInv[2] + Qrt[i * 3 + 1] * QttInv[5] + Qrt[i * 3 + 2] * QttInv[8];
+        for (int j = 0; j < 9; j++) omega[i * 9 + j] = Qrr[i * 9 + j] - (t0 * Qrt[j * 3] + t1 * Qrt[j * 3 + 1] + t2 * Qrt[j * 3 + 2]);
+        g[i] = qr[i] - (t0 * qt[0] + t1 * qt[1] + t2 * qt[2]);
+    }
+    {
+        double w[3];
+        mat3_vec(QttInv, qt, w);
+        cc = q0 - (qt[0] * w[0] + qt[1] * w[1] + qt[2] * w[2]);
+    }
+    double Aw[81], V[81], ev[9];
+    memcpy(Aw, omega, sizeof Aw);
+    {   /* Coplanar points (one tag; tags on one wall) with normal n: R n is free, Omega has the exact null space {vec(a n^T)} and its
+         * "three smallest eigenvectors" would be an arbitrary basis of it that says nothing about the pose.  The eigenvectors are then
+         * taken on the complement: mu * sum_k v_k v_k^T, v_k = vec(e_k n^T), mu = trace(Q_rr) >= every eigenvalue of Omega, moves
+         * that space to the top of the spectrum.  The refinement keeps Omega itself. */
+        double Sw[9], Sv[9], sw[3];
+        S[3] = S[1]; S[6] = S[2]; S[7] = S[5];
+        memcpy(Sw, S, sizeof Sw);
+        jacobi_eigen(Sw, 3, Sv, sw);
+        int k = 0;
+        double wmin = sw[0], wmax = sw[0];
+        if (sw[1] < wmin) { wmin = sw[1]; k = 1; }
+        if (sw[2] < wmin) { wmin = sw[2]; k = 2; }
+        if (sw[1] > wmax) wmax = sw[1];
+        if (sw[2] > wmax) wmax = sw[2];
+        if (wmin <= CK_RIG_PLANAR_EPS * wmax) {
+            const double nrm[3] = {Sv[k], Sv[3 + k], Sv[6 + k]};
+            double mu = 0;
+            for (int i = 0; i < 9; i++) mu += Qrr[i * 9 + i];
+            for (int i = 0; i < 9; i++)
+                for (int j = 0; j < 9; j++)
+                    if (i % 3 == j % 3) Aw[i * 9 + j] += mu * (nrm[i / 3] * nrm[j / 3]);
+        }
+    }
+    jacobi_eigen(Aw, 9, V, ev);
+    int idx[9] = {0, 1, 2, 3, 4, 5, 6, 7, 8};
+    for (int i = 1; i < 9; i++) { /* stable ascending order of the eigenvalues */
+        int v = idx[i], j = i - 1;
+        while (j >= 0 && ev[idx[j]] > ev[v]) { idx[j + 1] = idx[j]; j--; }
+        idx[j + 1] = v;
+    }
+    const double gc = cos(gyro), gs = sin(gyro);
+    double candR[6][9], candE[6];
+    for (int q = 0; q < 6; q++) {
+        const int t = q >> 1;
+        const double sign = (q & 1) ? 1.0 : -1.0;
+        double guess[9], *r = candR[q];
+        for (int k = 0; k < 9; k++) guess[k] = V[k * 9 + idx[t]] * sign;
+        nearest_so3(guess, r);
+        double energy = full_energy(optimization(prm->sqpnp.max_iter, prm->sqpnp.tol_sq, r, omega, g), r, g, cc);
+        double dot = r[0] * gc + r[3] * gs; /* the robot's forward axis in the world is row 0 of R */
+        double ae = 1.0 - dot;
+        if (ae < 0.0) ae = 0.0;
+        candE[q] = energy + prm->sign_change_error * ae;
+    }
+    int order[6] = {0, 1, 2, 3, 4, 5};
+    for (int i = 1; i < 6; i++) { /* stable sort by penalised energy */
+        int v = order[i], j = i - 1;
+        while (j >= 0 && candE[order[j]] > candE[v]) { order[j + 1] = order[j]; j--; }
+        order[j + 1] = v;
+    }
+    int found = 0;
+    double best_score = DBL_MAX, bestRm[9], bestT[3], best_energy = 0;
+    for (int oi = 0; oi < 6; oi++) {
+        const double *r = candR[order[oi]];
+        double Rm[9], qtr[3], d[3], tl[3], Rc[3], t[3];
+        for (int c = 0; c < 3; c++)
+            for (int rr = 0; rr < 3; rr++) Rm[rr * 3 + c] = r[c * 3 + rr];
+        for (int j = 0; j < 3; j++) {
+            double s = 0;
+            for (int i = 0; i < 9; i++) s += Qrt[i * 3 + j] * r[i];
+            qtr[j] = s;
+        }
+        for (int k = 0; k < 3; k++) d[k] = qt[k] - qtr[k];
+        mat3_vec(QttInv, d, tl);
+        mat3_vec(Rm, centroid, Rc);
+        for (int k = 0; k < 3; k++) t[k] = tl[k] - Rc[k];
+        int behind = 0;
+        for (int i = 0; i < N; i++) {
+            const int c = cam_of[i];
+            double pr[3];
+            mat3_vec(Rm, world + 3 * i, pr);
+            for (int k = 0; k < 3; k++) pr[k] += t[k];
+            if (!((A[c][6] * pr[0] + A[c][7] * pr[1] + A[c][8] * pr[2]) + b[c][2] > 0.0)) behind = 1;
+        }
+        if (behind) continue;
+        if (candE[order[oi]] < best_score) {
+            best_score = candE[order[oi]];
+            memcpy(bestRm, Rm, sizeof Rm);
+            memcpy(bestT, t, sizeof t);
+            found = 1;
+        }
+    }
+    if (!found) return;
+    /* The pose that is returned: R^ = polar(R), the rotation next to the refinement's last iterate (which meets the constraints to
+     * round-off only), and t.  Per camera: its tags and the RMS point-to-ray distance of its own points at that pose.  The squared
+     * distances, summed per camera and then over the cameras, are E again, without the cancellation of the quadratic form (terms
+     * of the size of |o|^2 * points against a sum of noise^2) and, taken ON the constraint manifold, without the first-order
+     * sensitivity to how far off it the iterate ended: that sum is the energy the record and the standard deviations carry. */
+    double bestR[9];
+    polar_rotation(bestRm, bestR);
+    best_energy = 0;
+    for (int c = 0; c < n_cams; c++) {
+        const int cnt = base[c + 1] - base[c];
+        out->cam_tags[c] = cnt / 4;
+        if (!cnt) continue;
+        double s = 0;
+        for (int i = base[c]; i < base[c + 1]; i++) {
+            const double *u = dir + 3 * i;
+            const double sq = u[0] * u[0] + u[1] * u[1] + u[2] * u[2], inv = 1.0 / sq;
+            double d[3], Pd[3];
+            mat3_vec(bestR, world + 3 * i, d);
+            for (int k = 0; k < 3; k++) d[k] = (d[k] + bestT[k]) - o[c][k];
+            /* d^T M d = |M d|^2 (M is a projector): the square of a small vector, not the product of a small with a large one */
+            const double along = (u[0] * d[0] + u[1] * d[1] + u[2] * d[2]) * inv;
+            for (int k = 0; k < 3; k++) Pd[k] = d[k] - u[k] * along;
+            s += Pd[0] * Pd[0] + Pd[1] * Pd[1] + Pd[2] * Pd[2];
+        }
+        out->cam_rms[c] = sqrt((s > 0.0 ? s : 0.0) / (double)cnt);
+        best_energy += s;
+    }
+    const double distance = sqrt(bestT[0] * bestT[0] + bestT[1] * bestT[1] + bestT[2] * bestT[2]);
+    {
+        const double n_points = (double)(total_tags * 4);
+        const double rms = sqrt((best_energy > 0.0 ? best_energy : 0.0) / n_points);
+        if (rms > MAX_TRUSTABLE_RMS) { out->std_devs[0] = out->std_devs[1] = out->std_devs[2] = DBL_MAX; }
+        else {
+            double mult = 1.0 + (distance / TAG_SIZE);
+            double xy = ((rms * mult) / sqrt((double)total_tags)) * XY_STD_DEV_SCALAR;
+            xy = xy < 0.01 ? 0.01 : (xy > 10.0 ? 10.0 : xy);
+            double th = (((rms / TAG_SIZE) * mult) / sqrt((double)total_tags)) * THETA_STD_DEV_SCALAR;
+            th = th < 0.05 ? 0.05 : (th > PI_D ? PI_D : th);
+            out->std_devs[0] = xy; out->std_devs[1] = xy; out->std_devs[2] = th;
+        }
+    }
+    /* world <- robot: rot = polar(R)^T, pos = -rot t; then the yaw pivot about the mean tag centre */
+    double robot_rot[9], robot_pos[3];
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) robot_rot[i * 3 + j] = bestR[j * 3 + i];
+    for (int k = 0; k < 3; k++) robot_pos[k] = -(robot_rot[k * 3] * bestT[0] + robot_rot[k * 3 + 1] * bestT[1] + robot_rot[k * 3 + 2] * bestT[2]);
+    for (int k = 0; k < 3; k++) tc[k] /= (double)total_tags;
+    double vision_yaw = atan2(robot_rot[3], robot_rot[0]);
+    double delta_yaw = gyro - vision_yaw;
+    delta_yaw = fmod(delta_yaw + PI_D, 2.0 * PI_D);
+    if (delta_yaw < 0) delta_yaw += 2.0 * PI_D;
+    delta_yaw -= PI_D;
+    double delta_deg = fabs(delta_yaw) * (180.0 / PI_D);
+    double weight = delta_deg / MAX_GYRO_DELTA;
+    weight = weight < 0 ? 0 : (weight > 1 ? 1 : weight);
+    weight = weight * weight * (3.0 - 2.0 * weight);
+    double applied = delta_yaw * weight;
+    double cz = cos(applied), sz = sin(applied);
+    double rotz[9] = {cz, -sz, 0, sz, cz, 0, 0, 0, 1};
+    double rel[3] = {robot_pos[0] - tc[0], robot_pos[1] - tc[1], robot_pos[2] - tc[2]}, piv[3];
+    mat3_vec(rotz, rel, piv);
+    for (int k = 0; k < 3; k++) out->pos[k] = tc[k] + piv[k];
+    mat3_mul(rotz, robot_rot, out->rot);
+    double yaw = 0.0;
+    if (fabs(out->rot[6]) < 1.0) { double pitch = -asin(out->rot[6]); double tcs = cos(pitch); yaw = atan2(out->rot[3] / tcs, out->rot[0] / tcs); }
+    out->yaw = yaw;
+    out->energy = best_energy;
+    out->n_tags = total_tags;
+    out->valid = 1;
+}
+
+void ck_rig_params_default(ck_rig_params_t *p) {
+    if (!p) return;
+    memset(p, 0, sizeof *p);
+    p->sqpnp.max_iter = 15;
+    p->sqpnp.tol_sq = 1e-16;
+    p->sign_change_error = 600.0;
+    p->rig_id = 255;
+}
+
+int ck_rig_solve_host(const ck_rig_params_t *params, int32_t n_cams, const ck_sqpnp_problem_t *problems, int32_t n, const ck_iso3_t *tags,
+                      int32_t n_tags_total, const double *bearings, int32_t n_bearings_total, const double *gyro, ck_rig_result_t *out) {
+    int32_t max_points = 0;
+    const int rc = ck_rig_check(params, n_cams, problems, n, tags, n_tags_total, bearings, n_bearings_total, gyro, out, &max_points);
+    if (rc != CK_OK) return rc;
+    const size_t cap = max_points > 0 ? (size_t)max_points : 1;
+    double *world = (double *)malloc(sizeof(double) * 6 * cap);
+    int *cam_of = (int *)malloc(sizeof(int) * cap);
+    if (!world || !cam_of) { free(world); free(cam_of); return CK_ENOMEM; }
+    for (int s = 0; s < n; s++) solve_step(params, n_cams, problems, n, s, tags, bearings, gyro[s], world, world + 3 * cap, cam_of, &out[s]);
+    free(world); free(cam_of);
+    return CK_OK;
+}

@@ -232,6 +232,7 @@ static int parts_wanted() {
 static int run_pipeline(ck_handle *h, const ck_dev_image &img, int n, int upto /*1 clusters, 2 quads, 3 all*/, ck_split *split = nullptr) {
     hipEvent_t *ev = h->ev;
     h->n_last_dets = -1; // the workspace is rewritten from here on; it holds this call's detections only once they are all enqueued
+    h->n_pose_inputs = -1;
     CK_HIP(hipEventRecord(ev[1], h->stream));
     int rc = ck_run_threshold_segment(h, img, n);
     if (rc != CK_OK) return rc;
@@ -407,6 +408,7 @@ static int process_common(ck_handle *h, const ck_dev_image &img, int n, const ck
     }
     if (rc == CK_OK) rc = join_split(h, sp);
     h->n_last_pose = rc == CK_OK ? n : -1;
+    h->n_pose_inputs = h->n_last_pose;
     CK_HIP(hipEventRecord(h->ev[6], h->stream));
     CK_HIP(hipStreamSynchronize(h->stream));
     fill_stage_ms(h);

@@ -118,6 +118,13 @@ def _bind(L):
     L.ck_calib_refine_host.argtypes = [cp, cq, vp, vp, vp, i32, i32, i32, cam, vp, cr, vp]
     L.ck_calib_refine_batch.argtypes = [vp, cp, cq, i32, vp, vp, vp, i32, i32, i32, cam, vp, cr, vp]
     L.ck_calibrate_batch.argtypes = [vp, cp, cq, i32, vp, vp, vp, i32, i32, i32, cr, vp]
+    rp, rr, sp = _P(A.RigParams), _P(A.RigResult), _P(A.SqpnpProblem)
+    L.ck_rig_params_default.argtypes = [rp]
+    L.ck_rig_params_default.restype = None
+    L.ck_rig_solve_host.argtypes = [rp, i32, sp, i32, _P(A.Iso3), i32, vp, i32, vp, rr]
+    L.ck_rig_solve_batch.argtypes = [vp, rp, i32, sp, i32, _P(A.Iso3), i32, vp, i32, vp, rr]
+    L.ck_rig_process_last.argtypes = [_P(vp), i32, i32, rp, vp, vp, rr, _P(A.VisionMeasurement), _P(i32)]
+    L.ck_rig_time_last.argtypes = [_P(vp), i32, i32, rp, vp, vp, i32, vp, vp]
     L._ck_bound = True
     return L
 

@@ -1,0 +1,121 @@
+"""All the cameras of a robot fused into one robot pose: SQPnP over rays with different origins.
+
+RigSolver is the stand-alone solver over the C ABI (ck_rig_solve_batch on a handle's device, ck_rig_solve_host without one);
+AprilTagsRig runs one AprilTags task per camera and fuses what they left on the device (ck_rig_process_last).
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _abi as A
+from ._lib import check, lib
+from .detector import _bind
+
+RESULT_DTYPE = np.dtype([("valid", np.int32), ("n_tags", np.int32), ("rot", np.float64, (3, 3)), ("pos", np.float64, 3),
+                         ("std_devs", np.float64, 3), ("yaw", np.float64), ("energy", np.float64),
+                         ("cam_tags", np.int32, A.CK_RIG_MAX_CAMS), ("cam_rms", np.float64, A.CK_RIG_MAX_CAMS)])
+assert RESULT_DTYPE.itemsize == C.sizeof(A.RigResult)
+
+
+def pack_steps(steps):
+    """steps[s][c] = (tags [Iso3], bearings (4 * len(tags), 3), robot_to_cam Iso3) for camera c at step s, every step with the
+    same cameras.  Returns (n_cams, problems [n_cams * n] camera-major, tags array, bearings (m, 3))."""
+    n = len(steps)
+    n_cams = len(steps[0]) if n else 1
+    probs = (A.SqpnpProblem * max(n_cams * n, 1))()
+    tags, bear, nb = [], [], 0
+    for s, cams in enumerate(steps):
+        if len(cams) != n_cams:
+            raise ValueError("every step needs the same number of cameras")
+        for c, (iso, p2, rtc) in enumerate(cams):
+            p2 = np.asarray(p2, np.float64).reshape(-1, 3)
+            p = probs[c * n + s]
+            p.n_tags, p.n_bearings, p.tag_offset, p.bearing_offset, p.robot_to_cam = len(iso), len(p2), len(tags), nb, rtc
+            tags.extend(iso)
+            bear.append(p2)
+            nb += len(p2)
+    tarr = (A.Iso3 * max(len(tags), 1))(*tags)
+    barr = np.ascontiguousarray(np.concatenate(bear) if bear else np.zeros((0, 3)), np.float64)
+    return n_cams, probs, tarr, len(tags), barr
+
+
+class RigSolver:
+    def __init__(self, handle=None, rig_id=255):
+        """`handle`: an AprilTagDetector whose device and stream solve_batch runs on; solve_host needs none."""
+        self._L = _bind(lib())
+        self._det = handle
+        self.params = A.RigParams()
+        self._L.ck_rig_params_default(C.byref(self.params))
+        self.params.rig_id = rig_id
+
+    def max_iter(self, n):
+        self.params.sqpnp.max_iter = int(n)
+        return self
+
+    def tolerance(self, tol):
+        self.params.sqpnp.tol_sq = float(tol) * float(tol)
+        return self
+
+    def _solve(self, steps, gyro, host):
+        n = len(steps)
+        n_cams, probs, tarr, nt, barr = pack_steps(steps)
+        g = np.ascontiguousarray(gyro, np.float64).reshape(-1)
+        if len(g) != n:
+            raise ValueError("one gyro heading per step")
+        g = g if n else np.zeros(1)
+        res = np.zeros(max(n, 1), RESULT_DTYPE)
+        rp = res.ctypes.data_as(C.POINTER(A.RigResult))
+        if host:
+            check(self._L.ck_rig_solve_host(C.byref(self.params), n_cams, probs, n, tarr, nt, barr.ctypes.data, len(barr),
+                                            g.ctypes.data, rp), "ck_rig_solve_host")
+        else:
+            if self._det is None:
+                raise RuntimeError("RigSolver.solve_batch needs a device handle (pass an AprilTagDetector)")
+            check(self._L.ck_rig_solve_batch(self._det._h, C.byref(self.params), n_cams, probs, n, tarr, nt, barr.ctypes.data,
+                                             len(barr), g.ctypes.data, rp), "ck_rig_solve_batch")
+        return res[:n]
+
+    def solve_batch(self, steps, gyro):
+        """One robot pose per step on the device; steps as pack_steps takes them.  Returns a RESULT_DTYPE array."""
+        return self._solve(steps, gyro, False)
+
+    def solve_host(self, steps, gyro):
+        """The same on the host, one thread, no device."""
+        return self._solve(steps, gyro, True)
+
+
+class AprilTagsRig:
+    def __init__(self, tasks, rig_id=255):
+        """tasks: one AprilTags task per camera (1..8, all on one device); sizes, calibrations and mounts may differ."""
+        if not 1 <= len(tasks) <= A.CK_RIG_MAX_CAMS:
+            raise ValueError(f"a rig has 1..{A.CK_RIG_MAX_CAMS} cameras")
+        self.tasks = list(tasks)
+        self.solver = RigSolver(self.tasks[0].detector, rig_id)
+        self.solver.params.sqpnp = self.tasks[0]._pp.sqpnp
+        self.solver.params.sign_change_error = self.tasks[0]._pp.sign_change_error
+
+    def process_batch(self, frames_per_camera, gyro):
+        """frames_per_camera[c] = camera c's frames [n][h][w], one per step; gyro: per-step heading or None entries.  Runs every
+        task's process_batch, then fuses on the device.  Returns (rig records [n] of VisionMeasurement, rig valid flags,
+        per-camera (records, valid) list); `last_results` keeps the RESULT_DTYPE records of the call."""
+        if len(frames_per_camera) != len(self.tasks):
+            raise ValueError("one frame batch per camera")
+        n = len(frames_per_camera[0])
+        per_cam = [t.process_batch(f, gyro) for t, f in zip(self.tasks, frames_per_camera)]
+        if n == 0:
+            self.last_results = np.zeros(0, RESULT_DTYPE)
+            return (A.VisionMeasurement * 0)(), np.zeros(0, bool), per_cam
+        g = np.zeros(max(n, 1), np.float64)
+        has = np.zeros(max(n, 1), np.uint8)
+        for i in range(n):
+            gi = None if gyro is None else (gyro if np.isscalar(gyro) else gyro[i])
+            if gi is not None:
+                g[i], has[i] = gi, 1
+        res = np.zeros(max(n, 1), RESULT_DTYPE)
+        meas = (A.VisionMeasurement * max(n, 1))()
+        valid = (C.c_int32 * max(n, 1))()
+        hs = (C.c_void_p * len(self.tasks))(*[t.detector._h.value for t in self.tasks])
+        check(self.solver._L.ck_rig_process_last(hs, len(self.tasks), n, C.byref(self.solver.params), g.ctypes.data, has.ctypes.data,
+                                                 res.ctypes.data_as(C.POINTER(A.RigResult)), meas, valid), "ck_rig_process_last")
+        self.last_results = res[:n]
+        return (A.VisionMeasurement * n)(*meas[:n]), np.array(valid[:n], bool), per_cam

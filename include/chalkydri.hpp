@@ -953,6 +953,86 @@ class AprilTags {
     ck_process_params_t pp_{};
 };
 
+// ---- camera rig (chalkydri_hip.h: ck_rig_*) ----------------------------------------------------------------------
+// All the cameras of a robot fused into one robot pose.  One camera's view of a step: its known tags, the bearings of their
+// corners (four per tag) and its mount.
+struct RigView {
+    std::vector<sqpnp::Iso3> tags;
+    std::vector<sqpnp::Vec3> bearings;
+    sqpnp::Iso3 robot_to_cam;
+};
+class RigSolver {
+  public:
+    RigSolver() { ck_rig_params_default(&prm_); }                                     // solve_host alone: no device
+    explicit RigSolver(std::shared_ptr<Handle> h) : h_(std::move(h)) { ck_rig_params_default(&prm_); }
+    RigSolver &max_iter(size_t n) { prm_.sqpnp.max_iter = (int32_t)n; return *this; }
+    RigSolver &tolerance(double tol) { prm_.sqpnp.tol_sq = tol * tol; return *this; }
+    RigSolver &rig_id(uint8_t id) { prm_.rig_id = id; return *this; }
+    const ck_rig_params_t &params() const { return prm_; }
+    // steps[s][c] = camera c at step s (every step with the same cameras); gyro[s] = the heading of step s.  On the device ...
+    std::vector<ck_rig_result_t> solve_batch(const std::vector<std::vector<RigView>> &steps, const std::vector<double> &gyro) const {
+        if (!h_) throw Panic("RigSolver::solve_batch needs a handle", CK_EINVAL);
+        return solve(steps, gyro, false);
+    }
+    // ... and on the host, one thread
+    std::vector<ck_rig_result_t> solve_host(const std::vector<std::vector<RigView>> &steps, const std::vector<double> &gyro) const {
+        return solve(steps, gyro, true);
+    }
+
+  private:
+    std::vector<ck_rig_result_t> solve(const std::vector<std::vector<RigView>> &steps, const std::vector<double> &gyro, bool host) const {
+        const int n = (int)steps.size(), n_cams = n ? (int)steps[0].size() : 1;
+        if (gyro.size() != steps.size()) throw Panic("RigSolver: one gyro heading per step", CK_EINVAL);
+        std::vector<ck_sqpnp_problem_t> probs((size_t)n_cams * n + 1);
+        std::vector<ck_iso3_t> tags;
+        std::vector<double> b;
+        for (int s = 0; s < n; s++) {
+            if ((int)steps[s].size() != n_cams) throw Panic("RigSolver: every step needs the same cameras", CK_EINVAL);
+            for (int c = 0; c < n_cams; c++) {
+                const RigView &v = steps[s][c];
+                ck_sqpnp_problem_t &p = probs[(size_t)c * n + s];
+                p = ck_sqpnp_problem_t{};
+                p.n_tags = (int32_t)v.tags.size(); p.n_bearings = (int32_t)v.bearings.size();
+                p.tag_offset = (int32_t)tags.size(); p.bearing_offset = (int32_t)(b.size() / 3);
+                p.robot_to_cam = v.robot_to_cam.raw();
+                for (const auto &t : v.tags) tags.push_back(t.raw());
+                for (const auto &x : v.bearings) b.insert(b.end(), x.begin(), x.end());
+            }
+        }
+        std::vector<ck_rig_result_t> out((size_t)n + 1);
+        const double g0 = 0.0;
+        const int rc = host ? ck_rig_solve_host(&prm_, n_cams, probs.data(), n, tags.data(), (int32_t)tags.size(), b.data(), (int32_t)(b.size() / 3),
+                                                n ? gyro.data() : &g0, out.data())
+                            : ck_rig_solve_batch(h_->get(), &prm_, n_cams, probs.data(), n, tags.data(), (int32_t)tags.size(), b.data(),
+                                                 (int32_t)(b.size() / 3), n ? gyro.data() : &g0, out.data());
+        check(rc, host ? "ck_rig_solve_host" : "ck_rig_solve_batch");
+        out.resize((size_t)n);
+        return out;
+    }
+    std::shared_ptr<Handle> h_;
+    ck_rig_params_t prm_{};
+};
+// After every task of `tasks` has processed the n frames of one instant each (AprilTags::process): the fused measurement of every
+// step, read from what the tasks left on the device.  results (optional): the full records.
+inline std::vector<std::pair<whacknet::VisionMeasurement, bool>> rig_process_last(const std::vector<AprilTags *> &tasks, const ck_rig_params_t &params,
+                                                                                  const std::vector<std::optional<double>> &gyro,
+                                                                                  std::vector<ck_rig_result_t> *results = nullptr) {
+    const int n = (int)gyro.size();
+    std::vector<ck_handle_t *> hs;
+    for (const AprilTags *t : tasks) hs.push_back(t ? t->handle()->get() : nullptr);
+    std::vector<double> g((size_t)n + 1);
+    std::vector<uint8_t> has((size_t)n + 1);
+    for (int i = 0; i < n; i++) { has[i] = gyro[i].has_value(); g[i] = gyro[i].value_or(0.0); }
+    std::vector<ck_rig_result_t> res((size_t)n + 1);
+    std::vector<whacknet::VisionMeasurement> out((size_t)n + 1);
+    std::vector<int32_t> valid((size_t)n + 1);
+    check(ck_rig_process_last(hs.data(), (int32_t)hs.size(), n, &params, g.data(), has.data(), res.data(), out.data(), valid.data()), "ck_rig_process_last");
+    std::vector<std::pair<whacknet::VisionMeasurement, bool>> r;
+    for (int i = 0; i < n; i++) r.emplace_back(out[i], valid[i] != 0);
+    if (results) results->assign(res.begin(), res.begin() + n);
+    return r;
+}
+
 // ---- camera calibration (chalkydri_hip.h: ck_calib_*) ---------------------------------------------------------
 // The reference configurator's `Calibrator` (crates/configurator/src/calibration.rs:30-143): process() collects frames of a tag
 // board, calibrate() solves for the OpenCVModel5 of the camera.  Here the frames become point correspondences on the host and the

@@ -850,6 +850,71 @@ int ck_calibrate_batch(ck_handle_t *h, const ck_calib_params_t *p, const ck_cali
                        const double *board_xy, const double *image_uv, const int32_t *frame_start, int32_t n_points_total,
                        int32_t n_starts_total, int32_t n_frames_total, ck_calib_result_t *results, double *poses_out);
 
+/* ---- camera rig: one robot pose from all the cameras of a robot ------------------------------------------
+ * SQPnP over rays with different origins.  The unknown is world -> robot (R, t): p_robot = R X + t; camera c is mounted by its
+ * robot_to_cam (A_c, b_c): p_cam = A_c p_robot + b_c.  A bearing v of camera c is the ray with direction u = A_c^T v through
+ * o_c = -A_c^T b_c, and the cost is sum_i (R X_i + t - o_i)^T (I - u_i u_i^T / u_i^T u_i) (R X_i + t - o_i) over the four corners
+ * of every tag of every camera: E(r) = r^T Omega r - 2 g^T r + c in r = vec(R) (column-major), minimised from SQPnP's six starts
+ * (for coplanar points, one tag or one wall, the three smallest eigenvectors outside Omega's exact null space {vec(a n^T)}).
+ * The candidate energy adds sign_change_error * max(0, 1 - (R00 cos gyro + R01 sin gyro)); the cheapest candidate with every point
+ * in front of its own camera wins.  One step = one instant: camera c's record of step s is problems[c * n + s], of which n_tags,
+ * n_bearings (= 4 * n_tags), the offsets and robot_to_cam are read.  A camera without tags at a step is skipped; a step without
+ * any tag has valid = 0 and an all-zero record.
+ * Beside ck_sqpnp_solve_batch: a rig of ONE camera returns its pose (1e-9) when the points are not coplanar.  Coplanar points (one
+ * tag; tags on one wall) are where the two differ on purpose: the per-camera solver's starts are then an arbitrary basis of a null
+ * space and its pose can be the other minimum of the planar ambiguity, this one takes its starts outside that space.  The switch is a
+ * threshold (smallest / largest eigenvalue of the points' scatter <= 1e-12): points a hair off a plane take SQPnP's own starts.
+ * std_devs takes the distance of the world origin from the ROBOT, the per-camera solver from the camera. */
+#define CK_RIG_MAX_CAMS 8
+typedef struct ck_rig_params {
+    ck_sqpnp_params_t sqpnp;       /* max_iter 15, tol_sq 1e-16 */
+    double sign_change_error;      /* 600.0 */
+    uint8_t rig_id;                /* camera_id of the fused measurement; default 255 */
+    uint8_t pad[7];
+} ck_rig_params_t;
+typedef struct ck_rig_result {
+    int32_t valid;                 /* 0: no pose; every other field is 0 then */
+    int32_t n_tags;                /* over all cameras */
+    double rot[9];                 /* pivoted robot rotation (world <- robot), row-major */
+    double pos[3];                 /* pivoted robot position */
+    double std_devs[3];            /* compute_std_devs of (E, |t|, n_tags) */
+    double yaw;
+    double energy;                 /* E at the returned pose, without the gyro penalty: the sum of the squared point-to-ray distances */
+    int32_t cam_tags[CK_RIG_MAX_CAMS]; /* tags camera c contributed */
+    double cam_rms[CK_RIG_MAX_CAMS];   /* sqrt(mean point-to-ray distance^2) of camera c's own points at the solution, metres */
+} ck_rig_result_t;
+void ck_rig_params_default(ck_rig_params_t *p);
+/* On the host, one thread, no device needed: the specification of the device solver (same summation and rotation order).
+ * CK_EINVAL: a null pointer (tags / bearings may be null when their total is 0), n < 0, n_cams outside 1..CK_RIG_MAX_CAMS, a
+ * record with a negative count or offset, offsets outside the arrays, 4 * n_tags != n_bearings.  CK_ENOMEM. */
+int ck_rig_solve_host(const ck_rig_params_t *params, int32_t n_cams, const ck_sqpnp_problem_t *problems, int32_t n,
+                      const ck_iso3_t *tags, int32_t n_tags_total, const double *bearings, int32_t n_bearings_total,
+                      const double *gyro, ck_rig_result_t *out);
+/* The same on the handle's stream, one workgroup per step.  Every pointer may be a host or a device pointer.  Returns when out is
+ * complete.  The workspace (inputs, results and 7 doubles per point of the call; allocated by the first call, grown on demand;
+ * ck_create allocates none of it) leaves the staged frames and the detection workspace as they are.  Errors: ck_rig_solve_host's
+ * (the handle among the null pointers), CK_ENOMEM. */
+int ck_rig_solve_batch(ck_handle_t *h, const ck_rig_params_t *params, int32_t n_cams, const ck_sqpnp_problem_t *problems, int32_t n,
+                       const ck_iso3_t *tags, int32_t n_tags_total, const double *bearings, int32_t n_bearings_total,
+                       const double *gyro, ck_rig_result_t *out);
+/* Fuses what the last ck_process_* call of each handle left on the device: frame s of every handle is step s.  The kernel reads
+ * the other handles' buffers in place, on handles[0]'s stream after an event on each of the others'.  Only out[n] (may be null)
+ * and meas[n], valid[n] come back; gyro, has_gyro, out, meas and valid may be host or device pointers.  meas[s].camera_id =
+ * rig_id, tag_count = the cameras' detection counts summed, saturated at 255; a step without a pose (no known tag in any camera,
+ * has_gyro[s] == 0, no candidate in front of the cameras) has valid 0 and the zeroed record with camera_id alone.  CK_EINVAL: a
+ * null pointer, n_cams outside 1..CK_RIG_MAX_CAMS, n < 1, handles on different devices, a handle whose last pipeline call was not
+ * a ck_process_* call of exactly n frames.  (The records are the library's own, written by that call: ck_rig_solve_host's checks of
+ * counts and offsets apply to the stand-alone calls only.)  CK_ENOMEM: the point scratch is sized for what the handles can hold,
+ * n * sum(4 * their detection capacity) * 56 bytes, not for what they saw. */
+int ck_rig_process_last(ck_handle_t *const *handles, int32_t n_cams, int32_t n, const ck_rig_params_t *params, const double *gyro,
+                        const uint8_t *has_gyro, ck_rig_result_t *out, ck_vision_measurement_t *meas, int32_t *valid);
+/* Measurement aid (tools/bench_rig.py): after the calls ck_rig_process_last needs, runs `iters` times on handles[0]'s stream, between two
+ * hipEvents each, (a) everything ck_rig_process_last enqueues (gyro in, k_rig, records out; written to ms_rig[iters]) and (b) k_sqpnp
+ * once per handle on the problems of its last ck_process_* call, back to back (ms_sqpnp[iters]): the solves the per-camera path pays.
+ * Errors as ck_rig_process_last, and CK_EINVAL for iters < 1 or a null array. */
+int ck_rig_time_last(ck_handle_t *const *handles, int32_t n_cams, int32_t n, const ck_rig_params_t *params, const double *gyro,
+                     const uint8_t *has_gyro, int32_t iters, float *ms_rig, float *ms_sqpnp);
+
 /* ---- multi-GPU: the final pose gather ----------------------------------------------------------------------------------
  * Frames shard over GPUs without any data-path collective (one handle, one process or host thread per GPU).  The only
  * exchange is the gather of the 64-byte records (the wire struct of crates/whacknet/src/lib.rs:43-66): ONE ncclAllGather
