@@ -133,6 +133,12 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 // a workgroup of one wave: its LDS operations are carried out in order, only the compiler has to keep them in place
 __device__ __forceinline__ void wave_sync() { asm volatile("" ::: "memory"); __builtin_amdgcn_wave_barrier(); asm volatile("" ::: "memory"); }
 
+// The thread's number for code inside a persistent loop over clusters.  Whatever depends on the thread number alone — LDS addresses,
+// lane predicates, the constants beside them — is invariant in such a loop, and the compiler forms all of it once, ahead of the loop, and
+// carries it through every cluster: dozens of registers the loop body then lacks (k_seq's multi-wave classes spilled for them).  An
+// opaque copy keeps these few instructions where they are used.
+__device__ __forceinline__ int loop_tid() { int t = threadIdx.x; asm volatile("" : "+v"(t)); return t; }
+
 template <int NTH>
 struct Block {
     static constexpr int NW = NTH / 64;
@@ -204,6 +210,25 @@ struct Block {
             }
             __syncthreads();
         }
+    }
+    // inclusive sum of one 32-bit value per thread together with the workgroup's maximum of a second one (non-negative, below 2^31),
+    // one table and one barrier pair for the two.  scratch: 2 * NW words of LDS
+    __device__ static uint32_t scan_incl_max(uint32_t v, uint32_t m, uint32_t *scratch, uint32_t *max_out) {
+        const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+        uint32_t x = wave_scan_u32(v);
+        uint32_t mx = (uint32_t)-wave_min_i32(-(int)m);
+        if (NW > 1) {
+            if (lane == 63) { scratch[wv] = x; scratch[NW + wv] = mx; }
+            __syncthreads();
+            uint32_t base = 0;
+            mx = scratch[NW];
+            for (int k = 0; k < NW; k++) { const uint32_t t = scratch[k]; if (k < wv) base += t; }
+            for (int k = 1; k < NW; k++) mx = max(mx, scratch[NW + k]);
+            x += base;
+            __syncthreads();
+        }
+        *max_out = mx;
+        return x;
     }
     // minima of four values per thread over the workgroup (every thread gets them), one barrier pair
     __device__ static void reduce_min4(int v[4], int *scratch /* [4*NW] */) {
@@ -318,8 +343,7 @@ __device__ __forceinline__ M6 moments_of(uint32_t xy, uint32_t Wt) {
 // compare-exchanges inside a thread, strides below 64*EPL are lane exchanges (ds_bpermute, no memory, no barrier); only
 // strides that cross a wave go through the LDS buffer.  Always sorts all CAP slots (unused ones hold ~0).
 template <int NTH, int EPL, int K, int J>
-__device__ __forceinline__ void sort_stage(unsigned long long (&k)[EPL], unsigned long long *buf) {
-    const int t = threadIdx.x;
+__device__ __forceinline__ void sort_stage(unsigned long long (&k)[EPL], unsigned long long *buf, const int t) {
     if constexpr (J < EPL) {
 #pragma unroll
         for (int e = 0; e < EPL; e++) {
@@ -363,30 +387,32 @@ __device__ __forceinline__ void sort_stage(unsigned long long (&k)[EPL], unsigne
 }
 template <int NTH, int EPL, int K, int J>
 struct SortJ {
-    __device__ __forceinline__ static void run(unsigned long long (&k)[EPL], unsigned long long *buf) {
-        sort_stage<NTH, EPL, K, J>(k, buf);
-        if constexpr (J > 1) SortJ<NTH, EPL, K, J / 2>::run(k, buf);
+    __device__ __forceinline__ static void run(unsigned long long (&k)[EPL], unsigned long long *buf, const int t) {
+        sort_stage<NTH, EPL, K, J>(k, buf, t);
+        if constexpr (J > 1) SortJ<NTH, EPL, K, J / 2>::run(k, buf, t);
     }
 };
 template <int NTH, int EPL, int K>
 struct SortK {
-    __device__ __forceinline__ static void run(unsigned long long (&k)[EPL], unsigned long long *buf) {
-        SortJ<NTH, EPL, K, K / 2>::run(k, buf);
-        if constexpr (K < NTH * EPL) SortK<NTH, EPL, K * 2>::run(k, buf);
+    __device__ __forceinline__ static void run(unsigned long long (&k)[EPL], unsigned long long *buf, const int t) {
+        SortJ<NTH, EPL, K, K / 2>::run(k, buf, t);
+        if constexpr (K < NTH * EPL) SortK<NTH, EPL, K * 2>::run(k, buf, t);
     }
 };
 template <int NTH, int EPL>
-__device__ __forceinline__ void sort_registers(unsigned long long (&k)[EPL], unsigned long long *buf) {
-    SortK<NTH, EPL, 2>::run(k, buf);
+__device__ __forceinline__ void sort_registers(unsigned long long (&k)[EPL], unsigned long long *buf, const int t) {
+    SortK<NTH, EPL, 2>::run(k, buf, t);
 }
 
 // keys of one cluster -> registers (thread t owns slots t*EPL .. t*EPL+EPL-1 of an NTH*EPL array), border-direction sum,
 // sort, write back.  Returns dot (valid on every thread).  `raw` = staged 8-byte points in sKeys[0..sz0).
-template <int NTH, int EPL>
+// RARE: this is the fallback of a sort that nearly always succeeds: what the network derives from the thread's number alone (a
+// direction flag per stage, the partners' addresses) must not be carried through every cluster of the loop around it (loop_tid).
+template <int NTH, int EPL, bool RARE>
 __device__ __forceinline__ long long keys_sort(unsigned long long *sKeys, long long *sScratch, int sz0, int xmin, int xmax, int ymin, int ymax,
                                                int normal_ok, int reversed_ok, bool do_sort = true) {
     using B = Block<NTH>;
-    const int tid = threadIdx.x;
+    const int tid = RARE ? loop_tid() : (int)threadIdx.x;
     unsigned long long kreg[EPL];
     long long dot = 0;
 #pragma unroll
@@ -405,7 +431,7 @@ __device__ __forceinline__ long long keys_sort(unsigned long long *sKeys, long l
     }
     dot = B::reduce_add(dot, sScratch);
     if (do_sort && ((dot < 0) ? reversed_ok : normal_ok)) { // uniform: skip the sort when the border direction is rejected anyway
-        sort_registers<NTH, EPL>(kreg, sKeys);
+        sort_registers<NTH, EPL>(kreg, sKeys, tid);
         __syncthreads();
 #pragma unroll
         for (int e = 0; e < EPL; e++) sKeys[tid * EPL + e] = kreg[e];
@@ -417,14 +443,16 @@ __device__ __forceinline__ long long keys_sort(unsigned long long *sKeys, long l
 // in-octant fraction, so bucket order = key order), then every key ranks itself inside its bucket.  About one LDS atomic,
 // two scatters and a handful of compares per key, against log^2(n)/2 compare-exchanges for the bitonic network.  A
 // cluster whose angles pile up in one bucket (more than BUCKET_LIMIT keys) is left to the bitonic path (*done = false;
-// the staged points are still intact then).  Same result either way: equal keys are adjacent, their order is irrelevant.
+// the key array has not been written then).  Same result either way: equal keys are adjacent, their order is irrelevant.
+// The points come in registers (rawp: the thread's packed points tid, tid + NTH, ...; the staged form is two shifts away), so the
+// key array is touched for the first time by the scatter into the buckets.
 constexpr int BUCKET_LIMIT = 32;
 template <int NTH, int EPLS>
-__device__ __forceinline__ long long keys_bucket_sort(unsigned long long *sKeys, uint32_t *hist /* [nb + 1] */, long long *sScratch, int sz0,
-                                                      int xmin, int xmax, int ymin, int ymax, int normal_ok, int reversed_ok, bool do_sort,
-                                                      bool *done) {
+__device__ __forceinline__ long long keys_bucket_sort(const ck_packed_point (&rawp)[EPLS], unsigned long long *sKeys, uint32_t *hist /* [nb + 1] */,
+                                                      long long *sScratch, int sz0, int xmin, int xmax, int ymin, int ymax, int normal_ok,
+                                                      int reversed_ok, bool do_sort, bool *done) {
     using B = Block<NTH>;
-    const int tid = threadIdx.x;
+    const int tid = loop_tid();
     int n2 = NTH;
     while (n2 < sz0) n2 <<= 1;
     int nb = n2 > 2048 ? 2048 : n2; // about one key per bucket; n2 >= NTH
@@ -438,7 +466,7 @@ __device__ __forceinline__ long long keys_bucket_sort(unsigned long long *sKeys,
         const int i = tid + e * NTH;
         kreg[e] = 0; meta[e] = 0;
         if (i < sz0) {
-            unsigned long long raw = sKeys[i];
+            const unsigned long long raw = ck_stage_point(rawp[e]);
             int px = (int)(raw & 0xFFFF), py = (int)((raw >> 16) & 0xFFFF);
             int pgx = (int)(signed char)((raw >> 32) & 0xFF), pgy = (int)(signed char)((raw >> 40) & 0xFF);
             const int dx = 4 * px - 2 * (xmin + xmax) - 1, dy = 4 * py - 2 * (ymin + ymax) + 1; // |.| < 2^15
@@ -449,7 +477,7 @@ __device__ __forceinline__ long long keys_bucket_sort(unsigned long long *sKeys,
     dot = B::reduce_add(dot, sScratch);
     *done = true;
     if (!do_sort || !((dot < 0) ? reversed_ok : normal_ok)) return dot; // uniform: rejected by border direction anyway
-    B::sync(); // histogram zeroed, every staged point read
+    if constexpr (B::NW == 1) B::sync(); // histogram zeroed (a larger workgroup has met at the barriers of the sum above)
 #pragma unroll
     for (int e = 0; e < EPLS; e++) {
         const int i = tid + e * NTH;
@@ -464,13 +492,11 @@ __device__ __forceinline__ long long keys_bucket_sort(unsigned long long *sKeys,
     B::sync();
     {   // exclusive scan of the counts in place (hist[nb] = sz0) and the largest count
         const int per = nb / NTH;
-        uint32_t sum = 0, mx = 0;
+        uint32_t sum = 0, mx = 0, worst;
         for (int q = 0; q < per; q++) { uint32_t c = hist[tid * per + q]; sum += c; mx = mx > c ? mx : c; }
-        long long total;
-        const long long incl = B::scan_incl((long long)sum, sScratch, &total);
-        const int worst = -B::reduce_min(-(int)mx, reinterpret_cast<int *>(sScratch));
-        if (worst > BUCKET_LIMIT) { *done = false; B::sync(); return dot; }
-        uint32_t run = (uint32_t)(incl - sum);
+        const uint32_t incl = B::scan_incl_max(sum, mx, reinterpret_cast<uint32_t *>(sScratch), &worst); // one barrier pair for the two
+        if (worst > (uint32_t)BUCKET_LIMIT) { *done = false; return dot; }
+        uint32_t run = incl - sum;
         for (int q = 0; q < per; q++) { uint32_t c = hist[tid * per + q]; hist[tid * per + q] = run; run += c; }
         if (tid == NTH - 1) hist[nb] = run;
     }
@@ -623,70 +649,135 @@ struct ChunkQueue {
     __device__ __forceinline__ int count() const { return (int)min(len, n_work - base); }
 };
 
-// 1. the packed points -> staged form in sKeys[0, sz0), and the bounding box (on every thread).  One coalesced pass; rawp holds the
-// thread's points tid, tid + NTH, ... when CAP / NTH <= RAWP_MAX (all of a lane's loads were issued before the first use: one
-// memory round trip), otherwise they are read from pts here.
+// 1. the bounding box of the packed points (on every thread).  rawp holds the thread's points tid, tid + NTH, ... when
+// CAP / NTH <= RAWP_MAX (all of a lane's loads were issued before the first use: one memory round trip): they stay in registers for
+// the sort, nothing is written.  Otherwise the points are read from pts here, one coalesced pass, and leave in staged form in
+// sKeys[0, sz0) for a sort that cannot hold them.
 template <int NTH, int CAP>
 __device__ __forceinline__ Box front_box(const ck_packed_point (&rawp)[CAP / NTH <= RAWP_MAX ? CAP / NTH : 1], const ck_packed_point *pts, int sz0,
                                          unsigned long long *sKeys, int *iscr) {
     constexpr int EPL = CAP / NTH;
-    const int tid = threadIdx.x;
+    const int tid = loop_tid();
     int xmin = 1 << 30, xmax = -(1 << 30), ymin = 1 << 30, ymax = -(1 << 30);
-    auto take = [&](int i, ck_packed_point v) {
-        const unsigned long long raw = ck_stage_point(v);
-        sKeys[i] = raw;
-        const int px = (int)(raw & 0xFFFF), py = (int)((raw >> 16) & 0xFFFF);
+    auto take = [&](ck_packed_point v) {
+        const int px = (int)((v >> 16) & 0x1FFFu), py = (int)((v >> 3) & 0x1FFFu); // ck_unpack_point's x and y
         xmin = min(xmin, px); xmax = max(xmax, px);
         ymin = min(ymin, py); ymax = max(ymax, py);
     };
     if constexpr (EPL <= RAWP_MAX) {
 #pragma unroll
-        for (int e = 0; e < EPL; e++) {
-            const int i = tid + e * NTH;
-            if (i < sz0) take(i, rawp[e]);
-        }
+        for (int e = 0; e < EPL; e++)
+            if (tid + e * NTH < sz0) take(rawp[e]);
     } else {
-        for (int i = tid; i < sz0; i += NTH) take(i, pts[i]);
+        for (int i = tid; i < sz0; i += NTH) { const ck_packed_point v = pts[i]; sKeys[i] = ck_stage_point(v); take(v); }
     }
     int bb[4] = {xmin, -xmax, ymin, -ymax};
     Block<NTH>::reduce_min4(bb, iscr);
     return Box{bb[0], -bb[1], bb[2], -bb[3]};
 }
 
-// 2a. border direction and sort of the staged points: the bucketed rank sort, and for a cluster it leaves alone the bitonic network
+// 2a. border direction and sort of the points: the bucketed rank sort, and for a cluster it leaves alone the bitonic network
 // with the keys-per-thread count that matches the cluster (padded to a power of two, at least one per thread).  Returns the
 // border-direction sum (on every thread); the keys are sorted unless its sign is one the families do not want (or !do_sort).
+// The classes whose keys fit in registers (MLDS) bring their points in registers too (rawp); only the bitonic network, which owns
+// consecutive slots, needs them staged in the key array, and stages them itself before it starts.
 template <int NTH, int CAP, bool MLDS, bool GK, class BAR>
-__device__ __forceinline__ long long front_sort(unsigned long long *sKeys, uint32_t *hist, long long *sScratch, unsigned long long *scratch8, int sz0,
-                                                const Box &b, int normal_ok, int reversed_ok, bool do_sort) {
+__device__ __forceinline__ long long front_sort(const ck_packed_point (&rawp)[CAP / NTH <= RAWP_MAX ? CAP / NTH : 1], unsigned long long *sKeys,
+                                                uint32_t *hist, long long *sScratch, unsigned long long *scratch8, int sz0, const Box &b,
+                                                int normal_ok, int reversed_ok, bool do_sort) {
     constexpr int EPLS = CAP / NTH;
+    static_assert(MLDS == (EPLS <= RAWP_MAX), "the classes with their keys in registers are the ones with their points in registers");
     int n2 = NTH;
     while (n2 < sz0) n2 <<= 1;
     const int epl = n2 / NTH;
-    BAR::sync(); // raw points staged by other threads
     bool sorted = false;
     long long dot;
-    if constexpr (MLDS) // keys fit in registers (CAP / NTH <= 16)
-        dot = keys_bucket_sort<NTH, EPLS>(sKeys, hist, sScratch, sz0, b.xmin, b.xmax, b.ymin, b.ymax, normal_ok, reversed_ok, do_sort, &sorted);
-    else
+    if constexpr (MLDS) { // keys fit in registers (CAP / NTH <= 16)
+        dot = keys_bucket_sort<NTH, EPLS>(rawp, sKeys, hist, sScratch, sz0, b.xmin, b.xmax, b.ymin, b.ymax, normal_ok, reversed_ok, do_sort, &sorted);
+        if (!sorted) { // (uniform) the bucket sort gave up before it wrote a key
+            const int tid = loop_tid();
+#pragma unroll
+            for (int e = 0; e < EPLS; e++) {
+                const int i = tid + e * NTH;
+                if (i < sz0) sKeys[i] = ck_stage_point(rawp[e]);
+            }
+            BAR::sync(); // points staged by other threads
+        }
+    } else {
+        BAR::sync(); // points staged by other threads
         dot = keys_bucket_sort_global<NTH, GK>(sKeys, hist, sScratch, scratch8, sz0, b.xmin, b.xmax, b.ymin, b.ymax, normal_ok, reversed_ok, do_sort, &sorted);
+    }
     if (sorted || GK) {}
-    else if (EPLS >= 32 && epl == 32) dot = keys_sort<NTH, (EPLS >= 32 && !GK ? 32 : 1)>(sKeys, sScratch, sz0, b.xmin, b.xmax, b.ymin, b.ymax, normal_ok, reversed_ok, do_sort);
-    else if (EPLS >= 16 && epl == 16) dot = keys_sort<NTH, (EPLS >= 16 && !GK ? 16 : 1)>(sKeys, sScratch, sz0, b.xmin, b.xmax, b.ymin, b.ymax, normal_ok, reversed_ok, do_sort);
-    else if (EPLS >= 8 && epl == 8) dot = keys_sort<NTH, (EPLS >= 8 && !GK ? 8 : 1)>(sKeys, sScratch, sz0, b.xmin, b.xmax, b.ymin, b.ymax, normal_ok, reversed_ok, do_sort);
-    else if (EPLS >= 4 && epl == 4) dot = keys_sort<NTH, (EPLS >= 4 && !GK ? 4 : 1)>(sKeys, sScratch, sz0, b.xmin, b.xmax, b.ymin, b.ymax, normal_ok, reversed_ok, do_sort);
-    else if (EPLS >= 2 && epl == 2) dot = keys_sort<NTH, (EPLS >= 2 && !GK ? 2 : 1)>(sKeys, sScratch, sz0, b.xmin, b.xmax, b.ymin, b.ymax, normal_ok, reversed_ok, do_sort);
-    else dot = keys_sort<NTH, 1>(sKeys, sScratch, sz0, b.xmin, b.xmax, b.ymin, b.ymax, normal_ok, reversed_ok, do_sort);
+    else if (EPLS >= 32 && epl == 32) dot = keys_sort<NTH, (EPLS >= 32 && !GK ? 32 : 1), MLDS>(sKeys, sScratch, sz0, b.xmin, b.xmax, b.ymin, b.ymax, normal_ok, reversed_ok, do_sort);
+    else if (EPLS >= 16 && epl == 16) dot = keys_sort<NTH, (EPLS >= 16 && !GK ? 16 : 1), MLDS>(sKeys, sScratch, sz0, b.xmin, b.xmax, b.ymin, b.ymax, normal_ok, reversed_ok, do_sort);
+    else if (EPLS >= 8 && epl == 8) dot = keys_sort<NTH, (EPLS >= 8 && !GK ? 8 : 1), MLDS>(sKeys, sScratch, sz0, b.xmin, b.xmax, b.ymin, b.ymax, normal_ok, reversed_ok, do_sort);
+    else if (EPLS >= 4 && epl == 4) dot = keys_sort<NTH, (EPLS >= 4 && !GK ? 4 : 1), MLDS>(sKeys, sScratch, sz0, b.xmin, b.xmax, b.ymin, b.ymax, normal_ok, reversed_ok, do_sort);
+    else if (EPLS >= 2 && epl == 2) dot = keys_sort<NTH, (EPLS >= 2 && !GK ? 2 : 1), MLDS>(sKeys, sScratch, sz0, b.xmin, b.xmax, b.ymin, b.ymax, normal_ok, reversed_ok, do_sort);
+    else dot = keys_sort<NTH, 1, MLDS>(sKeys, sScratch, sz0, b.xmin, b.xmax, b.ymin, b.ymax, normal_ok, reversed_ok, do_sort);
     return dot;
 }
 
 // 2b. duplicate removal, packing to (x, y): returns the number of points left, u32 x << 13 | y each, in the first half of the key
-// buffer.  The compaction writes at index <= i: a round only overwrites bytes below 4 * (base + NTH) while unread keys start at
-// byte 8 * (base + NTH).  (The caller's barrier stands between the sort and this.)
-template <int NTH, class BAR>
-__device__ __forceinline__ int front_pack(unsigned long long *sKeys, int sz0, int *iscr) {
-    const int tid = threadIdx.x;
+// buffer.  (The caller's barrier stands between the sort and this.)
+// One pass for the classes whose keys fit in registers (EPL <= RAWP_MAX): a thread reads the keys it owns in every round,
+// i = tid + e * NTH, each with its left neighbour, and keeps the (x, y) words; a round's keep flags are a ballot per wave, whose
+// counts go to a table of EPL x NW words (tbl; the sort's histogram, dead by now) — ONE barrier, behind which every key has been
+// read, so the kept words can go to their places in the same array.  The place of round e, wave w: the kept points of the rounds
+// before e and of the waves before w in e, i.e. the exclusive sum over the table in its own order, which every wave forms for itself
+// from the lanes' registers.  A second barrier, and the words are there for everyone: 2 barriers per cluster where the loop below pays 4
+// per NTH points.  The other classes keep that loop: the compaction writes at index <= i, a round only overwrites bytes below
+// 4 * (base + NTH) while unread keys start at byte 8 * (base + NTH).
+template <int NTH, int EPL, class BAR>
+__device__ __forceinline__ int front_pack(unsigned long long *sKeys, int sz0, int *iscr, uint32_t *tbl /* [EPL * NTH / 64] */) {
+    const int tid = loop_tid();
     uint32_t *sXY = reinterpret_cast<uint32_t *>(sKeys);
+    if constexpr (EPL <= RAWP_MAX) {
+        constexpr int NW = NTH / 64, NT = EPL * NW;
+        static_assert(NT <= 128, "the table is summed by one wave, two entries per lane");
+        const int lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+        // a kept point: (x, y) | its place among the kept points of its wave and round << 26 (below 64); anything else: ~0
+        uint32_t w[EPL];
+        uint32_t cum[NW == 1 ? EPL : 1], total = 0; // wave-uniform; one wave: where its round e starts
+#pragma unroll
+        for (int e = 0; e < EPL; e++) {
+            const int i = tid + e * NTH;
+            bool keep = false;
+            uint32_t xy = 0;
+            if (i < sz0) {
+                const unsigned long long key = sKeys[i];
+                keep = (i == 0) || (sKeys[i - 1] != key);
+                xy = (uint32_t)(key & 0x3FFFFFFu);
+            }
+            const unsigned long long bal = __ballot(keep);
+            const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+            w[e] = keep ? (xy | (before << 26)) : ~0u;
+            if constexpr (NW == 1) { cum[e] = total; total += (uint32_t)__popcll(bal); }
+            else if (lane == 0) tbl[e * NW + wv] = (uint32_t)__popcll(bal);
+        }
+        BAR::sync(); // every key read, every count filed
+        if constexpr (NW == 1) {
+#pragma unroll
+            for (int e = 0; e < EPL; e++)
+                if (w[e] != ~0u) sXY[cum[e] + (w[e] >> 26)] = w[e] & 0x3FFFFFFu;
+        } else {
+            const uint32_t c0 = lane < NT ? tbl[lane] : 0u, s0 = wave_scan_u32(c0);
+            const uint32_t x0 = s0 - c0; // exclusive
+            total = (uint32_t)__builtin_amdgcn_readlane((int)s0, 63);
+            uint32_t x1 = 0;
+            if constexpr (NT > 64) {
+                const uint32_t c1 = lane + 64 < NT ? tbl[lane + 64] : 0u, s1 = wave_scan_u32(c1);
+                x1 = s1 - c1 + total;
+                total += (uint32_t)__builtin_amdgcn_readlane((int)s1, 63);
+            }
+#pragma unroll
+            for (int e = 0; e < EPL; e++) {
+                const uint32_t start = (uint32_t)__builtin_amdgcn_readlane((int)(e * NW < 64 ? x0 : x1), (e * NW + wv) & 63);
+                if (w[e] != ~0u) sXY[start + (w[e] >> 26)] = w[e] & 0x3FFFFFFu;
+            }
+        }
+        BAR::sync();
+        return (int)total;
+    }
     int sz = 0;
     for (int base = 0; base < sz0; base += NTH) {
         const int i = base + tid;
@@ -807,7 +898,7 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(WPS, 8))) v
         const Box box = front_box<NTH, CAP>(rawp, pts, sz0, sKeys, iscr);
         if ((box.xmax - box.xmin) * (box.ymax - box.ymin) < a.min_tag_width) continue;
         if (a.stop_after == 10) continue;
-        const long long dot = front_sort<NTH, CAP, MLDS, GK, FenceBarrier>(sKeys, reinterpret_cast<uint32_t *>(sPraw), sScratch, scratch8, sz0, box,
+        const long long dot = front_sort<NTH, CAP, MLDS, GK, FenceBarrier>(rawp, sKeys, reinterpret_cast<uint32_t *>(sPraw), sScratch, scratch8, sz0, box,
                                                                           a.normal_ok, a.reversed_ok, a.stop_after != 11);
         const int reversed = dot < 0;
         PROF(0);
@@ -818,7 +909,7 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(WPS, 8))) v
         // ---- 2. duplicate removal, packing to (x,y) ----------------------------------------------------------------
         __syncthreads();
         PROF(1);
-        const int sz = front_pack<NTH, FenceBarrier>(sKeys, sz0, iscr);
+        const int sz = front_pack<NTH, CAP / NTH, FenceBarrier>(sKeys, sz0, iscr, reinterpret_cast<uint32_t *>(sPraw));
         PROF(2);
         if (sz < 24) continue;
         const int ksz = sz / 12 < 20 ? sz / 12 : 20; // half-width of the line-fit window
@@ -1399,12 +1490,14 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(WPS, 8))) v
             if constexpr (PF) {
                 const uint32_t item = sHItem[k], cnt = sHCount[k];
                 const ck_packed_point *p = ws.d_points + (size_t)(item >> 20) * ws.ext_cap + sHStart[k];
+                const int t = loop_tid();
 #pragma unroll
-                for (int e = 0; e < EPL; e++) { const uint32_t i = (uint32_t)(tid + e * NTH); nxt[e] = (i < cnt && cnt <= (uint32_t)CAP) ? p[i] : 0u; }
+                for (int e = 0; e < EPL; e++) { const uint32_t i = (uint32_t)(t + e * NTH); nxt[e] = (i < cnt && cnt <= (uint32_t)CAP) ? p[i] : 0u; }
             }
         };
         fetch(0);
         for (int k = 0; k < len; k++) {
+            const int tid = loop_tid();
             const uint32_t item = sHItem[k];
             const int frame = (int)(item >> 20), ci = (int)(item & 0xFFFFFu);
             const int sz0 = (int)sHCount[k];
@@ -1426,7 +1519,7 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(WPS, 8))) v
             if ((box.xmax - box.xmin) * (box.ymax - box.ymin) < a.min_tag_width) continue;
             if (a.stop_after == 10) continue;
             // ---- 2. border direction, sort ---------------------------------------------------------------------------------------
-            const long long dot = front_sort<NTH, CAP, MLDS, GK, B>(sKeys, reinterpret_cast<uint32_t *>(sHist), sScratch, scratch8, sz0, box,
+            const long long dot = front_sort<NTH, CAP, MLDS, GK, B>(rawp, sKeys, reinterpret_cast<uint32_t *>(sHist), sScratch, scratch8, sz0, box,
                                                                     a.normal_ok, a.reversed_ok, a.stop_after != 11);
             const int reversed = dot < 0;
             if (reversed && !a.reversed_ok) continue;
@@ -1434,7 +1527,7 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(WPS, 8))) v
             if (a.stop_after == 1 || a.stop_after == 11) continue;
             // ---- 3. duplicate removal, packing to (x, y) -------------------------------------------------------------------------
             B::sync();
-            const int sz = front_pack<NTH, B>(sKeys, sz0, iscr);
+            const int sz = front_pack<NTH, EPL, B>(sKeys, sz0, iscr, reinterpret_cast<uint32_t *>(sHist));
             if (sz < 24) continue;
             const int ksz = sz / 12 < 20 ? sz / 12 : 20; // half-width of the line-fit window
             if (ksz < 2) continue;
