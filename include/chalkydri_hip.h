@@ -52,7 +52,11 @@ enum {
 enum {
     CK_FRAME_OK = 0,
     CK_FRAME_POINTS_OVERFLOW = 1,   /* boundary-point buffer full: clusters may be missing */
-    CK_FRAME_CLUSTERS_OVERFLOW = 2, /* cluster table full */
+    CK_FRAME_CLUSTERS_OVERFLOW = 2, /* cluster table full.  Also: more than 512 distinct pairs of neighbouring components inside one
+                                       64 x 16-pixel tile of the quad image (the stage's per-tile table); the pairs beyond the 512
+                                       lose their points.  Reachable only with min_component_px of 1 or 2 (a one-pixel checkerboard
+                                       at min_component_px = 1 does it; at the default of 25 a tile has no room for that many
+                                       components); the frame's batch neighbours and later calls are not affected */
     CK_FRAME_QUADS_OVERFLOW = 4,    /* more candidate quads than capacity */
     CK_FRAME_DETS_OVERFLOW = 8,     /* more detections than `cap_per_frame` */
     CK_FRAME_UNVERIFIED_ID = 16     /* a detection's id is >= its family's n_upstream (see ck_family_t) */

@@ -1,6 +1,8 @@
 """Randomised parity stress of threshold + segmentation against the CPU oracle (test infrastructure: imports oracle/): random
-geometries (ragged widths / heights included), random content mixes, random min_white_black_diff / min_component_px and, through
-CK_FMERGE_CAP and CK_FMERGE_BAND_ROWS, every path of the merge kernels (one piece or bands of tile rows).  usage: python tests/stress_segment.py [cases] [seed]"""
+geometries (ragged widths / heights included), random content mixes and, through CK_FMERGE_CAP and CK_FMERGE_BAND_ROWS, every path of
+the merge kernels (one piece or bands of tile rows).  The detector's settings stay at their defaults: the labels and the full sizes
+that segment() returns do not depend on min_component_px (it reaches the device through the cluster stage only:
+tests/stress_clusters.py draws it).  usage: python tests/stress_segment.py [cases] [seed]"""
 import os, sys, json
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if __name__ == "__main__":   # CK_FMERGE_CAP is a knob of the diagnostics build: as a script this file runs against that library

@@ -35,6 +35,12 @@ def test_stress_detect_small_capacities(oracle, monkeypatch):
     assert stress_detect.run(60, 107) == 0
 
 
+def test_stress_clusters(oracle):
+    """the gradient clusters themselves, point for point (through detections a wrong point shows only in a cluster that becomes a quad)"""
+    import stress_clusters
+    assert stress_clusters.run(30, 115) == 0
+
+
 def test_stress_pose(oracle):
     import stress_pose
     assert stress_pose.run(25, 103) == 0
