@@ -163,6 +163,18 @@ class CalibResult(C.Structure):
                 ("rms", C.c_double), ("cost0", C.c_double), ("cost", C.c_double)]
 
 
+CK_RIGCAL_MAX_STEPS = 4096
+
+
+class RigcalParams(C.Structure):
+    _fields_ = [("fixed_mask", C.c_uint64), ("max_iters", C.c_int32), ("min_steps", C.c_int32), ("min_cams_per_step", C.c_int32),
+                ("pad", C.c_int32)]
+
+
+class RigcalProblem(C.Structure):
+    _fields_ = [("n_steps", C.c_int32), ("step_offset", C.c_int32)]
+
+
 class VisionMeasurement(C.Structure):
     _fields_ = [("pose_x", C.c_double), ("pose_y", C.c_double), ("pose_rot", C.c_double),
                 ("std_x", C.c_double), ("std_y", C.c_double), ("std_rot", C.c_double), ("ts", C.c_uint64),
@@ -199,6 +211,15 @@ assert C.sizeof(Rect) == 16 and C.sizeof(ExposureStats) == 6416 and C.sizeof(Exp
 assert C.sizeof(TriOtsuParams) == 16 and C.sizeof(TriOtsuInfo) == 160
 assert C.sizeof(CalibParams) == 24 and C.sizeof(CalibProblem) == 16 and C.sizeof(CalibResult) == 112
 assert C.sizeof(RigParams) == 32 and C.sizeof(RigResult) == 240
+
+
+class RigcalResult(C.Structure):
+    _fields_ = [("robot_to_cam", Iso3 * CK_RIG_MAX_CAMS), ("status", C.c_int32), ("iters", C.c_int32), ("n_steps", C.c_int32),
+                ("n_steps_used", C.c_int32), ("n_points", C.c_int32), ("pad", C.c_int32), ("rms", C.c_double), ("cost0", C.c_double),
+                ("cost", C.c_double), ("cam_points", C.c_int32 * CK_RIG_MAX_CAMS), ("cam_rms", C.c_double * CK_RIG_MAX_CAMS)]
+
+
+assert C.sizeof(RigcalParams) == 24 and C.sizeof(RigcalProblem) == 8 and C.sizeof(RigcalResult) == 592
 
 # per-frame status bits (include/chalkydri_hip.h)
 CK_FRAME_OK, CK_FRAME_POINTS_OVERFLOW, CK_FRAME_CLUSTERS_OVERFLOW, CK_FRAME_QUADS_OVERFLOW, CK_FRAME_DETS_OVERFLOW = 0, 1, 2, 4, 8

@@ -13,6 +13,7 @@
 #include "ck_tri_otsu.h"
 #include "ck_calib.h"
 #include "ck_rig.h"
+#include "ck_rigcal.h"
 
 thread_local char ck_err_text[512] = "";
 
@@ -181,6 +182,7 @@ extern "C" void ck_destroy(ck_handle_t *h) {
     delete h->tri_otsu;
     delete h->calib;
     delete h->rig;
+    delete h->rigcal;
     for (auto &e : h->ev) if (e) (void)hipEventDestroy(e);
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
     if (h->ev_join) (void)hipEventDestroy(h->ev_join);

@@ -233,6 +233,8 @@ struct ck_handle {
     struct ck_calib_ws *calib;
     // camera rig (k_rigpnp.hip): allocated by the first rig call, grown on demand
     struct ck_rig_ws *rig;
+    // mount calibration (ck_rigcal.hip, k_rigcal.hip): allocated by the first mount calibration call, grown on demand
+    struct ck_rigcal_ws *rigcal;
     bool fmerge_lds_allowed; // k_fmerge's dynamic LDS limit has been raised on this handle's device
 };
 

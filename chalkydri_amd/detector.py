@@ -125,6 +125,16 @@ def _bind(L):
     L.ck_rig_solve_batch.argtypes = [vp, rp, i32, sp, i32, _P(A.Iso3), i32, vp, i32, vp, rr]
     L.ck_rig_process_last.argtypes = [_P(vp), i32, i32, rp, vp, vp, rr, _P(A.VisionMeasurement), _P(i32)]
     L.ck_rig_time_last.argtypes = [_P(vp), i32, i32, rp, vp, vp, i32, vp, vp]
+    mp, mq, mr, iso = _P(A.RigcalParams), _P(A.RigcalProblem), _P(A.RigcalResult), _P(A.Iso3)
+    L.ck_rigcal_params_default.argtypes = [mp]
+    L.ck_rigcal_params_default.restype = None
+    capture = [i32, sp, i32, iso, i32, vp, i32]
+    L.ck_rigcal_check.argtypes = [mp] + capture + [mq, i32, vp, i32, iso]
+    L.ck_rigcal_jacobian.argtypes = [iso, vp, vp, vp, i32, C.c_uint32, vp, vp]
+    L.ck_rigcal_refine_host.argtypes = [mp] + capture + [mq, vp, i32, iso, vp, mr, vp]
+    L.ck_rigcal_refine_batch.argtypes = [vp, mp] + capture + [mq, i32, vp, i32, iso, vp, mr, vp]
+    L.ck_rig_calibrate_batch.argtypes = [vp, mp] + capture + [vp, mq, i32, vp, i32, iso, mr, vp]
+    L.ck_last_pose_inputs.argtypes = [vp, i32, sp, iso, i32, vp, i32, _P(i32), _P(i32)]
     L._ck_bound = True
     return L
 

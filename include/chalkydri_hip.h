@@ -919,6 +919,97 @@ int ck_rig_process_last(ck_handle_t *const *handles, int32_t n_cams, int32_t n, 
 int ck_rig_time_last(ck_handle_t *const *handles, int32_t n_cams, int32_t n, const ck_rig_params_t *params, const double *gyro,
                      const uint8_t *has_gyro, int32_t iters, float *ms_rig, float *ms_sqpnp);
 
+/* ---- camera mounts: the robot_to_cam of a rig's cameras from a capture, batched Levenberg-Marquardt ------
+ * The capture is what ck_rig_solve_batch takes: n_steps instants of n_cams cameras, camera c's record of step s at
+ * records[c * n_steps + s] (n_tags, n_bearings = 4 * n_tags and the offsets are read; the records' own robot_to_cam is ignored), and
+ * the start mounts mounts0[n_cams].  Unknowns: one world -> robot pose per step and the mount of every camera, kept as (A_c, o_c)
+ * with p_cam = A_c (p_robot - o_c); robot_to_cam (A_c, b_c = -A_c o_c) is converted at the boundary.  Residual of a corner with
+ * bearing v: p = A_c (R_s X + t_s - o_c), e = (p - v (v.p) / (v.v)) / |p|: the point-to-ray distance over the range, radians.
+ * fixed_mask: bit 6 c + i freezes increment i of camera c; i = 0..2 the rotation about robot x, y, z, i = 3..5 o_c x, y, z.  A
+ * camera with all six bits set comes back bit for bit, so does the quaternion of one with bits 0..2 set.  At least one camera that
+ * has observations must have all six bits set (the gauge).  A problem is a run of step_index[] (step numbers of the capture,
+ * strictly increasing), so leave-out subsets share one copy of the observations.  A step is used when at least min_cams_per_step
+ * cameras have a tag in it; the others are counted in n_steps - n_steps_used and their poses come back as given.  DEGENERATE
+ * (CK_CALIB_DEGENERATE; the statuses are ck_calib_status', except that the cost below which a solve is CONVERGED at once is 1e-40:
+ * the cost is in rad^2, and 1e-20 would end a noise-free solve at 1e-10 from the truth): fewer than min_steps used steps, a camera with free increments that
+ * no chain of shared used steps connects to a fully frozen camera, a start that is not finite.  Mounts and poses are the starts then.
+ * ck_rigcal_refine_host is the specification: ck_rigcal_refine_batch returns its bytes. */
+#define CK_RIGCAL_MAX_STEPS 4096 /* per problem */
+#define CK_RIGCAL_FIX_CAMERA(c) ((uint64_t)0x3F << (6 * (c)))
+#define CK_RIGCAL_FIX_POSITION(c) ((uint64_t)0x38 << (6 * (c)))
+typedef struct ck_rigcal_params {
+    uint64_t fixed_mask;
+    int32_t max_iters;             /* 100; 1..10000 */
+    int32_t min_steps;             /* 3 */
+    int32_t min_cams_per_step;     /* 2 */
+    int32_t pad;
+} ck_rigcal_params_t;
+typedef struct ck_rigcal_problem {
+    int32_t n_steps;               /* entries of step_index[] */
+    int32_t step_offset;           /* the first of them */
+} ck_rigcal_problem_t;
+typedef struct ck_rigcal_result {
+    ck_iso3_t robot_to_cam[CK_RIG_MAX_CAMS];
+    int32_t status;                /* CK_CALIB_* */
+    int32_t iters;
+    int32_t n_steps, n_steps_used;
+    int32_t n_points;              /* of the used steps */
+    int32_t pad;
+    double rms;                    /* sqrt(cost / n_points), radians */
+    double cost0, cost;
+    int32_t cam_points[CK_RIG_MAX_CAMS];
+    double cam_rms[CK_RIG_MAX_CAMS]; /* of camera c's own points at the solution */
+} ck_rigcal_result_t;
+void ck_rigcal_params_default(ck_rigcal_params_t *p);
+/* What every entry point refuses, in this order, before it touches a device.  CK_EINVAL: a null pointer (tags / bearings may be
+ * null when their total is 0); n_cams outside 1..CK_RIG_MAX_CAMS; a negative count or offset, or one outside its array;
+ * 4 * n_tags != n_bearings in a record; a problem's step indices out of range or not increasing; max_iters outside 1..10000;
+ * min_steps < 1; min_cams_per_step < 2; a tag, bearing or mount that is not finite; no camera with observations that has all six
+ * bits of fixed_mask.  CK_ECAPACITY: a problem of more than CK_RIGCAL_MAX_STEPS steps.  Host only. */
+int ck_rigcal_check(const ck_rigcal_params_t *p, int32_t n_cams, const ck_sqpnp_problem_t *records, int32_t n_steps, const ck_iso3_t *tags,
+                    int32_t n_tags_total, const double *bearings, int32_t n_bearings_total, const ck_rigcal_problem_t *problems,
+                    int32_t n_problems, const int32_t *step_index, int32_t n_index_total, const ck_iso3_t *mounts0);
+/* Residuals r_out [n][3] and analytic Jacobian J_out [n][3][12] of n points of one view: world_xyz [n][3] seen along bearings [n][3]
+ * by the camera mounted by `mount` at the step with pose [12] (R row-major, t).  Columns: the camera's six increments, the step's
+ * six (rotation, translation); the camera's frozen columns (bits 0..5 of fixed6) are zero.  Host only. */
+int ck_rigcal_jacobian(const ck_iso3_t *mount, const double *pose, const double *world_xyz, const double *bearings, int32_t n,
+                       uint32_t fixed6, double *r_out, double *J_out);
+/* One problem on the host, one thread, no device.  poses0 [n_steps][12]: the start pose of every step of the capture;
+ * poses_out [n_index_total][12]: entry step_offset + j is the pose of the problem's j-th step; it must not overlap poses0 (the two are
+ * indexed differently).  Errors: ck_rigcal_check's, CK_ENOMEM. */
+int ck_rigcal_refine_host(const ck_rigcal_params_t *p, int32_t n_cams, const ck_sqpnp_problem_t *records, int32_t n_steps,
+                          const ck_iso3_t *tags, int32_t n_tags_total, const double *bearings, int32_t n_bearings_total,
+                          const ck_rigcal_problem_t *problem, const int32_t *step_index, int32_t n_index_total, const ck_iso3_t *mounts0,
+                          const double *poses0, ck_rigcal_result_t *result, double *poses_out);
+/* n_problems problems on the handle's stream, one persistent workgroup each, the whole iteration inside the kernel; every byte of
+ * results and poses_out equals ck_rigcal_refine_host's.  All arrays are the host's.  Problems may share a run of step_index[]; they then
+ * share its entries of poses_out, which hold the poses of the last of them.  The workspace (allocated by the first call,
+ * grown on demand; ck_create allocates none of it) leaves the staged frames and the detection workspace as they are.  Errors:
+ * ck_rigcal_check's (the handle among the null pointers), CK_ECAPACITY when the records of the call pass 2^31 doubles, CK_ENOMEM. */
+int ck_rigcal_refine_batch(ck_handle_t *h, const ck_rigcal_params_t *p, int32_t n_cams, const ck_sqpnp_problem_t *records, int32_t n_steps,
+                           const ck_iso3_t *tags, int32_t n_tags_total, const double *bearings, int32_t n_bearings_total,
+                           const ck_rigcal_problem_t *problems, int32_t n_problems, const int32_t *step_index, int32_t n_index_total,
+                           const ck_iso3_t *mounts0, const double *poses0, ck_rigcal_result_t *results, double *poses_out);
+
+/* The starts from ck_rig_solve_batch with mounts0 and sign_change_error = 0 over the whole capture, once (gyro [n_steps]: the heading
+ * of every step, which that solver pivots towards), then ck_rigcal_refine_batch.  A step that solver has no pose for is left out of
+ * every problem (it is not counted in n_steps_used, and its pose in poses_out is zero).  The rig solver's device and host results
+ * agree to round-off (4e-16), not byte for byte, so this entry point equals the twin from the same starts to a tolerance (DESIGN.md
+ * §4l); the byte contract is ck_rigcal_refine_batch's.  Errors: ck_rigcal_check's, ck_rig_solve_batch's. */
+int ck_rig_calibrate_batch(ck_handle_t *h, const ck_rigcal_params_t *p, int32_t n_cams, const ck_sqpnp_problem_t *records, int32_t n_steps,
+                           const ck_iso3_t *tags, int32_t n_tags_total, const double *bearings, int32_t n_bearings_total, const double *gyro,
+                           const ck_rigcal_problem_t *problems, int32_t n_problems, const int32_t *step_index, int32_t n_index_total,
+                           const ck_iso3_t *mounts0, ck_rigcal_result_t *results, double *poses_out);
+/* Copies to the host what the last ck_process_* call of exactly n frames left on the device for the pose solvers: records_out [n]
+ * (n_tags, n_bearings, robot_to_cam, gyro, sign_change_error as that call wrote them; the offsets relative to tags_out and
+ * bearings_out, packed in frame order, whichever piece of a split batch wrote a record), the known tags' field poses and the four
+ * corner bearings of each.  *n_tags_out and *n_bearings_out are the totals, also when they do not fit.  Waits for the handle's
+ * stream.  CK_EINVAL: a null pointer, n < 1, a negative capacity, a handle whose last pipeline call was not a ck_process_* call of
+ * exactly n frames (the test ck_rig_process_last makes).  CK_ECAPACITY: tag_cap or bearing_cap (in tags, in bearings of 3 doubles)
+ * is too small; only records_out and the totals are written then.  CK_ENOMEM. */
+int ck_last_pose_inputs(ck_handle_t *h, int32_t n, ck_sqpnp_problem_t *records_out, ck_iso3_t *tags_out, int32_t tag_cap,
+                        double *bearings_out, int32_t bearing_cap, int32_t *n_tags_out, int32_t *n_bearings_out);
+
 /* ---- multi-GPU: the final pose gather ----------------------------------------------------------------------------------
  * Frames shard over GPUs without any data-path collective (one handle, one process or host thread per GPU).  The only
  * exchange is the gather of the 64-byte records (the wire struct of crates/whacknet/src/lib.rs:43-66): ONE ncclAllGather

@@ -1,0 +1,74 @@
+#!/usr/bin/env python3
+"""Times ck_rigcal_refine_batch against ck_rigcal_refine_host looping the same problems on one thread in the same
+process: a room capture of 3 cameras x 1000 steps at bearing noise 1e-3 (tests/np_rigcal.py's generator), start mounts off by up to 5
+degrees and 5 cm, start poses from ck_rig_solve_host, as one problem (B = 1) and as 64 random half-subsets in one call (B = 64).
+Wall-clock per call, copies included; medians after warm-up.  One JSON line.
+
+  python tools/bench_rigcal.py [--steps 1000] [--reps 9] [--warmup 2] [--subsets 64]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import rigcal_cases as RC  # noqa: E402
+from chalkydri_amd import rigcal as K  # noqa: E402
+from chalkydri_amd.detector import AprilTagDetector  # noqa: E402
+
+
+def timed(fn, reps, warmup):
+    for _ in range(warmup):
+        fn()
+    ts = []
+    for _ in range(reps):
+        t = time.perf_counter()
+        fn()
+        ts.append((time.perf_counter() - t) * 1e3)
+    return {"median_ms": float(np.median(ts)), "min_ms": float(np.min(ts)), "max_ms": float(np.max(ts))}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=1000)
+    ap.add_argument("--reps", type=int, default=9)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--subsets", type=int, default=64)
+    a = ap.parse_args()
+    cs = RC.acceptance_case(3, a.steps, 0, 1e-3)
+    ok = cs["ok"]
+    rng = np.random.default_rng(1)
+    halves = [[ok[i] for i in sorted(rng.choice(len(ok), len(ok) // 2, replace=False))] for _ in range(a.subsets)]
+    det = AprilTagDetector(640, 480)
+    p = K.params()
+    out = {"cameras": 3, "steps": a.steps, "steps_with_a_start": len(ok), "reps": a.reps, "warmup": a.warmup}
+    for name, problems in (("full_B1", [ok]), ("half_B%d" % a.subsets, halves)):
+        cap = K.Capture(cs["csteps"], problems)
+        got = {}
+
+        def device():
+            got["d"] = K.refine_batch(det, p, cap, cs["m0"], cs["poses0"])
+
+        def host():
+            got["h"] = [K.refine_host(p, cap, cs["m0"], cs["poses0"], i) for i in range(cap.n)]
+
+        d, h = timed(device, a.reps, a.warmup), timed(host, max(2, a.reps // 4), 0)
+        same = all(got["d"][0][i].tobytes() == got["h"][i][0].tobytes() and got["d"][1][i].tobytes() == got["h"][i][1].tobytes() for i in range(cap.n))
+        res = got["d"][0]
+        out[name] = {"device": d, "host_one_thread": h, "host_over_device": h["median_ms"] / d["median_ms"], "same_bytes": bool(same),
+                     "points": int(res[0]["n_points"]), "steps_used": int(res[0]["n_steps_used"]), "iters": [int(v) for v in res["iters"][:8]],
+                     "status": [int(v) for v in res["status"][:8]], "rms": float(res[0]["rms"])}
+    det.close()
+    print(json.dumps(out))
+    if not all(v["same_bytes"] for v in out.values() if isinstance(v, dict)):
+        sys.exit("device and host twin returned different bytes")
+
+
+if __name__ == "__main__":
+    main()
