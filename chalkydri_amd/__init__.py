@@ -6,6 +6,7 @@ the path runs in hand-written HIP kernels (csrc/*.hip, gfx950); there is no CPU 
 """
 from ._lib import ChalkydriError, default_config, family, lib  # noqa: F401
 from .calibration import Board, Calibrator  # noqa: F401
+from .fieldcal import FieldCalibrator  # noqa: F401
 from .rigcal import MountCalibrator  # noqa: F401
 
-__all__ = ["Board", "Calibrator", "ChalkydriError", "MountCalibrator", "default_config", "family", "lib"]
+__all__ = ["Board", "Calibrator", "ChalkydriError", "FieldCalibrator", "MountCalibrator", "default_config", "family", "lib"]

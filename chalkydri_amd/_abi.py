@@ -175,6 +175,18 @@ class RigcalProblem(C.Structure):
     _fields_ = [("n_steps", C.c_int32), ("step_offset", C.c_int32)]
 
 
+CK_FIELDCAL_MAX_TAGS, CK_FIELDCAL_MAX_STEPS, CK_FIELDCAL_FIX_ALL = 64, 4096, 63
+
+
+class FieldcalParams(C.Structure):
+    _fields_ = [("max_iters", C.c_int32), ("min_steps", C.c_int32), ("min_tags_per_step", C.c_int32), ("pad", C.c_int32)]
+
+
+class FieldcalResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("iters", C.c_int32), ("n_steps", C.c_int32), ("n_steps_used", C.c_int32), ("n_points", C.c_int32),
+                ("n_tags_solved", C.c_int32), ("rms", C.c_double), ("cost0", C.c_double), ("cost", C.c_double)]
+
+
 class VisionMeasurement(C.Structure):
     _fields_ = [("pose_x", C.c_double), ("pose_y", C.c_double), ("pose_rot", C.c_double),
                 ("std_x", C.c_double), ("std_y", C.c_double), ("std_rot", C.c_double), ("ts", C.c_uint64),
@@ -220,6 +232,7 @@ class RigcalResult(C.Structure):
 
 
 assert C.sizeof(RigcalParams) == 24 and C.sizeof(RigcalProblem) == 8 and C.sizeof(RigcalResult) == 592
+assert C.sizeof(FieldcalParams) == 16 and C.sizeof(FieldcalResult) == 48
 
 # per-frame status bits (include/chalkydri_hip.h)
 CK_FRAME_OK, CK_FRAME_POINTS_OVERFLOW, CK_FRAME_CLUSTERS_OVERFLOW, CK_FRAME_QUADS_OVERFLOW, CK_FRAME_DETS_OVERFLOW = 0, 1, 2, 4, 8

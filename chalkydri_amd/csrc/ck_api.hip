@@ -14,6 +14,7 @@
 #include "ck_calib.h"
 #include "ck_rig.h"
 #include "ck_rigcal.h"
+#include "ck_fieldcal.h"
 
 thread_local char ck_err_text[512] = "";
 
@@ -183,6 +184,7 @@ extern "C" void ck_destroy(ck_handle_t *h) {
     delete h->calib;
     delete h->rig;
     delete h->rigcal;
+    delete h->fieldcal;
     for (auto &e : h->ev) if (e) (void)hipEventDestroy(e);
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
     if (h->ev_join) (void)hipEventDestroy(h->ev_join);

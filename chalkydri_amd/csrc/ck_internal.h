@@ -235,6 +235,8 @@ struct ck_handle {
     struct ck_rig_ws *rig;
     // mount calibration (ck_rigcal.hip, k_rigcal.hip): allocated by the first mount calibration call, grown on demand
     struct ck_rigcal_ws *rigcal;
+    // field calibration (ck_fieldcal.hip, k_fieldcal.hip): allocated by the first field calibration call, grown on demand
+    struct ck_fieldcal_ws *fieldcal;
     bool fmerge_lds_allowed; // k_fmerge's dynamic LDS limit has been raised on this handle's device
 };
 

@@ -71,7 +71,7 @@ int ck_rigcal_check(const ck_rigcal_params_t *p, int32_t n_cams, const ck_sqpnp_
 }
 
 /* ---- what both solvers share ------------------------------------------------------------------------------------------------- */
-static void quat_to_mat(const double q[4], double R[9]) {
+void ck_rigcal_quat_to_mat(const double q[4], double R[9]) {
     double w = q[0], x = q[1], y = q[2], z = q[3];
     const double n = sqrt(w * w + x * x + y * y + z * z);
     w /= n; x /= n; y /= n; z /= n;
@@ -80,7 +80,7 @@ static void quat_to_mat(const double q[4], double R[9]) {
     R[6] = 2 * (x * z - y * w);     R[7] = 2 * (y * z + x * w);     R[8] = 1 - 2 * (x * x + y * y);
 }
 /* (w, x, y, z) of a rotation matrix by the largest of the four squared components, w >= 0 */
-static void mat_to_quat(const double R[9], double q[4]) {
+void ck_rigcal_mat_to_quat(const double R[9], double q[4]) {
     const double K[4] = {1 + R[0] + R[4] + R[8], 1 + R[0] - R[4] - R[8], 1 - R[0] + R[4] - R[8], 1 - R[0] - R[4] + R[8]};
     int k = 0;
     for (int i = 1; i < 4; i++)
@@ -95,7 +95,7 @@ static void mat_to_quat(const double R[9], double q[4]) {
 }
 
 void ck_rigcal_mount_in(const ck_iso3_t *iso, double *M) {
-    quat_to_mat(iso->q, M);
+    ck_rigcal_quat_to_mat(iso->q, M);
     for (int i = 0; i < 3; i++) M[9 + i] = -(M[i] * iso->t[0] + M[3 + i] * iso->t[1] + M[6 + i] * iso->t[2]);
 }
 
@@ -105,7 +105,7 @@ void ck_rigcal_table(int32_t n_cams, const ck_sqpnp_problem_t *records, int32_t 
                                     {0, CORNER_DISTANCE, CORNER_DISTANCE}, {0, -CORNER_DISTANCE, CORNER_DISTANCE}};
     for (int32_t t = 0; t < n_tags_total; t++) {
         double R[9];
-        quat_to_mat(tags[t].q, R);
+        ck_rigcal_quat_to_mat(tags[t].q, R);
         for (int j = 0; j < 4; j++)
             for (int k = 0; k < 3; k++)
                 world[((size_t)4 * t + j) * 3 + k] = (R[3 * k] * cp[j][0] + R[3 * k + 1] * cp[j][1] + R[3 * k + 2] * cp[j][2]) + tags[t].t[k];
@@ -173,7 +173,7 @@ void ck_rigcal_result_finish(const ck_rigcal_plan_t *plan, int32_t n_cams, const
         ck_iso3_t *o = res->robot_to_cam + c;
         *o = mounts0[c];
         if (m6 == 63u) continue;
-        if ((m6 & 7u) != 7u) mat_to_quat(Mc, o->q);
+        if ((m6 & 7u) != 7u) ck_rigcal_mat_to_quat(Mc, o->q);
         for (int i = 0; i < 3; i++) o->t[i] = -(Mc[3 * i] * Mc[9] + Mc[3 * i + 1] * Mc[10] + Mc[3 * i + 2] * Mc[11]);
     }
 }

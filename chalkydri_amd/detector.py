@@ -135,6 +135,16 @@ def _bind(L):
     L.ck_rigcal_refine_batch.argtypes = [vp, mp] + capture + [mq, i32, vp, i32, iso, vp, mr, vp]
     L.ck_rig_calibrate_batch.argtypes = [vp, mp] + capture + [vp, mq, i32, vp, i32, iso, mr, vp]
     L.ck_last_pose_inputs.argtypes = [vp, i32, sp, iso, i32, vp, i32, _P(i32), _P(i32)]
+    fp, fr = _P(A.FieldcalParams), _P(A.FieldcalResult)
+    L.ck_fieldcal_params_default.argtypes = [fp]
+    L.ck_fieldcal_params_default.restype = None
+    fcap, flay = [i32, sp, i32, vp, i32, vp, i32], [iso, iso, i32, vp]               # ..., mounts, layout0, n_layout, fixed6
+    fout = [fr, iso, vp, vp, vp]                                                     # results, layout_out, tag_sightings, tag_rms, poses_out
+    L.ck_fieldcal_check.argtypes = [fp] + fcap + [mq, i32, vp, i32] + flay
+    L.ck_fieldcal_jacobian.argtypes = [iso, vp, iso, vp, i32, C.c_uint32, vp, vp]
+    L.ck_fieldcal_refine_host.argtypes = [fp] + fcap + [mq, vp, i32] + flay + [vp] + fout
+    L.ck_fieldcal_refine_batch.argtypes = [vp, fp] + fcap + [mq, i32, vp, i32] + flay + [vp] + fout
+    L.ck_field_calibrate_batch.argtypes = [vp, fp] + fcap + [vp, mq, i32, vp, i32] + flay + fout
     L._ck_bound = True
     return L
 

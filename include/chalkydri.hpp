@@ -1241,5 +1241,137 @@ class MountCalibrator {
     std::vector<double> bear_, gyro_;
 };
 
+// Calibration of the field's tag layout (chalkydri_hip.h: ck_fieldcal_*): collects steps (instants in which the cameras
+// saw two or more field tags) and solves for the pose of every tag that is not frozen and one robot pose per step.  The mounts stay.
+class FieldCalibrator {
+  public:
+    struct Report {
+        ck_fieldcal_result_t result{};
+        std::vector<ck_iso3_t> layout;             // per entry of the layout
+        std::vector<int32_t> sightings;
+        std::vector<double> tag_rms;
+        std::vector<std::array<double, 12>> poses; // world -> robot per step: R row-major, t
+    };
+    // mounts: the robot_to_cam of every camera; layout: the nominal tag poses; fixed6: one mask per entry (one tag with sightings
+    // must be CK_FIELDCAL_FIX_ALL: the gauge)
+    FieldCalibrator(std::shared_ptr<Handle> h, std::vector<ck_iso3_t> mounts, std::vector<ck_iso3_t> layout, std::vector<uint8_t> fixed6)
+        : h_(std::move(h)), mounts_(std::move(mounts)), layout_(std::move(layout)), fixed_(std::move(fixed6)) {
+        if (mounts_.empty() || mounts_.size() > CK_RIG_MAX_CAMS) throw Panic("a rig has 1..8 cameras", CK_EINVAL);
+        if (layout_.empty() || fixed_.size() != layout_.size()) throw Panic("one mask per entry of the layout", CK_EINVAL);
+        for (size_t a = 0; a < layout_.size(); a++)
+            for (size_t b = 0; b < a; b++)
+                if (std::memcmp(&layout_[a], &layout_[b], sizeof(ck_iso3_t)) == 0) throw Panic("two entries of the layout have the same pose", CK_EINVAL);
+    }
+    // one step: per camera the entries of the layout it saw and the four corner bearings of each (x y z per corner); gyro = the heading
+    void add_step(const std::vector<std::vector<int32_t>> &tags, const std::vector<std::vector<double>> &bearings, double gyro) {
+        if (tags.size() != mounts_.size() || bearings.size() != mounts_.size()) throw Panic("add_step: one entry per camera", CK_EINVAL);
+        for (size_t c = 0; c < tags.size(); c++) {
+            if (bearings[c].size() != 12 * tags[c].size()) throw Panic("add_step: four bearings per tag", CK_EINVAL);
+            ck_sqpnp_problem_t r{};
+            r.n_tags = (int32_t)tags[c].size(); r.n_bearings = 4 * r.n_tags;
+            r.tag_offset = (int32_t)index_.size(); r.bearing_offset = (int32_t)(bear_.size() / 3);
+            r.robot_to_cam = mounts_[c];
+            index_.insert(index_.end(), tags[c].begin(), tags[c].end());
+            bear_.insert(bear_.end(), bearings[c].begin(), bearings[c].end());
+            steps_.push_back(r); // step-major here, camera-major in a call
+        }
+        gyro_.push_back(gyro);
+    }
+    // the steps of the last ck_process_* call of n frames of every camera's handle (ck_last_pose_inputs), gyro[n] their headings.  That
+    // call returns the tags' poses, not their ids: each is matched byte for byte against the layout, which must be the one the
+    // handles solved with
+    void add_last(const std::vector<std::shared_ptr<Handle>> &cams, int n, const std::vector<double> &gyro) {
+        if (cams.size() != mounts_.size() || (int)gyro.size() != n) throw Panic("add_last: one handle per camera, one heading per frame", CK_EINVAL);
+        std::vector<std::vector<ck_sqpnp_problem_t>> rec(cams.size(), std::vector<ck_sqpnp_problem_t>((size_t)n));
+        std::vector<std::vector<ck_iso3_t>> tg(cams.size());
+        std::vector<std::vector<double>> br(cams.size());
+        for (size_t c = 0; c < cams.size(); c++) {
+            int32_t nt = 0, nb = 0;
+            ck_iso3_t none{};
+            double nob = 0;
+            int rc = ck_last_pose_inputs(cams[c]->get(), n, rec[c].data(), &none, 0, &nob, 0, &nt, &nb);
+            if (rc != CK_OK && rc != CK_ECAPACITY) check(rc, "ck_last_pose_inputs");
+            tg[c].resize((size_t)nt + 1); br[c].resize(3 * (size_t)nb + 3);
+            check(ck_last_pose_inputs(cams[c]->get(), n, rec[c].data(), tg[c].data(), nt, br[c].data(), nb, &nt, &nb), "ck_last_pose_inputs");
+        }
+        for (int s = 0; s < n; s++) {
+            std::vector<std::vector<int32_t>> t(cams.size());
+            std::vector<std::vector<double>> b(cams.size());
+            for (size_t c = 0; c < cams.size(); c++) {
+                const ck_sqpnp_problem_t &r = rec[c][(size_t)s];
+                for (int32_t k = 0; k < r.n_tags; k++) {
+                    size_t at = 0;
+                    while (at < layout_.size() && std::memcmp(&layout_[at], &tg[c][(size_t)r.tag_offset + k], sizeof(ck_iso3_t)) != 0) at++;
+                    if (at == layout_.size()) throw Panic("add_last: a tag the handle solved with is not in the layout", CK_EINVAL);
+                    t[c].push_back((int32_t)at);
+                }
+                b[c].assign(br[c].begin() + 3 * (size_t)r.bearing_offset, br[c].begin() + 3 * ((size_t)r.bearing_offset + r.n_bearings));
+            }
+            add_step(t, b, gyro[(size_t)s]);
+        }
+    }
+    size_t steps() const { return gyro_.size(); }
+    void clear() { steps_.clear(); index_.clear(); bear_.clear(); gyro_.clear(); }
+
+    // The layout, or nullopt when the solve neither converged nor stalled at a finite rms.  Start poses from the rig solver on the
+    // device with the nominal layout (ck_field_calibrate_batch).  The steps stay until clear().
+    std::optional<std::vector<ck_iso3_t>> calibrate(Report *report = nullptr, int max_iters = 0) {
+        return solve(nullptr, false, report, max_iters);
+    }
+    // the refinement alone from given start poses [steps][12]: on the device (ck_fieldcal_refine_batch) or on the host, one thread,
+    // no device (ck_fieldcal_refine_host); the two return the same bytes
+    std::optional<std::vector<ck_iso3_t>> refine(const std::vector<std::array<double, 12>> &poses0, bool host, Report *report = nullptr,
+                                                  int max_iters = 0) {
+        if (poses0.size() != steps()) throw Panic("refine: one start pose per step", CK_EINVAL);
+        return solve(&poses0, host, report, max_iters);
+    }
+
+  private:
+    std::optional<std::vector<ck_iso3_t>> solve(const std::vector<std::array<double, 12>> *poses0, bool host, Report *report, int max_iters) {
+        const int n = (int)steps(), C = (int)mounts_.size(), L = (int)layout_.size();
+        ck_fieldcal_params_t p;
+        ck_fieldcal_params_default(&p);
+        if (max_iters > 0) p.max_iters = max_iters;
+        Report r;
+        r.poses.resize((size_t)n);
+        r.layout = layout_;
+        r.sightings.assign((size_t)L, 0);
+        r.tag_rms.assign((size_t)L, 0.0);
+        std::optional<std::vector<ck_iso3_t>> out;
+        if (n >= p.min_steps) {
+            std::vector<ck_sqpnp_problem_t> rec((size_t)C * n);
+            for (int s = 0; s < n; s++)
+                for (int c = 0; c < C; c++) rec[(size_t)c * n + s] = steps_[(size_t)s * C + c];
+            std::vector<int32_t> index((size_t)n);
+            for (int s = 0; s < n; s++) index[(size_t)s] = s;
+            const ck_rigcal_problem_t q{n, 0};
+            const int32_t nt = (int32_t)index_.size(), nb = (int32_t)(bear_.size() / 3);
+            if (!poses0)
+                check(ck_field_calibrate_batch(h_->get(), &p, C, rec.data(), n, index_.data(), nt, bear_.data(), nb, gyro_.data(), &q, 1, index.data(),
+                                               n, mounts_.data(), layout_.data(), L, fixed_.data(), &r.result, r.layout.data(), r.sightings.data(),
+                                               r.tag_rms.data(), r.poses[0].data()), "ck_field_calibrate_batch");
+            else if (host)
+                check(ck_fieldcal_refine_host(&p, C, rec.data(), n, index_.data(), nt, bear_.data(), nb, &q, index.data(), n, mounts_.data(),
+                                              layout_.data(), L, fixed_.data(), (*poses0)[0].data(), &r.result, r.layout.data(), r.sightings.data(),
+                                              r.tag_rms.data(), r.poses[0].data()), "ck_fieldcal_refine_host");
+            else
+                check(ck_fieldcal_refine_batch(h_->get(), &p, C, rec.data(), n, index_.data(), nt, bear_.data(), nb, &q, 1, index.data(), n,
+                                               mounts_.data(), layout_.data(), L, fixed_.data(), (*poses0)[0].data(), &r.result, r.layout.data(),
+                                               r.sightings.data(), r.tag_rms.data(), r.poses[0].data()), "ck_fieldcal_refine_batch");
+            if ((r.result.status == CK_CALIB_CONVERGED || r.result.status == CK_CALIB_STALLED) && std::isfinite(r.result.rms)) out = r.layout;
+        } else {
+            r.result.status = CK_CALIB_DEGENERATE;
+        }
+        if (report) *report = r;
+        return out;
+    }
+    std::shared_ptr<Handle> h_; // may be null for refine(..., host = true)
+    std::vector<ck_iso3_t> mounts_, layout_;
+    std::vector<uint8_t> fixed_;
+    std::vector<ck_sqpnp_problem_t> steps_;
+    std::vector<int32_t> index_;
+    std::vector<double> bear_, gyro_;
+};
+
 } // namespace chalkydri
 #endif // CHALKYDRI_HPP

@@ -1010,6 +1010,87 @@ int ck_rig_calibrate_batch(ck_handle_t *h, const ck_rigcal_params_t *p, int32_t 
 int ck_last_pose_inputs(ck_handle_t *h, int32_t n, ck_sqpnp_problem_t *records_out, ck_iso3_t *tags_out, int32_t tag_cap,
                         double *bearings_out, int32_t bearing_cap, int32_t *n_tags_out, int32_t *n_bearings_out);
 
+/* ---- field layout: the tag poses of field.json from a capture, batched Levenberg-Marquardt ----------------
+ * The capture is what ck_rig_solve_batch takes (records[c * n_steps + s]: n_tags, n_bearings = 4 * n_tags and the offsets are read,
+ * the records' robot_to_cam is ignored in favour of mounts[n_cams], which stay fixed), but in place of the tags' poses there is
+ * tag_index[n_tags_total]: for every observed tag its entry of layout0[n_layout].  The same tag in two cameras of a step is normal;
+ * twice in one view it is refused.  Unknowns: one world <- tag pose (Q_k, c_k) per tag and one world -> robot pose per used step.  A
+ * corner x of a tag (corner_points_from_center: (0, -S, -S), (0, S, -S), (0, S, S), (0, -S, S), S = 0.08255) is X = Q_k x + c_k, and
+ * its residual is §4l's: p = A_c (R_s X + t_s - o_c), e = (p - v (v.p) / (v.v)) / |p|, radians.  Increments: Q_k <- Q_k C(dw) about
+ * the tag's own axes, c_k <- c_k + dc in world axes.  fixed6[n_layout]: bits 0..2 of a tag's byte freeze its rotation, bits 3..5 c_k
+ * x, y, z; a wholly frozen tag (63) comes back bit for bit, so do the quaternion of a tag with bits 0..2 set and every frozen
+ * component of c_k.  At least one tag with sightings must be wholly frozen (the gauge).  A tag without a sighting in the used steps
+ * of a problem is returned as given with tag_sightings = 0.  Problems are runs of step_index[] as in §4l (ck_rigcal_problem_t).  A
+ * step is used when at least min_tags_per_step distinct tags are seen in it, over all cameras.  DEGENERATE (the statuses and the
+ * solver are §4l's): fewer than min_steps used steps, a start pose that is not finite, a tag with a free increment that no chain
+ * of shared used steps joins to a wholly frozen tag.  Layout and poses are the starts then.
+ * ck_fieldcal_refine_host is the specification: ck_fieldcal_refine_batch returns its bytes. */
+#define CK_FIELDCAL_MAX_TAGS 64    /* tags of the layout with sightings in one problem */
+#define CK_FIELDCAL_MAX_STEPS 4096 /* per problem */
+#define CK_FIELDCAL_FIX_ALL 63
+typedef struct ck_fieldcal_params {
+    int32_t max_iters;             /* 100; 1..10000 */
+    int32_t min_steps;             /* 3 */
+    int32_t min_tags_per_step;     /* 2 */
+    int32_t pad;
+} ck_fieldcal_params_t;
+typedef struct ck_fieldcal_result {
+    int32_t status;                /* CK_CALIB_* */
+    int32_t iters;
+    int32_t n_steps, n_steps_used;
+    int32_t n_points;              /* of the used steps */
+    int32_t n_tags_solved;         /* tags with sightings and a free increment */
+    double rms;                    /* sqrt(cost / n_points), radians */
+    double cost0, cost;
+} ck_fieldcal_result_t;
+void ck_fieldcal_params_default(ck_fieldcal_params_t *p);
+/* What every entry point refuses, in this order, before it touches a device.  CK_EINVAL: (1) a null pointer (tag_index / bearings may
+ * be null when their total is 0); (2) n_cams outside 1..CK_RIG_MAX_CAMS, n_layout < 1, a negative count; (3) a record's count or offset
+ * negative or outside its array; (4) 4 * n_tags != n_bearings in a record; (5) a tag_index outside 0..n_layout - 1; (6) a problem's run
+ * outside step_index[], its step numbers out of range or not increasing; (7) max_iters outside 1..10000, min_steps < 1,
+ * min_tags_per_step < 2, a fixed6 byte above 63; (8) a bearing, mount or layout pose that is not finite (a zero quaternion counts);
+ * (9) the same tag twice in one view; (10) no wholly frozen tag with a sighting.  CK_ECAPACITY: (11) a problem of more than
+ * CK_FIELDCAL_MAX_STEPS steps, or whose steps see more than CK_FIELDCAL_MAX_TAGS different tags.  Host only. */
+int ck_fieldcal_check(const ck_fieldcal_params_t *p, int32_t n_cams, const ck_sqpnp_problem_t *records, int32_t n_steps,
+                      const int32_t *tag_index, int32_t n_tags_total, const double *bearings, int32_t n_bearings_total,
+                      const ck_rigcal_problem_t *problems, int32_t n_problems, const int32_t *step_index, int32_t n_index_total,
+                      const ck_iso3_t *mounts, const ck_iso3_t *layout0, int32_t n_layout, const uint8_t *fixed6);
+/* Residuals r_out [n][3] and analytic Jacobian J_out [n][3][12] of the first n <= 4 corners of one sighting: the tag at `tag` seen
+ * along bearings [n][3] by the camera mounted by `mount` at the step with pose [12] (R row-major, t).  Columns: the tag's rotation
+ * about its own axes (0..2), the tag's position (3..5), the step's rotation and translation (6..11); the tag's frozen columns (bits
+ * 0..5 of fixed6) are zero.  Host only. */
+int ck_fieldcal_jacobian(const ck_iso3_t *mount, const double *pose, const ck_iso3_t *tag, const double *bearings, int32_t n,
+                         uint32_t fixed6, double *r_out, double *J_out);
+/* One problem on the host, one thread, no device.  poses0 [n_steps][12]: the start pose of every step of the capture.  Outputs:
+ * layout_out [n_layout], tag_sightings [n_layout], tag_rms [n_layout] (the rms of the tag's own points at the solution, radians; 0
+ * without sightings) and poses_out [n_index_total][12] as in ck_rigcal_refine_host.  Errors: ck_fieldcal_check's, CK_ENOMEM. */
+int ck_fieldcal_refine_host(const ck_fieldcal_params_t *p, int32_t n_cams, const ck_sqpnp_problem_t *records, int32_t n_steps,
+                            const int32_t *tag_index, int32_t n_tags_total, const double *bearings, int32_t n_bearings_total,
+                            const ck_rigcal_problem_t *problem, const int32_t *step_index, int32_t n_index_total, const ck_iso3_t *mounts,
+                            const ck_iso3_t *layout0, int32_t n_layout, const uint8_t *fixed6, const double *poses0,
+                            ck_fieldcal_result_t *result, ck_iso3_t *layout_out, int32_t *tag_sightings, double *tag_rms, double *poses_out);
+/* n_problems problems on the handle's stream, one persistent workgroup each, the whole iteration inside the kernel; every byte of
+ * results, layout_out [n_problems][n_layout], tag_sightings and tag_rms (the same shape) and poses_out equals
+ * ck_fieldcal_refine_host's.  All arrays are the host's.  The workspace (allocated by the first call, grown on demand; ck_create
+ * allocates none of it) leaves the staged frames and the detection workspace as they are.  Errors: ck_fieldcal_check's (the handle
+ * among the null pointers), CK_ECAPACITY when the records of the call pass 2^31 doubles, CK_ENOMEM. */
+int ck_fieldcal_refine_batch(ck_handle_t *h, const ck_fieldcal_params_t *p, int32_t n_cams, const ck_sqpnp_problem_t *records,
+                             int32_t n_steps, const int32_t *tag_index, int32_t n_tags_total, const double *bearings,
+                             int32_t n_bearings_total, const ck_rigcal_problem_t *problems, int32_t n_problems, const int32_t *step_index,
+                             int32_t n_index_total, const ck_iso3_t *mounts, const ck_iso3_t *layout0, int32_t n_layout,
+                             const uint8_t *fixed6, const double *poses0, ck_fieldcal_result_t *results, ck_iso3_t *layout_out,
+                             int32_t *tag_sightings, double *tag_rms, double *poses_out);
+/* The starts from ck_rig_solve_batch with the tags at layout0, the given mounts and sign_change_error = 0 over the whole capture, once
+ * (gyro [n_steps]), then ck_fieldcal_refine_batch.  A step that solver has no pose for is left out of every problem (its pose in
+ * poses_out is zero).  As with ck_rig_calibrate_batch this entry equals the twin from the host rig solver's starts to a tolerance
+ * (DESIGN.md §4m), not byte for byte.  Errors: ck_fieldcal_check's, ck_rig_solve_batch's. */
+int ck_field_calibrate_batch(ck_handle_t *h, const ck_fieldcal_params_t *p, int32_t n_cams, const ck_sqpnp_problem_t *records,
+                             int32_t n_steps, const int32_t *tag_index, int32_t n_tags_total, const double *bearings,
+                             int32_t n_bearings_total, const double *gyro, const ck_rigcal_problem_t *problems, int32_t n_problems,
+                             const int32_t *step_index, int32_t n_index_total, const ck_iso3_t *mounts, const ck_iso3_t *layout0,
+                             int32_t n_layout, const uint8_t *fixed6, ck_fieldcal_result_t *results, ck_iso3_t *layout_out,
+                             int32_t *tag_sightings, double *tag_rms, double *poses_out);
+
 /* ---- multi-GPU: the final pose gather ----------------------------------------------------------------------------------
  * Frames shard over GPUs without any data-path collective (one handle, one process or host thread per GPU).  The only
  * exchange is the gather of the 64-byte records (the wire struct of crates/whacknet/src/lib.rs:43-66): ONE ncclAllGather
