@@ -84,6 +84,20 @@ class RigResult(C.Structure):
                 ("cam_tags", C.c_int32 * CK_RIG_MAX_CAMS), ("cam_rms", C.c_double * CK_RIG_MAX_CAMS)]
 
 
+CK_RIG_ROBUST_MAX_TAGS = 64
+CK_RIG_ROBUST_CLEAN, CK_RIG_ROBUST_REJECTED, CK_RIG_ROBUST_MAXROUNDS, CK_RIG_ROBUST_NO_CONSENSUS = 0, 1, 2, 3
+
+
+class RigRobustParams(C.Structure):
+    _fields_ = [("rig", RigParams), ("gate_rad", C.c_double), ("mu_factor", C.c_double), ("max_rounds", C.c_int32),
+                ("min_inlier_tags", C.c_int32)]
+
+
+class RigRobustResult(C.Structure):
+    _fields_ = [("fused", RigResult), ("status", C.c_int32), ("rounds", C.c_int32), ("n_rejected", C.c_int32), ("pad", C.c_int32),
+                ("rejected", C.c_uint64 * CK_RIG_MAX_CAMS), ("worst_inlier_rad", C.c_double), ("best_rejected_rad", C.c_double)]
+
+
 class OpenCV5(C.Structure):
     _fields_ = [(k, C.c_double) for k in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3")]
 
@@ -223,6 +237,7 @@ assert C.sizeof(Rect) == 16 and C.sizeof(ExposureStats) == 6416 and C.sizeof(Exp
 assert C.sizeof(TriOtsuParams) == 16 and C.sizeof(TriOtsuInfo) == 160
 assert C.sizeof(CalibParams) == 24 and C.sizeof(CalibProblem) == 16 and C.sizeof(CalibResult) == 112
 assert C.sizeof(RigParams) == 32 and C.sizeof(RigResult) == 240
+assert C.sizeof(RigRobustParams) == 56 and C.sizeof(RigRobustResult) == 336
 
 
 class RigcalResult(C.Structure):

@@ -12,6 +12,7 @@
 struct ck_rig_ws {
     ck_dev_buf<double> d_points;            // [n][max_points][CK_RIG_POINT_DOUBLES] the kernel's first pass
     ck_dev_buf<ck_rig_result_t> d_res;      // [n]
+    ck_dev_buf<ck_rig_robust_result_t> d_rres; // [n] the robust calls' records, in d_res's place
     ck_dev_buf<double> d_gyro;              // [n]
     ck_dev_buf<uint8_t> d_has_gyro;         // [n] (ck_rig_process_last)
     ck_dev_buf<ck_vision_measurement_t> d_meas; // [n]

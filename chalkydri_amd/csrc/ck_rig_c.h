@@ -16,6 +16,9 @@ extern "C" {
 int ck_rig_check(const ck_rig_params_t *params, int32_t n_cams, const ck_sqpnp_problem_t *problems, int32_t n, const void *tags,
                  int32_t n_tags_total, const void *bearings, int32_t n_bearings_total, const void *gyro, const void *out,
                  int32_t *max_points);
+/* ... and what the robust solvers refuse beyond that: the four parameters of the robust params and, when `problems` (host
+ * memory, already through ck_rig_check) is given, a record of more than CK_RIG_ROBUST_MAX_TAGS tags. */
+int ck_rig_robust_check(const ck_rig_robust_params_t *params, int32_t n_cams, const ck_sqpnp_problem_t *problems, int32_t n);
 #ifdef __cplusplus
 }
 #endif

@@ -232,75 +232,98 @@ int ck_rig_check(const ck_rig_params_t *params, int32_t n_cams, const ck_sqpnp_p
     return CK_OK;
 }
 
-static void solve_step(const ck_rig_params_t *prm, int n_cams, const ck_sqpnp_problem_t *problems, int n, int step, const ck_iso3_t *tags,
-                       const double *bearings, double gyro, double *world, double *dir, int *cam_of, ck_rig_result_t *out) {
+/* One step's cameras and points.  A tag weight array `w` (one per tag, the tags numbered camera-major, then by the record's index;
+ * null: every tag counts once) runs through the pieces below: the plain solve is the pieces with w = null, the robust solve
+ *  the same pieces with the weights of its rounds.  A point of weight 0 is skipped, a weight of 1 multiplies exactly. */
+typedef struct {
+    int n_cams, N;
+    double A[CK_RIG_MAX_CAMS][9], b[CK_RIG_MAX_CAMS][3], o[CK_RIG_MAX_CAMS][3];
+    int base[CK_RIG_MAX_CAMS + 1];
+    const ck_iso3_t *tg[CK_RIG_MAX_CAMS];
+    double *world, *dir;
+    int *cam_of;
+} rig_step_t;
+typedef struct {
+    double centroid[3], Qrr[81], Qrt[27], qt[3], QttInv[9], omega[81], g[9], cc, S[9];
+} rig_sys_t;
+
+static double tag_weight(const double *w, int point) { return w ? w[point >> 2] : 1.0; }
+
+static void rig_prepare(rig_step_t *st, int n_cams, const ck_sqpnp_problem_t *problems, int n, int step, const ck_iso3_t *tags,
+                        const double *bearings, double *world, double *dir, int *cam_of) {
     static const double cp[4][3] = {{0, -CORNER_DISTANCE, -CORNER_DISTANCE}, {0, CORNER_DISTANCE, -CORNER_DISTANCE},
                                     {0, CORNER_DISTANCE, CORNER_DISTANCE}, {0, -CORNER_DISTANCE, CORNER_DISTANCE}};
-    double A[CK_RIG_MAX_CAMS][9], b[CK_RIG_MAX_CAMS][3], o[CK_RIG_MAX_CAMS][3];
-    int base[CK_RIG_MAX_CAMS + 1], total_tags = 0;
-    memset(out, 0, sizeof *out);
-    base[0] = 0;
+    st->n_cams = n_cams; st->world = world; st->dir = dir; st->cam_of = cam_of;
+    st->base[0] = 0;
     for (int c = 0; c < n_cams; c++) {
         const ck_sqpnp_problem_t *p = &problems[(size_t)c * (size_t)n + (size_t)step];
-        quat_to_mat(p->robot_to_cam.q, A[c]);
-        for (int k = 0; k < 3; k++) b[c][k] = p->robot_to_cam.t[k];
-        for (int i = 0; i < 3; i++) o[c][i] = -(A[c][i] * b[c][0] + A[c][3 + i] * b[c][1] + A[c][6 + i] * b[c][2]);
-        base[c + 1] = base[c] + 4 * p->n_tags;
-        total_tags += p->n_tags;
+        quat_to_mat(p->robot_to_cam.q, st->A[c]);
+        for (int k = 0; k < 3; k++) st->b[c][k] = p->robot_to_cam.t[k];
+        for (int i = 0; i < 3; i++) st->o[c][i] = -(st->A[c][i] * st->b[c][0] + st->A[c][3 + i] * st->b[c][1] + st->A[c][6 + i] * st->b[c][2]);
+        st->base[c + 1] = st->base[c] + 4 * p->n_tags;
+        st->tg[c] = tags + p->tag_offset;
     }
-    const int N = base[n_cams];
-    if (N < 3) return;
-    double tc[3] = {0, 0, 0}; /* sum of the tag centres, cameras and tags in index order */
+    st->N = st->base[n_cams];
     for (int c = 0; c < n_cams; c++) {
         const ck_sqpnp_problem_t *p = &problems[(size_t)c * (size_t)n + (size_t)step];
-        const ck_iso3_t *tg = tags + p->tag_offset;
+        const ck_iso3_t *tg = st->tg[c];
         const double *v = bearings + (size_t)3 * (size_t)p->bearing_offset;
         for (int j = 0; j < 4 * p->n_tags; j++) {
-            const int i = base[c] + j, t = j >> 2;
+            const int i = st->base[c] + j, t = j >> 2;
             double R[9], pt[3];
             quat_to_mat(tg[t].q, R);
             mat3_vec(R, cp[j & 3], pt);
             for (int k = 0; k < 3; k++) world[i * 3 + k] = pt[k] + tg[t].t[k];
-            for (int k = 0; k < 3; k++) dir[i * 3 + k] = A[c][k] * v[3 * j] + A[c][3 + k] * v[3 * j + 1] + A[c][6 + k] * v[3 * j + 2];
+            for (int k = 0; k < 3; k++) dir[i * 3 + k] = st->A[c][k] * v[3 * j] + st->A[c][3 + k] * v[3 * j + 1] + st->A[c][6 + k] * v[3 * j + 2];
             cam_of[i] = c;
         }
-        for (int t = 0; t < p->n_tags; t++)
-            for (int k = 0; k < 3; k++) tc[k] += tg[t].t[k];
     }
-    double centroid[3];
+}
+
+/* the accumulated entries, centred on the (weighted) centroid, and Omega, g, c */
+static void rig_system(const rig_step_t *st, const double *w, rig_sys_t *y) {
+    const int N = st->N;
+    const double *world = st->world, *dir = st->dir;
     for (int k = 0; k < 3; k++) {
-        double s = 0;
-        for (int i = 0; i < N; i++) s += world[i * 3 + k];
-        centroid[k] = s / (double)N;
+        double s = 0, sw = 0;
+        for (int i = 0; i < N; i++) {
+            const double wi = tag_weight(w, i);
+            if (wi == 0.0) continue;
+            s += wi * world[i * 3 + k];
+            sw += wi;
+        }
+        y->centroid[k] = s / sw;
     }
-    double Qrr[81], Qrt[27], Qtt[9], qr[9], qt[3], q0 = 0, S[9];
-    memset(Qrr, 0, sizeof Qrr); memset(Qrt, 0, sizeof Qrt); memset(Qtt, 0, sizeof Qtt); memset(qr, 0, sizeof qr); memset(qt, 0, sizeof qt);
-    memset(S, 0, sizeof S);
+    double *Qrr = y->Qrr, *Qrt = y->Qrt, Qtt[9], qr[9], *qt = y->qt, q0 = 0, *S = y->S;
+    memset(Qrr, 0, sizeof y->Qrr); memset(Qrt, 0, sizeof y->Qrt); memset(Qtt, 0, sizeof Qtt); memset(qr, 0, sizeof qr); memset(qt, 0, sizeof y->qt);
+    memset(S, 0, sizeof y->S);
     for (int k = 0; k < N; k++) {
-        const double *u = dir + 3 * k, *oc = o[cam_of[k]];
-        const double X[3] = {world[k * 3] - centroid[0], world[k * 3 + 1] - centroid[1], world[k * 3 + 2] - centroid[2]};
+        const double wk = tag_weight(w, k);
+        if (wk == 0.0) continue;
+        const double *u = dir + 3 * k, *oc = st->o[st->cam_of[k]];
+        const double X[3] = {world[k * 3] - y->centroid[0], world[k * 3 + 1] - y->centroid[1], world[k * 3 + 2] - y->centroid[2]};
         const double sq = u[0] * u[0] + u[1] * u[1] + u[2] * u[2], inv = 1.0 / sq;
         double P[9], Mo[3];
         for (int i = 0; i < 3; i++)
             for (int j = 0; j < 3; j++) P[i * 3 + j] = (i == j ? 1.0 : 0.0) - (u[i] * u[j]) * inv;
         for (int i = 0; i < 3; i++) Mo[i] = P[i * 3] * oc[0] + P[i * 3 + 1] * oc[1] + P[i * 3 + 2] * oc[2];
-        for (int i = 0; i < 9; i++) Qtt[i] += P[i];
+        for (int i = 0; i < 9; i++) Qtt[i] += wk * P[i];
         for (int a = 0; a < 3; a++) {
             for (int i = 0; i < 3; i++) {
-                for (int j = 0; j < 3; j++) Qrt[(3 * a + i) * 3 + j] += P[i * 3 + j] * X[a];
-                qr[3 * a + i] += X[a] * Mo[i];
+                for (int j = 0; j < 3; j++) Qrt[(3 * a + i) * 3 + j] += wk * (P[i * 3 + j] * X[a]);
+                qr[3 * a + i] += wk * (X[a] * Mo[i]);
             }
             for (int bb = 0; bb < 3; bb++)
                 for (int i = 0; i < 3; i++)
-                    for (int j = 0; j < 3; j++) Qrr[(3 * a + i) * 9 + 3 * bb + j] += (P[i * 3 + j] * X[a]) * X[bb];
+                    for (int j = 0; j < 3; j++) Qrr[(3 * a + i) * 9 + 3 * bb + j] += wk * ((P[i * 3 + j] * X[a]) * X[bb]);
         }
-        for (int i = 0; i < 3; i++) qt[i] += Mo[i];
-        q0 += oc[0] * Mo[0] + oc[1] * Mo[1] + oc[2] * Mo[2];
+        for (int i = 0; i < 3; i++) qt[i] += wk * Mo[i];
+        q0 += wk * (oc[0] * Mo[0] + oc[1] * Mo[1] + oc[2] * Mo[2]);
         for (int i = 0; i < 3; i++)
-            for (int j = i; j < 3; j++) S[i * 3 + j] += X[i] * X[j]; /* scatter of the centred points (upper triangle) */
+            for (int j = i; j < 3; j++) S[i * 3 + j] += wk * (X[i] * X[j]); /* scatter of the centred points (upper triangle) */
     }
-    double QttInv[9], omega[81], g[9], cc;
-    if (!mat3_try_inverse(Qtt, QttInv)) memset(QttInv, 0, sizeof QttInv);
+    double *QttInv = y->QttInv, *omega = y->omega, *g = y->g;
+    if (!mat3_try_inverse(Qtt, QttInv)) memset(QttInv, 0, sizeof y->QttInv);
     for (int i = 0; i < 9; i++) {
         const double t0 = Qrt[i * 3] * QttInv[0] + Qrt[i * 3 + 1] * QttInv[3] + Qrt[i * 3 + 2] * QttInv[6];
         const double t1 = Qrt[i * 3] * QttInv[1] + Qrt[i * 3 + 1] * QttInv[4] + Qrt[i * 3 + 2] * QttInv[7];
@@ -309,10 +332,16 @@ static void solve_step(const ck_rig_params_t *prm, int n_cams, const ck_sqpnp_pr
         g[i] = qr[i] - (t0 * qt[0] + t1 * qt[1] + t2 * qt[2]);
     }
     {
-        double w[3];
-        mat3_vec(QttInv, qt, w);
-        cc = q0 - (qt[0] * w[0] + qt[1] * w[1] + qt[2] * w[2]);
+        double ww[3];
+        mat3_vec(QttInv, qt, ww);
+        y->cc = q0 - (qt[0] * ww[0] + qt[1] * ww[1] + qt[2] * ww[2]);
     }
+}
+
+/* the six starts, refined, and their order by penalised energy */
+static void rig_starts(const ck_rig_params_t *prm, rig_sys_t *y, double gyro, double candR[6][9], double candE[6], int order[6]) {
+    const double *omega = y->omega, *g = y->g, *Qrr = y->Qrr;
+    double *S = y->S;
     double Aw[81], V[81], ev[9];
     memcpy(Aw, omega, sizeof Aw);
     {   /* Coplanar points (one tag; tags on one wall) with normal n: R n is free, Omega has the exact null space {vec(a n^T)} and its
@@ -346,48 +375,58 @@ static void solve_step(const ck_rig_params_t *prm, int n_cams, const ck_sqpnp_pr
         idx[j + 1] = v;
     }
     const double gc = cos(gyro), gs = sin(gyro);
-    double candR[6][9], candE[6];
     for (int q = 0; q < 6; q++) {
         const int t = q >> 1;
         const double sign = (q & 1) ? 1.0 : -1.0;
         double guess[9], *r = candR[q];
         for (int k = 0; k < 9; k++) guess[k] = V[k * 9 + idx[t]] * sign;
         nearest_so3(guess, r);
-        double energy = full_energy(optimization(prm->sqpnp.max_iter, prm->sqpnp.tol_sq, r, omega, g), r, g, cc);
+        double energy = full_energy(optimization(prm->sqpnp.max_iter, prm->sqpnp.tol_sq, r, omega, g), r, g, y->cc);
         double dot = r[0] * gc + r[3] * gs; /* the robot's forward axis in the world is row 0 of R */
         double ae = 1.0 - dot;
         if (ae < 0.0) ae = 0.0;
         candE[q] = energy + prm->sign_change_error * ae;
     }
-    int order[6] = {0, 1, 2, 3, 4, 5};
+    for (int i = 0; i < 6; i++) order[i] = i;
     for (int i = 1; i < 6; i++) { /* stable sort by penalised energy */
         int v = order[i], j = i - 1;
         while (j >= 0 && candE[order[j]] > candE[v]) { order[j + 1] = order[j]; j--; }
         order[j + 1] = v;
     }
+}
+
+/* R (row-major) of r (column-major) and the t that goes with it */
+static void rig_translation(const rig_sys_t *y, const double r[9], double Rm[9], double t[3]) {
+    double qtr[3], d[3], tl[3], Rc[3];
+    for (int c = 0; c < 3; c++)
+        for (int rr = 0; rr < 3; rr++) Rm[rr * 3 + c] = r[c * 3 + rr];
+    for (int j = 0; j < 3; j++) {
+        double s = 0;
+        for (int i = 0; i < 9; i++) s += y->Qrt[i * 3 + j] * r[i];
+        qtr[j] = s;
+    }
+    for (int k = 0; k < 3; k++) d[k] = y->qt[k] - qtr[k];
+    mat3_vec(y->QttInv, d, tl);
+    mat3_vec(Rm, y->centroid, Rc);
+    for (int k = 0; k < 3; k++) t[k] = tl[k] - Rc[k];
+}
+
+/* the cheapest candidate with every point (of a weight other than 0) in front of its own camera */
+static int rig_pick(const rig_step_t *st, const rig_sys_t *y, const double *w, double candR[6][9], const double candE[6], const int order[6],
+                    double bestRm[9], double bestT[3]) {
     int found = 0;
-    double best_score = DBL_MAX, bestRm[9], bestT[3], best_energy = 0;
+    double best_score = DBL_MAX;
     for (int oi = 0; oi < 6; oi++) {
-        const double *r = candR[order[oi]];
-        double Rm[9], qtr[3], d[3], tl[3], Rc[3], t[3];
-        for (int c = 0; c < 3; c++)
-            for (int rr = 0; rr < 3; rr++) Rm[rr * 3 + c] = r[c * 3 + rr];
-        for (int j = 0; j < 3; j++) {
-            double s = 0;
-            for (int i = 0; i < 9; i++) s += Qrt[i * 3 + j] * r[i];
-            qtr[j] = s;
-        }
-        for (int k = 0; k < 3; k++) d[k] = qt[k] - qtr[k];
-        mat3_vec(QttInv, d, tl);
-        mat3_vec(Rm, centroid, Rc);
-        for (int k = 0; k < 3; k++) t[k] = tl[k] - Rc[k];
+        double Rm[9], t[3];
+        rig_translation(y, candR[order[oi]], Rm, t);
         int behind = 0;
-        for (int i = 0; i < N; i++) {
-            const int c = cam_of[i];
+        for (int i = 0; i < st->N; i++) {
+            if (tag_weight(w, i) == 0.0) continue;
+            const int c = st->cam_of[i];
             double pr[3];
-            mat3_vec(Rm, world + 3 * i, pr);
+            mat3_vec(Rm, st->world + 3 * i, pr);
             for (int k = 0; k < 3; k++) pr[k] += t[k];
-            if (!((A[c][6] * pr[0] + A[c][7] * pr[1] + A[c][8] * pr[2]) + b[c][2] > 0.0)) behind = 1;
+            if (!((st->A[c][6] * pr[0] + st->A[c][7] * pr[1] + st->A[c][8] * pr[2]) + st->b[c][2] > 0.0)) behind = 1;
         }
         if (behind) continue;
         if (candE[order[oi]] < best_score) {
@@ -397,26 +436,39 @@ static void solve_step(const ck_rig_params_t *prm, int n_cams, const ck_sqpnp_pr
             found = 1;
         }
     }
-    if (!found) return;
+    return found;
+}
+
+/* the record of the chosen candidate; bestR = polar(bestRm) comes back too */
+static void rig_finish(const rig_step_t *st, const double *w, const double bestRm[9], const double bestT[3], double gyro, double bestR[9],
+                       ck_rig_result_t *out) {
     /* The pose that is returned: R^ = polar(R), the rotation next to the refinement's last iterate (which meets the constraints to
      * round-off only), and t.  Per camera: its tags and the RMS point-to-ray distance of its own points at that pose.  The squared
      * distances, summed per camera and then over the cameras, are E again, without the cancellation of the quadratic form (terms
      * of the size of |o|^2 * points against a sum of noise^2) and, taken ON the constraint manifold, without the first-order
      * sensitivity to how far off it the iterate ended: that sum is the energy the record and the standard deviations carry. */
-    double bestR[9];
+    const double *world = st->world, *dir = st->dir;
+    int total_tags = 0;
+    double best_energy = 0, tc[3] = {0, 0, 0}; /* tc: sum of the tag centres, cameras and tags in index order */
     polar_rotation(bestRm, bestR);
-    best_energy = 0;
-    for (int c = 0; c < n_cams; c++) {
-        const int cnt = base[c + 1] - base[c];
+    for (int c = 0; c < st->n_cams; c++) {
+        int cnt = 0;
+        for (int i = st->base[c]; i < st->base[c + 1]; i += 4)
+            if (tag_weight(w, i) != 0.0) {
+                cnt += 4;
+                for (int k = 0; k < 3; k++) tc[k] += st->tg[c][(i - st->base[c]) >> 2].t[k];
+            }
         out->cam_tags[c] = cnt / 4;
+        total_tags += cnt / 4;
         if (!cnt) continue;
         double s = 0;
-        for (int i = base[c]; i < base[c + 1]; i++) {
+        for (int i = st->base[c]; i < st->base[c + 1]; i++) {
+            if (tag_weight(w, i) == 0.0) continue;
             const double *u = dir + 3 * i;
             const double sq = u[0] * u[0] + u[1] * u[1] + u[2] * u[2], inv = 1.0 / sq;
             double d[3], Pd[3];
             mat3_vec(bestR, world + 3 * i, d);
-            for (int k = 0; k < 3; k++) d[k] = (d[k] + bestT[k]) - o[c][k];
+            for (int k = 0; k < 3; k++) d[k] = (d[k] + bestT[k]) - st->o[c][k];
             /* d^T M d = |M d|^2 (M is a projector): the square of a small vector, not the product of a small with a large one */
             const double along = (u[0] * d[0] + u[1] * d[1] + u[2] * d[2]) * inv;
             for (int k = 0; k < 3; k++) Pd[k] = d[k] - u[k] * along;
@@ -469,6 +521,131 @@ static void solve_step(const ck_rig_params_t *prm, int n_cams, const ck_sqpnp_pr
     out->valid = 1;
 }
 
+static void solve_step(const ck_rig_params_t *prm, int n_cams, const ck_sqpnp_problem_t *problems, int n, int step, const ck_iso3_t *tags,
+                       const double *bearings, double gyro, double *world, double *dir, int *cam_of, ck_rig_result_t *out) {
+    rig_step_t st;
+    rig_sys_t y;
+    double candR[6][9], candE[6], bestRm[9], bestT[3], bestR[9];
+    int order[6];
+    memset(out, 0, sizeof *out);
+    rig_prepare(&st, n_cams, problems, n, step, tags, bearings, world, dir, cam_of);
+    if (st.N < 3) return;
+    rig_system(&st, NULL, &y);
+    rig_starts(prm, &y, gyro, candR, candE, order);
+    if (!rig_pick(&st, &y, NULL, candR, candE, order, bestRm, bestT)) return;
+    rig_finish(&st, NULL, bestRm, bestT, gyro, bestR, out);
+}
+
+/* ---- the robust solve (chalkydri_hip.h has the arithmetic) ---- */
+/* rho of every tag at (R row-major, t): the mean over its corners of the squared sine of the angle between the ray and the point */
+static void rig_tag_rho(const rig_step_t *st, const double R[9], const double t[3], double *rho) {
+    for (int j = 0; j < st->N / 4; j++) {
+        double s = 0;
+        for (int i = 4 * j; i < 4 * j + 4; i++) {
+            const double *u = st->dir + 3 * i, *oc = st->o[st->cam_of[i]];
+            const double sq = u[0] * u[0] + u[1] * u[1] + u[2] * u[2], inv = 1.0 / sq;
+            double d[3], Pd[3];
+            mat3_vec(R, st->world + 3 * i, d);
+            for (int k = 0; k < 3; k++) d[k] = (d[k] + t[k]) - oc[k];
+            const double ud = u[0] * d[0] + u[1] * d[1] + u[2] * d[2], along = ud * inv;
+            for (int k = 0; k < 3; k++) Pd[k] = d[k] - u[k] * along;
+            const double pp = Pd[0] * Pd[0] + Pd[1] * Pd[1] + Pd[2] * Pd[2], dd = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
+            s += (ud > 0.0 && dd > 0.0) ? pp / dd : 1.0;
+        }
+        rho[j] = s * 0.25;
+    }
+}
+static double gnc_weight(double rho, double mu, double c, double c2) {
+    const double lo = (mu / (mu + 1.0)) * c2, hi = ((mu + 1.0) / mu) * c2;
+    if (rho <= lo) return 1.0;
+    if (rho >= hi) return 0.0;
+    return (c / sqrt(rho)) * sqrt(mu * (mu + 1.0)) - mu;
+}
+
+#define ROBUST_TAGS (CK_RIG_MAX_CAMS * CK_RIG_ROBUST_MAX_TAGS)
+static void solve_step_robust(const ck_rig_robust_params_t *rp, int n_cams, const ck_sqpnp_problem_t *problems, int n, int step,
+                              const ck_iso3_t *tags, const double *bearings, double gyro, double *world, double *dir, int *cam_of,
+                              ck_rig_robust_result_t *out) {
+    const ck_rig_params_t *prm = &rp->rig;
+    rig_step_t st;
+    rig_sys_t y;
+    double candR[6][9], candE[6], bestRm[9], bestT[3], bestR[9], Rm[9], t[3], r[9];
+    double rho[ROBUST_TAGS], w[ROBUST_TAGS];
+    int order[6];
+    memset(out, 0, sizeof *out);
+    rig_prepare(&st, n_cams, problems, n, step, tags, bearings, world, dir, cam_of);
+    if (st.N < 3) return;
+    const int nt = st.N / 4;
+    const double c = rp->gate_rad, c2 = c * c;
+    rig_system(&st, NULL, &y);
+    rig_starts(prm, &y, gyro, candR, candE, order);
+    int found = rig_pick(&st, &y, NULL, candR, candE, order, bestRm, bestT);
+    if (found) {
+        for (int cc = 0; cc < 3; cc++)
+            for (int rr = 0; rr < 3; rr++) r[cc * 3 + rr] = bestRm[rr * 3 + cc];
+        memcpy(Rm, bestRm, sizeof Rm); memcpy(t, bestT, sizeof t);
+    } else { /* the cheapest candidate stands in */
+        memcpy(r, candR[order[0]], sizeof r);
+        rig_translation(&y, r, Rm, t);
+    }
+    rig_tag_rho(&st, Rm, t, rho);
+    double rho_max = rho[0];
+    for (int j = 1; j < nt; j++)
+        if (rho[j] > rho_max) rho_max = rho[j];
+    const double *wf = NULL; /* the weights of the final solve: null when no round ran */
+    if (!(rho_max <= c2)) {
+        double mu = c2 / (2.0 * rho_max - c2);
+        int maxed = 0;
+        for (int j = 0; j < nt; j++) w[j] = 1.0;
+        for (;;) {
+            int binary = 1, same = 1, alive = 0;
+            for (int j = 0; j < nt; j++) {
+                const double wn = gnc_weight(rho[j], mu, c, c2);
+                if (wn != 0.0 && wn != 1.0) binary = 0;
+                if (wn != w[j]) same = 0;
+                if (wn > 0.0) alive = 1;
+                w[j] = wn;
+            }
+            if ((binary && same) || !alive) break;
+            if (out->rounds == rp->max_rounds) { maxed = 1; break; }
+            rig_system(&st, w, &y);
+            double start[9];
+            nearest_so3(r, start);
+            memcpy(r, start, sizeof r);
+            (void)optimization(prm->sqpnp.max_iter, prm->sqpnp.tol_sq, r, y.omega, y.g);
+            rig_translation(&y, r, Rm, t);
+            rig_tag_rho(&st, Rm, t, rho);
+            mu *= rp->mu_factor;
+            out->rounds++;
+        }
+        int n_in = 0;
+        for (int j = 0; j < nt; j++) {
+            w[j] = (maxed ? w[j] >= 0.5 : w[j] == 1.0) ? 1.0 : 0.0;
+            n_in += w[j] != 0.0;
+        }
+        for (int cc = 0; cc < n_cams; cc++)
+            for (int i = st.base[cc]; i < st.base[cc + 1]; i += 4)
+                if (w[i >> 2] == 0.0) out->rejected[cc] |= (uint64_t)1 << ((i - st.base[cc]) >> 2);
+        out->n_rejected = nt - n_in;
+        out->status = maxed ? CK_RIG_ROBUST_MAXROUNDS : (out->n_rejected ? CK_RIG_ROBUST_REJECTED : CK_RIG_ROBUST_CLEAN);
+        if (n_in < rp->min_inlier_tags) { out->status = CK_RIG_ROBUST_NO_CONSENSUS; return; }
+        wf = w;
+        rig_system(&st, w, &y);
+        rig_starts(prm, &y, gyro, candR, candE, order);
+        found = rig_pick(&st, &y, w, candR, candE, order, bestRm, bestT);
+    } else if (nt < rp->min_inlier_tags) { out->status = CK_RIG_ROBUST_NO_CONSENSUS; return; }
+    if (!found) return;
+    rig_finish(&st, wf, bestRm, bestT, gyro, bestR, &out->fused);
+    rig_tag_rho(&st, bestR, bestT, rho);
+    double worst = 0.0, best = DBL_MAX;
+    for (int j = 0; j < nt; j++) {
+        if (!wf || wf[j] != 0.0) { if (rho[j] > worst) worst = rho[j]; }
+        else if (rho[j] < best) best = rho[j];
+    }
+    out->worst_inlier_rad = sqrt(worst);
+    out->best_rejected_rad = out->n_rejected ? sqrt(best) : 0.0;
+}
+
 void ck_rig_params_default(ck_rig_params_t *p) {
     if (!p) return;
     memset(p, 0, sizeof *p);
@@ -488,6 +665,44 @@ int ck_rig_solve_host(const ck_rig_params_t *params, int32_t n_cams, const ck_sq
     int *cam_of = (int *)malloc(sizeof(int) * cap);
     if (!world || !cam_of) { free(world); free(cam_of); return CK_ENOMEM; }
     for (int s = 0; s < n; s++) solve_step(params, n_cams, problems, n, s, tags, bearings, gyro[s], world, world + 3 * cap, cam_of, &out[s]);
+    free(world); free(cam_of);
+    return CK_OK;
+}
+
+void ck_rig_robust_params_default(ck_rig_robust_params_t *p) {
+    if (!p) return;
+    memset(p, 0, sizeof *p);
+    ck_rig_params_default(&p->rig);
+    p->gate_rad = 0.01;
+    p->mu_factor = 1.4;
+    p->max_rounds = 64;
+    p->min_inlier_tags = 1;
+}
+
+int ck_rig_robust_check(const ck_rig_robust_params_t *params, int32_t n_cams, const ck_sqpnp_problem_t *problems, int32_t n) {
+    if (!params) return CK_EINVAL;
+    if (!isfinite(params->gate_rad) || !(params->gate_rad > 0.0) || !isfinite(params->mu_factor) || !(params->mu_factor > 1.0) ||
+        params->max_rounds < 1 || params->min_inlier_tags < 1) return CK_EINVAL;
+    if (problems)
+        for (size_t i = 0; i < (size_t)n_cams * (size_t)n; i++)
+            if (problems[i].n_tags > CK_RIG_ROBUST_MAX_TAGS) return CK_EINVAL;
+    return CK_OK;
+}
+
+int ck_rig_solve_robust_host(const ck_rig_robust_params_t *params, int32_t n_cams, const ck_sqpnp_problem_t *problems, int32_t n,
+                             const ck_iso3_t *tags, int32_t n_tags_total, const double *bearings, int32_t n_bearings_total,
+                             const double *gyro, ck_rig_robust_result_t *out) {
+    int32_t max_points = 0;
+    if (!params) return CK_EINVAL;
+    int rc = ck_rig_check(&params->rig, n_cams, problems, n, tags, n_tags_total, bearings, n_bearings_total, gyro, out, &max_points);
+    if (rc != CK_OK) return rc;
+    if ((rc = ck_rig_robust_check(params, n_cams, problems, n)) != CK_OK) return rc;
+    const size_t cap = max_points > 0 ? (size_t)max_points : 1;
+    double *world = (double *)malloc(sizeof(double) * 6 * cap);
+    int *cam_of = (int *)malloc(sizeof(int) * cap);
+    if (!world || !cam_of) { free(world); free(cam_of); return CK_ENOMEM; }
+    for (int s = 0; s < n; s++)
+        solve_step_robust(params, n_cams, problems, n, s, tags, bearings, gyro[s], world, world + 3 * cap, cam_of, &out[s]);
     free(world); free(cam_of);
     return CK_OK;
 }

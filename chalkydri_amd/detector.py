@@ -125,6 +125,12 @@ def _bind(L):
     L.ck_rig_solve_batch.argtypes = [vp, rp, i32, sp, i32, _P(A.Iso3), i32, vp, i32, vp, rr]
     L.ck_rig_process_last.argtypes = [_P(vp), i32, i32, rp, vp, vp, rr, _P(A.VisionMeasurement), _P(i32)]
     L.ck_rig_time_last.argtypes = [_P(vp), i32, i32, rp, vp, vp, i32, vp, vp]
+    bp, br = _P(A.RigRobustParams), _P(A.RigRobustResult)
+    L.ck_rig_robust_params_default.argtypes = [bp]
+    L.ck_rig_robust_params_default.restype = None
+    L.ck_rig_solve_robust_host.argtypes = [bp, i32, sp, i32, _P(A.Iso3), i32, vp, i32, vp, br]
+    L.ck_rig_solve_robust_batch.argtypes = [vp, bp, i32, sp, i32, _P(A.Iso3), i32, vp, i32, vp, br]
+    L.ck_rig_process_last_robust.argtypes = [_P(vp), i32, i32, bp, vp, vp, br, _P(A.VisionMeasurement), _P(i32)]
     mp, mq, mr, iso = _P(A.RigcalParams), _P(A.RigcalProblem), _P(A.RigcalResult), _P(A.Iso3)
     L.ck_rigcal_params_default.argtypes = [mp]
     L.ck_rigcal_params_default.restype = None

@@ -1,7 +1,8 @@
 """All the cameras of a robot fused into one robot pose: SQPnP over rays with different origins.
 
 RigSolver is the stand-alone solver over the C ABI (ck_rig_solve_batch on a handle's device, ck_rig_solve_host without one);
-AprilTagsRig runs one AprilTags task per camera and fuses what they left on the device (ck_rig_process_last).
+AprilTagsRig runs one AprilTags task per camera and fuses what they left on the device (ck_rig_process_last).  Both take
+`robust`: the solve that drops a wrong tag, GNC-TLS around the same solver (ck_rig_*_robust*).
 """
 import ctypes as C
 
@@ -15,6 +16,35 @@ RESULT_DTYPE = np.dtype([("valid", np.int32), ("n_tags", np.int32), ("rot", np.f
                          ("std_devs", np.float64, 3), ("yaw", np.float64), ("energy", np.float64),
                          ("cam_tags", np.int32, A.CK_RIG_MAX_CAMS), ("cam_rms", np.float64, A.CK_RIG_MAX_CAMS)])
 assert RESULT_DTYPE.itemsize == C.sizeof(A.RigResult)
+ROBUST_RESULT_DTYPE = np.dtype([("fused", RESULT_DTYPE), ("status", np.int32), ("rounds", np.int32), ("n_rejected", np.int32),
+                                ("pad", np.int32), ("rejected", np.uint64, A.CK_RIG_MAX_CAMS), ("worst_inlier_rad", np.float64),
+                                ("best_rejected_rad", np.float64)])
+assert ROBUST_RESULT_DTYPE.itemsize == C.sizeof(A.RigRobustResult)
+
+
+class RobustParams:
+    """gate_rad: the angle (rad) beyond which a tag's corners do not belong to the pose; mu_factor, max_rounds: the GNC schedule;
+    min_inlier_tags: fewer tags than this left is no pose (status NO_CONSENSUS)."""
+
+    def __init__(self, gate_rad=None, mu_factor=None, max_rounds=None, min_inlier_tags=None):
+        self.gate_rad, self.mu_factor, self.max_rounds, self.min_inlier_tags = gate_rad, mu_factor, max_rounds, min_inlier_tags
+
+    def _c(self, L, rig):
+        p = A.RigRobustParams()
+        L.ck_rig_robust_params_default(C.byref(p))
+        p.rig = rig
+        for k in ("gate_rad", "mu_factor", "max_rounds", "min_inlier_tags"):
+            if getattr(self, k) is not None:
+                setattr(p, k, getattr(self, k))
+        return p
+
+
+def _robust(robust):
+    if robust is None or isinstance(robust, RobustParams):
+        return robust
+    if robust is True:
+        return RobustParams()
+    raise TypeError("robust is None, True or a RobustParams")
 
 
 def pack_steps(steps):
@@ -56,13 +86,27 @@ class RigSolver:
         self.params.sqpnp.tol_sq = float(tol) * float(tol)
         return self
 
-    def _solve(self, steps, gyro, host):
+    def _solve(self, steps, gyro, host, robust=None):
+        robust = _robust(robust)
         n = len(steps)
         n_cams, probs, tarr, nt, barr = pack_steps(steps)
         g = np.ascontiguousarray(gyro, np.float64).reshape(-1)
         if len(g) != n:
             raise ValueError("one gyro heading per step")
         g = g if n else np.zeros(1)
+        if robust is not None:
+            prm = robust._c(self._L, self.params)
+            res = np.zeros(max(n, 1), ROBUST_RESULT_DTYPE)
+            rp = res.ctypes.data_as(C.POINTER(A.RigRobustResult))
+            if host:
+                check(self._L.ck_rig_solve_robust_host(C.byref(prm), n_cams, probs, n, tarr, nt, barr.ctypes.data, len(barr),
+                                                       g.ctypes.data, rp), "ck_rig_solve_robust_host")
+            else:
+                if self._det is None:
+                    raise RuntimeError("RigSolver.solve_batch needs a device handle (pass an AprilTagDetector)")
+                check(self._L.ck_rig_solve_robust_batch(self._det._h, C.byref(prm), n_cams, probs, n, tarr, nt, barr.ctypes.data,
+                                                        len(barr), g.ctypes.data, rp), "ck_rig_solve_robust_batch")
+            return res[:n]
         res = np.zeros(max(n, 1), RESULT_DTYPE)
         rp = res.ctypes.data_as(C.POINTER(A.RigResult))
         if host:
@@ -75,18 +119,21 @@ class RigSolver:
                                              len(barr), g.ctypes.data, rp), "ck_rig_solve_batch")
         return res[:n]
 
-    def solve_batch(self, steps, gyro):
-        """One robot pose per step on the device; steps as pack_steps takes them.  Returns a RESULT_DTYPE array."""
-        return self._solve(steps, gyro, False)
+    def solve_batch(self, steps, gyro, robust=None):
+        """One robot pose per step on the device; steps as pack_steps takes them.  Returns a RESULT_DTYPE array; with `robust` (True or
+        a RobustParams) the solve that drops wrong tags and a ROBUST_RESULT_DTYPE array, the pose in its "fused"."""
+        return self._solve(steps, gyro, False, robust)
 
-    def solve_host(self, steps, gyro):
+    def solve_host(self, steps, gyro, robust=None):
         """The same on the host, one thread, no device."""
-        return self._solve(steps, gyro, True)
+        return self._solve(steps, gyro, True, robust)
 
 
 class AprilTagsRig:
-    def __init__(self, tasks, rig_id=255):
-        """tasks: one AprilTags task per camera (1..8, all on one device); sizes, calibrations and mounts may differ."""
+    def __init__(self, tasks, rig_id=255, robust=None):
+        """tasks: one AprilTags task per camera (1..8, all on one device); sizes, calibrations and mounts may differ.  robust: True
+        or a RobustParams for the solve that drops wrong tags (last_results is then of ROBUST_RESULT_DTYPE)."""
+        self.robust = _robust(robust)
         if not 1 <= len(tasks) <= A.CK_RIG_MAX_CAMS:
             raise ValueError(f"a rig has 1..{A.CK_RIG_MAX_CAMS} cameras")
         self.tasks = list(tasks)
@@ -102,8 +149,9 @@ class AprilTagsRig:
             raise ValueError("one frame batch per camera")
         n = len(frames_per_camera[0])
         per_cam = [t.process_batch(f, gyro) for t, f in zip(self.tasks, frames_per_camera)]
+        dtype = RESULT_DTYPE if self.robust is None else ROBUST_RESULT_DTYPE
         if n == 0:
-            self.last_results = np.zeros(0, RESULT_DTYPE)
+            self.last_results = np.zeros(0, dtype)
             return (A.VisionMeasurement * 0)(), np.zeros(0, bool), per_cam
         g = np.zeros(max(n, 1), np.float64)
         has = np.zeros(max(n, 1), np.uint8)
@@ -111,11 +159,17 @@ class AprilTagsRig:
             gi = None if gyro is None else (gyro if np.isscalar(gyro) else gyro[i])
             if gi is not None:
                 g[i], has[i] = gi, 1
-        res = np.zeros(max(n, 1), RESULT_DTYPE)
+        res = np.zeros(max(n, 1), dtype)
         meas = (A.VisionMeasurement * max(n, 1))()
         valid = (C.c_int32 * max(n, 1))()
         hs = (C.c_void_p * len(self.tasks))(*[t.detector._h.value for t in self.tasks])
-        check(self.solver._L.ck_rig_process_last(hs, len(self.tasks), n, C.byref(self.solver.params), g.ctypes.data, has.ctypes.data,
-                                                 res.ctypes.data_as(C.POINTER(A.RigResult)), meas, valid), "ck_rig_process_last")
+        if self.robust is not None:
+            prm = self.robust._c(self.solver._L, self.solver.params)
+            check(self.solver._L.ck_rig_process_last_robust(hs, len(self.tasks), n, C.byref(prm), g.ctypes.data, has.ctypes.data,
+                                                            res.ctypes.data_as(C.POINTER(A.RigRobustResult)), meas, valid),
+                  "ck_rig_process_last_robust")
+        else:
+            check(self.solver._L.ck_rig_process_last(hs, len(self.tasks), n, C.byref(self.solver.params), g.ctypes.data, has.ctypes.data,
+                                                     res.ctypes.data_as(C.POINTER(A.RigResult)), meas, valid), "ck_rig_process_last")
         self.last_results = res[:n]
         return (A.VisionMeasurement * n)(*meas[:n]), np.array(valid[:n], bool), per_cam

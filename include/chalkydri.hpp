@@ -978,14 +978,36 @@ class RigSolver {
     std::vector<ck_rig_result_t> solve_host(const std::vector<std::vector<RigView>> &steps, const std::vector<double> &gyro) const {
         return solve(steps, gyro, true);
     }
-
-  private:
-    std::vector<ck_rig_result_t> solve(const std::vector<std::vector<RigView>> &steps, const std::vector<double> &gyro, bool host) const {
-        const int n = (int)steps.size(), n_cams = n ? (int)steps[0].size() : 1;
-        if (gyro.size() != steps.size()) throw Panic("RigSolver: one gyro heading per step", CK_EINVAL);
-        std::vector<ck_sqpnp_problem_t> probs((size_t)n_cams * n + 1);
+    // The solve that drops a wrong tag (chalkydri_hip.h: ck_rig_solve_robust_*): GNC-TLS around the same solver, the
+    // pose of the inliers in `fused`.  On the device, or with host = true on the host.  The robust parameters' own `rig` is ignored:
+    // this solver's parameters take its place.
+    static ck_rig_robust_params_t robust_defaults() { ck_rig_robust_params_t p; ck_rig_robust_params_default(&p); return p; }
+    std::vector<ck_rig_robust_result_t> solve_robust(const std::vector<std::vector<RigView>> &steps, const std::vector<double> &gyro,
+                                                     ck_rig_robust_params_t robust = robust_defaults(), bool host = false) const {
+        if (!host && !h_) throw Panic("RigSolver::solve_robust needs a handle", CK_EINVAL);
+        robust.rig = prm_;
+        std::vector<ck_sqpnp_problem_t> probs;
         std::vector<ck_iso3_t> tags;
         std::vector<double> b;
+        const int n = (int)steps.size(), n_cams = pack(steps, gyro, probs, tags, b);
+        std::vector<ck_rig_robust_result_t> out((size_t)n + 1);
+        const double g0 = 0.0;
+        const int rc = host ? ck_rig_solve_robust_host(&robust, n_cams, probs.data(), n, tags.data(), (int32_t)tags.size(), b.data(),
+                                                       (int32_t)(b.size() / 3), n ? gyro.data() : &g0, out.data())
+                            : ck_rig_solve_robust_batch(h_->get(), &robust, n_cams, probs.data(), n, tags.data(), (int32_t)tags.size(), b.data(),
+                                                        (int32_t)(b.size() / 3), n ? gyro.data() : &g0, out.data());
+        check(rc, host ? "ck_rig_solve_robust_host" : "ck_rig_solve_robust_batch");
+        out.resize((size_t)n);
+        return out;
+    }
+
+  private:
+    // the records, tags and bearings of the steps as the C calls take them; returns the number of cameras
+    static int pack(const std::vector<std::vector<RigView>> &steps, const std::vector<double> &gyro, std::vector<ck_sqpnp_problem_t> &probs,
+                    std::vector<ck_iso3_t> &tags, std::vector<double> &b) {
+        const int n = (int)steps.size(), n_cams = n ? (int)steps[0].size() : 1;
+        if (gyro.size() != steps.size()) throw Panic("RigSolver: one gyro heading per step", CK_EINVAL);
+        probs.assign((size_t)n_cams * n + 1, ck_sqpnp_problem_t{});
         for (int s = 0; s < n; s++) {
             if ((int)steps[s].size() != n_cams) throw Panic("RigSolver: every step needs the same cameras", CK_EINVAL);
             for (int c = 0; c < n_cams; c++) {
@@ -999,6 +1021,13 @@ class RigSolver {
                 for (const auto &x : v.bearings) b.insert(b.end(), x.begin(), x.end());
             }
         }
+        return n_cams;
+    }
+    std::vector<ck_rig_result_t> solve(const std::vector<std::vector<RigView>> &steps, const std::vector<double> &gyro, bool host) const {
+        std::vector<ck_sqpnp_problem_t> probs;
+        std::vector<ck_iso3_t> tags;
+        std::vector<double> b;
+        const int n = (int)steps.size(), n_cams = pack(steps, gyro, probs, tags, b);
         std::vector<ck_rig_result_t> out((size_t)n + 1);
         const double g0 = 0.0;
         const int rc = host ? ck_rig_solve_host(&prm_, n_cams, probs.data(), n, tags.data(), (int32_t)tags.size(), b.data(), (int32_t)(b.size() / 3),
@@ -1027,6 +1056,27 @@ inline std::vector<std::pair<whacknet::VisionMeasurement, bool>> rig_process_las
     std::vector<whacknet::VisionMeasurement> out((size_t)n + 1);
     std::vector<int32_t> valid((size_t)n + 1);
     check(ck_rig_process_last(hs.data(), (int32_t)hs.size(), n, &params, g.data(), has.data(), res.data(), out.data(), valid.data()), "ck_rig_process_last");
+    std::vector<std::pair<whacknet::VisionMeasurement, bool>> r;
+    for (int i = 0; i < n; i++) r.emplace_back(out[i], valid[i] != 0);
+    if (results) results->assign(res.begin(), res.begin() + n);
+    return r;
+}
+// ... and with the solve that drops a wrong tag (ck_rig_process_last_robust): `robust.rig` is the rig's parameters
+inline std::vector<std::pair<whacknet::VisionMeasurement, bool>> rig_process_last_robust(const std::vector<AprilTags *> &tasks,
+                                                                                         const ck_rig_robust_params_t &robust,
+                                                                                         const std::vector<std::optional<double>> &gyro,
+                                                                                         std::vector<ck_rig_robust_result_t> *results = nullptr) {
+    const int n = (int)gyro.size();
+    std::vector<ck_handle_t *> hs;
+    for (const AprilTags *t : tasks) hs.push_back(t ? t->handle()->get() : nullptr);
+    std::vector<double> g((size_t)n + 1);
+    std::vector<uint8_t> has((size_t)n + 1);
+    for (int i = 0; i < n; i++) { has[i] = gyro[i].has_value(); g[i] = gyro[i].value_or(0.0); }
+    std::vector<ck_rig_robust_result_t> res((size_t)n + 1);
+    std::vector<whacknet::VisionMeasurement> out((size_t)n + 1);
+    std::vector<int32_t> valid((size_t)n + 1);
+    check(ck_rig_process_last_robust(hs.data(), (int32_t)hs.size(), n, &robust, g.data(), has.data(), res.data(), out.data(), valid.data()),
+          "ck_rig_process_last_robust");
     std::vector<std::pair<whacknet::VisionMeasurement, bool>> r;
     for (int i = 0; i < n; i++) r.emplace_back(out[i], valid[i] != 0);
     if (results) results->assign(res.begin(), res.begin() + n);

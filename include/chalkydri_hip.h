@@ -919,6 +919,63 @@ int ck_rig_process_last(ck_handle_t *const *handles, int32_t n_cams, int32_t n, 
 int ck_rig_time_last(ck_handle_t *const *handles, int32_t n_cams, int32_t n, const ck_rig_params_t *params, const double *gyro,
                      const uint8_t *has_gyro, int32_t iters, float *ms_rig, float *ms_sqpnp);
 
+/* ---- robust camera rig: the rig solve that drops a wrong tag ---------------------------------------------------
+ * Graduated non-convexity with a truncated-least-squares cost (GNC-TLS; Yang, Antonante, Tzoumas, Carlone, RA-L 2020) around the rig
+ * solve above.  The unit of rejection is the TAG (its four corners together): a wrong id, a wrong rotation of the corners and a tag
+ * that was moved all corrupt a whole tag.  The tags of an instant are numbered camera-major, then by the tag index of the record.
+ *   round 0   the plain solve on all tags (when no candidate passes the cheirality test, the cheapest candidate stands in for
+ *             what follows).  At the refinement's rotation R and its t, a point of camera c has d = R X + t - o_c and
+ *             e^2 = |d - u (u.d)/(u.u)|^2 / |d|^2 (rad^2; e^2 = 1 when u.d <= 0 or d = 0); rho_j = the mean of tag j's four e^2.
+ *   gate      max_j rho_j <= gate_rad^2: every tag is an inlier, `fused` is the plain solve's record byte for byte, status CLEAN.
+ *   GNC       otherwise mu = c^2 / (2 rho_max - c^2), c = gate_rad, and per round: w_j = 1 for rho_j <= mu/(mu+1) c^2, 0 for
+ *             rho_j >= (mu+1)/mu c^2, c/sqrt(rho_j) sqrt(mu(mu+1)) - mu between; when every w_j is 0 or 1 and so it was, with the
+ *             same values, the round before (round 0: all 1), the loop ends; after max_rounds rounds it ends with w_j >= 0.5 as the
+ *             inliers (status MAXROUNDS); else the weighted system (every point's contribution times its tag's weight, centred
+ *             on the weighted centroid, points of weight 0 skipped) is solved by ONE refinement from the nearest rotation of the
+ *             previous round's r, the rho_j are taken at it, mu *= mu_factor.
+ *   final     fewer than min_inlier_tags inliers: no pose (status NO_CONSENSUS, `fused` zero).  Otherwise `fused` is the plain
+ *             solve on the inlier tags alone: what ck_rig_solve_batch returns for the input with the rejected tags deleted.
+ * A camera's record of one step holds at most CK_RIG_ROBUST_MAX_TAGS tags: more is CK_EINVAL in the stand-alone calls; in
+ * ck_rig_process_last_robust such a step takes the PLAIN solve (status CLEAN, rounds 0, rejected 0), whatever its residuals. */
+#define CK_RIG_ROBUST_MAX_TAGS 64
+#define CK_RIG_ROBUST_CLEAN 0        /* no tag dropped (no GNC round ran, or every tag came back in) */
+#define CK_RIG_ROBUST_REJECTED 1     /* >= 1 tag dropped */
+#define CK_RIG_ROBUST_MAXROUNDS 2    /* max_rounds rounds ran without the weights settling; the inliers are w >= 0.5 */
+#define CK_RIG_ROBUST_NO_CONSENSUS 3 /* fewer than min_inlier_tags inliers: no pose */
+typedef struct ck_rig_robust_params {
+    ck_rig_params_t rig;
+    double gate_rad;                      /* 0.01 */
+    double mu_factor;                     /* 1.4 */
+    int32_t max_rounds;                   /* 64 */
+    int32_t min_inlier_tags;              /* 1 */
+} ck_rig_robust_params_t;
+typedef struct ck_rig_robust_result {
+    ck_rig_result_t fused;                /* of the inliers */
+    int32_t status;                       /* CK_RIG_ROBUST_* */
+    int32_t rounds;                       /* GNC solves that ran */
+    int32_t n_rejected;
+    int32_t pad;
+    uint64_t rejected[CK_RIG_MAX_CAMS];   /* bit t: tag t of camera c's record at this step was dropped */
+    double worst_inlier_rad;              /* sqrt(rho) of the worst kept tag at the returned pose (polar(R), t), before the yaw pivot;
+                                             0 without a pose */
+    double best_rejected_rad;             /* sqrt(rho) of the best dropped tag there; 0 when none */
+} ck_rig_robust_result_t;
+void ck_rig_robust_params_default(ck_rig_robust_params_t *p);
+/* The twins of ck_rig_solve_host / ck_rig_solve_batch / ck_rig_process_last: same arguments (params->rig is theirs), same errors,
+ * and CK_EINVAL for gate_rad not finite or <= 0, mu_factor <= 1 (or not finite), max_rounds < 1, min_inlier_tags < 1 and, in the two
+ * stand-alone calls, a record of more than CK_RIG_ROBUST_MAX_TAGS tags.  A step without a pose has an all-zero `fused`; a step
+ * without tags (or, in ck_rig_process_last_robust, without a gyro heading) an all-zero record.  meas and valid are those of
+ * `fused`; tag_count still counts all detections. */
+int ck_rig_solve_robust_host(const ck_rig_robust_params_t *params, int32_t n_cams, const ck_sqpnp_problem_t *problems, int32_t n,
+                             const ck_iso3_t *tags, int32_t n_tags_total, const double *bearings, int32_t n_bearings_total,
+                             const double *gyro, ck_rig_robust_result_t *out);
+int ck_rig_solve_robust_batch(ck_handle_t *h, const ck_rig_robust_params_t *params, int32_t n_cams, const ck_sqpnp_problem_t *problems,
+                              int32_t n, const ck_iso3_t *tags, int32_t n_tags_total, const double *bearings, int32_t n_bearings_total,
+                              const double *gyro, ck_rig_robust_result_t *out);
+int ck_rig_process_last_robust(ck_handle_t *const *handles, int32_t n_cams, int32_t n, const ck_rig_robust_params_t *params,
+                               const double *gyro, const uint8_t *has_gyro, ck_rig_robust_result_t *out, ck_vision_measurement_t *meas,
+                               int32_t *valid);
+
 /* ---- camera mounts: the robot_to_cam of a rig's cameras from a capture, batched Levenberg-Marquardt ------
  * The capture is what ck_rig_solve_batch takes: n_steps instants of n_cams cameras, camera c's record of step s at
  * records[c * n_steps + s] (n_tags, n_bearings = 4 * n_tags and the offsets are read; the records' own robot_to_cam is ignored), and
