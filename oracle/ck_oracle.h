@@ -35,6 +35,11 @@ int ora_clusters(const uint8_t *thresh, const uint32_t *labels, const uint32_t *
 int ora_fit_quads(const uint8_t *quad_img, int qw, int qh, int qstride, const uint8_t *orig_img, int w, int h,
                   int stride, const ck_config_t *cfg, const ck_cluster_t *clusters, int n_clusters,
                   const ck_cluster_point_t *points, ck_quad_t *quads, int quad_cap, int *n_quads);
+/* test readouts of the fit: where clusters have left it since the last reset (16 counters, 14 = quad), and the last cluster's exit,
+   points before / after duplicate removal, ksz, maxima found / kept, 4-subsets tied for the best energy, reversed (-1 = not reached;
+   per thread) */
+void ora_fit_stats(long *out, int reset);
+void ora_fit_last(int out[8]);
 int ora_decode_quads(const uint8_t *img, int w, int h, int stride, const ck_config_t *cfg,
                      const ck_quad_t *quads, int n_quads, ck_detection_t *dets, int det_cap, int *n_dets);
 /* whole pipeline on one frame; returns CK_OK and a status word like the product */

@@ -284,10 +284,17 @@ static int dbl_desc(const void *a, const void *b) {
 /* debug statistics: where clusters leave fit_quad (read through ora_fit_stats) */
 static long g_fit_stats[16];
 void ora_fit_stats(long *out, int reset) { for (int i = 0; i < 16; i++) { out[i] = g_fit_stats[i]; if (reset) g_fit_stats[i] = 0; } }
-#define FIT_STAT(k) (g_fit_stats[k]++)
+/* the same per cluster: exit number (the FIT_STAT index, 14 = quad), points before / after duplicate removal, ksz, maxima found,
+   maxima kept after the cut, 4-subsets whose energy equals the best one's bit for bit (the winner included), reversed; -1 = not
+   reached.  Thread-local: the threaded CPU baseline runs fit_quad too. */
+static _Thread_local int g_fit_last[8];
+void ora_fit_last(int out[8]) { for (int i = 0; i < 8; i++) out[i] = g_fit_last[i]; }
+#define FIT_STAT(k) (g_fit_stats[k]++, (void)((k) > 0 && (g_fit_last[0] = (k))))
 
 static int fit_quad(const fitctx_t *c, const ck_cluster_point_t *pts, int sz0, ck_quad_t *quad) {
     FIT_STAT(0);
+    for (int i = 0; i < 8; i++) g_fit_last[i] = -1;
+    g_fit_last[1] = sz0;
     if (sz0 < c->cfg->min_cluster_pixels || sz0 < 24) { FIT_STAT(1); return 0; }
     if (sz0 > c->max_cluster_points) { FIT_STAT(2); return 0; }
     int xmin = pts[0].x, xmax = pts[0].x, ymin = pts[0].y, ymax = pts[0].y;
@@ -304,6 +311,7 @@ static int fit_quad(const fitctx_t *c, const ck_cluster_point_t *pts, int sz0, c
         dot += dx * pts[i].gx + dy * pts[i].gy;
     }
     int reversed = dot < 0;
+    g_fit_last[7] = reversed;
     if (reversed && !c->reversed_ok) { FIT_STAT(4); return 0; }
     if (!reversed && !c->normal_ok) { FIT_STAT(4); return 0; }
     /* sort by angle, drop duplicate coordinates */
@@ -313,6 +321,7 @@ static int fit_quad(const fitctx_t *c, const ck_cluster_point_t *pts, int sz0, c
     int sz = 0;
     for (int i = 0; i < sz0; i++)
         if (i == 0 || keys[i] != keys[i - 1]) keys[sz++] = keys[i];
+    g_fit_last[2] = sz;
     int ok = 0;
     lfps_t *lf = NULL; double *errs = NULL, *sm = NULL; int *maxima = NULL; double *maxima_errs = NULL;
     if (sz < 24) { FIT_STAT(5); goto done; }
@@ -337,6 +346,7 @@ static int fit_quad(const fitctx_t *c, const ck_cluster_point_t *pts, int sz0, c
     }
     /* corner candidates: local maxima of the smoothed line-fit error */
     int ksz = sz / 12 < 20 ? sz / 12 : 20;
+    g_fit_last[3] = ksz;
     if (ksz < 2) { FIT_STAT(5); goto done; }
     errs = (double *)malloc((size_t)sz * sizeof(double));
     sm = (double *)malloc((size_t)sz * sizeof(double));
@@ -351,6 +361,7 @@ static int fit_quad(const fitctx_t *c, const ck_cluster_point_t *pts, int sz0, c
     int nmax = 0;
     for (int i = 0; i < sz; i++)
         if (sm[i] > sm[(i + 1) % sz] && sm[i] > sm[(i + sz - 1) % sz]) { maxima[nmax] = i; maxima_errs[nmax] = sm[i]; nmax++; }
+    g_fit_last[4] = nmax;
     if (nmax < 4) { FIT_STAT(6); goto done; }
     int max_nmaxima = c->cfg->max_nmaxima;
     if (nmax > max_nmaxima) {
@@ -366,7 +377,9 @@ static int fit_quad(const fitctx_t *c, const ck_cluster_point_t *pts, int sz0, c
         }
         nmax = out;
     }
+    g_fit_last[5] = nmax;
     /* exhaustive search over 4-subsets of the maxima */
+    int n_best = 0;   /* (readout only) */
     int best[4] = {0, 0, 0, 0};
     double best_error = HUGE_VAL;
     double max_mse = c->cfg->max_line_fit_mse, max_dot = c->cfg->cos_critical_rad;
@@ -392,11 +405,13 @@ static int fit_quad(const fitctx_t *c, const ck_cluster_point_t *pts, int sz0, c
                     fit_line(lf, sz, i3, i0, NULL, &e30, &s30);
                     if (s30 > max_mse) continue;
                     double e = e01 + e12 + e23 + e30;
-                    if (e < best_error) { best_error = e; best[0] = i0; best[1] = i1; best[2] = i2; best[3] = i3; }
+                    if (e == best_error) n_best++;
+                    if (e < best_error) { best_error = e; best[0] = i0; best[1] = i1; best[2] = i2; best[3] = i3; n_best = 1; }
                 }
             }
         }
     }
+    g_fit_last[6] = n_best;
     if (best_error == HUGE_VAL) { FIT_STAT(7); goto done; }
     if (best_error / (double)sz >= max_mse) { FIT_STAT(8); goto done; }
     {

@@ -83,6 +83,32 @@ def fit_quads(img, cfg, cl_np, pt_np, quad_img=None):
     return [quads[i] for i in range(nq.value)], ov
 
 
+FIT_TRACE_FIELDS = ("exit", "points", "unique", "ksz", "nmax_found", "nmax_kept", "best_ties", "reversed")
+
+
+def fit_trace(img, cfg, cl_np, pt_np, quad_img=None):
+    """ora_fit_quads one cluster at a time: per cluster (readout, quad or None), the readout being ora_fit_last's eight numbers
+    (FIT_TRACE_FIELDS; exit 14 = quad, -1 = not reached).  The quads are the ones fit_quads returns, in cluster order."""
+    img, p = _u8(img)
+    h, w = img.shape
+    q = img if quad_img is None else np.ascontiguousarray(quad_img, np.uint8)
+    qh, qw = q.shape
+    cl = np.ascontiguousarray(cl_np, np.uint32).reshape(-1, 4)
+    pts = np.ascontiguousarray(pt_np)
+    L = lib()
+    out = []
+    for k in range(len(cl)):
+        quad = (A.Quad * 1)()
+        nq = C.c_int(0)
+        last = (C.c_int * 8)()
+        L.ora_fit_quads(C.c_void_p(q.ctypes.data), qw, qh, qw, C.c_void_p(p), w, h, w, C.byref(cfg),
+                        C.c_void_p(cl[k:k + 1].ctypes.data), 1, C.c_void_p(pts.ctypes.data), quad, 1, C.byref(nq))
+        L.ora_fit_last(last)
+        assert (last[0] == 14) == (nq.value == 1)
+        out.append((tuple(last), quad[0] if nq.value else None))
+    return out
+
+
 def quads_to_np(quads):
     out = np.zeros((len(quads), 11), np.float64)
     for i, q in enumerate(quads):

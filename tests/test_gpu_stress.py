@@ -41,6 +41,22 @@ def test_stress_clusters(oracle):
     assert stress_clusters.run(30, 115) == 0
 
 
+def test_stress_quads(oracle):
+    """the quads themselves, byte for byte (through detections a wrong quad shows only where its cluster decodes)"""
+    import stress_quads
+    assert stress_quads.run(30, 116) == 0
+
+
+def test_stress_quads_split_fit(oracle):
+    """the same kind of cases through k_seq -> k_chunk -> k_tail (CK_FIT_FLAT=2 on the diagnostics build, read once per process: a child)"""
+    import os, subprocess, sys
+    from conftest import diag_env
+    here = os.path.dirname(os.path.abspath(__file__))
+    r = subprocess.run(["timeout", "-k", "10", "240", sys.executable, os.path.join(here, "stress_quads.py"), "30", "117"], env=diag_env(CK_FIT_FLAT="2"),
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and '"mismatching_frames": 0' in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+
+
 def test_stress_pose(oracle):
     import stress_pose
     assert stress_pose.run(25, 103) == 0
