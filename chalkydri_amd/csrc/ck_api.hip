@@ -144,6 +144,9 @@ extern "C" int ck_create(const ck_config_t *cfg, ck_handle_t **out) {
     int qw = cfg->width / cfg->quad_decimate, qh = cfg->height / cfg->quad_decimate;
     if (qw < 8 || qh < 8) return CK_EINVAL;
     if (cfg->min_component_px < 1 || cfg->min_component_px > 0x3FFFFFFF) return CK_EINVAL;
+    // k_finalize ranks a frame's decode candidates (one per quad and family) in dynamic LDS, 4 bytes each, and raises no limit for
+    // it: 64 KiB is what a launch is given without hipFuncSetAttribute (CK_MAX_FRAME_CANDIDATES; stage_caps holds the same bound)
+    if ((long long)(cfg->max_quads_per_frame > 0 ? cfg->max_quads_per_frame : 1024) * cfg->n_families > CK_MAX_FRAME_CANDIDATES) return CK_EINVAL;
     if (ck_device_count() <= 0) return CK_ENODEVICE;
     ck_handle *h = new (std::nothrow) ck_handle();
     if (!h) return CK_ENOMEM;
@@ -242,14 +245,14 @@ int ck_stage_device_frames(ck_handle *h, const uint8_t *d_frames, int n, int str
 }
 
 // Q of n frames into d_qframes when the quad image is a buffer of its own: decimation and / or the quad_sigma filter
-static int make_quad_image(ck_handle *h, const ck_dev_image &img, int n) {
+int ck_make_quad_image(ck_handle *h, const ck_dev_image &img, int n) {
     if (!ck_quad_separate(h)) return CK_OK;
     return h->qf_ksz > 1 ? ck_launch_prefilter(h, img, n) : ck_launch_decimate(h, img, n);
 }
 
 // Runs that (if configured) + threshold + segment on n staged frames.
 int ck_run_threshold_segment(ck_handle *h, const ck_dev_image &img, int n) {
-    int rc = make_quad_image(h, img, n);
+    int rc = ck_make_quad_image(h, img, n);
     if (rc != CK_OK) return rc;
     return ck_launch_threshold_segment(h, ck_quad_image(h, img), n);
 }
@@ -320,7 +323,7 @@ extern "C" int ck_quad_image_batch(ck_handle_t *h, const ck_image_u8_t *imgs, in
     if (rc != CK_OK) return rc;
     if (n == 0) return CK_OK;
     CK_HIP(hipSetDevice(h->device));
-    rc = make_quad_image(h, ck_staged_image(h), n);
+    rc = ck_make_quad_image(h, ck_staged_image(h), n);
     if (rc != CK_OK) return rc;
     const ck_dev_image q = ck_quad_image(h, ck_staged_image(h));
     for (int i = 0; i < n; i++)

@@ -214,7 +214,7 @@ struct ck_handle {
     int n_pose_inputs;   // frames whose glue records (ws.d_problems, d_pose_tags, d_bearings) and detection counts the last ck_process_* call
                          // left in ws (what ck_rig_process_last reads in place); -1: none yet, or a later pipeline call rewrote the workspace
     int n_last_dets;     // frames whose detections the last ck_detect_* / ck_process_* call left in ws (what ck_last_tag_poses reads);
-                         // -1: none yet, or a later call (ck_clusters_batch, ck_quads_batch, a failed pipeline) rewrote the workspace
+                         // -1: none yet, or a later call (ck_clusters_batch, ck_quads_batch, ck_decode_quads_batch, a failed pipeline) rewrote the workspace
     // per-tag pose (k_tagpose.hip): allocated by the first ck_estimate_tag_poses / ck_last_tag_poses, max_batch * det_cap entries
     ck_detection_t *d_tp_dets; // caller detections staged for ck_estimate_tag_poses
     ck_tag_pose_t *d_tp_out;   // pose records
@@ -361,6 +361,8 @@ void ck_bufs_free(ck_handle *h);
 int ck_read_staged_luma(ck_handle *h, int n, uint8_t *luma_out);
 int ck_stage_device_frames(ck_handle *h, const uint8_t *d_frames, int n, int stride, int64_t frame_pitch, ck_dev_image *use);
 int ck_run_threshold_segment(ck_handle *h, const ck_dev_image &img, int n);
+// Q of n frames into d_qframes when the quad image is a buffer of its own (decimation and / or quad_sigma); nothing otherwise
+int ck_make_quad_image(ck_handle *h, const ck_dev_image &img, int n);
 // gradient clusters from thresh/labels/csize of frames [0,n)
 int ck_launch_clusters(ck_handle *h, int n);
 // quad fit (+ edge refinement) of every cluster; qframes = image the clusters came from, frames = full resolution

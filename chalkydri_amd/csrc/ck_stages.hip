@@ -126,7 +126,8 @@ static int stage_caps(ck_handle *h) {
     if (ws.cluster_cap > (1 << 19)) ws.cluster_cap = 1 << 19; // keeps the hash table (2x) at most 2^20 slots per frame
     ws.quad_cap = cfg.max_quads_per_frame > 0 ? cfg.max_quads_per_frame : 1024;
     // k_finalize ranks a frame's decode candidates (quad_cap per family) in LDS, 4 bytes each: refuse what would not launch
-    if ((size_t)ws.quad_cap * (size_t)cfg.n_families * sizeof(int) > 64 * 1024) return CK_EINVAL;
+    // (ck_create has refused it before it looked for a device)
+    if ((size_t)ws.quad_cap * (size_t)cfg.n_families > (size_t)CK_MAX_FRAME_CANDIDATES) return CK_EINVAL;
     ws.det_cap = 256;
     ws.ht_size = next_pow2(2 * ws.cluster_cap);
     if (ws.ht_size < 1024) ws.ht_size = 1024;
@@ -390,6 +391,53 @@ extern "C" int ck_quads_batch(ck_handle_t *h, const ck_image_u8_t *imgs, int32_t
         n_quads[i] = (int32_t)nq;
     }
     return CK_OK;
+}
+
+// ck_launch_decode on the caller's quads: the frames' counters and candidate counts are written from the host (quad count set,
+// everything else zero: the status word can only carry what decode sets), the quads copied into d_quads
+extern "C" int ck_decode_quads_batch(ck_handle_t *h, const ck_image_u8_t *imgs, int32_t n, const ck_quad_t *quads, int32_t quad_stride,
+                                     const int32_t *n_quads, ck_detection_t *dets, int32_t cap, int32_t *counts, uint32_t *status) {
+    if (!h || !quads || !n_quads || !dets || !counts || cap < 1 || n < 0 || quad_stride < 0) return CK_EINVAL;
+    if (!imgs && n > h->n_staged) return CK_EINVAL;
+    if (n > h->cfg.max_batch) return imgs ? CK_ECAPACITY : CK_EINVAL;
+    ck_stage_ws &ws = h->ws;
+    for (int i = 0; i < n; i++)
+        if (n_quads[i] < 0 || n_quads[i] > quad_stride || n_quads[i] > ws.quad_cap) return CK_EINVAL;
+    if (n == 0) return CK_OK;
+    CK_HIP(hipSetDevice(h->device));
+    CK_HIP(hipEventRecord(h->ev[0], h->stream));
+    if (imgs) {
+        int rc = ck_upload_frames(h, imgs, n);
+        if (rc != CK_OK) return rc;
+    }
+    h->n_last_dets = -1;
+    h->n_pose_inputs = -1;
+    const ck_dev_image staged = ck_staged_image(h);
+    CK_HIP(hipEventRecord(h->ev[1], h->stream));
+    if (ck_refine_reads_quad(h)) { // decode reads the filtered frame: make it
+        int rc = ck_make_quad_image(h, staged, n);
+        if (rc != CK_OK) return rc;
+    }
+    for (int e = 2; e <= 4; e++) CK_HIP(hipEventRecord(h->ev[e], h->stream));
+    // the copies below read the caller's quads and this vector while they are in flight: no return before the stream has drained
+    std::vector<uint32_t> counters((size_t)n * CK_CNT_STRIDE, 0u);
+    auto enqueue = [&]() -> int {
+        for (int i = 0; i < n; i++) {
+            counters[(size_t)i * CK_CNT_STRIDE + CK_CNT_QUADS] = (uint32_t)n_quads[i];
+            if (n_quads[i])
+                CK_HIP(hipMemcpyAsync(ws.d_quads + (size_t)i * ws.quad_cap, quads + (size_t)i * quad_stride, sizeof(ck_quad_t) * (size_t)n_quads[i],
+                                      hipMemcpyHostToDevice, h->stream));
+        }
+        CK_HIP(hipMemcpyAsync(ws.d_counters, counters.data(), counters.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+        CK_HIP(hipMemsetAsync(ck_fit_scratch_layout(ws, h->cfg.max_batch).cand_count, 0, sizeof(uint32_t) * (size_t)n, h->stream));
+        int rc = ck_launch_decode(h, ck_refine_image(h, staged), n);
+        if (rc != CK_OK) return rc;
+        CK_HIP(hipEventRecord(h->ev[5], h->stream));
+        return CK_OK;
+    };
+    int rc = enqueue();
+    if (rc != CK_OK) { (void)hipStreamSynchronize(h->stream); return rc; }
+    return fetch_detections(h, n, dets, cap, counts, status);
 }
 
 static int process_common(ck_handle *h, const ck_dev_image &img, int n, const ck_process_params_t *pp, const double *gyro,

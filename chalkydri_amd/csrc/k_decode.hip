@@ -62,11 +62,13 @@ __device__ __forceinline__ void hproject(const double *H, double x, double y, do
 }
 __device__ __forceinline__ double value_for_pixel(const uint8_t *im, int w, int h, int stride, double px, double py) {
     double fx = px - 0.5, fy = py - 0.5;
+    // inside the image is decided on the doubles, as the oracle does (floor(fx) >= 0 and ceil(fx) <= w - 1, the same for y): a
+    // non-finite or huge coordinate is never converted to int — the host and the device convert those differently
+    if (!(fx >= 0 && fx <= (double)(w - 1) && fy >= 0 && fy <= (double)(h - 1))) return -1.0;
     int x1 = (int)floor(fx), x2 = (int)ceil(fx);
     double x = fx - (double)x1;
     int y1 = (int)floor(fy), y2 = (int)ceil(fy);
     double y = fy - (double)y1;
-    if (x1 < 0 || x2 >= w || y1 < 0 || y2 >= h) return -1.0;
     return (double)im[(size_t)y1 * stride + x1] * (1.0 - x) * (1.0 - y) + (double)im[(size_t)y1 * stride + x2] * x * (1.0 - y) +
            (double)im[(size_t)y2 * stride + x1] * (1.0 - x) * y + (double)im[(size_t)y2 * stride + x2] * x * y;
 }
@@ -128,9 +130,8 @@ __global__ __launch_bounds__(64) void k_decode(DecodeArgs a) {
                 double tagx = 2.0 * (tagx01 - 0.5), tagy = 2.0 * (tagy01 - 0.5);
                 double px, py;
                 hproject(sH, tagx, tagy, &px, &py);
-                int ix = (int)px, iy = (int)py;
-                double gray = -1.0; // outside the image: the sample is skipped
-                if (!(px < 0 || py < 0 || ix < 0 || iy < 0 || ix >= w || iy >= h)) gray = (double)im[(size_t)iy * stride + ix];
+                double gray = -1.0; // outside the image (decided on the doubles, before any conversion): the sample is skipped
+                if (px >= 0 && py >= 0 && px < (double)w && py < (double)h) gray = (double)im[(size_t)(int)py * stride + (int)px];
                 sSamp[j][0] = tagx; sSamp[j][1] = tagy; sSamp[j][2] = gray;
             }
             __syncthreads();
@@ -258,6 +259,12 @@ __global__ __launch_bounds__(64) void k_decode(DecodeArgs a) {
             hproject(Hr, 0, 0, &d.c[0], &d.c[1]);
             const double tc[4][2] = {{-1, 1}, {1, 1}, {1, -1}, {-1, -1}};
             for (int i = 0; i < 4; i++) hproject(Hr, tc[i][0], tc[i][1], &d.p[i][0], &d.p[i][1]);
+            // A centre or corner that is not finite (zz == 0 at a tag corner: a quad with three collinear corners) is no detection, as
+            // in the oracle: det_cmp is a total order only on numbers — with a NaN it answers 1 both ways, two such candidates would
+            // take the same rank in k_finalize and leave an entry of sOrder unwritten.  (v - v is 0 exactly for finite v.)
+            bool finite = d.c[0] - d.c[0] == 0.0 && d.c[1] - d.c[1] == 0.0;
+            for (int i = 0; i < 4; i++) finite = finite && d.p[i][0] - d.p[i][0] == 0.0 && d.p[i][1] - d.p[i][1] == 0.0;
+            if (!finite) continue;
             uint32_t pos = atomicAdd(&a.cand_count[frame], 1u);
             if (pos < (uint32_t)a.cand_cap) a.cands[(size_t)frame * a.cand_cap + pos] = d;
         }

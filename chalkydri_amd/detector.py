@@ -34,6 +34,7 @@ def _bind(L):
     L.ck_detect_batch_device.argtypes = [vp, vp, i32, i32, C.c_int64, _P(A.Detection), i32, _P(i32), u32p]
     L.ck_clusters_batch.argtypes = [vp, _P(A.ImageU8), i32, vp, i32, _P(i32), vp, i32, _P(i32)]
     L.ck_quads_batch.argtypes = [vp, _P(A.ImageU8), i32, _P(A.Quad), i32, _P(i32)]
+    L.ck_decode_quads_batch.argtypes = [vp, _P(A.ImageU8), i32, _P(A.Quad), i32, _P(i32), _P(A.Detection), i32, _P(i32), u32p]
     L.ck_last_stage_ms.argtypes = [vp, _P(A.StageMs)]
     L.ck_selftest_fp64.argtypes = [vp, i32, vp, vp, i32, vp]
     L.ck_cat_calc_otsu.argtypes = [vp, vp, i32, i32, vp]
@@ -517,6 +518,32 @@ class AprilTagDetector:
         nq = (C.c_int32 * n)()
         check(self._L.ck_quads_batch(self._h, arr, n, q, cap, nq), "ck_quads_batch")
         return [[q[i * cap + k] for k in range(nq[i])] for i in range(n)]
+
+    def decode_quads(self, quads, frames=None, cap=64, return_status=False, raw=False):
+        """The decode stage alone (ck_decode_quads_batch): quads is one list of ck_quad_t (_abi.Quad) per frame; frames None runs on
+        the staged frames.  Returns what detect_batch returns; raw=True gives each frame's ck_detection_t records as bytes."""
+        n = len(quads)
+        arr = None if frames is None else _images(frames)
+        if arr is not None and len(arr[0]) != n:
+            raise ValueError("one list of quads per frame")
+        stride = max([len(q) for q in quads] + [1])
+        qa = (A.Quad * (max(n, 1) * stride))()
+        nq = (C.c_int32 * max(n, 1))()
+        for i, ql in enumerate(quads):
+            nq[i] = len(ql)
+            for k, q in enumerate(ql):
+                qa[i * stride + k] = q
+        dets = (A.Detection * (max(n, 1) * cap))()
+        counts = (C.c_int32 * max(n, 1))()
+        status = (C.c_uint32 * max(n, 1))()
+        check(self._L.ck_decode_quads_batch(self._h, None if arr is None else arr[0], n, qa, stride, nq, dets, cap, counts, status),
+              "ck_decode_quads_batch")
+        if raw:
+            sz = C.sizeof(A.Detection)
+            out = [C.string_at(C.addressof(dets) + i * cap * sz, counts[i] * sz) for i in range(n)]
+        else:
+            out = [[Detection(dets[i * cap + k]) for k in range(counts[i])] for i in range(n)]
+        return (out, list(status)[:n]) if return_status else out
 
     # -- the call the reference makes: detector.detect(&image) -----------------------------------------------
     def detect(self, frame, cap=64):

@@ -563,6 +563,31 @@ class Detector {
             for (int i = 0; i < counts[f] && i < (int)det_cap_; i++) out[f].emplace_back(dets[f * det_cap_ + i]);
         return out;
     }
+    // The decode stage alone on the caller's quads (ck_decode_quads_batch), one list per frame; `status` gets the frames' words.
+    // No images: the frames staged on the handle (imgs == NULL), one per list of quads.
+    std::vector<std::vector<Detection>> decode_quads(const std::vector<ck_image_u8_t> &imgs, const std::vector<std::vector<ck_quad_t>> &quads,
+                                                     std::vector<uint32_t> *status = nullptr) {
+        if (!imgs.empty() && imgs.size() != quads.size()) throw Panic("decode_quads: one list of quads per frame", CK_EINVAL);
+        const size_t n = quads.size();
+        size_t stride = 1;
+        for (const auto &q : quads) stride = std::max(stride, q.size());
+        std::vector<ck_quad_t> flat(stride * quads.size());
+        std::vector<int32_t> nq(quads.size()), counts(quads.size());
+        for (size_t f = 0; f < quads.size(); f++) {
+            nq[f] = (int32_t)quads[f].size();
+            std::copy(quads[f].begin(), quads[f].end(), flat.begin() + f * stride);
+        }
+        std::vector<ck_detection_t> dets(det_cap_ * n);
+        std::vector<uint32_t> st(n);
+        check(ck_decode_quads_batch(h_->get(), imgs.empty() ? nullptr : imgs.data(), (int)n, flat.data(), (int)stride, nq.data(), dets.data(), (int)det_cap_,
+                                    counts.data(), st.data()),
+              "ck_decode_quads_batch");
+        std::vector<std::vector<Detection>> out(n);
+        for (size_t f = 0; f < n; f++)
+            for (int i = 0; i < counts[f] && i < (int)det_cap_; i++) out[f].emplace_back(dets[f * det_cap_ + i]);
+        if (status) *status = st;
+        return out;
+    }
 
   private:
     void need_rgb(size_t len) const {

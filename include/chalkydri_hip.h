@@ -106,6 +106,9 @@ const ck_family_t *ck_family_builtin(const char *name);
 
 /* ---- detector configuration -------------------------------------------------------------------- */
 #define CK_MAX_FAMILIES 4
+/* max_quads_per_frame x n_families may not exceed this (ck_create: CK_EINVAL): the de-duplication ranks a frame's decode
+ * candidates, one per quad and family, in 4 bytes of workgroup memory each, and 64 KiB is what a launch gets without asking */
+#define CK_MAX_FRAME_CANDIDATES 16384
 
 typedef struct ck_config {
     int32_t width, height;        /* frame geometry, fixed per handle (cf. Detector::new(width,height,..)) */
@@ -157,7 +160,7 @@ int ck_device_count(void);       /* 0 when no HIP device is visible */
 /* Frame geometry accepted by ck_create: any width and height of 16..4095 pixels (at least 8 after quad_decimate) — what an
  * image_u8_t can describe within the 13-bit half-pixel coordinates of the boundary points; quad_decimate 1 or 2
  * (CK_EUNSUPPORTED otherwise); min_component_px >= 1; 1..CK_MAX_FAMILIES families, each valid as ck_family_t's
- * rules say.
+ * rules say; max_quads_per_frame (1024 when 0) x n_families <= CK_MAX_FRAME_CANDIDATES.
  * CK_EINVAL for everything else.  Arguments are validated before a device is looked for (CK_ENODEVICE). */
 int ck_create(const ck_config_t *cfg, ck_handle_t **out);
 void ck_destroy(ck_handle_t *h);
@@ -233,6 +236,18 @@ typedef struct ck_quad {
 /* Candidate quads after fit (+ edge refinement when enabled), sorted by (rep0,rep1). */
 int ck_quads_batch(ck_handle_t *h, const ck_image_u8_t *imgs, int32_t n, ck_quad_t *quads,
                    int32_t quad_cap, int32_t *n_quads);
+/* The decode stage alone, on the caller's quads: quads is [n][quad_stride], frame i decodes its first n_quads[i] entries
+ * (p and reversed_border are read; rep0 / rep1 are not).  It reads the image ck_detect_*'s decode reads on this handle — the
+ * frame, at either quad_decimate; the filtered frame while quad_sigma is on at quad_decimate 1 — and returns what ck_detect_*
+ * returns: dets [n][cap_per_frame], counts[n], status[n] (may be NULL) with the decode stage's bits only
+ * (CK_FRAME_DETS_OVERFLOW, CK_FRAME_UNVERIFIED_ID).  Runs on frames staged by ck_upload_frames when imgs == NULL.
+ * CK_EINVAL for null pointers, negative counts, cap_per_frame < 1, an n_quads[i] above quad_stride or above the handle's
+ * max_quads_per_frame (1024 by default), and n above what is staged; CK_ECAPACITY for more host frames than max_batch (as
+ * ck_upload_frames).  A quad that decodes but whose centre or a corner is not finite (three collinear corners put a tag corner at
+ * infinity) leaves no detection. */
+int ck_decode_quads_batch(ck_handle_t *h, const ck_image_u8_t *imgs, int32_t n, const ck_quad_t *quads,
+                          int32_t quad_stride, const int32_t *n_quads, ck_detection_t *dets,
+                          int32_t cap_per_frame, int32_t *counts, uint32_t *status);
 
 /* per-stage timings of the last ck_detect_* call, milliseconds (HIP events on the handle's stream) */
 typedef struct ck_stage_ms {
@@ -454,7 +469,7 @@ int ck_estimate_tag_poses(ck_handle_t *h, const ck_tag_pose_params_t *pp, const 
  * with n = the frames of that call; the entries of a frame past its count are zero records.  out and counts may be host or
  * device pointers.  Errors as ck_estimate_tag_poses, and CK_EINVAL for cap_per_frame < 1 or when the detection workspace
  * holds no such call's result: no detect / process call since ck_create, a failed one, or a later call that rewrote the
- * workspace: ck_clusters_batch and ck_quads_batch.  ck_upload_frames, ck_upload_raw, ck_upload_raw_device, ck_raw_luma_batch, ck_threshold_batch, ck_segment_batch,
+ * workspace: ck_clusters_batch, ck_quads_batch and ck_decode_quads_batch.  ck_upload_frames, ck_upload_raw, ck_upload_raw_device, ck_raw_luma_batch, ck_threshold_batch, ck_segment_batch,
  * ck_quad_image_batch, ck_time_threshold_segment, ck_set_quad_sigma, ck_sqpnp_solve_batch, ck_gather_poses, ck_preview_jpeg,
  * ck_preview_luma, the ck_preview_*color* calls, ck_exposure_stats, ck_exposure_stats_ingested, the ck_cat_*
  * calls (ck_cat_tri_otsu and ck_cat_tri_otsu_batch among them) and the ck_ingest_write / ck_ingest_submit calls leave it as it is. */

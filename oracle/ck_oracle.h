@@ -42,6 +42,23 @@ void ora_fit_stats(long *out, int reset);
 void ora_fit_last(int out[8]);
 int ora_decode_quads(const uint8_t *img, int w, int h, int stride, const ck_config_t *cfg,
                      const ck_quad_t *quads, int n_quads, ck_detection_t *dets, int det_cap, int *n_dets);
+/* test readout of the last ora_decode_quads call of this thread, one record per (quad, family) in that order.
+   exit: 0 homography singular, 1 border sense is not the family's, 2 sign test failed, 3 best distance above max_hamming,
+   4 margin not >= 0, 5 candidate, 6 decoded but a centre or corner coordinate is not finite (no candidate).  edges: 1 a border sample in (-1, 0), 2 in [w - 1, w) / [h - 1, h), 4 in [w, w + 1) / [h, h + 1),
+   8 a used bit sample on a pixel centre (x1 == x2 or y1 == y2), 16 a used bit sample within half a pixel of the last column / row,
+   32 a bit sample skipped within half a pixel beyond it.  model_nan: 1 white, 2 black model's constant is NaN. */
+typedef struct ora_decode_rec {
+    int32_t quad, family, exit, solved;
+    int32_t n_white, n_black;       /* border samples used */
+    int32_t n_wild, n_both_nan;     /* samples (border and bits) with a coordinate that is NaN, inf or |v| >= 2^31; NaN in both */
+    int32_t bits_outside, sign_ok, model_nan, edges;
+    int32_t best_hd, n_best, rot, id; /* best distance, (rotation, id) pairs at it, the pair chosen */
+    uint64_t code;                  /* the word read */
+    double margin;                  /* before the conversion to float */
+} ora_decode_rec_t;
+/* copies up to cap records, returns how many there are; call[4] (may be NULL): candidates, duplicates dropped, pairs of candidates
+   equal in (family, id, hamming, float margin), point_in_quad cross products that were exactly zero */
+int ora_decode_last(ora_decode_rec_t *recs, int cap, long call[4]);
 /* whole pipeline on one frame; returns CK_OK and a status word like the product */
 int ora_detect(const uint8_t *img, int w, int h, int stride, const ck_config_t *cfg, ck_detection_t *dets,
                int det_cap, int *n_dets, uint32_t *status);

@@ -645,11 +645,13 @@ static inline double gm_interp(const graymodel_t *g, double x, double y) { retur
 
 static double value_for_pixel(const uint8_t *im, int w, int h, int stride, double px, double py) {
     double fx = px - 0.5, fy = py - 0.5;
+    /* inside the image is decided on the doubles (floor(fx) >= 0 and ceil(fx) <= w - 1, the same for y): a non-finite or huge
+       coordinate is never converted to int, which C leaves undefined */
+    if (!(fx >= 0 && fx <= (double)(w - 1) && fy >= 0 && fy <= (double)(h - 1))) return -1.0;
     int x1 = (int)floor(fx), x2 = (int)ceil(fx);
     double x = fx - (double)x1;
     int y1 = (int)floor(fy), y2 = (int)ceil(fy);
     double y = fy - (double)y1;
-    if (x1 < 0 || x2 >= w || y1 < 0 || y2 >= h) return -1.0;
     return (double)im[(size_t)y1 * stride + x1] * (1.0 - x) * (1.0 - y) + (double)im[(size_t)y1 * stride + x2] * x * (1.0 - y) +
            (double)im[(size_t)y2 * stride + x1] * (1.0 - x) * y + (double)im[(size_t)y2 * stride + x2] * x * y;
 }
@@ -661,9 +663,30 @@ static uint64_t code_rotate90(uint64_t w, int nbits) {
     return w;
 }
 
-/* returns decision margin (negative = reject); fills id/hamming/rotation */
+/* test readout of the last ora_decode_quads call of this thread: one record per (quad, family) and four numbers per call */
+static _Thread_local ora_decode_rec_t *g_dec;
+static _Thread_local int g_dec_n, g_dec_cap;
+static _Thread_local long g_dec_call[4]; /* candidates, duplicates dropped, pairs equal in (family, id, hamming, float margin), zero cross products */
+int ora_decode_last(ora_decode_rec_t *recs, int cap, long call[4]) {
+    for (int i = 0; i < g_dec_n && i < cap; i++) recs[i] = g_dec[i];
+    if (call) for (int i = 0; i < 4; i++) call[i] = g_dec_call[i];
+    return g_dec_n;
+}
+static ora_decode_rec_t *dec_rec(int quad, int family) {
+    if (g_dec_n == g_dec_cap) {
+        g_dec_cap = g_dec_cap ? 2 * g_dec_cap : 256;
+        g_dec = (ora_decode_rec_t *)realloc(g_dec, (size_t)g_dec_cap * sizeof *g_dec);
+    }
+    ora_decode_rec_t *r = &g_dec[g_dec_n++];
+    memset(r, 0, sizeof *r);
+    r->quad = quad; r->family = family; r->best_hd = -1; r->rot = -1; r->id = -1; r->margin = -1.0;
+    return r;
+}
+static int dec_wild(double v) { return !(v > -2147483648.0 && v < 2147483648.0); } /* NaN, inf or beyond int */
+
+/* returns decision margin (negative = reject); fills id/hamming/rotation.  tr: the readout's record (values only, no decision) */
 static double quad_decode(const uint8_t *im, int w, int h, int stride, const ck_family_t *fam, const double *H,
-                          double sharpening, int max_hamming, int *id, int *hamming, int *rotation) {
+                          double sharpening, int max_hamming, int *id, int *hamming, int *rotation, ora_decode_rec_t *tr) {
     double wb = (double)fam->width_at_border;
     double patterns[8][5] = {
         {-0.5, 0.5, 0, 1, 1}, {0.5, 0.5, 0, 1, 0}, {wb + 0.5, 0.5, 0, 1, 1}, {wb - 0.5, 0.5, 0, 1, 0},
@@ -678,14 +701,23 @@ static double quad_decode(const uint8_t *im, int w, int h, int stride, const ck_
             double tagx = 2.0 * (tagx01 - 0.5), tagy = 2.0 * (tagy01 - 0.5);
             double px, py;
             hproject(H, tagx, tagy, &px, &py);
+            if (dec_wild(px) || dec_wild(py)) tr->n_wild++;
+            if (px != px && py != py) tr->n_both_nan++;
+            if ((px > -1 && px < 0) || (py > -1 && py < 0)) tr->edges |= 1;
+            if ((px >= w - 1 && px < w) || (py >= h - 1 && py < h)) tr->edges |= 2;
+            if ((px >= w && px < w + 1) || (py >= h && py < h + 1)) tr->edges |= 4;
+            /* inside the image, decided on the doubles before any conversion (see value_for_pixel) */
+            if (!(px >= 0 && py >= 0 && px < (double)w && py < (double)h)) continue;
             int ix = (int)px, iy = (int)py;
-            if (px < 0 || py < 0 || ix < 0 || iy < 0 || ix >= w || iy >= h) continue;
+            if (is_white) tr->n_white++; else tr->n_black++;
             int v = im[(size_t)iy * stride + ix];
             if (is_white) gm_add(&wm, tagx, tagy, (double)v); else gm_add(&bm, tagx, tagy, (double)v);
         }
     }
     gm_solve(&wm); gm_solve(&bm);
-    if (((gm_interp(&wm, 0, 0) - gm_interp(&bm, 0, 0)) < 0) != (fam->reversed_border != 0)) return -1.0;
+    tr->model_nan = (wm.C[2] != wm.C[2]) | ((bm.C[2] != bm.C[2]) << 1);
+    if (((gm_interp(&wm, 0, 0) - gm_interp(&bm, 0, 0)) < 0) != (fam->reversed_border != 0)) { tr->exit = 2; return -1.0; }
+    tr->sign_ok = 1;
     int tw = fam->total_width;
     double values[16 * 16];
     for (int i = 0; i < tw * tw; i++) values[i] = 0.0;
@@ -696,7 +728,15 @@ static double quad_decode(const uint8_t *im, int w, int h, int stride, const ck_
         double px, py;
         hproject(H, tagx, tagy, &px, &py);
         double v = value_for_pixel(im, w, h, stride, px, py);
-        if (v == -1.0) continue;
+        if (dec_wild(px) || dec_wild(py)) tr->n_wild++;
+        if (px != px && py != py) tr->n_both_nan++;
+        if (v == -1.0) {
+            tr->bits_outside++;
+            if ((px - 0.5 > w - 1 && px - 0.5 <= w - 0.5) || (py - 0.5 > h - 1 && py - 0.5 <= h - 0.5)) tr->edges |= 32;
+            continue;
+        }
+        if (px - 0.5 == floor(px - 0.5) || py - 0.5 == floor(py - 0.5)) tr->edges |= 8;
+        if (px - 0.5 > w - 1.5 || py - 0.5 > h - 1.5) tr->edges |= 16;
         double thr = (gm_interp(&bm, tagx, tagy) + gm_interp(&wm, tagx, tagy)) / 2.0;
         values[tw * (by - min_coord) + bx - min_coord] = v - thr;
     }
@@ -723,18 +763,21 @@ static double quad_decode(const uint8_t *im, int w, int h, int stride, const ck_
         else { black_score -= v; black_cnt += 1; }
     }
     /* minimum-Hamming match over rotations and ids; ties: fewer rotations first, then smaller id */
-    int best_h = 1 << 30, best_id = -1, best_rot = 0;
+    int best_h = 1 << 30, best_id = -1, best_rot = 0, n_best = 0;
     uint64_t rc = rcode;
     for (int rot = 0; rot < 4; rot++) {
         for (uint32_t k = 0; k < fam->ncodes; k++) {
             int hd = __builtin_popcountll(rc ^ fam->codes[k]);
-            if (hd < best_h) { best_h = hd; best_id = (int)k; best_rot = rot; }
+            if (hd == best_h) n_best++;
+            if (hd < best_h) { best_h = hd; best_id = (int)k; best_rot = rot; n_best = 1; }
         }
         rc = code_rotate90(rc, (int)fam->nbits);
     }
-    if (best_h > max_hamming) return -1.0;
-    *id = best_id; *hamming = best_h; *rotation = best_rot;
     double a = white_score / white_cnt, b = black_score / black_cnt;
+    tr->code = rcode; tr->best_hd = best_h; tr->n_best = n_best; tr->rot = best_rot; tr->id = best_id; tr->margin = a < b ? a : b;
+    if (best_h > max_hamming) { tr->exit = 3; return -1.0; }
+    *id = best_id; *hamming = best_h; *rotation = best_rot;
+    tr->exit = (a < b ? a : b) >= 0 ? 5 : 4;
     return a < b ? a : b;
 }
 
@@ -743,7 +786,7 @@ static int point_in_quad(const double q[4][2], double x, double y) {
     for (int i = 0; i < 4; i++) {
         int j = (i + 1) & 3;
         double cr = (q[j][0] - q[i][0]) * (y - q[i][1]) - (q[j][1] - q[i][1]) * (x - q[i][0]);
-        if (cr > 0) pos++; else if (cr < 0) neg++;
+        if (cr > 0) pos++; else if (cr < 0) neg++; else g_dec_call[3]++;
     }
     return pos == 0 || neg == 0;
 }
@@ -766,6 +809,8 @@ int ora_decode_quads(const uint8_t *im, int w, int h, int stride, const ck_confi
     int cap = n_quads * (cfg->n_families > 0 ? cfg->n_families : 1) + 1;
     ck_detection_t *all = (ck_detection_t *)malloc((size_t)cap * sizeof(ck_detection_t));
     int n = 0;
+    g_dec_n = 0;
+    memset(g_dec_call, 0, sizeof g_dec_call);
     for (int qi = 0; qi < n_quads; qi++) {
         const ck_quad_t *q = &quads[qi];
         double corr[4][4];
@@ -775,12 +820,14 @@ int ora_decode_quads(const uint8_t *im, int w, int h, int stride, const ck_confi
             corr[i][2] = q->p[i][0]; corr[i][3] = q->p[i][1];
         }
         double H[9];
-        if (!homography_compute(corr, H)) continue;
+        if (!homography_compute(corr, H)) { for (int f = 0; f < cfg->n_families; f++) dec_rec(qi, f); continue; } /* exit 0 */
         for (int f = 0; f < cfg->n_families; f++) {
             const ck_family_t *fam = cfg->families[f];
+            ora_decode_rec_t *tr = dec_rec(qi, f);
+            tr->solved = 1; tr->exit = 1;
             if ((fam->reversed_border != 0) != (q->reversed_border != 0)) continue;
             int id = -1, hd = 0, rot = 0;
-            double margin = quad_decode(im, w, h, stride, fam, H, cfg->decode_sharpening, cfg->max_hamming, &id, &hd, &rot);
+            double margin = quad_decode(im, w, h, stride, fam, H, cfg->decode_sharpening, cfg->max_hamming, &id, &hd, &rot, tr);
             if (!(margin >= 0) || id < 0) continue;
             ck_detection_t d;
             memset(&d, 0, sizeof d);
@@ -797,10 +844,18 @@ int ora_decode_quads(const uint8_t *im, int w, int h, int stride, const ck_confi
             hproject(Hr, 0, 0, &d.c[0], &d.c[1]);
             static const double tc[4][2] = {{-1, 1}, {1, 1}, {1, -1}, {-1, -1}};
             for (int i = 0; i < 4; i++) hproject(Hr, tc[i][0], tc[i][1], &d.p[i][0], &d.p[i][1]);
+            /* a centre or corner that is not finite is no detection: det_cmp orders numbers only (v - v is 0 exactly for finite v) */
+            int finite = d.c[0] - d.c[0] == 0.0 && d.c[1] - d.c[1] == 0.0;
+            for (int i = 0; i < 4; i++) finite = finite && d.p[i][0] - d.p[i][0] == 0.0 && d.p[i][1] - d.p[i][1] == 0.0;
+            if (!finite) { tr->exit = 6; continue; }
             all[n++] = d;
         }
     }
     qsort(all, (size_t)n, sizeof(ck_detection_t), det_cmp);
+    g_dec_call[0] = n;
+    for (int i = 0; i + 1 < n; i++) /* (sorted: equal candidates are neighbours, a run of m makes m (m - 1) / 2 pairs) */
+        for (int j = i + 1; j < n && all[j].family == all[i].family && all[j].id == all[i].id && all[j].hamming == all[i].hamming &&
+                                all[j].decision_margin == all[i].decision_margin; j++) g_dec_call[2]++;
     int out = 0, overflow = 0;
     for (int i = 0; i < n; i++) {
         int dup = 0;
@@ -809,7 +864,7 @@ int ora_decode_quads(const uint8_t *im, int w, int h, int stride, const ck_confi
             if (k->family != all[i].family || k->id != all[i].id) continue;
             if (point_in_quad(k->p, all[i].c[0], all[i].c[1]) || point_in_quad(all[i].p, k->c[0], k->c[1])) dup = 1;
         }
-        if (dup) continue;
+        if (dup) { g_dec_call[1]++; continue; }
         if (out >= det_cap) { overflow = 1; break; }
         dets[out++] = all[i];
     }

@@ -154,6 +154,33 @@ def decode_quads(img, cfg, quad_list, cap=256):
     return dets_to_list(dets, n.value)
 
 
+DECODE_REC = np.dtype([("quad", "<i4"), ("family", "<i4"), ("exit", "<i4"), ("solved", "<i4"), ("n_white", "<i4"), ("n_black", "<i4"),
+                       ("n_wild", "<i4"), ("n_both_nan", "<i4"), ("bits_outside", "<i4"), ("sign_ok", "<i4"), ("model_nan", "<i4"),
+                       ("edges", "<i4"), ("best_hd", "<i4"), ("n_best", "<i4"), ("rot", "<i4"), ("id", "<i4"), ("code", "<u8"),
+                       ("margin", "<f8")])     # ora_decode_rec_t (ck_oracle.h)
+DECODE_EXITS = ("singular", "border_sense", "sign", "hamming", "margin", "candidate", "nonfinite")
+DECODE_CALL = ("candidates", "duplicates", "equal_pairs", "zero_cross")
+
+
+def decode_trace(img, cfg, quad_list, cap=256):
+    """ora_decode_quads on the given quads, with ora_decode_last's readout: (detections, raw ck_detection_t bytes of them, records
+    [quads x families] of DECODE_REC, {DECODE_CALL: count}, overflow).  The detections are the ones decode_quads returns."""
+    img, p = _u8(img)
+    h, w = img.shape
+    arr = (A.Quad * max(len(quad_list), 1))(*quad_list)
+    dets = (A.Detection * cap)()
+    n = C.c_int(0)
+    L = lib()
+    ov = L.ora_decode_quads(C.c_void_p(p), w, h, w, C.byref(cfg), arr, len(quad_list), dets, cap, C.byref(n))
+    recs = np.zeros(max(len(quad_list) * cfg.n_families, 1), DECODE_REC)
+    call = (C.c_long * 4)()
+    L.ora_decode_last.restype = C.c_int
+    nr = L.ora_decode_last(C.c_void_p(recs.ctypes.data), len(recs), call)
+    assert nr == len(quad_list) * cfg.n_families
+    raw = C.string_at(C.addressof(dets), n.value * C.sizeof(A.Detection))
+    return dets_to_list(dets, n.value), raw, recs[:nr], dict(zip(DECODE_CALL, [int(v) for v in call])), int(ov)
+
+
 def dets_to_list(dets, n):
     out = []
     for i in range(n):

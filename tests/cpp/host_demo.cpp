@@ -175,8 +175,26 @@ int main(int argc, char **argv) {
                 hex(d.raw().c, 16); std::printf(" ");
                 hex(d.raw().p, 64); std::printf("\n");
             }
-            AprilTags task(c);
             ck_image_u8_t img{frame.data(), (int32_t)w, (int32_t)h, (int32_t)w};
+            {   // the decode stage alone on the detections' own corners, from the host frame and on the staged one: the same tags
+                std::vector<ck_quad_t> quads;
+                std::vector<size_t> ids;
+                for (const Detection &d : det.detect(frame.data(), w)) {
+                    ck_quad_t q{};
+                    for (int i = 0; i < 4; i++) { q.p[i][0] = d.raw().p[3 - i][0]; q.p[i][1] = d.raw().p[3 - i][1]; }
+                    quads.push_back(q);
+                    ids.push_back(d.id());
+                }
+                std::vector<uint32_t> st;
+                auto host = det.decode_quads({img}, {quads}, &st);
+                auto staged = det.decode_quads({}, {quads});
+                if (host.size() != 1 || staged.size() != 1 || host[0].size() != ids.size() || staged[0].size() != ids.size() || st.size() != 1)
+                    throw Panic("decode_quads: count differs from detect");
+                for (size_t i = 0; i < ids.size(); i++)
+                    if (host[0][i].id() != ids[i] || std::memcmp(&host[0][i].raw(), &staged[0][i].raw(), sizeof(ck_detection_t)) != 0)
+                        throw Panic("decode_quads: detections differ");
+            }
+            AprilTags task(c);
             auto r = task.process(img, gyro);
             std::printf("measurement %d ", r.second ? 1 : 0);
             hex(&r.first, sizeof r.first);

@@ -105,6 +105,31 @@ def test_create_validates_before_touching_a_device(built):
         L.ck_destroy(h)
 
 
+def test_create_refuses_more_candidates_than_finalize_can_rank(built):
+    """max_quads_per_frame x n_families is bounded by CK_MAX_FRAME_CANDIDATES (k_finalize's rank array in workgroup memory, 64 KiB
+    without a raised limit): one more is CK_EINVAL before any device is looked for, the bound itself is accepted."""
+    from chalkydri_amd.detector import _bind
+    L = _bind(_lib.lib())
+    h = C.c_void_p()
+    src = open(os.path.join(ROOT, "include", "chalkydri_hip.h")).read()
+    bound = int(re.search(r"#define\s+CK_MAX_FRAME_CANDIDATES\s+(\d+)", src).group(1))
+    assert bound * 4 == 64 * 1024
+    t36 = _lib.family("tag36h11")
+
+    def rc(quads, nfam):
+        cfg = default_config(64, 48, families=(t36,) * nfam, max_quads_per_frame=quads)
+        r = L.ck_create(C.byref(cfg), C.byref(h))
+        if h.value:
+            L.ck_destroy(h)
+            h.value = None
+        return r
+    for nfam in (1, 2, 4):
+        assert rc(bound // nfam + 1, nfam) == A.CK_EINVAL, nfam
+        assert rc(bound // nfam, nfam) in (A.CK_OK, A.CK_ENODEVICE), nfam
+    assert rc(0x7FFFFFFF, 4) == A.CK_EINVAL                     # (the product does not wrap)
+    assert rc(0, 4) in (A.CK_OK, A.CK_ENODEVICE)                # the default of 1024 quads with every family slot used
+
+
 def test_create_refuses_bad_families(built):
     """ck_create checks what k_decode relies on for memory safety (ck_family_t's rules in chalkydri_hip.h): each bad table is
     CK_EINVAL before any device is looked for; the good table it was made from is accepted."""

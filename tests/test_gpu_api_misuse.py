@@ -181,3 +181,50 @@ def test_cat_and_solver_entry_points_reject_bad_arguments(built):
     # and the handle still classifies a frame
     assert L.ck_cat_calc_otsu(hd, R, w, h, K) == 0 and set(np.unique(cls)) <= {0, 1, 2}
     det.close()
+
+
+def test_decode_quads_entry_point_rejects_bad_arguments(built):
+    """ck_decode_quads_batch: null pointers, negative counts, a count above quad_stride or above the handle's quad capacity, more
+    frames than are staged or than the handle holds; then the same call with good arguments works."""
+    from chalkydri_amd.detector import AprilTagDetector
+    w, h, n, qcap = 160, 120, 2, 8
+    det = AprilTagDetector(w, h, max_batch=n, max_quads_per_frame=qcap)
+    L, hd = det._L, det._h
+    frames, _ = synth.render_batch(73, n, w, h, 1, min_side=40, max_side=60)
+    imgs = (A.ImageU8 * 4)()
+    for i in range(4):
+        imgs[i].buf, imgs[i].width, imgs[i].height, imgs[i].stride = frames[i % n].ctypes.data, w, h, w
+    stride, cap = 16, 8
+    quads = (A.Quad * (4 * stride))()
+    for q in quads:
+        for k, (x, y) in enumerate(((20, 20), (60, 20), (60, 60), (20, 60))):
+            q.p[k][0], q.p[k][1] = x, y
+    nq = (C.c_int32 * 4)(1, qcap, 0, 0)
+    dets = (A.Detection * (cap * 4))(); counts = (C.c_int32 * 4)(); status = (C.c_uint32 * 4)()
+    call = L.ck_decode_quads_batch
+    bad = []
+    def expect_einval(rc, what):
+        if rc != A.CK_EINVAL:
+            bad.append((what, rc))
+    expect_einval(call(None, imgs, n, quads, stride, nq, dets, cap, counts, status), "null handle")
+    expect_einval(call(hd, imgs, n, None, stride, nq, dets, cap, counts, status), "null quads")
+    expect_einval(call(hd, imgs, n, quads, stride, None, dets, cap, counts, status), "null quad counts")
+    expect_einval(call(hd, imgs, n, quads, stride, nq, None, cap, counts, status), "null detections")
+    expect_einval(call(hd, imgs, n, quads, stride, nq, dets, cap, None, status), "null counts")
+    expect_einval(call(hd, imgs, -1, quads, stride, nq, dets, cap, counts, status), "n < 0")
+    expect_einval(call(hd, imgs, n, quads, -1, nq, dets, cap, counts, status), "quad_stride < 0")
+    expect_einval(call(hd, imgs, n, quads, stride, nq, dets, 0, counts, status), "cap < 1")
+    expect_einval(call(hd, imgs, n, quads, stride, (C.c_int32 * 4)(1, -1, 0, 0), dets, cap, counts, status), "a negative quad count")
+    expect_einval(call(hd, imgs, n, quads, stride, (C.c_int32 * 4)(1, qcap + 1, 0, 0), dets, cap, counts, status), "a count above quad_cap")
+    expect_einval(call(hd, imgs, n, quads, 4, (C.c_int32 * 4)(1, 5, 0, 0), dets, cap, counts, status), "a count above quad_stride")
+    expect_einval(call(hd, None, n, quads, stride, nq, dets, cap, counts, status), "nothing staged yet")
+    if call(hd, imgs, n + 1, quads, stride, nq, dets, cap, counts, status) == 0:
+        bad.append(("n > max_batch", 0))
+    det.upload(frames[:1])
+    expect_einval(call(hd, None, n, quads, stride, nq, dets, cap, counts, status), "n above what is staged")
+    assert not bad, f"not refused with CK_EINVAL: {bad}"
+    assert call(hd, imgs, 0, quads, stride, nq, dets, cap, counts, status) == 0      # n = 0 does nothing
+    assert call(hd, None, 1, quads, stride, nq, dets, cap, counts, None) == 0        # status may be NULL
+    assert call(hd, imgs, n, quads, stride, nq, dets, cap, counts, status) == 0 and all(0 <= counts[i] <= cap for i in range(n))
+    assert len(det.detect_batch(frames)) == n                                        # the handle still works
+    det.close()

@@ -47,6 +47,21 @@ def test_stress_quads(oracle):
     assert stress_quads.run(30, 116) == 0
 
 
+def test_stress_decode(oracle):
+    """the decode stage on the caller's quads (ck_decode_quads_batch): families, overhang, flips, sharpening, max_hamming, quad counts, batch"""
+    import stress_decode
+    assert stress_decode.run(30, 118) == 0
+
+
+def test_stress_decode_poisoned(oracle):
+    """the same kind of cases in a child whose handles' buffers start as 0xA5 bytes"""
+    import os, subprocess, sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    r = subprocess.run(["timeout", "-k", "10", "240", sys.executable, os.path.join(here, "stress_decode.py"), "30", "119"], env=dict(os.environ, CK_POISON="1"),
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and '"mismatching_cases": 0' in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+
+
 def test_stress_quads_split_fit(oracle):
     """the same kind of cases through k_seq -> k_chunk -> k_tail (CK_FIT_FLAT=2 on the diagnostics build, read once per process: a child)"""
     import os, subprocess, sys
