@@ -74,24 +74,7 @@ constexpr int CK_SEG_CHUNKS_MAX = 8;           // pieces a batch's threshold + s
 constexpr int CK_FIT_SIDE_STREAMS = 2;         // ... on the handle's stream and this many more (a process has few hardware queues)
 constexpr int CK_LSCRATCH_PER_WG = 16384, CK_LSCRATCH_WGS = 1024; // large class: points per cluster, workgroups in its grid (at most)
 
-// A boundary point inside the pipeline, packed into 32 bits: [x:13][y:13][direction:2][sign:1] at bits 28..16, 15..3, 2..1, 0.
-// x/y are half-pixel coordinates, direction = which of the four forward neighbours (1,0),(0,1),(-1,1),(1,1) the pair
-// spans, sign = 1 when the gradient points along it.  k_emit writes the points of one (tile, cluster) run next to each
-// other; k_scatter moves whole runs to their place inside the cluster; k_fit unpacks.
-typedef uint32_t ck_packed_point;
-__host__ __device__ inline ck_cluster_point_t ck_unpack_point(ck_packed_point v) {
-    const int k = (int)(v >> 1) & 3, sgn = (v & 1u) ? 1 : -1;
-    const int dx = k == 2 ? -1 : (k == 1 ? 0 : 1), dy = k == 0 ? 0 : 1;
-    ck_cluster_point_t p;
-    p.x = (uint16_t)((v >> 16) & 0x1FFFu); p.y = (uint16_t)((v >> 3) & 0x1FFFu);
-    p.gx = (int8_t)(dx * sgn); p.gy = (int8_t)(dy * sgn); p.pad = 0;
-    return p;
-}
-// The same fields in one word, the staged form the quad fit's sort reads: x | y << 16 | (u8)gx << 32 | (u8)gy << 40
-__host__ __device__ __forceinline__ unsigned long long ck_stage_point(ck_packed_point v) {
-    const ck_cluster_point_t p = ck_unpack_point(v);
-    return (unsigned long long)p.x | ((unsigned long long)p.y << 16) | ((unsigned long long)(uint8_t)p.gx << 32) | ((unsigned long long)(uint8_t)p.gy << 40);
-}
+#include "ck_point.h" // ck_packed_point: a boundary point inside the pipeline, 32 bits
 // One (tile, cluster) run of boundary points in the temp array
 struct ck_run {
     uint32_t slot;      // hash-table slot of the cluster
@@ -106,7 +89,7 @@ struct ck_stage_ws {
     int point_cap, cluster_cap, quad_cap, det_cap;
     int max_cluster_points;
     unsigned long long *d_ht_keys; // [n][ht_size]  (rep0<<32 | rep1), 0 = empty
-    uint32_t *d_ht_count;      // [n][ht_size]
+    unsigned long long *d_ht_count; // [n][ht_size] points of the cluster: logical count << 32 | physical count (one add carries both)
     uint32_t *d_ht_off;        // [n][ht_size] start of the cluster in d_points (k_scatter advances it as it fills), or 0xFFFFFFFF
     ck_packed_point *d_tmp;    // [n][ext_cap] (point_cap used) points in emission order (runs)
     ck_packed_point *d_points; // [n][ext_cap] (point_cap used) points grouped by cluster
@@ -145,7 +128,7 @@ struct ck_stage_ws {
     int32_t *d_valid;
 };
 #define CK_CNT_TMP 0
-#define CK_CNT_CLUSTERS 1
+#define CK_CNT_CLUSTERS 1 /* written by k_scan; until then k_emit2's running count of emitted points, twins counted twice */
 #define CK_CNT_POINTS 2
 #define CK_CNT_QUADS 3
 #define CK_CNT_DETS 4

@@ -44,7 +44,7 @@ static constexpr ck_buf_desc ck_bufs[] = {
     CK_BUF(d_tile_count, CK_BUF_FRAME, (size_t)h->tiles_x * h->tiles_y * sizeof(uint32_t)),
     CK_BUF(d_ring, CK_BUF_FRAME, h->ring_len * sizeof(uint16_t)),
     CK_BUF(ws.d_ht_keys, CK_BUF_FRAME, w.ht_size * sizeof(unsigned long long)),
-    CK_BUF(ws.d_ht_count, CK_BUF_FRAME, w.ht_size * sizeof(uint32_t)),
+    CK_BUF(ws.d_ht_count, CK_BUF_FRAME, w.ht_size * sizeof(unsigned long long)),
     CK_BUF(ws.d_ht_off, CK_BUF_FRAME, w.ht_size * sizeof(uint32_t)),
     CK_BUF(ws.d_tmp, CK_BUF_FRAME, w.ext_cap * sizeof(ck_packed_point)),
     CK_BUF(ws.d_ext_xy, CK_BUF_FRAME | CK_BUF_ALIAS, w.ext_cap * sizeof(uint32_t)),
@@ -365,13 +365,31 @@ extern "C" int ck_clusters_batch(ck_handle_t *h, const ck_image_u8_t *imgs, int3
     if (rc != CK_OK) return rc;
     ck_stage_ws &ws = h->ws;
     for (int i = 0; i < n; i++) {
+        // On the device a twin point is one word and the records count words (ck_internal.h); the caller gets every point on its own:
+        // a twin becomes its two points, and start / count / n_points are the logical ones, the records tiling the point array
+        // in their own order as they do on the device.
         uint32_t nc = counters[(size_t)i * CK_CNT_STRIDE + CK_CNT_CLUSTERS], np = counters[(size_t)i * CK_CNT_STRIDE + CK_CNT_POINTS];
-        if ((int)nc > cluster_cap || (int)np > point_cap) return CK_ECAPACITY;
-        CK_HIP(hipMemcpy(clusters + (size_t)i * cluster_cap, ws.d_clusters + (size_t)i * ws.cluster_cap, sizeof(ck_cluster_t) * nc, hipMemcpyDeviceToHost));
+        if ((int)nc > cluster_cap) return CK_ECAPACITY;
+        ck_cluster_t *cl = clusters + (size_t)i * cluster_cap;
+        CK_HIP(hipMemcpy(cl, ws.d_clusters + (size_t)i * ws.cluster_cap, sizeof(ck_cluster_t) * nc, hipMemcpyDeviceToHost));
         std::vector<ck_packed_point> packed(np);
         CK_HIP(hipMemcpy(packed.data(), ws.d_points + (size_t)i * ws.ext_cap, sizeof(ck_packed_point) * np, hipMemcpyDeviceToHost));
-        for (uint32_t k = 0; k < np; k++) points[(size_t)i * point_cap + k] = ck_unpack_point(packed[k]);
-        n_clusters[i] = (int32_t)nc; n_points[i] = (int32_t)np;
+        size_t total = np;
+        for (uint32_t k = 0; k < np; k++) total += (packed[k] & CK_PT_TWIN) ? 1u : 0u;
+        if (total > (size_t)point_cap) return CK_ECAPACITY;
+        ck_cluster_point_t *out = points + (size_t)i * point_cap;
+        uint32_t at = 0;
+        for (uint32_t c = 0; c < nc; c++) {
+            const uint32_t s0 = cl[c].start, s1 = cl[c].count ? s0 + cl[c].count : s0; // (an empty record: a cluster k_scan had no room for)
+            if (s1 > np) return CK_EDEVICE; // (cannot happen: k_scan keeps a cluster only when its points fit)
+            cl[c].start = cl[c].count ? at : 0u;
+            for (uint32_t k = s0; k < s1; k++) {
+                out[at++] = ck_unpack_point(packed[k]);
+                if (packed[k] & CK_PT_TWIN) out[at++] = ck_unpack_twin(packed[k]);
+            }
+            cl[c].count = cl[c].count ? at - cl[c].start : 0u;
+        }
+        n_clusters[i] = (int32_t)nc; n_points[i] = (int32_t)at;
     }
     return CK_OK;
 }

@@ -9,8 +9,10 @@
 //              hop for ring-touching components, see ck_internal.h), aggregates the tile's points per cluster key
 //              in an LDS hash table, then makes ONE global insert + one add per (tile, key), writes the tile's points to
 //              the temp array as one contiguous run per key (4-byte packed points) and one run record per key.
+//              k_emit2 stores the two points a straight edge emits at one half-pixel (diagonal twins) as ONE word
+//              (ck_point.h), so a cluster has a logical count (the oracle's) and a physical one (words stored).
 //   k_scan     one workgroup per frame: prefix sums over the frame's hash table -> cluster table + point offsets
-//              (clusters outside [min_cluster_pixels, max_cluster_points] are dropped here).
+//              (clusters outside [min_cluster_pixels, max_cluster_points], by their logical count, are dropped here).
 //   k_scatter  one wave per run: temp array -> points grouped by cluster.
 #include "ck_internal.h"
 
@@ -36,6 +38,7 @@ struct EmitArgs {
     int w, h, tiles_x, tiles_y, min_comp;
     int ccl_tiles_x; // tiles per row of the segmentation stage (the label words are local to its 32 x 128 tiles)
     int stop_after; // diagnostics (CK_EMIT_STOP_AFTER): 0 staging only, 1 +count, 2 +reserve; 99 = everything
+    int twins;      // k_emit2 merges diagonal twin points (diagnostics: CK_EMIT_TWINS=0 emits every point on its own)
     ck_stage_ws ws;
 };
 
@@ -62,7 +65,7 @@ __global__ __launch_bounds__(NT) void k_emit(EmitArgs a) {
     const uint32_t *GR = a.groot + (size_t)frame * a.slots, *GS = a.gsize + (size_t)frame * a.slots;
     const ck_stage_ws &ws = a.ws;
     unsigned long long *gkeys = ws.d_ht_keys + (size_t)frame * ws.ht_size;
-    uint32_t *gcount = ws.d_ht_count + (size_t)frame * ws.ht_size;
+    unsigned long long *gcount = ws.d_ht_count + (size_t)frame * ws.ht_size;
     uint32_t *counters = ws.d_counters + (size_t)frame * CK_CNT_STRIDE;
     ck_packed_point *tmp = ws.d_tmp + (size_t)frame * ws.ext_cap;
     ck_run *runs = ws.d_runs + (size_t)frame * ws.run_cap;
@@ -229,8 +232,9 @@ __global__ __launch_bounds__(NT) void k_emit(EmitArgs a) {
                 if (q) found1 = found; else found0 = found;
             }
         }
-        if (found0 != SKIP) atomicAdd(&gcount[found0], c0); // result unused: nothing waits for these
-        if (found1 != SKIP) atomicAdd(&gcount[found1], c1);
+        // (result unused: nothing waits for these.  No twins here: a cluster's logical and physical counts are the same number)
+        if (found0 != SKIP) atomicAdd(&gcount[found0], ((unsigned long long)c0 << 32) | c0);
+        if (found1 != SKIP) atomicAdd(&gcount[found1], ((unsigned long long)c1 << 32) | c1);
     }
     lds_barrier();
     if (a.stop_after == 2) return;
@@ -295,6 +299,7 @@ __global__ __launch_bounds__(NT) void k_emit(EmitArgs a) {
 //    one piece in the frame is several pieces inside a 32 x 128 tile (the white giant component of dense noise above all), so every
 //    black blob beside two of its pieces became two keys, two runs, two inserts: count pass 1.18 -> 1.75 ms, 4.05 ms in all.
 constexpr uint32_t ID_WHITE = 0x40000000u, ID_VALUE = 0x3FFFFFFFu; // a staged pixel: frame pixel of its root (< 2^24) | colour
+static_assert(ID_WHITE == CK_PT_TWIN_SIGN, "a twin's sign is its white neighbour's colour bit, taken as it stands");
 constexpr int SR_PAD = ((LH * LW + NT - 1) / NT) * NT; // ids: every thread stores SPT of them unconditionally
 
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80))) void k_emit2(EmitArgs a, int xcd_map, int n_frames) {
@@ -321,7 +326,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80))) void k_emi
     const uint32_t *GR = a.groot + (size_t)frame * a.slots, *GS = a.gsize + (size_t)frame * a.slots;
     const ck_stage_ws &ws = a.ws;
     unsigned long long *gkeys = ws.d_ht_keys + (size_t)frame * ws.ht_size;
-    uint32_t *gcount = ws.d_ht_count + (size_t)frame * ws.ht_size;
+    unsigned long long *gcount = ws.d_ht_count + (size_t)frame * ws.ht_size;
     uint32_t *counters = ws.d_counters + (size_t)frame * CK_CNT_STRIDE;
     ck_packed_point *tmp = ws.d_tmp + (size_t)frame * ws.ext_cap;
     ck_run *runs = ws.d_runs + (size_t)frame * ws.run_cap;
@@ -389,14 +394,32 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80))) void k_emi
             bool ok[4];
 #pragma unroll
             for (int k = 0; k < 4; k++) ok[k] = r0 != SKIP && r1v[k] != SKIP && ((r0 ^ r1v[k]) & ID_WHITE) != 0u;
-            uint32_t lead[4], nth[4], mult[4]; // a point's leader (first point of its key), its place among the key's points, how many the leader stands for
+            // Twins.  When both diagonals of the 2 x 2 block at (x, y) join the same two components, the point (2x+1, 2y+1) is emitted
+            // twice into one cluster: by (1,1) from (x, y) and by (-1,1) from (x+1, y).  The first ABSORBS the second (its word then
+            // stands for both), the owner of the second DROPS it.  Absorb, at (x, y): the own k = 3 pair is a point; the twin's
+            // owner (x+1, y) lies in the emitting columns (x+1 <= w-2; its row is this one); the twin's pair (x+1, y) / (x, y+1)
+            // holds the same two staged words — which makes it a point as well: equal words are equal colours and neither is SKIP.
+            // Drop, at (x, y): the mirror image — the own k = 2 pair is a point, (x-1, y) lies in the emitting columns (x-1 >= 1),
+            // and its k = 3 pair (x-1, y) / (x, y+1) holds the same two words.  Both threads evaluate the same four staged words by
+            // the same rule, also across an emit-tile boundary (the staged region carries a column either side and a row below,
+            // and a staged word is a function of the frame alone), so one absorbs exactly when the other drops.  At the frame's
+            // edges one copy does not exist (owner in column 0 or w-1; rows 0 and h-1 emit nothing for either) and nothing merges.
+            const bool absorb = a.twins && ok[3] && gx + 1 <= w - 2 &&
+                                ((r0 == r1v[0] && r1v[3] == r1v[1]) || (r0 == r1v[1] && r1v[3] == r1v[0]));
+            const bool drop = a.twins && ok[2] && gx - 1 >= 1 &&
+                              ((r0 == R[rr][0] && r1v[2] == r1v[1]) || (r0 == r1v[1] && r1v[2] == R[rr][0]));
+            ok[2] = ok[2] && !drop;
+            // a point's leader (first point of its key), its place among the key's points, what the leader adds to the key's entry: both
+            // counts of the points it stands for, physical << 16 | logical (a twin: one word, two points)
+            uint32_t lead[4], nth[4], mult[4];
+            const uint32_t unit = 0x10001u, unit3 = absorb ? 0x10002u : unit;
 #pragma unroll
             for (int k = 0; k < 4; k++) {
-                lead[k] = (uint32_t)k; nth[k] = 0; mult[k] = 1;
+                lead[k] = (uint32_t)k; nth[k] = 0; mult[k] = k == 3 ? unit3 : unit;
 #pragma unroll
                 for (int j = k - 1; j >= 0; j--) { const bool eq = ok[j] && r1v[j] == r1v[k]; lead[k] = eq ? (uint32_t)j : lead[k]; nth[k] += eq ? 1u : 0u; }
 #pragma unroll
-                for (int j = k + 1; j < 4; j++) mult[k] += (ok[j] && r1v[j] == r1v[k]) ? 1u : 0u;
+                for (int j = k + 1; j < 4; j++) mult[k] += (ok[j] && r1v[j] == r1v[k]) ? (j == 3 ? unit3 : unit) : 0u;
             }
             uint32_t cl[4] = {NONE, NONE, NONE, NONE};
 #pragma unroll
@@ -418,7 +441,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80))) void k_emi
                     s = (s + 1) & (LHT - 1);
                 }
                 if (placed) { last_key = key; last_s = s; }
-                if (placed) cl[k] = (s << 16) | atomicAdd(&sCnt[s], mult[k]);
+                // (one add carries both counts of the key: physical in the high half — what it was before is the point's rank —, logical
+                // in the low half, which never carries: a tile has at most 5 120 points, twins counted twice)
+                if (placed) cl[k] = (s << 16) | (atomicAdd(&sCnt[s], mult[k]) >> 16);
                 else atomicOr(&counters[CK_CNT_STATUS], (uint32_t)CK_FRAME_CLUSTERS_OVERFLOW);
             }
 #pragma unroll
@@ -426,7 +451,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80))) void k_emi
                 const uint32_t lk = lead[k];
                 const uint32_t c = lk == 0u ? cl[0] : (lk == 1u ? cl[1] : (lk == 2u ? cl[2] : cl[3]));
                 const uint32_t sign = (r1v[k] & ID_WHITE) ? 0x80000000u : 0u; // gradient sign: the neighbour is the white one
-                cand[rr * 4 + k] = (ok[k] && c != NONE) ? ((c + nth[k]) | sign) : NONE;
+                // (the twin's sign: its neighbour (x, y+1) is the white one — ID_WHITE is CK_PT_TWIN_SIGN's bit)
+                const uint32_t twin = (k == 3 && absorb) ? (CK_PT_TWIN | (r1v[1] & ID_WHITE)) : 0u;
+                cand[rr * 4 + k] = (ok[k] && c != NONE) ? ((c + nth[k]) | sign | twin) : NONE;
             }
         }
     }
@@ -437,15 +464,18 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80))) void k_emi
     // and per (tile, key) one insert into the frame's table (waited for: it yields the slot) + one add to the cluster's point
     // count that nobody waits for.
     const unsigned long long k0 = sKey[2 * tid], k1 = sKey[2 * tid + 1];
-    const uint32_t c0 = k0 ? sCnt[2 * tid] : 0u, c1 = k1 ? sCnt[2 * tid + 1] : 0u;
-    uint32_t found0 = SKIP, found1 = SKIP, ridx0, tile_total;
+    // (an entry's two counts, physical << 16 | logical, stay side by side through the scans: a tile's 1 024 pixels own at most four
+    // points each and absorb at most one more, so neither sum comes near 2^16)
+    const uint32_t b0 = k0 ? sCnt[2 * tid] : 0u, b1 = k1 ? sCnt[2 * tid + 1] : 0u;
+    const uint32_t c0 = b0 >> 16, c1 = b1 >> 16;
+    uint32_t found0 = SKIP, found1 = SKIP, ridx0;
     {
-        const uint32_t incl = wave_scan_u32(c0 + c1);
-        const unsigned long long b0 = __ballot(k0 != 0ull), b1 = __ballot(k1 != 0ull);
+        const uint32_t incl2 = wave_scan_u32(b0 + b1), incl = incl2 >> 16;
+        const unsigned long long u0 = __ballot(k0 != 0ull), u1 = __ballot(k1 != 0ull);
         const unsigned long long below = (1ull << (tid & 63)) - 1ull;
-        ridx0 = (uint32_t)(__popcll(b0 & below) + __popcll(b1 & below)); // rank of this thread's first used entry in its wave
-        if ((tid & 63) == 63) sWave[tid >> 6] = incl;
-        if ((tid & 63) == 0) sRunW[tid >> 6] = (uint32_t)(__popcll(b0) + __popcll(b1));
+        ridx0 = (uint32_t)(__popcll(u0 & below) + __popcll(u1 & below)); // rank of this thread's first used entry in its wave
+        if ((tid & 63) == 63) sWave[tid >> 6] = incl2;
+        if ((tid & 63) == 0) sRunW[tid >> 6] = (uint32_t)(__popcll(u0) + __popcll(u1));
         lds_barrier();
         uint32_t before = 0, total = 0, rbefore = 0, rtotal = 0;
 #pragma unroll
@@ -455,10 +485,17 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80))) void k_emi
             total += t; rtotal += r;
         }
         ridx0 += rbefore;
-        tile_total = total;
+        before >>= 16;
         if (tid == 0) { // (entries NT / 64 of the two arrays are not among those the loop above reads)
-            sWave[NT / 64] = total ? atomicAdd(&counters[CK_CNT_TMP], total) : 0u;
+            const uint32_t ptotal = total >> 16, ltotal = total & 0xFFFFu;
+            // One add reserves the tile's words in the temp array (CK_CNT_TMP) and counts its points as the oracle counts them, in
+            // the word beside it (CK_CNT_CLUSTERS, which is nobody's until k_scan writes it).  The frame's point buffer counts as
+            // full when the points the frame HAS pass its capacity, stored twice or once.
+            static_assert(CK_CNT_TMP == 0 && CK_CNT_CLUSTERS == 1 && CK_CNT_STRIDE % 2 == 0, "the two counters are one aligned 64-bit word");
+            const unsigned long long was = total ? atomicAdd(reinterpret_cast<unsigned long long *>(counters), ((unsigned long long)ltotal << 32) | ptotal) : 0ull;
+            sWave[NT / 64] = (uint32_t)was;
             sRunW[NT / 64] = rtotal ? atomicAdd(&counters[CK_CNT_RUNS], rtotal) : 0u;
+            if ((uint32_t)(was >> 32) + ltotal > (uint32_t)ws.point_cap) atomicOr(&counters[CK_CNT_STATUS], (uint32_t)CK_FRAME_POINTS_OVERFLOW);
         }
         const uint32_t excl = before + incl - (c0 + c1);
         sTBase[2 * tid] = excl; sTBase[2 * tid + 1] = excl + c0;
@@ -487,15 +524,15 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80))) void k_emi
                 if (q) found1 = found; else found0 = found;
             }
         }
-        if (found0 != SKIP) atomicAdd(&gcount[found0], c0); // result unused: nothing waits for these
-        if (found1 != SKIP) atomicAdd(&gcount[found1], c1);
+        // (result unused: nothing waits for these)
+        if (found0 != SKIP) atomicAdd(&gcount[found0], ((unsigned long long)(b0 & 0xFFFFu) << 32) | c0);
+        if (found1 != SKIP) atomicAdd(&gcount[found1], ((unsigned long long)(b1 & 0xFFFFu) << 32) | c1);
     }
     lds_barrier();
     if (a.stop_after == 2) return;
 
     // pass 3: write the points (one contiguous run per key in the frame's temp array)
     const uint32_t tile_base = sWave[NT / 64];
-    (void)tile_total;
 #pragma unroll
     for (int q = 0; q < 16; q++) {
         const uint32_t cd = cand[q];
@@ -505,9 +542,10 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80))) void k_emi
         const uint32_t s = (cd >> 16) & 0x3FFu, lr = cd & 0xFFFFu;
         if (sSlot[s] == SKIP) continue; // (a key dropped in pass 2: a member below min_component_px, or no room in the frame's table)
         const uint32_t ti = tile_base + sTBase[s] + lr;
-        if (ti >= (uint32_t)ws.point_cap) { atomicOr(&counters[CK_CNT_STATUS], (uint32_t)CK_FRAME_POINTS_OVERFLOW); continue; }
+        if (ti >= (uint32_t)ws.point_cap) continue; // (pass 2 has set the status bit: fewer words than points)
         const int gy = y0 + row0 + rr;
-        tmp[ti] = ((uint32_t)(2 * gx + dxk) << 16) | ((uint32_t)(2 * gy + dyk) << 3) | ((uint32_t)k << 1) | (cd >> 31);
+        const uint32_t twin = k == 3 ? cd & (CK_PT_TWIN | CK_PT_TWIN_SIGN) : 0u; // (only a (1,1) point absorbs)
+        tmp[ti] = twin | ((uint32_t)(2 * gx + dxk) << 16) | ((uint32_t)(2 * gy + dyk) << 3) | ((uint32_t)k << 1) | (cd >> 31);
     }
     // run records (their place inside the cluster is decided by k_scatter)
     {
@@ -545,46 +583,50 @@ __global__ __launch_bounds__(NT) void k_clear(uint4 *keys4, size_t nkeys4, uint4
 constexpr int SNT = 1024;
 // One workgroup per frame; every wave owns a contiguous 1/16 of the table and walks it 64 slots at a time (coalesced
 // reads, DPP wave scans, running offsets in registers): one pass for the wave totals, one to hand out the offsets.
+// A cluster's LOGICAL count (twins counted twice: the oracle's) passes the size gates and, as a running sum, decides what the
+// frame's point capacity has room for; its PHYSICAL count (words stored) makes the offsets and the cluster record.
 __global__ __launch_bounds__(SNT) void k_scan(ck_stage_ws ws, int min_cluster, int max_cluster) {
-    __shared__ uint32_t sPts[SNT / 64], sCl[SNT / 64];
+    __shared__ uint32_t sPts[SNT / 64], sLog[SNT / 64], sCl[SNT / 64];
     const int frame = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const unsigned long long *gkeys = ws.d_ht_keys + (size_t)frame * ws.ht_size;
-    const uint32_t *gcount = ws.d_ht_count + (size_t)frame * ws.ht_size;
+    const unsigned long long *gcount = ws.d_ht_count + (size_t)frame * ws.ht_size;
     uint32_t *goff = ws.d_ht_off + (size_t)frame * ws.ht_size;
     uint32_t *counters = ws.d_counters + (size_t)frame * CK_CNT_STRIDE;
     ck_cluster_t *clusters = ws.d_clusters + (size_t)frame * ws.cluster_cap;
     const int seg = ws.ht_size / (SNT / 64); // ht_size is a multiple of SNT, so seg is a multiple of 64
     const int base = wv * seg;
-    uint32_t pts = 0, cl = 0;
+    uint32_t pts = 0, lpts = 0, cl = 0;
 #pragma unroll 8
     for (int r = 0; r < seg; r += 64) { // (unrolled: eight loads in flight; as a plain loop every 64 slots cost a trip to memory)
-        uint32_t c = gcount[base + r + lane];
-        bool ok = (int)c >= min_cluster && (int)c <= max_cluster;
-        pts += ok ? c : 0u; cl += ok ? 1u : 0u;
+        const unsigned long long c2 = gcount[base + r + lane];
+        const uint32_t c = (uint32_t)c2, lc = (uint32_t)(c2 >> 32);
+        bool ok = (int)lc >= min_cluster && (int)lc <= max_cluster;
+        pts += ok ? c : 0u; lpts += ok ? lc : 0u; cl += ok ? 1u : 0u;
     }
     pts = (uint32_t)__builtin_amdgcn_readlane((int)wave_scan_u32(pts), 63);
+    lpts = (uint32_t)__builtin_amdgcn_readlane((int)wave_scan_u32(lpts), 63);
     cl = (uint32_t)__builtin_amdgcn_readlane((int)wave_scan_u32(cl), 63);
-    if (lane == 0) { sPts[wv] = pts; sCl[wv] = cl; }
+    if (lane == 0) { sPts[wv] = pts; sLog[wv] = lpts; sCl[wv] = cl; }
     __syncthreads();
-    uint32_t po = 0, co = 0;
-    for (int k = 0; k < wv; k++) { po += sPts[k]; co += sCl[k]; }
+    uint32_t po = 0, lo = 0, co = 0;
+    for (int k = 0; k < wv; k++) { po += sPts[k]; lo += sLog[k]; co += sCl[k]; }
     // (the counts of four rounds are fetched together, then worked off in order; seg is a multiple of 64, not always of 256)
     for (int r4 = 0; r4 < seg; r4 += 256) {
-        uint32_t c4[4];
+        unsigned long long c4[4];
 #pragma unroll
-        for (int q = 0; q < 4; q++) c4[q] = r4 + 64 * q < seg ? gcount[base + r4 + 64 * q + lane] : 0u;
+        for (int q = 0; q < 4; q++) c4[q] = r4 + 64 * q < seg ? gcount[base + r4 + 64 * q + lane] : 0ull;
 #pragma unroll
     for (int q = 0; q < 4; q++) {
         const int r = r4 + 64 * q;
         if (r >= seg) continue; // (uniform)
         const int e = base + r + lane;
-        const uint32_t c = c4[q];
-        const bool ok = (int)c >= min_cluster && (int)c <= max_cluster;
-        const uint32_t ip = wave_scan_u32(ok ? c : 0u), ic = wave_scan_u32(ok ? 1u : 0u);
+        const uint32_t c = (uint32_t)c4[q], lc = (uint32_t)(c4[q] >> 32);
+        const bool ok = (int)lc >= min_cluster && (int)lc <= max_cluster;
+        const uint32_t ip = wave_scan_u32(ok ? c : 0u), il = wave_scan_u32(ok ? lc : 0u), ic = wave_scan_u32(ok ? 1u : 0u);
         uint32_t off = SKIP;
         if (ok) {
-            const uint32_t my_po = po + ip - c, my_co = co + ic - 1u;
-            if (my_co < (uint32_t)ws.cluster_cap && my_po + c <= (uint32_t)ws.point_cap) {
+            const uint32_t my_po = po + ip - c, my_lo = lo + il - lc, my_co = co + ic - 1u;
+            if (my_co < (uint32_t)ws.cluster_cap && my_lo + lc <= (uint32_t)ws.point_cap) { // (my_po + c <= my_lo + lc: the words fit too)
                 off = my_po;
                 unsigned long long key = gkeys[e];
                 ck_cluster_t ck;
@@ -603,6 +645,7 @@ __global__ __launch_bounds__(SNT) void k_scan(ck_stage_ws ws, int min_cluster, i
         }
         goff[e] = off;
         po += (uint32_t)__builtin_amdgcn_readlane((int)ip, 63);
+        lo += (uint32_t)__builtin_amdgcn_readlane((int)il, 63);
         co += (uint32_t)__builtin_amdgcn_readlane((int)ic, 63);
     }
     }
@@ -697,7 +740,7 @@ int ck_launch_clusters(ck_handle *h, int n) {
         // list counts and dequeue heads, the decode candidates' counts (five fills before; their launches were a twentieth of
         // a one-frame call)
         const ck_fit_layout fl = ck_fit_scratch_layout(ws, h->cfg.max_batch);
-        const size_t nkeys4 = (size_t)ws.ht_size * n / 2, ncnt4 = (size_t)ws.ht_size * n / 4; // ht_size is a multiple of 1024
+        const size_t nkeys4 = (size_t)ws.ht_size * n / 2, ncnt4 = (size_t)ws.ht_size * n / 2; // (8 bytes per slot each) ht_size is a multiple of 1024
         const size_t total4 = nkeys4 + ncnt4;
         hipLaunchKernelGGL(k_clear, dim3((unsigned)((total4 + NT - 1) / NT)), dim3(NT), 0, h->stream,
                            reinterpret_cast<uint4 *>(ws.d_ht_keys), nkeys4, reinterpret_cast<uint4 *>(ws.d_ht_count), ncnt4, ws.d_counters,
@@ -708,6 +751,7 @@ int ck_launch_clusters(ck_handle *h, int n) {
     a.w = h->qw; a.h = h->qh; a.tiles_x = (h->qw + ETW - 1) / ETW; a.tiles_y = (h->qh + ETH - 1) / ETH;
     a.min_comp = h->cfg.min_component_px; a.ws = ws; a.ccl_tiles_x = h->tiles_x;
     { static const int stop_after = CK_KNOB("CK_EMIT_STOP_AFTER", 99); a.stop_after = stop_after; }
+    { static const int twins = CK_KNOB("CK_EMIT_TWINS", 1); a.twins = twins; } // (diagnostics: 0 = every point on its own, for A/B)
     static const int emit_v = CK_KNOB("CK_EMIT_V", 2);       // (diagnostics: 1 = the round-1..3 kernel, for A/B)
     static const int emit_xcd = CK_KNOB("CK_EMIT_XCD", -1);  // (diagnostics: frames dealt to XCDs 0 / 1; default: batches of 16 frames and more)
     if (emit_v == 1) hipLaunchKernelGGL(k_emit, dim3((unsigned)(a.tiles_x * a.tiles_y * n)), dim3(NT), 0, h->stream, a);

@@ -660,7 +660,7 @@ __device__ __forceinline__ Box front_box(const ck_packed_point (&rawp)[CAP / NTH
     const int tid = loop_tid();
     int xmin = 1 << 30, xmax = -(1 << 30), ymin = 1 << 30, ymax = -(1 << 30);
     auto take = [&](ck_packed_point v) {
-        const int px = (int)((v >> 16) & 0x1FFFu), py = (int)((v >> 3) & 0x1FFFu); // ck_unpack_point's x and y
+        const int px = (int)((v >> 16) & 0x1FFFu), py = (int)((v >> 3) & 0x1FFFu); // ck_unpack_point's x and y (the masks drop a twin's bits 29, 30)
         xmin = min(xmin, px); xmax = max(xmax, px);
         ymin = min(ymin, py); ymax = max(ymax, py);
     };
