@@ -35,22 +35,15 @@ static int refine_batch(ck_handle_t *h, const ck_calib_params_t *p, const ck_cal
     if (!ck_workspace(h->calib)) return CK_ENOMEM;
     ck_calib_ws &W = *h->calib;
     const size_t pt_bytes = sizeof(double) * 2 * (size_t)n_points, pose_bytes = sizeof(double) * 12 * (size_t)n_frames;
-    int rc = W.d_prob.reserve(sizeof(ck_calib_problem_t) * (size_t)n);
-    if (rc == CK_OK) rc = W.d_rec0.reserve(sizeof(int32_t) * (size_t)n);
-    if (rc == CK_OK) rc = W.d_fs.reserve(sizeof(int32_t) * (size_t)n_starts);
-    if (rc == CK_OK) rc = W.d_bxy.reserve(pt_bytes);
-    if (rc == CK_OK) rc = W.d_uv.reserve(pt_bytes);
+    int rc = ck_upload(W.d_prob, problems, sizeof(ck_calib_problem_t) * (size_t)n, h->stream);
+    if (rc == CK_OK) rc = ck_upload(W.d_rec0, rec0.data(), sizeof(int32_t) * (size_t)n, h->stream);
+    if (rc == CK_OK) rc = ck_upload(W.d_fs, frame_start, sizeof(int32_t) * (size_t)n_starts, h->stream);
+    if (rc == CK_OK) rc = ck_upload(W.d_bxy, board_xy, pt_bytes, h->stream);
+    if (rc == CK_OK) rc = ck_upload(W.d_uv, image_uv, pt_bytes, h->stream);
     if (rc == CK_OK) rc = W.d_rec.reserve(sizeof(double) * CKC_WS_STRIDE * (size_t)n_rec);
-    if (rc == CK_OK) rc = W.d_poses.reserve(pose_bytes);
-    if (rc == CK_OK) rc = W.d_res.reserve(sizeof(ck_calib_result_t) * (size_t)n);
+    if (rc == CK_OK) rc = ck_upload(W.d_poses, poses, pose_bytes, h->stream);
+    if (rc == CK_OK) rc = ck_upload(W.d_res, results, sizeof(ck_calib_result_t) * (size_t)n, h->stream);
     if (rc != CK_OK) return rc;
-    CK_HIP(hipMemcpyAsync(W.d_prob, problems, sizeof(ck_calib_problem_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
-    CK_HIP(hipMemcpyAsync(W.d_rec0, rec0.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
-    CK_HIP(hipMemcpyAsync(W.d_fs, frame_start, sizeof(int32_t) * (size_t)n_starts, hipMemcpyHostToDevice, h->stream));
-    CK_HIP(hipMemcpyAsync(W.d_bxy, board_xy, pt_bytes, hipMemcpyHostToDevice, h->stream));
-    CK_HIP(hipMemcpyAsync(W.d_uv, image_uv, pt_bytes, hipMemcpyHostToDevice, h->stream));
-    CK_HIP(hipMemcpyAsync(W.d_poses, poses, pose_bytes, hipMemcpyHostToDevice, h->stream));
-    CK_HIP(hipMemcpyAsync(W.d_res, results, sizeof(ck_calib_result_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
     rc = ck_launch_calib(h->stream, *p, W.d_prob, W.d_rec0, n, W.d_fs, W.d_bxy, W.d_uv, W.d_rec, W.d_poses, W.d_res);
     if (rc != CK_OK) return rc;
     CK_HIP(hipMemcpyAsync(results, W.d_res, sizeof(ck_calib_result_t) * (size_t)n, hipMemcpyDeviceToHost, h->stream));

@@ -274,7 +274,7 @@ int ck_calib_refine_host(const ck_calib_params_t *p, const ck_calib_problem_t *q
     const double cost0 = twin_cost(&T, kc);
     if (ckc_finite(cost0)) {
         ckc_lm_t lm;
-        ckc_lm_start(&lm, cost0);
+        ckc_lm_start(&lm, cost0, CKC_COST_FLOOR);
         while (lm.status < 0) {
             if (lm.need_jac) {
                 for (int f = 0; f < F; f++) {
@@ -312,7 +312,7 @@ int ck_calib_refine_host(const ck_calib_params_t *p, const ck_calib_problem_t *q
                 for (int f = 0; f < F; f++) pred = pred + T.ws[(size_t)CKC_WS_STRIDE * f + CKC_WS_PRED];
                 cost_new = twin_cost(&T, kc);
             }
-            if (ckc_lm_decide(&lm, solved, pred, cost_new, p->max_iters)) {
+            if (ckc_lm_decide(&lm, solved, pred, cost_new, p->max_iters, CKC_COST_FLOOR)) {
                 memcpy(k, kc, sizeof k);
                 for (int f = 0; f < F; f++)
                     memcpy(T.ws + (size_t)CKC_WS_STRIDE * f + CKC_WS_POSE, T.ws + (size_t)CKC_WS_STRIDE * f + CKC_WS_CAND, sizeof(double) * 12);

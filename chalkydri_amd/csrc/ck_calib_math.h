@@ -136,47 +136,46 @@ CKC_FN void ckc_accumulate(double *acc, const double *r, const double *Ju, const
 // Marquardt scaling: the diagonal of J^T J, floored
 CKC_FN double ckc_scale(double d) { return d < 1e-30 ? 1e-30 : d; }
 
-// In-place Cholesky of the lower triangle of the n x n row-major M; 0 when a pivot is not positive (the factor is garbage then)
-CKC_FN int ckc_chol(double *M, const int n) {
-    int ok = 1;
-    CKC_UNROLL
-    for (int j = 0; j < n; j++) {
-        double s = M[j * n + j];
-        CKC_UNROLL
-        for (int c = 0; c < j; c++) s = s - M[j * n + c] * M[j * n + c];
-        if (!(s > 0.0)) ok = 0;
-        const double d = sqrt(s);
-        M[j * n + j] = d;
-        CKC_UNROLL
-        for (int i = j + 1; i < n; i++) {
-            double t = M[i * n + j];
-            CKC_UNROLL
-            for (int c = 0; c < j; c++) t = t - M[i * n + c] * M[j * n + c];
-            M[i * n + j] = t / d;
-        }
+// Three dense helpers, one text in two forms: ckc_chol / ckc_fwd / ckc_bwd for an n that is a constant where they are called (6, 9:
+// every loop unrolled, the matrices in registers) and ckc_chol_n / ckc_fwd_n / ckc_bwd_n for an n known only at run time (plain loops:
+// there is nothing to unroll, and asking for it only earns a warning).  The operations and their order are the same.
+//   chol  in-place Cholesky of the lower triangle of the n x n row-major M; 0 when a pivot is not positive (the factor is garbage then)
+//   fwd   y = L^-1 b, products subtracted in increasing c; b and the result have stride `st`
+//   bwd   x = L^-T y, products subtracted in increasing c
+#define CKC_DENSE(SUFFIX, LOOP)                                                      \
+    CKC_FN int ckc_chol##SUFFIX(double *M, const int n) {                            \
+        int ok = 1;                                                                  \
+        LOOP for (int j = 0; j < n; j++) {                                           \
+            double s = M[j * n + j];                                                 \
+            LOOP for (int c = 0; c < j; c++) s = s - M[j * n + c] * M[j * n + c];    \
+            if (!(s > 0.0)) ok = 0;                                                  \
+            const double d = sqrt(s);                                                \
+            M[j * n + j] = d;                                                        \
+            LOOP for (int i = j + 1; i < n; i++) {                                   \
+                double t = M[i * n + j];                                             \
+                LOOP for (int c = 0; c < j; c++) t = t - M[i * n + c] * M[j * n + c]; \
+                M[i * n + j] = t / d;                                                \
+            }                                                                        \
+        }                                                                            \
+        return ok;                                                                   \
+    }                                                                                \
+    CKC_FN void ckc_fwd##SUFFIX(const double *L, const int n, double *b, const int st) { \
+        LOOP for (int i = 0; i < n; i++) {                                           \
+            double t = b[i * st];                                                    \
+            LOOP for (int c = 0; c < i; c++) t = t - L[i * n + c] * b[c * st];       \
+            b[i * st] = t / L[i * n + i];                                            \
+        }                                                                            \
+    }                                                                                \
+    CKC_FN void ckc_bwd##SUFFIX(const double *L, const int n, double *b) {           \
+        LOOP for (int ii = 0; ii < n; ii++) {                                        \
+            const int i = n - 1 - ii;                                                \
+            double t = b[i];                                                         \
+            LOOP for (int c = i + 1; c < n; c++) t = t - L[c * n + i] * b[c];        \
+            b[i] = t / L[i * n + i];                                                 \
+        }                                                                            \
     }
-    return ok;
-}
-// y = L^-1 b and x = L^-T y; b and the result have stride `st`
-CKC_FN void ckc_fwd(const double *L, const int n, double *b, const int st) {
-    CKC_UNROLL
-    for (int i = 0; i < n; i++) {
-        double t = b[i * st];
-        CKC_UNROLL
-        for (int c = 0; c < i; c++) t = t - L[i * n + c] * b[c * st];
-        b[i * st] = t / L[i * n + i];
-    }
-}
-CKC_FN void ckc_bwd(const double *L, const int n, double *b) {
-    CKC_UNROLL
-    for (int ii = 0; ii < n; ii++) {
-        const int i = n - 1 - ii;
-        double t = b[i];
-        CKC_UNROLL
-        for (int c = i + 1; c < n; c++) t = t - L[c * n + i] * b[c];
-        b[i] = t / L[i * n + i];
-    }
-}
+CKC_DENSE(, CKC_UNROLL)
+CKC_DENSE(_n, )
 
 // One frame's part of the Schur complement at damping lambda: factor A_f + lambda D_f, W = L^-1 B_f^T, wg = L^-1 g_f,
 // E = (W^T W, W^T wg).  `f` is the frame's record; 0 when the factorisation fails.
@@ -255,8 +254,31 @@ CKC_FN int ckc_reduced_solve(const double *Hs, const double *Es, double lambda, 
     return ok;
 }
 
-// One frame's step given the intrinsics' step: d_f = -L^-T (wg + W dk); candidate pose R C(d_w), t + d_t with the Cayley map
-// C(d) = ((1 - a.a) I + 2 a a^T + 2 [a]x) / (1 + a.a), a = d / 2; the frame's share of the predicted decrease.
+// The Cayley map C(d) = ((1 - a.a) I + 2 a a^T + 2 [a]x) / (1 + a.a), a = d / 2: a rotation for every d, the identity at d = 0
+CKC_FN void ckc_cayley(const double *d, double *Cm) {
+    const double a0 = 0.5 * d[0], a1 = 0.5 * d[1], a2 = 0.5 * d[2];
+    const double nn = a0 * a0 + a1 * a1 + a2 * a2, den = 1.0 + nn, e = 1.0 - nn;
+    Cm[0] = (e + (2.0 * a0) * a0) / den; Cm[1] = ((2.0 * a0) * a1 - 2.0 * a2) / den; Cm[2] = ((2.0 * a0) * a2 + 2.0 * a1) / den;
+    Cm[3] = ((2.0 * a1) * a0 + 2.0 * a2) / den; Cm[4] = (e + (2.0 * a1) * a1) / den; Cm[5] = ((2.0 * a1) * a2 - 2.0 * a0) / den;
+    Cm[6] = ((2.0 * a2) * a0 - 2.0 * a1) / den; Cm[7] = ((2.0 * a2) * a1 + 2.0 * a0) / den; Cm[8] = (e + (2.0 * a2) * a2) / den;
+}
+// The update of a rigid transform P = (R row-major, t) by the increment d = (d_w, d_t): Pc = (R C(d_w), t + d_t).  mask6 freezes
+// increments: a rotation whose three increments (bits 0..2) are all frozen and a frozen component of t (bits 3..5) are copied, so
+// they come back bit for bit.
+CKC_FN void ckc_rigid_step(const double *P, const double *d, unsigned mask6, double *Pc) {
+    double Cm[9];
+    ckc_cayley(d, Cm);
+    CKC_UNROLL
+    for (int i = 0; i < 3; i++) {
+        const double r0 = P[3 * i], r1 = P[3 * i + 1], r2 = P[3 * i + 2];
+        CKC_UNROLL
+        for (int j = 0; j < 3; j++) Pc[3 * i + j] = (mask6 & 7u) == 7u ? P[3 * i + j] : (r0 * Cm[j] + r1 * Cm[3 + j]) + r2 * Cm[6 + j];
+        Pc[9 + i] = ((mask6 >> (3 + i)) & 1u) ? P[9 + i] : P[9 + i] + d[3 + i];
+    }
+}
+
+// One frame's step given the intrinsics' step: d_f = -L^-T (wg + W dk); the candidate pose (ckc_rigid_step); the frame's share of
+// the predicted decrease.
 CKC_FN void ckc_frame_step(double *f, const double *dk, double lambda) {
     double d[6];
     CKC_UNROLL
@@ -275,33 +297,23 @@ CKC_FN void ckc_frame_step(double *f, const double *dk, double lambda) {
     for (int i = 0; i < 6; i++)
         p = p + d[i] * ((lambda * ckc_scale(f[CKC_WS_H + CKC_TRI(9 + i, 9 + i)])) * d[i] - f[CKC_WS_H + CKC_NH + 9 + i]);
     f[CKC_WS_PRED] = p;
-    const double a0 = 0.5 * d[0], a1 = 0.5 * d[1], a2 = 0.5 * d[2];
-    const double nn = a0 * a0 + a1 * a1 + a2 * a2, den = 1.0 + nn, e = 1.0 - nn;
-    double Cm[9];
-    Cm[0] = (e + (2.0 * a0) * a0) / den; Cm[1] = ((2.0 * a0) * a1 - 2.0 * a2) / den; Cm[2] = ((2.0 * a0) * a2 + 2.0 * a1) / den;
-    Cm[3] = ((2.0 * a1) * a0 + 2.0 * a2) / den; Cm[4] = (e + (2.0 * a1) * a1) / den; Cm[5] = ((2.0 * a1) * a2 - 2.0 * a0) / den;
-    Cm[6] = ((2.0 * a2) * a0 - 2.0 * a1) / den; Cm[7] = ((2.0 * a2) * a1 + 2.0 * a0) / den; Cm[8] = (e + (2.0 * a2) * a2) / den;
-    CKC_UNROLL
-    for (int i = 0; i < 3; i++) {
-        const double r0 = f[CKC_WS_POSE + 3 * i], r1 = f[CKC_WS_POSE + 3 * i + 1], r2 = f[CKC_WS_POSE + 3 * i + 2];
-        CKC_UNROLL
-        for (int j = 0; j < 3; j++) f[CKC_WS_CAND + 3 * i + j] = r0 * Cm[j] + r1 * Cm[3 + j] + r2 * Cm[6 + j];
-        f[CKC_WS_CAND + 9 + i] = f[CKC_WS_POSE + 9 + i] + d[3 + i];
-    }
+    ckc_rigid_step(f + CKC_WS_POSE, d, 0u, f + CKC_WS_CAND);
 }
 
-// Nielsen's damping and the stop rules.  The scalar state of one solve:
+// Nielsen's damping and the stop rules.  `cost_floor` is the cost below which a solve is done, in the units of the caller's cost: 1e-20
+// px^2 here (CKC_COST_FLOOR), CKR_COST_FLOOR for the two solvers of ck_cal_math.h.  The scalar state of one solve:
 typedef struct ckc_lm {
     double lambda, nu, cost;
     int iters, status, need_jac; // status -1 while running
 } ckc_lm_t;
-CKC_FN void ckc_lm_start(ckc_lm_t *s, double cost0) {
+#define CKC_COST_FLOOR 1e-20
+CKC_FN void ckc_lm_start(ckc_lm_t *s, double cost0, double cost_floor) {
     s->lambda = 1e-3; s->nu = 2.0; s->cost = cost0;
     s->iters = 0; s->need_jac = 1;
-    s->status = cost0 < 1e-20 ? 0 : -1;
+    s->status = cost0 < cost_floor ? 0 : -1;
 }
 // One outer iteration ends: solved = the factorisations went through, pred / cost_new as computed.  1: the candidate is accepted.
-CKC_FN int ckc_lm_decide(ckc_lm_t *s, int solved, double pred, double cost_new, int max_iters) {
+CKC_FN int ckc_lm_decide(ckc_lm_t *s, int solved, double pred, double cost_new, int max_iters, double cost_floor) {
     int accept = 0;
     double rho = 0.0;
     s->iters = s->iters + 1;
@@ -311,7 +323,7 @@ CKC_FN int ckc_lm_decide(ckc_lm_t *s, int solved, double pred, double cost_new, 
     }
     if (accept) {
         const double dec = s->cost - cost_new, t = 2.0 * rho - 1.0, m = 1.0 - (t * t) * t;
-        const int done = dec <= 1e-14 * s->cost || cost_new < 1e-20;
+        const int done = dec <= 1e-14 * s->cost || cost_new < cost_floor;
         s->lambda = s->lambda * (m < 1.0 / 3.0 ? 1.0 / 3.0 : m);
         s->nu = 2.0;
         s->cost = cost_new;

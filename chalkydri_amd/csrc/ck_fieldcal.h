@@ -24,8 +24,8 @@ struct ck_fieldcal_ws {
     ck_dev_buf<double> d_mounts;                // [n_cams][12]
     ck_dev_buf<double> d_tags;                  // [n_problems][CK_FIELDCAL_MAX_TAGS][12] starts in, results out
     ck_dev_buf<double> d_rms;                   // [n_problems][CK_FIELDCAL_MAX_TAGS] the tags' rms out
-    ck_dev_buf<double> d_steps;                 // [used steps of the call][CKR_S_STRIDE]; the start poses in, the results out (CKR_S_POSE)
-    ck_dev_buf<double> d_pairs;                 // [pairs of the call][CKF_P_STRIDE]
+    ck_dev_buf<double> d_steps;                 // [used steps of the call][CKA_S_STRIDE]; the start poses in, the results out (CKA_S_POSE)
+    ck_dev_buf<double> d_pairs;                 // [pairs of the call][CKA_B_STRIDE]
     ck_dev_buf<double> d_sights;                // [sightings of the call][CKF_I_STRIDE]
     ck_dev_buf<double> d_S;                     // the problems' reduced systems
     ck_dev_buf<ck_fieldcal_result_t> d_res;     // [n_problems] starts in (ck_fieldcal_result_start), results out

@@ -1,8 +1,10 @@
 /* Field calibration, the half that needs no device: the checks every entry point shares, what is decided about a
  * problem before it is solved (which steps count, the tags with sightings, the sightings in the order they are summed in, the gauge,
  * the co-visibility graph), the conversions at the ABI's boundary and ck_fieldcal_refine_host, the one-thread twin of k_fieldcal.hip.
- * The arithmetic is ck_fieldcal_math.h's, compiled into both; this file walks sightings, pairs and steps the way the kernel's lanes
- * and threads do, and factors the reduced system in the order the kernel's rows do, so that the two return the same bytes. */
+ * The arithmetic is ck_fieldcal_math.h's and ck_cal_math.h's, compiled into both; this file walks sightings, pairs and steps the way the
+ * kernel's lanes and threads do, and factors the reduced system in the order the kernel's rows do, so that the two return the same
+ * bytes.  What the mount calibration does the same way on the host is ck_cal_host.c's. */
+#include "ck_cal_c.h"
 #include "ck_fieldcal_c.h"
 #include "ck_fieldcal_math.h"
 #include "ck_rigcal_c.h"
@@ -15,55 +17,19 @@ void ck_fieldcal_params_default(ck_fieldcal_params_t *p) {
     p->max_iters = 100; p->min_steps = 3; p->min_tags_per_step = 2;
 }
 
-static int iso_finite(const ck_iso3_t *t) {
-    for (int k = 0; k < 3; k++)
-        if (!ckc_finite(t->t[k])) return 0;
-    for (int k = 0; k < 4; k++)
-        if (!ckc_finite(t->q[k])) return 0;
-    return t->q[0] * t->q[0] + t->q[1] * t->q[1] + t->q[2] * t->q[2] + t->q[3] * t->q[3] > 0.0;
-}
-
 int ck_fieldcal_check(const ck_fieldcal_params_t *p, int32_t n_cams, const ck_sqpnp_problem_t *records, int32_t n_steps,
                       const int32_t *tag_index, int32_t n_tags_total, const double *bearings, int32_t n_bearings_total,
                       const ck_rigcal_problem_t *problems, int32_t n_problems, const int32_t *step_index, int32_t n_index_total,
                       const ck_iso3_t *mounts, const ck_iso3_t *layout0, int32_t n_layout, const uint8_t *fixed6) {
-    if (!p || !records || !problems || !step_index || !mounts || !layout0 || !fixed6) return CK_EINVAL;
-    if ((!tag_index && n_tags_total != 0) || (!bearings && n_bearings_total != 0)) return CK_EINVAL;
-    if (n_cams < 1 || n_cams > CK_RIG_MAX_CAMS || n_layout < 1) return CK_EINVAL;
-    if (n_steps < 0 || n_tags_total < 0 || n_bearings_total < 0 || n_problems < 0 || n_index_total < 0) return CK_EINVAL;
-    if (n_tags_total > 0x0FFFFFFF || n_layout > 0x0FFFFFFF || (int64_t)n_cams * n_steps > 0x0FFFFFFF) return CK_EINVAL;
+    if (!p || !layout0 || !fixed6 || n_layout < 1 || n_layout > 0x0FFFFFFF) return CK_EINVAL;
+    int rc = ck_cal_check(n_cams, records, n_steps, tag_index, n_tags_total, bearings, n_bearings_total, problems, n_problems, step_index,
+                          n_index_total, mounts, p->max_iters, p->min_steps, p->min_tags_per_step);
+    if (rc != CK_OK) return rc;
     const int64_t n_rec = (int64_t)n_cams * n_steps;
-    for (int64_t i = 0; i < n_rec; i++) {
-        const ck_sqpnp_problem_t *r = records + i;
-        if (r->n_tags < 0 || r->n_bearings < 0 || r->tag_offset < 0 || r->bearing_offset < 0) return CK_EINVAL;
-        if ((int64_t)r->tag_offset + r->n_tags > n_tags_total || (int64_t)r->bearing_offset + r->n_bearings > n_bearings_total) return CK_EINVAL;
-    }
-    for (int64_t i = 0; i < n_rec; i++)
-        if ((int64_t)4 * records[i].n_tags != records[i].n_bearings) return CK_EINVAL;
     for (int32_t t = 0; t < n_tags_total; t++)
         if (tag_index[t] < 0 || tag_index[t] >= n_layout) return CK_EINVAL;
-    for (int32_t i = 0; i < n_problems; i++) {
-        const ck_rigcal_problem_t *q = problems + i;
-        if (q->n_steps < 0 || q->step_offset < 0 || (int64_t)q->step_offset + q->n_steps > n_index_total) return CK_EINVAL;
-        for (int32_t j = 0; j < q->n_steps; j++) {
-            const int32_t s = step_index[q->step_offset + j];
-            if (s < 0 || s >= n_steps || (j > 0 && s <= step_index[q->step_offset + j - 1])) return CK_EINVAL;
-        }
-    }
-    if (p->max_iters < 1 || p->max_iters > 10000) return CK_EINVAL;
-    if (p->min_steps < 1) return CK_EINVAL;
-    if (p->min_tags_per_step < 2) return CK_EINVAL;
     for (int32_t k = 0; k < n_layout; k++)
-        if (fixed6[k] > CK_FIELDCAL_FIX_ALL) return CK_EINVAL;
-    for (int64_t i = 0; i < n_rec; i++) {
-        const ck_sqpnp_problem_t *r = records + i;
-        for (int64_t j = 3 * (int64_t)r->bearing_offset; j < 3 * ((int64_t)r->bearing_offset + r->n_bearings); j++)
-            if (!ckc_finite(bearings[j])) return CK_EINVAL;
-    }
-    for (int32_t c = 0; c < n_cams; c++)
-        if (!iso_finite(mounts + c)) return CK_EINVAL;
-    for (int32_t k = 0; k < n_layout; k++)
-        if (!iso_finite(layout0 + k)) return CK_EINVAL;
+        if (fixed6[k] > CK_FIELDCAL_FIX_ALL || !ck_cal_iso_finite(layout0 + k)) return CK_EINVAL;
     int gauge = 0;
     for (int64_t i = 0; i < n_rec; i++) {
         const int32_t *ti = tag_index + records[i].tag_offset;
@@ -78,7 +44,6 @@ int ck_fieldcal_check(const ck_fieldcal_params_t *p, int32_t n_cams, const ck_sq
         if (problems[i].n_steps > CK_FIELDCAL_MAX_STEPS) return CK_ECAPACITY;
     int32_t *stamp = (int32_t *)calloc((size_t)n_layout, sizeof(int32_t));
     if (!stamp) return CK_ENOMEM;
-    int rc = CK_OK;
     for (int32_t i = 0; i < n_problems && rc == CK_OK; i++) {
         int32_t seen = 0;
         for (int32_t j = 0; j < problems[i].n_steps; j++) {
@@ -101,11 +66,6 @@ int ck_fieldcal_check(const ck_fieldcal_params_t *p, int32_t n_cams, const ck_sq
 void ck_fieldcal_tag_in(const ck_iso3_t *iso, double *T) {
     ck_rigcal_quat_to_mat(iso->q, T);
     for (int i = 0; i < 3; i++) T[9 + i] = iso->t[i];
-}
-
-static int find(int *parent, int i) {
-    while (parent[i] != i) i = parent[i] = parent[parent[i]];
-    return i;
 }
 
 void ck_fieldcal_plan_free(ck_fieldcal_plan_t *plan) {
@@ -160,9 +120,9 @@ int ck_fieldcal_plan(const ck_fieldcal_params_t *p, int32_t n_cams, const ck_sqp
     if (!plan->meta || !key || !kbo) goto done;
     {
         const ckf_meta_t m = ckf_meta_at(plan->meta, U, P, NS, T);
-        int32_t *m_used = (int32_t *)m.used, *step_pair = (int32_t *)m.step_pair, *pair_tag = (int32_t *)m.pair_tag;
-        int32_t *pair_step = (int32_t *)m.pair_step, *pair_sight = (int32_t *)m.pair_sight, *sight_pair = (int32_t *)m.sight_pair;
-        int32_t *sight_cam = (int32_t *)m.sight_cam, *sight_bear = (int32_t *)m.sight_bear, *pairmap = (int32_t *)m.pairmap;
+        int32_t *m_used = (int32_t *)m.ix.used, *step_pair = (int32_t *)m.ix.first, *pair_tag = (int32_t *)m.ix.col;
+        int32_t *pair_step = (int32_t *)m.ix.step, *pair_sight = (int32_t *)m.pair_sight, *sight_pair = (int32_t *)m.sight_pair;
+        int32_t *sight_cam = (int32_t *)m.sight_cam, *sight_bear = (int32_t *)m.sight_bear, *pairmap = (int32_t *)m.ix.colmap;
         int32_t *ltag = (int32_t *)m.ltag, *tag_ns = (int32_t *)m.tag_ns, *mask6 = (int32_t *)m.mask6;
         int parent[CK_FIELDCAL_MAX_TAGS], anchored[CK_FIELDCAL_MAX_TAGS];
         for (size_t i = 0; i < T * U; i++) pairmap[i] = -1;
@@ -190,7 +150,7 @@ int ck_fieldcal_plan(const ck_fieldcal_params_t *p, int32_t n_cams, const ck_sqp
                 if (i == 0 || key[i - 1] / CK_RIG_MAX_CAMS != k) {
                     pair_tag[np] = k; pair_step[np] = (int32_t)u; pair_sight[np] = ns;
                     pairmap[(size_t)k * U + u] = np;
-                    parent[find(parent, k)] = find(parent, key[0] / CK_RIG_MAX_CAMS);
+                    parent[ck_cal_find(parent, k)] = ck_cal_find(parent, key[0] / CK_RIG_MAX_CAMS);
                     np++;
                 }
                 sight_pair[ns] = np - 1; sight_cam[ns] = key[i] % CK_RIG_MAX_CAMS; sight_bear[ns] = kbo[i];
@@ -201,11 +161,11 @@ int ck_fieldcal_plan(const ck_fieldcal_params_t *p, int32_t n_cams, const ck_sqp
         pair_sight[P] = ns;
         /* every tag that moves hangs on one that does not */
         for (size_t k = 0; k < T; k++)
-            if (mask6[k] == 63) anchored[find(parent, (int)k)] = 1;
+            if (mask6[k] == 63) anchored[ck_cal_find(parent, (int)k)] = 1;
         for (size_t k = 0; k < T; k++) {
             if (mask6[k] == 63) continue;
             plan->n_solved++;
-            if (!anchored[find(parent, (int)k)]) plan->status = CK_CALIB_DEGENERATE;
+            if (!anchored[ck_cal_find(parent, (int)k)]) plan->status = CK_CALIB_DEGENERATE;
         }
     }
     ret = CK_OK;
@@ -246,12 +206,11 @@ int ck_fieldcal_jacobian(const ck_iso3_t *mount, const double *pose, const ck_is
     double M[12], T[12];
     ck_rigcal_mount_in(mount, M);
     ck_fieldcal_tag_in(tag, T);
-    for (int32_t i = 0; i < n; i++) ckf_jacobian(M, pose, T, i, bearings + 3 * (size_t)i, fixed6 & 63u, r_out + 3 * (size_t)i, J_out + 3 * CKR_NJ * (size_t)i);
+    for (int32_t i = 0; i < n; i++) ckf_jacobian(M, pose, T, i, bearings + 3 * (size_t)i, fixed6 & 63u, r_out + 3 * (size_t)i, J_out + 3 * CKA_NJ * (size_t)i);
     return CK_OK;
 }
 
 /* ---- the twin ---------------------------------------------------------------------------------------------------------------- */
-#define NACC (CKR_NH + CKR_NJ)
 typedef struct {
     ckf_meta_t m;
     int U, P, NS, T;
@@ -263,7 +222,7 @@ typedef struct {
 static double twin_cost(twin_t *W, const double *Tc) {
     for (int g = 0; g < W->NS; g++) {
         const int pi = W->m.sight_pair[g];
-        const double *T = Tc + 12 * (size_t)W->m.pair_tag[pi], *P = W->st + (size_t)CKR_S_STRIDE * W->m.pair_step[pi] + CKR_S_CAND;
+        const double *T = Tc + 12 * (size_t)W->m.ix.col[pi], *P = W->st + (size_t)CKA_S_STRIDE * W->m.ix.step[pi] + CKA_S_CAND;
         double a[CKF_GROUP];
         for (int l = 0; l < CKF_GROUP; l++) {
             double e[3];
@@ -274,35 +233,35 @@ static double twin_cost(twin_t *W, const double *Tc) {
     }
     double t = 0.0;
     for (int u = 0; u < W->U; u++) {
-        const int p0 = W->m.step_pair[u];
-        double *st = W->st + (size_t)CKR_S_STRIDE * u;
-        ckf_step_cost(st, W->pr + (size_t)CKF_P_STRIDE * p0, W->si + (size_t)CKF_I_STRIDE * W->m.pair_sight[p0], W->m.pair_sight + p0,
-                      W->m.step_pair[u + 1] - p0);
-        t = t + st[CKR_S_COST];
+        const int p0 = W->m.ix.first[u];
+        double *st = W->st + (size_t)CKA_S_STRIDE * u;
+        ckf_step_cost(st, W->pr + (size_t)CKA_B_STRIDE * p0, W->si + (size_t)CKF_I_STRIDE * W->m.pair_sight[p0], W->m.pair_sight + p0,
+                      W->m.ix.first[u + 1] - p0);
+        t = t + st[CKA_S_COST];
     }
     return t;
 }
 
 static void twin_jacobian(twin_t *W, const double *Tm) {
     for (int g = 0; g < W->NS; g++) {
-        const int pi = W->m.sight_pair[g], k = W->m.pair_tag[pi];
-        const double *P = W->st + (size_t)CKR_S_STRIDE * W->m.pair_step[pi] + CKR_S_POSE;
-        double part[CKF_GROUP][NACC];
+        const int pi = W->m.sight_pair[g], k = W->m.ix.col[pi];
+        const double *P = W->st + (size_t)CKA_S_STRIDE * W->m.ix.step[pi] + CKA_S_POSE;
+        double part[CKF_GROUP][CKA_NACC];
         for (int l = 0; l < CKF_GROUP; l++) {
-            double e[3], J[3 * CKR_NJ];
-            for (int j = 0; j < NACC; j++) part[l][j] = 0.0;
+            double e[3], J[3 * CKA_NJ];
+            for (int j = 0; j < CKA_NACC; j++) part[l][j] = 0.0;
             ckf_jacobian(W->M + 12 * W->m.sight_cam[g], P, Tm + 12 * (size_t)k, l, W->bear + 3 * ((size_t)W->m.sight_bear[g] + l),
                          (unsigned)W->m.mask6[k], e, J);
-            ckr_accumulate_rows(part[l], part[l] + CKR_NH, e, J, 0, CKR_NJ);
+            ckr_accumulate_rows(part[l], part[l] + CKA_NH, e, J, 0, CKA_NJ);
         }
-        for (int j = 0; j < NACC; j++) W->si[(size_t)CKF_I_STRIDE * g + CKF_I_H + j] = (part[0][j] + part[2][j]) + (part[1][j] + part[3][j]);
+        for (int j = 0; j < CKA_NACC; j++) W->si[(size_t)CKF_I_STRIDE * g + CKF_I_H + j] = (part[0][j] + part[2][j]) + (part[1][j] + part[3][j]);
     }
     for (int pi = 0; pi < W->P; pi++)
-        ckf_pair_sum(W->pr + (size_t)CKF_P_STRIDE * pi, W->si + (size_t)CKF_I_STRIDE * W->m.pair_sight[pi], W->m.pair_sight[pi + 1] - W->m.pair_sight[pi]);
+        ckf_pair_sum(W->pr + (size_t)CKA_B_STRIDE * pi, W->si + (size_t)CKF_I_STRIDE * W->m.pair_sight[pi], W->m.pair_sight[pi + 1] - W->m.pair_sight[pi]);
 }
 
 static void accept_costs(twin_t *W) {
-    for (int pi = 0; pi < W->P; pi++) W->pr[(size_t)CKF_P_STRIDE * pi + CKF_P_COSTA] = W->pr[(size_t)CKF_P_STRIDE * pi + CKF_P_COST];
+    for (int pi = 0; pi < W->P; pi++) W->pr[(size_t)CKA_B_STRIDE * pi + CKA_B_COSTA] = W->pr[(size_t)CKA_B_STRIDE * pi + CKA_B_COST];
 }
 
 /* The reduced system S (packed lower triangle, CKF_LT) d = rhs, in place in dk.  Left-looking column Cholesky: entry (i, j) subtracts
@@ -348,8 +307,7 @@ int ck_fieldcal_refine_host(const ck_fieldcal_params_t *p, int32_t n_cams, const
     int ret = ck_fieldcal_plan(p, n_cams, records, n_steps, tag_index, problem, step_index, n_layout, fixed6, poses0, tag_sightings, &plan);
     if (ret != CK_OK) return ret;
     ck_fieldcal_result_start(problem, &plan, layout0, n_layout, res, layout_out, tag_rms);
-    for (int32_t j = 0; j < problem->n_steps; j++)
-        memcpy(poses_out + 12 * ((size_t)problem->step_offset + j), poses0 + 12 * (size_t)step_index[problem->step_offset + j], sizeof(double) * 12);
+    ck_cal_poses_start(problem, step_index, poses0, poses_out);
     if (plan.status == CK_CALIB_DEGENERATE) { ck_fieldcal_plan_free(&plan); return CK_OK; }
     twin_t W;
     memset(&W, 0, sizeof W);
@@ -358,74 +316,68 @@ int ck_fieldcal_refine_host(const ck_fieldcal_params_t *p, int32_t n_cams, const
     W.bear = bearings;
     const int N = 6 * W.T;
     double M[12 * CK_RIG_MAX_CAMS];
-    double *Tm = (double *)calloc((size_t)24 * (size_t)W.T + (size_t)CKF_HK * W.T + 2 * (size_t)N + CKF_LT(N, 0) + 1, sizeof(double));
-    W.st = (double *)calloc((size_t)CKR_S_STRIDE * (size_t)W.U + 1, sizeof(double));
-    W.pr = (double *)calloc((size_t)CKF_P_STRIDE * (size_t)W.P + 1, sizeof(double));
+    double *Tm = (double *)calloc((size_t)24 * (size_t)W.T + (size_t)CKA_HK * W.T + 2 * (size_t)N + CKF_LT(N, 0) + 1, sizeof(double));
+    W.st = (double *)calloc((size_t)CKA_S_STRIDE * (size_t)W.U + 1, sizeof(double));
+    W.pr = (double *)calloc((size_t)CKA_B_STRIDE * (size_t)W.P + 1, sizeof(double));
     W.si = (double *)calloc((size_t)CKF_I_STRIDE * (size_t)W.NS + 1, sizeof(double));
     int32_t *shared = (int32_t *)malloc(sizeof(int32_t) * ((size_t)W.U + 1));
     ret = CK_ENOMEM;
     if (!Tm || !W.st || !W.pr || !W.si || !shared) goto done;
     ret = CK_OK;
     {
-        double *Tc = Tm + 12 * (size_t)W.T, *Hk = Tc + 12 * (size_t)W.T, *dk = Hk + (size_t)CKF_HK * W.T, *rms = dk + N, *S = rms + N;
+        double *Tc = Tm + 12 * (size_t)W.T, *Hk = Tc + 12 * (size_t)W.T, *dk = Hk + (size_t)CKA_HK * W.T, *rms = dk + N, *S = rms + N;
         for (int c = 0; c < n_cams; c++) ck_rigcal_mount_in(mounts + c, M + 12 * c);
         W.M = M;
         for (int k = 0; k < W.T; k++) ck_fieldcal_tag_in(layout0 + W.m.ltag[k], Tm + 12 * (size_t)k);
         memcpy(Tc, Tm, sizeof(double) * 12 * (size_t)W.T);
-        for (int u = 0; u < W.U; u++) {
-            memcpy(W.st + (size_t)CKR_S_STRIDE * u + CKR_S_POSE, poses0 + 12 * (size_t)W.m.used[u], sizeof(double) * 12);
-            memcpy(W.st + (size_t)CKR_S_STRIDE * u + CKR_S_CAND, poses0 + 12 * (size_t)W.m.used[u], sizeof(double) * 12);
-        }
+        ck_cal_steps_seed(W.st, W.m.ix.used, W.U, poses0);
         const double cost0 = twin_cost(&W, Tc);
         accept_costs(&W);
         res->status = CK_CALIB_DEGENERATE;
         if (!ckc_finite(cost0)) goto done;
         ckc_lm_t lm;
-        ckr_lm_start(&lm, cost0);
+        ckc_lm_start(&lm, cost0, CKR_COST_FLOOR);
         while (lm.status < 0) {
             if (lm.need_jac) {
                 twin_jacobian(&W, Tm);
                 for (int k = 0; k < W.T; k++)
-                    for (int j = 0; j < CKF_HK; j++) Hk[CKF_HK * k + j] = ckf_tag_sum(W.pr, W.m.pairmap + (size_t)k * W.U, W.U, j);
+                    for (int j = 0; j < CKA_HK; j++) Hk[CKA_HK * k + j] = cka_col_sum(W.pr, W.m.ix.colmap + (size_t)k * W.U, W.U, j);
             }
             int solved = 1;
             for (int u = 0; u < W.U; u++)
-                if (!ckf_step_schur(W.st + (size_t)CKR_S_STRIDE * u, W.pr + (size_t)CKF_P_STRIDE * W.m.step_pair[u],
-                                    W.m.step_pair[u + 1] - W.m.step_pair[u], lm.lambda))
+                if (!cka_step_schur(W.st + (size_t)CKA_S_STRIDE * u, W.pr + (size_t)CKA_B_STRIDE * W.m.ix.first[u],
+                                    W.m.ix.first[u + 1] - W.m.ix.first[u], lm.lambda))
                     solved = 0;
             for (int tr = 0; tr < W.T; tr++)
                 for (int tk = 0; tk <= tr; tk++) { /* the steps that see both tags, once for the block's entries */
                     int ns = 0;
                     for (int u = 0; u < W.U; u++)
-                        if (W.m.pairmap[(size_t)tr * W.U + u] >= 0 && W.m.pairmap[(size_t)tk * W.U + u] >= 0) shared[ns++] = u;
+                        if (W.m.ix.colmap[(size_t)tr * W.U + u] >= 0 && W.m.ix.colmap[(size_t)tk * W.U + u] >= 0) shared[ns++] = u;
                     for (int r = 6 * tr; r < 6 * tr + 6; r++)
                         for (int k = 6 * tk; k < 6 * tk + 6 && k <= r; k++)
-                            S[CKF_LT(r, k)] = ckf_reduced_entry(W.pr, W.m.pairmap, W.m.mask6, Hk, W.U, shared, ns, lm.lambda, r, k);
+                            S[CKF_LT(r, k)] = cka_reduced_entry(W.pr, W.m.ix.colmap, W.m.mask6, Hk, W.U, shared, ns, lm.lambda, r, k);
                 }
-            for (int r = 0; r < N; r++) dk[r] = ckf_reduced_rhs(W.pr, W.m.pairmap, W.m.mask6, Hk, W.U, r);
+            for (int r = 0; r < N; r++) dk[r] = cka_reduced_rhs(W.pr, W.m.ix.colmap, W.m.mask6, Hk, W.U, r);
             double pred = 0.0, cost_new = 0.0;
             if (!reduced_solve(S, N, dk)) solved = 0;
             if (solved) {
-                pred = ckf_reduced_pred(W.m.mask6, Hk, N, lm.lambda, dk);
-                for (int k = 0; k < W.T; k++) ckf_tag_step(Tm + 12 * (size_t)k, dk + 6 * k, (unsigned)W.m.mask6[k], Tc + 12 * (size_t)k);
+                pred = cka_reduced_pred(W.m.mask6, Hk, N, lm.lambda, dk);
+                for (int k = 0; k < W.T; k++) ckc_rigid_step(Tm + 12 * (size_t)k, dk + 6 * k, (unsigned)W.m.mask6[k], Tc + 12 * (size_t)k);
                 for (int u = 0; u < W.U; u++)
-                    ckf_step_step(W.st + (size_t)CKR_S_STRIDE * u, W.pr + (size_t)CKF_P_STRIDE * W.m.step_pair[u], W.m.pair_tag + W.m.step_pair[u],
-                                  W.m.step_pair[u + 1] - W.m.step_pair[u], dk, lm.lambda);
-                for (int u = 0; u < W.U; u++) pred = pred + W.st[(size_t)CKR_S_STRIDE * u + CKR_S_PRED];
+                    cka_step_step(W.st + (size_t)CKA_S_STRIDE * u, W.pr + (size_t)CKA_B_STRIDE * W.m.ix.first[u], W.m.ix.col + W.m.ix.first[u],
+                                  W.m.ix.first[u + 1] - W.m.ix.first[u], dk, lm.lambda);
+                for (int u = 0; u < W.U; u++) pred = pred + W.st[(size_t)CKA_S_STRIDE * u + CKA_S_PRED];
                 cost_new = twin_cost(&W, Tc);
             }
-            if (ckr_lm_decide(&lm, solved, pred, cost_new, p->max_iters)) {
+            if (ckc_lm_decide(&lm, solved, pred, cost_new, p->max_iters, CKR_COST_FLOOR)) {
                 memcpy(Tm, Tc, sizeof(double) * 12 * (size_t)W.T);
                 for (int u = 0; u < W.U; u++)
-                    memcpy(W.st + (size_t)CKR_S_STRIDE * u + CKR_S_POSE, W.st + (size_t)CKR_S_STRIDE * u + CKR_S_CAND, sizeof(double) * 12);
+                    memcpy(W.st + (size_t)CKA_S_STRIDE * u + CKA_S_POSE, W.st + (size_t)CKA_S_STRIDE * u + CKA_S_CAND, sizeof(double) * 12);
                 accept_costs(&W);
             }
         }
-        for (int u = 0, j = 0; u < W.U; u++) {
-            while (step_index[problem->step_offset + j] != W.m.used[u]) j++;
-            memcpy(poses_out + 12 * ((size_t)problem->step_offset + j), W.st + (size_t)CKR_S_STRIDE * u + CKR_S_POSE, sizeof(double) * 12);
-        }
-        for (int k = 0; k < W.T; k++) rms[k] = ckf_tag_rms(W.pr, W.m.pairmap + (size_t)k * W.U, W.U, W.m.tag_ns[k]);
+        ck_cal_poses_finish(problem, step_index, W.m.ix.used, W.U, W.st, poses_out);
+        for (int k = 0; k < W.T; k++) rms[k] = cka_col_rms(W.pr, W.m.ix.colmap + (size_t)k * W.U, W.U, 4 * W.m.tag_ns[k]);
         ck_fieldcal_result_finish(&plan, layout0, Tm, rms, layout_out, tag_rms);
         res->status = lm.status; res->iters = lm.iters;
         res->cost0 = cost0; res->cost = lm.cost;

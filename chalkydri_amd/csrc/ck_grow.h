@@ -30,6 +30,15 @@ struct ck_dev_buf { // device memory through ck_malloc_dev: CK_POISON fill and g
     }
 };
 
+// reserve() for `bytes + pad` and the copy of `bytes` of host memory up on `stream`; `pad` is what a kernel may read past the end
+template <typename T>
+static inline int ck_upload(ck_dev_buf<T> &b, const void *src, size_t bytes, hipStream_t stream, size_t pad = 0) {
+    const int rc = b.reserve(bytes + pad);
+    if (rc != CK_OK) return rc;
+    if (bytes) CK_HIP(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, stream));
+    return CK_OK;
+}
+
 template <typename T>
 struct ck_pinned_buf { // pinned host memory
     T *p = nullptr;

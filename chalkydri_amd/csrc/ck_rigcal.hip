@@ -1,18 +1,19 @@
 // Mount calibration: the host half that drives the device.  Validates a call (ck_rigcal_check, before any device is
-// touched), decides per problem what ck_rigcal_host.c decides for the twin (used steps, gauge, connectivity), grows the workspace,
+// touched), decides per problem what ck_rigcal_host.c decides for the twin (used steps and views, gauge, connectivity), grows the workspace,
 // copies the capture and the starts over, runs k_rigcal on the handle's stream and brings results, mounts and poses back.
 #include <string.h>
 
 #include <vector>
 
+#include "ck_cal.h"
 #include "ck_rigcal.h"
 #include "ck_rigcal_math.h"
 
 static_assert(sizeof(ck_rigcal_params_t) == 24, "ck_rigcal_params_t layout");
 static_assert(sizeof(ck_rigcal_problem_t) == 8, "ck_rigcal_problem_t layout");
 static_assert(sizeof(ck_rigcal_result_t) == 592, "ck_rigcal_result_t layout");
-static_assert(sizeof(ck_rigcal_dev_problem) == 16, "ck_rigcal_dev_problem layout");
-static_assert(CKR_V_WG + 6 <= CKR_V_STRIDE && CKR_S_COST < CKR_S_STRIDE, "record layouts");
+static_assert(sizeof(ck_rigcal_dev_problem) == 32, "ck_rigcal_dev_problem layout");
+static_assert(CKA_B_WG + 6 <= CKA_B_STRIDE && CKA_S_COST < CKA_S_STRIDE, "record layouts");
 
 extern "C" int ck_rigcal_refine_batch(ck_handle_t *h, const ck_rigcal_params_t *p, int32_t n_cams, const ck_sqpnp_problem_t *records,
                                       int32_t n_steps, const ck_iso3_t *tags, int32_t n_tags_total, const double *bearings,
@@ -23,84 +24,117 @@ extern "C" int ck_rigcal_refine_batch(ck_handle_t *h, const ck_rigcal_params_t *
     int rc = ck_rigcal_check(p, n_cams, records, n_steps, tags, n_tags_total, bearings, n_bearings_total, problems, n, step_index,
                              n_index_total, mounts0);
     if (rc != CK_OK || n == 0) return rc;
-    std::vector<int32_t> tab, used;
+    std::vector<int32_t> tab, index;
     std::vector<double> world, mounts, steps;
     std::vector<ck_rigcal_plan_t> plans;
     std::vector<ck_rigcal_dev_problem> dprob;
-    size_t n_used = 0;
+    size_t n_used = 0, n_views = 0, n_index = 0;
     try {
         tab.resize(CKR_TAB * (size_t)n_cams * (size_t)n_steps + 1);
         world.resize(12 * (size_t)n_tags_total + 1);
-        used.resize((size_t)n_index_total + 1);
         plans.resize((size_t)n);
         dprob.resize((size_t)n);
         mounts.assign((size_t)12 * CK_RIG_MAX_CAMS * (size_t)n, 0.0);
         ck_rigcal_table(n_cams, records, n_steps, tags, n_tags_total, tab.data(), world.data());
         for (int32_t i = 0; i < n; i++) {
             const ck_rigcal_problem_t &q = problems[i];
-            // (problems may share a run of step_index: every problem gets its own run of used steps)
-            if (n_used + (size_t)q.n_steps + 1 > used.size()) used.resize(n_used + (size_t)q.n_steps + 1);
-            ck_rigcal_plan(p, n_cams, tab.data(), n_steps, &q, step_index, poses0, used.data() + n_used, &plans[i]);
+            // (problems may share a run of step_index: every problem gets an index of its own)
+            index.resize(n_index + cka_index_size((size_t)q.n_steps, (size_t)n_cams * (size_t)q.n_steps, (size_t)n_cams) + 1);
+            ck_rigcal_plan(p, n_cams, tab.data(), n_steps, &q, step_index, poses0, index.data() + n_index, &plans[i]);
             ck_rigcal_result_start(&q, &plans[i], n_cams, mounts0, &results[i]);
-            for (int32_t j = 0; j < q.n_steps; j++)
-                memcpy(poses_out + 12 * ((size_t)q.step_offset + j), poses0 + 12 * (size_t)step_index[q.step_offset + j], sizeof(double) * 12);
+            ck_cal_poses_start(&q, step_index, poses0, poses_out);
             for (int c = 0; c < n_cams; c++) ck_rigcal_mount_in(mounts0 + c, mounts.data() + 12 * ((size_t)CK_RIG_MAX_CAMS * i + c));
-            dprob[i].used_off = (int32_t)n_used;
-            dprob[i].n_used = plans[i].status == CK_CALIB_DEGENERATE ? 0 : plans[i].n_used;
-            dprob[i].mask = plans[i].mask;
-            n_used += (size_t)dprob[i].n_used;
-            if (n_used * (size_t)n_cams >= ((size_t)1 << 31) / CKR_V_STRIDE) return CK_ECAPACITY;
+            ck_rigcal_dev_problem &d = dprob[i];
+            d.index_off = (int64_t)n_index; d.step_off = (int32_t)n_used; d.view_off = (int32_t)n_views;
+            d.n_used = d.n_views = 0;
+            d.mask = plans[i].mask;
+            if (plans[i].status == CK_CALIB_DEGENERATE) continue;
+            d.n_used = plans[i].n_used; d.n_views = plans[i].n_views;
+            n_index += cka_index_size((size_t)d.n_used, (size_t)d.n_views, (size_t)n_cams);
+            n_used += (size_t)d.n_used; n_views += (size_t)d.n_views;
+            if (n_used * (size_t)n_cams >= ((size_t)1 << 31) / CKA_B_STRIDE) return CK_ECAPACITY;
         }
-        steps.assign((size_t)CKR_S_STRIDE * (n_used + 1), 0.0);
+        index.resize(n_index + 1);
+        steps.assign((size_t)CKA_S_STRIDE * (n_used + 1), 0.0);
         for (int32_t i = 0; i < n; i++)
-            for (int32_t u = 0; u < dprob[i].n_used; u++) {
-                double *st = steps.data() + (size_t)CKR_S_STRIDE * ((size_t)dprob[i].used_off + u);
-                memcpy(st + CKR_S_POSE, poses0 + 12 * (size_t)used[(size_t)dprob[i].used_off + u], sizeof(double) * 12);
-                memcpy(st + CKR_S_CAND, st + CKR_S_POSE, sizeof(double) * 12);
-            }
+            ck_cal_steps_seed(steps.data() + (size_t)CKA_S_STRIDE * (size_t)dprob[i].step_off, index.data() + dprob[i].index_off, dprob[i].n_used, poses0);
     } catch (...) {
         return CK_ENOMEM;
     }
     CK_HIP(hipSetDevice(h->device));
     if (!ck_workspace(h->rigcal)) return CK_ENOMEM;
     ck_rigcal_ws &W = *h->rigcal;
-    const size_t tab_bytes = sizeof(int32_t) * CKR_TAB * (size_t)n_cams * (size_t)n_steps, used_bytes = sizeof(int32_t) * (n_used + 1);
-    const size_t world_bytes = sizeof(double) * 12 * (size_t)n_tags_total, bear_bytes = sizeof(double) * 3 * (size_t)n_bearings_total;
-    const size_t mount_bytes = sizeof(double) * mounts.size(), step_bytes = sizeof(double) * CKR_S_STRIDE * (n_used + 1);
-    rc = W.d_prob.reserve(sizeof(ck_rigcal_dev_problem) * (size_t)n);
-    if (rc == CK_OK) rc = W.d_tab.reserve(tab_bytes + 4);
-    if (rc == CK_OK) rc = W.d_used.reserve(used_bytes);
-    if (rc == CK_OK) rc = W.d_world.reserve(world_bytes + 8);
-    if (rc == CK_OK) rc = W.d_bear.reserve(bear_bytes + 8);
-    if (rc == CK_OK) rc = W.d_mounts.reserve(mount_bytes);
-    if (rc == CK_OK) rc = W.d_steps.reserve(step_bytes);
-    if (rc == CK_OK) rc = W.d_views.reserve(sizeof(double) * CKR_V_STRIDE * (n_used * (size_t)n_cams + 1));
-    if (rc == CK_OK) rc = W.d_res.reserve(sizeof(ck_rigcal_result_t) * (size_t)n);
+    const size_t mount_bytes = sizeof(double) * mounts.size(), step_bytes = sizeof(double) * steps.size();
+    const size_t res_bytes = sizeof(ck_rigcal_result_t) * (size_t)n;
+    rc = ck_upload(W.d_prob, dprob.data(), sizeof(ck_rigcal_dev_problem) * (size_t)n, h->stream);
+    if (rc == CK_OK) rc = ck_upload(W.d_tab, tab.data(), sizeof(int32_t) * CKR_TAB * (size_t)n_cams * (size_t)n_steps, h->stream, 4);
+    if (rc == CK_OK) rc = ck_upload(W.d_index, index.data(), sizeof(int32_t) * index.size(), h->stream);
+    if (rc == CK_OK) rc = ck_upload(W.d_world, world.data(), sizeof(double) * 12 * (size_t)n_tags_total, h->stream, 8);
+    if (rc == CK_OK) rc = ck_upload(W.d_bear, bearings, sizeof(double) * 3 * (size_t)n_bearings_total, h->stream, 8);
+    if (rc == CK_OK) rc = ck_upload(W.d_mounts, mounts.data(), mount_bytes, h->stream);
+    if (rc == CK_OK) rc = ck_upload(W.d_steps, steps.data(), step_bytes, h->stream);
+    if (rc == CK_OK) rc = W.d_views.reserve(sizeof(double) * CKA_B_STRIDE * (n_views + 1));
+    if (rc == CK_OK) rc = ck_upload(W.d_res, results, res_bytes, h->stream);
     if (rc != CK_OK) return rc;
-    CK_HIP(hipMemcpyAsync(W.d_prob, dprob.data(), sizeof(ck_rigcal_dev_problem) * (size_t)n, hipMemcpyHostToDevice, h->stream));
-    if (tab_bytes) CK_HIP(hipMemcpyAsync(W.d_tab, tab.data(), tab_bytes, hipMemcpyHostToDevice, h->stream));
-    CK_HIP(hipMemcpyAsync(W.d_used, used.data(), used_bytes, hipMemcpyHostToDevice, h->stream));
-    if (world_bytes) CK_HIP(hipMemcpyAsync(W.d_world, world.data(), world_bytes, hipMemcpyHostToDevice, h->stream));
-    if (bear_bytes) CK_HIP(hipMemcpyAsync(W.d_bear, bearings, bear_bytes, hipMemcpyHostToDevice, h->stream));
-    CK_HIP(hipMemcpyAsync(W.d_mounts, mounts.data(), mount_bytes, hipMemcpyHostToDevice, h->stream));
-    CK_HIP(hipMemcpyAsync(W.d_steps, steps.data(), step_bytes, hipMemcpyHostToDevice, h->stream));
-    CK_HIP(hipMemcpyAsync(W.d_res, results, sizeof(ck_rigcal_result_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
-    rc = ck_launch_rigcal(h->stream, p->max_iters, n_cams, n_steps, W.d_prob, n, W.d_tab, W.d_used, W.d_world, W.d_bear, W.d_mounts, W.d_steps,
+    rc = ck_launch_rigcal(h->stream, p->max_iters, n_cams, n_steps, W.d_prob, n, W.d_tab, W.d_index, W.d_world, W.d_bear, W.d_mounts, W.d_steps,
                           W.d_views, W.d_res);
     if (rc != CK_OK) return rc;
-    CK_HIP(hipMemcpyAsync(results, W.d_res, sizeof(ck_rigcal_result_t) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    CK_HIP(hipMemcpyAsync(results, W.d_res, res_bytes, hipMemcpyDeviceToHost, h->stream));
     CK_HIP(hipMemcpyAsync(mounts.data(), W.d_mounts, mount_bytes, hipMemcpyDeviceToHost, h->stream));
     CK_HIP(hipMemcpyAsync(steps.data(), W.d_steps, step_bytes, hipMemcpyDeviceToHost, h->stream));
     CK_HIP(hipStreamSynchronize(h->stream));
     for (int32_t i = 0; i < n; i++) {
         if (results[i].status == CK_CALIB_DEGENERATE) continue;
-        const ck_rigcal_problem_t &q = problems[i];
         ck_rigcal_result_finish(&plans[i], n_cams, mounts0, mounts.data() + (size_t)12 * CK_RIG_MAX_CAMS * i, &results[i]);
-        for (int32_t u = 0, j = 0; u < dprob[i].n_used; u++) {
-            const size_t at = (size_t)dprob[i].used_off + u;
-            while (step_index[q.step_offset + j] != used[at]) j++;
-            memcpy(poses_out + 12 * ((size_t)q.step_offset + j), steps.data() + (size_t)CKR_S_STRIDE * at + CKR_S_POSE, sizeof(double) * 12);
+        ck_cal_poses_finish(&problems[i], step_index, index.data() + dprob[i].index_off, dprob[i].n_used,
+                            steps.data() + (size_t)CKA_S_STRIDE * (size_t)dprob[i].step_off, poses_out);
+    }
+    return CK_OK;
+}
+
+int ck_cal_starts_solve(ck_handle_t *h, int32_t n_cams, const ck_sqpnp_problem_t *records, int32_t n_steps, const ck_iso3_t *tags,
+                        int32_t n_tags_total, const double *bearings, int32_t n_bearings_total, const double *gyro,
+                        const ck_rigcal_problem_t *problems, int32_t n, const int32_t *step_index, const ck_iso3_t *mounts, ck_cal_starts &s) {
+    std::vector<ck_sqpnp_problem_t> rec;
+    std::vector<ck_rig_result_t> rig;
+    try {
+        rec.assign(records, records + (size_t)n_cams * (size_t)n_steps);
+        rig.resize((size_t)n_steps + 1);
+        s.poses0.assign(12 * ((size_t)n_steps + 1), 0.0);
+        s.prob.resize((size_t)n);
+    } catch (...) {
+        return CK_ENOMEM;
+    }
+    for (int c = 0; c < n_cams; c++)
+        for (int32_t t = 0; t < n_steps; t++) rec[(size_t)c * n_steps + t].robot_to_cam = mounts[c];
+    ck_rig_params_t rp;
+    ck_rig_params_default(&rp);
+    rp.sign_change_error = 0.0;
+    const int rc = ck_rig_solve_batch(h, &rp, n_cams, rec.data(), n_steps, tags, n_tags_total, bearings, n_bearings_total, gyro, rig.data());
+    if (rc != CK_OK) return rc;
+    for (int32_t t = 0; t < n_steps; t++) { // world -> robot = (rot^T, -rot^T pos)
+        const ck_rig_result_t &r = rig[t];
+        double *P = s.poses0.data() + 12 * (size_t)t;
+        for (int i = 0; i < 3; i++) {
+            for (int j = 0; j < 3; j++) P[3 * i + j] = r.rot[3 * j + i];
+            P[9 + i] = -(r.rot[i] * r.pos[0] + r.rot[3 + i] * r.pos[1] + r.rot[6 + i] * r.pos[2]);
         }
+    }
+    try {
+        for (int32_t i = 0; i < n; i++) {
+            s.prob[i].step_offset = (int32_t)s.index.size();
+            for (int32_t j = 0; j < problems[i].n_steps; j++) {
+                const int32_t t = step_index[problems[i].step_offset + j];
+                if (!rig[t].valid) continue;
+                s.index.push_back(t);
+                s.where.push_back(problems[i].step_offset + j);
+            }
+            s.prob[i].n_steps = (int32_t)s.index.size() - s.prob[i].step_offset;
+        }
+        s.index.push_back(0);
+        s.poses.assign(12 * (s.where.size() + 1), 0.0); // every problem has a run of its own here, also where the caller's problems share one
+    } catch (...) {
+        return CK_ENOMEM;
     }
     return CK_OK;
 }
@@ -114,60 +148,13 @@ extern "C" int ck_rig_calibrate_batch(ck_handle_t *h, const ck_rigcal_params_t *
     int rc = ck_rigcal_check(p, n_cams, records, n_steps, tags, n_tags_total, bearings, n_bearings_total, problems, n, step_index,
                              n_index_total, mounts0);
     if (rc != CK_OK || n == 0) return rc;
-    std::vector<ck_sqpnp_problem_t> rec;
-    std::vector<ck_rig_result_t> rig;
-    std::vector<ck_rigcal_problem_t> prob2;
-    std::vector<int32_t> index2, where;
-    std::vector<double> poses0, poses2;
-    try {
-        rec.assign(records, records + (size_t)n_cams * (size_t)n_steps);
-        rig.resize((size_t)n_steps + 1);
-        poses0.assign(12 * ((size_t)n_steps + 1), 0.0);
-        prob2.resize((size_t)n);
-    } catch (...) {
-        return CK_ENOMEM;
-    }
-    // the starts: the rig solver with the start mounts and no gyro penalty over the whole capture, once
-    for (int c = 0; c < n_cams; c++)
-        for (int32_t s = 0; s < n_steps; s++) rec[(size_t)c * n_steps + s].robot_to_cam = mounts0[c];
-    ck_rig_params_t rp;
-    ck_rig_params_default(&rp);
-    rp.sign_change_error = 0.0;
-    rc = ck_rig_solve_batch(h, &rp, n_cams, rec.data(), n_steps, tags, n_tags_total, bearings, n_bearings_total, gyro, rig.data());
+    ck_cal_starts s;
+    rc = ck_cal_starts_solve(h, n_cams, records, n_steps, tags, n_tags_total, bearings, n_bearings_total, gyro, problems, n, step_index, mounts0, s);
     if (rc != CK_OK) return rc;
-    for (int32_t s = 0; s < n_steps; s++) { // world -> robot = (rot^T, -rot^T pos)
-        const ck_rig_result_t &r = rig[s];
-        double *P = poses0.data() + 12 * (size_t)s;
-        for (int i = 0; i < 3; i++) {
-            for (int j = 0; j < 3; j++) P[3 * i + j] = r.rot[3 * j + i];
-            P[9 + i] = -(r.rot[i] * r.pos[0] + r.rot[3 + i] * r.pos[1] + r.rot[6 + i] * r.pos[2]);
-        }
-    }
-    // a step without a start is left out of every problem
-    try {
-        for (int32_t i = 0; i < n; i++) {
-            prob2[i].step_offset = (int32_t)index2.size();
-            for (int32_t j = 0; j < problems[i].n_steps; j++) {
-                const int32_t s = step_index[problems[i].step_offset + j];
-                if (!rig[s].valid) continue;
-                index2.push_back(s);
-                where.push_back(problems[i].step_offset + j);
-            }
-            prob2[i].n_steps = (int32_t)index2.size() - prob2[i].step_offset;
-        }
-        index2.push_back(0);
-        poses2.assign(12 * (where.size() + 1), 0.0); // every problem has a run of its own here, also where the caller's problems share one
-    } catch (...) {
-        return CK_ENOMEM;
-    }
-    rc = ck_rigcal_refine_batch(h, p, n_cams, records, n_steps, tags, n_tags_total, bearings, n_bearings_total, prob2.data(), n, index2.data(),
-                                (int32_t)where.size(), mounts0, poses0.data(), results, poses2.data());
+    rc = ck_rigcal_refine_batch(h, p, n_cams, records, n_steps, tags, n_tags_total, bearings, n_bearings_total, s.prob.data(), n, s.index.data(),
+                                s.n_index(), mounts0, s.poses0.data(), results, s.poses.data());
     if (rc != CK_OK) return rc;
-    for (int32_t i = 0; i < n; i++) {
-        results[i].n_steps = problems[i].n_steps;
-        memset(poses_out + 12 * (size_t)problems[i].step_offset, 0, sizeof(double) * 12 * (size_t)problems[i].n_steps);
-    }
-    for (size_t k = 0; k < where.size(); k++) memcpy(poses_out + 12 * (size_t)where[k], poses2.data() + 12 * k, sizeof(double) * 12);
+    ck_cal_starts_finish(s, problems, n, results, poses_out);
     return CK_OK;
 }
 

@@ -10,20 +10,21 @@ extern "C" {
 #endif
 /* What the host decides about one problem before anything is solved */
 typedef struct ck_rigcal_plan {
-    int32_t n_used;                     /* used steps, their capture numbers in used[] */
+    int32_t n_used;                     /* used steps */
     int32_t n_points;                   /* of the used steps */
     int32_t cam_points[CK_RIG_MAX_CAMS];
     uint64_t mask;                      /* fixed_mask, and all six bits of every camera without a point in the used steps */
     int32_t status;                     /* -1: to be solved; CK_CALIB_DEGENERATE */
-    int32_t pad;
+    int32_t n_views;                    /* (used step, camera) pairs with points: the blocks of the index */
 } ck_rigcal_plan_t;
 /* Internal (not part of the C ABI in chalkydri_hip.h).  The arrays are the host's and have passed ck_rigcal_check. */
 /* the capture's view table tab[n_cams * n_steps][3] (first world point, first bearing, points) and the tags' corners world[4 * n_tags_total][3] */
 void ck_rigcal_table(int32_t n_cams, const ck_sqpnp_problem_t *records, int32_t n_steps, const ck_iso3_t *tags, int32_t n_tags_total,
                      int32_t *tab, double *world);
-/* used[problem->n_steps] and the plan of one problem; poses0 [n_steps][12] */
+/* the plan of one problem and its arrowhead index (ck_cal_math.h: cka_index_at(index, n_used, n_views), columns = cameras, blocks =
+ * views); index has room for cka_index_size(problem->n_steps, n_cams * problem->n_steps, n_cams); poses0 [n_steps][12] */
 void ck_rigcal_plan(const ck_rigcal_params_t *p, int32_t n_cams, const int32_t *tab, int32_t n_steps, const ck_rigcal_problem_t *problem,
-                    const int32_t *step_index, const double *poses0, int32_t *used, ck_rigcal_plan_t *plan);
+                    const int32_t *step_index, const double *poses0, int32_t *index, ck_rigcal_plan_t *plan);
 /* robot_to_cam (A, b) <-> the solver's mount M[12] = (A row-major, o = -A^T b) */
 void ck_rigcal_mount_in(const ck_iso3_t *iso, double *M);
 /* (w, x, y, z), any length > 0 -> R row-major; R -> the unit quaternion with w >= 0, by the largest of the four squared components */

@@ -1,7 +1,9 @@
 /* Mount calibration, the half that needs no device: the checks every entry point shares, what is decided about a
  * problem before it is solved (which steps count, the gauge, the co-visibility graph), the conversions at the ABI's boundary and
- * ck_rigcal_refine_host, the one-thread twin of k_rigcal.hip.  The arithmetic of the refinement is ck_rigcal_math.h's, compiled into
- * both; this file walks views and points the way the kernel's lane groups do, so that the two return the same bytes. */
+ * ck_rigcal_refine_host, the one-thread twin of k_rigcal.hip.  The arithmetic of the refinement is ck_rigcal_math.h's and ck_cal_math.h's,
+ * compiled into both; this file walks views and points the way the kernel's lane groups do, so that the two return the same bytes.
+ * What the field calibration does the same way on the host is ck_cal_host.c's. */
+#include "ck_cal_c.h"
 #include "ck_rigcal_c.h"
 #include "ck_rigcal_math.h"
 #include <stdlib.h>
@@ -16,49 +18,16 @@ void ck_rigcal_params_default(ck_rigcal_params_t *p) {
     p->max_iters = 100; p->min_steps = 3; p->min_cams_per_step = 2;
 }
 
-static int iso_finite(const ck_iso3_t *t) {
-    for (int k = 0; k < 3; k++)
-        if (!ckc_finite(t->t[k])) return 0;
-    for (int k = 0; k < 4; k++)
-        if (!ckc_finite(t->q[k])) return 0;
-    return t->q[0] * t->q[0] + t->q[1] * t->q[1] + t->q[2] * t->q[2] + t->q[3] * t->q[3] > 0.0;
-}
-
 int ck_rigcal_check(const ck_rigcal_params_t *p, int32_t n_cams, const ck_sqpnp_problem_t *records, int32_t n_steps, const ck_iso3_t *tags,
                     int32_t n_tags_total, const double *bearings, int32_t n_bearings_total, const ck_rigcal_problem_t *problems,
                     int32_t n_problems, const int32_t *step_index, int32_t n_index_total, const ck_iso3_t *mounts0) {
-    if (!p || !records || !problems || !step_index || !mounts0) return CK_EINVAL;
-    if ((!tags && n_tags_total != 0) || (!bearings && n_bearings_total != 0)) return CK_EINVAL;
-    if (n_cams < 1 || n_cams > CK_RIG_MAX_CAMS) return CK_EINVAL;
-    if (n_steps < 0 || n_tags_total < 0 || n_bearings_total < 0 || n_problems < 0 || n_index_total < 0) return CK_EINVAL;
-    if (n_tags_total > 0x0FFFFFFF || (int64_t)n_cams * n_steps > 0x0FFFFFFF) return CK_EINVAL;
-    for (int64_t i = 0; i < (int64_t)n_cams * n_steps; i++) {
-        const ck_sqpnp_problem_t *r = records + i;
-        if (r->n_tags < 0 || r->n_bearings < 0 || r->tag_offset < 0 || r->bearing_offset < 0) return CK_EINVAL;
-        if ((int64_t)r->tag_offset + r->n_tags > n_tags_total || (int64_t)r->bearing_offset + r->n_bearings > n_bearings_total) return CK_EINVAL;
-    }
+    if (!p) return CK_EINVAL;
+    const int rc = ck_cal_check(n_cams, records, n_steps, tags, n_tags_total, bearings, n_bearings_total, problems, n_problems, step_index,
+                                n_index_total, mounts0, p->max_iters, p->min_steps, p->min_cams_per_step);
+    if (rc != CK_OK) return rc;
     for (int64_t i = 0; i < (int64_t)n_cams * n_steps; i++)
-        if ((int64_t)4 * records[i].n_tags != records[i].n_bearings) return CK_EINVAL;
-    for (int32_t i = 0; i < n_problems; i++) {
-        const ck_rigcal_problem_t *q = problems + i;
-        if (q->n_steps < 0 || q->step_offset < 0 || (int64_t)q->step_offset + q->n_steps > n_index_total) return CK_EINVAL;
-        for (int32_t j = 0; j < q->n_steps; j++) {
-            const int32_t s = step_index[q->step_offset + j];
-            if (s < 0 || s >= n_steps || (j > 0 && s <= step_index[q->step_offset + j - 1])) return CK_EINVAL;
-        }
-    }
-    if (p->max_iters < 1 || p->max_iters > 10000) return CK_EINVAL;
-    if (p->min_steps < 1) return CK_EINVAL;
-    if (p->min_cams_per_step < 2) return CK_EINVAL;
-    for (int64_t i = 0; i < (int64_t)n_cams * n_steps; i++) {
-        const ck_sqpnp_problem_t *r = records + i;
-        for (int32_t t = 0; t < r->n_tags; t++)
-            if (!iso_finite(tags + r->tag_offset + t)) return CK_EINVAL;
-        for (int64_t j = 3 * (int64_t)r->bearing_offset; j < 3 * ((int64_t)r->bearing_offset + r->n_bearings); j++)
-            if (!ckc_finite(bearings[j])) return CK_EINVAL;
-    }
-    for (int32_t c = 0; c < n_cams; c++)
-        if (!iso_finite(mounts0 + c)) return CK_EINVAL;
+        for (int32_t t = 0; t < records[i].n_tags; t++)
+            if (!ck_cal_iso_finite(tags + records[i].tag_offset + t)) return CK_EINVAL;
     int gauge = 0;
     for (int32_t c = 0; c < n_cams && !gauge; c++) {
         if (((p->fixed_mask >> (6 * c)) & 63u) != 63u) continue;
@@ -117,13 +86,8 @@ void ck_rigcal_table(int32_t n_cams, const ck_sqpnp_problem_t *records, int32_t 
     }
 }
 
-static int find(int *parent, int i) {
-    while (parent[i] != i) i = parent[i] = parent[parent[i]];
-    return i;
-}
-
 void ck_rigcal_plan(const ck_rigcal_params_t *p, int32_t n_cams, const int32_t *tab, int32_t n_steps, const ck_rigcal_problem_t *problem,
-                    const int32_t *step_index, const double *poses0, int32_t *used, ck_rigcal_plan_t *plan) {
+                    const int32_t *step_index, const double *poses0, int32_t *index, ck_rigcal_plan_t *plan) {
     int parent[CK_RIG_MAX_CAMS], anchored[CK_RIG_MAX_CAMS];
     memset(plan, 0, sizeof *plan);
     plan->status = -1;
@@ -133,18 +97,31 @@ void ck_rigcal_plan(const ck_rigcal_params_t *p, int32_t n_cams, const int32_t *
         int seen = 0, first = -1;
         for (int c = 0; c < n_cams; c++) seen += CKR_NPTS(tab, n_steps, c, s) > 0;
         if (seen < p->min_cams_per_step) continue;
-        used[plan->n_used++] = s;
+        index[plan->n_used++] = s; /* (the index starts with the used steps, whatever their number) */
+        plan->n_views += seen;
         for (int c = 0; c < n_cams; c++) {
             const int32_t k = CKR_NPTS(tab, n_steps, c, s);
             if (k <= 0) continue;
             plan->cam_points[c] += k;
             plan->n_points += k;
             if (first < 0) first = c;
-            else parent[find(parent, c)] = find(parent, first);
+            else parent[ck_cal_find(parent, c)] = ck_cal_find(parent, first);
         }
         for (int i = 0; i < 12; i++)
             if (!ckc_finite(poses0[12 * (size_t)s + i])) plan->status = CK_CALIB_DEGENERATE;
     }
+    /* the views, step by step in camera order */
+    const cka_index_t x = cka_index_at(index, (size_t)plan->n_used, (size_t)plan->n_views);
+    int32_t *first = (int32_t *)x.first, *col = (int32_t *)x.col, *step = (int32_t *)x.step, *colmap = (int32_t *)x.colmap, nv = 0;
+    for (int32_t u = 0; u < plan->n_used; u++) {
+        first[u] = nv;
+        for (int c = 0; c < n_cams; c++) {
+            const int on = CKR_NPTS(tab, n_steps, c, x.used[u]) > 0;
+            colmap[(size_t)c * plan->n_used + u] = on ? nv : -1;
+            if (on) { col[nv] = c; step[nv] = u; nv++; }
+        }
+    }
+    first[plan->n_used] = nv;
     plan->mask = p->fixed_mask;
     for (int c = 0; c < n_cams; c++)
         if (plan->cam_points[c] == 0) plan->mask |= CK_RIGCAL_FIX_CAMERA(c);
@@ -152,9 +129,9 @@ void ck_rigcal_plan(const ck_rigcal_params_t *p, int32_t n_cams, const int32_t *
     /* every camera that moves hangs on one that does not */
     for (int c = 0; c < n_cams; c++) anchored[c] = 0;
     for (int c = 0; c < n_cams; c++)
-        if (plan->cam_points[c] > 0 && ((p->fixed_mask >> (6 * c)) & 63u) == 63u) anchored[find(parent, c)] = 1;
+        if (plan->cam_points[c] > 0 && ((p->fixed_mask >> (6 * c)) & 63u) == 63u) anchored[ck_cal_find(parent, c)] = 1;
     for (int c = 0; c < n_cams; c++)
-        if (plan->cam_points[c] > 0 && ((p->fixed_mask >> (6 * c)) & 63u) != 63u && !anchored[find(parent, c)]) plan->status = CK_CALIB_DEGENERATE;
+        if (plan->cam_points[c] > 0 && ((p->fixed_mask >> (6 * c)) & 63u) != 63u && !anchored[ck_cal_find(parent, c)]) plan->status = CK_CALIB_DEGENERATE;
 }
 
 void ck_rigcal_result_start(const ck_rigcal_problem_t *problem, const ck_rigcal_plan_t *plan, int32_t n_cams, const ck_iso3_t *mounts0,
@@ -183,22 +160,22 @@ int ck_rigcal_jacobian(const ck_iso3_t *mount, const double *pose, const double 
     if (!mount || !pose || !world_xyz || !bearings || !r_out || !J_out || n < 0) return CK_EINVAL;
     double M[12];
     ck_rigcal_mount_in(mount, M);
-    for (int32_t i = 0; i < n; i++) ckr_jacobian(M, pose, world_xyz + 3 * (size_t)i, bearings + 3 * (size_t)i, fixed6 & 63u, r_out + 3 * (size_t)i, J_out + 3 * CKR_NJ * (size_t)i);
+    for (int32_t i = 0; i < n; i++) ckr_jacobian(M, pose, world_xyz + 3 * (size_t)i, bearings + 3 * (size_t)i, fixed6 & 63u, r_out + 3 * (size_t)i, J_out + 3 * CKA_NJ * (size_t)i);
     return CK_OK;
 }
 
 /* ---- the twin ---------------------------------------------------------------------------------------------------------------- */
-#define NACC (CKR_NH + CKR_NJ)
 typedef struct {
-    const int32_t *tab, *used;
+    cka_index_t x;
+    const int32_t *tab;
     const double *world, *bear;
-    int n, n_cams, U;
+    int n, U, P;
     double *st, *vw;
-    double part[CKR_GROUP][NACC];
+    double part[CKR_GROUP][CKA_NACC];
 } twin_t;
 
 /* the xor butterfly 8, 4, 2, 1 of a group's partial sums, as its lane 0 sees it */
-static void butterfly(double (*part)[NACC], int n) {
+static void butterfly(double (*part)[CKA_NACC], int n) {
     for (int m = CKR_GROUP / 2; m >= 1; m >>= 1)
         for (int l = 0; l < m; l++)
             for (int j = 0; j < n; j++) part[l][j] = part[l][j] + part[l + m][j];
@@ -207,55 +184,49 @@ static void butterfly(double (*part)[NACC], int n) {
 /* the candidate's cost: per view by lanes and butterfly, per step the views in camera order, then the steps in order */
 static double twin_cost(twin_t *T, const double *Mc) {
     for (int u = 0; u < T->U; u++) {
-        const int s = T->used[u];
-        double *st = T->st + (size_t)CKR_S_STRIDE * u, cs = 0.0;
-        for (int c = 0; c < T->n_cams; c++) {
-            const int32_t *tb = T->tab + ((size_t)c * T->n + s) * CKR_TAB;
-            if (tb[2] <= 0) continue;
-            double *V = T->vw + (size_t)CKR_V_STRIDE * ((size_t)u * T->n_cams + c);
+        double *st = T->st + (size_t)CKA_S_STRIDE * u, cs = 0.0;
+        for (int v = T->x.first[u]; v < T->x.first[u + 1]; v++) {
+            const int c = T->x.col[v];
+            const int32_t *tb = T->tab + ((size_t)c * T->n + T->x.used[u]) * CKR_TAB;
             for (int l = 0; l < CKR_GROUP; l++) {
                 double a = 0.0, e[3];
                 for (int i = l; i < tb[2]; i += CKR_GROUP) {
-                    ckr_residual(Mc + 12 * c, st + CKR_S_CAND, T->world + 3 * ((size_t)tb[0] + i), T->bear + 3 * ((size_t)tb[1] + i), e);
+                    ckr_residual(Mc + 12 * c, st + CKA_S_CAND, T->world + 3 * ((size_t)tb[0] + i), T->bear + 3 * ((size_t)tb[1] + i), e);
                     a = a + ((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
                 }
                 T->part[l][0] = a;
             }
             butterfly(T->part, 1);
-            V[CKR_V_COST] = T->part[0][0];
-            cs = cs + V[CKR_V_COST];
+            T->vw[(size_t)CKA_B_STRIDE * v + CKA_B_COST] = T->part[0][0];
+            cs = cs + T->part[0][0];
         }
-        st[CKR_S_COST] = cs;
+        st[CKA_S_COST] = cs;
     }
     double t = 0.0;
-    for (int u = 0; u < T->U; u++) t = t + T->st[(size_t)CKR_S_STRIDE * u + CKR_S_COST];
+    for (int u = 0; u < T->U; u++) t = t + T->st[(size_t)CKA_S_STRIDE * u + CKA_S_COST];
     return t;
 }
 
-static void twin_jacobian(twin_t *T, const double *M, uint64_t mask) {
-    for (int u = 0; u < T->U; u++) {
-        const int s = T->used[u];
-        const double *st = T->st + (size_t)CKR_S_STRIDE * u;
-        for (int c = 0; c < T->n_cams; c++) {
-            const int32_t *tb = T->tab + ((size_t)c * T->n + s) * CKR_TAB;
-            if (tb[2] <= 0) continue;
-            for (int l = 0; l < CKR_GROUP; l++) {
-                double e[3], J[3 * CKR_NJ];
-                for (int j = 0; j < NACC; j++) T->part[l][j] = 0.0;
-                for (int i = l; i < tb[2]; i += CKR_GROUP) {
-                    ckr_jacobian(M + 12 * c, st + CKR_S_POSE, T->world + 3 * ((size_t)tb[0] + i), T->bear + 3 * ((size_t)tb[1] + i),
-                                 (unsigned)((mask >> (6 * c)) & 63u), e, J);
-                    ckr_accumulate_rows(T->part[l], T->part[l] + CKR_NH, e, J, 0, CKR_NJ);
-                }
+static void twin_jacobian(twin_t *T, const double *M, const int32_t *mask6) {
+    for (int v = 0; v < T->P; v++) {
+        const int c = T->x.col[v];
+        const int32_t *tb = T->tab + ((size_t)c * T->n + T->x.used[T->x.step[v]]) * CKR_TAB;
+        const double *st = T->st + (size_t)CKA_S_STRIDE * T->x.step[v];
+        for (int l = 0; l < CKR_GROUP; l++) {
+            double e[3], J[3 * CKA_NJ];
+            for (int j = 0; j < CKA_NACC; j++) T->part[l][j] = 0.0;
+            for (int i = l; i < tb[2]; i += CKR_GROUP) {
+                ckr_jacobian(M + 12 * c, st + CKA_S_POSE, T->world + 3 * ((size_t)tb[0] + i), T->bear + 3 * ((size_t)tb[1] + i), (unsigned)mask6[c], e, J);
+                ckr_accumulate_rows(T->part[l], T->part[l] + CKA_NH, e, J, 0, CKA_NJ);
             }
-            butterfly(T->part, NACC);
-            memcpy(T->vw + (size_t)CKR_V_STRIDE * ((size_t)u * T->n_cams + c) + CKR_V_H, T->part[0], sizeof(double) * NACC);
         }
+        butterfly(T->part, CKA_NACC);
+        memcpy(T->vw + (size_t)CKA_B_STRIDE * v + CKA_B_H, T->part[0], sizeof(double) * CKA_NACC);
     }
 }
 
 static void accept_costs(twin_t *T) {
-    for (size_t v = 0; v < (size_t)T->U * T->n_cams; v++) T->vw[CKR_V_STRIDE * v + CKR_V_COSTA] = T->vw[CKR_V_STRIDE * v + CKR_V_COST];
+    for (int v = 0; v < T->P; v++) T->vw[(size_t)CKA_B_STRIDE * v + CKA_B_COSTA] = T->vw[(size_t)CKA_B_STRIDE * v + CKA_B_COST];
 }
 
 int ck_rigcal_refine_host(const ck_rigcal_params_t *p, int32_t n_cams, const ck_sqpnp_problem_t *records, int32_t n_steps,
@@ -270,87 +241,81 @@ int ck_rigcal_refine_host(const ck_rigcal_params_t *p, int32_t n_cams, const ck_
     ck_rigcal_plan_t plan;
     int32_t *tab = (int32_t *)malloc(sizeof(int32_t) * CKR_TAB * ((size_t)n_cams * n_steps + 1));
     double *world = (double *)malloc(sizeof(double) * 12 * ((size_t)n_tags_total + 1));
-    int32_t *used = (int32_t *)malloc(sizeof(int32_t) * ((size_t)problem->n_steps + 1));
+    int32_t *index = (int32_t *)malloc(sizeof(int32_t) * (cka_index_size((size_t)problem->n_steps, (size_t)n_cams * (size_t)problem->n_steps, (size_t)n_cams) + 1));
     twin_t *T = (twin_t *)calloc(1, sizeof(twin_t));
-    double *S = (double *)malloc(sizeof(double) * ((size_t)N * N + (size_t)N * (N + 1) / 2 + 2 * (size_t)N + 27 * CK_RIG_MAX_CAMS));
+    double *S = (double *)malloc(sizeof(double) * ((size_t)N * N + (size_t)N + CKA_HK * CK_RIG_MAX_CAMS));
     int ret = CK_ENOMEM;
-    if (!tab || !world || !used || !T || !S) goto done;
+    if (!tab || !world || !index || !T || !S) goto done;
     ck_rigcal_table(n_cams, records, n_steps, tags, n_tags_total, tab, world);
-    ck_rigcal_plan(p, n_cams, tab, n_steps, problem, step_index, poses0, used, &plan);
+    ck_rigcal_plan(p, n_cams, tab, n_steps, problem, step_index, poses0, index, &plan);
     ck_rigcal_result_start(problem, &plan, n_cams, mounts0, res);
-    for (int32_t j = 0; j < problem->n_steps; j++)
-        memcpy(poses_out + 12 * ((size_t)problem->step_offset + j), poses0 + 12 * (size_t)step_index[problem->step_offset + j], sizeof(double) * 12);
+    ck_cal_poses_start(problem, step_index, poses0, poses_out);
     ret = CK_OK;
     if (plan.status == CK_CALIB_DEGENERATE) goto done;
-    T->tab = tab; T->used = used; T->world = world; T->bear = bearings;
-    T->n = n_steps; T->n_cams = n_cams; T->U = plan.n_used;
-    T->st = (double *)calloc((size_t)CKR_S_STRIDE * (size_t)T->U, sizeof(double));
-    T->vw = (double *)calloc((size_t)CKR_V_STRIDE * (size_t)T->U * (size_t)n_cams, sizeof(double));
+    T->x = cka_index_at(index, (size_t)plan.n_used, (size_t)plan.n_views);
+    T->tab = tab; T->world = world; T->bear = bearings;
+    T->n = n_steps; T->U = plan.n_used; T->P = plan.n_views;
+    T->st = (double *)calloc((size_t)CKA_S_STRIDE * (size_t)T->U, sizeof(double));
+    T->vw = (double *)calloc((size_t)CKA_B_STRIDE * (size_t)T->P, sizeof(double));
     if (!T->st || !T->vw) { ret = CK_ENOMEM; goto done; }
     {
         double M[12 * CK_RIG_MAX_CAMS], Mc[12 * CK_RIG_MAX_CAMS];
-        double *E = S + (size_t)N * N, *Eg = E + (size_t)N * (N + 1) / 2, *dk = Eg + N, *Hc = dk + N;
-        for (int c = 0; c < n_cams; c++) ck_rigcal_mount_in(mounts0 + c, M + 12 * c);
-        memcpy(Mc, M, sizeof M);
-        for (int u = 0; u < T->U; u++) {
-            memcpy(T->st + (size_t)CKR_S_STRIDE * u + CKR_S_POSE, poses0 + 12 * (size_t)used[u], sizeof(double) * 12);
-            memcpy(T->st + (size_t)CKR_S_STRIDE * u + CKR_S_CAND, poses0 + 12 * (size_t)used[u], sizeof(double) * 12);
+        double *dk = S + (size_t)N * N, *Hc = dk + N;
+        int32_t mask6[CK_RIG_MAX_CAMS];
+        for (int c = 0; c < n_cams; c++) {
+            ck_rigcal_mount_in(mounts0 + c, M + 12 * c);
+            mask6[c] = (int32_t)((plan.mask >> (6 * c)) & 63u);
         }
+        memcpy(Mc, M, sizeof M);
+        ck_cal_steps_seed(T->st, T->x.used, T->U, poses0);
         const double cost0 = twin_cost(T, Mc);
         accept_costs(T);
         res->status = CK_CALIB_DEGENERATE;
         if (!ckc_finite(cost0)) goto done;
         ckc_lm_t lm;
-        ckr_lm_start(&lm, cost0);
+        ckc_lm_start(&lm, cost0, CKR_COST_FLOOR);
         while (lm.status < 0) {
             if (lm.need_jac) {
-                twin_jacobian(T, M, plan.mask);
-                for (int c = 0; c < n_cams; c++)
-                    for (int j = 0; j < 27; j++) Hc[27 * c + j] = ckr_cam_sum(T->vw, T->U, n_cams, tab, n_steps, used, c, j);
+                twin_jacobian(T, M, mask6);
+                for (int j = 0; j < CKA_HK * n_cams; j++) Hc[j] = cka_col_sum(T->vw, T->x.colmap + (size_t)(j / CKA_HK) * T->U, T->U, j % CKA_HK);
             }
             int solved = 1;
             for (int u = 0; u < T->U; u++)
-                if (!ckr_step_schur(T->st + (size_t)CKR_S_STRIDE * u, T->vw + (size_t)CKR_V_STRIDE * (size_t)u * n_cams, n_cams, tab, n_steps, used[u], lm.lambda))
+                if (!cka_step_schur(T->st + (size_t)CKA_S_STRIDE * u, T->vw + (size_t)CKA_B_STRIDE * T->x.first[u], T->x.first[u + 1] - T->x.first[u], lm.lambda))
                     solved = 0;
-            int ne = 0;
             for (int r = 0; r < N; r++) {
-                for (int k = r; k < N; k++) E[ne++] = ckr_schur_sum(T->vw, T->U, n_cams, tab, n_steps, used, r, k);
-                Eg[r] = ckr_schur_sum(T->vw, T->U, n_cams, tab, n_steps, used, r, -1);
+                for (int k = 0; k <= r; k++) S[r * N + k] = cka_reduced_entry(T->vw, T->x.colmap, mask6, Hc, T->U, NULL, T->U, lm.lambda, r, k);
+                dk[r] = cka_reduced_rhs(T->vw, T->x.colmap, mask6, Hc, T->U, r);
             }
-            double pred = 0.0, cost_new = 0.0;
-            if (!ckr_reduced_solve(Hc, E, Eg, N, lm.lambda, plan.mask, S, dk, &pred)) solved = 0;
+            if (!ckc_chol_n(S, N)) solved = 0;
+            ckc_fwd_n(S, N, dk, 1);
+            ckc_bwd_n(S, N, dk);
+            double pred = cka_reduced_pred(mask6, Hc, N, lm.lambda, dk), cost_new = 0.0;
             if (solved) {
-                for (int c = 0; c < n_cams; c++) ckr_mount_step(M + 12 * c, dk + 6 * c, (unsigned)((plan.mask >> (6 * c)) & 63u), Mc + 12 * c);
+                for (int c = 0; c < n_cams; c++) ckc_rigid_step(M + 12 * c, dk + 6 * c, (unsigned)mask6[c], Mc + 12 * c);
                 for (int u = 0; u < T->U; u++)
-                    ckr_step_step(T->st + (size_t)CKR_S_STRIDE * u, T->vw + (size_t)CKR_V_STRIDE * (size_t)u * n_cams, n_cams, tab, n_steps, used[u], dk, lm.lambda);
-                for (int u = 0; u < T->U; u++) pred = pred + T->st[(size_t)CKR_S_STRIDE * u + CKR_S_PRED];
+                    cka_step_step(T->st + (size_t)CKA_S_STRIDE * u, T->vw + (size_t)CKA_B_STRIDE * T->x.first[u], T->x.col + T->x.first[u],
+                                  T->x.first[u + 1] - T->x.first[u], dk, lm.lambda);
+                for (int u = 0; u < T->U; u++) pred = pred + T->st[(size_t)CKA_S_STRIDE * u + CKA_S_PRED];
                 cost_new = twin_cost(T, Mc);
             }
-            if (ckr_lm_decide(&lm, solved, pred, cost_new, p->max_iters)) {
+            if (ckc_lm_decide(&lm, solved, pred, cost_new, p->max_iters, CKR_COST_FLOOR)) {
                 memcpy(M, Mc, sizeof M);
                 for (int u = 0; u < T->U; u++)
-                    memcpy(T->st + (size_t)CKR_S_STRIDE * u + CKR_S_POSE, T->st + (size_t)CKR_S_STRIDE * u + CKR_S_CAND, sizeof(double) * 12);
+                    memcpy(T->st + (size_t)CKA_S_STRIDE * u + CKA_S_POSE, T->st + (size_t)CKA_S_STRIDE * u + CKA_S_CAND, sizeof(double) * 12);
                 accept_costs(T);
             }
         }
-        for (int u = 0, j = 0; u < T->U; u++) {
-            while (step_index[problem->step_offset + j] != used[u]) j++;
-            memcpy(poses_out + 12 * ((size_t)problem->step_offset + j), T->st + (size_t)CKR_S_STRIDE * u + CKR_S_POSE, sizeof(double) * 12);
-        }
+        ck_cal_poses_finish(problem, step_index, T->x.used, T->U, T->st, poses_out);
         ck_rigcal_result_finish(&plan, n_cams, mounts0, M, res);
         res->status = lm.status; res->iters = lm.iters;
         res->cost0 = cost0; res->cost = lm.cost;
         res->rms = sqrt(lm.cost / (double)res->n_points);
-        for (int c = 0; c < n_cams; c++) {
-            if (plan.cam_points[c] == 0) continue;
-            double t = 0.0;
-            for (int u = 0; u < T->U; u++)
-                if (CKR_NPTS(tab, n_steps, c, used[u]) > 0) t = t + T->vw[(size_t)CKR_V_STRIDE * ((size_t)u * n_cams + c) + CKR_V_COSTA];
-            res->cam_rms[c] = sqrt(t / (double)plan.cam_points[c]);
-        }
+        for (int c = 0; c < n_cams; c++)
+            if (plan.cam_points[c] > 0) res->cam_rms[c] = cka_col_rms(T->vw, T->x.colmap + (size_t)c * T->U, T->U, plan.cam_points[c]);
     }
 done:
     if (T) { free(T->st); free(T->vw); }
-    free(tab); free(world); free(used); free(T); free(S);
+    free(tab); free(world); free(index); free(T); free(S);
     return ret;
 }

@@ -123,7 +123,7 @@ __global__ __launch_bounds__(NTH) void k_calib(const ck_calib_problem_t *__restr
         double c = 0.0;
         for (int f = 0; f < F; f++) c = c + rec[(size_t)CKC_WS_STRIDE * f + CKC_WS_COST];
         s_cost0 = c;
-        ckc_lm_start(&s_lm, c);
+        ckc_lm_start(&s_lm, c, CKC_COST_FLOOR);
         if (!ckc_finite(c)) s_lm.status = CK_CALIB_DEGENERATE;
     }
     __syncthreads();
@@ -163,7 +163,7 @@ __global__ __launch_bounds__(NTH) void k_calib(const ck_calib_problem_t *__restr
             }
         }
         if (tid == 0) {
-            s_accept = ckc_lm_decide(&s_lm, s_solved, pred, cost_new, max_iters);
+            s_accept = ckc_lm_decide(&s_lm, s_solved, pred, cost_new, max_iters, CKC_COST_FLOOR);
             if (s_accept)
                 for (int i = 0; i < 9; i++) s_k[i] = s_kc[i];
         }

@@ -1,6 +1,7 @@
 // k_fieldcal.hip — Levenberg-Marquardt refinement of the field's tag poses and one robot pose per step: one persistent
-// workgroup of 256 threads per problem, the whole iteration inside the kernel.  The arithmetic is ck_fieldcal_math.h's, the same text
-// the host twin (ck_fieldcal_host.c) compiles; this file only decides who computes what.
+// workgroup of 256 threads per problem, the whole iteration inside the kernel.  The arithmetic is ck_fieldcal_math.h's and, shared with
+// the mount calibration, ck_cal_math.h's, the same text the host twin (ck_fieldcal_host.c) compiles; this file only decides who
+// computes what.
 //   points          a group of 4 lanes takes the sightings group, group + 64, ... of the problem, in rounds that every group of the
 //                   workgroup walks together; lane l has corner l.  The 4 values meet in the xor butterfly 2, 1, which stands OUTSIDE
 //                   "has this group a sighting": every lane is active at every exchange (k_tail).  The 90 sums of a
@@ -40,8 +41,8 @@ __device__ __forceinline__ void sight_of(sight_t &w, int g, int NS, const ckf_me
     w.k = 0;
     if (w.on) {
         const int pi = m.sight_pair[g], c = m.sight_cam[g];
-        w.k = m.pair_tag[pi];
-        const double *P = steps + (size_t)CKR_S_STRIDE * m.pair_step[pi] + pose_at;
+        w.k = m.ix.col[pi];
+        const double *P = steps + (size_t)CKA_S_STRIDE * m.ix.step[pi] + pose_at;
         const double *b = bear + 3 * ((size_t)m.sight_bear[g] + lane);
 #pragma unroll
         for (int i = 0; i < 12; i++) { w.M[i] = s_M[12 * c + i]; w.P[i] = P[i]; w.T[i] = s_T[12 * w.k + i]; }
@@ -55,7 +56,7 @@ __device__ __forceinline__ void cost_pass(const double *s_M, const double *s_Tc,
                                           const ckf_meta_t &m, int NS, const double *__restrict__ bear, int group, int lane) {
     for (int g0 = 0; g0 < NS; g0 += NGRP) {
         sight_t w;
-        sight_of(w, g0 + group, NS, m, s_M, s_Tc, steps, CKR_S_CAND, bear, lane);
+        sight_of(w, g0 + group, NS, m, s_M, s_Tc, steps, CKA_S_CAND, bear, lane);
         double a = 0.0;
         if (w.on) {
             double e[3];
@@ -73,17 +74,17 @@ template <int A0, int A1>
 __device__ __forceinline__ void jacobian_pass(const double *s_M, const double *s_T, const int32_t *s_mask, const double *__restrict__ steps,
                                               double *__restrict__ sights, const ckf_meta_t &m, int NS, const double *__restrict__ bear,
                                               int group, int lane) {
-    constexpr int NT = CKR_TRI(A1, A1) - CKR_TRI(A0, A0), NG = A0 == 0 ? CKR_NJ : 0;
+    constexpr int NT = CKA_TRI(A1, A1) - CKA_TRI(A0, A0), NG = A0 == 0 ? CKA_NJ : 0;
     for (int g0 = 0; g0 < NS; g0 += NGRP) {
         sight_t w;
-        sight_of(w, g0 + group, NS, m, s_M, s_T, steps, CKR_S_POSE, bear, lane);
+        sight_of(w, g0 + group, NS, m, s_M, s_T, steps, CKA_S_POSE, bear, lane);
         double acc[NT], g[NG ? NG : 1];
 #pragma unroll
         for (int j = 0; j < NT; j++) acc[j] = 0.0;
 #pragma unroll
         for (int j = 0; j < NG; j++) g[j] = 0.0;
         if (w.on) {
-            double e[3], J[3 * CKR_NJ];
+            double e[3], J[3 * CKA_NJ];
             ckf_jacobian(w.M, w.P, w.T, lane, w.b, (unsigned)s_mask[w.k], e, J);
             ckr_accumulate_rows(acc, NG ? g : nullptr, e, J, A0, A1);
         }
@@ -94,7 +95,7 @@ __device__ __forceinline__ void jacobian_pass(const double *s_M, const double *s
         if (lane == 0 && w.on) {
             double *V = sights + (size_t)CKF_I_STRIDE * (g0 + group);
 #pragma unroll
-            for (int j = 0; j < NT; j++) V[CKF_I_H + CKR_TRI(A0, A0) + j] = acc[j];
+            for (int j = 0; j < NT; j++) V[CKF_I_H + CKA_TRI(A0, A0) + j] = acc[j];
 #pragma unroll
             for (int j = 0; j < NG; j++) V[CKF_I_G + j] = g[j];
         }
@@ -105,9 +106,9 @@ __device__ __forceinline__ void jacobian_pass(const double *s_M, const double *s
 __device__ __forceinline__ void step_costs(double *__restrict__ steps, double *__restrict__ pairs, const double *__restrict__ sights,
                                            const ckf_meta_t &m, int U, int tid) {
     for (int u = tid; u < U; u += NTH) {
-        const int p0 = m.step_pair[u];
-        ckf_step_cost(steps + (size_t)CKR_S_STRIDE * u, pairs + (size_t)CKF_P_STRIDE * p0, sights + (size_t)CKF_I_STRIDE * m.pair_sight[p0],
-                      m.pair_sight + p0, m.step_pair[u + 1] - p0);
+        const int p0 = m.ix.first[u];
+        ckf_step_cost(steps + (size_t)CKA_S_STRIDE * u, pairs + (size_t)CKA_B_STRIDE * p0, sights + (size_t)CKF_I_STRIDE * m.pair_sight[p0],
+                      m.pair_sight + p0, m.ix.first[u + 1] - p0);
     }
 }
 
@@ -183,7 +184,7 @@ __global__ __launch_bounds__(NTH) void k_fieldcal(const ck_fieldcal_dev_problem 
                                                   double *__restrict__ tags_all, double *__restrict__ rms_all, double *__restrict__ steps_all,
                                                   double *__restrict__ pairs_all, double *__restrict__ sights_all, double *__restrict__ S_all,
                                                   ck_fieldcal_result_t *__restrict__ res, int C, int max_iters) {
-    __shared__ double s_M[12 * CK_RIG_MAX_CAMS], s_T[12 * TMAX], s_Tc[12 * TMAX], s_Hk[CKF_HK * TMAX], s_dk[NMAX], s_col[NMAX];
+    __shared__ double s_M[12 * CK_RIG_MAX_CAMS], s_T[12 * TMAX], s_Tc[12 * TMAX], s_Hk[CKA_HK * TMAX], s_dk[NMAX], s_col[NMAX];
     __shared__ int32_t s_mask[TMAX];
     __shared__ double s_cost0, s_piv;
     __shared__ ckc_lm_t s_lm;
@@ -194,8 +195,8 @@ __global__ __launch_bounds__(NTH) void k_fieldcal(const ck_fieldcal_dev_problem 
     const ck_fieldcal_dev_problem q = prob[blockIdx.x];
     const int U = q.U, P = q.P, NS = q.NS, T = q.T, N = 6 * T, NE = (N * (N + 1)) / 2;
     const ckf_meta_t m = ckf_meta_at(meta_all + q.meta_off, (size_t)U, (size_t)P, (size_t)NS, (size_t)T);
-    double *steps = steps_all + (size_t)CKR_S_STRIDE * (size_t)q.step_off;
-    double *pairs = pairs_all + (size_t)CKF_P_STRIDE * (size_t)q.pair_off;
+    double *steps = steps_all + (size_t)CKA_S_STRIDE * (size_t)q.step_off;
+    double *pairs = pairs_all + (size_t)CKA_B_STRIDE * (size_t)q.pair_off;
     double *sights = sights_all + (size_t)CKF_I_STRIDE * (size_t)q.sight_off;
     double *S = S_all + q.s_off;
     double *Tg = tags_all + (size_t)12 * TMAX * blockIdx.x;
@@ -208,12 +209,12 @@ __global__ __launch_bounds__(NTH) void k_fieldcal(const ck_fieldcal_dev_problem 
     __syncthreads();
     step_costs(steps, pairs, sights, m, U, tid);
     __syncthreads();
-    for (int pi = tid; pi < P; pi += NTH) pairs[(size_t)CKF_P_STRIDE * pi + CKF_P_COSTA] = pairs[(size_t)CKF_P_STRIDE * pi + CKF_P_COST];
+    for (int pi = tid; pi < P; pi += NTH) pairs[(size_t)CKA_B_STRIDE * pi + CKA_B_COSTA] = pairs[(size_t)CKA_B_STRIDE * pi + CKA_B_COST];
     if (tid == 0) {
         double c = 0.0;
-        for (int u = 0; u < U; u++) c = c + steps[(size_t)CKR_S_STRIDE * u + CKR_S_COST];
+        for (int u = 0; u < U; u++) c = c + steps[(size_t)CKA_S_STRIDE * u + CKA_S_COST];
         s_cost0 = c;
-        ckr_lm_start(&s_lm, c);
+        ckc_lm_start(&s_lm, c, CKR_COST_FLOOR);
         if (!ckc_finite(c)) s_lm.status = CK_CALIB_DEGENERATE;
     }
     __syncthreads();
@@ -225,61 +226,59 @@ __global__ __launch_bounds__(NTH) void k_fieldcal(const ck_fieldcal_dev_problem 
         const double lambda = s_lm.lambda;
         if (s_lm.need_jac) {
             jacobian_pass<0, 4>(s_M, s_T, s_mask, steps, sights, m, NS, bear, group, lane);
-            jacobian_pass<4, CKR_NJ>(s_M, s_T, s_mask, steps, sights, m, NS, bear, group, lane);
+            jacobian_pass<4, CKA_NJ>(s_M, s_T, s_mask, steps, sights, m, NS, bear, group, lane);
             __syncthreads();
             for (int pi = tid; pi < P; pi += NTH)
-                ckf_pair_sum(pairs + (size_t)CKF_P_STRIDE * pi, sights + (size_t)CKF_I_STRIDE * m.pair_sight[pi], m.pair_sight[pi + 1] - m.pair_sight[pi]);
+                ckf_pair_sum(pairs + (size_t)CKA_B_STRIDE * pi, sights + (size_t)CKF_I_STRIDE * m.pair_sight[pi], m.pair_sight[pi + 1] - m.pair_sight[pi]);
             __syncthreads();
-            for (int j = tid; j < CKF_HK * T; j += NTH) s_Hk[j] = ckf_tag_sum(pairs, m.pairmap + (size_t)(j / CKF_HK) * U, U, j % CKF_HK);
+            for (int j = tid; j < CKA_HK * T; j += NTH) s_Hk[j] = cka_col_sum(pairs, m.ix.colmap + (size_t)(j / CKA_HK) * U, U, j % CKA_HK);
         }
         if (tid == 0) s_solved = 1;
         __syncthreads();
         for (int u = tid; u < U; u += NTH)
-            if (!ckf_step_schur(steps + (size_t)CKR_S_STRIDE * u, pairs + (size_t)CKF_P_STRIDE * m.step_pair[u], m.step_pair[u + 1] - m.step_pair[u], lambda))
+            if (!cka_step_schur(steps + (size_t)CKA_S_STRIDE * u, pairs + (size_t)CKA_B_STRIDE * m.ix.first[u], m.ix.first[u + 1] - m.ix.first[u], lambda))
                 s_solved = 0;
         __syncthreads();
         for (int e = tid; e < NE; e += NTH) {
-            int r = (int)((sqrt(8.0 * (double)e + 1.0) - 1.0) * 0.5);
-            while ((r * (r + 1)) / 2 > e) r--;
-            while (((r + 1) * (r + 2)) / 2 <= e) r++;
-            S[e] = ckf_reduced_entry(pairs, m.pairmap, s_mask, s_Hk, U, nullptr, U, lambda, r, e - (r * (r + 1)) / 2);
+            const int r = cka_lt_row(e);
+            S[e] = cka_reduced_entry(pairs, m.ix.colmap, s_mask, s_Hk, U, nullptr, U, lambda, r, e - (r * (r + 1)) / 2);
         }
-        for (int r = tid; r < N; r += NTH) s_dk[r] = ckf_reduced_rhs(pairs, m.pairmap, s_mask, s_Hk, U, r);
+        for (int r = tid; r < N; r += NTH) s_dk[r] = cka_reduced_rhs(pairs, m.ix.colmap, s_mask, s_Hk, U, r);
         __syncthreads();
         const bool factored = reduced_solve(S, N, s_dk, s_col, &s_piv, tid);
         double pred = 0.0, cost_new = 0.0;
         if (tid == 0) {
             if (!factored) s_solved = 0;
-            else pred = ckf_reduced_pred(s_mask, s_Hk, N, lambda, s_dk);
+            else pred = cka_reduced_pred(s_mask, s_Hk, N, lambda, s_dk);
         }
         __syncthreads();
         if (s_solved) {
-            if (tid < T) ckf_tag_step(s_T + 12 * tid, s_dk + 6 * tid, (unsigned)s_mask[tid], s_Tc + 12 * tid);
+            if (tid < T) ckc_rigid_step(s_T + 12 * tid, s_dk + 6 * tid, (unsigned)s_mask[tid], s_Tc + 12 * tid);
             for (int u = tid; u < U; u += NTH)
-                ckf_step_step(steps + (size_t)CKR_S_STRIDE * u, pairs + (size_t)CKF_P_STRIDE * m.step_pair[u], m.pair_tag + m.step_pair[u],
-                              m.step_pair[u + 1] - m.step_pair[u], s_dk, lambda);
+                cka_step_step(steps + (size_t)CKA_S_STRIDE * u, pairs + (size_t)CKA_B_STRIDE * m.ix.first[u], m.ix.col + m.ix.first[u],
+                              m.ix.first[u + 1] - m.ix.first[u], s_dk, lambda);
             __syncthreads();
             cost_pass(s_M, s_Tc, steps, sights, m, NS, bear, group, lane);
             __syncthreads();
             step_costs(steps, pairs, sights, m, U, tid);
             __syncthreads();
             if (tid == 0) {
-                for (int u = 0; u < U; u++) pred = pred + steps[(size_t)CKR_S_STRIDE * u + CKR_S_PRED];
-                for (int u = 0; u < U; u++) cost_new = cost_new + steps[(size_t)CKR_S_STRIDE * u + CKR_S_COST];
+                for (int u = 0; u < U; u++) pred = pred + steps[(size_t)CKA_S_STRIDE * u + CKA_S_PRED];
+                for (int u = 0; u < U; u++) cost_new = cost_new + steps[(size_t)CKA_S_STRIDE * u + CKA_S_COST];
             }
         }
-        if (tid == 0) s_accept = ckr_lm_decide(&s_lm, s_solved, pred, cost_new, max_iters);
+        if (tid == 0) s_accept = ckc_lm_decide(&s_lm, s_solved, pred, cost_new, max_iters, CKR_COST_FLOOR);
         __syncthreads();
         if (s_accept) {
             for (int i = tid; i < 12 * T; i += NTH) s_T[i] = s_Tc[i];
             for (int i = tid; i < 12 * U; i += NTH)
-                steps[(size_t)CKR_S_STRIDE * (i / 12) + CKR_S_POSE + i % 12] = steps[(size_t)CKR_S_STRIDE * (i / 12) + CKR_S_CAND + i % 12];
-            for (int pi = tid; pi < P; pi += NTH) pairs[(size_t)CKF_P_STRIDE * pi + CKF_P_COSTA] = pairs[(size_t)CKF_P_STRIDE * pi + CKF_P_COST];
+                steps[(size_t)CKA_S_STRIDE * (i / 12) + CKA_S_POSE + i % 12] = steps[(size_t)CKA_S_STRIDE * (i / 12) + CKA_S_CAND + i % 12];
+            for (int pi = tid; pi < P; pi += NTH) pairs[(size_t)CKA_B_STRIDE * pi + CKA_B_COSTA] = pairs[(size_t)CKA_B_STRIDE * pi + CKA_B_COST];
         }
         __syncthreads();
     }
     for (int i = tid; i < 12 * T; i += NTH) Tg[i] = s_T[i];
-    if (tid < T) rms_all[(size_t)TMAX * blockIdx.x + tid] = ckf_tag_rms(pairs, m.pairmap + (size_t)tid * U, U, m.tag_ns[tid]);
+    if (tid < T) rms_all[(size_t)TMAX * blockIdx.x + tid] = cka_col_rms(pairs, m.ix.colmap + (size_t)tid * U, U, 4 * m.tag_ns[tid]);
     if (tid == 0) {
         R->status = s_lm.status; R->iters = s_lm.iters;
         R->cost0 = s_cost0; R->cost = s_lm.cost;
