@@ -98,6 +98,21 @@ class RigRobustResult(C.Structure):
                 ("rejected", C.c_uint64 * CK_RIG_MAX_CAMS), ("worst_inlier_rad", C.c_double), ("best_rejected_rad", C.c_double)]
 
 
+CK_RIG_REFINE_FREE, CK_RIG_REFINE_PLANAR = 0, 1
+CK_RIG_REFINE_CONVERGED, CK_RIG_REFINE_MAXITERS, CK_RIG_REFINE_DEGENERATE, CK_RIG_REFINE_NO_START = 0, 1, 2, 3
+
+
+class RigRefineParams(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("max_iters", C.c_int32), ("sigma_rad", C.c_double), ("gyro_sigma_rad", C.c_double), ("z", C.c_double)]
+
+
+class RigRefined(C.Structure):
+    _fields_ = [("status", C.c_int32), ("iters", C.c_int32), ("n_points", C.c_int32), ("dof", C.c_int32), ("rot", C.c_double * 9),
+                ("pos", C.c_double * 3), ("cov", C.c_double * 36), ("std_devs", C.c_double * 3), ("cost0", C.c_double),
+                ("cost", C.c_double), ("rms", C.c_double), ("chi2", C.c_double), ("moved_m", C.c_double), ("moved_rad", C.c_double),
+                ("cam_rms", C.c_double * CK_RIG_MAX_CAMS)]
+
+
 class OpenCV5(C.Structure):
     _fields_ = [(k, C.c_double) for k in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3")]
 
@@ -238,6 +253,7 @@ assert C.sizeof(TriOtsuParams) == 16 and C.sizeof(TriOtsuInfo) == 160
 assert C.sizeof(CalibParams) == 24 and C.sizeof(CalibProblem) == 16 and C.sizeof(CalibResult) == 112
 assert C.sizeof(RigParams) == 32 and C.sizeof(RigResult) == 240
 assert C.sizeof(RigRobustParams) == 56 and C.sizeof(RigRobustResult) == 336
+assert C.sizeof(RigRefineParams) == 32 and C.sizeof(RigRefined) == 536
 
 
 class RigcalResult(C.Structure):

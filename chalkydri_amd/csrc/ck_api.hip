@@ -15,6 +15,7 @@
 #include "ck_rig.h"
 #include "ck_rigcal.h"
 #include "ck_fieldcal.h"
+#include "ck_rig_refine.h"
 
 thread_local char ck_err_text[512] = "";
 
@@ -188,6 +189,7 @@ extern "C" void ck_destroy(ck_handle_t *h) {
     delete h->rig;
     delete h->rigcal;
     delete h->fieldcal;
+    delete h->rig_refine;
     for (auto &e : h->ev) if (e) (void)hipEventDestroy(e);
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
     if (h->ev_join) (void)hipEventDestroy(h->ev_join);

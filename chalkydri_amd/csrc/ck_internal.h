@@ -220,6 +220,8 @@ struct ck_handle {
     struct ck_rigcal_ws *rigcal;
     // field calibration (ck_fieldcal.hip, k_fieldcal.hip): allocated by the first field calibration call, grown on demand
     struct ck_fieldcal_ws *fieldcal;
+    // rig pose refinement (ck_rig_refine.hip, k_rig_refine.hip): allocated by the first refinement call, grown on demand
+    struct ck_rig_refine_ws *rig_refine;
     bool fmerge_lds_allowed; // k_fmerge's dynamic LDS limit has been raised on this handle's device
 };
 

@@ -24,4 +24,12 @@ struct ck_rig_ws {
     ~ck_rig_ws() { for (auto &e : ev) if (e) (void)hipEventDestroy(e); }
 };
 
+// k_rigpnp.hip, for ck_rig_refine.hip: everything ck_rig_process_last (rp null) or ck_rig_process_last_robust (params = &rp->rig, out a
+// ck_rig_robust_result_t[n]) enqueues on handles[0]'s stream, without the wait; and k_rig once more over what the last
+// ck_rig_solve_batch of this shape left in the workspace (a measurement aid)
+int ck_rig_enqueue_last(ck_handle_t *const *handles, int32_t n_cams, int32_t n, const ck_rig_params_t *params,
+                        const ck_rig_robust_params_t *rp, const double *gyro, const uint8_t *has_gyro, void *out,
+                        ck_vision_measurement_t *meas, int32_t *valid);
+int ck_rig_relaunch_batch(ck_handle_t *h, const ck_rig_params_t *params, int32_t n_cams, int32_t n, int32_t max_points);
+
 #endif

@@ -740,9 +740,24 @@ extern "C" int ck_rig_solve_robust_batch(ck_handle_t *h, const ck_rig_robust_par
     return rig_solve_batch(h, &params->rig, params, n_cams, problems, n, tags, n_tags_total, bearings, n_bearings_total, gyro, out);
 }
 
+// Measurement aid (ck_rig_refine_time): k_rig once more over the arrays the last ck_rig_solve_batch of this shape left in the workspace
+int ck_rig_relaunch_batch(ck_handle_t *h, const ck_rig_params_t *params, int32_t n_cams, int32_t n, int32_t max_points) {
+    ck_rig_ws *ws = h->rig;
+    if (!ws || n < 1) return CK_EINVAL;
+    RigArgs a;
+    memset(&a, 0, sizeof a);
+    a.prm = *params;
+    for (int c = 0; c < n_cams; c++) a.cam[c] = {ws->d_prob.p + (size_t)c * n, ws->d_tags, ws->d_bearings, nullptr, 0, 0};
+    a.n_cams = n_cams; a.n = n; a.max_points = max_points;
+    a.gyro = ws->d_gyro; a.points = ws->d_points; a.out = ws->d_res;
+    rig_launch(ws, a, nullptr, h->stream);
+    CK_HIP(hipGetLastError());
+    return CK_OK;
+}
+
 // ck_rig_process_last up to, not including, the wait for the stream
-// (rp: the robust solve, params = &rp->rig and out a ck_rig_robust_result_t[n])
-static int rig_enqueue_last(ck_handle_t *const *handles, int32_t n_cams, int32_t n, const ck_rig_params_t *params,
+// (rp: the robust solve, params = &rp->rig and out a ck_rig_robust_result_t[n]); ck_rig_process_last_refined (ck_rig_refine.hip) goes on from here
+int ck_rig_enqueue_last(ck_handle_t *const *handles, int32_t n_cams, int32_t n, const ck_rig_params_t *params,
                             const ck_rig_robust_params_t *rp, const double *gyro, const uint8_t *has_gyro, void *out,
                             ck_vision_measurement_t *meas, int32_t *valid) {
     if (rp && ck_rig_robust_check(rp, 0, nullptr, 0) != CK_OK) return CK_EINVAL;
@@ -791,7 +806,7 @@ static int rig_enqueue_last(ck_handle_t *const *handles, int32_t n_cams, int32_t
 
 extern "C" int ck_rig_process_last(ck_handle_t *const *handles, int32_t n_cams, int32_t n, const ck_rig_params_t *params, const double *gyro,
                                    const uint8_t *has_gyro, ck_rig_result_t *out, ck_vision_measurement_t *meas, int32_t *valid) {
-    const int rc = rig_enqueue_last(handles, n_cams, n, params, nullptr, gyro, has_gyro, out, meas, valid);
+    const int rc = ck_rig_enqueue_last(handles, n_cams, n, params, nullptr, gyro, has_gyro, out, meas, valid);
     if (rc != CK_OK) return rc;
     CK_HIP(hipStreamSynchronize(handles[0]->stream));
     return CK_OK;
@@ -801,7 +816,7 @@ extern "C" int ck_rig_process_last_robust(ck_handle_t *const *handles, int32_t n
                                           const double *gyro, const uint8_t *has_gyro, ck_rig_robust_result_t *out,
                                           ck_vision_measurement_t *meas, int32_t *valid) {
     if (!params) return CK_EINVAL;
-    const int rc = rig_enqueue_last(handles, n_cams, n, &params->rig, params, gyro, has_gyro, out, meas, valid);
+    const int rc = ck_rig_enqueue_last(handles, n_cams, n, &params->rig, params, gyro, has_gyro, out, meas, valid);
     if (rc != CK_OK) return rc;
     CK_HIP(hipStreamSynchronize(handles[0]->stream));
     return CK_OK;
@@ -812,7 +827,7 @@ extern "C" int ck_rig_time_last(ck_handle_t *const *handles, int32_t n_cams, int
     if (iters < 1 || !ms_rig || !ms_sqpnp || n < 1) return CK_EINVAL;
     std::vector<ck_vision_measurement_t> meas((size_t)n);
     std::vector<int32_t> valid((size_t)n);
-    int rc = rig_enqueue_last(handles, n_cams, n, params, nullptr, gyro, has_gyro, nullptr, meas.data(), valid.data()); // (checks, workspace)
+    int rc = ck_rig_enqueue_last(handles, n_cams, n, params, nullptr, gyro, has_gyro, nullptr, meas.data(), valid.data()); // (checks, workspace)
     if (rc != CK_OK) return rc;
     ck_handle *h = handles[0];
     CK_HIP(hipStreamSynchronize(h->stream));
@@ -823,7 +838,7 @@ extern "C" int ck_rig_time_last(ck_handle_t *const *handles, int32_t n_cams, int
         float *dst[2] = {ms_rig + it, ms_sqpnp + it};
         for (int which = 0; which < 2 && rc == CK_OK; which++) {
             if (hipEventRecord(e0, h->stream) != hipSuccess) { rc = CK_EDEVICE; break; }
-            if (which == 0) rc = rig_enqueue_last(handles, n_cams, n, params, nullptr, gyro, has_gyro, nullptr, meas.data(), valid.data());
+            if (which == 0) rc = ck_rig_enqueue_last(handles, n_cams, n, params, nullptr, gyro, has_gyro, nullptr, meas.data(), valid.data());
             else for (int c = 0; c < n_cams && rc == CK_OK; c++) rc = ck_launch_sqpnp_last(handles[c], n, &params->sqpnp, h->stream);
             if (rc != CK_OK) break;
             if (hipEventRecord(e1, h->stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||

@@ -132,6 +132,13 @@ def _bind(L):
     L.ck_rig_solve_robust_host.argtypes = [bp, i32, sp, i32, _P(A.Iso3), i32, vp, i32, vp, br]
     L.ck_rig_solve_robust_batch.argtypes = [vp, bp, i32, sp, i32, _P(A.Iso3), i32, vp, i32, vp, br]
     L.ck_rig_process_last_robust.argtypes = [_P(vp), i32, i32, bp, vp, vp, br, _P(A.VisionMeasurement), _P(i32)]
+    fp, fr = _P(A.RigRefineParams), _P(A.RigRefined)
+    L.ck_rig_refine_params_default.argtypes = [fp]
+    L.ck_rig_refine_params_default.restype = None
+    L.ck_rig_refine_host.argtypes = [fp, i32, sp, i32, _P(A.Iso3), i32, vp, i32, vp, vp, vp, fr]
+    L.ck_rig_refine_batch.argtypes = [vp, fp, i32, sp, i32, _P(A.Iso3), i32, vp, i32, vp, vp, vp, fr]
+    L.ck_rig_process_last_refined.argtypes = [_P(vp), i32, i32, bp, i32, fp, vp, vp, vp, fr, _P(A.VisionMeasurement), _P(i32)]
+    L.ck_rig_refine_time.argtypes = [vp, fp, i32, sp, i32, _P(A.Iso3), i32, vp, i32, vp, i32, vp, vp]
     mp, mq, mr, iso = _P(A.RigcalParams), _P(A.RigcalProblem), _P(A.RigcalResult), _P(A.Iso3)
     L.ck_rigcal_params_default.argtypes = [mp]
     L.ck_rigcal_params_default.restype = None

@@ -1025,6 +1025,35 @@ class RigSolver {
         out.resize((size_t)n);
         return out;
     }
+    // The maximum-likelihood pose of every step and its covariance (chalkydri_hip.h: ck_rig_refine_*) from the fused
+    // records `start` of the same steps; `rejected` (optional, [steps][CK_RIG_MAX_CAMS]) are a robust solve's masks.  gyro is read
+    // when refine.gyro_sigma_rad > 0 and may be empty otherwise.  On the device, or with host = true on the host: the same bytes.
+    // The host call keeps no state between or across calls: it may run on several threads at once.
+    static ck_rig_refine_params_t refine_defaults() { ck_rig_refine_params_t p; ck_rig_refine_params_default(&p); return p; }
+    std::vector<ck_rig_refined_t> refine(const std::vector<std::vector<RigView>> &steps, const std::vector<double> &gyro,
+                                         const std::vector<ck_rig_result_t> &start, ck_rig_refine_params_t refine = refine_defaults(),
+                                         bool host = false, const std::vector<uint64_t> *rejected = nullptr) const {
+        if (!host && !h_) throw Panic("RigSolver::refine needs a handle", CK_EINVAL);
+        std::vector<ck_sqpnp_problem_t> probs;
+        std::vector<ck_iso3_t> tags;
+        std::vector<double> b;
+        const bool no_heading = gyro.empty() && !(refine.gyro_sigma_rad > 0.0);
+        const int n = (int)steps.size(), n_cams = pack(steps, no_heading ? std::vector<double>(steps.size(), 0.0) : gyro, probs, tags, b);
+        if (start.size() != steps.size() || (rejected && rejected->size() != steps.size() * CK_RIG_MAX_CAMS))
+            throw Panic("RigSolver::refine: one start record (and one row of masks) per step", CK_EINVAL);
+        std::vector<ck_rig_refined_t> out((size_t)n + 1);
+        std::vector<ck_rig_result_t> st(start);
+        st.resize((size_t)n + 1);
+        const double g0 = 0.0;
+        const uint64_t *rej = rejected && n ? rejected->data() : nullptr;
+        const int rc = host ? ck_rig_refine_host(&refine, n_cams, probs.data(), n, tags.data(), (int32_t)tags.size(), b.data(), (int32_t)(b.size() / 3),
+                                                 no_heading ? nullptr : n ? gyro.data() : &g0, st.data(), rej, out.data())
+                            : ck_rig_refine_batch(h_->get(), &refine, n_cams, probs.data(), n, tags.data(), (int32_t)tags.size(), b.data(),
+                                                  (int32_t)(b.size() / 3), no_heading ? nullptr : n ? gyro.data() : &g0, st.data(), rej, out.data());
+        check(rc, host ? "ck_rig_refine_host" : "ck_rig_refine_batch");
+        out.resize((size_t)n);
+        return out;
+    }
 
   private:
     // the records, tags and bearings of the steps as the C calls take them; returns the number of cameras
@@ -1105,6 +1134,34 @@ inline std::vector<std::pair<whacknet::VisionMeasurement, bool>> rig_process_las
     std::vector<std::pair<whacknet::VisionMeasurement, bool>> r;
     for (int i = 0; i < n; i++) r.emplace_back(out[i], valid[i] != 0);
     if (results) results->assign(res.begin(), res.begin() + n);
+    return r;
+}
+// ... and with the refinement behind either solve (ck_rig_process_last_refined): the measurements carry the refined x, y,
+// yaw and the standard deviations of its covariance where the refinement has a pose.  use_robust false: `robust.rig` alone is read.
+// refined (optional): the refinement's records; fused (optional): the robust solve's records (use_robust true only).
+inline std::vector<std::pair<whacknet::VisionMeasurement, bool>> rig_process_last_refined(const std::vector<AprilTags *> &tasks,
+                                                                                          const ck_rig_robust_params_t &robust, bool use_robust,
+                                                                                          const ck_rig_refine_params_t &refine,
+                                                                                          const std::vector<std::optional<double>> &gyro,
+                                                                                          std::vector<ck_rig_refined_t> *refined = nullptr,
+                                                                                          std::vector<ck_rig_robust_result_t> *fused = nullptr) {
+    const int n = (int)gyro.size();
+    std::vector<ck_handle_t *> hs;
+    for (const AprilTags *t : tasks) hs.push_back(t ? t->handle()->get() : nullptr);
+    std::vector<double> g((size_t)n + 1);
+    std::vector<uint8_t> has((size_t)n + 1);
+    for (int i = 0; i < n; i++) { has[i] = gyro[i].has_value(); g[i] = gyro[i].value_or(0.0); }
+    std::vector<ck_rig_robust_result_t> res((size_t)n + 1);
+    std::vector<ck_rig_refined_t> ref((size_t)n + 1);
+    std::vector<whacknet::VisionMeasurement> out((size_t)n + 1);
+    std::vector<int32_t> valid((size_t)n + 1);
+    check(ck_rig_process_last_refined(hs.data(), (int32_t)hs.size(), n, &robust, use_robust ? 1 : 0, &refine, g.data(), has.data(),
+                                      use_robust ? res.data() : nullptr, ref.data(), out.data(), valid.data()),
+          "ck_rig_process_last_refined");
+    std::vector<std::pair<whacknet::VisionMeasurement, bool>> r;
+    for (int i = 0; i < n; i++) r.emplace_back(out[i], valid[i] != 0);
+    if (refined) refined->assign(ref.begin(), ref.begin() + n);
+    if (fused && use_robust) fused->assign(res.begin(), res.begin() + n);
     return r;
 }
 

@@ -991,6 +991,93 @@ int ck_rig_process_last_robust(ck_handle_t *const *handles, int32_t n_cams, int3
                                const double *gyro, const uint8_t *has_gyro, ck_rig_robust_result_t *out, ck_vision_measurement_t *meas,
                                int32_t *valid);
 
+/* ---- rig pose refinement: the maximum-likelihood pose of an instant and its covariance -----------------------------
+ * Levenberg-Marquardt on the angular residual of §4l, e = (p - v (v.p)/(v.v)) / |p| with p = A_c (R X + t - o_c), over every corner of
+ * every tag of the instant that `rejected` does not delete, from the fused record's pose (ck_rig_result_t: rot / pos, world <- robot,
+ * inverted to world -> robot).  One unknown pose per instant:
+ *   CK_RIG_REFINE_FREE    six increments (rotation about world axes, translation), as the calibrators step a pose
+ *   CK_RIG_REFINE_PLANAR  world <- robot = (Rz(theta), (x, y, params.z)): three unknowns.  The start is projected: z = params.z,
+ *                         (cos theta, sin theta) = (rot[0], rot[3]) normalised (a zero norm: DEGENERATE)
+ * gyro_sigma_rad > 0 adds the heading as a measurement: one residual (R_wr[1][0] cos g - R_wr[0][0] sin g) / gyro_sigma_rad (sin(yaw - g)
+ * of a level robot); the bearing residuals then count 1 / sigma_rad^2, so both are in units of their standard deviation.  Without the
+ * prior sigma_rad only scales the covariance.  A candidate that puts a used point at or behind its camera is refused like a cost
+ * increase.  cov = the inverse of the normal matrix at the accepted pose in radians and metres (sigma_rad^2 (J^T J)^-1 with the prior's
+ * row scaled by sigma_rad / gyro_sigma_rad), in the world-axes tangent of the world <- robot pose (R_wr <- Exp(dw) R_wr, p <- p + dp),
+ * ordered (x, y, z, wx, wy, wz), row-major; in planar mode the rows and columns of z, wx and wy are zero.
+ * Status: CONVERGED (an accepted step's relative decrease fell below 1e-14, a step's predicted decrease below 1e-18 of the cost, the
+ * cost below 1e-40 rad^2, or no damping up to 1e30 found a decrease: a minimum to round-off), MAXITERS (max_iters iterations ran
+ * without a stop rule's confirmation: the record is complete, the pose the best accepted one and cov its covariance, as usable as a
+ * CONVERGED one; do not gate on the difference.  On weakly determined scenes, coplanar tags with six unknowns, the damping needs more
+ * than ten iterations to come down: at the default 10, 1412 of 2000 noisy draws of three tags on one wall end MAXITERS, within 5e-6 of
+ * their own standard deviations of the 30-iteration pose), DEGENERATE (no usable point, a non-finite cost, a normal matrix that does not factor, the
+ * planar projection of a vertical x axis: the pose is the start's, cov and std_devs are 0, and so is everything after them but
+ * cost0), NO_START (start.valid == 0: all other fields are 0). */
+#define CK_RIG_REFINE_FREE 0
+#define CK_RIG_REFINE_PLANAR 1
+#define CK_RIG_REFINE_CONVERGED 0
+#define CK_RIG_REFINE_MAXITERS 1
+#define CK_RIG_REFINE_DEGENERATE 2
+#define CK_RIG_REFINE_NO_START 3
+typedef struct ck_rig_refine_params {
+    int32_t mode;                  /* CK_RIG_REFINE_FREE */
+    int32_t max_iters;             /* 10; 1..100: a bound on the time of an instant, not a quality gate (see MAXITERS) */
+    double sigma_rad;              /* 1e-3: the standard deviation of a bearing, per component */
+    double gyro_sigma_rad;         /* 0: no heading prior */
+    double z;                      /* 0: the robot origin's height in planar mode */
+} ck_rig_refine_params_t;
+typedef struct ck_rig_refined {
+    int32_t status;                /* CK_RIG_REFINE_* */
+    int32_t iters;
+    int32_t n_points;              /* corners used */
+    int32_t dof;                   /* 2 per corner (the residual's rank), 1 for the prior, minus the unknowns */
+    double rot[9];                 /* world <- robot, row-major */
+    double pos[3];
+    double cov[36];
+    double std_devs[3];            /* sqrt of cov's x, y, wz diagonal */
+    double cost0, cost;            /* sum of the squared bearing residuals at the start and at the result, rad^2 (without the prior) */
+    double rms;                    /* sqrt(cost / n_points) */
+    double chi2;                   /* (cost / sigma_rad^2 + prior^2) / dof, 0 when dof < 1: near 1 when sigma_rad is the noise */
+    double moved_m;                /* |pos - start.pos| */
+    double moved_rad;              /* |rot - start.rot|_F / sqrt(2) = 2 sin(angle / 2) */
+    double cam_rms[CK_RIG_MAX_CAMS]; /* of camera c's used corners at the result, rad */
+} ck_rig_refined_t;
+void ck_rig_refine_params_default(ck_rig_refine_params_t *p);
+/* On the host, one thread, no device: the specification of the kernel (same summation order, same bytes).  Reentrant: every call works in
+ * memory of its own, so several threads may call it at once.  The first eight arguments
+ * after params are ck_rig_solve_host's; gyro [n] may be null when gyro_sigma_rad == 0; start [n] are the fused records; rejected
+ * [n][CK_RIG_MAX_CAMS] (may be null) is ck_rig_robust_result_t's mask: bit t of [s][c] deletes tag t (< 64) of camera c's record at
+ * instant s.  CK_EINVAL, checked in this order and before anything is written: a null params, problems, start or out; ck_rig_solve_host's
+ * checks of counts and records; a mode outside the two; sigma_rad or z not finite, sigma_rad <= 0; gyro_sigma_rad < 0 or not finite;
+ * max_iters outside 1..100; gyro_sigma_rad > 0 with a null gyro.  CK_ENOMEM. */
+int ck_rig_refine_host(const ck_rig_refine_params_t *params, int32_t n_cams, const ck_sqpnp_problem_t *problems, int32_t n,
+                       const ck_iso3_t *tags, int32_t n_tags_total, const double *bearings, int32_t n_bearings_total, const double *gyro,
+                       const ck_rig_result_t *start, const uint64_t *rejected, ck_rig_refined_t *out);
+/* The same on the handle's stream, one 64-lane wave per instant.  Every pointer may be a host or a device pointer.  Returns when out
+ * is complete; the twin's bytes when gyro is a host pointer or null (the heading's sine and cosine are then taken on the host, as
+ * the twin takes them; a device gyro takes them on the device).  The workspace is allocated by the first call and grown on demand.
+ * Errors: ck_rig_refine_host's (the handle among the null pointers). */
+int ck_rig_refine_batch(ck_handle_t *h, const ck_rig_refine_params_t *params, int32_t n_cams, const ck_sqpnp_problem_t *problems, int32_t n,
+                        const ck_iso3_t *tags, int32_t n_tags_total, const double *bearings, int32_t n_bearings_total, const double *gyro,
+                        const ck_rig_result_t *start, const uint64_t *rejected, ck_rig_refined_t *out);
+/* ck_rig_process_last (use_robust == 0: robust_params->rig is read) or ck_rig_process_last_robust, then the refinement of every
+ * instant on the same stream, reading the fused records (and the robust solve's masks) and the handles' buffers in place.  start_out
+ * [n] (may be null) is what the unrefined call returns in `out`, byte for byte; out [n] the refined records.  meas[s] carries the
+ * refined x, y, yaw and std_devs; camera_id and tag_count are the fused measurement's; an instant whose refinement is DEGENERATE or
+ * NO_START publishes the fused measurement unchanged.  With gyro_sigma_rad > 0 the heading's sine and cosine are taken on the device:
+ * out equals ck_rig_refine_batch on ck_last_pose_inputs' arrays to a tolerance, not byte for byte: 1e-9 (m, rad) on the pose and 1e-6
+ * relative on std_devs are what the tests hold it to; measured on an MI355X on the rendered two-camera scene the two were identical
+ * (DESIGN.md §4o).  Without the prior the bytes are equal.  Errors: the
+ * unrefined call's, ck_rig_refine_host's parameter checks, a null refine_params or out. */
+int ck_rig_process_last_refined(ck_handle_t *const *handles, int32_t n_cams, int32_t n, const ck_rig_robust_params_t *robust_params,
+                                int32_t use_robust, const ck_rig_refine_params_t *refine_params, const double *gyro, const uint8_t *has_gyro,
+                                void *start_out /* ck_rig_result_t [n], with use_robust ck_rig_robust_result_t [n] */, ck_rig_refined_t *out,
+                                ck_vision_measurement_t *meas, int32_t *valid);
+/* Measurement aid (tools/bench_rig_refine.py): after ck_rig_refine_batch's checks and uploads, runs `iters` times on the handle's
+ * stream, between two hipEvents each, k_rig_refine (ms_refine[iters]) and k_rig on the same inputs (ms_rig[iters]).  gyro [n] is the host's. */
+int ck_rig_refine_time(ck_handle_t *h, const ck_rig_refine_params_t *params, int32_t n_cams, const ck_sqpnp_problem_t *problems, int32_t n,
+                       const ck_iso3_t *tags, int32_t n_tags_total, const double *bearings, int32_t n_bearings_total, const double *gyro,
+                       int32_t iters, float *ms_refine, float *ms_rig);
+
 /* ---- camera mounts: the robot_to_cam of a rig's cameras from a capture, batched Levenberg-Marquardt ------
  * The capture is what ck_rig_solve_batch takes: n_steps instants of n_cams cameras, camera c's record of step s at
  * records[c * n_steps + s] (n_tags, n_bearings = 4 * n_tags and the offsets are read; the records' own robot_to_cam is ignored), and
