@@ -117,6 +117,14 @@ class OpenCV5(C.Structure):
     _fields_ = [(k, C.c_double) for k in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3")]
 
 
+CK_CAMERA_OPENCV5, CK_CAMERA_EUCM, CK_CAMERA_UCM = 0, 1, 2
+
+
+class Camera(C.Structure):
+    """ck_camera_t: k = fx fy cx cy k1 k2 p1 p2 k3 (OPENCV5), fx fy cx cy alpha beta 0 0 0 (EUCM), fx fy cx cy alpha (UCM)."""
+    _fields_ = [("model", C.c_int32), ("pad", C.c_int32), ("k", C.c_double * 9)]
+
+
 class TagPoseParams(C.Structure):
     _fields_ = [("cam", OpenCV5), ("tagsize", C.c_double * CK_MAX_FAMILIES), ("n_iters", C.c_int32), ("pad", C.c_int32)]
 
@@ -245,6 +253,7 @@ class SynthParams(C.Structure):
 
 assert C.sizeof(VisionMeasurement) == 64  # crates/whacknet/src/lib.rs:92-95
 assert C.sizeof(TagPoseParams) == 112 and C.sizeof(TagPose) == 296
+assert C.sizeof(Camera) == 80
 assert C.sizeof(JpegFrame) == 16 and C.sizeof(JpegInfo) == 32
 assert C.sizeof(RawFormat) == 8
 assert C.sizeof(PreviewParams) == 24
@@ -254,6 +263,17 @@ assert C.sizeof(CalibParams) == 24 and C.sizeof(CalibProblem) == 16 and C.sizeof
 assert C.sizeof(RigParams) == 32 and C.sizeof(RigResult) == 240
 assert C.sizeof(RigRobustParams) == 56 and C.sizeof(RigRobustResult) == 336
 assert C.sizeof(RigRefineParams) == 32 and C.sizeof(RigRefined) == 536
+
+
+CK_CAMCAL_STARTS = 6
+
+
+class CameraCalibResult(C.Structure):
+    _fields_ = [("cam", Camera), ("status", C.c_int32), ("iters", C.c_int32), ("n_frames", C.c_int32), ("n_points", C.c_int32),
+                ("rms", C.c_double), ("cost0", C.c_double), ("cost", C.c_double), ("start", C.c_int32), ("n_starts", C.c_int32)]
+
+
+assert C.sizeof(CameraCalibResult) == 128
 
 
 class RigcalResult(C.Structure):

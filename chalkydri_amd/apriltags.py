@@ -2,8 +2,8 @@
 (crates/apriltags/src/lib.rs:166-182 struct, :221-291 new, :293-379 process) — batched over frames.
 
 Configuration follows the reference: `family` (default tag36h11), `bits_corrected` (default 3), `cam_id`,
-`robot_to_cam` JSON {roll,pitch,yaw,x,y,z} and `calib` JSON {"OpenCVModel5": {...}} (chalkydri.ron:28-29), and the
-field layout JSON (field.json; crates/apriltags/src/field_layout.rs:18-44).
+`robot_to_cam` JSON {roll,pitch,yaw,x,y,z} and `calib` JSON {"OpenCVModel5": {...}} (chalkydri.ron:28-29) or, for wide-angle
+lenses, {"EUCM": {...}} / {"UCM": {...}} (chalkydri_amd/camera.py), and the field layout JSON (field.json; crates/apriltags/src/field_layout.rs:18-44).
 """
 import ctypes as C
 import json
@@ -46,12 +46,17 @@ class AprilTags:
             orientation_code(orientation)                           # (ValueError for an unknown name, before any device work)
         calib = json.loads(calib) if isinstance(calib, str) else calib
         r2c = json.loads(robot_to_cam) if isinstance(robot_to_cam, str) else robot_to_cam
-        m = calib["OpenCVModel5"]
-        self.cam = A.OpenCV5(*[float(m[k]) for k in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3")])
+        from .camera import camera_from_calib
+        self.camera = camera_from_calib(calib)                      # (ValueError for a model this library does not have)
+        # the params' OpenCVModel5: the model itself, or (EUCM / UCM, set on the handle below, where this field is ignored) its pinhole part
+        self.cam = A.OpenCV5(*([float(v) for v in self.camera.k] if self.camera.model == A.CK_CAMERA_OPENCV5 else
+                               [float(v) for v in self.camera.k[:4]] + [0.0] * 5))
         # argument order of the reference call (lib.rs:247-254): x, y, z, roll, pitch, yaw
         self.robot_to_cam = SqPnP.create_solver_camera_transform(r2c["x"], r2c["y"], r2c["z"], r2c["roll"], r2c["pitch"], r2c["yaw"])
         self.detector = AprilTagDetector(width, height, max_batch=max_batch, families=(family,), bits_corrected=bits_corrected,
                                          device=device, quad_sigma=quad_sigma, **cfg)
+        if self.camera.model != A.CK_CAMERA_OPENCV5:
+            self.detector.set_camera(self.camera)
         self.solver = SqPnP(self.detector)
         self.tags = field if isinstance(field, dict) and all(isinstance(v, A.Iso3) for v in field.values()) else load_field_layout(field)
         self.cam_id = cam_id

@@ -22,6 +22,12 @@ FIX_DISTORTION, FIX_FOCAL = A.CK_CALIB_FIX_DISTORTION, A.CK_CALIB_FIX_FOCAL
 RESULT_DTYPE = np.dtype([("cam", "<f8", (9,)), ("status", "<i4"), ("iters", "<i4"), ("n_frames", "<i4"), ("n_points", "<i4"),
                          ("rms", "<f8"), ("cost0", "<f8"), ("cost", "<f8")])
 assert RESULT_DTYPE.itemsize == C.sizeof(A.CalibResult)
+# ck_camera_calib_result_t: any camera model (chalkydri_amd/camera.py); `cam` = ck_camera_t.k, `start` of `n_starts` = the winner
+CAMERA_RESULT_DTYPE = np.dtype([("model", "<i4"), ("pad", "<i4"), ("cam", "<f8", (9,)), ("status", "<i4"), ("iters", "<i4"),
+                                ("n_frames", "<i4"), ("n_points", "<i4"), ("rms", "<f8"), ("cost0", "<f8"), ("cost", "<f8"),
+                                ("start", "<i4"), ("n_starts", "<i4")])
+assert CAMERA_RESULT_DTYPE.itemsize == C.sizeof(A.CameraCalibResult)
+MODEL_CODES = {"OpenCVModel5": A.CK_CAMERA_OPENCV5, "EUCM": A.CK_CAMERA_EUCM, "UCM": A.CK_CAMERA_UCM}
 
 
 class Board:
@@ -165,10 +171,79 @@ def calibrate_batch(det, p, problems):
     return res, [pk.poses_of(out, i).copy() for i in range(pk.n)]
 
 
-def project(k, pose, board_xy):
+def _model(model):
+    return MODEL_CODES[model] if isinstance(model, str) else int(model)
+
+
+def _camera(model, k):
+    cam = A.Camera()
+    cam.model = _model(model)
+    for i, v in enumerate(k):
+        cam.k[i] = float(v)
+    return cam
+
+
+def _cres(arr):
+    return C.cast(arr.ctypes.data, C.POINTER(A.CameraCalibResult))
+
+
+def camera_calib_init(model, p, frames, start_index=0):
+    """ck_camera_calib_init of one problem, on the host: start `start_index` of the model's starts -> (k0 [9], poses0 [F][12], status)."""
+    pk = Packed([frames])
+    cam0, poses, st = A.Camera(), np.zeros((pk.n_frames, 12)), C.c_int32(-1)
+    check(_bind(lib()).ck_camera_calib_init(_model(model), C.byref(p), pk.prob, *pk.args(), int(start_index), C.byref(cam0), poses.ctypes.data,
+                                            C.byref(st)), "ck_camera_calib_init")
+    return np.array(cam0.k[:]), poses, st.value
+
+
+def camera_jacobian(model, k, pose, board_xy, image_uv, fixed_mask=0):
+    """ck_camera_calib_jacobian: residuals [n][2] and analytic Jacobian [n][2][15] of one frame's observations under `model`."""
+    b, u = np.ascontiguousarray(board_xy, np.float64).reshape(-1, 2), np.ascontiguousarray(image_uv, np.float64).reshape(-1, 2)
+    pose = np.ascontiguousarray(pose, np.float64).reshape(12)
+    r, J = np.zeros((len(b), 2)), np.zeros((len(b), 2, 15))
+    check(_bind(lib()).ck_camera_calib_jacobian(_model(model), C.byref(_camera(model, k)), pose.ctypes.data, b.ctypes.data, u.ctypes.data, len(b),
+                                                int(fixed_mask), r.ctypes.data, J.ctypes.data), "ck_camera_calib_jacobian")
+    return r, J
+
+
+def camera_refine_host(model, p, frames, k0, poses0):
+    """ck_camera_calib_refine_host of one problem, one host thread: (result record, poses [F][12])."""
+    pk = Packed([frames])
+    res, out = np.zeros((), CAMERA_RESULT_DTYPE), np.zeros((pk.n_frames, 12))
+    poses0 = np.ascontiguousarray(poses0, np.float64).reshape(pk.n_frames, 12)
+    check(_bind(lib()).ck_camera_calib_refine_host(_model(model), C.byref(p), pk.prob, *pk.args(), C.byref(_camera(model, k0)), poses0.ctypes.data,
+                                                   _cres(res), out.ctypes.data), "ck_camera_calib_refine_host")
+    return res, out
+
+
+def camera_refine_batch(det, model, p, problems, cams0, poses0):
+    """ck_camera_calib_refine_batch on the detector's handle: as refine_batch, for any model."""
+    pk = Packed(problems)
+    cams = (A.Camera * max(pk.n, 1))(*[_camera(model, k) for k in cams0])
+    pin = np.ascontiguousarray(np.concatenate([np.asarray(q, np.float64).reshape(-1, 12) for q in poses0]) if pk.n else np.zeros((0, 12)))
+    res, out = np.zeros(pk.n, CAMERA_RESULT_DTYPE), np.zeros((pk.n_frames, 12))
+    check(_bind(lib()).ck_camera_calib_refine_batch(det._h, _model(model), C.byref(p), pk.prob, pk.n, *pk.args(), cams, pin.ctypes.data, _cres(res),
+                                                    out.ctypes.data), "ck_camera_calib_refine_batch")
+    return res, [pk.poses_of(out, i).copy() for i in range(pk.n)]
+
+
+def camera_calibrate_batch(det, model, p, problems):
+    """ck_camera_calibrate_batch: every problem from every start of its model in one launch, the lowest final cost kept."""
+    pk = Packed(problems)
+    res, out = np.zeros(pk.n, CAMERA_RESULT_DTYPE), np.zeros((pk.n_frames, 12))
+    check(_bind(lib()).ck_camera_calibrate_batch(det._h, _model(model), C.byref(p), pk.prob, pk.n, *pk.args(), _cres(res), out.ctypes.data),
+          "ck_camera_calibrate_batch")
+    return res, [pk.poses_of(out, i).copy() for i in range(pk.n)]
+
+
+def project(k, pose, board_xy, model="OpenCVModel5"):
     """The forward model on the host (numpy), for reports: k [9], pose [12] (R row-major, t), board_xy [n][2] -> pixels [n][2]."""
     R, t = np.asarray(pose[:9]).reshape(3, 3), np.asarray(pose[9:])
     P = np.asarray(board_xy) @ R[:, :2].T + t
+    if _model(model) != A.CK_CAMERA_OPENCV5:
+        d = np.sqrt(k[5] * (P[:, 0] ** 2 + P[:, 1] ** 2) + P[:, 2] ** 2)
+        den = k[4] * d + (1 - k[4]) * P[:, 2]
+        return np.stack([k[0] * P[:, 0] / den + k[2], k[1] * P[:, 1] / den + k[3]], 1)
     x, y = P[:, 0] / P[:, 2], P[:, 1] / P[:, 2]
     r2 = x * x + y * y
     rad = 1 + r2 * (k[4] + r2 * (k[5] + r2 * k[8]))
@@ -199,6 +274,17 @@ class Calibrator:
                 self._frames.append((np.concatenate(b), np.concatenate(u)))
         return len(self._frames)
 
+    def add_observations(self, board_xy, image_uv):
+        """Keeps a frame of correspondences the caller found itself (board_xy [n][2] metres, image_uv [n][2] pixels), like
+        chalkydri::Calibrator::add_observations; False (and nothing kept) below min_corners points."""
+        b, u = np.asarray(board_xy, np.float64).reshape(-1, 2), np.asarray(image_uv, np.float64).reshape(-1, 2)
+        if len(b) != len(u):
+            raise ValueError("a frame has as many board points as image points")
+        if len(b) < self.min_corners:
+            return False
+        self._frames.append((b.copy(), u.copy()))
+        return True
+
     def observations(self):
         """The kept frames: a list of (board_xy [n][2], image_uv [n][2])."""
         return list(self._frames)
@@ -206,9 +292,11 @@ class Calibrator:
     def clear(self):
         self._frames = []
 
-    def calibrate(self, fixed_mask=0, leave_out=0, seed=0, max_iters=None):
+    def calibrate(self, fixed_mask=0, leave_out=0, seed=0, max_iters=None, model="OpenCVModel5"):
         """Solves the kept frames: (calib_dict, report), or None when the solve neither converged nor stalled at a finite rms (the
-        reference likewise returns None after its retries).  calib_dict is what AprilTags(..., calib=) takes.  report: status,
+        reference likewise returns None after its retries).  calib_dict is what AprilTags(..., calib=) takes, in the schema of
+        `model`: "OpenCVModel5", or "EUCM" / "UCM" for wide-angle lenses (every problem is then solved from six starts in the same
+        launch and the lowest final cost kept: report["start"]; fixed_mask bits 0..5 = fx fy cx cy alpha beta).  report: status,
         iters, rms, per_frame_rms, poses, and with leave_out = K > 0 `std`, the standard deviation of each parameter over K
         random half-subsets of the frames (those that solved: `n_subsets`), all solved in the same batched call."""
         frames = self._frames
@@ -219,17 +307,28 @@ class Calibrator:
         half = max(p.min_frames, (len(frames) + 1) // 2)
         for _ in range(int(leave_out)):
             problems.append([frames[i] for i in sorted(rng.choice(len(frames), half, replace=False))])
-        res, poses = calibrate_batch(self.det, p, problems)
+        if _model(model) == A.CK_CAMERA_OPENCV5:
+            res, poses = calibrate_batch(self.det, p, problems)
+        else:
+            res, poses = camera_calibrate_batch(self.det, model, p, problems)
         ok = lambda r: r["status"] in (A.CK_CALIB_CONVERGED, A.CK_CALIB_STALLED) and np.isfinite(r["rms"])
         if not ok(res[0]):
             return None
         k = res[0]["cam"]
-        calib = {"OpenCVModel5": dict({n: float(v) for n, v in zip(PARAM_NAMES, k)}, width=int(self.det.width), height=int(self.det.height))}
-        per_frame = [float(np.sqrt(np.mean(np.sum((project(k, P, b) - u) ** 2, 1)))) for (b, u), P in zip(frames, poses[0])]
+        if _model(model) == A.CK_CAMERA_OPENCV5:
+            names = PARAM_NAMES
+            calib = {"OpenCVModel5": dict({n: float(v) for n, v in zip(PARAM_NAMES, k)}, width=int(self.det.width), height=int(self.det.height))}
+        else:
+            from .camera import MODELS, calib_from_camera
+            names = MODELS[model][1]
+            calib = calib_from_camera(_camera(model, k), self.det.width, self.det.height)
+        per_frame = [float(np.sqrt(np.mean(np.sum((project(k, P, b, model) - u) ** 2, 1)))) for (b, u), P in zip(frames, poses[0])]
         report = {"status": STATUS_NAMES[int(res[0]["status"])], "iters": int(res[0]["iters"]), "rms": float(res[0]["rms"]),
                   "per_frame_rms": per_frame, "poses": poses[0]}
+        if _model(model) != A.CK_CAMERA_OPENCV5:
+            report["start"], report["n_starts"] = int(res[0]["start"]), int(res[0]["n_starts"])
         if leave_out:
             sub = np.array([r["cam"] for r in res[1:] if ok(r)])
             report["n_subsets"] = len(sub)
-            report["std"] = {n: float(v) for n, v in zip(PARAM_NAMES, sub.std(0))} if len(sub) > 1 else None
+            report["std"] = {n: float(v) for n, v in zip(names, sub.std(0))} if len(sub) > 1 else None
         return calib, report

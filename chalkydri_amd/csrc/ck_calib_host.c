@@ -114,16 +114,14 @@ static int homography(const double *bxy, const double *uv, int n, double *H) {
     return 1;
 }
 
-int ck_calib_init(const ck_calib_params_t *p, const ck_calib_problem_t *q, const double *board_xy, const double *image_uv,
-                  const int32_t *frame_start, int32_t n_points_total, int32_t n_starts_total, int32_t n_frames_total,
-                  ck_opencv5_t *cam0_out, double *poses0, int32_t *status_out) {
-    if (!cam0_out || !poses0 || !status_out) return CK_EINVAL;
-    const int rc = ck_calib_check(p, q, 1, board_xy, image_uv, frame_start, n_points_total, n_starts_total, n_frames_total);
-    if (rc != CK_OK) return rc;
+// The start of one checked problem: k4 = fx fy cx cy and the poses (zero when there is none: *status_out DEGENERATE).  given_f <= 0:
+// the focal lengths come from the homographies (ck_calib_init's start); given_f > 0: fx = fy = given_f, the homographies give the poses.
+static int start_of(const ck_calib_params_t *p, const ck_calib_problem_t *q, const double *board_xy, const double *image_uv,
+                    const int32_t *frame_start, double given_f, double *k4, double *poses0, int32_t *status_out) {
     const int F = q->n_frames;
     const int32_t *fs = frame_start + q->start_offset;
     double *poses = poses0 + 12 * (size_t)q->pose_offset;
-    memset(cam0_out, 0, sizeof *cam0_out);
+    memset(k4, 0, sizeof(double) * 4);
     memset(poses, 0, sizeof(double) * 12 * (size_t)F);
     *status_out = CK_CALIB_DEGENERATE;
     double *H = (double *)malloc(sizeof(double) * 9 * (size_t)F);
@@ -149,12 +147,16 @@ int ck_calib_init(const ck_calib_params_t *p, const ck_calib_problem_t *q, const
     // Singular in the sense that matters: frames that are all (nearly) parallel to the image plane make every equation a multiple
     // of (1, -1, 0), and nothing separates the focal length from the distance.  sin^2 of the angle between the system's two columns
     // is at most 1.7e-5 for such captures of the reference's cameras and at least 1.2e-3 for captures tilted as DESIGN.md §4j says
-    if (ok) ok = N[0] * N[3] - N[1] * N[1] > 1e-4 * (N[0] * N[3]);
-    if (ok) ok = gauss(N, nb, 2);
-    if (ok) ok = nb[0] > 0.0 && nb[1] > 0.0 && ckc_finite(nb[0]) && ckc_finite(nb[1]);
-    if (ok) {
-        fx = 1.0 / sqrt(nb[0]); fy = 1.0 / sqrt(nb[1]);
-        ok = ckc_finite(fx) && ckc_finite(fy);
+    if (ok) ok = N[0] * N[3] - N[1] * N[1] > 1e-4 * (N[0] * N[3]); // (the capture's geometry: it holds for a given focal length too)
+    if (given_f > 0.0) {
+        fx = given_f; fy = given_f;
+    } else {
+        if (ok) ok = gauss(N, nb, 2);
+        if (ok) ok = nb[0] > 0.0 && nb[1] > 0.0 && ckc_finite(nb[0]) && ckc_finite(nb[1]);
+        if (ok) {
+            fx = 1.0 / sqrt(nb[0]); fy = 1.0 / sqrt(nb[1]);
+            ok = ckc_finite(fx) && ckc_finite(fy);
+        }
     }
     for (int f = 0; f < F && ok; f++) {
         const double *Hf = H + 9 * f;
@@ -183,9 +185,40 @@ int ck_calib_init(const ck_calib_params_t *p, const ck_calib_problem_t *q, const
         memset(poses, 0, sizeof(double) * 12 * (size_t)F);
         return CK_OK;
     }
-    cam0_out->fx = fx; cam0_out->fy = fy; cam0_out->cx = cx; cam0_out->cy = cy;
+    k4[0] = fx; k4[1] = fy; k4[2] = cx; k4[3] = cy;
     *status_out = CK_CALIB_CONVERGED;
     return CK_OK;
+}
+
+int ck_calib_init(const ck_calib_params_t *p, const ck_calib_problem_t *q, const double *board_xy, const double *image_uv,
+                  const int32_t *frame_start, int32_t n_points_total, int32_t n_starts_total, int32_t n_frames_total,
+                  ck_opencv5_t *cam0_out, double *poses0, int32_t *status_out) {
+    if (!cam0_out || !poses0 || !status_out) return CK_EINVAL;
+    const int rc = ck_calib_check(p, q, 1, board_xy, image_uv, frame_start, n_points_total, n_starts_total, n_frames_total);
+    if (rc != CK_OK) return rc;
+    memset(cam0_out, 0, sizeof *cam0_out);
+    return start_of(p, q, board_xy, image_uv, frame_start, 0.0, (double *)cam0_out, poses0, status_out);
+}
+
+static int model_ok(int32_t model) { return model == CK_CAMERA_OPENCV5 || model == CK_CAMERA_EUCM || model == CK_CAMERA_UCM; }
+
+// Start `start_index` of a problem.  OPENCV5 has one: ck_calib_init's.  EUCM / UCM have CK_CAMCAL_STARTS: 0 =
+// ck_calib_init's focal lengths, 1..5 = fx = fy = {0.3, 0.45, 0.65, 1.0, 1.5} max(width, height); each with the principal point at
+// the image centre, alpha = 0.5, beta = 1 and the poses from the frames' homographies and that K.
+int ck_camera_calib_init(int32_t model, const ck_calib_params_t *p, const ck_calib_problem_t *q, const double *board_xy,
+                         const double *image_uv, const int32_t *frame_start, int32_t n_points_total, int32_t n_starts_total,
+                         int32_t n_frames_total, int32_t start_index, ck_camera_t *cam0_out, double *poses0, int32_t *status_out) {
+    static const double ladder[CK_CAMCAL_STARTS] = {0.0, 0.3, 0.45, 0.65, 1.0, 1.5};
+    if (!cam0_out || !poses0 || !status_out) return CK_EINVAL;
+    if (!model_ok(model) || start_index < 0 || start_index >= (model == CK_CAMERA_OPENCV5 ? 1 : CK_CAMCAL_STARTS)) return CK_EINVAL;
+    const int rc = ck_calib_check(p, q, 1, board_xy, image_uv, frame_start, n_points_total, n_starts_total, n_frames_total);
+    if (rc != CK_OK) return rc;
+    memset(cam0_out, 0, sizeof *cam0_out);
+    cam0_out->model = model;
+    const double f = ladder[start_index] * (double)(p->width > p->height ? p->width : p->height);
+    const int rs = start_of(p, q, board_xy, image_uv, frame_start, f, cam0_out->k, poses0, status_out);
+    if (rs == CK_OK && *status_out == CK_CALIB_CONVERGED && model != CK_CAMERA_OPENCV5) { cam0_out->k[4] = 0.5; cam0_out->k[5] = 1.0; }
+    return rs;
 }
 
 // ---- the refinement ----------------------------------------------------------------------------------------------------------
@@ -208,6 +241,18 @@ int ck_calib_jacobian(const ck_opencv5_t *cam, const double *pose, const double 
     return CK_OK;
 }
 
+int ck_camera_calib_jacobian(int32_t model, const ck_camera_t *cam, const double *pose, const double *board_xy, const double *image_uv,
+                             int32_t n, uint32_t fixed_mask, double *r_out, double *J_out) {
+    if (!cam || !pose || !board_xy || !image_uv || !r_out || !J_out || n < 0 || !model_ok(model)) return CK_EINVAL;
+    double k[9];
+    memcpy(k, cam->k, sizeof k);
+    if (model == CK_CAMERA_UCM) k[5] = 1.0;
+    for (int32_t i = 0; i < n; i++)
+        ckc_jacobian_of(model, k, pose, board_xy[2 * i], board_xy[2 * i + 1], image_uv[2 * i], image_uv[2 * i + 1],
+                        fixed_mask | ckc_model_mask(model), r_out + 2 * i, J_out + 2 * CKC_NJ * (size_t)i, J_out + 2 * CKC_NJ * (size_t)i + CKC_NJ);
+    return CK_OK;
+}
+
 // the xor butterfly 32, 16, ..., 1 of 64 lanes' partial sums, as lane 0 sees it
 static void butterfly(double (*part)[CKC_NACC], int n) {
     for (int m = 32; m >= 1; m >>= 1)
@@ -218,7 +263,7 @@ static void butterfly(double (*part)[CKC_NACC], int n) {
 typedef struct {
     const double *bxy, *uv;
     const int32_t *fs;
-    int F;
+    int F, model;
     double *ws;
     double (*part)[CKC_NACC];
 } twin_t;
@@ -230,7 +275,7 @@ static double twin_cost(const twin_t *T, const double *k) {
         for (int l = 0; l < 64; l++) {
             double c = 0.0, r[2];
             for (int i = T->fs[f] + l; i < T->fs[f + 1]; i += 64) {
-                ckc_residual(k, wf + CKC_WS_CAND, T->bxy[2 * i], T->bxy[2 * i + 1], T->uv[2 * i], T->uv[2 * i + 1], r);
+                ckc_residual_of(T->model, k, wf + CKC_WS_CAND, T->bxy[2 * i], T->bxy[2 * i + 1], T->uv[2 * i], T->uv[2 * i + 1], r);
                 c = c + (r[0] * r[0] + r[1] * r[1]);
             }
             T->part[l][0] = c;
@@ -243,15 +288,13 @@ static double twin_cost(const twin_t *T, const double *k) {
     return c;
 }
 
-int ck_calib_refine_host(const ck_calib_params_t *p, const ck_calib_problem_t *q, const double *board_xy, const double *image_uv,
-                         const int32_t *frame_start, int32_t n_points_total, int32_t n_starts_total, int32_t n_frames_total,
-                         const ck_opencv5_t *cam0, const double *poses0, ck_calib_result_t *res, double *poses_out) {
-    if (!cam0 || !poses0 || !res || !poses_out) return CK_EINVAL;
-    const int rc = ck_calib_check(p, q, 1, board_xy, image_uv, frame_start, n_points_total, n_starts_total, n_frames_total);
-    if (rc != CK_OK) return rc;
+// The refinement of one checked problem of any model; an EUCM / UCM problem keeps its parameters in the nine slots of res->cam
+static int refine_host(int model, const ck_calib_params_t *p, const ck_calib_problem_t *q, const double *board_xy, const double *image_uv,
+                       const int32_t *frame_start, const ck_opencv5_t *cam0, const double *poses0, ck_calib_result_t *res, double *poses_out) {
     const int F = q->n_frames;
+    const unsigned fixed_mask = p->fixed_mask | ckc_model_mask(model);
     twin_t T;
-    T.fs = frame_start + q->start_offset; T.F = F;
+    T.fs = frame_start + q->start_offset; T.F = F; T.model = model;
     T.bxy = board_xy + 2 * (size_t)q->point_offset; T.uv = image_uv + 2 * (size_t)q->point_offset;
     const double *pin = poses0 + 12 * (size_t)q->pose_offset;
     double *pout = poses_out + 12 * (size_t)q->pose_offset;
@@ -283,7 +326,7 @@ int ck_calib_refine_host(const ck_calib_params_t *p, const ck_calib_problem_t *q
                         double r[2], Ju[CKC_NJ], Jv[CKC_NJ];
                         for (int j = 0; j < CKC_NACC; j++) T.part[l][j] = 0.0;
                         for (int i = T.fs[f] + l; i < T.fs[f + 1]; i += 64) {
-                            ckc_jacobian(k, wf + CKC_WS_POSE, T.bxy[2 * i], T.bxy[2 * i + 1], T.uv[2 * i], T.uv[2 * i + 1], p->fixed_mask, r, Ju, Jv);
+                            ckc_jacobian_of(model, k, wf + CKC_WS_POSE, T.bxy[2 * i], T.bxy[2 * i + 1], T.uv[2 * i], T.uv[2 * i + 1], fixed_mask, r, Ju, Jv);
                             ckc_accumulate(T.part[l], r, Ju, Jv);
                         }
                     }
@@ -305,9 +348,9 @@ int ck_calib_refine_host(const ck_calib_params_t *p, const ck_calib_problem_t *q
                 Es[j] = s;
             }
             double pred = 0.0, cost_new = 0.0;
-            if (!ckc_reduced_solve(Hs, Es, lm.lambda, p->fixed_mask, S, dk, &pred)) solved = 0;
+            if (!ckc_reduced_solve(Hs, Es, lm.lambda, fixed_mask, S, dk, &pred)) solved = 0;
             if (solved) {
-                for (int i = 0; i < 9; i++) kc[i] = ((p->fixed_mask >> i) & 1u) ? k[i] : k[i] + dk[i];
+                for (int i = 0; i < 9; i++) kc[i] = ((fixed_mask >> i) & 1u) ? k[i] : k[i] + dk[i];
                 for (int f = 0; f < F; f++) ckc_frame_step(T.ws + (size_t)CKC_WS_STRIDE * f, dk, lm.lambda);
                 for (int f = 0; f < F; f++) pred = pred + T.ws[(size_t)CKC_WS_STRIDE * f + CKC_WS_PRED];
                 cost_new = twin_cost(&T, kc);
@@ -327,4 +370,45 @@ int ck_calib_refine_host(const ck_calib_params_t *p, const ck_calib_problem_t *q
     free(T.ws);
     free(T.part);
     return CK_OK;
+}
+
+int ck_calib_refine_host(const ck_calib_params_t *p, const ck_calib_problem_t *q, const double *board_xy, const double *image_uv,
+                         const int32_t *frame_start, int32_t n_points_total, int32_t n_starts_total, int32_t n_frames_total,
+                         const ck_opencv5_t *cam0, const double *poses0, ck_calib_result_t *res, double *poses_out) {
+    if (!cam0 || !poses0 || !res || !poses_out) return CK_EINVAL;
+    const int rc = ck_calib_check(p, q, 1, board_xy, image_uv, frame_start, n_points_total, n_starts_total, n_frames_total);
+    if (rc != CK_OK) return rc;
+    return refine_host(CK_CAMERA_OPENCV5, p, q, board_xy, image_uv, frame_start, cam0, poses0, res, poses_out);
+}
+
+// ck_calib_result_t (the solver's record, any model in its nine slots) -> ck_camera_calib_result_t; ck_calib.hip converts here too
+void ck_calib_result_to_camera(int model, const ck_calib_result_t *r, int start, int n_starts, ck_camera_calib_result_t *o);
+void ck_calib_result_to_camera(int model, const ck_calib_result_t *r, int start, int n_starts, ck_camera_calib_result_t *o) {
+    memset(o, 0, sizeof *o);
+    o->cam.model = model;
+    memcpy(o->cam.k, &r->cam, sizeof o->cam.k);
+    o->status = r->status; o->iters = r->iters; o->n_frames = r->n_frames; o->n_points = r->n_points;
+    o->rms = r->rms; o->cost0 = r->cost0; o->cost = r->cost;
+    o->start = start; o->n_starts = n_starts;
+}
+// the start a caller hands over, in the solver's nine slots: UCM's slot 5 is 1.0 whatever it holds
+void ck_calib_start_from_camera(int model, const ck_camera_t *cam, ck_opencv5_t *k0);
+void ck_calib_start_from_camera(int model, const ck_camera_t *cam, ck_opencv5_t *k0) {
+    memcpy(k0, cam->k, sizeof *k0);
+    if (model == CK_CAMERA_UCM) ((double *)k0)[5] = 1.0;
+}
+
+int ck_camera_calib_refine_host(int32_t model, const ck_calib_params_t *p, const ck_calib_problem_t *q, const double *board_xy,
+                                const double *image_uv, const int32_t *frame_start, int32_t n_points_total, int32_t n_starts_total,
+                                int32_t n_frames_total, const ck_camera_t *cam0, const double *poses0, ck_camera_calib_result_t *res,
+                                double *poses_out) {
+    if (!cam0 || !poses0 || !res || !poses_out || !model_ok(model)) return CK_EINVAL;
+    const int rc = ck_calib_check(p, q, 1, board_xy, image_uv, frame_start, n_points_total, n_starts_total, n_frames_total);
+    if (rc != CK_OK) return rc;
+    ck_opencv5_t k0;
+    ck_calib_result_t r;
+    ck_calib_start_from_camera(model, cam0, &k0);
+    const int rr = refine_host(model, p, q, board_xy, image_uv, frame_start, &k0, poses0, &r, poses_out);
+    if (rr == CK_OK) ck_calib_result_to_camera(model, &r, 0, 1, res);
+    return rr;
 }

@@ -14,9 +14,11 @@
 
 #if defined(__HIPCC__)
 #define CKC_FN static __device__ __forceinline__
+#define CKC_HOST_FN static __host__ __device__ __forceinline__ /* what the launching host code asks too */
 #define CKC_UNROLL _Pragma("unroll")
 #else
 #define CKC_FN static inline
+#define CKC_HOST_FN static inline
 #define CKC_UNROLL
 #endif
 
@@ -106,6 +108,98 @@ CKC_FN void ckc_jacobian(const double *k, const double *P, double X, double Y, d
     Jv[9] = dv[0] * w0[0] + dv[1] * w0[1] + dv[2] * w0[2];
     Jv[10] = dv[0] * w1[0] + dv[1] * w1[1] + dv[2] * w1[2];
     Jv[11] = dv[0] * w2[0] + dv[1] * w2[1] + dv[2] * w2[2];
+}
+
+// The six pose columns of an observation's Jacobian from d(u, v) / d(camera point), as ckc_jacobian forms them (its text is left as it
+// is: the OpenCVModel5 kernel's code must not move)
+CKC_FN void ckc_pose_columns(const double *P, double X, double Y, const double *du, const double *dv, double *Ju, double *Jv) {
+    CKC_UNROLL
+    for (int i = 0; i < 3; i++) {
+        Ju[12 + i] = du[i];
+        Jv[12 + i] = dv[i];
+    }
+    double w0[3], w1[3], w2[3];
+    CKC_UNROLL
+    for (int i = 0; i < 3; i++) {
+        w0[i] = Y * P[3 * i + 2];
+        w1[i] = -(X * P[3 * i + 2]);
+        w2[i] = X * P[3 * i + 1] - Y * P[3 * i];
+    }
+    Ju[9] = du[0] * w0[0] + du[1] * w0[1] + du[2] * w0[2];
+    Ju[10] = du[0] * w1[0] + du[1] * w1[1] + du[2] * w1[2];
+    Ju[11] = du[0] * w2[0] + du[1] * w2[1] + du[2] * w2[2];
+    Jv[9] = dv[0] * w0[0] + dv[1] * w0[1] + dv[2] * w0[2];
+    Jv[10] = dv[0] * w1[0] + dv[1] * w1[1] + dv[2] * w1[2];
+    Jv[11] = dv[0] * w2[0] + dv[1] * w2[1] + dv[2] * w2[2];
+}
+
+// ---- EUCM / UCM ----------------------------------------------------------------------------------------------
+// k[9] = fx fy cx cy alpha beta 0 0 0 in the same nine slots, so the 9-column layout, the Schur complement, the Cayley update and
+// the LM rules are shared.  The slots a model does not have are frozen whatever the caller's mask says: 6..8 for EUCM, and 5 (at
+// 1.0, which the start holds) for UCM; the reduced system gives frozen columns the row of the identity.
+#define CKC_MODEL_OPENCV5 0
+#define CKC_MODEL_EUCM 1
+#define CKC_MODEL_UCM 2
+CKC_HOST_FN unsigned ckc_model_mask(int model) { return model == CKC_MODEL_OPENCV5 ? 0u : (model == CKC_MODEL_UCM ? 0x1E0u : 0x1C0u); }
+CKC_FN double ckc_nan(void) { return __builtin_nan(""); }
+
+// The projection rule: den > 0 and Pz > -w d; parameters outside the model (alpha outside [0, 1], beta <= 0) are never valid.  An
+// observation that is not valid makes the cost NaN, and ckc_lm_decide rejects the step: a candidate is rejected, never clamped.
+CKC_FN int ckc_eucm_valid(const double *k, double den, double d, double Pz) {
+    const double alpha = k[4], beta = k[5];
+    const double w = alpha > 0.5 ? (1.0 - alpha) / alpha : alpha / (1.0 - alpha);
+    return (alpha >= 0.0) & (alpha <= 1.0) & (beta > 0.0) & (den > 0.0) & (Pz > -w * d);
+}
+
+CKC_FN void ckc_residual_eucm(const double *k, const double *P, double X, double Y, double u, double v, double *r) {
+    const double Px = P[0] * X + P[1] * Y + P[9], Py = P[3] * X + P[4] * Y + P[10], Pz = P[6] * X + P[7] * Y + P[11];
+    const double d = sqrt(k[5] * (Px * Px + Py * Py) + Pz * Pz);
+    const double den = k[4] * d + (1.0 - k[4]) * Pz;
+    const int valid = ckc_eucm_valid(k, den, d, Pz); // (selects, not branches: nothing here may end up in scratch memory)
+    r[0] = valid ? k[0] * (Px / den) + k[2] - u : ckc_nan();
+    r[1] = valid ? k[1] * (Py / den) + k[3] - v : ckc_nan();
+}
+
+// columns fx fy cx cy alpha beta (slots 6..8 zero), then the six pose columns, analytically.  An invalid observation: r NaN; its J is
+// what the formulas give and never used (the solver differentiates at accepted parameters only, where the cost is finite)
+CKC_FN void ckc_jacobian_eucm(const double *k, const double *P, double X, double Y, double u, double v, unsigned fixed_mask, double *r,
+                              double *Ju, double *Jv) {
+    const double Px = P[0] * X + P[1] * Y + P[9], Py = P[3] * X + P[4] * Y + P[10], Pz = P[6] * X + P[7] * Y + P[11];
+    const double rho2 = Px * Px + Py * Py;
+    const double d = sqrt(k[5] * rho2 + Pz * Pz);
+    const double den = k[4] * d + (1.0 - k[4]) * Pz;
+    const int valid = ckc_eucm_valid(k, den, d, Pz);
+    const double xn = Px / den, yn = Py / den, id = 1.0 / den;
+    r[0] = valid ? k[0] * xn + k[2] - u : ckc_nan();
+    r[1] = valid ? k[1] * yn + k[3] - v : ckc_nan();
+    // d(den) / d(alpha, beta), d(xn, yn) / d(den) = -(xn, yn) / den
+    const double da = d - Pz, db = (k[4] * rho2) / (2.0 * d);
+    const double xq = xn * id, yq = yn * id;
+    Ju[0] = xn; Ju[1] = 0.0; Ju[2] = 1.0; Ju[3] = 0.0;
+    Ju[4] = -(k[0] * (xq * da)); Ju[5] = -(k[0] * (xq * db)); Ju[6] = 0.0; Ju[7] = 0.0; Ju[8] = 0.0;
+    Jv[0] = 0.0; Jv[1] = yn; Jv[2] = 0.0; Jv[3] = 1.0;
+    Jv[4] = -(k[1] * (yq * da)); Jv[5] = -(k[1] * (yq * db)); Jv[6] = 0.0; Jv[7] = 0.0; Jv[8] = 0.0;
+    CKC_UNROLL
+    for (int i = 0; i < CKC_NK; i++)
+        if ((fixed_mask >> i) & 1u) { Ju[i] = 0.0; Jv[i] = 0.0; }
+    // d(den) / d(camera point), then d(u, v) / d(camera point)
+    const double ab = k[4] * k[5];
+    const double dx = (ab * Px) / d, dy = (ab * Py) / d, dz = (k[4] * Pz) / d + (1.0 - k[4]);
+    double du[3], dv[3];
+    du[0] = k[0] * (id - xq * dx); du[1] = -(k[0] * (xq * dy)); du[2] = -(k[0] * (xq * dz));
+    dv[0] = -(k[1] * (yq * dx)); dv[1] = k[1] * (id - yq * dy); dv[2] = -(k[1] * (yq * dz));
+    ckc_pose_columns(P, X, Y, du, dv, Ju, Jv);
+}
+
+// the two by model: a constant where the kernel calls them (its template argument), a variable in the host twin
+CKC_FN void ckc_residual_of(const int model, const double *k, const double *P, double X, double Y, double u, double v, double *r) {
+    if (model == CKC_MODEL_OPENCV5) ckc_residual(k, P, X, Y, u, v, r);
+    else ckc_residual_eucm(k, P, X, Y, u, v, r);
+}
+CKC_FN void ckc_jacobian_of(const int model, const double *k, const double *P, double X, double Y, double u, double v, unsigned fixed_mask,
+                            double *r, double *Ju, double *Jv) {
+    if (model == CKC_MODEL_OPENCV5) ckc_jacobian(k, P, X, Y, u, v, fixed_mask, r, Ju, Jv);
+    else ckc_jacobian_eucm(k, P, X, Y, u, v, fixed_mask, r, Ju, Jv);
 }
 
 // acc += one observation's share of the normal equations.  SUMMATION ORDER (part of the contract): lane l of a wave of 64 adds the

@@ -223,7 +223,20 @@ struct ck_handle {
     // rig pose refinement (ck_rig_refine.hip, k_rig_refine.hip): allocated by the first refinement call, grown on demand
     struct ck_rig_refine_ws *rig_refine;
     bool fmerge_lds_allowed; // k_fmerge's dynamic LDS limit has been raised on this handle's device
+    // ck_set_camera: while has_camera, the glue and the per-tag pose unproject with `camera` (UCM's k[5] already 1.0) instead of their
+    // params' OpenCVModel5; 0 (the default): nothing about those paths changes
+    int has_camera;
+    ck_camera_t camera;
 };
+
+// the camera a pose kernel takes: the handle's setting, or the params' OpenCVModel5 in ck_camera_t's clothes
+static inline ck_camera_t ck_kernel_camera(const ck_handle *h, const ck_opencv5_t &c) {
+    if (h->has_camera) return h->camera;
+    ck_camera_t cam;
+    cam.model = CK_CAMERA_OPENCV5; cam.pad = 0;
+    cam.k[0] = c.fx; cam.k[1] = c.fy; cam.k[2] = c.cx; cam.k[3] = c.cy; cam.k[4] = c.k1; cam.k[5] = c.k2; cam.k[6] = c.p1; cam.k[7] = c.p2; cam.k[8] = c.k3;
+    return cam;
+}
 
 extern thread_local char ck_err_text[512];
 // The one path of a failed runtime call (ck_api.hip): writes ck_err_text, clears the runtime's per-thread error (the next launch

@@ -252,11 +252,20 @@ __global__ void k_unproject(ck_opencv5_t cam, const double *px, int n, double *b
     bearings[3 * i] = b[0]; bearings[3 * i + 1] = b[1]; bearings[3 * i + 2] = b[2];
     ok[i] = good ? 1 : 0;
 }
+// ... of any camera model (ck_camera_unproject): the bytes of ck_camera_unproject_host
+__global__ void k_camera_unproject(ck_camera_t cam, const double *px, int n, double *bearings, uint8_t *ok) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double b[3];
+    bool good = camera_unproject_one(cam, px[2 * i], px[2 * i + 1], b);
+    bearings[3 * i] = b[0]; bearings[3 * i + 1] = b[1]; bearings[3 * i + 2] = b[2];
+    ok[i] = good ? 1 : 0;
+}
 
 // AprilTags::process glue, one thread per frame: known-tag filter + unprojection -> one SQPnP problem per frame
 struct GlueArgs {
     ck_stage_ws ws;
-    ck_opencv5_t cam;
+    ck_camera_t cam; // the params' OpenCVModel5 or the handle's camera (ck_kernel_camera)
     ck_iso3_t robot_to_cam;
     const ck_field_tag_t *field; int n_field;
     const double *gyro; const uint8_t *has_gyro;
@@ -283,7 +292,7 @@ __global__ void k_glue(GlueArgs a) {
             if (!a.allow_unverified && (uint32_t)dets[i].id >= a.fams[dets[i].family].n_upstream) continue; // not an upstream id
             double b[12];
             bool ok = true;
-            for (int c = 0; c < 4; c++) ok = unproject_one(a.cam, dets[i].p[c][0], dets[i].p[c][1], b + 3 * c) && ok;
+            for (int c = 0; c < 4; c++) ok = camera_unproject_one(a.cam, dets[i].p[c][0], dets[i].p[c][1], b + 3 * c) && ok;
             if (!ok) continue; // lib.rs:324
             tags[nt] = a.field[k].pose;
             for (int q = 0; q < 12; q++) bear[nt * 12 + q] = b[q];
@@ -383,6 +392,35 @@ extern "C" int ck_unproject_opencv5(const ck_opencv5_t *cam, const double *px, i
     return CK_OK;
 }
 
+extern "C" int ck_camera_unproject(const ck_camera_t *cam, const double *px, int32_t n, double *bearings, uint8_t *ok) {
+    const int rc = ck_camera_check(cam);
+    if (rc != CK_OK) return rc;
+    if (!px || !bearings || !ok || n < 0) return CK_EINVAL;
+    if (n == 0) return CK_OK;
+    if (ck_device_count() <= 0) return CK_ENODEVICE;
+    ck_camera_t c = *cam;
+    ckm_effective(cam->model, cam->k, c.k);
+    DevBuf<double> dpx, db; DevBuf<uint8_t> dok;
+    if (dpx.alloc((size_t)2 * n) || db.alloc((size_t)3 * n) || dok.alloc((size_t)n)) return CK_ENOMEM;
+    CK_HIP(hipMemcpy(dpx.p, px, sizeof(double) * 2 * (size_t)n, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_camera_unproject, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, 0, c, dpx.p, n, db.p, dok.p);
+    CK_HIP(hipGetLastError());
+    CK_HIP(hipMemcpy(bearings, db.p, sizeof(double) * 3 * (size_t)n, hipMemcpyDeviceToHost));
+    CK_HIP(hipMemcpy(ok, dok.p, (size_t)n, hipMemcpyDeviceToHost));
+    return CK_OK;
+}
+
+extern "C" int ck_set_camera(ck_handle_t *h, const ck_camera_t *cam) {
+    if (!h) return CK_EINVAL;
+    if (!cam) { h->has_camera = 0; return CK_OK; }
+    const int rc = ck_camera_check(cam);
+    if (rc != CK_OK) return rc; // (the previous setting stays)
+    h->camera = *cam;
+    ckm_effective(cam->model, cam->k, h->camera.k);
+    h->has_camera = 1;
+    return CK_OK;
+}
+
 // k_sqpnp once more on the problems the handle's last ck_process_* call left in its workspace, on `stream` (ck_rig_time_last: what the
 // per-camera path pays for the solve).  It rewrites ws.d_results with the same values.
 int ck_launch_sqpnp_last(ck_handle *h, int n, const ck_sqpnp_params_t *prm, hipStream_t stream) {
@@ -406,7 +444,7 @@ int ck_run_pose(ck_handle *h, int n, const ck_process_params_t *pp, const double
     CK_HIP(hipMemcpyAsync(ws.d_gyro, gyro, sizeof(double) * (size_t)n, hipMemcpyDefault, h->stream));
     CK_HIP(hipMemcpyAsync(ws.d_has_gyro, has_gyro, (size_t)n, hipMemcpyDefault, h->stream));
     GlueArgs g;
-    g.ws = ws; g.cam = pp->cam; g.robot_to_cam = pp->robot_to_cam; g.field = ws.d_field; g.n_field = pp->n_field; g.gyro = ws.d_gyro;
+    g.ws = ws; g.cam = ck_kernel_camera(h, pp->cam); g.robot_to_cam = pp->robot_to_cam; g.field = ws.d_field; g.n_field = pp->n_field; g.gyro = ws.d_gyro;
     g.fams = h->d_fams; g.allow_unverified = pp->allow_unverified_ids;
     g.has_gyro = ws.d_has_gyro; g.sign_change_error = pp->sign_change_error; g.problems = ws.d_problems; g.tags = ws.d_pose_tags;
     g.bearings = ws.d_bearings; g.n = n;

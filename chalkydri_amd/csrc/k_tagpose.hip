@@ -292,6 +292,7 @@ __device__ inline bool second_minimum(const double p[4][3], const double v[4][3]
 
 struct TagPoseArgs {
     ck_tag_pose_params_t pp;
+    ck_camera_t cam;            // pp.cam or the handle's camera (ck_kernel_camera): what the corners are undistorted with
     int n_families;
     const ck_detection_t *dets; // ck_estimate_tag_poses: [n]; ck_last_tag_poses: ws.d_dets [frames][det_cap]
     ck_tag_pose_t *out;         // [n] / [frames][cap_eff]
@@ -316,7 +317,7 @@ __device__ inline void store_invalid(ck_tag_pose_t *o, int id, int family) {
     store_record(o, id, family, 0, 0, z, z, 0.0, z, z, 0.0, z);
 }
 
-__device__ void tag_pose(const ck_detection_t &d, const ck_tag_pose_params_t &pp, int n_families, ck_tag_pose_t *o) {
+__device__ void tag_pose(const ck_detection_t &d, const ck_tag_pose_params_t &pp, const ck_camera_t &cam, int n_families, ck_tag_pose_t *o) {
     const int fam = d.family;
     if (fam < 0 || fam >= n_families) { store_invalid(o, d.id, d.family); return; }
     const double tagsize = fam == 0 ? pp.tagsize[0] : (fam == 1 ? pp.tagsize[1] : (fam == 2 ? pp.tagsize[2] : pp.tagsize[3]));
@@ -329,7 +330,7 @@ __device__ void tag_pose(const ck_detection_t &d, const ck_tag_pose_params_t &pp
         ok = ok && isfinite(u[i]) && isfinite(w[i]);
     }
 #pragma unroll
-    for (int i = 0; i < 4; i++) ok = ok && undistort_one(pp.cam, u[i], w[i], &x[i], &y[i]);
+    for (int i = 0; i < 4; i++) ok = ok && camera_undistort_one(cam, u[i], w[i], &x[i], &y[i]);
     // initial pose from the homography of the normalised points
     double G[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, H[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     ok = ok && square_homography(x, y, G) && square_homography(u, w, H);
@@ -389,19 +390,21 @@ __global__ __launch_bounds__(TP_NT) void k_tagpose(TagPoseArgs a) {
         if (nd > (uint32_t)a.cap_eff) nd = (uint32_t)a.cap_eff;
         if ((uint32_t)k >= nd) { store_invalid(&a.out[i], 0, 0); return; } // past the frame's detections: a zero record
         const ck_detection_t d = a.dets[(size_t)f * a.det_cap + k];
-        tag_pose(d, a.pp, a.n_families, &a.out[i]);
+        tag_pose(d, a.pp, a.cam, a.n_families, &a.out[i]);
     } else {
         const ck_detection_t d = a.dets[i];
-        tag_pose(d, a.pp, a.n_families, &a.out[i]);
+        tag_pose(d, a.pp, a.cam, a.n_families, &a.out[i]);
     }
 }
 
 int check_params(const ck_handle *h, const ck_tag_pose_params_t *pp) {
     const ck_opencv5_t &c = pp->cam;
-    if (!isfinite(c.fx) || !isfinite(c.fy) || !(c.fx > 0.0) || !(c.fy > 0.0)) return CK_EINVAL;
-    const double rest[7] = {c.cx, c.cy, c.k1, c.k2, c.p1, c.p2, c.k3};
-    for (double v : rest)
-        if (!isfinite(v)) return CK_EINVAL;
+    if (!h->has_camera) { // (a camera set on the handle was checked by ck_set_camera; the params' field is ignored then)
+        if (!isfinite(c.fx) || !isfinite(c.fy) || !(c.fx > 0.0) || !(c.fy > 0.0)) return CK_EINVAL;
+        const double rest[7] = {c.cx, c.cy, c.k1, c.k2, c.p1, c.p2, c.k3};
+        for (double v : rest)
+            if (!isfinite(v)) return CK_EINVAL;
+    }
     for (int i = 0; i < h->cfg.n_families; i++)
         if (!isfinite(pp->tagsize[i]) || !(pp->tagsize[i] > 0.0)) return CK_EINVAL;
     if (pp->n_iters < 1 || pp->n_iters > 1000) return CK_EINVAL;
@@ -419,7 +422,7 @@ int alloc_buffers(ck_handle *h) {
 TagPoseArgs make_args(const ck_handle *h, const ck_tag_pose_params_t *pp) {
     TagPoseArgs a;
     memset(&a, 0, sizeof a);
-    a.pp = *pp; a.n_families = h->cfg.n_families; a.out = h->d_tp_out; a.det_cap = h->ws.det_cap;
+    a.pp = *pp; a.cam = ck_kernel_camera(h, pp->cam); a.n_families = h->cfg.n_families; a.out = h->d_tp_out; a.det_cap = h->ws.det_cap;
     return a;
 }
 

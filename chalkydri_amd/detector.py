@@ -159,6 +159,19 @@ def _bind(L):
     L.ck_fieldcal_refine_host.argtypes = [fp] + fcap + [mq, vp, i32] + flay + [vp] + fout
     L.ck_fieldcal_refine_batch.argtypes = [vp, fp] + fcap + [mq, i32, vp, i32] + flay + [vp] + fout
     L.ck_field_calibrate_batch.argtypes = [vp, fp] + fcap + [vp, mq, i32, vp, i32] + flay + fout
+    cm = _P(A.Camera)
+    L.ck_camera_check.argtypes = [cm]
+    L.ck_camera_unproject_host.argtypes = [cm, vp, i32, vp, vp]
+    L.ck_camera_normalize_host.argtypes = [cm, vp, i32, vp, vp]
+    L.ck_camera_project_host.argtypes = [cm, vp, i32, vp, vp]
+    L.ck_camera_unproject.argtypes = [cm, vp, i32, vp, vp]
+    L.ck_set_camera.argtypes = [vp, cm]
+    ccr = _P(A.CameraCalibResult)
+    L.ck_camera_calib_jacobian.argtypes = [i32, cm, vp, vp, vp, i32, C.c_uint32, vp, vp]
+    L.ck_camera_calib_init.argtypes = [i32, cp, cq, vp, vp, vp, i32, i32, i32, i32, cm, vp, _P(i32)]
+    L.ck_camera_calib_refine_host.argtypes = [i32, cp, cq, vp, vp, vp, i32, i32, i32, cm, vp, ccr, vp]
+    L.ck_camera_calib_refine_batch.argtypes = [vp, i32, cp, cq, i32, vp, vp, vp, i32, i32, i32, cm, vp, ccr, vp]
+    L.ck_camera_calibrate_batch.argtypes = [vp, i32, cp, cq, i32, vp, vp, vp, i32, i32, i32, ccr, vp]
     L._ck_bound = True
     return L
 
@@ -396,6 +409,7 @@ class AprilTagDetector:
         check(self._L.ck_create(C.byref(self.cfg), C.byref(h)), "ck_create")
         self._h = h
         self.quad_sigma = 0.0
+        self.camera = None
         if quad_sigma:
             self.set_quad_sigma(quad_sigma)
 
@@ -404,6 +418,12 @@ class AprilTagDetector:
         changed between calls."""
         check(self._L.ck_set_quad_sigma(self._h, float(sigma)), "ck_set_quad_sigma")
         self.quad_sigma = float(sigma)
+
+    def set_camera(self, cam):
+        """The camera model the pose paths unproject with (an A.Camera: chalkydri_amd.camera.camera_from_calib): while one is set,
+        process / tag-pose calls ignore their params' OpenCVModel5.  None restores it.  A refused camera leaves the setting as it was."""
+        check(self._L.ck_set_camera(self._h, None if cam is None else C.byref(cam)), "ck_set_camera")
+        self.camera = cam
 
     def close(self):
         if getattr(self, "_h", None):

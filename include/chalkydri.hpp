@@ -75,6 +75,9 @@ class Handle {
     const ck_config_t &config() const { return cfg_; }
     // AprilTag-3's quad_sigma (chalkydri_hip.h: ck_set_quad_sigma): > 0 blurs, < 0 sharpens the quad image; may change between calls
     void set_quad_sigma(float sigma) { check(ck_set_quad_sigma(h_, sigma), "ck_set_quad_sigma"); }
+    // the camera model the pose paths unproject with (chalkydri_hip.h: ck_set_camera; chalkydri::Camera::raw): while one is set, the
+    // process and tag-pose calls ignore their params' OpenCVModel5.  nullptr restores it; a refused camera leaves the setting as it was
+    void set_camera(const ck_camera_t *cam) { check(ck_set_camera(h_, cam), "ck_set_camera"); }
     // Raw camera frames (chalkydri_hip.h: ck_upload_raw) converted to luma and turned by fmt.orientation on the device, into the
     // staged frames; the handle's width x height is the ORIENTED frame, imgs carry the source's sw x sh (ck_raw_layout)
     void upload_raw(const std::vector<ck_image_u8_t> &imgs, const ck_raw_format_t &fmt) {
@@ -870,6 +873,43 @@ class IngestRing {
     ck_ingest_t *g_ = nullptr;
 };
 
+// A camera model (chalkydri_hip.h: ck_camera_t): what the reference's `calib` blob deserialises into
+// (camera_intrinsic_model::GenericModel, lib.rs:176,256), for the three models this library has.  The factories check their
+// parameters (Panic for what ck_camera_check refuses); the pixel <-> bearing functions are host arithmetic with the device's bytes.
+enum class CameraModel : int32_t { OpenCv5 = CK_CAMERA_OPENCV5, Eucm = CK_CAMERA_EUCM, Ucm = CK_CAMERA_UCM };
+struct Camera {
+    ck_camera_t raw{};
+    static Camera of(CameraModel m, std::initializer_list<double> k) {
+        Camera c;
+        c.raw.model = (int32_t)m;
+        int i = 0;
+        for (double v : k) c.raw.k[i++] = v;
+        if (m == CameraModel::Ucm) c.raw.k[5] = 1.0;
+        check(ck_camera_check(&c.raw), "ck_camera_check");
+        return c;
+    }
+    static Camera opencv5(const ck_opencv5_t &c) { return of(CameraModel::OpenCv5, {c.fx, c.fy, c.cx, c.cy, c.k1, c.k2, c.p1, c.p2, c.k3}); }
+    static Camera eucm(double fx, double fy, double cx, double cy, double alpha, double beta) { return of(CameraModel::Eucm, {fx, fy, cx, cy, alpha, beta}); }
+    static Camera ucm(double fx, double fy, double cx, double cy, double alpha) { return of(CameraModel::Ucm, {fx, fy, cx, cy, alpha}); }
+    CameraModel model() const { return (CameraModel)raw.model; }
+    // px as u0 v0 u1 v1 ... -> unit bearings x0 y0 z0 ...; ok[i] = 0: no bearing (outside the model's valid disc, not converged)
+    std::vector<double> unproject(const std::vector<double> &px, std::vector<uint8_t> *ok = nullptr) const {
+        std::vector<double> b(px.size() / 2 * 3);
+        std::vector<uint8_t> o(px.size() / 2);
+        check(ck_camera_unproject_host(&raw, px.data(), (int32_t)(px.size() / 2), b.data(), o.data()), "ck_camera_unproject_host");
+        if (ok) *ok = o;
+        return b;
+    }
+    // camera points x0 y0 z0 ... -> pixels u0 v0 ...; ok[i] = 0: the point does not project
+    std::vector<double> project(const std::vector<double> &xyz, std::vector<uint8_t> *ok = nullptr) const {
+        std::vector<double> px(xyz.size() / 3 * 2);
+        std::vector<uint8_t> o(xyz.size() / 3);
+        check(ck_camera_project_host(&raw, xyz.data(), (int32_t)(xyz.size() / 3), px.data(), o.data()), "ck_camera_project_host");
+        if (ok) *ok = o;
+        return px;
+    }
+};
+
 // crates/apriltags/src/lib.rs:185-192
 struct RobotToCamOffset { double roll = 0, pitch = 0, yaw = 0, x = 0, y = 0, z = 0; };
 
@@ -882,6 +922,7 @@ class AprilTags {
         std::string family = "tag36h11";       // lib.rs:229
         size_t bits_corrected = 3;              // lib.rs:230
         ck_opencv5_t calib{};                   // "calib" JSON -> OpenCVModel5 (lib.rs:232-238)
+        std::optional<Camera> camera;           // ... or another model of the blob (EUCM, UCM): set on the handle, `calib` is then ignored
         RobotToCamOffset robot_to_cam{};        // "robot_to_cam" JSON (lib.rs:240-254)
         std::map<size_t, sqpnp::Iso3> layout;   // AprilTagFieldLayout::load (field_layout.rs:18-44)
         uint8_t cam_id = 0;                     // lib.rs:256
@@ -904,6 +945,7 @@ class AprilTags {
         }
         if (c.quad_sigma != 0.0f) h_->set_quad_sigma(c.quad_sigma);
         pp_.cam = c.calib;
+        if (c.camera) h_->set_camera(&c.camera->raw);
         pp_.robot_to_cam = sqpnp::SqPnP::create_solver_camera_transform(c.robot_to_cam.x, c.robot_to_cam.y, c.robot_to_cam.z, c.robot_to_cam.roll,
                                                                         c.robot_to_cam.pitch, c.robot_to_cam.yaw).raw(); // lib.rs:247-254
         pp_.field = field_.data();
@@ -1244,6 +1286,37 @@ class Calibrator {
             check(ck_calibrate_batch(h_->get(), &p, &q, 1, bxy_.data(), uv_.data(), starts_.data(), starts_.back(), F + 1, F, &r.result,
                                      F ? r.poses[0].data() : nullptr), "ck_calibrate_batch");
             if ((r.result.status == CK_CALIB_CONVERGED || r.result.status == CK_CALIB_STALLED) && std::isfinite(r.result.rms)) out = r.result.cam;
+        } else {
+            r.result.status = CK_CALIB_DEGENERATE;
+        }
+        if (report) *report = r;
+        clear();
+        return out;
+    }
+
+    // The same for any camera model (ck_camera_calibrate_batch): an EUCM / UCM problem is solved from CK_CAMCAL_STARTS starts in one
+    // launch and the lowest final cost kept (report->result.start).  fixed_mask bits 0..5: fx fy cx cy alpha beta.
+    struct CameraReport {
+        ck_camera_calib_result_t result{};
+        std::vector<std::array<double, 12>> poses;
+    };
+    std::optional<Camera> calibrate(CameraModel model, uint32_t fixed_mask = 0, CameraReport *report = nullptr) {
+        ck_calib_params_t p;
+        ck_calib_params_default(&p, h_->config().width, h_->config().height);
+        p.fixed_mask = fixed_mask;
+        p.min_points_per_frame = std::max(4, min_corners_);
+        const int F = (int)frames();
+        CameraReport r;
+        r.poses.resize(F);
+        std::optional<Camera> out;
+        if (F >= p.min_frames) {
+            const ck_calib_problem_t q{F, 0, 0, 0};
+            check(ck_camera_calibrate_batch(h_->get(), (int32_t)model, &p, &q, 1, bxy_.data(), uv_.data(), starts_.data(), starts_.back(), F + 1, F,
+                                            &r.result, r.poses[0].data()), "ck_camera_calibrate_batch");
+            if ((r.result.status == CK_CALIB_CONVERGED || r.result.status == CK_CALIB_STALLED) && std::isfinite(r.result.rms)) {
+                out.emplace();
+                out->raw = r.result.cam;
+            }
         } else {
             r.result.status = CK_CALIB_DEGENERATE;
         }

@@ -1281,6 +1281,86 @@ const char *ck_comm_library(const ck_comm_t *comm);      /* path of the librccl 
 int ck_unproject_opencv5(const ck_opencv5_t *cam, const double *px, int32_t n, double *bearings,
                          uint8_t *ok);
 
+/* ---- camera models: OpenCVModel5, EUCM, UCM ----------------------------------------------------------------
+ * The Enhanced Unified Camera Model (Khomutenko, Garcia & Martinet 2016) for lenses whose image corners are 70 degrees and
+ * more off axis; UCM is its special case beta = 1, the pinhole alpha = 0.  Projection and closed-form unprojection use only
+ * + - * / sqrt on doubles (csrc/ck_camera_math.h, compiled into the host functions and into the kernels), so the host
+ * functions return the bytes of the device path. */
+enum { CK_CAMERA_OPENCV5 = 0, CK_CAMERA_EUCM = 1, CK_CAMERA_UCM = 2 };
+typedef struct ck_camera {
+    int32_t model;
+    int32_t pad;
+    double k[9]; /* OPENCV5: fx fy cx cy k1 k2 p1 p2 k3 (ck_opencv5_t's order)
+                  * EUCM:    fx fy cx cy alpha beta, k[6..8] = 0
+                  * UCM:     fx fy cx cy alpha; k[5] is read as 1.0 whatever it holds, k[6..8] = 0 */
+} ck_camera_t;
+
+/* CK_EINVAL, in this order: a null pointer; an unknown model; a parameter that is not finite; fx or fy <= 0; for EUCM / UCM
+ * alpha outside [0, 1], beta <= 0, a non-zero k[6..8].  UCM's k[5] is never looked at.  Host arithmetic, no device needed. */
+int ck_camera_check(const ck_camera_t *cam);
+/* Pixels px[n][2] -> unit bearings[n][3]; ok[i] = 0: OPENCV5 did not converge, EUCM / UCM the pixel lies outside the model's
+ * valid disc (alpha > 0.5: r2 >= 1 / (beta (2 alpha - 1))) or the bearing is not finite.  Pure C, no device needed.  For
+ * OPENCV5 the same 50-step fixed-point iteration as the device path.  Errors: ck_camera_check's, a null array, n < 0. */
+int ck_camera_unproject_host(const ck_camera_t *cam, const double *px, int32_t n, double *bearings, uint8_t *ok);
+/* Camera points xyz[n][3] -> pixels px[n][2].  ok[i] = 0 (and the pixel (0, 0)): the point does not project (OPENCV5: Z <= 0;
+ * EUCM / UCM: den <= 0 or Z <= -w d, w = alpha > 0.5 ? (1 - alpha) / alpha : alpha / (1 - alpha)) or the pixel is not finite. */
+int ck_camera_project_host(const ck_camera_t *cam, const double *xyz, int32_t n, double *px, uint8_t *ok);
+/* The normalised points (x, y) = (mx / kz, my / kz) of pixels, what the per-tag pose works on: ok[i] additionally needs
+ * kz > 0 (a pixel more than 90 degrees off axis has a bearing but no normalised point).  OPENCV5: the undistorted point. */
+int ck_camera_normalize_host(const ck_camera_t *cam, const double *px, int32_t n, double *xy, uint8_t *ok);
+/* The device counterpart of ck_unproject_opencv5, one thread per point: the bytes of ck_camera_unproject_host for every
+ * model and, for OPENCV5, of ck_unproject_opencv5.  CK_ENODEVICE without a device (after the argument checks). */
+int ck_camera_unproject(const ck_camera_t *cam, const double *px, int32_t n, double *bearings, uint8_t *ok);
+/* ---- intrinsic calibration of any camera model ---------------------------------------------------------------
+ * The five calibration entry points again, taking the model (CK_CAMERA_*) and ck_camera_t; the arrays, the problem records, the
+ * params, the checks and the LM rules are ck_calib_*'s.  EUCM / UCM keep fx fy cx cy alpha beta in the first six of the solver's
+ * nine parameter slots: fixed_mask bits 0..5 freeze them, slots 6..8 are always frozen, and UCM also freezes slot 5 at 1.0.  An
+ * observation that does not project (ck_camera_project_host's rule) and a candidate with alpha outside [0, 1] or beta <= 0 make the
+ * cost NaN: the step is rejected, never clamped; a start like that is DEGENERATE.  With model == CK_CAMERA_OPENCV5 every call
+ * returns what its ck_calib_* counterpart returns, byte for byte.  CK_EINVAL also for an unknown model. */
+#define CK_CAMCAL_STARTS 6
+typedef struct ck_camera_calib_result {
+    ck_camera_t cam;               /* the best accepted parameters (UCM: k[5] = 1.0) */
+    int32_t status, iters, n_frames, n_points;
+    double rms, cost0, cost;       /* as ck_calib_result_t */
+    int32_t start, n_starts;       /* ck_camera_calibrate_batch: the start this result came from, of how many; otherwise 0 of 1 */
+} ck_camera_calib_result_t;
+/* J_out [n][2][15]: columns fx fy cx cy alpha beta 0 0 0, then the six pose columns (OPENCV5: ck_calib_jacobian's). */
+int ck_camera_calib_jacobian(int32_t model, const ck_camera_t *cam, const double *pose, const double *board_xy, const double *image_uv,
+                             int32_t n, uint32_t fixed_mask, double *r_out, double *J_out);
+/* Start `start_index` of a problem, on the host.  OPENCV5 has one start, ck_calib_init's.  EUCM / UCM have CK_CAMCAL_STARTS,
+ * because the pinhole start alone is not usable on wide lenses: 0 = ck_calib_init's focal lengths, 1..5 = fx = fy = {0.3, 0.45,
+ * 0.65, 1.0, 1.5} * max(width, height); every one with the principal point at the image centre, alpha = 0.5, beta = 1, and each
+ * frame's pose from its DLT homography and that K.  *status_out as ck_calib_init.  CK_EINVAL also for a start_index outside the
+ * model's starts. */
+int ck_camera_calib_init(int32_t model, const ck_calib_params_t *p, const ck_calib_problem_t *problem, const double *board_xy,
+                         const double *image_uv, const int32_t *frame_start, int32_t n_points_total, int32_t n_starts_total,
+                         int32_t n_frames_total, int32_t start_index, ck_camera_t *cam0_out, double *poses0, int32_t *status_out);
+/* One problem from one start on the host, one thread: the bitwise specification of ck_camera_calib_refine_batch. */
+int ck_camera_calib_refine_host(int32_t model, const ck_calib_params_t *p, const ck_calib_problem_t *problem, const double *board_xy,
+                                const double *image_uv, const int32_t *frame_start, int32_t n_points_total, int32_t n_starts_total,
+                                int32_t n_frames_total, const ck_camera_t *cam0, const double *poses0, ck_camera_calib_result_t *result,
+                                double *poses_out);
+/* n_problems problems, each from its start cams0[i], one workgroup of 256 threads per problem: ck_camera_calib_refine_host's bytes. */
+int ck_camera_calib_refine_batch(ck_handle_t *h, int32_t model, const ck_calib_params_t *p, const ck_calib_problem_t *problems,
+                                 int32_t n_problems, const double *board_xy, const double *image_uv, const int32_t *frame_start,
+                                 int32_t n_points_total, int32_t n_starts_total, int32_t n_frames_total, const ck_camera_t *cams0,
+                                 const double *poses0, ck_camera_calib_result_t *results, double *poses_out);
+/* Every problem from every start of its model (ck_camera_calib_init), all of them in one launch; per problem the result with the
+ * lowest finite final cost (ties: the lowest start), its poses in poses_out, `start` and `n_starts` in the record.  A problem
+ * none of whose starts can be evaluated is DEGENERATE (start 0's record) and does not disturb its neighbours.  CK_ECAPACITY
+ * also when n_starts x n_frames_total passes 2^31. */
+int ck_camera_calibrate_batch(ck_handle_t *h, int32_t model, const ck_calib_params_t *p, const ck_calib_problem_t *problems,
+                              int32_t n_problems, const double *board_xy, const double *image_uv, const int32_t *frame_start,
+                              int32_t n_points_total, int32_t n_starts_total, int32_t n_frames_total,
+                              ck_camera_calib_result_t *results, double *poses_out);
+
+/* A handle setting, like ck_set_quad_sigma.  While a camera is set, ck_process_batch_device, ck_process_uploaded,
+ * ck_process_ingested, ck_estimate_tag_poses and ck_last_tag_poses use it instead of their params' `cam` field, which is then
+ * ignored (and not checked).  NULL restores the params' field.  A refused camera (ck_camera_check) leaves the previous
+ * setting in place.  What reads the glue's bearings in place (ck_rig_process_last*, ck_last_pose_inputs) inherits the model. */
+int ck_set_camera(ck_handle_t *h, const ck_camera_t *cam);
+
 /* fp64 conformance probe used by the parity tests: out[i] = op(a[i], b[i]) computed on the device with
  * the same flags as the kernels. op: 0 add, 1 mul, 2 div, 3 sqrt(a), 4 a*b+c style unfused (a*b)+a. */
 int ck_selftest_fp64(ck_handle_t *h, int32_t op, const double *a, const double *b, int32_t n,
