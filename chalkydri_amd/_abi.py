@@ -125,6 +125,33 @@ class Camera(C.Structure):
     _fields_ = [("model", C.c_int32), ("pad", C.c_int32), ("k", C.c_double * 9)]
 
 
+CK_SUBPIX_CONVERGED, CK_SUBPIX_MAXIT, CK_SUBPIX_FLAT, CK_SUBPIX_REJECTED = 0, 1, 2, 3
+
+
+class SubpixParams(C.Structure):
+    """ck_subpix_params_t"""
+    _fields_ = [("half_win", C.c_int32), ("max_iters", C.c_int32), ("eps", C.c_double), ("det_min", C.c_double)]
+
+
+class SubpixInfo(C.Structure):
+    """ck_subpix_info_t"""
+    _fields_ = [("status", C.c_int32), ("iters", C.c_int32), ("shift", C.c_double)]
+
+
+class BoardDesc(C.Structure):
+    """ck_board_t"""
+    _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("first_id", C.c_int32), ("family", C.c_int32),
+                ("tag_size", C.c_double), ("tag_spacing", C.c_double)]
+
+
+class BoardParams(C.Structure):
+    """ck_board_params_t"""
+    _fields_ = [("seed_max_shift", C.c_double), ("max_shift", C.c_double), ("probe", C.c_double * 2), ("agree", C.c_double)]
+
+
+assert C.sizeof(SubpixParams) == 24 and C.sizeof(SubpixInfo) == 16 and C.sizeof(BoardDesc) == 32 and C.sizeof(BoardParams) == 40
+
+
 class TagPoseParams(C.Structure):
     _fields_ = [("cam", OpenCV5), ("tagsize", C.c_double * CK_MAX_FAMILIES), ("n_iters", C.c_int32), ("pad", C.c_int32)]
 

@@ -33,14 +33,16 @@ def load_field_layout(path_or_dict):
 class AprilTags:
     def __init__(self, width, height, field, calib, robot_to_cam, cam_id=0, family="tag36h11", bits_corrected=3,
                  max_batch=1, device=0, quad_sigma=0.0, fourcc=None, orientation="none", auto_exposure=False, exposure0=1.0,
-                 exposure_params=None, jpeg_color=False, **cfg):
+                 exposure_params=None, jpeg_color=False, corner_subpix=None, **cfg):
         """width x height is the image the detector sees, and calib its intrinsics: with an `orientation` ("none", "clockwise",
         "rotate-180", "counterclockwise": the reference's VideoOrientation names) those of the ORIENTED image.  `fourcc` names the
         raw format of the camera's frames for process_raw_batch ("YUYV", "RGB3", ...; None: 8-bit luma), or "MJPG" / "JPEG": the
         camera delivers one JPEG per frame (what the reference's USB cameras do at full rate), decoded and turned on the device;
         with jpeg_color=True the decode keeps the frames' chroma on the device, so that preview(color=True) works for them too.
         auto_exposure=True (the reference's Camera.auto_exposure) meters the last frame of every batch the task stages, on the
-        device, and keeps the exposure to set next in `exposure` (unit and start: exposure0); off, nothing is launched."""
+        device, and keeps the exposure to set next in `exposure` (unit and start: exposure0); off, nothing is launched.
+        corner_subpix=True (or a dict of AprilTagDetector.set_corner_subpix's arguments) refines every detection's corners to
+        sub-pixel accuracy on the device before the pose is solved; off (the default), nothing is launched."""
         if fourcc in A.JPEG_FOURCCS:
             from .detector import orientation_code
             orientation_code(orientation)                           # (ValueError for an unknown name, before any device work)
@@ -54,7 +56,7 @@ class AprilTags:
         # argument order of the reference call (lib.rs:247-254): x, y, z, roll, pitch, yaw
         self.robot_to_cam = SqPnP.create_solver_camera_transform(r2c["x"], r2c["y"], r2c["z"], r2c["roll"], r2c["pitch"], r2c["yaw"])
         self.detector = AprilTagDetector(width, height, max_batch=max_batch, families=(family,), bits_corrected=bits_corrected,
-                                         device=device, quad_sigma=quad_sigma, **cfg)
+                                         device=device, quad_sigma=quad_sigma, corner_subpix=corner_subpix, **cfg)
         if self.camera.model != A.CK_CAMERA_OPENCV5:
             self.detector.set_camera(self.camera)
         self.solver = SqPnP(self.detector)

@@ -255,14 +255,21 @@ def project(k, pose, board_xy, model="OpenCVModel5"):
 class Calibrator:
     """Calibrator::{new, process, clear, calibrate} of the reference, with `det` an AprilTagDetector of the camera's geometry."""
 
-    def __init__(self, det, board=None, min_corners=MIN_CORNERS):
+    def __init__(self, det, board=None, min_corners=MIN_CORNERS, recover=False, subpix=None, board_params=None):
+        """recover=True: `process` recovers the whole board from the tags that decoded (AprilTagDetector.board_corners: the tags'
+        corners refined to sub-pixel accuracy, their neighbours predicted, refined and checked), which on an AprilGrid — black
+        squares at the tags' corners — finds several times the tags at a third of the corner error; `subpix` (an A.SubpixParams)
+        and `board_params` (an A.BoardParams) are its settings.  recover=False is the reference's path."""
         self.det, self.board, self.min_corners = det, board or Board.default_6x6(), int(min_corners)
+        self.recover, self.subpix, self.board_params = bool(recover), subpix, board_params
         self._ids = set(self.board.ids())
         self._frames = []
 
     def process(self, frames):
         """Detects the board in frames [n][h][w] (or one [h][w]) and keeps every frame with at least min_corners corners of the
         board's ids decoded without a corrected bit; returns the number of frames kept so far, like the reference."""
+        if self.recover:
+            return self._process_recover(frames)
         for dets in self.det.detect_batch(frames, cap=max(64, len(self._ids))):
             seen, b, u = set(), [], []
             for d in dets:
@@ -272,6 +279,19 @@ class Calibrator:
                     u.append(d.corners())
             if 4 * len(seen) >= self.min_corners:
                 self._frames.append((np.concatenate(b), np.concatenate(u)))
+        return len(self._frames)
+
+    def _process_recover(self, frames):
+        frames = np.asarray(frames)
+        frames = frames[None] if frames.ndim == 2 else frames
+        ids = list(self.board.ids())
+        for i0 in range(0, len(frames), self.det.max_batch):
+            self.det.detect_batch(frames[i0:i0 + self.det.max_batch], cap=max(64, len(ids)))
+            uv, state = self.det.board_corners(self.board, self.subpix, self.board_params)
+            for f in range(len(uv)):
+                known = np.nonzero(state[f])[0]
+                if 4 * len(known) >= self.min_corners:
+                    self._frames.append((np.concatenate([self.board.tag_corners(ids[t]) for t in known]), uv[f, known].reshape(-1, 2).copy()))
         return len(self._frames)
 
     def add_observations(self, board_xy, image_uv):

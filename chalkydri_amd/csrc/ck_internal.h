@@ -227,6 +227,17 @@ struct ck_handle {
     // params' OpenCVModel5; 0 (the default): nothing about those paths changes
     int has_camera;
     ck_camera_t camera;
+    // ck_set_corner_subpix: while has_subpix, the detections a pipeline call leaves in ws.d_dets get their corners refined on the frame
+    // the call was given (ck_subpix.hip: k_subpix_dets, launched by run_tail); 0 (the default): no launch is added
+    int has_subpix;
+    ck_subpix_params_t subpix;
+    // sub-pixel corners (ck_subpix.hip): the weight tables and the staging of its calls, allocated by the first of them
+    struct ck_subpix_ws *subpix_ws;
+    // the full-resolution frames of the call that left n_last_dets detections (what ck_board_corners_last reads): the staged frames,
+    // an ingest slot, or the caller's device memory, which has to be there still
+    const uint8_t *last_img_p;
+    int last_img_stride;
+    size_t last_img_pitch;
 };
 
 // the camera a pose kernel takes: the handle's setting, or the params' OpenCVModel5 in ck_camera_t's clothes

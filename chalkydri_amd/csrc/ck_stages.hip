@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "ck_internal.h"
+#include "ck_subpix.h"
 
 static int next_pow2(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 
@@ -213,6 +214,7 @@ static int run_tail(ck_handle *h, const ck_dev_image &img, int n, int upto, bool
     if (events) CK_HIP(hipEventRecord(ev[4], h->stream));
     if (upto >= 3) {
         rc = ck_launch_decode(h, fine, n);
+        if (rc == CK_OK) rc = ck_launch_subpix_dets(h, img, n); // ck_set_corner_subpix: on the unfiltered frame (nothing when off)
         if (rc != CK_OK) return rc;
     }
     if (events) CK_HIP(hipEventRecord(ev[5], h->stream));
@@ -234,6 +236,7 @@ static int run_pipeline(ck_handle *h, const ck_dev_image &img, int n, int upto /
     hipEvent_t *ev = h->ev;
     h->n_last_dets = -1; // the workspace is rewritten from here on; it holds this call's detections only once they are all enqueued
     h->n_pose_inputs = -1;
+    h->last_img_p = img.p; h->last_img_stride = img.stride; h->last_img_pitch = img.pitch;
     CK_HIP(hipEventRecord(ev[1], h->stream));
     int rc = ck_run_threshold_segment(h, img, n);
     if (rc != CK_OK) return rc;

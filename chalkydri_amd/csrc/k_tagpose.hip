@@ -11,6 +11,8 @@
 
 #include "ck_internal.h"
 #include "ck_mat3.h"
+#define CKS_HOMOGRAPHY_ONLY
+#include "ck_subpix_math.h"
 
 namespace {
 
@@ -94,22 +96,9 @@ __device__ inline bool finite9(const double m[9]) {
     return ok;
 }
 
-// The projective map of the tag square S_i = (-1,1), (1,1), (1,-1), (-1,-1) onto the points (x_i, y_i), row-major, up to scale:
-// Heckbert's unit-square mapping composed with (u, v) = ((X + 1) / 2, (1 - Y) / 2), which sends S_i to the unit square's
-// (0,0), (1,0), (1,1), (0,1).  false when the points do not define one (den == 0, or anything non-finite).
-__device__ inline bool square_homography(const double x[4], const double y[4], double G[9]) {
-    const double sx = x[0] - x[1] + x[2] - x[3], sy = y[0] - y[1] + y[2] - y[3];
-    const double dx1 = x[1] - x[2], dx2 = x[3] - x[2], dy1 = y[1] - y[2], dy2 = y[3] - y[2];
-    const double den = dx1 * dy2 - dx2 * dy1;
-    if (den == 0.0) return false;
-    const double g = (sx * dy2 - dx2 * sy) / den, hh = (dx1 * sy - sx * dy1) / den;
-    const double a = x[1] - x[0] + g * x[1], b = x[3] - x[0] + hh * x[3], c = x[0];
-    const double d = y[1] - y[0] + g * y[1], e = y[3] - y[0] + hh * y[3], f = y[0];
-    G[0] = 0.5 * a; G[1] = -0.5 * b; G[2] = 0.5 * (a + b) + c;
-    G[3] = 0.5 * d; G[4] = -0.5 * e; G[5] = 0.5 * (d + e) + f;
-    G[6] = 0.5 * g; G[7] = -0.5 * hh; G[8] = 0.5 * (g + hh) + 1.0;
-    return finite9(G);
-}
+// The projective map of the tag square onto four points (ck_subpix_math.h: the corner refinement recomputes a detection's centre with
+// the same text)
+__device__ inline bool square_homography(const double x[4], const double y[4], double G[9]) { return cks_square_homography(x, y, G) != 0; }
 
 // One orthogonal-iteration run from R (AprilTag-3's orthogonal_iteration): n_iters steps, no early exit; t of the last step
 // predates its rotation update.  p: object points (p_mean is 0 exactly for the square), F: v v^T / v^T v, Minv: (I - mean F)^-1.

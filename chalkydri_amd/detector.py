@@ -172,6 +172,17 @@ def _bind(L):
     L.ck_camera_calib_refine_host.argtypes = [i32, cp, cq, vp, vp, vp, i32, i32, i32, cm, vp, ccr, vp]
     L.ck_camera_calib_refine_batch.argtypes = [vp, i32, cp, cq, i32, vp, vp, vp, i32, i32, i32, cm, vp, ccr, vp]
     L.ck_camera_calibrate_batch.argtypes = [vp, i32, cp, cq, i32, vp, vp, vp, i32, i32, i32, ccr, vp]
+    sx, sb, sq = _P(A.SubpixParams), _P(A.BoardDesc), _P(A.BoardParams)
+    L.ck_subpix_params_default.argtypes = [sx]
+    L.ck_subpix_params_default.restype = None
+    L.ck_subpix_weights.argtypes = [sx, vp]
+    L.ck_corner_subpix.argtypes = [vp, sx, vp, vp, i32, vp, vp]
+    L.ck_corner_subpix_host.argtypes = [sx, _P(A.ImageU8), i32, vp, vp, i32, vp, vp]
+    L.ck_set_corner_subpix.argtypes = [vp, sx]
+    L.ck_board_params_default.argtypes = [sq]
+    L.ck_board_params_default.restype = None
+    L.ck_board_corners_last.argtypes = [vp, sb, sx, sq, vp, vp, vp]
+    L.ck_board_corners_host.argtypes = [sb, sx, sq, _P(A.ImageU8), i32, vp, i32, vp, vp, vp, vp]
     L._ck_bound = True
     return L
 
@@ -399,7 +410,8 @@ class MjpegStream:
 class AprilTagDetector:
     """One handle = one GPU + its stream; not thread-safe (mirrors `&mut self`)."""
 
-    def __init__(self, width, height, max_batch=1, families=("tag36h11",), bits_corrected=3, device=0, quad_sigma=0.0, **cfg):
+    def __init__(self, width, height, max_batch=1, families=("tag36h11",), bits_corrected=3, device=0, quad_sigma=0.0,
+                 corner_subpix=None, **cfg):
         self._L = _bind(lib())
         self.cfg = default_config(width, height, max_batch, families, max_hamming=bits_corrected, device=device,
                                   **cfg)
@@ -410,8 +422,11 @@ class AprilTagDetector:
         self._h = h
         self.quad_sigma = 0.0
         self.camera = None
+        self.corner_subpix_params = None
         if quad_sigma:
             self.set_quad_sigma(quad_sigma)
+        if corner_subpix:
+            self.set_corner_subpix(**({} if corner_subpix is True else dict(corner_subpix)))
 
     def set_quad_sigma(self, sigma):
         """AprilTag-3's quad_sigma: > 0 blurs, < 0 sharpens the image the quad stages run on; |sigma| < 0.5 is off.  May be
@@ -424,6 +439,44 @@ class AprilTagDetector:
         process / tag-pose calls ignore their params' OpenCVModel5.  None restores it.  A refused camera leaves the setting as it was."""
         check(self._L.ck_set_camera(self._h, None if cam is None else C.byref(cam)), "ck_set_camera")
         self.camera = cam
+
+    def set_corner_subpix(self, half_win=None, max_iters=None, eps=None, det_min=None, on=True):
+        """Sub-pixel refinement of every final detection's corners inside the detect / process calls (ck_set_corner_subpix): a
+        gradient-orthogonality iteration over a window of (2 half_win + 1)^2 taps on the full-resolution frame, which rewrites
+        the corners and the centre, so everything downstream inherits them.  Off by default; on=False turns it off again.  A
+        window wider than the blur of the lens helps, a narrower one can hurt: half_win is the caller's choice (default 5)."""
+        from .subpix import subpix_params
+        pp = subpix_params(half_win, max_iters, eps, det_min) if on else None
+        check(self._L.ck_set_corner_subpix(self._h, None if pp is None else C.byref(pp)), "ck_set_corner_subpix")
+        self.corner_subpix_params = pp
+
+    def corner_subpix(self, frame, xy, params=None, return_info=False):
+        """Refines points xy [n][2] (pixels, the detections' convention) of the staged frames on the device (ck_corner_subpix);
+        frame: the staged frame of every point (an int for all of them, or [n]).  Returns [n][2], with return_info also the
+        status, iteration count and shift of every point as a structured array."""
+        from .subpix import INFO_DTYPE, subpix_params
+        pp = params or self.corner_subpix_params or subpix_params()
+        xy = np.ascontiguousarray(xy, np.float64).reshape(-1, 2)
+        n = len(xy)
+        fr = np.ascontiguousarray(np.broadcast_to(np.asarray(frame, np.int32), (n,)))
+        out, info = np.empty((n, 2)), np.zeros(n, INFO_DTYPE)
+        check(self._L.ck_corner_subpix(self._h, C.byref(pp), fr.ctypes.data, xy.ctypes.data, n, out.ctypes.data, info.ctypes.data),
+              "ck_corner_subpix")
+        return (out, info) if return_info else out
+
+    def board_corners(self, board, params=None, board_params=None, family=0):
+        """Recovers a tag board (a calibration.Board) in every frame of the last detect / process call from the tags that decoded
+        (ck_board_corners_last): (uv [n][rows * cols][4][2], state [n][rows * cols]: 0 absent, 1 seed, 2 recovered)."""
+        from .subpix import board_desc, board_params as default_bp, subpix_params
+        pp = params or self.corner_subpix_params or subpix_params()
+        bd, bp = board_desc(board, family), board_params or default_bp()
+        nt, nb = board.rows * board.cols, self.max_batch
+        uv, state = np.zeros((nb, nt, 4, 2)), np.zeros((nb, nt), np.uint8)
+        counts = np.full(nb, -1, np.int32)  # the call writes one count per frame of the last call: the rest stay -1
+        check(self._L.ck_board_corners_last(self._h, C.byref(bd), C.byref(pp), C.byref(bp), uv.ctypes.data, state.ctypes.data,
+                                            counts.ctypes.data), "ck_board_corners_last")
+        n = int((counts >= 0).sum())
+        return uv[:n], state[:n]
 
     def close(self):
         if getattr(self, "_h", None):

@@ -78,6 +78,9 @@ class Handle {
     // the camera model the pose paths unproject with (chalkydri_hip.h: ck_set_camera; chalkydri::Camera::raw): while one is set, the
     // process and tag-pose calls ignore their params' OpenCVModel5.  nullptr restores it; a refused camera leaves the setting as it was
     void set_camera(const ck_camera_t *cam) { check(ck_set_camera(h_, cam), "ck_set_camera"); }
+    // sub-pixel refinement of every final detection's corners inside the detect / process calls (chalkydri_hip.h:
+    // ck_set_corner_subpix); nullptr = off, the default.  A refused parameter set leaves the setting as it was
+    void set_corner_subpix(const ck_subpix_params_t *pp) { check(ck_set_corner_subpix(h_, pp), "ck_set_corner_subpix"); }
     // Raw camera frames (chalkydri_hip.h: ck_upload_raw) converted to luma and turned by fmt.orientation on the device, into the
     // staged frames; the handle's width x height is the ORIENTED frame, imgs carry the source's sw x sh (ck_raw_layout)
     void upload_raw(const std::vector<ck_image_u8_t> &imgs, const ck_raw_format_t &fmt) {
@@ -1229,6 +1232,62 @@ struct Board {
     }
 };
 
+// ---- sub-pixel corners (chalkydri_hip.h: ck_corner_subpix, ck_board_corners_last) -----------------------------
+inline ck_subpix_params_t subpix_params(int half_win = 5) {
+    ck_subpix_params_t pp;
+    ck_subpix_params_default(&pp);
+    pp.half_win = half_win;
+    return pp;
+}
+// points xy (x0 y0 x1 y1 ...) of the staged frames, point i in frame frames[i] (empty: all in frame 0), refined on the device
+inline std::vector<double> corner_subpix(Handle &h, const ck_subpix_params_t &pp, const std::vector<int32_t> &frames, const std::vector<double> &xy,
+                                         std::vector<ck_subpix_info_t> *info = nullptr) {
+    if (xy.size() % 2 || (!frames.empty() && frames.size() != xy.size() / 2)) throw Panic("corner_subpix: size mismatch", CK_EINVAL);
+    const int32_t n = (int32_t)(xy.size() / 2);
+    std::vector<double> out(xy.size());
+    if (info) info->assign((size_t)n, ck_subpix_info_t{});
+    check(ck_corner_subpix(h.get(), &pp, frames.empty() ? nullptr : frames.data(), xy.data(), n, out.data(), info ? info->data() : nullptr), "ck_corner_subpix");
+    return out;
+}
+// the same on host images, one thread: the bytes of corner_subpix
+inline std::vector<double> corner_subpix_host(const ck_subpix_params_t &pp, const std::vector<ck_image_u8_t> &imgs, const std::vector<int32_t> &frames,
+                                              const std::vector<double> &xy, std::vector<ck_subpix_info_t> *info = nullptr) {
+    if (xy.size() % 2 || (!frames.empty() && frames.size() != xy.size() / 2)) throw Panic("corner_subpix_host: size mismatch", CK_EINVAL);
+    const int32_t n = (int32_t)(xy.size() / 2);
+    std::vector<double> out(xy.size());
+    if (info) info->assign((size_t)n, ck_subpix_info_t{});
+    check(ck_corner_subpix_host(&pp, imgs.data(), (int32_t)imgs.size(), frames.empty() ? nullptr : frames.data(), xy.data(), n, out.data(),
+                                info ? info->data() : nullptr), "ck_corner_subpix_host");
+    return out;
+}
+// A board recovered from the tags that decoded, in the n_frames frames of the handle's last detect / process call
+struct BoardCorners {
+    int n_frames = 0, n_tags_per_frame = 0;
+    std::vector<double> uv;       // [n_frames][rows * cols][4][2]
+    std::vector<uint8_t> state;   // [n_frames][rows * cols]: 0 absent, 1 seed, 2 recovered
+    std::vector<int32_t> n_tags;  // [n_frames]
+};
+inline ck_board_t board_desc(const Board &b, int family = 0) { return ck_board_t{b.rows, b.cols, b.first_id, family, b.tag_size, b.tag_spacing}; }
+inline BoardCorners board_corners(Handle &h, const Board &board, const ck_subpix_params_t *pp = nullptr, const ck_board_params_t *bp = nullptr) {
+    ck_subpix_params_t p = pp ? *pp : subpix_params();
+    ck_board_params_t q;
+    ck_board_params_default(&q);
+    if (bp) q = *bp;
+    const ck_board_t bd = board_desc(board);
+    BoardCorners r;
+    const int nb = h.config().max_batch;
+    r.n_tags_per_frame = board.rows * board.cols;
+    r.uv.assign((size_t)nb * r.n_tags_per_frame * 8, 0.0);
+    r.state.assign((size_t)nb * r.n_tags_per_frame, 0);
+    r.n_tags.assign((size_t)nb, -1); // the call writes one count per frame of the last call: the rest stay -1
+    check(ck_board_corners_last(h.get(), &bd, &p, &q, r.uv.data(), r.state.data(), r.n_tags.data()), "ck_board_corners_last");
+    while (r.n_frames < nb && r.n_tags[(size_t)r.n_frames] >= 0) r.n_frames++;
+    r.uv.resize((size_t)r.n_frames * r.n_tags_per_frame * 8);
+    r.state.resize((size_t)r.n_frames * r.n_tags_per_frame);
+    r.n_tags.resize((size_t)r.n_frames);
+    return r;
+}
+
 class Calibrator {
   public:
     static constexpr int MIN_CORNERS = 24; // calibration.rs:30
@@ -1236,8 +1295,10 @@ class Calibrator {
         ck_calib_result_t result{};
         std::vector<std::array<double, 12>> poses; // board -> camera per kept frame: R row-major, t
     };
-    explicit Calibrator(std::shared_ptr<Handle> h, const Board &board = Board(), int min_corners = MIN_CORNERS)
-        : h_(std::move(h)), board_(board), min_corners_(min_corners) {}
+    // recover: process() recovers the whole board from the tags that decoded (board_corners), every seed and recovered tag's four
+    // refined corners kept; false (the default) is the reference's path
+    explicit Calibrator(std::shared_ptr<Handle> h, const Board &board = Board(), int min_corners = MIN_CORNERS, bool recover = false)
+        : h_(std::move(h)), board_(board), min_corners_(min_corners), recover_(recover) {}
 
     // Detects the board in the frames and keeps each one with at least min_corners corners of the board's ids decoded without a
     // corrected bit; returns the number of frames kept so far, like the reference
@@ -1246,6 +1307,20 @@ class Calibrator {
         std::vector<ck_detection_t> dets((size_t)n * cap);
         std::vector<int32_t> counts(n);
         check(ck_detect_batch(h_->get(), imgs.data(), n, dets.data(), cap, counts.data(), nullptr), "ck_detect_batch");
+        if (recover_) {
+            const BoardCorners r = board_corners(*h_, board_);
+            for (int i = 0; i < r.n_frames; i++) {
+                std::vector<double> b, u;
+                for (int t = 0; t < r.n_tags_per_frame; t++) {
+                    if (!r.state[(size_t)i * r.n_tags_per_frame + t]) continue;
+                    const auto c = board_.tag_corners(board_.first_id + t);
+                    const double *q = &r.uv[((size_t)i * r.n_tags_per_frame + t) * 8];
+                    for (int j = 0; j < 4; j++) { b.push_back(c[j][0]); b.push_back(c[j][1]); u.push_back(q[2 * j]); u.push_back(q[2 * j + 1]); }
+                }
+                if ((int)b.size() / 2 >= min_corners_) add_observations(b, u);
+            }
+            return starts_.size() - 1;
+        }
         for (int i = 0; i < n; i++) {
             std::vector<double> b, u;
             std::vector<int> seen;
@@ -1329,6 +1404,7 @@ class Calibrator {
     std::shared_ptr<Handle> h_;
     Board board_;
     int min_corners_;
+    bool recover_ = false;
     std::vector<double> bxy_, uv_;
     std::vector<int32_t> starts_{0};
 };

@@ -471,7 +471,8 @@ int ck_estimate_tag_poses(ck_handle_t *h, const ck_tag_pose_params_t *pp, const 
  * holds no such call's result: no detect / process call since ck_create, a failed one, or a later call that rewrote the
  * workspace: ck_clusters_batch, ck_quads_batch and ck_decode_quads_batch.  ck_upload_frames, ck_upload_raw, ck_upload_raw_device, ck_raw_luma_batch, ck_threshold_batch, ck_segment_batch,
  * ck_quad_image_batch, ck_time_threshold_segment, ck_set_quad_sigma, ck_sqpnp_solve_batch, ck_gather_poses, ck_preview_jpeg,
- * ck_preview_luma, the ck_preview_*color* calls, ck_exposure_stats, ck_exposure_stats_ingested, the ck_cat_*
+ * ck_preview_luma, the ck_preview_*color* calls, ck_exposure_stats, ck_exposure_stats_ingested, ck_corner_subpix, ck_set_corner_subpix,
+ * ck_board_corners_last, the ck_cat_*
  * calls (ck_cat_tri_otsu and ck_cat_tri_otsu_batch among them) and the ck_ingest_write / ck_ingest_submit calls leave it as it is. */
 int ck_last_tag_poses(ck_handle_t *h, const ck_tag_pose_params_t *pp, ck_tag_pose_t *out, int32_t cap_per_frame,
                       int32_t *counts);
@@ -1360,6 +1361,82 @@ int ck_camera_calibrate_batch(ck_handle_t *h, int32_t model, const ck_calib_para
  * ignored (and not checked).  NULL restores the params' field.  A refused camera (ck_camera_check) leaves the previous
  * setting in place.  What reads the glue's bearings in place (ck_rig_process_last*, ck_last_pose_inputs) inherits the model. */
 int ck_set_camera(ck_handle_t *h, const ck_camera_t *cam);
+
+/* ---- sub-pixel corners: gradient-orthogonality refinement and board recovery -------------------------------
+ * The refinement looks at the pixels around a corner again (Förstner & Gülch 1987; OpenCV's cornerSubPix, ArUco's
+ * CORNER_REFINE_SUBPIX): at a corner or an X-saddle every image gradient in the neighbourhood is orthogonal to the vector from the
+ * corner to its pixel, so the corner q solves (sum m g g^T) q = sum m g g^T p over a window of (2 half_win + 1)^2 taps p, weighted
+ * by a Gaussian m, and the window is moved to q until the step falls below eps.  Coordinates are the library's: pixel (i, j) covers
+ * [i, i+1) x [j, j+1) (ck_detection_t.p).  Sampling is bilinear on the 8-bit frame, clamped to the frame edge.  Only + - * / and
+ * one sqrt on doubles in a summation order DESIGN.md states (csrc/ck_subpix_math.h, compiled into the host twins and into the
+ * kernels), so the host twins return the bytes of the device path. */
+enum { CK_SUBPIX_CONVERGED = 0, CK_SUBPIX_MAXIT = 1, CK_SUBPIX_FLAT = 2, CK_SUBPIX_REJECTED = 3 };
+typedef struct ck_subpix_params {
+    int32_t half_win;  /* w, 2..7: the window is (2w + 1)^2 taps; default 5 */
+    int32_t max_iters; /* 1..1000, default 30 */
+    double eps;        /* stop when the step is at most this long, pixels; >= 0, default 1e-3 */
+    double det_min;    /* |det| <= det_min: the window has no corner (FLAT); >= 0, default 1e-2 */
+} ck_subpix_params_t;
+typedef struct ck_subpix_info {
+    int32_t status;    /* CK_SUBPIX_*.  FLAT: a window's determinant was at most det_min.  REJECTED: the point ended more than
+                        * half_win from its start on either axis (or not finite).  Both return the input, bit for bit */
+    int32_t iters;     /* steps taken */
+    double shift;      /* |out - in|, pixels; 0 for FLAT and REJECTED */
+} ck_subpix_info_t;
+void ck_subpix_params_default(ck_subpix_params_t *pp);
+/* The (2w + 1)^2 weights exp(-(dx / w)^2) * exp(-(dy / w)^2), row-major: pure host arithmetic, no device needed.  The one table
+ * the kernels and the twins both read.  CK_EINVAL: a null pointer, a parameter out of range. */
+int ck_subpix_weights(const ck_subpix_params_t *pp, double *w_out);
+/* Refines n points xy_in [n][2] of the staged frames (ck_upload_frames and its kin): point i lies in frame frame[i] (NULL: every
+ * point in frame 0).  xy_out [n][2] and info [n] (may be NULL) come back; frame, xy_in, xy_out and info may be host or device
+ * pointers.  One 64-lane wave per point on the handle's stream; the detection workspace stays as it is.  n = 0 is a no-op.
+ * CK_EINVAL: a null pointer, n < 0, a parameter out of range, a frame index outside the staged frames, a point that is not finite
+ * or outside [0, width] x [0, height]. */
+int ck_corner_subpix(ck_handle_t *h, const ck_subpix_params_t *pp, const int32_t *frame, const double *xy_in, int32_t n,
+                     double *xy_out, ck_subpix_info_t *info);
+/* The one-thread C twin on host images (all of one size): the bytes of ck_corner_subpix.  No device needed. */
+int ck_corner_subpix_host(const ck_subpix_params_t *pp, const ck_image_u8_t *imgs, int32_t n_imgs, const int32_t *frame,
+                          const double *xy_in, int32_t n, double *xy_out, ck_subpix_info_t *info);
+/* A handle setting, like ck_set_quad_sigma and ck_set_camera; NULL = off, the default.  While it is on, every ck_detect_* and
+ * ck_process_* call refines the four corners of every final detection on the device, after the de-duplication, on the
+ * full-resolution unfiltered frame the call was given (staged, caller device memory, an ingest slot), rewrites `p` and recomputes `c`
+ * as the image of the tag centre under the homography of the four new corners.  A detection none of whose corners moved keeps its
+ * bytes.  What reads the detections afterwards (the glue's bearings, ck_last_tag_poses, ck_last_pose_inputs, the rig calls, the
+ * preview overlay) inherits the refined corners.  While it is off no launch is added.  CK_EINVAL: a parameter out of range (the
+ * previous setting stays). */
+int ck_set_corner_subpix(ck_handle_t *h, const ck_subpix_params_t *pp);
+
+/* Board recovery: from the few tags of a tag grid that decoded to all of them.  ck_board_t is the Board of
+ * chalkydri_amd/calibration.py: rows x cols tags of edge tag_size, tag_spacing times that between neighbours, ids row-major from
+ * first_id; rows * cols <= 64.  A seed is a detection of family `family` with an id on the board and hamming 0, the first per id;
+ * its corners are refined and it is kept when none moved more than seed_max_shift.  Then rounds: every absent tag with a known
+ * 4-neighbour (the first in the order left, right, up, down, among the tags known when the round began) maps its four corners
+ * through that neighbour's homography, skips the round when a prediction lies within half_win + 2 pixels of the frame edge,
+ * refines them, and is accepted when all four converge, none moved more than max_shift, and a second refinement started `probe`
+ * away from each result ends within `agree` of it — which keeps flat and occluded spots out.  Rounds go on until one adds no tag, at
+ * most rows + cols of them. */
+typedef struct ck_board {
+    int32_t rows, cols, first_id, family;
+    double tag_size, tag_spacing;
+} ck_board_t;
+typedef struct ck_board_params {
+    double seed_max_shift; /* 2.0 px */
+    double max_shift;      /* 2.5 px */
+    double probe[2];       /* (+0.7, -0.6) px */
+    double agree;          /* 0.05 px */
+} ck_board_params_t;
+void ck_board_params_default(ck_board_params_t *bp);
+/* On the detections the handle's last ck_detect_* / ck_process_* call left on the device (ck_last_tag_poses' validity rule) and the
+ * frames of that call.  uv_out [n][rows * cols][4][2] (zeros for absent tags), tag_state [n][rows * cols] (0 absent, 1 seed,
+ * 2 recovered) and n_tags [n] come back, n = the frames of that call; host or device pointers.  One workgroup per frame.
+ * CK_EINVAL: a null pointer, a board with rows or cols < 1, rows * cols > 64, a family the handle does not have, tag_size <= 0,
+ * tag_spacing < 0 or not finite, a parameter out of range, no such call's result in the workspace. */
+int ck_board_corners_last(ck_handle_t *h, const ck_board_t *board, const ck_subpix_params_t *pp, const ck_board_params_t *bp,
+                          double *uv_out, uint8_t *tag_state, int32_t *n_tags);
+/* The one-thread C twin: dets [n][cap_per_frame] with counts [n], as ck_detect_* returns them, and the n images they came from. */
+int ck_board_corners_host(const ck_board_t *board, const ck_subpix_params_t *pp, const ck_board_params_t *bp, const ck_image_u8_t *imgs,
+                          int32_t n, const ck_detection_t *dets, int32_t cap_per_frame, const int32_t *counts, double *uv_out,
+                          uint8_t *tag_state, int32_t *n_tags);
 
 /* fp64 conformance probe used by the parity tests: out[i] = op(a[i], b[i]) computed on the device with
  * the same flags as the kernels. op: 0 add, 1 mul, 2 div, 3 sqrt(a), 4 a*b+c style unfused (a*b)+a. */
