@@ -473,6 +473,22 @@ __device__ __forceinline__ void wave_argmin_u64_i32(unsigned long long &key, int
     tag = __builtin_amdgcn_readlane(tag, 63);
 }
 
+// The wave's largest key, for every lane, on the same ladder (two words per step, no LDS).
+template <int CTRL, int ROWS>
+__device__ __forceinline__ unsigned long long max_step_u64(unsigned long long key) {
+    const uint32_t lo = (uint32_t)key, hi = (uint32_t)(key >> 32);
+    const uint32_t olo = (uint32_t)__builtin_amdgcn_update_dpp((int)lo, (int)lo, CTRL, ROWS, 0xF, false);
+    const uint32_t ohi = (uint32_t)__builtin_amdgcn_update_dpp((int)hi, (int)hi, CTRL, ROWS, 0xF, false);
+    const unsigned long long okey = ((unsigned long long)ohi << 32) | olo;
+    return okey > key ? okey : key;
+}
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long key) {
+    key = max_step_u64<0x111, 0xF>(key); key = max_step_u64<0x112, 0xF>(key); key = max_step_u64<0x114, 0xF>(key); key = max_step_u64<0x118, 0xF>(key);
+    key = max_step_u64<0x142, 0xA>(key); key = max_step_u64<0x143, 0xC>(key);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)key, 63), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(key >> 32), 63);
+    return ((unsigned long long)hi << 32) | lo;
+}
+
 // CAT's gray level of an RGB pixel (utils.rs:33-46): trunc(fma(r, 0.33f, fma(g, 0.33f, b * 0.33f))) in f32, saturating.  The one
 // map of k_cat.hip and k_tri_otsu.hip.
 __device__ __forceinline__ uint8_t ck_cat_grayscale(uint8_t r, uint8_t g, uint8_t b) {

@@ -1759,6 +1759,7 @@ __device__ __forceinline__ long long readlane_i64(long long v, int l) {
 // sum starts at the first position of the cluster's first span and carries whatever lies between there and the cluster's first
 // point — the same addend in all of them, so it leaves with the differences; the cluster's total subtracts it by name (the head).
 constexpr int MAXRUN = 72; // spans a cluster of CK_HUGE_CAP points can touch
+constexpr int SEL_RV = 4;  // maxima per lane that the selection (5a) holds in registers: 1.6 % of the bench batch's clusters have more than 256
 #ifdef CK_FLAT_DEBUG
 __device__ unsigned int g_flat_dbg[32];
 #define FDBG(k) do { if (tid == 0) atomicAdd(&g_flat_dbg[k], 1u); } while (0)
@@ -2141,7 +2142,72 @@ __device__ __forceinline__ void k_tail_body(const FitArgs &a) {
                 if (pos < MAXSEL) sSelIdx[pos] = myo;
                 if (myo < 0 || myo >= sz) sBad = 1;
             }
-        } else {
+        } else if (nmax_all <= 64 * SEL_RV) {
+            // up to SEL_RV maxima per lane (number lane + 64 q of the cluster's list), fetched once: the slots find their runs, all loads
+            // are issued, one wait; the values stay in registers as their integer images (above), the positions beside them.  A slot
+            // beyond the list fetches the lane's first maximum again (the list has more than 64) and holds the image 0, below every value's
+            uint32_t idx[SEL_RV];
+            int myo[SEL_RV];
+#pragma unroll
+            for (int q = 0; q < SEL_RV; q++) { idx[q] = 0; myo[q] = 0; }
+            for (int r = 0; r < nruns; r++) {
+                const uint32_t off = sRunOff[r], n = sRunN[r], st0 = sRunStart[r];
+                const int ob = sRunO[r];
+#pragma unroll
+                for (int q = 0; q < SEL_RV; q++) {
+                    const uint32_t i = (uint32_t)(lane + 64 * q);
+                    if (i >= off && i < off + n) { idx[q] = st0 + (i - off); myo[q] = ob; }
+                }
+            }
+            double v[SEL_RV];
+            uint32_t p[SEL_RV];
+#pragma unroll
+            for (int q = 0; q < SEL_RV; q++) {
+                const uint32_t j = lane + 64 * q < nmax_all ? idx[q] : idx[0];
+                v[q] = mval[j];
+                p[q] = mpos[j];
+            }
+            __builtin_amdgcn_s_waitcnt(WAIT_VMCNT0);
+            unsigned long long key[SEL_RV];
+#pragma unroll
+            for (int q = 0; q < SEL_RV; q++) {
+                const unsigned long long b = (unsigned long long)__double_as_longlong(v[q]);
+                key[q] = lane + 64 * q < nmax_all ? ((b >> 63) ? ~b : (b | (1ull << 63))) : 0ull;
+                myo[q] += (int)p[q];
+            }
+            // the same descending walk as beyond 64 * SEL_RV maxima (below): the largest value under `cur` and how many slots hold it — the
+            // maximum on the DPP ladder, the multiplicity from ballots, nothing through LDS or memory.  (All lanes are active here.)
+            unsigned long long thrk = 1ull << 63; // (the image of 0.0)
+            if (use_thr) {
+                unsigned long long cur = 0xFFF0000000000000ull; // (the image of +infinity)
+                int remaining = a.max_nmaxima + 1;
+                for (int round = 0; round <= a.max_nmaxima; round++) {
+                    unsigned long long m = 0ull;
+#pragma unroll
+                    for (int q = 0; q < SEL_RV; q++)
+                        if (key[q] < cur && key[q] > m) m = key[q];
+                    m = wave_max_u64(m);
+                    if (m == 0ull) break; // (nothing below `cur`: fewer values than the cut, which use_thr excludes)
+                    int cnt = 0;
+#pragma unroll
+                    for (int q = 0; q < SEL_RV; q++) cnt += __popcll(__ballot(key[q] == m));
+                    if (cnt >= remaining) { thrk = m; break; }
+                    remaining -= cnt;
+                    cur = m;
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < SEL_RV; q++) { // slot q of all lanes before slot q + 1: list order, which is position order
+                const bool keep = lane + 64 * q < nmax_all && !(use_thr && key[q] <= thrk);
+                const unsigned long long kb = __ballot(keep);
+                if (keep) {
+                    const int pos = nsel + __popcll(kb & ((1ull << lane) - 1ull));
+                    if (pos < MAXSEL) sSelIdx[pos] = myo[q];
+                    if (myo[q] < 0 || myo[q] >= sz) sBad = 1;
+                }
+                nsel += __popcll(kb);
+            }
+        } else { // beyond 64 * SEL_RV maxima: every round of the walk reads the lists again
             double thr = 0.0;
             if (use_thr) {
                 double cur = HUGE_VAL;
@@ -2353,8 +2419,8 @@ __device__ __forceinline__ void k_tail_body(const FitArgs &a) {
     }
 }
 
-// Register budget: four waves per SIMD (128 registers; the code object says 118 used, no spilled register, no scratch — with the block
-// scan of 5b still in, it said 126, two spilled, 12 bytes of scratch).  A build for five (96 registers, 59 of them spilled) once
+// Register budget: four waves per SIMD (128 registers; the code object says 121 used, no spilled register, no scratch — with the block
+// scan of 5b still in, it said 126, two spilled, 12 bytes of scratch; with SEL_RV = 8 it says 126).  A build for five (96 registers, 59 of them spilled) once
 // looked 7 % faster and was WRONG (detections missing at 1920x1080 and 2448x2048, copies of one frame differing): two v_readlane
 // reads of the chunk heads stood inside `if (lane < ...)` / `if (tid == 0)` blocks, where the lane they read may be switched off, and
 // the spill code restores active lanes only.  With every v_readlane where all lanes are active that build is correct — and 3 %
@@ -2565,6 +2631,9 @@ int ck_launch_fit_quads(ck_handle *h, const ck_dev_image &qimg, const ck_dev_ima
     a.ws = ws; a.list_cap = list_cap;
     a.stop_after = CK_KNOB("CK_FIT_STOP_AFTER", 99); // (read per call)
     a.guided = CK_KNOB("CK_FIT_GUIDED", 1);          // (read per call)
+    // (measurements of the selection with CK_FIT_STOP_AFTER <= 5: a cut above every cluster's count skips the threshold search, and
+    // every cluster with more than MAXSEL maxima then leaves after the selection)
+    a.max_nmaxima = CK_KNOB("CK_FIT_NMAXIMA", a.max_nmaxima);
     auto use_list = [&](int l) { a.list = fl.lists + (size_t)l * list_cap; a.list_count = fl.list_counts + l; a.head = fl.heads + l; };
     auto launch_wimg = [&](hipStream_t st) {
         const int w4 = (h->qw + 3) / 4;
