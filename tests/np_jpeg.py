@@ -100,12 +100,15 @@ def stuff(b):
 
 
 def encode(luma, sampling="420", quality=85, restart_interval=0, chroma=None, tables=None, dht=True, q16=False, restart_rows=False,
-           dc_offset=0):
+           dc_offset=0, append=None, fill=None, eob=0x00):
     """Baseline JPEG of an 8-bit luma plane [h][w] (+ chroma planes [h][w] each, derived from the luma when None).
     sampling: "444", "422", "440", "420" (Y sampling 1x1, 2x1, 1x2, 2x2) or "grey".  restart_interval in MCUs (restart_rows: in
     MCU rows).  tables: {(class, slot): (bits[16], vals)} replacing the K.3 tables; dht=False leaves every DHT out (the stream
     then relies on the standard tables); q16: write the quantisation tables with 16-bit precision.  dc_offset (a number, or numbers cycled over the
-    blocks in raster order) is added to the quantised Y DCs (far out of the sample range with a coarse table: what reaches libjpeg's masked range limit)."""
+    blocks in raster order) is added to the quantised Y DCs (far out of the sample range with a coarse table: what reaches libjpeg's masked range limit).
+    append: {interval index (negative: from the end): raw bytes written as they are after the interval's last code and its padding, before
+    the marker that ends it}; fill: {interval index: number of 0xFF fill bytes in front of that marker}; eob: the symbol written where
+    EOB stands in a component whose AC table holds it (an EOB-run symbol 0x10 .. 0xE0 of a caller-given table; 0x00 otherwise)."""
     luma = np.asarray(luma, np.uint8)
     h, w = luma.shape
     grey = sampling == "grey"
@@ -177,7 +180,7 @@ def encode(luma, sampling="420", quality=85, restart_interval=0, chroma=None, ta
                         iv.append(val if val > 0 else val + (1 << s) - 1); il.append(s)
                         k = idx + 1
                     if k < 64:
-                        c, l = acc[0x00]
+                        c, l = acc[eob if eob in acc else 0x00]
                         iv.append(c); il.append(l)
     intervals.append((iv, il))
     scan = bytearray()
@@ -185,6 +188,10 @@ def encode(luma, sampling="420", quality=85, restart_interval=0, chroma=None, ta
         if i:
             scan += bytes([0xFF, 0xD0 + ((i - 1) & 7)])
         scan += stuff(pack_bits(vv, ll))
+        for extra, make in ((append, bytes), (fill, lambda n: b"\xff" * n)):
+            for key in (i, i - len(intervals)):
+                if extra and key in extra:
+                    scan += make(extra[key])
     out = bytearray(b"\xff\xd8")
 
     def seg(m, body):
@@ -417,9 +424,10 @@ def idct_islow(coef, q):
     return _range_limit((rows + (1 << 17)) >> 18)
 
 
-def decode_luma(data):
+def decode_luma(data, info=None):
     """(luma [h][w] uint8, status) under the library's rules; a frame that fails is all zeros ([0][0] when the header is
-    refused)."""
+    refused).  info: a dict that receives "end_bits", the bit position in the unstuffed scan after the last block of every
+    interval that was decoded whole (tests/jpeg_sync_model.py is checked against it)."""
     try:
         P = parse(data)
     except JpegError as e:
@@ -494,6 +502,8 @@ def decode_luma(data):
                     break
             if pos > lim:     # the interval ends before its MCUs do
                 return zero, CORRUPT
+        if info is not None:
+            info.setdefault("end_bits", []).append(pos)
     yc = np.array(ycoef, np.int64)
     yc = (yc + 32768) % 65536 - 32768                               # libjpeg stores coefficients as 16-bit JCOEFs
     pix = idct_islow(yc, P["qt"]).reshape(mcuy * V, mcux * H, 8, 8).transpose(0, 2, 1, 3).reshape(mcuy * V * 8, mcux * H * 8)
