@@ -20,6 +20,9 @@
 //   5. the max_nmaxima strongest maxima (rank-based selection), moment sums at them from a 32/128-point table, one line
 //      fit per ordered pair, every 4-subset evaluated in parallel (argmin with the oracle's lexicographic tie-break);
 //   6. lines, corners, area/angle/winding checks on four lanes, wave-parallel edge refinement.
+// Phases 1-2 are one text for k_fit and k_seq (front_box / front_sort / front_pack); so is everything behind the moment sums at the
+// selected maxima, 5c-6, for k_fit and k_tail (SelSums, back_pair_fits, back_best_subset, back_side, back_corner, back_refine_edges,
+// emit_quad).  Phases 3-5b are each kernel's own: the forms differ there (chunk loop / k_chunk, LDS lists / lists in memory).
 // Clusters are dispatched through per-size-class work lists built by k_classify (<= 256, <= 512, <= 1024, <= 2048, <= 4096,
 // <= 8192, <= 16384 points, and the rest); each variant is a persistent grid whose workgroups take a first chunk of their list by index and the
 // rest from a dequeue counter.  The phases can be cut short for measurements with CK_FIT_STOP_AFTER (tools/ablate_fit.sh).
@@ -794,6 +797,300 @@ __device__ __forceinline__ int front_pack(unsigned long long *sKeys, int sz0, in
     return sz;
 }
 
+// ---- the back half of the fit (phases 5c-6), one text for k_fit and k_tail --------------------------------------------------------------
+// Everything behind the point where the selected maxima and their moment sums lie in LDS.  Each passage must round as the oracle's, so
+// each stands here once.  The two kernels differ in the barrier (BAR::sync(): k_fit's workgroup barrier, k_tail's one wave), in the
+// number of threads (NTH: what only a workgroup of several waves needs stands behind `if constexpr (NTH > 64)`) and in their LDS
+// overlays: the functions take pointers and declare no __shared__ of their own.  The phase markers (stop_after, PROF, FDBG) stay with
+// the kernels, between the calls.
+
+// The moment sums at the selected maxima (5b left them: I inclusive, E exclusive of the maximum itself), the cluster's total and size.
+struct SelSums {
+    const long long (*I)[6], (*E)[6];
+    const int *idx;
+    M6 total;
+    int sz;
+    __device__ __forceinline__ M6 range(int sa, int sb, int *N) const { // points from maximum sa to maximum sb inclusive, going forward
+        M6 mi = {I[sb][0], I[sb][1], I[sb][2], I[sb][3], I[sb][4], I[sb][5]};
+        M6 me = {E[sa][0], E[sa][1], E[sa][2], E[sa][3], E[sa][4], E[sa][5]};
+        int i0 = idx[sa], i1 = idx[sb];
+        if (i0 < i1) { *N = i1 - i0 + 1; return m6_sub(mi, me); }
+        *N = sz - i0 + i1 + 1;
+        return m6_add(m6_sub(total, me), mi);
+    }
+};
+
+// 5c. one line fit per ordered pair of maxima into sF[sa * MAXSEL + sb]: lane k takes the pair a < b from the table and fits both
+// directions in one go (a -> b, and b -> a around the end); the two f64 dependency chains overlap.  A workgroup of several waves has
+// enough lanes for one fit each and walks the full table.  (The caller's barrier stands behind this.)
+template <int NTH>
+__device__ __forceinline__ void back_pair_fits(const SelSums &S, int nsel, PairFit *sF, int tid) {
+    if constexpr (NTH > 64) {
+        const int npairs = nsel * nsel;
+        for (int pr = tid; pr < npairs; pr += NTH) {
+            const int sa = pr / nsel, sb = pr - sa * nsel;
+            if (sa == sb) continue;
+            int N;
+            double lp[4], e, ms;
+            const M6 m = S.range(sa, sb, &N);
+            fit_line_m(m, N, lp, &e, &ms);
+            PairFit f;
+            f.err = e; f.mse = ms; f.nx = lp[2]; f.ny = lp[3];
+            sF[sa * MAXSEL + sb] = f;
+        }
+    } else {
+        const int npf = nsel * (nsel - 1) / 2;
+        for (int k = tid; k < npf; k += NTH) {
+            const int pk = g_pair_table.v[k], sa = pk >> 4, sb = pk & 15;
+            int Nf, Nw;
+            const M6 mf = S.range(sa, sb, &Nf), mw = S.range(sb, sa, &Nw);
+            double lp[4], lq[4], ef, msf, ew, msw;
+            fit_line_m(mf, Nf, lp, &ef, &msf);
+            fit_line_m(mw, Nw, lq, &ew, &msw);
+            PairFit f;
+            f.err = ef; f.mse = msf; f.nx = lp[2]; f.ny = lp[3];
+            sF[sa * MAXSEL + sb] = f;
+            f.err = ew; f.mse = msw; f.nx = lq[2]; f.ny = lq[3];
+            sF[sb * MAXSEL + sa] = f;
+        }
+    }
+}
+
+// 5c. the 4-subset search over the pair table: every lane walks its own subsets, the workgroup's smallest (error sum, packed subset)
+// comes back on every thread — the oracle's lexicographic tie-break.  HUGE_VAL: no subset passed.
+// A wave's smallest pair on the DPP ladder, `best` through its order-preserving integer image: a lane's best is HUGE_VAL or a sum
+// that passed `e < best`, never NaN; errors that compare equal have the same image once + 0.0 has made a -0.0 the +0.0 it equals.
+// The minimum of a total order does not depend on the order of the comparisons.  All lanes are active here (the ladder needs them);
+// the waves of a larger workgroup meet through sRed / sRedI (NTH / 64 entries each; unused by one wave).
+template <int NTH, class BAR>
+__device__ __forceinline__ void back_best_subset(const PairFit *sF, int nsel, const FitArgs &a, int tid, double *sRed, int *sRedI, double *best_out,
+                                                 int *bestc_out) {
+    double best = HUGE_VAL;
+    int bestc = 1 << 30;
+    const int ncomb = nsel * (nsel - 1) * (nsel - 2) * (nsel - 3) / 24;
+    for (int cb = tid; cb < ncomb; cb += NTH) {
+        const int pk = g_combo_table.v[cb];
+        const int m0 = pk >> 12, m1 = (pk >> 8) & 15, m2 = (pk >> 4) & 15, m3 = pk & 15;
+        const PairFit f01 = sF[m0 * MAXSEL + m1];
+        if (f01.mse > a.max_mse) continue;
+        const PairFit f12 = sF[m1 * MAXSEL + m2];
+        if (f12.mse > a.max_mse) continue;
+        double dp = f01.nx * f12.nx + f01.ny * f12.ny;
+        if (fabs(dp) > a.cos_critical) continue;
+        const PairFit f23 = sF[m2 * MAXSEL + m3];
+        if (f23.mse > a.max_mse) continue;
+        const PairFit f30 = sF[m3 * MAXSEL + m0];
+        if (f30.mse > a.max_mse) continue;
+        double e = f01.err + f12.err + f23.err + f30.err;
+        if (e < best || (e == best && pk < bestc)) { best = e; bestc = pk; }
+    }
+    {
+        const unsigned long long bb = (unsigned long long)__double_as_longlong(best + 0.0);
+        unsigned long long bk = (bb >> 63) ? ~bb : (bb | (1ull << 63));
+        wave_argmin_u64_i32(bk, bestc);
+        best = __longlong_as_double((long long)((bk >> 63) ? (bk ^ (1ull << 63)) : ~bk));
+    }
+    if constexpr (NTH > 64) {
+        if ((tid & 63) == 0) { sRed[tid >> 6] = best; sRedI[tid >> 6] = bestc; }
+        BAR::sync();
+        best = sRed[0]; bestc = sRedI[0];
+        for (int k = 1; k < NTH / 64; k++)
+            if (sRed[k] < best || (sRed[k] == best && sRedI[k] < bestc)) { best = sRed[k]; bestc = sRedI[k]; }
+        BAR::sync();
+    }
+    *best_out = best; *bestc_out = bestc;
+}
+
+// Where line l0 meets line l1 (a line: a point on it, then its normal).  det goes back to the caller, who uses it in two ways: in 5d a
+// corner with |det| < 0.001 rejects the quad, after the edge refinement a corner is replaced only where |det| > 0.001.
+__device__ __forceinline__ void intersect_lines(const double (&l0)[4], const double (&l1)[4], double *det_out, double *px, double *py) {
+    double A00 = l0[3], A01 = -l1[3], A10 = -l0[2], A11 = l1[2];
+    double B0 = -l0[0] + l1[0], B1 = -l0[1] + l1[1];
+    double det = A00 * A11 - A10 * A01;
+    double W00 = A11 / det, W01 = -A01 / det;
+    double L0 = W00 * B0 + W01 * B1;
+    *px = l0[0] + L0 * A00;
+    *py = l0[1] + L0 * A10;
+    *det_out = det;
+}
+
+// 5d. one side of the chosen subset: the weighted-mean sums of its points; normal and mse are in the pair table already (the same fit
+// of the same sums), only the point on the line is still to be formed
+struct SideRec { long long Mx, My, W; double nx, ny, mse; };
+__device__ __forceinline__ SideRec back_side(const SelSums &S, const PairFit *sF, int bestc, int li) {
+    const int sel[4] = {(bestc >> 12) & 15, (bestc >> 8) & 15, (bestc >> 4) & 15, bestc & 15};
+    int N;
+    const int s0 = sel[li], s1 = sel[(li + 1) & 3];
+    const M6 m = S.range(s0, s1, &N);
+    const PairFit pf = sF[s0 * MAXSEL + s1];
+    SideRec r;
+    r.Mx = m.Mx; r.My = m.My; r.W = m.W; r.nx = pf.nx; r.ny = pf.ny; r.mse = pf.mse;
+    return r;
+}
+
+// 5d. lines, corners, geometric checks on four lanes per cluster: lane 4 c + i owns side i / corner i of cluster c (mine: the lane has
+// one), even lanes the first triangle of the area, odd ones the second.  Every value is formed by the same operations as in the oracle's
+// sequential code, and the verdict is the conjunction of all checks, so their order does not matter: the quad stands when the four
+// lanes of its group all return true.  Px, Py: the lane's corner in full-resolution coordinates.  The other sides and corners come by
+// DPP moves inside the group (an indexed local array would live in scratch memory): ALL lanes of the wave must be active at the call.
+__device__ __forceinline__ bool back_corner(const SideRec *rec, bool mine, const FitArgs &a, double *Px_out, double *Py_out) {
+    bool ok = mine;
+    double line[4] = {0, 0, 0, 0};
+    if (mine) { // (rec is read on these lanes only)
+        const SideRec r = *rec;
+        const double inv = 1.0 / (double)r.W;
+        line[0] = (0.5 * (double)r.Mx) * inv; line[1] = (0.5 * (double)r.My) * inv;
+        line[2] = r.nx; line[3] = r.ny;
+        if (r.mse > a.max_mse) ok = false;
+    }
+    double ln[4]; // the next side of the same cluster
+#pragma unroll
+    for (int q = 0; q < 4; q++) ln[q] = quad_perm_f64<1, 2, 3, 0>(line[q]);
+    double Px, Py, det;
+    intersect_lines(line, ln, &det, &Px, &Py);
+    if (fabs(det) < 0.001) ok = false;
+    {   // Heron: triangle (0,1,2) on even lanes, (2,3,0) on odd ones; area = first + second
+        const double ax = quad_perm_f64<0, 2, 0, 2>(Px), ay = quad_perm_f64<0, 2, 0, 2>(Py), bx = quad_perm_f64<1, 3, 1, 3>(Px), by = quad_perm_f64<1, 3, 1, 3>(Py);
+        const double cx = quad_perm_f64<2, 0, 2, 0>(Px), cy = quad_perm_f64<2, 0, 2, 0>(Py);
+        double len[3];
+        { double ddx = bx - ax, ddy = by - ay; len[0] = sqrt(ddx * ddx + ddy * ddy); }
+        { double ddx = cx - bx, ddy = cy - by; len[1] = sqrt(ddx * ddx + ddy * ddy); }
+        { double ddx = ax - cx, ddy = ay - cy; len[2] = sqrt(ddx * ddx + ddy * ddy); }
+        double pp = (len[0] + len[1] + len[2]) / 2.0;
+        double term = sqrt(pp * (pp - len[0]) * (pp - len[1]) * (pp - len[2]));
+        double t0 = quad_perm_f64<0, 0, 0, 0>(term), t1 = quad_perm_f64<1, 1, 1, 1>(term);
+        double area = 0.0;
+        area += t0; area += t1;
+        double tw = (double)a.min_tag_width;
+        if (area < 0.95 * tw * tw) ok = false;
+    }
+    {
+        const double x1 = quad_perm_f64<1, 2, 3, 0>(Px), y1 = quad_perm_f64<1, 2, 3, 0>(Py), x2 = quad_perm_f64<2, 3, 0, 1>(Px), y2 = quad_perm_f64<2, 3, 0, 1>(Py);
+        double dx1 = x1 - Px, dy1 = y1 - Py;
+        double dx2 = x2 - x1, dy2 = y2 - y1;
+        double cs = (dx1 * dx2 + dy1 * dy2) / sqrt((dx1 * dx1 + dy1 * dy1) * (dx2 * dx2 + dy2 * dy2));
+        if (cs > a.cos_critical || cs < -a.cos_critical) ok = false;
+        if (dx1 * dy2 < dy1 * dx2) ok = false;
+    }
+    if (a.decimate > 1) { Px = (Px - 0.5) * (double)a.decimate + 0.5; Py = (Py - 0.5) * (double)a.decimate + 0.5; }
+    *Px_out = Px; *Py_out = Py;
+    return ok;
+}
+
+// 6. edge refinement (oracle refine_edges) of the quad in sQuad, in place.  The samples of an edge are independent: lane (edge, k) of
+// the 64 workers evaluates sample 16 * round + k (its 2 * range + 1 gradient probes are independent loads) into sRefine (x = NaN: no
+// point), then ONE lane per edge accumulates the refined points in sample order, so every sum is formed exactly as in the sequential
+// code.  Then the line through each edge's points (eigenvector of their covariance; the edge itself with fewer than two points) into
+// sLines, and the corners where consecutive lines meet.  worker: the thread is one of the 64 (every thread calls; sRedI carries the
+// number of rounds to the other waves of a larger workgroup).  im: the frame's full-resolution image.
+template <int NTH, class BAR>
+__device__ __forceinline__ void back_refine_edges(const FitArgs &a, const uint8_t *im, int reversed, bool worker, int tid, double (*sQuad)[2],
+                                                  double (*sLines)[4], double (*sRefine)[16][2], int *sRedI) {
+    const int edge = (tid >> 4) & 3, k = tid & 15;
+    const int ea = edge, eb = (edge + 1) & 3;
+    double nx = 0, ny = 0, mag = 1;
+    int nsamples = 0;
+    if (worker) {
+        nx = sQuad[eb][1] - sQuad[ea][1];
+        ny = -sQuad[eb][0] + sQuad[ea][0];
+        mag = sqrt(nx * nx + ny * ny);
+        nx = nx / mag; ny = ny / mag;
+        if (reversed) { nx = -nx; ny = -ny; }
+        nsamples = (int)(mag / 8.0);
+        if (nsamples < 16) nsamples = 16;
+    }
+    int max_samples = nsamples; // the same for the 16 lanes of an edge; rounds are driven by the largest edge
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) max_samples = max(max_samples, __shfl_xor(max_samples, d, 64));
+    if constexpr (NTH > 64) {
+        if (tid == 0) sRedI[0] = max_samples;
+        BAR::sync();
+        max_samples = sRedI[0];
+        BAR::sync();
+    }
+    double Mx = 0, My = 0, Mxx = 0, Mxy = 0, Myy = 0, N = 0; // meaningful on lane k == 0 of every edge
+    for (int base = 0; base < max_samples; base += 16) {
+        if (worker) {
+            const int sidx = base + k;
+            double bx = __builtin_nan(""), by = 0;
+            if (sidx < nsamples) {
+                double alpha = (1.0 + (double)sidx) / ((double)nsamples + 1.0);
+                double x0 = alpha * sQuad[ea][0] + (1.0 - alpha) * sQuad[eb][0];
+                double y0 = alpha * sQuad[ea][1] + (1.0 - alpha) * sQuad[eb][1];
+                double Mn = 0, Mcount = 0;
+                const int range = a.decimate + 1;
+                for (int n = -range; n <= range; n++) {
+                    double grange = 1.0;
+                    int x1 = (int)(x0 + ((double)n + grange) * nx), y1 = (int)(y0 + ((double)n + grange) * ny);
+                    if (x1 < 0 || x1 >= a.w || y1 < 0 || y1 >= a.h) continue;
+                    int x2 = (int)(x0 + ((double)n - grange) * nx), y2 = (int)(y0 + ((double)n - grange) * ny);
+                    if (x2 < 0 || x2 >= a.w || y2 < 0 || y2 >= a.h) continue;
+                    int g1 = im[(size_t)y1 * a.stride + x1], g2 = im[(size_t)y2 * a.stride + x2];
+                    if (g1 < g2) continue;
+                    double weight = (double)((g2 - g1) * (g2 - g1));
+                    Mn += weight * (double)n;
+                    Mcount += weight;
+                }
+                if (Mcount != 0) {
+                    double n0 = Mn / Mcount;
+                    bx = x0 + n0 * nx; by = y0 + n0 * ny;
+                }
+            }
+            sRefine[edge][k][0] = bx; sRefine[edge][k][1] = by;
+        }
+        BAR::sync();
+        if (worker && k == 0)
+            for (int q = 0; q < 16 && base + q < nsamples; q++) {
+                double bx = sRefine[edge][q][0], by = sRefine[edge][q][1];
+                if (bx != bx) continue; // no usable gradient at this sample
+                Mx += bx; My += by; Mxx += bx * bx; Mxy += bx * by; Myy += by * by; N += 1.0;
+            }
+        BAR::sync();
+    }
+    if (worker && k == 0) {
+        double line[4];
+        if (N < 2.0) {
+            line[0] = 0.5 * (sQuad[ea][0] + sQuad[eb][0]); line[1] = 0.5 * (sQuad[ea][1] + sQuad[eb][1]);
+            line[2] = nx; line[3] = ny;
+        } else {
+            double Ex = Mx / N, Ey = My / N;
+            double Cxx = Mxx / N - Ex * Ex, Cxy = Mxy / N - Ex * Ey, Cyy = Myy / N - Ey * Ey;
+            double d = Cxx - Cyy, q4 = 4.0 * Cxy;
+            double disc = sqrt(d * d + q4 * Cxy);
+            double eig = 0.5 * (Cxx + Cyy + disc);
+            double nx1 = Cxx - eig, ny1 = Cxy, M1 = nx1 * nx1 + ny1 * ny1;
+            double nx2 = Cxy, ny2 = Cyy - eig, M2 = nx2 * nx2 + ny2 * ny2;
+            double fx, fy, M;
+            if (M1 > M2) { fx = nx1; fy = ny1; M = M1; } else { fx = nx2; fy = ny2; M = M2; }
+            double len = sqrt(M);
+            line[0] = Ex; line[1] = Ey;
+            if (len < 1e-12) { line[2] = nx; line[3] = ny; }
+            else { line[2] = fx / len; line[3] = fy / len; }
+        }
+        for (int q = 0; q < 4; q++) sLines[edge][q] = line[q];
+    }
+    BAR::sync();
+    if (tid == 0)
+        for (int i = 0; i < 4; i++) {
+            int j = (i + 1) & 3;
+            double det, px, py;
+            intersect_lines(sLines[i], sLines[j], &det, &px, &py);
+            if (fabs(det) > 0.001) { sQuad[j][0] = px; sQuad[j][1] = py; }
+        }
+}
+
+// 6. the quad leaves: one thread appends sQuad to the frame's list, or marks the frame when the list is full
+__device__ __forceinline__ void emit_quad(const ck_stage_ws &ws, int frame, int reversed, uint32_t rep0, uint32_t rep1, const double (*sQuad)[2]) {
+    uint32_t *counters = ws.d_counters + (size_t)frame * CK_CNT_STRIDE;
+    uint32_t qi = atomicAdd(&counters[CK_CNT_QUADS], 1u);
+    if (qi < (uint32_t)ws.quad_cap) {
+        ck_quad_t q;
+        for (int i = 0; i < 4; i++) { q.p[i][0] = sQuad[i][0]; q.p[i][1] = sQuad[i][1]; }
+        q.reversed_border = reversed; q.rep0 = rep0; q.rep1 = rep1;
+        ws.d_quads[(size_t)frame * ws.quad_cap + qi] = q;
+    } else atomicOr(&counters[CK_CNT_STATUS], (uint32_t)CK_FRAME_QUADS_OVERFLOW);
+}
+
 // NTH threads per cluster, up to CAP points, chunks of CH points; MLDS: the maxima list fits in LDS; GK: the per-point arrays
 // (keys, then coordinates and weights) live in a per-workgroup slice of global memory instead of LDS (the largest class)
 template <int NTH, int CAP, int CH, bool MLDS, int WPS, bool GK = false>
@@ -1165,284 +1462,40 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(WPS, 8))) v
         }
         __syncthreads();
         const int ntot = (sz + G - 1) / G;
-        const M6 total = {sTot[ntot][0], sTot[ntot][1], sTot[ntot][2], sTot[ntot][3], sTot[ntot][4], sTot[ntot][5]};
-        auto rangeM = [&](int sa, int sb, int *N) { // points from maximum sa to maximum sb inclusive, going forward
-            M6 I = {sSelI[sb][0], sSelI[sb][1], sSelI[sb][2], sSelI[sb][3], sSelI[sb][4], sSelI[sb][5]};
-            M6 E = {sSelE[sa][0], sSelE[sa][1], sSelE[sa][2], sSelE[sa][3], sSelE[sa][4], sSelE[sa][5]};
-            int i0 = sSelIdx[sa], i1 = sSelIdx[sb];
-            if (i0 < i1) { *N = i1 - i0 + 1; return m6_sub(I, E); }
-            *N = sz - i0 + i1 + 1;
-            return m6_add(m6_sub(total, E), I);
-        };
+        const SelSums S = {sSelI, sSelE, sSelIdx, {sTot[ntot][0], sTot[ntot][1], sTot[ntot][2], sTot[ntot][3], sTot[ntot][4], sTot[ntot][5]}, sz};
 
         PROF(7);
         if (a.stop_after == 6) continue;
-        // ---- 5c. one line fit per ordered pair of maxima; the 4-subset search is then table lookups ------------------------
+        // ---- 5c. one line fit per ordered pair of maxima; the 4-subset search is then table lookups (the shared back half) ----
         PairFit *sF = reinterpret_cast<PairFit *>(sPraw);
-        {   // lane k takes the pair a < b from the table and fits both directions in one go (a -> b, and b -> a around the
-            // end); the two f64 dependency chains overlap
-            const int npf = nsel * (nsel - 1) / 2;
-            if constexpr (NTH > 64) { // enough lanes for one fit each
-                const int npairs = nsel * nsel;
-                for (int pr = tid; pr < npairs; pr += NTH) {
-                    const int sa = pr / nsel, sb = pr - sa * nsel;
-                    if (sa == sb) continue;
-                    int N;
-                    double lp[4], e, ms;
-                    const M6 m = rangeM(sa, sb, &N);
-                    fit_line_m(m, N, lp, &e, &ms);
-                    PairFit f;
-                    f.err = e; f.mse = ms; f.nx = lp[2]; f.ny = lp[3];
-                    sF[sa * MAXSEL + sb] = f;
-                }
-            } else
-            for (int k = tid; k < npf; k += NTH) {
-                const int pk = g_pair_table.v[k], sa = pk >> 4, sb = pk & 15;
-                int Nf, Nw;
-                const M6 mf = rangeM(sa, sb, &Nf), mw = rangeM(sb, sa, &Nw);
-                double lp[4], lq[4], ef, msf, ew, msw;
-                fit_line_m(mf, Nf, lp, &ef, &msf);
-                fit_line_m(mw, Nw, lq, &ew, &msw);
-                PairFit f;
-                f.err = ef; f.mse = msf; f.nx = lp[2]; f.ny = lp[3];
-                sF[sa * MAXSEL + sb] = f;
-                f.err = ew; f.mse = msw; f.nx = lq[2]; f.ny = lq[3];
-                sF[sb * MAXSEL + sa] = f;
-            }
-        }
+        back_pair_fits<NTH>(S, nsel, sF, tid);
         __syncthreads();
-        double best = HUGE_VAL;
-        int bestc = 1 << 30;
-        {
-            const int ncomb = nsel * (nsel - 1) * (nsel - 2) * (nsel - 3) / 24;
-            for (int cb = tid; cb < ncomb; cb += NTH) { // every lane walks its own subsets; ties resolved by the packed index
-                const int pk = g_combo_table.v[cb];
-                const int m0 = pk >> 12, m1 = (pk >> 8) & 15, m2 = (pk >> 4) & 15, m3 = pk & 15;
-                {
-                    {
-                        {
-                            const PairFit f01 = sF[m0 * MAXSEL + m1];
-                            if (f01.mse > a.max_mse) continue;
-                            const PairFit f12 = sF[m1 * MAXSEL + m2];
-                            if (f12.mse > a.max_mse) continue;
-                            double dp = f01.nx * f12.nx + f01.ny * f12.ny;
-                            if (fabs(dp) > a.cos_critical) continue;
-                            const PairFit f23 = sF[m2 * MAXSEL + m3];
-                            if (f23.mse > a.max_mse) continue;
-                            const PairFit f30 = sF[m3 * MAXSEL + m0];
-                            if (f30.mse > a.max_mse) continue;
-                            double e = f01.err + f12.err + f23.err + f30.err;
-                            if (e < best || (e == best && pk < bestc)) { best = e; bestc = pk; }
-                        }
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            double ob = __shfl_xor(best, d, 64);
-            int oc = __shfl_xor(bestc, d, 64);
-            if (ob < best || (ob == best && oc < bestc)) { best = ob; bestc = oc; }
-        }
-        if (NTH > 64) {
-            if ((tid & 63) == 0) { sRed[tid >> 6] = best; sRedI[tid >> 6] = bestc; }
-            __syncthreads();
-            best = sRed[0]; bestc = sRedI[0];
-            for (int k = 1; k < NTH / 64; k++)
-                if (sRed[k] < best || (sRed[k] == best && sRedI[k] < bestc)) { best = sRed[k]; bestc = sRedI[k]; }
-            __syncthreads();
-        }
+        double best;
+        int bestc;
+        back_best_subset<NTH, FenceBarrier>(sF, nsel, a, tid, sRed, sRedI, &best, &bestc);
         PROF(8);
         if (best == HUGE_VAL) continue;
         if (best / (double)sz >= a.max_mse) continue;
 
         if (a.stop_after == 7) continue;
-        // ---- 5d. lines, corners, geometric checks: lane i of the first wave owns side i / corner i, lanes 0 and 1 the two
-        // triangles of the area; every value is formed by the same operations as in the oracle's sequential code, and the
-        // verdict is the conjunction of all checks, so their order does not matter ---------------------------------------------
+        // ---- 5d. lines, corners, geometric checks (back_corner): every group of four lanes of the first wave holds the cluster's four
+        // sides.  That whole wave is active here (tid < 64 takes or leaves a wave as one), which back_corner's DPP moves require ----
         if (tid < 64) {
-            const int li = tid & 3;
-            const int sel[4] = {(bestc >> 12) & 15, (bestc >> 8) & 15, (bestc >> 4) & 15, bestc & 15};
-            int ok = 1;
-            double line[4];
-            {   // the side's line: normal and mse are in the pair table already (the same fit of the same sums), only the
-                // point on the line (the weighted mean) is formed here
-                int N;
-                const int s0 = sel[li], s1 = sel[(li + 1) & 3];
-                const M6 m = rangeM(s0, s1, &N);
-                const PairFit pf = sF[s0 * MAXSEL + s1];
-                const double inv = 1.0 / (double)m.W;
-                line[0] = (0.5 * (double)m.Mx) * inv; line[1] = (0.5 * (double)m.My) * inv;
-                line[2] = pf.nx; line[3] = pf.ny;
-                if (pf.mse > a.max_mse) ok = 0;
-            }
-            double ln[4]; // the next side's line
-#pragma unroll
-            for (int q = 0; q < 4; q++) ln[q] = __shfl(line[q], (tid & ~3) | ((li + 1) & 3), 64);
+            const SideRec side = back_side(S, sF, bestc, tid & 3);
             double Px, Py;
-            {
-                double A00 = line[3], A01 = -ln[3], A10 = -line[2], A11 = ln[2];
-                double B0 = -line[0] + ln[0], B1 = -line[1] + ln[1];
-                double det = A00 * A11 - A10 * A01;
-                if (fabs(det) < 0.001) ok = 0;
-                double W00 = A11 / det, W01 = -A01 / det;
-                double L0 = W00 * B0 + W01 * B1;
-                Px = line[0] + L0 * A00;
-                Py = line[1] + L0 * A10;
-            }
-            // corners of the other lanes come by shuffle with a computed source lane (an indexed local array would live in
-            // scratch memory)
-            const int g0 = tid & ~3;
-            auto corner_x = [&](int q) { return __shfl(Px, g0 | (q & 3), 64); };
-            auto corner_y = [&](int q) { return __shfl(Py, g0 | (q & 3), 64); };
-            {   // Heron: triangle (0,1,2) on even lanes, (2,3,0) on odd ones; area = first + second
-                const int t = li & 1;
-                const int va = t ? 2 : 0, vb = t ? 3 : 1, vc = t ? 0 : 2;
-                const double ax = corner_x(va), ay = corner_y(va), bx = corner_x(vb), by = corner_y(vb), cx = corner_x(vc), cy = corner_y(vc);
-                double len[3];
-                { double ddx = bx - ax, ddy = by - ay; len[0] = sqrt(ddx * ddx + ddy * ddy); }
-                { double ddx = cx - bx, ddy = cy - by; len[1] = sqrt(ddx * ddx + ddy * ddy); }
-                { double ddx = ax - cx, ddy = ay - cy; len[2] = sqrt(ddx * ddx + ddy * ddy); }
-                double pp = (len[0] + len[1] + len[2]) / 2.0;
-                double term = sqrt(pp * (pp - len[0]) * (pp - len[1]) * (pp - len[2]));
-                double t0 = __shfl(term, g0, 64), t1 = __shfl(term, g0 | 1, 64);
-                double area = 0.0;
-                area += t0; area += t1;
-                double tw = (double)a.min_tag_width;
-                if (area < 0.95 * tw * tw) ok = 0;
-            }
-            {
-                const double x1 = corner_x(li + 1), y1 = corner_y(li + 1), x2 = corner_x(li + 2), y2 = corner_y(li + 2);
-                double dx1 = x1 - Px, dy1 = y1 - Py;
-                double dx2 = x2 - x1, dy2 = y2 - y1;
-                double cs = (dx1 * dx2 + dy1 * dy2) / sqrt((dx1 * dx1 + dy1 * dy1) * (dx2 * dx2 + dy2 * dy2));
-                if (cs > a.cos_critical || cs < -a.cos_critical) ok = 0;
-                if (dx1 * dy2 < dy1 * dx2) ok = 0;
-            }
-            const int all_ok = (__ballot(ok != 0) & 0xFull) == 0xFull;
-            if (tid < 4 && all_ok) {
-                double qx = Px, qy = Py;
-                if (a.decimate > 1) { qx = (qx - 0.5) * (double)a.decimate + 0.5; qy = (qy - 0.5) * (double)a.decimate + 0.5; }
-                sQuad[li][0] = qx; sQuad[li][1] = qy;
-            }
+            const bool ok = back_corner(&side, true, a, &Px, &Py);
+            const int all_ok = (__ballot(ok) & 0xFull) == 0xFull;
+            if (tid < 4 && all_ok) { sQuad[tid][0] = Px; sQuad[tid][1] = Py; }
             if (tid == 0) sFlag = all_ok;
         }
         __syncthreads();
         PROF(9);
         if (!sFlag) continue;
-        if (a.refine) {
-            // Edge refinement (oracle refine_edges).  The samples of an edge are independent: lane (edge, k) evaluates sample
-            // 16*round + k (its 2*range+1 gradient probes are independent loads), then ONE lane per edge accumulates the
-            // refined points in sample order, so every sum is formed exactly as in the sequential code.
-            const int edge = (tid >> 4) & 3, k = tid & 15;
-            const bool worker = tid < 64;
-            const int ea = edge, eb = (edge + 1) & 3;
-            double nx = 0, ny = 0, mag = 1;
-            int nsamples = 0;
-            if (worker) {
-                nx = sQuad[eb][1] - sQuad[ea][1];
-                ny = -sQuad[eb][0] + sQuad[ea][0];
-                mag = sqrt(nx * nx + ny * ny);
-                nx = nx / mag; ny = ny / mag;
-                if (reversed) { nx = -nx; ny = -ny; }
-                nsamples = (int)(mag / 8.0);
-                if (nsamples < 16) nsamples = 16;
-            }
-            int max_samples = nsamples; // the same for the 16 lanes of an edge; rounds are driven by the largest edge
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) max_samples = max(max_samples, __shfl_xor(max_samples, d, 64));
-            if (NTH > 64) {
-                if (tid == 0) sRedI[0] = max_samples;
-                __syncthreads();
-                max_samples = sRedI[0];
-                __syncthreads();
-            }
-            double Mx = 0, My = 0, Mxx = 0, Mxy = 0, Myy = 0, N = 0; // meaningful on lane k == 0 of every edge
-            for (int base = 0; base < max_samples; base += 16) {
-                if (worker) {
-                    const int sidx = base + k;
-                    double bx = __builtin_nan(""), by = 0;
-                    if (sidx < nsamples) {
-                        double alpha = (1.0 + (double)sidx) / ((double)nsamples + 1.0);
-                        double x0 = alpha * sQuad[ea][0] + (1.0 - alpha) * sQuad[eb][0];
-                        double y0 = alpha * sQuad[ea][1] + (1.0 - alpha) * sQuad[eb][1];
-                        double Mn = 0, Mcount = 0;
-                        const int range = a.decimate + 1;
-                        for (int n = -range; n <= range; n++) {
-                            double grange = 1.0;
-                            int x1 = (int)(x0 + ((double)n + grange) * nx), y1 = (int)(y0 + ((double)n + grange) * ny);
-                            if (x1 < 0 || x1 >= a.w || y1 < 0 || y1 >= a.h) continue;
-                            int x2 = (int)(x0 + ((double)n - grange) * nx), y2 = (int)(y0 + ((double)n - grange) * ny);
-                            if (x2 < 0 || x2 >= a.w || y2 < 0 || y2 >= a.h) continue;
-                            int g1 = im[(size_t)y1 * a.stride + x1], g2 = im[(size_t)y2 * a.stride + x2];
-                            if (g1 < g2) continue;
-                            double weight = (double)((g2 - g1) * (g2 - g1));
-                            Mn += weight * (double)n;
-                            Mcount += weight;
-                        }
-                        if (Mcount != 0) {
-                            double n0 = Mn / Mcount;
-                            bx = x0 + n0 * nx; by = y0 + n0 * ny;
-                        }
-                    }
-                    sRefine[edge][k][0] = bx; sRefine[edge][k][1] = by;
-                }
-                __syncthreads();
-                if (worker && k == 0)
-                    for (int q = 0; q < 16 && base + q < nsamples; q++) {
-                        double bx = sRefine[edge][q][0], by = sRefine[edge][q][1];
-                        if (bx != bx) continue; // no usable gradient at this sample
-                        Mx += bx; My += by; Mxx += bx * bx; Mxy += bx * by; Myy += by * by; N += 1.0;
-                    }
-                __syncthreads();
-            }
-            if (worker && k == 0) {
-                double line[4];
-                if (N < 2.0) {
-                    line[0] = 0.5 * (sQuad[ea][0] + sQuad[eb][0]); line[1] = 0.5 * (sQuad[ea][1] + sQuad[eb][1]);
-                    line[2] = nx; line[3] = ny;
-                } else {
-                    double Ex = Mx / N, Ey = My / N;
-                    double Cxx = Mxx / N - Ex * Ex, Cxy = Mxy / N - Ex * Ey, Cyy = Myy / N - Ey * Ey;
-                    double d = Cxx - Cyy, q4 = 4.0 * Cxy;
-                    double disc = sqrt(d * d + q4 * Cxy);
-                    double eig = 0.5 * (Cxx + Cyy + disc);
-                    double nx1 = Cxx - eig, ny1 = Cxy, M1 = nx1 * nx1 + ny1 * ny1;
-                    double nx2 = Cxy, ny2 = Cyy - eig, M2 = nx2 * nx2 + ny2 * ny2;
-                    double fx, fy, M;
-                    if (M1 > M2) { fx = nx1; fy = ny1; M = M1; } else { fx = nx2; fy = ny2; M = M2; }
-                    double len = sqrt(M);
-                    line[0] = Ex; line[1] = Ey;
-                    if (len < 1e-12) { line[2] = nx; line[3] = ny; }
-                    else { line[2] = fx / len; line[3] = fy / len; }
-                }
-                for (int q = 0; q < 4; q++) sLines[edge][q] = line[q];
-            }
-            __syncthreads();
-            if (tid == 0)
-                for (int i = 0; i < 4; i++) {
-                    int j = (i + 1) & 3;
-                    double A00 = sLines[i][3], A01 = -sLines[j][3], A10 = -sLines[i][2], A11 = sLines[j][2];
-                    double B0 = -sLines[i][0] + sLines[j][0], B1 = -sLines[i][1] + sLines[j][1];
-                    double det = A00 * A11 - A10 * A01;
-                    if (fabs(det) > 0.001) {
-                        double W00 = A11 / det, W01 = -A01 / det;
-                        double L0 = W00 * B0 + W01 * B1;
-                        sQuad[j][0] = sLines[i][0] + L0 * A00;
-                        sQuad[j][1] = sLines[i][1] + L0 * A10;
-                    }
-                }
-        }
-        if (tid == 0) {
-            uint32_t *counters = ws.d_counters + (size_t)frame * CK_CNT_STRIDE;
-            uint32_t qi = atomicAdd(&counters[CK_CNT_QUADS], 1u);
-            if (qi < (uint32_t)ws.quad_cap) {
-                ck_quad_t q;
-                for (int i = 0; i < 4; i++) { q.p[i][0] = sQuad[i][0]; q.p[i][1] = sQuad[i][1]; }
-                q.reversed_border = reversed; q.rep0 = cl.rep0; q.rep1 = cl.rep1;
-                ws.d_quads[(size_t)frame * ws.quad_cap + qi] = q;
-            } else atomicOr(&counters[CK_CNT_STATUS], (uint32_t)CK_FRAME_QUADS_OVERFLOW);
-        }
+        // ---- 6. edge refinement on the first wave (the pair table's bytes become the sample buffer), the quad record ----------
+        // (loop_tid: the refinement's lane roles and LDS addresses are formed here, for the few clusters that get this far, not carried
+        // through every cluster of the loop — with them carried, the class of up to 256 points spills two registers)
+        if (a.refine) back_refine_edges<NTH, FenceBarrier>(a, im, reversed, tid < 64, loop_tid(), sQuad, sLines, sRefine, sRedI);
+        if (tid == 0) emit_quad(ws, frame, reversed, cl.rep0, cl.rep1, sQuad);
         PROF(10);
     }
 }
@@ -1755,7 +1808,7 @@ __device__ __forceinline__ long long readlane_i64(long long v, int l) {
 // The cluster's maxima are runs of the position-ordered lists k_chunk left (one run per span the cluster touches); the (max_nmaxima + 1)-th
 // largest smoothed error is the threshold, the survivors in index order are the candidate corners; their moment prefix sums come
 // from k_chunk's running sums at the block ends (one entry, plus the totals of the spans before the target's) plus at most 32 points
-// each; from there on the phases are k_fit's (pair fits, 4-subsets, corners and checks, edge refinement) on 64 lanes.  Every prefix
+// each; from there on the phases are the shared back half's (back_pair_fits ... emit_quad, above k_fit) on 64 lanes.  Every prefix
 // sum starts at the first position of the cluster's first span and carries whatever lies between there and the cluster's first
 // point — the same addend in all of them, so it leaves with the differences; the cluster's total subtracts it by name (the head).
 constexpr int MAXRUN = 72; // spans a cluster of CK_HUGE_CAP points can touch
@@ -1781,7 +1834,6 @@ __device__ __forceinline__ void k_tail_body(const FitArgs &a) {
     // The corner phase uses four lanes per cluster: the clusters that get that far leave a record per side here and are worked off
     // eight at a time (32 lanes) — an eighth of the instructions per cluster
     constexpr int BATCH = 8;
-    struct SideRec { long long Mx, My, W; double nx, ny, mse; };
     __shared__ SideRec sB[BATCH][4];
     __shared__ uint32_t sBMeta[BATCH][4]; // frame, reversed border, rep0, rep1
     __shared__ uint32_t sWork;
@@ -1861,64 +1913,16 @@ __device__ __forceinline__ void k_tail_body(const FitArgs &a) {
         };
         int nb = 0; // clusters waiting for the corner phase
         auto flush = [&]() {
-            // ---- 5d. lines, corners, geometric checks: lane 4 c + i owns side i / corner i of waiting cluster c; every value is formed by
-            // the same operations as in the oracle's sequential code, and the verdict is the conjunction of all checks ---------
+            // ---- 5d. lines, corners, geometric checks (back_corner): lane 4 c + i owns side i / corner i of waiting cluster c ---------
             const int c = tid >> 2, li = tid & 3;
             const bool mine = c < nb;
-            int ok = mine ? 1 : 0;
-            double line[4] = {0, 0, 0, 0};
-            if (mine) {
-                const SideRec r = sB[c][li];
-                const double inv = 1.0 / (double)r.W;
-                line[0] = (0.5 * (double)r.Mx) * inv; line[1] = (0.5 * (double)r.My) * inv;
-                line[2] = r.nx; line[3] = r.ny;
-                if (r.mse > a.max_mse) ok = 0;
-            }
-            double ln[4];
-#pragma unroll
-            for (int q = 0; q < 4; q++) ln[q] = quad_perm_f64<1, 2, 3, 0>(line[q]); // the next side of the same cluster (DPP: every lane reaches flush)
             double Px, Py;
-            {
-                double A00 = line[3], A01 = -ln[3], A10 = -line[2], A11 = ln[2];
-                double B0_ = -line[0] + ln[0], B1 = -line[1] + ln[1];
-                double det = A00 * A11 - A10 * A01;
-                if (fabs(det) < 0.001) ok = 0;
-                double W00 = A11 / det, W01 = -A01 / det;
-                double L0 = W00 * B0_ + W01 * B1;
-                Px = line[0] + L0 * A00;
-                Py = line[1] + L0 * A10;
-            }
-            {
-                // even lanes: the triangle of corners 0, 1, 2; odd lanes: 2, 3, 0
-                const double ax = quad_perm_f64<0, 2, 0, 2>(Px), ay = quad_perm_f64<0, 2, 0, 2>(Py), bx = quad_perm_f64<1, 3, 1, 3>(Px), by = quad_perm_f64<1, 3, 1, 3>(Py);
-                const double cx = quad_perm_f64<2, 0, 2, 0>(Px), cy = quad_perm_f64<2, 0, 2, 0>(Py);
-                double len[3];
-                { double ddx = bx - ax, ddy = by - ay; len[0] = sqrt(ddx * ddx + ddy * ddy); }
-                { double ddx = cx - bx, ddy = cy - by; len[1] = sqrt(ddx * ddx + ddy * ddy); }
-                { double ddx = ax - cx, ddy = ay - cy; len[2] = sqrt(ddx * ddx + ddy * ddy); }
-                double pp = (len[0] + len[1] + len[2]) / 2.0;
-                double term = sqrt(pp * (pp - len[0]) * (pp - len[1]) * (pp - len[2]));
-                double t0 = quad_perm_f64<0, 0, 0, 0>(term), t1 = quad_perm_f64<1, 1, 1, 1>(term);
-                double area = 0.0;
-                area += t0; area += t1;
-                double tw = (double)a.min_tag_width;
-                if (area < 0.95 * tw * tw) ok = 0;
-            }
-            {
-                const double x1 = quad_perm_f64<1, 2, 3, 0>(Px), y1 = quad_perm_f64<1, 2, 3, 0>(Py), x2 = quad_perm_f64<2, 3, 0, 1>(Px), y2 = quad_perm_f64<2, 3, 0, 1>(Py);
-                double dx1 = x1 - Px, dy1 = y1 - Py;
-                double dx2 = x2 - x1, dy2 = y2 - y1;
-                double cs = (dx1 * dx2 + dy1 * dy2) / sqrt((dx1 * dx1 + dy1 * dy1) * (dx2 * dx2 + dy2 * dy2));
-                if (cs > a.cos_critical || cs < -a.cos_critical) ok = 0;
-                if (dx1 * dy2 < dy1 * dx2) ok = 0;
-            }
-            const unsigned long long okb = __ballot(ok != 0);
+            const bool ok = back_corner(&sB[c][li], mine, a, &Px, &Py); // (DPP moves inside: every lane reaches flush)
+            const unsigned long long okb = __ballot(ok);
             wave_sync(); // every side record has been read: the accepted clusters' corners take their first bytes
             if (mine && ((okb >> (4 * c)) & 0xFull) == 0xFull) {
-                double qx = Px, qy = Py;
-                if (a.decimate > 1) { qx = (qx - 0.5) * (double)a.decimate + 0.5; qy = (qy - 0.5) * (double)a.decimate + 0.5; }
                 double *dst = reinterpret_cast<double *>(&sB[c][li]);
-                dst[0] = qx; dst[1] = qy;
+                dst[0] = Px; dst[1] = Py;
             }
             wave_sync();
             for (int cc = 0; cc < nb; cc++) {
@@ -1929,106 +1933,9 @@ __device__ __forceinline__ void k_tail_body(const FitArgs &a) {
                 const uint8_t *im = a.im + (size_t)frame * a.pitch;
                 if (tid < 4) { const double *src = reinterpret_cast<const double *>(&sB[cc][tid]); sQuad[tid][0] = src[0]; sQuad[tid][1] = src[1]; }
                 wave_sync();
-                if (a.refine) { // edge refinement (oracle refine_edges), as in k_fit: lane (edge, k) evaluates sample 16 * round + k, one lane per edge accumulates in sample order
-                    const int edge = (tid >> 4) & 3, k = tid & 15;
-                    const int ea = edge, eb = (edge + 1) & 3;
-                    double nx = sQuad[eb][1] - sQuad[ea][1];
-                    double ny = -sQuad[eb][0] + sQuad[ea][0];
-                    const double mag = sqrt(nx * nx + ny * ny);
-                    nx = nx / mag; ny = ny / mag;
-                    if (reversed) { nx = -nx; ny = -ny; }
-                    int nsamples = (int)(mag / 8.0);
-                    if (nsamples < 16) nsamples = 16;
-                    int max_samples = nsamples;
-        #pragma unroll
-                    for (int d = 32; d >= 1; d >>= 1) max_samples = max(max_samples, __shfl_xor(max_samples, d, 64));
-                    double Mx = 0, My = 0, Mxx = 0, Mxy = 0, Myy = 0, N = 0;
-                    wave_sync(); // the pair table's bytes become the sample buffer
-                    for (int base = 0; base < max_samples; base += 16) {
-                        {
-                            const int sidx = base + k;
-                            double bx = __builtin_nan(""), by = 0;
-                            if (sidx < nsamples) {
-                                double alpha = (1.0 + (double)sidx) / ((double)nsamples + 1.0);
-                                double x0 = alpha * sQuad[ea][0] + (1.0 - alpha) * sQuad[eb][0];
-                                double y0 = alpha * sQuad[ea][1] + (1.0 - alpha) * sQuad[eb][1];
-                                double Mn = 0, Mcount = 0;
-                                const int range = a.decimate + 1;
-                                for (int n = -range; n <= range; n++) {
-                                    double grange = 1.0;
-                                    int x1 = (int)(x0 + ((double)n + grange) * nx), y1 = (int)(y0 + ((double)n + grange) * ny);
-                                    if (x1 < 0 || x1 >= a.w || y1 < 0 || y1 >= a.h) continue;
-                                    int x2 = (int)(x0 + ((double)n - grange) * nx), y2 = (int)(y0 + ((double)n - grange) * ny);
-                                    if (x2 < 0 || x2 >= a.w || y2 < 0 || y2 >= a.h) continue;
-                                    int g1 = im[(size_t)y1 * a.stride + x1], g2 = im[(size_t)y2 * a.stride + x2];
-                                    if (g1 < g2) continue;
-                                    double weight = (double)((g2 - g1) * (g2 - g1));
-                                    Mn += weight * (double)n;
-                                    Mcount += weight;
-                                }
-                                if (Mcount != 0) {
-                                    double n0 = Mn / Mcount;
-                                    bx = x0 + n0 * nx; by = y0 + n0 * ny;
-                                }
-                            }
-                            sRefine[edge][k][0] = bx; sRefine[edge][k][1] = by;
-                        }
-                        wave_sync();
-                        if (k == 0)
-                            for (int q = 0; q < 16 && base + q < nsamples; q++) {
-                                double bx = sRefine[edge][q][0], by = sRefine[edge][q][1];
-                                if (bx != bx) continue;
-                                Mx += bx; My += by; Mxx += bx * bx; Mxy += bx * by; Myy += by * by; N += 1.0;
-                            }
-                        wave_sync();
-                    }
-                    if (k == 0) {
-                        double line[4];
-                        if (N < 2.0) {
-                            line[0] = 0.5 * (sQuad[ea][0] + sQuad[eb][0]); line[1] = 0.5 * (sQuad[ea][1] + sQuad[eb][1]);
-                            line[2] = nx; line[3] = ny;
-                        } else {
-                            double Ex = Mx / N, Ey = My / N;
-                            double Cxx = Mxx / N - Ex * Ex, Cxy = Mxy / N - Ex * Ey, Cyy = Myy / N - Ey * Ey;
-                            double d = Cxx - Cyy, q4 = 4.0 * Cxy;
-                            double disc = sqrt(d * d + q4 * Cxy);
-                            double eig = 0.5 * (Cxx + Cyy + disc);
-                            double nx1 = Cxx - eig, ny1 = Cxy, M1 = nx1 * nx1 + ny1 * ny1;
-                            double nx2 = Cxy, ny2 = Cyy - eig, M2 = nx2 * nx2 + ny2 * ny2;
-                            double fx, fy, M;
-                            if (M1 > M2) { fx = nx1; fy = ny1; M = M1; } else { fx = nx2; fy = ny2; M = M2; }
-                            double len = sqrt(M);
-                            line[0] = Ex; line[1] = Ey;
-                            if (len < 1e-12) { line[2] = nx; line[3] = ny; }
-                            else { line[2] = fx / len; line[3] = fy / len; }
-                        }
-                        for (int q = 0; q < 4; q++) sLines[edge][q] = line[q];
-                    }
-                    wave_sync();
-                    if (tid == 0)
-                        for (int i = 0; i < 4; i++) {
-                            int j = (i + 1) & 3;
-                            double A00 = sLines[i][3], A01 = -sLines[j][3], A10 = -sLines[i][2], A11 = sLines[j][2];
-                            double B0_ = -sLines[i][0] + sLines[j][0], B1 = -sLines[i][1] + sLines[j][1];
-                            double det = A00 * A11 - A10 * A01;
-                            if (fabs(det) > 0.001) {
-                                double W00 = A11 / det, W01 = -A01 / det;
-                                double L0 = W00 * B0_ + W01 * B1;
-                                sQuad[j][0] = sLines[i][0] + L0 * A00;
-                                sQuad[j][1] = sLines[i][1] + L0 * A10;
-                            }
-                        }
-                }
-                if (tid == 0) {
-                    uint32_t *counters = ws.d_counters + (size_t)frame * CK_CNT_STRIDE;
-                    uint32_t qi = atomicAdd(&counters[CK_CNT_QUADS], 1u);
-                    if (qi < (uint32_t)ws.quad_cap) {
-                        ck_quad_t q;
-                        for (int i = 0; i < 4; i++) { q.p[i][0] = sQuad[i][0]; q.p[i][1] = sQuad[i][1]; }
-                        q.reversed_border = reversed; q.rep0 = rep0; q.rep1 = rep1;
-                        ws.d_quads[(size_t)frame * ws.quad_cap + qi] = q;
-                    } else atomicOr(&counters[CK_CNT_STATUS], (uint32_t)CK_FRAME_QUADS_OVERFLOW);
-                }
+                // ---- 6. edge refinement on the wave's 64 lanes (the pair table's bytes become the sample buffer), the quad record ----
+                if (a.refine) back_refine_edges<NTH, Block<NTH>>(a, im, reversed, true, tid, sQuad, sLines, sRefine, nullptr);
+                if (tid == 0) emit_quad(ws, frame, reversed, rep0, rep1, sQuad);
                 wave_sync(); // the quad has been written out: the next accepted cluster may take the corner slots
             }
             nb = 0;
@@ -2334,65 +2241,16 @@ __device__ __forceinline__ void k_tail_body(const FitArgs &a) {
             for (int q = 0; q < 6; q++) tv[q] = (sF6[T_TAIL][q] + sPart[T_TAIL][q]) - (sF6[T_HEAD][q] + sPart[T_HEAD][q]);
             total.Mx = tv[0]; total.My = tv[1]; total.Mxx = tv[2]; total.Mxy = tv[3]; total.Myy = tv[4]; total.W = tv[5];
         }
-        auto rangeM = [&](int sa, int sb, int *N) { // points from maximum sa to maximum sb inclusive, going forward
-            M6 I = {sSelI[sb][0], sSelI[sb][1], sSelI[sb][2], sSelI[sb][3], sSelI[sb][4], sSelI[sb][5]};
-            M6 E = {sSelE[sa][0], sSelE[sa][1], sSelE[sa][2], sSelE[sa][3], sSelE[sa][4], sSelE[sa][5]};
-            int i0 = sSelIdx[sa], i1 = sSelIdx[sb];
-            if (i0 < i1) { *N = i1 - i0 + 1; return m6_sub(I, E); }
-            *N = sz - i0 + i1 + 1;
-            return m6_add(m6_sub(total, E), I);
-        };
+        const SelSums S = {sSelI, sSelE, sSelIdx, total, sz};
 
         if (a.stop_after == 6) continue;
-        // ---- 5c. one line fit per ordered pair of maxima; the 4-subset search is then table lookups ------------------------
+        // ---- 5c. one line fit per ordered pair of maxima; the 4-subset search is then table lookups (the shared back half) ----
         PairFit *sF = reinterpret_cast<PairFit *>(sPraw);
-        {
-            const int npf = nsel * (nsel - 1) / 2;
-            for (int k = tid; k < npf; k += NTH) {
-                const int pk = g_pair_table.v[k], sa = pk >> 4, sb = pk & 15;
-                int Nf, Nw;
-                const M6 mf = rangeM(sa, sb, &Nf), mw = rangeM(sb, sa, &Nw);
-                double lp[4], lq[4], ef, msf, ew, msw;
-                fit_line_m(mf, Nf, lp, &ef, &msf);
-                fit_line_m(mw, Nw, lq, &ew, &msw);
-                PairFit f;
-                f.err = ef; f.mse = msf; f.nx = lp[2]; f.ny = lp[3];
-                sF[sa * MAXSEL + sb] = f;
-                f.err = ew; f.mse = msw; f.nx = lq[2]; f.ny = lq[3];
-                sF[sb * MAXSEL + sa] = f;
-            }
-        }
+        back_pair_fits<NTH>(S, nsel, sF, tid);
         wave_sync();
-        double best = HUGE_VAL;
-        int bestc = 1 << 30;
-        {
-            const int ncomb = nsel * (nsel - 1) * (nsel - 2) * (nsel - 3) / 24;
-            for (int cb = tid; cb < ncomb; cb += NTH) {
-                const int pk = g_combo_table.v[cb];
-                const int m0 = pk >> 12, m1 = (pk >> 8) & 15, m2 = (pk >> 4) & 15, m3 = pk & 15;
-                const PairFit f01 = sF[m0 * MAXSEL + m1];
-                if (f01.mse > a.max_mse) continue;
-                const PairFit f12 = sF[m1 * MAXSEL + m2];
-                if (f12.mse > a.max_mse) continue;
-                double dp = f01.nx * f12.nx + f01.ny * f12.ny;
-                if (fabs(dp) > a.cos_critical) continue;
-                const PairFit f23 = sF[m2 * MAXSEL + m3];
-                if (f23.mse > a.max_mse) continue;
-                const PairFit f30 = sF[m3 * MAXSEL + m0];
-                if (f30.mse > a.max_mse) continue;
-                double e = f01.err + f12.err + f23.err + f30.err;
-                if (e < best || (e == best && pk < bestc)) { best = e; bestc = pk; }
-            }
-        }
-        {
-            // the wave's smallest (best, bestc) on the DPP ladder, `best` through its order-preserving integer image as in 5a: a lane's
-            // best is HUGE_VAL or a sum that passed `e < best`, never NaN; errors that compare equal have the same image once
-            // + 0.0 has made a -0.0 the +0.0 it equals
-            const unsigned long long bb = (unsigned long long)__double_as_longlong(best + 0.0);
-            unsigned long long bk = (bb >> 63) ? ~bb : (bb | (1ull << 63));
-            wave_argmin_u64_i32(bk, bestc);
-            best = __longlong_as_double((long long)((bk >> 63) ? (bk ^ (1ull << 63)) : ~bk));
-        }
+        double best;
+        int bestc;
+        back_best_subset<NTH, Block<NTH>>(sF, nsel, a, tid, nullptr, nullptr, &best, &bestc);
         if (best == HUGE_VAL) continue;
         FDBG(4);
         if (best / (double)sz >= a.max_mse) continue;
@@ -2400,16 +2258,7 @@ __device__ __forceinline__ void k_tail_body(const FitArgs &a) {
 
         if (a.stop_after == 7) continue;
         // ---- 5d. the four sides' records; the corner phase runs when eight clusters wait (or the chunk ends) -----------------------
-        if (tid < 4) {
-            const int sel[4] = {(bestc >> 12) & 15, (bestc >> 8) & 15, (bestc >> 4) & 15, bestc & 15};
-            int N;
-            const int s0 = sel[tid], s1 = sel[(tid + 1) & 3];
-            const M6 m = rangeM(s0, s1, &N);
-            const PairFit pf = sF[s0 * MAXSEL + s1];
-            SideRec r;
-            r.Mx = m.Mx; r.My = m.My; r.W = m.W; r.nx = pf.nx; r.ny = pf.ny; r.mse = pf.mse;
-            sB[nb][tid] = r;
-        }
+        if (tid < 4) sB[nb][tid] = back_side(S, sF, bestc, tid);
         if (tid == 0) { sBMeta[nb][0] = (uint32_t)frame; sBMeta[nb][1] = (uint32_t)reversed; sBMeta[nb][2] = rep0; sBMeta[nb][3] = rep1; }
         nb++;
         wave_sync();
@@ -2419,7 +2268,7 @@ __device__ __forceinline__ void k_tail_body(const FitArgs &a) {
     }
 }
 
-// Register budget: four waves per SIMD (128 registers; the code object says 121 used, no spilled register, no scratch — with the block
+// Register budget: four waves per SIMD (128 registers; the code object says 119 used, no spilled register, no scratch — with the block
 // scan of 5b still in, it said 126, two spilled, 12 bytes of scratch; with SEL_RV = 8 it says 126).  A build for five (96 registers, 59 of them spilled) once
 // looked 7 % faster and was WRONG (detections missing at 1920x1080 and 2448x2048, copies of one frame differing): two v_readlane
 // reads of the chunk heads stood inside `if (lane < ...)` / `if (tid == 0)` blocks, where the lane they read may be switched off, and

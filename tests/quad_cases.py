@@ -207,6 +207,38 @@ def long_frame(bright_on_dark=False, side=160, skew=0.1):
     return np.where(m, fg, bg).astype(np.uint8)
 
 
+# ---- classes: a quad from a cluster of every thread count k_fit runs at ----------------------------------------------------------------------
+# points of a cluster (before duplicate removal) up to -> threads of its workgroup (k_quads.hip: FIT_CLASS; what only a workgroup of
+# several waves does — one pair fit per lane, reductions and broadcasts across waves — runs at 128, 256 and 512).  Beyond 16 384 points
+# a cluster needs a frame of more than 1 400 px: left to the detect tests.
+CLASS_THREADS = ((512, 64), (1024, 128), (4096, 256), (16384, 512))
+# sides (px of the quad image) of one slightly skewed dark square per thread count, about 12.15 points per pixel of side: 436, 728,
+# 1 460 and 4 102 points in the trace (check_classes returns them).  The last is the smallest side whose outline has more than 4 096
+# (336 px: 4 090 points).
+CLASS_SIDES = (36, 60, 120, 337)
+# One frame, repeated: one more than a call may bring and still run its size classes side by side (k_quads.hip: ck_launch_fit_quads) —
+# such a call does without the class of 513..1024 points and would fit them on 256 threads; the batch plan has all four thread counts.
+CLASS_FRAMES = {1: 17, 2: 33}
+
+
+def classes_frame(decimate, sides=CLASS_SIDES, skew=0.1):
+    """The largest square as a dark frame 18 px thick (its inner outline, bright inside dark, leaves at the border direction), the
+    others dark on its bright inside: the image is no larger than the largest square needs.  Everything scales with quad_decimate,
+    so the clusters of the decimated image are those of quad_decimate 1."""
+    d, big = decimate, sides[-1]
+    h, w = d * (big + 24), d * (int(big * (1 + skew)) + 26)
+    yy, xx = np.mgrid[0:h, 0:w]
+    inside = lambda cx, cy, s: (np.abs((xx - cx) - skew * (yy - cy)) < d * s / 2) & (np.abs(yy - cy) < d * s / 2)
+    im = np.full((h, w), BRIGHT, np.uint8)
+    im[inside(w / 2, h / 2, big)] = DARK
+    im[inside(w / 2, h / 2, big - 36)] = BRIGHT
+    x = w / 2 - d * (big - 36) / 2 + d * 24
+    for s in sides[-2::-1]:   # left to right, the largest first, centred on the middle row
+        im[inside(x + d * s / 2, h / 2, s)] = DARK
+        x += d * (s + 16)
+    return im
+
+
 # ---- the cases -------------------------------------------------------------------------------------------------------------------------------
 TIES_SEEDS, TIES_NMAXIMA = (4, 6), (9, 10, 11)   # found by search_ties: the frames in which a tie straddles the cut and two subsets tie
 BORDER_OFFSETS = (1, 2, 3)
@@ -314,6 +346,26 @@ def check_batch(oracle, frames, settings, rd, quads):
                  {"quads in the distinct frames": 10})
 
 
+def quads_per_thread_count(rd):
+    """{threads: point counts of the clusters that left as quads} on the readouts, by CLASS_THREADS"""
+    q, out, lo = rd[rd[:, EXIT] == QUAD], {}, 0
+    for top, nth in CLASS_THREADS:
+        out[nth] = q[(q[:, POINTS] > lo) & (q[:, POINTS] <= top), POINTS].tolist()
+        lo = top
+    return out
+
+
+def check_classes(oracle, frames, settings, rd, quads):
+    """per thread count of k_fit: a cluster that leaves as a quad, with edge refinement on, in a call that takes the batch plan"""
+    assert settings["refine_edges"] == 1
+    assert len(frames) == CLASS_FRAMES[settings["quad_decimate"]] > (16 if settings["quad_decimate"] == 1 else 32)
+    per = quads_per_thread_count(rd)
+    fig = {"quads from %d threads" % nth: len(p) for nth, p in per.items()}
+    fig.update({"their points (%d threads)" % nth: p for nth, p in per.items()})
+    fig["frame"] = frames[0].shape
+    return _need(fig, {"quads from %d threads" % nth: 1 for _, nth in CLASS_THREADS})
+
+
 def _batch_frames():
     one = np.concatenate([small_frames(), noise_frames()])
     return np.concatenate([one] * (BATCH_FRAMES // len(one)))
@@ -337,6 +389,8 @@ def specs():
     out.append(("long", lambda: long_frame()[None], {"refine_edges": 1}, check_long))
     out.append(("reversed", lambda: long_frame(bright_on_dark=True)[None], {"refine_edges": 1, "families": list(REVERSED_FAMILIES)}, check_reversed))
     out += [("batch_d%d" % d, _batch_frames, {"quad_decimate": d}, check_batch) for d in (1, 2)]
+    out += [("classes_d%d" % d, (lambda d=d: np.stack([classes_frame(d)] * CLASS_FRAMES[d])), {"quad_decimate": d, "refine_edges": 1}, check_classes)
+            for d in (1, 2)]
     return out
 
 

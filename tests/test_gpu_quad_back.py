@@ -35,7 +35,8 @@ def cases(oracle, tmp_path_factory):
 
 @pytest.mark.parametrize("name", qc.NAMES)
 def test_back_half_on_the_product_library(cases, name):
-    """In this process: a call of a few frames runs k_fit, its size classes side by side; the 40 frames of batch_* take the batch plan."""
+    """In this process: a call of a few frames runs k_fit, its size classes side by side; the 40 frames of batch_* and the 17 / 33 of
+    classes_* take the batch plan, which has k_fit's 128-thread class too."""
     from quad_back_child import run_case
     _, data, figures = cases
     assert name in figures   # (the conditions held: the fixture asserts them)

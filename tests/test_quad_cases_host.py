@@ -33,7 +33,16 @@ Measured when the cases were written (condition: minimum -> measured):
   border_d1 / _d2           quads with a corner < quad_decimate + 1 px from the border    1   1 (1.0 px; four more at 2.0) / 2 (2.5 px)
   long; reversed            longest edge > 136 px; quads with reversed_border = 1         1   160.2 px; 1
   batch_d1 / _d2            frames (5 distinct); quads in the distinct frames            10   40; 156 / 68
+  classes_d1 / _d2          quads, refine_edges 1, from a cluster of 64 / 128 / 256 / 512
+                            threads (17 / 33 copies of one 361x396 / 722x792 frame)   1 each  1 / 1 / 1 / 1  (436, 728, 1460, 4102 points)
   (refine_edges does not enter the readout: the r0 and r1 cases of a noise setting measure the same.)
+
+Why classes_*: k_fit runs a cluster on 64 (up to 512 points), 128 (513..1024), 256 (1025..4096) or 512 threads (more), and what only a
+workgroup of several waves does (a pair fit per lane, reductions and a broadcast across waves) needs a cluster that goes all the way
+to a refined quad at each.  Quads per thread count (qc.quads_per_thread_count) in the cases that have refine_edges on, before classes_*:
+  64: every case but long / reversed; 128: noise_*_d1 3..6, noise_m12_d2 1, border_d1 9, batch_d1 5 — in calls of 3 frames, which do
+  without the 128-thread class, all but batch_d1's; 256: noise_m12_d1 1, long 1, reversed 1; 512: none; quad_decimate 2: 256 and 512 none.
+  tests/test_gpu_seq_front.py's nested quadrilaterals (default settings): edges640 1 / 1 / 2 / 0, edges272 2 / 1 / 1 / 0, shapes640 5 / 1 / 0 / 0.
 """
 import numpy as np
 import pytest
