@@ -95,7 +95,7 @@ struct ck_stage_ws {
     ck_packed_point *d_points; // [n][ext_cap] (point_cap used) points grouped by cluster
     // split quad fit: extended point sequences and what k_chunk leaves for k_tail.  d_tmp and d_points are dead by then and carry
     // the two largest arrays (same frame pitch, so a frame's bytes never overlap another frame's)
-    int ext_cap;               // positions per frame: point_cap + CK_EXT_HALO * cluster_cap, rounded up to a multiple of CK_SPAN; the frame pitch of d_tmp / d_points
+    int ext_cap;               // positions per frame: point_cap + CK_EXT_HALO * cluster_cap (+ 2 * CK_SPAN in the diagnostics build: CK_EXT_BASE), rounded up to a multiple of CK_SPAN; the frame pitch of d_tmp / d_points
     uint32_t *d_ext_xy;        // = d_tmp: [n][ext_cap] x << 13 | y (half-pixel) | window half-width << 26
     uint16_t *d_ext_w;         // [n][ext_cap] gradient weight
     double *d_maxval;          // = d_points: [n][ext_cap / CK_SPAN][CK_SPAN / 2] smoothed errors at the maxima of a span, in position order
@@ -262,7 +262,8 @@ int ck_hip_failed(hipError_t e, const char *call, const char *file, int line, bo
 #define CK_HIP_ALLOC(call) CK_HIP_(call, true)
 
 // Diagnostic knobs (CK_TILE_STOP_AFTER, CK_FIT_SKIP, CK_FMERGE_CAP, ...: kernels cut short, classes skipped, paths forced, launch
-// geometry varied) exist only in the -DCK_DIAG build (`make diag` -> chalkydri_amd/lib/diag/libchalkydri_hip.so), which the
+// geometry varied; CK_EXT_BASE: the first position of the split fit's extended sequences in every frame of a call, 0 .. 2 * CK_SPAN,
+// for which that build's frames are 2 * CK_SPAN positions longer) exist only in the -DCK_DIAG build (`make diag` -> chalkydri_amd/lib/diag/libchalkydri_hip.so), which the
 // measurement scripts under tools/ and the path-forcing tests load.  In the product build every knob IS its default: the macro
 // drops the name, so neither the getenv call nor the string is in the library a host links — the environment cannot change what
 // the drop-in returns.  The product library reads exactly two variables: CK_POISON (allocation fill / guard pages, below) and

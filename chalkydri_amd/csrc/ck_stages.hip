@@ -135,7 +135,10 @@ static int stage_caps(ck_handle *h) {
     ws.max_cluster_points = 3 * (2 * h->qw + 2 * h->qh); // AprilTag-3's bound; <= 3 * 4 * 4095 < CK_HUGE_CAP (ck_create bounds the sides)
     if (cfg.max_nmaxima < 4 || cfg.max_nmaxima > 12) return CK_EINVAL;
     {   // frame pitch of the point arrays = positions of the split fit's extended sequences (ck_internal.h)
-        const size_t e = (size_t)ws.point_cap + (size_t)CK_EXT_HALO * ws.cluster_cap;
+        size_t e = (size_t)ws.point_cap + (size_t)CK_EXT_HALO * ws.cluster_cap;
+#ifdef CK_DIAG
+        e += 2 * CK_SPAN; // room for CK_EXT_BASE (k_quads.hip: ck_launch_fit_quads), the diagnostics build's shift of a frame's sequences
+#endif
         const size_t r = (e + CK_SPAN - 1) / CK_SPAN * CK_SPAN;
         if (r > 0x7FFFFFFFu - 4096) return CK_EINVAL;
         ws.ext_cap = (int)r;

@@ -2428,6 +2428,14 @@ extern "C" int ck_fit_profile_read(unsigned long long *out, int reset) {
 }
 #endif
 
+#ifdef CK_DIAG
+// (diagnostics, CK_EXT_BASE: the first position k_seq hands out in every frame of the call — where a cluster lands on k_chunk's span grid)
+__global__ void k_ext_base(uint32_t *counters, int n, uint32_t base) {
+    const int f = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (f < n) counters[(size_t)f * CK_CNT_STRIDE + CK_CNT_EXT] = base;
+}
+#endif
+
 int ck_launch_fit_quads(ck_handle *h, const ck_dev_image &qimg, const ck_dev_image &img, int n) {
     ck_stage_ws &ws = h->ws;
     if (n > 4095 || ws.cluster_cap > (1 << 20)) return CK_EINVAL;
@@ -2483,6 +2491,14 @@ int ck_launch_fit_quads(ck_handle *h, const ck_dev_image &qimg, const ck_dev_ima
     // (measurements of the selection with CK_FIT_STOP_AFTER <= 5: a cut above every cluster's count skips the threshold search, and
     // every cluster with more than MAXSEL maxima then leaves after the selection)
     a.max_nmaxima = CK_KNOB("CK_FIT_NMAXIMA", a.max_nmaxima);
+#ifdef CK_DIAG
+    {   // the frames' position counters start at CK_EXT_BASE (read per call; clamped to the room stage_caps adds for it in this build):
+        // on the handle's stream, behind k_clear's zero and before the first k_seq of any lane
+        int ext_base = CK_KNOB("CK_EXT_BASE", 0);
+        if (ext_base > 2 * CK_SPAN) ext_base = 2 * CK_SPAN;
+        if (ext_base > 0) hipLaunchKernelGGL(k_ext_base, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, ws.d_counters, n, (uint32_t)ext_base);
+    }
+#endif
     auto use_list = [&](int l) { a.list = fl.lists + (size_t)l * list_cap; a.list_count = fl.list_counts + l; a.head = fl.heads + l; };
     auto launch_wimg = [&](hipStream_t st) {
         const int w4 = (h->qw + 3) / 4;

@@ -207,9 +207,10 @@ def test_product_library_reads_no_diagnostic_knob(built):
     # (error-code names appear in ck_strerror's texts; anything else that looks like a knob is a failure)
     knobs = {n for n in names if not n.startswith(("CK_E", "CK_OK", "CK_FRAME_", "CK_HIP", "CK_ALLOC", "CK_ABI"))}
     assert knobs <= {"CK_POISON", "CK_STREAMS"}, knobs
-    assert b"STOP_AFTER" not in prod and b"CK_FIT_" not in prod and b"CK_FMERGE" not in prod
+    assert b"STOP_AFTER" not in prod and b"CK_FIT_" not in prod and b"CK_FMERGE" not in prod and b"CK_EXT_BASE" not in prod
+    assert b"k_ext_base" not in prod   # (the kernel that sets the knob's value is the diagnostics build's too)
     diag = open(DIAG_LIB, "rb").read()
-    for k in (b"CK_TILE_STOP_AFTER", b"CK_FMERGE_CAP", b"CK_FIT_FLAT", b"CK_FIT_SKIP", b"CK_PARTS", b"CK_EMIT_STOP_AFTER"):
+    for k in (b"CK_TILE_STOP_AFTER", b"CK_FMERGE_CAP", b"CK_FIT_FLAT", b"CK_FIT_SKIP", b"CK_PARTS", b"CK_EMIT_STOP_AFTER", b"CK_EXT_BASE"):
         assert k in diag, k
 
 
