@@ -4,8 +4,7 @@
 // written (-ffp-contract=off on both sides), so the two produce the same bytes.  THE OPERATION ORDER IS PART OF THE CONTRACT.
 //
 // k[9]: EUCM fx fy cx cy alpha beta 0 0 0.  UCM is EUCM with beta = 1: whoever calls these functions has put 1.0 into k[5]
-// (ckm_effective).  OPENCV5 fx fy cx cy k1 k2 p1 p2 k3 is here only as the host's copy of ck_mat3.h's undistort_one; the device keeps
-// the text it has.
+// (ckm_effective).  OPENCV5: fx fy cx cy k1 k2 p1 p2 k3.
 #ifndef CK_CAMERA_MATH_H
 #define CK_CAMERA_MATH_H
 
@@ -70,7 +69,8 @@ CKM_FN int ckm_eucm_project(const double *k, double X, double Y, double Z, doubl
     return 1;
 }
 
-// OpenCVModel5: the text of ck_mat3.h's undistort_one on a parameter array (the fixed-point iteration of the reference's unproject)
+// OpenCVModel5 undistortion of one pixel to the normalised point (x, y): the fixed-point iteration of the reference's unproject.
+// With all-zero distortion the first step returns ((u - cx) / fx, (v - cy) / fy) exactly and converges.
 CKM_FN int ckm_opencv5_undistort(const double *c, double u, double v, double *xo, double *yo) {
     const double xd = (u - c[2]) / c[0], yd = (v - c[3]) / c[1];
     double x = xd, y = yd;

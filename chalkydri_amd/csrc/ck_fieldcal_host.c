@@ -7,6 +7,7 @@
 #include "ck_cal_c.h"
 #include "ck_fieldcal_c.h"
 #include "ck_fieldcal_math.h"
+#include "ck_pose_math.h"
 #include "ck_rigcal_c.h"
 #include <stdlib.h>
 #include <string.h>
@@ -64,7 +65,7 @@ int ck_fieldcal_check(const ck_fieldcal_params_t *p, int32_t n_cams, const ck_sq
 
 /* ---- what both solvers share ------------------------------------------------------------------------------------------------- */
 void ck_fieldcal_tag_in(const ck_iso3_t *iso, double *T) {
-    ck_rigcal_quat_to_mat(iso->q, T);
+    quat_to_mat(iso->q, T);
     for (int i = 0; i < 3; i++) T[9 + i] = iso->t[i];
 }
 

@@ -1,52 +1,22 @@
-/* ck_rig_host.c — the rig solver on the host, one thread, plain C: the specification of k_rig (k_rigpnp.hip) and what the CPU suite
- * tests the arithmetic with.  DESIGN.md §4k has the formulas; every sum runs over cameras in index order and points in index order,
- * every rotation and elimination in the order of the device code, so the two agree to round-off of the transcendental functions
- * alone.  No device, no HIP header. */
+/* ck_rig_host.c — the rig solver on the host, one thread, plain C: the specification of k_rig and k_rig_robust (k_rigpnp.hip) and what
+ * the CPU suite tests the arithmetic with.  DESIGN.md §4k has the formulas.  What one lane computes alone is ck_pose_math.h's, the text
+ * the kernels compile: the 3x3 algebra up to the nearest rotation, a point's world position, ray and residual, the translation of an r,
+ * the GNC weight, the standard deviations, the yaw pivot.  What the kernels spread over lanes is spelled out here a second time, in the
+ * order of the device code: the sums over cameras in index order and points in index order (rig_system), the 9x9 Jacobi (jacobi9), the
+ * 15x15 elimination of the SQP step (lu_solve15, optimization), the choice among the candidates.  So the two agree to round-off of the
+ * transcendental functions alone.  No device, no HIP header. */
 #include <float.h>
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
 
+#include "ck_pose_math.h"
 #include "ck_rig_c.h"
 
-#define XY_STD_DEV_SCALAR 5.0
-#define THETA_STD_DEV_SCALAR 2.0
-#define MAX_TRUSTABLE_RMS 0.1
-#define MAX_GYRO_DELTA 30.0
-#define TAG_SIZE 0.1651
-#define CORNER_DISTANCE (TAG_SIZE / 2.0)
-#define PI_D 3.14159265358979323846
-
-static void quat_to_mat(const double q[4], double R[9]) {
-    double w = q[0], x = q[1], y = q[2], z = q[3];
-    double n = sqrt(w * w + x * x + y * y + z * z);
-    w /= n; x /= n; y /= n; z /= n;
-    R[0] = 1 - 2 * (y * y + z * z); R[1] = 2 * (x * y - z * w);     R[2] = 2 * (x * z + y * w);
-    R[3] = 2 * (x * y + z * w);     R[4] = 1 - 2 * (x * x + z * z); R[5] = 2 * (y * z - x * w);
-    R[6] = 2 * (x * z - y * w);     R[7] = 2 * (y * z + x * w);     R[8] = 1 - 2 * (x * x + y * y);
-}
-static void mat3_mul(const double A[9], const double B[9], double C[9]) {
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) C[i * 3 + j] = A[i * 3] * B[j] + A[i * 3 + 1] * B[3 + j] + A[i * 3 + 2] * B[6 + j];
-}
-static void mat3_vec(const double A[9], const double v[3], double o[3]) {
-    for (int i = 0; i < 3; i++) o[i] = A[i * 3] * v[0] + A[i * 3 + 1] * v[1] + A[i * 3 + 2] * v[2];
-}
-static double mat3_det(const double m[9]) {
-    return m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
-}
-static int mat3_try_inverse(const double m[9], double o[9]) {
-    double det = mat3_det(m);
-    if (det == 0.0) return 0;
-    o[0] = (m[4] * m[8] - m[5] * m[7]) / det; o[1] = (m[2] * m[7] - m[1] * m[8]) / det; o[2] = (m[1] * m[5] - m[2] * m[4]) / det;
-    o[3] = (m[5] * m[6] - m[3] * m[8]) / det; o[4] = (m[0] * m[8] - m[2] * m[6]) / det; o[5] = (m[2] * m[3] - m[0] * m[5]) / det;
-    o[6] = (m[3] * m[7] - m[4] * m[6]) / det; o[7] = (m[1] * m[6] - m[0] * m[7]) / det; o[8] = (m[0] * m[4] - m[1] * m[3]) / det;
-    return 1;
-}
-
-/* cyclic Jacobi of a symmetric n x n matrix (n = 3, 9), row-major; the columns of V are the eigenvectors.  Stop rule, sweep order and
- * rotation formulas are jacobi3's (ck_mat3.h) and the 9 x 9 of the pose kernels. */
-static void jacobi_eigen(double *A, int n, double *V, double *w) {
+/* cyclic Jacobi of a symmetric 9x9 (destroyed), row-major; the columns of V are the eigenvectors.  Stop rule, sweep order and
+ * rotation formulas are jacobi3's (ck_pose_math.h) and jacobi9_wave's (ck_sqpnp_dev.h). */
+static void jacobi9(double *A, double *V, double *w) {
+    const int n = 9;
     for (int i = 0; i < n; i++)
         for (int j = 0; j < n; j++) V[i * n + j] = (i == j);
     double tot = 0;
@@ -71,65 +41,6 @@ static void jacobi_eigen(double *A, int n, double *V, double *w) {
             }
     }
     for (int i = 0; i < n; i++) w[i] = A[i * n + i];
-}
-
-static void svd3(const double M[9], double U[9], double s[3], double V[9]) {
-    double MtM[9], Vt[9], w[3];
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) MtM[i * 3 + j] = M[0 + i] * M[0 + j] + M[3 + i] * M[3 + j] + M[6 + i] * M[6 + j];
-    jacobi_eigen(MtM, 3, Vt, w);
-    int idx[3] = {0, 1, 2};
-    for (int i = 0; i < 3; i++)
-        for (int j = i + 1; j < 3; j++)
-            if (w[idx[j]] > w[idx[i]]) { int t = idx[i]; idx[i] = idx[j]; idx[j] = t; }
-    for (int c = 0; c < 3; c++) {
-        s[c] = sqrt(w[idx[c]] > 0 ? w[idx[c]] : 0);
-        for (int r = 0; r < 3; r++) V[r * 3 + c] = Vt[r * 3 + idx[c]];
-    }
-    for (int c = 0; c < 3; c++) {
-        double v[3] = {V[c], V[3 + c], V[6 + c]}, u[3];
-        mat3_vec(M, v, u);
-        double n = sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
-        if (n > 1e-12 * (s[0] > 0 ? s[0] : 1.0)) { for (int r = 0; r < 3; r++) U[r * 3 + c] = u[r] / n; }
-        else if (c == 2) { /* complete a right-handed frame */
-            double ua[3] = {U[0], U[3], U[6]}, ub[3] = {U[1], U[4], U[7]};
-            double cr[3] = {ua[1] * ub[2] - ua[2] * ub[1], ua[2] * ub[0] - ua[0] * ub[2], ua[0] * ub[1] - ua[1] * ub[0]};
-            double cn = sqrt(cr[0] * cr[0] + cr[1] * cr[1] + cr[2] * cr[2]);
-            for (int r = 0; r < 3; r++) U[r * 3 + 2] = cn > 0 ? cr[r] / cn : (r == 2);
-        } else if (c == 1) { /* rank 1: the coordinate axis least aligned with u0 (first on ties), made orthogonal to u0 */
-            double u0[3] = {U[0], U[3], U[6]};
-            int k = 0;
-            for (int r = 1; r < 3; r++)
-                if (fabs(u0[r]) < fabs(u0[k])) k = r;
-            double e[3] = {0, 0, 0};
-            e[k] = 1.0;
-            double d = u0[k], g[3] = {e[0] - d * u0[0], e[1] - d * u0[1], e[2] - d * u0[2]};
-            double gn = sqrt(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
-            for (int r = 0; r < 3; r++) U[r * 3 + 1] = g[r] / gn;
-        } else { /* zero matrix: U = I */
-            for (int r = 0; r < 3; r++) U[r * 3 + 0] = (r == 0);
-        }
-    }
-}
-/* nearest rotation of a row-major 3x3 (U V^T with the chirality fix) */
-static void polar_rotation(const double M[9], double out[9]) {
-    double U[9], s[3], V[9], Vt[9];
-    svd3(M, U, s, V);
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) Vt[i * 3 + j] = V[j * 3 + i];
-    mat3_mul(U, Vt, out);
-    if (mat3_det(out) < 0.0) {
-        for (int r = 0; r < 3; r++) U[r * 3 + 2] = -U[r * 3 + 2];
-        mat3_mul(U, Vt, out);
-    }
-}
-static void nearest_so3(const double r_vec[9], double out[9]) { /* column-major in and out */
-    double M[9], rot[9];
-    for (int c = 0; c < 3; c++)
-        for (int r = 0; r < 3; r++) M[r * 3 + c] = r_vec[c * 3 + r];
-    polar_rotation(M, rot);
-    for (int c = 0; c < 3; c++)
-        for (int r = 0; r < 3; r++) out[c * 3 + r] = rot[r * 3 + c];
 }
 
 /* 15x15 LU with partial pivoting (first maximum of a column); 0 when a pivot is exactly zero */
@@ -251,15 +162,13 @@ static double tag_weight(const double *w, int point) { return w ? w[point >> 2] 
 
 static void rig_prepare(rig_step_t *st, int n_cams, const ck_sqpnp_problem_t *problems, int n, int step, const ck_iso3_t *tags,
                         const double *bearings, double *world, double *dir, int *cam_of) {
-    static const double cp[4][3] = {{0, -CORNER_DISTANCE, -CORNER_DISTANCE}, {0, CORNER_DISTANCE, -CORNER_DISTANCE},
-                                    {0, CORNER_DISTANCE, CORNER_DISTANCE}, {0, -CORNER_DISTANCE, CORNER_DISTANCE}};
     st->n_cams = n_cams; st->world = world; st->dir = dir; st->cam_of = cam_of;
     st->base[0] = 0;
     for (int c = 0; c < n_cams; c++) {
         const ck_sqpnp_problem_t *p = &problems[(size_t)c * (size_t)n + (size_t)step];
         quat_to_mat(p->robot_to_cam.q, st->A[c]);
         for (int k = 0; k < 3; k++) st->b[c][k] = p->robot_to_cam.t[k];
-        for (int i = 0; i < 3; i++) st->o[c][i] = -(st->A[c][i] * st->b[c][0] + st->A[c][3 + i] * st->b[c][1] + st->A[c][6 + i] * st->b[c][2]);
+        ckp_camera_origin(st->A[c], st->b[c], st->o[c]);
         st->base[c + 1] = st->base[c] + 4 * p->n_tags;
         st->tg[c] = tags + p->tag_offset;
     }
@@ -270,11 +179,10 @@ static void rig_prepare(rig_step_t *st, int n_cams, const ck_sqpnp_problem_t *pr
         const double *v = bearings + (size_t)3 * (size_t)p->bearing_offset;
         for (int j = 0; j < 4 * p->n_tags; j++) {
             const int i = st->base[c] + j, t = j >> 2;
-            double R[9], pt[3];
+            double R[9];
             quat_to_mat(tg[t].q, R);
-            mat3_vec(R, cp[j & 3], pt);
-            for (int k = 0; k < 3; k++) world[i * 3 + k] = pt[k] + tg[t].t[k];
-            for (int k = 0; k < 3; k++) dir[i * 3 + k] = st->A[c][k] * v[3 * j] + st->A[c][3 + k] * v[3 * j + 1] + st->A[c][6 + k] * v[3 * j + 2];
+            ckp_tag_corner(R, tg[t].t, j & 3, world + i * 3);
+            ckp_ray(st->A[c], v + 3 * j, dir + i * 3);
             cam_of[i] = c;
         }
     }
@@ -351,7 +259,7 @@ static void rig_starts(const ck_rig_params_t *prm, rig_sys_t *y, double gyro, do
         double Sw[9], Sv[9], sw[3];
         S[3] = S[1]; S[6] = S[2]; S[7] = S[5];
         memcpy(Sw, S, sizeof Sw);
-        jacobi_eigen(Sw, 3, Sv, sw);
+        jacobi3(Sw, Sv, sw);
         int k = 0;
         double wmin = sw[0], wmax = sw[0];
         if (sw[1] < wmin) { wmin = sw[1]; k = 1; }
@@ -367,7 +275,7 @@ static void rig_starts(const ck_rig_params_t *prm, rig_sys_t *y, double gyro, do
                     if (i % 3 == j % 3) Aw[i * 9 + j] += mu * (nrm[i / 3] * nrm[j / 3]);
         }
     }
-    jacobi_eigen(Aw, 9, V, ev);
+    jacobi9(Aw, V, ev);
     int idx[9] = {0, 1, 2, 3, 4, 5, 6, 7, 8};
     for (int i = 1; i < 9; i++) { /* stable ascending order of the eigenvalues */
         int v = idx[i], j = i - 1;
@@ -397,18 +305,7 @@ static void rig_starts(const ck_rig_params_t *prm, rig_sys_t *y, double gyro, do
 
 /* R (row-major) of r (column-major) and the t that goes with it */
 static void rig_translation(const rig_sys_t *y, const double r[9], double Rm[9], double t[3]) {
-    double qtr[3], d[3], tl[3], Rc[3];
-    for (int c = 0; c < 3; c++)
-        for (int rr = 0; rr < 3; rr++) Rm[rr * 3 + c] = r[c * 3 + rr];
-    for (int j = 0; j < 3; j++) {
-        double s = 0;
-        for (int i = 0; i < 9; i++) s += y->Qrt[i * 3 + j] * r[i];
-        qtr[j] = s;
-    }
-    for (int k = 0; k < 3; k++) d[k] = y->qt[k] - qtr[k];
-    mat3_vec(y->QttInv, d, tl);
-    mat3_vec(Rm, y->centroid, Rc);
-    for (int k = 0; k < 3; k++) t[k] = tl[k] - Rc[k];
+    ckp_translation(y->Qrt, y->qt, y->QttInv, y->centroid, r, Rm, t);
 }
 
 /* the cheapest candidate with every point (of a weight other than 0) in front of its own camera */
@@ -464,58 +361,21 @@ static void rig_finish(const rig_step_t *st, const double *w, const double bestR
         double s = 0;
         for (int i = st->base[c]; i < st->base[c + 1]; i++) {
             if (tag_weight(w, i) == 0.0) continue;
-            const double *u = dir + 3 * i;
-            const double sq = u[0] * u[0] + u[1] * u[1] + u[2] * u[2], inv = 1.0 / sq;
-            double d[3], Pd[3];
-            mat3_vec(bestR, world + 3 * i, d);
-            for (int k = 0; k < 3; k++) d[k] = (d[k] + bestT[k]) - st->o[c][k];
-            /* d^T M d = |M d|^2 (M is a projector): the square of a small vector, not the product of a small with a large one */
-            const double along = (u[0] * d[0] + u[1] * d[1] + u[2] * d[2]) * inv;
-            for (int k = 0; k < 3; k++) Pd[k] = d[k] - u[k] * along;
-            s += Pd[0] * Pd[0] + Pd[1] * Pd[1] + Pd[2] * Pd[2];
+            double ud, dd;
+            s += ckp_ray_residual(bestR, bestT, world + 3 * i, dir + 3 * i, st->o[c], &ud, &dd);
         }
         out->cam_rms[c] = sqrt((s > 0.0 ? s : 0.0) / (double)cnt);
         best_energy += s;
     }
     const double distance = sqrt(bestT[0] * bestT[0] + bestT[1] * bestT[1] + bestT[2] * bestT[2]);
-    {
-        const double n_points = (double)(total_tags * 4);
-        const double rms = sqrt((best_energy > 0.0 ? best_energy : 0.0) / n_points);
-        if (rms > MAX_TRUSTABLE_RMS) { out->std_devs[0] = out->std_devs[1] = out->std_devs[2] = DBL_MAX; }
-        else {
-            double mult = 1.0 + (distance / TAG_SIZE);
-            double xy = ((rms * mult) / sqrt((double)total_tags)) * XY_STD_DEV_SCALAR;
-            xy = xy < 0.01 ? 0.01 : (xy > 10.0 ? 10.0 : xy);
-            double th = (((rms / TAG_SIZE) * mult) / sqrt((double)total_tags)) * THETA_STD_DEV_SCALAR;
-            th = th < 0.05 ? 0.05 : (th > PI_D ? PI_D : th);
-            out->std_devs[0] = xy; out->std_devs[1] = xy; out->std_devs[2] = th;
-        }
-    }
+    ckp_std_devs(best_energy > 0.0 ? best_energy : 0.0, total_tags, distance, out->std_devs); /* a round-off negative energy counts as 0 */
     /* world <- robot: rot = polar(R)^T, pos = -rot t; then the yaw pivot about the mean tag centre */
     double robot_rot[9], robot_pos[3];
     for (int i = 0; i < 3; i++)
         for (int j = 0; j < 3; j++) robot_rot[i * 3 + j] = bestR[j * 3 + i];
     for (int k = 0; k < 3; k++) robot_pos[k] = -(robot_rot[k * 3] * bestT[0] + robot_rot[k * 3 + 1] * bestT[1] + robot_rot[k * 3 + 2] * bestT[2]);
     for (int k = 0; k < 3; k++) tc[k] /= (double)total_tags;
-    double vision_yaw = atan2(robot_rot[3], robot_rot[0]);
-    double delta_yaw = gyro - vision_yaw;
-    delta_yaw = fmod(delta_yaw + PI_D, 2.0 * PI_D);
-    if (delta_yaw < 0) delta_yaw += 2.0 * PI_D;
-    delta_yaw -= PI_D;
-    double delta_deg = fabs(delta_yaw) * (180.0 / PI_D);
-    double weight = delta_deg / MAX_GYRO_DELTA;
-    weight = weight < 0 ? 0 : (weight > 1 ? 1 : weight);
-    weight = weight * weight * (3.0 - 2.0 * weight);
-    double applied = delta_yaw * weight;
-    double cz = cos(applied), sz = sin(applied);
-    double rotz[9] = {cz, -sz, 0, sz, cz, 0, 0, 0, 1};
-    double rel[3] = {robot_pos[0] - tc[0], robot_pos[1] - tc[1], robot_pos[2] - tc[2]}, piv[3];
-    mat3_vec(rotz, rel, piv);
-    for (int k = 0; k < 3; k++) out->pos[k] = tc[k] + piv[k];
-    mat3_mul(rotz, robot_rot, out->rot);
-    double yaw = 0.0;
-    if (fabs(out->rot[6]) < 1.0) { double pitch = -asin(out->rot[6]); double tcs = cos(pitch); yaw = atan2(out->rot[3] / tcs, out->rot[0] / tcs); }
-    out->yaw = yaw;
+    ckp_yaw_pivot(robot_rot, robot_pos, tc, gyro, out->rot, out->pos, &out->yaw);
     out->energy = best_energy;
     out->n_tags = total_tags;
     out->valid = 1;
@@ -542,24 +402,12 @@ static void rig_tag_rho(const rig_step_t *st, const double R[9], const double t[
     for (int j = 0; j < st->N / 4; j++) {
         double s = 0;
         for (int i = 4 * j; i < 4 * j + 4; i++) {
-            const double *u = st->dir + 3 * i, *oc = st->o[st->cam_of[i]];
-            const double sq = u[0] * u[0] + u[1] * u[1] + u[2] * u[2], inv = 1.0 / sq;
-            double d[3], Pd[3];
-            mat3_vec(R, st->world + 3 * i, d);
-            for (int k = 0; k < 3; k++) d[k] = (d[k] + t[k]) - oc[k];
-            const double ud = u[0] * d[0] + u[1] * d[1] + u[2] * d[2], along = ud * inv;
-            for (int k = 0; k < 3; k++) Pd[k] = d[k] - u[k] * along;
-            const double pp = Pd[0] * Pd[0] + Pd[1] * Pd[1] + Pd[2] * Pd[2], dd = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
+            double ud, dd;
+            const double pp = ckp_ray_residual(R, t, st->world + 3 * i, st->dir + 3 * i, st->o[st->cam_of[i]], &ud, &dd);
             s += (ud > 0.0 && dd > 0.0) ? pp / dd : 1.0;
         }
         rho[j] = s * 0.25;
     }
-}
-static double gnc_weight(double rho, double mu, double c, double c2) {
-    const double lo = (mu / (mu + 1.0)) * c2, hi = ((mu + 1.0) / mu) * c2;
-    if (rho <= lo) return 1.0;
-    if (rho >= hi) return 0.0;
-    return (c / sqrt(rho)) * sqrt(mu * (mu + 1.0)) - mu;
 }
 
 #define ROBUST_TAGS (CK_RIG_MAX_CAMS * CK_RIG_ROBUST_MAX_TAGS)

@@ -16,12 +16,12 @@
 #ifndef CK_RIG_REFINE_MATH_H
 #define CK_RIG_REFINE_MATH_H
 
+#include "ck_pose_math.h"
 #include "ck_rig_refine_c.h"
 #include "ck_rigcal_math.h"
 
 #define CKF_LANES 64
 #define CKF_NSUM 27               /* free mode: the upper triangle of the 6 x 6 J^T J row by row (21), then J^T e (6); planar: 6 + 3 */
-#define CKF_CORNER (0.1651 / 2.0) /* half a tag's side, metres (the rig solver's CORNER_DISTANCE) */
 
 // What a walker needs of one instant
 typedef struct ckf_ctx {
@@ -58,19 +58,12 @@ CKC_FN int ckf_kept_tag(int nt, uint64_t rej, int r) {
     return 64 + r;
 }
 
-CKC_FN void ckf_quat_to_mat(const double *q, double *R) {
-    const double n = sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
-    const double w = q[0] / n, x = q[1] / n, y = q[2] / n, z = q[3] / n;
-    R[0] = 1.0 - 2.0 * (y * y + z * z); R[1] = 2.0 * (x * y - z * w);       R[2] = 2.0 * (x * z + y * w);
-    R[3] = 2.0 * (x * y + z * w);       R[4] = 1.0 - 2.0 * (x * x + z * z); R[5] = 2.0 * (y * z - x * w);
-    R[6] = 2.0 * (x * z - y * w);       R[7] = 2.0 * (y * z + x * w);       R[8] = 1.0 - 2.0 * (x * x + y * y);
-}
 // One point's record but for its camera number: corner 0..3 of the tag (t, q) seen along v by the camera mounted by robot_to_cam (bt, bq)
 CKC_FN void ckf_point_record(const double *t, const double *q, const int corner, const double *v, const double *bt, const double *bq, double *rec) {
     double R[9], A[9];
-    ckf_quat_to_mat(q, R);
-    ckf_quat_to_mat(bq, A);
-    const double y = (corner == 1 || corner == 2) ? CKF_CORNER : -CKF_CORNER, z = corner >= 2 ? CKF_CORNER : -CKF_CORNER;
+    quat_to_mat(q, R);
+    quat_to_mat(bq, A);
+    const double y = (corner == 1 || corner == 2) ? CORNER_DISTANCE : -CORNER_DISTANCE, z = corner >= 2 ? CORNER_DISTANCE : -CORNER_DISTANCE;
     CKC_UNROLL
     for (int k = 0; k < 3; k++) {
         rec[k] = (R[3 * k + 1] * y + R[3 * k + 2] * z) + t[k];

@@ -27,8 +27,7 @@ void ck_rigcal_plan(const ck_rigcal_params_t *p, int32_t n_cams, const int32_t *
                     const int32_t *step_index, const double *poses0, int32_t *index, ck_rigcal_plan_t *plan);
 /* robot_to_cam (A, b) <-> the solver's mount M[12] = (A row-major, o = -A^T b) */
 void ck_rigcal_mount_in(const ck_iso3_t *iso, double *M);
-/* (w, x, y, z), any length > 0 -> R row-major; R -> the unit quaternion with w >= 0, by the largest of the four squared components */
-void ck_rigcal_quat_to_mat(const double q[4], double R[9]);
+/* R row-major -> the unit quaternion (w, x, y, z) with w >= 0, by the largest of the four squared components */
 void ck_rigcal_mat_to_quat(const double R[9], double q[4]);
 /* the result record before the solve (everything but status, iters, the costs and the rms) and after it (robot_to_cam from the
  * solved mounts M[n_cams][12]; frozen parts are mounts0's) */

@@ -4,13 +4,11 @@
  * compiled into both; this file walks views and points the way the kernel's lane groups do, so that the two return the same bytes.
  * What the field calibration does the same way on the host is ck_cal_host.c's. */
 #include "ck_cal_c.h"
+#include "ck_pose_math.h"
 #include "ck_rigcal_c.h"
 #include "ck_rigcal_math.h"
 #include <stdlib.h>
 #include <string.h>
-
-#define TAG_SIZE 0.1651
-#define CORNER_DISTANCE (TAG_SIZE / 2.0)
 
 void ck_rigcal_params_default(ck_rigcal_params_t *p) {
     if (!p) return;
@@ -40,14 +38,6 @@ int ck_rigcal_check(const ck_rigcal_params_t *p, int32_t n_cams, const ck_sqpnp_
 }
 
 /* ---- what both solvers share ------------------------------------------------------------------------------------------------- */
-void ck_rigcal_quat_to_mat(const double q[4], double R[9]) {
-    double w = q[0], x = q[1], y = q[2], z = q[3];
-    const double n = sqrt(w * w + x * x + y * y + z * z);
-    w /= n; x /= n; y /= n; z /= n;
-    R[0] = 1 - 2 * (y * y + z * z); R[1] = 2 * (x * y - z * w);     R[2] = 2 * (x * z + y * w);
-    R[3] = 2 * (x * y + z * w);     R[4] = 1 - 2 * (x * x + z * z); R[5] = 2 * (y * z - x * w);
-    R[6] = 2 * (x * z - y * w);     R[7] = 2 * (y * z + x * w);     R[8] = 1 - 2 * (x * x + y * y);
-}
 /* (w, x, y, z) of a rotation matrix by the largest of the four squared components, w >= 0 */
 void ck_rigcal_mat_to_quat(const double R[9], double q[4]) {
     const double K[4] = {1 + R[0] + R[4] + R[8], 1 + R[0] - R[4] - R[8], 1 - R[0] + R[4] - R[8], 1 - R[0] - R[4] + R[8]};
@@ -64,20 +54,16 @@ void ck_rigcal_mat_to_quat(const double R[9], double q[4]) {
 }
 
 void ck_rigcal_mount_in(const ck_iso3_t *iso, double *M) {
-    ck_rigcal_quat_to_mat(iso->q, M);
-    for (int i = 0; i < 3; i++) M[9 + i] = -(M[i] * iso->t[0] + M[3 + i] * iso->t[1] + M[6 + i] * iso->t[2]);
+    quat_to_mat(iso->q, M);
+    ckp_camera_origin(M, iso->t, M + 9);
 }
 
 void ck_rigcal_table(int32_t n_cams, const ck_sqpnp_problem_t *records, int32_t n_steps, const ck_iso3_t *tags, int32_t n_tags_total,
                      int32_t *tab, double *world) {
-    static const double cp[4][3] = {{0, -CORNER_DISTANCE, -CORNER_DISTANCE}, {0, CORNER_DISTANCE, -CORNER_DISTANCE},
-                                    {0, CORNER_DISTANCE, CORNER_DISTANCE}, {0, -CORNER_DISTANCE, CORNER_DISTANCE}};
     for (int32_t t = 0; t < n_tags_total; t++) {
         double R[9];
-        ck_rigcal_quat_to_mat(tags[t].q, R);
-        for (int j = 0; j < 4; j++)
-            for (int k = 0; k < 3; k++)
-                world[((size_t)4 * t + j) * 3 + k] = (R[3 * k] * cp[j][0] + R[3 * k + 1] * cp[j][1] + R[3 * k + 2] * cp[j][2]) + tags[t].t[k];
+        quat_to_mat(tags[t].q, R);
+        for (int j = 0; j < 4; j++) ckp_tag_corner(R, tags[t].t, j, world + ((size_t)4 * t + j) * 3);
     }
     for (int64_t i = 0; i < (int64_t)n_cams * n_steps; i++) {
         tab[CKR_TAB * i] = 4 * records[i].tag_offset;

@@ -1,33 +1,13 @@
 // ck_sqpnp_dev.h — the device pieces the two SQPnP kernels share: k_sqpnp (k_sqpnp.hip, one camera) and k_rig (k_rigpnp.hip, all the
-// cameras of a robot).  Constants of the reference's solver, the start rotations, the 16-lane SQP refinement, the wave-local Jacobi.
+// cameras of a robot) and that only a wave can run: the 16-lane SQP refinement, the wave-local Jacobi.  The arithmetic a single lane
+// does, and the host twin with it, is ck_pose_math.h's.
 #ifndef CK_SQPNP_DEV_H
 #define CK_SQPNP_DEV_H
 
 #include <math.h>
 
 #include "ck_internal.h"
-#include "ck_mat3.h"
-
-constexpr double XY_STD_DEV_SCALAR = 5.0, THETA_STD_DEV_SCALAR = 2.0, MAX_TRUSTABLE_RMS = 0.1, MAX_GYRO_DELTA = 30.0;
-constexpr double TAG_SIZE = 0.1651, CORNER_DISTANCE = TAG_SIZE / 2.0, PI_D = 3.14159265358979323846;
-constexpr double DBLMAX = 1.7976931348623157e308;
-
-static __device__ void quat_to_mat(const double q[4], double R[9]) {
-    double w = q[0], x = q[1], y = q[2], z = q[3];
-    double n = sqrt(w * w + x * x + y * y + z * z);
-    w /= n; x /= n; y /= n; z /= n;
-    R[0] = 1 - 2 * (y * y + z * z); R[1] = 2 * (x * y - z * w);     R[2] = 2 * (x * z + y * w);
-    R[3] = 2 * (x * y + z * w);     R[4] = 1 - 2 * (x * x + z * z); R[5] = 2 * (y * z - x * w);
-    R[6] = 2 * (x * z - y * w);     R[7] = 2 * (y * z + x * w);     R[8] = 1 - 2 * (x * x + y * y);
-}
-static __device__ void nearest_so3(const double r_vec[9], double out[9]) { // column-major in and out (lib.rs:42-59)
-    double M[9], rot[9];
-    for (int c = 0; c < 3; c++)
-        for (int r = 0; r < 3; r++) M[r * 3 + c] = r_vec[c * 3 + r];
-    polar_rotation(M, rot);
-    for (int c = 0; c < 3; c++)
-        for (int r = 0; r < 3; r++) out[c * 3 + r] = rot[r * 3 + c];
-}
+#include "ck_pose_math.h"
 
 // One SQP refinement by a group of 16 lanes (lib.rs:98-115, 463-480): lane `gl` of the group owns one row of the
 // 15x15 KKT system [[Omega, J^T], [J, 0]] in registers (lane 15 idles); r and the solution are replicated in every lane.

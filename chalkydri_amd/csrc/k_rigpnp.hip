@@ -13,7 +13,6 @@
 #include <vector>
 
 #include "ck_internal.h"
-#include "ck_mat3.h"
 #include "ck_rig.h"
 #include "ck_sqpnp_dev.h"
 
@@ -86,13 +85,14 @@ static __device__ __forceinline__ void rig_setup(const RigArgs &a, RigLds &L, in
             if (nt > 0 && (cap == 0 || nt <= cap)) cnt = 4 * nt;
             L.sTagAt[c] = cap > 0 ? (long long)step * cap : (long long)p->tag_offset;
             L.sBearAt[c] = cap > 0 ? (long long)step * cap * 4 : (long long)p->bearing_offset;
-            double A[9];
+            double A[9], o[3];
             quat_to_mat(p->robot_to_cam.q, A);
             const double b[3] = {p->robot_to_cam.t[0], p->robot_to_cam.t[1], p->robot_to_cam.t[2]};
+            ckp_camera_origin(A, b, o);
             for (int k = 0; k < 9; k++) L.sCamA[c][k] = A[k];
             for (int k = 0; k < 3; k++) {
                 L.sCamB[c][k] = b[k];
-                L.sCamO[c][k] = -(A[k] * b[0] + A[3 + k] * b[1] + A[6 + k] * b[2]);
+                L.sCamO[c][k] = o[k];
             }
         }
         L.sCnt[c] = cnt;
@@ -108,21 +108,17 @@ static __device__ __forceinline__ void rig_setup(const RigArgs &a, RigLds &L, in
 
 // first pass: world point, ray direction in the robot frame, camera of every point
 static __device__ __forceinline__ void rig_first_pass(const RigArgs &a, RigLds &L, double *pts, int n, int lane) {
-    const double cp[4][3] = {{0, -CORNER_DISTANCE, -CORNER_DISTANCE}, {0, CORNER_DISTANCE, -CORNER_DISTANCE},
-                             {0, CORNER_DISTANCE, CORNER_DISTANCE}, {0, -CORNER_DISTANCE, CORNER_DISTANCE}};
     for (int i = lane; i < n; i += RIG_NT) {
         int c = 0;
         while (i >= L.sBase[c + 1]) c++;
         const int j = i - L.sBase[c], t = j >> 2, corner = j & 3;
         const ck_iso3_t *tag = a.cam[c].tags + L.sTagAt[c] + t;
         const double *v = a.cam[c].bearings + 3 * (L.sBearAt[c] + j);
-        double R[9], p[3];
+        double R[9];
         quat_to_mat(tag->q, R);
-        mat3_vec(R, cp[corner], p);
         double *o = pts + (size_t)i * CK_RIG_POINT_DOUBLES;
-        for (int k = 0; k < 3; k++) o[k] = p[k] + tag->t[k];
-        const double *A = L.sCamA[c];
-        for (int k = 0; k < 3; k++) o[3 + k] = A[k] * v[0] + A[3 + k] * v[1] + A[6 + k] * v[2];
+        ckp_tag_corner(R, tag->t, corner, o);
+        ckp_ray(L.sCamA[c], v, o + 3);
         o[6] = (double)c;
     }
 }
@@ -295,17 +291,7 @@ static __device__ __forceinline__ void rig_six_starts(const ck_rig_params_t &prm
 
 // R (row-major) of r (column-major) and the t that goes with it
 static __device__ __forceinline__ void rig_translation(const RigLds &L, const double *r, double Rm[9], double t[3]) {
-    for (int c = 0; c < 3; c++)
-        for (int rr = 0; rr < 3; rr++) Rm[rr * 3 + c] = r[c * 3 + rr];
-    double d[3], tl[3], Rc[3];
-    for (int j = 0; j < 3; j++) {
-        double s = 0;
-        for (int i = 0; i < 9; i++) s += L.sQrt[i * 3 + j] * r[i];
-        d[j] = L.sQt[j] - s;
-    }
-    mat3_vec(L.sQttInv, d, tl);
-    mat3_vec(Rm, L.sCentroid, Rc);
-    for (int k = 0; k < 3; k++) t[k] = tl[k] - Rc[k];
+    ckp_translation(L.sQrt, L.sQt, L.sQttInv, L.sCentroid, r, Rm, t);
 }
 
 // The whole first wave: the cheapest candidate with every point (of a weight other than 0) in front of its own camera.
@@ -313,7 +299,7 @@ template <bool RB>
 static __device__ __forceinline__ bool rig_pick(const RigLds &L, const double *pts, int n, const double *wt, bool weighted, int lane, double bestRm[9],
                                                 double bestT[3]) {
     bool found = false;
-    double best_score = DBLMAX;
+    double best_score = DBL_MAX;
     for (int oi = 0; oi < 6; oi++) {
         double Rm[9], t[3];
         rig_translation(L, L.sCandR[L.sOrder[oi]], Rm, t);
@@ -365,15 +351,9 @@ static __device__ __forceinline__ void rig_finish(const RigArgs &a, const RigLds
             double s = 0;
             for (int i = L.sBase[c]; i < L.sBase[c] + L.sCnt[c]; i++) {
                 if (RB && rig_weight<RB>(wt, weighted, i) == 0.0) continue;
-                const double *pk = pts + (size_t)i * CK_RIG_POINT_DOUBLES, *u = pk + 3;
-                const double sq = u[0] * u[0] + u[1] * u[1] + u[2] * u[2], inv = 1.0 / sq;
-                double d[3], Pd[3];
-                mat3_vec(bestR, pk, d);
-                for (int k = 0; k < 3; k++) d[k] = (d[k] + bestT[k]) - L.sCamO[c][k];
-                // d^T M d = |M d|^2 (M is a projector): the square of a small vector, not the product of a small with a large one
-                const double along = (u[0] * d[0] + u[1] * d[1] + u[2] * d[2]) * inv;
-                for (int k = 0; k < 3; k++) Pd[k] = d[k] - u[k] * along;
-                s += Pd[0] * Pd[0] + Pd[1] * Pd[1] + Pd[2] * Pd[2];
+                const double *pk = pts + (size_t)i * CK_RIG_POINT_DOUBLES;
+                double ud, dd;
+                s += ckp_ray_residual(bestR, bestT, pk, pk + 3, L.sCamO[c], &ud, &dd);
             }
             res->cam_rms[c] = sqrt((s > 0.0 ? s : 0.0) / (double)cnt);
             cam_sum = s;
@@ -385,19 +365,8 @@ static __device__ __forceinline__ void rig_finish(const RigArgs &a, const RigLds
     }
     if (lane != 0) return;
     double distance = sqrt(bestT[0] * bestT[0] + bestT[1] * bestT[1] + bestT[2] * bestT[2]);
-    {   // compute_std_devs over all the cameras' tags; a round-off negative energy counts as 0
-        double n_points = (double)(n_tags * 4);
-        double rms = sqrt((best_energy > 0.0 ? best_energy : 0.0) / n_points);
-        if (rms > MAX_TRUSTABLE_RMS) { res->std_devs[0] = res->std_devs[1] = res->std_devs[2] = DBLMAX; }
-        else {
-            double mult = 1.0 + (distance / TAG_SIZE);
-            double xy = ((rms * mult) / sqrt((double)n_tags)) * XY_STD_DEV_SCALAR;
-            xy = xy < 0.01 ? 0.01 : (xy > 10.0 ? 10.0 : xy);
-            double th = (((rms / TAG_SIZE) * mult) / sqrt((double)n_tags)) * THETA_STD_DEV_SCALAR;
-            th = th < 0.05 ? 0.05 : (th > PI_D ? PI_D : th);
-            res->std_devs[0] = xy; res->std_devs[1] = xy; res->std_devs[2] = th;
-        }
-    }
+    // over all the cameras' tags; a round-off negative energy counts as 0
+    ckp_std_devs(best_energy > 0.0 ? best_energy : 0.0, n_tags, distance, res->std_devs);
     // world <- robot: rot = polar(R)^T, pos = -rot t; then the yaw pivot about the mean tag centre of all the cameras
     double robot_rot[9], robot_pos[3];
     for (int i = 0; i < 3; i++)
@@ -412,25 +381,8 @@ static __device__ __forceinline__ void rig_finish(const RigArgs &a, const RigLds
         }
     }
     for (int k = 0; k < 3; k++) tc[k] /= (double)n_tags;
-    double vision_yaw = atan2(robot_rot[3], robot_rot[0]);
-    double delta_yaw = gyro - vision_yaw;
-    delta_yaw = fmod(delta_yaw + PI_D, 2.0 * PI_D);
-    if (delta_yaw < 0) delta_yaw += 2.0 * PI_D;
-    delta_yaw -= PI_D;
-    double delta_deg = fabs(delta_yaw) * (180.0 / PI_D);
-    double weight = delta_deg / MAX_GYRO_DELTA;
-    weight = weight < 0 ? 0 : (weight > 1 ? 1 : weight);
-    weight = weight * weight * (3.0 - 2.0 * weight);
-    double applied = delta_yaw * weight;
-    double cz = cos(applied), sz = sin(applied);
-    double rotz[9] = {cz, -sz, 0, sz, cz, 0, 0, 0, 1};
-    double rel[3] = {robot_pos[0] - tc[0], robot_pos[1] - tc[1], robot_pos[2] - tc[2]}, piv[3], R2[9];
-    mat3_vec(rotz, rel, piv);
-    mat3_mul(rotz, robot_rot, R2);
-    for (int k = 0; k < 3; k++) res->pos[k] = tc[k] + piv[k];
-    for (int k = 0; k < 9; k++) res->rot[k] = R2[k];
-    double yaw = 0.0;
-    if (fabs(R2[6]) < 1.0) { double pitch = -asin(R2[6]); double tcs = cos(pitch); yaw = atan2(R2[3] / tcs, R2[0] / tcs); }
+    double yaw;
+    ckp_yaw_pivot(robot_rot, robot_pos, tc, gyro, res->rot, res->pos, &yaw);
     res->yaw = yaw;
     res->energy = best_energy;
     res->n_tags = n_tags;
@@ -499,24 +451,13 @@ static __device__ __forceinline__ void rig_tag_rho(const RigLds &L, const double
     for (int j = first; j < n_tags; j += stride) {
         double s = 0;
         for (int i = 4 * j; i < 4 * j + 4; i++) {
-            const double *pk = pts + (size_t)i * CK_RIG_POINT_DOUBLES, *u = pk + 3, *o = L.sCamO[(int)pk[6]];
-            const double sq = u[0] * u[0] + u[1] * u[1] + u[2] * u[2], inv = 1.0 / sq;
-            double d[3], Pd[3];
-            mat3_vec(R, pk, d);
-            for (int k = 0; k < 3; k++) d[k] = (d[k] + t[k]) - o[k];
-            const double ud = u[0] * d[0] + u[1] * d[1] + u[2] * d[2], along = ud * inv;
-            for (int k = 0; k < 3; k++) Pd[k] = d[k] - u[k] * along;
-            const double pp = Pd[0] * Pd[0] + Pd[1] * Pd[1] + Pd[2] * Pd[2], dd = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
+            const double *pk = pts + (size_t)i * CK_RIG_POINT_DOUBLES;
+            double ud, dd;
+            const double pp = ckp_ray_residual(R, t, pk, pk + 3, L.sCamO[(int)pk[6]], &ud, &dd);
             s += (ud > 0.0 && dd > 0.0) ? pp / dd : 1.0;
         }
         rho[j] = s * 0.25;
     }
-}
-static __device__ __forceinline__ double gnc_weight(double rho, double mu, double c, double c2) {
-    const double lo = (mu / (mu + 1.0)) * c2, hi = ((mu + 1.0) / mu) * c2;
-    if (rho <= lo) return 1.0;
-    if (rho >= hi) return 0.0;
-    return (c / sqrt(rho)) * sqrt(mu * (mu + 1.0)) - mu;
 }
 
 __global__ __launch_bounds__(RIG_NT) void k_rig_robust(RigRobustArgs ra) {
@@ -653,7 +594,7 @@ __global__ __launch_bounds__(RIG_NT) void k_rig_robust(RigRobustArgs ra) {
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     if (lane != 0) return;
-    double worst = 0.0, best = DBLMAX;
+    double worst = 0.0, best = DBL_MAX;
     bool any = false;
     for (int j = 0; j < n_tags; j++) {
         if (B.wt[j] != 0.0) { if (B.rho[j] > worst) worst = B.rho[j]; }

@@ -51,14 +51,11 @@ __global__ __launch_bounds__(SQ_NT) void k_sqpnp(SolveArgs a) {
     const ck_iso3_t *tags = a.tags + pr.tag_offset;
     const double *p2 = a.bearings + (size_t)3 * pr.bearing_offset;
     double *world = a.world + (size_t)pi * a.max_points * 3;
-    const double cp[4][3] = {{0, -CORNER_DISTANCE, -CORNER_DISTANCE}, {0, CORNER_DISTANCE, -CORNER_DISTANCE},
-                             {0, CORNER_DISTANCE, CORNER_DISTANCE}, {0, -CORNER_DISTANCE, CORNER_DISTANCE}};
-    for (int i = lane; i < n; i += SQ_NT) { // corner_points_from_center (lib.rs:379-394)
+    for (int i = lane; i < n; i += SQ_NT) {
         int t = i >> 2, c = i & 3;
-        double R[9], p[3];
+        double R[9];
         quat_to_mat(tags[t].q, R);
-        mat3_vec(R, cp[c], p);
-        for (int k = 0; k < 3; k++) world[i * 3 + k] = p[k] + tags[t].t[k];
+        ckp_tag_corner(R, tags[t].t, c, world + i * 3);
     }
     __syncthreads();
     if (lane < 3) { // centroid: index order, like the fold in lib.rs:259-260
@@ -156,7 +153,7 @@ __global__ __launch_bounds__(SQ_NT) void k_sqpnp(SolveArgs a) {
         order[j + 1] = v;
     }
     bool found = false;
-    double best_score = DBLMAX, bestR[9], bestT[3], best_energy = 0;
+    double best_score = DBL_MAX, bestR[9], bestT[3], best_energy = 0;
     for (int oi = 0; oi < 6; oi++) {
         const double *r = sCandR[order[oi]];
         double Rm[9];
@@ -193,21 +190,8 @@ __global__ __launch_bounds__(SQ_NT) void k_sqpnp(SolveArgs a) {
         }
     }
     if (!found || lane != 0) return;
-    // compute_std_devs (lib.rs:224-246)
     double distance = sqrt(bestT[0] * bestT[0] + bestT[1] * bestT[1] + bestT[2] * bestT[2]);
-    {
-        double n_points = (double)(n_tags * 4);
-        double rms = sqrt(best_energy / n_points);
-        if (rms > MAX_TRUSTABLE_RMS) { res->std_devs[0] = res->std_devs[1] = res->std_devs[2] = DBLMAX; }
-        else {
-            double mult = 1.0 + (distance / TAG_SIZE);
-            double xy = ((rms * mult) / sqrt((double)n_tags)) * XY_STD_DEV_SCALAR;
-            xy = xy < 0.01 ? 0.01 : (xy > 10.0 ? 10.0 : xy);
-            double th = (((rms / TAG_SIZE) * mult) / sqrt((double)n_tags)) * THETA_STD_DEV_SCALAR;
-            th = th < 0.05 ? 0.05 : (th > PI_D ? PI_D : th);
-            res->std_devs[0] = xy; res->std_devs[1] = xy; res->std_devs[2] = th;
-        }
-    }
+    ckp_std_devs(best_energy, n_tags, distance, res->std_devs);
     // world_to_cam^-1 * robot_to_cam, then the yaw pivot about the tag centroid (lib.rs:328-376)
     double Rt[9];
     for (int i = 0; i < 3; i++)
@@ -220,25 +204,8 @@ __global__ __launch_bounds__(SQ_NT) void k_sqpnp(SolveArgs a) {
     for (int t = 0; t < n_tags; t++)
         for (int k = 0; k < 3; k++) tc[k] += tags[t].t[k];
     for (int k = 0; k < 3; k++) tc[k] /= (double)n_tags;
-    double vision_yaw = atan2(robot_rot[3], robot_rot[0]);
-    double delta_yaw = pr.gyro - vision_yaw;
-    delta_yaw = fmod(delta_yaw + PI_D, 2.0 * PI_D);
-    if (delta_yaw < 0) delta_yaw += 2.0 * PI_D;
-    delta_yaw -= PI_D;
-    double delta_deg = fabs(delta_yaw) * (180.0 / PI_D);
-    double weight = delta_deg / MAX_GYRO_DELTA;
-    weight = weight < 0 ? 0 : (weight > 1 ? 1 : weight);
-    weight = weight * weight * (3.0 - 2.0 * weight);
-    double applied = delta_yaw * weight;
-    double cz = cos(applied), sz = sin(applied);
-    double rotz[9] = {cz, -sz, 0, sz, cz, 0, 0, 0, 1};
-    double rel[3] = {robot_pos[0] - tc[0], robot_pos[1] - tc[1], robot_pos[2] - tc[2]}, piv[3], R2[9];
-    mat3_vec(rotz, rel, piv);
-    mat3_mul(rotz, robot_rot, R2);
-    for (int k = 0; k < 3; k++) res->pos[k] = tc[k] + piv[k];
-    for (int k = 0; k < 9; k++) res->rot[k] = R2[k];
-    double yaw = 0.0;
-    if (fabs(R2[6]) < 1.0) { double pitch = -asin(R2[6]); double tcs = cos(pitch); yaw = atan2(R2[3] / tcs, R2[0] / tcs); }
+    double yaw;
+    ckp_yaw_pivot(robot_rot, robot_pos, tc, pr.gyro, res->rot, res->pos, &yaw);
     res->yaw = yaw;
     res->energy = best_energy;
     res->valid = 1;

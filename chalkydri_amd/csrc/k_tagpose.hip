@@ -423,7 +423,7 @@ static_assert(sizeof(ck_tag_pose_t) == 296, "ck_tag_pose_t layout");
 extern "C" void ck_tag_pose_params_default(ck_tag_pose_params_t *pp) {
     if (!pp) return;
     memset(pp, 0, sizeof *pp);
-    for (int i = 0; i < CK_MAX_FAMILIES; i++) pp->tagsize[i] = 0.1651; // TAG_SIZE (chalkydri_sqpnp/src/lib.rs:38)
+    for (int i = 0; i < CK_MAX_FAMILIES; i++) pp->tagsize[i] = TAG_SIZE;
     pp->n_iters = 50;                                                   // estimate_tag_pose's orthogonal-iteration steps
 }
 

@@ -239,7 +239,7 @@ def _notes(obj):
 
 def test_tagpose_kernel_keeps_its_budget(built):
     """k_tagpose: no spill and no more scratch than k_sqpnp's 32 bytes (it has none); k_sqpnp keeps its own figure after the
-    3x3 helpers moved to ck_mat3.h."""
+    3x3 helpers moved to a header of their own (ck_pose_math.h)."""
     build = os.path.join(ROOT, "chalkydri_amd", "csrc", "build")
     tp = [v for k, v in _notes(os.path.join(build, "k_tagpose.o")).items() if "k_tagpose" in k]
     sq = [v for k, v in _notes(os.path.join(build, "k_sqpnp.o")).items() if "7k_sqpnp" in k]
