@@ -15,6 +15,7 @@
 //              (clusters outside [min_cluster_pixels, max_cluster_points], by their logical count, are dropped here).
 //   k_scatter  one wave per run: temp array -> points grouped by cluster.
 #include "ck_internal.h"
+#include "ck_emit_row.h"
 
 namespace {
 
@@ -290,6 +291,10 @@ __global__ __launch_bounds__(NT) void k_emit(EmitArgs a) {
 // pixel below often continues the same boundary: -0.05 ms) the clusters stage takes 3.35 ms against k_emit's 3.50 (same box).  What the
 // count pass spends its 1.2 ms on, by ablation: the key probe (64-bit read, compare-and-swap on an empty slot, the divergent loop
 // around them) 0.63 ms, the counting add 0.08, reads and arithmetic 0.45.
+// The count pass's per-pixel predicates were 794 lane-mask instructions on the scalar unit, the fuller issue port of the kernel (1 242
+// scalar against 1 389 vector instructions per wave); they are now bits of one vector register per pixel row that index a table of
+// the row's leaders (ck_emit_row.h), and the probe-and-add block runs once per leader: 580 scalar + 1 300 vector instructions per
+// wave, count pass 1.36 -> 0.85 ms, kernel 2.58 -> 2.25 ms.
 // Tried on the way and measured slower (1280 x 800 x 256, clusters stage, same box; k_emit: 3.51-3.56 ms):
 //  * the count and write passes as straight-line code over all 16 candidate slots of a thread (a slot without a point counts 0 into
 //    a per-lane dummy entry) and the tile's points ordered in LDS and copied out in one piece: fewer scalar instructions, but 32 slot
@@ -301,11 +306,18 @@ __global__ __launch_bounds__(NT) void k_emit(EmitArgs a) {
 constexpr uint32_t ID_WHITE = 0x40000000u, ID_VALUE = 0x3FFFFFFFu; // a staged pixel: frame pixel of its root (< 2^24) | colour
 static_assert(ID_WHITE == CK_PT_TWIN_SIGN, "a twin's sign is its white neighbour's colour bit, taken as it stands");
 constexpr int SR_PAD = ((LH * LW + NT - 1) / NT) * NT; // ids: every thread stores SPT of them unconditionally
+static_assert(SKIP == CK_ER_SKIP && ID_WHITE == CK_ER_WHITE, "ck_emit_row.h speaks of the staged words of this kernel");
+// the row table (ck_emit_row.h), generated at compile time; every workgroup copies its 4 KB into LDS (one 16-byte load per thread,
+// after the staging loads: issued before them it holds four registers across the kernel's register peak): with it a workgroup holds
+// 19 508 of the 20 480 bytes that eight of them leave each other
+__device__ const ck_emit_row_table g_emit_rows = ck_make_emit_row_table();
+static_assert(CK_ER_ROWS == 4 * NT, "one uint4 of the row table per thread");
 
-__global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80))) void k_emit2(EmitArgs a, int xcd_map, int n_frames) {
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80), amdgpu_waves_per_eu(8))) void k_emit2(EmitArgs a, int xcd_map, int n_frames) {
     __shared__ __attribute__((aligned(16))) uint32_t sRaw[SR_PAD + LHT * 2 + LHT];
     __shared__ uint32_t sSlot[LHT], sTBase[LHT];
     __shared__ uint32_t sWave[NT / 64 + 1], sRunW[NT / 64 + 1];
+    __shared__ __attribute__((aligned(16))) uint32_t sRow[CK_ER_ROWS];
     uint32_t *sR = sRaw;                                                             // [LH][LW] ids
     unsigned long long *sKey = reinterpret_cast<unsigned long long *>(sRaw + SR_PAD); // [LHT]
     uint32_t *sCnt = sRaw + SR_PAD + LHT * 2;                                         // [LHT]
@@ -364,13 +376,13 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80))) void k_emi
             sR[tid + q * NT] = none ? SKIP : (root | (tv[q] == 255u ? ID_WHITE : 0u));
         }
     }
+    reinterpret_cast<uint4 *>(sRow)[tid] = reinterpret_cast<const uint4 *>(g_emit_rows.e)[tid];
     lds_barrier();
     if (a.stop_after == 0) return;
 
     const int lx = (tid & 63) + 1; // staged column of this thread's pixels
     const int gx = x0 + (tid & 63);
     const int row0 = (tid >> 6) * 4;
-    const bool colok = gx >= 1 && gx <= w - 2;
 
     // pass 1: count points per key in the LDS table; the add's return value is the point's rank inside (tile, key), kept in
     // registers (sign << 31 | slot << 16 | rank) so that the write pass neither probes nor counts again.  The thread's 5 x 3 ids
@@ -382,78 +394,78 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80))) void k_emi
         uint32_t R[5][3];
         unsigned long long last_key = 0ull; // the thread's last key and where it is: the pixel below often continues the same boundary
         uint32_t last_s = 0;
-#pragma unroll
-        for (int r = 0; r < 5; r++)
+        // (a staged row is read one pixel row ahead of its first use, not all five at the start: nine words live instead of fifteen)
+        auto stage_row = [&](int r) {
 #pragma unroll
             for (int c = 0; c < 3; c++) R[r][c] = sR[(row0 + r) * LW + lx - 1 + c];
+        };
+        stage_row(0); stage_row(1);
+        // The predicates of a pixel row (ck_emit_row.h) are bits of one vector register, never lane masks: the Boolean algebra the
+        // compiler makes of `bool`s runs on the scalar unit, which was this kernel's fuller issue port.  The equalities inside a
+        // staged row are formed once and serve the pixel row above (its partners') and the row itself (absorb / drop).
+        uint32_t H[5];
+        H[0] = ck_er_hword(R[0][0], R[0][1], R[0][2]);
+        // (all ones where a sign bit says "outside": columns 1..w-2 emit, x-1 >= 1 may drop, x+1 <= w-2 may absorb)
+        const uint32_t colskip = (uint32_t)(((gx - 1) | (w - 2 - gx)) >> 31);
+        const uint32_t can = (a.twins ? 3u : 0u) & ~(((uint32_t)((gx - 2) >> 31) & CK_ER_CAN_DROP) | ((uint32_t)((w - 3 - gx) >> 31) & CK_ER_CAN_ABSORB));
+        // one leader's probe and add: its place in the table << 16 | the rank of its first point, or NONE (no room in the table)
+        auto count = [&](uint32_t r0, uint32_t r1, uint32_t mult) -> uint32_t {
+            const uint32_t ra = r0 & ID_VALUE, rb = r1 & ID_VALUE; // (the roots without their colour bits: the cluster's key)
+            const unsigned long long key = ra < rb ? ((unsigned long long)ra << 32) | rb : ((unsigned long long)rb << 32) | ra;
+            uint32_t s = key_hash(key) & (LHT - 1);
+            bool placed = false;
+            if (key == last_key) { placed = true; s = last_s; } // (the probe is the expensive part of this pass: 0.6 of its 1.2 ms)
+            else
+            for (int probe = 0; probe < LHT; probe++) {
+                // most points meet their key already in place: a plain read (lanes with one address are served together)
+                // finds that out, and only a slot seen empty costs a compare-and-swap (same-address lanes one by one)
+                __asm__ volatile("" ::: "memory");
+                unsigned long long prev = sKey[s];
+                if (prev == 0ull) prev = atomicCAS(&sKey[s], 0ull, key);
+                if (prev == 0ull || prev == key) { placed = true; break; }
+                s = (s + 1) & (LHT - 1);
+            }
+            if (!placed) { atomicOr(&counters[CK_CNT_STATUS], (uint32_t)CK_FRAME_CLUSTERS_OVERFLOW); return NONE; }
+            last_key = key; last_s = s;
+            // (one add carries both counts of the key: physical in the high half — what it was before is the point's rank —, logical
+            // in the low half, which never carries: a tile has at most 5 120 points, twins counted twice)
+            return (s << 16) | (atomicAdd(&sCnt[s], mult) >> 16);
+        };
 #pragma unroll
         for (int rr = 0; rr < 4; rr++) {
             const int gy = y0 + row0 + rr;
-            const uint32_t r0 = (colok && gy >= 1 && gy <= h - 2) ? R[rr][1] : SKIP;
+            if (rr < 3) stage_row(rr + 2);
+            H[rr + 1] = ck_er_hword(R[rr + 1][0], R[rr + 1][1], R[rr + 1][2]);
+            const uint32_t r0 = R[rr][1] | colskip | (uint32_t)(((gy - 1) | (h - 2 - gy)) >> 31); // SKIP where the pixel emits nothing
             const uint32_t r1v[4] = {R[rr][2], R[rr + 1][1], R[rr + 1][0], R[rr + 1][2]}; // (1,0) (0,1) (-1,1) (1,1)
-            bool ok[4];
+            uint32_t absorb;
+            const uint32_t idx = ck_er_index(H[rr], H[rr + 1], r0, R[rr][0], R[rr][1], R[rr][2], R[rr + 1][0], R[rr + 1][1], R[rr + 1][2], can, &absorb);
+            const uint32_t e = sRow[idx];
+            // Only the first point of a key probes and adds (LDS traffic is what this pass is bound by): the row's LEADERS, which the
+            // entry lists with the number of points each stands for.  One block for all of them, in a loop: a wave goes round as
+            // often as its lane with the most leaders has them, and a thread has about 3.5 keys in its four rows.  A leader's result
+            // goes to the points that named it (c4); an absorbed twin is one more logical point of the (1,1) point's leader.
+            const uint32_t lj[4] = {0u, (e >> 20) & 1u, (e >> 21) & 3u, (e >> 23) & 3u}; // the place of a point's leader in the list
+            uint32_t c4[4] = {NONE, NONE, NONE, NONE};
+            uint32_t le = e & CK_ER_LEADERS; // (a row of four leaders ends with the list)
+            for (uint32_t j = 0; (le & 0x1Cu) != 0u; j++, le >>= 5) {
+                const uint32_t sl = le & 3u;
+                const uint32_t r1 = sl == 0u ? r1v[0] : (sl == 1u ? r1v[1] : (sl == 2u ? r1v[2] : r1v[3]));
+                // (physical << 16 | logical: a twin is one word and two points)
+                const uint32_t c = count(r0, r1, ((le >> 2) & 7u) * 0x10001u + (lj[3] == j ? absorb : 0u));
 #pragma unroll
-            for (int k = 0; k < 4; k++) ok[k] = r0 != SKIP && r1v[k] != SKIP && ((r0 ^ r1v[k]) & ID_WHITE) != 0u;
-            // Twins.  When both diagonals of the 2 x 2 block at (x, y) join the same two components, the point (2x+1, 2y+1) is emitted
-            // twice into one cluster: by (1,1) from (x, y) and by (-1,1) from (x+1, y).  The first ABSORBS the second (its word then
-            // stands for both), the owner of the second DROPS it.  Absorb, at (x, y): the own k = 3 pair is a point; the twin's
-            // owner (x+1, y) lies in the emitting columns (x+1 <= w-2; its row is this one); the twin's pair (x+1, y) / (x, y+1)
-            // holds the same two staged words — which makes it a point as well: equal words are equal colours and neither is SKIP.
-            // Drop, at (x, y): the mirror image — the own k = 2 pair is a point, (x-1, y) lies in the emitting columns (x-1 >= 1),
-            // and its k = 3 pair (x-1, y) / (x, y+1) holds the same two words.  Both threads evaluate the same four staged words by
-            // the same rule, also across an emit-tile boundary (the staged region carries a column either side and a row below,
-            // and a staged word is a function of the frame alone), so one absorbs exactly when the other drops.  At the frame's
-            // edges one copy does not exist (owner in column 0 or w-1; rows 0 and h-1 emit nothing for either) and nothing merges.
-            const bool absorb = a.twins && ok[3] && gx + 1 <= w - 2 &&
-                                ((r0 == r1v[0] && r1v[3] == r1v[1]) || (r0 == r1v[1] && r1v[3] == r1v[0]));
-            const bool drop = a.twins && ok[2] && gx - 1 >= 1 &&
-                              ((r0 == R[rr][0] && r1v[2] == r1v[1]) || (r0 == r1v[1] && r1v[2] == R[rr][0]));
-            ok[2] = ok[2] && !drop;
-            // a point's leader (first point of its key), its place among the key's points, what the leader adds to the key's entry: both
-            // counts of the points it stands for, physical << 16 | logical (a twin: one word, two points)
-            uint32_t lead[4], nth[4], mult[4];
-            const uint32_t unit = 0x10001u, unit3 = absorb ? 0x10002u : unit;
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                lead[k] = (uint32_t)k; nth[k] = 0; mult[k] = k == 3 ? unit3 : unit;
-#pragma unroll
-                for (int j = k - 1; j >= 0; j--) { const bool eq = ok[j] && r1v[j] == r1v[k]; lead[k] = eq ? (uint32_t)j : lead[k]; nth[k] += eq ? 1u : 0u; }
-#pragma unroll
-                for (int j = k + 1; j < 4; j++) mult[k] += (ok[j] && r1v[j] == r1v[k]) ? (j == 3 ? unit3 : unit) : 0u;
-            }
-            uint32_t cl[4] = {NONE, NONE, NONE, NONE};
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                if (!(ok[k] && lead[k] == (uint32_t)k)) continue; // only the first point of a key probes and adds (LDS traffic is what this pass is bound by)
-                const uint32_t ra = r0 & ID_VALUE, rb = r1v[k] & ID_VALUE; // (the roots without their colour bits: the cluster's key)
-                const unsigned long long key = ra < rb ? ((unsigned long long)ra << 32) | rb : ((unsigned long long)rb << 32) | ra;
-                uint32_t s = key_hash(key) & (LHT - 1);
-                bool placed = false;
-                if (key == last_key) { placed = true; s = last_s; } // (the probe is the expensive part of this pass: 0.6 of its 1.2 ms)
-                else
-                for (int probe = 0; probe < LHT; probe++) {
-                    // most points meet their key already in place: a plain read (lanes with one address are served together)
-                    // finds that out, and only a slot seen empty costs a compare-and-swap (same-address lanes one by one)
-                    __asm__ volatile("" ::: "memory");
-                    unsigned long long prev = sKey[s];
-                    if (prev == 0ull) prev = atomicCAS(&sKey[s], 0ull, key);
-                    if (prev == 0ull || prev == key) { placed = true; break; }
-                    s = (s + 1) & (LHT - 1);
-                }
-                if (placed) { last_key = key; last_s = s; }
-                // (one add carries both counts of the key: physical in the high half — what it was before is the point's rank —, logical
-                // in the low half, which never carries: a tile has at most 5 120 points, twins counted twice)
-                if (placed) cl[k] = (s << 16) | (atomicAdd(&sCnt[s], mult[k]) >> 16);
-                else atomicOr(&counters[CK_CNT_STATUS], (uint32_t)CK_FRAME_CLUSTERS_OVERFLOW);
+                for (int k = 0; k < 4; k++) c4[k] = lj[k] == j ? c : c4[k];
             }
 #pragma unroll
             for (int k = 0; k < 4; k++) {
-                const uint32_t lk = lead[k];
-                const uint32_t c = lk == 0u ? cl[0] : (lk == 1u ? cl[1] : (lk == 2u ? cl[2] : cl[3]));
-                const uint32_t sign = (r1v[k] & ID_WHITE) ? 0x80000000u : 0u; // gradient sign: the neighbour is the white one
+                const uint32_t nth = k == 0 ? 0u : (k == 1 ? (e >> 25) & 1u : (k == 2 ? (e >> 26) & 3u : (e >> 28) & 3u));
+                uint32_t c = c4[k];
+                c = ((idx >> (9 - k)) & 1u) ? c : NONE; // (not a point, or dropped)
+                const uint32_t sign = (r1v[k] & ID_WHITE) << 1; // gradient sign (bit 31): the neighbour is the white one
                 // (the twin's sign: its neighbour (x, y+1) is the white one — ID_WHITE is CK_PT_TWIN_SIGN's bit)
-                const uint32_t twin = (k == 3 && absorb) ? (CK_PT_TWIN | (r1v[1] & ID_WHITE)) : 0u;
-                cand[rr * 4 + k] = (ok[k] && c != NONE) ? ((c + nth[k]) | sign | twin) : NONE;
+                const uint32_t twin = k == 3 ? (0u - absorb) & (CK_PT_TWIN | (r1v[1] & ID_WHITE)) : 0u;
+                cand[rr * 4 + k] = c != NONE ? ((c + nth) | sign | twin) : NONE;
+                asm volatile("" : "+v"(cand[rr * 4 + k])); // (formed here: left to the compiler it sinks into pass 3, its five inputs kept alive instead)
             }
         }
     }
