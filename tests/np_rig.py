@@ -1,5 +1,6 @@
 """Numpy restatement of the camera-rig solver, written from the formulas and not from the C: numpy.linalg for the
-SVD, the eigen-decomposition and the KKT solve.  Used only to pin ck_rig_host.c; the device solver is pinned to that twin.
+SVD, the eigen-decomposition and the KKT solve.  It pins ck_rig_host.c, to which the device solver is pinned, and on the cases of
+tests/rig_cases.py the device solver itself (tests/test_gpu_rig_cases.py): twin and kernels share their leaf arithmetic.
 
 Frames: the unknown is world -> robot (R, t), p_robot = R X + t; camera c is mounted by robot_to_cam = (A_c, b_c), p_cam = A_c p_robot
 + b_c.  A bearing v of camera c is the ray u = A_c^T v through o_c = -A_c^T b_c; M = I - u u^T / u^T u;
@@ -115,6 +116,7 @@ class System:
         Xc = self.X - self.centroid
         w, V = np.linalg.eigh(Xc.T @ Xc)
         self.omega_starts = self.omega.copy()
+        self.scatter_w = w                                  # (read-out only)
         self.coplanar = bool(w[0] <= 1e-12 * w[2])
         if self.coplanar:
             for k in range(3):
@@ -170,15 +172,24 @@ def penalised(sys, r, gyro, sign_change_error):
     return sys.energy(r) + sign_change_error * max(0.0, 1.0 - (r[0] * np.cos(gyro) + r[3] * np.sin(gyro)))
 
 
-def pick(sys, cands, gyro, sign_change_error):
+def pick(sys, cands, gyro, sign_change_error, trace=None):
     """the first candidate, by penalised energy, with every point in front of its own camera"""
-    for r in sorted(cands, key=lambda r: penalised(sys, r, gyro, sign_change_error)):
+    ordered = sorted(cands, key=lambda r: penalised(sys, r, gyro, sign_change_error))
+    if trace is not None:                                   # read-out: every candidate in penalised order with its verdict, the winner
+        trace["candidates"] = [{"penalised": float(penalised(sys, r, gyro, sign_change_error)), "energy": float(sys.energy(r)),
+                                "in_front": bool(sys.in_front(r))} for r in ordered]
+        trace["winner"] = next((k for k, c in enumerate(trace["candidates"]) if c["in_front"]), None)
+    for r in ordered:
         if sys.in_front(r):
             return r
     return None
 
 
-def finish(sys, r, gyro):
+def _branch(raw, lo, hi):
+    return "lo" if raw < lo else ("hi" if raw > hi else "mid")
+
+
+def finish(sys, r, gyro, trace=None):
     """the result record of the chosen r"""
     R, t = r.reshape(3, 3).T, sys.translation(r)
     res = sys.residuals(r)
@@ -202,16 +213,27 @@ def finish(sys, r, gyro):
     rot, pos = Rz @ rot0, tc + Rz @ (pos0 - tc)
     yaw = np.arctan2(rot[1, 0], rot[0, 0]) if abs(rot[2, 0]) < 1 else 0.0
     cam_rms = [np.sqrt(max(res[sys.cam_of == c].sum(), 0.0) / (4 * k)) if k else 0.0 for c, k in enumerate(sys.cam_tags)]
+    if trace is not None:                                   # read-out: the yaw pivot, the branches of the standard deviations, the polar step
+        mult = 1 + np.linalg.norm(t) / TAG_SIZE
+        U, _, Vt = np.linalg.svd(R)
+        trace.update(yaw_delta=float(d), yaw_weight=float(w), vision_yaw=float(np.arctan2(rot0[1, 0], rot0[0, 0])), rms=float(rms),
+                     std_branch=("untrusted",) if rms > 0.1 else (_branch(rms * mult / np.sqrt(n_tags) * 5.0, 0.01, 10.0),
+                                                                  _branch(rms / TAG_SIZE * mult / np.sqrt(n_tags) * 2.0, 0.05, np.pi)),
+                     polar_flip=bool(np.linalg.det(U @ Vt) < 0))
     return {"rot": rot, "pos": pos, "std": std, "yaw": yaw, "energy": E, "n_tags": n_tags, "cam_tags": list(sys.cam_tags),
             "cam_rms": cam_rms, "r": r, "t": t}
 
 
-def solve_rig(cams, gyro, sign_change_error=600.0, max_iter=15, tol_sq=1e-16):
+def solve_rig(cams, gyro, sign_change_error=600.0, max_iter=15, tol_sq=1e-16, trace=None):
     """The solver: SQPnP's six starts (the three smallest eigenvectors of Omega, both signs, through the nearest rotation; for
-    coplanar points the three smallest outside Omega's exact null space)."""
+    coplanar points the three smallest outside Omega's exact null space).  `trace`: a dict that receives the read-out (the coplanar
+    flag and the scatter's eigenvalue ratio, the candidates in penalised order with their in-front verdicts, the winner's index, the
+    yaw delta and its smoothstep weight, rms and the branches of the standard deviations); it adds output only."""
     sys = System(cams)
     if sys.n < 3:
         return None
+    if trace is not None:
+        trace.update(coplanar=sys.coplanar, planar_ratio=float(sys.scatter_w[0] / sys.scatter_w[2]) if sys.scatter_w[2] > 0 else 0.0)
     w, V = np.linalg.eigh(sys.omega_starts)
     order = np.argsort(w, kind="stable")
     cands = []
@@ -219,8 +241,8 @@ def solve_rig(cams, gyro, sign_change_error=600.0, max_iter=15, tol_sq=1e-16):
         for sign in (-1.0, 1.0):
             start = nearest_rotation((V[:, i] * sign).reshape(3, 3).T).T.reshape(9)
             cands.append(sqp(sys, start, max_iter, tol_sq))
-    r = pick(sys, cands, gyro, sign_change_error)
-    return None if r is None else finish(sys, r, gyro)
+    r = pick(sys, cands, gyro, sign_change_error, trace)
+    return None if r is None else finish(sys, r, gyro, trace)
 
 
 def many_start_reference(cams, gyro, truth_R, rng, n_starts=60, iters=100, sign_change_error=600.0, tol_sq=1e-16):

@@ -72,9 +72,11 @@ def delete_tags(cams, keep):
 
 
 def solve_robust(cams, gyro, gate=GATE, mu_factor=MU_FACTOR, max_rounds=MAX_ROUNDS, min_inlier_tags=1, sign_change_error=600.0,
-                 max_iter=15, tol_sq=1e-16):
+                 max_iter=15, tol_sq=1e-16, trace=None):
     """None for a step without tags, else {"status", "rounds", "keep" (per tag, camera-major), "rejected" (a mask per camera),
-    "fused" (np_rig.solve_rig's record of the inliers, or None), "worst", "best"}"""
+    "fused" (np_rig.solve_rig's record of the inliers, or None), "worst", "best"}.  `trace`: a dict that receives the read-out (whether
+    the first pass found a candidate in front of the cameras, rho_max / gate^2, the rounds, the final weights and whether any was left
+    above 0, and np_rig.solve_rig's read-out of the final solve under "fused"); it adds output only."""
     sys = N.System(cams)
     if sys.n < 3:
         return None
@@ -86,10 +88,14 @@ def solve_robust(cams, gyro, gate=GATE, mu_factor=MU_FACTOR, max_rounds=MAX_ROUN
         for sign in (-1.0, 1.0):
             cands.append(N.sqp(sys, N.nearest_rotation((V[:, i] * sign).reshape(3, 3).T).T.reshape(9), max_iter, tol_sq))
     r = N.pick(sys, cands, gyro, sign_change_error)
+    if trace is not None:
+        trace["found"] = r is not None
     if r is None:
         r = sorted(cands, key=lambda q: N.penalised(sys, q, gyro, sign_change_error))[0]
     rho = tag_rho(sys, r.reshape(3, 3).T, sys.translation(r))
     keep, rounds, status = np.ones(nt, bool), 0, CLEAN
+    if trace is not None:
+        trace.update(gate_ratio=float(rho.max() / (gate * gate)), weights=np.ones(nt), alive=True)
     if not rho.max() <= gate * gate:
         mu = gate * gate / (2 * rho.max() - gate * gate)
         w, maxed = np.ones(nt), False
@@ -107,6 +113,8 @@ def solve_robust(cams, gyro, gate=GATE, mu_factor=MU_FACTOR, max_rounds=MAX_ROUN
             rho = tag_rho(sys, r.reshape(3, 3).T, ws.translation(r))
             mu *= mu_factor
             rounds += 1
+        if trace is not None:
+            trace.update(weights=w.copy(), alive=bool((w > 0).any()))
         keep = (w >= 0.5) if maxed else (w == 1.0)
         status = MAXROUNDS if maxed else (REJECTED if not keep.all() else CLEAN)
     rejected, j = [], 0
@@ -114,10 +122,14 @@ def solve_robust(cams, gyro, gate=GATE, mu_factor=MU_FACTOR, max_rounds=MAX_ROUN
         rejected.append(sum(1 << t for t in range(len(tags)) if not keep[j + t]))
         j += len(tags)
     out = {"status": status, "rounds": rounds, "keep": keep, "rejected": rejected, "fused": None, "worst": 0.0, "best": 0.0}
+    if trace is not None:
+        trace["rounds"] = rounds
     if keep.sum() < min_inlier_tags:
         out["status"] = NO_CONSENSUS
         return out
-    fused = N.solve_rig(delete_tags(cams, keep), gyro, sign_change_error, max_iter, tol_sq)
+    if trace is not None:
+        trace["fused"] = {}
+    fused = N.solve_rig(delete_tags(cams, keep), gyro, sign_change_error, max_iter, tol_sq, None if trace is None else trace["fused"])
     out["fused"] = fused
     if fused is not None:
         rho = tag_rho(sys, N.nearest_rotation(fused["r"].reshape(3, 3).T), fused["t"])

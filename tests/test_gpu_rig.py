@@ -1,5 +1,7 @@
 """The camera rig on the device (k_rig, chalkydri_amd/csrc/k_rigpnp.hip): ck_rig_solve_batch against its host twin and
-against k_sqpnp for one camera, ck_rig_process_last end to end on two rendered cameras, misuse, determinism."""
+against k_sqpnp for one camera, ck_rig_process_last end to end on two rendered cameras, misuse, determinism.
+The kernel's own edges (more than 64 and 128 points, empty cameras in every position, coplanar and singular scenes, candidates behind
+a camera, the gyro far off and across +-pi, every branch of std_devs) are pinned by tests/test_gpu_rig_cases.py, against this twin and against tests/np_rig.py."""
 import ctypes as C
 import os
 import sys
