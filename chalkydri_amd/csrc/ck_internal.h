@@ -421,6 +421,11 @@ __device__ __forceinline__ uint32_t wave_scan_u32(uint32_t x) {
     x += dpp0<0x142, 0xA>(x); x += dpp0<0x143, 0xC>(x);
     return x;
 }
+// the same inside every row of 16 lanes on its own (the first four steps): sixteen values and fewer, one per lane of a row
+__device__ __forceinline__ uint32_t row_scan_u32(uint32_t x) {
+    x += dpp0<0x111, 0xF>(x); x += dpp0<0x112, 0xF>(x); x += dpp0<0x114, 0xF>(x); x += dpp0<0x118, 0xF>(x);
+    return x;
+}
 __device__ __forceinline__ unsigned long long wave_scan_u64(unsigned long long x) {
     x += dpp0_64<0x111, 0xF>(x); x += dpp0_64<0x112, 0xF>(x); x += dpp0_64<0x114, 0xF>(x); x += dpp0_64<0x118, 0xF>(x);
     x += dpp0_64<0x142, 0xA>(x); x += dpp0_64<0x143, 0xC>(x);

@@ -314,7 +314,8 @@ __device__ const ComboTable g_combo_table{}; // built at compile time: nothing t
 // Reciprocals of the window weights of k_chunk: a window holds at most 2 * 20 + 1 points of weight <= 362, so its weight sum is an
 // integer below INV_N and 1.0 / W a table entry — the IEEE quotient, formed by the compiler: the same bits as the device's division
 // (a dozen instructions around v_rcp_f64, 70 clocks of a SIMD per position by tools/probes/valu_rate_probe.hip) for one 8-byte load
-// from a 116 KB table that lives in L2.  A position nobody wrote can hold any weight: beyond the table it divides.
+// from a 116 KB table that lives in L2.  A position nobody wrote has a weight like any other (k_chunk gathers it from the weight image
+// at whatever coordinates the position holds, or takes 1), so no window leaves the table; k_chunk clamps the index all the same.
 constexpr int INV_N = 41 * 362 + 1;
 struct InvTable {
     double v[INV_N];
@@ -1613,17 +1614,20 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(WPS, 8))) v
 // the doubles are formed by the operations of k_fit's chunk loop in the same order: the same bits.
 constexpr int KL = 1024, KOFF = 32;
 static_assert(CK_SPAN == 960 && KOFF >= CK_EXT_PRE + 3 && KL - KOFF - CK_SPAN >= CK_EXT_POST + 4, "span geometry");
-__device__ __forceinline__ void k_chunk_body(const ck_stage_ws &ws, int qw, int qh) {
+// (diagnostics, CK_CHUNK_STOP_AFTER: every span ends after step k, the next span's points and weights in hand as ever; the product
+// kernel passes the constant 99 and holds none of it)
+__device__ __forceinline__ void k_chunk_body(const ck_stage_ws &ws, int qw, int qh, const int stop_after) {
     __shared__ __attribute__((aligned(16))) unsigned long long sP64[3][KL]; // inclusive sums from the first loaded position: Mxx, Mxy, Myy
     __shared__ __attribute__((aligned(16))) uint32_t sP32[3][KL];           // Mx, My, W (a window's sums stay below 2^32: differences are exact)
     __shared__ uint8_t sKsz[KL];
-    __shared__ unsigned long long sScan64[3][4];
-    __shared__ uint32_t sScan32[3][4];
+    __shared__ __attribute__((aligned(16))) unsigned long long sScan64[3][4];
+    __shared__ __attribute__((aligned(16))) uint32_t sScan32[3][4];
     __shared__ uint32_t sCnt[16];
     // the errors and their smoothed values take the place of two of the sums once every window has been formed (the four errors of a
     // thread wait in registers for the barrier in between): 38 KB instead of 46, four workgroups per CU instead of three
     double *sS = reinterpret_cast<double *>(&sP64[0][0]), *sErr = reinterpret_cast<double *>(&sP64[1][0]);
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int wvs = __builtin_amdgcn_readfirstlane(wv); // the wave's number where it decides what a whole wave does: a scalar, so no loop over lanes
     const int frame = blockIdx.y;
     const uint32_t *counters = ws.d_counters + (size_t)frame * CK_CNT_STRIDE;
     const uint32_t ext_total = min(counters[CK_CNT_EXT], (uint32_t)ws.ext_cap); // positions k_seq handed out
@@ -1680,9 +1684,13 @@ __device__ __forceinline__ void k_chunk_body(const ck_stage_ws &ws, int qw, int 
         lds_barrier();
 #pragma unroll
         for (int q = 0; q < 3; q++) {
-            unsigned long long b64 = 0;
-            uint32_t b32 = 0;
-            for (int k = 0; k < wv; k++) { b64 += sScan64[q][k]; b32 += sScan32[q][k]; }
+            // the waves before this one: all totals in three wide reads, summed under the wave's own number (a scalar: no loop over
+            // lanes that agree anyway, no read that waits for the one before)
+            const ulonglong2 t01 = *reinterpret_cast<const ulonglong2 *>(&sScan64[q][0]);
+            const unsigned long long t2 = sScan64[q][2];
+            const uint4 u = *reinterpret_cast<const uint4 *>(&sScan32[q][0]);
+            const unsigned long long b64 = (wvs > 0 ? t01.x : 0ull) + (wvs > 1 ? t01.y : 0ull) + (wvs > 2 ? t2 : 0ull);
+            const uint32_t b32 = (wvs > 0 ? u.x : 0u) + (wvs > 1 ? u.y : 0u) + (wvs > 2 ? u.z : 0u);
             x64[q] += b64 - a64[q]; x32[q] += b32 - a32[q]; // exclusive of this thread's four
         }
 #pragma unroll
@@ -1702,7 +1710,7 @@ __device__ __forceinline__ void k_chunk_body(const ck_stage_ws &ws, int qw, int 
         // whatever the span's positions hold, written in this call or not: a coordinate is 13 bits of the point word (+ 1: <= 8192)
         // and a weight comes from the weight image (<= 362; k_tail reads nine bits of it), so a span's worth is at most
         // 960 x 511 x 8192 < 2^32
-        if (tid < 180) {
+        if (tid < 180 && stop_after >= 2) {
             const int b = tid / 6, q = tid - 6 * b;
             const int jh = KOFF + 32 * b + 31, jl = KOFF - 1;
             long long d;
@@ -1712,36 +1720,56 @@ __device__ __forceinline__ void k_chunk_body(const ck_stage_ws &ws, int qw, int 
             else d = (long long)(sP64[q - 2][jh] - sP64[q - 2][jl]);
             blk[((size_t)s * (CK_SPAN / 32) + b) * 6 + q] = d;
         }
+        if (stop_after <= 2) { // diagnostics: 1 ends the span behind the running sums, 2 behind the block sums
+            x4 = nx4;
+            ww[0] = gather_w(nx4.x); ww[1] = gather_w(nx4.y); ww[2] = gather_w(nx4.z); ww[3] = gather_w(nx4.w);
+            continue;
+        }
         // 3. windowed line-fit error of the positions whose smoothed value is needed (k_fit's chunk loop, same operations)
+        // 1 / W first, for all four positions of the thread: four table reads under way together, one wait in front of the doubles.
+        // Every position takes the same path — one outside [KOFF - 4, KOFF + CK_SPAN + 4) works on the nearest one inside, its
+        // result is never read — and every index lies in the table: a weight is what gather_w gave, the weight image's (<= 362)
+        // or 1, whatever the position holds, and sKsz is clamped to 20, so a window's weights sum to (2 * 20 + 1) * 362 at most.  The
+        // clamp is for a reader of this code, not for a case
+        static_assert(INV_N == (2 * 20 + 1) * 362 + 1 && KOFF - 4 - 20 - 1 >= 0 && KOFF + CK_SPAN + 3 + 20 < KL, "a window's weight sum and its ends");
+        int jc[4], ksz4[4];
+        double inv4[4];
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            jc[r] = min(max(tid + 256 * r, KOFF - 4), KOFF + CK_SPAN + 3);
+            ksz4[r] = (int)sKsz[jc[r]];
+            const uint32_t mw = sP32[2][jc[r] + ksz4[r]] - sP32[2][jc[r] - ksz4[r] - 1];
+            inv4[r] = g_inv_table.v[min(mw, (uint32_t)(INV_N - 1))];
+        }
         double ev[4];
 #pragma unroll
         for (int r = 0; r < 4; r++) {
-            const int j = tid + 256 * r;
-            ev[r] = 0.0;
-            if (j >= KOFF - 4 && j < KOFF + CK_SPAN + 4) {
-                const int ksz = (int)sKsz[j];
-                const int hi = j + ksz, lo = j - ksz - 1;
-                const uint32_t mx = sP32[0][hi] - sP32[0][lo], my = sP32[1][hi] - sP32[1][lo], mw = sP32[2][hi] - sP32[2][lo];
-                M6 m;
-                m.Mxx = (long long)(sP64[0][hi] - sP64[0][lo]); m.Mxy = (long long)(sP64[1][hi] - sP64[1][lo]); m.Myy = (long long)(sP64[2][hi] - sP64[2][lo]);
-                const double inv = mw < (uint32_t)INV_N ? g_inv_table.v[mw] : 1.0 / (double)mw;
-                const double Ex = (0.5 * (double)mx) * inv, Ey = (0.5 * (double)my) * inv;
-                const double Cxx = (0.25 * f64_of_u52((unsigned long long)m.Mxx)) * inv - Ex * Ex;
-                const double Cxy = (0.25 * f64_of_u52((unsigned long long)m.Mxy)) * inv - Ex * Ey;
-                const double Cyy = (0.25 * f64_of_u52((unsigned long long)m.Myy)) * inv - Ey * Ey;
-                const double d = Cxx - Cyy, q4 = 4.0 * Cxy;
-                const double disc = sqrt(d * d + q4 * Cxy);
-                ev[r] = (double)(2 * ksz + 1) * (0.5 * ((Cxx + Cyy) - disc));
-            }
+            const int ksz = ksz4[r], hi = jc[r] + ksz, lo = jc[r] - ksz - 1;
+            const uint32_t mx = sP32[0][hi] - sP32[0][lo], my = sP32[1][hi] - sP32[1][lo];
+            M6 m;
+            m.Mxx = (long long)(sP64[0][hi] - sP64[0][lo]); m.Mxy = (long long)(sP64[1][hi] - sP64[1][lo]); m.Myy = (long long)(sP64[2][hi] - sP64[2][lo]);
+            const double inv = inv4[r];
+            const double Ex = (0.5 * (double)mx) * inv, Ey = (0.5 * (double)my) * inv;
+            const double Cxx = (0.25 * f64_of_u52((unsigned long long)m.Mxx)) * inv - Ex * Ex;
+            const double Cxy = (0.25 * f64_of_u52((unsigned long long)m.Mxy)) * inv - Ex * Ey;
+            const double Cyy = (0.25 * f64_of_u52((unsigned long long)m.Myy)) * inv - Ey * Ey;
+            const double d = Cxx - Cyy, q4 = 4.0 * Cxy;
+            const double disc = sqrt(d * d + q4 * Cxy);
+            ev[r] = (double)(2 * ksz + 1) * (0.5 * ((Cxx + Cyy) - disc));
         }
         lds_barrier(); // every window has been read: the sums may go
+        // (all KL entries are written, the ones outside [KOFF - 4, KOFF + CK_SPAN + 4) with their nearest neighbour's value, which
+        // nobody reads: under a condition the compiler moves the first position's table read and doubles in here, behind the barrier)
 #pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const int j = tid + 256 * r;
-            if (j >= KOFF - 4 && j < KOFF + CK_SPAN + 4) sErr[j] = ev[r];
-        }
+        for (int r = 0; r < 4; r++) sErr[tid + 256 * r] = ev[r];
         const uint32_t nww[4] = {gather_w(nx4.x), gather_w(nx4.y), gather_w(nx4.z), gather_w(nx4.w)};
         lds_barrier();
+        auto next_span = [&]() {
+            x4 = nx4;
+#pragma unroll
+            for (int e = 0; e < 4; e++) ww[e] = nww[e];
+        };
+        if (stop_after == 3) { next_span(); continue; } // diagnostics: behind the window errors
         // 4. smoothed errors (the oracle's one-value-at-a-time sum, in its order)
 #pragma unroll
         for (int r = 0; r < 4; r++) {
@@ -1754,6 +1782,7 @@ __device__ __forceinline__ void k_chunk_body(const ck_stage_ws &ws, int qw, int 
             }
         }
         lds_barrier();
+        if (stop_after == 4) { next_span(); continue; } // diagnostics: behind the smoothing
         // 5. maxima: one word of 64 positions per wave and round
         unsigned long long bal[4];
         double myv[4];
@@ -1768,16 +1797,16 @@ __device__ __forceinline__ void k_chunk_body(const ck_stage_ws &ws, int qw, int 
                 ismax = v > sS[j + 1] && v > sS[j - 1];
             }
             bal[r] = __ballot(ismax);
-            const int k = 4 * r + wv;
-            if (lane == 0 && k < 16) sCnt[k] = (uint32_t)__popcll(bal[r]);
+            if (lane == 0) sCnt[4 * r + wvs] = (uint32_t)__popcll(bal[r]);
         }
         lds_barrier();
+        // the maxima in the words before word k: the sixteen counts in the lanes of a row, summed there, lane k's sum less its own
+        const uint32_t cnt = sCnt[lane & 15], cnt_excl = row_scan_u32(cnt) - cnt;
 #pragma unroll
         for (int r = 0; r < 4; r++) {
-            const int k = 4 * r + wv;
+            const int k = 4 * r + wvs;
             if (k >= CK_SPAN / 64) continue;
-            uint32_t pre = 0;
-            for (int i = 0; i < k; i++) pre += sCnt[i];
+            const uint32_t pre = (uint32_t)__builtin_amdgcn_readlane((int)cnt_excl, k);
             if (lane == 0) { mmask[(size_t)s * (CK_SPAN / 64) + k] = bal[r]; mpre[(size_t)s * (CK_SPAN / 64) + k] = (uint16_t)pre; }
             if ((bal[r] >> lane) & 1ull) {
                 const uint32_t pos = pre + (uint32_t)__popcll(bal[r] & ((1ull << lane) - 1ull));
@@ -1785,13 +1814,15 @@ __device__ __forceinline__ void k_chunk_body(const ck_stage_ws &ws, int qw, int 
                 mpos[(size_t)s * (CK_SPAN / 2) + pos] = (uint16_t)(tid + 256 * r);
             }
         }
-        x4 = nx4;
-#pragma unroll
-        for (int e = 0; e < 4; e++) ww[e] = nww[e];
+        next_span();
     }
 }
 
-__global__ __launch_bounds__(256) void k_chunk(ck_stage_ws ws, int qw, int qh) { k_chunk_body(ws, qw, qh); }
+#ifdef CK_DIAG
+__global__ __launch_bounds__(256) void k_chunk(ck_stage_ws ws, int qw, int qh, int stop_after) { k_chunk_body(ws, qw, qh, stop_after); }
+#else
+__global__ __launch_bounds__(256) void k_chunk(ck_stage_ws ws, int qw, int qh) { k_chunk_body(ws, qw, qh, 99); }
+#endif
 
 __device__ __forceinline__ double readlane_f64(double v, int l) {
     const unsigned long long u = (unsigned long long)__double_as_longlong(v);
@@ -2531,7 +2562,15 @@ int ck_launch_fit_quads(ck_handle *h, const ck_dev_image &qimg, const ck_dev_ima
         if (gx < 8) gx = 8;
         if (gx > spans) gx = spans;
         // (k_chunk's register count capped at 96 / 80: no difference — three workgroups per CU either way, its LDS decides)
+#ifdef CK_DIAG
+        // (read per call; tools/ablate_chunk.sh.  Cut short — 5 is the whole kernel — its lists are not there for k_tail, which then ends
+        // every cluster before it reads them, as under CK_FIT_STOP_AFTER=4)
+        const int chunk_stop = CK_KNOB("CK_CHUNK_STOP_AFTER", 99);
+        if (a.stop_after > 3) hipLaunchKernelGGL(k_chunk, dim3(gx, (unsigned)n), dim3(256), 0, h->stream, ws, h->qw, h->qh, chunk_stop);
+        if (chunk_stop <= 5 && a.stop_after > 4) a.stop_after = 4;
+#else
         if (a.stop_after > 3) hipLaunchKernelGGL(k_chunk, dim3(gx, (unsigned)n), dim3(256), 0, h->stream, ws, h->qw, h->qh);
+#endif
         use_list(CK_FIT_CLASSES); // every cluster of the batch
         hipLaunchKernelGGL(k_tail, dim3((unsigned)(FIT_CUS * k_tail_wgs)), dim3(64), 0, h->stream, a);
     }
