@@ -34,7 +34,9 @@ typedef uint16_t ck_label_t;
 #define CK_RING_CAP (2 * (CK_TW + CK_TH)) /* ring-touching roots a tile can have: one per ring pixel at most */
 
 // frame-level resolution of a label word at pixel (x, y): the root's pixel index for an interior component, CK_LBL_INVALID for none;
-// a ring-touching component (CK_LBL_BORDER) is resolved by the caller through the slot tables (ck_label_slot)
+// a ring-touching component (CK_LBL_BORDER) is resolved by the caller through the slot tables (ck_label_slot).
+// Both are a term of the pixel's CCL tile + a term of the label word: k_emit2's group staging forms the tile terms once for four
+// pixels of one tile (ck_emit_stage.h: ck_es_slot_base, ck_es_root_base; tests/cpp/emit_stage_check.cpp holds the two texts together)
 __host__ __device__ inline uint32_t ck_label_slot(uint32_t l, int x, int y, int ccl_tiles_x) {
     return (uint32_t)((y / CK_TH) * ccl_tiles_x + x / CK_TW) * (uint32_t)CK_RING_CAP + (l & CK_LBL_ID_MASK);
 }

@@ -16,6 +16,7 @@
 //   k_scatter  one wave per run: temp array -> points grouped by cluster.
 #include "ck_internal.h"
 #include "ck_emit_row.h"
+#include "ck_emit_stage.h"
 
 namespace {
 
@@ -40,6 +41,7 @@ struct EmitArgs {
     int ccl_tiles_x; // tiles per row of the segmentation stage (the label words are local to its 32 x 128 tiles)
     int stop_after; // diagnostics (CK_EMIT_STOP_AFTER): 0 staging only, 1 +count, 2 +reserve; 99 = everything
     int twins;      // k_emit2 merges diagonal twin points (diagnostics: CK_EMIT_TWINS=0 emits every point on its own)
+    int stage4;     // k_emit2 stages its tile in aligned groups of four pixels where the frame allows it (diagnostics: CK_EMIT_STAGE4=0 never)
     ck_stage_ws ws;
 };
 
@@ -295,6 +297,11 @@ __global__ __launch_bounds__(NT) void k_emit(EmitArgs a) {
 // scalar against 1 389 vector instructions per wave); they are now bits of one vector register per pixel row that index a table of
 // the row's leaders (ck_emit_row.h), and the probe-and-add block runs once per leader: 580 scalar + 1 300 vector instructions per
 // wave, count pass 1.36 -> 0.85 ms, kernel 2.58 -> 2.25 ms.
+// The point writes read ONE LDS word per point and make one test: pass 2 marks the run start of a key without a place in the frame's
+// table (NO_RUN, bit 31), which puts its points past point_cap; the table of places (2 KB of LDS) is gone: write pass and run
+// records 251 + 212 -> 235 vector + 145 scalar and 36 -> 18 LDS instructions (static), -0.15 ms.  When the frame's width is a multiple
+// of four the tile is staged in aligned groups of four pixels (ck_emit_stage.h, k_emit2<true>): staging 292 + 292 -> 197 + 240
+// (static, the two waves with a second round), -0.09 ms on top (by itself, on the earlier write pass, it was inside the noise).
 // Tried on the way and measured slower (1280 x 800 x 256, clusters stage, same box; k_emit: 3.51-3.56 ms):
 //  * the count and write passes as straight-line code over all 16 candidate slots of a thread (a slot without a point counts 0 into
 //    a per-lane dummy entry) and the tile's points ordered in LDS and copied out in one piece: fewer scalar instructions, but 32 slot
@@ -309,13 +316,19 @@ constexpr int SR_PAD = ((LH * LW + NT - 1) / NT) * NT; // ids: every thread stor
 static_assert(SKIP == CK_ER_SKIP && ID_WHITE == CK_ER_WHITE, "ck_emit_row.h speaks of the staged words of this kernel");
 // the row table (ck_emit_row.h), generated at compile time; every workgroup copies its 4 KB into LDS (one 16-byte load per thread,
 // after the staging loads: issued before them it holds four registers across the kernel's register peak): with it a workgroup holds
-// 19 508 of the 20 480 bytes that eight of them leave each other
+// 17 460 of the 20 480 bytes that eight of them leave each other
 __device__ const ck_emit_row_table g_emit_rows = ck_make_emit_row_table();
 static_assert(CK_ER_ROWS == 4 * NT, "one uint4 of the row table per thread");
+static_assert(CK_ES_NT == NT && CK_ES_TW == ETW && CK_ES_TH == ETH && CK_ES_LW == LW && CK_ES_LH == LH && CK_ES_WORDS <= SR_PAD, "ck_emit_stage.h speaks of this kernel's tile");
+static_assert(CK_ES_CCL_TW == CK_TW && CK_ES_CCL_TH == CK_TH && CK_ES_RING_CAP == CK_RING_CAP && CK_ES_LBL_BORDER == CK_LBL_BORDER && CK_ES_LBL_SMALL == CK_LBL_SMALL &&
+              CK_ES_LBL_ID_MASK == CK_LBL_ID_MASK && CK_ES_SKIP == SKIP && CK_ES_WHITE == ID_WHITE, "... and of the label words of ck_internal.h");
 
+// G4: the tile is staged in aligned groups of four pixels (ck_emit_stage.h; the width is a multiple of four and the buffers are
+// aligned: ck_launch_clusters decides for the whole launch).  Without it: every pixel on its own, for any width.
+template <bool G4>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80), amdgpu_waves_per_eu(8))) void k_emit2(EmitArgs a, int xcd_map, int n_frames) {
     __shared__ __attribute__((aligned(16))) uint32_t sRaw[SR_PAD + LHT * 2 + LHT];
-    __shared__ uint32_t sSlot[LHT], sTBase[LHT];
+    __shared__ uint32_t sTBase[LHT];
     __shared__ uint32_t sWave[NT / 64 + 1], sRunW[NT / 64 + 1];
     __shared__ __attribute__((aligned(16))) uint32_t sRow[CK_ER_ROWS];
     uint32_t *sR = sRaw;                                                             // [LH][LW] ids
@@ -344,6 +357,55 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80), amdgpu_wave
     ck_run *runs = ws.d_runs + (size_t)frame * ws.run_cap;
 
     for (int i = tid; i < LHT; i += NT) { sKey[i] = 0ull; sCnt[i] = 0; }
+    if constexpr (G4) {
+        // staging in groups (ck_emit_stage.h): one dword of threshold bytes and one 8-byte word of labels per four pixels, the tile
+        // terms of slot and root once per group, one 16-byte LDS write.  Round 0: every thread one group of the tile's own pixels;
+        // round 1: the bottom halo row and the two halo columns, 98 single pixels, the first two waves' — the other two skip it on
+        // a scalar.  A wave has both rounds' loads in flight together, then both rounds' gathers.
+        // (every address is a uniform base + a 32-bit byte offset, which the load takes as it is: a frame's labels and a frame's slot
+        // tables are far below 4 GiB)
+        auto at = [](const void *base, uint32_t bytes) { return reinterpret_cast<const char *>(base) + bytes; };
+        auto gather = [&](uint32_t slot, uint32_t &hop, uint32_t &csz) {
+            hop = *reinterpret_cast<const uint32_t *>(at(GR, slot * 4u)); csz = *reinterpret_cast<const uint32_t *>(at(GS, slot * 4u));
+        };
+        const bool round1 = __builtin_amdgcn_readfirstlane(tid >> 6) < CK_ES_ROUND1_WAVES;
+        const ck_es_item it0 = ck_es_round0(tid, x0, y0, w, h);
+        ck_es_item it1 = it0;
+        uint32_t lab[4], tv[4], hop[4], csz[4], lab1 = 0u, tv1 = 0u, hop1 = 0u, csz1 = 0u;
+        {
+            const uint32_t p = (uint32_t)it0.cy * (uint32_t)w + (uint32_t)it0.cx; // (a multiple of four)
+            const uint32_t t4 = *reinterpret_cast<const uint32_t *>(at(T, p));
+            const uint2 l4 = *reinterpret_cast<const uint2 *>(at(L, p * (uint32_t)sizeof(ck_label_t)));
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                tv[j] = (t4 >> (8 * j)) & 0xFFu;
+                const uint32_t l2 = j < 2 ? l4.x : l4.y;
+                lab[j] = (j & 1) ? l2 >> 16 : l2 & 0xFFFFu;
+            }
+        }
+        if (round1) {
+            it1 = ck_es_round1(tid, x0, y0, w, h);
+            const uint32_t p = (uint32_t)it1.cy * (uint32_t)w + (uint32_t)it1.cx;
+            tv1 = T[p]; lab1 = L[p];
+        }
+        {
+            const uint32_t slot_base = ck_es_slot_base(it0.cx, it0.cy, a.ccl_tiles_x);
+#pragma unroll
+            for (int j = 0; j < 4; j++) gather(ck_es_pixel_slot(lab[j], tv[j], it0.inb, slot_base), hop[j], csz[j]);
+        }
+        if (round1) gather(ck_es_pixel_slot(lab1, tv1, it1.inb && it1.keep, ck_es_slot_base(it1.cx, it1.cy, a.ccl_tiles_x)), hop1, csz1);
+        {
+            const uint32_t rb = ck_es_root_base(it0.cx, it0.cy, w);
+            uint4 v;
+            v.x = ck_es_pixel_word(lab[0], tv[0], it0.inb, hop[0], csz[0], rb, w, a.min_comp);
+            v.y = ck_es_pixel_word(lab[1], tv[1], it0.inb, hop[1], csz[1], rb, w, a.min_comp);
+            v.z = ck_es_pixel_word(lab[2], tv[2], it0.inb, hop[2], csz[2], rb, w, a.min_comp);
+            v.w = ck_es_pixel_word(lab[3], tv[3], it0.inb, hop[3], csz[3], rb, w, a.min_comp);
+            *reinterpret_cast<uint4 *>(sR + ck_es_item_word(it0)) = v;
+        }
+        if (round1 && it1.keep)
+            sR[ck_es_item_word(it1)] = ck_es_pixel_word(lab1, tv1, it1.inb, hop1, csz1, ck_es_root_base(it1.cx, it1.cy, w), w, a.min_comp);
+    } else
     {   // staging: every thread's pixels go through the (up to two) dependent loads side by side (addresses clamped into the frame,
         // results masked): a pixel becomes the frame pixel of its component's root | its colour, or SKIP
         constexpr int SPT = SR_PAD / NT;
@@ -388,7 +450,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80), amdgpu_wave
     // registers (sign << 31 | slot << 16 | rank) so that the write pass neither probes nor counts again.  The thread's 5 x 3 ids
     // are read once; the (up to four) points of a pixel often share their key — the three neighbours below are side by side, so
     // when they are white they are one component — and then make ONE add, the first point of the key doing it for the others.
-    constexpr uint32_t NONE = 0xFFFFFFFFu;
+    constexpr uint32_t NONE = 0xFFFFFFFFu, NO_RUN = 0x80000000u;
     uint32_t cand[16];
     {
         uint32_t R[5][3];
@@ -397,7 +459,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80), amdgpu_wave
         // (a staged row is read one pixel row ahead of its first use, not all five at the start: nine words live instead of fifteen)
         auto stage_row = [&](int r) {
 #pragma unroll
-            for (int c = 0; c < 3; c++) R[r][c] = sR[(row0 + r) * LW + lx - 1 + c];
+            for (int c = 0; c < 3; c++) R[r][c] = sR[G4 ? ck_es_word(row0 + r, lx - 1 + c) : (row0 + r) * LW + lx - 1 + c];
         };
         stage_row(0); stage_row(1);
         // The predicates of a pixel row (ck_emit_row.h) are bits of one vector register, never lane masks: the Boolean algebra the
@@ -480,7 +542,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80), amdgpu_wave
     // points each and absorb at most one more, so neither sum comes near 2^16)
     const uint32_t b0 = k0 ? sCnt[2 * tid] : 0u, b1 = k1 ? sCnt[2 * tid + 1] : 0u;
     const uint32_t c0 = b0 >> 16, c1 = b1 >> 16;
-    uint32_t found0 = SKIP, found1 = SKIP, ridx0;
+    uint32_t found0 = SKIP, found1 = SKIP, ridx0, tb0, tb1; // (tb: where the key's run starts in the tile's piece of the temp array)
     {
         const uint32_t incl2 = wave_scan_u32(b0 + b1), incl = incl2 >> 16;
         const unsigned long long u0 = __ballot(k0 != 0ull), u1 = __ballot(k1 != 0ull);
@@ -510,7 +572,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80), amdgpu_wave
             if ((uint32_t)(was >> 32) + ltotal > (uint32_t)ws.point_cap) atomicOr(&counters[CK_CNT_STATUS], (uint32_t)CK_FRAME_POINTS_OVERFLOW);
         }
         const uint32_t excl = before + incl - (c0 + c1);
-        sTBase[2 * tid] = excl; sTBase[2 * tid + 1] = excl + c0;
+        tb0 = excl; tb1 = excl + c0;
         {   // both first probes of the frame table in flight together; only a probe that met another key walks on
             const uint32_t hm = (uint32_t)(ws.ht_size - 1);
             const uint32_t g0 = key_hash(k0) & hm, g1 = key_hash(k1) & hm;
@@ -532,7 +594,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80), amdgpu_wave
                     }
                     if (found == SKIP) atomicOr(&counters[CK_CNT_STATUS], (uint32_t)CK_FRAME_CLUSTERS_OVERFLOW);
                 }
-                sSlot[2 * tid + q] = found;
+                // (a key without a place — no room in the frame's table — has no run: the mark puts every point of it past point_cap
+                // in pass 3, which so needs no test of its own for it; point_cap and a tile's base are far below 2^31)
+                sTBase[2 * tid + q] = (q ? tb1 : tb0) | (found == SKIP ? NO_RUN : 0u);
                 if (q) found1 = found; else found0 = found;
             }
         }
@@ -552,9 +616,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80), amdgpu_wave
         const int rr = q >> 2, k = q & 3;
         const int dxk = k == 1 ? 0 : (k == 2 ? -1 : 1), dyk = k == 0 ? 0 : 1;
         const uint32_t s = (cd >> 16) & 0x3FFu, lr = cd & 0xFFFFu;
-        if (sSlot[s] == SKIP) continue; // (a key dropped in pass 2: a member below min_component_px, or no room in the frame's table)
         const uint32_t ti = tile_base + sTBase[s] + lr;
-        if (ti >= (uint32_t)ws.point_cap) continue; // (pass 2 has set the status bit: fewer words than points)
+        if (ti >= (uint32_t)ws.point_cap) continue; // (pass 2 has set the status bit: fewer words than points; or NO_RUN: a key it dropped)
         const int gy = y0 + row0 + rr;
         const uint32_t twin = k == 3 ? cd & (CK_PT_TWIN | CK_PT_TWIN_SIGN) : 0u; // (only a (1,1) point absorbs)
         tmp[ti] = twin | ((uint32_t)(2 * gx + dxk) << 16) | ((uint32_t)(2 * gy + dyk) << 3) | ((uint32_t)k << 1) | (cd >> 31);
@@ -570,7 +633,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80), amdgpu_wave
             // as it was, k_scatter would follow whatever an earlier call had written there)
             if (ri < (uint32_t)ws.run_cap) {
                 ck_run r;
-                r.slot = found != SKIP ? found : 0u; r.base = 0; r.tmp_start = tile_base + (q ? sTBase[2 * tid + 1] : sTBase[2 * tid]);
+                r.slot = found != SKIP ? found : 0u; r.base = 0; r.tmp_start = tile_base + (q ? tb1 : tb0);
                 r.count = found != SKIP ? (q ? c1 : c0) : 0u;
                 runs[ri] = r;
             } else if (found != SKIP) atomicOr(&counters[CK_CNT_STATUS], (uint32_t)CK_FRAME_CLUSTERS_OVERFLOW);
@@ -764,13 +827,17 @@ int ck_launch_clusters(ck_handle *h, int n) {
     a.min_comp = h->cfg.min_component_px; a.ws = ws; a.ccl_tiles_x = h->tiles_x;
     { static const int stop_after = CK_KNOB("CK_EMIT_STOP_AFTER", 99); a.stop_after = stop_after; }
     { static const int twins = CK_KNOB("CK_EMIT_TWINS", 1); a.twins = twins; } // (diagnostics: 0 = every point on its own, for A/B)
+    { static const int stage4 = CK_KNOB("CK_EMIT_STAGE4", 1); a.stage4 = stage4; } // (diagnostics: 0 = every pixel staged on its own, for A/B)
     static const int emit_v = CK_KNOB("CK_EMIT_V", 2);       // (diagnostics: 1 = the round-1..3 kernel, for A/B)
     static const int emit_xcd = CK_KNOB("CK_EMIT_XCD", -1);  // (diagnostics: frames dealt to XCDs 0 / 1; default: batches of 16 frames and more)
     if (emit_v == 1) hipLaunchKernelGGL(k_emit, dim3((unsigned)(a.tiles_x * a.tiles_y * n)), dim3(NT), 0, h->stream, a);
     else {
         const int xcd_map = emit_xcd >= 0 ? emit_xcd : (n >= 16 ? 1 : 0);
         const unsigned grid = xcd_map ? (unsigned)(((n + 7) / 8) * 8 * a.tiles_x * a.tiles_y) : (unsigned)(a.tiles_x * a.tiles_y * n);
-        hipLaunchKernelGGL(k_emit2, dim3(grid), dim3(NT), 0, h->stream, a, xcd_map, n);
+        // groups of four pixels: rows, frames and the buffers themselves start at multiples of four pixels
+        const bool g4 = a.stage4 && ck_es_group_path(a.w) && ((uintptr_t)a.thresh & 3u) == 0 && ((uintptr_t)a.labels & 7u) == 0;
+        if (g4) hipLaunchKernelGGL(k_emit2<true>, dim3(grid), dim3(NT), 0, h->stream, a, xcd_map, n);
+        else hipLaunchKernelGGL(k_emit2<false>, dim3(grid), dim3(NT), 0, h->stream, a, xcd_map, n);
     }
     int min_cluster = h->cfg.min_cluster_pixels < 24 ? 24 : h->cfg.min_cluster_pixels;
     hipLaunchKernelGGL(k_scan, dim3((unsigned)n), dim3(SNT), 0, h->stream, ws, min_cluster, ws.max_cluster_points);
