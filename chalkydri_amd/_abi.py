@@ -125,6 +125,34 @@ class Camera(C.Structure):
     _fields_ = [("model", C.c_int32), ("pad", C.c_int32), ("k", C.c_double * 9)]
 
 
+# coloured game pieces: ck_blob_t.flags, then the per-frame status bits
+CK_BLOB_MAX_CLASSES = 4
+CK_BLOB_HAS_BEARING, CK_BLOB_HAS_GROUND, CK_BLOB_AT_BORDER = 1, 2, 4
+CK_BLOB_TRUNCATED, CK_BLOB_OVERFLOW = 1, 2
+
+
+class BlobClass(C.Structure):
+    """ck_blob_class_t"""
+    _fields_ = [(k, C.c_int32) for k in ("h_min", "h_max", "s_min", "s_max", "v_min", "v_max", "min_area", "max_area",
+                                         "min_fill_permille", "min_aspect_permille", "max_aspect_permille", "pad")] + [("ground_z", C.c_double)]
+
+
+class BlobParams(C.Structure):
+    """ck_blob_params_t"""
+    _fields_ = [(k, C.c_int32) for k in ("n_classes", "erode", "dilate", "max_targets", "max_components", "has_camera", "has_mount", "pad")] + [
+        ("cls", BlobClass * CK_BLOB_MAX_CLASSES), ("cam", Camera), ("robot_to_cam", Iso3), ("max_range", C.c_double)]
+
+
+class Blob(C.Structure):
+    """ck_blob_t"""
+    _fields_ = [(k, C.c_int32) for k in ("class_id", "flags", "area", "x0", "y0", "x1", "y1", "seed")] + [
+        (k, C.c_int64) for k in ("sx", "sy", "sxx", "sxy", "syy")] + [
+        ("cx", C.c_double), ("cy", C.c_double), ("major", C.c_double), ("minor", C.c_double), ("axis", C.c_double * 2),
+        ("bearing", C.c_double * 3), ("ground", C.c_double * 2)]
+
+
+assert C.sizeof(BlobClass) == 56 and C.sizeof(BlobParams) == 400 and C.sizeof(Blob) == 160
+
 CK_SUBPIX_CONVERGED, CK_SUBPIX_MAXIT, CK_SUBPIX_FLAT, CK_SUBPIX_REJECTED = 0, 1, 2, 3
 
 

@@ -33,7 +33,7 @@ def load_field_layout(path_or_dict):
 class AprilTags:
     def __init__(self, width, height, field, calib, robot_to_cam, cam_id=0, family="tag36h11", bits_corrected=3,
                  max_batch=1, device=0, quad_sigma=0.0, fourcc=None, orientation="none", auto_exposure=False, exposure0=1.0,
-                 exposure_params=None, jpeg_color=False, corner_subpix=None, **cfg):
+                 exposure_params=None, jpeg_color=False, corner_subpix=None, blobs=None, **cfg):
         """width x height is the image the detector sees, and calib its intrinsics: with an `orientation` ("none", "clockwise",
         "rotate-180", "counterclockwise": the reference's VideoOrientation names) those of the ORIENTED image.  `fourcc` names the
         raw format of the camera's frames for process_raw_batch ("YUYV", "RGB3", ...; None: 8-bit luma), or "MJPG" / "JPEG": the
@@ -42,7 +42,11 @@ class AprilTags:
         auto_exposure=True (the reference's Camera.auto_exposure) meters the last frame of every batch the task stages, on the
         device, and keeps the exposure to set next in `exposure` (unit and start: exposure0); off, nothing is launched.
         corner_subpix=True (or a dict of AprilTagDetector.set_corner_subpix's arguments) refines every detection's corners to
-        sub-pixel accuracy on the device before the pose is solved; off (the default), nothing is launched."""
+        sub-pixel accuracy on the device before the pose is solved; off (the default), nothing is launched.
+        blobs (a ck_blob_params_t from chalkydri_amd.blobs.blob_params, or a list of its ColorClass): the camera's second consumer,
+        the reference's `ml` slot: after process_raw_batch of a packed colour format (or of JPEG frames with jpeg_color=True)
+        `.blobs` holds the coloured targets of the frames just processed, found on the device in the same raw frames
+        (AprilTagDetector.detect_blobs' triple), with the task's own calib and robot_to_cam behind the bearings and ground points."""
         if fourcc in A.JPEG_FOURCCS:
             from .detector import orientation_code
             orientation_code(orientation)                           # (ValueError for an unknown name, before any device work)
@@ -71,6 +75,12 @@ class AprilTags:
         self._pp.field, self._pp.n_field = self._field, len(self.tags)
         self._pp.camera_id, self._pp.sign_change_error = cam_id, SIGN_FLIP_CONST
         self._pp.sqpnp = self.solver._prm
+        self.blobs, self._blob_params = None, None
+        if blobs is not None:
+            from .blobs import blob_params
+            bp = blobs if isinstance(blobs, A.BlobParams) else blob_params(list(blobs))
+            bp.has_camera, bp.cam, bp.has_mount, bp.robot_to_cam = 1, self.camera, 1, self.robot_to_cam
+            self._blob_params = bp
         self._exposure = None
         if auto_exposure:
             from .exposure import ExposureController
@@ -116,7 +126,10 @@ class AprilTags:
             n = self.detector.upload_jpeg(raw_frames, self.orientation, color=self.jpeg_color)
         else:
             n = self.detector.upload_raw(raw_frames, self.fourcc or "GREY", self.orientation)
-        return self.process_batch(None, gyro, n=n)
+        out = self.process_batch(None, gyro, n=n)
+        if self._blob_params is not None:   # (a source without colour is an error here, not an empty answer)
+            self.blobs = self.detector.detect_blobs(self._blob_params, n=n)
+        return out
 
     process_raw = process_raw_batch
 

@@ -16,6 +16,7 @@
 #include "ck_rigcal.h"
 #include "ck_fieldcal.h"
 #include "ck_rig_refine.h"
+#include "ck_blobs.h"
 #include "ck_subpix.h"
 
 thread_local char ck_err_text[512] = "";
@@ -191,6 +192,7 @@ extern "C" void ck_destroy(ck_handle_t *h) {
     delete h->rigcal;
     delete h->fieldcal;
     delete h->rig_refine;
+    delete h->blobs;
     delete h->subpix_ws;
     for (auto &e : h->ev) if (e) (void)hipEventDestroy(e);
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);

@@ -1,4 +1,4 @@
-// The buffers of the on-demand workspaces (JPEG decode, raw staging, preview, exposure, tri-class threshold, calibration; one JPEG workspace per slot
+// The buffers of the on-demand workspaces (JPEG decode, raw staging, preview, exposure, tri-class threshold, calibration, coloured pieces; one JPEG workspace per slot
 // of a JPEG ingest ring): each owns its memory, grows when a call needs more and releases it when its workspace is deleted.  DESIGN.md §4g.
 #ifndef CK_GROW_H
 #define CK_GROW_H

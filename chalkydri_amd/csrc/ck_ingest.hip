@@ -12,6 +12,7 @@
 #include "ck_exposure.h"
 #include "ck_internal.h"
 #include "ck_jpeg.h"
+#include "ck_blobs.h"
 #include "ck_preview.h"
 #include "ck_rawfmt.h"
 
@@ -244,6 +245,20 @@ static int preview_color_ingested(ck_ingest_t *g, int32_t slot, const ck_preview
     if (decoded) return ck_preview_color_run(g->h, pp, {nullptr, 0, 0, js.n_frames, nullptr, &js}, frames, n, out, files, cap_per_frame, sizes, status);
     return ck_preview_color_run(g->h, pp, {g->rawdev[slot], g->geo.stride16, (int64_t)g->geo.pitch16, g->staged[slot], &g->fmt, nullptr}, frames, n, out,
                                 files, cap_per_frame, sizes, status);
+}
+// Coloured game pieces (ck_blobs.hip) of a submitted slot, from the same sources; the slot stays as it is.
+extern "C" int ck_detect_blobs_ingested(ck_ingest_t *g, int32_t slot, const ck_blob_params_t *pp, const int32_t *frames, int32_t n,
+                                        ck_blob_t *out, int32_t cap, int32_t *counts, uint32_t *status) {
+    if (!slot_ok(g, slot)) return CK_EINVAL;
+    ck_jpeg_color_src js;
+    const bool decoded = g->jpeg && ck_jpeg_slots_color_source(g->jpeg, slot, slot_image(g, slot), g->staged[slot], &js);
+    if (!g->raw && !decoded) return CK_EUNSUPPORTED;
+    ck_dev_image img;
+    const int rc = await_slot(g, slot, &img);
+    if (rc != CK_OK) return rc;
+    if (decoded) return ck_blobs_run(g->h, pp, {nullptr, 0, 0, js.n_frames, nullptr, &js}, frames, n, out, cap, counts, status);
+    return ck_blobs_run(g->h, pp, {g->rawdev[slot], g->geo.stride16, (int64_t)g->geo.pitch16, g->staged[slot], &g->fmt, nullptr}, frames, n, out,
+                        cap, counts, status);
 }
 extern "C" int ck_preview_jpeg_color_ingested(ck_ingest_t *g, int32_t slot, const ck_preview_params_t *pp, const int32_t *frames, int32_t n,
                                               uint8_t *out, int64_t cap_per_frame, int64_t *sizes, uint32_t *status) {

@@ -224,6 +224,8 @@ struct ck_handle {
     struct ck_fieldcal_ws *fieldcal;
     // rig pose refinement (ck_rig_refine.hip, k_rig_refine.hip): allocated by the first refinement call, grown on demand
     struct ck_rig_refine_ws *rig_refine;
+    // coloured game pieces (ck_blobs.hip, k_blobs.hip): allocated by the first blob call, grown on demand
+    struct ck_blob_ws *blobs;
     bool fmerge_lds_allowed; // k_fmerge's dynamic LDS limit has been raised on this handle's device
     // ck_set_camera: while has_camera, the glue and the per-tag pose unproject with `camera` (UCM's k[5] already 1.0) instead of their
     // params' OpenCVModel5; 0 (the default): nothing about those paths changes

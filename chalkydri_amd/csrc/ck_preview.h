@@ -84,4 +84,9 @@ struct ck_pv_color_src { const uint8_t *p; int stride; int64_t pitch; int n_fram
 int ck_preview_color_run(ck_handle *h, const ck_preview_params_t *pp, const ck_pv_color_src &src, const int32_t *frames, int32_t n,
                          uint8_t *out, bool files, int64_t cap_per_frame, int64_t *sizes, uint32_t *status);
 
+// the same source as the kernels take it (identity: a packed colour family's own R, G, B instead of its Y Cb Cr: §4r), checked;
+// *n_avail: the frames an index may name.  ck_pv_staged_source: the colour source behind the staged frames (CK_EINVAL: none).
+int ck_pv_source(ck_handle *h, const ck_pv_color_src &src, bool identity, ck_pv_csrc *cs, ck_pv_jsrc *js, ck_pv_src *any, int *n_avail);
+int ck_pv_staged_source(ck_handle *h, ck_pv_color_src *src, ck_jpeg_color_src *js);
+
 #endif

@@ -190,7 +190,8 @@ int overlay_component(int c) { return (kYcc[c][0] * 0 + kYcc[c][1] * 255 + kYcc[
 
 // what the kernels need of a packed colour family (ck_raw_class: bpp 2 with the luma's byte offset in k[2], bpp 3 / 4 with the luma
 // weight of a pixel's bytes 0, 1, 2: the weight of byte 0 tells RGB from BGR)
-void color_source(const ck_raw_geom &L, int orientation, const uint8_t *p, int stride, size_t pitch, ck_pv_csrc *cs) {
+// identity: the weights that hand a packed colour family's own R, G, B bytes through instead (the coloured-piece detector, §4r)
+void color_source(const ck_raw_geom &L, int orientation, const uint8_t *p, int stride, size_t pitch, bool identity, ck_pv_csrc *cs) {
     memset(cs, 0, sizeof *cs);
     cs->p = p; cs->stride = stride; cs->pitch = pitch;
     cs->sw = L.sw; cs->sh = L.sh; cs->orientation = orientation; cs->bpp = L.cls.bpp;
@@ -200,13 +201,34 @@ void color_source(const ck_raw_geom &L, int orientation, const uint8_t *p, int s
     }
     const bool bgr = L.cls.k[0] == CK_LUMA_B;
     for (int c = 0; c < 3; c++) {
-        for (int k = 0; k < 3; k++) cs->wgt[c][k] = kYcc[c][bgr ? 2 - k : k];
-        cs->bias[c] = kYccBias[c];
+        for (int k = 0; k < 3; k++) cs->wgt[c][k] = identity ? ((bgr ? 2 - k : k) == c ? 65536 : 0) : kYcc[c][bgr ? 2 - k : k];
+        cs->bias[c] = identity ? 0 : kYccBias[c];
         cs->ovl[c] = overlay_component(c);
     }
 }
 
 } // namespace
+
+// The source of a colour call as the kernels take it, checked in the contract's order; *n_avail: the frames an index may name.
+int ck_pv_source(ck_handle *h, const ck_pv_color_src &src, bool identity, ck_pv_csrc *cs, ck_pv_jsrc *js, ck_pv_src *any, int *n_avail) {
+    *any = {nullptr, nullptr};
+    if (src.jpeg) { // the frames of a JPEG decode in the colour form (§4i)
+        const ck_jpeg_color_src &J = *src.jpeg;
+        *js = {J.img.p, J.img.stride, J.img.pitch, J.descs, J.status, J.planes, J.sw, J.sh, J.orientation, {overlay_component(0), overlay_component(1), overlay_component(2)}};
+        any->jpeg = js;
+        *n_avail = J.n_frames;
+        return CK_OK;
+    }
+    ck_raw_geom L;
+    const int rc = ck_raw_geometry(src.fmt, h->w, h->h, &L);
+    if (rc != CK_OK) return rc;
+    if (L.cls.bpp == 1) return CK_EUNSUPPORTED; // a luma-first family: its chroma never reaches the device (the grey preview serves it)
+    if ((!src.p && src.n_frames > 0) || src.n_frames < 0 || src.stride < L.min_stride || src.pitch < (int64_t)src.stride * L.sh) return CK_EINVAL;
+    color_source(L, src.fmt->orientation, src.p, src.stride, (size_t)src.pitch, identity, cs);
+    any->raw = cs;
+    *n_avail = src.n_frames;
+    return CK_OK;
+}
 
 int ck_preview_color_run(ck_handle *h, const ck_preview_params_t *pp, const ck_pv_color_src &src, const int32_t *frames, int32_t n,
                          uint8_t *out, bool files, int64_t cap_per_frame, int64_t *sizes, uint32_t *status) {
@@ -216,24 +238,11 @@ int ck_preview_color_run(ck_handle *h, const ck_preview_params_t *pp, const ck_p
     if (rc != CK_OK) return rc;
     ck_pv_csrc cs;
     ck_pv_jsrc js;
-    ck_pv_src any = {nullptr, nullptr};
-    if (src.jpeg) { // the frames of a JPEG decode in the colour form (§4i)
-        const ck_jpeg_color_src &J = *src.jpeg;
-        rc = begin(h, frames, n, J.n_frames, &g);
-        if (rc != CK_OK || n == 0) return rc;
-        js = {J.img.p, J.img.stride, J.img.pitch, J.descs, J.status, J.planes, J.sw, J.sh, J.orientation, {overlay_component(0), overlay_component(1), overlay_component(2)}};
-        any.jpeg = &js;
-    } else {
-        ck_raw_geom L;
-        rc = ck_raw_geometry(src.fmt, h->w, h->h, &L);
-        if (rc != CK_OK) return rc;
-        if (L.cls.bpp == 1) return CK_EUNSUPPORTED; // a luma-first family: its chroma never reaches the device (the grey preview serves it)
-        if ((!src.p && src.n_frames > 0) || src.n_frames < 0 || src.stride < L.min_stride || src.pitch < (int64_t)src.stride * L.sh) return CK_EINVAL;
-        rc = begin(h, frames, n, src.n_frames, &g);
-        if (rc != CK_OK || n == 0) return rc;
-        color_source(L, src.fmt->orientation, src.p, src.stride, (size_t)src.pitch, &cs);
-        any.raw = &cs;
-    }
+    ck_pv_src any;
+    int n_avail;
+    rc = ck_pv_source(h, src, false, &cs, &js, &any, &n_avail);
+    if (rc == CK_OK) rc = begin(h, frames, n, n_avail, &g);
+    if (rc != CK_OK || n == 0) return rc;
     if (files) return encode_files(h, pp, g, &any, n, out, cap_per_frame, sizes, status);
     return read_pixels(h, (size_t)g.pw * g.ph * 3 * n, out, [&](uint8_t *d) { return ck_launch_preview_color(h, g, any, n, d); });
 }
@@ -282,7 +291,7 @@ extern "C" int ck_preview_jpeg(ck_handle_t *h, const ck_preview_params_t *pp, co
 // ---- colour (§4g): the raw frames of the handle's staging, or of the caller's device memory ---------------------------------------
 // the colour source behind the staged frames: their raw twin, while the last ck_upload_raw / ck_raw_luma_batch still is what staged
 // them; or the chroma planes beside them, while the last ck_upload_jpeg_color is (*js is then what src->jpeg points to)
-static int staged_color_source(ck_handle *h, ck_pv_color_src *src, ck_jpeg_color_src *js) {
+int ck_pv_staged_source(ck_handle *h, ck_pv_color_src *src, ck_jpeg_color_src *js) {
     if (!h) return CK_EINVAL;
     if (h->n_jpeg_color >= 0) {
         const int rc = ck_jpeg_color_source(h, js);
@@ -301,13 +310,13 @@ extern "C" int ck_preview_jpeg_color(ck_handle_t *h, const ck_preview_params_t *
                                      int64_t cap_per_frame, int64_t *sizes, uint32_t *status) {
     ck_pv_color_src src;
     ck_jpeg_color_src js;
-    const int rc = staged_color_source(h, &src, &js);
+    const int rc = ck_pv_staged_source(h, &src, &js);
     return rc != CK_OK ? rc : ck_preview_color_run(h, pp, src, frames, n, out, true, cap_per_frame, sizes, status);
 }
 extern "C" int ck_preview_color(ck_handle_t *h, const ck_preview_params_t *pp, const int32_t *frames, int32_t n, uint8_t *out) {
     ck_pv_color_src src;
     ck_jpeg_color_src js;
-    const int rc = staged_color_source(h, &src, &js);
+    const int rc = ck_pv_staged_source(h, &src, &js);
     return rc != CK_OK ? rc : ck_preview_color_run(h, pp, src, frames, n, out, false, 0, nullptr, nullptr);
 }
 extern "C" int ck_preview_jpeg_color_device(ck_handle_t *h, const ck_preview_params_t *pp, const uint8_t *d_raw, int32_t stride,

@@ -183,6 +183,21 @@ def _bind(L):
     L.ck_board_params_default.restype = None
     L.ck_board_corners_last.argtypes = [vp, sb, sx, sq, vp, vp, vp]
     L.ck_board_corners_host.argtypes = [sb, sx, sq, _P(A.ImageU8), i32, vp, i32, vp, vp, vp, vp]
+    bb, bo = _P(A.BlobParams), _P(A.Blob)
+    L.ck_blob_params_default.argtypes = [bb]
+    L.ck_blob_params_default.restype = None
+    L.ck_blob_check.argtypes = [bb]
+    L.ck_blob_rgb_hsv.argtypes = [vp, C.c_int64, vp]
+    L.ck_blob_mask_host.argtypes = [bb, vp, i32, i32, i32, i32, i32, vp]
+    L.ck_blobs_host.argtypes = [bb, vp, i32, i32, i32, vp, i32, vp, vp]
+    L.ck_detect_blobs.argtypes = [vp, bb, vp, i32, vp, i32, vp, vp]
+    L.ck_detect_blobs_device.argtypes = [vp, bb, vp, i32, C.c_int64, rf, vp, i32, i32, vp, i32, vp, vp]
+    L.ck_detect_blobs_ingested.argtypes = [vp, i32, bb, vp, i32, vp, i32, vp, vp]
+    L.ck_blob_rgb.argtypes = [vp, vp, i32, vp]
+    L.ck_blob_rgb_device.argtypes = [vp, vp, i32, C.c_int64, rf, vp, i32, i32, vp]
+    L.ck_blob_mask.argtypes = [vp, bb, vp, i32, i32, i32, vp]
+    L.ck_blob_mask_device.argtypes = [vp, bb, vp, i32, C.c_int64, rf, vp, i32, i32, i32, i32, vp]
+    L.ck_blob_time.argtypes = [vp, bb, vp, i32, C.c_int64, rf, i32, i32, i32, _P(C.c_float)]
     L._ck_bound = True
     return L
 
@@ -746,6 +761,77 @@ class AprilTagDetector:
                                                                        C.byref(fmt), idx, n_frames, n, out)
         return self._preview_triples(call, "ck_preview_color_device", frames, n, width, height, quality, restart_rows, overlay)
 
+    # -- coloured game pieces (chalkydri_amd/blobs.py has the parameters and the host twin) ------------------------
+    def _frame_list(self, frames, n):
+        if frames is None:
+            if n is None:
+                raise ValueError("frames (indices into the source's frames) or n is required")
+            return None, None, int(n)
+        idx = np.ascontiguousarray(frames, np.int32).reshape(-1)
+        return idx, idx.ctypes.data, idx.size
+
+    def _blob_records(self, call, name, params, frames, n, cap):
+        """(records [n][n_classes][cap], counts [n][n_classes], status [n]) of one of the ck_detect_blobs entry points:
+        call(pp, idx, n, out, cap, counts, status) -> its return code."""
+        from .blobs import BLOB_DTYPE
+        idx, ip, n = self._frame_list(frames, n)
+        cap = params.max_targets if cap is None else int(cap)
+        out = np.zeros((n, params.n_classes, cap), BLOB_DTYPE)
+        counts, status = np.zeros((n, params.n_classes), np.int32), np.zeros(n, np.uint32)
+        buf = out if out.size else np.zeros(1, BLOB_DTYPE)
+        check(call(C.byref(params), ip, n, buf.ctypes.data, cap, counts.ctypes.data, status.ctypes.data), name)
+        return out, counts, status
+
+    def detect_blobs(self, params, frames=None, n=None, cap=None):
+        """Coloured targets of the frames behind the staged ones (the RAW frames of the last upload_raw / raw_luma, or the JPEG
+        frames of the last upload_jpeg(..., color=True)): blobs.blobs_host's triple, byte for byte, given blob_rgb's pixels.
+        frames: indices (one may repeat), or n for 0..n-1.  cap: records per frame and class (None: params.max_targets)."""
+        call = lambda pp, idx, n, out, cap, counts, status: self._L.ck_detect_blobs(self._h, pp, idx, n, out, cap, counts, status)
+        return self._blob_records(call, "ck_detect_blobs", params, frames, n, cap)
+
+    def detect_blobs_device(self, params, ptr, n_frames, stride, frame_pitch, code, orientation="none", frames=None, n=None, cap=None):
+        """detect_blobs of n_frames raw frames in device memory (laid out as upload_raw_device takes them)."""
+        fmt = raw_format(code, orientation)
+        call = lambda pp, idx, n, out, cap, counts, status: self._L.ck_detect_blobs_device(
+            self._h, pp, C.c_void_p(ptr), stride, frame_pitch, C.byref(fmt), idx, n_frames, n, out, cap, counts, status)
+        return self._blob_records(call, "ck_detect_blobs_device", params, frames, n_frames if n is None and frames is None else n, cap)
+
+    def blob_rgb(self, frames=None, n=None, device=None):
+        """[n][H][W][3] uint8: the RGB the classifier sees.  device: (ptr, n_frames, stride, frame_pitch, code, orientation) for raw
+        frames in device memory instead of the frames behind the staged ones."""
+        idx, ip, n = self._frame_list(frames, n)
+        out = np.empty((n, self.height, self.width, 3), np.uint8)
+        buf = out if n else np.empty(1, np.uint8)
+        if device is None:
+            check(self._L.ck_blob_rgb(self._h, ip, n, buf.ctypes.data), "ck_blob_rgb")
+        else:
+            ptr, n_frames, stride, pitch, code, orientation = device
+            fmt = raw_format(code, orientation)
+            check(self._L.ck_blob_rgb_device(self._h, C.c_void_p(ptr), stride, pitch, C.byref(fmt), ip, n_frames, n, buf.ctypes.data), "ck_blob_rgb_device")
+        return out
+
+    def blob_mask(self, params, cls=0, stage=1, frames=None, n=None, device=None):
+        """[n][H][ceil(W/32)] uint32: class cls's packed plane after the threshold (stage 0) or the morphology (1);
+        blobs.mask_host's bytes.  device: as blob_rgb's."""
+        idx, ip, n = self._frame_list(frames, n)
+        out = np.zeros((n, self.height, (self.width + 31) // 32), np.uint32)
+        buf = out if n else np.zeros(1, np.uint32)
+        if device is None:
+            check(self._L.ck_blob_mask(self._h, C.byref(params), ip, n, int(cls), int(stage), buf.ctypes.data), "ck_blob_mask")
+        else:
+            ptr, n_frames, stride, pitch, code, orientation = device
+            fmt = raw_format(code, orientation)
+            check(self._L.ck_blob_mask_device(self._h, C.byref(params), C.c_void_p(ptr), stride, pitch, C.byref(fmt), ip, n_frames, n, int(cls),
+                                              int(stage), buf.ctypes.data), "ck_blob_mask_device")
+        return out
+
+    def blob_time(self, params, ptr, n_frames, stride, frame_pitch, code, orientation="none", n=None, reps=10):
+        """ck_blob_time: mean milliseconds of the kernels of one detect_blobs_device call on frames 0..n-1."""
+        fmt, ms = raw_format(code, orientation), C.c_float()
+        check(self._L.ck_blob_time(self._h, C.byref(params), C.c_void_p(ptr), stride, frame_pitch, C.byref(fmt), n_frames,
+                                   n_frames if n is None else int(n), int(reps), C.byref(ms)), "ck_blob_time")
+        return ms.value
+
     def preview_luma(self, frames=None, n=None, width=640, height=480, quality=50, restart_rows=0, overlay=False):
         """[n][ph][pw] uint8: the scaled (+ overlaid) pixels the encoder is given."""
         pp, pw, ph, _, idx, n = self._preview_in(frames, n, width, height, quality, restart_rows, overlay)
@@ -880,6 +966,12 @@ class IngestRing:
     def preview_color(self, slot, frames=None, n=None, width=640, height=480, quality=50, restart_rows=0, overlay=False):
         call = lambda pp, idx, n, out: self._L.ck_preview_color_ingested(self._g, slot, C.byref(pp), idx, n, out)
         return self.det._preview_triples(call, "ck_preview_color_ingested", frames, n, width, height, quality, restart_rows, overlay)
+
+    def detect_blobs(self, slot, params, frames=None, n=None, cap=None):
+        """AprilTagDetector.detect_blobs on the raw frames of a submitted slot of a raw ring, or on the decoded frames of a slot of
+        a JPEG ring made with color=True (waits for its upload; the slot stays as it is)."""
+        call = lambda pp, idx, n, out, cap, counts, status: self._L.ck_detect_blobs_ingested(self._g, slot, pp, idx, n, out, cap, counts, status)
+        return self.det._blob_records(call, "ck_detect_blobs_ingested", params, frames, n, cap)
 
     def detect(self, slot, n, cap=64):
         dets = (A.Detection * (cap * n))()

@@ -113,11 +113,49 @@ class Handle {
         check(ck_upload_jpeg_color(h_, f.data(), (int32_t)f.size(), orientation, st.data()), "ck_upload_jpeg_color");
         return st;
     }
+    // Coloured game pieces (chalkydri_hip.h: ck_detect_blobs) of the frames behind the staged ones: out [n][n_classes][cap] records
+    // (the unwritten ones zero), counts [n][n_classes], status [n]; frames: indices into those frames, one may repeat
+    struct BlobResult { std::vector<ck_blob_t> records; std::vector<int32_t> counts; std::vector<uint32_t> status; int32_t cap = 0; };
+    BlobResult detect_blobs(const ck_blob_params_t &pp, const std::vector<int32_t> &frames, int32_t cap = -1) {
+        BlobResult r;
+        r.cap = cap < 0 ? pp.max_targets : cap;
+        const size_t planes = frames.size() * (size_t)(pp.n_classes > 0 ? pp.n_classes : 1);
+        r.records.assign(planes * (size_t)r.cap + 1, ck_blob_t{});
+        r.counts.assign(planes + 1, 0);
+        r.status.assign(frames.size() + 1, 0);
+        check(ck_detect_blobs(h_, &pp, frames.data(), (int32_t)frames.size(), r.records.data(), r.cap, r.counts.data(), r.status.data()),
+              "ck_detect_blobs");
+        r.records.resize(planes * (size_t)r.cap); r.counts.resize(planes); r.status.resize(frames.size());
+        return r;
+    }
 
   private:
     ck_config_t cfg_{};
     ck_handle_t *h_ = nullptr;
 };
+
+// ---- coloured game pieces (chalkydri_hip.h: ck_detect_blobs) ----------------------------------------------------
+// ck_blob_params_t with its defaults; class(i) is the i-th colour, add_class() appends one with the default bounds
+struct BlobParams {
+    ck_blob_params_t p;
+    BlobParams() { ck_blob_params_default(&p); }
+    ck_blob_class_t &cls(int i) { return p.cls[i]; }
+    ck_blob_class_t &add_class() {
+        if (p.n_classes >= CK_BLOB_MAX_CLASSES) throw Panic("at most CK_BLOB_MAX_CLASSES colour classes", CK_EINVAL);
+        return p.cls[p.n_classes++];
+    }
+    BlobParams &hsv(int i, int h_min, int h_max, int s_min, int s_max, int v_min, int v_max) {
+        ck_blob_class_t &c = p.cls[i];
+        c.h_min = h_min; c.h_max = h_max; c.s_min = s_min; c.s_max = s_max; c.v_min = v_min; c.v_max = v_max;
+        return *this;
+    }
+    BlobParams &camera(const ck_camera_t &cam) { p.cam = cam; p.has_camera = 1; return *this; }
+    BlobParams &mount(const ck_iso3_t &robot_to_cam) { p.robot_to_cam = robot_to_cam; p.has_mount = 1; return *this; }
+    void check_ok() const { check(ck_blob_check(&p), "ck_blob_check"); }
+};
+inline Handle::BlobResult detect_blobs(Handle &h, const BlobParams &pp, const std::vector<int32_t> &frames, int32_t cap = -1) {
+    return h.detect_blobs(pp.p, frames, cap);
+}
 
 // ck_raw_format_t from a fourcc ("YUYV", "RGB3", "BGR ", ...) and the reference's VideoOrientation serde name
 // (crates/chalkydri_core/src/config.rs:201-207): "none", "clockwise", "rotate-180", "counterclockwise"

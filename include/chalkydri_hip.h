@@ -1438,6 +1438,119 @@ int ck_board_corners_host(const ck_board_t *board, const ck_subpix_params_t *pp,
                           int32_t n, const ck_detection_t *dets, int32_t cap_per_frame, const int32_t *counts, double *uv_out,
                           uint8_t *tag_state, int32_t *n_tags);
 
+/* ---- coloured game pieces: HSV mask, connected components, targets ----------------------------------------------
+ * The second consumer of a camera's frames (the reference's `ml` slot, config.rs:88-102): objects of one saturated colour, found in
+ * the colour information that is on the device already — the sources of the colour preview (§4g, §4i).  All integer arithmetic.
+ *
+ * Pixels.  O[y][x] is the oriented full-resolution triple of ck_preview_color (width = W, height = H, overlay = 0).  The packed
+ * colour families (RGB3 BGR3 RGBA BGRA) give the classifier their own R, G, B bytes; the 4:2:2 families and the JPEG colour form
+ * give it libjpeg's ycc_rgb_convert of the triple, clamped to 0..255 (arithmetic shifts):
+ *   R = Y + ((91881 (Cr-128) + 32768) >> 16),  G = Y + ((-22554 (Cb-128) - 46802 (Cr-128) + 32768) >> 16),
+ *   B = Y + ((116130 (Cb-128) + 32768) >> 16).
+ * HSV, 8 bits, OpenCV's ranges.  V = max, m = min, d = V - m; S = V ? floor(255 d / V) : 0; H = 0 when d = 0, else with ties for
+ * the maximum going to R, then G, then B: hn = 30 (G-B) + (G < B ? 180 d : 0) | 30 (B-R) + 60 d | 30 (R-G) + 120 d and
+ * H = floor((2 hn + d) / (2 d)) mod 180.  The kernels compare by cross-multiplication and never divide.
+ * Class c holds a pixel when s_min <= S <= s_max, v_min <= V <= v_max and H in [h_min, h_max], or, when h_min > h_max (red wraps),
+ * in [h_min, 179] or [0, h_max].  Every class is a bit plane of its own: 32-bit words, bit x & 31 of word x >> 5 of row y, rows
+ * of ceil(W / 32) words, the bits at x >= W zero.
+ * Morphology: `erode` then `dilate` iterations of the 3x3 square, outside the frame background for both.
+ * Components: 8-connected.  Per component the area N, the inclusive box x0 y0 x1 y1, seed = the smallest y W + x, and the sums
+ * sx sy sxx sxy syy of its pixels' coordinates.  Filter, with bw = x1-x0+1 and bh = y1-y0+1: min_area <= N; N <= max_area (0: no
+ * upper bound); 1000 N >= min_fill_permille bw bh; min_aspect_permille bh <= 1000 bw <= max_aspect_permille bh (0: no upper bound).
+ * Order: area descending, then seed ascending.  counts[frame][class] is the number that pass; min(count, max_targets, cap) records
+ * are written (the rest of `out` is zero) and CK_BLOB_TRUNCATED is set in the frame's status when that is fewer.
+ * Capacity: at most max_components components of area >= min_area per frame and class.  More set CK_BLOB_OVERFLOW in the frame's
+ * status and make that class's count 0: no targets rather than an arbitrary subset. */
+#define CK_BLOB_MAX_CLASSES 4
+enum { CK_BLOB_HAS_BEARING = 1, CK_BLOB_HAS_GROUND = 2, CK_BLOB_AT_BORDER = 4 }; /* ck_blob_t.flags */
+enum { CK_BLOB_TRUNCATED = 1, CK_BLOB_OVERFLOW = 2 };                             /* status[frame] */
+typedef struct ck_blob_class {
+    int32_t h_min, h_max;          /* 0..179 each; h_min > h_max wraps through 0 */
+    int32_t s_min, s_max;          /* 0..255 */
+    int32_t v_min, v_max;          /* 0..255 */
+    int32_t min_area, max_area;    /* pixels, >= 0; max_area 0: no upper bound */
+    int32_t min_fill_permille;     /* >= 0: area against the box */
+    int32_t min_aspect_permille;   /* >= 0: box width against box height */
+    int32_t max_aspect_permille;   /* >= 0; 0: no upper bound */
+    int32_t pad;
+    double ground_z;               /* the plane the piece's lowest point rests on, robot frame, metres */
+} ck_blob_class_t;
+typedef struct ck_blob_params {
+    int32_t n_classes;             /* 1..CK_BLOB_MAX_CLASSES */
+    int32_t erode, dilate;         /* 0..4 iterations each */
+    int32_t max_targets;           /* >= 0: records written per frame and class, at most */
+    int32_t max_components;        /* >= 1, default 4096 */
+    int32_t has_camera;            /* cam is valid (a camera set with ck_set_camera comes first) */
+    int32_t has_mount;             /* robot_to_cam is valid */
+    int32_t pad;
+    ck_blob_class_t cls[CK_BLOB_MAX_CLASSES];
+    ck_camera_t cam;
+    ck_iso3_t robot_to_cam;        /* the solver's convention: cam from robot */
+    double max_range;              /* metres along the ray; beyond it there is no ground point */
+} ck_blob_params_t;
+/* One target.  Doubles in the library's pixel convention, pixel i covers [i, i+1). */
+typedef struct ck_blob {
+    int32_t class_id, flags;       /* CK_BLOB_HAS_BEARING | CK_BLOB_HAS_GROUND | CK_BLOB_AT_BORDER (the box touches the frame edge) */
+    int32_t area;
+    int32_t x0, y0, x1, y1;        /* inclusive */
+    int32_t seed;                  /* the smallest y W + x */
+    int64_t sx, sy, sxx, sxy, syy;
+    double cx, cy;                 /* sx / N + 0.5, sy / N + 0.5 */
+    double major, minor;           /* square roots of the eigenvalues of the covariance of the pixel centres */
+    double axis[2];                /* unit major axis, first non-zero component positive; (1, 0) when isotropic */
+    double bearing[3];             /* unit ray of (cx, cy) through the camera model; zeros without CK_BLOB_HAS_BEARING */
+    double ground[2];              /* robot-frame (x, y) where the ray through the box's bottom centre ((x0+x1+1)/2, y1+1) meets
+                                    * z = ground_z: valid with CK_BLOB_HAS_GROUND, that is with a mount, a ray that goes down, a
+                                    * camera above the plane and a range <= max_range; zeros otherwise */
+} ck_blob_t;
+/* One class, and in every class slot: any hue (0..179), s and v 64..255, min_area 16, no other filter, ground_z 0.  No morphology,
+ * max_targets 16, max_components 4096, no camera, no mount (the identity), max_range 20. */
+void ck_blob_params_default(ck_blob_params_t *pp);
+/* CK_EINVAL, in this order: a null pointer; n_classes outside 1..4; erode or dilate outside 0..4; max_targets < 0;
+ * max_components < 1; then per class in turn: a hue bound outside 0..179, an s or v bound outside 0..255, a negative area or
+ * permille value, a ground_z that is not finite; then, with has_camera, a camera ck_camera_check refuses; then, with has_mount, a
+ * mount that is not finite or whose quaternion is zero; max_range not finite or negative.  Host arithmetic, no device needed. */
+int ck_blob_check(const ck_blob_params_t *pp);
+/* rgb [n][3] -> hsv [n][3] by the definition above: for tuning UIs and tests.  Host arithmetic. */
+int ck_blob_rgb_hsv(const uint8_t *rgb, int64_t n, uint8_t *hsv_out);
+/* The host twin, pure C, one thread: rgb [n][H][W][3] is what ck_blob_rgb returns.  stage 0: class `cls`'s plane after the
+ * threshold, 1: after the morphology; bits_out [n][H][ceil(W/32)].  ck_blobs_host: out [n][n_classes][cap], counts
+ * [n][n_classes], status [n] (may be NULL); the camera is params.cam when has_camera.  CK_EINVAL: ck_blob_check's, a null
+ * pointer, W or H < 1, W H >= 2^31, n < 0, cap < 0, a class or stage out of range. */
+int ck_blob_mask_host(const ck_blob_params_t *pp, const uint8_t *rgb, int32_t W, int32_t H, int32_t n, int32_t cls, int32_t stage,
+                      uint32_t *bits_out);
+int ck_blobs_host(const ck_blob_params_t *pp, const uint8_t *rgb, int32_t W, int32_t H, int32_t n, ck_blob_t *out, int32_t cap,
+                  int32_t *counts, uint32_t *status);
+/* On the device, from the three sources of the colour preview with its validity rules and errors (ck_preview_color,
+ * ck_preview_color_device, ck_preview_color_ingested): the frames behind the staged ones, raw frames in the caller's device
+ * memory, a submitted slot of a raw or JPEG-colour ring.  frames [n]: indices into the source's frames (NULL: 0 .. n-1; an index may
+ * repeat).  out, counts and status (may be NULL) are host or device pointers.  The camera of the bearings is the handle's
+ * (ck_set_camera) if one is set, else params.cam when has_camera.  For any source the call returns the bytes of ck_blobs_host
+ * given ck_blob_rgb's pixels (and that camera).  Everything runs on the handle's stream in a workspace of its own, allocated by
+ * the first call and grown on demand: the staged frames, the detection workspace and the ring slots stay as they are.
+ * CK_EINVAL also for cap < 0; CK_ECAPACITY for n > max_batch. */
+int ck_detect_blobs(ck_handle_t *h, const ck_blob_params_t *pp, const int32_t *frames, int32_t n, ck_blob_t *out, int32_t cap,
+                    int32_t *counts, uint32_t *status);
+int ck_detect_blobs_device(ck_handle_t *h, const ck_blob_params_t *pp, const uint8_t *d_raw, int32_t stride, int64_t frame_pitch,
+                           const ck_raw_format_t *fmt, const int32_t *frames, int32_t n_frames, int32_t n, ck_blob_t *out,
+                           int32_t cap, int32_t *counts, uint32_t *status);
+int ck_detect_blobs_ingested(ck_ingest_t *ing, int32_t slot, const ck_blob_params_t *pp, const int32_t *frames, int32_t n,
+                             ck_blob_t *out, int32_t cap, int32_t *counts, uint32_t *status);
+/* The stages, for parity: the RGB the classifier sees, rgb_out [n][H][W][3], and one class's plane at a stage, bits_out
+ * [n][H][ceil(W/32)]; host or device pointers. */
+int ck_blob_rgb(ck_handle_t *h, const int32_t *frames, int32_t n, uint8_t *rgb_out);
+int ck_blob_rgb_device(ck_handle_t *h, const uint8_t *d_raw, int32_t stride, int64_t frame_pitch, const ck_raw_format_t *fmt,
+                       const int32_t *frames, int32_t n_frames, int32_t n, uint8_t *rgb_out);
+int ck_blob_mask(ck_handle_t *h, const ck_blob_params_t *pp, const int32_t *frames, int32_t n, int32_t cls, int32_t stage,
+                 uint32_t *bits_out);
+int ck_blob_mask_device(ck_handle_t *h, const ck_blob_params_t *pp, const uint8_t *d_raw, int32_t stride, int64_t frame_pitch,
+                        const ck_raw_format_t *fmt, const int32_t *frames, int32_t n_frames, int32_t n, int32_t cls, int32_t stage,
+                        uint32_t *bits_out);
+/* The kernels of ck_detect_blobs_device alone, `reps` times between two events on the handle's stream: *ms_out is the mean of one
+ * pass in milliseconds.  Nothing is copied out. */
+int ck_blob_time(ck_handle_t *h, const ck_blob_params_t *pp, const uint8_t *d_raw, int32_t stride, int64_t frame_pitch,
+                 const ck_raw_format_t *fmt, int32_t n_frames, int32_t n, int32_t reps, float *ms_out);
+
 /* fp64 conformance probe used by the parity tests: out[i] = op(a[i], b[i]) computed on the device with
  * the same flags as the kernels. op: 0 add, 1 mul, 2 div, 3 sqrt(a), 4 a*b+c style unfused (a*b)+a. */
 int ck_selftest_fp64(ck_handle_t *h, int32_t op, const double *a, const double *b, int32_t n,
