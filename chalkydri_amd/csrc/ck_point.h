@@ -15,7 +15,7 @@
 
 // A boundary point inside the pipeline, packed into 32 bits: [twin sign:1][twin:1][x:13][y:13][direction:2][sign:1] at bits 30, 29,
 // 28..16, 15..3, 2..1, 0 (bit 31 unused).  x/y are half-pixel coordinates, direction = which of the four forward neighbours
-// (1,0),(0,1),(-1,1),(1,1) the pair spans, sign = 1 when the gradient points along it.  k_emit writes the points of one
+// (1,0),(0,1),(-1,1),(1,1) the pair spans, sign = 1 when the gradient points along it.  k_emit2 writes the points of one
 // (tile, cluster) run next to each other; k_scatter moves whole runs to their place inside the cluster; k_fit unpacks.
 // A TWIN point (k_emit2) stands for two points of one cluster at the same (odd, odd) coordinates: its own, of direction (1,1) from
 // pixel (x, y), and the one of direction (-1,1) from pixel (x+1, y), whose sign is the twin sign bit.  A cluster then has two

@@ -275,7 +275,7 @@ __global__ __launch_bounds__(KNT) __attribute__((amdgpu_num_sgpr(80))) void k_ti
                                              int w, int h, int tiles_x, int tiles_y, int frame0, int n_frames, int xcd_map, int min_diff, int min_comp,
                                              uint8_t *__restrict__ thresh, ck_label_t *__restrict__ labels,
                                              ck_border_root *__restrict__ broots, uint32_t *__restrict__ tile_count,
-                                             uint16_t *__restrict__ ring, size_t ring_len, int stop_after, int sweeps) {
+                                             uint16_t *__restrict__ ring, size_t ring_len, int stop_after) {
     __shared__ __attribute__((aligned(16))) uint8_t lds[LDS_BYTES];
     // The waves' ROLES rotate with the workgroup: wave k of every workgroup sits on SIMD k, and the roles are not equally heavy (the
     // second min/max round, the pooled unions, the second round of ring pixels fall to the first waves) — with fixed roles SIMD 0
@@ -612,19 +612,9 @@ __global__ __launch_bounds__(KNT) __attribute__((amdgpu_num_sgpr(80))) void k_ti
     nruns = nwhite + misc[1];
     TPROF(4);
     if (stop_after == 4) return; // diagnostics (CK_TILE_STOP_AFTER)
-    // ---- P5b: one pointer-jumping sweep over the (static) adoption forest: a node's parent lies in an earlier pair (or earlier in
-    // its own), so the chains down a tag edge (one hop per pair, two where a lookup entry sits in between) are shortened before
-    // the finds of the next two phases walk them
+    // ---- P5b: (a pointer-jumping sweep over the adoption forest here was measured at 0, 1 and 2 passes and made no difference,
+    // because the nodes are pair components)
     tabled = nruns <= (uint32_t)LIST_CAP;
-    if (tabled)
-    for (int sweep = 0; sweep < sweeps; sweep++)
-    for (uint32_t j = (uint32_t)tid; j < nruns; j += KNT) {
-        const uint32_t pe = list_at(j) & 0xFFFu;
-        const uint32_t q = parent[pe];
-        const uint32_t g = parent[q & 0xFFFu]; // (a root's own entry has no parent to look at: the read is harmless, the result unused)
-        if (!(q & CK_ROOT) && !(g & CK_ROOT)) parent[pe] = (uint16_t)g;
-    }
-    if (sweeps) lds_barrier(); // (uniform)
     TPROF(5);
     if (stop_after == 5) return; // diagnostics (CK_TILE_STOP_AFTER)
     // ---- P5c: the pooled links, one lane per link, through the atomic union ------------------------------------------
@@ -1809,9 +1799,6 @@ __global__ __launch_bounds__(NT) void k_decimate(const uint8_t *__restrict__ src
 int ck_launch_threshold_segment(ck_handle *h, const ck_dev_image &img, int n, bool precomputed) {
     const int tiles = h->tiles_x * h->tiles_y;
     static const int stop_after = CK_KNOB("CK_TILE_STOP_AFTER", 99);
-    static const int sweeps = CK_KNOB("CK_TILE_SWEEPS", 0); // (pointer-jumping sweeps before the pooled unions: 0, 1 and 2 time the same since the nodes are pair components)
-    // frames dealt to XCDs (a frame's tiles share one L2): worth it once there are frames for all eight (CK_TILE_XCD=0/1 forces it)
-    static const int xcd_env = CK_KNOB("CK_TILE_XCD", -1);
     static const int fm_stop = CK_KNOB("CK_FMERGE_STOP_AFTER", 99);
     // CK_SEG_CHUNKS=k cuts the batch into k chunks of frames (multiples of 8: the XCD dealing) and runs chunk i's k_fmerge — one
     // workgroup per frame, bound by chains of dependent steps — on a side stream beside chunk i + 1's k_tile.  Measured on the
@@ -1855,16 +1842,16 @@ int ck_launch_threshold_segment(ck_handle *h, const ck_dev_image &img, int n, bo
     bool forked = false;
     for (int f0 = 0, ci = 0; f0 < n; f0 += per, ci++) {
         const int f1 = f0 + per < n ? f0 + per : n, cn = f1 - f0;
-        const int xcd_map = xcd_env >= 0 ? xcd_env : (cn >= 16 ? 1 : 0);
+        const int xcd_map = cn >= 16 ? 1 : 0; // frames dealt to XCDs (a frame's tiles share one L2): worth it once there are frames for all eight
         const unsigned grid = xcd_map ? (unsigned)(((cn + 7) / 8) * 8 * tiles) : (unsigned)(tiles * cn);
         if (precomputed)
             hipLaunchKernelGGL(k_tile<true>, dim3(grid), dim3(KNT), 0, h->stream, img.p, img.pitch, img.stride, h->qw, h->qh,
                                h->tiles_x, h->tiles_y, f0, f1, xcd_map, h->cfg.min_white_black_diff, h->cfg.min_component_px, h->d_thresh, h->d_labels,
-                               h->d_broots, h->d_tile_count, h->d_ring, h->ring_len, stop_after, sweeps);
+                               h->d_broots, h->d_tile_count, h->d_ring, h->ring_len, stop_after);
         else
             hipLaunchKernelGGL(k_tile<false>, dim3(grid), dim3(KNT), 0, h->stream, img.p, img.pitch, img.stride, h->qw, h->qh,
                                h->tiles_x, h->tiles_y, f0, f1, xcd_map, h->cfg.min_white_black_diff, h->cfg.min_component_px, h->d_thresh, h->d_labels,
-                               h->d_broots, h->d_tile_count, h->d_ring, h->ring_len, stop_after, sweeps);
+                               h->d_broots, h->d_tile_count, h->d_ring, h->ring_len, stop_after);
         if (stop_after < 98) continue; // (a k_tile cut short by the diagnostics knob leaves tile counts or ring entries unwritten: nothing for the merge to read)
         hipStream_t ms = h->stream;
         if (f1 < n) { // not the last chunk: its merge goes beside the next chunk's k_tile

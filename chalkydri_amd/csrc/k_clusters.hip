@@ -5,11 +5,11 @@
 // the hash-map-of-component-pairs formulation is the one CAT was converging on (stub `ClusterHash`, `u64hash_2`
 // and the 0.2*w*h cluster map at crates/chalkydri-apriltags/src/lib.rs:115-124,551-557).
 //
-//   k_emit     one workgroup per 16x64 pixel tile: resolves every pixel's component once into LDS (one extra
+//   k_emit2    one workgroup per 16x64 pixel tile: resolves every pixel's component once into LDS (one extra
 //              hop for ring-touching components, see ck_internal.h), aggregates the tile's points per cluster key
 //              in an LDS hash table, then makes ONE global insert + one add per (tile, key), writes the tile's points to
 //              the temp array as one contiguous run per key (4-byte packed points) and one run record per key.
-//              k_emit2 stores the two points a straight edge emits at one half-pixel (diagonal twins) as ONE word
+//              The two points a straight edge emits at one half-pixel (diagonal twins) are stored as ONE word
 //              (ck_point.h), so a cluster has a logical count (the oracle's) and a physical one (words stored).
 //   k_scan     one workgroup per frame: prefix sums over the frame's hash table -> cluster table + point offsets
 //              (clusters outside [min_cluster_pixels, max_cluster_points], by their logical count, are dropped here).
@@ -25,6 +25,7 @@ constexpr int ETW = 64, ETH = 16;         // emit tile
 constexpr int LW = ETW + 2, LH = ETH + 1; // staged region: one column each side, one row below
 constexpr int LHT = 512;                  // LDS hash slots (= 2 * NT: the reservation pass gives every thread two)
 constexpr uint32_t SKIP = 0xFFFFFFFFu;
+constexpr unsigned SCATTER_WGS = 32;      // k_scatter<64>: workgroups per frame
 
 __device__ __forceinline__ uint32_t key_hash(unsigned long long k) {
     uint32_t x = (uint32_t)((k >> 32) ^ k); // u64hash_2 of the reference's stub
@@ -47,242 +48,11 @@ struct EmitArgs {
 
 // A barrier that orders LDS traffic only: __syncthreads() carries a workgroup-scope fence, i.e. a wait for EVERY outstanding memory
 // operation — the barrier before the point writes would wait for the acknowledgement of the cluster-count adds nobody reads.
-// Nothing a workgroup of k_emit writes to global memory is read by it again.
+// Nothing a workgroup of k_emit2 writes to global memory is read by it again.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-__global__ __launch_bounds__(NT) void k_emit(EmitArgs a) {
-    __shared__ uint8_t sT[LH][LW + 2];
-    __shared__ uint32_t sR[LH][LW];
-    __shared__ unsigned long long sKey[LHT];
-    __shared__ uint32_t sCnt[LHT], sSlot[LHT], sTBase[LHT];
-    __shared__ uint32_t sWave[NT / 64 + 1], sRunW[NT / 64 + 1];
-    const int tid = threadIdx.x;
-    const int tiles = a.tiles_x * a.tiles_y;
-    const int frame = blockIdx.x / tiles, tile = blockIdx.x - frame * tiles;
-    const int ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
-    const int x0 = tx * ETW, y0 = ty * ETH;
-    const int w = a.w, h = a.h;
-    const size_t npix = (size_t)w * h;
-    const uint8_t *T = a.thresh + (size_t)frame * npix;
-    const ck_label_t *L = a.labels + (size_t)frame * npix;
-    const uint32_t *GR = a.groot + (size_t)frame * a.slots, *GS = a.gsize + (size_t)frame * a.slots;
-    const ck_stage_ws &ws = a.ws;
-    unsigned long long *gkeys = ws.d_ht_keys + (size_t)frame * ws.ht_size;
-    unsigned long long *gcount = ws.d_ht_count + (size_t)frame * ws.ht_size;
-    uint32_t *counters = ws.d_counters + (size_t)frame * CK_CNT_STRIDE;
-    ck_packed_point *tmp = ws.d_tmp + (size_t)frame * ws.ext_cap;
-    ck_run *runs = ws.d_runs + (size_t)frame * ws.run_cap;
-
-    for (int i = tid; i < LHT; i += NT) { sKey[i] = 0ull; sCnt[i] = 0; }
-    {   // staging: every thread's pixels go through the (up to three) dependent loads side by side, so a thread waits for
-        // three memory round trips, not three per pixel
-        constexpr int SPT = (LH * LW + NT - 1) / NT;
-        uint32_t lab[SPT], hop[SPT], csz[SPT], slot[SPT];
-        uint8_t tv[SPT];
-#pragma unroll
-        for (int q = 0; q < SPT; q++) {
-            const int i = tid + q * NT;
-            const int ly = i / LW, lx = i - ly * LW;
-            const int gy = y0 + ly, gx = x0 - 1 + lx;
-            tv[q] = 127; lab[q] = CK_LBL_NONE; slot[q] = 0;
-            if (i < LH * LW && gy < h && gx >= 0 && gx < w) {
-                const uint32_t p = (uint32_t)gy * (uint32_t)w + (uint32_t)gx;
-                tv[q] = T[p]; lab[q] = L[p];
-                slot[q] = ck_label_slot(lab[q], gx, gy, a.ccl_tiles_x);
-            }
-        }
-        // (a word with CK_LBL_SMALL: an interior component below min_component_px — or no component: CK_LBL_NONE has every bit set)
-#pragma unroll
-        for (int q = 0; q < SPT; q++) { // ring-touching components: the word holds a tile-local id; root and size come from the frame's tables
-            const bool two = tv[q] != 127 && !(lab[q] & CK_LBL_SMALL) && (lab[q] & CK_LBL_BORDER);
-            hop[q] = two ? GR[slot[q]] : CK_LBL_INVALID;
-            csz[q] = two ? GS[slot[q]] : 0u;
-        }
-#pragma unroll
-        for (int q = 0; q < SPT; q++) {
-            const int i = tid + q * NT;
-            if (i >= LH * LW) continue;
-            const int ly = i / LW, lx = i - ly * LW;
-            uint32_t r = SKIP;
-            if (tv[q] != 127 && !(lab[q] & CK_LBL_SMALL)) { // SMALL covers CK_LBL_NONE too
-                if (lab[q] & CK_LBL_BORDER) r = ((int)csz[q] < a.min_comp) ? SKIP : hop[q];
-                else r = ck_label_interior_root(lab[q], x0 - 1 + lx, y0 + ly, w);
-            }
-            sT[ly][lx] = tv[q];
-            sR[ly][lx] = r;
-        }
-    }
-    lds_barrier();
-    if (a.stop_after == 0) return;
-
-    const int lx = (tid & 63) + 1; // staged column of this thread's pixels
-    const int gx = x0 + (tid & 63);
-    const int row0 = (tid >> 6) * 4;
-    const int dxs[4] = {1, 0, -1, 1}, dys[4] = {0, 1, 1, 1};
-    const bool colok = gx >= 1 && gx <= w - 2;
-
-    // pass 1: count points per key in the LDS table; the add's return value is the point's rank inside (tile, key),
-    // kept in registers (slot << 16 | rank) so that the write pass neither probes nor counts again
-    constexpr uint32_t NONE = 0xFFFFFFFFu;
-    uint32_t cand[16];
-#pragma unroll
-    for (int q = 0; q < 16; q++) cand[q] = NONE;
-    if (colok) {
-#pragma unroll
-        for (int rr = 0; rr < 4; rr++) {
-            int ly = row0 + rr, gy = y0 + ly;
-            if (gy < 1 || gy > h - 2) continue;
-            int v0 = sT[ly][lx];
-            uint32_t r0 = sR[ly][lx];
-            if (r0 == SKIP) continue;
-            // the (up to four) points of a pixel often share their key — the three neighbours below are side by side, so when
-            // they are white they are one component: one slot search and ONE add per distinct key, the first point of the key
-            // doing it for the others (fewer LDS atomics, and fewer lanes on one address in each)
-            uint32_t r1v[4];
-            bool ok[4];
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const int v1 = sT[ly + dys[k]][lx + dxs[k]];
-                r1v[k] = sR[ly + dys[k]][lx + dxs[k]];
-                ok[k] = (v0 + v1 == 255) && r1v[k] != SKIP;
-            }
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                bool leader = ok[k];
-#pragma unroll
-                for (int j = 0; j < k; j++) leader = leader && !(ok[j] && r1v[j] == r1v[k]);
-                if (!leader) continue;
-                uint32_t n = 1;
-#pragma unroll
-                for (int j = k + 1; j < 4; j++) n += (ok[j] && r1v[j] == r1v[k]) ? 1u : 0u;
-                const uint32_t r1 = r1v[k];
-                unsigned long long key = r0 < r1 ? ((unsigned long long)r0 << 32) | r1 : ((unsigned long long)r1 << 32) | r0;
-                uint32_t s = key_hash(key) & (LHT - 1);
-                bool placed = false;
-                for (int probe = 0; probe < LHT; probe++) {
-                    // most points meet their key already in place: a plain read (lanes with one address are served together)
-                    // finds that out, and only a slot seen empty costs a compare-and-swap (same-address lanes one by one)
-                    __asm__ volatile("" ::: "memory");
-                    unsigned long long prev = sKey[s];
-                    if (prev == 0ull) prev = atomicCAS(&sKey[s], 0ull, key);
-                    if (prev == 0ull || prev == key) {
-                        uint32_t c = (s << 16) | atomicAdd(&sCnt[s], n);
-                        cand[rr * 4 + k] = c;
-#pragma unroll
-                        for (int j = k + 1; j < 4; j++)
-                            if (ok[j] && r1v[j] == r1) cand[rr * 4 + j] = ++c;
-                        placed = true;
-                        break;
-                    }
-                    s = (s + 1) & (LHT - 1);
-                }
-                if (!placed) atomicOr(&counters[CK_CNT_STATUS], (uint32_t)CK_FRAME_CLUSTERS_OVERFLOW);
-            }
-        }
-    }
-    lds_barrier();
-    if (a.stop_after == 1) return;
-
-    // pass 2: one reservation of temp space and of run records per tile (exclusive scans of the per-key counts / used
-    // slots), and per (tile, key) one global insert (waited for: it yields the slot) + one add to the cluster's point
-    // count that nobody waits for.
-    const unsigned long long k0 = sKey[2 * tid], k1 = sKey[2 * tid + 1];
-    const uint32_t c0 = k0 ? sCnt[2 * tid] : 0u, c1 = k1 ? sCnt[2 * tid + 1] : 0u;
-    uint32_t found0 = SKIP, found1 = SKIP, ridx0;
-    {
-        const uint32_t incl = wave_scan_u32(c0 + c1);
-        const unsigned long long b0 = __ballot(k0 != 0ull), b1 = __ballot(k1 != 0ull);
-        const unsigned long long below = (1ull << (tid & 63)) - 1ull;
-        ridx0 = (uint32_t)(__popcll(b0 & below) + __popcll(b1 & below)); // rank of this thread's first used slot in its wave
-        if ((tid & 63) == 63) sWave[tid >> 6] = incl;
-        if ((tid & 63) == 0) sRunW[tid >> 6] = (uint32_t)(__popcll(b0) + __popcll(b1));
-        lds_barrier();
-        uint32_t before = 0, total = 0, rbefore = 0, rtotal = 0;
-#pragma unroll
-        for (int wv = 0; wv < NT / 64; wv++) {
-            uint32_t t = sWave[wv], r = sRunW[wv];
-            if (wv < (tid >> 6)) { before += t; rbefore += r; }
-            total += t; rtotal += r;
-        }
-        ridx0 += rbefore;
-        lds_barrier(); // every thread has read the per-wave totals before thread 0 reuses the arrays' last entries
-        if (tid == 0) {
-            sWave[NT / 64] = total ? atomicAdd(&counters[CK_CNT_TMP], total) : 0u;
-            sRunW[NT / 64] = rtotal ? atomicAdd(&counters[CK_CNT_RUNS], rtotal) : 0u;
-        }
-        const uint32_t excl = before + incl - (c0 + c1);
-        sTBase[2 * tid] = excl; sTBase[2 * tid + 1] = excl + c0;
-        {   // both first probes of the frame table in flight together; only a probe that met another key walks on
-            const uint32_t hm = (uint32_t)(ws.ht_size - 1);
-            const uint32_t g0 = key_hash(k0) & hm, g1 = key_hash(k1) & hm;
-            const unsigned long long p0 = k0 ? atomicCAS(&gkeys[g0], 0ull, k0) : 0ull;
-            const unsigned long long p1 = k1 ? atomicCAS(&gkeys[g1], 0ull, k1) : 0ull;
-#pragma unroll
-            for (int q = 0; q < 2; q++) {
-                const unsigned long long key = q ? k1 : k0, pv = q ? p1 : p0;
-                if (key == 0ull) continue;
-                uint32_t g = q ? g1 : g0, found = SKIP;
-                if (pv == 0ull || pv == key) found = g;
-                else {
-                    for (int probe = 1; probe < ws.ht_size; probe++) {
-                        g = (g + 1) & hm;
-                        unsigned long long prev = atomicCAS(&gkeys[g], 0ull, key);
-                        if (prev == 0ull || prev == key) { found = g; break; }
-                    }
-                }
-                if (found == SKIP) atomicOr(&counters[CK_CNT_STATUS], (uint32_t)CK_FRAME_CLUSTERS_OVERFLOW);
-                sSlot[2 * tid + q] = found;
-                if (q) found1 = found; else found0 = found;
-            }
-        }
-        // (result unused: nothing waits for these.  No twins here: a cluster's logical and physical counts are the same number)
-        if (found0 != SKIP) atomicAdd(&gcount[found0], ((unsigned long long)c0 << 32) | c0);
-        if (found1 != SKIP) atomicAdd(&gcount[found1], ((unsigned long long)c1 << 32) | c1);
-    }
-    lds_barrier();
-    if (a.stop_after == 2) return;
-
-    // pass 3: write the points
-    const uint32_t tile_base = sWave[NT / 64];
-    if (colok) {
-#pragma unroll
-        for (int rr = 0; rr < 4; rr++) {
-            int ly = row0 + rr, gy = y0 + ly;
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const uint32_t cd = cand[rr * 4 + k];
-                if (cd == NONE) continue;
-                const uint32_t s = cd >> 16, lr = cd & 0xFFFFu;
-                uint32_t slot = sSlot[s];
-                if (slot == SKIP) continue;
-                uint32_t ti = tile_base + sTBase[s] + lr;
-                if (ti >= (uint32_t)ws.point_cap) { atomicOr(&counters[CK_CNT_STATUS], (uint32_t)CK_FRAME_POINTS_OVERFLOW); continue; }
-                int v0 = sT[ly][lx], v1 = sT[ly + dys[k]][lx + dxs[k]];
-                tmp[ti] = ((uint32_t)(2 * gx + dxs[k]) << 16) | ((uint32_t)(2 * gy + dys[k]) << 3) | ((uint32_t)k << 1) | (v1 > v0 ? 1u : 0u);
-            }
-        }
-    }
-    // run records (their place inside the cluster is decided by k_scatter)
-    {
-        uint32_t ri = sRunW[NT / 64] + ridx0;
-#pragma unroll
-        for (int q = 0; q < 2; q++) {
-            if ((q ? k1 : k0) == 0ull) continue;
-            const uint32_t found = q ? found1 : found0;
-            // (a key the frame's table had no room for still owns its place in the run list: it gets an empty record — left
-            // as it was, k_scatter would follow whatever an earlier call had written there)
-            if (ri < (uint32_t)ws.run_cap) {
-                ck_run r;
-                r.slot = found != SKIP ? found : 0u; r.base = 0; r.tmp_start = tile_base + sTBase[2 * tid + q];
-                r.count = found != SKIP ? (q ? c1 : c0) : 0u;
-                runs[ri] = r;
-            } else if (found != SKIP) atomicOr(&counters[CK_CNT_STATUS], (uint32_t)CK_FRAME_CLUSTERS_OVERFLOW);
-            ri++;
-        }
-    }
-}
-
 // ---- k_emit2 (round 4): the same function as k_emit, re-cut around what the counters said about it ---------------------------------
+// (k_emit is the round-1..3 kernel, since removed: git history holds it.)
 // k_emit on the bench batch (rocprofv3 --pmc): 1 226 vector, 1 128 scalar and 171 LDS instructions per wave; by phase (stop-after knob)
 // staging 0.5 ms · count pass 1.16 · reservation 0.44 · point writes 0.35.  Every pixel of the count pass re-read its centre and four
 // neighbours (ten LDS reads: threshold byte and root each) before it probed.  Here a staged pixel is ONE word — the frame pixel of its
@@ -828,24 +598,16 @@ int ck_launch_clusters(ck_handle *h, int n) {
     { static const int stop_after = CK_KNOB("CK_EMIT_STOP_AFTER", 99); a.stop_after = stop_after; }
     { static const int twins = CK_KNOB("CK_EMIT_TWINS", 1); a.twins = twins; } // (diagnostics: 0 = every point on its own, for A/B)
     { static const int stage4 = CK_KNOB("CK_EMIT_STAGE4", 1); a.stage4 = stage4; } // (diagnostics: 0 = every pixel staged on its own, for A/B)
-    static const int emit_v = CK_KNOB("CK_EMIT_V", 2);       // (diagnostics: 1 = the round-1..3 kernel, for A/B)
-    static const int emit_xcd = CK_KNOB("CK_EMIT_XCD", -1);  // (diagnostics: frames dealt to XCDs 0 / 1; default: batches of 16 frames and more)
-    if (emit_v == 1) hipLaunchKernelGGL(k_emit, dim3((unsigned)(a.tiles_x * a.tiles_y * n)), dim3(NT), 0, h->stream, a);
-    else {
-        const int xcd_map = emit_xcd >= 0 ? emit_xcd : (n >= 16 ? 1 : 0);
-        const unsigned grid = xcd_map ? (unsigned)(((n + 7) / 8) * 8 * a.tiles_x * a.tiles_y) : (unsigned)(a.tiles_x * a.tiles_y * n);
-        // groups of four pixels: rows, frames and the buffers themselves start at multiples of four pixels
-        const bool g4 = a.stage4 && ck_es_group_path(a.w) && ((uintptr_t)a.thresh & 3u) == 0 && ((uintptr_t)a.labels & 7u) == 0;
-        if (g4) hipLaunchKernelGGL(k_emit2<true>, dim3(grid), dim3(NT), 0, h->stream, a, xcd_map, n);
-        else hipLaunchKernelGGL(k_emit2<false>, dim3(grid), dim3(NT), 0, h->stream, a, xcd_map, n);
-    }
+    const int xcd_map = n >= 16 ? 1 : 0; // frames dealt to XCDs: batches of 16 frames and more
+    const unsigned grid = xcd_map ? (unsigned)(((n + 7) / 8) * 8 * a.tiles_x * a.tiles_y) : (unsigned)(a.tiles_x * a.tiles_y * n);
+    // groups of four pixels: rows, frames and the buffers themselves start at multiples of four pixels
+    const bool g4 = a.stage4 && ck_es_group_path(a.w) && ((uintptr_t)a.thresh & 3u) == 0 && ((uintptr_t)a.labels & 7u) == 0;
+    if (g4) hipLaunchKernelGGL(k_emit2<true>, dim3(grid), dim3(NT), 0, h->stream, a, xcd_map, n);
+    else hipLaunchKernelGGL(k_emit2<false>, dim3(grid), dim3(NT), 0, h->stream, a, xcd_map, n);
     int min_cluster = h->cfg.min_cluster_pixels < 24 ? 24 : h->cfg.min_cluster_pixels;
     hipLaunchKernelGGL(k_scan, dim3((unsigned)n), dim3(SNT), 0, h->stream, ws, min_cluster, ws.max_cluster_points);
     if (n <= 4) hipLaunchKernelGGL(k_scatter<8>, dim3(256u, (unsigned)n), dim3(NT), 0, h->stream, ws);
-    else {
-        static const unsigned sc_wgs = (unsigned)CK_KNOB("CK_SCATTER_WGS", 32); // (diagnostics: workgroups per frame)
-        hipLaunchKernelGGL(k_scatter<64>, dim3(sc_wgs, (unsigned)n), dim3(NT), 0, h->stream, ws);
-    }
+    else hipLaunchKernelGGL(k_scatter<64>, dim3(SCATTER_WGS, (unsigned)n), dim3(NT), 0, h->stream, ws);
     CK_HIP(hipGetLastError());
     return CK_OK;
 }

@@ -42,11 +42,10 @@ struct FitArgs {
     double cos_critical, max_mse;
     ck_stage_ws ws;
     int stop_after;         // diagnostics (CK_FIT_STOP_AFTER): end every cluster after phase k; 99 = run everything
-    int guided;             // chunks handed out by the work counter shrink towards the end of the list
-    int list_cap;           // capacity of one class list
     const uint32_t *list;   // work list of this size class: frame << 20 | cluster index
     const uint32_t *list_count;
     uint32_t *head;         // dequeue counter
+    int list_cap;           // capacity of one class list
 };
 
 struct M6 { long long Mx, My, Mxx, Mxy, Myy, W; };
@@ -645,7 +644,7 @@ struct ChunkQueue {
             BAR::sync();
             base = *word;
             len = dq_next;
-            if (a.guided) dq_next = dq_guided(n_work, base, dq);
+            dq_next = dq_guided(n_work, base, dq);
         }
         first = false;
         return base < n_work;
@@ -1165,7 +1164,7 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(WPS, 8))) v
             chunk_base = sWork;
             if (chunk_base >= n_work) break;
             chunk_left = chunk_len = dq_next;
-            if (a.guided) dq_next = dq_guided(n_work, chunk_base, DQ);
+            dq_next = dq_guided(n_work, chunk_base, DQ);
         }
         const uint32_t work = chunk_base + (chunk_len - chunk_left);
         chunk_left--;
@@ -2380,6 +2379,7 @@ __global__ __launch_bounds__(1024) void k_classify(ck_stage_ws ws, int n, uint32
 // The persistent grids are sized for the 256 CUs of the device this library is written for (MI355X): a class's grid is this many
 // times its workgroups per CU.
 constexpr int FIT_CUS = 256;
+constexpr int TAIL_WGS = 16; // k_tail: workgroups (of one wave) per CU
 // Template parameters and grid of k_fit and of k_seq per size class (ck_internal.h: CK_FIT_CLASSES), indexed by class.  WPS: waves
 // per EU the kernel's registers are budgeted for.  Chunk sizes (CH): 512 points for the multi-wave classes (fewer scans and barriers
 // per point, 9 % less halo work); their LDS then sits at the occupancy steps — 52.9 KB (3 workgroups/CU), 80.5 KB (2/CU), ≈ 124 KB and
@@ -2426,19 +2426,18 @@ constexpr FitMode FIT_TAILS_ASIDE = {true, {0, 0, 0, 1, 1, 1, 0, 0}, 8, {4, 5, 3
 // ... and a batch in a process whose later stages already run on two streams (CK_STREAMS=2) keeps everything on the handle's stream
 constexpr FitMode FIT_SINGLE_LANE = {false, {0, 0, 0, 0, 0, 0, 0, 0}, 8, {7, 0, 6, 1, 2, 3, 4, 5}};
 
-// class C's kernel on stream st: k_seq for the split fit (flat), k_fit otherwise; wgs: workgroups per CU when not the plan's (0)
+// class C's kernel on stream st: k_seq for the split fit (flat), k_fit otherwise
 template <int C>
-void launch_class(bool flat, int wgs, hipStream_t st, const FitArgs &a) {
+void launch_class(bool flat, hipStream_t st, const FitArgs &a) {
     constexpr FitClass p = FIT_CLASS[C];
     if (p.gk && !a.ws.d_hscratch) return;
-    if (!wgs) wgs = flat ? p.seq_wgs : p.fit_wgs;
-    const unsigned grid = p.gk ? (unsigned)CK_HUGE_WGS : (unsigned)(FIT_CUS * wgs);
+    const unsigned grid = p.gk ? (unsigned)CK_HUGE_WGS : (unsigned)(FIT_CUS * (flat ? p.seq_wgs : p.fit_wgs));
     if (flat) hipLaunchKernelGGL((k_seq<p.nth, p.cap, p.mlds, p.seq_wps, p.gk>), dim3(grid), dim3(p.nth), 0, st, a);
     else hipLaunchKernelGGL((k_fit<p.nth, p.cap, p.ch, p.mlds, p.fit_wps, p.gk>), dim3(grid), dim3(p.nth), 0, st, a);
 }
 template <int... C>
-void launch_class_of(std::integer_sequence<int, C...>, int c, bool flat, int wgs, hipStream_t st, const FitArgs &a) {
-    ((c == C ? launch_class<C>(flat, wgs, st, a) : (void)0), ...);
+void launch_class_of(std::integer_sequence<int, C...>, int c, bool flat, hipStream_t st, const FitArgs &a) {
+    ((c == C ? launch_class<C>(flat, st, a) : (void)0), ...);
 }
 } // namespace
 
@@ -2471,21 +2470,15 @@ int ck_launch_fit_quads(ck_handle *h, const ck_dev_image &qimg, const ck_dev_ima
     ck_stage_ws &ws = h->ws;
     if (n > 4095 || ws.cluster_cap > (1 << 20)) return CK_EINVAL;
     // The knobs of the diagnostics build (ck_internal.h: CK_KNOB; in the product build each IS its default), read once, all here
-    // but the two that are read per call (below)
+    // but the three that are read per call (below)
     static const int k_split = CK_KNOB("CK_FIT_SPLIT", 3); // bit 0 = 513..1024 points have their own class, bit 1 = up to 256 points have
-    static const int k_par = CK_KNOB("CK_FIT_PAR", 0);     // the classes side by side whatever the call's size
     static const int k_flat = CK_KNOB("CK_FIT_FLAT", 1);   // the split fit: 0 never, 2 always, 1: for the calls it pays for (below)
-    static const int k_wimg_aside = CK_KNOB("CK_FIT_WIMG_ASIDE", 1); // the split fit's weight image beside its first kernels (0: before them)
-    static const int k_tails_aside = CK_KNOB("CK_FIT_TAILS_ASIDE", 1) && ck_streams_wanted() < 2; // FIT_TAILS_ASIDE for a batch
     static const int k_skip = CK_KNOB("CK_FIT_SKIP", 0);   // bit c set = class c is not launched
-    static const int k_wgs[2][CK_FIT_CLASSES] = {          // workgroups per CU of [k_fit, k_seq][class]; 0 = the plan's
-        {CK_KNOB("CK_FIT_S_WGS", 0), 0, 0, 0, 0, 0, 0, 0},
-        {CK_KNOB("CK_SEQ_WGS0", 0), 0, 0, 0, 0, 0, CK_KNOB("CK_SEQ_WGS6", 0), CK_KNOB("CK_SEQ_WGS7", 0)}};
-    static const int k_chunk_wgs = CK_KNOB("CK_CHUNK_WGS", 64), k_tail_wgs = CK_KNOB("CK_TAIL_WGS", 16); // k_chunk workgroups per CU over the batch, k_tail's per CU
+    static const int k_chunk_wgs = CK_KNOB("CK_CHUNK_WGS", 64); // k_chunk workgroups per CU over the batch
     // ---- policy: which form of the fit, on which lanes --------------------------------------------------------------------------
     // (measured at 1280x800: side by side wins up to 16 frames at quad_decimate 1, up to 32 at 2, where the clusters are fewer)
-    const bool side_by_side = n <= (h->cfg.quad_decimate > 1 ? 2 * CK_FIT_PARALLEL_MAX_FRAMES : CK_FIT_PARALLEL_MAX_FRAMES) || k_par;
-    const bool tails_aside = !side_by_side && k_tails_aside;
+    const bool side_by_side = n <= (h->cfg.quad_decimate > 1 ? 2 * CK_FIT_PARALLEL_MAX_FRAMES : CK_FIT_PARALLEL_MAX_FRAMES);
+    const bool tails_aside = !side_by_side && ck_streams_wanted() < 2;
     const FitMode &mode = side_by_side ? FIT_SIDE_BY_SIDE : (tails_aside ? FIT_TAILS_ASIDE : FIT_SINGLE_LANE);
     // The split fit (k_seq per class -> k_chunk over all positions -> k_tail over all clusters): for calls that run their classes one
     // after the other AND bring enough pixels — its three stages each ramp a persistent grid up and down, which a quarter-size batch
@@ -2494,7 +2487,7 @@ int ck_launch_fit_quads(ck_handle *h, const ck_dev_image &qimg, const ck_dev_ima
     const bool flat = k_flat >= 2 || (k_flat == 1 && !side_by_side && (size_t)n * (size_t)h->qw * (size_t)h->qh >= ((size_t)100 << 20));
     // The split fit needs the weights in its second kernel only: the weight image (a streaming kernel, bound by HBM) then runs on the
     // second side stream beside the first kernels (bound by their sort) instead of before them
-    const bool wimg_aside = flat && tails_aside && k_wimg_aside;
+    const bool wimg_aside = flat && tails_aside;
     hipStream_t lanes[1 + CK_FIT_SIDE_STREAMS] = {h->stream, h->fit_stream[0], h->fit_stream[1]};
 
     // work lists, their counts and the dequeue heads live in the fit scratch; counts and heads were zeroed with the cluster
@@ -2518,10 +2511,6 @@ int ck_launch_fit_quads(ck_handle *h, const ck_dev_image &qimg, const ck_dev_ima
     if (a.min_tag_width < 3) a.min_tag_width = 3;
     a.ws = ws; a.list_cap = list_cap;
     a.stop_after = CK_KNOB("CK_FIT_STOP_AFTER", 99); // (read per call)
-    a.guided = CK_KNOB("CK_FIT_GUIDED", 1);          // (read per call)
-    // (measurements of the selection with CK_FIT_STOP_AFTER <= 5: a cut above every cluster's count skips the threshold search, and
-    // every cluster with more than MAXSEL maxima then leaves after the selection)
-    a.max_nmaxima = CK_KNOB("CK_FIT_NMAXIMA", a.max_nmaxima);
 #ifdef CK_DIAG
     {   // the frames' position counters start at CK_EXT_BASE (read per call; clamped to the room stage_caps adds for it in this build):
         // on the handle's stream, behind k_clear's zero and before the first k_seq of any lane
@@ -2548,7 +2537,7 @@ int ck_launch_fit_quads(ck_handle *h, const ck_dev_image &qimg, const ck_dev_ima
         const int c = mode.order[i];
         if ((k_skip >> c) & 1) continue;
         use_list(c);
-        launch_class_of(std::make_integer_sequence<int, CK_FIT_CLASSES>{}, c, flat, k_wgs[flat][c], lanes[mode.lane[c]], a);
+        launch_class_of(std::make_integer_sequence<int, CK_FIT_CLASSES>{}, c, flat, lanes[mode.lane[c]], a);
     }
     if (mode.forks)
         for (int s = 0; s < CK_FIT_SIDE_STREAMS; s++) {
@@ -2572,7 +2561,7 @@ int ck_launch_fit_quads(ck_handle *h, const ck_dev_image &qimg, const ck_dev_ima
         if (a.stop_after > 3) hipLaunchKernelGGL(k_chunk, dim3(gx, (unsigned)n), dim3(256), 0, h->stream, ws, h->qw, h->qh);
 #endif
         use_list(CK_FIT_CLASSES); // every cluster of the batch
-        hipLaunchKernelGGL(k_tail, dim3((unsigned)(FIT_CUS * k_tail_wgs)), dim3(64), 0, h->stream, a);
+        hipLaunchKernelGGL(k_tail, dim3((unsigned)(FIT_CUS * TAIL_WGS)), dim3(64), 0, h->stream, a);
     }
     CK_HIP(hipGetLastError());
     return CK_OK;
