@@ -97,7 +97,7 @@ struct ck_stage_ws {
     ck_packed_point *d_points; // [n][ext_cap] (point_cap used) points grouped by cluster
     // split quad fit: extended point sequences and what k_chunk leaves for k_tail.  d_tmp and d_points are dead by then and carry
     // the two largest arrays (same frame pitch, so a frame's bytes never overlap another frame's)
-    int ext_cap;               // positions per frame: point_cap + CK_EXT_HALO * cluster_cap (+ 2 * CK_SPAN in the diagnostics build: CK_EXT_BASE), rounded up to a multiple of CK_SPAN; the frame pitch of d_tmp / d_points
+    int ext_cap;               // positions per frame: point_cap + CK_EXT_HALO * cluster_cap (+ ck_ext_room()), rounded up to a multiple of CK_SPAN; the frame pitch of d_tmp / d_points
     uint32_t *d_ext_xy;        // = d_tmp: [n][ext_cap] x << 13 | y (half-pixel) | window half-width << 26
     uint16_t *d_ext_w;         // [n][ext_cap] gradient weight
     double *d_maxval;          // = d_points: [n][ext_cap / CK_SPAN][CK_SPAN / 2] smoothed errors at the maxima of a span, in position order
@@ -265,21 +265,8 @@ int ck_hip_failed(hipError_t e, const char *call, const char *file, int line, bo
 #define CK_HIP(call) CK_HIP_(call, false)
 #define CK_HIP_ALLOC(call) CK_HIP_(call, true)
 
-// Diagnostic knobs (CK_TILE_STOP_AFTER, CK_FIT_SKIP, CK_FMERGE_CAP, ...: kernels cut short, classes skipped, paths forced, launch
-// geometry varied; CK_EXT_BASE: the first position of the split fit's extended sequences in every frame of a call, 0 .. 2 * CK_SPAN,
-// for which that build's frames are 2 * CK_SPAN positions longer) exist only in the -DCK_DIAG build (`make diag` -> chalkydri_amd/lib/diag/libchalkydri_hip.so), which the
-// measurement scripts under tools/ and the path-forcing tests load.  In the product build every knob IS its default: the macro
-// drops the name, so neither the getenv call nor the string is in the library a host links — the environment cannot change what
-// the drop-in returns.  The product library reads exactly two variables: CK_POISON (allocation fill / guard pages, below) and
-// CK_STREAMS (ck_stages.hip: the post-segmentation stages on two streams; the bytes do not depend on it).
-#ifdef CK_DIAG
-static inline int ck_knob_(const char *name, int dflt, int base) { const char *e = getenv(name); return e ? (int)strtol(e, nullptr, base) : dflt; }
-#define CK_KNOB(name, dflt) ck_knob_(name, dflt, 10)
-#define CK_KNOB0(name, dflt) ck_knob_(name, dflt, 0)   /* hexadecimal masks allowed */
-#else
-#define CK_KNOB(name, dflt) (dflt)
-#define CK_KNOB0(name, dflt) (dflt)
-#endif
+// The diagnostic knobs (ck_knob(CK_KNOB_...): values only the diagnostics library takes from the environment) have one table: ck_knobs.h.
+#include "ck_knobs.h"
 int ck_streams_wanted(); // ck_stages.hip: CK_STREAMS (1 or 2), read once
 
 // The quad stages run on a buffer of their own (d_qframes) when the frame is decimated or filtered; otherwise on the frame itself.
@@ -381,6 +368,15 @@ int ck_make_quad_image(ck_handle *h, const ck_dev_image &img, int n);
 int ck_launch_clusters(ck_handle *h, int n);
 // quad fit (+ edge refinement) of every cluster; qframes = image the clusters came from, frames = full resolution
 int ck_launch_fit_quads(ck_handle *h, const ck_dev_image &qimg, const ck_dev_image &img, int n);
+// k_chunk.hip, the one unit whose device code differs in the diagnostics library (ck_knobs.h): the split fit's middle kernel
+// k_chunk over the n frames' positions on the handle's stream, `wgs` workgroups over the batch at most (never fewer than 8 a frame, never more
+// than a frame has spans).  *fit_stop is the quad fit's stop_after: at 3 and below nothing is launched; a k_chunk that the
+// diagnostics library cuts short (CK_CHUNK_STOP_AFTER) lowers it to 4, where k_tail ends every cluster before it reads k_chunk's lists
+void ck_launch_chunk(ck_handle *h, int n, int wgs, int *fit_stop);
+// diagnostics library: the n frames' position counters start at CK_EXT_BASE, on the handle's stream.  Product: nothing
+void ck_launch_ext_base(ck_handle *h, int n);
+// positions a frame's extended sequences are longer by for CK_EXT_BASE: 2 * CK_SPAN in the diagnostics library, 0 in the product
+int ck_ext_room();
 int ck_launch_decode(ck_handle *h, const ck_dev_image &img, int n);
 // whole pipeline on device-resident frames (16-byte aligned rows): detections to the host / pose records
 int ck_detect_frames(ck_handle *h, const ck_dev_image &img, int n, ck_detection_t *dets, int cap, int32_t *counts, uint32_t *status);

@@ -136,9 +136,7 @@ static int stage_caps(ck_handle *h) {
     if (cfg.max_nmaxima < 4 || cfg.max_nmaxima > 12) return CK_EINVAL;
     {   // frame pitch of the point arrays = positions of the split fit's extended sequences (ck_internal.h)
         size_t e = (size_t)ws.point_cap + (size_t)CK_EXT_HALO * ws.cluster_cap;
-#ifdef CK_DIAG
-        e += 2 * CK_SPAN; // room for CK_EXT_BASE (k_quads.hip: ck_launch_fit_quads), the diagnostics build's shift of a frame's sequences
-#endif
+        e += (size_t)ck_ext_room(); // for CK_EXT_BASE (k_chunk.hip), the diagnostics library's shift of a frame's sequences: 0 in the product
         const size_t r = (e + CK_SPAN - 1) / CK_SPAN * CK_SPAN;
         if (r > 0x7FFFFFFFu - 4096) return CK_EINVAL;
         ws.ext_cap = (int)r;
@@ -231,7 +229,7 @@ struct ck_split {
     bool split() const { return parts > 1; }
 };
 static int parts_wanted() {
-    static const int v = CK_KNOB("CK_PARTS", 2);
+    static const int v = ck_knob(CK_KNOB_PARTS);
     return v < 1 ? 1 : (v > 8 ? 8 : v);
 }
 

@@ -1798,27 +1798,27 @@ __global__ __launch_bounds__(NT) void k_decimate(const uint8_t *__restrict__ src
 
 int ck_launch_threshold_segment(ck_handle *h, const ck_dev_image &img, int n, bool precomputed) {
     const int tiles = h->tiles_x * h->tiles_y;
-    static const int stop_after = CK_KNOB("CK_TILE_STOP_AFTER", 99);
-    static const int fm_stop = CK_KNOB("CK_FMERGE_STOP_AFTER", 99);
+    static const int stop_after = ck_knob(CK_KNOB_TILE_STOP_AFTER);
+    static const int fm_stop = ck_knob(CK_KNOB_FMERGE_STOP_AFTER);
     // CK_SEG_CHUNKS=k cuts the batch into k chunks of frames (multiples of 8: the XCD dealing) and runs chunk i's k_fmerge — one
     // workgroup per frame, bound by chains of dependent steps — on a side stream beside chunk i + 1's k_tile.  Measured on the
     // bench batch (1280 x 800 x 256, same box): 1.07 ms whole, 1.10 in two chunks, 1.22 in four, 1.77 in eight: the merge's
     // workgroups (16 waves and most of a CU's LDS each) displace more of k_tile than their waiting hides.  So the default is one chunk.
-    static const int chunks_env = CK_KNOB("CK_SEG_CHUNKS", 0);
+    static const int chunks_env = ck_knob(CK_KNOB_SEG_CHUNKS);
     // (not together with CK_STREAMS=2: the views of a split batch share the handle's one side stream and its events)
     int chunks = chunks_env > 0 && ck_streams_wanted() < 2 ? chunks_env : 1;
     if (chunks > CK_SEG_CHUNKS_MAX) chunks = CK_SEG_CHUNKS_MAX;
     const int per = ((n + chunks - 1) / chunks + 7) & ~7;
-    const int cap_env = CK_KNOB("CK_FMERGE_CAP", 0); // the path-forcing tests (diag build) force the global-memory path with a small value (read per call)
+    const int cap_env = ck_knob(CK_KNOB_FMERGE_CAP); // the path-forcing tests (diagnostics library) force the global-memory path with a small value (read per call)
     // roots the LDS path of one workgroup holds (dense binary noise has about 90 per tile).  A frame whose roots fit is joined by ONE
     // workgroup, both colours in one sweep; a larger one by two, one per colour (1920 x 1080 of dense noise: 23 000 each); a
     // workgroup with more takes the global-memory path.
     // Bands of tile rows (round 4): a frame with more than FM_BAND_MIN tiles is joined band by band (k_fmerge), then across the
     // bands (k_fseam twice, k_fapply) — every band's roots then fit the keyed LDS path.  2448 x 2048 (1280 tiles, three bands of 22
     // tile rows), per 256 frames: k_fmerge 0.93 + k_fseam 0.15 + k_fapply 0.18 ms against 2.4 in one piece per colour (parents only
-    // in LDS, sizes and smallest pixels by atomics in global memory).  CK_FMERGE_BAND_ROWS (diagnostics build, read per call) forces
+    // in LDS, sizes and smallest pixels by atomics in global memory).  CK_FMERGE_BAND_ROWS (diagnostics library, read per call) forces
     // the band height: the path-forcing tests.
-    const int band_env = CK_KNOB("CK_FMERGE_BAND_ROWS", 0);
+    const int band_env = ck_knob(CK_KNOB_FMERGE_BAND_ROWS);
     int band_rows = h->tiles_y;
     if (tiles > FM_BAND_MIN) {
         const int rows = FM_BAND_TILES / h->tiles_x > 0 ? FM_BAND_TILES / h->tiles_x : 1, nb = (h->tiles_y + rows - 1) / rows;

@@ -595,9 +595,9 @@ int ck_launch_clusters(ck_handle *h, int n) {
     a.thresh = h->d_thresh; a.labels = h->d_labels; a.groot = h->d_groot; a.gsize = h->d_gsize; a.slots = (size_t)h->broot_cap;
     a.w = h->qw; a.h = h->qh; a.tiles_x = (h->qw + ETW - 1) / ETW; a.tiles_y = (h->qh + ETH - 1) / ETH;
     a.min_comp = h->cfg.min_component_px; a.ws = ws; a.ccl_tiles_x = h->tiles_x;
-    { static const int stop_after = CK_KNOB("CK_EMIT_STOP_AFTER", 99); a.stop_after = stop_after; }
-    { static const int twins = CK_KNOB("CK_EMIT_TWINS", 1); a.twins = twins; } // (diagnostics: 0 = every point on its own, for A/B)
-    { static const int stage4 = CK_KNOB("CK_EMIT_STAGE4", 1); a.stage4 = stage4; } // (diagnostics: 0 = every pixel staged on its own, for A/B)
+    { static const int stop_after = ck_knob(CK_KNOB_EMIT_STOP_AFTER); a.stop_after = stop_after; }
+    { static const int twins = ck_knob(CK_KNOB_EMIT_TWINS); a.twins = twins; } // (diagnostics: 0 = every point on its own, for A/B)
+    { static const int stage4 = ck_knob(CK_KNOB_EMIT_STAGE4); a.stage4 = stage4; } // (diagnostics: 0 = every pixel staged on its own, for A/B)
     const int xcd_map = n >= 16 ? 1 : 0; // frames dealt to XCDs: batches of 16 frames and more
     const unsigned grid = xcd_map ? (unsigned)(((n + 7) / 8) * 8 * a.tiles_x * a.tiles_y) : (unsigned)(a.tiles_x * a.tiles_y * n);
     // groups of four pixels: rows, frames and the buffers themselves start at multiples of four pixels

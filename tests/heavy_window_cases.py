@@ -1,7 +1,7 @@
 """Inputs of the heavy-window parity test of the split quad fit's middle kernel (tests/test_gpu_heavy_windows.py;
 tests/test_heavy_window_cases_host.py proves on the CPU that the cases reach what they name).  Nothing here touches the GPU.
 
-k_chunk (chalkydri_amd/csrc/k_quads.hip) looks 1 / W of a window up in a table whose size is the largest weight sum a window can
+k_chunk (chalkydri_amd/csrc/k_chunk.hip) looks 1 / W of a window up in a table whose size is the largest weight sum a window can
 have — 41 points of the weight image's ceiling, 362 — and its running sums are sized by the same ceiling.  The frames of
 tests/span_cases.py have gradients of 175 grey levels; these have full-contrast edges (0 against 255) along an axis, at 45 degrees
 and at a shallow angle, so their points carry the heaviest weights a frame can give: 256 on an axis-parallel edge (gx = 255, gy = 0),

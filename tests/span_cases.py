@@ -28,7 +28,7 @@ from quad_cases import EXIT, FOUND, KSZ, QUAD, UNIQUE
 SPAN = 960                       # CK_SPAN of ck_internal.h
 EXT_PRE, EXT_POST = 25, 24       # CK_EXT_PRE, CK_EXT_POST of ck_internal.h
 HALO = EXT_PRE + EXT_POST
-KOFF = 32                        # k_quads.hip: positions k_chunk loads in front of the span it decides
+KOFF = 32                        # k_chunk.hip: positions k_chunk loads in front of the span it decides
 SHEET, BIG_SHEET = tc.SHEET, tc.BIG_SHEET
 BASES = range(1024)              # every residue of e0, e1 and of every maximum modulo 960, the cluster starting in span 0 and in span 1
 BASE_MAX = 2 * SPAN              # the library clamps CK_EXT_BASE to this

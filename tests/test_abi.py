@@ -214,6 +214,52 @@ def test_product_library_reads_no_diagnostic_knob(built):
         assert k in diag, k
 
 
+def test_diagnostics_library_is_the_products_device_code_but_for_k_chunk(built):
+    """Every path-forcing test runs against the diagnostics library (lib/diag/), so what it proves about a kernel holds for the product
+    only if the kernel is the same one.  It is, by construction: that library links the product's own object files and compiles only
+    ck_knobs.c and k_chunk.hip a second time (csrc/Makefile).  Here: the gfx950 code objects of the two libraries, one per unit, are
+    byte for byte the same but for one on each side, and that one holds k_chunk."""
+    import collections
+    import hashlib
+    import shutil
+    import subprocess
+    import tempfile
+    from conftest import DIAG_LIB
+    llvm = "/opt/rocm/lib/llvm/bin"
+    if not os.path.exists(os.path.join(llvm, "llvm-objdump")):
+        pytest.skip("no llvm-objdump in this image")
+
+    def code_objects(lib):   # SHA-256 -> bytes, and the multiset of the SHA-256s
+        with tempfile.TemporaryDirectory() as td:
+            shutil.copy(lib, os.path.join(td, "lib.so"))
+            subprocess.check_call([os.path.join(llvm, "llvm-objdump"), "--offloading", "lib.so"], cwd=td, stdout=subprocess.DEVNULL)
+            blobs = [open(os.path.join(td, f), "rb").read() for f in sorted(os.listdir(td)) if f.startswith("lib.so") and "amdgcn" in f]
+        by_sum = {hashlib.sha256(b).hexdigest(): b for b in blobs}
+        return by_sum, collections.Counter(hashlib.sha256(b).hexdigest() for b in blobs)
+
+    prod, n_prod = code_objects(os.path.join(os.path.dirname(_lib.__file__), "lib", "libchalkydri_hip.so"))
+    diag, n_diag = code_objects(DIAG_LIB)
+    assert sum(n_prod.values()) == sum(n_diag.values()) >= 20   # one per HIP unit
+    only_prod, only_diag = n_prod - n_diag, n_diag - n_prod
+    assert sum(only_prod.values()) == 1 and sum(only_diag.values()) == 1, (only_prod, only_diag)
+    for by_sum, odd in ((prod, only_prod), (diag, only_diag)):
+        assert re.search(rb"7k_chunkE\w+\.kd\x00", by_sum[next(iter(odd))])   # the kernel descriptor's symbol: (anonymous namespace)::k_chunk(...)
+
+
+def test_knob_table_says_how_each_site_reads_its_knob():
+    """ck_knobs.h is the one list of the diagnostic knobs.  Every row has exactly one site that reads it, and the row's ONCE / PER_CALL
+    is what the site does: a `static const int` keeps the first call's value, anything else reads the environment in every call
+    (the path-forcing tests change the PER_CALL ones between two calls of one process)."""
+    csrc = os.path.join(ROOT, "chalkydri_amd", "csrc")
+    rows = re.findall(r"^\s*X\((\w+),\s*(-?\d+), (ONCE|PER_CALL),\s*\"[^\"]+\"\)", open(os.path.join(csrc, "ck_knobs.h")).read(), re.M)
+    assert len(rows) == 16 and {r[0] for r in rows if r[2] == "PER_CALL"} == {"FMERGE_CAP", "FMERGE_BAND_ROWS", "FIT_STOP_AFTER", "EXT_BASE",
+                                                                           "CHUNK_STOP_AFTER"}
+    lines = [l for f in os.listdir(csrc) if f.endswith(".hip") for l in open(os.path.join(csrc, f)).read().splitlines()]
+    for name, _, read in rows:
+        sites = [l for l in lines if "ck_knob(CK_KNOB_%s)" % name in l]
+        assert len(sites) == 1 and ("static const int" in sites[0]) == (read == "ONCE"), (name, sites)
+
+
 def test_fit_kernels_keep_their_register_budgets(built):
     """The split quad fit's kernels read other lanes' registers (v_readlane) around divergent code; a build of k_tail that spilled
     heavily once lost detections (the reads stood inside divergent blocks, where the spill code restores active lanes
@@ -230,7 +276,7 @@ def test_fit_kernels_keep_their_register_budgets(built):
     build = os.path.join(ROOT, "chalkydri_amd", "csrc", "build")
     res = {}
     with tempfile.TemporaryDirectory() as td:
-        for obj in ("k_quads.o", "k_ccl.o"):
+        for obj in ("k_quads.o", "k_chunk.o", "k_ccl.o"):
             shutil.copy(os.path.join(build, obj), td)
             subprocess.check_call([os.path.join(llvm, "llvm-objdump"), "--offloading", obj], cwd=td, stdout=subprocess.DEVNULL)
             co = [f for f in os.listdir(td) if f.startswith(obj) and "amdgcn" in f][0]

@@ -28,7 +28,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _sources():
-    src = open(os.path.join(ROOT, "chalkydri_amd", "csrc", "k_quads.hip")).read()
+    src = open(os.path.join(ROOT, "chalkydri_amd", "csrc", "k_chunk.hip")).read()
     hdr = open(os.path.join(ROOT, "chalkydri_amd", "csrc", "ck_internal.h")).read()
     return src, hdr
 

@@ -106,15 +106,18 @@ def test_crowded_frames_give_every_workgroup_several_spans(oracle):
 
 
 def test_cases_know_the_kernels_constants():
-    src = open(os.path.join(ROOT, "chalkydri_amd", "csrc", "k_quads.hip")).read()
-    hdr = open(os.path.join(ROOT, "chalkydri_amd", "csrc", "ck_internal.h")).read()
+    csrc = os.path.join(ROOT, "chalkydri_amd", "csrc")
+    src = open(os.path.join(csrc, "k_quads.hip")).read()
+    chunk = open(os.path.join(csrc, "k_chunk.hip")).read()
+    hdr = open(os.path.join(csrc, "ck_internal.h")).read()
     assert int(re.search(r"constexpr int CK_SPAN = (\d+);", hdr).group(1)) == sc.SPAN
     m = re.search(r"constexpr int CK_EXT_PRE = (\d+), CK_EXT_POST = (\d+),", hdr)
     assert (int(m.group(1)), int(m.group(2))) == (sc.EXT_PRE, sc.EXT_POST)
-    assert int(re.search(r"constexpr int KL = 1024, KOFF = (\d+);", src).group(1)) == sc.KOFF
+    assert int(re.search(r"constexpr int KL = 1024, KOFF = (\d+);", chunk).group(1)) == sc.KOFF
     # the knob: clamped to the room the diagnostics build adds to a frame, and that room is the diagnostics build's alone
-    assert re.search(r"if \(ext_base > 2 \* CK_SPAN\) ext_base = 2 \* CK_SPAN;", src) and sc.BASE_MAX == 2 * sc.SPAN
-    stages = open(os.path.join(ROOT, "chalkydri_amd", "csrc", "ck_stages.hip")).read()
-    assert re.search(r"#ifdef CK_DIAG\n\s*e \+= 2 \* CK_SPAN;", stages)
+    assert re.search(r"if \(ext_base > 2 \* CK_SPAN\) ext_base = 2 \* CK_SPAN;", chunk) and sc.BASE_MAX == 2 * sc.SPAN
+    stages = open(os.path.join(csrc, "ck_stages.hip")).read()
+    assert re.search(r"int ck_ext_room\(\) \{\n#ifdef CK_DIAG\n\s*return 2 \* CK_SPAN;\n#else\n\s*return 0;\n#endif\n\}", chunk)
+    assert re.search(r"e \+= \(size_t\)ck_ext_room\(\);", stages) and "CK_DIAG" not in stages and "CK_DIAG" not in src
     # k_chunk's workgroups per frame in the loop test: the grid's minimum
-    assert re.search(r"if \(gx < (\d+)\) gx = \1;", src).group(1) == str(sc.LOOP_WGS)
+    assert re.search(r"if \(gx < (\d+)\) gx = \1;", chunk).group(1) == str(sc.LOOP_WGS)

@@ -1,22 +1,10 @@
-"""Diagnostic: builds a -DCK_TILE_PROFILE copy of the library into /tmp and prints per-phase cycle shares of k_tile."""
+"""Diagnostic: builds a -DCK_TILE_PROFILE variant of the diagnostics library (tools/build_variant.sh) and prints per-phase cycle shares of k_tile."""
 import ctypes as C, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-src = os.path.join(ROOT, "chalkydri_amd", "csrc")
-out = "/tmp/cktprof"; os.makedirs(out, exist_ok=True)
-objs = []
-for f in sorted(os.listdir(src)):
-    if f.endswith(".hip"):
-        o = os.path.join(out, f + ".o")
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off",
-                               "-DCK_TILE_PROFILE", "-DCK_DIAG", "-I" + os.path.join(ROOT, "include"), "-I" + src, "-c", os.path.join(src, f), "-o", o])
-        objs.append(o)
-    elif f.endswith(".c"):
-        o = os.path.join(out, f + ".o")
-        subprocess.check_call(["gcc", "-O2", "-fPIC", "-ffp-contract=off", "-I" + os.path.join(ROOT, "include"), "-I" + src, "-c", os.path.join(src, f), "-o", o])
-        objs.append(o)
-lib = os.path.join(out, "libchalkydri_hip.so")
-subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs)
+# (k_ccl.hip with the flag, everything else from the regular build: run make first)
+subprocess.check_call([os.path.join(ROOT, "tools", "build_variant.sh"), "tileprof", "-DCK_TILE_PROFILE"], env=dict(os.environ, UNITS="k_ccl"))
+lib = os.path.join(ROOT, "chalkydri_amd", "lib", "ref", "libchalkydri_hip_tileprof.so")
 from chalkydri_amd import _lib
 _lib.LIB_PATH = lib
 import numpy as np
