@@ -123,15 +123,9 @@ static bool family_ok(const ck_family_t *f) {
 static int create_device_side(ck_handle *h) {
     CK_HIP_ALLOC(hipSetDevice(h->device));
     CK_HIP_ALLOC(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    CK_HIP_ALLOC(hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking));
     for (auto &e : h->ev) CK_HIP_ALLOC(hipEventCreate(&e));
-    CK_HIP_ALLOC(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-    CK_HIP_ALLOC(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
     CK_HIP_ALLOC(hipEventCreateWithFlags(&h->ev_fit_fork, hipEventDisableTiming));
     for (auto &st : h->fit_stream) CK_HIP_ALLOC(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    CK_HIP_ALLOC(hipStreamCreateWithFlags(&h->seg_stream, hipStreamNonBlocking));
-    for (auto &e : h->ev_seg) CK_HIP_ALLOC(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    CK_HIP_ALLOC(hipEventCreateWithFlags(&h->ev_seg_join, hipEventDisableTiming));
     for (auto &e : h->ev_fit_join) CK_HIP_ALLOC(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     return ck_bufs_create(h);
 }
@@ -178,9 +172,7 @@ extern "C" void ck_destroy(ck_handle_t *h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    if (h->stream2) (void)hipStreamSynchronize(h->stream2);
     for (auto &st : h->fit_stream) if (st) (void)hipStreamSynchronize(st);
-    if (h->seg_stream) (void)hipStreamSynchronize(h->seg_stream);
     ck_bufs_free(h);
     delete h->jpeg; // the on-demand workspaces own their buffers (ck_grow.h)
     delete h->raw;
@@ -195,15 +187,9 @@ extern "C" void ck_destroy(ck_handle_t *h) {
     delete h->blobs;
     delete h->subpix_ws;
     for (auto &e : h->ev) if (e) (void)hipEventDestroy(e);
-    if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-    if (h->ev_join) (void)hipEventDestroy(h->ev_join);
     if (h->ev_fit_fork) (void)hipEventDestroy(h->ev_fit_fork);
     for (auto &e : h->ev_fit_join) if (e) (void)hipEventDestroy(e);
-    for (auto &e : h->ev_seg) if (e) (void)hipEventDestroy(e);
-    if (h->ev_seg_join) (void)hipEventDestroy(h->ev_seg_join);
-    if (h->seg_stream) (void)hipStreamDestroy(h->seg_stream);
     for (auto &st : h->fit_stream) if (st) (void)hipStreamDestroy(st);
-    if (h->stream2) (void)hipStreamDestroy(h->stream2);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     (void)hipGetLastError(); // (what the clean-up calls above may have left behind — a handle that never got its device, say — is not the next call's error)

@@ -72,7 +72,6 @@ constexpr int CK_EXT_PRE = 25, CK_EXT_POST = 24, CK_EXT_HALO = CK_EXT_PRE + CK_E
 constexpr int CK_SPAN = 960;       // positions one k_chunk workgroup decides (15 words of 64), CK_SPAN / 2 = most maxima it can find
 constexpr int CK_HUGE_CAP = 65536, CK_HUGE_WGS = 256; // largest class: points per cluster (3 * 4 * 4095 < 65536), workgroups in its grid
 constexpr int CK_FIT_PARALLEL_MAX_FRAMES = 16; // calls with at most this many frames (twice as many at quad_decimate >= 2) run the classes side by side
-constexpr int CK_SEG_CHUNKS_MAX = 8;           // pieces a batch's threshold + segmentation is cut into at most
 constexpr int CK_FIT_SIDE_STREAMS = 2;         // ... on the handle's stream and this many more (a process has few hardware queues)
 constexpr int CK_LSCRATCH_PER_WG = 16384, CK_LSCRATCH_WGS = 1024; // large class: points per cluster, workgroups in its grid (at most)
 
@@ -109,7 +108,7 @@ struct ck_stage_ws {
     ck_run *d_runs;            // [n][run_cap]
     int run_cap;
     unsigned long long *d_lscratch; // [CK_LSCRATCH_WGS][CK_LSCRATCH_PER_WG]: sort scratch / maxima list of the large fit class, per workgroup
-    unsigned long long *d_hscratch; // [2][CK_HUGE_WGS][2][hcap]: keys + sort scratch / maxima list of the largest class (null when no cluster can be that large)
+    unsigned long long *d_hscratch; // [CK_HUGE_WGS][2][hcap]: keys + sort scratch / maxima list of the largest class (null when no cluster can be that large)
     int hcap;                       // points per cluster that buffer is laid out for: max_cluster_points rounded up to 1024 (<= CK_HUGE_CAP)
     ck_cluster_t *d_clusters;  // [n][cluster_cap]
     uint32_t *d_counters;      // [n][8]: 0 tmp points, 1 clusters, 2 kept points, 3 quads, 4 detections, 5 status
@@ -142,17 +141,11 @@ struct ck_stage_ws {
 struct ck_handle {
     ck_config_t cfg;
     int device;
-    hipStream_t stream;
-    hipStream_t stream2;  // with CK_STREAMS=2 the later pieces of a batch run their irregular stages here (ck_stages.hip: run_pipeline)
+    hipStream_t stream;   // every stage of a call runs here (ck_stages.hip: run_pipeline), but for the quad fit's side lanes below
     hipEvent_t ev[16];
-    hipEvent_t ev_fork, ev_join;
     // a call with a few frames runs the size classes of the quad fit side by side (k_quads.hip): each class is then a handful of
     // workgroups whose time is one cluster's dependency chain, and five chains in a row were a quarter of a one-frame call
     hipStream_t fit_stream[CK_FIT_SIDE_STREAMS];
-    // threshold + segmentation of a large batch runs in chunks of frames: k_fmerge of chunk i (one workgroup per frame, bound by
-    // chains of dependent steps) on seg_stream beside k_tile of chunk i + 1 on the handle's stream (k_ccl.hip)
-    hipStream_t seg_stream;
-    hipEvent_t ev_seg[CK_SEG_CHUNKS_MAX], ev_seg_join;
     hipEvent_t ev_fit_fork, ev_fit_join[CK_FIT_SIDE_STREAMS];
     int w, h;            // full-resolution frame
     int qw, qh;          // geometry of the image the quad stages run on (w/decimate)
@@ -232,7 +225,7 @@ struct ck_handle {
     int has_camera;
     ck_camera_t camera;
     // ck_set_corner_subpix: while has_subpix, the detections a pipeline call leaves in ws.d_dets get their corners refined on the frame
-    // the call was given (ck_subpix.hip: k_subpix_dets, launched by run_tail); 0 (the default): no launch is added
+    // the call was given (ck_subpix.hip: k_subpix_dets, launched by run_pipeline); 0 (the default): no launch is added
     int has_subpix;
     ck_subpix_params_t subpix;
     // sub-pixel corners (ck_subpix.hip): the weight tables and the staging of its calls, allocated by the first of them
@@ -267,7 +260,6 @@ int ck_hip_failed(hipError_t e, const char *call, const char *file, int line, bo
 
 // The diagnostic knobs (ck_knob(CK_KNOB_...): values only the diagnostics library takes from the environment) have one table: ck_knobs.h.
 #include "ck_knobs.h"
-int ck_streams_wanted(); // ck_stages.hip: CK_STREAMS (1 or 2), read once
 
 // The quad stages run on a buffer of their own (d_qframes) when the frame is decimated or filtered; otherwise on the frame itself.
 static inline bool ck_quad_separate(const ck_handle *h) { return h->cfg.quad_decimate > 1 || h->qf_ksz > 1; }

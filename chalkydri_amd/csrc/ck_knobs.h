@@ -5,8 +5,7 @@
 // exceptions, the two units compiled a second time with -DCK_DIAG: ck_knobs.c, whose ck_knob() reads the environment there, and
 // k_chunk.hip, whose kernels are the only device code a knob changes.  In the product ck_knob() returns the default: ck_knobs.o holds
 // neither the names nor a getenv call, so the environment cannot change what the drop-in returns.  The product library reads exactly
-// two variables, which are no knobs: CK_POISON (ck_internal.h: allocation fill / guard pages) and CK_STREAMS (ck_stages.hip: the
-// post-segmentation stages on two streams; the bytes do not depend on it).
+// one variable, which is no knob: CK_POISON (ck_internal.h: allocation fill / guard pages).
 //
 // ONCE: the one site that reads the knob keeps the value in a `static const int` — the environment at the first call counts.
 // PER_CALL: read by every call, so that a test can change it between two calls of one process.
@@ -17,7 +16,6 @@
 #define CK_KNOB_TABLE(X) \
     X(TILE_STOP_AFTER,   99, ONCE,     "k_tile ends after phase k (k_ccl.hip); 99 = all of it") \
     X(FMERGE_STOP_AFTER, 99, ONCE,     "k_fmerge ends after step k (k_ccl.hip); 99 = all of it") \
-    X(SEG_CHUNKS,         0, ONCE,     "the batch in k chunks of frames, chunk i's k_fmerge beside chunk i + 1's k_tile; 0 = one chunk") \
     X(FMERGE_CAP,         0, PER_CALL, "roots k_fmerge's LDS path holds, when smaller than the computed capacity: forces the global-memory path") \
     X(FMERGE_BAND_ROWS,   0, PER_CALL, "tile rows per band of the segmentation's merge; 0 = the computed height") \
     X(EMIT_STOP_AFTER,   99, ONCE,     "k_emit2 ends after phase k (k_clusters.hip); 99 = all of it") \
@@ -29,8 +27,7 @@
     X(CHUNK_WGS,         64, ONCE,     "k_chunk workgroups per CU over the batch") \
     X(FIT_STOP_AFTER,    99, PER_CALL, "every cluster of the quad fit ends after phase k (k_quads.hip); 99 = all of it") \
     X(EXT_BASE,           0, PER_CALL, "first position of the split fit's extended sequences in every frame, 0 .. 2 * CK_SPAN (k_chunk.hip)") \
-    X(CHUNK_STOP_AFTER,  99, PER_CALL, "every span of k_chunk ends after step k (k_chunk.hip); 99 = all of it") \
-    X(PARTS,              2, ONCE,     "pieces the post-segmentation stages cut a batch into under CK_STREAMS=2, 1 .. 8 (ck_stages.hip)")
+    X(CHUNK_STOP_AFTER,  99, PER_CALL, "every span of k_chunk ends after step k (k_chunk.hip); 99 = all of it")
 
 #define CK_KNOB_ID_(id, dflt, read, about) CK_KNOB_##id,
 enum ck_knob_id { CK_KNOB_TABLE(CK_KNOB_ID_) CK_KNOB_COUNT };

@@ -177,8 +177,8 @@ extern "C" int ck_last_pose_inputs(ck_handle_t *h, int32_t n, ck_sqpnp_problem_t
     CK_HIP(hipMemcpyAsync(tags.data(), w.d_pose_tags, sizeof(ck_iso3_t) * tags.size(), hipMemcpyDeviceToHost, h->stream));
     CK_HIP(hipMemcpyAsync(bear.data(), w.d_bearings, sizeof(double) * bear.size(), hipMemcpyDeviceToHost, h->stream));
     CK_HIP(hipStreamSynchronize(h->stream));
-    // Step s owns tags [s * det_cap ..] and bearings [s * det_cap * 4 ..] of the workspace whichever piece of a split batch wrote its
-    // record (the record's own offsets are relative to that piece): the outputs are packed in step order
+    // Step s owns tags [s * det_cap ..] and bearings [s * det_cap * 4 ..] of the workspace (its record's offsets say the same); the
+    // outputs are packed in step order, and the records' offsets rewritten to match
     int64_t nt = 0;
     for (int32_t s = 0; s < n; s++) nt += records_out[s].n_tags > 0 && (size_t)records_out[s].n_tags <= cap ? records_out[s].n_tags : 0;
     *n_tags_out = (int32_t)nt; *n_bearings_out = (int32_t)(4 * nt);

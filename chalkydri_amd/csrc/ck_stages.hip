@@ -1,5 +1,5 @@
-// ck_stages.hip — the handle's device buffers (one table: allocation, release, the views of a split batch, the names CK_POISON=2
-// prints) and the detect / clusters / quads / process entry points.
+// ck_stages.hip — the handle's device buffers (one table: allocation, release, the names CK_POISON=2 prints) and the
+// detect / clusters / quads / process entry points.
 #include <string.h>
 
 #include <vector>
@@ -11,11 +11,10 @@ static int next_pow2(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 
 // ---- the handle's device buffers ---------------------------------------------------------------------------------------------
 // Every device buffer of ck_handle / ck_stage_ws is one row of ck_bufs[]: allocation (ck_bufs_create in this order; ck_buf_alloc
-// for the ones allocated on first use), release (ck_bufs_free), the per-frame advance of a split batch's views (make_view) and
-// the name CK_POISON=2 prints all walk this table.  A new buffer is a member + a row; ck_jpeg_ws and ck_raw_ws (grown per call) keep their own.
+// for the ones allocated on first use), release (ck_bufs_free) and the name CK_POISON=2 prints all walk this table.  A new buffer
+// is a member + a row; ck_jpeg_ws and ck_raw_ws (grown per call) keep their own.
 enum : unsigned {
-    CK_BUF_FRAME = 1, // [max_batch][bytes]: a view of the frames from f0 on starts f0 * bytes further
-    CK_BUF_TWIN = 2,  // [2][bytes], per handle: the second copy is the one the pieces on stream2 use
+    CK_BUF_FRAME = 1, // [max_batch][bytes]
     CK_BUF_LAZY = 4,  // not allocated by ck_create (d_qframes: at quad_decimate 2 it is)
     CK_BUF_ALIAS = 8, // the row before it seen as another type: same storage, same pitch in bytes; not allocated, not freed
 };
@@ -23,7 +22,7 @@ struct ck_buf_desc {
     const char *name;
     size_t member;                     // offsetof(ck_handle, the pointer)
     unsigned flags;                    // (none: one array of `bytes` per handle)
-    size_t (*bytes)(const ck_handle *); // per frame / per copy / in all; 0: this handle has no such buffer
+    size_t (*bytes)(const ck_handle *); // per frame / in all; 0: this handle has no such buffer
 };
 #define CK_BUF(member, flags, expr) \
     {#member, offsetof(ck_handle, member), flags, [](const ck_handle *h) -> size_t { const ck_stage_ws &w = h->ws; (void)w; return (size_t)(expr); }}
@@ -58,14 +57,14 @@ static constexpr ck_buf_desc ck_bufs[] = {
     CK_BUF(ws.d_blk, CK_BUF_FRAME, 6 * (size_t)(w.ext_cap / 32) * sizeof(long long)),
     CK_BUF(ws.d_cstate, CK_BUF_FRAME, 2 * w.cluster_cap * sizeof(uint32_t)),
     CK_BUF(ws.d_runs, CK_BUF_FRAME, w.run_cap * sizeof(ck_run)),
-    CK_BUF(ws.d_lscratch, CK_BUF_TWIN, sizeof(unsigned long long) * CK_LSCRATCH_PER_WG * CK_LSCRATCH_WGS),
+    CK_BUF(ws.d_lscratch, 0, sizeof(unsigned long long) * CK_LSCRATCH_PER_WG * CK_LSCRATCH_WGS),
     // (1920 x 1080: 18 432 points, 144 MiB instead of the 512 MiB of the class's template capacity)
-    CK_BUF(ws.d_hscratch, CK_BUF_TWIN, w.max_cluster_points > 16384 ? sizeof(unsigned long long) * 2 * w.hcap * CK_HUGE_WGS : 0),
+    CK_BUF(ws.d_hscratch, 0, w.max_cluster_points > 16384 ? sizeof(unsigned long long) * 2 * w.hcap * CK_HUGE_WGS : 0),
     CK_BUF(ws.d_clusters, CK_BUF_FRAME, w.cluster_cap * sizeof(ck_cluster_t)),
     CK_BUF(ws.d_counters, CK_BUF_FRAME, CK_CNT_STRIDE * sizeof(uint32_t)),
     CK_BUF(ws.d_quads, CK_BUF_FRAME, w.quad_cap * sizeof(ck_quad_t)),
     CK_BUF(ws.d_dets, CK_BUF_FRAME, w.det_cap * sizeof(ck_detection_t)),
-    CK_BUF(ws.d_fit_scratch, CK_BUF_TWIN, w.fit_scratch_bytes),
+    CK_BUF(ws.d_fit_scratch, 0, w.fit_scratch_bytes),
     CK_BUF(ws.d_wimg, CK_BUF_FRAME, h->npix * sizeof(uint16_t)),
     CK_BUF(ws.d_field, 0, w.field_cap * sizeof(ck_field_tag_t)),
     CK_BUF(ws.d_gyro, CK_BUF_FRAME, sizeof(double)),
@@ -79,7 +78,7 @@ static constexpr ck_buf_desc ck_bufs[] = {
     CK_BUF(ws.d_valid, CK_BUF_FRAME, sizeof(int32_t)),
     CK_BUF(d_fam_codes, 0, fam_codes_bytes(h)),
     CK_BUF(d_fams, 0, h->cfg.n_families * sizeof(ck_dev_family)),
-    // per-tag pose (k_tagpose.hip), by the first call that needs them; one call's records, never part of a split
+    // per-tag pose (k_tagpose.hip), by the first call that needs them; one call's records, max_batch * det_cap of them
     CK_BUF(d_tp_dets, CK_BUF_LAZY, (size_t)h->cfg.max_batch * w.det_cap * sizeof(ck_detection_t)),
     CK_BUF(d_tp_counts, CK_BUF_LAZY, h->cfg.max_batch * sizeof(int32_t)),
     CK_BUF(d_tp_out, CK_BUF_LAZY, (size_t)h->cfg.max_batch * w.det_cap * sizeof(ck_tag_pose_t)),
@@ -98,7 +97,7 @@ static char *&buf_ptr(ck_handle *h, const ck_buf_desc &d) { return *reinterpret_
 
 static int alloc_one(ck_handle *h, const ck_buf_desc &d) {
     if (d.flags & CK_BUF_ALIAS) { buf_ptr(h, d) = buf_ptr(h, (&d)[-1]); return CK_OK; }
-    const size_t bytes = d.bytes(h) * (d.flags & CK_BUF_FRAME ? (size_t)h->cfg.max_batch : d.flags & CK_BUF_TWIN ? 2 : 1);
+    const size_t bytes = d.bytes(h) * (d.flags & CK_BUF_FRAME ? (size_t)h->cfg.max_batch : 1);
     if (!bytes || buf_ptr(h, d)) return CK_OK;
     CK_HIP_ALLOC(ck_malloc_dev_at(&buf_ptr(h, d), bytes, d.name, __LINE__)); // (a buffer whose fill failed is still the handle's: ck_bufs_free)
     return CK_OK;
@@ -177,63 +176,9 @@ int ck_bufs_create(ck_handle *h) {
     return CK_OK;
 }
 
-// the whole detector on n frames resident on the device
-// The stages after segmentation can run as consecutive pieces of the batch on two streams (CK_STREAMS=2), each piece filling
-// the other's gaps (one-workgroup-per-frame kernels, latency chains).  Threshold + segmentation always run for the whole
-// batch on the handle's stream (that is the stage the HBM roofline is quoted on); then the later pieces continue
-// on stream2 through a VIEW of the handle — a copy whose per-frame pointers are advanced by n0 frames and whose scratch
-// regions are the second copies allocated for it.  Frames are independent, so the results do not depend on the split.
-int ck_streams_wanted() {
-    // default 1: since the fit kernels dequeue their clusters in chunks (no long tail left to fill) two dense kernels side by
-    // side only get in each other's way (21.8 vs 22.4 ms per 1280x800x256 batch); CK_STREAMS=2 keeps the split available
-    static const int v = getenv("CK_STREAMS") ? atoi(getenv("CK_STREAMS")) : 1;
-    return v;
-}
-static ck_handle make_view(const ck_handle *h, int f0, bool second_stream = true) {
-    ck_handle v = *h; // (capacities and the rest stay; only the pointers move)
-    if (second_stream) v.stream = h->stream2;
-    for (const ck_buf_desc &d : ck_bufs) {
-        char *&p = buf_ptr(&v, d);
-        if (!p) continue;
-        if (d.flags & CK_BUF_FRAME) p += (size_t)f0 * d.bytes(h);
-        else if ((d.flags & CK_BUF_TWIN) && second_stream) p += d.bytes(h);
-    }
-    return v;
-}
-
-// clusters -> quad fit -> decode of n frames on h->stream
-static int run_tail(ck_handle *h, const ck_dev_image &img, int n, int upto, bool events) {
-    hipEvent_t *ev = h->ev;
-    int rc = ck_launch_clusters(h, n);
-    if (rc != CK_OK) return rc;
-    if (events) CK_HIP(hipEventRecord(ev[3], h->stream));
-    const ck_dev_image fine = ck_refine_image(h, img);
-    if (upto >= 2) {
-        rc = ck_launch_fit_quads(h, ck_quad_image(h, img), fine, n);
-        if (rc != CK_OK) return rc;
-    }
-    if (events) CK_HIP(hipEventRecord(ev[4], h->stream));
-    if (upto >= 3) {
-        rc = ck_launch_decode(h, fine, n);
-        if (rc == CK_OK) rc = ck_launch_subpix_dets(h, img, n); // ck_set_corner_subpix: on the unfiltered frame (nothing when off)
-        if (rc != CK_OK) return rc;
-    }
-    if (events) CK_HIP(hipEventRecord(ev[5], h->stream));
-    return CK_OK;
-}
-
-struct ck_split {
-    int parts = 1;     // the batch is cut into `parts` consecutive pieces; piece p runs on stream (p & 1)
-    int first[9] = {0}; // piece p = frames [first[p], first[p + 1])
-    ck_handle view[8]; // view[p] for p >= 1 (piece 0 uses the handle itself)
-    bool split() const { return parts > 1; }
-};
-static int parts_wanted() {
-    static const int v = ck_knob(CK_KNOB_PARTS);
-    return v < 1 ? 1 : (v > 8 ? 8 : v);
-}
-
-static int run_pipeline(ck_handle *h, const ck_dev_image &img, int n, int upto /*1 clusters, 2 quads, 3 all*/, ck_split *split = nullptr) {
+// the whole detector on n frames resident on the device: threshold + segmentation -> clusters -> quad fit -> decode, all on
+// h->stream (the quad fit alone puts some size classes on the handle's side streams: k_quads.hip)
+static int run_pipeline(ck_handle *h, const ck_dev_image &img, int n, int upto /*1 clusters, 2 quads, 3 all*/) {
     hipEvent_t *ev = h->ev;
     h->n_last_dets = -1; // the workspace is rewritten from here on; it holds this call's detections only once they are all enqueued
     h->n_pose_inputs = -1;
@@ -242,33 +187,22 @@ static int run_pipeline(ck_handle *h, const ck_dev_image &img, int n, int upto /
     int rc = ck_run_threshold_segment(h, img, n);
     if (rc != CK_OK) return rc;
     CK_HIP(hipEventRecord(ev[2], h->stream));
-    int parts = parts_wanted();
-    if (parts > n) parts = n;
-    if (!split || parts < 2 || ck_streams_wanted() < 2) {
-        if (split) { split->parts = 1; split->first[0] = 0; split->first[1] = n; }
-        rc = run_tail(h, img, n, upto, true);
-        if (rc == CK_OK && upto >= 3) h->n_last_dets = n;
-        return rc;
-    }
-    split->parts = parts;
-    for (int p = 0; p <= parts; p++) split->first[p] = (int)((long long)n * p / parts);
-    CK_HIP(hipEventRecord(h->ev_fork, h->stream));
-    CK_HIP(hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
-    for (int p = 0; p < parts; p++) {
-        const int f0 = split->first[p], cnt = split->first[p + 1] - f0;
-        ck_handle *hp = h;
-        if (p > 0) { split->view[p] = make_view(h, f0, (p & 1) != 0); hp = &split->view[p]; }
-        rc = run_tail(hp, {img.p + (size_t)f0 * img.pitch, img.stride, img.pitch}, cnt, upto, p == 0);
+    rc = ck_launch_clusters(h, n);
+    if (rc != CK_OK) return rc;
+    CK_HIP(hipEventRecord(ev[3], h->stream));
+    const ck_dev_image fine = ck_refine_image(h, img);
+    if (upto >= 2) {
+        rc = ck_launch_fit_quads(h, ck_quad_image(h, img), fine, n);
         if (rc != CK_OK) return rc;
     }
+    CK_HIP(hipEventRecord(ev[4], h->stream));
+    if (upto >= 3) {
+        rc = ck_launch_decode(h, fine, n);
+        if (rc == CK_OK) rc = ck_launch_subpix_dets(h, img, n); // ck_set_corner_subpix: on the unfiltered frame (nothing when off)
+        if (rc != CK_OK) return rc;
+    }
+    CK_HIP(hipEventRecord(ev[5], h->stream));
     if (upto >= 3) h->n_last_dets = n;
-    return CK_OK;
-}
-// the handle's stream continues only after stream2 has finished its half
-static int join_split(ck_handle *h, const ck_split &sp) {
-    if (!sp.split()) return CK_OK;
-    CK_HIP(hipEventRecord(h->ev_join, h->stream2));
-    CK_HIP(hipStreamWaitEvent(h->stream, h->ev_join, 0));
     return CK_OK;
 }
 
@@ -302,9 +236,7 @@ static int fetch_detections(ck_handle *h, int n, ck_detection_t *dets, int cap, 
 
 // what every detect entry point does once its input is staged (ev[0] recorded before the staging)
 static int detect_common(ck_handle *h, const ck_dev_image &img, int n, ck_detection_t *dets, int cap, int32_t *counts, uint32_t *status) {
-    ck_split sp;
-    int rc = run_pipeline(h, img, n, 3, &sp);
-    if (rc == CK_OK) rc = join_split(h, sp);
+    const int rc = run_pipeline(h, img, n, 3);
     if (rc != CK_OK) return rc;
     return fetch_detections(h, n, dets, cap, counts, status);
 }
@@ -467,16 +399,10 @@ static int process_common(ck_handle *h, const ck_dev_image &img, int n, const ck
     if (!pp || !gyro || !has_gyro || !out || !valid || (pp->n_field > 0 && !pp->field) || pp->n_field < 0) return CK_EINVAL;
     CK_HIP(hipEventRecord(h->ev[0], h->stream));
     if (pp->n_field > h->ws.field_cap) return CK_ECAPACITY;
-    // the field layout is shared by both halves: upload it once, ahead of the fork
     if (pp->n_field) CK_HIP(hipMemcpyAsync(h->ws.d_field, pp->field, sizeof(ck_field_tag_t) * (size_t)pp->n_field, hipMemcpyDefault, h->stream));
-    ck_split sp;
-    int rc = run_pipeline(h, img, n, 3, &sp);
+    int rc = run_pipeline(h, img, n, 3);
     if (rc != CK_OK) return rc;
-    for (int p = 0; p < sp.parts && rc == CK_OK; p++) {
-        const int f0 = sp.first[p], cnt = sp.first[p + 1] - f0;
-        rc = ck_run_pose(p ? &sp.view[p] : h, cnt, pp, gyro + f0, has_gyro + f0, out + f0, valid + f0, false, false);
-    }
-    if (rc == CK_OK) rc = join_split(h, sp);
+    rc = ck_run_pose(h, n, pp, gyro, has_gyro, out, valid, false, false);
     h->n_last_pose = rc == CK_OK ? n : -1;
     h->n_pose_inputs = h->n_last_pose;
     CK_HIP(hipEventRecord(h->ev[6], h->stream));

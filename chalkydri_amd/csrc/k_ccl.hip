@@ -1800,15 +1800,6 @@ int ck_launch_threshold_segment(ck_handle *h, const ck_dev_image &img, int n, bo
     const int tiles = h->tiles_x * h->tiles_y;
     static const int stop_after = ck_knob(CK_KNOB_TILE_STOP_AFTER);
     static const int fm_stop = ck_knob(CK_KNOB_FMERGE_STOP_AFTER);
-    // CK_SEG_CHUNKS=k cuts the batch into k chunks of frames (multiples of 8: the XCD dealing) and runs chunk i's k_fmerge — one
-    // workgroup per frame, bound by chains of dependent steps — on a side stream beside chunk i + 1's k_tile.  Measured on the
-    // bench batch (1280 x 800 x 256, same box): 1.07 ms whole, 1.10 in two chunks, 1.22 in four, 1.77 in eight: the merge's
-    // workgroups (16 waves and most of a CU's LDS each) displace more of k_tile than their waiting hides.  So the default is one chunk.
-    static const int chunks_env = ck_knob(CK_KNOB_SEG_CHUNKS);
-    // (not together with CK_STREAMS=2: the views of a split batch share the handle's one side stream and its events)
-    int chunks = chunks_env > 0 && ck_streams_wanted() < 2 ? chunks_env : 1;
-    if (chunks > CK_SEG_CHUNKS_MAX) chunks = CK_SEG_CHUNKS_MAX;
-    const int per = ((n + chunks - 1) / chunks + 7) & ~7;
     const int cap_env = ck_knob(CK_KNOB_FMERGE_CAP); // the path-forcing tests (diagnostics library) force the global-memory path with a small value (read per call)
     // roots the LDS path of one workgroup holds (dense binary noise has about 90 per tile).  A frame whose roots fit is joined by ONE
     // workgroup, both colours in one sweep; a larger one by two, one per colour (1920 x 1080 of dense noise: 23 000 each); a
@@ -1839,41 +1830,29 @@ int ck_launch_threshold_segment(ck_handle *h, const ck_dev_image &img, int n, bo
         CK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_fmerge), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512));
         h->fmerge_lds_allowed = true;
     }
-    bool forked = false;
-    for (int f0 = 0, ci = 0; f0 < n; f0 += per, ci++) {
-        const int f1 = f0 + per < n ? f0 + per : n, cn = f1 - f0;
-        const int xcd_map = cn >= 16 ? 1 : 0; // frames dealt to XCDs (a frame's tiles share one L2): worth it once there are frames for all eight
-        const unsigned grid = xcd_map ? (unsigned)(((cn + 7) / 8) * 8 * tiles) : (unsigned)(tiles * cn);
-        if (precomputed)
-            hipLaunchKernelGGL(k_tile<true>, dim3(grid), dim3(KNT), 0, h->stream, img.p, img.pitch, img.stride, h->qw, h->qh,
-                               h->tiles_x, h->tiles_y, f0, f1, xcd_map, h->cfg.min_white_black_diff, h->cfg.min_component_px, h->d_thresh, h->d_labels,
-                               h->d_broots, h->d_tile_count, h->d_ring, h->ring_len, stop_after);
-        else
-            hipLaunchKernelGGL(k_tile<false>, dim3(grid), dim3(KNT), 0, h->stream, img.p, img.pitch, img.stride, h->qw, h->qh,
-                               h->tiles_x, h->tiles_y, f0, f1, xcd_map, h->cfg.min_white_black_diff, h->cfg.min_component_px, h->d_thresh, h->d_labels,
-                               h->d_broots, h->d_tile_count, h->d_ring, h->ring_len, stop_after);
-        if (stop_after < 98) continue; // (a k_tile cut short by the diagnostics knob leaves tile counts or ring entries unwritten: nothing for the merge to read)
-        hipStream_t ms = h->stream;
-        if (f1 < n) { // not the last chunk: its merge goes beside the next chunk's k_tile
-            CK_HIP(hipEventRecord(h->ev_seg[ci], h->stream));
-            CK_HIP(hipStreamWaitEvent(h->seg_stream, h->ev_seg[ci], 0));
-            ms = h->seg_stream;
-            forked = true;
-        }
-        hipLaunchKernelGGL(k_fmerge, dim3((unsigned)(((cn + 7) / 8) * 16 * bands)), dim3(FM_NT), lds, ms, h->d_broots, h->d_tile_count, h->d_ring, h->ring_len,
+    // the whole batch in one pass (the kernels take a range of frames [f0, f1))
+    const int f0 = 0, f1 = n;
+    const int xcd_map = n >= 16 ? 1 : 0; // frames dealt to XCDs (a frame's tiles share one L2): worth it once there are frames for all eight
+    const unsigned grid = xcd_map ? (unsigned)(((n + 7) / 8) * 8 * tiles) : (unsigned)(tiles * n);
+    if (precomputed)
+        hipLaunchKernelGGL(k_tile<true>, dim3(grid), dim3(KNT), 0, h->stream, img.p, img.pitch, img.stride, h->qw, h->qh,
+                           h->tiles_x, h->tiles_y, f0, f1, xcd_map, h->cfg.min_white_black_diff, h->cfg.min_component_px, h->d_thresh, h->d_labels,
+                           h->d_broots, h->d_tile_count, h->d_ring, h->ring_len, stop_after);
+    else
+        hipLaunchKernelGGL(k_tile<false>, dim3(grid), dim3(KNT), 0, h->stream, img.p, img.pitch, img.stride, h->qw, h->qh,
+                           h->tiles_x, h->tiles_y, f0, f1, xcd_map, h->cfg.min_white_black_diff, h->cfg.min_component_px, h->d_thresh, h->d_labels,
+                           h->d_broots, h->d_tile_count, h->d_ring, h->ring_len, stop_after);
+    if (stop_after >= 98) { // (a k_tile cut short by the diagnostics knob leaves tile counts or ring entries unwritten: nothing for the merge to read)
+        hipLaunchKernelGGL(k_fmerge, dim3((unsigned)(((n + 7) / 8) * 16 * bands)), dim3(FM_NT), lds, h->stream, h->d_broots, h->d_tile_count, h->d_ring, h->ring_len,
                            h->d_groot, h->d_gsize, h->d_gscratch, h->npix, h->qw, h->qh, h->tiles_x, h->tiles_y, f0, f1, h->cfg.min_component_px, cap,
                            fm_stop, band_rows, bands > 1 ? h->d_xband : nullptr);
         if (bands > 1 && fm_stop >= 99) {
-            const dim3 sg((unsigned)(((bands - 1) * h->qw + NT - 1) / NT), (unsigned)cn);
-            hipLaunchKernelGGL(k_fseam<false>, sg, dim3(NT), 0, ms, h->d_ring, h->ring_len, h->d_groot, h->d_gsize, h->d_xband, h->qw, h->tiles_x, h->tiles_y, band_rows, f0);
-            hipLaunchKernelGGL(k_fseam<true>, sg, dim3(NT), 0, ms, h->d_ring, h->ring_len, h->d_groot, h->d_gsize, h->d_xband, h->qw, h->tiles_x, h->tiles_y, band_rows, f0);
-            hipLaunchKernelGGL(k_fapply, dim3((unsigned)((tiles + NT / 64 - 1) / (NT / 64)), (unsigned)cn), dim3(NT), 0, ms, h->d_tile_count, h->d_groot,
+            const dim3 sg((unsigned)(((bands - 1) * h->qw + NT - 1) / NT), (unsigned)n);
+            hipLaunchKernelGGL(k_fseam<false>, sg, dim3(NT), 0, h->stream, h->d_ring, h->ring_len, h->d_groot, h->d_gsize, h->d_xband, h->qw, h->tiles_x, h->tiles_y, band_rows, f0);
+            hipLaunchKernelGGL(k_fseam<true>, sg, dim3(NT), 0, h->stream, h->d_ring, h->ring_len, h->d_groot, h->d_gsize, h->d_xband, h->qw, h->tiles_x, h->tiles_y, band_rows, f0);
+            hipLaunchKernelGGL(k_fapply, dim3((unsigned)((tiles + NT / 64 - 1) / (NT / 64)), (unsigned)n), dim3(NT), 0, h->stream, h->d_tile_count, h->d_groot,
                                h->d_gsize, h->d_xband, tiles, f0);
         }
-    }
-    if (forked) {
-        CK_HIP(hipEventRecord(h->ev_seg_join, h->seg_stream));
-        CK_HIP(hipStreamWaitEvent(h->stream, h->ev_seg_join, 0));
     }
     CK_HIP(hipGetLastError());
     return CK_OK;

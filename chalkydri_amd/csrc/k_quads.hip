@@ -2133,9 +2133,9 @@ constexpr FitClass FIT_CLASS[CK_FIT_CLASSES] = {
 };
 static_assert(FIT_CUS == CK_HUGE_WGS, "the largest class: one workgroup per CU, like the two before it");
 
-// Where the classes run, and in which order they are launched.  lane[c]: 0 = the handle's stream, 1 / 2 = side stream 0 / 1.
+// Where the classes run, and in which order they are launched.  lane[c]: 0 = the handle's stream, 1 / 2 = side stream 0 / 1:
+// the side streams wait for the handle's stream before the launches, and it waits for them after.
 struct FitMode {
-    bool forks; // the side streams wait for the handle's stream before the launches, and it waits for them after
     int8_t lane[CK_FIT_CLASSES];
     int n_order;
     int8_t order[CK_FIT_CLASSES];
@@ -2146,15 +2146,13 @@ struct FitMode {
 // handle's lane (0.64 -> 0.70 ms per 1280x800 frame at quad_decimate 2).  Three lanes of similar length for a typical frame:
 // {S, M1} on the handle's stream, {L1} and {M2, L2} on the side streams (more streams than that end up sharing hardware queues and
 // wait for each other anyway); the side lanes first, then the handle's own.
-constexpr FitMode FIT_SIDE_BY_SIDE = {true, {0, 0, 2, 1, 2, 0, 0, 0}, 6, {3, 2, 4, 0, 1, 5}};
+constexpr FitMode FIT_SIDE_BY_SIDE = {{0, 0, 2, 1, 2, 0, 0, 0}, 6, {3, 2, 4, 0, 1, 5}};
 // A batch keeps one lane, except for the three classes with ONE 512-thread workgroup per CU (8193..16384 points: 2.2 clusters per
 // workgroup on average, so a quarter of the CUs do a third cluster while the rest idle; the largest; 4097..8192): one after the
 // other on a side stream, started first, their tails and barrier waits run under the small classes instead of before them.
 // (Measured: the 2049..4096 class there as well, or the three on two side streams, is slower than this.  Split fit, other
 // assignments of the classes to the three streams: 8.52 .. 8.68 ms against 8.59, all within the noise of one box.)
-constexpr FitMode FIT_TAILS_ASIDE = {true, {0, 0, 0, 1, 1, 1, 0, 0}, 8, {4, 5, 3, 7, 0, 6, 1, 2}};
-// ... and a batch in a process whose later stages already run on two streams (CK_STREAMS=2) keeps everything on the handle's stream
-constexpr FitMode FIT_SINGLE_LANE = {false, {0, 0, 0, 0, 0, 0, 0, 0}, 8, {7, 0, 6, 1, 2, 3, 4, 5}};
+constexpr FitMode FIT_TAILS_ASIDE = {{0, 0, 0, 1, 1, 1, 0, 0}, 8, {4, 5, 3, 7, 0, 6, 1, 2}};
 
 // class C's kernel on stream st: k_seq for the split fit (flat), k_fit otherwise
 template <int C>
@@ -2200,8 +2198,8 @@ int ck_launch_fit_quads(ck_handle *h, const ck_dev_image &qimg, const ck_dev_ima
     // ---- policy: which form of the fit, on which lanes --------------------------------------------------------------------------
     // (measured at 1280x800: side by side wins up to 16 frames at quad_decimate 1, up to 32 at 2, where the clusters are fewer)
     const bool side_by_side = n <= (h->cfg.quad_decimate > 1 ? 2 * CK_FIT_PARALLEL_MAX_FRAMES : CK_FIT_PARALLEL_MAX_FRAMES);
-    const bool tails_aside = !side_by_side && ck_streams_wanted() < 2;
-    const FitMode &mode = side_by_side ? FIT_SIDE_BY_SIDE : (tails_aside ? FIT_TAILS_ASIDE : FIT_SINGLE_LANE);
+    const bool tails_aside = !side_by_side;
+    const FitMode &mode = side_by_side ? FIT_SIDE_BY_SIDE : FIT_TAILS_ASIDE;
     // The split fit (k_seq per class -> k_chunk over all positions -> k_tail over all clusters): for calls that run their classes one
     // after the other AND bring enough pixels — its three stages each ramp a persistent grid up and down, which a quarter-size batch
     // notices (1280x800 x 256 at quad_decimate 2: 2.85 against 2.52 ms unsplit; at full resolution 9.75 against 9.94, 1920x1080 21.4
@@ -2243,22 +2241,19 @@ int ck_launch_fit_quads(ck_handle *h, const ck_dev_image &qimg, const ck_dev_ima
 
     // ---- the launches ---------------------------------------------------------------------------------------------------------------
     if (!wimg_aside) launch_wimg(h->stream);
-    if (mode.forks) {
-        CK_HIP(hipEventRecord(h->ev_fit_fork, h->stream));
-        for (int s = 0; s < CK_FIT_SIDE_STREAMS; s++) CK_HIP(hipStreamWaitEvent(h->fit_stream[s], h->ev_fit_fork, 0));
-        if (wimg_aside) launch_wimg(h->fit_stream[1]); // (joined with the side streams before k_chunk)
-    }
+    CK_HIP(hipEventRecord(h->ev_fit_fork, h->stream));
+    for (int s = 0; s < CK_FIT_SIDE_STREAMS; s++) CK_HIP(hipStreamWaitEvent(h->fit_stream[s], h->ev_fit_fork, 0));
+    if (wimg_aside) launch_wimg(h->fit_stream[1]); // (joined with the side streams before k_chunk)
     for (int i = 0; i < mode.n_order; i++) {
         const int c = mode.order[i];
         if ((k_skip >> c) & 1) continue;
         use_list(c);
         launch_class_of(std::make_integer_sequence<int, CK_FIT_CLASSES>{}, c, flat, lanes[mode.lane[c]], a);
     }
-    if (mode.forks)
-        for (int s = 0; s < CK_FIT_SIDE_STREAMS; s++) {
-            CK_HIP(hipEventRecord(h->ev_fit_join[s], h->fit_stream[s]));
-            CK_HIP(hipStreamWaitEvent(h->stream, h->ev_fit_join[s], 0));
-        }
+    for (int s = 0; s < CK_FIT_SIDE_STREAMS; s++) {
+        CK_HIP(hipEventRecord(h->ev_fit_join[s], h->fit_stream[s]));
+        CK_HIP(hipStreamWaitEvent(h->stream, h->ev_fit_join[s], 0));
+    }
     if (flat) {
         ck_launch_chunk(h, n, FIT_CUS * k_chunk_wgs, &a.stop_after);
         use_list(CK_FIT_CLASSES); // every cluster of the batch

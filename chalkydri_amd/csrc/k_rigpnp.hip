@@ -23,8 +23,8 @@ struct RigCam {
     const ck_iso3_t *tags;
     const double *bearings;
     const uint32_t *counters;           // the handle's per-frame counters (detections for tag_count), or null
-    int det_cap;                        // > 0: a handle's workspace, step s owns tags[s * det_cap ..] and bearings[s * det_cap * 4 ..] (the
-                                        // records' offsets are relative to the piece of a split batch that wrote them); 0: the records' offsets
+    int det_cap;                        // > 0: a handle's workspace, step s owns tags[s * det_cap ..] and bearings[s * det_cap * 4 ..] (what
+                                        // k_glue wrote into the records' offsets too: they are not read); 0: the records' offsets
     int pad;
 };
 struct RigArgs {

@@ -1162,7 +1162,7 @@ int ck_rig_calibrate_batch(ck_handle_t *h, const ck_rigcal_params_t *p, int32_t 
                            const ck_iso3_t *mounts0, ck_rigcal_result_t *results, double *poses_out);
 /* Copies to the host what the last ck_process_* call of exactly n frames left on the device for the pose solvers: records_out [n]
  * (n_tags, n_bearings, robot_to_cam, gyro, sign_change_error as that call wrote them; the offsets relative to tags_out and
- * bearings_out, packed in frame order, whichever piece of a split batch wrote a record), the known tags' field poses and the four
+ * bearings_out, packed in frame order), the known tags' field poses and the four
  * corner bearings of each.  *n_tags_out and *n_bearings_out are the totals, also when they do not fit.  Waits for the handle's
  * stream.  CK_EINVAL: a null pointer, n < 1, a negative capacity, a handle whose last pipeline call was not a ck_process_* call of
  * exactly n frames (the test ck_rig_process_last makes).  CK_ECAPACITY: tag_cap or bearing_cap (in tags, in bearings of 3 doubles)

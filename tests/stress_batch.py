@@ -1,7 +1,7 @@
-"""Randomised check that a frame's result does not depend on the call that carries it: whole batches (one stream, or split over
-two with CK_STREAMS=2 / CK_PARTS), calls of at most four frames (calls of up to 16 run their fit classes side by side on three streams) and
-single-frame calls must return the same bytes per frame — detections and 64-byte pose records.
-usage: [CK_STREAMS=2 CK_PARTS=3] python tests/stress_batch.py [cases] [seed]"""
+"""Randomised check that a frame's result does not depend on the call that carries it: whole batches, calls of at most four
+frames (calls of up to 16 run their fit classes side by side on three streams) and single-frame calls must return the same bytes
+per frame — detections and 64-byte pose records.
+usage: python tests/stress_batch.py [cases] [seed]"""
 import os, sys, json
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -39,7 +39,7 @@ def run(cases, seed):
             bad += 1
             print(json.dumps({"case": c, "w": w, "h": h, "n": n, "k": k, "i": i, "dec": dec}))
         det.close()
-    print(json.dumps({"cases": cases, "mismatching_cases": bad, "CK_STREAMS": os.environ.get("CK_STREAMS", "1"), "CK_PARTS": os.environ.get("CK_PARTS", "-")}))
+    print(json.dumps({"cases": cases, "mismatching_cases": bad}))
     return bad
 
 

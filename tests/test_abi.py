@@ -197,8 +197,8 @@ def test_create_refuses_bad_families(built):
 
 def test_product_library_reads_no_diagnostic_knob(built):
     """The drop-in must not change what it returns with the environment: the measurement / path-forcing knobs (CK_*_STOP_AFTER,
-    CK_FIT_SKIP, CK_FMERGE_CAP, CK_SEG_CHUNKS, ...) exist only in the -DCK_DIAG build (lib/diag/).  The product library names exactly
-    two variables: CK_POISON (allocation fill / guard pages) and CK_STREAMS (post-segmentation stages on two streams: same bytes)."""
+    CK_FIT_SKIP, CK_FMERGE_CAP, CK_EXT_BASE, ...) exist only in the -DCK_DIAG build (lib/diag/).  The product library names exactly
+    one variable: CK_POISON (allocation fill / guard pages)."""
     import re
     from conftest import DIAG_LIB
     from chalkydri_amd import _lib
@@ -206,11 +206,11 @@ def test_product_library_reads_no_diagnostic_knob(built):
     names = set(m.decode() for m in re.findall(rb"CK_[A-Z0-9_]{3,}(?=\x00)", prod))
     # (error-code names appear in ck_strerror's texts; anything else that looks like a knob is a failure)
     knobs = {n for n in names if not n.startswith(("CK_E", "CK_OK", "CK_FRAME_", "CK_HIP", "CK_ALLOC", "CK_ABI"))}
-    assert knobs <= {"CK_POISON", "CK_STREAMS"}, knobs
+    assert knobs <= {"CK_POISON"}, knobs
     assert b"STOP_AFTER" not in prod and b"CK_FIT_" not in prod and b"CK_FMERGE" not in prod and b"CK_EXT_BASE" not in prod
     assert b"k_ext_base" not in prod   # (the kernel that sets the knob's value is the diagnostics build's too)
     diag = open(DIAG_LIB, "rb").read()
-    for k in (b"CK_TILE_STOP_AFTER", b"CK_FMERGE_CAP", b"CK_FIT_FLAT", b"CK_FIT_SKIP", b"CK_PARTS", b"CK_EMIT_STOP_AFTER", b"CK_EXT_BASE"):
+    for k in (b"CK_TILE_STOP_AFTER", b"CK_FMERGE_CAP", b"CK_FIT_FLAT", b"CK_FIT_SKIP", b"CK_EMIT_STOP_AFTER", b"CK_EXT_BASE"):
         assert k in diag, k
 
 
@@ -252,7 +252,7 @@ def test_knob_table_says_how_each_site_reads_its_knob():
     (the path-forcing tests change the PER_CALL ones between two calls of one process)."""
     csrc = os.path.join(ROOT, "chalkydri_amd", "csrc")
     rows = re.findall(r"^\s*X\((\w+),\s*(-?\d+), (ONCE|PER_CALL),\s*\"[^\"]+\"\)", open(os.path.join(csrc, "ck_knobs.h")).read(), re.M)
-    assert len(rows) == 16 and {r[0] for r in rows if r[2] == "PER_CALL"} == {"FMERGE_CAP", "FMERGE_BAND_ROWS", "FIT_STOP_AFTER", "EXT_BASE",
+    assert len(rows) == 14 and {r[0] for r in rows if r[2] == "PER_CALL"} == {"FMERGE_CAP", "FMERGE_BAND_ROWS", "FIT_STOP_AFTER", "EXT_BASE",
                                                                            "CHUNK_STOP_AFTER"}
     lines = [l for f in os.listdir(csrc) if f.endswith(".hip") for l in open(os.path.join(csrc, f)).read().splitlines()]
     for name, _, read in rows:

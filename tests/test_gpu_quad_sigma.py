@@ -3,9 +3,6 @@ after it equals the oracle run on that image — thresh
 pose records; at quad_decimate 2 refinement and decode keep reading the unfiltered frame, at quad_decimate 1 they read Q.  With
 the filter off nothing changes."""
 import ctypes as C
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -18,7 +15,6 @@ from chalkydri_amd._lib import ChalkydriError
 from chalkydri_amd.detector import AprilTagDetector
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIGMAS = [0.5, 0.8, 1.0, 1.6, 3.0, 8.0, -0.8, -1.5]
 
 
@@ -214,38 +210,6 @@ def test_device_frames_and_ingest_ring_equal_host_frames(built, dec):
     assert key(got3) == key(want) and list(st3) == list(wst)
     ring.close()
     det.close(); det2.close()
-
-
-SPLIT = r"""
-import sys, hashlib
-sys.path.insert(0, %r); sys.path.insert(0, %r)
-import numpy as np
-from test_gpu_quad_sigma import _scene
-from chalkydri_amd.apriltags import AprilTags
-n = 6
-for dec in (1, 2):
-    frames, gyros, layout, calib, r2c = _scene(n, seed=900)
-    task = AprilTags(640, 480, layout, calib, r2c, cam_id=1, max_batch=n, quad_decimate=dec, quad_sigma=0.8)
-    recs, valid = task.process_batch(frames, gyros)
-    dets = task.detector.detect_batch(frames, cap=32)
-    hh = hashlib.sha256()
-    for r in recs: hh.update(bytes(r))
-    for fr in dets:
-        for d in fr: hh.update(np.asarray(d.corners(), np.float64).tobytes())
-    print("HASH", dec, hh.hexdigest(), int(valid.sum()))
-"""
-
-
-def test_split_streams_give_the_same_bytes(built):
-    outs = []
-    for streams in ("1", "2"):
-        env = dict(os.environ, CK_STREAMS=streams)
-        r = subprocess.run([sys.executable, "-c", SPLIT % (ROOT, os.path.join(ROOT, "tests"))], capture_output=True, text=True, env=env,
-                           timeout=600)
-        assert r.returncode == 0, r.stderr[-2000:]
-        outs.append([ln for ln in r.stdout.splitlines() if ln.startswith("HASH")])
-    assert len(outs[0]) == 2 and outs[0] == outs[1]
-    assert all(int(ln.split()[3]) == 6 for ln in outs[0])
 
 
 @pytest.mark.parametrize("dec", [1, 2])

@@ -4,7 +4,6 @@ frames â€” detections, pose records, the ingest ring, the quad-image settings â€
 Nothing here has a tolerance: nothing here is floating point before the detector, and the detector is deterministic."""
 import ctypes as C
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -251,8 +250,7 @@ def test_raw_ingest_ring_matches_the_plain_path(built):
 
 def settings_check():
     """quad_decimate 2 and quad_sigma 0.8 behind a raw upload equal the same settings behind ck_upload_frames; a handle that
-    served raw calls returns from a plain detect_batch what an untouched handle returns.  (Also the child of the CK_STREAMS=2
-    test: the variable is read once per process.)"""
+    served raw calls returns from a plain detect_batch what an untouched handle returns."""
     from chalkydri_amd.detector import AprilTagDetector
     n = 2
     frames, _, _, _, _ = wall_frames(n)
@@ -278,12 +276,6 @@ def settings_check():
 
 def test_settings_behind_a_raw_upload(built):
     assert settings_check()
-
-
-def test_two_streams_behind_a_raw_upload(built):
-    env = dict(os.environ, CK_STREAMS="2")
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), "settings"], env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "settings ok" in r.stdout, (r.returncode, r.stdout[-800:], r.stderr[-1500:])
 
 
 def test_misuse_is_refused_and_the_handle_stays_usable(built):
@@ -348,8 +340,3 @@ def test_stress_helping(built):
     out = S.run(40, 7)
     assert out["mismatching"] == 0 and out["device_cases"] == 10, out
 
-
-if __name__ == "__main__":
-    if sys.argv[1:] == ["settings"]:
-        settings_check()
-        print("settings ok")

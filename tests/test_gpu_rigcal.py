@@ -208,22 +208,10 @@ def _tasks(r2c1, max_batch):
             for c, (w, h, f, r2c) in enumerate(CAMS)]
 
 
-def _pose_inputs_bytes(K, tasks, n):
-    out = b""
-    for t in tasks:
-        steps, rec = K.last_pose_inputs(t.detector, n)
-        out += b"".join(bytes(tag) for tg, _ in steps for tag in tg) + b"".join(b.tobytes() for _, b in steps)
-        out += np.array([(r.n_tags, r.n_bearings, r.tag_offset, r.bearing_offset) for r in rec], np.int32).tobytes()
-    return out
-
-
 def test_last_pose_inputs(K, rig_scene):
     """after AprilTagsRig.process_batch the accessor returns, per camera, the known tags and corner bearings with which
-    RigSolver.solve_batch reproduces last_results; the packed offsets; CK_ECAPACITY with the totals; CK_EINVAL after a plain detect;
-    the same bytes from a child process that runs the batch split over two streams (CK_STREAMS=2)"""
+    RigSolver.solve_batch reproduces last_results; the packed offsets; CK_ECAPACITY with the totals; CK_EINVAL after a plain detect"""
     import ctypes as C
-    import hashlib
-    import subprocess
     from chalkydri_amd import ChalkydriError
     from chalkydri_amd.rig import AprilTagsRig, RigSolver
     tasks, steps = rig_scene
@@ -249,23 +237,10 @@ def test_last_pose_inputs(K, rig_scene):
     assert L.ck_last_pose_inputs(tasks[0].detector._h, 4, rec, one, 0, b.ctypes.data, 0, C.byref(nt), C.byref(nb)) == A.CK_ECAPACITY
     assert nt.value == sum(len(t) for t, _ in per_cam[0][0]) and nb.value == 4 * nt.value
     assert L.ck_last_pose_inputs(tasks[0].detector._h, 3, rec, one, 0, b.ctypes.data, 0, C.byref(nt), C.byref(nb)) == A.CK_EINVAL
-    whole = hashlib.sha256(_pose_inputs_bytes(K, tasks, 4)).hexdigest()
     tasks[1].detector.detect_batch(frames[1])
     with pytest.raises(ChalkydriError) as e:
         K.last_pose_inputs(tasks[1].detector, 4)
     assert e.value.code == A.CK_EINVAL
-    child = ("import sys, hashlib, numpy as np; sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + '/tests')\n"
-             "import test_gpu_rigcal as T\nfrom chalkydri_amd import rigcal as K\nfrom chalkydri_amd.rig import AprilTagsRig\n"
-             "d = np.load(sys.argv[2])\ntasks = T._tasks(T.CAMS[1][3], 4)\n"
-             "AprilTagsRig(tasks, rig_id=42).process_batch([d['f0'], d['f1']], list(d['gyro']))\n"
-             "print('HASH', hashlib.sha256(T._pose_inputs_bytes(K, tasks, 4)).hexdigest())\n")
-    import tempfile
-    with tempfile.TemporaryDirectory() as tmp:
-        np.savez(os.path.join(tmp, "frames.npz"), f0=frames[0], f1=frames[1], gyro=np.array(gyro))
-        root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-        r = subprocess.run([sys.executable, "-c", child, root, os.path.join(tmp, "frames.npz")], capture_output=True, text=True, timeout=120,
-                           env=dict(os.environ, CK_STREAMS="2"))
-    assert r.returncode == 0 and ("HASH " + whole) in r.stdout, (r.stdout[-500:], r.stderr[-1500:])
 
 
 # ck_rig_calibrate_batch against the twin from the host rig solver's starts, measured when the test was written on this capture: 1.9e-15
