@@ -177,6 +177,8 @@ struct ck_handle {
     size_t ring_len;
     // later stages
     ck_stage_ws ws;      // workspace of clusters / quads / decode
+    int pts_distinct;    // what ck_launch_clusters says of the points it left in ws.d_points: 1 = no coordinate twice in a cluster (k_emit2
+                         // merged the diagonal twins, the only points that share one), so the quad fit's front half searches for none
     ck_stage_ms_t last_ms;
     ck_dev_family *d_fams;
     uint64_t *d_fam_codes; // every family's code table, one after the other (ck_dev_family::codes point into it)

@@ -19,7 +19,7 @@
     X(FMERGE_CAP,         0, PER_CALL, "roots k_fmerge's LDS path holds, when smaller than the computed capacity: forces the global-memory path") \
     X(FMERGE_BAND_ROWS,   0, PER_CALL, "tile rows per band of the segmentation's merge; 0 = the computed height") \
     X(EMIT_STOP_AFTER,   99, ONCE,     "k_emit2 ends after phase k (k_clusters.hip); 99 = all of it") \
-    X(EMIT_TWINS,         1, ONCE,     "0 = k_emit2 stores every point on its own instead of diagonal twins as one word") \
+    X(EMIT_TWINS,         1, ONCE,     "0 = k_emit2 stores every point on its own instead of diagonal twins as one word; 2 = twins as one word, but the quad fit keeps the duplicate removal it needs for 0 (FitArgs::distinct off)") \
     X(EMIT_STAGE4,        1, ONCE,     "0 = k_emit2 stages every pixel on its own instead of aligned groups of four") \
     X(FIT_SPLIT,          3, ONCE,     "bit 0 = 513..1024 points have a size class of their own, bit 1 = up to 256 points have") \
     X(FIT_FLAT,           1, ONCE,     "the split fit (k_seq, k_chunk, k_tail): 0 never, 2 always, 1 = for the calls it pays for") \

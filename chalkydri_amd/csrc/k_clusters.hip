@@ -596,7 +596,8 @@ int ck_launch_clusters(ck_handle *h, int n) {
     a.w = h->qw; a.h = h->qh; a.tiles_x = (h->qw + ETW - 1) / ETW; a.tiles_y = (h->qh + ETH - 1) / ETH;
     a.min_comp = h->cfg.min_component_px; a.ws = ws; a.ccl_tiles_x = h->tiles_x;
     { static const int stop_after = ck_knob(CK_KNOB_EMIT_STOP_AFTER); a.stop_after = stop_after; }
-    { static const int twins = ck_knob(CK_KNOB_EMIT_TWINS); a.twins = twins; } // (diagnostics: 0 = every point on its own, for A/B)
+    // (diagnostics: 0 = every point on its own, for A/B; 2 = twins merged, but the quad fit is not told and keeps its duplicate removal)
+    { static const int twins = ck_knob(CK_KNOB_EMIT_TWINS); a.twins = twins; h->pts_distinct = twins == 1; }
     { static const int stage4 = ck_knob(CK_KNOB_EMIT_STAGE4); a.stage4 = stage4; } // (diagnostics: 0 = every pixel staged on its own, for A/B)
     const int xcd_map = n >= 16 ? 1 : 0; // frames dealt to XCDs: batches of 16 frames and more
     const unsigned grid = xcd_map ? (unsigned)(((n + 7) / 8) * 8 * a.tiles_x * a.tiles_y) : (unsigned)(a.tiles_x * a.tiles_y * n);

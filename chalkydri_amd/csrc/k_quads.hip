@@ -13,7 +13,12 @@
 //   1. points arrive packed (4 bytes, ck_internal.h); bounding box and border direction are integer reductions (DPP);
 //   2. exact 60-bit angular keys -> bucketed rank sort (counting pass over angle buckets + ranks inside a bucket; LDS
 //      for the classes whose keys fit in registers, a per-workgroup L2-resident scratch for the large one; the bitonic
-//      network remains as the fallback for clusters whose angles pile up) -> duplicate coordinates dropped (ballot scan);
+//      network remains as the fallback for clusters whose angles pile up) -> duplicate coordinates dropped (ballot scan).
+//      On DISTINCT points (FitArgs::distinct: k_emit2 merged the diagonal twins, the only points of a cluster that share a coordinate;
+//      every call of the product) equal keys cannot occur: the ranks need no tie-break, the sort's last placement leaves the 26-bit
+//      (x, y) words where the duplicate removal would have left them, and that pass (front_pack) is not run; a cluster of fewer than 24
+//      words leaves before its bounding box, and k_seq asks for its sequence's place as soon as the border direction is accepted.  The
+//      flag is a run-time, wave-uniform branch inside the one set of instantiations; with it off every line of the other path runs;
 //   3. gradient weights: one u16 gather per point from the weight image k_weight_image wrote;
 //   4. chunk loop: moment prefix sums over the chunk + halo (DPP wave scans; first-order sums in 32 bit), windowed
 //      line-fit error, 7-tap smoothing fused with the maxima test, maxima appended to a per-cluster list;
@@ -42,6 +47,8 @@ struct FitArgs {
     double cos_critical, max_mse;
     ck_stage_ws ws;
     int stop_after;         // diagnostics (CK_FIT_STOP_AFTER): end every cluster after phase k; 99 = run everything
+    int distinct;           // no coordinate comes twice in a cluster (k_emit2 merged the diagonal twins: ck_handle::pts_distinct): the sort
+                            // leaves the (x, y) words, nothing is searched for duplicates.  0: the path for points of any origin
     const uint32_t *list;   // work list of this size class: frame << 20 | cluster index
     const uint32_t *list_count;
     uint32_t *head;         // dequeue counter
@@ -363,7 +370,7 @@ __device__ __forceinline__ void sort_registers(unsigned long long (&k)[EPL], uns
 // direction flag per stage, the partners' addresses) must not be carried through every cluster of the loop around it (loop_tid).
 template <int NTH, int EPL, bool RARE>
 __device__ __forceinline__ long long keys_sort(unsigned long long *sKeys, long long *sScratch, int sz0, int xmin, int xmax, int ymin, int ymax,
-                                               int normal_ok, int reversed_ok, bool do_sort = true) {
+                                               int normal_ok, int reversed_ok, int distinct, bool do_sort = true) {
     using B = Block<NTH>;
     const int tid = RARE ? loop_tid() : (int)threadIdx.x;
     unsigned long long kreg[EPL];
@@ -386,8 +393,15 @@ __device__ __forceinline__ long long keys_sort(unsigned long long *sKeys, long l
     if (do_sort && ((dot < 0) ? reversed_ok : normal_ok)) { // uniform: skip the sort when the border direction is rejected anyway
         sort_registers<NTH, EPL>(kreg, sKeys, tid);
         __syncthreads();
+        if (distinct) { // (uniform) every exchange has been read: the words go where front_pack would have left them
+            uint32_t *sXY = reinterpret_cast<uint32_t *>(sKeys);
 #pragma unroll
-        for (int e = 0; e < EPL; e++) sKeys[tid * EPL + e] = kreg[e];
+            for (int e = 0; e < EPL; e++)
+                if (tid * EPL + e < sz0) sXY[tid * EPL + e] = (uint32_t)kreg[e] & 0x3FFFFFFu;
+        } else {
+#pragma unroll
+            for (int e = 0; e < EPL; e++) sKeys[tid * EPL + e] = kreg[e];
+        }
     }
     return dot;
 }
@@ -400,10 +414,10 @@ __device__ __forceinline__ long long keys_sort(unsigned long long *sKeys, long l
 // The points come in registers (rawp: the thread's packed points tid, tid + NTH, ...; the staged form is two shifts away), so the
 // key array is touched for the first time by the scatter into the buckets.
 constexpr int BUCKET_LIMIT = 32;
-template <int NTH, int EPLS>
+template <int NTH, int EPLS, class ACC>
 __device__ __forceinline__ long long keys_bucket_sort(const ck_packed_point (&rawp)[EPLS], unsigned long long *sKeys, uint32_t *hist /* [nb + 1] */,
                                                       long long *sScratch, int sz0, int xmin, int xmax, int ymin, int ymax, int normal_ok,
-                                                      int reversed_ok, bool do_sort, bool *done) {
+                                                      int reversed_ok, int distinct, bool do_sort, bool *done, ACC &accepted) {
     using B = Block<NTH>;
     const int tid = loop_tid();
     int n2 = NTH;
@@ -430,6 +444,7 @@ __device__ __forceinline__ long long keys_bucket_sort(const ck_packed_point (&ra
     dot = B::reduce_add(dot, sScratch);
     *done = true;
     if (!do_sort || !((dot < 0) ? reversed_ok : normal_ok)) return dot; // uniform: rejected by border direction anyway
+    accepted();
     if constexpr (B::NW == 1) B::sync(); // histogram zeroed (a larger workgroup has met at the barriers of the sum above)
 #pragma unroll
     for (int e = 0; e < EPLS; e++) {
@@ -460,27 +475,42 @@ __device__ __forceinline__ long long keys_bucket_sort(const ck_packed_point (&ra
         if (i < sz0) sKeys[hist[meta[e] >> 16] + (meta[e] & 0xFFFFu)] = kreg[e];
     }
     B::sync();
+    // distinct (uniform): no two keys are equal, so a key's rank is the number of smaller ones and the arrival index breaks no tie; and
+    // behind the barrier, where every bucket copy has been read, the (x, y) words take the first half of the key array — what
+    // front_pack would have made of the sorted keys.
     uint32_t pos[EPLS];
 #pragma unroll
     for (int e = 0; e < EPLS; e++) {
         const int i = tid + e * NTH;
         pos[e] = 0;
         if (i < sz0) {
-            const uint32_t b = meta[e] >> 16, s0 = hist[b], s1 = hist[b + 1], mine = s0 + (meta[e] & 0xFFFFu);
+            const uint32_t b = meta[e] >> 16, s0 = hist[b], s1 = hist[b + 1];
             const unsigned long long key = kreg[e];
             uint32_t rank = 0;
-            for (uint32_t j = s0; j < s1; j++) {
-                const unsigned long long o = sKeys[j];
-                rank += (o < key || (o == key && j < mine)) ? 1u : 0u;
+            if (distinct) {
+                for (uint32_t j = s0; j < s1; j++) rank += sKeys[j] < key ? 1u : 0u;
+            } else {
+                const uint32_t mine = s0 + (meta[e] & 0xFFFFu);
+                for (uint32_t j = s0; j < s1; j++) {
+                    const unsigned long long o = sKeys[j];
+                    rank += (o < key || (o == key && j < mine)) ? 1u : 0u;
+                }
             }
             pos[e] = s0 + rank;
         }
     }
     B::sync();
+    uint32_t *sXY = reinterpret_cast<uint32_t *>(sKeys);
 #pragma unroll
     for (int e = 0; e < EPLS; e++) {
         const int i = tid + e * NTH;
-        if (i < sz0) sKeys[pos[e]] = kreg[e];
+        if (i < sz0) {
+            // (the word is formed ahead of the uniform branch: formed inside it, the two classes of 16 keys per thread spill some 2 400 and
+            // 3 700 registers in both kernels — seen in the code objects' notes, the cause not looked into)
+            const uint32_t w = (uint32_t)kreg[e] & 0x3FFFFFFu;
+            if (distinct) sXY[pos[e]] = w;
+            else sKeys[pos[e]] = kreg[e];
+        }
     }
     return dot;
 }
@@ -491,10 +521,10 @@ __device__ __forceinline__ long long keys_bucket_sort(const ck_packed_point (&ra
 // so the bitonic fallback can still start from them.
 constexpr int BUCKET_LIMIT_L = 96;
 // NOLIMIT: the largest class has no other sort to fall back on; its rank pass takes whatever the buckets hold
-template <int NTH, bool NOLIMIT>
+template <int NTH, bool NOLIMIT, class ACC>
 __device__ __forceinline__ long long keys_bucket_sort_global(unsigned long long *sKeys, uint32_t *hist /* [2 * (1024 + 1)] */, long long *sScratch,
                                                              unsigned long long *gtmp, int sz0, int xmin, int xmax, int ymin, int ymax,
-                                                             int normal_ok, int reversed_ok, bool do_sort, bool *done) {
+                                                             int normal_ok, int reversed_ok, int distinct, bool do_sort, bool *done, ACC &accepted) {
     using B = Block<NTH>;
     const int tid = threadIdx.x;
     constexpr int nb = 1024, lgq = 7;
@@ -519,6 +549,7 @@ __device__ __forceinline__ long long keys_bucket_sort_global(unsigned long long 
     dot = B::reduce_add(dot, sScratch);
     *done = true;
     if (!do_sort || !((dot < 0) ? reversed_ok : normal_ok)) return dot;
+    accepted();
     __syncthreads();
     {
         constexpr int per = nb / NTH;
@@ -539,6 +570,17 @@ __device__ __forceinline__ long long keys_bucket_sort_global(unsigned long long 
         gtmp[atomicAdd(&cursor[bucket_of(key)], 1u)] = key;
     }
     __syncthreads(); // workgroup-scope release/acquire: the slice written above is read by other waves below
+    if (distinct) { // (uniform) as in keys_bucket_sort; the staged points were read for the last time ahead of the barrier above
+        uint32_t *sXY = reinterpret_cast<uint32_t *>(sKeys);
+        for (int j = tid; j < sz0; j += NTH) {
+            const unsigned long long key = gtmp[j];
+            const uint32_t b = bucket_of(key), s0 = hist[b], s1 = hist[b + 1];
+            uint32_t rank = 0;
+            for (uint32_t k = s0; k < s1; k++) rank += gtmp[k] < key ? 1u : 0u;
+            sXY[s0 + rank] = (uint32_t)key & 0x3FFFFFFu;
+        }
+        return dot;
+    }
     for (int j = tid; j < sz0; j += NTH) {
         const unsigned long long key = gtmp[j];
         const uint32_t b = bucket_of(key), s0 = hist[b], s1 = hist[b + 1];
@@ -634,10 +676,10 @@ __device__ __forceinline__ Box front_box(const ck_packed_point (&rawp)[CAP / NTH
 // border-direction sum (on every thread); the keys are sorted unless its sign is one the families do not want (or !do_sort).
 // The classes whose keys fit in registers (MLDS) bring their points in registers too (rawp); only the bitonic network, which owns
 // consecutive slots, needs them staged in the key array, and stages them itself before it starts.
-template <int NTH, int CAP, bool MLDS, bool GK, class BAR>
+template <int NTH, int CAP, bool MLDS, bool GK, class BAR, class ACC>
 __device__ __forceinline__ long long front_sort(const ck_packed_point (&rawp)[CAP / NTH <= RAWP_MAX ? CAP / NTH : 1], unsigned long long *sKeys,
                                                 uint32_t *hist, long long *sScratch, unsigned long long *scratch8, int sz0, const Box &b,
-                                                int normal_ok, int reversed_ok, bool do_sort) {
+                                                int normal_ok, int reversed_ok, int distinct, bool do_sort, ACC &&accepted) {
     constexpr int EPLS = CAP / NTH;
     static_assert(MLDS == (EPLS <= RAWP_MAX), "the classes with their keys in registers are the ones with their points in registers");
     int n2 = NTH;
@@ -646,7 +688,7 @@ __device__ __forceinline__ long long front_sort(const ck_packed_point (&rawp)[CA
     bool sorted = false;
     long long dot;
     if constexpr (MLDS) { // keys fit in registers (CAP / NTH <= 16)
-        dot = keys_bucket_sort<NTH, EPLS>(rawp, sKeys, hist, sScratch, sz0, b.xmin, b.xmax, b.ymin, b.ymax, normal_ok, reversed_ok, do_sort, &sorted);
+        dot = keys_bucket_sort<NTH, EPLS, ACC>(rawp, sKeys, hist, sScratch, sz0, b.xmin, b.xmax, b.ymin, b.ymax, normal_ok, reversed_ok, distinct, do_sort, &sorted, accepted);
         if (!sorted) { // (uniform) the bucket sort gave up before it wrote a key
             const int tid = loop_tid();
 #pragma unroll
@@ -658,15 +700,15 @@ __device__ __forceinline__ long long front_sort(const ck_packed_point (&rawp)[CA
         }
     } else {
         BAR::sync(); // points staged by other threads
-        dot = keys_bucket_sort_global<NTH, GK>(sKeys, hist, sScratch, scratch8, sz0, b.xmin, b.xmax, b.ymin, b.ymax, normal_ok, reversed_ok, do_sort, &sorted);
+        dot = keys_bucket_sort_global<NTH, GK, ACC>(sKeys, hist, sScratch, scratch8, sz0, b.xmin, b.xmax, b.ymin, b.ymax, normal_ok, reversed_ok, distinct, do_sort, &sorted, accepted);
     }
     if (sorted || GK) {}
-    else if (EPLS >= 32 && epl == 32) dot = keys_sort<NTH, (EPLS >= 32 && !GK ? 32 : 1), MLDS>(sKeys, sScratch, sz0, b.xmin, b.xmax, b.ymin, b.ymax, normal_ok, reversed_ok, do_sort);
-    else if (EPLS >= 16 && epl == 16) dot = keys_sort<NTH, (EPLS >= 16 && !GK ? 16 : 1), MLDS>(sKeys, sScratch, sz0, b.xmin, b.xmax, b.ymin, b.ymax, normal_ok, reversed_ok, do_sort);
-    else if (EPLS >= 8 && epl == 8) dot = keys_sort<NTH, (EPLS >= 8 && !GK ? 8 : 1), MLDS>(sKeys, sScratch, sz0, b.xmin, b.xmax, b.ymin, b.ymax, normal_ok, reversed_ok, do_sort);
-    else if (EPLS >= 4 && epl == 4) dot = keys_sort<NTH, (EPLS >= 4 && !GK ? 4 : 1), MLDS>(sKeys, sScratch, sz0, b.xmin, b.xmax, b.ymin, b.ymax, normal_ok, reversed_ok, do_sort);
-    else if (EPLS >= 2 && epl == 2) dot = keys_sort<NTH, (EPLS >= 2 && !GK ? 2 : 1), MLDS>(sKeys, sScratch, sz0, b.xmin, b.xmax, b.ymin, b.ymax, normal_ok, reversed_ok, do_sort);
-    else dot = keys_sort<NTH, 1, MLDS>(sKeys, sScratch, sz0, b.xmin, b.xmax, b.ymin, b.ymax, normal_ok, reversed_ok, do_sort);
+    else if (EPLS >= 32 && epl == 32) dot = keys_sort<NTH, (EPLS >= 32 && !GK ? 32 : 1), MLDS>(sKeys, sScratch, sz0, b.xmin, b.xmax, b.ymin, b.ymax, normal_ok, reversed_ok, distinct, do_sort);
+    else if (EPLS >= 16 && epl == 16) dot = keys_sort<NTH, (EPLS >= 16 && !GK ? 16 : 1), MLDS>(sKeys, sScratch, sz0, b.xmin, b.xmax, b.ymin, b.ymax, normal_ok, reversed_ok, distinct, do_sort);
+    else if (EPLS >= 8 && epl == 8) dot = keys_sort<NTH, (EPLS >= 8 && !GK ? 8 : 1), MLDS>(sKeys, sScratch, sz0, b.xmin, b.xmax, b.ymin, b.ymax, normal_ok, reversed_ok, distinct, do_sort);
+    else if (EPLS >= 4 && epl == 4) dot = keys_sort<NTH, (EPLS >= 4 && !GK ? 4 : 1), MLDS>(sKeys, sScratch, sz0, b.xmin, b.xmax, b.ymin, b.ymax, normal_ok, reversed_ok, distinct, do_sort);
+    else if (EPLS >= 2 && epl == 2) dot = keys_sort<NTH, (EPLS >= 2 && !GK ? 2 : 1), MLDS>(sKeys, sScratch, sz0, b.xmin, b.xmax, b.ymin, b.ymax, normal_ok, reversed_ok, distinct, do_sort);
+    else dot = keys_sort<NTH, 1, MLDS>(sKeys, sScratch, sz0, b.xmin, b.xmax, b.ymin, b.ymax, normal_ok, reversed_ok, distinct, do_sort);
     return dot;
 }
 
@@ -1134,6 +1176,7 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(WPS, 8))) v
         PROF(15);
 
         if (a.stop_after == 0) continue;
+        if (a.distinct && sz0 < 24) continue; // the exit behind the duplicate removal, known here: the points are the distinct ones
         // ---- 1. bounding box + border direction ----------------------------------------------------------
         constexpr int EPL0 = CAP / NTH;
         ck_packed_point rawp[EPL0 <= RAWP_MAX ? EPL0 : 1];
@@ -1146,17 +1189,17 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(WPS, 8))) v
         if ((box.xmax - box.xmin) * (box.ymax - box.ymin) < a.min_tag_width) continue;
         if (a.stop_after == 10) continue;
         const long long dot = front_sort<NTH, CAP, MLDS, GK, FenceBarrier>(rawp, sKeys, reinterpret_cast<uint32_t *>(sPraw), sScratch, scratch8, sz0, box,
-                                                                          a.normal_ok, a.reversed_ok, a.stop_after != 11);
+                                                                          a.normal_ok, a.reversed_ok, a.distinct, a.stop_after != 11, [] {});
         const int reversed = dot < 0;
         PROF(0);
         if (reversed && !a.reversed_ok) continue;
         if (!reversed && !a.normal_ok) continue;
         if (a.stop_after == 1 || a.stop_after == 11) continue;
 
-        // ---- 2. duplicate removal, packing to (x,y) ----------------------------------------------------------------
+        // ---- 2. duplicate removal, packing to (x,y): the sort has done it where the points are distinct -------------------
         __syncthreads();
         PROF(1);
-        const int sz = front_pack<NTH, CAP / NTH, FenceBarrier>(sKeys, sz0, iscr, reinterpret_cast<uint32_t *>(sPraw));
+        const int sz = a.distinct ? sz0 : front_pack<NTH, CAP / NTH, FenceBarrier>(sKeys, sz0, iscr, reinterpret_cast<uint32_t *>(sPraw));
         PROF(2);
         if (sz < 24) continue;
         const int ksz = sz / 12 < 20 ? sz / 12 : 20; // half-width of the line-fit window
@@ -1517,27 +1560,36 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(WPS, 8))) v
             if (tid == 0) *cstate = 0u; // rejected unless the end says otherwise (same thread: ordered)
             if (sz0 > CAP || sz0 < 1) continue; // cannot happen: the class lists are built from the counts
             if (a.stop_after == 0) continue;
+            if (a.distinct && sz0 < 24) continue; // the exit behind the duplicate removal, known here: the points are the distinct ones
             // ---- 1. bounding box ---------------------------------------------------------------------------------------------
             const Box box = front_box<NTH, CAP>(rawp, pts, sz0, sKeys, iscr);
             if ((box.xmax - box.xmin) * (box.ymax - box.ymin) < a.min_tag_width) continue;
             if (a.stop_after == 10) continue;
-            // ---- 2. border direction, sort ---------------------------------------------------------------------------------------
+            // ---- 2. border direction, sort.  Distinct points: the cluster's size is final, and behind the border direction nothing rejects it any
+            // more, so thread 0 asks for the sequence's place in the frame (step 4) as soon as the direction is accepted; the answer is not
+            // looked at before the sequence is written, and in the classes of one wave, whose barriers wait for no memory operation, the
+            // round trip runs under the sort.  (The larger workgroups wait for it at their next __syncthreads, as they did at the end.) ---------
+            uint32_t *const ext_counter = ws.d_counters + (size_t)frame * CK_CNT_STRIDE + CK_CNT_EXT;
+            uint32_t es_early = 0;
+            auto reserve = [&] {
+                if (a.distinct && a.stop_after > 2 && loop_tid() == 0) es_early = atomicAdd(ext_counter, (uint32_t)(sz0 + CK_EXT_HALO));
+            };
             const long long dot = front_sort<NTH, CAP, MLDS, GK, B>(rawp, sKeys, reinterpret_cast<uint32_t *>(sHist), sScratch, scratch8, sz0, box,
-                                                                    a.normal_ok, a.reversed_ok, a.stop_after != 11);
+                                                                    a.normal_ok, a.reversed_ok, a.distinct, a.stop_after != 11, reserve);
             const int reversed = dot < 0;
             if (reversed && !a.reversed_ok) continue;
             if (!reversed && !a.normal_ok) continue;
             if (a.stop_after == 1 || a.stop_after == 11) continue;
-            // ---- 3. duplicate removal, packing to (x, y) -------------------------------------------------------------------------
+            // ---- 3. duplicate removal, packing to (x, y): the sort has done it where the points are distinct -----------------------
             B::sync();
-            const int sz = front_pack<NTH, EPL, B>(sKeys, sz0, iscr, reinterpret_cast<uint32_t *>(sHist));
+            const int sz = a.distinct ? sz0 : front_pack<NTH, EPL, B>(sKeys, sz0, iscr, reinterpret_cast<uint32_t *>(sHist));
             if (sz < 24) continue;
             const int ksz = sz / 12 < 20 ? sz / 12 : 20; // half-width of the line-fit window
             if (ksz < 2) continue;
             if (a.stop_after == 2) continue;
             // ---- 4. the extended sequence.  Its place in the frame is handed out in the order the clusters get here (k_chunk and k_tail
             // do not care where a cluster lies), so the positions k_chunk works through are all live ones --------------------------
-            if (tid == 0) sWork = atomicAdd(ws.d_counters + (size_t)frame * CK_CNT_STRIDE + CK_CNT_EXT, (uint32_t)(sz + CK_EXT_HALO));
+            if (tid == 0) sWork = a.distinct ? es_early : atomicAdd(ext_counter, (uint32_t)(sz + CK_EXT_HALO));
             B::sync();
             const uint32_t es32 = sWork;
             uint32_t *exy = ws.d_ext_xy + (size_t)frame * ws.ext_cap + es32;
@@ -2231,6 +2283,7 @@ int ck_launch_fit_quads(ck_handle *h, const ck_dev_image &qimg, const ck_dev_ima
     if (a.min_tag_width < 3) a.min_tag_width = 3;
     a.ws = ws; a.list_cap = list_cap;
     a.stop_after = ck_knob(CK_KNOB_FIT_STOP_AFTER); // (read per call)
+    a.distinct = h->pts_distinct; // (this function's one caller, run_pipeline, has just had ck_launch_clusters fill ws.d_points)
     ck_launch_ext_base(h, n); // (diagnostics library, CK_EXT_BASE; the product launches nothing)
     auto use_list = [&](int l) { a.list = fl.lists + (size_t)l * list_cap; a.list_count = fl.list_counts + l; a.head = fl.heads + l; };
     auto launch_wimg = [&](hipStream_t st) {
