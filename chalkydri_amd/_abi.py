@@ -203,6 +203,11 @@ class RawFormat(C.Structure):
     _fields_ = [("fourcc", C.c_uint32), ("orientation", C.c_int32)]
 
 
+class RawPlanes(C.Structure):   # ck_raw_planes_t
+    _fields_ = [("sw", C.c_int32), ("sh", C.c_int32), ("cw", C.c_int32), ("ch", C.c_int32), ("offset", C.c_int64 * 3),
+                ("row_stride", C.c_int32 * 3), ("step", C.c_int32 * 3), ("pad", C.c_int32 * 2), ("bytes", C.c_int64)]
+
+
 class PreviewParams(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("width", "height", "quality", "restart_rows", "overlay", "pad")]
 
@@ -310,7 +315,7 @@ assert C.sizeof(VisionMeasurement) == 64  # crates/whacknet/src/lib.rs:92-95
 assert C.sizeof(TagPoseParams) == 112 and C.sizeof(TagPose) == 296
 assert C.sizeof(Camera) == 80
 assert C.sizeof(JpegFrame) == 16 and C.sizeof(JpegInfo) == 32
-assert C.sizeof(RawFormat) == 8
+assert C.sizeof(RawFormat) == 8 and C.sizeof(RawPlanes) == 80
 assert C.sizeof(PreviewParams) == 24
 assert C.sizeof(Rect) == 16 and C.sizeof(ExposureStats) == 6416 and C.sizeof(ExposureParams) == 96
 assert C.sizeof(TriOtsuParams) == 16 and C.sizeof(TriOtsuInfo) == 160
@@ -354,6 +359,9 @@ CK_PREVIEW_OK, CK_PREVIEW_TRUNCATED = 0, 1
 CK_ORIENT_NONE, CK_ORIENT_CLOCKWISE, CK_ORIENT_ROTATE_180, CK_ORIENT_COUNTERCLOCKWISE = 0, 1, 2, 3
 ORIENTATIONS = {"none": CK_ORIENT_NONE, "clockwise": CK_ORIENT_CLOCKWISE, "rotate-180": CK_ORIENT_ROTATE_180,
                 "counterclockwise": CK_ORIENT_COUNTERCLOCKWISE}
+# or-ed into ck_raw_format_t.orientation: the chroma planes behind the luma plane are part of every frame (PLANAR_FOURCCS only)
+CK_RAW_PLANES = 0x100
+PLANAR_FOURCCS = ("NV12", "NV21", "I420", "YV12")
 # the fourccs of the raw entry points (ck_raw_layout answers CK_EUNSUPPORTED to every other one)
 RAW_FOURCCS = ("GREY", "GRAY", "Y800", "NV12", "NV21", "I420", "YV12", "YUYV", "YUY2", "UYVY", "RGB3", "RGB ", "BGR3", "BGR ",
                "RGBA", "BGRA")

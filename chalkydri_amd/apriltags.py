@@ -33,12 +33,14 @@ def load_field_layout(path_or_dict):
 class AprilTags:
     def __init__(self, width, height, field, calib, robot_to_cam, cam_id=0, family="tag36h11", bits_corrected=3,
                  max_batch=1, device=0, quad_sigma=0.0, fourcc=None, orientation="none", auto_exposure=False, exposure0=1.0,
-                 exposure_params=None, jpeg_color=False, corner_subpix=None, blobs=None, **cfg):
+                 exposure_params=None, jpeg_color=False, corner_subpix=None, blobs=None, planes=False, **cfg):
         """width x height is the image the detector sees, and calib its intrinsics: with an `orientation` ("none", "clockwise",
         "rotate-180", "counterclockwise": the reference's VideoOrientation names) those of the ORIENTED image.  `fourcc` names the
         raw format of the camera's frames for process_raw_batch ("YUYV", "RGB3", ...; None: 8-bit luma), or "MJPG" / "JPEG": the
         camera delivers one JPEG per frame (what the reference's USB cameras do at full rate), decoded and turned on the device;
         with jpeg_color=True the decode keeps the frames' chroma on the device, so that preview(color=True) works for them too.
+        planes=True with "NV12" / "NV21" / "I420" / "YV12": the camera's frames carry their chroma planes behind the luma plane
+        ([sh + ch][bytes] each), and preview(color=True) and `blobs` work for such a camera as for a packed colour format.
         auto_exposure=True (the reference's Camera.auto_exposure) meters the last frame of every batch the task stages, on the
         device, and keeps the exposure to set next in `exposure` (unit and start: exposure0); off, nothing is launched.
         corner_subpix=True (or a dict of AprilTagDetector.set_corner_subpix's arguments) refines every detection's corners to
@@ -67,6 +69,9 @@ class AprilTags:
         self.tags = field if isinstance(field, dict) and all(isinstance(v, A.Iso3) for v in field.values()) else load_field_layout(field)
         self.cam_id = cam_id
         self.fourcc, self.orientation, self.jpeg_color = fourcc, orientation, bool(jpeg_color)
+        self.planes = bool(planes)
+        if self.planes and fourcc not in A.PLANAR_FOURCCS:
+            raise ValueError(f"planes=True needs one of the planar formats {A.PLANAR_FOURCCS}")
         self._field = (A.FieldTag * max(len(self.tags), 1))()
         for i, (tid, pose) in enumerate(sorted(self.tags.items())):
             self._field[i].id, self._field[i].pose = tid, pose
@@ -125,7 +130,7 @@ class AprilTags:
         if self.fourcc in A.JPEG_FOURCCS:   # one bytes object per frame
             n = self.detector.upload_jpeg(raw_frames, self.orientation, color=self.jpeg_color)
         else:
-            n = self.detector.upload_raw(raw_frames, self.fourcc or "GREY", self.orientation)
+            n = self.detector.upload_raw(raw_frames, self.fourcc or "GREY", self.orientation, planes=self.planes)
         out = self.process_batch(None, gyro, n=n)
         if self._blob_params is not None:   # (a source without colour is an error here, not an empty answer)
             self.blobs = self.detector.detect_blobs(self._blob_params, n=n)

@@ -35,11 +35,10 @@ int run(ck_handle *h, const ck_pv_color_src &src, const int32_t *frames, int32_t
     if (c.mode == MASK && (c.cls < 0 || c.cls >= c.pp->n_classes || c.stage < 0 || c.stage > 1)) return CK_EINVAL;
     if (c.mode == DETECT && (c.cap < 0 || !c.counts)) return CK_EINVAL;
     if (c.mode == TIME && (c.reps < 1 || !c.ms)) return CK_EINVAL;
-    ck_pv_csrc cs;
-    ck_pv_jsrc js;
+    ck_pv_any store;
     ck_pv_src any;
     int n_avail;
-    int rc = ck_pv_source(h, src, true, &cs, &js, &any, &n_avail);
+    int rc = ck_pv_source(h, src, true, &store, &any, &n_avail);
     if (rc != CK_OK) return rc;
     if (n > h->cfg.max_batch) return CK_ECAPACITY;
     if (!ck_frame_list_ok(frames, n, n_avail)) return CK_EINVAL;

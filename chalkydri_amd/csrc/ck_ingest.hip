@@ -14,6 +14,7 @@
 #include "ck_jpeg.h"
 #include "ck_blobs.h"
 #include "ck_preview.h"
+#include "ck_raw_planes.h"
 #include "ck_rawfmt.h"
 
 struct ck_ingest {
@@ -146,8 +147,10 @@ extern "C" int ck_ingest_write(ck_ingest_t *g, int32_t slot, int32_t index, cons
     if (ck_raw_classify(fourcc, &cls) != CK_OK) return CK_EUNSUPPORTED;
     if (g->raw) { // exactly the ring's family, the ring's source geometry, min_stride bytes per row
         const ck_raw_geom &G = g->geo;
+        if (!G.planes && cls.bpp == 1) cls.k[0] = 0; // without CK_RAW_PLANES the luma-first fourccs are one family
         if (!ck_raw_same_family(cls, G.cls)) return CK_EUNSUPPORTED;
-        if (img->width != G.sw || img->height != G.sh || img->stride < G.min_stride) return CK_EINVAL;
+        if (img->width != G.sw || img->height != G.sh || !ck_raw_stride_ok(G, img->stride)) return CK_EINVAL;
+        if (G.planes) { ckp_copy(G.planes, G.sw, G.sh, img->buf, img->stride, dst, G.stride16); return CK_OK; } // all planes
         for (int y = 0; y < G.sh; y++) memcpy(dst + (size_t)y * G.stride16, img->buf + (size_t)y * img->stride, (size_t)G.min_stride);
         return CK_OK;
     }
@@ -189,7 +192,7 @@ extern "C" int ck_ingest_submit(ck_ingest_t *g, int32_t slot, int32_t n) {
     } else if (n && g->raw) { // the copy and the conversion both run on the copy stream, ahead of the slot's event
         const ck_raw_geom &G = g->geo;
         CK_HIP(hipMemcpyAsync(g->rawdev[slot], g->host[slot], G.pitch16 * (size_t)n, hipMemcpyHostToDevice, g->copy));
-        const int rc = ck_launch_rawfmt(g->h, g->copy, {g->rawdev[slot], G.stride16, G.pitch16, G.sw, G.sh}, G.cls, g->fmt.orientation, g->dev[slot], n);
+        const int rc = ck_launch_rawfmt(g->h, g->copy, {g->rawdev[slot], G.stride16, G.pitch16, G.sw, G.sh}, G.cls, G.turn, g->dev[slot], n);
         if (rc != CK_OK) return rc;
     } else if (n) CK_HIP(hipMemcpyAsync(g->dev[slot], g->host[slot], g->h->frame_pitch * (size_t)n, hipMemcpyHostToDevice, g->copy));
     CK_HIP(hipEventRecord(g->ready[slot], g->copy));

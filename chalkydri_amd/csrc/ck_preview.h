@@ -64,8 +64,18 @@ struct ck_pv_jsrc {
     int sw, sh, orientation;
     int ovl[3];
 };
-// the source of a colour call: one of the two
-struct ck_pv_src { const ck_pv_csrc *raw; const ck_pv_jsrc *jpeg; };
+// The planar 4:2:0 raw formats with CK_RAW_PLANES (§4s): component c of source pixel (u, v) of a frame is the byte at
+// off[c] + (v >> rs[c]) * rstride[c] + (u >> cs[c]) * step[c] (ck_raw_planes.h's map at the source's stride, in 32 bits).  ovl as above.
+struct ck_pv_psrc {
+    const uint8_t *p; size_t pitch;
+    int sw, sh, orientation;
+    int off[3], rstride[3], step[3], cs[3], rs[3];
+    int ovl[3];
+};
+// the source of a colour call: one of the three
+struct ck_pv_src { const ck_pv_csrc *raw; const ck_pv_jsrc *jpeg; const ck_pv_psrc *planar; };
+// ... and the storage behind it, whichever it is
+struct ck_pv_any { ck_pv_csrc cs; ck_pv_jsrc js; ck_pv_psrc ps; };
 
 // k_jpegenc.hip: the stages, enqueued on the handle's stream, in two halves.  d_out == nullptr: scale .. stuffing scan, after which
 // d_sizes holds every file's size, its offset in the output (i * cap for a caller's device buffer, one file behind the other with
@@ -86,7 +96,7 @@ int ck_preview_color_run(ck_handle *h, const ck_preview_params_t *pp, const ck_p
 
 // the same source as the kernels take it (identity: a packed colour family's own R, G, B instead of its Y Cb Cr: §4r), checked;
 // *n_avail: the frames an index may name.  ck_pv_staged_source: the colour source behind the staged frames (CK_EINVAL: none).
-int ck_pv_source(ck_handle *h, const ck_pv_color_src &src, bool identity, ck_pv_csrc *cs, ck_pv_jsrc *js, ck_pv_src *any, int *n_avail);
+int ck_pv_source(ck_handle *h, const ck_pv_color_src &src, bool identity, ck_pv_any *store, ck_pv_src *any, int *n_avail);
 int ck_pv_staged_source(ck_handle *h, ck_pv_color_src *src, ck_jpeg_color_src *js);
 
 #endif

@@ -5,6 +5,7 @@
 
 #include "ck_jpeg_tables.h"
 #include "ck_preview.h"
+#include "ck_raw_planes.h"
 #include "ck_rawfmt.h"
 
 namespace {
@@ -207,26 +208,78 @@ void color_source(const ck_raw_geom &L, int orientation, const uint8_t *p, int s
     }
 }
 
+// the plane map of a planar 4:2:0 frame (ck_raw_planes.h) as the kernels take it
+void planar_source(const ckp_map &m, int turn, const uint8_t *p, size_t pitch, ck_pv_psrc *ps) {
+    memset(ps, 0, sizeof *ps);
+    ps->p = p; ps->pitch = pitch;
+    ps->sw = m.sw; ps->sh = m.sh; ps->orientation = turn;
+    for (int c = 0; c < 3; c++) {
+        ps->off[c] = (int)m.c[c].off; ps->rstride[c] = m.c[c].row_stride; ps->step[c] = m.c[c].step;
+        ps->cs[c] = m.c[c].cs; ps->rs[c] = m.c[c].rs;
+        ps->ovl[c] = overlay_component(c);
+    }
+}
+
 } // namespace
 
 // The source of a colour call as the kernels take it, checked in the contract's order; *n_avail: the frames an index may name.
-int ck_pv_source(ck_handle *h, const ck_pv_color_src &src, bool identity, ck_pv_csrc *cs, ck_pv_jsrc *js, ck_pv_src *any, int *n_avail) {
-    *any = {nullptr, nullptr};
+int ck_pv_source(ck_handle *h, const ck_pv_color_src &src, bool identity, ck_pv_any *store, ck_pv_src *any, int *n_avail) {
+    *any = {nullptr, nullptr, nullptr};
     if (src.jpeg) { // the frames of a JPEG decode in the colour form (§4i)
         const ck_jpeg_color_src &J = *src.jpeg;
-        *js = {J.img.p, J.img.stride, J.img.pitch, J.descs, J.status, J.planes, J.sw, J.sh, J.orientation, {overlay_component(0), overlay_component(1), overlay_component(2)}};
-        any->jpeg = js;
+        store->js = {J.img.p, J.img.stride, J.img.pitch, J.descs, J.status, J.planes, J.sw, J.sh, J.orientation, {overlay_component(0), overlay_component(1), overlay_component(2)}};
+        any->jpeg = &store->js;
         *n_avail = J.n_frames;
         return CK_OK;
     }
     ck_raw_geom L;
     const int rc = ck_raw_geometry(src.fmt, h->w, h->h, &L);
     if (rc != CK_OK) return rc;
-    if (L.cls.bpp == 1) return CK_EUNSUPPORTED; // a luma-first family: its chroma never reaches the device (the grey preview serves it)
-    if ((!src.p && src.n_frames > 0) || src.n_frames < 0 || src.stride < L.min_stride || src.pitch < (int64_t)src.stride * L.sh) return CK_EINVAL;
-    color_source(L, src.fmt->orientation, src.p, src.stride, (size_t)src.pitch, identity, cs);
-    any->raw = cs;
+    if (L.cls.bpp == 1 && !L.planes) return CK_EUNSUPPORTED; // a luma-first family without CK_RAW_PLANES: its chroma is not part of the frame (the grey preview serves it)
+    if ((!src.p && src.n_frames > 0) || src.n_frames < 0 || !ck_raw_pitch_ok(L, src.stride, src.pitch)) return CK_EINVAL;
     *n_avail = src.n_frames;
+    if (L.planes) {
+        ckp_map m;
+        if (ckp_map_make(L.planes, L.sw, L.sh, src.stride, &m) != 0) return CK_EINVAL;
+        if (m.bytes > INT32_MAX) return CK_ECAPACITY; // the kernels place a sample of a frame in 32 bits
+        planar_source(m, L.turn, src.p, (size_t)src.pitch, &store->ps);
+        any->planar = &store->ps;
+        return CK_OK;
+    }
+    color_source(L, L.turn, src.p, src.stride, (size_t)src.pitch, identity, &store->cs);
+    any->raw = &store->cs;
+    return CK_OK;
+}
+
+// The one-thread host twin of the colour triples (§4g, §4s): what k_pv_color writes at the identity size without overlay.
+extern "C" int ck_raw_ycc_host(const ck_raw_format_t *fmt, const ck_image_u8_t *imgs, int32_t n, int32_t W, int32_t H, uint8_t *ycc_out) {
+    ck_raw_geom L;
+    const int rc = ck_raw_geometry(fmt, W, H, &L);
+    if (rc != CK_OK) return rc;
+    if (L.cls.bpp == 1 && !L.planes) return CK_EUNSUPPORTED;
+    if (n < 0 || (n > 0 && !imgs) || !ycc_out) return CK_EINVAL;
+    for (int i = 0; i < n; i++)
+        if (!imgs[i].buf || imgs[i].width != L.sw || imgs[i].height != L.sh || !ck_raw_stride_ok(L, imgs[i].stride)) return CK_EINVAL;
+    for (int i = 0; i < n; i++) {
+        const uint8_t *S = imgs[i].buf;
+        uint8_t *out = ycc_out + (size_t)i * W * H * 3;
+        ckp_map m;
+        ck_pv_csrc cs;
+        if (L.planes) { if (ckp_map_make(L.planes, L.sw, L.sh, imgs[i].stride, &m) != 0) return CK_EINVAL; }
+        else color_source(L, L.turn, S, imgs[i].stride, 0, false, &cs);
+        for (int oy = 0; oy < H; oy++)
+            for (int ox = 0; ox < W; ox++, out += 3) {
+                int32_t u, v;
+                ckp_source_xy(L.turn, L.sw, L.sh, ox, oy, &u, &v);
+                if (L.planes) { ckp_triple(&m, S, u, v, out); continue; }
+                const uint8_t *row = S + (size_t)v * imgs[i].stride;
+                for (int c = 0; c < 3; c++) {
+                    if (cs.bpp == 2) { out[c] = row[(c ? (u >> 1) << 2 : u << 1) + cs.off[c]]; continue; }
+                    const uint8_t *px = row + (size_t)u * cs.bpp;
+                    out[c] = (uint8_t)((cs.wgt[c][0] * px[0] + cs.wgt[c][1] * px[1] + cs.wgt[c][2] * px[2] + cs.bias[c]) >> 16);
+                }
+            }
+    }
     return CK_OK;
 }
 
@@ -236,11 +289,10 @@ int ck_preview_color_run(ck_handle *h, const ck_preview_params_t *pp, const ck_p
     ck_pv_geom g;
     int rc = resolve(pp, h->w, h->h, 3, &g);
     if (rc != CK_OK) return rc;
-    ck_pv_csrc cs;
-    ck_pv_jsrc js;
+    ck_pv_any store;
     ck_pv_src any;
     int n_avail;
-    rc = ck_pv_source(h, src, false, &cs, &js, &any, &n_avail);
+    rc = ck_pv_source(h, src, false, &store, &any, &n_avail);
     if (rc == CK_OK) rc = begin(h, frames, n, n_avail, &g);
     if (rc != CK_OK || n == 0) return rc;
     if (files) return encode_files(h, pp, g, &any, n, out, cap_per_frame, sizes, status);

@@ -127,6 +127,45 @@ struct Decoded {
     }
 };
 
+// Planar: the 4:2:0 raw formats with CK_RAW_PLANES (§4s).  The place is a byte offset into the frame, as Raw's is: component c of
+// source pixel (u, v) lies at off + (v >> rs) * rstride + (u >> cs) * step, a term of u plus a term of v, so under all four index
+// maps it is a term of the oriented column plus a term of the oriented row (the plane's offset rides on the row's).  Lanes differ
+// in these five constants, never in control flow.  Every read lies inside the plane's own rows: u < sw and v < sh bound
+// (u >> cs) * step + step - 1 by the bytes a row of the plane holds and v >> rs by its rows (ck_raw_planes.h).
+struct Planar {
+    ck_pv_psrc s;
+    struct Lane { int comp, off, rstride, step, cs, rs, ovl; };
+    using Frame = const uint8_t *;
+    __device__ __forceinline__ Lane lane(int comp) const {
+        const auto pick = [&](const int (&a)[3]) { return comp == 0 ? a[0] : (comp == 1 ? a[1] : a[2]); };
+        return {comp, pick(s.off), pick(s.rstride), pick(s.step), pick(s.cs), pick(s.rs), pick(s.ovl)};
+    }
+    __device__ __forceinline__ int col(const Lane &L, int u) const { return (u >> L.cs) * L.step; }
+    __device__ __forceinline__ int row(const Lane &L, int v) const { return (v >> L.rs) * L.rstride; }
+    __device__ __forceinline__ int term_x(const Lane &L, int ox) const {
+        switch (s.orientation) {
+        case CK_ORIENT_CLOCKWISE: return row(L, s.sh - 1 - ox);
+        case CK_ORIENT_COUNTERCLOCKWISE: return row(L, ox);
+        case CK_ORIENT_ROTATE_180: return col(L, s.sw - 1 - ox);
+        }
+        return col(L, ox);
+    }
+    __device__ __forceinline__ int term_y(const Lane &L, int oy) const {
+        switch (s.orientation) {
+        case CK_ORIENT_CLOCKWISE: return L.off + col(L, oy);
+        case CK_ORIENT_COUNTERCLOCKWISE: return L.off + col(L, s.sw - 1 - oy);
+        case CK_ORIENT_ROTATE_180: return L.off + row(L, s.sh - 1 - oy);
+        }
+        return L.off + row(L, oy);
+    }
+    __device__ __forceinline__ Frame frame(int f) const { return s.p + (size_t)f * s.pitch; }
+    __device__ __forceinline__ int pixel(Frame p, int at, const Lane &L, const uint32_t *mask, int bit) const {
+        int v = p[at];
+        if (mask && ((mask[bit >> 5] >> (bit & 31)) & 1u)) v = L.ovl;
+        return v;
+    }
+};
+
 } // namespace
 
 #endif

@@ -21,6 +21,7 @@ struct Classes { ck_blob_class_t c[CK_BLOB_MAX_CLASSES]; };
 
 template <bool YUV> __device__ constexpr bool is_ycc(const Raw<YUV> &) { return YUV; }
 __device__ constexpr bool is_ycc(const Decoded &) { return true; }
+__device__ constexpr bool is_ycc(const Planar &) { return true; }
 
 // the RGB the classifier sees of oriented pixel (x, y) of frame F
 template <class SRC>
@@ -48,6 +49,9 @@ __device__ __forceinline__ void blob_rgb(const ck_blob_geom &g, const SRC &s, in
 template <bool YUV>
 __global__ __launch_bounds__(BL_NT) void k_blob_rgb(ck_blob_geom g, ck_pv_csrc s, int n, const int32_t *frames, uint8_t *out) {
     blob_rgb(g, Raw<YUV>{s}, n, frames, out);
+}
+__global__ __launch_bounds__(BL_NT) void k_blob_prgb(ck_blob_geom g, ck_pv_psrc s, int n, const int32_t *frames, uint8_t *out) {
+    blob_rgb(g, Planar{s}, n, frames, out);
 }
 __global__ __launch_bounds__(BL_NT) void k_blob_jrgb(ck_blob_geom g, ck_pv_jsrc s, int n, const int32_t *frames, uint8_t *out) {
     blob_rgb(g, Decoded{s}, n, frames, out);
@@ -93,6 +97,9 @@ __device__ __forceinline__ void blob_mask(const ck_blob_geom &g, const SRC &s, c
 template <bool YUV>
 __global__ __launch_bounds__(BL_NT) void k_blob_mask(ck_blob_geom g, ck_pv_csrc s, Classes K, const int32_t *frames, uint32_t *bits) {
     blob_mask(g, Raw<YUV>{s}, K, frames, bits);
+}
+__global__ __launch_bounds__(BL_NT) void k_blob_pmask(ck_blob_geom g, ck_pv_psrc s, Classes K, const int32_t *frames, uint32_t *bits) {
+    blob_mask(g, Planar{s}, K, frames, bits);
 }
 __global__ __launch_bounds__(BL_NT) void k_blob_jmask(ck_blob_geom g, ck_pv_jsrc s, Classes K, const int32_t *frames, uint32_t *bits) {
     blob_mask(g, Decoded{s}, K, frames, bits);
@@ -364,6 +371,7 @@ int ck_launch_blob_rgb(ck_handle *h, const ck_blob_geom &g, const ck_pv_src &src
     ck_blob_ws &P = *h->blobs;
     const dim3 grid(blocks_of((long)g.W * g.H * n));
     if (src.jpeg) hipLaunchKernelGGL(k_blob_jrgb, grid, dim3(BL_NT), 0, h->stream, g, *src.jpeg, n, P.d_frames, d_out);
+    else if (src.planar) hipLaunchKernelGGL(k_blob_prgb, grid, dim3(BL_NT), 0, h->stream, g, *src.planar, n, P.d_frames, d_out);
     else if (src.raw->bpp == 2) hipLaunchKernelGGL(k_blob_rgb<true>, grid, dim3(BL_NT), 0, h->stream, g, *src.raw, n, P.d_frames, d_out);
     else hipLaunchKernelGGL(k_blob_rgb<false>, grid, dim3(BL_NT), 0, h->stream, g, *src.raw, n, P.d_frames, d_out);
     CK_HIP(hipGetLastError());
@@ -383,6 +391,7 @@ int ck_launch_blob_mask(ck_handle *h, const ck_blob_geom &g, const ck_blob_param
     uint32_t *b[2] = {P.d_bits.p, P.d_bits.p + total};
     const dim3 grid((g.W + 64 * MASK_CHUNKS - 1) / (64 * MASK_CHUNKS), (g.H + 3) / 4, n), block(64, 4);
     if (src.jpeg) hipLaunchKernelGGL(k_blob_jmask, grid, block, 0, h->stream, g, *src.jpeg, K, P.d_frames, b[0]);
+    else if (src.planar) hipLaunchKernelGGL(k_blob_pmask, grid, block, 0, h->stream, g, *src.planar, K, P.d_frames, b[0]);
     else if (src.raw->bpp == 2) hipLaunchKernelGGL(k_blob_mask<true>, grid, block, 0, h->stream, g, *src.raw, K, P.d_frames, b[0]);
     else hipLaunchKernelGGL(k_blob_mask<false>, grid, block, 0, h->stream, g, *src.raw, K, P.d_frames, b[0]);
     CK_HIP(hipGetLastError());

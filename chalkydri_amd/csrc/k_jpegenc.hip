@@ -120,6 +120,10 @@ template <bool YUV>
 __global__ __launch_bounds__(PV_NT) void k_pv_color(ck_pv_geom g, ck_pv_csrc s, int n, const int32_t *frames, const uint32_t *mask, uint8_t *out) {
     pv_triples(g, Raw<YUV>{s}, n, frames, mask, out);
 }
+// ... from the planar 4:2:0 raw formats (§4s)
+__global__ __launch_bounds__(PV_NT) void k_pv_ptriples(ck_pv_geom g, ck_pv_psrc s, int n, const int32_t *frames, const uint32_t *mask, uint8_t *out) {
+    pv_triples(g, Planar{s}, n, frames, mask, out);
+}
 __global__ __launch_bounds__(PV_NT) void k_pv_jtriples(ck_pv_geom g, ck_pv_jsrc s, int n, const int32_t *frames, const uint32_t *mask, uint8_t *out) {
     pv_triples(g, Decoded{s}, n, frames, mask, out);
 }
@@ -249,6 +253,12 @@ __global__ __launch_bounds__(PV_NT) void k_pv_fdct_color(ck_pv_geom g, ck_pv_tab
                                                          const uint32_t *mask, int16_t *coef, int16_t *dc, uint32_t *len) {
     __shared__ uint32_t enc[2 * PV_ENC_WORDS];
     pv_fdct_color(g, tab, Raw<YUV>{s}, n, frames, mask, coef, dc, len, enc);
+}
+// ... from the planar 4:2:0 raw formats (§4s)
+__global__ __launch_bounds__(PV_NT) void k_pv_pfdct(ck_pv_geom g, ck_pv_tables tab, ck_pv_psrc s, int n, const int32_t *frames,
+                                                    const uint32_t *mask, int16_t *coef, int16_t *dc, uint32_t *len) {
+    __shared__ uint32_t enc[2 * PV_ENC_WORDS];
+    pv_fdct_color(g, tab, Planar{s}, n, frames, mask, coef, dc, len, enc);
 }
 // ... and from the frames of a JPEG decode in the colour form (§4i)
 __global__ __launch_bounds__(PV_NT) void k_pv_jfdct(ck_pv_geom g, ck_pv_tables tab, ck_pv_jsrc s, int n, const int32_t *frames,
@@ -509,6 +519,7 @@ int ck_launch_preview_color(ck_handle *h, const ck_pv_geom &g, const ck_pv_src &
     ck_preview_ws &P = *h->preview;
     const dim3 grid(blocks_for((long)n * g.pw * g.ph * 3));
     if (src.jpeg) hipLaunchKernelGGL(k_pv_jtriples, grid, dim3(PV_NT), 0, h->stream, g, *src.jpeg, n, P.d_frames, P.d_mask, d_out);
+    else if (src.planar) hipLaunchKernelGGL(k_pv_ptriples, grid, dim3(PV_NT), 0, h->stream, g, *src.planar, n, P.d_frames, P.d_mask, d_out);
     else if (src.raw->bpp == 2) hipLaunchKernelGGL(k_pv_color<true>, grid, dim3(PV_NT), 0, h->stream, g, *src.raw, n, P.d_frames, P.d_mask, d_out);
     else hipLaunchKernelGGL(k_pv_color<false>, grid, dim3(PV_NT), 0, h->stream, g, *src.raw, n, P.d_frames, P.d_mask, d_out);
     CK_HIP(hipGetLastError());
@@ -525,6 +536,7 @@ void launch_first_half(ck_handle *h, const ck_pv_geom &g, const ck_pv_tables &t,
     const unsigned nb = blocks_for((long)n * g.nblk);
     if constexpr (NC == 1) hipLaunchKernelGGL(k_pv_fdct, dim3(nb), dim3(PV_NT), 0, st, g, t, n, ck_staged_image(h), P.d_frames, P.d_mask, P.d_coef, P.d_dc, P.d_len);
     else if (cs->jpeg) hipLaunchKernelGGL(k_pv_jfdct, dim3(nb), dim3(PV_NT), 0, st, g, t, *cs->jpeg, n, P.d_frames, P.d_mask, P.d_coef, P.d_dc, P.d_len);
+    else if (cs->planar) hipLaunchKernelGGL(k_pv_pfdct, dim3(nb), dim3(PV_NT), 0, st, g, t, *cs->planar, n, P.d_frames, P.d_mask, P.d_coef, P.d_dc, P.d_len);
     else if (cs->raw->bpp == 2) hipLaunchKernelGGL(k_pv_fdct_color<true>, dim3(nb), dim3(PV_NT), 0, st, g, t, *cs->raw, n, P.d_frames, P.d_mask, P.d_coef, P.d_dc, P.d_len);
     else hipLaunchKernelGGL(k_pv_fdct_color<false>, dim3(nb), dim3(PV_NT), 0, st, g, t, *cs->raw, n, P.d_frames, P.d_mask, P.d_coef, P.d_dc, P.d_len);
     hipLaunchKernelGGL(k_pv_scan<NC>, dim3((unsigned)(((long)n * g.nint + PV_NT / 64 - 1) / (PV_NT / 64))), dim3(PV_NT), 0, st, g, n, P.d_dc, P.d_len, P.d_istart);

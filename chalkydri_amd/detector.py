@@ -83,6 +83,8 @@ def _bind(L):
     L.ck_upload_raw_device.argtypes = [vp, vp, i32, i32, C.c_int64, rf]
     L.ck_raw_luma_batch.argtypes = [vp, _P(A.ImageU8), i32, rf, vp]
     L.ck_ingest_create_raw.argtypes = [vp, i32, rf, _P(vp)]
+    L.ck_raw_plane_layout.argtypes = [rf, i32, i32, i32, _P(A.RawPlanes)]
+    L.ck_raw_ycc_host.argtypes = [rf, _P(A.ImageU8), i32, i32, i32, vp]
     pv = _P(A.PreviewParams)
     L.ck_preview_params_default.argtypes = [pv]
     L.ck_preview_params_default.restype = None
@@ -330,17 +332,49 @@ def orientation_code(orientation):
     return int(orientation)
 
 
-def raw_format(code, orientation="none"):
-    """ck_raw_format_t from a fourcc string (or its u32) and an orientation."""
-    return A.RawFormat(fourcc(code) if isinstance(code, str) else int(code), orientation_code(orientation))
+def raw_format(code, orientation="none", planes=False):
+    """ck_raw_format_t from a fourcc string (or its u32) and an orientation.  planes: CK_RAW_PLANES, the chroma planes behind the
+    luma plane of 'NV12' / 'NV21' / 'I420' / 'YV12' are part of every frame."""
+    return A.RawFormat(fourcc(code) if isinstance(code, str) else int(code),
+                       orientation_code(orientation) | (A.CK_RAW_PLANES if planes else 0))
 
 
-def raw_layout(code, width, height, orientation="none"):
+def raw_layout(code, width, height, orientation="none", planes=False):
     """ck_raw_layout: (sw, sh, min_stride, min_bytes) of the source of an oriented width x height frame.  No device needed."""
     sw, sh, ms, mb = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
-    fmt = raw_format(code, orientation)
+    fmt = raw_format(code, orientation, planes)
     check(_bind(lib()).ck_raw_layout(C.byref(fmt), width, height, C.byref(sw), C.byref(sh), C.byref(ms), C.byref(mb)), "ck_raw_layout")
     return sw.value, sh.value, ms.value, mb.value
+
+
+def raw_plane_layout(code, width, height, stride, orientation="none"):
+    """ck_raw_plane_layout: where the samples of a planar frame (CK_RAW_PLANES) of row stride `stride` lie, as a dict of
+    sw, sh, cw, ch, offset[3], row_stride[3], step[3] (Y, Cb, Cr) and bytes.  No device needed."""
+    fmt, out = raw_format(code, orientation, True), A.RawPlanes()
+    check(_bind(lib()).ck_raw_plane_layout(C.byref(fmt), width, height, int(stride), C.byref(out)), "ck_raw_plane_layout")
+    return {"sw": out.sw, "sh": out.sh, "cw": out.cw, "ch": out.ch, "offset": tuple(out.offset), "row_stride": tuple(out.row_stride),
+            "step": tuple(out.step), "bytes": out.bytes}
+
+
+def _raw_rows(fmt, width, height):
+    """(sw, sh, rows) of a format's source: rows = the rows of the row stride a frame holds, sh + ch with CK_RAW_PLANES."""
+    sw, sh, _, _ = raw_layout(fmt.fourcc, width, height, fmt.orientation)
+    return sw, sh, sh + ((sh + 1) // 2 if fmt.orientation & A.CK_RAW_PLANES else 0)
+
+
+def raw_ycc_host(frames, code, width, height, orientation="none", planes=False):
+    """ck_raw_ycc_host: [n][height][width][3] uint8, the (Y, Cb, Cr) triples of raw frames turned by `orientation`, computed on the
+    host by the library's one-thread twin of preview_color at the identity size.  No device needed."""
+    fmt = raw_format(code, orientation, planes)
+    sw, sh, rows = _raw_rows(fmt, width, height)
+    arr, keep = _raw_images(frames, sw, sh)
+    for f in keep:
+        if f.shape[0] < rows:
+            raise ValueError(f"a raw frame needs {rows} rows")
+    out = np.empty((len(keep), height, width, 3), np.uint8)
+    buf = out if out.size else np.empty(1, np.uint8)
+    check(_bind(lib()).ck_raw_ycc_host(C.byref(fmt), arr, len(keep), width, height, buf.ctypes.data), "ck_raw_ycc_host")
+    return out
 
 
 def _raw_images(frames, sw, sh):
@@ -536,34 +570,35 @@ class AprilTagDetector:
         check(self._L.ck_jpeg_luma_batch_oriented(self._h, arr, len(keep), o, out.ctypes.data, status), "ck_jpeg_luma_batch_oriented")
         return (out, list(status)[:len(keep)]) if return_status else out
 
-    def upload_raw(self, frames, code, orientation="none"):
+    def upload_raw(self, frames, code, orientation="none", planes=False):
         """Raw camera frames ([rows][bytes] each: 'YUYV', 'RGB3', 'BGRA', ... as ck_raw_layout lists them) are converted to luma
         and turned by `orientation` on the device into the staged frames; the detector's width x height is the ORIENTED frame.
-        detect_batch(None, n=...) / the process and pose calls follow, as after `upload`."""
-        fmt = raw_format(code, orientation)
-        sw, sh, _, _ = raw_layout(fmt.fourcc, self.width, self.height, fmt.orientation)
+        detect_batch(None, n=...) / the process and pose calls follow, as after `upload`.  planes=True ('NV12', 'NV21', 'I420',
+        'YV12'): every frame carries its chroma planes ([sh + ch][bytes]), which the colour preview and the blob calls then read."""
+        fmt = raw_format(code, orientation, planes)
+        sw, sh, rows = _raw_rows(fmt, self.width, self.height)
         arr, keep = _raw_images(frames, sw, sh)
         for f in keep:
-            if f.shape[0] < sh:
-                raise ValueError(f"a raw frame needs {sh} rows")
+            if f.shape[0] < rows:
+                raise ValueError(f"a raw frame needs {rows} rows")
         check(self._L.ck_upload_raw(self._h, arr, len(keep), C.byref(fmt)), "ck_upload_raw")
         return len(keep)
 
-    def upload_raw_device(self, ptr, n, stride, frame_pitch, code, orientation="none"):
+    def upload_raw_device(self, ptr, n, stride, frame_pitch, code, orientation="none", planes=False):
         """The same from device-resident frames (a torch tensor's data_ptr(), another decoder's output): no host copy.  The
         work that produced them must have completed (torch.cuda.synchronize / the producing stream)."""
-        fmt = raw_format(code, orientation)
+        fmt = raw_format(code, orientation, planes)
         check(self._L.ck_upload_raw_device(self._h, C.c_void_p(ptr), n, stride, frame_pitch, C.byref(fmt)), "ck_upload_raw_device")
         return n
 
-    def raw_luma(self, frames, code, orientation="none"):
+    def raw_luma(self, frames, code, orientation="none", planes=False):
         """[n][height][width] uint8: the oriented luma the device makes of the raw frames (and leaves staged)."""
-        fmt = raw_format(code, orientation)
-        sw, sh, _, _ = raw_layout(fmt.fourcc, self.width, self.height, fmt.orientation)
+        fmt = raw_format(code, orientation, planes)
+        sw, sh, rows = _raw_rows(fmt, self.width, self.height)
         arr, keep = _raw_images(frames, sw, sh)
         for f in keep:
-            if f.shape[0] < sh:
-                raise ValueError(f"a raw frame needs {sh} rows")
+            if f.shape[0] < rows:
+                raise ValueError(f"a raw frame needs {rows} rows")
         out = np.empty((len(keep), self.height, self.width), np.uint8)
         check(self._L.ck_raw_luma_batch(self._h, arr, len(keep), C.byref(fmt), out.ctypes.data), "ck_raw_luma_batch")
         return out
@@ -735,7 +770,8 @@ class AprilTagDetector:
     def preview_jpeg_color(self, frames=None, n=None, width=640, height=480, quality=50, restart_rows=0, overlay=False, cap=None,
                            return_status=False):
         """preview_jpeg in colour: three-component 4:4:4 files of the RAW frames the last upload_raw / raw_luma left on the
-        device (a packed colour family: 'YUYV', 'UYVY', 'RGB3', 'BGR3', 'RGBA', 'BGRA'), or of the JPEG frames the last
+        device (a packed colour family: 'YUYV', 'UYVY', 'RGB3', 'BGR3', 'RGBA', 'BGRA'; or 'NV12', 'NV21', 'I420', 'YV12' uploaded
+        with planes=True), or of the JPEG frames the last
         upload_jpeg(..., color=True) decoded, byte-equal to libjpeg's.  Valid until frames are staged another way."""
         call = lambda pp, idx, n, out, c, sizes, status: self._L.ck_preview_jpeg_color(self._h, C.byref(pp), idx, n, out, c, sizes, status)
         return self._preview_files(call, "ck_preview_jpeg_color", True, frames, n, width, height, quality, restart_rows, overlay, cap, return_status)
@@ -746,17 +782,17 @@ class AprilTagDetector:
         return self._preview_triples(call, "ck_preview_color", frames, n, width, height, quality, restart_rows, overlay)
 
     def preview_jpeg_color_device(self, ptr, n_frames, stride, frame_pitch, code, orientation="none", frames=None, n=None, width=640,
-                                  height=480, quality=50, restart_rows=0, overlay=False, cap=None, return_status=False):
+                                  height=480, quality=50, restart_rows=0, overlay=False, cap=None, return_status=False, planes=False):
         """preview_jpeg_color of n_frames raw frames in device memory (laid out as upload_raw_device takes them)."""
-        fmt = raw_format(code, orientation)
+        fmt = raw_format(code, orientation, planes)
         call = lambda pp, idx, n, out, c, sizes, status: self._L.ck_preview_jpeg_color_device(
             self._h, C.byref(pp), C.c_void_p(ptr), stride, frame_pitch, C.byref(fmt), idx, n_frames, n, out, c, sizes, status)
         return self._preview_files(call, "ck_preview_jpeg_color_device", True, frames, n, width, height, quality, restart_rows, overlay, cap,
                                    return_status)
 
     def preview_color_device(self, ptr, n_frames, stride, frame_pitch, code, orientation="none", frames=None, n=None, width=640,
-                             height=480, quality=50, restart_rows=0, overlay=False):
-        fmt = raw_format(code, orientation)
+                             height=480, quality=50, restart_rows=0, overlay=False, planes=False):
+        fmt = raw_format(code, orientation, planes)
         call = lambda pp, idx, n, out: self._L.ck_preview_color_device(self._h, C.byref(pp), C.c_void_p(ptr), stride, frame_pitch,
                                                                        C.byref(fmt), idx, n_frames, n, out)
         return self._preview_triples(call, "ck_preview_color_device", frames, n, width, height, quality, restart_rows, overlay)
@@ -789,24 +825,25 @@ class AprilTagDetector:
         call = lambda pp, idx, n, out, cap, counts, status: self._L.ck_detect_blobs(self._h, pp, idx, n, out, cap, counts, status)
         return self._blob_records(call, "ck_detect_blobs", params, frames, n, cap)
 
-    def detect_blobs_device(self, params, ptr, n_frames, stride, frame_pitch, code, orientation="none", frames=None, n=None, cap=None):
+    def detect_blobs_device(self, params, ptr, n_frames, stride, frame_pitch, code, orientation="none", frames=None, n=None, cap=None,
+                            planes=False):
         """detect_blobs of n_frames raw frames in device memory (laid out as upload_raw_device takes them)."""
-        fmt = raw_format(code, orientation)
+        fmt = raw_format(code, orientation, planes)
         call = lambda pp, idx, n, out, cap, counts, status: self._L.ck_detect_blobs_device(
             self._h, pp, C.c_void_p(ptr), stride, frame_pitch, C.byref(fmt), idx, n_frames, n, out, cap, counts, status)
         return self._blob_records(call, "ck_detect_blobs_device", params, frames, n_frames if n is None and frames is None else n, cap)
 
     def blob_rgb(self, frames=None, n=None, device=None):
-        """[n][H][W][3] uint8: the RGB the classifier sees.  device: (ptr, n_frames, stride, frame_pitch, code, orientation) for raw
-        frames in device memory instead of the frames behind the staged ones."""
+        """[n][H][W][3] uint8: the RGB the classifier sees.  device: (ptr, n_frames, stride, frame_pitch, code, orientation[, planes])
+        for raw frames in device memory instead of the frames behind the staged ones."""
         idx, ip, n = self._frame_list(frames, n)
         out = np.empty((n, self.height, self.width, 3), np.uint8)
         buf = out if n else np.empty(1, np.uint8)
         if device is None:
             check(self._L.ck_blob_rgb(self._h, ip, n, buf.ctypes.data), "ck_blob_rgb")
         else:
-            ptr, n_frames, stride, pitch, code, orientation = device
-            fmt = raw_format(code, orientation)
+            ptr, n_frames, stride, pitch, code, orientation = device[:6]
+            fmt = raw_format(code, orientation, *device[6:])
             check(self._L.ck_blob_rgb_device(self._h, C.c_void_p(ptr), stride, pitch, C.byref(fmt), ip, n_frames, n, buf.ctypes.data), "ck_blob_rgb_device")
         return out
 
@@ -819,15 +856,15 @@ class AprilTagDetector:
         if device is None:
             check(self._L.ck_blob_mask(self._h, C.byref(params), ip, n, int(cls), int(stage), buf.ctypes.data), "ck_blob_mask")
         else:
-            ptr, n_frames, stride, pitch, code, orientation = device
-            fmt = raw_format(code, orientation)
+            ptr, n_frames, stride, pitch, code, orientation = device[:6]
+            fmt = raw_format(code, orientation, *device[6:])
             check(self._L.ck_blob_mask_device(self._h, C.byref(params), C.c_void_p(ptr), stride, pitch, C.byref(fmt), ip, n_frames, n, int(cls),
                                               int(stage), buf.ctypes.data), "ck_blob_mask_device")
         return out
 
-    def blob_time(self, params, ptr, n_frames, stride, frame_pitch, code, orientation="none", n=None, reps=10):
+    def blob_time(self, params, ptr, n_frames, stride, frame_pitch, code, orientation="none", n=None, reps=10, planes=False):
         """ck_blob_time: mean milliseconds of the kernels of one detect_blobs_device call on frames 0..n-1."""
-        fmt, ms = raw_format(code, orientation), C.c_float()
+        fmt, ms = raw_format(code, orientation, planes), C.c_float()
         check(self._L.ck_blob_time(self._h, C.byref(params), C.c_void_p(ptr), stride, frame_pitch, C.byref(fmt), n_frames,
                                    n_frames if n is None else int(n), int(reps), C.byref(ms)), "ck_blob_time")
         return ms.value
@@ -883,13 +920,13 @@ def fourcc(code):
 class IngestRing:
     """Pinned host slots + asynchronous upload in front of a detector (the pooled host buffers of the reference's camera
     layer, gst_to_cu.rs:49-72,131-188).  slot_view(s) is a writable numpy view [max_batch][h][stride] of pinned memory.
-    With a fourcc the slots hold RAW frames of that format ([max_batch][sh][raw stride]); submit converts and orients them on
-    the device, and detect / process work as on a plain ring.  With fourcc "MJPG" (or "JPEG") the slots take one compressed
+    With a fourcc the slots hold RAW frames of that format ([max_batch][sh][raw stride]; with planes=True the chroma planes too,
+    [max_batch][sh + ch][raw stride]); submit converts and orients them on the device, and detect / process work as on a plain ring.  With fourcc "MJPG" (or "JPEG") the slots take one compressed
     frame per index (write(slot, index, data) with bytes, at most max_frame_bytes each; 0 = sw * sh); submit decodes and
     orients them on the ring's copy stream, and jpeg_status(slot, n) gives their CK_JPEG_* words; with color=True the slots also
     keep their frames' chroma planes (ck_ingest_create_jpeg_color), the source of preview_jpeg_color / preview_color."""
 
-    def __init__(self, detector, n_slots=2, fourcc=None, orientation="none", max_frame_bytes=0, color=False):
+    def __init__(self, detector, n_slots=2, fourcc=None, orientation="none", max_frame_bytes=0, color=False, planes=False):
         self.det, self._L = detector, detector._L
         g = C.c_void_p()
         self._g = None
@@ -897,6 +934,8 @@ class IngestRing:
         self.jpeg = isinstance(fourcc, str) and fourcc in A.JPEG_FOURCCS
         if color and not self.jpeg:
             raise ValueError("color=True is an option of a JPEG ring: a raw ring keeps its raw frames anyway")
+        if planes and (fourcc is None or self.jpeg):
+            raise ValueError("planes=True is an option of a raw ring of a planar format")
         if fourcc is None:
             check(self._L.ck_ingest_create(detector._h, n_slots, C.byref(g)), "ck_ingest_create")
         elif self.jpeg:
@@ -906,9 +945,10 @@ class IngestRing:
             else:
                 check(self._L.ck_ingest_create_jpeg(detector._h, n_slots, o, int(max_frame_bytes), C.byref(g)), "ck_ingest_create_jpeg")
         else:
-            fmt = raw_format(fourcc, orientation)
+            fmt = raw_format(fourcc, orientation, planes)
             # (the layout first: an unknown fourcc or orientation is refused on the host, before the ring touches the device)
-            self.sw, self.rows, self.min_stride, _ = raw_layout(fmt.fourcc, detector.width, detector.height, fmt.orientation)
+            self.sw, self.sh, self.min_stride, _ = raw_layout(fmt.fourcc, detector.width, detector.height, fmt.orientation)
+            self.rows = _raw_rows(fmt, detector.width, detector.height)[2]   # sh, and the chroma rows behind them with planes
             check(self._L.ck_ingest_create_raw(detector._h, n_slots, C.byref(fmt), C.byref(g)), "ck_ingest_create_raw")
         self._g, self.n_slots = g, n_slots
         self.stride = self._L.ck_ingest_stride(g)
@@ -936,7 +976,7 @@ class IngestRing:
         if self.code is None:
             arr, keep = _images(frame)
         else:
-            arr, keep = _raw_images(frame, self.sw, self.rows)
+            arr, keep = _raw_images(frame, self.sw, self.sh)
         code = code or self.code or "GREY"
         check(self._L.ck_ingest_write(self._g, slot, index, arr, fourcc(code)), "ck_ingest_write")
 

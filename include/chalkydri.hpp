@@ -166,11 +166,12 @@ inline int32_t orientation_code(const std::string &orientation) {
     if (orientation == "counterclockwise") return CK_ORIENT_COUNTERCLOCKWISE;
     throw Panic("unknown orientation " + orientation, CK_EINVAL);
 }
-inline ck_raw_format_t raw_format(const std::string &fourcc, const std::string &orientation = "none") {
+// planes: CK_RAW_PLANES, the chroma planes behind the luma plane of "NV12" / "NV21" / "I420" / "YV12" are part of every frame
+inline ck_raw_format_t raw_format(const std::string &fourcc, const std::string &orientation = "none", bool planes = false) {
     if (fourcc.size() != 4) throw Panic("a fourcc has exactly 4 characters: " + fourcc, CK_EINVAL);
     ck_raw_format_t f{};
     for (int i = 0; i < 4; i++) f.fourcc |= (uint32_t)(uint8_t)fourcc[i] << (8 * i);
-    f.orientation = orientation_code(orientation);
+    f.orientation = orientation_code(orientation) | (planes ? CK_RAW_PLANES : 0);
     return f;
 }
 // the names the host layers take for a camera that delivers one JPEG per frame (not raw formats: ck_raw_layout refuses them)
@@ -181,6 +182,12 @@ inline RawLayout raw_layout(const ck_raw_format_t &fmt, int width, int height) {
     RawLayout l;
     check(ck_raw_layout(&fmt, width, height, &l.sw, &l.sh, &l.min_stride, &l.min_bytes), "ck_raw_layout");
     return l;
+}
+// where the samples of a planar frame (a format with CK_RAW_PLANES) of row stride `stride` lie (no device needed)
+inline ck_raw_planes_t raw_plane_layout(const ck_raw_format_t &fmt, int width, int height, int stride) {
+    ck_raw_planes_t p{};
+    check(ck_raw_plane_layout(&fmt, width, height, stride, &p), "ck_raw_plane_layout");
+    return p;
 }
 
 // What the reference reads from an `apriltag::Detection` (crates/apriltags/src/lib.rs:306-314).
@@ -974,6 +981,9 @@ class AprilTags {
         // delivers one JPEG per frame, which `process_jpeg` takes
         std::string fourcc;
         std::string orientation = "none";
+        // "NV12" / "NV21" / "I420" / "YV12" only: the frames carry their chroma planes behind the luma plane (CK_RAW_PLANES), so the
+        // colour preview and the coloured-piece detector work from the frames `process` staged
+        bool raw_planes = false;
     };
     explicit AprilTags(const Config &c)
         : cfg_(c), h_(std::make_shared<Handle>((int)c.width, (int)c.height, c.max_batch, std::vector<std::string>{c.family}, (int)c.bits_corrected,
@@ -1002,7 +1012,7 @@ class AprilTags {
         const int n = (int)imgs.size();
         if (n > cfg_.max_batch || gyro.size() != imgs.size()) throw Panic("process: batch larger than max_batch or gyro size mismatch", CK_EINVAL);
         if (cfg_.fourcc.empty() && cfg_.orientation == "none") check(ck_upload_frames(h_->get(), imgs.data(), n), "ck_upload_frames");
-        else h_->upload_raw(imgs, raw_format(cfg_.fourcc.empty() ? "GREY" : cfg_.fourcc, cfg_.orientation));
+        else h_->upload_raw(imgs, raw_format(cfg_.fourcc.empty() ? "GREY" : cfg_.fourcc, cfg_.orientation, cfg_.raw_planes));
         std::vector<double> g(n);
         std::vector<uint8_t> has(n);
         for (int i = 0; i < n; i++) { has[i] = gyro[i].has_value(); g[i] = gyro[i].value_or(0.0); }

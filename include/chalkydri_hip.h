@@ -578,7 +578,8 @@ int ck_ingest_create_jpeg_color(ck_handle_t *h, int32_t n_slots, int32_t orienta
  * (crates/chalkydri/src/cameras/gst_to_cu.rs:152-188) become 8-bit luma, turned by the camera's mounting, on the device, straight
  * into the staged frames.  DESIGN.md §4d is the contract.  fourcc (four ASCII bytes, little-endian), minimum row stride, luma of
  * pixel x of a row r[]:
- *   GREY GRAY Y800 NV12 NV21 I420 YV12   sw             r[x]  (only the leading plane is read)
+ *   GREY GRAY Y800 NV12 NV21 I420 YV12   sw             r[x]  (only the leading plane is read; with CK_RAW_PLANES below the
+ *                                                             chroma planes of the last four are part of the frame)
  *   YUYV YUY2                            4*ceil(sw/2)   r[2x]
  *   UYVY                                 4*ceil(sw/2)   r[2x+1]
  *   RGB3 "RGB "  /  BGR3 "BGR "          3*sw           L(r[3x], r[3x+1], r[3x+2])  /  L(r[3x+2], r[3x+1], r[3x])
@@ -595,13 +596,31 @@ enum {
     CK_ORIENT_ROTATE_180 = 2,
     CK_ORIENT_COUNTERCLOCKWISE = 3
 };
+/* Or-ed into ck_raw_format_t.orientation: the chroma planes behind the luma plane are part of every frame.  Only
+ * NV12, NV21, I420 and YV12 take it (CK_EUNSUPPORTED with any other fourcc of the table), and with it they are four families.
+ * The layout is V4L2's single-buffer one; with cw = ceil(sw / 2), ch = ceil(sh / 2) and a row stride `stride`:
+ *   all four     luma row y at y * stride; min_stride = 2 cw; a frame extends stride * (sh + ch) bytes
+ *   NV12 / NV21  one interleaved plane at stride * sh, ch rows of `stride` bytes, pair i of a row at bytes 2i, 2i + 1:
+ *                (Cb, Cr) / (Cr, Cb)
+ *   I420 / YV12  stride even (CK_EINVAL otherwise); Cb / Cr at stride * sh, ch rows of stride / 2 bytes; then Cr / Cb at
+ *                stride * sh + (stride / 2) * ch
+ * The triple of source pixel (x, y) is Y = luma[y][x], Cb = Cb[y >> 1][x >> 1], Cr = Cr[y >> 1][x >> 1]: the bytes unchanged,
+ * chroma replicated, the rule of the 4:2:2 families.  Bytes of a row beyond what the plane holds (sw of luma, 2 cw of an
+ * interleaved chroma row, cw of a split one) are never read.  What the flag switches on: ck_upload_raw / ck_raw_luma_batch copy
+ * all planes (every image's buf spans stride * (sh + ch) bytes) and the colour and blob calls then work from the staging; the
+ * *_device forms need frame_pitch >= stride * (sh + ch); a ring of ck_ingest_create_raw holds whole frames (ck_ingest_frame
+ * points at sh + ch rows of ck_ingest_stride, ck_ingest_write copies all planes and takes the ring's own fourcc only).  The
+ * staged luma and everything computed from it are those of the same call without the flag. */
+#define CK_RAW_PLANES 0x100
+/* orientation: CK_ORIENT_* in bits 0..1, optionally | CK_RAW_PLANES */
 typedef struct ck_raw_format {
     uint32_t fourcc;
     int32_t orientation;
 } ck_raw_format_t;
-/* Host only (no device needed): the source geometry of an oriented width x height frame.  min_bytes = sh * min_stride.
- * CK_EINVAL: a null pointer, width or height < 1, an orientation outside 0..3; CK_EUNSUPPORTED: a fourcc outside the table.
- * Every raw entry point validates its format through this. */
+/* Host only (no device needed): the source geometry of an oriented width x height frame.  min_bytes = sh * min_stride; with
+ * CK_RAW_PLANES min_stride = 2 cw and min_bytes = (sh + ch) * min_stride.
+ * CK_EINVAL: a null pointer, width or height < 1, an orientation with a bit outside 0x103; CK_EUNSUPPORTED: a fourcc outside the
+ * table, then CK_RAW_PLANES with a fourcc that has no chroma planes.  Every raw entry point validates its format through this. */
 int ck_raw_layout(const ck_raw_format_t *fmt, int32_t width, int32_t height, int32_t *sw, int32_t *sh, int32_t *min_stride,
                   int64_t *min_bytes);
 /* Host frames (width / height = sw / sh, stride in bytes) -> one pinned staging buffer -> one asynchronous copy -> the convert
@@ -614,7 +633,7 @@ int ck_raw_layout(const ck_raw_format_t *fmt, int32_t width, int32_t height, int
 int ck_upload_raw(ck_handle_t *h, const ck_image_u8_t *imgs, int32_t n, const ck_raw_format_t *fmt);
 /* The same from device-resident frames (row y of frame f at d_raw + f * frame_pitch + y * stride), no host copy and no staging.
  * The caller's work on d_raw must have completed; the source may be reused when the call returns.  CK_EINVAL also for
- * frame_pitch < stride * sh. */
+ * frame_pitch < stride * sh (with CK_RAW_PLANES: stride * (sh + ch); the luma is staged, the planes are only validated). */
 int ck_upload_raw_device(ck_handle_t *h, const uint8_t *d_raw, int32_t n, int32_t stride, int64_t frame_pitch,
                          const ck_raw_format_t *fmt);
 /* As ck_upload_raw, then copies the oriented luma out: luma_out is [n][height][width]. */
@@ -624,6 +643,25 @@ int ck_raw_luma_batch(ck_handle_t *h, const ck_image_u8_t *imgs, int32_t n, cons
  * min_stride bytes per row; ck_ingest_submit enqueues the copy and the conversion on the ring's copy stream, so the slot's device
  * frames are oriented luma and ck_detect_ingested / ck_process_ingested work as on a ring of ck_ingest_create. */
 int ck_ingest_create_raw(ck_handle_t *h, int32_t n_slots, const ck_raw_format_t *fmt, ck_ingest_t **out);
+/* Host only: where the samples of a frame with CK_RAW_PLANES lie, for the source of an oriented width x height frame at row stride
+ * `stride`.  Component c (0 Y, 1 Cb, 2 Cr) of source pixel (x, y) is the byte at offset[c] + (y >> (c ? 1 : 0)) * row_stride[c] +
+ * (x >> (c ? 1 : 0)) * step[c].  Errors of ck_raw_layout; CK_EUNSUPPORTED without the flag; CK_EINVAL for a null out, a stride
+ * below 2 cw, or an odd stride with I420 / YV12. */
+typedef struct ck_raw_planes {
+    int32_t sw, sh, cw, ch;
+    int64_t offset[3];      /* byte of the first Y, Cb, Cr sample from the frame's start */
+    int32_t row_stride[3];  /* bytes between rows of that component */
+    int32_t step[3];        /* bytes between samples of a row: 1,2,2 for NV12/NV21; 1,1,1 for I420/YV12 */
+    int32_t pad[2];
+    int64_t bytes;          /* stride * (sh + ch) */
+} ck_raw_planes_t;
+int ck_raw_plane_layout(const ck_raw_format_t *fmt, int32_t width, int32_t height, int32_t stride, ck_raw_planes_t *out);
+/* Host only: the triples (Y, Cb, Cr) of n frames turned by the format's orientation, ycc_out [n][H][W][3]: the one-thread C twin of
+ * ck_preview_color at width = W, height = H, overlay = 0, for every colour source a raw format can name (the packed families by
+ * the formulas of the colour preview below, the planar ones with CK_RAW_PLANES).  imgs as ck_upload_raw takes them.  Errors of
+ * ck_raw_layout; CK_EUNSUPPORTED: a luma-first fourcc without the flag; CK_EINVAL: null imgs / buffer / ycc_out, n < 0, an image
+ * that is not sw x sh or whose stride the format cannot have. */
+int ck_raw_ycc_host(const ck_raw_format_t *fmt, const ck_image_u8_t *imgs, int32_t n, int32_t W, int32_t H, uint8_t *ycc_out);
 
 /* ---- JPEG preview of the staged frames, encoded on the device -------------------------------------------------------------
  * The way back of the camera layer: what the reference's driver-station stream does with videoconvertscale (nearest neighbour,
@@ -678,8 +716,9 @@ int ck_preview_luma(ck_handle_t *h, const ck_preview_params_t *pp, const int32_t
  * The reference's stream is a colour picture (videoconvertscale to RGB, turbojpeg::compress(.., PixelFormat::RGB, 50,
  * Subsamp::None): mjpeg.rs:41-49,108-118); the staged frames are luma, so the colour form reads the RAW frames they were made
  * from, while those are still on the device.  DESIGN.md §4g is the contract.  Sources: the packed colour families of
- * ck_raw_layout (YUYV / YUY2, UYVY, RGB3 / "RGB ", BGR3 / "BGR ", RGBA, BGRA); a luma-first family (GREY .. YV12) is
- * CK_EUNSUPPORTED: its chroma never reaches the device, and ck_preview_jpeg serves it.  Per entry, with S the sh x sw source:
+ * ck_raw_layout (YUYV / YUY2, UYVY, RGB3 / "RGB ", BGR3 / "BGR ", RGBA, BGRA) and NV12 / NV21 / I420 / YV12 with CK_RAW_PLANES
+ * (their triple is stated there); a luma-first family (GREY .. YV12) without the flag is CK_EUNSUPPORTED: its chroma does not
+ * reach the device, and ck_preview_jpeg serves it.  Per entry, with S the sh x sw source:
  *   orient   O[y][x] = the triple (Y, Cb, Cr) of the source pixel the index maps of ck_raw_format_t name.  RGB families: libjpeg's
  *            rgb_ycc_convert on R, G, B (alpha ignored), in 32-bit signed arithmetic:
  *              Y  = (19595 R + 38470 G + 7471 B + 32768) >> 16          (the staged luma)
@@ -700,11 +739,11 @@ int ck_preview_color_layout(const ck_preview_params_t *pp, int32_t W, int32_t H,
  * ck_upload_jpeg_color (O = orient(C, orientation) of its triples C; `frames` indexes them).  Valid only while they are the
  * handle's staged frames: after any call that stages frames another way (ck_upload_frames, ck_upload_jpeg, ck_upload_jpeg_oriented,
  * ck_jpeg_luma_batch*, ck_upload_raw_device, the *_batch calls given images, the *_device calls) CK_EINVAL.  CK_EUNSUPPORTED: that
- * upload was of a luma-first family. */
+ * upload was of a luma-first family without CK_RAW_PLANES. */
 int ck_preview_jpeg_color(ck_handle_t *h, const ck_preview_params_t *pp, const int32_t *frames, int32_t n, uint8_t *out,
                           int64_t cap_per_frame, int64_t *sizes, uint32_t *status);
 /* From n_frames raw frames in the caller's device memory, laid out as ck_upload_raw_device takes them: any stride >= min_stride,
- * frame_pitch >= stride * sh, any base alignment.  The work that produced them must have completed.  CK_EINVAL also for a null
+ * frame_pitch >= stride * sh (stride * (sh + ch) with CK_RAW_PLANES), any base alignment.  The work that produced them must have completed.  CK_EINVAL also for a null
  * d_raw / fmt, n_frames < 0, a stride or pitch below the minimum, an orientation out of range; CK_EUNSUPPORTED: the fourcc. */
 int ck_preview_jpeg_color_device(ck_handle_t *h, const ck_preview_params_t *pp, const uint8_t *d_raw, int32_t stride,
                                  int64_t frame_pitch, const ck_raw_format_t *fmt, const int32_t *frames, int32_t n_frames, int32_t n,

@@ -8,7 +8,9 @@ quality 50, beside
 all in the same run.  The device files are byte-checked against (b) and against the restatement.  One JSON line per format;
 `latency_n1_ms` is the median call of one frame.
 Run it alone, and under `rocprofv3 --kernel-trace --stats -- python tools/bench_preview_color.py --iters 3` for the per-kernel split.
-usage: python tools/bench_preview_color.py [--iters N] [--frames N] [--only FOURCC]"""
+With --fourcc NV12 --planes (or NV21 / I420 / YV12) the frames are of that planar 4:2:0 format with their chroma planes (§4s);
+--orientation turns the source; --no-host leaves the host's way out.
+usage: python tools/bench_preview_color.py [--iters N] [--frames N] [--only FOURCC] [--fourcc FOURCC --planes] [--orientation NAME] [--no-host]"""
 import argparse
 import io
 import json
@@ -25,6 +27,7 @@ import torch  # noqa: E402  (one HIP runtime per process: torch's, as bench.py l
 
 import np_jpeg_enc_color as EC  # noqa: E402
 import preview_color_ref as PC  # noqa: E402
+import raw_planes_ref as P  # noqa: E402
 import raw_format_ref as R  # noqa: E402
 from chalkydri_amd import scenes  # noqa: E402
 from chalkydri_amd.detector import AprilTagDetector  # noqa: E402
@@ -39,6 +42,8 @@ def camera_frame(scene, fourcc):
     if fourcc == "RGB3":
         return R.pack(rgb, fourcc)
     yc = EC.rgb_to_ycc(rgb)
+    if fourcc in P.FOURCCS:                                 # ... or with the chroma of every second pixel of every second row
+        return P.pack_planes(yc[..., 0], yc[0::2, 0::2, 1], yc[0::2, 0::2, 2], fourcc, W)
     buf = np.empty((H, 2 * W), np.uint8)
     buf[:, 0::2], buf[:, 1::4], buf[:, 3::4] = yc[..., 0], yc[:, 0::2, 1], yc[:, 0::2, 2]
     return buf
@@ -53,20 +58,26 @@ def median_ms(call, iters):
     return float(np.median(t)), float(np.min(t))
 
 
-def host_path(dev, n, fourcc, stride, iters, threads=16):
+def triples(f, fourcc, stride, o, pw, ph):
+    """The restatement's preview triples of one raw frame."""
+    if fourcc in P.FOURCCS:
+        return P.preview(P.triples_vec(f, fourcc, W, H, stride, o), pw, ph)
+    return PC.triples_vec(f, fourcc, W, H, stride, o, pw, ph)
+
+
+def host_path(dev, n, fourcc, stride, iters, o, pw, ph, threads=16):
     """(median ms, files): D2H of the raw frames + conversion and nearest-neighbour scale in numpy + Pillow on `threads` threads."""
     from PIL import Image
 
     def enc(f):
         buf = io.BytesIO()
-        P = PC.triples_vec(f, fourcc, W, H, stride, "none", PW, PH)
-        Image.fromarray(P, "YCbCr").save(buf, "JPEG", quality=Q, subsampling=0, optimize=False)
+        Image.fromarray(triples(f, fourcc, stride, o, pw, ph), "YCbCr").save(buf, "JPEG", quality=Q, subsampling=0, optimize=False)
         return buf.getvalue()
     t = []
     with ThreadPoolExecutor(threads) as ex:
         for it in range(iters + 1):
             t0 = time.perf_counter()
-            frames = dev.cpu().numpy().reshape(n, H, stride)
+            frames = dev.cpu().numpy().reshape(n, -1, stride)
             files = list(ex.map(enc, frames))
             if it:
                 t.append((time.perf_counter() - t0) * 1e3)
@@ -78,18 +89,27 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--frames", type=int, default=256)
     ap.add_argument("--only", default=None)
+    ap.add_argument("--fourcc", default=None)
+    ap.add_argument("--planes", action="store_true")
+    ap.add_argument("--orientation", default="none")
+    ap.add_argument("--no-host", action="store_true")
     args = ap.parse_args()
+    if args.planes != (args.fourcc in P.FOURCCS):
+        raise SystemExit("--planes goes with --fourcc NV12 / NV21 / I420 / YV12, and they with it")
+    o = args.orientation
+    ow, oh = (H, W) if o in ("clockwise", "counterclockwise") else (W, H)
+    pw, ph = (PH, PW) if (ow, oh) != (W, H) else (PW, PH)
     n = args.frames
     uniq = scenes.bench_stream(1, 4, W, H, 12, unique=4)[0]
-    det = AprilTagDetector(W, H, max_batch=n)
-    kw = dict(width=PW, height=PH, quality=Q)
-    for fourcc in ("YUYV", "RGB3"):
+    det = AprilTagDetector(ow, oh, max_batch=n)
+    kw = dict(width=pw, height=ph, quality=Q)
+    for fourcc in (args.fourcc,) if args.fourcc else ("YUYV", "RGB3"):
         if args.only and fourcc != args.only:
             continue
         src = [camera_frame(f, fourcc) for f in uniq]
         stride = src[0].shape[1]
         raw = [src[i % len(src)] for i in range(n)]
-        det.upload_raw(raw, fourcc)
+        det.upload_raw(raw, fourcc, o, planes=args.planes)
         for _ in range(3):
             files = det.preview_jpeg_color(n=n, **kw)
             det.preview_jpeg_color(n=1, **kw)
@@ -99,11 +119,17 @@ def main():
         grey, _ = median_ms(lambda: det.preview_jpeg(n=n, **kw), args.iters)
         grey1, _ = median_ms(lambda: det.preview_jpeg(n=1, **kw), args.iters)
         files = det.preview_jpeg_color(n=n, **kw)
-        exact = all(files[i] == EC.encode_ycc(PC.triples_vec(raw[i], fourcc, W, H, stride, "none", PW, PH), Q, 0) for i in range(len(src)))
+        exact = all(files[i] == EC.encode_ycc(triples(raw[i], fourcc, stride, o, pw, ph), Q, 0) for i in range(len(src)))
+        if args.no_host:
+            print(json.dumps({"format": fourcc, "planes": args.planes, "orientation": o, "frames": n, "preview": [pw, ph], "quality": Q,
+                              "files_MB": round(sum(len(b) for b in files) / 1e6, 2), "preview_jpeg_color_ms": round(m, 3),
+                              "preview_jpeg_color_min_ms": round(mn, 3), "frames_per_s": round(n / m * 1e3, 1), "latency_n1_ms": round(lat, 3),
+                              "grey_preview_jpeg_ms": round(grey, 3), "color_over_grey": round(m / grey, 2), "byte_exact": exact}), flush=True)
+            continue
         dev = torch.from_numpy(np.stack(raw)).cuda()          # the raw frames as a caller holds them on the device
         torch.cuda.synchronize()
-        host = host_path(dev, n, fourcc, stride, max(3, args.iters // 4))
-        print(json.dumps({"format": fourcc, "frames": n, "preview": [PW, PH], "quality": Q, "files_MB": round(sum(len(b) for b in files) / 1e6, 2),
+        host = host_path(dev, n, fourcc, stride, max(3, args.iters // 4), o, pw, ph)
+        print(json.dumps({"format": fourcc, "planes": args.planes, "orientation": o, "frames": n, "preview": [pw, ph], "quality": Q, "files_MB": round(sum(len(b) for b in files) / 1e6, 2),
                           "preview_jpeg_color_ms": round(m, 3), "preview_jpeg_color_min_ms": round(mn, 3), "frames_per_s": round(n / m * 1e3, 1),
                           "latency_n1_ms": round(lat, 3), "grey_preview_jpeg_ms": round(grey, 3), "grey_latency_n1_ms": round(grey1, 3),
                           "color_over_grey": round(m / grey, 2), "host_d2h_numpy_pillow_16_threads_ms": round(host[0], 3),
